@@ -14,10 +14,16 @@ the last one is waited for inside the timed region.
 
 Protocol = the reference's scripts/benchmark.py:15-26: bytes = sum of UTF-8 lengths, warm-up first,
 wall clock around the timed calls (here: barrier + synchronize on both sides, max over ranks).
-Rank 0 prints ONE JSON line; `roofline` is for the dominant kernel (HIP-event durations measured
-here, on the stream the kernels run on), `cpu_baseline` is the C oracle timed on the host cores
-over a bounded sample of the same corpus; the WHOLE GPU result (every document, every token of the
-1 GiB) is compared with the oracle.
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: corpus, encoder,
+warm-up, the K timed steps, the outputs (--dump-outputs DIR), the line.  Everything else runs with
+--full: `roofline` for the dominant kernel (HIP-event durations measured here, on the stream the
+kernels run on), `cpu_baseline` (the C oracle timed on the host cores over a bounded sample of the
+same corpus), the comparison of the WHOLE GPU result (every document, every token of the 1 GiB) with
+the oracle, the host-boundary rates, the cold start, the generic engine and the other configurations.
+
+--dump-outputs DIR writes what the last timed step handed its caller (rank 0's shard when N > 1):
+DIR/token_offsets.npy (float64) and DIR/token_ids_sample.npy (float32, the ids of a fixed, seeded
+sample of the documents), at most 64 MB in all.  The corpus depends on --mib and the seed only.
 """
 from __future__ import annotations
 
@@ -154,6 +160,35 @@ class DevArray:
         self.__cuda_array_interface__ = {"shape": (n,), "typestr": typestr, "data": (ptr, False), "version": 2}
 
 
+DUMP_BUDGET = 60_000_000  # bytes of array data --dump-outputs may write in all (the .npy headers stay well inside 64 MB)
+
+
+def dump_outputs(out_dir, dt, nt, do, n_docs, torch, device="cuda"):
+    """--dump-outputs: the result of the last timed step as float arrays that two builds can be compared on, value for value.
+    token_offsets.npy: the token-id offset of every document (float64, exact), or a seeded sample of them if they alone would take more
+    than a quarter of the budget; token_ids_sample.npy: the ids of a seeded sample of 1/32 of the documents, concatenated in document
+    order until the rest of the budget is spent (float32, exact: ids < 2**24).  Read through the library's device buffers, valid until
+    the call after the next."""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(0x5EED0D)
+    tok_off = torch.as_tensor(DevArray(do, n_docs + 1, "<i8"), device=device).cpu().numpy()
+    if int(tok_off[0]) != 0 or int(tok_off[-1]) != nt or np.any(np.diff(tok_off) < 0):
+        raise RuntimeError(f"bench: the token offsets of the last step are not monotone up to its {nt} tokens")
+    keep = np.arange(n_docs + 1) if (n_docs + 1) * 8 <= DUMP_BUDGET // 4 else np.sort(rng.choice(n_docs + 1, DUMP_BUDGET // 32, replace=False))
+    offs = tok_off[keep].astype(np.float64)
+    docs = np.sort(rng.choice(n_docs, size=max(1, n_docs // 32), replace=False))
+    lens = tok_off[docs + 1] - tok_off[docs]
+    room = (DUMP_BUDGET - offs.nbytes) // 4
+    docs, lens = docs[np.cumsum(lens) <= room], lens[np.cumsum(lens) <= room]
+    idx = np.repeat(tok_off[docs] - (np.cumsum(lens) - lens), lens) + np.arange(int(lens.sum()), dtype=np.int64)
+    ids = np.zeros(0, np.float32)
+    if len(idx):  # (every index below nt: checked above through the offsets)
+        toks = torch.as_tensor(DevArray(dt, max(nt, 1), "<i4"), device=device)[:nt]
+        ids = toks[torch.from_numpy(idx).to(toks.device)].cpu().numpy().view(np.uint32).astype(np.float32)
+    np.save(os.path.join(out_dir, "token_offsets.npy"), offs)
+    np.save(os.path.join(out_dir, "token_ids_sample.npy"), ids)
+
+
 def one_process(args, torch):
     """bench.py --gpus N --one-process: the product's own several-GPU path.  N document shards of --mib MiB each, host text in (the group's
     contract), every shard encoded on its device, ids gathered on the first device; value = PCIe-inclusive aggregate rate."""
@@ -181,9 +216,11 @@ def one_process(args, torch):
     for _ in range(args.steps):
         dt, nt, do = core.encode_batch_gathered(blob, doc_off)
     el = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dt, nt, do, len(doc_off) - 1, torch, device=f"cuda:{devices[0]}")
     # what device 0 holds after the gather against the oracle's encoding of the undivided batch (outside the timed region)
     parity = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import c_oracle
 
         pat_id = {"gpt2_shaped": 0, "cl100k_shaped": 1, "o200k_shaped": 2, "o200k_custom8": 2}[args.encoding]
@@ -213,7 +250,7 @@ def generic_engine_figure(encoding: str, mib: int = 256):
     this run does not depend on it."""
     import subprocess
 
-    cmd = [sys.executable, os.path.abspath(__file__), "--generic-engine", "--mib", str(mib), "--steps", "3", "--warmup", "1", "--no-host-path", "--no-hf",
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--generic-engine", "--mib", str(mib), "--steps", "3", "--warmup", "1", "--no-host-path", "--no-hf",
            "--cpu-sample-mib", "16", "--encoding", encoding]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     try:
@@ -223,7 +260,7 @@ def generic_engine_figure(encoding: str, mib: int = 256):
         k = (j.get("roofline") or {}).get("kernels_ms_avg") or {}
         return {"gbps": j["value"], "ms_per_step": j["ms_per_step"], "mib": mib, "all_tokens_equal_to_the_oracle": j.get("parity_all_tokens_vs_oracle"),
                 "kernels_ms_avg": {n: v for n, v in k.items() if "rx_" in n},
-                "what": f"bench.py --generic-engine --mib {mib} --steps 3 --warmup 1 in a process of its own: the encoding's pat_str forced through the generic "
+                "what": f"bench.py --full --generic-engine --mib {mib} --steps 3 --warmup 1 in a process of its own: the encoding's pat_str forced through the generic "
                         "regex engine (its DFA form) instead of the hand-written scanners, inputs resident in HBM, every token compared with the oracle"}
     except Exception as e:  # (time-out, no line, ...)
         return {"error": f"{type(e).__name__}: {str(e)[:200]}"}
@@ -264,6 +301,10 @@ def main():
     ap.add_argument("--one-process", action="store_true",
                     help="NOT the driver's mode: drive the product's several-GPU entry (CoreBPE(devices=...), tk_group_encode_batch_device: host text in, "
                          "ids gathered on device 0 over xGMI) from this one process; a device is named several times when the box has fewer GPUs")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline, parity of the whole result, CPU baseline, host path, cold start, generic engine, other configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result of the last timed step as DIR/*.npy (float32 / float64, at most 64 MB)")
     ap.add_argument("--csrc-digest", action="store_true", help="print the digest of the kernel sources (what profiles/traffic.json is tied to) and exit")
     ap.add_argument("--generic-engine", action="store_true",
                     help="NOT the headline: run the encoding's pat_str on the generic regex engine instead of the hand-written scanners")
@@ -404,6 +445,8 @@ def main():
     if dist:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # (before any further call writes the result buffers again)
+        dump_outputs(args.dump_outputs, dt, nt, do, n_docs, torch)
     if dist:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -419,7 +462,7 @@ def main():
     # N > 1: the result of the last TIMED step -- this rank's ids and offsets, and on rank 0 what the gather delivered -- goes to host
     # memory now, before further steps write the (alternating) result buffers again; compared further down, outside every timed region
     own_result, gather_check = None, None
-    if dist and not args.no_cpu_baseline:
+    if dist and args.full and not args.no_cpu_baseline:
         from tiktoken_amd.distributed import exchange_verdicts, ids_digest, verify_gathered
 
         own_result = (torch.as_tensor(DevArray(dt, max(nt, 1), "<i4"), device="cuda")[: nt].cpu().numpy().view(np.uint32),
@@ -427,7 +470,7 @@ def main():
         if rank == 0 and last_gather[0] is not None and last_gather[0][0] is not None:
             gather_check = [ids_digest(p.cpu().numpy()) for p in last_gather[0][0]]  # (count, digest) of what was RECEIVED, per rank
         last_gather[0] = None
-    if dist:  # the same K steps without the gather: what the encoders do when nobody collects the ids on one rank
+    if dist and args.full:  # the same K steps without the gather: what the encoders do when nobody collects the ids on one rank
         torch.cuda.synchronize()
         dist.barrier()
         t0 = time.perf_counter()
@@ -439,18 +482,19 @@ def main():
         dist.all_reduce(el2, op=dist.ReduceOp.MAX)
         value_encode_only = round(total_bytes * args.steps / float(el2.item()) / 1e9, 3)
 
-    # ---- per-kernel durations (HIP events on the library's stream), one profiled pass
-    core.set_profiling(True)
-    core.reset_kernel_ms()
-    prof_steps = 2
-    for _ in range(prof_steps):
-        core.encode_batch_device(d_text.data_ptr(), nbytes, d_off.data_ptr(), doc_off, n_docs)
-    core.set_profiling(False)
+    # ---- per-kernel durations (HIP events on the library's stream), one profiled pass (--full)
     kern = {}
-    for k in KERNELS:
-        ms, n = core.kernel_ms(k)
-        if n:
-            kern[k] = {"ms_total": ms, "launches": n, "ms_avg": ms / n}
+    prof_steps = 2
+    if args.full:
+        core.set_profiling(True)
+        core.reset_kernel_ms()
+        for _ in range(prof_steps):
+            core.encode_batch_device(d_text.data_ptr(), nbytes, d_off.data_ptr(), doc_off, n_docs)
+        core.set_profiling(False)
+        for k in KERNELS:
+            ms, n = core.kernel_ms(k)
+            if n:
+                kern[k] = {"ms_total": ms, "launches": n, "ms_avg": ms / n}
     stats = core.last_stats()
     b_alg = nbytes + 4 * stats["tokens"] + 16 * (n_docs + 1)  # text in + u32 ids out + offsets in/out
     dom = max(kern, key=lambda k: kern[k]["ms_total"]) if kern else None
@@ -483,7 +527,7 @@ def main():
                     "pipeline_achieved_over_summed_kernel_time": round(b_alg / (sum_ms * 1e-3) / 1e9, 2),  # (kernels overlap on side streams: a lower bound)
                     "kernels_ms_avg": {k: round(v["ms_avg"], 4) for k, v in kern.items()}}
 
-    # ---- parity of the WHOLE result + CPU baseline (rank 0, N = 1 only)
+    # ---- parity of the WHOLE result + CPU baseline (rank 0, N = 1 only; --full)
     cpu = None
     parity = None
     gather_verified = None
@@ -519,7 +563,7 @@ def main():
                 gather_verified = False
         del ctoks, coff, g_toks, g_tok_off
         own_result = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import c_oracle
 
         pat_id = {"gpt2_shaped": 0, "cl100k_shaped": 1, "o200k_shaped": 2, "o200k_custom8": 2}[args.encoding]
@@ -571,7 +615,7 @@ def main():
     # ---- host-boundary rates (rank 0, N = 1; never `value`): T2 = tk_encode_batch, host buffers in, host token ids out (pinned staging,
     # PCIe both ways inside the call); T3 = Encoding.encode_ordinary_batch on a bounded sample, Python list[str] -> list[list[int]]
     host_path = None
-    if rank == 0 and world == 1 and not args.no_host_path:
+    if rank == 0 and world == 1 and args.full and not args.no_host_path:
         host_path = {}
         hb = blob[:nbytes]
         core.encode_batch_packed(hb, doc_off)
@@ -653,7 +697,7 @@ def main():
         del lists, docs, enc
 
     cold = None
-    if rank == 0 and world == 1 and not args.no_host_path:
+    if rank == 0 and world == 1 and args.full and not args.no_host_path:
         # from a vocabulary FILE to an Encoding that can encode -- what get_encoding() costs after the library and the device
         # are up (file read + gunzip, native .tiktoken parser, table build on the host threads, upload); best of three
         from tiktoken_ext import amd_shaped
@@ -677,7 +721,7 @@ def main():
 
     generic = None
     configs = None
-    if rank == 0 and world == 1 and not args.no_host_path and not args.generic_engine:
+    if rank == 0 and world == 1 and args.full and not args.no_host_path and not args.generic_engine:
         generic = generic_engine_figure(args.encoding)
         configs = other_configs_figure()
 
@@ -687,7 +731,7 @@ def main():
             "value": round(value, 3), "unit": "GB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "value_encode_only": value_encode_only,
-            "dtype": "u8", "data": "synthetic",
+            "dtype": "u8", "data": "synthetic", "full": args.full,
             "config": {"workload": f"{args.encoding} encode_ordinary_batch, {args.mib} MiB synthetic web-text per GPU "
                                    f"(tkc_generate mix=1, seed {'0x5EED0003' if world == 1 else '0x5EED0004+rank'}), "
                                    f"{n_docs} docs on rank 0, inputs resident in HBM, packed u32 output",

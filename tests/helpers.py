@@ -54,6 +54,61 @@ def golden_vocab(name: str) -> dict[bytes, int]:
     return g["mergeable_ranks"] if g.get("mergeable_ranks") else load_vocab(g["vocab"])
 
 
+def data_gym_files(dirpath) -> dict:
+    """A synthetic GPT-2-style vocabulary (256 bytes + 644 merges, seeded) written as data-gym files into `dirpath`: vocab.bpe + encoder.json
+    and a second pair in which one merge is listed twice.  The same files every time: tests/golden/reference_load.json holds what the
+    reference's load.py made of them (tools/gen_golden_load.py)."""
+    import random
+
+    from tiktoken_amd import vocab_io
+
+    rng = random.Random(7)
+    order = vocab_io.data_gym_byte_order()
+    to_char = {b: chr(b) for b in order[:188]}
+    to_char.update({b: chr(256 + i) for i, b in enumerate(order[188:])})
+
+    def gym(tok: bytes) -> str:
+        return "".join(to_char[b] for b in tok)
+
+    toks = [bytes([b]) for b in order]
+    ranks = {t: i for i, t in enumerate(toks)}
+    lines = ["#version: 0.2"]
+    while len(ranks) < 900:
+        a, b = rng.choice(toks), rng.choice(toks)
+        if a + b in ranks or len(a + b) > 12:
+            continue
+        ranks[a + b] = len(ranks)
+        toks.append(a + b)
+        lines.append(gym(a) + " " + gym(b))
+    bpe, enc = os.path.join(dirpath, "vocab.bpe"), os.path.join(dirpath, "encoder.json")
+    with open(bpe, "w", encoding="utf-8") as f:
+        f.write("\n".join(lines) + "\n")
+    table = {gym(t): r for t, r in ranks.items()}
+    table["<|endoftext|>"] = len(ranks)
+    with open(enc, "w", encoding="utf-8") as f:
+        f.write(json.dumps(table))
+    # a merge listed twice takes a number both times (the later ones move up by one): encoder.json numbered that way is accepted, as in the reference
+    dup = lines[:400] + [lines[300]] + lines[400:]
+    bpe2, enc2 = os.path.join(dirpath, "vocab2.bpe"), os.path.join(dirpath, "encoder2.json")
+    with open(bpe2, "w", encoding="utf-8") as f:
+        f.write("\n".join(dup) + "\n")
+    first, second = lines[300].split()
+    back = {v: k for k, v in to_char.items()}
+    dup_tok = bytes(back[c] for c in first) + bytes(back[c] for c in second)
+    ranks2 = {t: (r if r < 256 + 399 else r + 1) for t, r in ranks.items()}
+    ranks2[dup_tok] = 256 + 399
+    with open(enc2, "w", encoding="utf-8") as f:
+        f.write(json.dumps({gym(t): r for t, r in ranks2.items()}))
+    return {"bpe": bpe, "enc": enc, "bpe2": bpe2, "enc2": enc2, "ranks": ranks, "ranks2": ranks2}
+
+
+def ranks_digest(ranks: dict[bytes, int]) -> str:
+    """sha256 of a rank table in the .tiktoken line form (base64 token, space, rank; by rank)."""
+    import hashlib
+
+    return hashlib.sha256(b"".join(base64.b64encode(t) + b" %d\n" % r for t, r in sorted(ranks.items(), key=lambda kv: kv[1]))).hexdigest()
+
+
 @functools.lru_cache(maxsize=None)
 def c_oracle_for(name: str) -> c_oracle.COracle:
     g = load_golden(name) if os.path.exists(os.path.join(ROOT, "tests", "golden", name + ".json.gz")) else None

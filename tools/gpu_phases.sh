@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 VARS=${VARIANTS:-0 0x1000 0x2000 0x4000 0x8000 0x10000 2 8}
 for V in $VARS; do
   D=$((V))
-  TIKTOKEN_AMD_DEBUG=$D timeout 90 python $R/bench.py --gpus 1 --steps 2 --warmup 1 --mib 1024 --no-cpu-baseline --no-host-path > $O/bench_$V.json 2> $O/bench_$V.err || { echo "variant $V failed: $(tail -2 $O/bench_$V.err)"; break; }
+  TIKTOKEN_AMD_DEBUG=$D timeout 90 python $R/bench.py --full --gpus 1 --steps 2 --warmup 1 --mib 1024 --no-cpu-baseline --no-host-path > $O/bench_$V.json 2> $O/bench_$V.err || { echo "variant $V failed: $(tail -2 $O/bench_$V.err)"; break; }
 done
 for V in ${PMC_VARIANTS:-$VARS}; do
   D=$((V))
