@@ -428,7 +428,7 @@ def test_ten_megabytes_without_a_certain_start_take_the_generic_way():
 
 
 def test_sparse_non_ascii_chars_by_dense_lanes(cores):
-    """Round 6, tk_fused.h phase B (TKF_DENSE_DECODE): a wavefront whose 1024 bytes hold few non-ASCII chars lists their lead bytes and decodes them by
+    """Round 6, tk_fused.h phase B (the dense-lane decode): a wavefront whose 1024 bytes hold few non-ASCII chars lists their lead bytes and decodes them by
     dense lanes -- the class goes into the class planes by LDS atomics at the char's position, whichever lane holds its bytes -- while a wavefront with more
     than TKF_DENSE_MAX of them keeps the loop per lane.  Chars of two, three and four bytes (letters with and without case, digits, marks, white space,
     punctuation, astral letters and emoji) at EVERY offset against the lanes' sixteen bytes, the wavefronts' 1024 and the planes' 32-bit words, sparse
@@ -459,7 +459,7 @@ def test_sparse_non_ascii_chars_by_dense_lanes(cores):
 
 def test_letter_runs_around_tile_ends(cores):
     """Round 6, tk_fused.h: a tile whose left context holds no certain start begins its scan at a position where the matcher's state is known (a letter
-    behind a letter, TKF_SYNC_POINTS), and a letter run that leaves a tile's window is read on to its end (TKF_EXTEND) -- unless what ends the run lets
+    behind a letter: a sync point), and a letter run that leaves a tile's window is read on to its end -- unless what ends the run lets
     the piece go on (o200k: a cased letter, an apostrophe), more than 2 KiB follow, or the run is not of the kind the rule is about: then the tile goes to
     the workgroup-wide scanner as before.  Runs of every such kind and ending, at every offset against the tiles' ends (3840 bytes), documents and special
     tokens inside them; every token compared with the oracle."""
@@ -551,7 +551,7 @@ def test_ordinary_text_through_the_give_up_path(monkeypatch, name):
         toks, toff = core.encode_batch_packed(blob, off, allowed)
         rt, ro = C.encode_batch(blob, off, None if allowed is None else set(g["special_tokens"]), 8)
         assert np.array_equal(toff, ro) and np.array_equal(toks, rt), allowed
-    # (cl100k: since round 6 a tile of this text never walks -- a letter behind a letter is a position the scan can start from, tk_fused.h TKF_SYNC_POINTS,
+    # (cl100k: since round 6 a tile of this text never walks -- a letter behind a letter is a position the scan can start from, tk_fused.h phase D,
     # and every other class pair of "x'll" / "q're" is a certain start under that pattern: the text is encoded under the zero budget without the way out)
     assert core.stat("fallbacks") >= (0 if name == "cl100k_shaped" else 2)
 

@@ -496,7 +496,7 @@ extern "C" int tk_create(const uint8_t* ranks_blob, const uint64_t* ranks_off, c
     memcpy(D.cert, H.cert, sizeof D.cert);
     // a document of a few KiB is cut at "letter, then space" when that is a certain piece start of the pattern (encode_mid): both cases of letter,
     // in the family's table and in what was derived for this pattern
-    c->mid_cut = tk_mid_cut_certain(H.cert) && !(c->dbg & 0x4000000);  // (debug bit 0x4000000: never)
+    c->mid_cut = tk_mid_cut_certain(H.cert) && !(c->dbg & TK_DBG_NO_MID_CUT);
     for (size_t k = 0; k + 1 < H.spec_off.size(); ++k) c->spec_max_len = std::max(c->spec_max_len, H.spec_off[k + 1] - H.spec_off[k]);
     {  // decode table: id -> {offset into the token / special blob, length}
         uint32_t max_id = 0;
@@ -537,7 +537,7 @@ extern "C" int tk_create(const uint8_t* ranks_blob, const uint64_t* ranks_off, c
         }
     }
     {
-        // tk_k_front reads some of its arguments from the kernarg segment again, at offsets taken from TkFrontArgs (tk_fused.h, TKF_PARK_ARGS): one launch
+        // tk_k_front reads some of its arguments from the kernarg segment again, at offsets taken from TkFrontArgs (tk_fused.h, phases E and F): one launch
         // of a kernel with the same parameter list and arguments of distinct values checks that the compiler lays the segment out that way
         TkTables Tt{};
         uint64_t v = 0x1000;
@@ -696,7 +696,7 @@ static int rx_split(tk_core* c, WorkSet& w, hipStream_t s, const uint8_t* d_text
                                    ahead, spec, spec + nwords + 2, xexit);
             });
     }));
-    const bool links = !(c->dbg & 0x20000);  // (debug bit 0x20000: no link pass -- the resolving pass matches its way from one chain to the next)
+    const bool links = !(c->dbg & TK_DBG_NO_LINKS);  // (without: the resolving pass matches its way from one chain to the next)
     if (links) {
         TRY(timed(c, s, "tk_k_rx_link", [&] {
             by_form([&](auto form) {
@@ -708,7 +708,7 @@ static int rx_split(tk_core* c, WorkSet& w, hipStream_t s, const uint8_t* d_text
     const TkRxMaps maps{spec, spec + nwords + 2, xexit, links ? lnk : (const uint32_t*)nullptr, lnk + nwords + 2, lmerge, lexit, seg_shift};
     TRY(timed(c, s, "tk_k_rx_resolve", [&] {
         by_form([&](auto form) {
-            if (c->dbg & 0x40000)  // (debug bit 0x40000: one lane per document instead of one wavefront)
+            if (c->dbg & TK_DBG_RX_LANE)  // (one lane per document instead of one wavefront)
                 hipLaunchKernelGGL(tk_k_rx_resolve<decltype(form)::value>, dim3(grid_for(n_docs, 256, 65536)), dim3(256), lds, s, c->rx, d_text, (uint32_t)n, brk, ss, si,
                                    d_doc_off, n_docs, base, maps, gst, gst + nwords + 2, counters);
             else
@@ -740,7 +740,7 @@ static int stage_deferred(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s) 
     // segment's guess is taken -- splits the chunk under the same pat_str, its piece starts become hard starts, and the tiles that gave up
     // run again: every piece start is certain now.  (Pieces that are already final are what they were: a hard start at the start of a
     // piece changes nothing, and the stock patterns match a piece the same way when the text ends behind it.)
-    const bool can_fall_back = c->has_rx_fb && job.n >= (256u << 10) && !(c->dbg & 0x400000);  // (debug bit 0x400000: never)
+    const bool can_fall_back = c->has_rx_fb && job.n >= (256u << 10) && !(c->dbg & TK_DBG_NO_FALL_BACK);
     if (job.n > 0 && !job.single_piece) {
         TkFrontOut fo{w.starts.as<uint32_t>(), w.tile_np.as<uint32_t>(), w.res.as<uint32_t>(), w.tile_sum.as<uint8_t>(), miss_of(w, job), job.ovf_cap,
                       w.listC.as<uint32_t>(), w.counters.as<uint32_t>()};
@@ -755,16 +755,16 @@ static int stage_deferred(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s) 
         if (job.optimistic && defer_guess < slow_wgs) slow_wgs = defer_guess;
         const dim3 grid((uint32_t)(job.ntiles < slow_wgs ? job.ntiles : slow_wgs));
         const int pat_id = T.pat.generic() ? TK_PAT_GENERIC : T.pattern;
-        TkMissKey* mt_arg = (c->dbg & 256) ? (TkMissKey*)nullptr : job.mt;
+        TkMissKey* mt_arg = (c->dbg & TK_DBG_NO_MT) ? (TkMissKey*)nullptr : job.mt;
         const uint32_t* gapb = c->has_rx ? w.rx_gst.as<uint32_t>() + (job.n + 31) / 32 + 2 : (const uint32_t*)nullptr;
-        int fdbg = c->dbg | (job.pretok ? 8 : 0);  // (piece starts only: every probe counts as a hit, nothing is listed for the merges)
+        const int fdbg = (c->dbg & ~TK_DBG_INTERNAL) | (job.pretok ? TK_DBG_STARTS_ONLY : 0);  // (the piece-offsets entry: piece starts only)
         // The deferred tiles in two kernels: the deferred-tile instance finds a tile's piece starts (the workgroup-wide scanner: 128 registers,
         // four workgroups per CU), the one-tile-per-workgroup instance does the rest from the starts it is given (phases E and F, at eight
         // workgroups per CU).  Its grid is the list's length where the host reads the counters (inputs of 256 KiB and more); otherwise one
         // workgroup per tile of the chunk, of which all but the list's length return at once.
         TRY(timed(c, s, "tk_k_front_slow", [&] {
             launch_front<TKF_MODE_STARTS>(pat_id, job.spec, grid, s, T, job.d_text, job.n, job.base, w.brk.as<uint32_t>(), docb, ss, si, fo, mt_arg, (1u << job.mt_bits) - 1u,
-                               w.deferred.as<uint32_t>(), gapb, (fdbg & ~TKF_DBG_SECOND) | (can_fall_back ? TKF_DBG_MAY_GIVE_UP : 0));
+                               w.deferred.as<uint32_t>(), gapb, fdbg | (can_fall_back ? TK_DBG_MAY_GIVE_UP : 0));
         }));
         uint64_t n_given = job.ntiles;
         // (round 6) The host does not wait for the counters here any more: the wait cost every chunk ~25 us of an idle device between the two kernels
@@ -786,16 +786,16 @@ static int stage_deferred(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s) 
                 TRY(rx_split(c, w, s, job.d_text, job.n, w.brk.as<uint32_t>(), ss, si, job.d_doc_off, job.n_docs, job.base));
                 TRY(timed(c, s, "tk_k_front_slow", [&] {
                     launch_front<TKF_MODE_STARTS>(pat_id, job.spec, grid, s, T, job.d_text, job.n, job.base, w.brk.as<uint32_t>(), docb, ss, si, fo, mt_arg, (1u << job.mt_bits) - 1u,
-                                       w.deferred.as<uint32_t>() + job.ntiles + 2, gapb, (fdbg & ~TKF_DBG_MAY_GIVE_UP) | TKF_DBG_SECOND);
+                                       w.deferred.as<uint32_t>() + job.ntiles + 2, gapb, fdbg | TK_DBG_SECOND);
                 }));
                 c->st_fallbacks += 1;
             }
             n_given = w.h_counters[TK_CNT_DEFER];
         }
-        if (n_given && !(c->dbg & 0x1F000)) {  // (debug bits 0x1000 .. 0x10000: the kernels stop after a phase, there are no starts to go on from)
+        if (n_given && !(c->dbg & TK_DBG_STOPS)) {  // (the kernels stop after a phase: there are no starts to go on from)
             TRY(timed(c, s, "tk_k_front_given", [&] {
                 launch_front<TKF_MODE_GIVEN>(pat_id, job.spec, dim3((uint32_t)n_given), s, T, job.d_text, job.n, job.base, w.brk.as<uint32_t>(), docb, ss, si, fo, mt_arg,
-                                    (1u << job.mt_bits) - 1u, w.deferred.as<uint32_t>(), gapb, fdbg & ~(TKF_DBG_SECOND | TKF_DBG_MAY_GIVE_UP));
+                                    (1u << job.mt_bits) - 1u, w.deferred.as<uint32_t>(), gapb, fdbg);
             }));
         }
     }
@@ -930,12 +930,12 @@ static int stage_front(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, con
         if (c->has_rx) TRY(rx_split(c, w, s, d_text, n, brk, ss, si, d_doc_off, n_docs, base));  // the generic engine finds the piece starts; they join the hard starts in `brk`
         TRY(ensure(w.deferred, 2 * (ntiles + 2) * 4));  // (behind the list of deferred tiles: those that gave up their walk, stage_deferred)
         uint32_t* deferred = w.deferred.as<uint32_t>();
-        TkMissKey* mt_arg = (c->dbg & 256) ? (TkMissKey*)nullptr : job.mt;
+        TkMissKey* mt_arg = (c->dbg & TK_DBG_NO_MT) ? (TkMissKey*)nullptr : job.mt;
         TRY(timed(c, s, "tk_k_front", [&] {
             const dim3 grid((uint32_t)ntiles);
             launch_front<TKF_MODE_TILE>(T.pat.generic() ? TK_PAT_GENERIC : T.pattern, ss != nullptr, grid, s, T, d_text, n, base, brk, docb, ss, si, fo,
                                 mt_arg, (1u << job.mt_bits) - 1u, deferred, c->has_rx ? w.rx_gst.as<uint32_t>() + nwords + 2 : (const uint32_t*)nullptr,
-                                c->dbg | (pretok_only ? 8 : 0) | ((c->has_rx && !(c->dbg & 4)) ? TKF_DBG_HARD_ONLY : 0));  // (debug bit 4: the scanners run even so)
+                                (c->dbg & ~TK_DBG_INTERNAL) | (pretok_only ? TK_DBG_STARTS_ONLY : 0) | ((c->has_rx && !(c->dbg & TK_DBG_SCANNERS)) ? TK_DBG_HARD_ONLY : 0));
         }));
     } else if (n > 0) {
         hipLaunchKernelGGL(tk_k_chunk_clear, dim3(1), dim3(256), 0, s, clr);
@@ -986,9 +986,9 @@ static int stage_back(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, uint
     const unsigned long long* tok_base = c->tok_bases.as<unsigned long long>() + job.index;
     uint64_t nC = 0;
     TRY(stage_deferred(c, w, job, s));
-    // (perf experiments, tools/gpu_phases.sh: debug bits 0x1000 .. 0x10000 stop the front kernel after one of its phases -- its outputs are
+    // (perf experiments, tools/gpu_phases.sh: TK_DBG_STOPS -- the front kernel stops after one of its phases -- its outputs are
     // incomplete, so nothing behind it runs: the call returns zero tokens and offsets that mean nothing)
-    const bool front_only = (c->dbg & 0x1F000) != 0;
+    const bool front_only = (c->dbg & TK_DBG_STOPS) != 0;
     if (front_only) {
         HIPCHK(hipMemsetAsync(w.total.p, 0, 32, s));
         if (prev_tot) HIPCHK(hipStreamWaitEvent(s, prev_tot, 0));
@@ -1007,14 +1007,14 @@ static int stage_back(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, uint
         const uint64_t n_entries = (uint64_t)job.ovf_base + job.ovf_cap;
         const uint32_t dd_blocks = grid_for(n_entries, 4 * 256, TKD_WAVES / 4);
         TRY(timed(c, s, "tk_k_bincount", [&] {
-            hipLaunchKernelGGL(tk_k_bincount, dim3(dd_blocks), dim3(256), 0, s, T, d_text, data, job.mt, job.ovf_cap, counters, wbin, (c->dbg & 512) ? 0 : 1);
+            hipLaunchKernelGGL(tk_k_bincount, dim3(dd_blocks), dim3(256), 0, s, T, d_text, data, job.mt, job.ovf_cap, counters, wbin, (c->dbg & TK_DBG_COLLIDE) ? 0 : 1);
         }));
         TRY(scan_u32(c, w, s, wbin, (uint64_t)TK_NBIN * dd_blocks * 4 + 1, w.total.as<uint64_t>()));
         TRY(timed(c, s, "tk_k_binfill", [&] {
             hipLaunchKernelGGL(tk_k_binfill, dim3(dd_blocks), dim3(256), 0, s, T, d_text, data, job.mt, job.ovf_cap, wbin, listB, counters);
         }));
-        if (T.pair8 && !(c->dbg & 0x800000)) {
-            // every bin in one launch (tk_k_merge_all); debug bit 0x800000: the kernel-per-bin form below
+        if (T.pair8 && !(c->dbg & TK_DBG_MERGE_PER_BIN)) {
+            // every bin in one launch (tk_k_merge_all); TK_DBG_MERGE_PER_BIN: the kernel-per-bin form below
             uint64_t most_units = 0;
             for (int b = 0; b < TK_NBIN; ++b)
                 if (n >= tk_bin_lo(b)) most_units += std::min<uint64_t>(n / tk_bin_lo(b), n_entries) / (64u >> (b == 0 ? 0 : (b <= 2 ? 1 : (b <= 4 ? 2 : b - 2)))) + 1;
@@ -1081,7 +1081,7 @@ static int stage_back(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, uint
             TRY(ensure(w.g_nx, (lb + 64) * 4));
             TRY(ensure(w.g_pv, (lb + 64) * 4));
             TRY(ensure(w.g_lv, (lvls + 64) * 8));
-            const bool rounds = !(c->dbg & 1024);  // (debug bit 1024: one merge at a time for every long piece)
+            const bool rounds = !(c->dbg & TK_DBG_ONE_MERGE);
             if (rounds) {
                 TRY(timed(c, s, "tk_k_merge_rounds", [&] {
                     hipLaunchKernelGGL(tk_k_merge_rounds, dim3(grid_for(nC, 1, 1024)), dim3(TKB_THREADS), 0, s, T, d_text, w.listC.as<uint32_t>(),
@@ -1158,7 +1158,7 @@ static int chunk_finish(tk_core* c, WorkSet& w, const ChunkJob& job, uint64_t* n
     uint64_t nB = 0;
     for (int b = 0; b < TK_NBIN; ++b) {
         nB += hb[TK_CNT_BIN0 + b];
-        if ((c->dbg & 64) && hb[TK_CNT_BIN0 + b]) fprintf(stderr, "bin %d (%u..%u bytes): %u pieces\n", b, tk_bin_lo(b), tk_bin_hi(b), hb[TK_CNT_BIN0 + b]);
+        if ((c->dbg & TK_DBG_VERBOSE) && hb[TK_CNT_BIN0 + b]) fprintf(stderr, "bin %d (%u..%u bytes): %u pieces\n", b, tk_bin_lo(b), tk_bin_hi(b), hb[TK_CNT_BIN0 + b]);
     }
     if (hb[TK_CNT_ERR] & (TK_RX_ERR_GAP | TK_RX_ERR_STACK | TK_RX_ERR_LIMIT)) return rx_failure(hb, job.base);
     if (hb[TK_CNT_ERR]) return fail(TK_RUNTIME_ERROR, "internal error in the front kernel (scanner list overflow, code " + std::to_string(hb[TK_CNT_ERR]) + ")");
@@ -1596,7 +1596,7 @@ static int small_wait(tk_core* c, tk_core::SmallSlot* const* mine, uint32_t k) {
 static int encode_mid(tk_core* c, const uint8_t* utf8, uint32_t n, uint32_t** tokens_out, uint64_t* n_tokens_out, bool* handled) {
     *handled = false;
     auto why = [&](const char* r) {
-        if (c->dbg & 64) fprintf(stderr, "encode_mid: %u bytes not taken: %s\n", n, r);
+        if (c->dbg & TK_DBG_VERBOSE) fprintf(stderr, "encode_mid: %u bytes not taken: %s\n", n, r);
         return TK_OK;
     };
     if (!c->mid_cut) return why("letter -> space is not a certain start of this pattern");
@@ -1637,8 +1637,8 @@ static int encode_mid(tk_core* c, const uint8_t* utf8, uint32_t n, uint32_t** to
     // -- measured on web text, profiles/r04_mid_calls_corpus.txt)
     // (documents of up to 6 KiB: the segments merge their long pieces themselves -- 4 KiB of web text 140 us against 162 when a segment gives the
     // document up at such a piece, and 170 through the general pipeline; from 16 KiB on the pipeline wins on such text either way:
-    // profiles/r05_small_variants.txt.  Debug bit 0x20000000: always.)
-    const bool keep_long = n <= 6144u || (c->dbg & 0x20000000);
+    // profiles/r05_small_variants.txt.  TK_DBG_KEEP_LONG: always.)
+    const bool keep_long = n <= 6144u || (c->dbg & TK_DBG_KEEP_LONG);
     for (uint32_t i = 0; i < k; ++i) small_slot_submit(mine[i], utf8 + cuts[i], cuts[i + 1] - cuts[i], !keep_long);
     TRY(small_wait(c, mine, k));
     // the segments' tokens, one after the other.  A segment the small kernel did not do sends the WHOLE document to the general pipeline (one pass
@@ -1754,7 +1754,7 @@ static int encode_batch_impl(tk_core* c, const uint8_t* utf8, const uint64_t* do
     for (uint64_t d = 0; d < n_docs; ++d)
         if (doc_off[d + 1] < doc_off[d]) return fail(TK_VALUE_ERROR, "doc_off must be non-decreasing");
     const uint64_t n_bytes = doc_off[n_docs];
-    if (!no_small && !device_result && n_docs == 1 && n_bytes > 0 && n_bytes <= (uint64_t)TK_SMALL_MAX * TK_MID_SEGMENTS && !(use_special && n_allowed) && !(c->dbg & 2048) && !c->has_rx &&
+    if (!no_small && !device_result && n_docs == 1 && n_bytes > 0 && n_bytes <= (uint64_t)TK_SMALL_MAX * TK_MID_SEGMENTS && !(use_special && n_allowed) && !(c->dbg & TK_DBG_NO_SMALL) && !c->has_rx &&
         (n_bytes <= TK_SMALL_MAX || !c->profiling)) {
         bool handled = false;  // (before the lock: small calls of several threads run side by side)
         if (n_bytes <= TK_SMALL_MAX) TRY(encode_small(c, utf8, (uint32_t)n_bytes, tokens_out, n_tokens_out, &handled));
@@ -2240,7 +2240,7 @@ extern "C" int tk_decode_batch(tk_core* c, const uint32_t* tokens, const uint64_
             host_cap = est;
         }
         const double t_3 = now_us();
-        if (c->dbg & 64)
+        if (c->dbg & TK_DBG_VERBOSE)
             fprintf(stderr, "decode range %llu: at %.0f us; ids waited %.0f us, lengths %.0f us, buffers %.0f us\n", (unsigned long long)k, t_0 - t_call, t_1 - t_0,
                     t_2 - t_1, t_3 - t_2);
         HIPCHK(hipStreamWaitEvent(c->cs_d2h, ev_copy, 0));
@@ -2267,7 +2267,7 @@ extern "C" int tk_decode_batch(tk_core* c, const uint32_t* tokens, const uint64_
     if (e == hipSuccess) e = hipStreamSynchronize(c->cs_d2h);
     if (e == hipSuccess) e = hipGetLastError();
     drop_events();
-    if (c->dbg & 64) fprintf(stderr, "decode: %llu ranges, ids %s, %.0f us\n", (unsigned long long)n_ranges, src_pinned ? "page-locked" : "staged", now_us() - t_call);
+    if (c->dbg & TK_DBG_VERBOSE) fprintf(stderr, "decode: %llu ranges, ids %s, %.0f us\n", (unsigned long long)n_ranges, src_pinned ? "page-locked" : "staged", now_us() - t_call);
     if (rc == TK_KEY_ERROR && bad_pos != ~0ull) rc = fail(TK_KEY_ERROR, "Invalid token for decoding: " + std::to_string(tokens[bad_pos]));
     if (rc == TK_OK && e != hipSuccess) rc = fail(TK_RUNTIME_ERROR, std::string("HIP error: ") + hipGetErrorString(e));
     if (rc == TK_OK) rc = drain_events(c);  // (before the outputs are published: a caller that gets an error owns nothing)

@@ -47,18 +47,14 @@
 #define TKF_CONT_CAP_FAST 768  // ... one-workgroup-per-tile variant (the list lives in the byte table's LDS, dead after phase B)
 #define TKF_SLOW_CAP 8    // pieces of one tile that leave its window
 // A deferred tile in a stretch without certain starts walks towards itself from the stretch's start, a 4 KiB window per step; every tile
-// of the stretch does: quadratic.  With TKF_DBG_MAY_GIVE_UP in `dbg` a tile gives up after TKF_WALK_BUDGET windows and goes on a second
+// of the stretch does: quadratic.  With TK_DBG_MAY_GIVE_UP in `dbg` a tile gives up after TKF_WALK_BUDGET windows and goes on a second
 // list (behind the first, count in TK_CNT_DEFER2); the host then lets the generic engine split the chunk -- every piece start becomes a
-// hard start -- and runs the kernel again over that list (TKF_DBG_SECOND).  TIKTOKEN_AMD_DEBUG bit 0x20000000: a budget of zero windows
-// (tests: ordinary corpora through this path).
+// hard start -- and runs the kernel again over that list (TK_DBG_SECOND).  TK_DBG_NO_BUDGET: a budget of zero windows (tests: ordinary
+// corpora through this path).
 #define TKF_WALK_BUDGET 32u
-#define TKF_DBG_MAY_GIVE_UP 0x8000000
-#define TKF_DBG_SECOND 0x10000000
-#define TKF_DBG_NO_BUDGET 0x20000000
-// Every piece start of the chunk is a hard start already (the generic engine has split it: tk_api.hip, rx_split): the tile's piece starts
-// ARE its hard starts, phases B-D (classes, certain starts, scanners: 2 of the kernel's 5.3 ms per GiB) are skipped by the one-tile-per-
-// workgroup instances.  The deferred-tile instance never takes this way (it is the general one).
-#define TKF_DBG_HARD_ONLY 0x40000000
+// With TK_DBG_HARD_ONLY every piece start of the chunk is a hard start already (the generic engine has split it: tk_api.hip, rx_split): the
+// tile's piece starts ARE its hard starts, phases B-D (classes, certain starts, scanners: 2 of the kernel's 5.3 ms per GiB) are skipped by the
+// one-tile-per-workgroup instances.  The deferred-tile instance never takes this way (it is the general one).
 // The deferred tiles in TWO kernels (round 5).  The scanner of the deferred tiles compiles at 128 registers with ~70 spilled, four
 // workgroups per CU: so its instance (TKF_MODE_STARTS) only FINDS the piece starts -- it leaves the tile's start bitmap and, in tile_np,
 // where the tile's last piece ends -- and a third instance (TKF_MODE_GIVEN), launched over the deferred list, takes starts and end from
@@ -597,23 +593,16 @@ __device__ __forceinline__ bool tk_equal_lds_text(const uint8_t* raw, uint32_t o
 #define TKF_OCC 8
 #endif
 #ifndef TKF_GIVEN_OCC
-#define TKF_GIVEN_OCC TKF_OCC  // ... of the instance that finishes the deferred tiles (round 6: its loop over the list spills 26 registers at eight per CU; at six or five it spills fewer or none and is no faster -- 0.068 ms either way, tools/gpu_r6_call6.sh)
+#define TKF_GIVEN_OCC TKF_OCC  // ... of the instance that finishes the deferred tiles (round 6: its loop over the list spills 26 registers at eight per CU; at six or five it spills fewer or none and is no faster -- 0.068 ms either way, tools/gpu_r6_call6.sh at 1670321)
 #endif
 #ifndef TKF_SLOW_OCC
-#define TKF_SLOW_OCC 3  // workgroups per CU of the deferred-tile variant (its grid: tk_api.hip, stage_deferred).  Round 6, on one box (tools/gpu_slowocc.sh):
+#define TKF_SLOW_OCC 3  // workgroups per CU of the deferred-tile variant (its grid: tk_api.hip, stage_deferred).  Round 6, on one box (tools/gpu_slowocc.sh at 1670321):
                         // 3 against 4 -- C2 78.5 / 77.0 GB/s, C5 its kernel 0.168 / 0.188 ms, C3 0.40 / 0.38 ms (within the noise of the box)
 #endif
 // A pointer put together from an integer (the kernarg segment read again, a word parked in LDS) is a GENERIC pointer to the compiler: its loads and stores
 // become flat_* instructions -- a 64-bit address in vector registers for every access (no scalar base + 32-bit offset form), and counted by lgkmcnt as well as
 // vmcnt, so that every wait for an LDS read also waits for the table probes in flight.  Through a pointer of the global address space they are global_* again.
-#ifndef TKF_GLOBAL_PTRS
-#define TKF_GLOBAL_PTRS 1
-#endif
-#if TKF_GLOBAL_PTRS
 #define TKF_PTR(type, v) ((type)(__attribute__((address_space(1))) void*)(uintptr_t)(v))
-#else
-#define TKF_PTR(type, v) ((type)(uintptr_t)(v))
-#endif
 #ifndef TKF_CLAIM_SPIN
 #define TKF_CLAIM_SPIN 8  // looks a duplicate takes at a slot whose claimant has not written its words yet (see `claim`)
 #endif
@@ -633,7 +622,7 @@ __device__ unsigned long long tk_time_acc[2 * 1024 * 16];  // (spread over 1024 
 #else
 #define TKT(i) do { } while (0)
 #endif
-// (round 6, TKF_EXTEND) Where does the run of letters that reaches the end of a front-kernel window end?  One wavefront reads on from `from` (8-byte
+// (round 6) Where does the run of letters that reaches the end of a front-kernel window end?  One wavefront reads on from `from` (8-byte
 // aligned), eight bytes per lane and 512 per step, a class lookup per char, up to 2 KiB.  CL (cl100k): letters of any kind, ended by anything else;
 // otherwise (o200k) letters without case and marks, ended by anything but a cased letter or an apostrophe.  Returns the end relative to `from - TK2_WIN`
 // (the window's base), or 0 when the run goes on differently or for too long.  The table and bitmap pointers come from LDS (ext_sh in tk_k_front): as
@@ -694,8 +683,8 @@ __device__ __forceinline__ uint32_t tk_extend_letter_run(const uint8_t* __restri
     }
     return 0u;
 }
-// The kernel's arguments as the kernarg segment lays them out (TKF_PARK_ARGS == 2: phase E reads what it needs of them from there again, by scalar loads
-// at the point of use, instead of carrying them in registers from the kernel's entry; the static_asserts in tk_k_front tie the offsets to the signature).
+// The kernel's arguments as the kernarg segment lays them out: phases E and F read what they need of them from there again, by scalar loads at the
+// point of use, instead of carrying them in registers from the kernel's entry (tk_k_front_args_check ties the offsets to the signature).
 struct TkFrontArgs {
     TkTables T;
     const uint8_t* text;
@@ -740,21 +729,15 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
     // phase C reads each lane's 16 bits from global memory, phase F finds the starts of special tokens in `brkw`, reloaded in phase E)
     __shared__ uint32_t brkw[TK2_WIN / 32 + 1];
     __shared__ uint32_t scan_sh[8];
-    // (TKF_EXTEND) four pointers the rare way out of "a piece leaves the window" needs, parked in LDS by phase A: kept in scalar registers up to that point
+    // four pointers the rare way out of "a piece leaves the window" needs, parked in LDS by phase A: kept in scalar registers up to that point
     // of the kernel they made it spill 135 more scalar reloads into the paths that every tile takes (4.38 -> 4.46 ms per GiB)
     __shared__ uint64_t ext_sh[4];
-#ifndef TKF_PARK_ARGS
-#define TKF_PARK_ARGS 2  // 0: the arguments stay in registers; 1: parked in LDS (park_sh); 2: read from the kernarg segment again where phase E begins
-#endif
-    // (experiment, round 6) what only phases E and F need of the kernel's arguments, parked in LDS by phase A and read back where phase E begins: kept in scalar
-    // registers from the kernel's first instruction they are part of the 150 scalar values the kernel spills into vector-register lanes
-    // ... and better still (TKF_PARK_ARGS == 2, shipped): they are in memory already -- the kernarg segment -- and a scalar load at the point of use costs
-    // neither LDS traffic nor the thirty-four v_readfirstlane of the LDS form: front 4.39 -> 4.35 ms per GiB on one box.  The compiler must not see that the
-    // pointer is the kernarg segment's (it would load at the kernel's entry again): it goes through an empty asm statement.  tk_k_front_args_check
-    // (run once by tk_create) compares what the offsets of TkFrontArgs give with the arguments themselves.
-#if TKF_PARK_ARGS == 1
-    __shared__ uint64_t park_sh[18];
-#endif
+    // What only phases E and F need of the kernel's arguments is read from the kernarg segment again where it is used (below, where phase E begins): kept
+    // in scalar registers from the kernel's first instruction these words were part of the 150 scalar values the kernel spills into vector-register lanes;
+    // a scalar load at the point of use costs neither registers nor LDS traffic (front 4.39 -> 4.35 ms per GiB on one box; parking them in LDS was the
+    // slower form: profiles/HISTORY.md part 0).  The compiler must not see that the pointer is the kernarg segment's (it would load at the kernel's
+    // entry again): it goes through an empty asm statement.  tk_k_front_args_check (run once by tk_create) compares what the offsets of TkFrontArgs give
+    // with the arguments themselves.
     uint64_t(*bm)[NW] = (uint64_t(*)[NW])pool;
     uint8_t* lastc = lastc_own;
     // From phase C on the byte table is dead in the one-tile-per-workgroup variant: its 2 KiB hold the "stop" bitmap of the scanners'
@@ -763,10 +746,7 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
     uint16_t* stop16 = SLOW ? stop_own : (uint16_t*)btab;          // [256] char starts at which a piece may start (16 per lane)
     uint16_t* contl = SLOW ? contl_own : (uint16_t*)btab + 256;    // [CONT_CAP] scan chains still to be walked (window positions)
     const uint32_t tid = threadIdx.x;
-#ifndef TKF_SCALAR_WID
-#define TKF_SCALAR_WID 1
-#endif
-    const int lane = tid & 63, wid = TKF_SCALAR_WID ? __builtin_amdgcn_readfirstlane((int)(tid >> 6)) : (int)(tid >> 6);
+    const int lane = tid & 63, wid = __builtin_amdgcn_readfirstlane((int)(tid >> 6));
     uint32_t item = blockIdx.x;
 #ifdef TKF_TIMING
     unsigned long long tkt_prev = __builtin_readcyclecounter();
@@ -777,7 +757,7 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
     // (round 6) GIVEN as well: the host launches it without having read the list's length (a grid from the chunk before, stage_deferred) and the grid
     // walks the list with its stride -- an instance of its own, whose loop state costs the common instance nothing.
     constexpr bool PERSIST = SLOW || GIVEN;
-    const uint32_t n_items = SLOW ? out.counters[(dbg & TKF_DBG_SECOND) ? TK_CNT_DEFER2 : TK_CNT_DEFER] : (GIVEN ? (uint32_t)__builtin_amdgcn_readfirstlane((int)out.counters[TK_CNT_DEFER]) : gridDim.x);
+    const uint32_t n_items = SLOW ? out.counters[(dbg & TK_DBG_SECOND) ? TK_CNT_DEFER2 : TK_CNT_DEFER] : (GIVEN ? (uint32_t)__builtin_amdgcn_readfirstlane((int)out.counters[TK_CNT_DEFER]) : gridDim.x);
     if (PERSIST && item >= n_items) return;
     // (round 6) The deferred tiles differ a lot -- a walk back through a megabyte of one class, or nothing of the kind: 30 000 to 400 000 cycles -- and
     // there are few of them (0.75 % of the tiles of web text: 2.7 per workgroup of this grid).  With the stride of the grid the kernel lasted as long as
@@ -789,7 +769,7 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
             return item < n_items;
         }
         __syncthreads();
-        if (tid == 0) next_item_sh = gridDim.x + atomicAdd(&out.counters[TK_CNT_SLOWQ + ((dbg & TKF_DBG_SECOND) ? 1 : 0)], 1u);
+        if (tid == 0) next_item_sh = gridDim.x + atomicAdd(&out.counters[TK_CNT_SLOWQ + ((dbg & TK_DBG_SECOND) ? 1 : 0)], 1u);
         __syncthreads();
         item = next_item_sh;
         return item < n_items;
@@ -812,20 +792,6 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
     const uint64_t tile_start = tile * TK_TILE;
     const uint64_t tile_end = tile_start + TK_TILE < n ? tile_start + TK_TILE : n;
     const int64_t base = (int64_t)tile_start - TK2_LEFT;
-#ifndef TKF_FRESH_SCALARS
-#define TKF_FRESH_SCALARS 0  // experiment (see below): 0 off, 1 in phases E and F, 2 in the whole kernel
-#endif
-#if TKF_FRESH_SCALARS == 2
-    // (round 6) What the compiler derives from the tile's index and keeps for the whole kernel -- the tile's first byte (tile x TK_TILE, 64 bits), its end, the
-    // window's base -- were scalar registers spilled at the kernel's entry and reloaded by vector instructions wherever they are used (74 of the kernel's 150
-    // v_readlane).  Through an empty asm statement at the point of use they are two scalar multiplications there and nothing is kept but the index.
-    auto tile_start_fresh = [&]() -> uint64_t { uint32_t t = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)tile); asm volatile("" : "+s"(t)); return (uint64_t)t * (uint64_t)TK_TILE; };
-    auto tile_end_fresh = [&]() -> uint64_t { const uint64_t e = tile_start_fresh() + TK_TILE; return e < n ? e : n; };
-    auto base_fresh = [&]() -> int64_t { return (int64_t)tile_start_fresh() - TK2_LEFT; };
-#define tile_start tile_start_fresh()
-#define tile_end tile_end_fresh()
-#define base base_fresh()
-#endif
     // ---- A: every lane owns 16 bytes of the window (kept in registers and copied to LDS)
     const int64_t gp = base + (int64_t)tid * 16;
     uint32_t w[4] = {0, 0, 0, 0};
@@ -866,27 +832,6 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
             ext_sh[2] = (uint64_t)(uintptr_t)T.uc_stage1;
             ext_sh[3] = (uint64_t)(uintptr_t)T.uc_stage2;
         }
-#if TKF_PARK_ARGS == 1
-        if (!SLOW) {
-            park_sh[0] = (uint64_t)(uintptr_t)T.short_tab;
-            park_sh[1] = (uint64_t)(uintptr_t)T.mid_tab;
-            park_sh[2] = (uint64_t)(uintptr_t)T.xl;
-            park_sh[3] = (uint64_t)(uintptr_t)T.tok_bytes;
-            park_sh[4] = (uint64_t)(uintptr_t)mt;
-            park_sh[5] = (uint64_t)(uintptr_t)out.res;
-            park_sh[6] = (uint64_t)(uintptr_t)out.data.tab;
-            park_sh[7] = (uint64_t)(uintptr_t)out.data.ovf;
-            park_sh[8] = (uint64_t)(uintptr_t)out.listC;
-            park_sh[9] = (uint64_t)T.short_mask | ((uint64_t)T.short_shift << 32);
-            park_sh[10] = (uint64_t)T.mid_mask | ((uint64_t)T.mid_shift << 32);
-            park_sh[11] = (uint64_t)T.xl_mask | ((uint64_t)T.max_token_len << 32);
-            park_sh[12] = (uint64_t)mt_mask | ((uint64_t)out.data.ovf_base << 32);
-            park_sh[13] = (uint64_t)out.ovf_cap;
-            park_sh[14] = (uint64_t)(uintptr_t)T.piece;  // (the probe of a piece of more than TK_XL_MAX bytes where there is no in-call table: small chunks)
-            park_sh[15] = (uint64_t)(uintptr_t)T.piece_off;
-            park_sh[16] = T.piece_mask;
-        }
-#endif
         need_walk = 0;
         ncont_sh = 0;
         nslow_sh = 0;
@@ -899,13 +844,10 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
     if (tid < 4) planes[tid][TK2_NSEG] = planes[tid][TK2_NSEG + 1] = tid >= 2 ? ~0ull : 0ull;  // (class END)
     __syncthreads();
     TKT(0);
-    if (dbg & 0x1000) {  // (perf experiments: stop after this phase)
+    if (dbg & TK_DBG_STOP_A) {  // (perf experiments: stop after this phase)
         if (tid == 0) out.tile_np[tile] = 0;
         continue;
     }
-#ifndef TKF_HARD_ONLY
-#define TKF_HARD_ONLY 1
-#endif
     if constexpr (GIVEN) {
         // ---- the tile's piece starts and the end of its last piece are given (the deferred-tile instance has found them)
         if (tid < TK_TILE / 32) {
@@ -914,7 +856,7 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
         }
         if (tid == 0) last_end_sh = out.tile_np[tile];
         __syncthreads();
-    } else if (TKF_HARD_ONLY && !SLOW && (dbg & TKF_DBG_HARD_ONLY)) {
+    } else if (!SLOW && (dbg & TK_DBG_HARD_ONLY)) {
         // ---- hard starts only: the pieces that start in the tile begin at its hard starts; the last of them ends at the first hard start
         // at or behind the tile's end -- in the 128 bytes of look-ahead, or the tile is one for the workgroup-wide scanner
         const uint32_t te = (uint32_t)(tile_end - tile_start) + (uint32_t)TK2_LEFT;
@@ -985,11 +927,8 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
             return cl;
         };
         const uint32_t prev = tid ? dw[tid * 4u - 1u] : 0u;
-#ifndef TKF_DENSE_DECODE
-#define TKF_DENSE_DECODE 1
-#endif
         bool decoded = false;
-        if constexpr (TKF_DENSE_DECODE && MODE == TKF_MODE_TILE) {
+        if constexpr (MODE == TKF_MODE_TILE) {
             // (round 6) The non-ASCII chars of a wavefront's 1024 bytes by DENSE lanes.  tk_chunk_decode is a loop of ~100 vector instructions per two chars of
             // a lane that runs as long as the lane with the most chars (up to eight in sixteen bytes) while the average lane of web text has fewer than two:
             // most of its instructions are issued for a handful of active lanes.  Here the lanes list the window positions of their lead bytes (a prefix sum
@@ -1061,7 +1000,7 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
         if (!decoded) tk_chunk_decode(ch, prev, tid > 0, get4, cls_of);
     }
     TKT(1);
-    if (dbg & 0x2000) {  // (perf experiments: stop after the classification)
+    if (dbg & TK_DBG_STOP_B) {  // (perf experiments: stop after the classification)
         if (tid == 0 || (ch.acc0 ^ ch.acc1) == 0xFFFFFFF1u) out.tile_np[tile] = 0;
         continue;
     }
@@ -1151,10 +1090,7 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
                 else walk = true;
             }
         }
-#ifndef TKF_SYNC_POINTS
-#define TKF_SYNC_POINTS 1
-#endif
-        if constexpr (TKF_SYNC_POINTS && (PAT == TK_PAT_O200K || PAT == TK_PAT_CL100K) && !SLOW) {
+        if constexpr ((PAT == TK_PAT_O200K || PAT == TK_PAT_CL100K) && !SLOW) {
             // (round 6) No certain start in the left context -- the inside of a sentence of a script without spaces (a piece of 120 to 1000 bytes: half of the
             // tiles that went to the workgroup-wide scanner on web text).  A scan does not need a piece START to be in phase with the sequential regex, only a
             // position at which the matcher's state is known: a lower-case letter (LL) that follows a letter of class LL or LC, with no apostrophe in the three
@@ -1223,7 +1159,7 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
         continue;
     }
     TKT(2);
-    if (dbg & 0x4000) {  // (perf experiments: stop after this phase)
+    if (dbg & TK_DBG_STOP_C) {  // (perf experiments: stop after this phase)
         if (tid == 0) out.tile_np[tile] = 0;
         continue;
     }
@@ -1293,7 +1229,7 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
                 if (fam != TK_PAT_R50K && pat.digits() && p < tile_start && (tk_class_byte_slow(&T, text, p, n, brk, coop.ss, coop.si) & 15u) == TK_C_NU)
                     e = tk_coop_skip_digit_groups(&coop, p, tile_start);  // whole three-digit groups left of the tile
                 if (e == p && p + 1024u < tile_start) {  // far left of the tile: a window of pieces per step (nothing of them lies in this tile)
-                    if ((dbg & TKF_DBG_MAY_GIVE_UP) && windows++ >= ((dbg & TKF_DBG_NO_BUDGET) ? 0u : TKF_WALK_BUDGET)) {  // (uniform: every lane counts the same)
+                    if ((dbg & TK_DBG_MAY_GIVE_UP) && windows++ >= ((dbg & TK_DBG_NO_BUDGET) ? 0u : TKF_WALK_BUDGET)) {  // (uniform: every lane counts the same)
                         gave_up = true;
                         return;
                     }
@@ -1476,9 +1412,6 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
         if (cont_now == cont_done) break;
     }
     if (!SLOW && nslow_sh) {
-#ifndef TKF_EXTEND
-#define TKF_EXTEND 1
-#endif
         // (round 6) A piece leaves the window.  The other half of the tiles that went to the workgroup-wide scanner on web text: a sentence of a script without
         // spaces (120 to 1000 bytes, one piece) that starts near the tile's end.  Everything else about the tile is known -- what is missing is where that piece
         // ends, and for a letter piece that runs into the window's end inside a run of letters of ONE kind that is the end of the run: cl100k (`\p{L}++`) any
@@ -1490,7 +1423,7 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
         // bench corpora (tools/experiments/extend_piece.cpp): applies to 78 of 78 such tiles per 17 474 (o200k web text) and 23 of 23 (cl100k mixed text), right
         // every time.
         bool extended = false;
-        if constexpr (TKF_EXTEND && (PAT == TK_PAT_O200K || PAT == TK_PAT_CL100K)) {
+        if constexpr (PAT == TK_PAT_O200K || PAT == TK_PAT_CL100K) {
             constexpr bool CL = PAT == TK_PAT_CL100K;
             constexpr uint32_t SET = CL ? TK_M_L : (TK_CB(TK_C_LC) | TK_CB(TK_C_MK) | TK_CB(TK_C_LL));
             constexpr uint32_t LETTER = CL ? TK_M_L : (TK_M_L | TK_CB(TK_C_MK));
@@ -1528,7 +1461,7 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
     }
     }
     TKT(3);
-    if (dbg & 0x8000) {  // (perf experiments: stop after this phase)
+    if (dbg & TK_DBG_STOP_D) {  // (perf experiments: stop after this phase)
         if (tid == 0) out.tile_np[tile] = 0;
         continue;
     }
@@ -1551,19 +1484,6 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
     // zeros where the row needs it), beside it the piece's index k in the tile (its result word is res[run + k]).
     constexpr uint32_t NWB = (uint32_t)TK_TILE / 32u;  // words of the tile's bitmap (even)
     const uint32_t run_base = (uint32_t)tile * TKF_CAP;
-#if TKF_PARK_ARGS
-    // (the names of the kernel's arguments, shadowed by what was parked: the code below reads as before)
-#if TKF_PARK_ARGS == 1
-    auto unpark = [&](int i) -> uint64_t {
-        const uint64_t v = park_sh[i];
-        return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v) | ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32);
-    };
-#endif
-    TkTables T_f{};
-    TkFrontOut out_f{};
-    TkMissKey* __restrict__ mt_f = nullptr;
-    uint32_t mt_mask_f = 0;
-#if TKF_PARK_ARGS == 2
     // The kernarg segment once more: a pointer the compiler cannot see through, in the constant address space (scalar loads).  What the rows and the dense
     // passes need of the tables is loaded WHERE IT IS USED (fresh_T(): the pointer goes through an empty asm statement every time, so the loads are not
     // moved out of the loop of the rows -- which uses a different table in each of its branches: all of them alive across the whole loop were spilled
@@ -1608,62 +1528,16 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
         mask_out = TKF_KA32(ka, offsetof(TkFrontArgs, mt_mask));
         return TKF_PTR(TkMissKey*, TKF_KA64(ka, offsetof(TkFrontArgs, mt)));
     };
-    if constexpr (!SLOW) {
-        out_f.starts = TKF_KA_OP(ka_e, uint32_t*, starts);
-        out_f.tile_np = TKF_KA_OP(ka_e, uint32_t*, tile_np);
-        out_f.res = TKF_KA_OP(ka_e, uint32_t*, res);
-        mt_f = fresh_mt(mt_mask_f);
-    }
-#else
-    if constexpr (!SLOW) {
-        T_f.short_tab = (const TkShortSlot*)(uintptr_t)unpark(0);
-        T_f.mid_tab = (const TkPieceSlot*)(uintptr_t)unpark(1);
-        T_f.xl = (const TkXlSlot*)(uintptr_t)unpark(2);
-        T_f.tok_bytes = (const uint8_t*)(uintptr_t)unpark(3);
-        mt_f = (TkMissKey*)(uintptr_t)unpark(4);
-        out_f.res = (uint32_t*)(uintptr_t)unpark(5);
-        out_f.data.tab = (TkMissTab*)(uintptr_t)unpark(6);
-        out_f.data.ovf = (TkMissOvf*)(uintptr_t)unpark(7);
-        out_f.listC = (uint32_t*)(uintptr_t)unpark(8);
-        const uint64_t a = unpark(9), b = unpark(10), c = unpark(11), d = unpark(12);
-        T_f.short_mask = (uint32_t)a; T_f.short_shift = (uint32_t)(a >> 32);
-        T_f.mid_mask = (uint32_t)b; T_f.mid_shift = (uint32_t)(b >> 32);
-        T_f.xl_mask = (uint32_t)c; T_f.max_token_len = (uint32_t)(c >> 32);
-        mt_mask_f = (uint32_t)d; out_f.data.ovf_base = (uint32_t)(d >> 32);
-        out_f.ovf_cap = (uint32_t)unpark(13);
-        T_f.piece = (const TkPieceSlot*)(uintptr_t)unpark(14);
-        T_f.piece_off = (const uint32_t*)(uintptr_t)unpark(15);
-        T_f.piece_mask = unpark(16);
-        out_f.starts = out.starts; out_f.tile_np = out.tile_np; out_f.counters = out.counters;
-        if constexpr (SPEC) {  // (the instances with allowed special tokens look their ids up here: tk_special_id)
-            T_f.n_spec = T.n_spec; T_f.spec_bytes = T.spec_bytes; T_f.spec_id = T.spec_id; T_f.spec_off = T.spec_off;
-        }
-    }
-#endif
-    const TkTables& T_outer = T;
-    (void)T_outer;
-#if TKF_PARK_ARGS == 2
-    (void)T_f;
-#define T fresh_T()  /* (undefined again where the kernel's loop ends) */
-#if TKF_FRESH_SCALARS
-    // The same for the tests of the debug word's bits in phases E and F: each was a 64-bit lane mask computed before the loop of the rows, spilled, and
-    // reloaded by two vector instructions in every row and every dense pass.  Through an empty asm statement they are a scalar test at the point of use.
-    auto dbg_fresh = [&]() -> int { int d = dbg; asm volatile("" : "+s"(d)); return d; };
-#define dbg dbg_fresh()
-#if TKF_FRESH_SCALARS == 1
-    auto tile_start_fresh = [&]() -> uint64_t { uint32_t t = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)tile); asm volatile("" : "+s"(t)); return (uint64_t)t * (uint64_t)TK_TILE; };
-    auto base_fresh = [&]() -> int64_t { return (int64_t)tile_start_fresh() - TK2_LEFT; };
-#define tile_start tile_start_fresh()
-#define base base_fresh()
-#endif
-#endif
-#else
-    const TkTables& T = T_f;
-#endif
+    // The names of the kernel's arguments, shadowed by what is read here, so that the code below reads as it would with the arguments themselves
+    // (`T` loads at every use; the dense passes read `mt` again).
+    TkFrontOut out_f{};
+    out_f.starts = TKF_KA_OP(ka_e, uint32_t*, starts);
+    out_f.tile_np = TKF_KA_OP(ka_e, uint32_t*, tile_np);
+    out_f.res = TKF_KA_OP(ka_e, uint32_t*, res);
     const TkFrontOut& out = out_f;
-    TkMissKey* __restrict__ mt = mt_f;
-    uint32_t mt_mask = mt_mask_f;
-#endif
+    uint32_t mt_mask;
+    TkMissKey* __restrict__ mt = fresh_mt(mt_mask);
+#define T fresh_T()  /* (undefined again where the kernel's loop ends) */
     uint32_t* bx = certw;                            // [128] the start bitmap once more, plus the END of the tile's last piece (the certain starts are dead)
     uint16_t* ord_sl = (uint16_t*)btab;              // [1024] short pieces from the front, long ones from the back: window positions (the byte table is dead)
     uint16_t* ord_m = (uint16_t*)planes;             // [1024] mid pieces (the planes are dead)
@@ -1697,7 +1571,7 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
     }
     __syncthreads();
     TKT(4);
-    if (dbg & 0x10000) {  // (perf experiments: stop after this phase)
+    if (dbg & TK_DBG_STOP_E) {  // (perf experiments: stop after this phase)
         if (tid == 0) out.tile_np[tile] = 0;
         continue;
     }
@@ -1734,11 +1608,7 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
                 __hip_atomic_store(&mt[i].w0, w0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __hip_atomic_store(&mt[i].w1, w1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __hip_atomic_store(&mt[i].w2, w2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#if TKF_PARK_ARGS == 2
                 *(uint2*)&fresh_out().data.tab[i].start = make_uint2((uint32_t)gs, len);
-#else
-                *(uint2*)&out.data.tab[i].start = make_uint2((uint32_t)gs, len);
-#endif
                 return i;
             }
             if (cur == kk) {
@@ -1891,7 +1761,7 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
         // A piece that is not a token goes on the wavefront's list.
         const uint32_t n_s = scan_sh[0], n_m = scan_sh[1], n_l = scan_sh[2], n_xl = scan_sh[3];
         const uint32_t rows_l = (n_l + 63u) >> 6, rows_m = (n_m + 63u) >> 6, rows_s = (n_s + 63u) >> 6, rows_all = rows_l + rows_m + rows_s;
-        const bool use_mt = mt != nullptr && !(dbg & 8);
+        const bool use_mt = mt != nullptr && !(dbg & TK_DBG_STARTS_ONLY);
         n_mine = (n_xl + 3u - (uint32_t)wid) >> 2;
         for (uint32_t r = (uint32_t)wid;; r += 4u) {
             const bool more = r < rows_all;
@@ -1901,9 +1771,7 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
                 // and the last eight bytes, the length, and a comparison in the text).  Round 5 did this inside every row, for the 19 % of its
                 // lanes whose piece was not a token -- eleven sparse passes through this code per tile where these are four.
                 for (uint32_t c0 = 0; c0 < n_mine; c0 += 64u) {
-#if TKF_PARK_ARGS == 2
                     mt = fresh_mt(mt_mask);  // (the in-call table's base and mask: alive inside a dense pass only)
-#endif
                     const uint32_t q = c0 + (uint32_t)lane;
                     const bool have = q < n_mine;
                     const uint32_t e = mlw[have ? q : 0u];
@@ -1915,8 +1783,8 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
                         const uint32_t e_loc = (e >> 24) == 3u ? far_end(pos) : pos + near_len(pos);
                         len = e_loc - pos;
                         gs = (uint64_t)(base + pos);
-                        if (dbg & (2 | 8)) {  // (perf experiments / piece starts only: every probe counts as a hit -- only the longest pieces get here)
-                            out.res[run_base + k] = (dbg & 2) ? len : 0u;
+                        if (dbg & (TK_DBG_PROBE_LEN | TK_DBG_STARTS_ONLY)) {  // (perf experiments / piece starts only: every probe counts as a hit -- only the longest pieces get here)
+                            out.res[run_base + k] = (dbg & TK_DBG_PROBE_LEN) ? len : 0u;
                         } else {
                             fail = true;
                             if (use_mt && len <= TK_GLANE_MAX) {
@@ -1924,7 +1792,7 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
                                 uint64_t w0, w1, w2;
                                 tk_ident([&](uint32_t o) { return in_lds ? tk_lds_load8(raw, pos + o) : tk_load8(text, gs + o); }, len, (uint32_t)gs, w0, w1, w2);
                                 unsigned long long kk = tk_ident_hash(w0, w1, w2, exact);
-                                if (dbg & 512) kk &= 0xFFFull;  // test hook: force collisions between different pieces
+                                if (dbg & TK_DBG_COLLIDE) kk &= 0xFFFull;  // test hook: force collisions between different pieces
                                 if (kk == TK_EMPTY_KEY) kk = 0;
                                 const uint32_t i = ((uint32_t)kk ^ (uint32_t)(kk >> 40)) & mt_mask;
                                 ref = claim(w0, w1, w2, kk, exact, in_lds, pos, gs, len, i, *(const ulonglong2*)&mt[i].key, *(const ulonglong2*)&mt[i].w1);
@@ -1949,9 +1817,7 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
                         }
                         const uint64_t m = __ballot(over);
                         if (m) {
-#if TKF_PARK_ARGS == 2
                             const TkFrontOut out = fresh_out();  // (shadows the view that holds the result words' base only)
-#endif
                             const int leader = __ffsll((unsigned long long)m) - 1;
                             uint32_t at = 0;
                             if (lane == leader) at = atomicAdd(&out.counters[TK_CNT_OVF], (uint32_t)__popcll(m));
@@ -1972,20 +1838,20 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
             bool miss = false;
             uint32_t e = 0;
             if (r < rows_l) {
-                const TkTables Tr = T;  // (TKF_PARK_ARGS == 2: this row's table, loaded here -- on its way while the row reads its list)
+                const TkTables Tr = T;  // (this row's table, loaded here -- on its way while the row reads its list)
                 const uint32_t q = r * 64u + (uint32_t)lane;
                 if (q < n_l) {
                     const uint32_t pos = ord_sl[1023u - q], k = ordk_sl[1023u - q];
                     const uint32_t len = near_len(pos);
                     const bool in_lds = pos + len + 8u <= (uint32_t)TK2_WIN;
                     uint32_t rk = len;
-                    if (!(dbg & 2)) {
+                    if (!(dbg & TK_DBG_PROBE_LEN)) {
                         const uint64_t gs = (uint64_t)(base + pos);
                         uint64_t w0, w1, w2;
                         tk_ident([&](uint32_t o) { return in_lds ? tk_lds_load8(raw, pos + o) : tk_load8(text, gs + o); }, len, 0u, w0, w1, w2);
                         rk = tk_probe_xl(Tr, w0, w1, w2);
                     }
-                    if (rk != TK_RANK_MAX || (dbg & 8)) out.res[run_base + k] = rk == TK_RANK_MAX ? 0u : rk;
+                    if (rk != TK_RANK_MAX || (dbg & TK_DBG_STARTS_ONLY)) out.res[run_base + k] = rk == TK_RANK_MAX ? 0u : rk;
                     else {
                         miss = true;
                         e = pos | (k << 12) | (2u << 24);
@@ -1998,8 +1864,8 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
                     const uint32_t pos = ord_m[q], k = ordk_m[q];
                     const uint32_t len = near_len(pos);
                     const uint64_t key_m = tk_mask_low_bytes(tk_lds_load8(raw, pos), len);
-                    const uint32_t rk = (dbg & 2) ? len : tk_probe_mid(Tr, key_m, len);
-                    if (rk != TK_RANK_MAX || (dbg & 8)) out.res[run_base + k] = rk == TK_RANK_MAX ? 0u : rk;
+                    const uint32_t rk = (dbg & TK_DBG_PROBE_LEN) ? len : tk_probe_mid(Tr, key_m, len);
+                    if (rk != TK_RANK_MAX || (dbg & TK_DBG_STARTS_ONLY)) out.res[run_base + k] = rk == TK_RANK_MAX ? 0u : rk;
                     else {
                         miss = true;
                         e = pos | (k << 12) | (1u << 24);
@@ -2013,8 +1879,8 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
                     const uint32_t len = near_len(pos);
                     const uint32_t v = __builtin_amdgcn_alignbyte(dwr[(pos >> 2) + 1], dwr[pos >> 2], pos & 3u);
                     const uint32_t key_s = v & (0xFFFFFFFFu >> (32u - 8u * len));
-                    const uint32_t rk = (dbg & 2) ? len : (short_tab ? tk_probe_short(Tr, key_s, len) : tk_probe_mid(Tr, (uint64_t)key_s, len));
-                    if (rk != TK_RANK_MAX || (dbg & 8)) out.res[run_base + k] = rk == TK_RANK_MAX ? 0u : rk;
+                    const uint32_t rk = (dbg & TK_DBG_PROBE_LEN) ? len : (short_tab ? tk_probe_short(Tr, key_s, len) : tk_probe_mid(Tr, (uint64_t)key_s, len));
+                    if (rk != TK_RANK_MAX || (dbg & TK_DBG_STARTS_ONLY)) out.res[run_base + k] = rk == TK_RANK_MAX ? 0u : rk;
                     else {
                         miss = true;
                         e = pos | (k << 12);
@@ -2035,26 +1901,16 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
         out.res[run_base + TKF_TAIL_NGAP] = GEN ? ngap_sh : 0u;
     }
     }  // (!SLOW)
-#if TKF_PARK_ARGS == 2
 #undef T
-#if TKF_FRESH_SCALARS
-#undef dbg
-#endif
 #undef TKF_KA_OP
 #undef TKF_KA_T32
 #undef TKF_KA_TP
 #undef TKF_KA32
 #undef TKF_KA64
-#endif
-#if TKF_FRESH_SCALARS
-#undef tile_start
-#undef tile_end
-#undef base
-#endif
     } while (PERSIST && next_item());
 }
 
-// The kernarg offsets TKF_PARK_ARGS == 2 relies on, checked on the device (tk_create runs this once with arguments of distinct values): the same
+// The kernarg offsets phases E and F of tk_k_front rely on, checked on the device (tk_create runs this once with arguments of distinct values): the same
 // parameter list as tk_k_front, so the same kernarg layout.  ok[0] = 1 when every field read through TkFrontArgs' offsets equals the argument.
 __global__ void tk_k_front_args_check(TkTables T, const uint8_t* text, uint64_t n, uint64_t chunk_base, const uint32_t* brk, const uint32_t* docb, const uint32_t* ss,
                                       const uint32_t* si, TkFrontOut out, TkMissKey* mt, uint32_t mt_mask, uint32_t* deferred, const uint32_t* gapb, int dbg, uint32_t* ok) {
@@ -2589,8 +2445,9 @@ __global__ __launch_bounds__(64 * TKM_WAVES, TKM_MIN_WAVES_EU) void tk_k_merge_a
         }
         __builtin_amdgcn_wave_barrier();
         uint32_t lkey = local_min();
-        // (perf experiments, debug bits 25..28 = bin + 1: only that bin is merged, the pieces of the others come out as their single bytes)
-        if (((dbg >> 25) & 15) && ((dbg >> 25) & 15) - 1 != b) lkey = TKM_NOKEY;
+        // (perf experiments, the merge-bin field = bin + 1: only that bin is merged, the pieces of the others come out as their single bytes)
+        const int only_bin = (dbg >> TK_DBG_MERGE_BIN_SHIFT) & TK_DBG_MERGE_BIN_MASK;
+        if (only_bin && only_bin - 1 != b) lkey = TKM_NOKEY;
         for (;;) {
             // the piece's lowest key: leftmost lowest rank
             const uint32_t best = tkm_group_min(lkey, lg);
@@ -2605,8 +2462,8 @@ __global__ __launch_bounds__(64 * TKM_WAVES, TKM_MIN_WAVES_EU) void tk_k_merge_a
             const uint32_t oj = j / C, jl = j % C;
             const uint32_t nn_raw = pid[j] >> TKM_ID_BITS, pp_raw = pprv[bi];
             const uint32_t nn = nn_raw == TKM_NO_NEXT ? NONE : nn_raw, pp = pp_raw == TKM_NO_PREV ? NONE : pp_raw;
-            if (lg >= 2 && !(dbg & 0x80000)) {
-                // TWO merges per step (pieces of four lanes and more; debug bit 0x80000: one).  The step's time is the latency of its
+            if (lg >= 2 && !(dbg & TK_DBG_ONE_MERGE_STEP)) {
+                // TWO merges per step (pieces of four lanes and more; TK_DBG_ONE_MERGE_STEP: one).  The step's time is the latency of its
                 // table probes, and a long piece is a chain of hundreds of steps.  What the reference merges next (lib.rs:151,190) is the
                 // lowest key once more: either the lowest of the keys this merge leaves untouched -- known now -- or one of the two it
                 // creates.  So the second-lowest untouched key's merge is prepared at once, its neighbours taken from the state this
@@ -2641,7 +2498,7 @@ __global__ __launch_bounds__(64 * TKM_WAVES, TKM_MIN_WAVES_EU) void tk_k_merge_a
                 {
                     const uint32_t nb_pos = g == 0 ? nn : (g == 1 ? pp : (g == 2 ? nn2 : pp2));  // the neighbour this lane's pair is made with
                     const bool second = g >= 2, left = (g & 1u) != 0;                             // lanes 1, 3: (previous, merged)
-                    const bool on = !fin && g < 4u && nb_pos != NONE && (!second || has2) && !(dbg & 0x1000000);  // (0x1000000, perf experiments: no probes)
+                    const bool on = !fin && g < 4u && nb_pos != NONE && (!second || has2) && !(dbg & TK_DBG_MERGE_NO_PROBES);  // (perf experiments: no probes)
                     const uint32_t nid = pid[nb_pos != NONE ? nb_pos : 0u] & TKM_ID_MASK, mid = second ? rank2 : brank;
                     if (on) newr = tk_probe_pair(T, left ? nid : mid, left ? mid : nid);
                 }
@@ -2679,7 +2536,7 @@ __global__ __launch_bounds__(64 * TKM_WAVES, TKM_MIN_WAVES_EU) void tk_k_merge_a
             }
             // the two new pairs: (merged, next) and (previous, merged)
             uint32_t newr_i = TK_RANK_MAX, newr_p = TK_RANK_MAX;
-            if (dbg & 0x1000000) {  // (perf experiments: no probes -- wrong tokens, the cost of everything else)
+            if (dbg & TK_DBG_MERGE_NO_PROBES) {  // (perf experiments: no probes -- wrong tokens, the cost of everything else)
             } else if (lg == 0) {
                 if (!fin) tkm_probe2(T, brank, nn != NONE ? (pid[nn & (NMAX - 1u)] & TKM_ID_MASK) : 0u, nn != NONE, pp != NONE ? (pid[pp & (NMAX - 1u)] & TKM_ID_MASK) : 0u, brank, pp != NONE, newr_i, newr_p);
             } else {

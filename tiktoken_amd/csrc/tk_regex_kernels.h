@@ -187,7 +187,7 @@ __global__ __launch_bounds__(256) void tk_k_rx_link(TkRxDev R, const uint8_t* __
         tk_rx_link_lane<tk_rx_matcher_of(FORM)>(P, t, k, seg_shift, spec, xexit, lnk, lgap, lmerge, lexit);
 }
 
-// one lane per document (debug bit 0x40000; the CPU tests run this form lane by lane)
+// one lane per document (TK_DBG_RX_LANE; the CPU tests run this form lane by lane)
 template <int FORM>
 __global__ __launch_bounds__(256) void tk_k_rx_resolve(TkRxDev R, const uint8_t* __restrict__ text, uint32_t n, const uint32_t* __restrict__ brk,
                                                        const uint32_t* __restrict__ ss, const uint32_t* __restrict__ si,

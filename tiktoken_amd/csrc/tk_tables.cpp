@@ -24,7 +24,7 @@ TkPat tk_nosplit_pat() { return TkPat{(uint32_t)TK_PAT_R50K | 32u, 0u, {0u, 0u}}
 std::string tk_compile_pattern(const char* pat_str, TkPat* pat, uint16_t* cert, TkRxCompiled* rx) {
     // (TIKTOKEN_AMD_DEBUG bit 0x100000 = 1048576: the generic engine for every pattern -- how the tests compare it with the hand-written scanners)
     const char* dbg = getenv("TIKTOKEN_AMD_DEBUG");
-    const bool force_generic = dbg && (atoi(dbg) & 0x100000);
+    const bool force_generic = dbg && (atoi(dbg) & TK_DBG_GENERIC);
     const std::string perr = force_generic ? std::string("generic engine forced by TIKTOKEN_AMD_DEBUG") : tk_parse_pattern(pat_str, pat, cert);
     if (perr.empty()) return "";
     const std::string rerr = tk_rx_compile(pat_str, rx);

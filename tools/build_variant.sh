@@ -1,5 +1,5 @@
 #!/bin/bash
-# usage: tools/build_variant.sh NAME [-DTKF_HOT_BITS=11 -DTKF_OCC=3 ...]
+# usage: tools/build_variant.sh NAME [-DTKF_OCC=7 -DTKF_DENSE_MAX=96 -DTKF_TIMING ...]
 # Builds the product library with other compile-time parameters into tiktoken_amd/csrc/variants/libtiktoken_amd_NAME.so (experiments only:
 # $TIKTOKEN_AMD_LIB selects it at run time; the shipped library is the Makefile's).
 set -e

@@ -1,4 +1,4 @@
-// Experiment (round 6): the "letter run that leaves the window" rule of tk_k_front (tk_fused.h, TKF_EXTEND) checked on the bench corpora: for every
+// Experiment (round 6): the "letter run that leaves the window" rule of tk_k_front (tk_fused.h, end of phase D) checked on the bench corpora: for every
 // tile whose last piece ends behind the window, does the rule apply, and does it give the piece's end?  Host code over the product headers.
 //   g++ -O2 -std=c++17 -I. tools/experiments/extend_piece.cpp tiktoken_amd/csrc/tk_tables.cpp tiktoken_amd/csrc/tk_pattern.cpp tiktoken_amd/csrc/tk_regex.cpp -ldl -pthread -o /tmp/extend && /tmp/extend 2
 #include "../../tests/hostsim/tk_hostsim.cpp"

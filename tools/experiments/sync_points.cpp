@@ -1,4 +1,4 @@
-// Experiment (round 6): the "sync point" rule of tk_k_front (tk_fused.h, TKF_SYNC_POINTS) checked on the bench corpus -- every position that qualifies, not only
+// Experiment (round 6): the "sync point" rule of tk_k_front (tk_fused.h, phase D) checked on the bench corpus -- every position that qualifies, not only
 // the ones the kernel uses: the scan from it must end where its piece ends.  Host code over the product headers (like tests/hostsim).
 //   g++ -O2 -std=c++17 -I. tools/experiments/sync_points.cpp tiktoken_amd/csrc/tk_tables.cpp tiktoken_amd/csrc/tk_pattern.cpp tiktoken_amd/csrc/tk_regex.cpp -ldl -pthread -o /tmp/sync && /tmp/sync 2
 #include "../../tests/hostsim/tk_hostsim.cpp"
