@@ -310,12 +310,16 @@ def test_multi_chunk_batches(monkeypatch):
 def test_size_independent_properties_at_scale(cores):
     """At a size the oracle would need minutes for: decode(encode(x)) == x per document (sampled), token
     offsets are non-decreasing and end at the token count, and re-encoding a document alone gives the same
-    tokens as inside the 256 MiB batch (documents never interact)."""
+    tokens as inside the 256 MiB batch (documents never interact).  The whole batch decoded from pageable ids
+    on the core that has just run the pipelined host-buffer encode (tk_decode_batch through its staging
+    buffers) gives back the blob and the document offsets."""
     core = cores["o200k_shaped"]
     blob, off = h.gen_corpus(0x5CA1E, 1, 256 << 20, threads=16)
     toks, toff = core.encode_batch_packed(blob, off)
     assert toff[0] == 0 and toff[-1] == len(toks) and np.all(np.diff(toff.astype(np.int64)) >= 0)
     bb = blob.tobytes()
+    data, boff = core.decode_batch_packed(np.array(toks), toff)  # (a copy: the result buffer itself is page-locked)
+    assert data == bb and np.array_equal(boff, off)
     rng = np.random.default_rng(3)
     for d in rng.integers(0, len(off) - 1, size=200):
         a, b = int(off[d]), int(off[d + 1])

@@ -109,9 +109,8 @@ struct tk_core {
     int device = 0;
     hipStream_t stream = nullptr;
     hipStream_t aux[TK_NAUX] = {};  // side streams: the merge kernels are independent of each other
-    hipEvent_t ev_start = nullptr;
-    hipStream_t cs_h2d = nullptr, cs_d2h = nullptr;  // copy streams of the host-buffer entry point (created on first use)
-    void* stage[2] = {nullptr, nullptr};             // page-locked staging buffers
+    hipStream_t cs_h2d = nullptr, cs_d2h = nullptr;  // copy streams of the host-buffer entry points (created on first use)
+    void* stage[2] = {nullptr, nullptr};             // page-locked staging buffers of tk_decode_batch (created on its first use)
     hipEvent_t ev_stage[2] = {nullptr, nullptr};
     TkHostTables H;
     TkTables D;  // device view
@@ -127,7 +126,6 @@ struct tk_core {
     uint32_t defer_ppm = 1u << 12;  // deferred tiles per 2^20 tiles of the last chunk (the grid of the kernel that finishes them; first guess: one in 256 -- 4400 empty workgroups of that kernel were 0.06 ms of a first 1 GiB call)
     TkRxDev rx{};
     Buf t_rx_ins, t_rx_sets, t_rx_ranges, t_rx_first, t_rx_s1, t_rx_s2, t_rx_dtrans, t_rx_dascii, t_rx_ds1, t_rx_ds2;
-    bool rx_staged = true;  // the speculative pass over text staged in LDS where the pattern's DFA allows it ($TIKTOKEN_AMD_RX_STAGED=0: never)
     int rx_form = TK_RX_FORM_PROGRAM;  // how the generic engine's kernels match: the pattern's DFA where it has one ($TIKTOKEN_AMD_RX_MATCHER)
     std::mutex mu;
     // workspace: per chunk in flight, and what a whole call shares
@@ -154,9 +152,6 @@ struct tk_core {
     int dbg = 0;
     uint32_t n_cu = 256;             // compute units of the device
     uint32_t rx_grid_cap = 65536;    // most workgroups of tk_k_rx_speculate_staged (each walks the stretches with the stride of the grid: a chunk of more than 2 GiB, or $TIKTOKEN_AMD_RX_GRID_CAP)
-    uint32_t rx_seg_shift = 0;       // 0: by chunk size (tk_regex_split.h)
-    uint32_t rx_ahead = 0;           // 0: TK_RX_AHEAD / TK_RX_AHEAD_DFA by the kernels' form ($TIKTOKEN_AMD_RX_AHEAD: bytes)
-    uint32_t front_wgs = TKF_OCC;    // workgroups per CU of the persistent front kernel ($TIKTOKEN_AMD_FRONT_WGS)
     uint32_t n_dec = 0;  // entries of the device decode table (0: ids too sparse for a direct table -- decode stays on the host)
     Buf d_tok, d_lens, d_bsum, d_tboff, d_bytes, d_bytes_alt, d_boff;  // decode workspace (d_bytes_alt: the other range's bytes on their way to the host)
     // Small calls (tk_k_small) do not take `mu`: the reference's normal use is several threads on one Encoding (core.py:175, a thread pool
@@ -334,16 +329,11 @@ extern "C" int tk_create(const uint8_t* ranks_blob, const uint64_t* ranks_off, c
     if (hipSetDevice(device) != hipSuccess) return bail(fail(TK_RUNTIME_ERROR, "hipSetDevice failed"));
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return bail(fail(TK_RUNTIME_ERROR, "hipStreamCreate failed"));
     // All streams at the default priority.  (Measured, profiles/r03_stream_priority.txt: the mere existence of high-priority streams
-    // in the process slows the front kernel from 5.76 to 6.28 ms per GiB even while nothing runs on them.  $TIKTOKEN_AMD_PRIO=1 gives the
-    // back stages' streams the highest priority for experiments.)
-    int prio_lo = 0, prio_hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    if (!getenv("TIKTOKEN_AMD_PRIO")) prio_hi = 0;
+    // in the process slows the front kernel from 5.76 to 6.28 ms per GiB even while nothing runs on them.)
     for (int i = 0; i < TK_NAUX; ++i)
-        if (hipStreamCreateWithPriority(&c->aux[i], hipStreamNonBlocking, prio_hi) != hipSuccess) return bail(fail(TK_RUNTIME_ERROR, "hipStreamCreate failed"));
-    if (hipEventCreateWithFlags(&c->ev_start, hipEventDisableTiming) != hipSuccess) return bail(fail(TK_RUNTIME_ERROR, "hipEventCreate failed"));
+        if (hipStreamCreateWithFlags(&c->aux[i], hipStreamNonBlocking) != hipSuccess) return bail(fail(TK_RUNTIME_ERROR, "hipStreamCreate failed"));
     for (WorkSet& w : c->ws) {
-        if (hipStreamCreateWithPriority(&w.sb, hipStreamNonBlocking, prio_hi) != hipSuccess) return bail(fail(TK_RUNTIME_ERROR, "hipStreamCreate failed"));
+        if (hipStreamCreateWithFlags(&w.sb, hipStreamNonBlocking) != hipSuccess) return bail(fail(TK_RUNTIME_ERROR, "hipStreamCreate failed"));
         for (hipEvent_t* e : {&w.ev_front, &w.ev_cnt, &w.ev_tot, &w.ev_done, &w.ev_fork})
             if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) return bail(fail(TK_RUNTIME_ERROR, "hipEventCreate failed"));
         for (int i = 0; i < TK_NAUX; ++i)
@@ -368,7 +358,6 @@ extern "C" int tk_create(const uint8_t* ranks_blob, const uint64_t* ranks_off, c
         // the pattern's DFA (tk_regex_dfa.inc), where it has one: $TIKTOKEN_AMD_RX_MATCHER = program | dfa | flat (the default) chooses the
         // kernels' form -- "dfa" keeps the piece-by-piece speculative lane, "program" interprets the backtracking program as before
         const char* want = getenv("TIKTOKEN_AMD_RX_MATCHER");
-        if (const char* st = getenv("TIKTOKEN_AMD_RX_STAGED")) c->rx_staged = strcmp(st, "0") != 0;
         if (X.has_dfa() && !(want && !strcmp(want, "program"))) {
             std::vector<uint16_t> tr(X.dfa_trans);
             tr.resize((tr.size() + 1) & ~(size_t)1, 0);  // (whole 32-bit words: the kernels copy it to LDS word by word)
@@ -515,26 +504,13 @@ extern "C" int tk_create(const uint8_t* ranks_blob, const uint64_t* ranks_off, c
         if (v >= 4096 && v <= (3ull << 30)) c->chunk_bytes = v;
     }
     if (const char* e = getenv("TIKTOKEN_AMD_DEBUG")) c->dbg = atoi(e);
-    if (const char* e = getenv("TIKTOKEN_AMD_DEFER_SYNC")) c->defer_sync = atoi(e) != 0;  // (experiments: the host waits for the deferred tiles' counters in every chunk)
-    if (const char* e = getenv("TIKTOKEN_AMD_RX_AHEAD")) {  // (experiments: bytes a speculative match may look beyond its segment)
-        const int k = atoi(e);
-        if (k >= 16 && k <= (1 << 20)) c->rx_ahead = (uint32_t)k;
-    }
     if (const char* e = getenv("TIKTOKEN_AMD_RX_GRID_CAP")) {  // (tests: most workgroups of the staged speculative pass, so that a small input makes every workgroup take several stretches)
         const int k = atoi(e);
         if (k >= 1 && k <= 65536) c->rx_grid_cap = (uint32_t)k;
     }
-    if (const char* e = getenv("TIKTOKEN_AMD_RX_SEG_SHIFT")) {  // (experiments: segment size of the generic engine's speculative pass, 2^k bytes)
-        const int k = atoi(e);
-        if (k >= 5 && k <= 14) c->rx_seg_shift = (uint32_t)k;
-    }
     {
         int cu = 0;
         if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cu > 0) c->n_cu = (uint32_t)cu;
-        if (const char* e = getenv("TIKTOKEN_AMD_FRONT_WGS")) {
-            const int v = atoi(e);
-            if (v >= 1 && v <= 8) c->front_wgs = (uint32_t)v;
-        }
     }
     {
         // tk_k_front reads some of its arguments from the kernarg segment again, at offsets taken from TkFrontArgs (tk_fused.h, phases E and F): one launch
@@ -607,7 +583,6 @@ extern "C" void tk_destroy(tk_core* c) {
         if (c->stage[i]) (void)hipHostFree(c->stage[i]);
         if (c->ev_stage[i]) (void)hipEventDestroy(c->ev_stage[i]);
     }
-    if (c->ev_start) (void)hipEventDestroy(c->ev_start);
     delete c;
 }
 
@@ -669,14 +644,14 @@ static int rx_split(tk_core* c, WorkSet& w, hipStream_t s, const uint8_t* d_text
                     const uint64_t* d_doc_off, uint64_t n_docs, uint64_t base) {
     const uint64_t nwords = (n + 31) / 32;
     uint32_t* counters = w.counters.as<uint32_t>();
-    const uint32_t seg_shift = c->rx_seg_shift ? c->rx_seg_shift : (n < TK_RX_SEG_SMALL_BELOW ? TK_RX_SEG_SHIFT_SMALL : TK_RX_SEG_SHIFT_LARGE);
+    const uint32_t seg_shift = n < TK_RX_SEG_SMALL_BELOW ? TK_RX_SEG_SHIFT_SMALL : TK_RX_SEG_SHIFT_LARGE;
     const uint64_t nseg = (n + (1ull << seg_shift) - 1) >> seg_shift;
     TRY(ensure(w.rx_exit, 3 * (nseg + 2) * 4));  // exit of every segment's chain; where the link met it; where the link left the segment
     uint32_t *spec = w.rx_spec.as<uint32_t>(), *gst = w.rx_gst.as<uint32_t>(), *xexit = w.rx_exit.as<uint32_t>();
     uint32_t *lnk = w.rx_lnk.as<uint32_t>(), *lmerge = xexit + nseg + 2, *lexit = xexit + 2 * (nseg + 2);
     // (the kernels' form: the pattern's DFA in LDS -- its speculative pass as one loop -- or the backtracking program; tk_regex_kernels.h)
     const uint32_t lds = c->rx_form == TK_RX_FORM_PROGRAM ? 0u : tk_rx_dfa_lds_bytes(c->rx);
-    const uint32_t ahead = c->rx_ahead ? c->rx_ahead : (c->rx_form == TK_RX_FORM_PROGRAM ? TK_RX_AHEAD : TK_RX_AHEAD_DFA);
+    const uint32_t ahead = c->rx_form == TK_RX_FORM_PROGRAM ? TK_RX_AHEAD : TK_RX_AHEAD_DFA;
     auto by_form = [&](auto&& launch) {
         if (c->rx_form == TK_RX_FORM_DFA_FLAT) launch(std::integral_constant<int, TK_RX_FORM_DFA_FLAT>{});
         else if (c->rx_form == TK_RX_FORM_DFA) launch(std::integral_constant<int, TK_RX_FORM_DFA>{});
@@ -684,8 +659,9 @@ static int rx_split(tk_core* c, WorkSet& w, hipStream_t s, const uint8_t* d_text
         else if (c->rx_form == TK_RX_FORM_DFA_PREV) launch(std::integral_constant<int, TK_RX_FORM_DFA_PREV>{});
         else launch(std::integral_constant<int, TK_RX_FORM_PROGRAM>{});
     };
-    // (the pattern's DFA without look-behind over 128-byte segments: the lanes walk codes staged in LDS -- tk_k_rx_speculate_staged; $TIKTOKEN_AMD_RX_STAGED=0: the one-loop lanes over global memory)
-    const bool staged = c->rx_staged && c->rx_form == TK_RX_FORM_DFA_FLAT && seg_shift == TK_RX_SEG_SHIFT_SMALL && tk_rx_staged_fits(c->rx);
+    // (the pattern's DFA without look-behind over 128-byte segments: the lanes walk codes staged in LDS -- tk_k_rx_speculate_staged; otherwise
+    // the one-loop lanes over global memory)
+    const bool staged = c->rx_form == TK_RX_FORM_DFA_FLAT && seg_shift == TK_RX_SEG_SHIFT_SMALL && tk_rx_staged_fits(c->rx);
     TRY(timed(c, s, "tk_k_rx_speculate", [&] {
         if (staged)
             hipLaunchKernelGGL(tk_k_rx_speculate_staged, dim3(grid_for(nseg, TK_RX_STAGE_SEGS, c->rx_grid_cap)), dim3(TK_RX_STAGE_SEGS), tk_rx_staged_lds_bytes(c->rx), s, c->rx, d_text, (uint32_t)n, brk, ss,
@@ -696,24 +672,17 @@ static int rx_split(tk_core* c, WorkSet& w, hipStream_t s, const uint8_t* d_text
                                    ahead, spec, spec + nwords + 2, xexit);
             });
     }));
-    const bool links = !(c->dbg & TK_DBG_NO_LINKS);  // (without: the resolving pass matches its way from one chain to the next)
-    if (links) {
-        TRY(timed(c, s, "tk_k_rx_link", [&] {
-            by_form([&](auto form) {
-                hipLaunchKernelGGL(tk_k_rx_link<decltype(form)::value>, dim3(grid_for(nseg, 256, 65536)), dim3(256), lds, s, c->rx, d_text, (uint32_t)n, brk, ss, si, seg_shift,
-                                   ahead, spec, xexit, lnk, lnk + nwords + 2, lmerge, lexit);
-            });
-        }));
-    }
-    const TkRxMaps maps{spec, spec + nwords + 2, xexit, links ? lnk : (const uint32_t*)nullptr, lnk + nwords + 2, lmerge, lexit, seg_shift};
-    TRY(timed(c, s, "tk_k_rx_resolve", [&] {
+    TRY(timed(c, s, "tk_k_rx_link", [&] {
         by_form([&](auto form) {
-            if (c->dbg & TK_DBG_RX_LANE)  // (one lane per document instead of one wavefront)
-                hipLaunchKernelGGL(tk_k_rx_resolve<decltype(form)::value>, dim3(grid_for(n_docs, 256, 65536)), dim3(256), lds, s, c->rx, d_text, (uint32_t)n, brk, ss, si,
-                                   d_doc_off, n_docs, base, maps, gst, gst + nwords + 2, counters);
-            else
-                hipLaunchKernelGGL(tk_k_rx_resolve_wave<decltype(form)::value>, dim3(grid_for(n_docs, 4, 65536)), dim3(256), lds, s, c->rx, d_text, (uint32_t)n, brk, ss, si,
-                                   d_doc_off, n_docs, base, maps, gst, gst + nwords + 2, counters);
+            hipLaunchKernelGGL(tk_k_rx_link<decltype(form)::value>, dim3(grid_for(nseg, 256, 65536)), dim3(256), lds, s, c->rx, d_text, (uint32_t)n, brk, ss, si, seg_shift,
+                               ahead, spec, xexit, lnk, lnk + nwords + 2, lmerge, lexit);
+        });
+    }));
+    const TkRxMaps maps{spec, spec + nwords + 2, xexit, lnk, lnk + nwords + 2, lmerge, lexit, seg_shift};
+    TRY(timed(c, s, "tk_k_rx_resolve", [&] {  // (the wavefront form, tk_k_rx_resolve_wave: kernel times keep this name)
+        by_form([&](auto form) {
+            hipLaunchKernelGGL(tk_k_rx_resolve_wave<decltype(form)::value>, dim3(grid_for(n_docs, 4, 65536)), dim3(256), lds, s, c->rx, d_text, (uint32_t)n, brk, ss, si,
+                               d_doc_off, n_docs, base, maps, gst, gst + nwords + 2, counters);
         });
     }));
     TRY(timed(c, s, "tk_k_rx_merge", [&] { hipLaunchKernelGGL(tk_k_rx_merge, dim3(grid_for(nwords, 256, 4096)), dim3(256), 0, s, brk, gst, nwords); }));
@@ -740,7 +709,7 @@ static int stage_deferred(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s) 
     // segment's guess is taken -- splits the chunk under the same pat_str, its piece starts become hard starts, and the tiles that gave up
     // run again: every piece start is certain now.  (Pieces that are already final are what they were: a hard start at the start of a
     // piece changes nothing, and the stock patterns match a piece the same way when the text ends behind it.)
-    const bool can_fall_back = c->has_rx_fb && job.n >= (256u << 10) && !(c->dbg & TK_DBG_NO_FALL_BACK);
+    const bool can_fall_back = c->has_rx_fb && job.n >= (256u << 10);
     if (job.n > 0 && !job.single_piece) {
         TkFrontOut fo{w.starts.as<uint32_t>(), w.tile_np.as<uint32_t>(), w.res.as<uint32_t>(), w.tile_sum.as<uint8_t>(), miss_of(w, job), job.ovf_cap,
                       w.listC.as<uint32_t>(), w.counters.as<uint32_t>()};
@@ -749,7 +718,7 @@ static int stage_deferred(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s) 
         // least 64: they take their tiles from a counter).  On ordinary text no tile is deferred since round 6, and an empty grid of 768 such workgroups
         // -- 168 registers, 37 KiB of LDS, scratch -- costs 12.6 us against the 7 of 64.)
         const uint64_t defer_guess = ((job.ntiles * (uint64_t)c->defer_ppm) >> 20) * 5 / 4 + 64;
-        const bool sync_now = can_fall_back && (c->defer_sync || job.pretok);  // ($TIKTOKEN_AMD_DEFER_SYNC=1: from the start; the piece-offsets entry has no chunk_finish)
+        const bool sync_now = can_fall_back && (c->defer_sync || job.pretok);  // (the piece-offsets entry has no chunk_finish)
         job.optimistic = can_fall_back && !sync_now;
         uint64_t slow_wgs = 256u * TKF_SLOW_OCC;
         if (job.optimistic && defer_guess < slow_wgs) slow_wgs = defer_guess;
@@ -1447,27 +1416,28 @@ extern "C" int tk_encode_batch_device(tk_core* c, const void* d_utf8, uint64_t n
     return TK_OK;
 }
 
-// Host-buffer batches: the text goes to the device through two page-locked staging buffers (filled by a few host threads, sent by DMA on
-// a copy stream) while earlier chunks are being encoded, and every chunk's tokens start their way back to a page-locked result buffer on a
-// second copy stream while the next chunk is being encoded.  PCIe is the ceiling of this path (about 50 GB/s per direction).
-#define TK_STAGE_BYTES (64ull << 20)
-#define TK_HOST_CHUNK (128ull << 20)
+// Host-buffer batches: the text goes to the device by DMA on a copy stream, straight from the caller's buffer, while earlier chunks are
+// being encoded, and every chunk's tokens start their way back to a page-locked result buffer on a second copy stream while the next chunk
+// is being encoded.  PCIe is the ceiling of this path (about 50 GB/s per direction).
+#define TK_STAGE_BYTES (64ull << 20)  // a block of text on its way to the device; a staging buffer of tk_decode_batch
 
-static uint64_t host_chunk_bytes(bool direct) {  // ($TIKTOKEN_AMD_HOST_CHUNK_MIB: experiments)
-    if (const char* e = getenv("TIKTOKEN_AMD_HOST_CHUNK_MIB")) {
-        const long v = atol(e);
-        if (v >= 8 && v <= 2048) return (uint64_t)v << 20;
-    }
-    return direct ? (32ull << 20) : TK_HOST_CHUNK;
+// host threads of the staging copies (ids into / bytes and regrown results out of page-locked buffers): the copy, not the link, bounds
+// them (round 4: 8 threads, 25-34 GB/s of text; a GPU box gives the container 16 cores)
+static unsigned copy_threads(unsigned hw) { return hw == 0 ? 4u : (hw > 16u ? 16u : hw); }
+
+// the copy streams of the host-buffer entry points
+static int ensure_copy_streams(tk_core* c) {
+    for (hipStream_t* cs : {&c->cs_h2d, &c->cs_d2h})
+        if (!*cs) HIPCHK(hipStreamCreateWithFlags(cs, hipStreamNonBlocking));
+    return TK_OK;
 }
-// host threads of the staging copies (text into / ids out of the page-locked buffers): the copy, not the link, bounds the host-buffer
-// entries (round 4: 8 threads, 25-34 GB/s of text; a GPU box gives the container 16 cores); $TIKTOKEN_AMD_COPY_THREADS overrides
-static unsigned copy_threads(unsigned hw) {
-    if (const char* e = getenv("TIKTOKEN_AMD_COPY_THREADS")) {
-        const int v = atoi(e);
-        if (v >= 1 && v <= 64) return (unsigned)v;
-    }
-    return hw == 0 ? 4u : (hw > 16u ? 16u : hw);
+
+// offsets of a batch's documents: [0] is 0 and none is below the one before it (`name`: the argument's name in the message)
+static int check_offsets(const uint64_t* off, uint64_t n_docs, const char* name) {
+    if (off[0] != 0) return fail(TK_VALUE_ERROR, std::string(name) + "[0] must be 0");
+    for (uint64_t d = 0; d < n_docs; ++d)
+        if (off[d + 1] < off[d]) return fail(TK_VALUE_ERROR, std::string(name) + " must be non-decreasing");
+    return TK_OK;
 }
 static void parallel_memcpy(void* dst, const void* src, size_t n, unsigned nth) {
     if (n < (8u << 20) || nth <= 1) {
@@ -1750,9 +1720,7 @@ static int encode_batch_impl(tk_core* c, const uint8_t* utf8, const uint64_t* do
                              uint64_t* tok_off_out, bool device_result, bool no_small) {
     if (!c) return fail(TK_VALUE_ERROR, "core is null");
     if (!doc_off || (!device_result && !tokens_out) || !n_tokens_out) return fail(TK_VALUE_ERROR, "null argument");
-    if (doc_off[0] != 0) return fail(TK_VALUE_ERROR, "doc_off[0] must be 0");
-    for (uint64_t d = 0; d < n_docs; ++d)
-        if (doc_off[d + 1] < doc_off[d]) return fail(TK_VALUE_ERROR, "doc_off must be non-decreasing");
+    TRY(check_offsets(doc_off, n_docs, "doc_off"));
     const uint64_t n_bytes = doc_off[n_docs];
     if (!no_small && !device_result && n_docs == 1 && n_bytes > 0 && n_bytes <= (uint64_t)TK_SMALL_MAX * TK_MID_SEGMENTS && !(use_special && n_allowed) && !(c->dbg & TK_DBG_NO_SMALL) && !c->has_rx &&
         (n_bytes <= TK_SMALL_MAX || !c->profiling)) {
@@ -1799,23 +1767,13 @@ static int encode_batch_impl(tk_core* c, const uint8_t* utf8, const uint64_t* do
         return TK_OK;
     }
     // ---- pipelined
-    if (!c->cs_h2d) {
-        HIPCHK(hipStreamCreateWithFlags(&c->cs_h2d, hipStreamNonBlocking));
-        HIPCHK(hipStreamCreateWithFlags(&c->cs_d2h, hipStreamNonBlocking));
-        for (int i = 0; i < 2; ++i) {
-            HIPCHK(hipHostMalloc(&c->stage[i], TK_STAGE_BYTES, hipHostMallocPortable));
-            HIPCHK(hipEventCreateWithFlags(&c->ev_stage[i], hipEventDisableTiming));
-        }
-    }
+    TRY(ensure_copy_streams(c));
     // How the text gets to the device.  Round 6 measured the link on the bench's box (tools/ubench/pcie_rates.hip, profiles/r06_pcie_link.txt):
     // 57 GB/s either way alone, 48 GB/s each way with both directions busy -- and hipMemcpyAsync straight from PAGEABLE memory at 56.5 GB/s,
-    // the runtime's own staging.  So the default is that copy, in blocks of 64 MiB (smaller ones cost the copy its rate: 28 ms with 16 MiB), and
+    // the runtime's own staging.  So the text takes that copy, in blocks of 64 MiB (smaller ones cost the copy its rate: 28 ms with 16 MiB), and
     // chunks of 32 MiB: 25 ms per GiB = 0.88 of what the link gives in both directions at once, where the staging buffers of rounds 2-5
-    // (filled by host threads, 64 MiB at a time, chunks of 128 MiB) took 32 ms.  $TIKTOKEN_AMD_H2D_DIRECT=0 brings those back.
-    const bool h2d_direct = !(getenv("TIKTOKEN_AMD_H2D_DIRECT") && atoi(getenv("TIKTOKEN_AMD_H2D_DIRECT")) == 0);
-    uint64_t block_bytes = TK_STAGE_BYTES;
-    if (const char* e = getenv("TIKTOKEN_AMD_H2D_BLOCK_MIB"))  // (experiments; the staging buffers bound it)
-        if (h2d_direct && atol(e) >= 4 && atol(e) <= 1024) block_bytes = (uint64_t)atol(e) << 20;
+    // (filled by host threads, 64 MiB at a time, chunks of 128 MiB) took 32 ms.
+    const uint64_t block_bytes = TK_STAGE_BYTES;
     const uint64_t n_blocks = (n_bytes + block_bytes - 1) / block_bytes;
     std::vector<hipEvent_t> ev_block(n_blocks, nullptr);
     for (auto& e : ev_block) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -1823,30 +1781,21 @@ static int encode_batch_impl(tk_core* c, const uint8_t* utf8, const uint64_t* do
         for (auto e : ev_block)
             if (e) (void)hipEventDestroy(e);
     };
-    // producer: stage + send the text, block by block
+    // producer: send the text, block by block
     std::atomic<int> h2d_rc{TK_OK};
     std::atomic<uint64_t> blocks_sent{0};
     const int dev = c->device;
-    unsigned nth = std::thread::hardware_concurrency();
-    nth = copy_threads(nth);
     std::thread producer([&]() {
         (void)hipSetDevice(dev);
         for (uint64_t b = 0; b < n_blocks; ++b) {
-            const int slot = (int)(b & 1);
             const uint64_t a = b * block_bytes, len = a + block_bytes < n_bytes ? block_bytes : n_bytes - a;
-            if (h2d_direct) {  // (the runtime's own way from pageable memory: measured at the link's rate on this platform, tools/ubench/pcie_rates.hip)
-                if (hipMemcpyAsync((uint8_t*)c->text.p + a, utf8 + a, len, hipMemcpyHostToDevice, c->cs_h2d) != hipSuccess) h2d_rc = TK_RUNTIME_ERROR;
-            } else {
-                if (b >= 2 && hipEventSynchronize(c->ev_stage[slot]) != hipSuccess) h2d_rc = TK_RUNTIME_ERROR;  // the slot's previous DMA is done
-                parallel_memcpy(c->stage[slot], utf8 + a, len, nth);
-                if (hipMemcpyAsync((uint8_t*)c->text.p + a, c->stage[slot], len, hipMemcpyHostToDevice, c->cs_h2d) != hipSuccess) h2d_rc = TK_RUNTIME_ERROR;
-            }
-            (void)hipEventRecord(c->ev_stage[slot], c->cs_h2d);
+            if (hipMemcpyAsync((uint8_t*)c->text.p + a, utf8 + a, len, hipMemcpyHostToDevice, c->cs_h2d) != hipSuccess) h2d_rc = TK_RUNTIME_ERROR;
             (void)hipEventRecord(ev_block[b], c->cs_h2d);
             blocks_sent.store(b + 1, std::memory_order_release);
         }
     });
     // consumer side
+    const unsigned nth = copy_threads(std::thread::hardware_concurrency());  // (a result buffer regrown: the ids so far copied over)
     uint32_t* host = nullptr;
     uint64_t host_cap = 0;  // tokens
     ChunkHooks hooks;
@@ -1877,7 +1826,7 @@ static int encode_batch_impl(tk_core* c, const uint8_t* utf8, const uint64_t* do
         return TK_OK;
     };
     int rc = encode_device_locked(c, s, c->text.as<uint8_t>(), n_bytes, c->doc_off.as<uint64_t>(), doc_off, n_docs, use_special && any, &total,
-                                  host_chunk_bytes(h2d_direct), &hooks);
+                                  32ull << 20, &hooks);
     producer.join();
     hipError_t e = hipStreamSynchronize(c->cs_h2d);
     if (e == hipSuccess) e = hipStreamSynchronize(c->cs_d2h);
@@ -1911,9 +1860,7 @@ extern "C" int tk_pretokenize_batch(tk_core* c, const uint8_t* utf8, const uint6
                                     const uint32_t* allowed_ids, uint64_t n_allowed, uint32_t** starts_out, uint64_t* n_out) {
     if (!c) return fail(TK_VALUE_ERROR, "core is null");
     if (!doc_off || !starts_out || !n_out) return fail(TK_VALUE_ERROR, "null argument");
-    if (doc_off[0] != 0) return fail(TK_VALUE_ERROR, "doc_off[0] must be 0");
-    for (uint64_t d = 0; d < n_docs; ++d)
-        if (doc_off[d + 1] < doc_off[d]) return fail(TK_VALUE_ERROR, "doc_off must be non-decreasing");
+    TRY(check_offsets(doc_off, n_docs, "doc_off"));
     const uint64_t n_bytes = doc_off[n_docs];
     if (n_bytes > c->chunk_bytes) return fail(TK_VALUE_ERROR, "tk_pretokenize_batch handles a single chunk only");
     if (n_bytes >= (1ull << 31)) return fail(TK_VALUE_ERROR, "tk_pretokenize_batch: less than 2 GiB per call (bit 31 of an offset marks a gap char)");
@@ -2120,9 +2067,7 @@ extern "C" int tk_decode_batch(tk_core* c, const uint32_t* tokens, const uint64_
                                uint64_t* n_bytes_out, uint64_t* byte_off_out) {
     if (!c) return fail(TK_VALUE_ERROR, "core is null");
     if (!tok_off || !bytes_out || !n_bytes_out) return fail(TK_VALUE_ERROR, "null argument");
-    if (tok_off[0] != 0) return fail(TK_VALUE_ERROR, "tok_off[0] must be 0");
-    for (uint64_t d = 0; d < n_docs; ++d)
-        if (tok_off[d + 1] < tok_off[d]) return fail(TK_VALUE_ERROR, "tok_off must be non-decreasing");
+    TRY(check_offsets(tok_off, n_docs, "tok_off"));
     if (!c->n_dec) return fail(TK_UNSUPPORTED, "token ids are too sparse for the device decode table");
     const uint64_t n = tok_off[n_docs];
     std::lock_guard<std::mutex> lk(c->mu);
@@ -2138,13 +2083,10 @@ extern "C" int tk_decode_batch(tk_core* c, const uint32_t* tokens, const uint64_
     TRY(ensure(c->d_boff, (n_docs + 2) * 8 * 2));
     unsigned long long* tots = c->d_bsum.as<unsigned long long>() + nb + 2;  // per range {bytes, first invalid position}; [0 .. 1] also the batch's
     unsigned long long* d_tboff = byte_off_out ? c->d_tboff.as<unsigned long long>() : nullptr;
-    if (!c->cs_h2d) {
-        HIPCHK(hipStreamCreateWithFlags(&c->cs_h2d, hipStreamNonBlocking));
-        HIPCHK(hipStreamCreateWithFlags(&c->cs_d2h, hipStreamNonBlocking));
-        for (int i = 0; i < 2; ++i) {
-            HIPCHK(hipHostMalloc(&c->stage[i], TK_STAGE_BYTES, hipHostMallocPortable));
-            HIPCHK(hipEventCreateWithFlags(&c->ev_stage[i], hipEventDisableTiming));
-        }
+    TRY(ensure_copy_streams(c));
+    for (int i = 0; i < 2; ++i) {  // the staging buffers (this entry's own: the text of tk_encode_batch goes straight from the caller's buffer)
+        if (!c->stage[i]) HIPCHK(hipHostMalloc(&c->stage[i], TK_STAGE_BYTES, hipHostMallocPortable));
+        if (!c->ev_stage[i]) HIPCHK(hipEventCreateWithFlags(&c->ev_stage[i], hipEventDisableTiming));
     }
     // is the caller's buffer page-locked (then the DMA engine reads it directly)?
     bool src_pinned = false;
@@ -2166,8 +2108,7 @@ extern "C" int tk_decode_batch(tk_core* c, const uint32_t* tokens, const uint64_
     std::atomic<int> h2d_rc{TK_OK};
     std::atomic<uint64_t> sent{0};
     const int dev = c->device;
-    unsigned nth = std::thread::hardware_concurrency();
-    nth = copy_threads(nth);
+    const unsigned nth = copy_threads(std::thread::hardware_concurrency());
     std::thread producer([&]() {
         (void)hipSetDevice(dev);
         for (uint64_t k = 0; k < n_ranges; ++k) {
@@ -2398,9 +2339,7 @@ static int group_encode(tk_group* g, const uint8_t* utf8, const uint64_t* doc_of
                         uint64_t n_allowed, std::vector<ShardResult>& res, std::vector<uint64_t>& first, bool on_device) {
     if (!g) return fail(TK_VALUE_ERROR, "group is null");
     if (!doc_off) return fail(TK_VALUE_ERROR, "null argument");
-    if (doc_off[0] != 0) return fail(TK_VALUE_ERROR, "doc_off[0] must be 0");
-    for (uint64_t d = 0; d < n_docs; ++d)
-        if (doc_off[d + 1] < doc_off[d]) return fail(TK_VALUE_ERROR, "doc_off must be non-decreasing");
+    TRY(check_offsets(doc_off, n_docs, "doc_off"));
     const uint32_t R = (uint32_t)g->cores.size();
     first = partition_by_bytes(doc_off, n_docs, R);
     res.assign(R, ShardResult());
@@ -2711,7 +2650,7 @@ extern "C" void tk_last_stats(tk_core* c, uint64_t* n_bytes, uint64_t* n_pieces,
 extern "C" uint64_t tk_stat(tk_core* c, const char* name) {
     if (!c || !name) return 0;
     const std::string k(name);
-    if (k == "front_wgs_per_cu") return c->front_wgs;
+    if (k == "front_wgs_per_cu") return TKF_OCC;  // (workgroups per CU of the persistent front kernel: a compile-time constant)
     if (k == "compute_units") return c->n_cu;
     if (k == "chunks") return c->st_chunks;
     if (k == "small_launches") return c->st_small_launches;  // launches of tk_k_small and the calls they carried (several callers share a launch)

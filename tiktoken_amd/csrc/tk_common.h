@@ -48,12 +48,9 @@ enum : int {
     TK_DBG_STOP_D = 0x8000,            // ... after phase D
     TK_DBG_STOP_E = 0x10000,           // ... after phase E
     TK_DBG_STOPS = 0x1F000,            // any of the five
-    TK_DBG_NO_LINKS = 0x20000,         // host: no link pass of the generic engine (the resolving pass matches from one chain to the next)
-    TK_DBG_RX_LANE = 0x40000,          // host: the generic engine's resolving pass by one lane per document instead of one wavefront
     TK_DBG_ONE_MERGE_STEP = 0x80000,   // tk_k_merge_all: one merge per step instead of two
     TK_DBG_GENERIC = 0x100000,         // the split pattern through the generic engine even where a hand-written scanner exists (tk_tables.cpp)
     TK_DBG_NO_MID_CUT = 0x200000,      // host: never cut a mid-size call into segments (encode_mid)
-    TK_DBG_NO_FALL_BACK = 0x400000,    // host: no fall-back to the generic engine for tiles that gave up their walk
     TK_DBG_MERGE_PER_BIN = 0x800000,   // host: a merge kernel per length bin instead of tk_k_merge_all
     TK_DBG_MERGE_NO_PROBES = 0x1000000,  // tk_k_merge_all: no probes (perf experiments: the cost of everything else)
     TK_DBG_MERGE_BIN_SHIFT = 25,       // tk_k_merge_all: a field of 4 bits -- nonzero: merge only the pieces of length bin (field - 1) (timing only)
@@ -69,8 +66,7 @@ enum : int {
 // the bits a user sets: one bit each, none shared with another, with the merge-bin field or with the internal flags
 constexpr int TK_DBG_USER[] = {TK_DBG_PROBE_LEN, TK_DBG_SCANNERS, TK_DBG_STARTS_ONLY, TK_DBG_VERBOSE, TK_DBG_KEEP_LONG, TK_DBG_NO_MT, TK_DBG_COLLIDE,
                                TK_DBG_ONE_MERGE, TK_DBG_NO_SMALL, TK_DBG_STOP_A, TK_DBG_STOP_B, TK_DBG_STOP_C, TK_DBG_STOP_D, TK_DBG_STOP_E,
-                               TK_DBG_NO_LINKS, TK_DBG_RX_LANE, TK_DBG_ONE_MERGE_STEP, TK_DBG_GENERIC, TK_DBG_NO_MID_CUT, TK_DBG_NO_FALL_BACK,
-                               TK_DBG_MERGE_PER_BIN, TK_DBG_MERGE_NO_PROBES, TK_DBG_NO_BUDGET};
+                               TK_DBG_ONE_MERGE_STEP, TK_DBG_GENERIC, TK_DBG_NO_MID_CUT, TK_DBG_MERGE_PER_BIN, TK_DBG_MERGE_NO_PROBES, TK_DBG_NO_BUDGET};
 constexpr bool tk_dbg_user_bits_disjoint() {
     int seen = (TK_DBG_MERGE_BIN_MASK << TK_DBG_MERGE_BIN_SHIFT) | TK_DBG_INTERNAL;
     for (int b : TK_DBG_USER) {

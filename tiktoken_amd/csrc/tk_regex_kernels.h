@@ -5,8 +5,7 @@
 //   tk_k_rx_link      : one lane per segment walks from where the segment before it was left (as guessed) until it meets its own segment's
 //                       chain: with these links a segment is taken whole wherever the guesses were right;
 //   tk_k_rx_resolve_wave : one wavefront per document walks the true chain, 64 segments per step wherever the plans of its lanes hold, one
-//                       match where they do not (exact: a match depends only on the text around it) -> bitmap `gst` of true piece starts
-//                       (tk_k_rx_resolve: the same by one lane per document);
+//                       match where they do not (exact: a match depends only on the text around it) -> bitmap `gst` of true piece starts;
 //   (gap chars -- positions at which the pattern matches nothing: find_iter skips them -- are pieces of their own, marked in `sgap` / `ggap`:
 //    the front kernel gives them no token)
 //   tk_k_rx_merge     : brk |= gst.  From here on every piece start is a "hard" start for the front kernel, which runs with a class table
@@ -185,31 +184,6 @@ __global__ __launch_bounds__(256) void tk_k_rx_link(TkRxDev R, const uint8_t* __
     t.ahead = ahead;
     for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < nseg; k += gridDim.x * blockDim.x)
         tk_rx_link_lane<tk_rx_matcher_of(FORM)>(P, t, k, seg_shift, spec, xexit, lnk, lgap, lmerge, lexit);
-}
-
-// one lane per document (TK_DBG_RX_LANE; the CPU tests run this form lane by lane)
-template <int FORM>
-__global__ __launch_bounds__(256) void tk_k_rx_resolve(TkRxDev R, const uint8_t* __restrict__ text, uint32_t n, const uint32_t* __restrict__ brk,
-                                                       const uint32_t* __restrict__ ss, const uint32_t* __restrict__ si,
-                                                       const uint64_t* __restrict__ doc_off, uint64_t n_docs, uint64_t base, TkRxMaps M,
-                                                       uint32_t* __restrict__ gst, uint32_t* __restrict__ ggap, uint32_t* __restrict__ counters) {
-    TK_RX_STAGE(P, R)
-    const TkRxText t{text, n, brk, ss, si, 0xFFFFFFFFu, false};
-    for (uint64_t d = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; d < n_docs; d += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t b = doc_off[d] - base, e = doc_off[d + 1] - base;
-        if (b >= e || e > n) continue;
-        uint32_t err_pos = 0;
-        const uint32_t err = tk_rx_resolve_lane<tk_rx_matcher_of(FORM)>(P, t, M, (uint32_t)b, (uint32_t)e,
-                                                [&](uint32_t w, uint32_t bits, uint32_t gaps) {
-                                                    if (bits) atomicOr(&gst[w], bits);
-                                                    if (gaps) atomicOr(&ggap[w], gaps);
-                                                },
-                                                &err_pos);
-        if (err) {
-            atomicOr(&counters[TK_CNT_ERR], err);
-            atomicMax(&counters[TK_CNT_RXPOS], ~err_pos);  // (the counters start at zero: the smallest position wins)
-        }
-    }
 }
 
 // One WAVEFRONT per document (tk_rx_resolve_group_host is the same, lane after lane): lane j plans segment k0 + j as if the chain entered

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Kernel experiments on the GPU box: one configuration of the library (selected through $TIKTOKEN_AMD_LIB / $TIKTOKEN_AMD_FRONT_WGS /
-$TIKTOKEN_AMD_DEBUG) on the bench corpus; prints one JSON line with wall time per step, per-kernel HIP-event times and whether EVERY token equals the oracle's (computed once per box and kept in /tmp).
+"""Kernel experiments on the GPU box: one configuration of the library (selected through $TIKTOKEN_AMD_LIB / $TIKTOKEN_AMD_DEBUG)
+on the bench corpus; prints one JSON line with wall time per step, per-kernel HIP-event times and whether EVERY token equals the oracle's (computed once per box and kept in /tmp).
 
     python tools/exp_front.py --tag NAME [--mib 1024] [--steps 3]
 """
