@@ -503,7 +503,13 @@ extern "C" int tk_create(const uint8_t* ranks_blob, const uint64_t* ranks_off, c
         uint64_t v = strtoull(e, nullptr, 10);
         if (v >= 4096 && v <= (3ull << 30)) c->chunk_bytes = v;
     }
-    if (const char* e = getenv("TIKTOKEN_AMD_DEBUG")) c->dbg = atoi(e);
+    if (const char* e = getenv("TIKTOKEN_AMD_DEBUG")) {
+        c->dbg = atoi(e);
+        int unknown = c->dbg;
+        for (int b : TK_DBG_USER) unknown &= ~b;
+        if (unknown)  // (the phase stops and merge hooks of earlier rounds are compile-time parameters now: tools/build_variant.sh)
+            fprintf(stderr, "tiktoken_amd: TIKTOKEN_AMD_DEBUG: 0x%x holds no debug bits (ignored)\n", (unsigned)unknown);
+    }
     if (const char* e = getenv("TIKTOKEN_AMD_RX_GRID_CAP")) {  // (tests: most workgroups of the staged speculative pass, so that a small input makes every workgroup take several stretches)
         const int k = atoi(e);
         if (k >= 1 && k <= 65536) c->rx_grid_cap = (uint32_t)k;
@@ -761,7 +767,7 @@ static int stage_deferred(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s) 
             }
             n_given = w.h_counters[TK_CNT_DEFER];
         }
-        if (n_given && !(c->dbg & TK_DBG_STOPS)) {  // (the kernels stop after a phase: there are no starts to go on from)
+        if (n_given && TKF_STOP_AFTER == 0) {  // (TKF_STOP_AFTER: the kernels stop after a phase, there are no starts to go on from)
             TRY(timed(c, s, "tk_k_front_given", [&] {
                 launch_front<TKF_MODE_GIVEN>(pat_id, job.spec, dim3((uint32_t)n_given), s, T, job.d_text, job.n, job.base, w.brk.as<uint32_t>(), docb, ss, si, fo, mt_arg,
                                     (1u << job.mt_bits) - 1u, w.deferred.as<uint32_t>(), gapb, fdbg);
@@ -955,9 +961,9 @@ static int stage_back(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, uint
     const unsigned long long* tok_base = c->tok_bases.as<unsigned long long>() + job.index;
     uint64_t nC = 0;
     TRY(stage_deferred(c, w, job, s));
-    // (perf experiments, tools/gpu_phases.sh: TK_DBG_STOPS -- the front kernel stops after one of its phases -- its outputs are
-    // incomplete, so nothing behind it runs: the call returns zero tokens and offsets that mean nothing)
-    const bool front_only = (c->dbg & TK_DBG_STOPS) != 0;
+    // (perf experiments, tools/gpu_phases.sh: a build with TKF_STOP_AFTER -- the front kernel stops after one of its phases -- its outputs
+    // are incomplete, so nothing behind it runs: the call returns zero tokens and offsets that mean nothing)
+    constexpr bool front_only = TKF_STOP_AFTER != 0;
     if (front_only) {
         HIPCHK(hipMemsetAsync(w.total.p, 0, 32, s));
         if (prev_tot) HIPCHK(hipStreamWaitEvent(s, prev_tot, 0));
@@ -990,7 +996,7 @@ static int stage_back(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, uint
             uint32_t wgs = (uint32_t)std::min<uint64_t>((most_units + TKM_WAVES - 1) / TKM_WAVES, (uint64_t)c->n_cu * TKM_WGS_PER_CU);
             wgs = std::max(16u / TKM_WAVES, (wgs + 16u / TKM_WAVES - 1u) / (16u / TKM_WAVES) * (16u / TKM_WAVES));  // (wavefronts: a multiple of 16, tk_k_merge_all's work counters rely on it)
             TRY(timed(c, s, "tk_k_merge_all", [&] {
-                hipLaunchKernelGGL(tk_k_merge_all, dim3(wgs), dim3(64 * TKM_WAVES), TKM_LDS_BYTES, s, T, d_text, listB, counters, data, stg, w.merge_work.as<uint32_t>(), c->dbg);
+                hipLaunchKernelGGL(tk_k_merge_all, dim3(wgs), dim3(64 * TKM_WAVES), TKM_LDS_BYTES, s, T, d_text, listB, counters, data, stg, w.merge_work.as<uint32_t>());
             }));
         } else
         {

@@ -30,9 +30,9 @@
 #define TK_RANK_MAX 0xFFFFFFFFu
 
 // The debug word: $TIKTOKEN_AMD_DEBUG, an int read at tk_create (tests and experiments only; wrong tokens where a bit says so), and the flags the host
-// adds to it for the front kernel's launches.  Every expression on it stays in `int`.
+// adds to it for the front kernel's launches.  Every expression on it stays in `int`.  (Hooks that only time a part of a kernel are compile-time
+// parameters, not bits: TKF_STOP_AFTER, TKF_PROBE_LEN, TKM_* in tk_fused.h.)
 enum : int {
-    TK_DBG_PROBE_LEN = 2,              // front kernel: every probe counts as a hit, its result word is the piece's length (perf experiments)
     TK_DBG_SCANNERS = 4,               // the front kernel's scanners run even where the generic engine has split the chunk (no TK_DBG_HARD_ONLY)
     TK_DBG_STARTS_ONLY = 8,            // front kernel: piece starts only -- every probe counts as a hit, nothing is listed for the merges (the host
                                        // sets it for the piece-offsets entry as well)
@@ -42,33 +42,21 @@ enum : int {
     TK_DBG_COLLIDE = 512,              // the in-call table's keys cut to 12 bits: collisions between different pieces (tests)
     TK_DBG_ONE_MERGE = 1024,           // host: one merge at a time for every long piece
     TK_DBG_NO_SMALL = 2048,            // host: never the one-launch path of small calls
-    TK_DBG_STOP_A = 0x1000,            // front kernel: stop after phase A (perf experiments: nothing behind the front kernel runs) ...
-    TK_DBG_STOP_B = 0x2000,            // ... after phase B (the classification)
-    TK_DBG_STOP_C = 0x4000,            // ... after phase C
-    TK_DBG_STOP_D = 0x8000,            // ... after phase D
-    TK_DBG_STOP_E = 0x10000,           // ... after phase E
-    TK_DBG_STOPS = 0x1F000,            // any of the five
-    TK_DBG_ONE_MERGE_STEP = 0x80000,   // tk_k_merge_all: one merge per step instead of two
     TK_DBG_GENERIC = 0x100000,         // the split pattern through the generic engine even where a hand-written scanner exists (tk_tables.cpp)
     TK_DBG_NO_MID_CUT = 0x200000,      // host: never cut a mid-size call into segments (encode_mid)
     TK_DBG_MERGE_PER_BIN = 0x800000,   // host: a merge kernel per length bin instead of tk_k_merge_all
-    TK_DBG_MERGE_NO_PROBES = 0x1000000,  // tk_k_merge_all: no probes (perf experiments: the cost of everything else)
-    TK_DBG_MERGE_BIN_SHIFT = 25,       // tk_k_merge_all: a field of 4 bits -- nonzero: merge only the pieces of length bin (field - 1) (timing only)
-    TK_DBG_MERGE_BIN_MASK = 15,
     TK_DBG_NO_BUDGET = 0x20000000,     // front kernel: a walk budget of zero windows (TKF_WALK_BUDGET; tests: ordinary corpora through that path)
-    // set by the host for the front kernel's launches only, cleared from what the user set (they share bits with the merge-bin field, which only
-    // tk_k_merge_all reads)
+    // set by the host for the front kernel's launches only, cleared from what the user set
     TK_DBG_MAY_GIVE_UP = 0x8000000,    // a deferred tile may give up its walk (there is a fall-back pass)
     TK_DBG_SECOND = 0x10000000,        // the deferred-tile instance runs over the list of the tiles that gave up
     TK_DBG_HARD_ONLY = 0x40000000,     // every piece start is a hard start (the generic engine has split the chunk)
     TK_DBG_INTERNAL = TK_DBG_MAY_GIVE_UP | TK_DBG_SECOND | TK_DBG_HARD_ONLY,
 };
-// the bits a user sets: one bit each, none shared with another, with the merge-bin field or with the internal flags
-constexpr int TK_DBG_USER[] = {TK_DBG_PROBE_LEN, TK_DBG_SCANNERS, TK_DBG_STARTS_ONLY, TK_DBG_VERBOSE, TK_DBG_KEEP_LONG, TK_DBG_NO_MT, TK_DBG_COLLIDE,
-                               TK_DBG_ONE_MERGE, TK_DBG_NO_SMALL, TK_DBG_STOP_A, TK_DBG_STOP_B, TK_DBG_STOP_C, TK_DBG_STOP_D, TK_DBG_STOP_E,
-                               TK_DBG_ONE_MERGE_STEP, TK_DBG_GENERIC, TK_DBG_NO_MID_CUT, TK_DBG_MERGE_PER_BIN, TK_DBG_MERGE_NO_PROBES, TK_DBG_NO_BUDGET};
+// the bits a user sets: one bit each, none shared with another or with the internal flags (tk_create names on stderr any other bit it is given)
+constexpr int TK_DBG_USER[] = {TK_DBG_SCANNERS, TK_DBG_STARTS_ONLY, TK_DBG_VERBOSE, TK_DBG_KEEP_LONG, TK_DBG_NO_MT, TK_DBG_COLLIDE, TK_DBG_ONE_MERGE,
+                               TK_DBG_NO_SMALL, TK_DBG_GENERIC, TK_DBG_NO_MID_CUT, TK_DBG_MERGE_PER_BIN, TK_DBG_NO_BUDGET};
 constexpr bool tk_dbg_user_bits_disjoint() {
-    int seen = (TK_DBG_MERGE_BIN_MASK << TK_DBG_MERGE_BIN_SHIFT) | TK_DBG_INTERNAL;
+    int seen = TK_DBG_INTERNAL;
     for (int b : TK_DBG_USER) {
         if ((b & (b - 1)) != 0 || (seen & b) != 0) return false;
         seen |= b;
@@ -76,7 +64,6 @@ constexpr bool tk_dbg_user_bits_disjoint() {
     return true;
 }
 static_assert(tk_dbg_user_bits_disjoint(), "a debug bit a user sets is shared");
-static_assert(TK_DBG_STOPS == (TK_DBG_STOP_A | TK_DBG_STOP_B | TK_DBG_STOP_C | TK_DBG_STOP_D | TK_DBG_STOP_E), "the phase stops");
 
 enum { TK_PAT_R50K = 0, TK_PAT_CL100K = 1, TK_PAT_O200K = 2 };
 

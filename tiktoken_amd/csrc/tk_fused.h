@@ -606,6 +606,13 @@ __device__ __forceinline__ bool tk_equal_lds_text(const uint8_t* raw, uint32_t o
 #ifndef TKF_CLAIM_SPIN
 #define TKF_CLAIM_SPIN 8  // looks a duplicate takes at a slot whose claimant has not written its words yet (see `claim`)
 #endif
+// Experiments only (builds of their own, tools/build_variant.sh and tools/gpu_phases.sh; the shipped library has none of it):
+#ifndef TKF_STOP_AFTER
+#define TKF_STOP_AFTER 0  // 1 .. 5: the kernel stops after phase A .. E, and nothing behind it runs (tk_api.hip, stage_back `front_only`)
+#endif
+#ifndef TKF_PROBE_LEN
+#define TKF_PROBE_LEN 0  // 1: every probe of phase F counts as a hit without a table access, its result word is the piece's length
+#endif
 // Experiments only (-DTKF_TIMING, tools/build_variant.sh): where a workgroup's time per tile goes.  Thread 0 reads the shader clock at the phase
 // boundaries of the one-tile-per-workgroup instance and adds the differences up in tk_time_acc (read and reset through tk_stat "time_<i>" /
 // "time_reset"); slot 15 counts the tiles.
@@ -844,7 +851,7 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
     if (tid < 4) planes[tid][TK2_NSEG] = planes[tid][TK2_NSEG + 1] = tid >= 2 ? ~0ull : 0ull;  // (class END)
     __syncthreads();
     TKT(0);
-    if (dbg & TK_DBG_STOP_A) {  // (perf experiments: stop after this phase)
+    if constexpr (TKF_STOP_AFTER == 1) {  // (perf experiments: stop after this phase)
         if (tid == 0) out.tile_np[tile] = 0;
         continue;
     }
@@ -1000,7 +1007,7 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
         if (!decoded) tk_chunk_decode(ch, prev, tid > 0, get4, cls_of);
     }
     TKT(1);
-    if (dbg & TK_DBG_STOP_B) {  // (perf experiments: stop after the classification)
+    if constexpr (TKF_STOP_AFTER == 2) {  // (perf experiments: stop after the classification)
         if (tid == 0 || (ch.acc0 ^ ch.acc1) == 0xFFFFFFF1u) out.tile_np[tile] = 0;
         continue;
     }
@@ -1159,7 +1166,7 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
         continue;
     }
     TKT(2);
-    if (dbg & TK_DBG_STOP_C) {  // (perf experiments: stop after this phase)
+    if constexpr (TKF_STOP_AFTER == 3) {  // (perf experiments: stop after this phase)
         if (tid == 0) out.tile_np[tile] = 0;
         continue;
     }
@@ -1461,7 +1468,7 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
     }
     }
     TKT(3);
-    if (dbg & TK_DBG_STOP_D) {  // (perf experiments: stop after this phase)
+    if constexpr (TKF_STOP_AFTER == 4) {  // (perf experiments: stop after this phase)
         if (tid == 0) out.tile_np[tile] = 0;
         continue;
     }
@@ -1571,7 +1578,7 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
     }
     __syncthreads();
     TKT(4);
-    if (dbg & TK_DBG_STOP_E) {  // (perf experiments: stop after this phase)
+    if constexpr (TKF_STOP_AFTER == 5) {  // (perf experiments: stop after this phase)
         if (tid == 0) out.tile_np[tile] = 0;
         continue;
     }
@@ -1783,8 +1790,8 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
                         const uint32_t e_loc = (e >> 24) == 3u ? far_end(pos) : pos + near_len(pos);
                         len = e_loc - pos;
                         gs = (uint64_t)(base + pos);
-                        if (dbg & (TK_DBG_PROBE_LEN | TK_DBG_STARTS_ONLY)) {  // (perf experiments / piece starts only: every probe counts as a hit -- only the longest pieces get here)
-                            out.res[run_base + k] = (dbg & TK_DBG_PROBE_LEN) ? len : 0u;
+                        if (TKF_PROBE_LEN || (dbg & TK_DBG_STARTS_ONLY)) {  // (TKF_PROBE_LEN / piece starts only: every probe counts as a hit -- only the longest pieces get here)
+                            out.res[run_base + k] = TKF_PROBE_LEN ? len : 0u;
                         } else {
                             fail = true;
                             if (use_mt && len <= TK_GLANE_MAX) {
@@ -1845,7 +1852,7 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
                     const uint32_t len = near_len(pos);
                     const bool in_lds = pos + len + 8u <= (uint32_t)TK2_WIN;
                     uint32_t rk = len;
-                    if (!(dbg & TK_DBG_PROBE_LEN)) {
+                    if (!TKF_PROBE_LEN) {
                         const uint64_t gs = (uint64_t)(base + pos);
                         uint64_t w0, w1, w2;
                         tk_ident([&](uint32_t o) { return in_lds ? tk_lds_load8(raw, pos + o) : tk_load8(text, gs + o); }, len, 0u, w0, w1, w2);
@@ -1864,7 +1871,7 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
                     const uint32_t pos = ord_m[q], k = ordk_m[q];
                     const uint32_t len = near_len(pos);
                     const uint64_t key_m = tk_mask_low_bytes(tk_lds_load8(raw, pos), len);
-                    const uint32_t rk = (dbg & TK_DBG_PROBE_LEN) ? len : tk_probe_mid(Tr, key_m, len);
+                    const uint32_t rk = TKF_PROBE_LEN ? len : tk_probe_mid(Tr, key_m, len);
                     if (rk != TK_RANK_MAX || (dbg & TK_DBG_STARTS_ONLY)) out.res[run_base + k] = rk == TK_RANK_MAX ? 0u : rk;
                     else {
                         miss = true;
@@ -1879,7 +1886,7 @@ __global__ __launch_bounds__(256, MODE == TKF_MODE_STARTS ? TKF_SLOW_OCC : (MODE
                     const uint32_t len = near_len(pos);
                     const uint32_t v = __builtin_amdgcn_alignbyte(dwr[(pos >> 2) + 1], dwr[pos >> 2], pos & 3u);
                     const uint32_t key_s = v & (0xFFFFFFFFu >> (32u - 8u * len));
-                    const uint32_t rk = (dbg & TK_DBG_PROBE_LEN) ? len : (short_tab ? tk_probe_short(Tr, key_s, len) : tk_probe_mid(Tr, (uint64_t)key_s, len));
+                    const uint32_t rk = TKF_PROBE_LEN ? len : (short_tab ? tk_probe_short(Tr, key_s, len) : tk_probe_mid(Tr, (uint64_t)key_s, len));
                     if (rk != TK_RANK_MAX || (dbg & TK_DBG_STARTS_ONLY)) out.res[run_base + k] = rk == TK_RANK_MAX ? 0u : rk;
                     else {
                         miss = true;
@@ -2349,10 +2356,20 @@ __device__ __forceinline__ void tkm_probe2(const TkTables& T, uint32_t a0, uint3
 #ifndef TKM_MIN_WAVES_EU
 #define TKM_MIN_WAVES_EU 4  // (the second launch bound is wavefronts per SIMD in HIP)
 #endif
+// Experiments only (builds of their own, tools/build_variant.sh and tools/gpu_merge_bins.sh; the shipped library has none of it):
+#ifndef TKM_ONLY_BIN
+#define TKM_ONLY_BIN -1  // 0 .. TK_NBIN - 1: only the pieces of this length bin are merged, the others come out as their single bytes (wrong tokens)
+#endif
+#ifndef TKM_NO_PROBES
+#define TKM_NO_PROBES 0  // 1: merges without table probes (wrong tokens: the cost of everything else)
+#endif
+#ifndef TKM_ONE_STEP
+#define TKM_ONE_STEP 0  // 1: one merge per step for every piece, not two for pieces of four lanes and more
+#endif
 #define TKM_WORK_STRIDE 64  // words between two work counters (256 bytes)
 __global__ __launch_bounds__(64 * TKM_WAVES, TKM_MIN_WAVES_EU) void tk_k_merge_all(TkTables T, const uint8_t* __restrict__ text, const uint32_t* __restrict__ listB,
                                                                       uint32_t* __restrict__ counters, TkMiss data, uint32_t* __restrict__ staging,
-                                                                      uint32_t* __restrict__ work /* 16 counters, TKM_WORK_STRIDE words apart, zero */, int dbg) {
+                                                                      uint32_t* __restrict__ work /* 16 counters, TKM_WORK_STRIDE words apart, zero */) {
     constexpr int C = 16;
     constexpr uint32_t NONE = 0xFFFFu;
     // (dynamic LDS, TKM_LDS_BYTES at the launch: with a static size the compiler derives the occupancy from it and lets the registers
@@ -2445,9 +2462,7 @@ __global__ __launch_bounds__(64 * TKM_WAVES, TKM_MIN_WAVES_EU) void tk_k_merge_a
         }
         __builtin_amdgcn_wave_barrier();
         uint32_t lkey = local_min();
-        // (perf experiments, the merge-bin field = bin + 1: only that bin is merged, the pieces of the others come out as their single bytes)
-        const int only_bin = (dbg >> TK_DBG_MERGE_BIN_SHIFT) & TK_DBG_MERGE_BIN_MASK;
-        if (only_bin && only_bin - 1 != b) lkey = TKM_NOKEY;
+        if (TKM_ONLY_BIN >= 0 && b != TKM_ONLY_BIN) lkey = TKM_NOKEY;
         for (;;) {
             // the piece's lowest key: leftmost lowest rank
             const uint32_t best = tkm_group_min(lkey, lg);
@@ -2462,8 +2477,8 @@ __global__ __launch_bounds__(64 * TKM_WAVES, TKM_MIN_WAVES_EU) void tk_k_merge_a
             const uint32_t oj = j / C, jl = j % C;
             const uint32_t nn_raw = pid[j] >> TKM_ID_BITS, pp_raw = pprv[bi];
             const uint32_t nn = nn_raw == TKM_NO_NEXT ? NONE : nn_raw, pp = pp_raw == TKM_NO_PREV ? NONE : pp_raw;
-            if (lg >= 2 && !(dbg & TK_DBG_ONE_MERGE_STEP)) {
-                // TWO merges per step (pieces of four lanes and more; TK_DBG_ONE_MERGE_STEP: one).  The step's time is the latency of its
+            if (lg >= 2 && !TKM_ONE_STEP) {
+                // TWO merges per step (pieces of four lanes and more; TKM_ONE_STEP: one).  The step's time is the latency of its
                 // table probes, and a long piece is a chain of hundreds of steps.  What the reference merges next (lib.rs:151,190) is the
                 // lowest key once more: either the lowest of the keys this merge leaves untouched -- known now -- or one of the two it
                 // creates.  So the second-lowest untouched key's merge is prepared at once, its neighbours taken from the state this
@@ -2498,7 +2513,7 @@ __global__ __launch_bounds__(64 * TKM_WAVES, TKM_MIN_WAVES_EU) void tk_k_merge_a
                 {
                     const uint32_t nb_pos = g == 0 ? nn : (g == 1 ? pp : (g == 2 ? nn2 : pp2));  // the neighbour this lane's pair is made with
                     const bool second = g >= 2, left = (g & 1u) != 0;                             // lanes 1, 3: (previous, merged)
-                    const bool on = !fin && g < 4u && nb_pos != NONE && (!second || has2) && !(dbg & TK_DBG_MERGE_NO_PROBES);  // (perf experiments: no probes)
+                    const bool on = !fin && g < 4u && nb_pos != NONE && (!second || has2) && !TKM_NO_PROBES;
                     const uint32_t nid = pid[nb_pos != NONE ? nb_pos : 0u] & TKM_ID_MASK, mid = second ? rank2 : brank;
                     if (on) newr = tk_probe_pair(T, left ? nid : mid, left ? mid : nid);
                 }
@@ -2536,7 +2551,7 @@ __global__ __launch_bounds__(64 * TKM_WAVES, TKM_MIN_WAVES_EU) void tk_k_merge_a
             }
             // the two new pairs: (merged, next) and (previous, merged)
             uint32_t newr_i = TK_RANK_MAX, newr_p = TK_RANK_MAX;
-            if (dbg & TK_DBG_MERGE_NO_PROBES) {  // (perf experiments: no probes -- wrong tokens, the cost of everything else)
+            if (TKM_NO_PROBES) {  // (the new pairs have no rank)
             } else if (lg == 0) {
                 if (!fin) tkm_probe2(T, brank, nn != NONE ? (pid[nn & (NMAX - 1u)] & TKM_ID_MASK) : 0u, nn != NONE, pp != NONE ? (pid[pp & (NMAX - 1u)] & TKM_ID_MASK) : 0u, brank, pp != NONE, newr_i, newr_p);
             } else {
