@@ -6,10 +6,11 @@
  * that ships here is tiktoken_amd/_tiktoken.py (ctypes).  All pointers are plain host pointers
  * unless the name says `_device`; no torch/HIP types appear in any signature.
  *
- * Status codes: every function returning int returns one of TK_OK ... TK_UNSUPPORTED; on failure
+ * Status codes: every function returning int returns one of TK_OK ... TK_DISALLOWED_SPECIAL; on failure
  * tk_last_error() holds a message (thread-local).  The Python shim maps them to the reference's
  * exception types: TK_VALUE_ERROR -> ValueError (src/py.rs:21-22,46), TK_KEY_ERROR -> KeyError
- * (src/py.rs:142,160,171), TK_RUNTIME_ERROR -> RuntimeError (HIP failures; no reference analogue).
+ * (src/py.rs:142,160,171), TK_RUNTIME_ERROR -> RuntimeError (HIP failures; no reference analogue),
+ * TK_DISALLOWED_SPECIAL -> DisallowedSpecialError, a ValueError (tiktoken/core.py:441-449; the _checked calls only).
  *
  * There is no CPU implementation behind these calls: without a usable HIP device tk_create fails
  * with TK_RUNTIME_ERROR.
@@ -22,7 +23,7 @@
 extern "C" {
 #endif
 
-enum { TK_OK = 0, TK_VALUE_ERROR = 1, TK_KEY_ERROR = 2, TK_RUNTIME_ERROR = 3, TK_UNSUPPORTED = 4 };
+enum { TK_OK = 0, TK_VALUE_ERROR = 1, TK_KEY_ERROR = 2, TK_RUNTIME_ERROR = 3, TK_UNSUPPORTED = 4, TK_DISALLOWED_SPECIAL = 5 };
 
 typedef struct tk_core tk_core;
 
@@ -71,6 +72,24 @@ int tk_encode_batch(tk_core* core, const uint8_t* utf8, const uint64_t* doc_off,
                     const uint32_t* allowed_ids, uint64_t n_allowed, uint32_t** tokens_out, uint64_t* n_tokens_out,
                     uint64_t* tok_off_out);
 
+/* Encoding.encode / encode_batch with disallowed_special                 tiktoken/core.py:116-124, raise_disallowed_special_token :441-449
+ * The reference searches every text for the disallowed special tokens, on the host, before it encodes anything.  The _checked calls do
+ * that search in the same call, on the text they have moved to the device anyway (one more read of it per chunk: tk_k_spec_find).
+ * disallowed_ids[0..n_disallowed): ids of registered special tokens (any other id: TK_VALUE_ERROR).  The search looks at the raw text,
+ * whatever allowed_ids makes of it, and an id in both lists is disallowed (the reference searches first; for "all" its Python layer
+ * has subtracted the allowed set already, core.py:100-106).
+ * No occurrence: exactly what the unchecked call does and returns.  n_disallowed == 0 IS the unchecked call (no extra launch).
+ * Otherwise TK_DISALLOWED_SPECIAL: *hit describes the first occurrence -- the lowest document, in it the lowest byte offset, there the
+ * longest disallowed token that fits its document (a token that would run across a document boundary is no occurrence) --, no
+ * tokens are handed out (*tokens_out is not written), and tk_last_error() names document, offset and id.  The core stays usable. */
+typedef struct {
+    uint64_t doc, pos; /* pos: byte offset inside document `doc` */
+    uint32_t id, len;  /* the token's id and its length in bytes */
+} tk_special_hit;
+int tk_encode_batch_checked(tk_core* core, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special,
+                            const uint32_t* allowed_ids, uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed,
+                            uint32_t** tokens_out, uint64_t* n_tokens_out, uint64_t* tok_off_out, tk_special_hit* hit);
+
 /* Same, with inputs already resident in HBM and results left in HBM (bench / torch interop).
  * d_utf8 must be readable for 64 bytes past n_bytes.  d_doc_off: uint64[n_docs+1] on the device,
  * h_doc_off: the same offsets on the host (needed only when n_bytes exceeds the per-launch chunk,
@@ -80,6 +99,12 @@ int tk_encode_batch_device(tk_core* core, const void* d_utf8, uint64_t n_bytes, 
                            const uint64_t* h_doc_off, uint64_t n_docs, int use_special, const uint32_t* allowed_ids,
                            uint64_t n_allowed, void* stream, const uint32_t** d_tokens_out, uint64_t* n_tokens_out,
                            const uint64_t** d_tok_off_out);
+/* ... checked (see tk_encode_batch_checked); on a hit the few bytes at it, and d_doc_off where h_doc_off is NULL, are copied to the host */
+int tk_encode_batch_device_checked(tk_core* core, const void* d_utf8, uint64_t n_bytes, const void* d_doc_off,
+                                   const uint64_t* h_doc_off, uint64_t n_docs, int use_special, const uint32_t* allowed_ids,
+                                   uint64_t n_allowed, void* stream, const uint32_t** d_tokens_out, uint64_t* n_tokens_out,
+                                   const uint64_t** d_tok_off_out, const uint32_t* disallowed_ids, uint64_t n_disallowed,
+                                   tk_special_hit* hit);
 
 /* Test / debug entry with no reference counterpart: the piece boundaries the GPU pre-tokeniser
  * finds, i.e. what `regex.find_iter` yields at src/lib.rs:365 and :405.  *starts_out receives
@@ -136,6 +161,11 @@ uint32_t tk_group_size(tk_group* group);
 int tk_group_encode_batch(tk_group* group, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special,
                           const uint32_t* allowed_ids, uint64_t n_allowed, uint32_t** tokens_out, uint64_t* n_tokens_out,
                           uint64_t* tok_off_out);
+/* ... checked (see tk_encode_batch_checked): every shard searches its own text; *hit is the hit with the lowest document index, in the
+ * batch's document numbers */
+int tk_group_encode_batch_checked(tk_group* group, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special,
+                                  const uint32_t* allowed_ids, uint64_t n_allowed, uint32_t** tokens_out, uint64_t* n_tokens_out,
+                                  uint64_t* tok_off_out, const uint32_t* disallowed_ids, uint64_t n_disallowed, tk_special_hit* hit);
 /* Results gathered on the first core's device; only the text crosses PCIe (every shard's ids stay on its device until the gather).
  * The gather is ONE exchange over xGMI: grouped ncclSend / ncclRecv through RCCL (rccl.h:700-722, loaded on first use) when the
  * group's devices are pairwise distinct, concurrent peer copies (one stream per source device) when a device is named twice or
@@ -176,7 +206,8 @@ int tk_get_kernel_ms(tk_core* core, const char* kernel_name, double* ms_out, uin
 void tk_last_stats(tk_core* core, uint64_t* n_bytes, uint64_t* n_pieces, uint64_t* n_tokens, uint64_t* n_docs,
                    uint64_t* n_medium, uint64_t* n_long);
 /* One named figure of the last encode call; 0 for a name it does not know: "chunks", "small_launches", "small_calls", "mid_calls",
- * "back_streams", "regrown", "workspace_bytes", "front_wgs_per_cu", "compute_units". */
+ * "back_streams", "regrown", "workspace_bytes", "front_wgs_per_cu", "compute_units", "spec_find_launches" (launches of the disallowed scan since
+ * the core was made: one per chunk of a _checked call), "stage_bytes" (host-buffer batches of twice that many bytes and more are pipelined). */
 uint64_t tk_stat(tk_core* core, const char* name);
 
 #ifdef __cplusplus

@@ -17,7 +17,12 @@ _SO = os.environ.get("TIKTOKEN_AMD_LIB") or os.path.join(_HERE, "csrc", "libtikt
 _lock = threading.Lock()
 _lib = None
 
-TK_OK, TK_VALUE_ERROR, TK_KEY_ERROR, TK_RUNTIME_ERROR, TK_UNSUPPORTED = range(5)
+TK_OK, TK_VALUE_ERROR, TK_KEY_ERROR, TK_RUNTIME_ERROR, TK_UNSUPPORTED, TK_DISALLOWED_SPECIAL = range(6)
+
+
+class SpecialHit(ctypes.Structure):
+    """tk_special_hit: the first disallowed special token a checked call met (include/tiktoken_amd.h)."""
+    _fields_ = [("doc", ctypes.c_uint64), ("pos", ctypes.c_uint64), ("id", ctypes.c_uint32), ("len", ctypes.c_uint32)]
 
 
 def build(force: bool = False) -> str:
@@ -102,6 +107,13 @@ def lib() -> ctypes.CDLL:
         L.tk_get_kernel_ms.restype = i32
         L.tk_get_kernel_ms.argtypes = [vp, ctypes.c_char_p, P(ctypes.c_double), P(u64)]
         L.tk_last_stats.argtypes = [vp, P(u64), P(u64), P(u64), P(u64), P(u64), P(u64)]
+        if hasattr(L, "tk_encode_batch_checked"):  # (absent from older builds selected through $TIKTOKEN_AMD_LIB: a checked call then fails with AttributeError)
+            L.tk_encode_batch_checked.restype = i32
+            L.tk_encode_batch_checked.argtypes = [vp, vp, vp, u64, i32, vp, u64, vp, u64, P(vp), P(u64), vp, P(SpecialHit)]
+            L.tk_encode_batch_device_checked.restype = i32
+            L.tk_encode_batch_device_checked.argtypes = [vp, vp, u64, vp, vp, u64, i32, vp, u64, vp, P(vp), P(u64), P(vp), vp, u64, P(SpecialHit)]
+            L.tk_group_encode_batch_checked.restype = i32
+            L.tk_group_encode_batch_checked.argtypes = [vp, vp, vp, u64, i32, vp, u64, P(vp), P(u64), vp, vp, u64, P(SpecialHit)]
         if hasattr(L, "tk_stat"):  # (absent from older builds selected through $TIKTOKEN_AMD_LIB)
             L.tk_stat.restype = u64
             L.tk_stat.argtypes = [vp, ctypes.c_char_p]
@@ -125,7 +137,7 @@ def raise_for(rc: int, key=None):
     if rc == TK_OK:
         return
     msg = last_error()
-    if rc in (TK_VALUE_ERROR, TK_UNSUPPORTED):
+    if rc in (TK_VALUE_ERROR, TK_UNSUPPORTED, TK_DISALLOWED_SPECIAL):  # (the checked calls raise DisallowedSpecialError themselves: _tiktoken.py)
         raise ValueError(msg)
     if rc == TK_KEY_ERROR:
         raise KeyError(key if key is not None else msg)

@@ -3,7 +3,8 @@
 
 Same constructor and the same eleven methods, same exception types.  Two additive entry points,
 `encode_batch_packed` and `pretokenize_packed`, expose the batch shape the GPU actually runs
-(one launch sequence per batch instead of one FFI call per document).
+(one launch sequence per batch instead of one FFI call per document).  With `disallowed_special` the batch
+calls also search the text for those special tokens, on the device, and raise `DisallowedSpecialError`.
 """
 from __future__ import annotations
 
@@ -90,6 +91,27 @@ def invalid_utf8_at(data: bytes) -> int | None:
     buf = np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(1, dtype=np.uint8)
     pos = ctypes.c_uint64()
     return None if _lib.lib().tk_validate_utf8(buf.ctypes.data, len(data), ctypes.byref(pos)) == 0 else int(pos.value)
+
+
+def disallowed_special_message(token: str) -> str:
+    """The reference's text for a disallowed special token (raise_disallowed_special_token, tiktoken/core.py:441-449)."""
+    return (
+        f"Encountered text corresponding to disallowed special token {token!r}.\n"
+        "If you want this text to be encoded as a special token, "
+        f"pass it to `allowed_special`, e.g. `allowed_special={{{token!r}, ...}}`.\n"
+        f"If you want this text to be encoded as normal text, disable the check for this token "
+        f"by passing `disallowed_special=(enc.special_tokens_set - {{{token!r}}})`.\n"
+        "To disable this check for all special tokens, pass `disallowed_special=()`.\n"
+    )
+
+
+class DisallowedSpecialError(ValueError):
+    """A batch holds a disallowed special token: the first occurrence -- document `doc`, byte offset `pos` inside it, the `token` (the
+    longest disallowed one that matches there).  What the reference raises as a plain ValueError, with its message."""
+
+    def __init__(self, doc: int, pos: int, token: str):
+        super().__init__(disallowed_special_message(token))
+        self.doc, self.pos, self.token = doc, pos, token
 
 
 def default_devices() -> list[int]:
@@ -182,6 +204,27 @@ class CoreBPE:
         ids = [self._specials[s] for s in allowed_special if s in self._specials]
         return np.asarray(ids if ids else [0], dtype=np.uint32), len(ids)
 
+    def _disallowed_ids(self, disallowed_special) -> tuple[np.ndarray, int]:
+        """ids of the special tokens a checked call searches for (None or empty: none, the unchecked call)"""
+        if disallowed_special is None:
+            return np.zeros(1, dtype=np.uint32), 0
+        if isinstance(disallowed_special, str):
+            if disallowed_special != "all":
+                raise ValueError("disallowed_special must be a collection of special-token strings or 'all'")
+            disallowed_special = self._specials.keys()
+        unknown = [s for s in disallowed_special if s not in self._specials]
+        if unknown:  # (the device searches for registered special tokens only; Encoding keeps its host search for any other string)
+            raise ValueError(f"not a special token of this encoding: {unknown[0]!r}")
+        ids = sorted({self._specials[s] for s in disallowed_special})
+        return np.asarray(ids if ids else [0], dtype=np.uint32), len(ids)
+
+    def _raise_hit(self, hit: "_lib.SpecialHit"):
+        # (two special strings may share an id: the length tells them apart)
+        token = next((s for s, i in self._specials.items() if i == hit.id and len(s.encode("utf-8")) == hit.len), None)
+        if token is None:
+            raise RuntimeError(f"internal error: the library reported special token id {hit.id} of {hit.len} bytes, which is not registered")
+        raise DisallowedSpecialError(int(hit.doc), int(hit.pos), token)
+
     @staticmethod
     def _as_u8(data: bytes) -> np.ndarray:
         return np.frombuffer(data, dtype=np.uint8) if data else np.zeros(1, dtype=np.uint8)
@@ -212,9 +255,12 @@ class CoreBPE:
         arr.setflags(write=False)
         return arr
 
-    def encode_batch_packed(self, blob: np.ndarray, doc_off: np.ndarray, allowed_special: AbstractSet[str] | None = None):
+    def encode_batch_packed(self, blob: np.ndarray, doc_off: np.ndarray, allowed_special: AbstractSet[str] | None = None, *,
+                            disallowed_special=None):
         """One GPU batch: `blob` = documents packed back to back (uint8), `doc_off` = uint64[n+1].
-        Returns (tokens uint32[T], tok_off uint64[n+1])."""
+        Returns (tokens uint32[T], tok_off uint64[n+1]).
+        `disallowed_special`: special-token strings (or "all") the text must not spell -- searched for on the device in the same call
+        (tk_encode_batch_checked); DisallowedSpecialError names the first occurrence.  None or empty: no search."""
         blob = np.ascontiguousarray(blob, dtype=np.uint8)
         doc_off = np.ascontiguousarray(doc_off, dtype=np.uint64)
         _check_packed(blob, doc_off)
@@ -227,7 +273,18 @@ class CoreBPE:
         else:
             ids, k = self._allowed_ids(allowed_special)
             mode = 1
-        if self._group is not None and n_docs > 1:
+        dis, n_dis = self._disallowed_ids(disallowed_special)
+        if n_dis:
+            hit = _lib.SpecialHit()
+            if self._group is not None and n_docs > 1:
+                rc = self._L.tk_group_encode_batch_checked(self._group, src.ctypes.data, doc_off.ctypes.data, n_docs, mode, ids.ctypes.data, k,
+                                                           ctypes.byref(out), ctypes.byref(n), tok_off.ctypes.data, dis.ctypes.data, n_dis, ctypes.byref(hit))
+            else:
+                rc = self._L.tk_encode_batch_checked(self._h, src.ctypes.data, doc_off.ctypes.data, n_docs, mode, ids.ctypes.data, k, dis.ctypes.data, n_dis,
+                                                     ctypes.byref(out), ctypes.byref(n), tok_off.ctypes.data, ctypes.byref(hit))
+            if rc == _lib.TK_DISALLOWED_SPECIAL:
+                self._raise_hit(hit)
+        elif self._group is not None and n_docs > 1:
             rc = self._L.tk_group_encode_batch(self._group, src.ctypes.data, doc_off.ctypes.data, n_docs, mode, ids.ctypes.data, k,
                                                ctypes.byref(out), ctypes.byref(n), tok_off.ctypes.data)
         else:
@@ -260,10 +317,11 @@ class CoreBPE:
         return int(self._L.tk_group_stat(self._group, name.encode())) if self._group is not None else 0
 
     def encode_batch_device(self, d_text_ptr: int, n_bytes: int, d_doc_off_ptr: int, h_doc_off: np.ndarray | None,
-                            n_docs: int, allowed_special: AbstractSet[str] | None = None, stream: int = 0):
+                            n_docs: int, allowed_special: AbstractSet[str] | None = None, stream: int = 0, *, disallowed_special=None):
         """Device-resident batch (tk_encode_batch_device): inputs already in HBM, results stay in HBM.
         Returns (d_tokens_ptr, n_tokens, d_tok_off_ptr); the pointers are owned by this CoreBPE and valid
-        until its next encode call.  d_text must be readable 64 bytes past n_bytes."""
+        until its next encode call.  d_text must be readable 64 bytes past n_bytes.
+        `disallowed_special`: as in encode_batch_packed (tk_encode_batch_device_checked)."""
         dt, dn, do = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_void_p()
         if allowed_special is None:
             ids, k, mode = np.zeros(1, dtype=np.uint32), 0, 0
@@ -274,8 +332,16 @@ class CoreBPE:
         if h_doc_off is not None:
             h_doc_off = np.ascontiguousarray(h_doc_off, dtype=np.uint64)
             h_ptr = h_doc_off.ctypes.data
-        rc = self._L.tk_encode_batch_device(self._h, d_text_ptr, n_bytes, d_doc_off_ptr, h_ptr, n_docs, mode, ids.ctypes.data, k,
-                                            stream or None, ctypes.byref(dt), ctypes.byref(dn), ctypes.byref(do))
+        dis, n_dis = self._disallowed_ids(disallowed_special)
+        if n_dis:
+            hit = _lib.SpecialHit()
+            rc = self._L.tk_encode_batch_device_checked(self._h, d_text_ptr, n_bytes, d_doc_off_ptr, h_ptr, n_docs, mode, ids.ctypes.data, k, stream or None,
+                                                        ctypes.byref(dt), ctypes.byref(dn), ctypes.byref(do), dis.ctypes.data, n_dis, ctypes.byref(hit))
+            if rc == _lib.TK_DISALLOWED_SPECIAL:
+                self._raise_hit(hit)
+        else:
+            rc = self._L.tk_encode_batch_device(self._h, d_text_ptr, n_bytes, d_doc_off_ptr, h_ptr, n_docs, mode, ids.ctypes.data, k,
+                                                stream or None, ctypes.byref(dt), ctypes.byref(dn), ctypes.byref(do))
         _lib.raise_for(rc)
         return dt.value, dn.value, do.value
 

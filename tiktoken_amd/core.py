@@ -30,13 +30,6 @@ def _repair_surrogates(text: str) -> str:
     return text.encode(_SURROGATE_FIX[0], _SURROGATE_FIX[1]).decode(_SURROGATE_FIX[2], _SURROGATE_FIX[3])
 
 
-def _utf8(text: str) -> bytes:
-    try:
-        return text.encode("utf-8")
-    except UnicodeEncodeError:
-        return _repair_surrogates(text).encode("utf-8")
-
-
 class Encoding:
     def __init__(self, name: str, *, pat_str: str, mergeable_ranks: dict[bytes, int], special_tokens: dict[str, int],
                  explicit_n_vocab: int | None = None):
@@ -144,13 +137,32 @@ class Encoding:
         return np.frombuffer(buffer, dtype=np.uint32)
 
     @staticmethod
-    def _pack(texts: Sequence[str]):
-        chunks = [_utf8(t) for t in texts]
+    def _pack_repaired(texts: Sequence[str]):
+        """(blob uint8, doc_off uint64[n+1], repaired): the texts as UTF-8, back to back, encoded text by text without a Python-level call
+        per text.  (One encode of the joined string was measured and is no faster even for ASCII batches, and 2.4 times slower where the
+        joined str has wide chars: profiles/r08_default_args.txt.)  Texts with surrogate code units, which the encode refuses, get the
+        reference's repair (core.py:79,135); `repaired` says whether any text needed it."""
+        if not isinstance(texts, (list, tuple)):
+            texts = list(texts)
+        repaired = False
+        try:
+            chunks = list(map(str.encode, texts))
+        except UnicodeEncodeError:
+            chunks = []
+            for t in texts:
+                try:
+                    chunks.append(t.encode("utf-8"))
+                except UnicodeEncodeError:
+                    chunks.append(_repair_surrogates(t).encode("utf-8"))
+                    repaired = True
         off = np.zeros(len(chunks) + 1, dtype=np.uint64)
         if chunks:
-            np.cumsum(np.fromiter((len(c) for c in chunks), dtype=np.uint64, count=len(chunks)), out=off[1:])
-        blob = np.frombuffer(b"".join(chunks), dtype=np.uint8)
-        return blob, off
+            np.cumsum(np.fromiter(map(len, chunks), dtype=np.uint64, count=len(chunks)), out=off[1:])
+        return np.frombuffer(b"".join(chunks), dtype=np.uint8), off, repaired
+
+    @staticmethod
+    def _pack(texts: Sequence[str]):
+        return Encoding._pack_repaired(texts)[:2]
 
     @staticmethod
     def _unpack(tokens: np.ndarray, tok_off: np.ndarray) -> list[list[int]]:
@@ -165,12 +177,29 @@ class Encoding:
 
     def encode_batch_packed(self, text: Sequence[str], *, allowed_special: Literal["all"] | AbstractSet[str] = set(),  # noqa: B006
                             disallowed_special: Literal["all"] | Collection[str] = "all"):
+        """(tokens uint32[T], tok_off uint64[n+1]) for a batch; see `encode` for the special-token arguments.  The search for disallowed
+        special tokens runs on the device, in the same call and on the text the encode has moved there anyway, when every member of
+        `disallowed_special` is a special token of this encoding and no text needed surrogate repair; otherwise on the host, text by
+        text, as the reference does it (any string may be disallowed there, and a surrogate pair spelled as two code units matches a
+        str differently from its repaired bytes).  The ValueError is the host search's either way."""
         allowed_special, disallowed_special = self._special_policy(allowed_special, disallowed_special)
-        if disallowed_special:
+        if not disallowed_special:
+            blob, off = self._pack(text)
+            return self._core_bpe.encode_batch_packed(blob, off, allowed_special)
+        if not isinstance(disallowed_special, frozenset):
+            disallowed_special = frozenset(disallowed_special)
+        blob, off, repaired = self._pack_repaired(text)
+        if repaired or not all(t in self._special_tokens for t in disallowed_special):
             for t in text:
                 self._reject_disallowed(t, disallowed_special)
-        blob, off = self._pack(text)
-        return self._core_bpe.encode_batch_packed(blob, off, allowed_special)
+            return self._core_bpe.encode_batch_packed(blob, off, allowed_special)
+        try:
+            return self._core_bpe.encode_batch_packed(blob, off, allowed_special, disallowed_special=disallowed_special)
+        except _tiktoken.DisallowedSpecialError as e:
+            # today's search on that one document: the message -- which token is named where one is a prefix of another -- is the host's
+            self._reject_disallowed(text[e.doc], disallowed_special)
+            raise RuntimeError(f"internal error: the device reported the disallowed special token {e.token!r} in document {e.doc} at byte "
+                               f"{e.pos}, the host search finds none there") from e
 
     def encode_ordinary_batch(self, text: list[str], *, num_threads: int = 8) -> list[list[int]]:
         """Encode a list of strings, ignoring special tokens (one GPU batch; `num_threads` is kept for
@@ -321,11 +350,4 @@ def _special_token_regex(tokens: frozenset[str]) -> "re.Pattern[str]":
 
 
 def raise_disallowed_special_token(token: str) -> NoReturn:
-    raise ValueError(
-        f"Encountered text corresponding to disallowed special token {token!r}.\n"
-        "If you want this text to be encoded as a special token, "
-        f"pass it to `allowed_special`, e.g. `allowed_special={{{token!r}, ...}}`.\n"
-        f"If you want this text to be encoded as normal text, disable the check for this token "
-        f"by passing `disallowed_special=(enc.special_tokens_set - {{{token!r}}})`.\n"
-        "To disable this check for all special tokens, pass `disallowed_special=()`.\n"
-    )
+    raise ValueError(_tiktoken.disallowed_special_message(token))

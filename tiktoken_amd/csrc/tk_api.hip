@@ -10,6 +10,7 @@
 
 #include <chrono>
 #include <functional>
+#include <algorithm>
 #include <atomic>
 #include <map>
 #include <mutex>
@@ -71,7 +72,7 @@ struct KernelStat {
 // Work buffers of ONE chunk in flight.
 struct WorkSet {
     Buf text_al, tile_sum, wide_ws, scan_sums, row_base, brk, docb, cand, ss, si, starts, blockcnt, pstart, res, staging, listB, listC, counters, total, g_id, g_rk,
-        g_nx, g_pv, g_lv, tile_np, tile_nt, mt_keys, mtab, movf, mcnt, wbin, deferred, big, rx_spec, rx_gst, rx_lnk, rx_exit, merge_work;
+        g_nx, g_pv, g_lv, tile_np, tile_nt, mt_keys, mtab, movf, mcnt, wbin, deferred, big, rx_spec, rx_gst, rx_lnk, rx_exit, merge_work, find;
     hipStream_t sb = nullptr;        // the set's back stage in a multi-chunk batch: back stages of different chunks overlap each other too
                                      // (they are chains of short latency-bound kernels, ~2 ms however small the chunk)
     hipEvent_t ev_front = nullptr;   // the front kernel is done
@@ -80,11 +81,11 @@ struct WorkSet {
     hipEvent_t ev_done = nullptr;    // the back stage is done: totals and counters are in h_total / h_counters + TK_CNT_N, the buffers are free
     hipEvent_t ev_fork = nullptr, ev_join[TK_NAUX] = {};  // fork / join of the merge kernels on the side streams
     uint32_t* h_counters = nullptr;  // pinned [2][TK_CNT_N]
-    uint64_t* h_total = nullptr;     // pinned [2]: tokens, pieces of the chunk
+    uint64_t* h_total = nullptr;     // pinned [3]: tokens, pieces of the chunk; where its first disallowed special token starts (all ones: nowhere)
     std::vector<Buf*> all() {
         return {&text_al, &tile_sum, &wide_ws, &scan_sums, &row_base, &brk, &docb, &cand, &ss, &si, &starts, &blockcnt, &pstart, &res, &staging, &listB,
                 &listC, &counters, &total, &g_id, &g_rk, &g_nx, &g_pv, &g_lv, &tile_np, &tile_nt, &mt_keys, &mtab, &movf, &mcnt, &wbin, &deferred, &big, &rx_spec,
-                &rx_gst, &rx_lnk, &rx_exit, &merge_work};
+                &rx_gst, &rx_lnk, &rx_exit, &merge_work, &find};
     }
 };
 // What the front stage of a chunk leaves for its back stage.
@@ -94,6 +95,7 @@ struct ChunkJob {
     const uint64_t* d_doc_off = nullptr;
     uint64_t* d_tok_off = nullptr;
     bool single_piece = false, spec = false, pretok = false;
+    bool find = false;  // the chunk's text was searched for disallowed special tokens (tk_k_spec_find -> w.find)
     uint32_t index = 0;  // position of the chunk in its batch
     uint32_t mt_bits = 14;
     TkMissKey* mt = nullptr;   // the in-call miss table's keys (null: no table -- every missed piece gets an overflow entry)
@@ -131,6 +133,13 @@ struct tk_core {
     // workspace: per chunk in flight, and what a whole call shares
     WorkSet ws[TK_NSET];
     Buf text, doc_off, out_tokens, out_tok_off, allowed, tok_bases;  // tok_bases[k]: tokens of the chunks before chunk k (on the device)
+    // The disallowed special tokens of a checked call (tk_encode_batch_checked and its kin): `disallowed` is a byte per special token, as
+    // `allowed`; find_on is set by the entry point, under the mutex, for the duration of its call, and every chunk's front stage then runs
+    // tk_k_spec_find.  find_hit: where in the batch the first hit starts (chunk_finish).
+    Buf disallowed;
+    bool find_on = false;
+    uint64_t find_hit = ~0ull;
+    uint64_t st_find_launches = 0;  // launches of that scan since the core was made
     // Streams of the back stages of a multi-chunk batch.  HIP multiplexes its streams onto a few hardware queues (four by default), and
     // two streams that share a queue run one after the other: the back stage of chunk k, queued behind the front kernel of chunk
     // k + 1, then waits for that kernel to END instead of running beside it (seen in the kernel timeline of round 4: no overlap at all).
@@ -451,34 +460,10 @@ extern "C" int tk_create(const uint8_t* ranks_blob, const uint64_t* ranks_off, c
     D.spec_off = c->t_spec_off.as<uint32_t>();
     D.spec_id = c->t_spec_id.as<uint32_t>();
     {
-        std::vector<uint32_t> head(4 * (H.spec_id.size() + 1), 0u);
-        for (size_t k = 0; k < H.spec_id.size(); ++k) {
-            const uint32_t o = H.spec_off[k], len = H.spec_off[k + 1] - o;
-            uint64_t h8 = 0;
-            for (uint32_t i = 0; i < len && i < 8u; ++i) h8 |= (uint64_t)H.spec_bytes[o + i] << (8u * i);
-            head[4 * k] = (uint32_t)h8;
-            head[4 * k + 1] = (uint32_t)(h8 >> 32);
-            head[4 * k + 2] = len;
-            head[4 * k + 3] = o;
-        }
+        std::vector<uint32_t> head;
+        tk_spec_tables(H, head, D);
         if ((rc = upload(c->t_spec_head, head.data(), head.size() * 4))) return bail(rc);
         D.spec_head = c->t_spec_head.as<uint32_t>();
-    }
-    D.n_spec = (uint32_t)H.spec_id.size();
-    memcpy(D.spec_first, H.spec_first, sizeof D.spec_first);
-    D.spec_fb = 0;
-    D.n_spec_fb = 0;
-    for (uint32_t b = 0; b < 256; ++b)
-        if ((H.spec_first[b >> 5] >> (b & 31)) & 1u) {
-            if (D.n_spec_fb < 4) D.spec_fb |= b << (8 * D.n_spec_fb);
-            D.n_spec_fb += 1;
-        }
-    if (D.n_spec_fb > 4) D.n_spec_fb = 0xFF;
-    memset(D.spec_second, 0, sizeof D.spec_second);
-    for (size_t k = 0; k + 1 < H.spec_off.size(); ++k) {
-        const uint32_t o = H.spec_off[k], len = H.spec_off[k + 1] - o;
-        if (len < 2) memset(D.spec_second, 0xFF, sizeof D.spec_second);
-        else D.spec_second[H.spec_bytes[o + 1] >> 5] |= 1u << (H.spec_bytes[o + 1] & 31);
     }
     D.pattern = H.pattern;
     D.pat = H.pat;
@@ -557,7 +542,7 @@ extern "C" void tk_destroy(tk_core* c) {
     for (Buf* b : {&c->t_rx_ins, &c->t_rx_sets, &c->t_rx_ranges, &c->t_rx_first, &c->t_rx_s1, &c->t_rx_s2, &c->t_rx_dtrans, &c->t_rx_dascii, &c->t_rx_ds1, &c->t_rx_ds2}) release(*b);
     for (Buf* b : {&c->t_stage1, &c->t_stage2, &c->t_bmp, &c->t_byte_tab, &c->t_short, &c->t_mid, &c->t_dec, &c->d_tok, &c->d_lens, &c->d_bsum, &c->d_tboff, &c->d_bytes, &c->d_bytes_alt, &c->d_boff, &c->t_piece,
                    &c->t_piece_off, &c->t_tok_bytes, &c->t_pair, &c->t_pair2, &c->t_byte_rank, &c->t_xl, &c->t_xfilter, &c->t_spec_bytes, &c->t_spec_off, &c->t_spec_id, &c->t_spec_head, &c->text, &c->doc_off,
-                   &c->out_tokens, &c->out_tok_off, &c->out_tokens_alt, &c->out_tok_off_alt, &c->allowed, &c->tok_bases})
+                   &c->out_tokens, &c->out_tok_off, &c->out_tokens_alt, &c->out_tok_off_alt, &c->allowed, &c->disallowed, &c->tok_bases})
         release(*b);
     if (c->h_probe) (void)hipHostFree(c->h_probe);
     for (WorkSet& w : c->ws) {
@@ -850,6 +835,7 @@ static int stage_front(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, con
     clear(w.total, 32, 0u);
     uint32_t *brk = w.brk.as<uint32_t>(), *starts = w.starts.as<uint32_t>();
     uint32_t *ss = nullptr, *si = nullptr, *docb = nullptr;
+    uint32_t* find_docb = nullptr;  // the document starts for the disallowed scan: `docb`, or the same bitmap made for the scan alone
     uint32_t* counters = w.counters.as<uint32_t>();
     TRY(ensure(w.tile_sum, ntiles + 16));
     // (round 6) the first document that starts in every tile (tk_k_mark_docs), for tk_k_place, which writes the documents' token offsets as it
@@ -876,6 +862,16 @@ static int stage_front(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, con
             ss = w.ss.as<uint32_t>();
             si = w.si.as<uint32_t>();
         }
+        if (c->find_on && !pretok_only) {
+            job.find = true;
+            TRY(ensure(w.find, 16));
+            clear(w.find, 16, 0xFFFFFFFFu);
+            if (!docb) {
+                TRY(ensure(w.docb, (nwords + 4) * 4));
+                clear(w.docb, (nwords + 4) * 4, 0u);
+            }
+            find_docb = w.docb.as<uint32_t>();
+        }
         if (c->has_rx) {
             // (two bitmaps each: the starts, and behind them the gap chars among the starts)
             TRY(ensure(w.rx_spec, 2 * (nwords + 2) * 4));
@@ -888,7 +884,7 @@ static int stage_front(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, con
         hipLaunchKernelGGL(tk_k_chunk_clear, dim3(grid_for(n / 64 + 1, 256, 2048)), dim3(256), 0, s, clr);
         clr.n = 0;
         TRY(timed(c, s, "tk_k_mark_docs", [&] {
-            hipLaunchKernelGGL(tk_k_mark_docs, dim3(grid_for(n_docs, 256, 4096)), dim3(256), 0, s, d_doc_off, n_docs, base, n, brk, docb,
+            hipLaunchKernelGGL(tk_k_mark_docs, dim3(grid_for(n_docs, 256, 4096)), dim3(256), 0, s, d_doc_off, n_docs, base, n, brk, docb ? docb : find_docb,
                                docs_in_place ? w.row_base.as<uint32_t>() : (uint32_t*)nullptr, ntiles);
         }));
         if (use_special) {
@@ -901,6 +897,15 @@ static int stage_front(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, con
                 hipLaunchKernelGGL(tk_k_spec_resolve, dim3(grid_for(nwords, 256, 65536)), dim3(256), 0, s, T, d_text, n, allowed, docb, cand,
                                    c->spec_max_len, ss, si, brk);
             }));
+        }
+        if (job.find) {
+            // (a match ends inside the chunk -- tk_special_at asks for pos + len <= n -- and inside its document: the text behind the chunk, the
+            // next document or the zeroed slack, is never part of one)
+            TRY(timed(c, s, "tk_k_spec_find", [&] {
+                hipLaunchKernelGGL(tk_k_spec_find, dim3(grid_for(n / 16 + 1, 256, 65536)), dim3(256), 0, s, T, d_text, n, c->disallowed.as<uint8_t>(), find_docb, base,
+                                   w.find.as<unsigned long long>());
+            }));
+            c->st_find_launches += 1;
         }
         if (c->has_rx) TRY(rx_split(c, w, s, d_text, n, brk, ss, si, d_doc_off, n_docs, base));  // the generic engine finds the piece starts; they join the hard starts in `brk`
         TRY(ensure(w.deferred, 2 * (ntiles + 2) * 4));  // (behind the list of deferred tiles: those that gave up their walk, stage_deferred)
@@ -970,6 +975,7 @@ static int stage_back(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, uint
         hipLaunchKernelGGL(tk_k_advance, dim3(1), dim3(64), 0, s, c->tok_bases.as<unsigned long long>(), job.index, w.total.as<uint64_t>());
         HIPCHK(hipEventRecord(w.ev_tot, s));
         HIPCHK(hipMemcpyAsync(w.h_total, w.total.p, 16, hipMemcpyDeviceToHost, s));
+        if (job.find) HIPCHK(hipMemcpyAsync(w.h_total + 2, w.find.p, 8, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(w.h_counters + TK_CNT_N, counters, TK_CNT_N * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipEventRecord(w.ev_done, s));
         return TK_OK;
@@ -1119,6 +1125,7 @@ static int stage_back(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, uint
         }));
     }
     HIPCHK(hipMemcpyAsync(w.h_total, w.total.p, 16, hipMemcpyDeviceToHost, s));
+    if (job.find) HIPCHK(hipMemcpyAsync(w.h_total + 2, w.find.p, 8, hipMemcpyDeviceToHost, s));  // (read where the host waits for the totals anyway: chunk_finish)
     HIPCHK(hipMemcpyAsync(w.h_counters + TK_CNT_N, counters, TK_CNT_N * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipEventRecord(w.ev_done, s));
     c->st_long += nC;
@@ -1126,9 +1133,14 @@ static int stage_back(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, uint
 }
 
 #define TK_GROW (-1000)  // (internal) the batch has to be repeated with a larger miss data: encode_device_locked
+#define TK_SPEC_HIT (-1002)  // (internal) a chunk holds a disallowed special token (c->find_hit): the entry point reports it, no tokens are handed out
 // the chunk of `w` is complete: its totals, statistics and error flags (waits for its back stage)
 static int chunk_finish(tk_core* c, WorkSet& w, const ChunkJob& job, uint64_t* n_tokens_out) {
     HIPCHK(hipEventSynchronize(w.ev_done));
+    if (job.find && w.h_total[2] != ~0ull) {  // (before anything else: the reference refuses such text before it encodes any of it)
+        c->find_hit = w.h_total[2];
+        return TK_SPEC_HIT;
+    }
     const uint32_t* hb = w.h_counters + TK_CNT_N;
     uint64_t nB = 0;
     for (int b = 0; b < TK_NBIN; ++b) {
@@ -1173,20 +1185,76 @@ static int run_chunk(tk_core* c, hipStream_t s, const uint8_t* d_text, uint64_t 
     return chunk_finish(c, w, job, n_tokens_out);
 }
 
-static int prepare_allowed(tk_core* c, hipStream_t s, const uint32_t* allowed_ids, uint64_t n_allowed, bool* any) {
+// a byte per special token on the device: 1 for those whose id is among ids[0..n)
+static int prepare_mask(tk_core* c, hipStream_t s, Buf& mask, const uint32_t* ids, uint64_t n, bool* any) {
     const TkHostTables& H = c->H;
     std::vector<uint8_t> a(H.spec_id.size() + 16, 0);
     *any = false;
     for (size_t k = 0; k < H.spec_id.size(); ++k)
-        for (uint64_t j = 0; j < n_allowed; ++j)
-            if (H.spec_id[k] == allowed_ids[j]) {
+        for (uint64_t j = 0; j < n; ++j)
+            if (H.spec_id[k] == ids[j]) {
                 a[k] = 1;
                 *any = true;
             }
-    TRY(ensure(c->allowed, a.size()));
-    HIPCHK(hipMemcpyAsync(c->allowed.p, a.data(), a.size(), hipMemcpyHostToDevice, s));
+    TRY(ensure(mask, a.size()));
+    HIPCHK(hipMemcpyAsync(mask.p, a.data(), a.size(), hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s));  // `a` goes out of scope
     return TK_OK;
+}
+static int prepare_allowed(tk_core* c, hipStream_t s, const uint32_t* allowed_ids, uint64_t n_allowed, bool* any) {
+    return prepare_mask(c, s, c->allowed, allowed_ids, n_allowed, any);
+}
+
+// ---- checked calls: the disallowed special tokens of Encoding.encode / encode_batch (tiktoken/core.py:116-124) ----
+struct CheckArgs {
+    const uint32_t* ids;  // the disallowed special tokens
+    uint64_t n;
+    tk_special_hit* hit;
+};
+// every id names a special token of the core (host only: before anything is locked or sent)
+static int check_disallowed_ids(tk_core* c, const CheckArgs* chk) {
+    if (!chk || !chk->n) return TK_OK;
+    if (!chk->ids || !chk->hit) return fail(TK_VALUE_ERROR, "null argument");
+    for (uint64_t j = 0; j < chk->n; ++j)
+        if (std::find(c->H.spec_id.begin(), c->H.spec_id.end(), chk->ids[j]) == c->H.spec_id.end())
+            return fail(TK_VALUE_ERROR, "disallowed id " + std::to_string(chk->ids[j]) + " is not a special token of this encoding");
+    return TK_OK;
+}
+// The scan is on for the calls of this scope (the core's mutex is held).
+struct FindScope {
+    tk_core* c;
+    explicit FindScope(tk_core* core) : c(core) {}
+    int begin(hipStream_t s, const CheckArgs* chk) {
+        if (!chk || !chk->n) return TK_OK;
+        bool any = false;
+        TRY(prepare_mask(c, s, c->disallowed, chk->ids, chk->n, &any));
+        c->find_on = any;
+        c->find_hit = ~0ull;
+        return TK_OK;
+    }
+    ~FindScope() { c->find_on = false; }
+};
+// A pass has ended with TK_SPEC_HIT: which document c->find_hit lies in and which token it is -- the longest disallowed one that matches
+// there inside the document -- from the few bytes at the hit (`at`: the batch's text from the hit on, at least min(spec_max_len,
+// bytes left in the batch) of it, on the host).  Returns TK_DISALLOWED_SPECIAL.
+static int report_hit(tk_core* c, const uint8_t* at, const uint64_t* doc_off, uint64_t n_docs, const CheckArgs* chk) {
+    const TkHostTables& H = c->H;
+    const uint64_t pos = c->find_hit;
+    const uint64_t doc = (uint64_t)(std::upper_bound(doc_off, doc_off + n_docs + 1, pos) - doc_off) - 1;  // (the last document that starts at or before pos: not an empty one)
+    if (doc >= n_docs) return fail(TK_RUNTIME_ERROR, "internal error: a special token was found outside every document");
+    const uint64_t room = doc_off[doc + 1] - pos;
+    uint32_t best = 0, id = 0;
+    for (size_t k = 0; k < H.spec_id.size(); ++k) {
+        const uint32_t o = H.spec_off[k], len = H.spec_off[k + 1] - o;
+        if (len <= best || len > room || memcmp(at, H.spec_bytes.data() + o, len) != 0) continue;
+        if (std::find(chk->ids, chk->ids + chk->n, H.spec_id[k]) == chk->ids + chk->n) continue;
+        best = len;
+        id = H.spec_id[k];
+    }
+    if (!best) return fail(TK_RUNTIME_ERROR, "internal error: no disallowed special token at the position the device reported");
+    *chk->hit = tk_special_hit{doc, pos - doc_off[doc], id, best};
+    return fail(TK_DISALLOWED_SPECIAL, "disallowed special token " + std::to_string(id) + " (" + std::string((const char*)at, best) + ") in document " + std::to_string(doc) +
+                                           " at byte " + std::to_string(pos - doc_off[doc]));
 }
 
 // ---- which of the library's streams run BESIDE a given stream (see tk_core::back_s) ----
@@ -1395,31 +1463,65 @@ static int encode_device_locked(tk_core* c, hipStream_t s, const uint8_t* d_utf8
         else c->st_resynced += 1;
         rc = encode_device_pass(c, s, d_utf8, n_bytes, d_doc_off, h_doc_off, n_docs, use_special, n_tokens_out, chunk_bytes, hooks);
     }
+    if (rc == TK_SPEC_HIT) {  // (chunks are finished in document order: the first chunk with a hit holds the batch's first; those behind it are abandoned)
+        HIPCHK(hipDeviceSynchronize());
+        (void)drain_events(c);
+        return rc;
+    }
     if (rc == TK_GROW) return fail(TK_RUNTIME_ERROR, "internal error: the miss data overflowed at its largest size");
     if (rc == TK_RESYNC) return fail(TK_RUNTIME_ERROR, "internal error: a deferred tile gave up although the host was waiting");
     return rc;
 }
 
-extern "C" int tk_encode_batch_device(tk_core* c, const void* d_utf8, uint64_t n_bytes, const void* d_doc_off,
-                                      const uint64_t* h_doc_off, uint64_t n_docs, int use_special, const uint32_t* allowed_ids,
-                                      uint64_t n_allowed, void* stream, const uint32_t** d_tokens_out, uint64_t* n_tokens_out,
-                                      const uint64_t** d_tok_off_out) {
+static int encode_batch_device_impl(tk_core* c, const void* d_utf8, uint64_t n_bytes, const void* d_doc_off, const uint64_t* h_doc_off, uint64_t n_docs,
+                                    int use_special, const uint32_t* allowed_ids, uint64_t n_allowed, void* stream, const uint32_t** d_tokens_out,
+                                    uint64_t* n_tokens_out, const uint64_t** d_tok_off_out, const CheckArgs* chk) {
     if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    TRY(check_disallowed_ids(c, chk));
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     bool any = false;
     if (use_special) TRY(prepare_allowed(c, s, allowed_ids, n_allowed, &any));
+    FindScope find(c);
+    TRY(find.begin(s, chk));
     uint64_t total = 0;
     if (c->out_bufs == 2) {  // (the previous call's result stays where it is: a consumer on another stream may still be reading it)
         std::swap(c->out_tokens, c->out_tokens_alt);
         std::swap(c->out_tok_off, c->out_tok_off_alt);
     }
-    TRY(encode_device_locked(c, s, (const uint8_t*)d_utf8, n_bytes, (const uint64_t*)d_doc_off, h_doc_off, n_docs, use_special && any, &total));
+    const int rc = encode_device_locked(c, s, (const uint8_t*)d_utf8, n_bytes, (const uint64_t*)d_doc_off, h_doc_off, n_docs, use_special && any, &total);
+    if (rc == TK_SPEC_HIT) {  // the few bytes at the hit, and the offsets where the caller has not given them, come to the host
+        std::vector<uint8_t> at((size_t)std::min<uint64_t>(c->spec_max_len, n_bytes - c->find_hit));
+        HIPCHK(hipMemcpy(at.data(), (const uint8_t*)d_utf8 + c->find_hit, at.size(), hipMemcpyDeviceToHost));
+        std::vector<uint64_t> off;
+        if (!h_doc_off) {
+            off.resize(n_docs + 1);
+            HIPCHK(hipMemcpy(off.data(), d_doc_off, (n_docs + 1) * 8, hipMemcpyDeviceToHost));
+            h_doc_off = off.data();
+        }
+        return report_hit(c, at.data(), h_doc_off, n_docs, chk);
+    }
+    TRY(rc);
     if (d_tokens_out) *d_tokens_out = c->out_tokens.as<uint32_t>();
     if (d_tok_off_out) *d_tok_off_out = c->out_tok_off.as<uint64_t>();
     if (n_tokens_out) *n_tokens_out = total;
     return TK_OK;
+}
+extern "C" int tk_encode_batch_device(tk_core* c, const void* d_utf8, uint64_t n_bytes, const void* d_doc_off,
+                                      const uint64_t* h_doc_off, uint64_t n_docs, int use_special, const uint32_t* allowed_ids,
+                                      uint64_t n_allowed, void* stream, const uint32_t** d_tokens_out, uint64_t* n_tokens_out,
+                                      const uint64_t** d_tok_off_out) {
+    return encode_batch_device_impl(c, d_utf8, n_bytes, d_doc_off, h_doc_off, n_docs, use_special, allowed_ids, n_allowed, stream, d_tokens_out, n_tokens_out,
+                                    d_tok_off_out, nullptr);
+}
+extern "C" int tk_encode_batch_device_checked(tk_core* c, const void* d_utf8, uint64_t n_bytes, const void* d_doc_off, const uint64_t* h_doc_off,
+                                              uint64_t n_docs, int use_special, const uint32_t* allowed_ids, uint64_t n_allowed, void* stream,
+                                              const uint32_t** d_tokens_out, uint64_t* n_tokens_out, const uint64_t** d_tok_off_out,
+                                              const uint32_t* disallowed_ids, uint64_t n_disallowed, tk_special_hit* hit) {
+    const CheckArgs chk{disallowed_ids, n_disallowed, hit};
+    return encode_batch_device_impl(c, d_utf8, n_bytes, d_doc_off, h_doc_off, n_docs, use_special, allowed_ids, n_allowed, stream, d_tokens_out, n_tokens_out,
+                                    d_tok_off_out, &chk);
 }
 
 // Host-buffer batches: the text goes to the device by DMA on a copy stream, straight from the caller's buffer, while earlier chunks are
@@ -1462,7 +1564,8 @@ static void parallel_memcpy(void* dst, const void* src, size_t n, unsigned nth) 
 }
 
 static int encode_batch_impl(tk_core* c, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special, const uint32_t* allowed_ids,
-                             uint64_t n_allowed, uint32_t** tokens_out, uint64_t* n_tokens_out, uint64_t* tok_off_out, bool device_result, bool no_small);
+                             uint64_t n_allowed, uint32_t** tokens_out, uint64_t* n_tokens_out, uint64_t* tok_off_out, bool device_result, bool no_small,
+                             const CheckArgs* chk = nullptr);
 // ---- the slots of the small-call path (tk_core::SmallSlot) ----
 static int small_slot_init(tk_core* c, tk_core::SmallSlot* sl) {
     if (sl->ready) return TK_OK;  // (a first use that failed: what it did make is kept, the rest is made now)
@@ -1723,10 +1826,12 @@ static int encode_small(tk_core* c, const uint8_t* utf8, uint32_t n, uint32_t** 
 // several-GPU gather needs; the one-launch small path (which writes straight to host memory) is not taken then.
 static int encode_batch_impl(tk_core* c, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special,
                              const uint32_t* allowed_ids, uint64_t n_allowed, uint32_t** tokens_out, uint64_t* n_tokens_out,
-                             uint64_t* tok_off_out, bool device_result, bool no_small) {
+                             uint64_t* tok_off_out, bool device_result, bool no_small, const CheckArgs* chk) {
     if (!c) return fail(TK_VALUE_ERROR, "core is null");
     if (!doc_off || (!device_result && !tokens_out) || !n_tokens_out) return fail(TK_VALUE_ERROR, "null argument");
     TRY(check_offsets(doc_off, n_docs, "doc_off"));
+    TRY(check_disallowed_ids(c, chk));
+    if (chk && chk->n) no_small = true;  // (the one-launch paths do not search: a checked call takes the general pipeline)
     const uint64_t n_bytes = doc_off[n_docs];
     if (!no_small && !device_result && n_docs == 1 && n_bytes > 0 && n_bytes <= (uint64_t)TK_SMALL_MAX * TK_MID_SEGMENTS && !(use_special && n_allowed) && !(c->dbg & TK_DBG_NO_SMALL) && !c->has_rx &&
         (n_bytes <= TK_SMALL_MAX || !c->profiling)) {
@@ -1750,11 +1855,15 @@ static int encode_batch_impl(tk_core* c, const uint8_t* utf8, const uint64_t* do
     HIPCHK(hipMemcpyAsync(c->doc_off.p, doc_off, (n_docs + 1) * 8, hipMemcpyHostToDevice, s));
     bool any = false;
     if (use_special) TRY(prepare_allowed(c, s, allowed_ids, n_allowed, &any));
+    FindScope find(c);
+    TRY(find.begin(s, chk));
     uint64_t total = 0;
     if (n_bytes < 2 * TK_STAGE_BYTES) {
         // small batches: one copy each way (latency matters more than overlap)
         if (n_bytes) HIPCHK(hipMemcpyAsync(c->text.p, utf8, n_bytes, hipMemcpyHostToDevice, s));
-        TRY(encode_device_locked(c, s, c->text.as<uint8_t>(), n_bytes, c->doc_off.as<uint64_t>(), doc_off, n_docs, use_special && any, &total));
+        const int rc = encode_device_locked(c, s, c->text.as<uint8_t>(), n_bytes, c->doc_off.as<uint64_t>(), doc_off, n_docs, use_special && any, &total);
+        if (rc == TK_SPEC_HIT) return report_hit(c, utf8 + c->find_hit, doc_off, n_docs, chk);
+        TRY(rc);
         if (device_result) {
             *n_tokens_out = total;
             return TK_OK;
@@ -1837,6 +1946,11 @@ static int encode_batch_impl(tk_core* c, const uint8_t* utf8, const uint64_t* do
     hipError_t e = hipStreamSynchronize(c->cs_h2d);
     if (e == hipSuccess) e = hipStreamSynchronize(c->cs_d2h);
     drop_events();
+    if (rc == TK_SPEC_HIT) {  // (the text has arrived and nothing is on its way back: the caller's buffers are his again)
+        tk_free(host);
+        if (e != hipSuccess) return fail(TK_RUNTIME_ERROR, std::string("HIP error: ") + hipGetErrorString(e));
+        return report_hit(c, utf8 + c->find_hit, doc_off, n_docs, chk);
+    }
     if (rc == TK_OK && e != hipSuccess) rc = fail(TK_RUNTIME_ERROR, std::string("HIP error: ") + hipGetErrorString(e));
     if (rc == TK_OK && tok_off_out && !device_result) {
         e = hipMemcpy(tok_off_out, c->out_tok_off.p, (n_docs + 1) * 8, hipMemcpyDeviceToHost);
@@ -1857,6 +1971,14 @@ extern "C" int tk_encode_batch(tk_core* c, const uint8_t* utf8, const uint64_t* 
                                const uint32_t* allowed_ids, uint64_t n_allowed, uint32_t** tokens_out, uint64_t* n_tokens_out,
                                uint64_t* tok_off_out) {
     return encode_batch_impl(c, utf8, doc_off, n_docs, use_special, allowed_ids, n_allowed, tokens_out, n_tokens_out, tok_off_out, false, false);
+}
+// The same with Encoding.encode_batch's disallowed_special (tiktoken/core.py:116-124) checked in the same call, on the text it has moved to
+// the device: see include/tiktoken_amd.h.
+extern "C" int tk_encode_batch_checked(tk_core* c, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special, const uint32_t* allowed_ids,
+                                       uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed, uint32_t** tokens_out,
+                                       uint64_t* n_tokens_out, uint64_t* tok_off_out, tk_special_hit* hit) {
+    const CheckArgs chk{disallowed_ids, n_disallowed, hit};
+    return encode_batch_impl(c, utf8, doc_off, n_docs, use_special, allowed_ids, n_allowed, tokens_out, n_tokens_out, tok_off_out, false, false, &chk);
 }
 
 // Debug / test entry: the piece-start offsets the GPU pre-tokeniser produces for a packed batch
@@ -2338,12 +2460,14 @@ struct ShardResult {
     uint32_t* tokens = nullptr;
     uint64_t n_tokens = 0;
     std::vector<uint64_t> tok_off;
+    tk_special_hit hit{};  // (a checked call, rc == TK_DISALLOWED_SPECIAL) in the shard's own document numbers
 };
 
 // every core encodes its document range from its own host thread; on_device: the ids stay in each core's out_tokens / out_tok_off
 static int group_encode(tk_group* g, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special, const uint32_t* allowed_ids,
-                        uint64_t n_allowed, std::vector<ShardResult>& res, std::vector<uint64_t>& first, bool on_device) {
+                        uint64_t n_allowed, std::vector<ShardResult>& res, std::vector<uint64_t>& first, bool on_device, const CheckArgs* chk = nullptr) {
     if (!g) return fail(TK_VALUE_ERROR, "group is null");
+    if (chk && chk->n && !chk->hit) return fail(TK_VALUE_ERROR, "null argument");
     if (!doc_off) return fail(TK_VALUE_ERROR, "null argument");
     TRY(check_offsets(doc_off, n_docs, "doc_off"));
     const uint32_t R = (uint32_t)g->cores.size();
@@ -2357,8 +2481,9 @@ static int group_encode(tk_group* g, const uint8_t* utf8, const uint64_t* doc_of
             for (uint64_t k = 0; k <= nd; ++k) off[k] = doc_off[d0 + k] - doc_off[d0];
             ShardResult& o = res[r];
             if (!on_device) o.tok_off.assign(nd + 1, 0);
+            const CheckArgs shard_chk{chk ? chk->ids : nullptr, chk ? chk->n : 0, &o.hit};
             o.rc = encode_batch_impl(g->cores[r], utf8 + doc_off[d0], off.data(), nd, use_special, allowed_ids, n_allowed, &o.tokens, &o.n_tokens,
-                                     on_device ? nullptr : o.tok_off.data(), on_device, false);
+                                     on_device ? nullptr : o.tok_off.data(), on_device, false, shard_chk.n ? &shard_chk : nullptr);
             if (o.rc != TK_OK) o.err = tk_last_error();  // (thread-local message of this worker)
         });
     }
@@ -2366,7 +2491,12 @@ static int group_encode(tk_group* g, const uint8_t* utf8, const uint64_t* doc_of
     for (uint32_t r = 0; r < R; ++r)
         if (res[r].rc != TK_OK) {
             const int rc = res[r].rc;
-            const std::string msg = "device " + std::to_string(g->cores[r]->device) + ": " + res[r].err;
+            std::string msg = "device " + std::to_string(g->cores[r]->device) + ": " + res[r].err;
+            if (rc == TK_DISALLOWED_SPECIAL) {  // shards are document ranges in order: the first shard that reports one holds the batch's first
+                *chk->hit = res[r].hit;
+                chk->hit->doc += first[r];
+                msg = "disallowed special token " + std::to_string(chk->hit->id) + " in document " + std::to_string(chk->hit->doc) + " at byte " + std::to_string(chk->hit->pos);
+            }
             for (auto& o : res) tk_free(o.tokens);
             return fail(rc, msg);
         }
@@ -2374,15 +2504,14 @@ static int group_encode(tk_group* g, const uint8_t* utf8, const uint64_t* doc_of
 }
 
 // Encoding.encode_ordinary_batch / encode_batch over several GPUs; same contract as tk_encode_batch.
-extern "C" int tk_group_encode_batch(tk_group* g, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special,
-                                     const uint32_t* allowed_ids, uint64_t n_allowed, uint32_t** tokens_out, uint64_t* n_tokens_out,
-                                     uint64_t* tok_off_out) {
+static int group_encode_batch_impl(tk_group* g, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special, const uint32_t* allowed_ids,
+                                   uint64_t n_allowed, uint32_t** tokens_out, uint64_t* n_tokens_out, uint64_t* tok_off_out, const CheckArgs* chk) {
     if (!tokens_out || !n_tokens_out) return fail(TK_VALUE_ERROR, "null argument");
     if (!g) return fail(TK_VALUE_ERROR, "group is null");
     std::lock_guard<std::mutex> lk(g->mu);
     std::vector<ShardResult> res;
     std::vector<uint64_t> first;
-    TRY(group_encode(g, utf8, doc_off, n_docs, use_special, allowed_ids, n_allowed, res, first, false));
+    TRY(group_encode(g, utf8, doc_off, n_docs, use_special, allowed_ids, n_allowed, res, first, false, chk));
     uint64_t total = 0;
     std::vector<uint64_t> base(res.size() + 1, 0);
     for (size_t r = 0; r < res.size(); ++r) {
@@ -2407,6 +2536,19 @@ extern "C" int tk_group_encode_batch(tk_group* g, const uint8_t* utf8, const uin
     *tokens_out = host;
     *n_tokens_out = total;
     return TK_OK;
+}
+
+extern "C" int tk_group_encode_batch(tk_group* g, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special,
+                                     const uint32_t* allowed_ids, uint64_t n_allowed, uint32_t** tokens_out, uint64_t* n_tokens_out,
+                                     uint64_t* tok_off_out) {
+    return group_encode_batch_impl(g, utf8, doc_off, n_docs, use_special, allowed_ids, n_allowed, tokens_out, n_tokens_out, tok_off_out, nullptr);
+}
+// ... with the disallowed special tokens checked on every shard's device: the hit with the lowest document index, in the batch's numbering
+extern "C" int tk_group_encode_batch_checked(tk_group* g, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special,
+                                             const uint32_t* allowed_ids, uint64_t n_allowed, uint32_t** tokens_out, uint64_t* n_tokens_out,
+                                             uint64_t* tok_off_out, const uint32_t* disallowed_ids, uint64_t n_disallowed, tk_special_hit* hit) {
+    const CheckArgs chk{disallowed_ids, n_disallowed, hit};
+    return group_encode_batch_impl(g, utf8, doc_off, n_docs, use_special, allowed_ids, n_allowed, tokens_out, n_tokens_out, tok_off_out, &chk);
 }
 
 // raw[0 .. n]: a shard's own token offsets; out[k] = raw[k] + base for its documents (k < n), and out[n] as well when `last`
@@ -2664,6 +2806,7 @@ extern "C" uint64_t tk_stat(tk_core* c, const char* name) {
     if (k == "mid_calls") return c->st_mid_calls;  // documents of 2 .. 128 KiB encoded as segments in one launch
     if (k == "back_streams") return (uint64_t)c->n_back;  // streams found to run beside the front stream (0: no multi-chunk batch yet)
     if (k == "resynced") return c->st_resynced;  // batches repeated because a deferred tile gave up while the host was not waiting (stage_deferred)
+    if (k == "spec_find_launches") return c->st_find_launches;  // launches of the disallowed scan (tk_k_spec_find) since the core was made: one per chunk of a checked call
     if (k == "regrown") return c->st_regrown;  // batches repeated with a larger miss data since the core was made (encode_device_locked)
     if (k == "workspace_bytes") {             // device memory of the work sets (everything but the text, the tables and the outputs)
         uint64_t t = 0;
@@ -2687,6 +2830,7 @@ extern "C" uint64_t tk_stat(tk_core* c, const char* name) {
     if (k == "host_tail_us") return (uint64_t)c->host_us[4];
     if (k == "host_total_us") return (uint64_t)c->host_us[5];
     if (k == "chunk_bytes") return c->chunk_bytes;
+    if (k == "stage_bytes") return TK_STAGE_BYTES;  // a block of text on its way to the device; host-buffer batches of twice that and more are pipelined (encode_batch_impl)
 #ifdef TKF_TIMING
     if (k.rfind("time_", 0) == 0) {  // (experiments: tk_fused.h, TKT)
         static unsigned long long acc[2 * 1024 * 16];

@@ -5,11 +5,13 @@
 //   tk_k_mark_docs      document starts -> break bitmap          (core.py:174-176: documents never interact)
 //   tk_k_spec_*         (encode() path only) special-token occurrences -> start / interior / break bitmaps
 //                                                                 (src/lib.rs:386-402)
+//   tk_k_spec_find      the first occurrence of a disallowed special token        (tiktoken/core.py:116-124)
 //   tk_k_count/_scan_small/_emit   piece-start bitmap -> packed piece offsets (tk_pretokenize_batch)
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "tk_device.h"
+#include "tk_special.h"
 
 #define TK_TILE 3840  // text bytes per tile: with 128 bytes of left context and 128 of look-ahead the LDS window is 4096 = 256 lanes x 16
 
@@ -175,96 +177,42 @@ __global__ void tk_k_mark_docs(const uint64_t* __restrict__ doc_off, uint64_t n_
 // ------------------------------------------------------------------------------------------
 // special tokens (encode() with allowed_special; src/lib.rs:386-402, 426-434)
 // ------------------------------------------------------------------------------------------
-// Longest allowed special token that matches at text[pos..] without crossing a document start.
-// Returns its length (0 = none) and index.  The next 32 text bytes and the document starts among the next 64 positions are read once; a
-// special token of at most 32 bytes is compared with them word by word (four independent loads of its bytes instead of a load per byte
-// that waits for the byte before it: the resolving pass calls this two or three times per candidate, one lane of a wavefront at a time).
-__device__ __forceinline__ uint64_t tk_bits64(const uint32_t* __restrict__ bm, uint64_t pos) {  // bits [pos, pos + 64) of a bitmap (readable two words past them)
-    const uint64_t wi = pos >> 5;
-    const uint32_t sh = (uint32_t)(pos & 31);
-    const uint32_t w0 = bm[wi], w1 = bm[wi + 1], w2 = bm[wi + 2];
-    const uint64_t lo = ((uint64_t)w1 << 32) | w0;
-    return sh ? ((lo >> sh) | ((uint64_t)w2 << (64u - sh))) : lo;
-}
-__device__ __forceinline__ uint32_t tk_special_at(const TkTables& T, const uint8_t* __restrict__ text, uint64_t pos, uint64_t n,
-                                                  const uint8_t* __restrict__ allowed, const uint32_t* __restrict__ docb,
-                                                  uint32_t* idx_out) {
-    uint32_t b0 = text[pos];
-    if (!((T.spec_first[b0 >> 5] >> (b0 & 31)) & 1u)) return 0;
-    uint64_t tw[4];  // (the text is readable 64 bytes past n)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) tw[i] = tk_load8(text, pos + 8u * i);
-    const uint64_t db = docb ? tk_bits64(docb, pos + 1) : 0ull;  // document starts at pos + 1 .. pos + 64
-    uint32_t best = 0, bi = 0;
-    for (uint32_t k = 0; k < T.n_spec; ++k) {
-        // (round 6: a token's first eight bytes, length and offset in one load that depends on nothing -- the loads of all tokens are in flight
-        // together; a candidate that is no special token, "<|x", leaves after it.  Offsets, first byte and bytes were four dependent loads per token.)
-        const uint4 hd = ((const uint4*)T.spec_head)[k];
-        const uint32_t o = hd.w, len = hd.z;
-        if (len <= best || pos + len > n) continue;
-        if (tk_mask_low_bytes(tw[0] ^ (((uint64_t)hd.y << 32) | hd.x), len < 8u ? len : 8u) != 0ull) continue;
-        if (allowed && !allowed[k]) continue;
-        bool ok = true;
-        if (len <= 32u) {
-#pragma unroll
-            for (int i = 1; i < 4; ++i)
-                if (8u * i < len) ok = ok && tk_mask_low_bytes(tw[i] ^ tk_load8(T.spec_bytes, (uint64_t)o + 8u * i), len - 8u * i) == 0ull;
-            ok = ok && (db & ((1ull << (len - 1u)) - 1ull)) == 0ull;
-        } else {
-            for (uint32_t i = 1; i < len && ok; ++i) ok = (text[pos + i] == T.spec_bytes[o + i]) && !(docb && tk_bit(docb, pos + i));
-        }
-        if (ok) {
-            best = len;
-            bi = k;
-        }
-    }
-    *idx_out = bi;
-    return best;
-}
-
 // Candidates: positions at which an allowed special token matches.  16 text bytes per thread; almost every byte fails the first-byte
-// test, so the kernel is one coalesced read of the text.  With at most four distinct first bytes (every stock encoding: '<') the test is
-// four byte-equality tests per 32-bit word (x ^ c has a zero byte; the borrow may mark a byte above a true hit as well: a false
-// candidate, which tk_special_at rejects); otherwise the 256-bit set decides byte by byte.
+// test (tk_spec_hits16), so the kernel is one coalesced read of the text.
 __global__ void tk_k_spec_cand(TkTables T, const uint8_t* __restrict__ text, uint64_t n, const uint8_t* __restrict__ allowed,
                                const uint32_t* __restrict__ docb, uint32_t* __restrict__ cand) {
     for (uint64_t p0 = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) * 16; p0 < n; p0 += (uint64_t)gridDim.x * blockDim.x * 16) {
         const uint4 v = *(const uint4*)(text + p0);  // (text is readable 64 bytes past n)
         const uint32_t nxt = *(const uint32_t*)(text + p0 + 16) & 0xFFu;  // (the byte behind the sixteen, asked for together with them: inside `if (hits)` it was a second trip for every wavefront with a '<')
         const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-        uint32_t hits = 0;
-        if (T.n_spec_fb <= 4u) {
-            for (uint32_t f = 0; f < T.n_spec_fb; ++f) {
-                const uint32_t c4 = ((T.spec_fb >> (8u * f)) & 0xFFu) * 0x01010101u;
-#pragma unroll
-                for (int d = 0; d < 4; ++d) {
-                    const uint32_t x = w[d] ^ c4;
-                    const uint32_t z = (x - 0x01010101u) & ~x & 0x80808080u;  // bit 7 of every zero byte (and, rarely, of a 0x01 above one)
-                    // bits 7, 15, 23, 31 -> bits 0..3
-                    hits |= (((z >> 7) | (z >> 14) | (z >> 21) | (z >> 28)) & 0xFu) << (4 * d);
-                }
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 16; ++k) {
-                const uint32_t b = (w[k >> 2] >> ((k & 3) * 8)) & 0xFFu;
-                hits |= ((T.spec_first[b >> 5] >> (b & 31)) & 1u) << k;
-            }
-        }
-        if (hits) {  // the byte behind a hit must be some special token's second byte ("<" is common in web text, "<|" is not)
-            uint32_t keep = 0;
-            for (uint32_t m = hits; m; m &= m - 1) {
-                const uint32_t k = (uint32_t)__ffs((int)m) - 1u;
-                const uint32_t b1 = k < 15u ? (w[(k + 1) >> 2] >> (((k + 1) & 3u) * 8u)) & 0xFFu : nxt;
-                keep |= ((T.spec_second[b1 >> 5] >> (b1 & 31u)) & 1u) << k;
-            }
-            hits = keep;
-        }
+        uint32_t hits = tk_spec_hits16(T, w, nxt);
         while (hits) {
             const uint64_t pos = p0 + (uint32_t)(__ffs((int)hits) - 1);
             hits &= hits - 1;
             uint32_t idx;
             if (pos < n && tk_special_at(T, text, pos, n, allowed, docb, &idx)) atomicOr(&cand[pos >> 5], 1u << (pos & 31));
+        }
+    }
+}
+
+// The first disallowed special token of a chunk (Encoding.encode's disallowed_special, tiktoken/core.py:116-124): the same read of the
+// text as tk_k_spec_cand, against the set `disallowed`.  *first (all ones before the launch) receives base + the leftmost position at
+// which a token of the set matches wholly inside one document.  Matches are rare or absent in text that passes; in text dense with
+// them a thread looks at the current minimum first, and only a match below it goes to the atomic.
+__global__ void tk_k_spec_find(TkTables T, const uint8_t* __restrict__ text, uint64_t n, const uint8_t* __restrict__ disallowed,
+                               const uint32_t* __restrict__ docb, uint64_t base, unsigned long long* __restrict__ first) {
+    for (uint64_t p0 = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) * 16; p0 < n; p0 += (uint64_t)gridDim.x * blockDim.x * 16) {
+        const uint4 v = *(const uint4*)(text + p0);  // (text is readable 64 bytes past n)
+        const uint32_t nxt = *(const uint32_t*)(text + p0 + 16) & 0xFFu;
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+        const uint32_t hits = tk_spec_hits16(T, w, nxt);
+        if (!hits) continue;
+        const unsigned long long cur = __hip_atomic_load(first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur <= base + p0) return;  // (every later position of this thread lies behind the minimum as well)
+        const uint64_t pos = tk_spec_find16(T, text, p0, n, hits, disallowed, docb, cur - base);
+        if (pos != ~0ull) {
+            atomicMin(first, (unsigned long long)(base + pos));
+            return;
         }
     }
 }
