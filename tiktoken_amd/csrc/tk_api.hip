@@ -13,9 +13,11 @@
 #include <algorithm>
 #include <atomic>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/tiktoken_amd.h"
@@ -39,9 +41,24 @@ static int fail(int code, const std::string& msg) {
             return fail(TK_RUNTIME_ERROR, std::string("HIP error: ") + hipGetErrorString(e__) + " at " #expr); \
     } while (0)
 
-struct Buf {
+// ------------------------------------------------------------------------------------------
+// Owners.  Every device buffer, page-locked block, stream and event of this file belongs to one of these and goes with it: nothing
+// below (the pinned pool aside) calls hipFree / hipHostFree / hipStreamDestroy / hipEventDestroy itself.  Movable, not copyable; each converts to its raw handle.
+// ------------------------------------------------------------------------------------------
+struct Buf {  // device memory
     void* p = nullptr;
     size_t cap = 0;
+    Buf() = default;
+    Buf(Buf&& o) noexcept : p(o.p), cap(o.cap) {
+        o.p = nullptr;
+        o.cap = 0;
+    }
+    Buf& operator=(Buf&& o) noexcept {  // (the old block goes with `o`)
+        std::swap(p, o.p);
+        std::swap(cap, o.cap);
+        return *this;
+    }
+    ~Buf() { if (p) (void)hipFree(p); }
     template <class T>
     T* as() const { return (T*)p; }
 };
@@ -55,11 +72,45 @@ static int ensure(Buf& b, size_t bytes) {
     b.cap = want;
     return TK_OK;
 }
-static void release(Buf& b) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-}
+static void release(Buf& b) { b = Buf(); }  // the explicit early free
+template <class T>
+struct Pinned {  // a page-locked host block (the flags are the call site's)
+    T* p = nullptr;
+    Pinned() = default;
+    Pinned(Pinned&& o) noexcept : p(o.p) { o.p = nullptr; }
+    ~Pinned() { if (p) (void)hipHostFree(p); }
+    hipError_t alloc(size_t bytes, unsigned flags) { return hipHostMalloc((void**)&p, bytes, flags); }
+    operator T*() const { return p; }
+};
+struct Stream {  // default priority, hipStreamNonBlocking: the one kind this library makes (tk_create)
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(Stream&& o) noexcept : s(o.s) { o.s = nullptr; }
+    ~Stream() { if (s) (void)hipStreamDestroy(s); }
+    hipError_t create() { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+    operator hipStream_t() const { return s; }
+};
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    hipError_t create(bool timing = false) { return timing ? hipEventCreate(&e) : hipEventCreateWithFlags(&e, hipEventDisableTiming); }
+    operator hipEvent_t() const { return e; }
+};
+template <class T>
+struct HostResult {  // a result on its way to the caller, from the pinned pool (pinned_get) or from malloc: tk_free takes either
+    T* p = nullptr;
+    explicit HostResult(void* q = nullptr) : p((T*)q) {}
+    HostResult(HostResult&& o) noexcept : p(o.p) { o.p = nullptr; }
+    HostResult& operator=(HostResult&& o) noexcept {
+        std::swap(p, o.p);
+        return *this;
+    }
+    ~HostResult() { if (p) tk_free(p); }
+    T* release() { return std::exchange(p, nullptr); }  // success: the caller's from here on
+    operator T*() const { return p; }
+};
 
 struct KernelStat {
     double ms = 0;
@@ -69,23 +120,32 @@ struct KernelStat {
 #define TK_NAUX 6  // side streams of the merge kernels
 #define TK_NSET 4  // chunks in flight (work sets): the front kernel of chunk k + 1 runs while chunk k is merged and its tokens are placed
 
-// Work buffers of ONE chunk in flight.
+// Work buffers of ONE chunk in flight.  This list is the one place that names them: it declares the members and adds them up (WorkSet::bytes).
+#define TK_WORK_BUFS(X)                                                                                                                                  \
+    X(text_al) X(tile_sum) X(wide_ws) X(scan_sums) X(row_base) X(brk) X(docb) X(cand) X(ss) X(si) X(starts) X(blockcnt) X(pstart) X(res) X(staging)     \
+    X(listB) X(listC) X(counters) X(total) X(g_id) X(g_rk) X(g_nx) X(g_pv) X(g_lv) X(tile_np) X(tile_nt) X(mt_keys) X(mtab) X(movf) X(mcnt) X(wbin)       \
+    X(deferred) X(big) X(rx_spec) X(rx_gst) X(rx_lnk) X(rx_exit) X(merge_work) X(find)
+// (Members go in reverse order: the buffers, declared last, are freed first -- hipFree waits for the device -- then the events, the
+// stream and the page-locked words.)
 struct WorkSet {
-    Buf text_al, tile_sum, wide_ws, scan_sums, row_base, brk, docb, cand, ss, si, starts, blockcnt, pstart, res, staging, listB, listC, counters, total, g_id, g_rk,
-        g_nx, g_pv, g_lv, tile_np, tile_nt, mt_keys, mtab, movf, mcnt, wbin, deferred, big, rx_spec, rx_gst, rx_lnk, rx_exit, merge_work, find;
-    hipStream_t sb = nullptr;        // the set's back stage in a multi-chunk batch: back stages of different chunks overlap each other too
-                                     // (they are chains of short latency-bound kernels, ~2 ms however small the chunk)
-    hipEvent_t ev_front = nullptr;   // the front kernel is done
-    hipEvent_t ev_cnt = nullptr;     // ... and the deferred tiles: the counters are in h_counters
-    hipEvent_t ev_tot = nullptr;     // the chunk's token base and total are known (tok_bases[k + 1] written)
-    hipEvent_t ev_done = nullptr;    // the back stage is done: totals and counters are in h_total / h_counters + TK_CNT_N, the buffers are free
-    hipEvent_t ev_fork = nullptr, ev_join[TK_NAUX] = {};  // fork / join of the merge kernels on the side streams
-    uint32_t* h_counters = nullptr;  // pinned [2][TK_CNT_N]
-    uint64_t* h_total = nullptr;     // pinned [3]: tokens, pieces of the chunk; where its first disallowed special token starts (all ones: nowhere)
-    std::vector<Buf*> all() {
-        return {&text_al, &tile_sum, &wide_ws, &scan_sums, &row_base, &brk, &docb, &cand, &ss, &si, &starts, &blockcnt, &pstart, &res, &staging, &listB,
-                &listC, &counters, &total, &g_id, &g_rk, &g_nx, &g_pv, &g_lv, &tile_np, &tile_nt, &mt_keys, &mtab, &movf, &mcnt, &wbin, &deferred, &big, &rx_spec,
-                &rx_gst, &rx_lnk, &rx_exit, &merge_work, &find};
+    Pinned<uint32_t> h_counters;  // [2][TK_CNT_N]
+    Pinned<uint64_t> h_total;     // [3]: tokens, pieces of the chunk; where its first disallowed special token starts (all ones: nowhere)
+    Stream sb;                    // the set's back stage in a multi-chunk batch: back stages of different chunks overlap each other too
+                                  // (they are chains of short latency-bound kernels, ~2 ms however small the chunk)
+    Event ev_front;               // the front kernel is done
+    Event ev_cnt;                 // ... and the deferred tiles: the counters are in h_counters
+    Event ev_tot;                 // the chunk's token base and total are known (tok_bases[k + 1] written)
+    Event ev_done;                // the back stage is done: totals and counters are in h_total / h_counters + TK_CNT_N, the buffers are free
+    Event ev_fork, ev_join[TK_NAUX];  // fork / join of the merge kernels on the side streams
+#define X(name) Buf name;
+    TK_WORK_BUFS(X)
+#undef X
+    uint64_t bytes() const {  // device memory of the set
+        uint64_t t = 0;
+#define X(name) t += name.cap;
+        TK_WORK_BUFS(X)
+#undef X
+        return t;
     }
 };
 // What the front stage of a chunk leaves for its back stage.
@@ -109,11 +169,12 @@ static TkMiss miss_of(WorkSet& w, const ChunkJob& job) { return TkMiss{w.mtab.as
 
 struct tk_core {
     int device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t aux[TK_NAUX] = {};  // side streams: the merge kernels are independent of each other
-    hipStream_t cs_h2d = nullptr, cs_d2h = nullptr;  // copy streams of the host-buffer entry points (created on first use)
-    void* stage[2] = {nullptr, nullptr};             // page-locked staging buffers of tk_decode_batch (created on its first use)
-    hipEvent_t ev_stage[2] = {nullptr, nullptr};
+    // (members go in reverse order: the streams declared here outlive every buffer declared below)
+    Stream stream;
+    Stream aux[TK_NAUX];     // side streams: the merge kernels are independent of each other
+    Stream cs_h2d, cs_d2h;   // copy streams of the host-buffer entry points (created on first use)
+    Pinned<void> stage[2];   // page-locked staging buffers of tk_decode_batch (created on its first use)
+    Event ev_stage[2];
     TkHostTables H;
     TkTables D;  // device view
     Buf t_stage1, t_stage2, t_bmp, t_byte_tab, t_short, t_mid, t_dec, t_piece, t_piece_off, t_tok_bytes, t_pair, t_pair2, t_byte_rank, t_xl, t_xfilter, t_spec_bytes, t_spec_off, t_spec_id, t_spec_head;
@@ -153,7 +214,7 @@ struct tk_core {
     bool back_probed = false;
     hipStream_t back_s[3] = {};      // streams that share a queue neither with back_for nor with each other (as far as the pool has any)
     int n_back = 0;
-    uint32_t* h_probe = nullptr;     // page-locked words of the probe: [0] the gate, [1 ..] one per candidate
+    Pinned<uint32_t> h_probe;        // page-locked words of the probe: [0] the gate, [1 ..] one per candidate (made by the first probe)
     Buf out_tokens_alt, out_tok_off_alt;  // the other pair of result buffers of tk_encode_batch_device (tk_set_output_buffers(core, 2))
     uint32_t out_bufs = 1;
     bool ovf_full = false;  // a batch has asked for more overflow entries of the miss data than the default: room for the worst case from then on
@@ -170,12 +231,12 @@ struct tk_core {
     struct SmallSlot {
         std::atomic<int> busy{0};
         std::atomic<int> state{0};  // 0 idle, 1 ready (input written, waiting for a launch), 2 launched
-        uint8_t* in = nullptr;    // page-locked, device-visible: text of the call
-        uint32_t* out = nullptr;  // page-locked, device-visible: its result
+        Pinned<uint8_t> in;       // page-locked, device-visible: text of the call
+        Pinned<uint32_t> out;     // page-locked, device-visible: its result
         void *d_in = nullptr, *d_out = nullptr;
         uint32_t seq = 0, n = 0;
         Buf ws;
-        hipStream_t s = nullptr;
+        Stream s;
         bool ready = false;       // every piece above has been made (set last: a first use that failed half-way is repeated by the next caller)
     };
     SmallSlot small[TK_SMALL_SLOTS];
@@ -188,7 +249,7 @@ struct tk_core {
     std::atomic<int> mid_fail_run{0};  // such attempts in a row
     bool mid_cut = false;             // an ASCII letter followed by a space is a certain piece start of this pattern: documents of 2 .. 128 KiB are cut there
     uint64_t st_mid_calls = 0;
-    hipStream_t small_s[4] = {};
+    Stream small_s[4];
     uint32_t small_turn = 0;
     uint64_t st_small_launches = 0, st_small_calls = 0;
     std::vector<uint8_t> sorted_blob;  // token_byte_values(), packed (built on first use)
@@ -196,7 +257,11 @@ struct tk_core {
     // instrumentation
     bool profiling = false;
     std::map<std::string, KernelStat> stats;
-    std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> pending;
+    struct TimedPair {
+        std::string name;
+        Event a, b;
+    };
+    std::vector<TimedPair> pending;
     uint64_t st_bytes = 0, st_pieces = 0, st_tokens = 0, st_docs = 0, st_medium = 0, st_long = 0;
     uint64_t st_chunks = 0;
     double host_us[6] = {0, 0, 0, 0, 0, 0};  // host time of the last call: front stages, back stages (of which: waiting for the front kernel), finish waits, total
@@ -257,35 +322,30 @@ static int timed(tk_core* c, hipStream_t s, const char* name, F&& f) {
         HIPCHK(hipGetLastError());
         return TK_OK;
     }
-    hipEvent_t a = nullptr, b = nullptr;
-    hipError_t e = hipEventCreate(&a);
-    if (e == hipSuccess) e = hipEventCreate(&b);
-    if (e == hipSuccess) e = hipEventRecord(a, s);
+    tk_core::TimedPair t{name, {}, {}};
+    hipError_t e = t.a.create(true);
+    if (e == hipSuccess) e = t.b.create(true);
+    if (e == hipSuccess) e = hipEventRecord(t.a, s);
     if (e == hipSuccess) {
         f();
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipEventRecord(b, s);
-    if (e != hipSuccess) {  // (no event pair is left behind by a failed launch)
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-        return fail(TK_RUNTIME_ERROR, std::string("HIP error: ") + hipGetErrorString(e) + " in " + name);
-    }
-    c->pending.push_back({name, {a, b}});
+    if (e == hipSuccess) e = hipEventRecord(t.b, s);
+    if (e != hipSuccess) return fail(TK_RUNTIME_ERROR, std::string("HIP error: ") + hipGetErrorString(e) + " in " + name);  // (no event pair is left behind by a failed launch)
+    c->pending.push_back(std::move(t));
     return TK_OK;
 }
 static int drain_events(tk_core* c) {
-    for (auto& pe : c->pending) {
+    std::vector<tk_core::TimedPair> pending;  // (every pair goes with this list, whichever wait fails)
+    pending.swap(c->pending);
+    for (auto& pe : pending) {
         float ms = 0;
-        HIPCHK(hipEventSynchronize(pe.second.second));
-        HIPCHK(hipEventElapsedTime(&ms, pe.second.first, pe.second.second));
-        KernelStat& ks = c->stats[pe.first];
+        HIPCHK(hipEventSynchronize(pe.b));
+        HIPCHK(hipEventElapsedTime(&ms, pe.a, pe.b));
+        KernelStat& ks = c->stats[pe.name];
         ks.ms += ms;
         ks.launches += 1;
-        (void)hipEventDestroy(pe.second.first);
-        (void)hipEventDestroy(pe.second.second);
     }
-    c->pending.clear();
     return TK_OK;
 }
 #define TRY(x)                      \
@@ -324,35 +384,30 @@ extern "C" int tk_create(const uint8_t* ranks_blob, const uint64_t* ranks_off, c
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(TK_RUNTIME_ERROR, "no HIP device available: tiktoken_amd has no CPU path");
     if (device < 0 || device >= ndev) return fail(TK_VALUE_ERROR, "device ordinal out of range");
-    tk_core* c = new tk_core();
+    struct Destroy {
+        void operator()(tk_core* core) const { tk_destroy(core); }
+    };
+    std::unique_ptr<tk_core, Destroy> owner(new tk_core());  // (every early return below destroys what has been made; released into *out at the end)
+    tk_core* c = owner.get();
     c->device = device;
     std::string err = tk_build_tables(ranks_blob, ranks_off, ranks_ids, n_ranks, spec_blob, spec_off, spec_ids, n_spec, pat_str, &c->H);
-    if (!err.empty()) {
-        delete c;
-        return fail(TK_VALUE_ERROR, err);
-    }
-    auto bail = [&](int rc) {
-        tk_destroy(c);
-        return rc;
-    };
-    if (hipSetDevice(device) != hipSuccess) return bail(fail(TK_RUNTIME_ERROR, "hipSetDevice failed"));
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return bail(fail(TK_RUNTIME_ERROR, "hipStreamCreate failed"));
+    if (!err.empty()) return fail(TK_VALUE_ERROR, err);
+    if (hipSetDevice(device) != hipSuccess) return fail(TK_RUNTIME_ERROR, "hipSetDevice failed");
+    if (c->stream.create() != hipSuccess) return fail(TK_RUNTIME_ERROR, "hipStreamCreate failed");
     // All streams at the default priority.  (Measured, profiles/r03_stream_priority.txt: the mere existence of high-priority streams
     // in the process slows the front kernel from 5.76 to 6.28 ms per GiB even while nothing runs on them.)
     for (int i = 0; i < TK_NAUX; ++i)
-        if (hipStreamCreateWithFlags(&c->aux[i], hipStreamNonBlocking) != hipSuccess) return bail(fail(TK_RUNTIME_ERROR, "hipStreamCreate failed"));
+        if (c->aux[i].create() != hipSuccess) return fail(TK_RUNTIME_ERROR, "hipStreamCreate failed");
     for (WorkSet& w : c->ws) {
-        if (hipStreamCreateWithFlags(&w.sb, hipStreamNonBlocking) != hipSuccess) return bail(fail(TK_RUNTIME_ERROR, "hipStreamCreate failed"));
-        for (hipEvent_t* e : {&w.ev_front, &w.ev_cnt, &w.ev_tot, &w.ev_done, &w.ev_fork})
-            if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) return bail(fail(TK_RUNTIME_ERROR, "hipEventCreate failed"));
+        if (w.sb.create() != hipSuccess) return fail(TK_RUNTIME_ERROR, "hipStreamCreate failed");
+        for (Event* e : {&w.ev_front, &w.ev_cnt, &w.ev_tot, &w.ev_done, &w.ev_fork})
+            if (e->create() != hipSuccess) return fail(TK_RUNTIME_ERROR, "hipEventCreate failed");
         for (int i = 0; i < TK_NAUX; ++i)
-            if (hipEventCreateWithFlags(&w.ev_join[i], hipEventDisableTiming) != hipSuccess) return bail(fail(TK_RUNTIME_ERROR, "hipEventCreate failed"));
-        if (hipHostMalloc((void**)&w.h_counters, 2 * TK_CNT_N * 4 + 64, hipHostMallocDefault) != hipSuccess ||
-            hipHostMalloc((void**)&w.h_total, 64, hipHostMallocDefault) != hipSuccess)
-            return bail(fail(TK_RUNTIME_ERROR, "hipHostMalloc failed"));
+            if (w.ev_join[i].create() != hipSuccess) return fail(TK_RUNTIME_ERROR, "hipEventCreate failed");
+        if (w.h_counters.alloc(2 * TK_CNT_N * 4 + 64, hipHostMallocDefault) != hipSuccess || w.h_total.alloc(64, hipHostMallocDefault) != hipSuccess)
+            return fail(TK_RUNTIME_ERROR, "hipHostMalloc failed");
     }
     const TkHostTables& H = c->H;
-    int rc;
     auto upload_rx = [&](const TkRxCompiled& X) -> int {  // the program of the generic engine
         TRY(upload(c->t_rx_ins, X.ins.data(), X.ins.size() * sizeof(TkRxIns)));
         TRY(upload(c->t_rx_sets, X.sets.data(), X.sets.size() * sizeof(TkRxSet)));
@@ -396,42 +451,42 @@ extern "C" int tk_create(const uint8_t* ranks_blob, const uint64_t* ranks_off, c
         // a pattern of the scanner families: compiled for the generic engine as well, for stretches of text without certain starts
         // (stage_deferred); a family member the generic compiler cannot take keeps its scanners alone
         if (tk_rx_compile(pat_str, &c->rx_fb).empty()) {
-            if ((rc = upload_rx(c->rx_fb))) return bail(rc);
+            TRY(upload_rx(c->rx_fb));
             c->has_rx_fb = true;
         }
-        if ((rc = upload(c->t_stage1, tk_uc_stage1, sizeof tk_uc_stage1))) return bail(rc);
-        if ((rc = upload(c->t_stage2, tk_uc_stage2, sizeof tk_uc_stage2))) return bail(rc);
-        if ((rc = upload_bmp(tk_uc_stage1, tk_uc_stage2))) return bail(rc);
+        TRY(upload(c->t_stage1, tk_uc_stage1, sizeof tk_uc_stage1));
+        TRY(upload(c->t_stage2, tk_uc_stage2, sizeof tk_uc_stage2));
+        TRY(upload_bmp(tk_uc_stage1, tk_uc_stage2));
         uint32_t bt[256 * 2];
         tk_build_byte_table(tk_uc_stage1, tk_uc_stage2, bt);
-        if ((rc = upload(c->t_byte_tab, bt, sizeof bt))) return bail(rc);
+        TRY(upload(c->t_byte_tab, bt, sizeof bt));
     } else {
         // The generic engine splits (tk_regex_kernels.h) and hands every piece start to the front kernel as a hard start; the scanners
         // then run over a class table in which every char is a lower-case letter: a piece is a run of letters up to the next hard start.
         std::vector<uint8_t> s1(0x1100, 0), s2(256, (uint8_t)TK_C_LL);
-        if ((rc = upload(c->t_stage1, s1.data(), s1.size()))) return bail(rc);
-        if ((rc = upload(c->t_stage2, s2.data(), s2.size()))) return bail(rc);
-        if ((rc = upload_bmp(s1.data(), s2.data()))) return bail(rc);
+        TRY(upload(c->t_stage1, s1.data(), s1.size()));
+        TRY(upload(c->t_stage2, s2.data(), s2.size()));
+        TRY(upload_bmp(s1.data(), s2.data()));
         uint32_t bt[256 * 2];
         tk_build_byte_table(s1.data(), s2.data(), bt);
-        if ((rc = upload(c->t_byte_tab, bt, sizeof bt))) return bail(rc);
-        if ((rc = upload_rx(H.rx))) return bail(rc);
+        TRY(upload(c->t_byte_tab, bt, sizeof bt));
+        TRY(upload_rx(H.rx));
         c->has_rx = true;
     }
-    if ((rc = upload(c->t_short, H.short_tab.data(), H.short_tab.size() * sizeof(TkShortSlot)))) return bail(rc);
-    if ((rc = upload(c->t_mid, H.mid_tab.data(), H.mid_tab.size() * sizeof(TkPieceSlot)))) return bail(rc);
-    if ((rc = upload(c->t_piece, H.piece.data(), H.piece.size() * sizeof(TkPieceSlot)))) return bail(rc);
-    if ((rc = upload(c->t_piece_off, H.piece_off.data(), H.piece_off.size() * 4))) return bail(rc);
-    if ((rc = upload(c->t_tok_bytes, H.tok_bytes.data(), H.tok_bytes.size()))) return bail(rc);
-    if ((rc = upload(c->t_pair, H.pair8.empty() ? (const void*)H.pair.data() : (const void*)H.pair8.data(),
-                     H.pair8.empty() ? H.pair.size() * sizeof(TkPairSlot) : H.pair8.size() * 8))) return bail(rc);
-    if ((rc = upload(c->t_pair2, H.pair2.data(), H.pair2.size() * 4))) return bail(rc);
-    if ((rc = upload(c->t_byte_rank, H.byte_rank, sizeof H.byte_rank))) return bail(rc);
-    if ((rc = upload(c->t_xl, H.xl.data(), H.xl.size() * sizeof(TkXlSlot)))) return bail(rc);
-    if ((rc = upload(c->t_xfilter, H.xfilter.data(), H.xfilter.size() * 4))) return bail(rc);
-    if ((rc = upload(c->t_spec_bytes, H.spec_bytes.data(), H.spec_bytes.size()))) return bail(rc);
-    if ((rc = upload(c->t_spec_off, H.spec_off.data(), H.spec_off.size() * 4))) return bail(rc);
-    if ((rc = upload(c->t_spec_id, H.spec_id.data(), H.spec_id.size() * 4))) return bail(rc);
+    TRY(upload(c->t_short, H.short_tab.data(), H.short_tab.size() * sizeof(TkShortSlot)));
+    TRY(upload(c->t_mid, H.mid_tab.data(), H.mid_tab.size() * sizeof(TkPieceSlot)));
+    TRY(upload(c->t_piece, H.piece.data(), H.piece.size() * sizeof(TkPieceSlot)));
+    TRY(upload(c->t_piece_off, H.piece_off.data(), H.piece_off.size() * 4));
+    TRY(upload(c->t_tok_bytes, H.tok_bytes.data(), H.tok_bytes.size()));
+    TRY(upload(c->t_pair, H.pair8.empty() ? (const void*)H.pair.data() : (const void*)H.pair8.data(),
+                     H.pair8.empty() ? H.pair.size() * sizeof(TkPairSlot) : H.pair8.size() * 8));
+    TRY(upload(c->t_pair2, H.pair2.data(), H.pair2.size() * 4));
+    TRY(upload(c->t_byte_rank, H.byte_rank, sizeof H.byte_rank));
+    TRY(upload(c->t_xl, H.xl.data(), H.xl.size() * sizeof(TkXlSlot)));
+    TRY(upload(c->t_xfilter, H.xfilter.data(), H.xfilter.size() * 4));
+    TRY(upload(c->t_spec_bytes, H.spec_bytes.data(), H.spec_bytes.size()));
+    TRY(upload(c->t_spec_off, H.spec_off.data(), H.spec_off.size() * 4));
+    TRY(upload(c->t_spec_id, H.spec_id.data(), H.spec_id.size() * 4));
     TkTables& D = c->D;
     D.uc_stage1 = c->t_stage1.as<uint8_t>();
     D.uc_stage2 = c->t_stage2.as<uint8_t>();
@@ -462,7 +517,7 @@ extern "C" int tk_create(const uint8_t* ranks_blob, const uint64_t* ranks_off, c
     {
         std::vector<uint32_t> head;
         tk_spec_tables(H, head, D);
-        if ((rc = upload(c->t_spec_head, head.data(), head.size() * 4))) return bail(rc);
+        TRY(upload(c->t_spec_head, head.data(), head.size() * 4));
         D.spec_head = c->t_spec_head.as<uint32_t>();
     }
     D.pattern = H.pattern;
@@ -480,7 +535,7 @@ extern "C" int tk_create(const uint8_t* ranks_blob, const uint64_t* ranks_off, c
             std::vector<uint2> dec((size_t)max_id + 1, make_uint2(0, 0));
             for (const auto& kv : H.spec_decoder) dec[kv.first] = make_uint2(kv.second.first | TK_DEC_SPEC, kv.second.second);
             H.for_each_token([&](uint32_t r, uint32_t o, uint32_t l) { dec[r] = make_uint2(o, l); });  // (lib.rs:347-351: decoder first)
-            if ((rc = upload(c->t_dec, dec.data(), dec.size() * sizeof(uint2)))) return bail(rc);
+            TRY(upload(c->t_dec, dec.data(), dec.size() * sizeof(uint2)));
             c->n_dec = max_id + 1;
         }
     }
@@ -519,7 +574,7 @@ extern "C" int tk_create(const uint8_t* ranks_blob, const uint64_t* ranks_off, c
         fo.data.tab = (TkMissTab*)nextp(); fo.data.ovf = (TkMissOvf*)nextp(); fo.data.ovf_base = (uint32_t)nextp(); fo.ovf_cap = (uint32_t)nextp();
         fo.listC = (uint32_t*)nextp(); fo.counters = (uint32_t*)nextp();
         Buf okb;
-        if (ensure(okb, 64) != TK_OK) { tk_destroy(c); return TK_RUNTIME_ERROR; }
+        TRY(ensure(okb, 64));
         (void)hipMemsetAsync(okb.p, 0, 4, c->stream);
         hipLaunchKernelGGL(tk_k_front_args_check, dim3(1), dim3(64), 0, c->stream, Tt, (const uint8_t*)nextp(), (uint64_t)nextp(), (uint64_t)nextp(), (const uint32_t*)nextp(),
                            (const uint32_t*)nextp(), (const uint32_t*)nextp(), (const uint32_t*)nextp(), fo, (TkMissKey*)nextp(), (uint32_t)nextp(), (uint32_t*)nextp(),
@@ -527,54 +582,16 @@ extern "C" int tk_create(const uint8_t* ranks_blob, const uint64_t* ranks_off, c
         uint32_t ok = 0;
         const bool copied = hipMemcpyAsync(&ok, okb.p, 4, hipMemcpyDeviceToHost, c->stream) == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess;
         release(okb);
-        if (!copied || ok != 1u) {
-            tk_destroy(c);
-            return fail(TK_RUNTIME_ERROR, "internal error: the front kernel's arguments do not lie in the kernarg segment as TkFrontArgs says");
-        }
+        if (!copied || ok != 1u) return fail(TK_RUNTIME_ERROR, "internal error: the front kernel's arguments do not lie in the kernarg segment as TkFrontArgs says");
     }
-    *out = c;
+    *out = owner.release();
     return TK_OK;
 }
 
 extern "C" void tk_destroy(tk_core* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    for (Buf* b : {&c->t_rx_ins, &c->t_rx_sets, &c->t_rx_ranges, &c->t_rx_first, &c->t_rx_s1, &c->t_rx_s2, &c->t_rx_dtrans, &c->t_rx_dascii, &c->t_rx_ds1, &c->t_rx_ds2}) release(*b);
-    for (Buf* b : {&c->t_stage1, &c->t_stage2, &c->t_bmp, &c->t_byte_tab, &c->t_short, &c->t_mid, &c->t_dec, &c->d_tok, &c->d_lens, &c->d_bsum, &c->d_tboff, &c->d_bytes, &c->d_bytes_alt, &c->d_boff, &c->t_piece,
-                   &c->t_piece_off, &c->t_tok_bytes, &c->t_pair, &c->t_pair2, &c->t_byte_rank, &c->t_xl, &c->t_xfilter, &c->t_spec_bytes, &c->t_spec_off, &c->t_spec_id, &c->t_spec_head, &c->text, &c->doc_off,
-                   &c->out_tokens, &c->out_tok_off, &c->out_tokens_alt, &c->out_tok_off_alt, &c->allowed, &c->disallowed, &c->tok_bases})
-        release(*b);
-    if (c->h_probe) (void)hipHostFree(c->h_probe);
-    for (WorkSet& w : c->ws) {
-        for (Buf* b : w.all()) release(*b);
-        for (hipEvent_t e : {w.ev_front, w.ev_cnt, w.ev_tot, w.ev_done, w.ev_fork})
-            if (e) (void)hipEventDestroy(e);
-        for (int i = 0; i < TK_NAUX; ++i)
-            if (w.ev_join[i]) (void)hipEventDestroy(w.ev_join[i]);
-        if (w.sb) (void)hipStreamDestroy(w.sb);
-        if (w.h_counters) (void)hipHostFree(w.h_counters);
-        if (w.h_total) (void)hipHostFree(w.h_total);
-    }
-    for (auto& sl : c->small) {
-        if (sl.in) (void)hipHostFree(sl.in);
-        if (sl.out) (void)hipHostFree(sl.out);
-        if (sl.ws.p) (void)hipFree(sl.ws.p);
-        if (sl.s) (void)hipStreamDestroy(sl.s);
-    }
-    for (hipStream_t& ls : c->small_s) {
-        if (ls) (void)hipStreamDestroy(ls);
-        ls = nullptr;
-    }
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    for (int i = 0; i < TK_NAUX; ++i)
-        if (c->aux[i]) (void)hipStreamDestroy(c->aux[i]);
-    if (c->cs_h2d) (void)hipStreamDestroy(c->cs_h2d);
-    if (c->cs_d2h) (void)hipStreamDestroy(c->cs_d2h);
-    for (int i = 0; i < 2; ++i) {
-        if (c->stage[i]) (void)hipHostFree(c->stage[i]);
-        if (c->ev_stage[i]) (void)hipEventDestroy(c->ev_stage[i]);
-    }
-    delete c;
+    delete c;  // (its members free what they own)
 }
 
 // entries of the piece-id space of an n-byte chunk: TKF_CAP per tile (a tile's pieces form a run at tile * TKF_CAP)
@@ -1270,7 +1287,7 @@ __global__ void tk_k_touch(uint32_t* p) { __hip_atomic_store(p, 1u, __ATOMIC_REL
 static int streams_beside(tk_core* c, hipStream_t on, const std::vector<hipStream_t>& cand, std::vector<hipStream_t>* beside) {
     beside->clear();
     if (cand.empty()) return TK_OK;
-    if (!c->h_probe) HIPCHK(hipHostMalloc((void**)&c->h_probe, 64 * 4, hipHostMallocCoherent | hipHostMallocMapped));
+    if (!c->h_probe) HIPCHK(c->h_probe.alloc(64 * 4, hipHostMallocCoherent | hipHostMallocMapped));
     volatile uint32_t* h = c->h_probe;
     uint32_t* d = nullptr;
     HIPCHK(hipHostGetDevicePointer((void**)&d, c->h_probe, 0));
@@ -1535,8 +1552,8 @@ static unsigned copy_threads(unsigned hw) { return hw == 0 ? 4u : (hw > 16u ? 16
 
 // the copy streams of the host-buffer entry points
 static int ensure_copy_streams(tk_core* c) {
-    for (hipStream_t* cs : {&c->cs_h2d, &c->cs_d2h})
-        if (!*cs) HIPCHK(hipStreamCreateWithFlags(cs, hipStreamNonBlocking));
+    for (Stream* cs : {&c->cs_h2d, &c->cs_d2h})
+        if (!*cs) HIPCHK(cs->create());
     return TK_OK;
 }
 
@@ -1570,11 +1587,11 @@ static int encode_batch_impl(tk_core* c, const uint8_t* utf8, const uint64_t* do
 static int small_slot_init(tk_core* c, tk_core::SmallSlot* sl) {
     if (sl->ready) return TK_OK;  // (a first use that failed: what it did make is kept, the rest is made now)
     if (!sl->in) {
-        HIPCHK(hipHostMalloc((void**)&sl->in, TK_SMALL_MAX + 64, hipHostMallocCoherent | hipHostMallocMapped));
+        HIPCHK(sl->in.alloc(TK_SMALL_MAX + 64, hipHostMallocCoherent | hipHostMallocMapped));
         memset(sl->in, 0, TK_SMALL_MAX + 64);
     }
     if (!sl->out) {
-        HIPCHK(hipHostMalloc((void**)&sl->out, (TK_SMALL_HDR + TK_SMALL_MAX + 16) * 4, hipHostMallocCoherent | hipHostMallocMapped));
+        HIPCHK(sl->out.alloc((TK_SMALL_HDR + TK_SMALL_MAX + 16) * 4, hipHostMallocCoherent | hipHostMallocMapped));
         memset(sl->out, 0, (TK_SMALL_HDR + TK_SMALL_MAX + 16) * 4);
     }
     TRY(ensure(sl->ws, 256 * TK_SMALL_PIECE * 4));
@@ -1634,8 +1651,8 @@ static int small_wait(tk_core* c, tk_core::SmallSlot* const* mine, uint32_t k) {
                     R.r[cnt++] = TkSmallReq{(const uint8_t*)q.d_in, (uint32_t*)q.d_out, q.ws.as<uint32_t>(), q.n, q.seq};
             }
             if (cnt) {
-                hipStream_t& ls = c->small_s[c->small_turn++ & 3u];
-                if (!ls) HIPCHK(hipStreamCreateWithFlags(&ls, hipStreamNonBlocking));
+                Stream& ls = c->small_s[c->small_turn++ & 3u];
+                if (!ls) HIPCHK(ls.create());
                 hipLaunchKernelGGL(tk_k_small, dim3(cnt), dim3(256), 0, ls, c->D, R);
                 const hipError_t le = hipGetLastError();
                 if (le != hipSuccess) {
@@ -1793,7 +1810,7 @@ static int encode_small(tk_core* c, const uint8_t* utf8, uint32_t n, uint32_t** 
         memset(sl->in + n, 0, 8);
         sl->seq = ++sl->seq ? sl->seq : ++sl->seq;
         sl->n = n;
-        if (!sl->s) HIPCHK(hipStreamCreateWithFlags(&sl->s, hipStreamNonBlocking));
+        if (!sl->s) HIPCHK(sl->s.create());
         TkSmallReqs R{};
         R.r[0] = TkSmallReq{(const uint8_t*)sl->d_in, (uint32_t*)sl->d_out, sl->ws.as<uint32_t>(), n, sl->seq};
         TRY(timed(c, sl->s, "tk_k_small", [&] { hipLaunchKernelGGL(tk_k_small, dim3(1), dim3(256), 0, sl->s, c->D, R); }));
@@ -1868,16 +1885,11 @@ static int encode_batch_impl(tk_core* c, const uint8_t* utf8, const uint64_t* do
             *n_tokens_out = total;
             return TK_OK;
         }
-        uint32_t* host = (uint32_t*)(total * 4 >= (1u << 20) ? pinned_get((total ? total : 1) * 4) : malloc((total ? total : 1) * 4));
+        HostResult<uint32_t> host(total * 4 >= (1u << 20) ? pinned_get((total ? total : 1) * 4) : malloc((total ? total : 1) * 4));
         if (!host) return fail(TK_RUNTIME_ERROR, "out of host memory");
-        hipError_t e = hipSuccess;
-        if (total) e = hipMemcpy(host, c->out_tokens.p, total * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && tok_off_out) e = hipMemcpy(tok_off_out, c->out_tok_off.p, (n_docs + 1) * 8, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) {
-            tk_free(host);
-            return fail(TK_RUNTIME_ERROR, std::string("HIP error: ") + hipGetErrorString(e));
-        }
-        *tokens_out = host;
+        if (total) HIPCHK(hipMemcpy(host, c->out_tokens.p, total * 4, hipMemcpyDeviceToHost));
+        if (tok_off_out) HIPCHK(hipMemcpy(tok_off_out, c->out_tok_off.p, (n_docs + 1) * 8, hipMemcpyDeviceToHost));
+        *tokens_out = host.release();
         *n_tokens_out = total;
         return TK_OK;
     }
@@ -1890,13 +1902,10 @@ static int encode_batch_impl(tk_core* c, const uint8_t* utf8, const uint64_t* do
     // (filled by host threads, 64 MiB at a time, chunks of 128 MiB) took 32 ms.
     const uint64_t block_bytes = TK_STAGE_BYTES;
     const uint64_t n_blocks = (n_bytes + block_bytes - 1) / block_bytes;
-    std::vector<hipEvent_t> ev_block(n_blocks, nullptr);
-    for (auto& e : ev_block) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    auto drop_events = [&]() {
-        for (auto e : ev_block)
-            if (e) (void)hipEventDestroy(e);
-    };
-    // producer: send the text, block by block
+    std::vector<Event> ev_block(n_blocks);
+    for (auto& e : ev_block) HIPCHK(e.create());
+    // producer: send the text, block by block.  (Nothing returns between its start and producer.join() below: the events and the result
+    // buffer are let go only after it has ended.)
     std::atomic<int> h2d_rc{TK_OK};
     std::atomic<uint64_t> blocks_sent{0};
     const int dev = c->device;
@@ -1911,7 +1920,7 @@ static int encode_batch_impl(tk_core* c, const uint8_t* utf8, const uint64_t* do
     });
     // consumer side
     const unsigned nth = copy_threads(std::thread::hardware_concurrency());  // (a result buffer regrown: the ids so far copied over)
-    uint32_t* host = nullptr;
+    HostResult<uint32_t> host;
     uint64_t host_cap = 0;  // tokens
     ChunkHooks hooks;
     hooks.before = [&](uint64_t byte_end) -> int {
@@ -1927,14 +1936,13 @@ static int encode_batch_impl(tk_core* c, const uint8_t* utf8, const uint64_t* do
         if (need > host_cap || !host) {
             uint64_t est = last ? need : (uint64_t)((double)need / (double)(bytes_done ? bytes_done : 1) * (double)n_bytes * 1.08) + 4096;
             if (est < need) est = need;
-            uint32_t* nh = (uint32_t*)pinned_get((est ? est : 1) * 4);
+            HostResult<uint32_t> nh(pinned_get((est ? est : 1) * 4));
             if (!nh) return fail(TK_RUNTIME_ERROR, "out of page-locked host memory");
             if (host) {
                 HIPCHK(hipStreamSynchronize(c->cs_d2h));
                 if (tok_begin) parallel_memcpy(nh, host, tok_begin * 4, nth);
-                tk_free(host);
             }
-            host = nh;
+            host = std::move(nh);  // (the old buffer goes back to the pool with `nh`)
             host_cap = est;
         }
         if (n_tok) HIPCHK(hipMemcpyAsync(host + tok_begin, c->out_tokens.as<uint32_t>() + tok_begin, n_tok * 4, hipMemcpyDeviceToHost, c->cs_d2h));
@@ -1945,9 +1953,7 @@ static int encode_batch_impl(tk_core* c, const uint8_t* utf8, const uint64_t* do
     producer.join();
     hipError_t e = hipStreamSynchronize(c->cs_h2d);
     if (e == hipSuccess) e = hipStreamSynchronize(c->cs_d2h);
-    drop_events();
     if (rc == TK_SPEC_HIT) {  // (the text has arrived and nothing is on its way back: the caller's buffers are his again)
-        tk_free(host);
         if (e != hipSuccess) return fail(TK_RUNTIME_ERROR, std::string("HIP error: ") + hipGetErrorString(e));
         return report_hit(c, utf8 + c->find_hit, doc_off, n_docs, chk);
     }
@@ -1956,14 +1962,10 @@ static int encode_batch_impl(tk_core* c, const uint8_t* utf8, const uint64_t* do
         e = hipMemcpy(tok_off_out, c->out_tok_off.p, (n_docs + 1) * 8, hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = fail(TK_RUNTIME_ERROR, std::string("HIP error: ") + hipGetErrorString(e));
     }
-    if (rc != TK_OK) {
-        tk_free(host);
-        return rc;
-    }
+    TRY(rc);
     *n_tokens_out = total;
     if (device_result) return TK_OK;
-    if (!host) host = (uint32_t*)pinned_get(64);
-    *tokens_out = host;
+    *tokens_out = host ? host.release() : (uint32_t*)pinned_get(64);
     return TK_OK;
 }
 
@@ -2006,16 +2008,10 @@ extern "C" int tk_pretokenize_batch(tk_core* c, const uint8_t* utf8, const uint6
     TRY(run_chunk(c, s, c->text.as<uint8_t>(), n_bytes, c->doc_off.as<uint64_t>(), n_docs, 0, use_special && any, false, nullptr, nullptr, &P, true));
     HIPCHK(hipStreamSynchronize(s));
     TRY(drain_events(c));
-    uint32_t* host = (uint32_t*)malloc((P + 1) * 4);
+    HostResult<uint32_t> host(malloc((P + 1) * 4));
     if (!host) return fail(TK_RUNTIME_ERROR, "out of host memory");
-    {
-        hipError_t e = hipMemcpy(host, c->ws[0].pstart.p, (P + 1) * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) {
-            free(host);
-            return fail(TK_RUNTIME_ERROR, std::string("HIP error: ") + hipGetErrorString(e));
-        }
-    }
-    *starts_out = host;
+    HIPCHK(hipMemcpy(host, c->ws[0].pstart.p, (P + 1) * 4, hipMemcpyDeviceToHost));
+    *starts_out = host.release();
     *n_out = P + 1;
     return TK_OK;
 }
@@ -2047,16 +2043,10 @@ static int single_piece(tk_core* c, const uint8_t* piece, uint64_t len, bool no_
     TRY(run_chunk(c, s, c->text.as<uint8_t>(), len, nullptr, 0, 0, false, true, c->out_tokens.as<uint32_t>(), nullptr, &total, false, no_lookup));
     HIPCHK(hipStreamSynchronize(s));
     TRY(drain_events(c));
-    uint32_t* host = (uint32_t*)malloc((total ? total : 1) * 4);
+    HostResult<uint32_t> host(malloc((total ? total : 1) * 4));
     if (!host) return fail(TK_RUNTIME_ERROR, "out of host memory");
-    if (total) {
-        hipError_t e = hipMemcpy(host, c->out_tokens.p, total * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) {
-            free(host);
-            return fail(TK_RUNTIME_ERROR, std::string("HIP error: ") + hipGetErrorString(e));
-        }
-    }
-    *tokens_out = host;
+    if (total) HIPCHK(hipMemcpy(host, c->out_tokens.p, total * 4, hipMemcpyDeviceToHost));
+    *tokens_out = host.release();
     *n_tokens_out = total;
     return TK_OK;
 }
@@ -2213,8 +2203,8 @@ extern "C" int tk_decode_batch(tk_core* c, const uint32_t* tokens, const uint64_
     unsigned long long* d_tboff = byte_off_out ? c->d_tboff.as<unsigned long long>() : nullptr;
     TRY(ensure_copy_streams(c));
     for (int i = 0; i < 2; ++i) {  // the staging buffers (this entry's own: the text of tk_encode_batch goes straight from the caller's buffer)
-        if (!c->stage[i]) HIPCHK(hipHostMalloc(&c->stage[i], TK_STAGE_BYTES, hipHostMallocPortable));
-        if (!c->ev_stage[i]) HIPCHK(hipEventCreateWithFlags(&c->ev_stage[i], hipEventDisableTiming));
+        if (!c->stage[i]) HIPCHK(c->stage[i].alloc(TK_STAGE_BYTES, hipHostMallocPortable));
+        if (!c->ev_stage[i]) HIPCHK(c->ev_stage[i].create());
     }
     // is the caller's buffer page-locked (then the DMA engine reads it directly)?
     bool src_pinned = false;
@@ -2223,16 +2213,12 @@ extern "C" int tk_decode_batch(tk_core* c, const uint32_t* tokens, const uint64_
         if (n && hipPointerGetAttributes(&at, tokens) == hipSuccess) src_pinned = at.type == hipMemoryTypeHost;
         else (void)hipGetLastError();
     }
-    std::vector<hipEvent_t> ev_in(n_ranges, nullptr), ev_out(2, nullptr);
-    for (auto& e : ev_in) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (auto& e : ev_out) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    hipEvent_t ev_copy = nullptr;
-    HIPCHK(hipEventCreateWithFlags(&ev_copy, hipEventDisableTiming));
-    auto drop_events = [&]() {
-        for (auto e : ev_in) (void)hipEventDestroy(e);
-        for (auto e : ev_out) (void)hipEventDestroy(e);
-        (void)hipEventDestroy(ev_copy);
-    };
+    std::vector<Event> ev_in(n_ranges), ev_out(2);
+    for (auto& e : ev_in) HIPCHK(e.create());
+    for (auto& e : ev_out) HIPCHK(e.create());
+    Event ev_copy;
+    HIPCHK(ev_copy.create());
+    // (nothing returns between the producer's start and producer.join() below: events and result buffer are let go only after it has ended)
     std::atomic<int> h2d_rc{TK_OK};
     std::atomic<uint64_t> sent{0};
     const int dev = c->device;
@@ -2256,7 +2242,7 @@ extern "C" int tk_decode_batch(tk_core* c, const uint32_t* tokens, const uint64_
             sent.store(k + 1, std::memory_order_release);
         }
     });
-    uint8_t* host = nullptr;
+    HostResult<uint8_t> host;
     uint64_t host_cap = 0, base = 0;
     Buf* dout[2] = {&c->d_bytes, &c->d_bytes_alt};
     int rc = TK_OK;
@@ -2298,14 +2284,13 @@ extern "C" int tk_decode_batch(tk_core* c, const uint32_t* tokens, const uint64_
         if (need > host_cap || !host) {
             uint64_t est = done == n ? need : (uint64_t)((double)need / (double)done * (double)n * 1.06) + 4096;
             if (est < need) est = need;
-            uint8_t* nh = (uint8_t*)(est >= (1u << 20) || n_ranges > 1 ? pinned_get(est ? est : 1) : malloc(est ? est : 1));
+            HostResult<uint8_t> nh(est >= (1u << 20) || n_ranges > 1 ? pinned_get(est ? est : 1) : malloc(est ? est : 1));
             if (!nh) return fail(TK_RUNTIME_ERROR, "out of host memory");
             if (host) {
                 HIPCHK(hipStreamSynchronize(c->cs_d2h));
                 if (base) parallel_memcpy(nh, host, base, nth);
-                tk_free(host);
             }
-            host = nh;
+            host = std::move(nh);  // (the old buffer is freed with `nh`)
             host_cap = est;
         }
         const double t_3 = now_us();
@@ -2335,18 +2320,13 @@ extern "C" int tk_decode_batch(tk_core* c, const uint32_t* tokens, const uint64_
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e == hipSuccess) e = hipStreamSynchronize(c->cs_d2h);
     if (e == hipSuccess) e = hipGetLastError();
-    drop_events();
     if (c->dbg & TK_DBG_VERBOSE) fprintf(stderr, "decode: %llu ranges, ids %s, %.0f us\n", (unsigned long long)n_ranges, src_pinned ? "page-locked" : "staged", now_us() - t_call);
     if (rc == TK_KEY_ERROR && bad_pos != ~0ull) rc = fail(TK_KEY_ERROR, "Invalid token for decoding: " + std::to_string(tokens[bad_pos]));
     if (rc == TK_OK && e != hipSuccess) rc = fail(TK_RUNTIME_ERROR, std::string("HIP error: ") + hipGetErrorString(e));
     if (rc == TK_OK) rc = drain_events(c);  // (before the outputs are published: a caller that gets an error owns nothing)
     else (void)drain_events(c);
-    if (rc != TK_OK) {
-        if (host) tk_free(host);
-        return rc;
-    }
-    if (!host) host = (uint8_t*)malloc(1);
-    *bytes_out = host;
+    TRY(rc);
+    *bytes_out = host ? host.release() : (uint8_t*)malloc(1);
     *n_bytes_out = base;
     return TK_OK;
 }
@@ -2400,8 +2380,8 @@ struct tk_group {
     std::vector<tk_core*> cores;
     std::mutex mu;
     Buf root_tokens, root_off, root_raw;  // gathered results on cores[0]'s device; root_raw: the shards' own offsets before rebasing
-    std::vector<hipStream_t> gs;          // one copy stream per core, on the core's device
-    std::vector<hipEvent_t> ge;
+    std::vector<Stream> gs;               // one copy stream per core, on the core's device (made by the first device gather)
+    std::vector<Event> ge;
     std::vector<ncclComm_t> comms;        // RCCL communicators (one per core), empty: peer copies
     bool rccl_tried = false;
     uint64_t gathers_rccl = 0, gathers_peer = 0;
@@ -2418,18 +2398,15 @@ extern "C" int tk_group_create(tk_core** cores, uint32_t n, tk_group** out) {
 }
 extern "C" void tk_group_destroy(tk_group* g) {
     if (!g) return;
-    for (size_t r = 0; r < g->gs.size(); ++r) {
-        (void)hipSetDevice(g->cores[r]->device);
-        if (g->gs[r]) (void)hipStreamDestroy(g->gs[r]);
-        if (g->ge[r]) (void)hipEventDestroy(g->ge[r]);
+    while (!g->gs.empty()) {  // every core's stream and event with its device selected
+        (void)hipSetDevice(g->cores[g->gs.size() - 1]->device);
+        g->gs.pop_back();
+        g->ge.pop_back();
     }
     for (ncclComm_t cm : g->comms)
         if (cm) (void)g_rccl.CommDestroy(cm);
     if (!g->cores.empty()) (void)hipSetDevice(g->cores[0]->device);
-    release(g->root_tokens);
-    release(g->root_off);
-    release(g->root_raw);
-    delete g;
+    delete g;  // (the gathered results: on the first core's device)
 }
 extern "C" uint32_t tk_group_size(tk_group* g) { return g ? (uint32_t)g->cores.size() : 0; }
 // 1: the device gather of the last tk_group_encode_batch_device ran on RCCL, 0: on peer copies
@@ -2578,14 +2555,16 @@ extern "C" int tk_group_encode_batch_device(tk_group* g, const uint8_t* utf8, co
         total += res[r].n_tokens;
     }
     tk_core* root = g->cores[0];
-    if (g->gs.empty()) {
-        g->gs.assign(R, nullptr);
-        g->ge.assign(R, nullptr);
+    if (g->gs.empty()) {  // (the group gets them when all have been made: a first use that failed half-way is repeated by the next call)
+        std::vector<Stream> gs(R);
+        std::vector<Event> ge(R);
         for (size_t r = 0; r < R; ++r) {
             HIPCHK(hipSetDevice(g->cores[r]->device));
-            HIPCHK(hipStreamCreateWithFlags(&g->gs[r], hipStreamNonBlocking));
-            HIPCHK(hipEventCreateWithFlags(&g->ge[r], hipEventDisableTiming));
+            HIPCHK(gs[r].create());
+            HIPCHK(ge[r].create());
         }
+        g->gs = std::move(gs);
+        g->ge = std::move(ge);
     }
     if (!g->rccl_tried) {  // communicators once per group, when no device is named twice
         g->rccl_tried = true;
@@ -2810,8 +2789,7 @@ extern "C" uint64_t tk_stat(tk_core* c, const char* name) {
     if (k == "regrown") return c->st_regrown;  // batches repeated with a larger miss data since the core was made (encode_device_locked)
     if (k == "workspace_bytes") {             // device memory of the work sets (everything but the text, the tables and the outputs)
         uint64_t t = 0;
-        for (auto& w : c->ws)
-            for (Buf* b : w.all()) t += b->cap;
+        for (auto& w : c->ws) t += w.bytes();
         return t;
     }
     // (experiments) the deferred tiles of the last chunk of work set 0: "deferred_count", "deferred_tile_<i>" (read from the device: the caller has waited for the call)
