@@ -141,6 +141,37 @@ int tk_decode_batch(tk_core* core, const uint32_t* tokens, const uint64_t* tok_o
  * consumer that keeps text on the device; no reference counterpart (the reference returns owned Vec<u8>s, src/lib.rs:345-358). */
 int tk_decode_batch_device(tk_core* core, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_docs, void* stream,
                            const uint8_t** d_bytes_out, uint64_t* n_bytes_out, const uint64_t** d_byte_off_out);
+/* Encoding.decode_with_offsets / decode_tokens_bytes for whole batches     tiktoken/core.py:312-335, :303-310
+ * Token spans: for every token of a packed batch where it starts in ITS document -- byte_start (the sum of the lengths of the document's
+ * tokens before it) and char_start (core.py:327-331: the chars, i.e. bytes outside 0x80..0xBF, before it, less one when the token's first
+ * byte is a continuation byte, never below 0) --, both uint32; and per document byte_off / char_off (uint64[n_docs + 1]): the bytes / chars
+ * of the documents before it.  A token's bytes are bytes[byte_off[d] + byte_start[i] ..), the next token's start or byte_off[d + 1] their end.
+ * TK_KEY_ERROR as tk_decode_bytes; TK_UNSUPPORTED when the ids are too sparse for a direct table (as tk_decode_batch); TK_VALUE_ERROR for a
+ * document that decodes to 4 GiB or more.  One device per call: a group has no spans entry.
+ *
+ * Device pointers in (ids uint32, d_tok_off uint64[n_docs + 1], required), device pointers out: buffers of the core, valid until its next
+ * decode or spans call.  d_doc_off (may be null): the byte offsets of the documents' TEXT when the ids come from an encode call
+ * (tk_encode_batch_device's d_doc_off) -- then every document's tokens must add up to its length; they do not only where a pat_str of the
+ * generic engine leaves chars unmatched (find_iter skips them, src/lib.rs:365,405): TK_UNSUPPORTED naming the first such document. */
+int tk_token_spans_device(tk_core* core, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_docs, const void* d_doc_off,
+                          void* stream, const uint32_t** d_byte_start_out, const uint32_t** d_char_start_out, const uint64_t** d_byte_off_out,
+                          const uint64_t** d_char_off_out);
+/* Host buffers in and out (core.py:312-335 over a batch).  bytes_out null: spans only.  *bytes_out, *byte_start_out, *char_start_out:
+ * library-owned (tk_free); byte_off_out / char_off_out (may be null): caller's arrays of n_docs + 1.  validate != 0: the decoded documents are
+ * checked on the device as bytes.decode("utf-8", "strict") checks them (core.py:334) and *invalid_doc_out is the first document, in order,
+ * that is not well-formed (all ones: none; a sequence cut by a document boundary is ill-formed in both documents).  The call still returns
+ * TK_OK and every output: the caller decodes that one document to raise the reference's UnicodeDecodeError.  Batches of 32 Mi ids and more run
+ * in overlapped ranges of 16 Mi ids, as tk_decode_batch's do. */
+int tk_decode_batch_spans(tk_core* core, const uint32_t* tokens, const uint64_t* tok_off, uint64_t n_docs, int validate, uint8_t** bytes_out,
+                          uint64_t* n_bytes_out, uint32_t** byte_start_out, uint32_t** char_start_out, uint64_t* byte_off_out,
+                          uint64_t* char_off_out, uint64_t* invalid_doc_out);
+/* tk_encode_batch -- with n_disallowed != 0: tk_encode_batch_checked -- plus the spans of the tokens it returns (core.py:312-335 applied to
+ * core.py:164-206's result without a decode call in between): the span pass runs over the ids while they are on the device, against
+ * doc_off.  *byte_start_out / *char_start_out: library-owned (tk_free).  TK_UNSUPPORTED for text a generic pat_str leaves unmatched (above). */
+int tk_encode_batch_spans(tk_core* core, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special,
+                          const uint32_t* allowed_ids, uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed,
+                          uint32_t** tokens_out, uint64_t* n_tokens_out, uint64_t* tok_off_out, uint32_t** byte_start_out,
+                          uint32_t** char_start_out, tk_special_hit* hit);
 /* CoreBPE.decode_single_token_bytes(token)  (pointer into the core; do not free)  src/py.rs:164-172 */
 int tk_decode_single_token_bytes(tk_core* core, uint32_t token, const uint8_t** bytes_out, uint64_t* len_out);
 /* CoreBPE.token_byte_values(): tokens in lexicographic byte order                  src/py.rs:178-183, lib.rs:648-650 */

@@ -76,6 +76,12 @@ def lib() -> ctypes.CDLL:
         L.tk_decode_batch.argtypes = [vp, vp, vp, u64, P(vp), P(u64), vp]
         L.tk_decode_batch_device.restype = i32
         L.tk_decode_batch_device.argtypes = [vp, vp, u64, vp, u64, vp, P(vp), P(u64), P(vp)]
+        L.tk_token_spans_device.restype = i32
+        L.tk_token_spans_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, P(vp), P(vp), P(vp), P(vp)]
+        L.tk_decode_batch_spans.restype = i32
+        L.tk_decode_batch_spans.argtypes = [vp, vp, vp, u64, i32, P(vp), P(u64), P(vp), P(vp), vp, vp, P(u64)]
+        L.tk_encode_batch_spans.restype = i32
+        L.tk_encode_batch_spans.argtypes = [vp, vp, vp, u64, i32, vp, u64, vp, u64, P(vp), P(u64), vp, P(vp), P(vp), P(SpecialHit)]
         L.tk_decode_single_token_bytes.restype = i32
         L.tk_decode_single_token_bytes.argtypes = [vp, u32, P(vp), P(u64)]
         L.tk_n_tokens.restype = u64

@@ -3,7 +3,8 @@
 
 Same constructor and the same eleven methods, same exception types.  Two additive entry points,
 `encode_batch_packed` and `pretokenize_packed`, expose the batch shape the GPU actually runs
-(one launch sequence per batch instead of one FFI call per document).  With `disallowed_special` the batch
+(one launch sequence per batch instead of one FFI call per document); `decode_batch_spans_packed`, `token_spans_device` and
+`encode_batch_spans_packed` give, for whole batches, where every token starts in its document (bytes and chars).  With `disallowed_special` the batch
 calls also search the text for those special tokens, on the device, and raise `DisallowedSpecialError`.
 """
 from __future__ import annotations
@@ -71,6 +72,15 @@ def _take_u32(ptr: ctypes.c_void_p, n: int) -> np.ndarray:
     if n >= (1 << 16):
         return np.asarray(_OwnedBuffer(ptr.value, n))
     out = np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctypes.c_uint32)), shape=(n,)).copy()
+    _lib.lib().tk_free(ptr)
+    return out
+
+
+def _take_u8(ptr: ctypes.c_void_p, n: int) -> np.ndarray:
+    """... of a uint8 result (read-only use: decoded bytes)."""
+    if n >= (1 << 16):
+        return np.asarray(_OwnedBuffer(ptr.value, n, "|u1"))
+    out = np.frombuffer(ctypes.string_at(ptr, n), dtype=np.uint8)
     _lib.lib().tk_free(ptr)
     return out
 
@@ -525,6 +535,75 @@ class CoreBPE:
                                             ctypes.byref(nb), ctypes.byref(do))
         _lib.raise_for(rc)
         return db.value or 0, nb.value, do.value or 0
+
+    # ------------------------------------------------------------------ token spans (tiktoken/core.py:303-335 over batches)
+    def _one_device(self, what: str) -> None:
+        if self._group is not None:
+            raise ValueError(f"{what} runs on one device: this CoreBPE was built with {len(self.devices)}")
+
+    def decode_batch_spans_packed(self, tokens: np.ndarray, tok_off: np.ndarray, *, want_bytes: bool = True, validate: bool = True):
+        """One GPU call for a packed batch (tk_decode_batch_spans): where every token starts in its own document.
+        Returns (data, byte_off, char_off, byte_start, char_start, invalid_doc):
+          data         uint8 array of all decoded bytes back to back (None without want_bytes)
+          byte_off     uint64[n_docs + 1], the bytes of the documents before each document; char_off likewise in chars
+          byte_start   uint32[T], the byte of its document at which token i starts: its bytes are data[byte_off[d] + byte_start[i] : ...]
+          char_start   uint32[T], the reference's offset (Encoding.decode_with_offsets, core.py:327-331)
+          invalid_doc  with validate: the first document whose bytes are not well-formed UTF-8, or None -- the reference raises for it
+                       (core.py:334); decode that document's bytes to get Python's own UnicodeDecodeError."""
+        self._one_device("decode_batch_spans_packed")
+        tokens = np.ascontiguousarray(tokens, dtype=np.uint32)
+        tok_off = np.ascontiguousarray(tok_off, dtype=np.uint64)
+        if tok_off.ndim != 1 or len(tok_off) < 1 or int(tok_off[-1]) != len(tokens):
+            raise ValueError("tok_off must hold n_docs + 1 offsets ending at len(tokens)")
+        n_docs = len(tok_off) - 1
+        byte_off, char_off = np.empty(n_docs + 1, dtype=np.uint64), np.empty(n_docs + 1, dtype=np.uint64)
+        data, nb, bs, cs, bad = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64()
+        src = tokens if len(tokens) else np.zeros(1, dtype=np.uint32)
+        rc = self._L.tk_decode_batch_spans(self._h, src.ctypes.data, tok_off.ctypes.data, n_docs, 1 if validate else 0, ctypes.byref(data) if want_bytes else None,
+                                           ctypes.byref(nb), ctypes.byref(bs), ctypes.byref(cs), byte_off.ctypes.data, char_off.ctypes.data, ctypes.byref(bad))
+        _lib.raise_for(rc)
+        n = len(tokens)
+        return (_take_u8(data, nb.value) if want_bytes else None, byte_off, char_off, _take_u32(bs, n), _take_u32(cs, n),
+                int(bad.value) if validate and bad.value != 0xFFFFFFFFFFFFFFFF else None)
+
+    def token_spans_device(self, d_tokens: int, n_tokens: int, d_tok_off: int, n_docs: int, d_doc_off: int = 0, stream: int = 0):
+        """Device-resident spans (tk_token_spans_device): pointers to uint32 ids and uint64[n_docs + 1] token offsets on this core's device ->
+        device pointers (byte_start uint32[n_tokens], char_start uint32[n_tokens], byte_off uint64[n_docs + 1], char_off uint64[n_docs + 1]),
+        the library's buffers, valid until the next decode or spans call.  d_doc_off: the offsets of the documents' text when the ids are
+        the result of `encode_batch_device` -- ValueError if a document's tokens do not add up to its text."""
+        self._one_device("token_spans_device")
+        out = [ctypes.c_void_p() for _ in range(4)]
+        rc = self._L.tk_token_spans_device(self._h, d_tokens or None, n_tokens, d_tok_off or None, n_docs, d_doc_off or None, stream or None,
+                                           *[ctypes.byref(x) for x in out])
+        _lib.raise_for(rc)
+        return tuple(x.value or 0 for x in out)
+
+    def encode_batch_spans_packed(self, blob: np.ndarray, doc_off: np.ndarray, allowed_special: AbstractSet[str] | None = None, *,
+                                  disallowed_special=None):
+        """`encode_batch_packed` plus the spans of the tokens it returns (tk_encode_batch_spans), computed while the ids are on the device:
+        (tokens uint32[T], tok_off uint64[n+1], byte_start uint32[T], char_start uint32[T]); token i of document d is
+        blob[doc_off[d] + byte_start[i] : ...].  ValueError naming the document where a pat_str leaves characters of the text unmatched."""
+        self._one_device("encode_batch_spans_packed")
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        doc_off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+        _check_packed(blob, doc_off)
+        n_docs = len(doc_off) - 1
+        tok_off = np.empty(n_docs + 1, dtype=np.uint64)
+        out, n, bs, cs = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_void_p(), ctypes.c_void_p()
+        src = blob if len(blob) else np.zeros(1, dtype=np.uint8)
+        if allowed_special is None:
+            ids, k, mode = np.zeros(1, dtype=np.uint32), 0, 0
+        else:
+            ids, k = self._allowed_ids(allowed_special)
+            mode = 1
+        dis, n_dis = self._disallowed_ids(disallowed_special)
+        hit = _lib.SpecialHit()
+        rc = self._L.tk_encode_batch_spans(self._h, src.ctypes.data, doc_off.ctypes.data, n_docs, mode, ids.ctypes.data, k, dis.ctypes.data, n_dis,
+                                           ctypes.byref(out), ctypes.byref(n), tok_off.ctypes.data, ctypes.byref(bs), ctypes.byref(cs), ctypes.byref(hit))
+        if rc == _lib.TK_DISALLOWED_SPECIAL:
+            self._raise_hit(hit)
+        _lib.raise_for(rc)
+        return _take_u32(out, n.value), tok_off, _take_u32(bs, n.value), _take_u32(cs, n.value)
 
     def decode_single_token_bytes(self, token: int) -> bytes:
         if not 0 <= token <= 0xFFFFFFFF:

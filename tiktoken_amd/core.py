@@ -201,6 +201,35 @@ class Encoding:
             raise RuntimeError(f"internal error: the device reported the disallowed special token {e.token!r} in document {e.doc} at byte "
                                f"{e.pos}, the host search finds none there") from e
 
+    def encode_ordinary_batch_offsets_packed(self, text: Sequence[str]):
+        """`encode_ordinary_batch_packed` plus where every token starts in its text: (tokens uint32[T], tok_off uint64[n+1],
+        byte_start uint32[T], char_start uint32[T]) -- offsets into the text's UTF-8 and into the text (what `decode_with_offsets` of the
+        same tokens gives), computed in the same GPU call."""
+        blob, off = self._pack(text)
+        return self._core_bpe.encode_batch_spans_packed(blob, off, None)
+
+    def encode_batch_offsets_packed(self, text: Sequence[str], *, allowed_special: Literal["all"] | AbstractSet[str] = set(),  # noqa: B006
+                                    disallowed_special: Literal["all"] | Collection[str] = "all"):
+        """`encode_batch_packed` plus where every token starts in its text (see `encode_ordinary_batch_offsets_packed`); the special-token
+        arguments as in `encode`.  A text that needed surrogate repair is measured in its repaired form."""
+        allowed_special, disallowed_special = self._special_policy(allowed_special, disallowed_special)
+        if not disallowed_special:
+            blob, off = self._pack(text)
+            return self._core_bpe.encode_batch_spans_packed(blob, off, allowed_special)
+        if not isinstance(disallowed_special, frozenset):
+            disallowed_special = frozenset(disallowed_special)
+        blob, off, repaired = self._pack_repaired(text)
+        if repaired or not all(t in self._special_tokens for t in disallowed_special):  # (as encode_batch_packed: the host's search)
+            for t in text:
+                self._reject_disallowed(t, disallowed_special)
+            return self._core_bpe.encode_batch_spans_packed(blob, off, allowed_special)
+        try:
+            return self._core_bpe.encode_batch_spans_packed(blob, off, allowed_special, disallowed_special=disallowed_special)
+        except _tiktoken.DisallowedSpecialError as e:
+            self._reject_disallowed(text[e.doc], disallowed_special)
+            raise RuntimeError(f"internal error: the device reported the disallowed special token {e.token!r} in document {e.doc} at byte "
+                               f"{e.pos}, the host search finds none there") from e
+
     def encode_ordinary_batch(self, text: list[str], *, num_threads: int = 8) -> list[list[int]]:
         """Encode a list of strings, ignoring special tokens (one GPU batch; `num_threads` is kept for
         signature compatibility)."""
@@ -238,13 +267,39 @@ class Encoding:
     def decode_single_token_bytes(self, token: int) -> bytes:
         return self._core_bpe.decode_single_token_bytes(token)
 
-    def decode_tokens_bytes(self, tokens: Sequence[int]) -> list[bytes]:
+    def _decode_tokens_bytes_host(self, tokens: Sequence[int]) -> list[bytes]:
         return [self.decode_single_token_bytes(t) for t in tokens]
+
+    def _spans_on_device(self, tokens: Sequence[int]) -> bool:
+        """Whether the single forms below go through the batch call.  Not when the ids are too sparse for the device table or the core has
+        several devices (the batch call refuses both), and not when an id has no token or does not fit uint32: the per-token path then
+        raises what it always raised (KeyError with the id).  Any other error of the batch call is the caller's to see."""
+        core = self._core_bpe
+        if getattr(core, "_group", None) is not None or self.max_token_value >= 1 << 26:
+            return False
+        try:
+            arr = np.asarray(tokens, dtype=np.int64)
+        except (OverflowError, TypeError, ValueError):
+            return False
+        return arr.ndim == 1 and (not len(arr) or (0 <= int(arr.min()) and int(arr.max()) <= 0xFFFFFFFF))
+
+    def decode_tokens_bytes(self, tokens: Sequence[int]) -> list[bytes]:
+        if self._spans_on_device(tokens):
+            try:
+                return self.decode_tokens_bytes_batch([tokens])[0]
+            except KeyError:  # (an id without a token)
+                pass
+        return self._decode_tokens_bytes_host(tokens)
 
     def decode_with_offsets(self, tokens: Sequence[int]) -> tuple[str, list[int]]:
         """Text plus, per token, the index of the character in which the token starts (a token that begins
         with a continuation byte is attributed to the character it continues).  Strict UTF-8."""
-        pieces = self.decode_tokens_bytes(tokens)
+        if self._spans_on_device(tokens):
+            try:
+                return self.decode_with_offsets_batch([tokens])[0]
+            except KeyError:  # (an id without a token)
+                pass
+        pieces = self._decode_tokens_bytes_host(tokens)
         offsets: list[int] = []
         n_chars = 0
         for piece in pieces:
@@ -252,6 +307,46 @@ class Encoding:
             offsets.append(max(0, n_chars - (1 if starts_mid_char else 0)))
             n_chars += sum(1 for b in piece if not 0x80 <= b < 0xC0)
         return b"".join(pieces).decode("utf-8", errors="strict"), offsets
+
+    # ---- the same for whole batches: one GPU call (tk_decode_batch_spans), no per-token work on the host
+    @staticmethod
+    def _flatten(batch: Sequence[Sequence[int]]):
+        """(ids uint32[T], tok_off uint64[n + 1]) of a batch of token lists"""
+        lens = np.fromiter((len(t) for t in batch), dtype=np.uint64, count=len(batch))
+        tok_off = np.zeros(len(batch) + 1, dtype=np.uint64)
+        np.cumsum(lens, out=tok_off[1:])
+        return np.fromiter((t for doc in batch for t in doc), dtype=np.uint32, count=int(tok_off[-1])), tok_off
+
+    def decode_with_offsets_packed(self, tokens: "npt.NDArray[np.uint32]", tok_off: "npt.NDArray[np.uint64]"):
+        """`decode_with_offsets` for a packed batch (ids of all documents back to back, tok_off uint64[n + 1]), as arrays:
+        (data uint8 -- the documents' UTF-8 back to back --, byte_off uint64[n + 1], char_off uint64[n + 1], byte_start uint32[T],
+        char_start uint32[T]).  char_start[i] is the reference's offset of token i in its own document's text, byte_start[i] the same
+        in bytes: the token's bytes are data[byte_off[d] + byte_start[i] : ...].  Like the reference, raises UnicodeDecodeError (Python's
+        own, for the first such document) when a document is not valid UTF-8, and KeyError for an id without a token."""
+        data, byte_off, char_off, byte_start, char_start, bad = self._core_bpe.decode_batch_spans_packed(tokens, tok_off)
+        if bad is not None:
+            bytes(data[int(byte_off[bad]):int(byte_off[bad + 1])]).decode("utf-8", "strict")
+            raise RuntimeError(f"internal error: the device reported document {bad} as invalid UTF-8, Python decodes it")
+        return data, byte_off, char_off, byte_start, char_start
+
+    def decode_with_offsets_batch(self, batch: Sequence[Sequence[int]]) -> list[tuple[str, list[int]]]:
+        """`decode_with_offsets` of every document of a batch, in one GPU call."""
+        flat, tok_off = self._flatten(batch)
+        data, byte_off, _, _, char_start = self.decode_with_offsets_packed(flat, tok_off)
+        view = memoryview(data)
+        bb, tb = byte_off.tolist(), tok_off.tolist()
+        return [(str(view[bb[d]:bb[d + 1]], "utf-8", "strict") if bb[d + 1] > bb[d] else "", char_start[tb[d]:tb[d + 1]].tolist()) for d in range(len(batch))]
+
+    def decode_tokens_bytes_batch(self, batch: Sequence[Sequence[int]]) -> list[list[bytes]]:
+        """`decode_tokens_bytes` of every document of a batch: the packed bytes of one GPU call, cut at the tokens' byte offsets."""
+        flat, tok_off = self._flatten(batch)
+        data, byte_off, _, byte_start, _, _ = self._core_bpe.decode_batch_spans_packed(flat, tok_off, validate=False)
+        starts = byte_start.astype(np.uint64) + np.repeat(byte_off[:-1], np.diff(tok_off).astype(np.int64))  # in the batch: ascending, so a token ends where the next starts
+        cuts = starts.tolist() + [int(byte_off[-1])]
+        raw = data.tobytes()
+        pieces = [raw[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
+        tb = tok_off.tolist()
+        return [pieces[tb[d]:tb[d + 1]] for d in range(len(batch))]
 
     def decode_batch(self, batch: Sequence[Sequence[int]], *, errors: str = "replace", num_threads: int = 8) -> list[str]:
         """Decode a batch; the whole batch goes to the GPU in one call (`num_threads` is accepted for compatibility)."""
@@ -264,12 +359,7 @@ class Encoding:
     def _decode_packed(self, batch: Sequence[Sequence[int]]):
         """(uint8 array of all bytes back to back -- a view of the library's result buffer --, list of n + 1 byte offsets), or (None, None)
         when the ids are too sparse for the device table."""
-        import numpy as np
-
-        lens = np.fromiter((len(t) for t in batch), dtype=np.uint64, count=len(batch))
-        tok_off = np.zeros(len(batch) + 1, dtype=np.uint64)
-        np.cumsum(lens, out=tok_off[1:])
-        flat = np.fromiter((t for doc in batch for t in doc), dtype=np.uint32, count=int(tok_off[-1]))
+        flat, tok_off = self._flatten(batch)
         try:
             data, byte_off = self._core_bpe.decode_batch_packed(flat, tok_off, as_array=True)
         except ValueError:  # (ids too sparse for the device table)

@@ -22,6 +22,7 @@
 
 #include "../../include/tiktoken_amd.h"
 #include "tk_decode.h"
+#include "tk_offsets.h"
 #include "tk_fused.h"
 #include "tk_mid_plan.h"
 #include "tk_tables.h"
@@ -224,6 +225,10 @@ struct tk_core {
     uint32_t rx_grid_cap = 65536;    // most workgroups of tk_k_rx_speculate_staged (each walks the stretches with the stride of the grid: a chunk of more than 2 GiB, or $TIKTOKEN_AMD_RX_GRID_CAP)
     uint32_t n_dec = 0;  // entries of the device decode table (0: ids too sparse for a direct table -- decode stays on the host)
     Buf d_tok, d_lens, d_bsum, d_tboff, d_bytes, d_bytes_alt, d_boff;  // decode workspace (d_bytes_alt: the other range's bytes on their way to the host)
+    // Token spans (tk_offsets.h).  t_cw: the second per-id table, beside t_dec and with its indexing (tk_char_word); d_span: byte_start and
+    // char_start of every token; d_span_blk: per workgroup {chars, mark key, document start bytes / chars}; d_span_marks: document starts over
+    // the tokens, d_span_bmarks: over the decoded bytes; d_span_doc: byte_off, char_off, then the TK_SPAN_WORDS report words.
+    Buf t_cw, d_span, d_span_blk, d_span_marks, d_span_bmarks, d_span_doc;
     // Small calls (tk_k_small) do not take `mu`: the reference's normal use is several threads on one Encoding (core.py:175, a thread pool
     // over encode; lib.rs:232-238 keeps a regex per thread for it), and a small call needs nothing of the shared workspace -- a slot of its
     // own (page-locked text and result buffers the kernel reads and writes directly, merge scratch, a stream) is all.  A caller takes a
@@ -537,6 +542,11 @@ extern "C" int tk_create(const uint8_t* ranks_blob, const uint64_t* ranks_off, c
             H.for_each_token([&](uint32_t r, uint32_t o, uint32_t l) { dec[r] = make_uint2(o, l); });  // (lib.rs:347-351: decoder first)
             TRY(upload(c->t_dec, dec.data(), dec.size() * sizeof(uint2)));
             c->n_dec = max_id + 1;
+            // ... and id -> char word (core.py:330-331: what the token adds to the char count, whether it starts inside a char), special tokens from their text
+            std::vector<uint32_t> cw((size_t)max_id + 1, 0u);
+            for (const auto& kv : H.spec_decoder) cw[kv.first] = tk_char_word(H.spec_bytes.data() + kv.second.first, kv.second.second);
+            H.for_each_token([&](uint32_t r, uint32_t o, uint32_t l) { cw[r] = tk_char_word(H.tok_bytes.data() + o, l); });
+            TRY(upload(c->t_cw, cw.data(), cw.size() * sizeof(uint32_t)));
         }
     }
     if (const char* e = getenv("TIKTOKEN_AMD_CHUNK_BYTES")) {
@@ -1582,7 +1592,7 @@ static void parallel_memcpy(void* dst, const void* src, size_t n, unsigned nth) 
 
 static int encode_batch_impl(tk_core* c, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special, const uint32_t* allowed_ids,
                              uint64_t n_allowed, uint32_t** tokens_out, uint64_t* n_tokens_out, uint64_t* tok_off_out, bool device_result, bool no_small,
-                             const CheckArgs* chk = nullptr);
+                             const CheckArgs* chk = nullptr, bool locked = false);
 // ---- the slots of the small-call path (tk_core::SmallSlot) ----
 static int small_slot_init(tk_core* c, tk_core::SmallSlot* sl) {
     if (sl->ready) return TK_OK;  // (a first use that failed: what it did make is kept, the rest is made now)
@@ -1843,7 +1853,7 @@ static int encode_small(tk_core* c, const uint8_t* utf8, uint32_t n, uint32_t** 
 // several-GPU gather needs; the one-launch small path (which writes straight to host memory) is not taken then.
 static int encode_batch_impl(tk_core* c, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special,
                              const uint32_t* allowed_ids, uint64_t n_allowed, uint32_t** tokens_out, uint64_t* n_tokens_out,
-                             uint64_t* tok_off_out, bool device_result, bool no_small, const CheckArgs* chk) {
+                             uint64_t* tok_off_out, bool device_result, bool no_small, const CheckArgs* chk, bool locked /* the caller holds c->mu (and passes no_small) */) {
     if (!c) return fail(TK_VALUE_ERROR, "core is null");
     if (!doc_off || (!device_result && !tokens_out) || !n_tokens_out) return fail(TK_VALUE_ERROR, "null argument");
     TRY(check_offsets(doc_off, n_docs, "doc_off"));
@@ -1863,7 +1873,8 @@ static int encode_batch_impl(tk_core* c, const uint8_t* utf8, const uint64_t* do
             return TK_OK;
         }
     }
-    std::lock_guard<std::mutex> lk(c->mu);
+    std::unique_lock<std::mutex> lk(c->mu, std::defer_lock);
+    if (!locked) lk.lock();
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     TRY(ensure(c->text, n_bytes + 256));
@@ -2328,6 +2339,305 @@ extern "C" int tk_decode_batch(tk_core* c, const uint32_t* tokens, const uint64_
     TRY(rc);
     *bytes_out = host ? host.release() : (uint8_t*)malloc(1);
     *n_bytes_out = base;
+    return TK_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Token spans (tk_offsets.h): Encoding.decode_with_offsets (tiktoken/core.py:312-335) and decode_tokens_bytes (:303-310) for packed batches.
+// ------------------------------------------------------------------------------------------
+struct SpanView {  // device buffers of the core, valid until its next decode or spans call
+    uint32_t *byte_start = nullptr, *char_start = nullptr;
+    uint64_t *byte_off = nullptr, *char_off = nullptr;
+    uint64_t n_bytes = 0, n_chars = 0;
+    uint64_t bad_doc = ~0ull;  // the first document that is not well-formed UTF-8 (when asked for)
+};
+// The span passes in their parts; the caller holds c->mu.  spans_begin: the buffers of a batch of n tokens in n_docs documents, the report
+// words, the document starts over the tokens.  spans_range: the three passes over the tokens [a, a + cnt) (a: a multiple of TK_DEC_BLOCK;
+// ranges in order, the last one ends at n).  spans_end: the per-document pass, then the host waits and looks at the report words.
+static int spans_begin(tk_core* c, hipStream_t s, uint64_t n, const uint64_t* d_tok_off, uint64_t n_docs, SpanView* out, unsigned long long** words_out) {
+    if (!c->n_dec) return fail(TK_UNSUPPORTED, "token ids are too sparse for the device decode table");
+    const uint64_t nb = n / TK_DEC_BLOCK + 1;  // (workgroups over the positions 0 .. n)
+    TRY(ensure(c->d_lens, (n + 1) * 4));
+    TRY(ensure(c->d_bsum, (nb + 8) * 8));
+    TRY(ensure(c->d_span, (n + 1) * 8));
+    TRY(ensure(c->d_span_blk, nb * 8 * 4));
+    TRY(ensure(c->d_span_marks, (n / 32 + 4) * 4));
+    TRY(ensure(c->d_span_doc, ((n_docs + 1) * 2 + TK_SPAN_WORDS) * 8));
+    out->byte_start = c->d_span.as<uint32_t>();
+    out->char_start = out->byte_start + n + 1;
+    out->byte_off = c->d_span_doc.as<uint64_t>();
+    out->char_off = out->byte_off + n_docs + 1;
+    unsigned long long* words = (unsigned long long*)(out->char_off + n_docs + 1);
+    const unsigned long long h_words[TK_SPAN_WORDS] = {~0ull, ~0ull, ~0ull, ~0ull, 0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(words, h_words, sizeof h_words, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(c->d_span_marks.p, 0, (n / 32 + 4) * 4, s));
+    TRY(timed(c, s, "tk_k_span_mark", [&] {
+        hipLaunchKernelGGL(tk_k_span_mark, dim3(grid_for(n_docs + 1, 256, 4096)), dim3(256), 0, s, d_tok_off, n_docs + 1, n, c->d_span_marks.as<uint32_t>());
+    }));
+    *words_out = words;
+    return TK_OK;
+}
+static int spans_range(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n, uint64_t a, uint64_t cnt, const uint64_t* d_tok_off, uint64_t n_docs,
+                       const SpanView* v, unsigned long long* words) {
+    const uint32_t end = a + cnt == n ? 1u : 0u;
+    const uint64_t nb_all = n / TK_DEC_BLOCK + 1, b0 = a / TK_DEC_BLOCK, nb = (cnt + end + TK_DEC_BLOCK - 1) / TK_DEC_BLOCK;
+    unsigned long long* bsum = c->d_bsum.as<unsigned long long>() + b0;  // (where tk_k_dec_copy reads the workgroups' bases)
+    unsigned long long *csum = c->d_span_blk.as<unsigned long long>() + b0, *mkey = csum + nb_all, *doc_b = mkey + nb_all, *doc_c = doc_b + nb_all;
+    uint32_t* lens = c->d_lens.as<uint32_t>() + a;
+    const uint8_t* marks = c->d_span_marks.as<uint8_t>() + a / 8;
+    const uint32_t* cw = c->t_cw.as<uint32_t>();
+    if (nb)
+        TRY(timed(c, s, "tk_k_span_len", [&] {
+            hipLaunchKernelGGL(tk_k_span_len, dim3((uint32_t)nb), dim3(256), 0, s, d_tok + a, cnt, end, a, c->t_dec.as<uint2>(), cw, c->n_dec, marks, lens, bsum, csum, mkey, words);
+        }));
+    TRY(timed(c, s, "tk_k_span_scan", [&] { hipLaunchKernelGGL(tk_k_span_scan, dim3(1), dim3(1024), 0, s, bsum, csum, mkey, nb, doc_b, doc_c, words); }));
+    if (nb)
+        TRY(timed(c, s, "tk_k_span_write", [&] {
+            hipLaunchKernelGGL(tk_k_span_write, dim3((uint32_t)nb), dim3(256), 0, s, d_tok + a, cnt, end, a, cw, c->n_dec, lens, marks, d_tok_off, n_docs, bsum, csum, doc_b, doc_c,
+                               v->byte_start + a, v->char_start + a, v->byte_off, v->char_off);
+        }));
+    return TK_OK;
+}
+static int spans_end(tk_core* c, hipStream_t s, const uint32_t* d_tok, const uint64_t* d_tok_off, uint64_t n_docs, const uint64_t* d_doc_off, SpanView* out,
+                     unsigned long long* words) {
+    TRY(timed(c, s, "tk_k_span_docs", [&] {
+        hipLaunchKernelGGL(tk_k_span_docs, dim3(grid_for(n_docs + 1, 256, 4096)), dim3(256), 0, s, d_tok_off, out->byte_off, out->char_off, d_doc_off, n_docs, words);
+    }));
+    unsigned long long h_words[TK_SPAN_WORDS];
+    HIPCHK(hipMemcpyAsync(h_words, words, sizeof h_words, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    if (h_words[TK_SPAN_BAD_TOKEN] != ~0ull) {  // (reported as tk_k_dec_len's: the first id without an entry)
+        uint32_t bad_tok = 0;
+        (void)hipMemcpy(&bad_tok, d_tok + h_words[TK_SPAN_BAD_TOKEN], 4, hipMemcpyDeviceToHost);
+        return fail(TK_KEY_ERROR, "Invalid token for decoding: " + std::to_string(bad_tok));
+    }
+    if (h_words[TK_SPAN_BIG_DOC] != ~0ull)
+        return fail(TK_VALUE_ERROR, "document " + std::to_string(h_words[TK_SPAN_BIG_DOC]) + " decodes to 4 GiB or more: token spans are 32-bit offsets into a document");
+    if (h_words[TK_SPAN_GAP_DOC] != ~0ull)
+        return fail(TK_UNSUPPORTED, "document " + std::to_string(h_words[TK_SPAN_GAP_DOC]) +
+                                        ": its tokens do not add up to its text -- the pat_str leaves characters unmatched (they yield no token); token spans "
+                                        "across such gaps are not supported");
+    out->n_bytes = h_words[TK_SPAN_BYTES];
+    out->n_chars = h_words[TK_SPAN_CHARS];
+    return TK_OK;
+}
+// the strict UTF-8 check over the batch's bytes in c->d_bytes (queued; out->bad_doc is there once the stream has been waited for)
+static int spans_validate(tk_core* c, hipStream_t s, uint64_t n_docs, SpanView* out, unsigned long long* words) {
+    const uint64_t nbytes = out->n_bytes;
+    if (!nbytes) return TK_OK;
+    TRY(ensure(c->d_span_bmarks, (nbytes / 32 + 4) * 4));
+    HIPCHK(hipMemsetAsync(c->d_span_bmarks.p, 0, (nbytes / 32 + 4) * 4, s));
+    TRY(timed(c, s, "tk_k_span_mark", [&] {
+        hipLaunchKernelGGL(tk_k_span_mark, dim3(grid_for(n_docs + 1, 256, 4096)), dim3(256), 0, s, out->byte_off, n_docs + 1, nbytes, c->d_span_bmarks.as<uint32_t>());
+    }));
+    const uint64_t lanes = (nbytes + 15) / 16;
+    TRY(timed(c, s, "tk_k_utf8_docs", [&] {
+        hipLaunchKernelGGL(tk_k_utf8_docs, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, s, c->d_bytes.as<uint8_t>(), nbytes, c->d_span_bmarks.as<uint32_t>(), out->byte_off,
+                           n_docs, words);
+    }));
+    HIPCHK(hipMemcpyAsync(&out->bad_doc, words + TK_SPAN_BAD_UTF8, 8, hipMemcpyDeviceToHost, s));
+    return TK_OK;
+}
+// A whole batch that is on the device.  d_doc_off (may be null): the offsets of the documents' text -- the tokens of every document must
+// add up to its length.  want_bytes: the decoded bytes in c->d_bytes as well; validate: ... and checked (they are decoded for that in any case).
+static int spans_run(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n, const uint64_t* d_tok_off, uint64_t n_docs, const uint64_t* d_doc_off,
+                     bool want_bytes, bool validate, SpanView* out) {
+    unsigned long long* words = nullptr;
+    TRY(spans_begin(c, s, n, d_tok_off, n_docs, out, &words));
+    TRY(spans_range(c, s, d_tok, n, 0, n, d_tok_off, n_docs, out, words));
+    TRY(spans_end(c, s, d_tok, d_tok_off, n_docs, d_doc_off, out, words));
+    if (want_bytes || validate) {
+        TRY(ensure(c->d_bytes, out->n_bytes + 16));
+        if (n) TRY(decode_range_copy(c, s, d_tok, 0, n, c->d_bytes.as<uint8_t>(), nullptr, 0));
+        if (validate) TRY(spans_validate(c, s, n_docs, out, words));
+        HIPCHK(hipStreamSynchronize(s));
+        HIPCHK(hipGetLastError());
+    }
+    return TK_OK;
+}
+static int spans_locked(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n, const uint64_t* d_tok_off, uint64_t n_docs, const uint64_t* d_doc_off,
+                        bool want_bytes, bool validate, SpanView* out) {
+    const int rc = spans_run(c, s, d_tok, n, d_tok_off, n_docs, d_doc_off, want_bytes, validate, out);
+    const int rc2 = drain_events(c);  // (the timed pairs go whatever happened)
+    return rc != TK_OK ? rc : rc2;
+}
+
+extern "C" int tk_token_spans_device(tk_core* c, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_docs, const void* d_doc_off, void* stream,
+                                     const uint32_t** d_byte_start_out, const uint32_t** d_char_start_out, const uint64_t** d_byte_off_out,
+                                     const uint64_t** d_char_off_out) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if (!d_tok_off || (n_tokens && !d_tokens)) return fail(TK_VALUE_ERROR, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    SpanView v;
+    TRY(spans_locked(c, stream ? (hipStream_t)stream : c->stream, (const uint32_t*)d_tokens, n_tokens, (const uint64_t*)d_tok_off, n_docs, (const uint64_t*)d_doc_off, false,
+                     false, &v));
+    if (d_byte_start_out) *d_byte_start_out = v.byte_start;
+    if (d_char_start_out) *d_char_start_out = v.char_start;
+    if (d_byte_off_out) *d_byte_off_out = v.byte_off;
+    if (d_char_off_out) *d_char_off_out = v.char_off;
+    return TK_OK;
+}
+
+// a result array on its way to the caller: page-locked from a MiB on (the copy back runs at the link's rate)
+static void* result_alloc(size_t bytes) { return bytes >= (1u << 20) ? pinned_get(bytes) : malloc(bytes ? bytes : 1); }
+// the spans of n tokens from the device into two result arrays
+static int spans_to_host(const SpanView& v, uint64_t n, HostResult<uint32_t>& bs, HostResult<uint32_t>& cs) {
+    bs = HostResult<uint32_t>(result_alloc(n * 4));
+    cs = HostResult<uint32_t>(result_alloc(n * 4));
+    if (!bs || !cs) return fail(TK_RUNTIME_ERROR, "out of host memory");
+    if (n) {
+        HIPCHK(hipMemcpy(bs, v.byte_start, n * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(cs, v.char_start, n * 4, hipMemcpyDeviceToHost));
+    }
+    return TK_OK;
+}
+
+// Host buffers in and out.  A batch of less than two ranges of 16 Mi ids takes one copy each way.  A larger one runs in those ranges, as
+// tk_decode_batch does: the ids of range k + 1 travel to the device (straight from the caller's buffer, sent by a thread of their own)
+// while range k is scanned and the spans of range k - 1 travel back -- both directions of the link at once; the scan's carry (sums and
+// last document start) stays on the device between the ranges.  Then the bytes, range by range: the copy kernel of range k + 1 runs while
+// the bytes of range k travel (by then the byte count is known: the result buffer has its size at once), and the UTF-8 check behind them.
+static int decode_spans_ranges(tk_core* c, hipStream_t s, const uint32_t* tokens, uint64_t n, uint64_t n_docs, bool want_bytes, bool validate, SpanView* v,
+                               HostResult<uint32_t>& bs, HostResult<uint32_t>& cs, HostResult<uint8_t>& host) {
+    constexpr uint64_t RANGE = TK_STAGE_BYTES / 4;  // ids per range (a multiple of TK_DEC_BLOCK)
+    const uint64_t n_ranges = (n + RANGE - 1) / RANGE;
+    const uint64_t* d_tok_off = c->d_boff.as<uint64_t>();
+    uint32_t* d_tok = c->d_tok.as<uint32_t>();
+    TRY(ensure_copy_streams(c));
+    std::vector<Event> ev_in(n_ranges), ev_out(n_ranges);
+    for (auto& e : ev_in) HIPCHK(e.create());
+    for (auto& e : ev_out) HIPCHK(e.create());
+    bs = HostResult<uint32_t>(pinned_get(n * 4));
+    cs = HostResult<uint32_t>(pinned_get(n * 4));
+    Pinned<unsigned long long> cum;  // bytes of the batch up to the end of every range
+    HIPCHK(cum.alloc((n_ranges + 1) * 8, hipHostMallocPortable));
+    if (!bs || !cs) return fail(TK_RUNTIME_ERROR, "out of page-locked host memory");
+    unsigned long long* words = nullptr;
+    TRY(spans_begin(c, s, n, d_tok_off, n_docs, v, &words));
+    // (nothing returns between the producer's start and producer.join(): the events are let go only after it has ended)
+    std::atomic<int> h2d_rc{TK_OK};
+    std::atomic<uint64_t> sent{0};
+    const int dev = c->device;
+    std::thread producer([&]() {
+        (void)hipSetDevice(dev);
+        for (uint64_t k = 0; k < n_ranges; ++k) {
+            const uint64_t a = k * RANGE, cnt = a + RANGE < n ? RANGE : n - a;
+            if (hipMemcpyAsync(d_tok + a, tokens + a, cnt * 4, hipMemcpyHostToDevice, c->cs_h2d) != hipSuccess) h2d_rc = TK_RUNTIME_ERROR;
+            (void)hipEventRecord(ev_in[k], c->cs_h2d);
+            sent.store(k + 1, std::memory_order_release);
+        }
+    });
+    auto step = [&](uint64_t k) -> int {
+        const uint64_t a = k * RANGE, cnt = a + RANGE < n ? RANGE : n - a;
+        while (sent.load(std::memory_order_acquire) <= k) std::this_thread::yield();
+        if (h2d_rc.load() != TK_OK) return fail(TK_RUNTIME_ERROR, "host-to-device copy failed");
+        HIPCHK(hipStreamWaitEvent(s, ev_in[k], 0));
+        TRY(spans_range(c, s, d_tok, n, a, cnt, d_tok_off, n_docs, v, words));
+        HIPCHK(hipMemcpyAsync(cum + k + 1, words + TK_SPAN_BYTES, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipEventRecord(ev_out[k], s));
+        HIPCHK(hipStreamWaitEvent(c->cs_d2h, ev_out[k], 0));
+        HIPCHK(hipMemcpyAsync(bs + a, v->byte_start + a, cnt * 4, hipMemcpyDeviceToHost, c->cs_d2h));
+        HIPCHK(hipMemcpyAsync(cs + a, v->char_start + a, cnt * 4, hipMemcpyDeviceToHost, c->cs_d2h));
+        return TK_OK;
+    };
+    int rc = TK_OK;
+    for (uint64_t k = 0; k < n_ranges && rc == TK_OK; ++k) rc = step(k);
+    producer.join();
+    hipError_t e = hipStreamSynchronize(c->cs_h2d);
+    if (rc == TK_OK) rc = spans_end(c, s, d_tok, d_tok_off, n_docs, nullptr, v, words);
+    if (rc == TK_OK && (want_bytes || validate)) rc = [&]() -> int {
+        cum[0] = 0;
+        TRY(ensure(c->d_bytes, v->n_bytes + 16));
+        if (want_bytes) {
+            host = HostResult<uint8_t>(pinned_get(v->n_bytes));
+            if (!host) return fail(TK_RUNTIME_ERROR, "out of page-locked host memory");
+        }
+        for (uint64_t k = 0; k < n_ranges; ++k) {
+            const uint64_t a = k * RANGE, cnt = a + RANGE < n ? RANGE : n - a;
+            TRY(decode_range_copy(c, s, d_tok, a, cnt, c->d_bytes.as<uint8_t>(), nullptr, 0));  // (the bases are the batch's: every range writes at its place)
+            if (!want_bytes) continue;
+            HIPCHK(hipEventRecord(ev_in[k], s));
+            HIPCHK(hipStreamWaitEvent(c->cs_d2h, ev_in[k], 0));
+            if (cum[k + 1] > cum[k]) HIPCHK(hipMemcpyAsync(host + cum[k], c->d_bytes.as<uint8_t>() + cum[k], cum[k + 1] - cum[k], hipMemcpyDeviceToHost, c->cs_d2h));
+        }
+        if (validate) TRY(spans_validate(c, s, n_docs, v, words));
+        return TK_OK;
+    }();
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    const hipError_t e2 = hipStreamSynchronize(c->cs_d2h);  // (nothing is on its way into the result buffers when they are let go)
+    if (e == hipSuccess) e = e2;
+    if (e == hipSuccess) e = hipGetLastError();
+    if (rc == TK_OK && e != hipSuccess) rc = fail(TK_RUNTIME_ERROR, std::string("HIP error: ") + hipGetErrorString(e));
+    return rc;
+}
+
+extern "C" int tk_decode_batch_spans(tk_core* c, const uint32_t* tokens, const uint64_t* tok_off, uint64_t n_docs, int validate, uint8_t** bytes_out,
+                                     uint64_t* n_bytes_out, uint32_t** byte_start_out, uint32_t** char_start_out, uint64_t* byte_off_out, uint64_t* char_off_out,
+                                     uint64_t* invalid_doc_out) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if (!tok_off || !byte_start_out || !char_start_out || (validate && !invalid_doc_out)) return fail(TK_VALUE_ERROR, "null argument");
+    TRY(check_offsets(tok_off, n_docs, "tok_off"));
+    if (!c->n_dec) return fail(TK_UNSUPPORTED, "token ids are too sparse for the device decode table");
+    const uint64_t n = tok_off[n_docs];
+    if (n && !tokens) return fail(TK_VALUE_ERROR, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    TRY(ensure(c->d_tok, (n + 1) * 4));
+    TRY(ensure(c->d_boff, (n_docs + 2) * 8 * 2));
+    HIPCHK(hipMemcpyAsync(c->d_boff.p, tok_off, (n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+    SpanView v;
+    HostResult<uint32_t> bs, cs;
+    HostResult<uint8_t> host;
+    if (n >= 2 * (TK_STAGE_BYTES / 4)) {
+        const int rc = decode_spans_ranges(c, s, tokens, n, n_docs, bytes_out != nullptr, validate != 0, &v, bs, cs, host);
+        const int rc2 = drain_events(c);
+        TRY(rc);
+        TRY(rc2);
+    } else {
+        if (n) HIPCHK(hipMemcpyAsync(c->d_tok.p, tokens, n * 4, hipMemcpyHostToDevice, s));
+        TRY(spans_locked(c, s, c->d_tok.as<uint32_t>(), n, c->d_boff.as<uint64_t>(), n_docs, nullptr, bytes_out != nullptr, validate != 0, &v));
+        TRY(spans_to_host(v, n, bs, cs));
+        if (bytes_out) {
+            host = HostResult<uint8_t>(result_alloc(v.n_bytes));
+            if (!host) return fail(TK_RUNTIME_ERROR, "out of host memory");
+            if (v.n_bytes) HIPCHK(hipMemcpy(host, c->d_bytes.p, v.n_bytes, hipMemcpyDeviceToHost));
+        }
+    }
+    if (byte_off_out) HIPCHK(hipMemcpy(byte_off_out, v.byte_off, (n_docs + 1) * 8, hipMemcpyDeviceToHost));
+    if (char_off_out) HIPCHK(hipMemcpy(char_off_out, v.char_off, (n_docs + 1) * 8, hipMemcpyDeviceToHost));
+    if (invalid_doc_out) *invalid_doc_out = v.bad_doc;
+    if (n_bytes_out) *n_bytes_out = v.n_bytes;
+    if (bytes_out) *bytes_out = host.release();
+    *byte_start_out = bs.release();
+    *char_start_out = cs.release();
+    return TK_OK;
+}
+
+// tk_encode_batch (tk_encode_batch_checked with disallowed ids) with the spans of the tokens it has just produced: the span pass runs over
+// the ids while they are still on the device, against the offsets of the documents' text.
+extern "C" int tk_encode_batch_spans(tk_core* c, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special, const uint32_t* allowed_ids,
+                                     uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed, uint32_t** tokens_out, uint64_t* n_tokens_out,
+                                     uint64_t* tok_off_out, uint32_t** byte_start_out, uint32_t** char_start_out, tk_special_hit* hit) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if (!tokens_out || !n_tokens_out || !byte_start_out || !char_start_out || (n_disallowed && !hit)) return fail(TK_VALUE_ERROR, "null argument");
+    const CheckArgs chk{disallowed_ids, n_disallowed, hit};
+    std::lock_guard<std::mutex> lk(c->mu);
+    uint64_t n = 0;
+    TRY(encode_batch_impl(c, utf8, doc_off, n_docs, use_special, allowed_ids, n_allowed, nullptr, &n, nullptr, true, true, n_disallowed ? &chk : nullptr, true));
+    SpanView v;
+    TRY(spans_locked(c, c->stream, c->out_tokens.as<uint32_t>(), n, c->out_tok_off.as<uint64_t>(), n_docs, c->doc_off.as<uint64_t>(), false, false, &v));
+    HostResult<uint32_t> bs, cs, tok(result_alloc(n * 4));
+    if (!tok) return fail(TK_RUNTIME_ERROR, "out of host memory");
+    TRY(spans_to_host(v, n, bs, cs));
+    if (n) HIPCHK(hipMemcpy(tok, c->out_tokens.p, n * 4, hipMemcpyDeviceToHost));
+    if (tok_off_out) HIPCHK(hipMemcpy(tok_off_out, c->out_tok_off.p, (n_docs + 1) * 8, hipMemcpyDeviceToHost));
+    *tokens_out = tok.release();
+    *n_tokens_out = n;
+    *byte_start_out = bs.release();
+    *char_start_out = cs.release();
     return TK_OK;
 }
 
