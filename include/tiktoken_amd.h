@@ -172,6 +172,44 @@ int tk_encode_batch_spans(tk_core* core, const uint8_t* utf8, const uint64_t* do
                           const uint32_t* allowed_ids, uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed,
                           uint32_t** tokens_out, uint64_t* n_tokens_out, uint64_t* tok_off_out, uint32_t** byte_start_out,
                           uint32_t** char_start_out, tk_special_hit* hit);
+/* Training rows: a packed batch -> fixed-length rows with document ids, positions and segment boundaries.  Replaces nothing in the
+ * reference: it is the host loop of the reference's users, the data-preparation script that appends a separator to every encoded document,
+ * concatenates the lists and reshapes -- here one call on ids that are on the device anyway.
+ * The stream holds, for every document d in order, [bos_id] tokens[tok_off[d] .. tok_off[d + 1]) [eos_id] (TK_ROWS_NO_TOKEN: none; k = how
+ * many of the two there are, so document d starts at tok_off[d] + d * k and the stream has S = n_tokens + n_docs * k elements; with k == 0
+ * an empty document owns no position).  It is cut into rows of seq_len (L): R = ceil(S / L) rows, the last one filled with pad_id, M = R * L
+ * positions -- or, with TK_ROWS_DROP_LAST, R = floor(S / L) whole rows followed by the n_tail = S - R * L positions left over (M = S), so that
+ * a caller can carry them into its next batch.  Per position j < M:
+ *   ids[j]   the stream element (pad_id from S on); uint16 with TK_ROWS_IDS16, else uint32
+ *   doc[j]   the document whose stream range holds j (TK_ROWS_NO_TOKEN on padding)
+ *   pos[j]   j - max(start of that document (S on padding), start of the row): positions restart at every document and at every row
+ * cu_seqlens[0 .. n_segs]: the positions with pos == 0, ascending, then M (the boundaries variable-length attention takes); row_seg[0 .. R]:
+ * the number of segment starts below r * L, so cu_seqlens[row_seg[a] .. row_seg[b]] - a * L are the boundaries of the rows a .. b alone.
+ * TK_VALUE_ERROR: seq_len == 0; max(S, R * L) >= 2^32 or n_docs >= 2^32 - 1 (the outputs are 32-bit); tok_off that does not ascend from 0
+ * to n_tokens (checked on the device before anything is indexed with it; the message names the first offending document); TK_ROWS_IDS16
+ * unless every id of the vocabulary, the special tokens, bos_id, eos_id and pad_id fit 16 bits.  One device per call: a group has no rows entry. */
+#define TK_ROWS_NO_TOKEN 0xFFFFFFFFu
+#define TK_ROWS_DROP_LAST 1u
+#define TK_ROWS_IDS16 2u
+typedef struct {
+    uint32_t seq_len, bos_id, eos_id, pad_id, flags;
+} tk_rows_spec;
+/* Device pointers in (ids uint32, d_tok_off uint64[n_docs + 1]: e.g. the results of tk_encode_batch_device), device pointers out: buffers
+ * of the core, valid until its next rows call and apart from the encode, decode and span buffers (packing an encode call's result leaves it
+ * intact).  *d_ids_out .. *d_pos_out: M elements each (*n_rows_out rows of seq_len, then *n_tail_out more); *d_cu_seqlens_out: *n_segs_out + 1;
+ * *d_row_seg_out: *n_rows_out + 1; *n_stream_out: S.  `stream`: a hipStream_t or null (the core's); the call returns when the rows are there. */
+int tk_pack_rows_device(tk_core* core, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_docs, const tk_rows_spec* spec,
+                        void* stream, const void** d_ids_out, const uint32_t** d_doc_out, const uint32_t** d_pos_out,
+                        const uint32_t** d_cu_seqlens_out, const uint32_t** d_row_seg_out, uint64_t* n_rows_out, uint64_t* n_segs_out,
+                        uint64_t* n_stream_out, uint64_t* n_tail_out);
+/* tk_encode_batch -- with n_disallowed != 0: tk_encode_batch_checked -- with its result packed into rows while the ids are on the device:
+ * host text in, host rows out, and only the row arrays cross the link (the ids themselves are not handed out).  *ids_out .. *row_seg_out:
+ * library-owned (tk_free), sized as above.  On TK_DISALLOWED_SPECIAL nothing is handed out. */
+int tk_encode_batch_rows(tk_core* core, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special,
+                         const uint32_t* allowed_ids, uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed,
+                         const tk_rows_spec* spec, void** ids_out, uint32_t** doc_out, uint32_t** pos_out, uint32_t** cu_seqlens_out,
+                         uint32_t** row_seg_out, uint64_t* n_rows_out, uint64_t* n_segs_out, uint64_t* n_stream_out, uint64_t* n_tail_out,
+                         tk_special_hit* hit);
 /* CoreBPE.decode_single_token_bytes(token)  (pointer into the core; do not free)  src/py.rs:164-172 */
 int tk_decode_single_token_bytes(tk_core* core, uint32_t token, const uint8_t** bytes_out, uint64_t* len_out);
 /* CoreBPE.token_byte_values(): tokens in lexicographic byte order                  src/py.rs:178-183, lib.rs:648-650 */

@@ -25,6 +25,14 @@ class SpecialHit(ctypes.Structure):
     _fields_ = [("doc", ctypes.c_uint64), ("pos", ctypes.c_uint64), ("id", ctypes.c_uint32), ("len", ctypes.c_uint32)]
 
 
+class RowsSpec(ctypes.Structure):
+    """tk_rows_spec: how a packed batch is cut into training rows (include/tiktoken_amd.h)."""
+    _fields_ = [("seq_len", ctypes.c_uint32), ("bos_id", ctypes.c_uint32), ("eos_id", ctypes.c_uint32), ("pad_id", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+ROWS_NO_TOKEN, ROWS_DROP_LAST, ROWS_IDS16 = 0xFFFFFFFF, 1, 2
+
+
 def build(force: bool = False) -> str:
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     if force or not os.path.exists(_SO):
@@ -82,6 +90,11 @@ def lib() -> ctypes.CDLL:
         L.tk_decode_batch_spans.argtypes = [vp, vp, vp, u64, i32, P(vp), P(u64), P(vp), P(vp), vp, vp, P(u64)]
         L.tk_encode_batch_spans.restype = i32
         L.tk_encode_batch_spans.argtypes = [vp, vp, vp, u64, i32, vp, u64, vp, u64, P(vp), P(u64), vp, P(vp), P(vp), P(SpecialHit)]
+        L.tk_pack_rows_device.restype = i32
+        L.tk_pack_rows_device.argtypes = [vp, vp, u64, vp, u64, P(RowsSpec), vp, P(vp), P(vp), P(vp), P(vp), P(vp), P(u64), P(u64), P(u64), P(u64)]
+        L.tk_encode_batch_rows.restype = i32
+        L.tk_encode_batch_rows.argtypes = [vp, vp, vp, u64, i32, vp, u64, vp, u64, P(RowsSpec), P(vp), P(vp), P(vp), P(vp), P(vp), P(u64), P(u64), P(u64), P(u64),
+                                           P(SpecialHit)]
         L.tk_decode_single_token_bytes.restype = i32
         L.tk_decode_single_token_bytes.argtypes = [vp, u32, P(vp), P(u64)]
         L.tk_n_tokens.restype = u64

@@ -4,7 +4,8 @@
 Same constructor and the same eleven methods, same exception types.  Two additive entry points,
 `encode_batch_packed` and `pretokenize_packed`, expose the batch shape the GPU actually runs
 (one launch sequence per batch instead of one FFI call per document); `decode_batch_spans_packed`, `token_spans_device` and
-`encode_batch_spans_packed` give, for whole batches, where every token starts in its document (bytes and chars).  With `disallowed_special` the batch
+`encode_batch_spans_packed` give, for whole batches, where every token starts in its document (bytes and chars); `pack_rows_device` and
+`encode_batch_rows_packed` cut a batch into fixed-length training rows with document ids, positions and cu_seqlens.  With `disallowed_special` the batch
 calls also search the text for those special tokens, on the device, and raise `DisallowedSpecialError`.
 """
 from __future__ import annotations
@@ -12,7 +13,7 @@ from __future__ import annotations
 import atexit
 import ctypes
 import weakref
-from typing import AbstractSet, Sequence
+from typing import AbstractSet, NamedTuple, Sequence
 
 import numpy as np
 
@@ -76,6 +77,18 @@ def _take_u32(ptr: ctypes.c_void_p, n: int) -> np.ndarray:
     return out
 
 
+def _take(ptr: ctypes.c_void_p, n: int, dtype) -> np.ndarray:
+    """... of a uint32 or uint16 result"""
+    dtype = np.dtype(dtype)
+    if dtype == np.uint32:
+        return _take_u32(ptr, n)
+    if n >= (1 << 16):
+        return np.asarray(_OwnedBuffer(ptr.value, n, "<u2"))
+    out = np.frombuffer(ctypes.string_at(ptr, n * 2), dtype=np.uint16).copy() if n else np.zeros(0, dtype=np.uint16)
+    _lib.lib().tk_free(ptr)
+    return out
+
+
 def _take_u8(ptr: ctypes.c_void_p, n: int) -> np.ndarray:
     """... of a uint8 result (read-only use: decoded bytes)."""
     if n >= (1 << 16):
@@ -113,6 +126,38 @@ def disallowed_special_message(token: str) -> str:
         f"by passing `disallowed_special=(enc.special_tokens_set - {{{token!r}}})`.\n"
         "To disable this check for all special tokens, pass `disallowed_special=()`.\n"
     )
+
+
+class PackedRows(NamedTuple):
+    """A batch as training rows (tk_encode_batch_rows; the rule: include/tiktoken_amd.h).  The stream is [bos] document [eos] for every
+    document in order, cut into rows of seq_len; `doc` is the document of a position (0xFFFFFFFF on padding), `pos` its position in its
+    segment -- positions restart at every document and at every row --, `cu_seqlens` the positions where a segment starts plus the end,
+    `row_seg[r]` the number of segments that start before row r: cu_seqlens[row_seg[a] : row_seg[b] + 1] - a * seq_len are the
+    cu_seqlens of the rows a .. b alone.  With drop_last the positions that do not fill a row come as the tail_ arrays (to be carried
+    into the caller's next batch) and cu_seqlens / row_seg cover them too; without it the last row is padded and the tails are empty."""
+    ids: np.ndarray  # [R, seq_len], uint32 or uint16
+    doc: np.ndarray  # [R, seq_len] uint32
+    pos: np.ndarray  # [R, seq_len] uint32
+    cu_seqlens: np.ndarray  # uint32[n_segs + 1]
+    row_seg: np.ndarray  # uint32[R + 1]
+    n_stream: int
+    tail_ids: np.ndarray
+    tail_doc: np.ndarray
+    tail_pos: np.ndarray
+
+
+class RowsDevice(NamedTuple):
+    """`pack_rows_device`: device pointers (the core's buffers, valid until its next rows call) and the figures that size them:
+    ids / doc / pos hold n_rows * seq_len + n_tail elements, cu_seqlens n_segs + 1, row_seg n_rows + 1."""
+    ids: int
+    doc: int
+    pos: int
+    cu_seqlens: int
+    row_seg: int
+    n_rows: int
+    n_segs: int
+    n_stream: int
+    n_tail: int
 
 
 class DisallowedSpecialError(ValueError):
@@ -604,6 +649,80 @@ class CoreBPE:
             self._raise_hit(hit)
         _lib.raise_for(rc)
         return _take_u32(out, n.value), tok_off, _take_u32(bs, n.value), _take_u32(cs, n.value)
+
+    # ------------------------------------------------------------------ training rows (no reference counterpart: the host loop of its users)
+    @staticmethod
+    def _rows_spec(seq_len: int, bos, eos, pad, drop_last: bool, dtype) -> "tuple[_lib.RowsSpec, bool]":
+        """(the tk_rows_spec, whether the caller has named a pad id -- eos stands in for it)"""
+        dtype = np.dtype(dtype)
+        if dtype not in (np.dtype(np.uint32), np.dtype(np.uint16)):
+            raise ValueError("dtype must be uint32 or uint16")
+        for name, v in (("bos", bos), ("eos", eos), ("pad", pad)):
+            if v is not None and not 0 <= int(v) < 0xFFFFFFFF:
+                raise ValueError(f"{name} must be a token id below 2^32 - 1")
+        if not 0 <= int(seq_len) <= 0xFFFFFFFF:
+            raise ValueError("seq_len must fit 32 bits")
+        if pad is None:
+            pad = eos
+        none = _lib.ROWS_NO_TOKEN
+        flags = (_lib.ROWS_DROP_LAST if drop_last else 0) | (_lib.ROWS_IDS16 if dtype == np.uint16 else 0)
+        spec = _lib.RowsSpec(int(seq_len), none if bos is None else int(bos), none if eos is None else int(eos), 0 if pad is None else int(pad), flags)
+        return spec, pad is not None
+
+    @staticmethod
+    def _pad_needed(has_pad: bool, drop_last: bool, n_stream: int, seq_len: int) -> None:
+        if not has_pad and not drop_last and seq_len and n_stream % seq_len:
+            raise ValueError(f"the stream of {n_stream} ids does not fill rows of {seq_len}: name a pad or eos id, or pass drop_last=True")
+
+    def pack_rows_device(self, d_tokens: int, n_tokens: int, d_tok_off: int, n_docs: int, *, seq_len: int, bos: int | None = None, eos: int | None = None,
+                         pad: int | None = None, drop_last: bool = False, dtype=np.uint32, stream: int = 0) -> RowsDevice:
+        """Device-resident rows (tk_pack_rows_device): pointers to uint32 ids and uint64[n_docs + 1] token offsets on this core's device -- e.g.
+        what `encode_batch_device` returns, which stays intact -- cut into rows of `seq_len`; see `PackedRows` for the arrays.  `bos` / `eos`:
+        ids put before / after every document; `pad` (default: eos) fills the last row unless `drop_last`; dtype uint16: 16-bit ids."""
+        self._one_device("pack_rows_device")
+        spec, has_pad = self._rows_spec(seq_len, bos, eos, pad, drop_last, dtype)
+        k = (bos is not None) + (eos is not None)
+        self._pad_needed(has_pad, drop_last, n_tokens + n_docs * k, spec.seq_len)
+        out = [ctypes.c_void_p() for _ in range(5)]
+        cnt = [ctypes.c_uint64() for _ in range(4)]
+        rc = self._L.tk_pack_rows_device(self._h, d_tokens or None, n_tokens, d_tok_off or None, n_docs, ctypes.byref(spec), stream or None,
+                                         *[ctypes.byref(x) for x in out], *[ctypes.byref(x) for x in cnt])
+        _lib.raise_for(rc)
+        return RowsDevice(*[x.value or 0 for x in out], *[int(x.value) for x in cnt])
+
+    def encode_batch_rows_packed(self, blob: np.ndarray, doc_off: np.ndarray, allowed_special: AbstractSet[str] | None = None, *, disallowed_special=None,
+                                 seq_len: int, bos: int | None = None, eos: int | None = None, pad: int | None = None, drop_last: bool = False,
+                                 dtype=np.uint32) -> PackedRows:
+        """`encode_batch_packed` with its result cut into training rows while the ids are on the device (tk_encode_batch_rows): only the row
+        arrays come back.  The special-token arguments as in `encode_batch_packed`, the others as in `pack_rows_device`."""
+        self._one_device("encode_batch_rows_packed")
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        doc_off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+        _check_packed(blob, doc_off)
+        spec, has_pad = self._rows_spec(seq_len, bos, eos, pad, drop_last, dtype)
+        n_docs = len(doc_off) - 1
+        src = blob if len(blob) else np.zeros(1, dtype=np.uint8)
+        if allowed_special is None:
+            ids, k, mode = np.zeros(1, dtype=np.uint32), 0, 0
+        else:
+            ids, k = self._allowed_ids(allowed_special)
+            mode = 1
+        dis, n_dis = self._disallowed_ids(disallowed_special)
+        hit = _lib.SpecialHit()
+        out = [ctypes.c_void_p() for _ in range(5)]
+        cnt = [ctypes.c_uint64() for _ in range(4)]
+        rc = self._L.tk_encode_batch_rows(self._h, src.ctypes.data, doc_off.ctypes.data, n_docs, mode, ids.ctypes.data, k, dis.ctypes.data, n_dis, ctypes.byref(spec),
+                                          *[ctypes.byref(x) for x in out], *[ctypes.byref(x) for x in cnt], ctypes.byref(hit))
+        if rc == _lib.TK_DISALLOWED_SPECIAL:
+            self._raise_hit(hit)
+        _lib.raise_for(rc)
+        n_rows, n_segs, n_stream, n_tail = (int(x.value) for x in cnt)
+        L = spec.seq_len
+        m = n_rows * L + n_tail
+        arrays = [_take(out[0], m, dtype), _take_u32(out[1], m), _take_u32(out[2], m)]
+        cu, row_seg = _take_u32(out[3], n_segs + 1), _take_u32(out[4], n_rows + 1)
+        self._pad_needed(has_pad, drop_last, n_stream, L)
+        return PackedRows(*[a[: n_rows * L].reshape(n_rows, L) for a in arrays], cu, row_seg, n_stream, *[a[n_rows * L:] for a in arrays])
 
     def decode_single_token_bytes(self, token: int) -> bytes:
         if not 0 <= token <= 0xFFFFFFFF:

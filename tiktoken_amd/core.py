@@ -230,6 +230,40 @@ class Encoding:
             raise RuntimeError(f"internal error: the device reported the disallowed special token {e.token!r} in document {e.doc} at byte "
                                f"{e.pos}, the host search finds none there") from e
 
+    def encode_ordinary_batch_rows(self, text: Sequence[str], seq_len: int, *, bos: int | None = None, eos: int | None = None, pad: int | None = None,
+                                   drop_last: bool = False, dtype=np.uint32) -> "_tiktoken.PackedRows":
+        """A batch as fixed-length training rows, ignoring special tokens: every text is encoded, `bos` / `eos` (token ids) go before / after
+        it, the results are concatenated and cut into rows of `seq_len` -- in one GPU call, only the rows come back.  Returns a
+        `PackedRows`: `ids`, `doc` (the text a position belongs to) and `pos` (its position in its segment: they restart at every text and
+        at every row) as [R, seq_len] arrays, `cu_seqlens` and `row_seg` for variable-length attention, `n_stream`, and -- with `drop_last`,
+        which keeps whole rows only -- what is left over as `tail_ids`, `tail_doc`, `tail_pos`.  Without `drop_last` the last row is filled
+        with `pad` (default: `eos`); ValueError if that is needed and neither is given.  dtype uint16: 16-bit ids, for vocabularies that fit."""
+        blob, off = self._pack(text)
+        return self._core_bpe.encode_batch_rows_packed(blob, off, None, seq_len=seq_len, bos=bos, eos=eos, pad=pad, drop_last=drop_last, dtype=dtype)
+
+    def encode_batch_rows(self, text: Sequence[str], seq_len: int, *, allowed_special: Literal["all"] | AbstractSet[str] = set(),  # noqa: B006
+                          disallowed_special: Literal["all"] | Collection[str] = "all", bos: int | None = None, eos: int | None = None,
+                          pad: int | None = None, drop_last: bool = False, dtype=np.uint32) -> "_tiktoken.PackedRows":
+        """`encode_ordinary_batch_rows` with the special-token arguments of `encode` -- the policy, and the error, of `encode_batch_packed`."""
+        rows = dict(seq_len=seq_len, bos=bos, eos=eos, pad=pad, drop_last=drop_last, dtype=dtype)
+        allowed_special, disallowed_special = self._special_policy(allowed_special, disallowed_special)
+        if not disallowed_special:
+            blob, off = self._pack(text)
+            return self._core_bpe.encode_batch_rows_packed(blob, off, allowed_special, **rows)
+        if not isinstance(disallowed_special, frozenset):
+            disallowed_special = frozenset(disallowed_special)
+        blob, off, repaired = self._pack_repaired(text)
+        if repaired or not all(t in self._special_tokens for t in disallowed_special):  # (as encode_batch_packed: the host's search)
+            for t in text:
+                self._reject_disallowed(t, disallowed_special)
+            return self._core_bpe.encode_batch_rows_packed(blob, off, allowed_special, **rows)
+        try:
+            return self._core_bpe.encode_batch_rows_packed(blob, off, allowed_special, disallowed_special=disallowed_special, **rows)
+        except _tiktoken.DisallowedSpecialError as e:
+            self._reject_disallowed(text[e.doc], disallowed_special)
+            raise RuntimeError(f"internal error: the device reported the disallowed special token {e.token!r} in document {e.doc} at byte "
+                               f"{e.pos}, the host search finds none there") from e
+
     def encode_ordinary_batch(self, text: list[str], *, num_threads: int = 8) -> list[list[int]]:
         """Encode a list of strings, ignoring special tokens (one GPU batch; `num_threads` is kept for
         signature compatibility)."""

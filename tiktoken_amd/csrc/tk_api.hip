@@ -23,6 +23,7 @@
 #include "../../include/tiktoken_amd.h"
 #include "tk_decode.h"
 #include "tk_offsets.h"
+#include "tk_rows.h"
 #include "tk_fused.h"
 #include "tk_mid_plan.h"
 #include "tk_tables.h"
@@ -229,6 +230,9 @@ struct tk_core {
     // char_start of every token; d_span_blk: per workgroup {chars, mark key, document start bytes / chars}; d_span_marks: document starts over
     // the tokens, d_span_bmarks: over the decoded bytes; d_span_doc: byte_off, char_off, then the TK_SPAN_WORDS report words.
     Buf t_cw, d_span, d_span_blk, d_span_marks, d_span_bmarks, d_span_doc;
+    // Training rows (tk_rows.h), apart from everything above: d_rows: ids, doc and pos of every position; d_rows_seg: the TK_ROWS_WORDS report
+    // words, cu_seqlens, row_seg; d_rows_marks: document starts over the stream positions; d_rows_blk: segment starts per workgroup.
+    Buf d_rows, d_rows_seg, d_rows_marks, d_rows_blk;
     // Small calls (tk_k_small) do not take `mu`: the reference's normal use is several threads on one Encoding (core.py:175, a thread pool
     // over encode; lib.rs:232-238 keeps a regex per thread for it), and a small call needs nothing of the shared workspace -- a slot of its
     // own (page-locked text and result buffers the kernel reads and writes directly, merge scratch, a stream) is all.  A caller takes a
@@ -2638,6 +2642,155 @@ extern "C" int tk_encode_batch_spans(tk_core* c, const uint8_t* utf8, const uint
     *n_tokens_out = n;
     *byte_start_out = bs.release();
     *char_start_out = cs.release();
+    return TK_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Training rows (tk_rows.h): a packed batch on the device -> rows of seq_len with document ids, positions and segment boundaries.
+// ------------------------------------------------------------------------------------------
+struct RowsView {  // device buffers of the core, valid until its next rows call
+    void* ids = nullptr;
+    uint32_t *doc = nullptr, *pos = nullptr, *cu = nullptr, *row_seg = nullptr;
+    uint64_t n_rows = 0, n_segs = 0, n_stream = 0, n_tail = 0, n_pos = 0;  // n_pos: positions written (M)
+    bool ids16 = false;
+};
+// rows_run: the caller holds c->mu.  Everything but the number of segments follows from the arguments; the host waits once, at the end, for
+// that number and for what tk_k_rows_mark has to say about tok_off.
+// What of a tk_rows_spec can be refused without looking at the batch (the host-text entry asks before it encodes anything).
+static int rows_check_spec(tk_core* c, const tk_rows_spec* spec) {
+    if (!spec) return fail(TK_VALUE_ERROR, "null argument");
+    if (spec->flags & ~(TK_ROWS_DROP_LAST | TK_ROWS_IDS16)) return fail(TK_VALUE_ERROR, "tk_rows_spec: unknown flag");
+    if (!spec->seq_len) return fail(TK_VALUE_ERROR, "seq_len must be at least 1");
+    if (spec->flags & TK_ROWS_IDS16) {
+        uint32_t max_id = c->H.max_rank;
+        for (const auto& kv : c->H.spec_decoder) max_id = std::max(max_id, kv.first);
+        if (max_id > 0xFFFFu) return fail(TK_VALUE_ERROR, "16-bit ids: the vocabulary has ids up to " + std::to_string(max_id));
+        const uint32_t extra[3] = {spec->bos_id, spec->eos_id, spec->pad_id};
+        const char* names[3] = {"bos_id", "eos_id", "pad_id"};
+        for (int i = 0; i < 3; ++i)
+            if (extra[i] > 0xFFFFu && (i == 2 || extra[i] != TK_ROWS_NO_TOKEN)) return fail(TK_VALUE_ERROR, std::string("16-bit ids: ") + names[i] + " does not fit");
+    }
+    return TK_OK;
+}
+static int rows_run(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n, const uint64_t* d_tok_off, uint64_t n_docs, const tk_rows_spec* spec, RowsView* out) {
+    TRY(rows_check_spec(c, spec));
+    TkRows r;
+    switch (tk_rows_shape(n, n_docs, spec->seq_len, spec->bos_id, spec->eos_id, spec->pad_id, (spec->flags & TK_ROWS_DROP_LAST) != 0, &r)) {
+        case 0: break;
+        case 1: return fail(TK_VALUE_ERROR, "seq_len must be at least 1");
+        case 3: return fail(TK_VALUE_ERROR, "too many documents: the document indices of the rows are 32-bit");
+        default: return fail(TK_VALUE_ERROR, "the stream has 2^32 positions or more: the positions of the rows are 32-bit");
+    }
+    const bool ids16 = (spec->flags & TK_ROWS_IDS16) != 0;
+    const uint64_t m8 = (r.M + 7) & ~7ull, ids_bytes = m8 * (ids16 ? 2 : 4);  // (every array starts at a multiple of 16 bytes)
+    const uint64_t nb = (r.M + TK_DEC_BLOCK - 1) / TK_DEC_BLOCK, cu_cap = (n_docs + r.R + 4 + 3) & ~3ull;
+    TRY(ensure(c->d_rows, ids_bytes + m8 * 8 + 64));
+    TRY(ensure(c->d_rows_seg, TK_ROWS_WORDS * 8 + (cu_cap + r.R + 1) * 4));
+    TRY(ensure(c->d_rows_marks, (r.M / 32 + 4) * 4));
+    TRY(ensure(c->d_rows_blk, (nb + 1) * 8));
+    out->ids = c->d_rows.p;
+    out->doc = (uint32_t*)((uint8_t*)c->d_rows.p + ids_bytes);
+    out->pos = out->doc + m8;
+    unsigned long long* words = c->d_rows_seg.as<unsigned long long>();
+    out->cu = (uint32_t*)(words + TK_ROWS_WORDS);
+    out->row_seg = out->cu + cu_cap;
+    out->ids16 = ids16;
+    out->n_rows = r.R;
+    out->n_stream = r.S;
+    out->n_pos = r.M;
+    out->n_tail = (spec->flags & TK_ROWS_DROP_LAST) ? r.S - r.R * r.seq_len : 0;
+    unsigned long long* cnt = c->d_rows_blk.as<unsigned long long>();
+    HIPCHK(hipMemsetAsync(words + TK_ROWS_BAD_OFF, 0xFF, 8, s));  // (all ones: none; tk_k_rows_scan writes the other word)
+    HIPCHK(hipMemsetAsync(c->d_rows_marks.p, 0, (r.M / 32 + 4) * 4, s));
+    TRY(timed(c, s, "tk_k_rows_mark", [&] {
+        hipLaunchKernelGGL(tk_k_rows_mark, dim3(grid_for(n_docs + 1, 256, 4096)), dim3(256), 0, s, d_tok_off, r, c->d_rows_marks.as<uint32_t>(), words);
+    }));
+    if (nb)
+        TRY(timed(c, s, "tk_k_rows_count", [&] { hipLaunchKernelGGL(tk_k_rows_count, dim3((uint32_t)nb), dim3(256), 0, s, c->d_rows_marks.as<uint8_t>(), r, cnt); }));
+    TRY(timed(c, s, "tk_k_rows_scan", [&] { hipLaunchKernelGGL(tk_k_rows_scan, dim3(1), dim3(1024), 0, s, cnt, nb, r, out->cu, out->row_seg, words); }));
+    if (nb)
+        TRY(timed(c, s, "tk_k_rows_write", [&] {
+            if (ids16) hipLaunchKernelGGL(tk_k_rows_write<true>, dim3((uint32_t)nb), dim3(256), 0, s, d_tok, d_tok_off, r, cnt, words, out->ids, out->doc, out->pos, out->cu, out->row_seg);
+            else hipLaunchKernelGGL(tk_k_rows_write<false>, dim3((uint32_t)nb), dim3(256), 0, s, d_tok, d_tok_off, r, cnt, words, out->ids, out->doc, out->pos, out->cu, out->row_seg);
+        }));
+    unsigned long long got[TK_ROWS_WORDS];
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(got, words, sizeof got, hipMemcpyDeviceToHost));  // (synchronous: nothing is on its way into `got` when this returns, however it returns)
+    if (got[TK_ROWS_BAD_OFF] != ~0ull) {
+        const std::string d = std::to_string(got[TK_ROWS_BAD_OFF] >> 2);
+        switch (got[TK_ROWS_BAD_OFF] & 3u) {
+            case 1: return fail(TK_VALUE_ERROR, "tok_off[0] must be 0 (document " + d + ")");
+            case 2: return fail(TK_VALUE_ERROR, "tok_off must be non-decreasing: document " + d + " ends before it starts");
+            default: return fail(TK_VALUE_ERROR, "tok_off must end at n_tokens: document " + d + " ends elsewhere");
+        }
+    }
+    out->n_segs = got[TK_ROWS_NSEGS];
+    return TK_OK;
+}
+static int rows_locked(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n, const uint64_t* d_tok_off, uint64_t n_docs, const tk_rows_spec* spec, RowsView* out) {
+    const int rc = rows_run(c, s, d_tok, n, d_tok_off, n_docs, spec, out);
+    const int rc2 = drain_events(c);  // (the timed pairs go whatever happened)
+    return rc != TK_OK ? rc : rc2;
+}
+
+extern "C" int tk_pack_rows_device(tk_core* c, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_docs, const tk_rows_spec* spec, void* stream,
+                                   const void** d_ids_out, const uint32_t** d_doc_out, const uint32_t** d_pos_out, const uint32_t** d_cu_seqlens_out,
+                                   const uint32_t** d_row_seg_out, uint64_t* n_rows_out, uint64_t* n_segs_out, uint64_t* n_stream_out, uint64_t* n_tail_out) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if (!d_tok_off || (n_tokens && !d_tokens) || !spec) return fail(TK_VALUE_ERROR, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    RowsView v;
+    TRY(rows_locked(c, stream ? (hipStream_t)stream : c->stream, (const uint32_t*)d_tokens, n_tokens, (const uint64_t*)d_tok_off, n_docs, spec, &v));
+    if (d_ids_out) *d_ids_out = v.ids;
+    if (d_doc_out) *d_doc_out = v.doc;
+    if (d_pos_out) *d_pos_out = v.pos;
+    if (d_cu_seqlens_out) *d_cu_seqlens_out = v.cu;
+    if (d_row_seg_out) *d_row_seg_out = v.row_seg;
+    if (n_rows_out) *n_rows_out = v.n_rows;
+    if (n_segs_out) *n_segs_out = v.n_segs;
+    if (n_stream_out) *n_stream_out = v.n_stream;
+    if (n_tail_out) *n_tail_out = v.n_tail;
+    return TK_OK;
+}
+
+// tk_encode_batch (tk_encode_batch_checked with disallowed ids) with the rows of the tokens it has just produced: the row passes run over
+// the ids while they are still on the device, and only the row arrays travel back.
+extern "C" int tk_encode_batch_rows(tk_core* c, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special, const uint32_t* allowed_ids,
+                                    uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed, const tk_rows_spec* spec, void** ids_out,
+                                    uint32_t** doc_out, uint32_t** pos_out, uint32_t** cu_seqlens_out, uint32_t** row_seg_out, uint64_t* n_rows_out,
+                                    uint64_t* n_segs_out, uint64_t* n_stream_out, uint64_t* n_tail_out, tk_special_hit* hit) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if (!spec || !ids_out || !doc_out || !pos_out || !cu_seqlens_out || !row_seg_out || !n_rows_out || !n_segs_out || (n_disallowed && !hit))
+        return fail(TK_VALUE_ERROR, "null argument");
+    TRY(rows_check_spec(c, spec));  // (before the encode, not after it)
+    const CheckArgs chk{disallowed_ids, n_disallowed, hit};
+    std::lock_guard<std::mutex> lk(c->mu);
+    uint64_t n = 0;
+    TRY(encode_batch_impl(c, utf8, doc_off, n_docs, use_special, allowed_ids, n_allowed, nullptr, &n, nullptr, true, true, n_disallowed ? &chk : nullptr, true));
+    RowsView v;
+    TRY(rows_locked(c, c->stream, c->out_tokens.as<uint32_t>(), n, c->out_tok_off.as<uint64_t>(), n_docs, spec, &v));
+    const uint64_t ids_bytes = v.n_pos * (v.ids16 ? 2 : 4);
+    HostResult<uint8_t> ids(result_alloc(ids_bytes));
+    HostResult<uint32_t> doc(result_alloc(v.n_pos * 4)), pos(result_alloc(v.n_pos * 4)), cu(result_alloc((v.n_segs + 1) * 4)), rs(result_alloc((v.n_rows + 1) * 4));
+    if (!ids || !doc || !pos || !cu || !rs) return fail(TK_RUNTIME_ERROR, "out of host memory");
+    if (v.n_pos) {
+        HIPCHK(hipMemcpy(ids, v.ids, ids_bytes, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(doc, v.doc, v.n_pos * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(pos, v.pos, v.n_pos * 4, hipMemcpyDeviceToHost));
+    }
+    HIPCHK(hipMemcpy(cu, v.cu, (v.n_segs + 1) * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(rs, v.row_seg, (v.n_rows + 1) * 4, hipMemcpyDeviceToHost));
+    *ids_out = ids.release();
+    *doc_out = doc.release();
+    *pos_out = pos.release();
+    *cu_seqlens_out = cu.release();
+    *row_seg_out = rs.release();
+    *n_rows_out = v.n_rows;
+    *n_segs_out = v.n_segs;
+    if (n_stream_out) *n_stream_out = v.n_stream;
+    if (n_tail_out) *n_tail_out = v.n_tail;
     return TK_OK;
 }
 
