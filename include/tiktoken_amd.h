@@ -210,6 +210,34 @@ int tk_encode_batch_rows(tk_core* core, const uint8_t* utf8, const uint64_t* doc
                          const tk_rows_spec* spec, void** ids_out, uint32_t** doc_out, uint32_t** pos_out, uint32_t** cu_seqlens_out,
                          uint32_t** row_seg_out, uint64_t* n_rows_out, uint64_t* n_segs_out, uint64_t* n_stream_out, uint64_t* n_tail_out,
                          tk_special_hit* hit);
+/* bpe_train(data, vocab_size, pat_str, visualise=None)                      tiktoken/_educational.py:119-185
+ * Training a vocabulary: the merges the reference's educational trainer makes on the same text -- the same pairs in the same order -- for a
+ * packed batch of documents, under the core's pat_str (stock scanners or the generic engine).  The core's ranks and special tokens play
+ * no part.  On success *pairs_out holds *n_out = vocab_size - 256 pairs {left, right} and *counts_out the count of each pair when it won
+ * (both library-owned: tk_free); token 256 + k is the bytes of left followed by the bytes of right.  The rule:
+ *  1. Words: the pieces the pre-tokeniser yields for every document, in document order, each as its UTF-8 bytes; a piece never crosses a
+ *     document boundary, chars a generic pat_str leaves unmatched are no words.  Symbols 0..255 are the bytes, symbol 256 + k is merge k.
+ *  2. Equal pieces are ONE word with a weight, the number of its occurrences (64-bit), and the byte offset of its first occurrence in the
+ *     whole corpus (64-bit, across documents and chunks).  A symbol keeps, for its whole life, the offset of its first byte inside its
+ *     word; a merged symbol keeps that of its left part.  A symbol's position is word offset + symbol offset: ascending positions are the
+ *     order in which the reference's loop over its word list meets symbols first.
+ *  3. A step counts every adjacent pair (a, b) inside words, each occurrence with its word's weight.  cmax = the largest count; the
+ *     winner is the pair found at the smallest position among all positions whose pair has count cmax (= the reference's max() over a
+ *     Counter: the first maximal key in insertion order, which is the order of first occurrence).  counts_out[k] = cmax of step k.
+ *  4. In every word, from left to right, non-overlapping occurrences of the winner are replaced by the new symbol: for a == b a run of k
+ *     equal symbols gives floor(k / 2) merges from the run's first symbol on and leaves a lone one at its end if k is odd.
+ *  5. After vocab_size - 256 steps the call returns.  A step that finds no pair at all: TK_VALUE_ERROR (the reference raises ValueError
+ *     from max() there).  vocab_size < 256: TK_VALUE_ERROR before anything runs; vocab_size == 256: no merges, *n_out = 0.
+ *  6. NOT built: a merge that spells an existing token (two different pairs with the same concatenated bytes).  The reference overwrites
+ *     the dict entry and runs one step more, which leaves ids with holes.  This call returns pairs, not byte strings, and knows nothing of
+ *     spellings; whoever assembles the byte strings (tiktoken_amd.train.merges_to_ranks) refuses such a list with an error that names
+ *     the two pairs instead of building the hole-ridden ids.
+ * A corpus longer than the core's chunk size goes chunk by chunk, cut at document boundaries, into one word table, offsets kept global; a
+ * single document longer than a chunk (at most 2 GiB): TK_VALUE_ERROR -- split it into documents.  More than 4 GiB of DISTINCT words:
+ * TK_VALUE_ERROR.  The merge loop runs without a host wait; every step counts from scratch (tk_train.h).  Holds the core's mutex.  One
+ * device per call, host text in: a device-resident entry and several devices are not built. */
+int tk_train_bpe(tk_core* core, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, uint32_t vocab_size,
+                 uint32_t** pairs_out /* n x {left, right} */, uint64_t** counts_out /* cmax of each step */, uint64_t* n_out);
 /* CoreBPE.decode_single_token_bytes(token)  (pointer into the core; do not free)  src/py.rs:164-172 */
 int tk_decode_single_token_bytes(tk_core* core, uint32_t token, const uint8_t** bytes_out, uint64_t* len_out);
 /* CoreBPE.token_byte_values(): tokens in lexicographic byte order                  src/py.rs:178-183, lib.rs:648-650 */

@@ -1,0 +1,219 @@
+"""The training passes (tk_train.h) on the CPU: tests/hostsim/train_sim.cpp compiles the plain C++ they are made of
+(tiktoken_amd/csrc/tk_train_rule.h) for the host and drives it the way the kernels do -- a lane per piece into the word table, a lane per
+symbol in workgroups of 4, 64 and 256 for the step.  Input: words with weights; expected: the merges, their counts and the final symbols,
+from the Python restatement of the rule in tests/train_ref.py.  The same case list runs a second time through the driver built as a
+program of its own with the address and undefined-behaviour sanitizers (host code only: nothing of it is loaded into Python)."""
+import ctypes
+import fcntl
+import os
+import random
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+import helpers as h
+import train_ref as tr
+
+_lib = None
+BLOCKS = (4, 64, 256)
+SEED = 0x243F6A8885A308D3
+D = os.path.join(h.ROOT, "tests", "hostsim")
+C = os.path.join(h.ROOT, "tiktoken_amd", "csrc")
+SRCS = [os.path.join(D, "train_sim.cpp"), os.path.join(C, "tk_train_rule.h"), os.path.join(C, "tk_common.h")]
+
+
+def _build(out, flags):
+    def stale():
+        return not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(s) for s in SRCS)
+
+    if stale():  # (several workers may get here at once: one builds, into a file of its own, and renames)
+        with open(out + ".lock", "w") as lk:
+            fcntl.flock(lk, fcntl.LOCK_EX)
+            if stale():
+                tmp = f"{out}.{os.getpid()}.tmp"
+                subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", *flags, SRCS[0], "-o", tmp])
+                os.replace(tmp, out)
+    return out
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        L = ctypes.CDLL(_build(os.path.join(D, "libtrain_sim.so"), ["-O2", "-fPIC", "-shared"]))
+        vp, u64, u32 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32
+        L.train_sim.restype = ctypes.c_int64
+        L.train_sim.argtypes = [vp, vp, vp, vp, u64, u64, u64, u32, u32, ctypes.c_int, vp, vp, vp, vp, vp, u64, vp]
+        _lib = L
+    return _lib
+
+
+class Case:
+    """words: [(bytes, weight)] in corpus order, a byte of other text between two of them; flags: 1 the table is moved once, 2 the words
+    are laid out in the order of the list."""
+
+    def __init__(self, name, words, n_merges, block, slots=None, seed=SEED, flags=2):
+        self.name, self.n_merges, self.block, self.seed, self.flags = name, n_merges, block, seed, flags
+        self.data = [w for w, _ in words]
+        self.weight = [wt for _, wt in words]
+        self.first, at = [], 0
+        for w in self.data:
+            self.first.append(at)
+            at += len(w) + 1
+        distinct = len(set(self.data))
+        self.slots = slots or max(16, 1 << (2 * distinct - 1).bit_length())
+        assert self.slots >= distinct and self.slots & (self.slots - 1) == 0
+
+    def arrays(self):
+        blob = np.frombuffer(b"".join(self.data) + b"\0", dtype=np.uint8)
+        off = np.zeros(len(self.data) + 1, dtype=np.uint64)
+        np.cumsum([len(w) for w in self.data], out=off[1:])
+        return blob, off, np.array(self.weight + [0], dtype=np.uint64), np.array(self.first + [0], dtype=np.uint64)
+
+    def expected(self):
+        """(rc, Trained) by the restatement: equal words are one word, weights add, the first offset is the smallest"""
+        seen = {}
+        for w, wt, f in zip(self.data, self.weight, self.first):
+            e = seen.setdefault(w, [0, f])
+            e[0] += wt
+            e[1] = min(e[1], f)
+        words = [tr.Word(w, wt, f) for w, (wt, f) in seen.items()]
+        try:
+            return 0, tr.train_words(words, self.n_merges)
+        except tr.Exhausted as e:
+            return 1, e.partial
+
+
+def run_lib(c: Case):
+    blob, off, weight, first = c.arrays()
+    n_sym_cap = len(blob)
+    pairs, counts = np.zeros(2 * c.n_merges + 1, np.uint32), np.zeros(c.n_merges + 1, np.uint64)
+    sym, pos = np.zeros(n_sym_cap + 1, np.uint32), np.zeros(n_sym_cap + 1, np.uint64)
+    n_done, n_sym = ctypes.c_uint64(), ctypes.c_uint64()
+    rc = lib().train_sim(blob.ctypes.data, off.ctypes.data, weight.ctypes.data, first.ctypes.data, len(c.data), c.slots, c.seed, c.block, c.n_merges, c.flags,
+                         pairs.ctypes.data, counts.ctypes.data, ctypes.byref(n_done), sym.ctypes.data, pos.ctypes.data, n_sym_cap, ctypes.byref(n_sym))
+    k = n_done.value
+    return rc, pairs[: 2 * k].reshape(k, 2).tolist(), counts[:k].tolist(), sorted(zip(pos[: n_sym.value].tolist(), sym[: n_sym.value].tolist()))
+
+
+def same(c: Case, got):
+    rc, pairs, counts, symbols = got
+    want_rc, want = c.expected()
+    assert rc == want_rc, (c.name, rc)
+    assert [tuple(p) for p in pairs] == want.pairs, (c.name, pairs[:8], want.pairs[:8])
+    assert counts == want.counts, (c.name, counts[:8], want.counts[:8])
+    assert symbols == want.symbols, (c.name, symbols[:8], want.symbols[:8])
+
+
+def filler(n, start=1):
+    """n bytes whose adjacent pairs are all different for n < 199 (and none is 'a', 'b' or 'c')"""
+    return bytes(1 + (start + 7 * i) % 96 for i in range(n))
+
+
+def run_lengths(block):
+    return sorted(set(list(range(1, 10)) + [63, 64, 65, block - 1, block, block + 1]) - {0})
+
+
+def cases(block):
+    rng = random.Random(block)
+    out = []
+    # runs of one symbol around workgroup boundaries: at the start of a word (the word before it ends p symbols into the arrays), at its end,
+    # and in its middle; several merges, so that the halved runs are merged again
+    for k in run_lengths(block):
+        for p in sorted({0, 1, block - 2, block - 1, block, block + 1} - {-1, -2}):
+            words = [(filler(p), 1)] if p else []
+            words += [(b"a" * k + filler(3, 50), 1), (filler(2, 70) + b"a" * k, 1), (filler(block - 1, 20) + b"a" * k + filler(2, 90), 1)]
+            out.append(Case(f"run k={k} p={p}", words, 7, block))
+    out.append(Case("5000 equal bytes", [(filler(block + 1), 1), (b"a" * 5000, 1), (b"ab", 3)], 14, block))
+    out.append(Case("words of one byte", [(b"a", 5), (b"b", 1), (b"a", 2), (b"\xff", 1)], 3, block))
+    out.append(Case("one-byte words among others", [(b"a", 5), (b"ab", 1), (b"b", 2), (b"abab", 4), (b"c", 1)], 5, block))
+    for total in (block, block - 1, block + 1, 2 * block + 40):
+        if total < 2:
+            continue
+        words, left = [], total
+        while left:
+            n = min(left, rng.choice([1, 2, 3, 5, 8]))
+            w = bytes(rng.choice(b"abc") for _ in range(n))
+            if w in [x for x, _ in words]:
+                w = bytes([rng.randrange(100, 250)]) + w[1:] if n > 1 else bytes([100 + len(words) % 150])
+                if w in [x for x, _ in words]:
+                    continue
+            words.append((w, rng.randrange(1, 4)))
+            left -= n
+        assert sum(len(w) for w, _ in words) == total
+        out.append(Case(f"{total} symbols", words, 12, block))
+    out.append(Case("weight above 2^32", [(b"abab", (1 << 32) + 7), (b"ba", (1 << 33)), (b"bab", 1), (b"abab", 5)], 4, block))
+    out.append(Case("every pair once", [(filler(40, 3), 1), (filler(30, 9)[::-1], 1)], 5, block))
+    out.append(Case("same word many times", [(b"hello", 1)] * 9 + [(b"help", 2)] * 3 + [(b"hello", 1)], 6, block, flags=3))
+    return out
+
+
+def table_cases():
+    rng = random.Random(7)
+    words = set()
+    while len(words) < 3000:
+        words.add(bytes(rng.choice(b"abcdefghijklmnopqrstuvwxyz") for _ in range(rng.randrange(2, 7))))
+    words = sorted(words)
+    rng.shuffle(words)
+    lst = [(w, rng.randrange(1, 50)) for w in words] + [(w, 1) for w in words[:500]]
+    return [
+        Case("3000 words, 4096 slots", lst, 40, 256, slots=4096, flags=1),
+        Case("3000 words, 4096 slots, colliding hashes", lst, 25, 64, slots=4096, seed=0, flags=0),
+        Case("two words in one hash", [(b"ab", 2), (b"ac", 3), (b"ab", 1), (b"ad", 1), (b"abc", 1), (b"acc", 2)], 4, 4, slots=8, seed=0, flags=3),
+        Case("a full table", [(bytes([65 + i, 66]), 1 + i) for i in range(16)], 5, 4, slots=16, flags=1),
+    ]
+
+
+def test_hash_seed_zero_collides():
+    """The test-only seed: two different words of one length and first byte share their hash (what the table cases above rely on)."""
+    got = run_lib(Case("x", [(b"ab", 1), (b"ac", 1)], 1, 4, slots=2, seed=0))
+    assert got[0] == 0 and len(got[1]) == 1  # (two slots, one hash: the second word moved on to the other slot)
+
+
+@pytest.mark.parametrize("block", BLOCKS)
+def test_case_list(block):
+    for c in cases(block):
+        same(c, run_lib(c))
+
+
+def test_word_table():
+    for c in table_cases():
+        same(c, run_lib(c))
+
+
+def test_table_too_small_is_reported():
+    c = Case("x", [(bytes([65 + i, 66]), 1) for i in range(9)], 1, 4, slots=16)
+    c.slots = 8
+    assert run_lib(c)[0] == 2
+
+
+def test_case_list_under_sanitizers(tmp_path):
+    """The driver as a program of its own, built with -fsanitize=address,undefined, on the same case list: it must run clean and give the
+    same results."""
+    exe = _build(os.path.join(D, "train_sim_san"), ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DTRAIN_SIM_MAIN"])
+    todo = [c for b in BLOCKS for c in cases(b)] + table_cases()
+    src, dst = tmp_path / "cases.bin", tmp_path / "results.bin"
+    with open(src, "wb") as f:
+        for c in todo:
+            blob, off, weight, first = c.arrays()
+            f.write(struct.pack("<9Q", len(c.data), c.slots, c.seed, c.block, c.n_merges, c.flags, len(blob), 0, 0))
+            f.write(off.tobytes() + weight[:-1].tobytes() + first[:-1].tobytes() + blob.tobytes())
+    r = subprocess.run([exe, str(src), str(dst)], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stderr == "", (r.returncode, r.stderr[-2000:])
+    assert r.stdout.strip() == f"{len(todo)} cases"
+    raw = open(dst, "rb").read()
+    at = 0
+    for c in todo:
+        rc, k, n_sym = struct.unpack_from("<qQQ", raw, at)
+        at += 24
+        pairs = np.frombuffer(raw, np.uint32, 2 * c.n_merges, at)
+        at += 8 * c.n_merges
+        counts = np.frombuffer(raw, np.uint64, c.n_merges, at)
+        at += 8 * c.n_merges
+        sym = np.frombuffer(raw, np.uint32, n_sym, at)
+        at += 4 * n_sym
+        pos = np.frombuffer(raw, np.uint64, n_sym, at)
+        at += 8 * n_sym
+        same(c, (rc, pairs[: 2 * k].reshape(k, 2).tolist(), counts[:k].tolist(), sorted(zip(pos.tolist(), sym.tolist()))))
+    assert at == len(raw)

@@ -133,6 +133,9 @@ def lib() -> ctypes.CDLL:
             L.tk_encode_batch_device_checked.argtypes = [vp, vp, u64, vp, vp, u64, i32, vp, u64, vp, P(vp), P(u64), P(vp), vp, u64, P(SpecialHit)]
             L.tk_group_encode_batch_checked.restype = i32
             L.tk_group_encode_batch_checked.argtypes = [vp, vp, vp, u64, i32, vp, u64, P(vp), P(u64), vp, vp, u64, P(SpecialHit)]
+        if hasattr(L, "tk_train_bpe"):  # (absent from older builds selected through $TIKTOKEN_AMD_LIB)
+            L.tk_train_bpe.restype = i32
+            L.tk_train_bpe.argtypes = [vp, vp, vp, u64, u32, P(vp), P(vp), P(u64)]
         if hasattr(L, "tk_stat"):  # (absent from older builds selected through $TIKTOKEN_AMD_LIB)
             L.tk_stat.restype = u64
             L.tk_stat.argtypes = [vp, ctypes.c_char_p]

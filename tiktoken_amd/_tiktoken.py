@@ -5,7 +5,8 @@ Same constructor and the same eleven methods, same exception types.  Two additiv
 `encode_batch_packed` and `pretokenize_packed`, expose the batch shape the GPU actually runs
 (one launch sequence per batch instead of one FFI call per document); `decode_batch_spans_packed`, `token_spans_device` and
 `encode_batch_spans_packed` give, for whole batches, where every token starts in its document (bytes and chars); `pack_rows_device` and
-`encode_batch_rows_packed` cut a batch into fixed-length training rows with document ids, positions and cu_seqlens.  With `disallowed_special` the batch
+`encode_batch_rows_packed` cut a batch into fixed-length training rows with document ids, positions and cu_seqlens; `train_bpe_packed`
+trains a vocabulary: the merges of the reference's educational `bpe_train`, made on the device.  With `disallowed_special` the batch
 calls also search the text for those special tokens, on the device, and raise `DisallowedSpecialError`.
 """
 from __future__ import annotations
@@ -723,6 +724,30 @@ class CoreBPE:
         cu, row_seg = _take_u32(out[3], n_segs + 1), _take_u32(out[4], n_rows + 1)
         self._pad_needed(has_pad, drop_last, n_stream, L)
         return PackedRows(*[a[: n_rows * L].reshape(n_rows, L) for a in arrays], cu, row_seg, n_stream, *[a[n_rows * L:] for a in arrays])
+
+    # ------------------------------------------------------------------ training (tiktoken/_educational.py: bpe_train)
+    def train_bpe_packed(self, blob: np.ndarray, doc_off: np.ndarray, vocab_size: int) -> tuple[np.ndarray, np.ndarray]:
+        """The merges the reference's `bpe_train` makes on a packed batch under this core's pat_str (tk_train_bpe; the rule:
+        include/tiktoken_amd.h): (pairs uint32[n, 2], counts uint64[n]) with n = vocab_size - 256 -- merge k joins the symbols pairs[k]
+        (0..255: the bytes, 256 + j: merge j) into symbol 256 + k, and counts[k] is that pair's weighted count when it won.  The core's
+        ranks play no part.  ValueError for vocab_size < 256, for a text that runs out of pairs, for a document longer than a chunk."""
+        self._one_device("train_bpe_packed")
+        if not 0 <= int(vocab_size) <= 0xFFFFFFFF:
+            raise ValueError("vocab_size must fit 32 bits")
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        doc_off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+        _check_packed(blob, doc_off)
+        src = blob if len(blob) else np.zeros(1, dtype=np.uint8)
+        pairs, counts, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64()
+        rc = self._L.tk_train_bpe(self._h, src.ctypes.data, doc_off.ctypes.data, len(doc_off) - 1, int(vocab_size), ctypes.byref(pairs), ctypes.byref(counts),
+                                  ctypes.byref(n))
+        _lib.raise_for(rc)
+        k = int(n.value)
+        p = np.frombuffer(ctypes.string_at(pairs, k * 8), dtype=np.uint32).reshape(k, 2).copy()
+        cn = np.frombuffer(ctypes.string_at(counts, k * 8), dtype=np.uint64).copy()
+        self._L.tk_free(pairs)
+        self._L.tk_free(counts)
+        return p, cn
 
     def decode_single_token_bytes(self, token: int) -> bytes:
         if not 0 <= token <= 0xFFFFFFFF:

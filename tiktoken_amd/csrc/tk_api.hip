@@ -24,6 +24,7 @@
 #include "tk_decode.h"
 #include "tk_offsets.h"
 #include "tk_rows.h"
+#include "tk_train.h"
 #include "tk_fused.h"
 #include "tk_mid_plan.h"
 #include "tk_tables.h"
@@ -2791,6 +2792,200 @@ extern "C" int tk_encode_batch_rows(tk_core* c, const uint8_t* utf8, const uint6
     *n_segs_out = v.n_segs;
     if (n_stream_out) *n_stream_out = v.n_stream;
     if (n_tail_out) *n_tail_out = v.n_tail;
+    return TK_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// BPE training (tk_train.h; the rule: include/tiktoken_amd.h).  Every buffer of a call belongs to its TrainRun and goes with it.
+// ------------------------------------------------------------------------------------------
+struct TrainRun {
+    Buf key, weight, first;  // the word table
+    uint64_t slots = 0;
+    Buf blob;                // the distinct words' bytes
+    Buf cells;
+    Buf sym[2], wid[2], pos[2], dec, pair, blk_mark, blk_cnt, merges, counts;
+    TkTrainTab tab() const { return TkTrainTab{key.as<unsigned long long>(), weight.as<unsigned long long>(), first.as<unsigned long long>(), slots - 1}; }
+};
+
+static int train_tab_alloc(tk_core* c, hipStream_t s, TrainRun& r, uint64_t slots) {
+    TRY(ensure(r.key, slots * 8));
+    TRY(ensure(r.weight, slots * 8));
+    TRY(ensure(r.first, slots * 8));
+    r.slots = slots;
+    return timed(c, s, "tk_k_train_tab_init", [&] { hipLaunchKernelGGL(tk_k_train_tab_init, dim3(grid_for(slots, 256, 65536)), dim3(256), 0, s, r.tab()); });
+}
+
+// room for `words` distinct words at a load of at most one half: the slot count follows from the number of pieces, known before they go in
+static int train_tab_reserve(tk_core* c, hipStream_t s, TrainRun& r, uint64_t words) {
+    uint64_t want = 1024;
+    while (want < 2 * words) want <<= 1;
+    if (want <= r.slots) return TK_OK;
+    if (want > (1ull << 32)) return fail(TK_VALUE_ERROR, "tk_train_bpe: more than 2^31 pieces");
+    if (!r.slots) return train_tab_alloc(c, s, r, want);
+    TrainRun old;
+    std::swap(old.key, r.key);
+    std::swap(old.weight, r.weight);
+    std::swap(old.first, r.first);
+    old.slots = r.slots;
+    TRY(train_tab_alloc(c, s, r, want));
+    TRY(timed(c, s, "tk_k_train_rehash", [&] {
+        hipLaunchKernelGGL(tk_k_train_rehash, dim3(grid_for(old.slots, 256, 65536)), dim3(256), 0, s, old.tab(), r.tab(), r.blob.as<uint8_t>(), (uint64_t)TK_HASH_SEED,
+                           r.cells.as<unsigned long long>());
+    }));
+    HIPCHK(hipStreamSynchronize(s));  // (the old table goes with `old`)
+    return TK_OK;
+}
+
+static int train_blob_reserve(hipStream_t s, TrainRun& r, uint64_t used, uint64_t bytes) {
+    if (bytes <= r.blob.cap && r.blob.p) return TK_OK;
+    Buf bigger;
+    TRY(ensure(bigger, bytes + bytes / 2));
+    if (used) HIPCHK(hipMemcpyAsync(bigger.p, r.blob.p, used, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    r.blob = std::move(bigger);
+    return TK_OK;
+}
+
+extern "C" int tk_train_bpe(tk_core* c, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, uint32_t vocab_size, uint32_t** pairs_out,
+                            uint64_t** counts_out, uint64_t* n_out) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if (!doc_off || !pairs_out || !counts_out || !n_out) return fail(TK_VALUE_ERROR, "null argument");
+    if (vocab_size < 256) return fail(TK_VALUE_ERROR, "vocab_size must be at least 256, so that every byte is a token");
+    if (vocab_size > (1u << 30)) return fail(TK_VALUE_ERROR, "vocab_size must be at most 2^30");
+    TRY(check_offsets(doc_off, n_docs, "doc_off"));
+    const uint64_t steps = vocab_size - 256u;
+    HostResult<uint32_t> pairs(malloc(steps * 8 + 8));
+    HostResult<uint64_t> counts(malloc(steps * 8 + 8));
+    if (!pairs || !counts) return fail(TK_RUNTIME_ERROR, "out of host memory");
+    if (!steps) {
+        *pairs_out = pairs.release();
+        *counts_out = counts.release();
+        *n_out = 0;
+        return TK_OK;
+    }
+    if (!utf8 && doc_off[n_docs]) return fail(TK_VALUE_ERROR, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    TrainRun r;
+    TRY(ensure(r.cells, TKT_CELLS * 8));
+    unsigned long long cells[TKT_CELLS] = {};
+    HIPCHK(hipMemsetAsync(r.cells.p, 0, TKT_CELLS * 8, s));
+    unsigned long long* d_cells = r.cells.as<unsigned long long>();
+
+    // The word table, chunk by chunk: document ranges [d0, d1) of at most `limit` bytes; offsets stay global (doc_off[d0] + place in the chunk).
+    const uint64_t limit = std::min<uint64_t>(c->chunk_bytes, (1ull << 31) - 4096);  // (bit 31 of a piece start marks a gap char)
+    std::vector<uint64_t> local;
+    for (uint64_t d0 = 0; d0 < n_docs;) {
+        uint64_t d1 = d0;
+        while (d1 < n_docs && doc_off[d1 + 1] - doc_off[d0] <= limit) ++d1;
+        if (d1 == d0)
+            return fail(TK_VALUE_ERROR, "tk_train_bpe: document " + std::to_string(d0) + " has " + std::to_string(doc_off[d0 + 1] - doc_off[d0]) +
+                                            " bytes, more than a chunk of " + std::to_string(limit) + ": split it into documents");
+        const uint64_t base = doc_off[d0], n = doc_off[d1] - base, nd = d1 - d0;
+        if (n) {
+            local.resize(nd + 1);
+            for (uint64_t d = 0; d <= nd; ++d) local[d] = doc_off[d0 + d] - base;
+            TRY(ensure(c->text, n + 256));
+            TRY(ensure(c->doc_off, (nd + 2) * 8));
+            HIPCHK(hipMemcpyAsync(c->text.p, utf8 + base, n, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemsetAsync((uint8_t*)c->text.p + n, 0, 128, s));
+            HIPCHK(hipMemcpyAsync(c->doc_off.p, local.data(), (nd + 1) * 8, hipMemcpyHostToDevice, s));
+            uint64_t P = 0;
+            TRY(run_chunk(c, s, c->text.as<uint8_t>(), n, c->doc_off.as<uint64_t>(), nd, 0, false, false, nullptr, nullptr, &P, true));  // (waits: P is known)
+            if (P) {
+                TRY(train_blob_reserve(s, r, cells[TKT_BLOB], cells[TKT_BLOB] + n + 64));
+                if ((cells[TKT_BLOB] + n) >> 32) return fail(TK_VALUE_ERROR, "tk_train_bpe: more than 4 GiB of distinct words");
+                TRY(train_tab_reserve(c, s, r, cells[TKT_NWORDS] + P));
+                const TkTrainTab t = r.tab();
+                TRY(timed(c, s, "tk_k_train_words", [&] {
+                    hipLaunchKernelGGL(tk_k_train_words, dim3(grid_for(P, 256, 65536)), dim3(256), 0, s, c->text.as<uint8_t>(), c->ws[0].pstart.as<uint32_t>(), P, base,
+                                       r.blob.as<uint8_t>(), t, (uint64_t)TK_HASH_SEED, d_cells);
+                }));
+                TRY(timed(c, s, "tk_k_train_blob", [&] {
+                    hipLaunchKernelGGL(tk_k_train_blob, dim3(grid_for(r.slots, 256, 65536)), dim3(256), 0, s, c->text.as<uint8_t>(), r.blob.as<uint8_t>(), (uint64_t)r.blob.cap, t,
+                                       d_cells);
+                }));
+                HIPCHK(hipMemcpyAsync(cells, d_cells, sizeof(cells), hipMemcpyDeviceToHost, s));
+                HIPCHK(hipStreamSynchronize(s));
+                if (cells[TKT_FULL]) return fail(TK_RUNTIME_ERROR, "tk_train_bpe: internal error: the word table or the word blob ran full");
+            }
+        }
+        d0 = d1;
+    }
+    TRY(drain_events(c));
+    const uint64_t N = cells[TKT_BLOB];  // symbols of the first step: a byte of a distinct word each
+    if (N < 2) return fail(TK_VALUE_ERROR, "tk_train_bpe: no pair left to merge after 0 of " + std::to_string(steps) + " merges: the text has no piece of two bytes");
+
+    // The symbol arrays (two sets: a step writes its survivors into the other one), the pair table, the per-workgroup words.
+    const uint64_t nb = (N + TKT_BLOCK - 1) / TKT_BLOCK;
+    uint64_t pair_slots = 1024;
+    while (pair_slots < 2 * N) pair_slots <<= 1;
+    for (int p = 0; p < 2; ++p) {
+        TRY(ensure(r.sym[p], N * 4));
+        TRY(ensure(r.wid[p], N * 4));
+        TRY(ensure(r.pos[p], N * 8));
+    }
+    TRY(ensure(r.dec, N));
+    TRY(ensure(r.pair, pair_slots * sizeof(TkTrainPair)));
+    TRY(ensure(r.blk_mark, nb * 4));
+    TRY(ensure(r.blk_cnt, nb * 8));
+    TRY(ensure(r.merges, steps * 8));
+    TRY(ensure(r.counts, steps * 8));
+    TRY(timed(c, s, "tk_k_train_expand", [&] {
+        hipLaunchKernelGGL(tk_k_train_expand, dim3(grid_for(r.slots, 256, 65536)), dim3(256), 0, s, r.tab(), r.blob.as<uint8_t>(), N, r.sym[0].as<uint32_t>(),
+                           r.wid[0].as<uint32_t>(), r.pos[0].as<unsigned long long>());
+    }));
+    cells[TKT_LIVE] = N;
+    cells[TKT_LIVE + 1] = 0;
+    cells[TKT_CMAX] = 0;
+    cells[TKT_BEST] = ~0ull;
+    cells[TKT_WIN] = 0;
+    cells[TKT_DONE] = 0;
+    HIPCHK(hipMemcpyAsync(d_cells, cells, sizeof(cells), hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));  // (`cells` is pageable memory and is written again below)
+
+    TkTrainStep st{};
+    for (int p = 0; p < 2; ++p) {
+        st.sym[p] = r.sym[p].as<uint32_t>();
+        st.wid[p] = r.wid[p].as<uint32_t>();
+        st.pos[p] = r.pos[p].as<unsigned long long>();
+    }
+    st.weight = r.weight.as<unsigned long long>();
+    st.pair = r.pair.as<TkTrainPair>();
+    st.pair_mask = pair_slots - 1;
+    st.dec = r.dec.as<uint8_t>();
+    st.blk_mark = r.blk_mark.as<uint32_t>();
+    st.blk_cnt = r.blk_cnt.as<unsigned long long>();
+    st.cells = d_cells;
+    st.merges = r.merges.as<uint32_t>();
+    st.counts = r.counts.as<unsigned long long>();
+    const dim3 grid((uint32_t)nb), one(1);
+    // The merge loop: no host wait inside -- the live count, the winner and the "no pair left" flag stay in the cells.
+    for (uint64_t k = 0; k < steps; ++k) {
+        st.step = (uint32_t)k;
+        st.par = (uint32_t)(k & 1u);
+        TRY(timed(c, s, "tk_train_pair_clear", [&] { (void)hipMemsetAsync(r.pair.p, 0, pair_slots * sizeof(TkTrainPair), s); }));
+        TRY(timed(c, s, "tk_k_train_count", [&] { hipLaunchKernelGGL(tk_k_train_count, grid, dim3(TKT_BLOCK), 0, s, st); }));
+        TRY(timed(c, s, "tk_k_train_best", [&] { hipLaunchKernelGGL(tk_k_train_best, grid, dim3(TKT_BLOCK), 0, s, st); }));
+        TRY(timed(c, s, "tk_k_train_pick", [&] { hipLaunchKernelGGL(tk_k_train_pick, grid, dim3(TKT_BLOCK), 0, s, st); }));
+        TRY(timed(c, s, "tk_k_train_breaks", [&] { hipLaunchKernelGGL(tk_k_train_breaks, grid, dim3(TKT_BLOCK), 0, s, st); }));
+        TRY(timed(c, s, "tk_k_train_carry", [&] { hipLaunchKernelGGL(tk_k_train_carry, one, dim3(1024), 0, s, st); }));
+        TRY(timed(c, s, "tk_k_train_decide", [&] { hipLaunchKernelGGL(tk_k_train_decide, grid, dim3(TKT_BLOCK), 0, s, st); }));
+        TRY(timed(c, s, "tk_k_train_offsets", [&] { hipLaunchKernelGGL(tk_k_train_offsets, one, dim3(1024), 0, s, st); }));
+        TRY(timed(c, s, "tk_k_train_rewrite", [&] { hipLaunchKernelGGL(tk_k_train_rewrite, grid, dim3(TKT_BLOCK), 0, s, st); }));
+    }
+    HIPCHK(hipMemcpyAsync(cells, d_cells, sizeof(cells), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(pairs, r.merges.p, steps * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(counts, r.counts.p, steps * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    TRY(drain_events(c));
+    if (cells[TKT_DONE])
+        return fail(TK_VALUE_ERROR, "tk_train_bpe: no pair left to merge after " + std::to_string(cells[TKT_DONE] - 1) + " of " + std::to_string(steps) +
+                                        " merges: vocab_size is too large for this text");
+    *pairs_out = pairs.release();
+    *counts_out = counts.release();
+    *n_out = steps;
     return TK_OK;
 }
 
