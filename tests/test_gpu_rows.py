@@ -105,6 +105,22 @@ def test_token_pointer_that_is_not_16_byte_aligned():
         same(got, rr.rows_rule(tokens, tok_off, 64, pad=0), shift)
 
 
+def test_more_than_1024_workgroups():
+    """tk_k_rows_scan takes the counts of 1024 workgroups at a time: 1024 * 2048 + 2049 positions are 1026 workgroups, the last one partial,
+    so its loop runs twice and the segments of the first 1024 workgroups are carried into the rest."""
+    core = core_of()
+    rng = np.random.default_rng(1026)
+    n = 1024 * BLOCK + 2049
+    cuts = rng.integers(0, n + 1, size=260)
+    cuts = np.sort(np.concatenate([cuts, rng.choice(cuts, size=40), [n, n]]))  # 303 documents, 42 and more of them empty
+    tok_off = np.concatenate([[0], cuts, [n]]).astype(np.uint64)
+    tokens = rng.integers(0, 50000, size=n).astype(np.uint32)
+    assert int((np.diff(tok_off.astype(np.int64)) == 0).sum()) >= 42 and int((cuts > 1024 * BLOCK).sum()) >= 2
+    want = rr.rows_rule(tokens, tok_off, 1000, None, None, 7, True)
+    assert want.n_stream == n and want.n_tail == n % 1000 and -(-(want.n_rows * 1000 + want.n_tail) // BLOCK) == 1026
+    same(pack_device(core, tokens, tok_off, 1000, None, None, 7, True), want, "1026 workgroups")
+
+
 # ---------------------------------------------------------------- invariants on a random batch
 def test_invariants_on_a_random_batch():
     core = core_of("cl100k_shaped")

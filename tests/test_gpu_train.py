@@ -102,6 +102,27 @@ def test_long_run_single_bytes_and_sizes(core, whole_core):
     check_against_restatement(whole_core, [filler(40, 3), filler(30, 9)[::-1]], 5, pat=WHOLE)  # every pair occurs once: position decides
 
 
+def test_more_than_1024_workgroups(whole_core):
+    """The step's single-workgroup kernels (tk_k_train_carry, tk_k_train_offsets) take the values of 1024 workgroups of 256 symbols at a time:
+    distinct words of just over 1024 * 256 symbols run their loops twice.  Most words hold a run of one letter, many of them longer than a
+    workgroup, so the first winners have a == b and the largest break mark is carried from workgroup to workgroup, the 1024th included;
+    later winners are pairs of the other letters."""
+    rng = np.random.default_rng(1024)
+    letters, total = list("abcde"), 1024 * 256 + 300
+    words, left = set(), total
+    while left:
+        w = "".join(rng.choice(letters, size=int(rng.integers(1, 120)))) + "z" * int(rng.choice([0, 0, 3, 50, 300, 700])) + "".join(rng.choice(letters, size=int(rng.integers(0, 10))))
+        w = w[:left]
+        if w in words:
+            continue
+        words.add(w)
+        left -= len(w)
+    docs = sorted(words)
+    assert sum(map(len, docs)) == total and len(docs) > 500 and len(set(map(len, docs))) > 100
+    pairs, _ = check_against_restatement(whole_core, docs, 8, pat=WHOLE)
+    assert pairs[0].tolist() == [122, 122] and pairs[1].tolist() == [256, 256] and any(a != b for a, b in pairs.tolist())
+
+
 def test_large_weight_and_many_words(core):
     rng = np.random.default_rng(11)
     words = ["".join(rng.choice(list("abcdefghijklmnopqrstuvwxyz"), size=int(rng.integers(2, 7)))) for _ in range(3000)]

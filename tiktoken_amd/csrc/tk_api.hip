@@ -47,6 +47,7 @@ static int fail(int code, const std::string& msg) {
 // ------------------------------------------------------------------------------------------
 // Owners.  Every device buffer, page-locked block, stream and event of this file belongs to one of these and goes with it: nothing
 // below (the pinned pool aside) calls hipFree / hipHostFree / hipStreamDestroy / hipEventDestroy itself.  Movable, not copyable; each converts to its raw handle.
+// (The owner of a host thread that sends a block after the other to the device, Feed, stands further down, beside the copies it makes.)
 // ------------------------------------------------------------------------------------------
 struct Buf {  // device memory
     void* p = nullptr;
@@ -357,6 +358,13 @@ static int drain_events(tk_core* c) {
         ks.launches += 1;
     }
     return TK_OK;
+}
+// a pass of timed launches: the timed pairs go whatever happened to it; the first error
+template <class F>
+static int drained(tk_core* c, F&& f) {
+    const int rc = f();
+    const int rc2 = drain_events(c);
+    return rc != TK_OK ? rc : rc2;
 }
 #define TRY(x)                      \
     do {                            \
@@ -1595,6 +1603,87 @@ static void parallel_memcpy(void* dst, const void* src, size_t n, unsigned nth) 
     for (auto& t : th) t.join();
 }
 
+// One more owner (see the top of the file): a host array on its way to the device in blocks, sent on c->cs_h2d by a thread of its own
+// while the caller's thread consumes the blocks.  The thread, its events and its flags go with this object, and it leaves no scope
+// before the thread has ended and the copy stream is idle: an early return of the consumer cannot outlive either.
+// staged: the source is pageable and the caller wants it copied through the core's two page-locked staging blocks (c->stage, c->ev_stage:
+// made by the caller, a block of this feed fits into one) by a few host threads; otherwise the copy takes the source as it is.
+struct Feed {
+    tk_core* const c;
+    uint8_t* const dst;
+    const uint8_t* const src;
+    const uint64_t n, block, n_blocks;
+    const bool staged;
+    std::vector<Event> ev;  // one per block: it has arrived
+    std::atomic<int> rc{TK_OK};
+    std::atomic<uint64_t> sent{0};
+    std::thread th;
+    Feed(tk_core* c_, void* dst_, const void* src_, uint64_t bytes, uint64_t block_, bool staged_ = false)
+        : c(c_), dst((uint8_t*)dst_), src((const uint8_t*)src_), n(bytes), block(block_), n_blocks((bytes + block_ - 1) / block_), staged(staged_), ev(n_blocks) {}
+    ~Feed() { if (th.joinable()) (void)finish(); }
+    int start() {
+        for (auto& e : ev) HIPCHK(e.create());
+        th = std::thread([this]() {
+            (void)hipSetDevice(c->device);
+            const unsigned nth = copy_threads(std::thread::hardware_concurrency());
+            for (uint64_t k = 0; k < n_blocks; ++k) {
+                const uint64_t a = k * block, len = a + block < n ? block : n - a;
+                const int slot = (int)(k & 1);
+                const void* from = src + a;
+                if (staged) {
+                    if (k >= 2 && hipEventSynchronize(c->ev_stage[slot]) != hipSuccess) rc = TK_RUNTIME_ERROR;
+                    parallel_memcpy(c->stage[slot], from, len, nth);
+                    from = c->stage[slot];
+                }
+                if (hipMemcpyAsync(dst + a, from, len, hipMemcpyHostToDevice, c->cs_h2d) != hipSuccess) rc = TK_RUNTIME_ERROR;
+                if (staged) (void)hipEventRecord(c->ev_stage[slot], c->cs_h2d);
+                (void)hipEventRecord(ev[k], c->cs_h2d);
+                sent.store(k + 1, std::memory_order_release);
+            }
+        });
+        return TK_OK;
+    }
+    // the consumer: block k (and every one before it) has been sent, and stream `s` goes on once it has arrived
+    int wait(uint64_t k, hipStream_t s) {
+        while (sent.load(std::memory_order_acquire) <= k) std::this_thread::yield();
+        if (rc.load() != TK_OK) return fail(TK_RUNTIME_ERROR, "host-to-device copy failed");
+        HIPCHK(hipStreamWaitEvent(s, ev[k], 0));
+        return TK_OK;
+    }
+    // every block has been sent and has arrived (or not: the copy stream's error)
+    hipError_t finish() {
+        if (th.joinable()) th.join();
+        return hipStreamSynchronize(c->cs_h2d);
+    }
+};
+
+// a result array on its way to the caller: page-locked from a MiB on (the copy back runs at the link's rate)
+static void* result_alloc(size_t bytes) { return bytes >= (1u << 20) ? pinned_get(bytes) : malloc(bytes ? bytes : 1); }
+// A result array that is filled while its final size is not known yet, sized by the density so far: `done` of the call's `all` input units
+// have made `need` elements (`filled` of them are in the array or on their way into it on c->cs_d2h, the others follow once this returns).
+// An array that turns out too small is replaced by one of the new estimate and what it holds is copied over.
+struct GrowRule {
+    double slack;     // the estimate: the density so far times this ...
+    uint64_t extra;   // ... plus so many elements
+    bool pinned;      // page-locked whatever the size (otherwise: result_alloc's rule)
+    const char* oom;  // the message when there is no memory
+};
+template <class T>
+static int result_grow(tk_core* c, HostResult<T>& host, uint64_t& cap, uint64_t filled, uint64_t need, uint64_t done, uint64_t all, bool last, const GrowRule& g) {
+    if (need <= cap && host) return TK_OK;
+    uint64_t est = last ? need : (uint64_t)((double)need / (double)(done ? done : 1) * (double)all * g.slack) + g.extra;
+    if (est < need) est = need;
+    HostResult<T> nh(g.pinned ? pinned_get((est ? est : 1) * sizeof(T)) : result_alloc(est * sizeof(T)));
+    if (!nh) return fail(TK_RUNTIME_ERROR, g.oom);
+    if (host) {
+        HIPCHK(hipStreamSynchronize(c->cs_d2h));
+        if (filled) parallel_memcpy(nh, host, filled * sizeof(T), copy_threads(std::thread::hardware_concurrency()));
+    }
+    host = std::move(nh);  // (the old array goes with `nh`)
+    cap = est;
+    return TK_OK;
+}
+
 static int encode_batch_impl(tk_core* c, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special, const uint32_t* allowed_ids,
                              uint64_t n_allowed, uint32_t** tokens_out, uint64_t* n_tokens_out, uint64_t* tok_off_out, bool device_result, bool no_small,
                              const CheckArgs* chk = nullptr, bool locked = false);
@@ -1901,7 +1990,7 @@ static int encode_batch_impl(tk_core* c, const uint8_t* utf8, const uint64_t* do
             *n_tokens_out = total;
             return TK_OK;
         }
-        HostResult<uint32_t> host(total * 4 >= (1u << 20) ? pinned_get((total ? total : 1) * 4) : malloc((total ? total : 1) * 4));
+        HostResult<uint32_t> host(result_alloc(total * 4));
         if (!host) return fail(TK_RUNTIME_ERROR, "out of host memory");
         if (total) HIPCHK(hipMemcpy(host, c->out_tokens.p, total * 4, hipMemcpyDeviceToHost));
         if (tok_off_out) HIPCHK(hipMemcpy(tok_off_out, c->out_tok_off.p, (n_docs + 1) * 8, hipMemcpyDeviceToHost));
@@ -1916,58 +2005,22 @@ static int encode_batch_impl(tk_core* c, const uint8_t* utf8, const uint64_t* do
     // the runtime's own staging.  So the text takes that copy, in blocks of 64 MiB (smaller ones cost the copy its rate: 28 ms with 16 MiB), and
     // chunks of 32 MiB: 25 ms per GiB = 0.88 of what the link gives in both directions at once, where the staging buffers of rounds 2-5
     // (filled by host threads, 64 MiB at a time, chunks of 128 MiB) took 32 ms.
-    const uint64_t block_bytes = TK_STAGE_BYTES;
-    const uint64_t n_blocks = (n_bytes + block_bytes - 1) / block_bytes;
-    std::vector<Event> ev_block(n_blocks);
-    for (auto& e : ev_block) HIPCHK(e.create());
-    // producer: send the text, block by block.  (Nothing returns between its start and producer.join() below: the events and the result
-    // buffer are let go only after it has ended.)
-    std::atomic<int> h2d_rc{TK_OK};
-    std::atomic<uint64_t> blocks_sent{0};
-    const int dev = c->device;
-    std::thread producer([&]() {
-        (void)hipSetDevice(dev);
-        for (uint64_t b = 0; b < n_blocks; ++b) {
-            const uint64_t a = b * block_bytes, len = a + block_bytes < n_bytes ? block_bytes : n_bytes - a;
-            if (hipMemcpyAsync((uint8_t*)c->text.p + a, utf8 + a, len, hipMemcpyHostToDevice, c->cs_h2d) != hipSuccess) h2d_rc = TK_RUNTIME_ERROR;
-            (void)hipEventRecord(ev_block[b], c->cs_h2d);
-            blocks_sent.store(b + 1, std::memory_order_release);
-        }
-    });
-    // consumer side
-    const unsigned nth = copy_threads(std::thread::hardware_concurrency());  // (a result buffer regrown: the ids so far copied over)
     HostResult<uint32_t> host;
     uint64_t host_cap = 0;  // tokens
+    Feed feed(c, c->text.p, utf8, n_bytes, TK_STAGE_BYTES);
+    TRY(feed.start());
     ChunkHooks hooks;
-    hooks.before = [&](uint64_t byte_end) -> int {
-        const uint64_t need = (byte_end + block_bytes - 1) / block_bytes;  // blocks [0, need) must have been sent
-        while (blocks_sent.load(std::memory_order_acquire) < need) std::this_thread::yield();
-        if (need) HIPCHK(hipStreamWaitEvent(s, ev_block[need - 1], 0));
-        return h2d_rc.load() == TK_OK ? TK_OK : fail(TK_RUNTIME_ERROR, "host-to-device copy failed");
-    };
-    uint64_t bytes_done = 0;
+    hooks.before = [&](uint64_t byte_end) -> int { return byte_end ? feed.wait((byte_end - 1) / feed.block, s) : TK_OK; };  // the blocks up to byte_end
+    const GrowRule grow{1.08, 4096, true, "out of page-locked host memory"};
     if (!device_result) hooks.after = [&](uint64_t tok_begin, uint64_t n_tok, bool last) -> int {
-        bytes_done = c->st_bytes;  // (bytes encoded so far: the density of the chunks seen sizes the result buffer)
-        const uint64_t need = tok_begin + n_tok;
-        if (need > host_cap || !host) {
-            uint64_t est = last ? need : (uint64_t)((double)need / (double)(bytes_done ? bytes_done : 1) * (double)n_bytes * 1.08) + 4096;
-            if (est < need) est = need;
-            HostResult<uint32_t> nh(pinned_get((est ? est : 1) * 4));
-            if (!nh) return fail(TK_RUNTIME_ERROR, "out of page-locked host memory");
-            if (host) {
-                HIPCHK(hipStreamSynchronize(c->cs_d2h));
-                if (tok_begin) parallel_memcpy(nh, host, tok_begin * 4, nth);
-            }
-            host = std::move(nh);  // (the old buffer goes back to the pool with `nh`)
-            host_cap = est;
-        }
+        // (c->st_bytes: bytes encoded so far -- the density of the chunks seen sizes the result buffer)
+        TRY(result_grow(c, host, host_cap, tok_begin, tok_begin + n_tok, c->st_bytes, n_bytes, last, grow));
         if (n_tok) HIPCHK(hipMemcpyAsync(host + tok_begin, c->out_tokens.as<uint32_t>() + tok_begin, n_tok * 4, hipMemcpyDeviceToHost, c->cs_d2h));
         return TK_OK;
     };
     int rc = encode_device_locked(c, s, c->text.as<uint8_t>(), n_bytes, c->doc_off.as<uint64_t>(), doc_off, n_docs, use_special && any, &total,
                                   32ull << 20, &hooks);
-    producer.join();
-    hipError_t e = hipStreamSynchronize(c->cs_h2d);
+    hipError_t e = feed.finish();
     if (e == hipSuccess) e = hipStreamSynchronize(c->cs_d2h);
     if (rc == TK_SPEC_HIT) {  // (the text has arrived and nothing is on its way back: the caller's buffers are his again)
         if (e != hipSuccess) return fail(TK_RUNTIME_ERROR, std::string("HIP error: ") + hipGetErrorString(e));
@@ -1983,6 +2036,13 @@ static int encode_batch_impl(tk_core* c, const uint8_t* utf8, const uint64_t* do
     if (device_result) return TK_OK;
     *tokens_out = host ? host.release() : (uint32_t*)pinned_get(64);
     return TK_OK;
+}
+
+// encode, keep the ids on the device (c->out_tokens, c->out_tok_off) for a pass over them; the caller holds c->mu
+static int encode_batch_kept(tk_core* c, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special, const uint32_t* allowed_ids,
+                             uint64_t n_allowed, const CheckArgs& chk, uint64_t* n_tokens_out) {
+    return encode_batch_impl(c, utf8, doc_off, n_docs, use_special, allowed_ids, n_allowed, nullptr, n_tokens_out, nullptr, /* device_result */ true, /* no_small */ true,
+                             chk.n ? &chk : nullptr, /* locked */ true);
 }
 
 extern "C" int tk_encode_batch(tk_core* c, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special,
@@ -2104,6 +2164,14 @@ extern "C" int tk_decode_single_token_bytes(tk_core* c, uint32_t token, const ui
     return fail(TK_KEY_ERROR, std::to_string(token));
 }
 
+// the reference's KeyError for an id that has no bytes: ids[pos], ids on the device or on the host
+static int invalid_token(const uint32_t* ids, uint64_t pos, bool on_device) {
+    uint32_t bad_tok = 0;
+    if (on_device) (void)hipMemcpy(&bad_tok, ids + pos, 4, hipMemcpyDeviceToHost);
+    else bad_tok = ids[pos];
+    return fail(TK_KEY_ERROR, "Invalid token for decoding: " + std::to_string(bad_tok));
+}
+
 extern "C" int tk_decode_bytes(tk_core* c, const uint32_t* tokens, uint64_t n, uint8_t** bytes_out, uint64_t* len_out) {
     if (!c) return fail(TK_VALUE_ERROR, "core is null");
     if (n >= 8192 && c->n_dec) {  // long inputs: on the device (short ones are quicker on the host than a launch)
@@ -2115,8 +2183,7 @@ extern "C" int tk_decode_bytes(tk_core* c, const uint32_t* tokens, uint64_t n, u
     for (uint64_t i = 0; i < n; ++i) {
         const uint8_t* p;
         uint64_t l;
-        if (tk_decode_single_token_bytes(c, tokens[i], &p, &l) != TK_OK)
-            return fail(TK_KEY_ERROR, "Invalid token for decoding: " + std::to_string(tokens[i]));
+        if (tk_decode_single_token_bytes(c, tokens[i], &p, &l) != TK_OK) return invalid_token(tokens, i, false);
         acc.append((const char*)p, l);
     }
     uint8_t* host = (uint8_t*)malloc(acc.size() ? acc.size() : 1);
@@ -2171,11 +2238,7 @@ extern "C" int tk_decode_batch_device(tk_core* c, const void* d_tokens, uint64_t
     if (n) TRY(decode_range_len(c, s, (const uint32_t*)d_tokens, 0, n, tot));
     HIPCHK(hipMemcpyAsync(h_tot, tot, 16, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    if (h_tot[1] != ~0ull) {
-        uint32_t bad_tok = 0;
-        (void)hipMemcpy(&bad_tok, (const uint32_t*)d_tokens + h_tot[1], 4, hipMemcpyDeviceToHost);
-        return fail(TK_KEY_ERROR, "Invalid token for decoding: " + std::to_string(bad_tok));
-    }
+    if (h_tot[1] != ~0ull) return invalid_token((const uint32_t*)d_tokens, h_tot[1], true);
     const uint64_t nbytes = h_tot[0];
     TRY(ensure(c->d_bytes, nbytes + 16));
     if (n) TRY(decode_range_copy(c, s, (const uint32_t*)d_tokens, 0, n, c->d_bytes.as<uint8_t>(), d_tok_off ? c->d_tboff.as<unsigned long long>() : nullptr, 0));
@@ -2229,37 +2292,15 @@ extern "C" int tk_decode_batch(tk_core* c, const uint32_t* tokens, const uint64_
         if (n && hipPointerGetAttributes(&at, tokens) == hipSuccess) src_pinned = at.type == hipMemoryTypeHost;
         else (void)hipGetLastError();
     }
-    std::vector<Event> ev_in(n_ranges), ev_out(2);
-    for (auto& e : ev_in) HIPCHK(e.create());
+    std::vector<Event> ev_out(2);
     for (auto& e : ev_out) HIPCHK(e.create());
     Event ev_copy;
     HIPCHK(ev_copy.create());
-    // (nothing returns between the producer's start and producer.join() below: events and result buffer are let go only after it has ended)
-    std::atomic<int> h2d_rc{TK_OK};
-    std::atomic<uint64_t> sent{0};
-    const int dev = c->device;
-    const unsigned nth = copy_threads(std::thread::hardware_concurrency());
-    std::thread producer([&]() {
-        (void)hipSetDevice(dev);
-        for (uint64_t k = 0; k < n_ranges; ++k) {
-            const uint64_t a = k * RANGE, cnt = a + RANGE < n ? RANGE : n - a;
-            const void* src = tokens + a;
-            if (!src_pinned) {
-                const int slot = (int)(k & 1);
-                if (k >= 2 && hipEventSynchronize(c->ev_stage[slot]) != hipSuccess) h2d_rc = TK_RUNTIME_ERROR;
-                parallel_memcpy(c->stage[slot], tokens + a, cnt * 4, nth);
-                src = c->stage[slot];
-                if (hipMemcpyAsync(c->d_tok.as<uint32_t>() + a, src, cnt * 4, hipMemcpyHostToDevice, c->cs_h2d) != hipSuccess) h2d_rc = TK_RUNTIME_ERROR;
-                (void)hipEventRecord(c->ev_stage[slot], c->cs_h2d);
-            } else if (hipMemcpyAsync(c->d_tok.as<uint32_t>() + a, src, cnt * 4, hipMemcpyHostToDevice, c->cs_h2d) != hipSuccess) {
-                h2d_rc = TK_RUNTIME_ERROR;
-            }
-            (void)hipEventRecord(ev_in[k], c->cs_h2d);
-            sent.store(k + 1, std::memory_order_release);
-        }
-    });
     HostResult<uint8_t> host;
     uint64_t host_cap = 0, base = 0;
+    const GrowRule grow{1.06, 4096, n_ranges > 1, "out of host memory"};
+    Feed feed(c, c->d_tok.p, tokens, n * 4, RANGE * 4, !src_pinned);
+    TRY(feed.start());
     Buf* dout[2] = {&c->d_bytes, &c->d_bytes_alt};
     int rc = TK_OK;
     uint64_t bad_pos = ~0ull;
@@ -2275,10 +2316,8 @@ extern "C" int tk_decode_batch(tk_core* c, const uint32_t* tokens, const uint64_
     auto step = [&](uint64_t k) -> int {
         const uint64_t a = k * RANGE, cnt = a + RANGE < n ? RANGE : n - a;
         const double t_0 = now_us();
-        while (sent.load(std::memory_order_acquire) <= k) std::this_thread::yield();
+        TRY(feed.wait(k, s));
         const double t_1 = now_us();
-        if (h2d_rc.load() != TK_OK) return fail(TK_RUNTIME_ERROR, "host-to-device copy failed");
-        HIPCHK(hipStreamWaitEvent(s, ev_in[k], 0));
         unsigned long long* tot = tots + 2 * (k + 1);
         TRY(decode_range_len(c, s, c->d_tok.as<uint32_t>(), a, cnt, tot));
         unsigned long long h_tot[2] = {0, ~0ull};
@@ -2297,18 +2336,7 @@ extern "C" int tk_decode_batch(tk_core* c, const uint32_t* tokens, const uint64_
         HIPCHK(hipEventRecord(ev_copy, s));
         // the result buffer: sized by the density so far
         const uint64_t need = base + nbk, done = a + cnt;
-        if (need > host_cap || !host) {
-            uint64_t est = done == n ? need : (uint64_t)((double)need / (double)done * (double)n * 1.06) + 4096;
-            if (est < need) est = need;
-            HostResult<uint8_t> nh(est >= (1u << 20) || n_ranges > 1 ? pinned_get(est ? est : 1) : malloc(est ? est : 1));
-            if (!nh) return fail(TK_RUNTIME_ERROR, "out of host memory");
-            if (host) {
-                HIPCHK(hipStreamSynchronize(c->cs_d2h));
-                if (base) parallel_memcpy(nh, host, base, nth);
-            }
-            host = std::move(nh);  // (the old buffer is freed with `nh`)
-            host_cap = est;
-        }
+        TRY(result_grow(c, host, host_cap, base, need, done, n, done == n, grow));
         const double t_3 = now_us();
         if (c->dbg & TK_DBG_VERBOSE)
             fprintf(stderr, "decode range %llu: at %.0f us; ids waited %.0f us, lengths %.0f us, buffers %.0f us\n", (unsigned long long)k, t_0 - t_call, t_1 - t_0,
@@ -2320,8 +2348,7 @@ extern "C" int tk_decode_batch(tk_core* c, const uint32_t* tokens, const uint64_
         return TK_OK;
     };
     for (uint64_t k = 0; k < n_ranges && rc == TK_OK; ++k) rc = step(k);
-    producer.join();
-    hipError_t e = hipStreamSynchronize(c->cs_h2d);
+    hipError_t e = feed.finish();
     if (rc == TK_OK && byte_off_out) {
         uint64_t* d_tok_off = c->d_boff.as<uint64_t>();
         uint64_t* d_byte_off = d_tok_off + n_docs + 1;
@@ -2337,7 +2364,7 @@ extern "C" int tk_decode_batch(tk_core* c, const uint32_t* tokens, const uint64_
     if (e == hipSuccess) e = hipStreamSynchronize(c->cs_d2h);
     if (e == hipSuccess) e = hipGetLastError();
     if (c->dbg & TK_DBG_VERBOSE) fprintf(stderr, "decode: %llu ranges, ids %s, %.0f us\n", (unsigned long long)n_ranges, src_pinned ? "page-locked" : "staged", now_us() - t_call);
-    if (rc == TK_KEY_ERROR && bad_pos != ~0ull) rc = fail(TK_KEY_ERROR, "Invalid token for decoding: " + std::to_string(tokens[bad_pos]));
+    if (rc == TK_KEY_ERROR && bad_pos != ~0ull) rc = invalid_token(tokens, bad_pos, false);
     if (rc == TK_OK && e != hipSuccess) rc = fail(TK_RUNTIME_ERROR, std::string("HIP error: ") + hipGetErrorString(e));
     if (rc == TK_OK) rc = drain_events(c);  // (before the outputs are published: a caller that gets an error owns nothing)
     else (void)drain_events(c);
@@ -2412,11 +2439,7 @@ static int spans_end(tk_core* c, hipStream_t s, const uint32_t* d_tok, const uin
     HIPCHK(hipMemcpyAsync(h_words, words, sizeof h_words, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
-    if (h_words[TK_SPAN_BAD_TOKEN] != ~0ull) {  // (reported as tk_k_dec_len's: the first id without an entry)
-        uint32_t bad_tok = 0;
-        (void)hipMemcpy(&bad_tok, d_tok + h_words[TK_SPAN_BAD_TOKEN], 4, hipMemcpyDeviceToHost);
-        return fail(TK_KEY_ERROR, "Invalid token for decoding: " + std::to_string(bad_tok));
-    }
+    if (h_words[TK_SPAN_BAD_TOKEN] != ~0ull) return invalid_token(d_tok, h_words[TK_SPAN_BAD_TOKEN], true);  // (reported as tk_k_dec_len's: the first id without an entry)
     if (h_words[TK_SPAN_BIG_DOC] != ~0ull)
         return fail(TK_VALUE_ERROR, "document " + std::to_string(h_words[TK_SPAN_BIG_DOC]) + " decodes to 4 GiB or more: token spans are 32-bit offsets into a document");
     if (h_words[TK_SPAN_GAP_DOC] != ~0ull)
@@ -2461,12 +2484,6 @@ static int spans_run(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t 
     }
     return TK_OK;
 }
-static int spans_locked(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n, const uint64_t* d_tok_off, uint64_t n_docs, const uint64_t* d_doc_off,
-                        bool want_bytes, bool validate, SpanView* out) {
-    const int rc = spans_run(c, s, d_tok, n, d_tok_off, n_docs, d_doc_off, want_bytes, validate, out);
-    const int rc2 = drain_events(c);  // (the timed pairs go whatever happened)
-    return rc != TK_OK ? rc : rc2;
-}
 
 extern "C" int tk_token_spans_device(tk_core* c, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_docs, const void* d_doc_off, void* stream,
                                      const uint32_t** d_byte_start_out, const uint32_t** d_char_start_out, const uint64_t** d_byte_off_out,
@@ -2476,8 +2493,9 @@ extern "C" int tk_token_spans_device(tk_core* c, const void* d_tokens, uint64_t 
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(hipSetDevice(c->device));
     SpanView v;
-    TRY(spans_locked(c, stream ? (hipStream_t)stream : c->stream, (const uint32_t*)d_tokens, n_tokens, (const uint64_t*)d_tok_off, n_docs, (const uint64_t*)d_doc_off, false,
-                     false, &v));
+    TRY(drained(c, [&] {
+        return spans_run(c, stream ? (hipStream_t)stream : c->stream, (const uint32_t*)d_tokens, n_tokens, (const uint64_t*)d_tok_off, n_docs, (const uint64_t*)d_doc_off, false, false, &v);
+    }));
     if (d_byte_start_out) *d_byte_start_out = v.byte_start;
     if (d_char_start_out) *d_char_start_out = v.char_start;
     if (d_byte_off_out) *d_byte_off_out = v.byte_off;
@@ -2485,8 +2503,6 @@ extern "C" int tk_token_spans_device(tk_core* c, const void* d_tokens, uint64_t 
     return TK_OK;
 }
 
-// a result array on its way to the caller: page-locked from a MiB on (the copy back runs at the link's rate)
-static void* result_alloc(size_t bytes) { return bytes >= (1u << 20) ? pinned_get(bytes) : malloc(bytes ? bytes : 1); }
 // the spans of n tokens from the device into two result arrays
 static int spans_to_host(const SpanView& v, uint64_t n, HostResult<uint32_t>& bs, HostResult<uint32_t>& cs) {
     bs = HostResult<uint32_t>(result_alloc(n * 4));
@@ -2511,9 +2527,9 @@ static int decode_spans_ranges(tk_core* c, hipStream_t s, const uint32_t* tokens
     const uint64_t* d_tok_off = c->d_boff.as<uint64_t>();
     uint32_t* d_tok = c->d_tok.as<uint32_t>();
     TRY(ensure_copy_streams(c));
-    std::vector<Event> ev_in(n_ranges), ev_out(n_ranges);
-    for (auto& e : ev_in) HIPCHK(e.create());
+    std::vector<Event> ev_out(n_ranges), ev_bytes(want_bytes ? n_ranges : 0);  // the spans of a range are there; so are its bytes
     for (auto& e : ev_out) HIPCHK(e.create());
+    for (auto& e : ev_bytes) HIPCHK(e.create());
     bs = HostResult<uint32_t>(pinned_get(n * 4));
     cs = HostResult<uint32_t>(pinned_get(n * 4));
     Pinned<unsigned long long> cum;  // bytes of the batch up to the end of every range
@@ -2521,24 +2537,11 @@ static int decode_spans_ranges(tk_core* c, hipStream_t s, const uint32_t* tokens
     if (!bs || !cs) return fail(TK_RUNTIME_ERROR, "out of page-locked host memory");
     unsigned long long* words = nullptr;
     TRY(spans_begin(c, s, n, d_tok_off, n_docs, v, &words));
-    // (nothing returns between the producer's start and producer.join(): the events are let go only after it has ended)
-    std::atomic<int> h2d_rc{TK_OK};
-    std::atomic<uint64_t> sent{0};
-    const int dev = c->device;
-    std::thread producer([&]() {
-        (void)hipSetDevice(dev);
-        for (uint64_t k = 0; k < n_ranges; ++k) {
-            const uint64_t a = k * RANGE, cnt = a + RANGE < n ? RANGE : n - a;
-            if (hipMemcpyAsync(d_tok + a, tokens + a, cnt * 4, hipMemcpyHostToDevice, c->cs_h2d) != hipSuccess) h2d_rc = TK_RUNTIME_ERROR;
-            (void)hipEventRecord(ev_in[k], c->cs_h2d);
-            sent.store(k + 1, std::memory_order_release);
-        }
-    });
+    Feed feed(c, d_tok, tokens, n * 4, RANGE * 4);
+    TRY(feed.start());
     auto step = [&](uint64_t k) -> int {
         const uint64_t a = k * RANGE, cnt = a + RANGE < n ? RANGE : n - a;
-        while (sent.load(std::memory_order_acquire) <= k) std::this_thread::yield();
-        if (h2d_rc.load() != TK_OK) return fail(TK_RUNTIME_ERROR, "host-to-device copy failed");
-        HIPCHK(hipStreamWaitEvent(s, ev_in[k], 0));
+        TRY(feed.wait(k, s));
         TRY(spans_range(c, s, d_tok, n, a, cnt, d_tok_off, n_docs, v, words));
         HIPCHK(hipMemcpyAsync(cum + k + 1, words + TK_SPAN_BYTES, 8, hipMemcpyDeviceToHost, s));
         HIPCHK(hipEventRecord(ev_out[k], s));
@@ -2549,8 +2552,7 @@ static int decode_spans_ranges(tk_core* c, hipStream_t s, const uint32_t* tokens
     };
     int rc = TK_OK;
     for (uint64_t k = 0; k < n_ranges && rc == TK_OK; ++k) rc = step(k);
-    producer.join();
-    hipError_t e = hipStreamSynchronize(c->cs_h2d);
+    hipError_t e = feed.finish();
     if (rc == TK_OK) rc = spans_end(c, s, d_tok, d_tok_off, n_docs, nullptr, v, words);
     if (rc == TK_OK && (want_bytes || validate)) rc = [&]() -> int {
         cum[0] = 0;
@@ -2563,8 +2565,8 @@ static int decode_spans_ranges(tk_core* c, hipStream_t s, const uint32_t* tokens
             const uint64_t a = k * RANGE, cnt = a + RANGE < n ? RANGE : n - a;
             TRY(decode_range_copy(c, s, d_tok, a, cnt, c->d_bytes.as<uint8_t>(), nullptr, 0));  // (the bases are the batch's: every range writes at its place)
             if (!want_bytes) continue;
-            HIPCHK(hipEventRecord(ev_in[k], s));
-            HIPCHK(hipStreamWaitEvent(c->cs_d2h, ev_in[k], 0));
+            HIPCHK(hipEventRecord(ev_bytes[k], s));
+            HIPCHK(hipStreamWaitEvent(c->cs_d2h, ev_bytes[k], 0));
             if (cum[k + 1] > cum[k]) HIPCHK(hipMemcpyAsync(host + cum[k], c->d_bytes.as<uint8_t>() + cum[k], cum[k + 1] - cum[k], hipMemcpyDeviceToHost, c->cs_d2h));
         }
         if (validate) TRY(spans_validate(c, s, n_docs, v, words));
@@ -2597,13 +2599,10 @@ extern "C" int tk_decode_batch_spans(tk_core* c, const uint32_t* tokens, const u
     HostResult<uint32_t> bs, cs;
     HostResult<uint8_t> host;
     if (n >= 2 * (TK_STAGE_BYTES / 4)) {
-        const int rc = decode_spans_ranges(c, s, tokens, n, n_docs, bytes_out != nullptr, validate != 0, &v, bs, cs, host);
-        const int rc2 = drain_events(c);
-        TRY(rc);
-        TRY(rc2);
+        TRY(drained(c, [&] { return decode_spans_ranges(c, s, tokens, n, n_docs, bytes_out != nullptr, validate != 0, &v, bs, cs, host); }));
     } else {
         if (n) HIPCHK(hipMemcpyAsync(c->d_tok.p, tokens, n * 4, hipMemcpyHostToDevice, s));
-        TRY(spans_locked(c, s, c->d_tok.as<uint32_t>(), n, c->d_boff.as<uint64_t>(), n_docs, nullptr, bytes_out != nullptr, validate != 0, &v));
+        TRY(drained(c, [&] { return spans_run(c, s, c->d_tok.as<uint32_t>(), n, c->d_boff.as<uint64_t>(), n_docs, nullptr, bytes_out != nullptr, validate != 0, &v); }));
         TRY(spans_to_host(v, n, bs, cs));
         if (bytes_out) {
             host = HostResult<uint8_t>(result_alloc(v.n_bytes));
@@ -2631,9 +2630,9 @@ extern "C" int tk_encode_batch_spans(tk_core* c, const uint8_t* utf8, const uint
     const CheckArgs chk{disallowed_ids, n_disallowed, hit};
     std::lock_guard<std::mutex> lk(c->mu);
     uint64_t n = 0;
-    TRY(encode_batch_impl(c, utf8, doc_off, n_docs, use_special, allowed_ids, n_allowed, nullptr, &n, nullptr, true, true, n_disallowed ? &chk : nullptr, true));
+    TRY(encode_batch_kept(c, utf8, doc_off, n_docs, use_special, allowed_ids, n_allowed, chk, &n));
     SpanView v;
-    TRY(spans_locked(c, c->stream, c->out_tokens.as<uint32_t>(), n, c->out_tok_off.as<uint64_t>(), n_docs, c->doc_off.as<uint64_t>(), false, false, &v));
+    TRY(drained(c, [&] { return spans_run(c, c->stream, c->out_tokens.as<uint32_t>(), n, c->out_tok_off.as<uint64_t>(), n_docs, c->doc_off.as<uint64_t>(), false, false, &v); }));
     HostResult<uint32_t> bs, cs, tok(result_alloc(n * 4));
     if (!tok) return fail(TK_RUNTIME_ERROR, "out of host memory");
     TRY(spans_to_host(v, n, bs, cs));
@@ -2729,11 +2728,6 @@ static int rows_run(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n
     out->n_segs = got[TK_ROWS_NSEGS];
     return TK_OK;
 }
-static int rows_locked(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n, const uint64_t* d_tok_off, uint64_t n_docs, const tk_rows_spec* spec, RowsView* out) {
-    const int rc = rows_run(c, s, d_tok, n, d_tok_off, n_docs, spec, out);
-    const int rc2 = drain_events(c);  // (the timed pairs go whatever happened)
-    return rc != TK_OK ? rc : rc2;
-}
 
 extern "C" int tk_pack_rows_device(tk_core* c, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_docs, const tk_rows_spec* spec, void* stream,
                                    const void** d_ids_out, const uint32_t** d_doc_out, const uint32_t** d_pos_out, const uint32_t** d_cu_seqlens_out,
@@ -2743,7 +2737,7 @@ extern "C" int tk_pack_rows_device(tk_core* c, const void* d_tokens, uint64_t n_
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(hipSetDevice(c->device));
     RowsView v;
-    TRY(rows_locked(c, stream ? (hipStream_t)stream : c->stream, (const uint32_t*)d_tokens, n_tokens, (const uint64_t*)d_tok_off, n_docs, spec, &v));
+    TRY(drained(c, [&] { return rows_run(c, stream ? (hipStream_t)stream : c->stream, (const uint32_t*)d_tokens, n_tokens, (const uint64_t*)d_tok_off, n_docs, spec, &v); }));
     if (d_ids_out) *d_ids_out = v.ids;
     if (d_doc_out) *d_doc_out = v.doc;
     if (d_pos_out) *d_pos_out = v.pos;
@@ -2769,9 +2763,9 @@ extern "C" int tk_encode_batch_rows(tk_core* c, const uint8_t* utf8, const uint6
     const CheckArgs chk{disallowed_ids, n_disallowed, hit};
     std::lock_guard<std::mutex> lk(c->mu);
     uint64_t n = 0;
-    TRY(encode_batch_impl(c, utf8, doc_off, n_docs, use_special, allowed_ids, n_allowed, nullptr, &n, nullptr, true, true, n_disallowed ? &chk : nullptr, true));
+    TRY(encode_batch_kept(c, utf8, doc_off, n_docs, use_special, allowed_ids, n_allowed, chk, &n));
     RowsView v;
-    TRY(rows_locked(c, c->stream, c->out_tokens.as<uint32_t>(), n, c->out_tok_off.as<uint64_t>(), n_docs, spec, &v));
+    TRY(drained(c, [&] { return rows_run(c, c->stream, c->out_tokens.as<uint32_t>(), n, c->out_tok_off.as<uint64_t>(), n_docs, spec, &v); }));
     const uint64_t ids_bytes = v.n_pos * (v.ids16 ? 2 : 4);
     HostResult<uint8_t> ids(result_alloc(ids_bytes));
     HostResult<uint32_t> doc(result_alloc(v.n_pos * 4)), pos(result_alloc(v.n_pos * 4)), cu(result_alloc((v.n_segs + 1) * 4)), rs(result_alloc((v.n_rows + 1) * 4));

@@ -5,7 +5,7 @@
 //   tk_k_dec_scan64  exclusive prefix sum of those counts (64-bit: outputs may exceed 4 GiB)
 //   tk_k_dec_copy    workgroup base + local scan = byte offset of every token; one lane per token copies its bytes to their place
 //   tk_k_dec_docoff  byte offset of every document of a packed batch
-// Included by tk_api.hip only.
+// Included by tk_api.hip only (itself, and through tk_offsets.h and tk_rows.h).
 #pragma once
 #include "tk_kernels.h"
 #include "tk_device.h"
@@ -32,42 +32,15 @@ __global__ __launch_bounds__(256) void tk_k_dec_len(const uint32_t* __restrict__
         }
         sum += len;
     }
-    sum = tk_wave_sum_u32(sum);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) bsum[blockIdx.x] = (unsigned long long)sh[0] + sh[1] + sh[2] + sh[3];
+    const unsigned long long tot = tk_block_sum_256(sum, sh);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
 }
 
 // single-workgroup exclusive scan of the per-workgroup sums (64-bit); total -> total_out[0]
 __global__ __launch_bounds__(1024) void tk_k_dec_scan64(unsigned long long* __restrict__ a, uint64_t nb, unsigned long long* __restrict__ total_out) {
     __shared__ unsigned long long wsum[16];
-    __shared__ unsigned long long carry_sh;
-    if (threadIdx.x == 0) carry_sh = 0;
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    for (uint64_t base = 0; base < nb; base += 1024) {
-        const uint64_t i = base + threadIdx.x;
-        const unsigned long long v = i < nb ? a[i] : 0ull;
-        unsigned long long inc = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned long long w = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += w;
-        }
-        if (lane == 63) wsum[wid] = inc;
-        __syncthreads();
-        unsigned long long wbase = 0, tot = 0;
-        for (int w = 0; w < 16; ++w) {
-            if (w < wid) wbase += wsum[w];
-            tot += wsum[w];
-        }
-        const unsigned long long carry = carry_sh;
-        if (i < nb) a[i] = carry + wbase + inc - v;
-        __syncthreads();
-        if (threadIdx.x == 0) carry_sh = carry + tot;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) total_out[0] = carry_sh;
+    const unsigned long long total = tk_scan_blocks<false>(a, nb, 0ull, wsum);
+    if (threadIdx.x == 0) total_out[0] = total;
 }
 
 // byte offset of every token: workgroup base + local exclusive scan; then the copy.  A lane owns eight consecutive tokens, so its bytes

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include "tk_device.h"
+#include "tk_scan.h"
 #include "tk_special.h"
 
 #define TK_TILE 3840  // text bytes per tile: with 128 bytes of left context and 128 of look-ahead the LDS window is 4096 = 256 lanes x 16
@@ -49,29 +50,8 @@ enum {
 #define TK_MAX_LEVELS 6          // 64-ary min-tree levels of the long-piece merge
 
 // ------------------------------------------------------------------------------------------
-// wave helpers (wave64)
+// wave helpers (wave64; the scans and reductions: tk_scan.h)
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t tk_wave_min_u32(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        uint32_t w = __shfl_xor(v, o, 64);
-        v = w < v ? w : v;
-    }
-    return v;
-}
-__device__ __forceinline__ uint64_t tk_wave_min_u64(uint64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        uint64_t w = __shfl_xor(v, o, 64);
-        v = w < v ? w : v;
-    }
-    return v;
-}
-__device__ __forceinline__ uint32_t tk_wave_sum_u32(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __device__ __forceinline__ uint32_t tk_row16_sum(uint32_t v) {  // sum over the aligned 16 lanes of a DPP row, in every lane of it
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);   // quad_perm [1,0,3,2]: lane ^ 1
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true);   // quad_perm [2,3,0,1]: lane ^ 2
@@ -79,53 +59,6 @@ __device__ __forceinline__ uint32_t tk_row16_sum(uint32_t v) {  // sum over the 
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, true);  // row_mirror: the other half of 16
     return v;
 }
-// inclusive prefix sum across the wave
-// inclusive prefix sum over the wavefront: four DPP row shifts inside the rows of sixteen lanes, then the last lane of a row to the rows
-// behind it (row_bcast:15 to rows 1 and 3, row_bcast:31 to rows 2 and 3) -- six full-rate instructions (round 4: six __shfl_up, each a
-// ds_bpermute through the LDS crossbar plus a compare and a select)
-// (row_bcast:15 / row_bcast:31 are DPP controls of the GFX9 / CDNA encodings only -- the library is built for gfx950; a wave64 target without
-// them takes the shuffle form by itself instead of failing in the assembler)
-#if !defined(TK_SCAN_SHFL) && defined(__HIP_DEVICE_COMPILE__) && !defined(__GFX9__)
-#define TK_SCAN_SHFL 1
-#endif
-#ifndef TK_SCAN_SHFL
-__device__ __forceinline__ uint32_t tk_wave_scan_u32(uint32_t v, int /*lane*/) {
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true);   // row_shr:1 (a lane without a source adds nothing)
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true);   // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true);   // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true);   // row_shr:8
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);  // row_bcast:15 -> rows 1, 3
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);  // row_bcast:31 -> rows 2, 3
-    return v;
-}
-#else
-__device__ __forceinline__ uint32_t tk_wave_scan_u32(uint32_t v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        uint32_t w = __shfl_up(v, o, 64);
-        if (lane >= o) v += w;
-    }
-    return v;
-}
-#endif
-// block-wide (256 threads) exclusive scan; returns the exclusive prefix, *total gets the block sum
-__device__ __forceinline__ uint32_t tk_block_exscan_256(uint32_t v, uint32_t* total, uint32_t* sh /*[8]*/) {
-    int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    uint32_t inc = tk_wave_scan_u32(v, lane);
-    if (lane == 63) sh[wid] = inc;
-    __syncthreads();
-    uint32_t base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        uint32_t s = sh[w];
-        if (w < wid) base += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
-
 // wave-aggregated append: every lane with `want` gets a distinct slot index from the LDS counter
 __device__ __forceinline__ uint32_t tk_wave_append(bool want, uint32_t* counter, int lane) {
     uint64_t m = __ballot(want);

@@ -31,31 +31,6 @@ __global__ __launch_bounds__(256) void tk_k_span_mark(const uint64_t* __restrict
     }
 }
 
-__device__ __forceinline__ unsigned long long tk_max64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
-// exclusive max-scan over the 256 threads of a workgroup (0 = nothing before); *total = the workgroup's maximum
-__device__ __forceinline__ unsigned long long tk_block_exmax64_256(unsigned long long v, unsigned long long* total, unsigned long long* sh /*[4]*/) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    unsigned long long inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned long long w = __shfl_up(inc, o, 64);
-        if (lane >= o) inc = tk_max64(inc, w);
-    }
-    const unsigned long long before = __shfl_up(inc, 1, 64);
-    if (lane == 63) sh[wid] = inc;
-    __syncthreads();
-    unsigned long long base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        const unsigned long long s = sh[w];
-        if (w < wid) base = tk_max64(base, s);
-        tot = tk_max64(tot, s);
-    }
-    __syncthreads();
-    *total = tot;
-    return lane ? tk_max64(base, before) : base;
-}
-
 // first index d of off[0 .. count) with off[d] >= v (count if none)
 __device__ __forceinline__ uint64_t tk_lower_bound64(const uint64_t* __restrict__ off, uint64_t count, uint64_t v) {
     uint64_t lo = 0, hi = count;
@@ -113,31 +88,6 @@ __global__ __launch_bounds__(256) void tk_k_span_len(const uint32_t* __restrict_
         csum[blockIdx.x] = tot_c;
         mkey[blockIdx.x] = last;
     }
-}
-
-// exclusive scan over the 1024 threads of the one workgroup: sums, or maxima with 0 = nothing
-template <bool MAX>
-__device__ __forceinline__ unsigned long long tk_scan1024(unsigned long long v, unsigned long long* total, unsigned long long* wsum /*[16]*/) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    unsigned long long inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned long long w = __shfl_up(inc, o, 64);
-        if (lane >= o) inc = MAX ? tk_max64(inc, w) : inc + w;
-    }
-    const unsigned long long before = __shfl_up(inc, 1, 64);
-    if (lane == 63) wsum[wid] = inc;
-    __syncthreads();
-    unsigned long long base = 0, tot = 0;
-    for (int w = 0; w < 16; ++w) {
-        const unsigned long long s = wsum[w];
-        if (w < wid) base = MAX ? tk_max64(base, s) : base + s;
-        tot = MAX ? tk_max64(tot, s) : tot + s;
-    }
-    __syncthreads();
-    *total = tot;
-    if (!lane) return base;
-    return MAX ? tk_max64(base, before) : base + before;
 }
 
 // In place: bsum / csum -> the bytes / chars of the batch before every workgroup of the range.  doc_b / doc_c [w]: byte / char offset in the batch of the last document

@@ -6,7 +6,7 @@
 //   tk_k_rows_mark    one thread per tok_off entry: the entry is checked (ascending from 0 to n_tokens; the first offending document goes
 //                     into a report word) and the start of every document that owns a position -> a bitmap over the stream positions
 //   tk_k_rows_count   per workgroup: segment starts = marked bits | row starts, a coincidence counted once
-//   tk_k_rows_scan    one workgroup: exclusive sums of those counts (tk_scan1024), the number of segments, the closing cu_seqlens entry
+//   tk_k_rows_scan    one workgroup: exclusive sums of those counts (tk_scan_blocks), the number of segments, the closing cu_seqlens entry
 //   tk_k_rows_write   ids (uint32 or uint16), doc, pos, the cu_seqlens entries at their scanned indices, row_seg at row starts
 // How a lane learns its document: it SEARCHES tok_off once, for its first position, and walks along the documents from there (a position
 // at or beyond the current document's end moves on to the next one; behind a run of empty documents with k == 0 the walk searches once
@@ -19,8 +19,9 @@
 // when the report word names a document, so no kernel reads or writes out of bounds whatever tok_off holds.
 // Included by tk_api.hip only.
 #pragma once
-#include "tk_offsets.h"
+#include "tk_decode.h"
 #include "tk_rows_rule.h"
+#include "tk_scan.h"
 
 // the words the passes report in (unsigned long long each): the lowest tk_rows_bad_key (starts as all ones = none), the segments
 enum { TK_ROWS_BAD_OFF = 0, TK_ROWS_NSEGS, TK_ROWS_WORDS };
@@ -41,10 +42,8 @@ __global__ __launch_bounds__(256) void tk_k_rows_count(const uint8_t* __restrict
     const uint64_t i0 = (uint64_t)blockIdx.x * TK_DEC_BLOCK + (uint64_t)threadIdx.x * 8;
     uint32_t bits = 0;
     if (i0 < r.M) bits = tk_rows_seg_bits(marks[i0 >> 3], tk_rows_row_bits((uint32_t)i0 % r.seq_len, r.seq_len), tk_rows_valid_bits(i0, r.M));
-    const uint32_t sum = tk_wave_sum_u32((uint32_t)__popc(bits));
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) cnt[blockIdx.x] = (unsigned long long)sh[0] + sh[1] + sh[2] + sh[3];
+    const unsigned long long tot = tk_block_sum_256((uint32_t)__popc(bits), sh);
+    if (threadIdx.x == 0) cnt[blockIdx.x] = tot;
 }
 
 // In place: cnt -> the segment starts before every workgroup.  cu_seqlens closes with M; row_seg[R] is written here when no position R * L
@@ -52,14 +51,7 @@ __global__ __launch_bounds__(256) void tk_k_rows_count(const uint8_t* __restrict
 __global__ __launch_bounds__(1024) void tk_k_rows_scan(unsigned long long* __restrict__ cnt, uint64_t nb, TkRows r, uint32_t* __restrict__ cu,
                                                        uint32_t* __restrict__ row_seg, unsigned long long* __restrict__ words) {
     __shared__ unsigned long long wsum[16];
-    unsigned long long carry = 0;
-    for (uint64_t base = 0; base < nb; base += 1024) {
-        const uint64_t i = base + threadIdx.x;
-        unsigned long long tot;
-        const unsigned long long at = carry + tk_scan1024<false>(i < nb ? cnt[i] : 0ull, &tot, wsum);
-        if (i < nb) cnt[i] = at;
-        carry += tot;
-    }
+    const unsigned long long carry = tk_scan_blocks<false>(cnt, nb, 0ull, wsum);
     if (threadIdx.x == 0) {
         words[TK_ROWS_NSEGS] = carry;
         cu[carry] = (uint32_t)r.M;

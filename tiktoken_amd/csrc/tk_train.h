@@ -22,7 +22,7 @@
 // All atomics are integer adds, minima, maxima and claims of empty slots: the merges do not depend on the order in which they land (the
 // layout of the blob and of the table does, and nothing reads it that way).  The rule is tk_train_rule.h's.  Included by tk_api.hip only.
 #pragma once
-#include "tk_offsets.h"
+#include "tk_scan.h"
 #include "tk_train_rule.h"
 
 #define TKT_BLOCK 256u  // symbols per workgroup of the step's kernels, one per lane
@@ -150,15 +150,6 @@ struct TkTrainStep {
     uint32_t step, par;
 };
 
-__device__ __forceinline__ unsigned long long tk_wave_max_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long w = __shfl_xor(v, o, 64);
-        v = w > v ? w : v;
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(TKT_BLOCK) void tk_k_train_count(TkTrainStep st) {
     const unsigned long long n = st.cells[TKT_LIVE + st.par];
     const uint64_t i = (uint64_t)blockIdx.x * TKT_BLOCK + threadIdx.x;
@@ -223,11 +214,7 @@ __global__ __launch_bounds__(TKT_BLOCK) void tk_k_train_breaks(TkTrainStep st) {
         const bool has_prev = i > 0 && wid[i - 1] == wid[i];
         mark = tk_train_break_mark((uint32_t)i, tk_train_continues(has_prev, has_prev ? sym[i - 1] : 0u, sym[i], a));
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t w = __shfl_xor(mark, o, 64);
-        mark = w > mark ? w : mark;
-    }
+    mark = tk_wave_max_u32(mark);
     if ((threadIdx.x & 63u) == 0u) sh[threadIdx.x >> 6] = mark;
     __syncthreads();
     if (threadIdx.x == 0) st.blk_mark[blockIdx.x] = max(max(sh[0], sh[1]), max(sh[2], sh[3]));
@@ -239,14 +226,7 @@ __global__ __launch_bounds__(1024) void tk_k_train_carry(TkTrainStep st) {
     const unsigned long long n = st.cells[TKT_LIVE + st.par], win = st.cells[TKT_WIN];
     if (st.cells[TKT_DONE] || (uint32_t)(win >> 32) != (uint32_t)win) return;
     const uint64_t nb = (n + TKT_BLOCK - 1) / TKT_BLOCK;
-    unsigned long long carry = 0;
-    for (uint64_t base = 0; base < nb; base += 1024) {
-        const uint64_t i = base + threadIdx.x;
-        unsigned long long tot;
-        const unsigned long long before = tk_max64(carry, tk_scan1024<true>(i < nb ? (unsigned long long)st.blk_mark[i] : 0ull, &tot, wsum));
-        if (i < nb) st.blk_mark[i] = (uint32_t)before;
-        carry = tk_max64(carry, tot);
-    }
+    (void)tk_scan_blocks<true>(st.blk_mark, nb, 0ull, wsum);
 }
 
 __global__ __launch_bounds__(TKT_BLOCK) void tk_k_train_decide(TkTrainStep st) {
@@ -256,7 +236,6 @@ __global__ __launch_bounds__(TKT_BLOCK) void tk_k_train_decide(TkTrainStep st) {
     const uint64_t i = (uint64_t)blockIdx.x * TKT_BLOCK + threadIdx.x;
     if ((uint64_t)blockIdx.x * TKT_BLOCK >= n || st.cells[TKT_DONE]) return;
     const uint32_t *sym = st.sym[st.par], *wid = st.wid[st.par];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     bool has_prev = false, has_next = false;
     uint32_t s = 0, s_prev = 0, s_next = 0;
     if (i < n) {
@@ -270,17 +249,9 @@ __global__ __launch_bounds__(TKT_BLOCK) void tk_k_train_decide(TkTrainStep st) {
     uint32_t d = 0;
     if (a == b) {  // (the same in every lane) the run's start: the largest mark at or before this lane, in the workgroup or before it
         uint32_t mark = i < n ? tk_train_break_mark((uint32_t)i, tk_train_continues(has_prev, s_prev, s, a)) : 0u;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t w = __shfl_up(mark, o, 64);
-            if (lane >= o) mark = w > mark ? w : mark;
-        }
-        if (lane == 63) sh[wv] = mark;
-        __syncthreads();
-        uint32_t before = st.blk_mark[blockIdx.x];
-        for (int w = 0; w < wv; ++w) before = sh[w] > before ? sh[w] : before;
-        mark = before > mark ? before : mark;
-        __syncthreads();
+        uint32_t tot;
+        const uint32_t before = max(st.blk_mark[blockIdx.x], tk_block_exmax32_256(mark, &tot, sh));
+        mark = max(before, mark);
         d = mark ? (uint32_t)i - (mark - 1u) : 0u;  // (symbol 0 never continues: there is a mark)
     }
     int dec = TK_TRAIN_KEEP;
@@ -288,10 +259,8 @@ __global__ __launch_bounds__(TKT_BLOCK) void tk_k_train_decide(TkTrainStep st) {
         dec = tk_train_decide(a, b, has_prev, s_prev, s, has_next, s_next, d);
         st.dec[i] = (uint8_t)dec;
     }
-    const uint32_t kept = tk_wave_sum_u32(i < n && dec != TK_TRAIN_RIGHT ? 1u : 0u);
-    if (lane == 0) sh[wv] = kept;
-    __syncthreads();
-    if (threadIdx.x == 0) st.blk_cnt[blockIdx.x] = (unsigned long long)sh[0] + sh[1] + sh[2] + sh[3];
+    const unsigned long long kept = tk_block_sum_256(i < n && dec != TK_TRAIN_RIGHT ? 1u : 0u, sh);
+    if (threadIdx.x == 0) st.blk_cnt[blockIdx.x] = kept;
 }
 
 // In place: survivors per workgroup -> survivors before it; the next step's live count; cmax and best are reset for it.
@@ -300,14 +269,7 @@ __global__ __launch_bounds__(1024) void tk_k_train_offsets(TkTrainStep st) {
     const unsigned long long n = st.cells[TKT_LIVE + st.par];
     if (st.cells[TKT_DONE]) return;
     const uint64_t nb = (n + TKT_BLOCK - 1) / TKT_BLOCK;
-    unsigned long long carry = 0;
-    for (uint64_t base = 0; base < nb; base += 1024) {
-        const uint64_t i = base + threadIdx.x;
-        unsigned long long tot;
-        const unsigned long long at = carry + tk_scan1024<false>(i < nb ? st.blk_cnt[i] : 0ull, &tot, wsum);
-        if (i < nb) st.blk_cnt[i] = at;
-        carry += tot;
-    }
+    const unsigned long long carry = tk_scan_blocks<false>(st.blk_cnt, nb, 0ull, wsum);
     if (threadIdx.x == 0) {
         st.cells[TKT_LIVE + (st.par ^ 1u)] = carry;
         st.cells[TKT_CMAX] = 0ull;
