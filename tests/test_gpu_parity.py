@@ -302,9 +302,56 @@ def test_multi_chunk_batches(monkeypatch):
     toks, toff = core.encode_batch_packed(blob, off)
     rt, ro = C.encode_batch(blob, off, None, 8)
     assert np.array_equal(toff, ro) and np.array_equal(toks, rt)
+    assert core.stat("chunks") >= 3 * 16  # (far more chunks than work sets: every set is handed on to a later chunk many times)
     toks, toff = core.encode_batch_packed(blob, off, {"<|endoftext|>"})
     rt, ro = C.encode_batch(blob, off, {"<|endoftext|>"}, 8)
     assert np.array_equal(toff, ro) and np.array_equal(toks, rt)
+
+
+def test_empty_batches_through_the_chunk_pipeline(cores):
+    """A batch without documents and a batch of one empty document are one empty chunk each (tk_api.hip, stage_front / stage_back with n = 0:
+    nothing but the clears, tk_k_advance and tk_k_docoff run), from host buffers and device-resident, with and without special tokens; the
+    piece-starts entry on the same two batches gives the end sentinel alone.  Tokens and offsets are the oracle's."""
+    import torch
+
+    core, C = cores["o200k_shaped"], h.c_oracle_for("o200k_shaped")
+    d_text = torch.zeros(256, dtype=torch.uint8).cuda()
+    for n_docs in (0, 1):
+        blob, off = np.zeros(0, np.uint8), np.zeros(n_docs + 1, np.uint64)
+        d_off = torch.from_numpy(off.view(np.int64)).cuda()
+        for allowed in (None, {"<|endoftext|>"}):
+            rt, ro = C.encode_batch(blob, off, allowed, 1)
+            assert len(rt) == 0 and ro.tolist() == [0] * (n_docs + 1)
+            toks, toff = core.encode_batch_packed(blob, off, allowed)
+            assert np.array_equal(toks, rt) and np.array_equal(toff, ro), (n_docs, allowed)
+            assert core.stat("chunks") == 1
+            dt, nt, do = core.encode_batch_device(d_text.data_ptr(), 0, d_off.data_ptr(), off, n_docs, allowed)
+            assert nt == 0 and np.array_equal(h.dev_u64(do, n_docs + 1), ro), (n_docs, allowed)
+            assert core.stat("chunks") == 1
+            assert core.pretokenize_packed(blob, off, allowed).tolist() == [0]
+
+
+def test_one_hundred_bytes_through_the_device_entry(cores):
+    """tk_encode_batch_device has no small-call path: one document of 100 bytes is a chunk of one tile through both stages of the general
+    pipeline, for every pattern family.  Tokens and offsets are the oracle's."""
+    import torch
+
+    text = "The quick brown fox's 12345 jumps\n\n  over\tthe lazy dog. \u4e2d\u6587 \U0001f600 DON'T STOP <|endoftext|> believing ..."
+    data = text.encode()[:100]
+    assert len(data) == 100 and data.decode()  # (the cut falls between two chars)
+    host = np.zeros(100 + 64, np.uint8)
+    host[:100] = np.frombuffer(data, np.uint8)
+    d_text = torch.from_numpy(host).cuda()
+    off = np.array([0, 100], np.uint64)
+    d_off = torch.from_numpy(off.view(np.int64)).cuda()
+    for name in h.ENCODING_NAMES:
+        core, C = cores[name], h.c_oracle_for(name)
+        for allowed in (None, {"<|endoftext|>"}):
+            rt, ro = C.encode_batch(host[:100], off, allowed, 1)
+            small = core.stat("small_calls")
+            dt, nt, do = core.encode_batch_device(d_text.data_ptr(), 100, d_off.data_ptr(), off, 1, allowed)
+            assert np.array_equal(h.dev_u32(dt, nt), rt) and np.array_equal(h.dev_u64(do, 2), ro), (name, allowed)
+            assert core.stat("chunks") == 1 and core.stat("small_calls") == small
 
 
 def test_size_independent_properties_at_scale(cores):

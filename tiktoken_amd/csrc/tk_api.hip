@@ -11,6 +11,7 @@
 #include <chrono>
 #include <functional>
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <map>
 #include <memory>
@@ -152,13 +153,47 @@ struct WorkSet {
         return t;
     }
 };
+#define TK_GROW (-1000)  // (internal) the batch has to be repeated with a larger miss data: encode_device_locked
+#define TK_RESYNC (-1001)  // (internal) a deferred tile gave up while the host was not waiting: the batch is repeated, encode_device_locked
+#define TK_SPEC_HIT (-1002)  // (internal) a chunk holds a disallowed special token (c->find_hit): the entry point reports it, no tokens are handed out
+#ifndef TK_MT_DIV
+#define TK_MT_DIV 128  // bytes of a chunk per slot of the in-call miss table (stage_front)
+#endif
+
+// What a caller asks of the chunk pipeline (stage_front .. chunk_finish, run_chunk): one chunk (n < 4 GiB bytes) of packed documents on the device.
+enum class ChunkKind {
+    Batch,                // documents, pre-tokenised and encoded
+    SinglePiece,          // the whole buffer is one piece (encode_single_piece), no pre-tokenisation
+    SinglePieceNoLookup,  // ... and is not looked up as a whole first (_byte_pair_encode)
+    PieceStarts,          // debugging / test entry and training: piece offsets only (w.pstart), no tokens
+};
+struct ChunkAsk {  // (call sites name the fields they set, in this order)
+    ChunkKind kind = ChunkKind::Batch;
+    const uint8_t* d_text = nullptr;      // chunk text, readable 64 bytes past n
+    const uint64_t* d_doc_off = nullptr;  // uint64 offsets of the chunk's documents (n_docs + 1 entries, absolute: `base` is subtracted)
+    uint64_t n = 0, n_docs = 0, base = 0;
+    uint32_t* d_out = nullptr;            // the batch's token buffer (null: piece starts only)
+    uint64_t* d_tok_off = nullptr;        // the documents' token offsets (null: not wanted)
+    bool use_special = false;
+    bool single_piece() const { return kind == ChunkKind::SinglePiece || kind == ChunkKind::SinglePieceNoLookup; }
+    bool piece_starts() const { return kind == ChunkKind::PieceStarts; }
+};
+// What every launch of the front kernel in a chunk is given behind the tables, the text and the base (tk_k_front's parameters, in their order; the
+// list of deferred tiles and the internal debug bits are the launch's own: launch_front).  Filled once, by stage_front.
+struct FrontArgs {
+    int pat_id = 0;
+    uint32_t *brk = nullptr, *docb = nullptr, *ss = nullptr, *si = nullptr;  // (docb, ss, si: null without special tokens in the chunk)
+    TkFrontOut out{};
+    TkMissKey* mt = nullptr;
+    uint32_t mt_mask = 0;
+    const uint32_t* gapb = nullptr;  // gap chars of the generic engine's split, or null
+    int dbg = 0;                     // the core's debug word without the internal bits (the piece-offsets entry: piece starts only)
+};
 // What the front stage of a chunk leaves for its back stage.
 struct ChunkJob {
-    const uint8_t* d_text = nullptr;
-    uint64_t n = 0, n_docs = 0, base = 0, ntiles = 0;
-    const uint64_t* d_doc_off = nullptr;
-    uint64_t* d_tok_off = nullptr;
-    bool single_piece = false, spec = false, pretok = false;
+    ChunkAsk ask;
+    FrontArgs front;
+    uint64_t ntiles = 0;
     bool find = false;  // the chunk's text was searched for disallowed special tokens (tk_k_spec_find -> w.find)
     uint32_t index = 0;  // position of the chunk in its batch
     uint32_t mt_bits = 14;
@@ -627,21 +662,22 @@ static uint32_t grid_for(uint64_t items, uint32_t per_block, uint32_t cap) {
     return (uint32_t)g;
 }
 
-template <int MODE, class... A>
-static void launch_front(int pattern, bool spec, dim3 grid, hipStream_t s, A... a) {
-    if (pattern == TK_PAT_R50K) {
-        if (spec) hipLaunchKernelGGL((tk_k_front<TK_PAT_R50K, true, MODE>), grid, dim3(256), 0, s, a...);
-        else hipLaunchKernelGGL((tk_k_front<TK_PAT_R50K, false, MODE>), grid, dim3(256), 0, s, a...);
-    } else if (pattern == TK_PAT_CL100K) {
-        if (spec) hipLaunchKernelGGL((tk_k_front<TK_PAT_CL100K, true, MODE>), grid, dim3(256), 0, s, a...);
-        else hipLaunchKernelGGL((tk_k_front<TK_PAT_CL100K, false, MODE>), grid, dim3(256), 0, s, a...);
-    } else if (pattern == TK_PAT_O200K) {
-        if (spec) hipLaunchKernelGGL((tk_k_front<TK_PAT_O200K, true, MODE>), grid, dim3(256), 0, s, a...);
-        else hipLaunchKernelGGL((tk_k_front<TK_PAT_O200K, false, MODE>), grid, dim3(256), 0, s, a...);
-    } else {  // a pattern of the family that is not one of the stock three: family and parameters are run-time values
-        if (spec) hipLaunchKernelGGL((tk_k_front<TK_PAT_GENERIC, true, MODE>), grid, dim3(256), 0, s, a...);
-        else hipLaunchKernelGGL((tk_k_front<TK_PAT_GENERIC, false, MODE>), grid, dim3(256), 0, s, a...);
-    }
+// one launch of the front kernel for the chunk of `job`: the instance of its pattern, with the arguments stage_front has put together
+template <int MODE>
+static void launch_front(tk_core* c, const ChunkJob& job, dim3 grid, hipStream_t s, uint32_t* deferred, int internal_dbg) {
+    const ChunkAsk& a = job.ask;
+    const FrontArgs& f = job.front;
+    auto go = [&](auto* kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, c->D, a.d_text, a.n, a.base, f.brk, f.docb, f.ss, f.si, f.out, f.mt, f.mt_mask, deferred, f.gapb, f.dbg | internal_dbg);
+    };
+    auto of_pattern = [&](auto pat) {  // (with or without special tokens in the chunk)
+        if (f.ss) go(tk_k_front<decltype(pat)::value, true, MODE>);
+        else go(tk_k_front<decltype(pat)::value, false, MODE>);
+    };
+    if (f.pat_id == TK_PAT_R50K) of_pattern(std::integral_constant<int, TK_PAT_R50K>{});
+    else if (f.pat_id == TK_PAT_CL100K) of_pattern(std::integral_constant<int, TK_PAT_CL100K>{});
+    else if (f.pat_id == TK_PAT_O200K) of_pattern(std::integral_constant<int, TK_PAT_O200K>{});
+    else of_pattern(std::integral_constant<int, TK_PAT_GENERIC>{});  // a pattern of the family that is not one of the stock three: family and parameters are run-time values
 }
 
 // exclusive prefix sum of a uint32 array in place, total -> total_out[0]
@@ -669,17 +705,30 @@ static int rx_failure(const uint32_t* counters, uint64_t base) {
                                     " of the batch (nested quantifiers; the reference's fancy-regex gives up after 1 000 000 backtracks as well)");
 }
 
+// The generic engine's bitmaps over a chunk of n bytes: three pairs (w.rx_spec, w.rx_gst, w.rx_lnk), in each the starts and, behind them, the
+// gap chars among the starts.
+struct RxPairs {
+    const uint64_t nwords;  // of one bitmap, before its two words of slack
+    explicit RxPairs(uint64_t n) : nwords((n + 31) / 32) {}
+    uint64_t bytes() const { return 2 * (nwords + 2) * 4; }  // of one pair
+    uint32_t* gap(const Buf& pair) const { return pair.as<uint32_t>() + nwords + 2; }
+    static std::array<Buf*, 3> of(WorkSet& w) { return {&w.rx_spec, &w.rx_gst, &w.rx_lnk}; }
+};
+
 // The generic engine's split of a chunk (tk_regex_kernels.h): speculate, link, resolve, then brk |= the true piece starts.  The three
-// pairs of bitmaps (rx_spec, rx_lnk, rx_gst: starts and gap chars) are zero on entry.
-static int rx_split(tk_core* c, WorkSet& w, hipStream_t s, const uint8_t* d_text, uint64_t n, uint32_t* brk, const uint32_t* ss, const uint32_t* si,
-                    const uint64_t* d_doc_off, uint64_t n_docs, uint64_t base) {
-    const uint64_t nwords = (n + 31) / 32;
+// pairs of bitmaps (RxPairs) are zero on entry.
+static int rx_split(tk_core* c, WorkSet& w, const ChunkJob& job, hipStream_t s) {
+    const uint8_t* d_text = job.ask.d_text;
+    const uint64_t n = job.ask.n, nwords = (n + 31) / 32;
+    uint32_t *brk = job.front.brk, *ss = job.front.ss, *si = job.front.si;
+    const RxPairs rx(n);
     uint32_t* counters = w.counters.as<uint32_t>();
     const uint32_t seg_shift = n < TK_RX_SEG_SMALL_BELOW ? TK_RX_SEG_SHIFT_SMALL : TK_RX_SEG_SHIFT_LARGE;
     const uint64_t nseg = (n + (1ull << seg_shift) - 1) >> seg_shift;
     TRY(ensure(w.rx_exit, 3 * (nseg + 2) * 4));  // exit of every segment's chain; where the link met it; where the link left the segment
     uint32_t *spec = w.rx_spec.as<uint32_t>(), *gst = w.rx_gst.as<uint32_t>(), *xexit = w.rx_exit.as<uint32_t>();
     uint32_t *lnk = w.rx_lnk.as<uint32_t>(), *lmerge = xexit + nseg + 2, *lexit = xexit + 2 * (nseg + 2);
+    uint32_t *spec_gap = rx.gap(w.rx_spec), *gst_gap = rx.gap(w.rx_gst), *lnk_gap = rx.gap(w.rx_lnk);
     // (the kernels' form: the pattern's DFA in LDS -- its speculative pass as one loop -- or the backtracking program; tk_regex_kernels.h)
     const uint32_t lds = c->rx_form == TK_RX_FORM_PROGRAM ? 0u : tk_rx_dfa_lds_bytes(c->rx);
     const uint32_t ahead = c->rx_form == TK_RX_FORM_PROGRAM ? TK_RX_AHEAD : TK_RX_AHEAD_DFA;
@@ -696,24 +745,24 @@ static int rx_split(tk_core* c, WorkSet& w, hipStream_t s, const uint8_t* d_text
     TRY(timed(c, s, "tk_k_rx_speculate", [&] {
         if (staged)
             hipLaunchKernelGGL(tk_k_rx_speculate_staged, dim3(grid_for(nseg, TK_RX_STAGE_SEGS, c->rx_grid_cap)), dim3(TK_RX_STAGE_SEGS), tk_rx_staged_lds_bytes(c->rx), s, c->rx, d_text, (uint32_t)n, brk, ss,
-                               si, ahead, spec, spec + nwords + 2, xexit);
+                               si, ahead, spec, spec_gap, xexit);
         else
             by_form([&](auto form) {
                 hipLaunchKernelGGL(tk_k_rx_speculate<decltype(form)::value>, dim3(grid_for(nseg, 256, 65536)), dim3(256), lds, s, c->rx, d_text, (uint32_t)n, brk, ss, si, seg_shift,
-                                   ahead, spec, spec + nwords + 2, xexit);
+                                   ahead, spec, spec_gap, xexit);
             });
     }));
     TRY(timed(c, s, "tk_k_rx_link", [&] {
         by_form([&](auto form) {
             hipLaunchKernelGGL(tk_k_rx_link<decltype(form)::value>, dim3(grid_for(nseg, 256, 65536)), dim3(256), lds, s, c->rx, d_text, (uint32_t)n, brk, ss, si, seg_shift,
-                               ahead, spec, xexit, lnk, lnk + nwords + 2, lmerge, lexit);
+                               ahead, spec, xexit, lnk, lnk_gap, lmerge, lexit);
         });
     }));
-    const TkRxMaps maps{spec, spec + nwords + 2, xexit, lnk, lnk + nwords + 2, lmerge, lexit, seg_shift};
+    const TkRxMaps maps{spec, spec_gap, xexit, lnk, lnk_gap, lmerge, lexit, seg_shift};
     TRY(timed(c, s, "tk_k_rx_resolve", [&] {  // (the wavefront form, tk_k_rx_resolve_wave: kernel times keep this name)
         by_form([&](auto form) {
-            hipLaunchKernelGGL(tk_k_rx_resolve_wave<decltype(form)::value>, dim3(grid_for(n_docs, 4, 65536)), dim3(256), lds, s, c->rx, d_text, (uint32_t)n, brk, ss, si,
-                               d_doc_off, n_docs, base, maps, gst, gst + nwords + 2, counters);
+            hipLaunchKernelGGL(tk_k_rx_resolve_wave<decltype(form)::value>, dim3(grid_for(job.ask.n_docs, 4, 65536)), dim3(256), lds, s, c->rx, d_text, (uint32_t)n, brk, ss, si,
+                               job.ask.d_doc_off, job.ask.n_docs, job.ask.base, maps, gst, gst_gap, counters);
         });
     }));
     TRY(timed(c, s, "tk_k_rx_merge", [&] { hipLaunchKernelGGL(tk_k_rx_merge, dim3(grid_for(nwords, 256, 4096)), dim3(256), 0, s, brk, gst, nwords); }));
@@ -726,46 +775,36 @@ static int rx_split(tk_core* c, WorkSet& w, hipStream_t s, const uint8_t* d_text
 // on their own stream), the front kernel of chunk k + 1 (bound by the vector ALU) already runs on the caller's stream.  Each chunk in
 // flight has its own WorkSet.  The host never needs a chunk's token count to queue the next one: the running total stays on the device
 // (c->tok_bases[k]: written by chunk k - 1's back stage as soon as it knows its token count).
-//   d_text: chunk text (readable 64 bytes past n); d_doc_off: uint64 offsets of the chunk's documents (n_docs + 1 entries, absolute;
-//   `base` is subtracted); single_piece: the whole buffer is one piece (encode_single_piece), no pre-tokenisation.
+//   What the caller asks for -- text, documents, where the results go, which of the entries it is -- is a ChunkAsk.
 // ------------------------------------------------------------------------------------------
 // The tiles the front kernel has deferred (they need the workgroup-wide scanner: long pieces, far-away piece starts; their number stays
 // on the device), then the counters of both kernels -- pieces for the tree kernel, errors of the generic engine -- on their way to the host.
 // A kernel of a few hundred workgroups that each take ~0.3 ms: it belongs to the back stage, beside the next chunk's front kernel.
 static int stage_deferred(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s) {
-    const TkTables& T = c->D;
     // A stretch without certain starts ("x'llx'll...": whether 'll ends a piece depends on everything before it) makes every deferred tile
     // inside it walk from the stretch's start -- quadratic in its length, seconds for 10 MB.  A tile whose walk exceeds TKF_WALK_BUDGET
     // windows gives up instead (second list); if any did, the generic engine -- linear on exactly such text: the pieces are short, every
     // segment's guess is taken -- splits the chunk under the same pat_str, its piece starts become hard starts, and the tiles that gave up
     // run again: every piece start is certain now.  (Pieces that are already final are what they were: a hard start at the start of a
     // piece changes nothing, and the stock patterns match a piece the same way when the text ends behind it.)
-    const bool can_fall_back = c->has_rx_fb && job.n >= (256u << 10);
-    if (job.n > 0 && !job.single_piece) {
-        TkFrontOut fo{w.starts.as<uint32_t>(), w.tile_np.as<uint32_t>(), w.res.as<uint32_t>(), w.tile_sum.as<uint8_t>(), miss_of(w, job), job.ovf_cap,
-                      w.listC.as<uint32_t>(), w.counters.as<uint32_t>()};
-        uint32_t *ss = job.spec ? w.ss.as<uint32_t>() : nullptr, *si = job.spec ? w.si.as<uint32_t>() : nullptr, *docb = job.spec ? w.docb.as<uint32_t>() : nullptr;
+    const uint64_t n = job.ask.n;
+    const bool can_fall_back = c->has_rx_fb && n >= (256u << 10);
+    if (n > 0 && !job.ask.single_piece()) {
+        uint32_t* deferred = w.deferred.as<uint32_t>();
         // (the grid: what is resident -- or, where the host does not wait for the counters, as many workgroups as the chunks before had deferred tiles (at
         // least 64: they take their tiles from a counter).  On ordinary text no tile is deferred since round 6, and an empty grid of 768 such workgroups
         // -- 168 registers, 37 KiB of LDS, scratch -- costs 12.6 us against the 7 of 64.)
         const uint64_t defer_guess = ((job.ntiles * (uint64_t)c->defer_ppm) >> 20) * 5 / 4 + 64;
-        const bool sync_now = can_fall_back && (c->defer_sync || job.pretok);  // (the piece-offsets entry has no chunk_finish)
+        const bool sync_now = can_fall_back && (c->defer_sync || job.ask.piece_starts());  // (the piece-offsets entry has no chunk_finish)
         job.optimistic = can_fall_back && !sync_now;
         uint64_t slow_wgs = 256u * TKF_SLOW_OCC;
         if (job.optimistic && defer_guess < slow_wgs) slow_wgs = defer_guess;
         const dim3 grid((uint32_t)(job.ntiles < slow_wgs ? job.ntiles : slow_wgs));
-        const int pat_id = T.pat.generic() ? TK_PAT_GENERIC : T.pattern;
-        TkMissKey* mt_arg = (c->dbg & TK_DBG_NO_MT) ? (TkMissKey*)nullptr : job.mt;
-        const uint32_t* gapb = c->has_rx ? w.rx_gst.as<uint32_t>() + (job.n + 31) / 32 + 2 : (const uint32_t*)nullptr;
-        const int fdbg = (c->dbg & ~TK_DBG_INTERNAL) | (job.pretok ? TK_DBG_STARTS_ONLY : 0);  // (the piece-offsets entry: piece starts only)
         // The deferred tiles in two kernels: the deferred-tile instance finds a tile's piece starts (the workgroup-wide scanner: 128 registers,
         // four workgroups per CU), the one-tile-per-workgroup instance does the rest from the starts it is given (phases E and F, at eight
         // workgroups per CU).  Its grid is the list's length where the host reads the counters (inputs of 256 KiB and more); otherwise one
         // workgroup per tile of the chunk, of which all but the list's length return at once.
-        TRY(timed(c, s, "tk_k_front_slow", [&] {
-            launch_front<TKF_MODE_STARTS>(pat_id, job.spec, grid, s, T, job.d_text, job.n, job.base, w.brk.as<uint32_t>(), docb, ss, si, fo, mt_arg, (1u << job.mt_bits) - 1u,
-                               w.deferred.as<uint32_t>(), gapb, fdbg | (can_fall_back ? TK_DBG_MAY_GIVE_UP : 0));
-        }));
+        TRY(timed(c, s, "tk_k_front_slow", [&] { launch_front<TKF_MODE_STARTS>(c, job, grid, s, deferred, can_fall_back ? TK_DBG_MAY_GIVE_UP : 0); }));
         uint64_t n_given = job.ntiles;
         // (round 6) The host does not wait for the counters here any more: the wait cost every chunk ~25 us of an idle device between the two kernels
         // (3 % of a 64 MiB batch) and kept the host from queueing the next chunk -- for a decision that ordinary text never needs.  The kernel that
@@ -778,54 +817,38 @@ static int stage_deferred(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s) 
             HIPCHK(hipEventRecord(w.ev_cnt, s));
             HIPCHK(hipEventSynchronize(w.ev_cnt));
             if (can_fall_back && w.h_counters[TK_CNT_DEFER2]) {
-                const uint64_t nwords = (job.n + 31) / 32;
-                for (Buf* b : {&w.rx_spec, &w.rx_gst, &w.rx_lnk}) {
-                    TRY(ensure(*b, 2 * (nwords + 2) * 4));
-                    HIPCHK(hipMemsetAsync(b->p, 0, 2 * (nwords + 2) * 4, s));
+                const RxPairs rx(n);
+                for (Buf* b : rx.of(w)) {
+                    TRY(ensure(*b, rx.bytes()));
+                    HIPCHK(hipMemsetAsync(b->p, 0, rx.bytes(), s));
                 }
-                TRY(rx_split(c, w, s, job.d_text, job.n, w.brk.as<uint32_t>(), ss, si, job.d_doc_off, job.n_docs, job.base));
-                TRY(timed(c, s, "tk_k_front_slow", [&] {
-                    launch_front<TKF_MODE_STARTS>(pat_id, job.spec, grid, s, T, job.d_text, job.n, job.base, w.brk.as<uint32_t>(), docb, ss, si, fo, mt_arg, (1u << job.mt_bits) - 1u,
-                                       w.deferred.as<uint32_t>() + job.ntiles + 2, gapb, fdbg | TK_DBG_SECOND);
-                }));
+                TRY(rx_split(c, w, job, s));
+                TRY(timed(c, s, "tk_k_front_slow", [&] { launch_front<TKF_MODE_STARTS>(c, job, grid, s, deferred + job.ntiles + 2, TK_DBG_SECOND); }));
                 c->st_fallbacks += 1;
             }
             n_given = w.h_counters[TK_CNT_DEFER];
         }
-        if (n_given && TKF_STOP_AFTER == 0) {  // (TKF_STOP_AFTER: the kernels stop after a phase, there are no starts to go on from)
-            TRY(timed(c, s, "tk_k_front_given", [&] {
-                launch_front<TKF_MODE_GIVEN>(pat_id, job.spec, dim3((uint32_t)n_given), s, T, job.d_text, job.n, job.base, w.brk.as<uint32_t>(), docb, ss, si, fo, mt_arg,
-                                    (1u << job.mt_bits) - 1u, w.deferred.as<uint32_t>(), gapb, fdbg);
-            }));
-        }
+        if (n_given && TKF_STOP_AFTER == 0)  // (TKF_STOP_AFTER: the kernels stop after a phase, there are no starts to go on from)
+            TRY(timed(c, s, "tk_k_front_given", [&] { launch_front<TKF_MODE_GIVEN>(c, job, dim3((uint32_t)n_given), s, deferred, 0); }));
     }
     HIPCHK(hipMemcpyAsync(w.h_counters, w.counters.p, TK_CNT_N * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipEventRecord(w.ev_cnt, s));
     return TK_OK;
 }
-#define TK_RESYNC (-1001)  // (internal) a deferred tile gave up while the host was not waiting: the batch is repeated, encode_device_locked
 
-static int stage_front(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, const uint8_t* d_text, uint64_t n, const uint64_t* d_doc_off, uint64_t n_docs,
-                       uint64_t base, bool use_special, bool single_piece, uint64_t* d_tok_off, bool pretok_only, bool no_lookup,
-                       uint64_t* pretok_count_out) {
+static int stage_front(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, const ChunkAsk& ask) {
     const TkTables& T = c->D;
+    const uint8_t* d_text = ask.d_text;
+    const uint64_t n = ask.n, n_docs = ask.n_docs, base = ask.base;
+    const bool single_piece = ask.single_piece(), pretok_only = ask.piece_starts();
     const uint64_t nwords = (n + 31) / 32;
     const uint64_t nblk = (nwords + 255) / 256;
     const uint64_t ntiles = (n && !single_piece) ? (n + TK_TILE - 1) / TK_TILE : 1;  // (single piece: one run of one piece)
     job = ChunkJob();
-    job.d_text = d_text;
-    job.n = n;
-    job.n_docs = n_docs;
-    job.base = base;
+    job.ask = ask;
     job.ntiles = ntiles;
-    job.d_doc_off = d_doc_off;
-    job.d_tok_off = d_tok_off;
-    job.single_piece = single_piece;
-    TRY(ensure(w.brk, (nwords + 2) * 4));
     TRY(ensure(w.starts, (nwords + 2) * 4));
     TRY(ensure(w.blockcnt, (nblk + 2) * 4));
-    TRY(ensure(w.counters, TK_CNT_N * 4));
-    TRY(ensure(w.total, 32));
     TRY(ensure(w.tile_np, (ntiles + 2) * 4));
     TRY(ensure(w.tile_nt, (ntiles + 2) * 4));
     TRY(ensure(w.wbin, (TK_NBIN * TKD_WAVES + 2) * 4));
@@ -837,13 +860,9 @@ static int stage_front(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, con
     // the overflow entries behind them.  The table takes what repeats; the overflow entries are sized for a sixteenth of the worst case
     // (every piece a distinct two-byte piece that is not a token) unless the chunk is small or a batch has already asked for more
     // (c->ovf_full: encode_device_locked repeats such a batch once, with room for the worst case).
-    job.pretok = pretok_only;
     // (small chunks too: without the table every missed piece has an overflow entry, whose tokens tk_k_place copies from the staging area two
     // pieces at a time -- 92 us for a 4 KiB call, against 4 us for clearing 16 Ki keys)
     if (n >= 512 && !single_piece && !pretok_only) {
-#ifndef TK_MT_DIV
-#define TK_MT_DIV 128
-#endif
         while (job.mt_bits < TK_MT_BITS && (1ull << job.mt_bits) < n / TK_MT_DIV) ++job.mt_bits;  // 4 Mi slots from 512 MiB up
         job.ovf_base = 1u << job.mt_bits;
     }
@@ -861,81 +880,71 @@ static int stage_front(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, con
     TRY(ensure(w.big, (1 + 3 * TK_BIGCOPY_CAP) * 4));
     TkClearArgs clr;
     clr.n = 0;
-    auto clear = [&](Buf& b, uint64_t bytes, uint32_t v) {  // (every Buf has at least 256 bytes of slack behind what was asked for)
+    auto clear = [&](Buf& b, uint64_t bytes, uint32_t v) -> int {  // room for `bytes` (nothing to do where more was asked for above), all of them filled
+        TRY(ensure(b, bytes));
         clr.p[clr.n] = b.as<uint4>();
-        clr.n16[clr.n] = (bytes + 15) / 16;
+        clr.n16[clr.n] = (bytes + 15) / 16;  // (every Buf has at least 256 bytes of slack behind what was asked for)
         clr.v[clr.n] = v;
         ++clr.n;
+        return TK_OK;
     };
-    clear(w.brk, (nwords + 2) * 4, 0u);
-    clear(w.counters, TK_CNT_N * 4, 0u);
-    clear(w.big, 4, 0u);
-    TRY(ensure(w.merge_work, 16 * TKM_WORK_STRIDE * 4));
-    clear(w.merge_work, 16 * TKM_WORK_STRIDE * 4, 0u);
-    clear(w.total, 32, 0u);
-    uint32_t *brk = w.brk.as<uint32_t>(), *starts = w.starts.as<uint32_t>();
-    uint32_t *ss = nullptr, *si = nullptr, *docb = nullptr;
+    TRY(clear(w.brk, (nwords + 2) * 4, 0u));
+    TRY(clear(w.counters, TK_CNT_N * 4, 0u));
+    TRY(clear(w.big, 4, 0u));
+    TRY(clear(w.merge_work, 16 * TKM_WORK_STRIDE * 4, 0u));
+    TRY(clear(w.total, 32, 0u));
     uint32_t* find_docb = nullptr;  // the document starts for the disallowed scan: `docb`, or the same bitmap made for the scan alone
-    uint32_t* counters = w.counters.as<uint32_t>();
-    TRY(ensure(w.tile_sum, ntiles + 16));
     // (round 6) the first document that starts in every tile (tk_k_mark_docs), for tk_k_place, which writes the documents' token offsets as it
     // passes their pieces; one piece without pre-tokenisation and empty chunks keep tk_k_docoff
-    const bool docs_in_place = n > 0 && !single_piece && d_tok_off != nullptr;
+    const bool docs_in_place = n > 0 && !single_piece && ask.d_tok_off != nullptr;
     TRY(ensure(w.row_base, (ntiles + 4) * 4));
-    if (docs_in_place) clear(w.row_base, (ntiles + 2) * 4, 0xFFFFFFFFu);
-    clear(w.tile_sum, ntiles + 16, 0xFFFFFFFFu);
+    if (docs_in_place) TRY(clear(w.row_base, (ntiles + 2) * 4, 0xFFFFFFFFu));
+    TRY(clear(w.tile_sum, ntiles + 16, 0xFFFFFFFFu));
+    FrontArgs& f = job.front;
     if (job.ovf_base) {
-        TRY(ensure(w.mt_keys, sizeof(TkMissKey) * job.ovf_base));
-        clear(w.mt_keys, sizeof(TkMissKey) * job.ovf_base, 0xFFFFFFFFu);
+        TRY(clear(w.mt_keys, sizeof(TkMissKey) * job.ovf_base, 0xFFFFFFFFu));
         job.mt = w.mt_keys.as<TkMissKey>();
     }
-    TkFrontOut fo{starts, w.tile_np.as<uint32_t>(), w.res.as<uint32_t>(), w.tile_sum.as<uint8_t>(), miss_of(w, job), job.ovf_cap, w.listC.as<uint32_t>(), counters};
+    f.pat_id = T.pat.generic() ? TK_PAT_GENERIC : T.pattern;
+    f.brk = w.brk.as<uint32_t>();
+    f.out = TkFrontOut{w.starts.as<uint32_t>(), w.tile_np.as<uint32_t>(), w.res.as<uint32_t>(), w.tile_sum.as<uint8_t>(), miss_of(w, job), job.ovf_cap, w.listC.as<uint32_t>(), w.counters.as<uint32_t>()};
+    f.mt = (c->dbg & TK_DBG_NO_MT) ? (TkMissKey*)nullptr : job.mt;
+    f.mt_mask = (1u << job.mt_bits) - 1u;
+    f.dbg = (c->dbg & ~TK_DBG_INTERNAL) | (pretok_only ? TK_DBG_STARTS_ONLY : 0);
     if (n > 0 && !single_piece) {
-        if (use_special) {
-            TRY(ensure(w.docb, (nwords + 4) * 4));  // (tk_bits64 reads two words past the one a position lies in)
-            TRY(ensure(w.cand, (nwords + 4) * 4));
-            TRY(ensure(w.ss, (nwords + 2) * 4));
-            TRY(ensure(w.si, (nwords + 2) * 4));
-            for (Buf* b : {&w.docb, &w.cand}) clear(*b, (nwords + 4) * 4, 0u);
-            for (Buf* b : {&w.ss, &w.si}) clear(*b, (nwords + 2) * 4, 0u);
-            docb = w.docb.as<uint32_t>();
-            ss = w.ss.as<uint32_t>();
-            si = w.si.as<uint32_t>();
+        if (ask.use_special) {
+            for (Buf* b : {&w.docb, &w.cand}) TRY(clear(*b, (nwords + 4) * 4, 0u));  // (tk_bits64 reads two words past the one a position lies in)
+            for (Buf* b : {&w.ss, &w.si}) TRY(clear(*b, (nwords + 2) * 4, 0u));
+            f.docb = w.docb.as<uint32_t>();
+            f.ss = w.ss.as<uint32_t>();
+            f.si = w.si.as<uint32_t>();
         }
         if (c->find_on && !pretok_only) {
             job.find = true;
-            TRY(ensure(w.find, 16));
-            clear(w.find, 16, 0xFFFFFFFFu);
-            if (!docb) {
-                TRY(ensure(w.docb, (nwords + 4) * 4));
-                clear(w.docb, (nwords + 4) * 4, 0u);
-            }
+            TRY(clear(w.find, 16, 0xFFFFFFFFu));
+            if (!f.docb) TRY(clear(w.docb, (nwords + 4) * 4, 0u));
             find_docb = w.docb.as<uint32_t>();
         }
         if (c->has_rx) {
-            // (two bitmaps each: the starts, and behind them the gap chars among the starts)
-            TRY(ensure(w.rx_spec, 2 * (nwords + 2) * 4));
-            TRY(ensure(w.rx_gst, 2 * (nwords + 2) * 4));
-            TRY(ensure(w.rx_lnk, 2 * (nwords + 2) * 4));
-            clear(w.rx_spec, 2 * (nwords + 2) * 4, 0u);
-            clear(w.rx_gst, 2 * (nwords + 2) * 4, 0u);
-            clear(w.rx_lnk, 2 * (nwords + 2) * 4, 0u);
+            const RxPairs rx(n);
+            for (Buf* b : rx.of(w)) TRY(clear(*b, rx.bytes(), 0u));
+            f.gapb = rx.gap(w.rx_gst);
         }
         hipLaunchKernelGGL(tk_k_chunk_clear, dim3(grid_for(n / 64 + 1, 256, 2048)), dim3(256), 0, s, clr);
         clr.n = 0;
         TRY(timed(c, s, "tk_k_mark_docs", [&] {
-            hipLaunchKernelGGL(tk_k_mark_docs, dim3(grid_for(n_docs, 256, 4096)), dim3(256), 0, s, d_doc_off, n_docs, base, n, brk, docb ? docb : find_docb,
+            hipLaunchKernelGGL(tk_k_mark_docs, dim3(grid_for(n_docs, 256, 4096)), dim3(256), 0, s, ask.d_doc_off, n_docs, base, n, f.brk, f.docb ? f.docb : find_docb,
                                docs_in_place ? w.row_base.as<uint32_t>() : (uint32_t*)nullptr, ntiles);
         }));
-        if (use_special) {
+        if (ask.use_special) {
             const uint8_t* allowed = c->allowed.as<uint8_t>();
             uint32_t* cand = w.cand.as<uint32_t>();
             TRY(timed(c, s, "tk_k_spec_cand", [&] {
-                hipLaunchKernelGGL(tk_k_spec_cand, dim3(grid_for(n / 16 + 1, 256, 65536)), dim3(256), 0, s, T, d_text, n, allowed, docb, cand);
+                hipLaunchKernelGGL(tk_k_spec_cand, dim3(grid_for(n / 16 + 1, 256, 65536)), dim3(256), 0, s, T, d_text, n, allowed, f.docb, cand);
             }));
             TRY(timed(c, s, "tk_k_spec_resolve", [&] {
-                hipLaunchKernelGGL(tk_k_spec_resolve, dim3(grid_for(nwords, 256, 65536)), dim3(256), 0, s, T, d_text, n, allowed, docb, cand,
-                                   c->spec_max_len, ss, si, brk);
+                hipLaunchKernelGGL(tk_k_spec_resolve, dim3(grid_for(nwords, 256, 65536)), dim3(256), 0, s, T, d_text, n, allowed, f.docb, cand,
+                                   c->spec_max_len, f.ss, f.si, f.brk);
             }));
         }
         if (job.find) {
@@ -947,59 +956,54 @@ static int stage_front(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, con
             }));
             c->st_find_launches += 1;
         }
-        if (c->has_rx) TRY(rx_split(c, w, s, d_text, n, brk, ss, si, d_doc_off, n_docs, base));  // the generic engine finds the piece starts; they join the hard starts in `brk`
+        if (c->has_rx) TRY(rx_split(c, w, job, s));  // the generic engine finds the piece starts; they join the hard starts in `brk`
         TRY(ensure(w.deferred, 2 * (ntiles + 2) * 4));  // (behind the list of deferred tiles: those that gave up their walk, stage_deferred)
-        uint32_t* deferred = w.deferred.as<uint32_t>();
-        TkMissKey* mt_arg = (c->dbg & TK_DBG_NO_MT) ? (TkMissKey*)nullptr : job.mt;
         TRY(timed(c, s, "tk_k_front", [&] {
-            const dim3 grid((uint32_t)ntiles);
-            launch_front<TKF_MODE_TILE>(T.pat.generic() ? TK_PAT_GENERIC : T.pattern, ss != nullptr, grid, s, T, d_text, n, base, brk, docb, ss, si, fo,
-                                mt_arg, (1u << job.mt_bits) - 1u, deferred, c->has_rx ? w.rx_gst.as<uint32_t>() + nwords + 2 : (const uint32_t*)nullptr,
-                                (c->dbg & ~TK_DBG_INTERNAL) | (pretok_only ? TK_DBG_STARTS_ONLY : 0) | ((c->has_rx && !(c->dbg & TK_DBG_SCANNERS)) ? TK_DBG_HARD_ONLY : 0));
+            launch_front<TKF_MODE_TILE>(c, job, dim3((uint32_t)ntiles), s, w.deferred.as<uint32_t>(), (c->has_rx && !(c->dbg & TK_DBG_SCANNERS)) ? TK_DBG_HARD_ONLY : 0);
         }));
     } else if (n > 0) {
         hipLaunchKernelGGL(tk_k_chunk_clear, dim3(1), dim3(256), 0, s, clr);
         clr.n = 0;
-        TRY(timed(c, s, "tk_k_single_front", [&] { hipLaunchKernelGGL(tk_k_single_front, dim3(1), dim3(64), 0, s, T, d_text, (uint32_t)n, fo, no_lookup ? 1 : 0); }));
+        TRY(timed(c, s, "tk_k_single_front", [&] { hipLaunchKernelGGL(tk_k_single_front, dim3(1), dim3(64), 0, s, T, d_text, (uint32_t)n, f.out, ask.kind == ChunkKind::SinglePieceNoLookup ? 1 : 0); }));
     }
     if (clr.n) hipLaunchKernelGGL(tk_k_chunk_clear, dim3(1), dim3(256), 0, s, clr);  // (an empty chunk)
-    job.spec = ss != nullptr;
     HIPCHK(hipEventRecord(w.ev_front, s));
-    if (pretok_only) {  // debugging / test entry: piece offsets only
-        TRY(stage_deferred(c, w, job, s));
-        uint64_t P = 0;
-        TRY(ensure(w.pstart, 16));
-        if (n > 0) {
-            TRY(timed(c, s, "tk_k_count", [&] {
-                hipLaunchKernelGGL(tk_k_count, dim3((uint32_t)nblk), dim3(256), 0, s, starts, nwords, w.blockcnt.as<uint32_t>());
-            }));
-            TRY(timed(c, s, "tk_k_scan_small", [&] {
-                hipLaunchKernelGGL(tk_k_scan_small, dim3(1), dim3(TK_SCAN_THREADS), 0, s, w.blockcnt.as<uint32_t>(), nblk, w.total.as<uint64_t>());
-            }));
-            HIPCHK(hipMemcpyAsync(&P, w.total.p, 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            if (w.h_counters[TK_CNT_ERR] & (TK_RX_ERR_GAP | TK_RX_ERR_STACK | TK_RX_ERR_LIMIT)) return rx_failure(w.h_counters, base);
-            TRY(ensure(w.pstart, (P + 2) * 4));
-            TRY(timed(c, s, "tk_k_emit", [&] {
-                hipLaunchKernelGGL(tk_k_emit, dim3((uint32_t)nblk), dim3(256), 0, s, starts, nwords, w.blockcnt.as<uint32_t>(),
-                                   w.pstart.as<uint32_t>(), P, n, c->has_rx ? w.rx_gst.as<uint32_t>() + nwords + 2 : (const uint32_t*)nullptr);
-            }));
-        } else {
-            HIPCHK(hipMemsetAsync(w.pstart.p, 0, 4, s));
-        }
-        *pretok_count_out = P;
+    return TK_OK;
+}
+
+// The piece-starts entry (debugging / test entry, training), behind the front stage and the deferred tiles of its chunk: the piece starts are
+// counted and written to w.pstart (ascending, then the total byte count; bit 31 marks a gap char).  Waits: *count_out pieces.
+static int piece_starts(tk_core* c, WorkSet& w, const ChunkJob& job, hipStream_t s, uint64_t* count_out) {
+    const uint64_t n = job.ask.n, nwords = (n + 31) / 32, nblk = (nwords + 255) / 256;
+    uint32_t *starts = w.starts.as<uint32_t>(), *blockcnt = w.blockcnt.as<uint32_t>();
+    uint64_t P = 0;
+    TRY(ensure(w.pstart, 16));
+    if (n > 0) {
+        TRY(timed(c, s, "tk_k_count", [&] { hipLaunchKernelGGL(tk_k_count, dim3((uint32_t)nblk), dim3(256), 0, s, starts, nwords, blockcnt); }));
+        TRY(timed(c, s, "tk_k_scan_small", [&] { hipLaunchKernelGGL(tk_k_scan_small, dim3(1), dim3(TK_SCAN_THREADS), 0, s, blockcnt, nblk, w.total.as<uint64_t>()); }));
+        HIPCHK(hipMemcpyAsync(&P, w.total.p, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (w.h_counters[TK_CNT_ERR] & (TK_RX_ERR_GAP | TK_RX_ERR_STACK | TK_RX_ERR_LIMIT)) return rx_failure(w.h_counters, job.ask.base);
+        TRY(ensure(w.pstart, (P + 2) * 4));
+        TRY(timed(c, s, "tk_k_emit", [&] {
+            hipLaunchKernelGGL(tk_k_emit, dim3((uint32_t)nblk), dim3(256), 0, s, starts, nwords, blockcnt, w.pstart.as<uint32_t>(), P, n, job.front.gapb);
+        }));
+    } else {
+        HIPCHK(hipMemsetAsync(w.pstart.p, 0, 4, s));
     }
+    *count_out = P;
     return TK_OK;
 }
 
 // Second stage of a chunk, on stream s (the front stage's stream for a single chunk, the set's own otherwise; the caller has made it wait
-// for w.ev_front).  d_out: the batch's token buffer; the chunk's tokens go behind tok_bases[job.index] of them, which the previous chunk's
-// back stage writes (prev_tot: the event to wait for, null for the first chunk or on a single stream).
-static int stage_back(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, uint32_t* d_out, hipEvent_t prev_tot) {
+// for w.ev_front).  The chunk's tokens go into the batch's token buffer (ask.d_out) behind tok_bases[job.index] of them, which the previous
+// chunk's back stage writes (prev_tot: the event to wait for; none for the first chunk or on a single stream).
+static int stage_back(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, hipEvent_t prev_tot = nullptr) {
     const TkTables& T = c->D;
-    const uint64_t n = job.n, ntiles = job.ntiles;
-    const uint8_t* d_text = job.d_text;
-    uint32_t* counters = w.counters.as<uint32_t>();
+    const ChunkAsk& ask = job.ask;
+    const uint64_t n = ask.n, ntiles = job.ntiles;
+    const uint8_t* d_text = ask.d_text;
+    uint32_t *d_out = ask.d_out, *counters = w.counters.as<uint32_t>();
     uint32_t *res = w.res.as<uint32_t>(), *stg = w.staging.as<uint32_t>();
     const TkMiss data = miss_of(w, job);
     uint32_t *tile_np = w.tile_np.as<uint32_t>(), *tile_nt = w.tile_nt.as<uint32_t>();
@@ -1007,20 +1011,10 @@ static int stage_back(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, uint
     uint64_t nC = 0;
     TRY(stage_deferred(c, w, job, s));
     // (perf experiments, tools/gpu_phases.sh: a build with TKF_STOP_AFTER -- the front kernel stops after one of its phases -- its outputs
-    // are incomplete, so nothing behind it runs: the call returns zero tokens and offsets that mean nothing)
+    // are incomplete, so nothing behind it runs but the chunk's end, as for an empty chunk: the call returns zero tokens and offsets that mean nothing)
     constexpr bool front_only = TKF_STOP_AFTER != 0;
-    if (front_only) {
-        HIPCHK(hipMemsetAsync(w.total.p, 0, 32, s));
-        if (prev_tot) HIPCHK(hipStreamWaitEvent(s, prev_tot, 0));
-        hipLaunchKernelGGL(tk_k_advance, dim3(1), dim3(64), 0, s, c->tok_bases.as<unsigned long long>(), job.index, w.total.as<uint64_t>());
-        HIPCHK(hipEventRecord(w.ev_tot, s));
-        HIPCHK(hipMemcpyAsync(w.h_total, w.total.p, 16, hipMemcpyDeviceToHost, s));
-        if (job.find) HIPCHK(hipMemcpyAsync(w.h_total + 2, w.find.p, 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(w.h_counters + TK_CNT_N, counters, TK_CNT_N * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipEventRecord(w.ev_done, s));
-        return TK_OK;
-    }
-    if (n > 0) {
+    const bool encode = n > 0 && !front_only;
+    if (encode) {
         uint32_t* wbin = w.wbin.as<uint32_t>();
         uint32_t* listB = w.listB.as<uint32_t>();
         // the two list passes walk the miss data (table slots + overflow entries): as many wavefronts as it has rows of 64 entries for
@@ -1127,7 +1121,7 @@ static int stage_back(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, uint
         }
     }
     const bool small_rows = n < (8u << 20);  // (the one-row instances: a third of the code to fetch for a kernel that runs over a few tiles)
-    if (n > 0) {
+    if (encode) {
         // token count per tile (a missed piece's count from its entry), then the tiles' places (tk_fused.h: back end)
         TRY(timed(c, s, "tk_k_count_tiles", [&] {
             if (small_rows) hipLaunchKernelGGL(tk_k_count_tiles<1>, dim3(grid_for(ntiles, 4, 2048)), dim3(256), 0, s, ntiles, tile_np, res, data, tile_nt,
@@ -1144,24 +1138,24 @@ static int stage_back(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, uint
     if (prev_tot) HIPCHK(hipStreamWaitEvent(s, prev_tot, 0));
     hipLaunchKernelGGL(tk_k_advance, dim3(1), dim3(64), 0, s, c->tok_bases.as<unsigned long long>(), job.index, w.total.as<uint64_t>());
     HIPCHK(hipEventRecord(w.ev_tot, s));
-    if (n > 0) {
+    if (encode) {
         TRY(timed(c, s, "tk_k_place", [&] {
             // (one instance for every size: three rows per step for inputs of a few tiles measured slower -- C1 0.082 ms against 0.060 --, profiles/r05_place_experiments.txt)
-            const bool docs_in_place = !job.single_piece && job.d_tok_off != nullptr;
-            const TkPlaceDocs docs{job.d_doc_off, job.base, n, job.n_docs, w.row_base.as<uint32_t>(), w.starts.as<uint32_t>(), w.total.as<uint64_t>(), docs_in_place ? job.d_tok_off : (uint64_t*)nullptr};
+            const bool docs_in_place = !ask.single_piece() && ask.d_tok_off != nullptr;
+            const TkPlaceDocs docs{ask.d_doc_off, ask.base, n, ask.n_docs, w.row_base.as<uint32_t>(), w.starts.as<uint32_t>(), w.total.as<uint64_t>(), docs_in_place ? ask.d_tok_off : (uint64_t*)nullptr};
             // (six workgroups per CU: 80 registers, 26 688 B of LDS; a grid of four times what is resident -- 0.84 ms with 4096 workgroups, 0.81 with 1536 or 3072,
             // 0.80 with 6144 or 12 288, round 6)
             hipLaunchKernelGGL(tk_k_place<TKP_ROWS_PLACE>, dim3(grid_for(ntiles, 4, 6144)), dim3(256), 0, s, ntiles, tile_np, tile_nt, res, data, stg, d_out, tok_base, w.big.as<uint32_t>(), docs);
         }));
     }
-    if (n > TK_BIGCOPY)  // (a token run of TK_BIGCOPY tokens needs at least as many bytes)
+    if (encode && n > TK_BIGCOPY)  // (a token run of TK_BIGCOPY tokens needs at least as many bytes)
         hipLaunchKernelGGL(tk_k_bigcopy, dim3(1024), dim3(256), 0, s, w.big.as<uint32_t>(), stg, d_out, tok_base);
     // (the document offsets need the tile counts only, but beside tk_k_place on a second stream the two take as long as one after the
     // other: both are bound by the rate of random accesses -- measured in round 4)
-    if (job.d_tok_off && (n == 0 || job.single_piece)) {  // (else tk_k_place has written them)
+    if (!front_only && ask.d_tok_off && (n == 0 || ask.single_piece())) {  // (else tk_k_place has written them)
         TRY(timed(c, s, "tk_k_docoff", [&] {
-            hipLaunchKernelGGL(tk_k_docoff, dim3(grid_for(job.n_docs + 1, 16, 4096)), dim3(256), 0, s, job.n_docs, job.d_doc_off, job.base, n, w.starts.as<uint32_t>(), tile_nt, res, data,
-                               (n > 0 && !job.single_piece) ? w.row_base.as<uint32_t>() : (const uint32_t*)nullptr, w.total.as<uint64_t>(), tok_base, job.d_tok_off);
+            hipLaunchKernelGGL(tk_k_docoff, dim3(grid_for(ask.n_docs + 1, 16, 4096)), dim3(256), 0, s, ask.n_docs, ask.d_doc_off, ask.base, n, w.starts.as<uint32_t>(), tile_nt, res, data,
+                               (n > 0 && !ask.single_piece()) ? w.row_base.as<uint32_t>() : (const uint32_t*)nullptr, w.total.as<uint64_t>(), tok_base, ask.d_tok_off);
         }));
     }
     HIPCHK(hipMemcpyAsync(w.h_total, w.total.p, 16, hipMemcpyDeviceToHost, s));
@@ -1172,8 +1166,6 @@ static int stage_back(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, uint
     return TK_OK;
 }
 
-#define TK_GROW (-1000)  // (internal) the batch has to be repeated with a larger miss data: encode_device_locked
-#define TK_SPEC_HIT (-1002)  // (internal) a chunk holds a disallowed special token (c->find_hit): the entry point reports it, no tokens are handed out
 // the chunk of `w` is complete: its totals, statistics and error flags (waits for its back stage)
 static int chunk_finish(tk_core* c, WorkSet& w, const ChunkJob& job, uint64_t* n_tokens_out) {
     HIPCHK(hipEventSynchronize(w.ev_done));
@@ -1187,7 +1179,7 @@ static int chunk_finish(tk_core* c, WorkSet& w, const ChunkJob& job, uint64_t* n
         nB += hb[TK_CNT_BIN0 + b];
         if ((c->dbg & TK_DBG_VERBOSE) && hb[TK_CNT_BIN0 + b]) fprintf(stderr, "bin %d (%u..%u bytes): %u pieces\n", b, tk_bin_lo(b), tk_bin_hi(b), hb[TK_CNT_BIN0 + b]);
     }
-    if (hb[TK_CNT_ERR] & (TK_RX_ERR_GAP | TK_RX_ERR_STACK | TK_RX_ERR_LIMIT)) return rx_failure(hb, job.base);
+    if (hb[TK_CNT_ERR] & (TK_RX_ERR_GAP | TK_RX_ERR_STACK | TK_RX_ERR_LIMIT)) return rx_failure(hb, job.ask.base);
     if (hb[TK_CNT_ERR]) return fail(TK_RUNTIME_ERROR, "internal error in the front kernel (scanner list overflow, code " + std::to_string(hb[TK_CNT_ERR]) + ")");
     if (job.optimistic) {  // (stage_deferred did not wait for these)
         if (hb[TK_CNT_DEFER2]) {
@@ -1198,11 +1190,11 @@ static int chunk_finish(tk_core* c, WorkSet& w, const ChunkJob& job, uint64_t* n
         const uint32_t ppm = (uint32_t)std::min<uint64_t>(((uint64_t)hb[TK_CNT_DEFER] << 20) / (job.ntiles ? job.ntiles : 1), 1u << 20);
         c->defer_ppm = std::max(ppm, c->defer_ppm / 4);
     }
-    if (hb[TK_CNT_OVF] > job.ovf_cap && !job.pretok) {  // more distinct missed pieces than the miss data has room for: the batch is repeated with room for the worst case
+    if (hb[TK_CNT_OVF] > job.ovf_cap && !job.ask.piece_starts()) {  // more distinct missed pieces than the miss data has room for: the batch is repeated with room for the worst case
         c->ovf_full = true;
         return TK_GROW;
     }
-    c->st_bytes += job.n;
+    c->st_bytes += job.ask.n;
     c->st_pieces += w.h_total[1];
     c->st_tokens += w.h_total[0];
     c->st_medium += nB;
@@ -1211,18 +1203,19 @@ static int chunk_finish(tk_core* c, WorkSet& w, const ChunkJob& job, uint64_t* n
     return TK_OK;
 }
 
-// one chunk, both stages on one stream, waited for: the single-chunk entries (pre-tokenise only, single piece)
-static int run_chunk(tk_core* c, hipStream_t s, const uint8_t* d_text, uint64_t n, const uint64_t* d_doc_off, uint64_t n_docs,
-                     uint64_t base, bool use_special, bool single_piece, uint32_t* d_out, uint64_t* d_tok_off, uint64_t* n_tokens_out,
-                     bool pretok_only = false, bool no_lookup = false) {
+// one chunk, both stages on one stream, waited for: the single-chunk entries (piece starts only, single piece).  *n_out: its tokens, or its pieces
+static int run_chunk(tk_core* c, hipStream_t s, const ChunkAsk& ask, uint64_t* n_out) {
     WorkSet& w = c->ws[0];
     ChunkJob job;
     TRY(ensure(c->tok_bases, 64));
     HIPCHK(hipMemsetAsync(c->tok_bases.p, 0, 16, s));
-    TRY(stage_front(c, w, job, s, d_text, n, d_doc_off, n_docs, base, use_special, single_piece, d_tok_off, pretok_only, no_lookup, n_tokens_out));
-    if (pretok_only) return TK_OK;
-    TRY(stage_back(c, w, job, s, d_out, nullptr));
-    return chunk_finish(c, w, job, n_tokens_out);
+    TRY(stage_front(c, w, job, s, ask));
+    if (ask.piece_starts()) {
+        TRY(stage_deferred(c, w, job, s));
+        return piece_starts(c, w, job, s, n_out);
+    }
+    TRY(stage_back(c, w, job, s));
+    return chunk_finish(c, w, job, n_out);
 }
 
 // a byte per special token on the device: 1 for those whose id is among ids[0..n)
@@ -1444,7 +1437,9 @@ static int encode_device_pass(tk_core* c, hipStream_t s, const uint8_t* d_utf8, 
             HIPCHK(hipMemsetAsync((uint8_t*)w.text_al.p + q.nn, 0, 128, s));
             tx = w.text_al.as<uint8_t>();
         }
-        TRY(stage_front(c, w, jobs[k % TK_NSET], s, tx, q.nn, d_doc_off + q.d0, q.d1 - q.d0, q.b, use_special, false, d_tok_off + q.d0, false, false, nullptr));
+        const ChunkAsk ask{.kind = ChunkKind::Batch, .d_text = tx, .d_doc_off = d_doc_off + q.d0, .n = q.nn, .n_docs = q.d1 - q.d0, .base = q.b, .d_out = d_out,
+                           .d_tok_off = d_tok_off + q.d0, .use_special = use_special};
+        TRY(stage_front(c, w, jobs[k % TK_NSET], s, ask));
         jobs[k % TK_NSET].index = (uint32_t)k;
         return TK_OK;
     };
@@ -1473,7 +1468,7 @@ static int encode_device_pass(tk_core* c, hipStream_t s, const uint8_t* d_utf8, 
         WorkSet& w = c->ws[k % TK_NSET];
         hipStream_t sb = N > 1 ? c->back_s[k % (size_t)c->n_back] : s;
         if (N > 1) HIPCHK(hipStreamWaitEvent(sb, w.ev_front, 0));
-        TRY(stage_back(c, w, jobs[k % TK_NSET], sb, d_out, (N > 1 && k > 0) ? c->ws[(k - 1) % TK_NSET].ev_tot : (hipEvent_t) nullptr));
+        TRY(stage_back(c, w, jobs[k % TK_NSET], sb, (N > 1 && k > 0) ? c->ws[(k - 1) % TK_NSET].ev_tot : (hipEvent_t) nullptr));
         c->host_us[1] += now_us() - tb0;
     }
     const double t_tail = now_us();
@@ -2081,7 +2076,9 @@ extern "C" int tk_pretokenize_batch(tk_core* c, const uint8_t* utf8, const uint6
     bool any = false;
     if (use_special) TRY(prepare_allowed(c, s, allowed_ids, n_allowed, &any));
     uint64_t P = 0;
-    TRY(run_chunk(c, s, c->text.as<uint8_t>(), n_bytes, c->doc_off.as<uint64_t>(), n_docs, 0, use_special && any, false, nullptr, nullptr, &P, true));
+    const ChunkAsk ask{.kind = ChunkKind::PieceStarts, .d_text = c->text.as<uint8_t>(), .d_doc_off = c->doc_off.as<uint64_t>(), .n = n_bytes, .n_docs = n_docs,
+                       .use_special = use_special && any};
+    TRY(run_chunk(c, s, ask, &P));
     HIPCHK(hipStreamSynchronize(s));
     TRY(drain_events(c));
     HostResult<uint32_t> host(malloc((P + 1) * 4));
@@ -2103,7 +2100,7 @@ extern "C" int tk_encode(tk_core* c, const uint8_t* utf8, uint64_t len, const ui
     return tk_encode_batch(c, utf8, off, 1, 1, allowed_ids, n_allowed, tokens_out, n_tokens_out, nullptr);
 }
 
-static int single_piece(tk_core* c, const uint8_t* piece, uint64_t len, bool no_lookup, uint32_t** tokens_out, uint64_t* n_tokens_out) {
+static int single_piece(tk_core* c, const uint8_t* piece, uint64_t len, ChunkKind kind, uint32_t** tokens_out, uint64_t* n_tokens_out) {
     if (!c) return fail(TK_VALUE_ERROR, "core is null");
     if (!tokens_out || !n_tokens_out) return fail(TK_VALUE_ERROR, "null argument");
     if (len >= (4ull << 30) - 65536) return fail(TK_VALUE_ERROR, "piece too long");
@@ -2116,7 +2113,8 @@ static int single_piece(tk_core* c, const uint8_t* piece, uint64_t len, bool no_
     HIPCHK(hipMemsetAsync((uint8_t*)c->text.p + len, 0, 128, s));
     TRY(ensure(c->out_tokens, (len + 64) * 4));
     uint64_t total = 0;
-    TRY(run_chunk(c, s, c->text.as<uint8_t>(), len, nullptr, 0, 0, false, true, c->out_tokens.as<uint32_t>(), nullptr, &total, false, no_lookup));
+    const ChunkAsk ask{.kind = kind, .d_text = c->text.as<uint8_t>(), .n = len, .d_out = c->out_tokens.as<uint32_t>()};
+    TRY(run_chunk(c, s, ask, &total));
     HIPCHK(hipStreamSynchronize(s));
     TRY(drain_events(c));
     HostResult<uint32_t> host(malloc((total ? total : 1) * 4));
@@ -2128,11 +2126,11 @@ static int single_piece(tk_core* c, const uint8_t* piece, uint64_t len, bool no_
 }
 
 extern "C" int tk_encode_single_piece(tk_core* c, const uint8_t* piece, uint64_t len, uint32_t** tokens_out, uint64_t* n_tokens_out) {
-    return single_piece(c, piece, len, false, tokens_out, n_tokens_out);
+    return single_piece(c, piece, len, ChunkKind::SinglePiece, tokens_out, n_tokens_out);
 }
 
 extern "C" int tk_byte_pair_encode(tk_core* c, const uint8_t* piece, uint64_t len, uint32_t** tokens_out, uint64_t* n_tokens_out) {
-    return single_piece(c, piece, len, true, tokens_out, n_tokens_out);
+    return single_piece(c, piece, len, ChunkKind::SinglePieceNoLookup, tokens_out, n_tokens_out);
 }
 
 extern "C" int tk_encode_single_token(tk_core* c, const uint8_t* piece, uint64_t len, uint32_t* token_out) {
@@ -2886,7 +2884,8 @@ extern "C" int tk_train_bpe(tk_core* c, const uint8_t* utf8, const uint64_t* doc
             HIPCHK(hipMemsetAsync((uint8_t*)c->text.p + n, 0, 128, s));
             HIPCHK(hipMemcpyAsync(c->doc_off.p, local.data(), (nd + 1) * 8, hipMemcpyHostToDevice, s));
             uint64_t P = 0;
-            TRY(run_chunk(c, s, c->text.as<uint8_t>(), n, c->doc_off.as<uint64_t>(), nd, 0, false, false, nullptr, nullptr, &P, true));  // (waits: P is known)
+            const ChunkAsk ask{.kind = ChunkKind::PieceStarts, .d_text = c->text.as<uint8_t>(), .d_doc_off = c->doc_off.as<uint64_t>(), .n = n, .n_docs = nd};
+            TRY(run_chunk(c, s, ask, &P));  // (waits: P is known)
             if (P) {
                 TRY(train_blob_reserve(s, r, cells[TKT_BLOB], cells[TKT_BLOB] + n + 64));
                 if ((cells[TKT_BLOB] + n) >> 32) return fail(TK_VALUE_ERROR, "tk_train_bpe: more than 4 GiB of distinct words");
