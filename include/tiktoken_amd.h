@@ -210,6 +210,50 @@ int tk_encode_batch_rows(tk_core* core, const uint8_t* utf8, const uint64_t* doc
                          const tk_rows_spec* spec, void** ids_out, uint32_t** doc_out, uint32_t** pos_out, uint32_t** cu_seqlens_out,
                          uint32_t** row_seg_out, uint64_t* n_rows_out, uint64_t* n_segs_out, uint64_t* n_stream_out, uint64_t* n_tail_out,
                          tk_special_hit* hit);
+/* Padded model inputs: a packed batch -> one row per document, truncated to a maximum length and padded, with an attention mask -- or a
+ * long document continued in further rows that overlap by `stride` tokens.  Replaces nothing in the reference: it is the host loop of the
+ * reference's users (`enc.encode(t)[:n]` plus list padding, a token-window text splitter; elsewhere `tokenizer(batch, padding=...,
+ * truncation=..., max_length=..., stride=..., return_overflowing_tokens=True)`) -- here one call on ids that are on the device anyway.
+ * The rule.  Input: tokens uint32[T], tok_off uint64[n_docs + 1].  bos_id / eos_id: TK_ROWS_NO_TOKEN for none; k = how many of the two
+ * exist, has_bos = 0 or 1, c = max_len - k the body capacity of a row.  Document d has n_d = tok_off[d + 1] - tok_off[d] body tokens.
+ *  Rows of a document.  Every document owns at least one row, an empty one too ([bos][eos], or nothing but padding).  Without
+ *   TK_PAD_WINDOWS there is one row: its body is tokens [0, min(n_d, c)) of the document, with TK_PAD_KEEP_TAIL [max(n_d - c, 0), n_d).
+ *   With TK_PAD_WINDOWS let step = c - stride: n_d <= c gives one row, otherwise w_d = 1 + ceil((n_d - c) / step) rows, row j holding body
+ *   tokens [j * step, min(j * step + c, n_d)) -- the last row may be short, consecutive rows share `stride` tokens, every row gets its
+ *   own bos / eos.
+ *  Row contents.  Row r belongs to document row_doc[r] and starts at body token row_tok[r], an index inside the document;
+ *   len[r] = k + (body tokens it holds).  Its elements are [bos] body [eos]: with TK_PAD_LEFT in columns [W - len, W), otherwise in
+ *   [0, len); everywhere else ids = pad_id.  mask (uint8) is 1 on elements and 0 on padding.
+ *  Row order.  Rows are in document order; doc_row[d] (uint32[n_docs + 1]) is the first row of document d, doc_row[n_docs] = R.
+ *  Width.  width_multiple == 0: W = max_len.  Otherwise W = min(max_len, ceil(longest / width_multiple) * width_multiple) with
+ *   longest = max len[r], 0 when there is no row.  W = 0 is a legal result (only empty documents, no bos / eos, width_multiple = 1):
+ *   ids and mask are [R, 0] then, and len, row_doc, row_tok, doc_row are still filled.
+ *  TK_VALUE_ERROR: max_len == 0 or c == 0; stride >= c; stride != 0 without TK_PAD_WINDOWS; TK_PAD_KEEP_TAIL together with
+ *   TK_PAD_WINDOWS; n_docs >= 2^32 - 1, T >= 2^32, R >= 2^32 or R * W >= 2^32 (found after the count, before any output is written);
+ *   TK_PAD_IDS16 unless every id of the vocabulary, the special tokens, bos_id, eos_id and pad_id fit 16 bits (as TK_ROWS_IDS16); a tok_off
+ *   that does not ascend from 0 to n_tokens (checked on the device before anything is indexed with it; the message names the first
+ *   offending document).  No kernel reads or writes out of bounds, whatever tok_off holds.  One device per call: a group has no padded entry. */
+#define TK_PAD_WINDOWS 1u   /* a document that does not fit goes on in further rows */
+#define TK_PAD_KEEP_TAIL 2u /* without WINDOWS: keep a long document's last tokens, not its first */
+#define TK_PAD_LEFT 4u      /* padding in front of the row's elements, not behind */
+#define TK_PAD_IDS16 8u     /* ids as uint16 (same condition as TK_ROWS_IDS16) */
+typedef struct {
+    uint32_t max_len, stride, width_multiple, bos_id, eos_id, pad_id, flags;
+} tk_pad_spec;
+/* Device pointers in (ids uint32, d_tok_off uint64[n_docs + 1]: e.g. the results of tk_encode_batch_device), device pointers out: buffers
+ * of the core, valid until its next padded call that succeeds (a refused call writes into none of them) and apart from the encode, decode,
+ * span and rows buffers (padding an encode call's result leaves it intact).  *d_ids_out (uint32 or uint16) and *d_mask_out: *n_rows_out x *width_out; *d_len_out, *d_row_doc_out, *d_row_tok_out:
+ * *n_rows_out; *d_doc_row_out: n_docs + 1.  `stream`: a hipStream_t or null (the core's); the call returns when the rows are there. */
+int tk_pad_batch_device(tk_core* core, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_docs, const tk_pad_spec* spec,
+                        void* stream, const void** d_ids_out, const uint8_t** d_mask_out, const uint32_t** d_len_out, const uint32_t** d_row_doc_out,
+                        const uint32_t** d_row_tok_out, const uint32_t** d_doc_row_out, uint64_t* n_rows_out, uint64_t* width_out);
+/* tk_encode_batch -- with n_disallowed != 0: tk_encode_batch_checked -- with its result padded while the ids are on the device: host text
+ * in, and only the padded arrays cross the link (the ids themselves are not handed out).  *ids_out .. *doc_row_out: library-owned
+ * (tk_free), sized as above.  On TK_DISALLOWED_SPECIAL nothing is handed out. */
+int tk_encode_batch_padded(tk_core* core, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special,
+                           const uint32_t* allowed_ids, uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed,
+                           const tk_pad_spec* spec, void** ids_out, uint8_t** mask_out, uint32_t** len_out, uint32_t** row_doc_out,
+                           uint32_t** row_tok_out, uint32_t** doc_row_out, uint64_t* n_rows_out, uint64_t* width_out, tk_special_hit* hit);
 /* bpe_train(data, vocab_size, pat_str, visualise=None)                      tiktoken/_educational.py:119-185
  * Training a vocabulary: the merges the reference's educational trainer makes on the same text -- the same pairs in the same order -- for a
  * packed batch of documents, under the core's pat_str (stock scanners or the generic engine).  The core's ranks and special tokens play

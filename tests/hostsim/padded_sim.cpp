@@ -1,0 +1,117 @@
+// The padded passes (tiktoken_amd/csrc/tk_padded.h) on the CPU: the plain C++ they are made of -- tk_padded_rule.h: what a spec may say, the
+// rows of a document, the width, a row's body, the document of a row, where a column's element comes from -- compiled for the host and
+// driven the way the kernels drive it: lanes of eight positions, workgroups of `block` positions.  Test infrastructure only
+// (tests/test_padded_sim.py builds it).
+#include <stdint.h>
+
+#include "../../tiktoken_amd/csrc/tk_padded_rule.h"
+
+extern "C" {
+// The figures of a call: counts = {R, W}.  Returns 0; 1 .. 8: tk_pad_shape's / tk_pad_size's refusal; 16 + tk_rows_bad_key: tok_off is
+// refused.  doc_row: room for n_docs + 1.  Nothing else is written: the caller sizes the other arrays from counts and calls padded_sim.
+int64_t padded_sim_count(uint64_t T, const uint64_t* tok_off, uint64_t n_docs, uint32_t max_len, uint32_t stride, uint32_t width_multiple, uint32_t bos, uint32_t eos,
+                         uint32_t pad, uint32_t flags, uint32_t* doc_row, uint64_t* counts) {
+    TkPad p;
+    const int refused = tk_pad_shape(T, n_docs, max_len, stride, width_multiple, bos, eos, pad, flags, &p);
+    if (refused) return refused;
+    // tk_k_pad_count
+    uint64_t bad = ~0ull;
+    uint32_t longest = 0;
+    for (uint64_t d = 0; d <= n_docs; ++d) {
+        const uint64_t a = tok_off[d], b = d < n_docs ? tok_off[d + 1] : p.n_tokens;
+        const uint32_t why = tk_rows_off_error(a, b, d, p.n_docs);
+        if (why) {
+            const uint64_t key = tk_rows_bad_key(d, p.n_docs, why);
+            bad = key < bad ? key : bad;
+        }
+        if (d < n_docs) {
+            const uint64_t n = why ? 0 : b - a;
+            doc_row[d] = (uint32_t)tk_pad_windows(p, n);
+            const uint32_t l = tk_pad_longest(p, n);
+            longest = l > longest ? l : longest;
+        }
+    }
+    // tk_k_pad_scan
+    uint64_t carry = 0;
+    for (uint64_t d = 0; d < n_docs; ++d) {
+        const uint64_t at = carry;
+        carry += doc_row[d];
+        doc_row[d] = (uint32_t)at;
+    }
+    doc_row[n_docs] = (uint32_t)carry;
+    // the host
+    if (bad != ~0ull) return 16 + (int64_t)bad;
+    const int too_big = tk_pad_size(&p, carry, longest);
+    counts[0] = p.R;
+    counts[1] = p.W;
+    return too_big;
+}
+
+// The token array as tk_pad_lane reads it, every index checked: eight ids at once where their address is a multiple of 16, as on the device
+struct SimTokens {
+    const uint32_t* p;
+    uint64_t T;
+    bool* oob;
+    uint32_t one(uint64_t i) const {
+        if (i >= T) {
+            *oob = true;
+            return 0;
+        }
+        return p[i];
+    }
+    bool eight(uint64_t i, uint32_t out[8]) const {
+        if ((uintptr_t)(p + i) & 15u) return false;
+        if (i + 8 > T) {
+            *oob = true;
+            return false;
+        }
+        for (int j = 0; j < 8; ++j) out[j] = p[i + j];
+        return true;
+    }
+};
+
+// tk_k_pad_rows and tk_k_pad_write after padded_sim_count has accepted the call and left doc_row: the per-row pass statement by statement,
+// the write pass through tk_pad_block_docs and tk_pad_lane -- the functions the kernel itself calls -- with the kernel's stores.  ids /
+// mask: room for R * W, len / row_doc / row_tok: R.  -1 if a token index or a document index lies out of bounds.
+int64_t padded_sim(const uint32_t* tokens, uint64_t T, const uint64_t* tok_off, uint64_t n_docs, uint32_t max_len, uint32_t stride, uint32_t width_multiple, uint32_t bos,
+                   uint32_t eos, uint32_t pad, uint32_t flags, uint32_t block, const uint32_t* doc_row, uint64_t R, uint32_t W, uint32_t* ids_out, uint8_t* mask_out,
+                   uint32_t* len, uint32_t* row_doc, uint32_t* row_tok) {
+    TkPad p;
+    if (tk_pad_shape(T, n_docs, max_len, stride, width_multiple, bos, eos, pad, flags, &p)) return -3;
+    p.R = R;
+    p.W = W;  // (what padded_sim_count settled)
+    // tk_k_pad_rows
+    for (uint64_t r = 0; r < p.R; ++r) {
+        const uint64_t d = tk_pad_doc_of_row(doc_row, 0, p.n_docs, r);
+        if (d >= n_docs) return -1;
+        TkPadRow w;
+        tk_pad_row_load(p, tok_off, doc_row, d, r, &w);
+        len[r] = w.len;
+        row_doc[r] = (uint32_t)w.d;
+        row_tok[r] = (uint32_t)w.tok;
+    }
+    // tk_k_pad_write
+    bool oob = false;
+    const SimTokens tok{tokens, T, &oob};
+    const uint32_t N = (uint32_t)(p.R * p.W), nb = (uint32_t)(((uint64_t)N + block - 1) / block);
+    for (uint32_t blk = 0; blk < nb; ++blk) {
+        const uint32_t b0 = blk * block;
+        uint64_t lo = 0, hi = 0;
+        tk_pad_block_docs(p, doc_row, b0, block, N, &lo, &hi);
+        if (hi > n_docs) return -1;
+        for (uint32_t t = 0; t < block / 8; ++t) {
+            if (N - b0 <= t * 8u) continue;
+            const uint32_t i0 = b0 + t * 8u;
+            uint32_t id[8];
+            uint64_t mask;
+            tk_pad_lane(p, tok, tok_off, doc_row, lo, hi, i0, N, id, &mask);
+            for (uint32_t j = 0; j < 8; ++j)
+                if (N - i0 > j) {
+                    ids_out[i0 + j] = id[j];
+                    mask_out[i0 + j] = (uint8_t)(mask >> (8 * j));
+                }
+        }
+    }
+    return oob ? -1 : 0;
+}
+}

@@ -1,0 +1,234 @@
+"""The padded passes (tk_padded.h) on the CPU: tests/hostsim/padded_sim.cpp compiles the plain C++ they are made of
+(tiktoken_amd/csrc/tk_padded_rule.h) for the host and drives it the way the kernels do -- lanes of eight positions, workgroups of 16 and
+2048; the write pass runs through tk_pad_lane, the function the kernel itself calls.  Compared with the numpy restatement of the rule in tests/padded_ref.py, which is written from the rule's description
+(include/tiktoken_amd.h), not from the kernels."""
+import ctypes
+import fcntl
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import helpers as h
+import padded_ref as pr
+
+_lib = None
+BLOCKS = (16, 2048)
+WINDOWS, KEEP_TAIL, LEFT = 1, 2, 4
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        d = os.path.join(h.ROOT, "tests", "hostsim")
+        c = os.path.join(h.ROOT, "tiktoken_amd", "csrc")
+        so = os.path.join(d, "libpadded_sim.so")
+        srcs = [os.path.join(d, "padded_sim.cpp"), os.path.join(c, "tk_padded_rule.h"), os.path.join(c, "tk_rows_rule.h"), os.path.join(c, "tk_common.h")]
+
+        def stale():
+            return not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs)
+
+        if stale():  # (several workers may get here at once: one builds, into a file of its own, and renames)
+            with open(so + ".lock", "w") as lk:
+                fcntl.flock(lk, fcntl.LOCK_EX)
+                if stale():
+                    tmp = f"{so}.{os.getpid()}.tmp"
+                    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Werror", srcs[0], "-o", tmp])
+                    os.replace(tmp, so)
+        L = ctypes.CDLL(so)
+        vp, u64, u32 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32
+        L.padded_sim_count.restype = ctypes.c_int64
+        L.padded_sim_count.argtypes = [u64, vp, u64, u32, u32, u32, u32, u32, u32, u32, vp, vp]
+        L.padded_sim.restype = ctypes.c_int64
+        L.padded_sim.argtypes = [vp, u64, vp, u64, u32, u32, u32, u32, u32, u32, u32, u32, vp, u64, u32, vp, vp, vp, vp, vp]
+        _lib = L
+    return _lib
+
+
+def flags_of(windows=False, keep_tail=False, left=False):
+    return (WINDOWS if windows else 0) | (KEEP_TAIL if keep_tail else 0) | (LEFT if left else 0)
+
+
+def run_sim(tokens, tok_off, max_len, block, *, stride=0, width_multiple=0, bos=None, eos=None, pad=0, T=None, **fl):
+    """(rc, Padded or None) of the simulation; the arrays sit between guard words that must survive."""
+    tokens = np.ascontiguousarray(tokens, np.uint32)
+    tok_off = np.ascontiguousarray(tok_off, np.uint64)
+    T, n_docs = len(tokens) if T is None else T, len(tok_off) - 1
+    G = 0xDEADBEEF
+    none = pr.NONE
+    spec = (max_len, stride, width_multiple, none if bos is None else bos, none if eos is None else eos, pad, flags_of(**fl))
+    doc_row = np.full(n_docs + 2, G, np.uint32)
+    counts = np.zeros(2, np.uint64)
+    rc = lib().padded_sim_count(T, tok_off.ctypes.data, n_docs, *spec, doc_row.ctypes.data, counts.ctypes.data)
+    if rc:
+        return rc, None
+    R, W = (int(x) for x in counts)
+    ids = np.full(R * W + 1, G, np.uint32)
+    mask = np.full(R * W + 1, 0xAB, np.uint8)
+    ln, row_doc, row_tok = (np.full(R + 1, G, np.uint32) for _ in range(3))
+    src = tokens if T else np.zeros(1, np.uint32)
+    rc = lib().padded_sim(src.ctypes.data, T, tok_off.ctypes.data, n_docs, *spec, block, doc_row.ctypes.data, R, W, ids.ctypes.data, mask.ctypes.data, ln.ctypes.data,
+                          row_doc.ctypes.data, row_tok.ctypes.data)
+    if rc:
+        return rc, None
+    assert ids[-1] == G and mask[-1] == 0xAB and ln[-1] == G and row_doc[-1] == G and row_tok[-1] == G and doc_row[-1] == G
+    return 0, pr.Padded(ids[:-1].reshape(R, W), mask[:-1].reshape(R, W), ln[:-1], row_doc[:-1], row_tok[:-1], doc_row[:-1])
+
+
+def check(docs, max_lens, blocks=BLOCKS, specials=pr.SPECIALS, pad=7, settings=None):
+    tokens, tok_off = pr.pack_docs(docs)
+    for bos, eos in specials:
+        k = (bos is not None) + (eos is not None)
+        for max_len in max_lens:
+            for kw in (settings if settings is not None else pr.settings(max_len, k)):
+                want = pr.padded_rule(tokens, tok_off, max_len, bos=bos, eos=eos, pad=pad, **kw)
+                for block in blocks:
+                    rc, got = run_sim(tokens, tok_off, max_len, block, bos=bos, eos=eos, pad=pad, **kw)
+                    assert rc == 0, (rc, max_len, bos, eos, kw, block)
+                    pr.same(got, want, (max_len, bos, eos, kw, block, [len(d) for d in docs][:12]))
+
+
+def test_a_case_worked_by_hand():
+    """Four documents of 5, 0, 2 and 9 tokens, max_len 6 with an eos (99): c = 5.  Written down from the rule's text, for the restatement
+    and for the simulation."""
+    docs = [[10, 11, 12, 13, 14], [], [20, 21], [30, 31, 32, 33, 34, 35, 36, 37, 38]]
+    tokens, tok_off = pr.pack_docs(docs)
+    # truncation, right padding, fixed width
+    want_ids = [[10, 11, 12, 13, 14, 99], [99, 0, 0, 0, 0, 0], [20, 21, 99, 0, 0, 0], [30, 31, 32, 33, 34, 99]]
+    want_mask = [[1, 1, 1, 1, 1, 1], [1, 0, 0, 0, 0, 0], [1, 1, 1, 0, 0, 0], [1, 1, 1, 1, 1, 1]]
+    for got in (pr.padded_rule(tokens, tok_off, 6, eos=99, pad=0), run_sim(tokens, tok_off, 6, 16, eos=99, pad=0)[1]):
+        assert got.ids.tolist() == want_ids and got.mask.tolist() == want_mask
+        assert got.len.tolist() == [6, 1, 3, 6] and got.row_doc.tolist() == [0, 1, 2, 3] and got.row_tok.tolist() == [0, 0, 0, 0] and got.doc_row.tolist() == [0, 1, 2, 3, 4]
+    # the tail of the long document, left padding
+    for got in (pr.padded_rule(tokens, tok_off, 6, eos=99, pad=0, keep_tail=True, left=True), run_sim(tokens, tok_off, 6, 16, eos=99, pad=0, keep_tail=True, left=True)[1]):
+        assert got.ids.tolist() == [[10, 11, 12, 13, 14, 99], [0, 0, 0, 0, 0, 99], [0, 0, 0, 20, 21, 99], [34, 35, 36, 37, 38, 99]]
+        assert got.row_tok.tolist() == [0, 0, 0, 4] and got.mask.sum(1).tolist() == [6, 1, 3, 6]
+    # windows with stride 2: step 3, the last document has 1 + ceil((9 - 5) / 3) = 3 rows: [0, 5) [3, 8) [6, 9)
+    for got in (pr.padded_rule(tokens, tok_off, 6, eos=99, pad=0, windows=True, stride=2), run_sim(tokens, tok_off, 6, 16, eos=99, pad=0, windows=True, stride=2)[1]):
+        assert got.ids.tolist() == [[10, 11, 12, 13, 14, 99], [99, 0, 0, 0, 0, 0], [20, 21, 99, 0, 0, 0], [30, 31, 32, 33, 34, 99], [33, 34, 35, 36, 37, 99],
+                                    [36, 37, 38, 99, 0, 0]]
+        assert got.len.tolist() == [6, 1, 3, 6, 6, 4] and got.row_doc.tolist() == [0, 1, 2, 3, 3, 3] and got.row_tok.tolist() == [0, 0, 0, 0, 3, 6]
+        assert got.doc_row.tolist() == [0, 1, 2, 3, 6]
+    # the width: the longest row is 3 + 1 under max_len 4 -> a multiple of 8 is cut back to max_len; under max_len 64 it is 8
+    for got in (pr.padded_rule(tokens, tok_off, 4, eos=99, pad=0, width_multiple=8), run_sim(tokens, tok_off, 4, 16, eos=99, pad=0, width_multiple=8)[1]):
+        assert got.ids.shape == (4, 4)
+    for got in (pr.padded_rule(tokens[:7], tok_off[:4], 64, eos=99, pad=0, width_multiple=8), run_sim(tokens[:7], tok_off[:4], 64, 16, eos=99, pad=0, width_multiple=8)[1]):
+        assert got.ids.shape == (3, 8) and got.ids[2].tolist() == [20, 21, 99, 0, 0, 0, 0, 0]
+    # W == 0: only empty documents, no bos / eos, width_multiple 1 -- the per-row arrays are still there
+    for got in (pr.padded_rule([], [0, 0, 0], 5, width_multiple=1), run_sim([], [0, 0, 0], 5, 16, width_multiple=1)[1]):
+        assert got.ids.shape == (2, 0) and got.mask.shape == (2, 0)
+        assert got.len.tolist() == [0, 0] and got.row_doc.tolist() == [0, 1] and got.row_tok.tolist() == [0, 0] and got.doc_row.tolist() == [0, 1, 2]
+
+
+@pytest.mark.parametrize("block", BLOCKS)
+def test_case_list(block):
+    rng = np.random.default_rng(block)
+    for name, docs, max_lens in pr.cases(block, rng):
+        for bos, eos in pr.SPECIALS:
+            for max_len in max_lens:
+                check(docs, [max_len], blocks=(block,), specials=[(bos, eos)], settings=pr.settings(max_len, (bos is not None) + (eos is not None), max(map(len, docs), default=0)))
+
+
+def test_token_pointer_that_is_not_16_byte_aligned():
+    """tk_pad_lane fetches eight body tokens at once where their address is a multiple of 16: the token array at every offset from one"""
+    rng = np.random.default_rng(6)
+    tokens, tok_off = pr.pack_docs([rng.integers(0, 50000, size=n).tolist() for n in (70, 0, 150, 9)])
+    room = np.zeros(len(tokens) + 8, np.uint32)
+    first = (-room.ctypes.data // 4) % 4  # the element of `room` that lies on a 16-byte boundary
+    for shift in range(4):
+        held = room[first + shift: first + shift + len(tokens)]
+        held[:] = tokens
+        assert held.ctypes.data % 16 == 4 * shift
+        for bos, eos in pr.SPECIALS:
+            for kw in (dict(), dict(left=True, keep_tail=True), dict(windows=True, stride=5), dict(windows=True, left=True, width_multiple=8)):
+                for max_len in (24, 27):
+                    rc, got = run_sim(held, tok_off, max_len, 16, bos=bos, eos=eos, pad=7, **kw)
+                    assert rc == 0
+                    pr.same(got, pr.padded_rule(tokens, tok_off, max_len, bos=bos, eos=eos, pad=7, **kw), (shift, bos, eos, kw, max_len))
+
+
+@pytest.mark.parametrize("bos,eos", pr.SPECIALS)
+def test_documents_around_the_capacity(bos, eos):
+    """n_d in {c - 1, c, c + 1, c + step - 1, c + step, c + step + 1} for stride in {0, 1, c - 1} and max_len in {1 + k, 7, 8, 9, 64}"""
+    rng = np.random.default_rng(7)
+    k = (bos is not None) + (eos is not None)
+    for max_len in (1 + k, 7, 8, 9, 64):
+        c = max_len - k
+        for stride in sorted({0, 1, c - 1}):
+            if stride >= c:
+                continue
+            docs = pr.around_capacity(max_len, k, stride, rng)
+            sets = [dict(left=left, width_multiple=wm, windows=True, stride=stride) for left in (False, True) for wm in (0, 8)]
+            if stride == 0:
+                sets += [dict(left=left, keep_tail=kt, width_multiple=wm) for left in (False, True) for kt in (False, True) for wm in (0, 1, 64)]
+            check(docs, [max_len], specials=[(bos, eos)], settings=sets)
+
+
+def test_max_len_around_a_workgroup_of_2048():
+    rng = np.random.default_rng(4)
+    docs = [rng.integers(0, 50000, size=n).tolist() for n in (2047, 2048, 2049, 0, 5000, 1)]
+    for max_len in (2048, 2049):
+        sets = [dict(windows=True, stride=1), dict(windows=True, stride=max_len - 3, left=True), dict(keep_tail=True, width_multiple=64), dict(left=True)]
+        check(docs[:4] + docs[5:], [max_len], blocks=(2048,), specials=pr.SPECIALS[::3], settings=sets[2:])
+        check(docs[3:], [max_len], blocks=(2048,), specials=pr.SPECIALS[1:3], settings=sets[:1])
+    check([docs[0][:40]], [9], blocks=(2048,), specials=pr.SPECIALS[3:], settings=[dict(windows=True, stride=6, left=True)])
+
+
+def test_width_multiple_with_the_longest_row_below_at_and_above_max_len():
+    rng = np.random.default_rng(5)
+    for longest in (5, 15, 16, 17, 24, 40):  # max_len 16: below, just below, at, above
+        docs = [rng.integers(0, 50000, size=n).tolist() for n in (3, 0, longest, 1)]
+        for wm in (0, 1, 8, 64):
+            for left in (False, True):
+                check(docs, [16], specials=pr.SPECIALS[:2], settings=[dict(width_multiple=wm, left=left), dict(width_multiple=wm, left=left, windows=True, stride=3)])
+
+
+def test_random_sweep():
+    rng = np.random.default_rng(0x9AD)
+    for _ in range(150):
+        docs = []
+        for _ in range(int(rng.choice([1, 2, 5, 40, 120]))):
+            u = rng.random()
+            n = 0 if u < 0.25 else 1 if u < 0.35 else int(rng.choice([2, 7, 8, 9, 30, 200, 60, 2500 if rng.random() < 0.1 else 17]))
+            docs.append(rng.integers(0, 60000, size=n).tolist())
+        bos, eos = pr.SPECIALS[int(rng.integers(0, 4))]
+        k = (bos is not None) + (eos is not None)
+        max_len = int(rng.choice([1, 2, 3, 8, 13, 64, 100, 2048])) + k
+        c = max_len - k
+        kw = dict(left=bool(rng.integers(0, 2)), width_multiple=int(rng.choice([0, 1, 3, 8, 64])))
+        mode = int(rng.integers(0, 3))
+        if mode == 0:
+            kw.update(windows=True, stride=int(rng.integers(0, c)))
+        elif mode == 1:
+            kw.update(keep_tail=True)
+        check(docs, [max_len], specials=[(bos, eos)], settings=[kw])
+
+
+def test_refusals():
+    tokens, tok_off = pr.pack_docs([[1, 2, 3], [4], [5, 6]])
+    assert run_sim(tokens, tok_off, 4, 16)[0] == 0
+    assert run_sim(tokens, tok_off, 0, 16)[0] == 1  # max_len == 0
+    assert run_sim(tokens, tok_off, 1, 16, eos=9)[0] == 1 and run_sim(tokens, tok_off, 2, 16, bos=8, eos=9)[0] == 1  # c == 0
+    assert run_sim(tokens, tok_off, 3, 16, bos=8, eos=9)[0] == 0
+    assert run_sim(tokens, tok_off, 4, 16, windows=True, stride=4)[0] == 2 and run_sim(tokens, tok_off, 4, 16, eos=9, windows=True, stride=3)[0] == 2  # stride >= c
+    assert run_sim(tokens, tok_off, 4, 16, eos=9, windows=True, stride=2)[0] == 0
+    assert run_sim(tokens, tok_off, 4, 16, stride=1)[0] == 3  # stride without windows
+    assert run_sim(tokens, tok_off, 4, 16, windows=True, keep_tail=True)[0] == 4
+    # 32-bit outputs, refused from the figures alone (nothing is read): documents, tokens
+    n = None
+    assert lib().padded_sim_count(5, n, (1 << 32) - 1, 4, 0, 0, pr.NONE, pr.NONE, 0, 0, n, n) == 5
+    assert lib().padded_sim_count(1 << 32, n, 3, 4, 0, 0, pr.NONE, pr.NONE, 0, 0, n, n) == 6
+    # ... and after the count: rows times width (three rows of 2^31; the figures alone, T is not the array's), and the same batch one bit narrower
+    off = np.array([0, 1, 2, 3], np.uint64)
+    assert run_sim(np.zeros(3, np.uint32), off, 1 << 31, 16)[0] == 8
+    doc_row, counts = np.zeros(5, np.uint32), np.zeros(2, np.uint64)
+    assert lib().padded_sim_count(3, off.ctypes.data, 3, 1 << 30, 0, 0, pr.NONE, pr.NONE, 0, 0, doc_row.ctypes.data, counts.ctypes.data) == 0 and counts.tolist() == [3, 1 << 30]
+    # a tok_off that does not describe the batch: the first offending document, and no access out of bounds on the way (rc -1 would say so)
+    for bad, doc, why in (([1, 3, 4, 6], 0, 1), ([0, 4, 3, 6], 1, 2), ([0, 3, 4, 5], 2, 3), ([0, 3, 4, 7], 2, 3), ([0, 1 << 40, 4, 6], 1, 2), ([0, 3, 1 << 63, 6], 2, 2),
+                          ([0, 9, 9, 6], 2, 2), ([2, 1, 0, 9], 0, 1)):
+        for bos, eos in pr.SPECIALS:
+            for kw in (dict(), dict(windows=True, stride=1), dict(keep_tail=True, left=True, width_multiple=8)):
+                rc, _ = run_sim(tokens, np.array(bad, np.uint64), 4 + (bos is not None) + (eos is not None), 16, bos=bos, eos=eos, **kw)
+                assert rc == 16 + (doc << 2 | why), (bad, rc)
+    assert run_sim(np.zeros(0, np.uint32), np.array([3], np.uint64), 4, 16, eos=1)[0] == 16 + 1  # no documents, tok_off = [3]

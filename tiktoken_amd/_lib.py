@@ -33,6 +33,15 @@ class RowsSpec(ctypes.Structure):
 ROWS_NO_TOKEN, ROWS_DROP_LAST, ROWS_IDS16 = 0xFFFFFFFF, 1, 2
 
 
+class PadSpec(ctypes.Structure):
+    """tk_pad_spec: how a packed batch becomes padded rows (include/tiktoken_amd.h)."""
+    _fields_ = [("max_len", ctypes.c_uint32), ("stride", ctypes.c_uint32), ("width_multiple", ctypes.c_uint32), ("bos_id", ctypes.c_uint32), ("eos_id", ctypes.c_uint32),
+                ("pad_id", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+PAD_WINDOWS, PAD_KEEP_TAIL, PAD_LEFT, PAD_IDS16 = 1, 2, 4, 8
+
+
 def build(force: bool = False) -> str:
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     if force or not os.path.exists(_SO):
@@ -95,6 +104,10 @@ def lib() -> ctypes.CDLL:
         L.tk_encode_batch_rows.restype = i32
         L.tk_encode_batch_rows.argtypes = [vp, vp, vp, u64, i32, vp, u64, vp, u64, P(RowsSpec), P(vp), P(vp), P(vp), P(vp), P(vp), P(u64), P(u64), P(u64), P(u64),
                                            P(SpecialHit)]
+        L.tk_pad_batch_device.restype = i32
+        L.tk_pad_batch_device.argtypes = [vp, vp, u64, vp, u64, P(PadSpec), vp, P(vp), P(vp), P(vp), P(vp), P(vp), P(vp), P(u64), P(u64)]
+        L.tk_encode_batch_padded.restype = i32
+        L.tk_encode_batch_padded.argtypes = [vp, vp, vp, u64, i32, vp, u64, vp, u64, P(PadSpec), P(vp), P(vp), P(vp), P(vp), P(vp), P(vp), P(u64), P(u64), P(SpecialHit)]
         L.tk_decode_single_token_bytes.restype = i32
         L.tk_decode_single_token_bytes.argtypes = [vp, u32, P(vp), P(u64)]
         L.tk_n_tokens.restype = u64

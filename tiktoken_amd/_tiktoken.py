@@ -5,7 +5,8 @@ Same constructor and the same eleven methods, same exception types.  Two additiv
 `encode_batch_packed` and `pretokenize_packed`, expose the batch shape the GPU actually runs
 (one launch sequence per batch instead of one FFI call per document); `decode_batch_spans_packed`, `token_spans_device` and
 `encode_batch_spans_packed` give, for whole batches, where every token starts in its document (bytes and chars); `pack_rows_device` and
-`encode_batch_rows_packed` cut a batch into fixed-length training rows with document ids, positions and cu_seqlens; `train_bpe_packed`
+`encode_batch_rows_packed` cut a batch into fixed-length training rows with document ids, positions and cu_seqlens; `pad_batch_device` and
+`encode_batch_padded_packed` give one padded row per document (or overlapping windows) with an attention mask; `train_bpe_packed`
 trains a vocabulary: the merges of the reference's educational `bpe_train`, made on the device.  With `disallowed_special` the batch
 calls also search the text for those special tokens, on the device, and raise `DisallowedSpecialError`.
 """
@@ -159,6 +160,32 @@ class RowsDevice(NamedTuple):
     n_segs: int
     n_stream: int
     n_tail: int
+
+
+class PaddedBatch(NamedTuple):
+    """A batch as padded model inputs (tk_encode_batch_padded; the rule: include/tiktoken_amd.h): one row per document, truncated to
+    max_length -- or, with windows, as many rows as a long document needs, consecutive ones sharing `stride` tokens.  Row r belongs to
+    document row_doc[r], starts at its body token row_tok[r] and holds lengths[r] elements ([bos] body [eos]) where attention_mask is 1;
+    everywhere else input_ids is the pad id.  The rows of document d are doc_row[d] .. doc_row[d + 1]."""
+    input_ids: np.ndarray  # [R, W], uint32 or uint16
+    attention_mask: np.ndarray  # [R, W] uint8
+    lengths: np.ndarray  # uint32[R]
+    row_doc: np.ndarray  # uint32[R]
+    row_tok: np.ndarray  # uint32[R]
+    doc_row: np.ndarray  # uint32[n_docs + 1]
+
+
+class PaddedDevice(NamedTuple):
+    """`pad_batch_device`: device pointers (the core's buffers, valid until its next padded call) and the figures that size them:
+    input_ids / attention_mask hold n_rows * width elements, lengths / row_doc / row_tok n_rows, doc_row n_docs + 1."""
+    input_ids: int
+    attention_mask: int
+    lengths: int
+    row_doc: int
+    row_tok: int
+    doc_row: int
+    n_rows: int
+    width: int
 
 
 class DisallowedSpecialError(ValueError):
@@ -724,6 +751,95 @@ class CoreBPE:
         cu, row_seg = _take_u32(out[3], n_segs + 1), _take_u32(out[4], n_rows + 1)
         self._pad_needed(has_pad, drop_last, n_stream, L)
         return PackedRows(*[a[: n_rows * L].reshape(n_rows, L) for a in arrays], cu, row_seg, n_stream, *[a[n_rows * L:] for a in arrays])
+
+    # ------------------------------------------------------------------ padded model inputs (no reference counterpart: the host loop of its users)
+    @staticmethod
+    def _pad_spec(max_length: int, stride: int, windows: bool, keep: str, padding_side: str, pad_to_multiple_of, bos, eos, pad, dtype) -> "tuple[_lib.PadSpec, bool]":
+        """(the tk_pad_spec, whether the caller has named a pad id -- eos stands in for it)"""
+        dtype = np.dtype(dtype)
+        if dtype not in (np.dtype(np.uint32), np.dtype(np.uint16)):
+            raise ValueError("dtype must be uint32 or uint16")
+        if keep not in ("head", "tail"):
+            raise ValueError("keep must be 'head' or 'tail'")
+        if padding_side not in ("right", "left"):
+            raise ValueError("padding_side must be 'right' or 'left'")
+        for name, v in (("bos", bos), ("eos", eos), ("pad", pad)):
+            if v is not None and not 0 <= int(v) < 0xFFFFFFFF:
+                raise ValueError(f"{name} must be a token id below 2^32 - 1")
+        if pad_to_multiple_of is not None and int(pad_to_multiple_of) < 1:
+            raise ValueError("pad_to_multiple_of must be at least 1 (None: the fixed width max_length)")
+        for name, v in (("max_length", max_length), ("stride", stride), ("pad_to_multiple_of", pad_to_multiple_of or 0)):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise ValueError(f"{name} must fit 32 bits")
+        if pad is None:
+            pad = eos
+        none = _lib.ROWS_NO_TOKEN
+        flags = ((_lib.PAD_WINDOWS if windows else 0) | (_lib.PAD_KEEP_TAIL if keep == "tail" else 0) | (_lib.PAD_LEFT if padding_side == "left" else 0)
+                 | (_lib.PAD_IDS16 if dtype == np.uint16 else 0))
+        spec = _lib.PadSpec(int(max_length), int(stride), int(pad_to_multiple_of or 0), none if bos is None else int(bos), none if eos is None else int(eos),
+                            0 if pad is None else int(pad), flags)
+        return spec, pad is not None
+
+    @staticmethod
+    def _pad_id_needed(has_pad: bool, n_rows: int, width: int, lengths) -> None:
+        if not has_pad and n_rows and int(lengths.min()) < width:
+            raise ValueError(f"a row of {int(lengths.min())} ids does not fill the width of {width}: name a pad or eos id")
+
+    def pad_batch_device(self, d_tokens: int, n_tokens: int, d_tok_off: int, n_docs: int, *, max_length: int, stride: int = 0, windows: bool = False,
+                         keep: str = "head", padding_side: str = "right", pad_to_multiple_of: int | None = None, bos: int | None = None, eos: int | None = None,
+                         pad: int | None = None, dtype=np.uint32, stream: int = 0) -> PaddedDevice:
+        """Device-resident padded rows (tk_pad_batch_device): pointers to uint32 ids and uint64[n_docs + 1] token offsets on this core's
+        device -- e.g. what `encode_batch_device` returns, which stays intact --, one row per document cut to `max_length` (`keep`: its
+        head or its tail) or, with `windows`, further rows that overlap by `stride`; see `PaddedBatch` for the arrays.  `bos` / `eos`: ids
+        put before / after every row's body; `pad` (default: eos; one of the two must be named); `pad_to_multiple_of`: the width is the longest row rounded up to a
+        multiple of it, at most `max_length` (None: `max_length`); dtype uint16: 16-bit ids."""
+        self._one_device("pad_batch_device")
+        spec, has_pad = self._pad_spec(max_length, stride, windows, keep, padding_side, pad_to_multiple_of, bos, eos, pad, dtype)
+        if not has_pad:  # (the lengths stay on the device: whether a row needs padding cannot be seen from here)
+            raise ValueError("pad_batch_device: name a pad or eos id")
+        out = [ctypes.c_void_p() for _ in range(6)]
+        cnt = [ctypes.c_uint64() for _ in range(2)]
+        rc = self._L.tk_pad_batch_device(self._h, d_tokens or None, n_tokens, d_tok_off or None, n_docs, ctypes.byref(spec), stream or None,
+                                         *[ctypes.byref(x) for x in out], *[ctypes.byref(x) for x in cnt])
+        _lib.raise_for(rc)
+        return PaddedDevice(*[x.value or 0 for x in out], *[int(x.value) for x in cnt])
+
+    def encode_batch_padded_packed(self, blob: np.ndarray, doc_off: np.ndarray, allowed_special: AbstractSet[str] | None = None, *, disallowed_special=None,
+                                   max_length: int, stride: int = 0, windows: bool = False, keep: str = "head", padding_side: str = "right",
+                                   pad_to_multiple_of: int | None = None, bos: int | None = None, eos: int | None = None, pad: int | None = None,
+                                   dtype=np.uint32) -> PaddedBatch:
+        """`encode_batch_packed` with its result padded while the ids are on the device (tk_encode_batch_padded): only the padded arrays
+        come back.  The special-token arguments as in `encode_batch_packed`, the others as in `pad_batch_device`."""
+        self._one_device("encode_batch_padded_packed")
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        doc_off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+        _check_packed(blob, doc_off)
+        spec, has_pad = self._pad_spec(max_length, stride, windows, keep, padding_side, pad_to_multiple_of, bos, eos, pad, dtype)
+        n_docs = len(doc_off) - 1
+        src = blob if len(blob) else np.zeros(1, dtype=np.uint8)
+        if allowed_special is None:
+            ids, k, mode = np.zeros(1, dtype=np.uint32), 0, 0
+        else:
+            ids, k = self._allowed_ids(allowed_special)
+            mode = 1
+        dis, n_dis = self._disallowed_ids(disallowed_special)
+        hit = _lib.SpecialHit()
+        out = [ctypes.c_void_p() for _ in range(6)]
+        cnt = [ctypes.c_uint64() for _ in range(2)]
+        rc = self._L.tk_encode_batch_padded(self._h, src.ctypes.data, doc_off.ctypes.data, n_docs, mode, ids.ctypes.data, k, dis.ctypes.data, n_dis, ctypes.byref(spec),
+                                            *[ctypes.byref(x) for x in out], *[ctypes.byref(x) for x in cnt], ctypes.byref(hit))
+        if rc == _lib.TK_DISALLOWED_SPECIAL:
+            self._raise_hit(hit)
+        _lib.raise_for(rc)
+        n_rows, width = (int(x.value) for x in cnt)
+        input_ids = _take(out[0], n_rows * width, dtype).reshape(n_rows, width)
+        mask = _take_u8(out[1], n_rows * width)
+        if not mask.flags.writeable:  # (a small result comes as a view of a bytes object: the caller gets an array of its own, as for the ids)
+            mask = mask.copy()
+        mask = mask.reshape(n_rows, width)
+        lengths, row_doc, row_tok, doc_row = _take_u32(out[2], n_rows), _take_u32(out[3], n_rows), _take_u32(out[4], n_rows), _take_u32(out[5], n_docs + 1)
+        self._pad_id_needed(has_pad, n_rows, width, lengths)
+        return PaddedBatch(input_ids, mask, lengths, row_doc, row_tok, doc_row)
 
     # ------------------------------------------------------------------ training (tiktoken/_educational.py: bpe_train)
     def train_bpe_packed(self, blob: np.ndarray, doc_off: np.ndarray, vocab_size: int) -> tuple[np.ndarray, np.ndarray]:

@@ -264,6 +264,45 @@ class Encoding:
             raise RuntimeError(f"internal error: the device reported the disallowed special token {e.token!r} in document {e.doc} at byte "
                                f"{e.pos}, the host search finds none there") from e
 
+    def encode_ordinary_batch_padded(self, text: Sequence[str], max_length: int, *, stride: int = 0, windows: bool = False, keep: str = "head",
+                                     padding_side: str = "right", pad_to_multiple_of: int | None = None, bos: int | None = None, eos: int | None = None,
+                                     pad: int | None = None, dtype=np.uint32) -> "_tiktoken.PaddedBatch":
+        """A batch as padded model inputs, ignoring special tokens: every text is encoded and becomes one row `[bos] tokens [eos]` of at most
+        `max_length` elements -- its head, or with keep="tail" its tail --, or with `windows` as many rows as it needs, consecutive ones
+        sharing `stride` tokens; in one GPU call, only the padded arrays come back.  Returns a `PaddedBatch`: `input_ids` and
+        `attention_mask` as [R, W] arrays, `lengths`, `row_doc` (the text of a row), `row_tok` (the row's first token inside its text) and
+        `doc_row` (the first row of every text).  W is `max_length`, or with `pad_to_multiple_of` the longest row rounded up to a multiple of
+        it.  Rows are filled with `pad` (default: `eos`) on the right or, padding_side="left", on the left; ValueError if that is needed
+        and neither is given.  dtype uint16: 16-bit ids, for vocabularies that fit."""
+        blob, off = self._pack(text)
+        return self._core_bpe.encode_batch_padded_packed(blob, off, None, max_length=max_length, stride=stride, windows=windows, keep=keep, padding_side=padding_side,
+                                                         pad_to_multiple_of=pad_to_multiple_of, bos=bos, eos=eos, pad=pad, dtype=dtype)
+
+    def encode_batch_padded(self, text: Sequence[str], max_length: int, *, allowed_special: Literal["all"] | AbstractSet[str] = set(),  # noqa: B006
+                            disallowed_special: Literal["all"] | Collection[str] = "all", stride: int = 0, windows: bool = False, keep: str = "head",
+                            padding_side: str = "right", pad_to_multiple_of: int | None = None, bos: int | None = None, eos: int | None = None,
+                            pad: int | None = None, dtype=np.uint32) -> "_tiktoken.PaddedBatch":
+        """`encode_ordinary_batch_padded` with the special-token arguments of `encode` -- the policy, and the error, of `encode_batch_packed`."""
+        rows = dict(max_length=max_length, stride=stride, windows=windows, keep=keep, padding_side=padding_side, pad_to_multiple_of=pad_to_multiple_of, bos=bos, eos=eos,
+                    pad=pad, dtype=dtype)
+        allowed_special, disallowed_special = self._special_policy(allowed_special, disallowed_special)
+        if not disallowed_special:
+            blob, off = self._pack(text)
+            return self._core_bpe.encode_batch_padded_packed(blob, off, allowed_special, **rows)
+        if not isinstance(disallowed_special, frozenset):
+            disallowed_special = frozenset(disallowed_special)
+        blob, off, repaired = self._pack_repaired(text)
+        if repaired or not all(t in self._special_tokens for t in disallowed_special):  # (as encode_batch_packed: the host's search)
+            for t in text:
+                self._reject_disallowed(t, disallowed_special)
+            return self._core_bpe.encode_batch_padded_packed(blob, off, allowed_special, **rows)
+        try:
+            return self._core_bpe.encode_batch_padded_packed(blob, off, allowed_special, disallowed_special=disallowed_special, **rows)
+        except _tiktoken.DisallowedSpecialError as e:
+            self._reject_disallowed(text[e.doc], disallowed_special)
+            raise RuntimeError(f"internal error: the device reported the disallowed special token {e.token!r} in document {e.doc} at byte "
+                               f"{e.pos}, the host search finds none there") from e
+
     def encode_ordinary_batch(self, text: list[str], *, num_threads: int = 8) -> list[list[int]]:
         """Encode a list of strings, ignoring special tokens (one GPU batch; `num_threads` is kept for
         signature compatibility)."""

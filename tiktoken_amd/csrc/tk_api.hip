@@ -24,6 +24,7 @@
 #include "../../include/tiktoken_amd.h"
 #include "tk_decode.h"
 #include "tk_offsets.h"
+#include "tk_padded.h"
 #include "tk_rows.h"
 #include "tk_train.h"
 #include "tk_fused.h"
@@ -270,6 +271,9 @@ struct tk_core {
     // Training rows (tk_rows.h), apart from everything above: d_rows: ids, doc and pos of every position; d_rows_seg: the TK_ROWS_WORDS report
     // words, cu_seqlens, row_seg; d_rows_marks: document starts over the stream positions; d_rows_blk: segment starts per workgroup.
     Buf d_rows, d_rows_seg, d_rows_marks, d_rows_blk;
+    // Padded inputs (tk_padded.h), apart from everything above: d_pad: ids and mask of every position; d_pad_row: len, row_doc, row_tok of
+    // every row; d_pad_doc: doc_row; d_pad_cnt: the TK_PAD_WORDS report words and the doc_row a call counts in until it is accepted.
+    Buf d_pad, d_pad_row, d_pad_doc, d_pad_cnt;
     // Small calls (tk_k_small) do not take `mu`: the reference's normal use is several threads on one Encoding (core.py:175, a thread pool
     // over encode; lib.rs:232-238 keeps a regex per thread for it), and a small call needs nothing of the shared workspace -- a slot of its
     // own (page-locked text and result buffers the kernel reads and writes directly, merge scratch, a stream) is all.  A caller takes a
@@ -2652,6 +2656,17 @@ struct RowsView {  // device buffers of the core, valid until its next rows call
     uint64_t n_rows = 0, n_segs = 0, n_stream = 0, n_tail = 0, n_pos = 0;  // n_pos: positions written (M)
     bool ids16 = false;
 };
+// 16-bit ids (TK_ROWS_IDS16, TK_PAD_IDS16): every id of the vocabulary, the special tokens, bos_id, eos_id and pad_id must fit
+static int ids16_check(tk_core* c, uint32_t bos_id, uint32_t eos_id, uint32_t pad_id) {
+    uint32_t max_id = c->H.max_rank;
+    for (const auto& kv : c->H.spec_decoder) max_id = std::max(max_id, kv.first);
+    if (max_id > 0xFFFFu) return fail(TK_VALUE_ERROR, "16-bit ids: the vocabulary has ids up to " + std::to_string(max_id));
+    const uint32_t extra[3] = {bos_id, eos_id, pad_id};
+    const char* names[3] = {"bos_id", "eos_id", "pad_id"};
+    for (int i = 0; i < 3; ++i)
+        if (extra[i] > 0xFFFFu && (i == 2 || extra[i] != TK_ROWS_NO_TOKEN)) return fail(TK_VALUE_ERROR, std::string("16-bit ids: ") + names[i] + " does not fit");
+    return TK_OK;
+}
 // rows_run: the caller holds c->mu.  Everything but the number of segments follows from the arguments; the host waits once, at the end, for
 // that number and for what tk_k_rows_mark has to say about tok_off.
 // What of a tk_rows_spec can be refused without looking at the batch (the host-text entry asks before it encodes anything).
@@ -2659,15 +2674,7 @@ static int rows_check_spec(tk_core* c, const tk_rows_spec* spec) {
     if (!spec) return fail(TK_VALUE_ERROR, "null argument");
     if (spec->flags & ~(TK_ROWS_DROP_LAST | TK_ROWS_IDS16)) return fail(TK_VALUE_ERROR, "tk_rows_spec: unknown flag");
     if (!spec->seq_len) return fail(TK_VALUE_ERROR, "seq_len must be at least 1");
-    if (spec->flags & TK_ROWS_IDS16) {
-        uint32_t max_id = c->H.max_rank;
-        for (const auto& kv : c->H.spec_decoder) max_id = std::max(max_id, kv.first);
-        if (max_id > 0xFFFFu) return fail(TK_VALUE_ERROR, "16-bit ids: the vocabulary has ids up to " + std::to_string(max_id));
-        const uint32_t extra[3] = {spec->bos_id, spec->eos_id, spec->pad_id};
-        const char* names[3] = {"bos_id", "eos_id", "pad_id"};
-        for (int i = 0; i < 3; ++i)
-            if (extra[i] > 0xFFFFu && (i == 2 || extra[i] != TK_ROWS_NO_TOKEN)) return fail(TK_VALUE_ERROR, std::string("16-bit ids: ") + names[i] + " does not fit");
-    }
+    if (spec->flags & TK_ROWS_IDS16) TRY(ids16_check(c, spec->bos_id, spec->eos_id, spec->pad_id));
     return TK_OK;
 }
 static int rows_run(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n, const uint64_t* d_tok_off, uint64_t n_docs, const tk_rows_spec* spec, RowsView* out) {
@@ -2784,6 +2791,158 @@ extern "C" int tk_encode_batch_rows(tk_core* c, const uint8_t* utf8, const uint6
     *n_segs_out = v.n_segs;
     if (n_stream_out) *n_stream_out = v.n_stream;
     if (n_tail_out) *n_tail_out = v.n_tail;
+    return TK_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Padded model inputs (tk_padded.h): a packed batch on the device -> one row per document or overlapping windows, ids and mask as [R, W].
+// ------------------------------------------------------------------------------------------
+static_assert(TK_PAD_WINDOWS == TK_PADF_WINDOWS && TK_PAD_KEEP_TAIL == TK_PADF_KEEP_TAIL && TK_PAD_LEFT == TK_PADF_LEFT && TK_PAD_IDS16 == TK_PADF_IDS16, "tk_pad_spec flags");
+struct PadView {  // device buffers of the core, valid until its next padded call
+    void* ids = nullptr;
+    uint8_t* mask = nullptr;
+    uint32_t *len = nullptr, *row_doc = nullptr, *row_tok = nullptr, *doc_row = nullptr;
+    uint64_t n_rows = 0, width = 0;
+    bool ids16 = false;
+};
+static int pad_refusal(int why) {
+    switch (why) {
+        case 0: return TK_OK;
+        case 1: return fail(TK_VALUE_ERROR, "max_len must be at least 1 and leave room for a body token beside bos_id / eos_id");
+        case 2: return fail(TK_VALUE_ERROR, "stride must be less than max_len minus the bos / eos elements");
+        case 3: return fail(TK_VALUE_ERROR, "stride without TK_PAD_WINDOWS");
+        case 4: return fail(TK_VALUE_ERROR, "TK_PAD_KEEP_TAIL together with TK_PAD_WINDOWS");
+        case 5: return fail(TK_VALUE_ERROR, "too many documents: the document indices of the rows are 32-bit");
+        case 6: return fail(TK_VALUE_ERROR, "2^32 tokens or more: the token indices of the rows are 32-bit");
+        case 7: return fail(TK_VALUE_ERROR, "2^32 rows or more: the row indices are 32-bit");
+        default: return fail(TK_VALUE_ERROR, "rows times width reaches 2^32: the positions are 32-bit");
+    }
+}
+// What of a tk_pad_spec can be refused without looking at the batch (the host-text entry asks before it encodes anything).
+static int pad_check_spec(tk_core* c, const tk_pad_spec* spec) {
+    if (!spec) return fail(TK_VALUE_ERROR, "null argument");
+    if (spec->flags & ~(TK_PAD_WINDOWS | TK_PAD_KEEP_TAIL | TK_PAD_LEFT | TK_PAD_IDS16)) return fail(TK_VALUE_ERROR, "tk_pad_spec: unknown flag");
+    TkPad p;
+    TRY(pad_refusal(tk_pad_shape(0, 0, spec->max_len, spec->stride, spec->width_multiple, spec->bos_id, spec->eos_id, spec->pad_id, spec->flags, &p)));
+    if (spec->flags & TK_PAD_IDS16) TRY(ids16_check(c, spec->bos_id, spec->eos_id, spec->pad_id));
+    return TK_OK;
+}
+// pad_run: the caller holds c->mu.  The host waits twice: for R, the longest row and what tk_k_pad_count has to say about tok_off -- W and
+// the sizes of the outputs follow from them --, and at the end.  A call that is refused has written into d_pad_cnt only: the previous
+// result, doc_row included, stays whole.
+static int pad_run(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n, const uint64_t* d_tok_off, uint64_t n_docs, const tk_pad_spec* spec, PadView* out) {
+    TRY(pad_check_spec(c, spec));
+    TkPad p;
+    TRY(pad_refusal(tk_pad_shape(n, n_docs, spec->max_len, spec->stride, spec->width_multiple, spec->bos_id, spec->eos_id, spec->pad_id, spec->flags, &p)));
+    TRY(ensure(c->d_pad_cnt, TK_PAD_WORDS * 8 + (n_docs + 1) * 4));
+    unsigned long long* words = c->d_pad_cnt.as<unsigned long long>();
+    uint32_t* counted = (uint32_t*)(words + TK_PAD_WORDS);  // (the result's doc_row is written once the call is accepted)
+    HIPCHK(hipMemsetAsync(words + TK_PAD_BAD_OFF, 0xFF, 8, s));  // (all ones: none; tk_k_pad_scan writes the second word)
+    HIPCHK(hipMemsetAsync(words + TK_PAD_LONGEST, 0, 8, s));
+    TRY(timed(c, s, "tk_k_pad_count", [&] { hipLaunchKernelGGL(tk_k_pad_count, dim3(grid_for(n_docs + 1, 256, 4096)), dim3(256), 0, s, d_tok_off, p, counted, words); }));
+    TRY(timed(c, s, "tk_k_pad_scan", [&] { hipLaunchKernelGGL(tk_k_pad_scan, dim3(1), dim3(1024), 0, s, counted, n_docs, words); }));
+    unsigned long long got[TK_PAD_WORDS];
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(got, words, sizeof got, hipMemcpyDeviceToHost));  // (synchronous: nothing is on its way into `got` when this returns, however it returns)
+    if (got[TK_PAD_BAD_OFF] != ~0ull) {
+        const std::string d = std::to_string(got[TK_PAD_BAD_OFF] >> 2);
+        switch (got[TK_PAD_BAD_OFF] & 3u) {
+            case 1: return fail(TK_VALUE_ERROR, "tok_off[0] must be 0 (document " + d + ")");
+            case 2: return fail(TK_VALUE_ERROR, "tok_off must be non-decreasing: document " + d + " ends before it starts");
+            default: return fail(TK_VALUE_ERROR, "tok_off must end at n_tokens: document " + d + " ends elsewhere");
+        }
+    }
+    TRY(pad_refusal(tk_pad_size(&p, got[TK_PAD_NROWS], (uint32_t)got[TK_PAD_LONGEST])));
+    const bool ids16 = (spec->flags & TK_PAD_IDS16) != 0;
+    const uint64_t N = p.R * p.W, n8 = (N + 7) & ~7ull, ids_bytes = n8 * (ids16 ? 2 : 4), r4 = (p.R + 3) & ~3ull;  // (every array starts at a multiple of 16 bytes)
+    const uint64_t nb = (N + TK_DEC_BLOCK - 1) / TK_DEC_BLOCK;
+    TRY(ensure(c->d_pad, ids_bytes + n8 + 64));
+    TRY(ensure(c->d_pad_row, r4 * 12 + 64));
+    TRY(ensure(c->d_pad_doc, (n_docs + 1) * 4));
+    uint32_t* doc_row = c->d_pad_doc.as<uint32_t>();
+    HIPCHK(hipMemcpyAsync(doc_row, counted, (n_docs + 1) * 4, hipMemcpyDeviceToDevice, s));
+    out->ids = c->d_pad.p;
+    out->mask = (uint8_t*)c->d_pad.p + ids_bytes;
+    out->len = c->d_pad_row.as<uint32_t>();
+    out->row_doc = out->len + r4;
+    out->row_tok = out->row_doc + r4;
+    out->doc_row = doc_row;
+    out->n_rows = p.R;
+    out->width = p.W;
+    out->ids16 = ids16;
+    if (p.R)
+        TRY(timed(c, s, "tk_k_pad_rows", [&] {
+            hipLaunchKernelGGL(tk_k_pad_rows, dim3(grid_for(p.R, 256, 4096)), dim3(256), 0, s, d_tok_off, doc_row, p, out->len, out->row_doc, out->row_tok);
+        }));
+    if (nb)
+        TRY(timed(c, s, "tk_k_pad_write", [&] {
+            if (ids16) hipLaunchKernelGGL(tk_k_pad_write<true>, dim3((uint32_t)nb), dim3(256), 0, s, d_tok, d_tok_off, doc_row, p, out->ids, out->mask);
+            else hipLaunchKernelGGL(tk_k_pad_write<false>, dim3((uint32_t)nb), dim3(256), 0, s, d_tok, d_tok_off, doc_row, p, out->ids, out->mask);
+        }));
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    return TK_OK;
+}
+
+extern "C" int tk_pad_batch_device(tk_core* c, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_docs, const tk_pad_spec* spec, void* stream,
+                                   const void** d_ids_out, const uint8_t** d_mask_out, const uint32_t** d_len_out, const uint32_t** d_row_doc_out,
+                                   const uint32_t** d_row_tok_out, const uint32_t** d_doc_row_out, uint64_t* n_rows_out, uint64_t* width_out) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if (!d_tok_off || (n_tokens && !d_tokens) || !spec) return fail(TK_VALUE_ERROR, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    PadView v;
+    TRY(drained(c, [&] { return pad_run(c, stream ? (hipStream_t)stream : c->stream, (const uint32_t*)d_tokens, n_tokens, (const uint64_t*)d_tok_off, n_docs, spec, &v); }));
+    if (d_ids_out) *d_ids_out = v.ids;
+    if (d_mask_out) *d_mask_out = v.mask;
+    if (d_len_out) *d_len_out = v.len;
+    if (d_row_doc_out) *d_row_doc_out = v.row_doc;
+    if (d_row_tok_out) *d_row_tok_out = v.row_tok;
+    if (d_doc_row_out) *d_doc_row_out = v.doc_row;
+    if (n_rows_out) *n_rows_out = v.n_rows;
+    if (width_out) *width_out = v.width;
+    return TK_OK;
+}
+
+// tk_encode_batch (tk_encode_batch_checked with disallowed ids) with the padded rows of the tokens it has just produced: the passes run
+// over the ids while they are still on the device, and only the padded arrays travel back.
+extern "C" int tk_encode_batch_padded(tk_core* c, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special, const uint32_t* allowed_ids,
+                                      uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed, const tk_pad_spec* spec, void** ids_out,
+                                      uint8_t** mask_out, uint32_t** len_out, uint32_t** row_doc_out, uint32_t** row_tok_out, uint32_t** doc_row_out,
+                                      uint64_t* n_rows_out, uint64_t* width_out, tk_special_hit* hit) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if (!spec || !ids_out || !mask_out || !len_out || !row_doc_out || !row_tok_out || !doc_row_out || !n_rows_out || !width_out || (n_disallowed && !hit))
+        return fail(TK_VALUE_ERROR, "null argument");
+    TRY(pad_check_spec(c, spec));  // (before the encode, not after it)
+    const CheckArgs chk{disallowed_ids, n_disallowed, hit};
+    std::lock_guard<std::mutex> lk(c->mu);
+    uint64_t n = 0;
+    TRY(encode_batch_kept(c, utf8, doc_off, n_docs, use_special, allowed_ids, n_allowed, chk, &n));
+    PadView v;
+    TRY(drained(c, [&] { return pad_run(c, c->stream, c->out_tokens.as<uint32_t>(), n, c->out_tok_off.as<uint64_t>(), n_docs, spec, &v); }));
+    const uint64_t N = v.n_rows * v.width, ids_bytes = N * (v.ids16 ? 2 : 4);
+    HostResult<uint8_t> ids(result_alloc(ids_bytes)), mask(result_alloc(N));
+    HostResult<uint32_t> len(result_alloc(v.n_rows * 4)), rd(result_alloc(v.n_rows * 4)), rt(result_alloc(v.n_rows * 4)), dr(result_alloc((n_docs + 1) * 4));
+    if (!ids || !mask || !len || !rd || !rt || !dr) return fail(TK_RUNTIME_ERROR, "out of host memory");
+    if (N) {
+        HIPCHK(hipMemcpy(ids, v.ids, ids_bytes, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(mask, v.mask, N, hipMemcpyDeviceToHost));
+    }
+    if (v.n_rows) {
+        HIPCHK(hipMemcpy(len, v.len, v.n_rows * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(rd, v.row_doc, v.n_rows * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(rt, v.row_tok, v.n_rows * 4, hipMemcpyDeviceToHost));
+    }
+    HIPCHK(hipMemcpy(dr, v.doc_row, (n_docs + 1) * 4, hipMemcpyDeviceToHost));
+    *ids_out = ids.release();
+    *mask_out = mask.release();
+    *len_out = len.release();
+    *row_doc_out = rd.release();
+    *row_tok_out = rt.release();
+    *doc_row_out = dr.release();
+    *n_rows_out = v.n_rows;
+    *width_out = v.width;
     return TK_OK;
 }
 
