@@ -330,29 +330,45 @@ def pack(docs: list[bytes]):
 
 
 # ---------------------------------------------------------------- CPU simulation of the device logic
+HOSTSIM = os.path.join(ROOT, "tests", "hostsim")
+CSRC = os.path.join(ROOT, "tiktoken_amd", "csrc")
+
+
+def build_once(name: str, sources, flags) -> str:
+    """tests/hostsim/`name`, built by g++ from the .cpp files among `sources` unless it is newer than all of them (the headers are listed so
+    that an edit rebuilds); returns its path.  `sources`: file names in tests/hostsim or in tiktoken_amd/csrc.  Several pytest-xdist workers
+    may get here at once: one builds, into a file of its own, and renames."""
+    import fcntl
+
+    out = os.path.join(HOSTSIM, name)
+    srcs = [os.path.join(HOSTSIM if os.path.exists(os.path.join(HOSTSIM, f)) else CSRC, f) for f in sources]
+
+    def stale():
+        return not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(s) for s in srcs)
+
+    if stale():
+        with open(out + ".lock", "w") as lk:
+            fcntl.flock(lk, fcntl.LOCK_EX)
+            if stale():
+                tmp = f"{out}.{os.getpid()}.tmp"
+                subprocess.check_call(["g++", "-std=c++17", *flags, *[s for s in srcs if s.endswith(".cpp")], "-o", tmp])
+                os.replace(tmp, out)
+    return out
+
+
+def build_sim(so_name: str, sources, extra_flags=()) -> ctypes.CDLL:
+    """A host simulation as a shared library, built once; the caller sets the argtypes."""
+    return ctypes.CDLL(build_once(so_name, sources, ["-O2", "-fPIC", "-shared", *extra_flags]))
+
+
 _sim_lib = None
 
 
 def sim_lib():
     global _sim_lib
     if _sim_lib is None:
-        d = os.path.join(ROOT, "tests", "hostsim")
-        so = os.path.join(d, "libtk_hostsim.so")
-        srcs = [os.path.join(d, "tk_hostsim.cpp")] + [os.path.join(ROOT, "tiktoken_amd", "csrc", f)
-                                                       for f in ("tk_tables.cpp", "tk_pattern.cpp", "tk_regex.cpp", "tk_device.h", "tk_common.h", "tk_tables.h", "tk_chunk.h", "tk_regex.h",
-                                                                 "tk_regex_split.h", "tk_regex_host.h", "tk_regex_dfa.inc", "tk_mid_plan.h", "tk_regex_casefold.inc")]
-        def stale():
-            return not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs)
-
-        if stale():  # (several pytest-xdist workers may get here at once: one builds, into a file of its own, and renames)
-            import fcntl
-            with open(so + ".lock", "w") as lk:
-                fcntl.flock(lk, fcntl.LOCK_EX)
-                if stale():
-                    tmp = f"{so}.{os.getpid()}.tmp"
-                    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", srcs[0], srcs[1], srcs[2], srcs[3], "-o", tmp])
-                    os.replace(tmp, so)
-        L = ctypes.CDLL(so)
+        L = build_sim("libtk_hostsim.so", ("tk_hostsim.cpp", "tk_tables.cpp", "tk_pattern.cpp", "tk_regex.cpp", "tk_device.h", "tk_common.h", "tk_tables.h", "tk_chunk.h",
+                                           "tk_regex.h", "tk_regex_split.h", "tk_regex_host.h", "tk_regex_dfa.inc", "tk_mid_plan.h", "tk_regex_casefold.inc"), ("-pthread",))
         vp, u64 = ctypes.c_void_p, ctypes.c_uint64
         L.tks_create.restype = vp
         L.tks_create.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, ctypes.c_char_p, ctypes.c_char_p, u64]

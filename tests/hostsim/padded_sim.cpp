@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../tiktoken_amd/csrc/tk_padded_rule.h"
+#include "sim_readers.h"
 
 extern "C" {
 // The figures of a call: counts = {R, W}.  Returns 0; 1 .. 8: tk_pad_shape's / tk_pad_size's refusal; 16 + tk_rows_bad_key: tok_off is
@@ -15,15 +16,11 @@ int64_t padded_sim_count(uint64_t T, const uint64_t* tok_off, uint64_t n_docs, u
     const int refused = tk_pad_shape(T, n_docs, max_len, stride, width_multiple, bos, eos, pad, flags, &p);
     if (refused) return refused;
     // tk_k_pad_count
-    uint64_t bad = ~0ull;
+    unsigned long long bad = ~0ull;
     uint32_t longest = 0;
     for (uint64_t d = 0; d <= n_docs; ++d) {
-        const uint64_t a = tok_off[d], b = d < n_docs ? tok_off[d + 1] : p.n_tokens;
-        const uint32_t why = tk_rows_off_error(a, b, d, p.n_docs);
-        if (why) {
-            const uint64_t key = tk_rows_bad_key(d, p.n_docs, why);
-            bad = key < bad ? key : bad;
-        }
+        uint64_t a, b;
+        const uint32_t why = tk_rows_off_check(tok_off, d, p.n_docs, p.n_tokens, &a, &b, &bad);
         if (d < n_docs) {
             const uint64_t n = why ? 0 : b - a;
             doc_row[d] = (uint32_t)tk_pad_windows(p, n);
@@ -46,29 +43,6 @@ int64_t padded_sim_count(uint64_t T, const uint64_t* tok_off, uint64_t n_docs, u
     counts[1] = p.W;
     return too_big;
 }
-
-// The token array as tk_pad_lane reads it, every index checked: eight ids at once where their address is a multiple of 16, as on the device
-struct SimTokens {
-    const uint32_t* p;
-    uint64_t T;
-    bool* oob;
-    uint32_t one(uint64_t i) const {
-        if (i >= T) {
-            *oob = true;
-            return 0;
-        }
-        return p[i];
-    }
-    bool eight(uint64_t i, uint32_t out[8]) const {
-        if ((uintptr_t)(p + i) & 15u) return false;
-        if (i + 8 > T) {
-            *oob = true;
-            return false;
-        }
-        for (int j = 0; j < 8; ++j) out[j] = p[i + j];
-        return true;
-    }
-};
 
 // tk_k_pad_rows and tk_k_pad_write after padded_sim_count has accepted the call and left doc_row: the per-row pass statement by statement,
 // the write pass through tk_pad_block_docs and tk_pad_lane -- the functions the kernel itself calls -- with the kernel's stores.  ids /

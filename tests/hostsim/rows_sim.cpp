@@ -1,15 +1,16 @@
 // The row passes (tiktoken_amd/csrc/tk_rows.h) on the CPU: the plain C++ they are made of -- tk_rows_rule.h: the shape, the check of tok_off,
-// the document of a position, where an element comes from, the pos rule, what counts as a segment start -- compiled for the host and
-// driven the way the kernels drive it: lanes of eight positions, workgroups of `block` positions.  Test infrastructure only
-// (tests/test_rows_sim.py builds it).
+// the documents of a workgroup, a lane of the write pass -- compiled for the host and driven the way the kernels drive it: lanes of eight
+// positions, workgroups of `block` positions.  The write pass runs through tk_rows_block_docs and tk_rows_lane, the functions the kernel
+// itself calls.  Test infrastructure only (tests/test_rows_sim.py builds it).
 #include <stdint.h>
 
 #include <vector>
 
 #include "../../tiktoken_amd/csrc/tk_rows_rule.h"
+#include "sim_readers.h"
 
 extern "C" {
-// Statement by statement what the kernels do with the shared rule.  ids / doc / pos: room for M (+ 8), cu: n_docs + R + 4, row_seg: R + 1;
+// The passes in the kernels' order, with the kernels' stores.  ids / doc / pos: room for M (+ 8), cu: n_docs + R + 4, row_seg: R + 1;
 // counts: {R, n_segs, S, n_tail, M}.  Every access to tokens and tok_off is checked here: -1 if one lies out of bounds.
 // Returns 0; 1 .. 3: tk_rows_shape's refusal; 16 + tk_rows_bad_key: tok_off is refused.
 int64_t rows_sim(const uint32_t* tokens_in, uint64_t T, const uint64_t* tok_off_in, uint64_t n_docs, uint32_t L, uint32_t bos, uint32_t eos, uint32_t pad, int drop_last,
@@ -18,32 +19,14 @@ int64_t rows_sim(const uint32_t* tokens_in, uint64_t T, const uint64_t* tok_off_
     const int refused = tk_rows_shape(T, n_docs, L, bos, eos, pad, drop_last != 0, &r);
     if (refused) return refused;
     bool oob = false;
-    std::vector<uint64_t> off_copy(tok_off_in, tok_off_in + n_docs + 1);
-    const uint64_t* tok_off = off_copy.data();
-    auto off_at = [&](uint64_t d) -> uint64_t {
-        if (d > n_docs) {
-            oob = true;
-            return 0;
-        }
-        return tok_off[d];
-    };
-    auto token_at = [&](uint64_t t) -> uint32_t {
-        if (t >= T) {
-            oob = true;
-            return 0;
-        }
-        return tokens_in[t];
-    };
+    const SimOffsets tok_off{tok_off_in, n_docs, &oob};
+    const SimTokens tok{tokens_in, T, &oob};
     // tk_k_rows_mark
     std::vector<uint32_t> bm(r.M / 32 + 4, 0u);
-    uint64_t bad = ~0ull;
+    unsigned long long bad = ~0ull;
     for (uint64_t d = 0; d <= n_docs; ++d) {
-        const uint64_t a = off_at(d), b = d < n_docs ? off_at(d + 1) : r.n_tokens;
-        const uint32_t why = tk_rows_off_error(a, b, d, r.n_docs);
-        if (why) {
-            const uint64_t key = tk_rows_bad_key(d, r.n_docs, why);
-            bad = key < bad ? key : bad;
-        }
+        uint64_t a, b;
+        tk_rows_off_check(tok_off, d, r.n_docs, r.n_tokens, &a, &b, &bad);
         const uint64_t p = tk_rows_mark_at(a, b, d, r);
         if (p != ~0ull) {
             if ((p >> 5) >= bm.size()) return -1;
@@ -82,50 +65,21 @@ int64_t rows_sim(const uint32_t* tokens_in, uint64_t T, const uint64_t* tok_off_
     for (uint64_t blk = 0; blk < nb; ++blk) {
         const uint64_t b0 = blk * block;
         uint64_t d_lo = 0, d_hi = 0;
-        if (b0 < r.S) {
-            const uint64_t last = b0 + block <= r.S ? b0 + block - 1 : r.S - 1;
-            d_lo = tk_rows_last_doc(tok_off, 0, r.n_docs, r.k, b0);
-            d_hi = tk_rows_last_doc(tok_off, d_lo, r.n_docs, r.k, last) + 1;
-        }
+        tk_rows_block_docs(r, tok_off, b0, block, &d_lo, &d_hi);
+        if (d_hi > n_docs) return -1;
         uint64_t at = cnt[blk];  // (the lanes in order: the exclusive scan of their counts)
         for (uint32_t l = 0; l < lanes; ++l) {
             const uint64_t i0 = b0 + l * 8ull;
             uint32_t seg = 0, rows = 0;
             if (i0 < r.M) {
-                uint64_t d = 0, start = r.S, next = r.S;
-                if (i0 < r.S) {
-                    d = tk_rows_last_doc(tok_off, d_lo, d_hi, r.k, i0);
-                    start = tk_rows_out_off(off_at(d), d, r.k);
-                    next = tk_rows_out_off(off_at(d + 1), d + 1, r.k);
-                }
-                uint32_t rem = (uint32_t)i0 % r.seq_len;
-                for (int j = 0; j < 8; ++j) {
-                    const uint64_t p = i0 + j;
-                    uint32_t id = r.pad, dc = TK_ROWS_NONE, ps = 0;
-                    if (p < r.M) {
-                        if (p < r.S) {
-                            if (p >= next) {
-                                ++d;
-                                if (tk_rows_out_off(off_at(d + 1), d + 1, r.k) <= p) d = tk_rows_last_doc(tok_off, d + 1, d_hi, r.k, p);
-                                start = tk_rows_out_off(off_at(d), d, r.k);
-                                next = tk_rows_out_off(off_at(d + 1), d + 1, r.k);
-                            }
-                            uint64_t t = 0;
-                            const int src = tk_rows_source(r, d, start, next, p, &t);
-                            id = src == TK_ROWS_BOS ? r.bos : src == TK_ROWS_EOS ? r.eos : token_at(t);
-                            dc = (uint32_t)d;
-                        } else {
-                            start = r.S;
-                        }
-                        ps = tk_rows_pos(p, start, p - rem);
-                        seg |= (ps == 0u ? 1u : 0u) << j;
-                        rows |= (rem == 0u ? 1u : 0u) << j;
-                        ids_out[p] = id;
-                        doc_out[p] = dc;
-                        pos_out[p] = ps;
+                uint32_t id[8], dc[8], ps[8];
+                tk_rows_lane(r, tok, tok_off, d_lo, d_hi, i0, id, dc, ps, &seg, &rows);
+                for (uint32_t j = 0; j < 8; ++j)
+                    if (i0 + j < r.M) {
+                        ids_out[i0 + j] = id[j];
+                        doc_out[i0 + j] = dc[j];
+                        pos_out[i0 + j] = ps[j];
                     }
-                    if (++rem == r.seq_len) rem = 0u;
-                }
             }
             while (seg) {
                 const uint32_t j = (uint32_t)__builtin_ctz(seg);

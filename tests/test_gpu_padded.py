@@ -345,3 +345,63 @@ def test_remaining_refusals():
         several.pad_batch_device(*args, max_length=2, pad=0)
     with pytest.raises(ValueError, match="one device"):
         several.encode_batch_padded_packed(np.frombuffer(b"ab", np.uint8), np.array([0, 2], np.uint64), max_length=2)
+
+
+# ---------------------------------------------------------------- the id store the row passes and the padded passes share
+@pytest.mark.parametrize("dtype", [np.uint32, np.uint16])
+def test_last_lane_stores_three_ids_and_nothing_behind_them(dtype):
+    """2048 + 3 positions through both write passes: two workgroups, whose last lane writes three elements one by one where every other
+    lane writes eight at once.  The library's arrays hold a multiple of 8 elements each, so the five behind the result exist: they are
+    painted between two calls of the same shape and must come through the second one untouched."""
+    import torch
+
+    import rows_ref as rr
+
+    core = core_of()
+    rng = np.random.default_rng(2051)
+    n, n8 = BLOCK + 3, BLOCK + 8
+    ids_t, ids_np, paint = ("<i2", np.uint16, 0x5A5A) if np.dtype(dtype) == np.uint16 else ("<i4", np.uint32, 0x5A5A5A5A)
+
+    def behind(ptr, typestr, size, value=None):
+        """the five elements behind the n of an array of the library: painted, or read"""
+        t = torch.as_tensor(h._DevArray(ptr + n * size, n8 - n, typestr), device="cuda")
+        if value is not None:
+            t.fill_(value)
+            torch.cuda.synchronize()
+        return t.cpu().numpy()
+
+    # rows: no bos / eos and drop_last, so the positions written are the tokens
+    tokens, tok_off = rr.pack_docs([rng.integers(0, 50000, size=k).tolist() for k in (700, 0, 1340, 11)])
+    assert len(tokens) == n
+    d_tok, d_off = to_device(tokens, tok_off)
+    want = rr.rows_rule(tokens, tok_off, 64, None, None, 7, True)
+    seen = None
+    for call in range(2):
+        r = core.pack_rows_device(d_tok.data_ptr(), n, d_off.data_ptr(), len(tok_off) - 1, seq_len=64, pad=7, drop_last=True, dtype=dtype)
+        arrays = ((r.ids, ids_t, np.dtype(ids_np).itemsize, paint), (r.doc, "<i4", 4, 0x5A5A5A5A), (r.pos, "<i4", 4, 0x5A5A5A5A))
+        assert r.n_rows * 64 + r.n_tail == n and seen in (None, (r.ids, r.doc, r.pos))
+        seen = (r.ids, r.doc, r.pos)
+        for ptr, typestr, size, value in arrays:
+            if call == 0:
+                behind(ptr, typestr, size, value)
+            else:
+                assert (behind(ptr, typestr, size).astype(np.int64) & (256 ** size - 1) == value).all(), (typestr, ptr == r.ids)
+        assert np.array_equal(dev(r.ids, n, ids_t, ids_np), want.ids) and np.array_equal(h.dev_u32(r.doc, n), want.doc) and np.array_equal(h.dev_u32(r.pos, n), want.pos)
+        assert np.array_equal(h.dev_u32(r.cu_seqlens, r.n_segs + 1), want.cu_seqlens) and np.array_equal(h.dev_u32(r.row_seg, r.n_rows + 1), want.row_seg)
+
+    # padded: 7 rows of 293
+    tokens, tok_off = pr.pack_docs([rng.integers(0, 50000, size=k).tolist() for k in (293, 10, 300, 0, 1000, 294, 292)])
+    d_tok, d_off = to_device(tokens, tok_off)
+    want = pr.padded_rule(tokens, tok_off, 293, bos=None, eos=None, pad=7)
+    seen = None
+    for call in range(2):
+        r = core.pad_batch_device(d_tok.data_ptr(), len(tokens), d_off.data_ptr(), 7, max_length=293, pad=7, dtype=dtype)
+        assert r.n_rows * r.width == n and seen in (None, (r.input_ids, r.attention_mask))
+        seen = (r.input_ids, r.attention_mask)
+        for ptr, typestr, size, value in ((r.input_ids, ids_t, np.dtype(ids_np).itemsize, paint), (r.attention_mask, "|u1", 1, 0x5A)):
+            if call == 0:
+                behind(ptr, typestr, size, value)
+            else:
+                assert (behind(ptr, typestr, size).astype(np.int64) & (256 ** size - 1) == value).all(), (typestr, ptr == r.input_ids)
+        pr.same(pad_device(core, tokens, tok_off, 293, None, None, 7, dtype=dtype, held=(d_tok, d_off)), want, ("store", np.dtype(dtype).name))
+        assert (r.n_rows, r.width) == (7, 293)

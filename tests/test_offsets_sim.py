@@ -2,10 +2,7 @@
 (tiktoken_amd/csrc/tk_span_rule.h) for the host and drives it the way the kernels do.  Compared with restatements in Python of the
 reference's rule (Encoding.decode_with_offsets, tiktoken/core.py:312-335) and with Python's own strict UTF-8 decoder."""
 import ctypes
-import fcntl
-import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
@@ -20,22 +17,7 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        d = os.path.join(h.ROOT, "tests", "hostsim")
-        c = os.path.join(h.ROOT, "tiktoken_amd", "csrc")
-        so = os.path.join(d, "liboffsets_sim.so")
-        srcs = [os.path.join(d, "offsets_sim.cpp"), os.path.join(c, "tk_span_rule.h"), os.path.join(c, "tk_common.h")]
-
-        def stale():
-            return not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs)
-
-        if stale():  # (several workers may get here at once: one builds, into a file of its own, and renames)
-            with open(so + ".lock", "w") as lk:
-                fcntl.flock(lk, fcntl.LOCK_EX)
-                if stale():
-                    tmp = f"{so}.{os.getpid()}.tmp"
-                    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", srcs[0], "-o", tmp])
-                    os.replace(tmp, so)
-        L = ctypes.CDLL(so)
+        L = h.build_sim("liboffsets_sim.so", ("offsets_sim.cpp", "tk_span_rule.h", "tk_common.h"), ("-Wall",))
         vp, u64, u32 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32
         L.ofs_char_word.restype = u32
         L.ofs_char_word.argtypes = [ctypes.c_char_p, u32]

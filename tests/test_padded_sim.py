@@ -3,9 +3,6 @@
 2048; the write pass runs through tk_pad_lane, the function the kernel itself calls.  Compared with the numpy restatement of the rule in tests/padded_ref.py, which is written from the rule's description
 (include/tiktoken_amd.h), not from the kernels."""
 import ctypes
-import fcntl
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -21,22 +18,7 @@ WINDOWS, KEEP_TAIL, LEFT = 1, 2, 4
 def lib():
     global _lib
     if _lib is None:
-        d = os.path.join(h.ROOT, "tests", "hostsim")
-        c = os.path.join(h.ROOT, "tiktoken_amd", "csrc")
-        so = os.path.join(d, "libpadded_sim.so")
-        srcs = [os.path.join(d, "padded_sim.cpp"), os.path.join(c, "tk_padded_rule.h"), os.path.join(c, "tk_rows_rule.h"), os.path.join(c, "tk_common.h")]
-
-        def stale():
-            return not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs)
-
-        if stale():  # (several workers may get here at once: one builds, into a file of its own, and renames)
-            with open(so + ".lock", "w") as lk:
-                fcntl.flock(lk, fcntl.LOCK_EX)
-                if stale():
-                    tmp = f"{so}.{os.getpid()}.tmp"
-                    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Werror", srcs[0], "-o", tmp])
-                    os.replace(tmp, so)
-        L = ctypes.CDLL(so)
+        L = h.build_sim("libpadded_sim.so", ("padded_sim.cpp", "sim_readers.h", "tk_padded_rule.h", "tk_rows_rule.h", "tk_common.h"), ("-Wall", "-Werror",))
         vp, u64, u32 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32
         L.padded_sim_count.restype = ctypes.c_int64
         L.padded_sim_count.argtypes = [u64, vp, u64, u32, u32, u32, u32, u32, u32, u32, vp, vp]

@@ -1,10 +1,8 @@
 """The row passes (tk_rows.h) on the CPU: tests/hostsim/rows_sim.cpp compiles the plain C++ they are made of (tiktoken_amd/csrc/tk_rows_rule.h)
-for the host and drives it the way the kernels do -- lanes of eight positions, workgroups of 8, 16 and 2048.  Compared with the numpy
-restatement of the rule in tests/rows_ref.py, which is written from the rule's description (include/tiktoken_amd.h), not from the kernels."""
+for the host and drives it the way the kernels do -- lanes of eight positions, workgroups of 8, 16 and 2048; the write pass runs through
+tk_rows_lane, the function the kernel itself calls.  Compared with the numpy restatement of the rule in tests/rows_ref.py, which is written
+from the rule's description (include/tiktoken_amd.h), not from the kernels."""
 import ctypes
-import fcntl
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -19,22 +17,7 @@ BLOCKS = (8, 16, 2048)
 def lib():
     global _lib
     if _lib is None:
-        d = os.path.join(h.ROOT, "tests", "hostsim")
-        c = os.path.join(h.ROOT, "tiktoken_amd", "csrc")
-        so = os.path.join(d, "librows_sim.so")
-        srcs = [os.path.join(d, "rows_sim.cpp"), os.path.join(c, "tk_rows_rule.h"), os.path.join(c, "tk_common.h")]
-
-        def stale():
-            return not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs)
-
-        if stale():  # (several workers may get here at once: one builds, into a file of its own, and renames)
-            with open(so + ".lock", "w") as lk:
-                fcntl.flock(lk, fcntl.LOCK_EX)
-                if stale():
-                    tmp = f"{so}.{os.getpid()}.tmp"
-                    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Werror", srcs[0], "-o", tmp])
-                    os.replace(tmp, so)
-        L = ctypes.CDLL(so)
+        L = h.build_sim("librows_sim.so", ("rows_sim.cpp", "sim_readers.h", "tk_rows_rule.h", "tk_common.h"), ("-Wall", "-Werror",))
         vp, u64, u32 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32
         L.rows_sim.restype = ctypes.c_int64
         L.rows_sim.argtypes = [vp, u64, vp, u64, u32, u32, u32, u32, ctypes.c_int, u32, vp, vp, vp, vp, vp, vp]
@@ -137,6 +120,35 @@ def test_random_sweep():
             n = 0 if u < 0.25 else 1 if u < 0.35 else int(rng.choice([2, 7, 8, 9, 30, 200, 60, 2500 if rng.random() < 0.1 else 17]))
             docs.append(rng.integers(0, 60000, size=n).tolist())
         check(docs, [int(rng.choice([1, 2, 3, 8, 13, 64, 100, 2048]))], blocks=(8, 16, 2048), specials=[rr.SPECIALS[int(rng.integers(0, 4))]])
+
+
+def placed(tokens, shift):
+    """The tokens in memory of their own, the first one `shift` elements behind a multiple of 16 bytes."""
+    buf = np.zeros(len(tokens) + 8, np.uint32)
+    at = (-(buf.ctypes.data // 4)) % 4 + shift
+    buf[at: at + len(tokens)] = tokens
+    out = buf[at: at + len(tokens)]
+    assert out.ctypes.data % 16 == 4 * shift
+    return out
+
+
+@pytest.mark.parametrize("T", [7, 8, 9, 2048 + 5])
+def test_sixteen_byte_token_loads(T):
+    """Without bos and eos the stream is the token array, and a lane whose eight ids all exist fetches them as two 16-byte words where
+    the array's address allows it.  Both placements -- the array at a multiple of 16 bytes, where every such lane does, and one element
+    behind, where none does -- give the rule's rows, and no lane reads past n_tokens (rc -1 would say so): the last lane of T = 9 and of
+    2048 + 5 has fewer than eight ids left."""
+    rng = np.random.default_rng(T)
+    cuts = sorted(int(c) for c in rng.integers(0, T + 1, size=3))
+    tokens, tok_off = rr.pack_docs([d.tolist() for d in np.split(rng.integers(0, 60000, size=T), cuts)])
+    for L in (5, 8, T):
+        for drop_last in (False, True):
+            want = rr.rows_rule(tokens, tok_off, L, None, None, 7, drop_last)
+            for block in BLOCKS:
+                for shift in (0, 1):
+                    rc, got = run_sim(placed(tokens, shift), tok_off, L, None, None, 7, drop_last, block)
+                    assert rc == 0, (rc, L, drop_last, block, shift)
+                    same(got, want, (T, L, drop_last, block, shift))
 
 
 def test_refusals():

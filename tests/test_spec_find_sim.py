@@ -3,10 +3,7 @@ per-thread body (tk_special.h) for the host and runs it lane by lane over packed
 first disallowed special token starts -- is compared with the reference's own search (tiktoken/core.py:116-124): the first
 document, in order, in which `_special_token_regex(disallowed).search(text)` finds something, and the match's start as a byte offset."""
 import ctypes
-import fcntl
-import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
@@ -22,23 +19,8 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        d = os.path.join(h.ROOT, "tests", "hostsim")
-        c = os.path.join(h.ROOT, "tiktoken_amd", "csrc")
-        so = os.path.join(d, "libspec_find_sim.so")
-        srcs = [os.path.join(d, "spec_find_sim.cpp")] + [os.path.join(c, f) for f in ("tk_tables.cpp", "tk_pattern.cpp", "tk_regex.cpp", "tk_special.h", "tk_device.h",
-                                                                                      "tk_common.h", "tk_tables.h", "tk_regex.h", "tk_regex_host.h")]
-
-        def stale():
-            return not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs)
-
-        if stale():  # (several workers may get here at once: one builds, into a file of its own, and renames)
-            with open(so + ".lock", "w") as lk:
-                fcntl.flock(lk, fcntl.LOCK_EX)
-                if stale():
-                    tmp = f"{so}.{os.getpid()}.tmp"
-                    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread"] + srcs[:4] + ["-o", tmp])
-                    os.replace(tmp, so)
-        L = ctypes.CDLL(so)
+        L = h.build_sim("libspec_find_sim.so", ("spec_find_sim.cpp", "tk_tables.cpp", "tk_pattern.cpp", "tk_regex.cpp", "tk_special.h", "tk_device.h", "tk_common.h",
+                                                "tk_tables.h", "tk_regex.h", "tk_regex_host.h"), ("-pthread",))
         vp, u64 = ctypes.c_void_p, ctypes.c_uint64
         L.sfs_create.restype = vp
         L.sfs_create.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, ctypes.c_char_p, ctypes.c_char_p, u64]

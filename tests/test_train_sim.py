@@ -4,8 +4,6 @@ symbol in workgroups of 4, 64 and 256 for the step.  Input: words with weights; 
 from the Python restatement of the rule in tests/train_ref.py.  The same case list runs a second time through the driver built as a
 program of its own with the address and undefined-behaviour sanitizers (host code only: nothing of it is loaded into Python)."""
 import ctypes
-import fcntl
-import os
 import random
 import struct
 import subprocess
@@ -19,29 +17,13 @@ import train_ref as tr
 _lib = None
 BLOCKS = (4, 64, 256)
 SEED = 0x243F6A8885A308D3
-D = os.path.join(h.ROOT, "tests", "hostsim")
-C = os.path.join(h.ROOT, "tiktoken_amd", "csrc")
-SRCS = [os.path.join(D, "train_sim.cpp"), os.path.join(C, "tk_train_rule.h"), os.path.join(C, "tk_common.h")]
-
-
-def _build(out, flags):
-    def stale():
-        return not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(s) for s in SRCS)
-
-    if stale():  # (several workers may get here at once: one builds, into a file of its own, and renames)
-        with open(out + ".lock", "w") as lk:
-            fcntl.flock(lk, fcntl.LOCK_EX)
-            if stale():
-                tmp = f"{out}.{os.getpid()}.tmp"
-                subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", *flags, SRCS[0], "-o", tmp])
-                os.replace(tmp, out)
-    return out
+SRCS = ("train_sim.cpp", "tk_train_rule.h", "tk_common.h")
 
 
 def lib():
     global _lib
     if _lib is None:
-        L = ctypes.CDLL(_build(os.path.join(D, "libtrain_sim.so"), ["-O2", "-fPIC", "-shared"]))
+        L = h.build_sim("libtrain_sim.so", SRCS, ("-Wall", "-Werror"))
         vp, u64, u32 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32
         L.train_sim.restype = ctypes.c_int64
         L.train_sim.argtypes = [vp, vp, vp, vp, u64, u64, u64, u32, u32, ctypes.c_int, vp, vp, vp, vp, vp, u64, vp]
@@ -191,7 +173,7 @@ def test_table_too_small_is_reported():
 def test_case_list_under_sanitizers(tmp_path):
     """The driver as a program of its own, built with -fsanitize=address,undefined, on the same case list: it must run clean and give the
     same results."""
-    exe = _build(os.path.join(D, "train_sim_san"), ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DTRAIN_SIM_MAIN"])
+    exe = h.build_once("train_sim_san", SRCS, ["-Wall", "-Werror", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DTRAIN_SIM_MAIN"])
     todo = [c for b in BLOCKS for c in cases(b)] + table_cases()
     src, dst = tmp_path / "cases.bin", tmp_path / "results.bin"
     with open(src, "wb") as f:

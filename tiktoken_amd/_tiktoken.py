@@ -308,6 +308,24 @@ class CoreBPE:
             raise RuntimeError(f"internal error: the library reported special token id {hit.id} of {hit.len} bytes, which is not registered")
         raise DisallowedSpecialError(int(hit.doc), int(hit.pos), token)
 
+    def _batch_args(self, blob, doc_off, allowed_special, disallowed_special):
+        """A packed batch and its special-token arguments as the tk_encode_batch* entries take them: (the arguments from utf8 to n_allowed,
+        disallowed_ids and n_disallowed, n_docs, the arrays behind the pointers -- to be kept until the call is over)."""
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        doc_off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+        _check_packed(blob, doc_off)
+        n_docs = len(doc_off) - 1
+        src = blob if len(blob) else np.zeros(1, dtype=np.uint8)
+        ids, k = (np.zeros(1, dtype=np.uint32), 0) if allowed_special is None else self._allowed_ids(allowed_special)
+        dis, n_dis = self._disallowed_ids(disallowed_special)
+        return ((src.ctypes.data, doc_off.ctypes.data, n_docs, 0 if allowed_special is None else 1, ids.ctypes.data, k), (dis.ctypes.data, n_dis), n_docs,
+                (src, doc_off, ids, dis))
+
+    def _raise_for(self, rc: int, hit: "_lib.SpecialHit") -> None:
+        if rc == _lib.TK_DISALLOWED_SPECIAL:
+            self._raise_hit(hit)
+        _lib.raise_for(rc)
+
     @staticmethod
     def _as_u8(data: bytes) -> np.ndarray:
         return np.frombuffer(data, dtype=np.uint8) if data else np.zeros(1, dtype=np.uint8)
@@ -344,36 +362,20 @@ class CoreBPE:
         Returns (tokens uint32[T], tok_off uint64[n+1]).
         `disallowed_special`: special-token strings (or "all") the text must not spell -- searched for on the device in the same call
         (tk_encode_batch_checked); DisallowedSpecialError names the first occurrence.  None or empty: no search."""
-        blob = np.ascontiguousarray(blob, dtype=np.uint8)
-        doc_off = np.ascontiguousarray(doc_off, dtype=np.uint64)
-        _check_packed(blob, doc_off)
-        n_docs = len(doc_off) - 1
+        text, dis, n_docs, _keep = self._batch_args(blob, doc_off, allowed_special, disallowed_special)
         tok_off = np.empty(n_docs + 1, dtype=np.uint64)
-        out, n = ctypes.c_void_p(), ctypes.c_uint64()
-        src = blob if len(blob) else np.zeros(1, dtype=np.uint8)
-        if allowed_special is None:
-            ids, k, mode = np.zeros(1, dtype=np.uint32), 0, 0
+        out, n, hit = ctypes.c_void_p(), ctypes.c_uint64(), _lib.SpecialHit()
+        res = (ctypes.byref(out), ctypes.byref(n), tok_off.ctypes.data)
+        grouped = self._group is not None and n_docs > 1
+        if dis[1] and grouped:
+            rc = self._L.tk_group_encode_batch_checked(self._group, *text, *res, *dis, ctypes.byref(hit))
+        elif dis[1]:
+            rc = self._L.tk_encode_batch_checked(self._h, *text, *dis, *res, ctypes.byref(hit))
+        elif grouped:
+            rc = self._L.tk_group_encode_batch(self._group, *text, *res)
         else:
-            ids, k = self._allowed_ids(allowed_special)
-            mode = 1
-        dis, n_dis = self._disallowed_ids(disallowed_special)
-        if n_dis:
-            hit = _lib.SpecialHit()
-            if self._group is not None and n_docs > 1:
-                rc = self._L.tk_group_encode_batch_checked(self._group, src.ctypes.data, doc_off.ctypes.data, n_docs, mode, ids.ctypes.data, k,
-                                                           ctypes.byref(out), ctypes.byref(n), tok_off.ctypes.data, dis.ctypes.data, n_dis, ctypes.byref(hit))
-            else:
-                rc = self._L.tk_encode_batch_checked(self._h, src.ctypes.data, doc_off.ctypes.data, n_docs, mode, ids.ctypes.data, k, dis.ctypes.data, n_dis,
-                                                     ctypes.byref(out), ctypes.byref(n), tok_off.ctypes.data, ctypes.byref(hit))
-            if rc == _lib.TK_DISALLOWED_SPECIAL:
-                self._raise_hit(hit)
-        elif self._group is not None and n_docs > 1:
-            rc = self._L.tk_group_encode_batch(self._group, src.ctypes.data, doc_off.ctypes.data, n_docs, mode, ids.ctypes.data, k,
-                                               ctypes.byref(out), ctypes.byref(n), tok_off.ctypes.data)
-        else:
-            rc = self._L.tk_encode_batch(self._h, src.ctypes.data, doc_off.ctypes.data, n_docs, mode, ids.ctypes.data, k,
-                                         ctypes.byref(out), ctypes.byref(n), tok_off.ctypes.data)
-        _lib.raise_for(rc)
+            rc = self._L.tk_encode_batch(self._h, *text, *res)
+        self._raise_for(rc, hit)
         return _take_u32(out, n.value), tok_off
 
     def encode_batch_gathered(self, blob: np.ndarray, doc_off: np.ndarray, allowed_special: AbstractSet[str] | None = None):
@@ -657,45 +659,38 @@ class CoreBPE:
         (tokens uint32[T], tok_off uint64[n+1], byte_start uint32[T], char_start uint32[T]); token i of document d is
         blob[doc_off[d] + byte_start[i] : ...].  ValueError naming the document where a pat_str leaves characters of the text unmatched."""
         self._one_device("encode_batch_spans_packed")
-        blob = np.ascontiguousarray(blob, dtype=np.uint8)
-        doc_off = np.ascontiguousarray(doc_off, dtype=np.uint64)
-        _check_packed(blob, doc_off)
-        n_docs = len(doc_off) - 1
+        text, dis, n_docs, _keep = self._batch_args(blob, doc_off, allowed_special, disallowed_special)
         tok_off = np.empty(n_docs + 1, dtype=np.uint64)
-        out, n, bs, cs = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_void_p(), ctypes.c_void_p()
-        src = blob if len(blob) else np.zeros(1, dtype=np.uint8)
-        if allowed_special is None:
-            ids, k, mode = np.zeros(1, dtype=np.uint32), 0, 0
-        else:
-            ids, k = self._allowed_ids(allowed_special)
-            mode = 1
-        dis, n_dis = self._disallowed_ids(disallowed_special)
-        hit = _lib.SpecialHit()
-        rc = self._L.tk_encode_batch_spans(self._h, src.ctypes.data, doc_off.ctypes.data, n_docs, mode, ids.ctypes.data, k, dis.ctypes.data, n_dis,
-                                           ctypes.byref(out), ctypes.byref(n), tok_off.ctypes.data, ctypes.byref(bs), ctypes.byref(cs), ctypes.byref(hit))
-        if rc == _lib.TK_DISALLOWED_SPECIAL:
-            self._raise_hit(hit)
-        _lib.raise_for(rc)
+        out, n, bs, cs, hit = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_void_p(), ctypes.c_void_p(), _lib.SpecialHit()
+        rc = self._L.tk_encode_batch_spans(self._h, *text, *dis, ctypes.byref(out), ctypes.byref(n), tok_off.ctypes.data, ctypes.byref(bs), ctypes.byref(cs),
+                                           ctypes.byref(hit))
+        self._raise_for(rc, hit)
         return _take_u32(out, n.value), tok_off, _take_u32(bs, n.value), _take_u32(cs, n.value)
 
     # ------------------------------------------------------------------ training rows (no reference counterpart: the host loop of its users)
     @staticmethod
-    def _rows_spec(seq_len: int, bos, eos, pad, drop_last: bool, dtype) -> "tuple[_lib.RowsSpec, bool]":
-        """(the tk_rows_spec, whether the caller has named a pad id -- eos stands in for it)"""
+    def _ids_spec(bos, eos, pad, dtype) -> "tuple[int, int, int, bool, bool]":
+        """What tk_rows_spec and tk_pad_spec share: (bos_id, eos_id, pad_id, whether the caller has named a pad id -- eos stands in for it,
+        whether the ids are 16-bit)"""
         dtype = np.dtype(dtype)
         if dtype not in (np.dtype(np.uint32), np.dtype(np.uint16)):
             raise ValueError("dtype must be uint32 or uint16")
         for name, v in (("bos", bos), ("eos", eos), ("pad", pad)):
             if v is not None and not 0 <= int(v) < 0xFFFFFFFF:
                 raise ValueError(f"{name} must be a token id below 2^32 - 1")
-        if not 0 <= int(seq_len) <= 0xFFFFFFFF:
-            raise ValueError("seq_len must fit 32 bits")
         if pad is None:
             pad = eos
         none = _lib.ROWS_NO_TOKEN
-        flags = (_lib.ROWS_DROP_LAST if drop_last else 0) | (_lib.ROWS_IDS16 if dtype == np.uint16 else 0)
-        spec = _lib.RowsSpec(int(seq_len), none if bos is None else int(bos), none if eos is None else int(eos), 0 if pad is None else int(pad), flags)
-        return spec, pad is not None
+        return none if bos is None else int(bos), none if eos is None else int(eos), 0 if pad is None else int(pad), pad is not None, dtype == np.uint16
+
+    @classmethod
+    def _rows_spec(cls, seq_len: int, bos, eos, pad, drop_last: bool, dtype) -> "tuple[_lib.RowsSpec, bool]":
+        """(the tk_rows_spec, whether the caller has named a pad id)"""
+        bos_id, eos_id, pad_id, has_pad, ids16 = cls._ids_spec(bos, eos, pad, dtype)
+        if not 0 <= int(seq_len) <= 0xFFFFFFFF:
+            raise ValueError("seq_len must fit 32 bits")
+        flags = (_lib.ROWS_DROP_LAST if drop_last else 0) | (_lib.ROWS_IDS16 if ids16 else 0)
+        return _lib.RowsSpec(int(seq_len), bos_id, eos_id, pad_id, flags), has_pad
 
     @staticmethod
     def _pad_needed(has_pad: bool, drop_last: bool, n_stream: int, seq_len: int) -> None:
@@ -724,26 +719,13 @@ class CoreBPE:
         """`encode_batch_packed` with its result cut into training rows while the ids are on the device (tk_encode_batch_rows): only the row
         arrays come back.  The special-token arguments as in `encode_batch_packed`, the others as in `pack_rows_device`."""
         self._one_device("encode_batch_rows_packed")
-        blob = np.ascontiguousarray(blob, dtype=np.uint8)
-        doc_off = np.ascontiguousarray(doc_off, dtype=np.uint64)
-        _check_packed(blob, doc_off)
+        text, dis, n_docs, _keep = self._batch_args(blob, doc_off, allowed_special, disallowed_special)
         spec, has_pad = self._rows_spec(seq_len, bos, eos, pad, drop_last, dtype)
-        n_docs = len(doc_off) - 1
-        src = blob if len(blob) else np.zeros(1, dtype=np.uint8)
-        if allowed_special is None:
-            ids, k, mode = np.zeros(1, dtype=np.uint32), 0, 0
-        else:
-            ids, k = self._allowed_ids(allowed_special)
-            mode = 1
-        dis, n_dis = self._disallowed_ids(disallowed_special)
         hit = _lib.SpecialHit()
         out = [ctypes.c_void_p() for _ in range(5)]
         cnt = [ctypes.c_uint64() for _ in range(4)]
-        rc = self._L.tk_encode_batch_rows(self._h, src.ctypes.data, doc_off.ctypes.data, n_docs, mode, ids.ctypes.data, k, dis.ctypes.data, n_dis, ctypes.byref(spec),
-                                          *[ctypes.byref(x) for x in out], *[ctypes.byref(x) for x in cnt], ctypes.byref(hit))
-        if rc == _lib.TK_DISALLOWED_SPECIAL:
-            self._raise_hit(hit)
-        _lib.raise_for(rc)
+        rc = self._L.tk_encode_batch_rows(self._h, *text, *dis, ctypes.byref(spec), *[ctypes.byref(x) for x in out], *[ctypes.byref(x) for x in cnt], ctypes.byref(hit))
+        self._raise_for(rc, hit)
         n_rows, n_segs, n_stream, n_tail = (int(x.value) for x in cnt)
         L = spec.seq_len
         m = n_rows * L + n_tail
@@ -753,32 +735,22 @@ class CoreBPE:
         return PackedRows(*[a[: n_rows * L].reshape(n_rows, L) for a in arrays], cu, row_seg, n_stream, *[a[n_rows * L:] for a in arrays])
 
     # ------------------------------------------------------------------ padded model inputs (no reference counterpart: the host loop of its users)
-    @staticmethod
-    def _pad_spec(max_length: int, stride: int, windows: bool, keep: str, padding_side: str, pad_to_multiple_of, bos, eos, pad, dtype) -> "tuple[_lib.PadSpec, bool]":
-        """(the tk_pad_spec, whether the caller has named a pad id -- eos stands in for it)"""
-        dtype = np.dtype(dtype)
-        if dtype not in (np.dtype(np.uint32), np.dtype(np.uint16)):
-            raise ValueError("dtype must be uint32 or uint16")
+    @classmethod
+    def _pad_spec(cls, max_length: int, stride: int, windows: bool, keep: str, padding_side: str, pad_to_multiple_of, bos, eos, pad, dtype) -> "tuple[_lib.PadSpec, bool]":
+        """(the tk_pad_spec, whether the caller has named a pad id)"""
+        bos_id, eos_id, pad_id, has_pad, ids16 = cls._ids_spec(bos, eos, pad, dtype)
         if keep not in ("head", "tail"):
             raise ValueError("keep must be 'head' or 'tail'")
         if padding_side not in ("right", "left"):
             raise ValueError("padding_side must be 'right' or 'left'")
-        for name, v in (("bos", bos), ("eos", eos), ("pad", pad)):
-            if v is not None and not 0 <= int(v) < 0xFFFFFFFF:
-                raise ValueError(f"{name} must be a token id below 2^32 - 1")
         if pad_to_multiple_of is not None and int(pad_to_multiple_of) < 1:
             raise ValueError("pad_to_multiple_of must be at least 1 (None: the fixed width max_length)")
         for name, v in (("max_length", max_length), ("stride", stride), ("pad_to_multiple_of", pad_to_multiple_of or 0)):
             if not 0 <= int(v) <= 0xFFFFFFFF:
                 raise ValueError(f"{name} must fit 32 bits")
-        if pad is None:
-            pad = eos
-        none = _lib.ROWS_NO_TOKEN
         flags = ((_lib.PAD_WINDOWS if windows else 0) | (_lib.PAD_KEEP_TAIL if keep == "tail" else 0) | (_lib.PAD_LEFT if padding_side == "left" else 0)
-                 | (_lib.PAD_IDS16 if dtype == np.uint16 else 0))
-        spec = _lib.PadSpec(int(max_length), int(stride), int(pad_to_multiple_of or 0), none if bos is None else int(bos), none if eos is None else int(eos),
-                            0 if pad is None else int(pad), flags)
-        return spec, pad is not None
+                 | (_lib.PAD_IDS16 if ids16 else 0))
+        return _lib.PadSpec(int(max_length), int(stride), int(pad_to_multiple_of or 0), bos_id, eos_id, pad_id, flags), has_pad
 
     @staticmethod
     def _pad_id_needed(has_pad: bool, n_rows: int, width: int, lengths) -> None:
@@ -811,26 +783,13 @@ class CoreBPE:
         """`encode_batch_packed` with its result padded while the ids are on the device (tk_encode_batch_padded): only the padded arrays
         come back.  The special-token arguments as in `encode_batch_packed`, the others as in `pad_batch_device`."""
         self._one_device("encode_batch_padded_packed")
-        blob = np.ascontiguousarray(blob, dtype=np.uint8)
-        doc_off = np.ascontiguousarray(doc_off, dtype=np.uint64)
-        _check_packed(blob, doc_off)
+        text, dis, n_docs, _keep = self._batch_args(blob, doc_off, allowed_special, disallowed_special)
         spec, has_pad = self._pad_spec(max_length, stride, windows, keep, padding_side, pad_to_multiple_of, bos, eos, pad, dtype)
-        n_docs = len(doc_off) - 1
-        src = blob if len(blob) else np.zeros(1, dtype=np.uint8)
-        if allowed_special is None:
-            ids, k, mode = np.zeros(1, dtype=np.uint32), 0, 0
-        else:
-            ids, k = self._allowed_ids(allowed_special)
-            mode = 1
-        dis, n_dis = self._disallowed_ids(disallowed_special)
         hit = _lib.SpecialHit()
         out = [ctypes.c_void_p() for _ in range(6)]
         cnt = [ctypes.c_uint64() for _ in range(2)]
-        rc = self._L.tk_encode_batch_padded(self._h, src.ctypes.data, doc_off.ctypes.data, n_docs, mode, ids.ctypes.data, k, dis.ctypes.data, n_dis, ctypes.byref(spec),
-                                            *[ctypes.byref(x) for x in out], *[ctypes.byref(x) for x in cnt], ctypes.byref(hit))
-        if rc == _lib.TK_DISALLOWED_SPECIAL:
-            self._raise_hit(hit)
-        _lib.raise_for(rc)
+        rc = self._L.tk_encode_batch_padded(self._h, *text, *dis, ctypes.byref(spec), *[ctypes.byref(x) for x in out], *[ctypes.byref(x) for x in cnt], ctypes.byref(hit))
+        self._raise_for(rc, hit)
         n_rows, width = (int(x.value) for x in cnt)
         input_ids = _take(out[0], n_rows * width, dtype).reshape(n_rows, width)
         mask = _take_u8(out[1], n_rows * width)

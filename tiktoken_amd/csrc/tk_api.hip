@@ -1658,6 +1658,14 @@ struct Feed {
 
 // a result array on its way to the caller: page-locked from a MiB on (the copy back runs at the link's rate)
 static void* result_alloc(size_t bytes) { return bytes >= (1u << 20) ? pinned_get(bytes) : malloc(bytes ? bytes : 1); }
+// ... made for n elements that are on the device and filled with them (the caller lets go of it once every array of its call is there)
+template <class T>
+static int result_from_device(HostResult<T>& host, const void* d_src, uint64_t n) {
+    host = HostResult<T>(result_alloc(n * sizeof(T)));
+    if (!host) return fail(TK_RUNTIME_ERROR, "out of host memory");
+    if (n) HIPCHK(hipMemcpy(host, d_src, n * sizeof(T), hipMemcpyDeviceToHost));
+    return TK_OK;
+}
 // A result array that is filled while its final size is not known yet, sized by the density so far: `done` of the call's `all` input units
 // have made `need` elements (`filled` of them are in the array or on their way into it on c->cs_d2h, the others follow once this returns).
 // An array that turns out too small is replaced by one of the new estimate and what it holds is copied over.
@@ -1989,9 +1997,8 @@ static int encode_batch_impl(tk_core* c, const uint8_t* utf8, const uint64_t* do
             *n_tokens_out = total;
             return TK_OK;
         }
-        HostResult<uint32_t> host(result_alloc(total * 4));
-        if (!host) return fail(TK_RUNTIME_ERROR, "out of host memory");
-        if (total) HIPCHK(hipMemcpy(host, c->out_tokens.p, total * 4, hipMemcpyDeviceToHost));
+        HostResult<uint32_t> host;
+        TRY(result_from_device(host, c->out_tokens.p, total));
         if (tok_off_out) HIPCHK(hipMemcpy(tok_off_out, c->out_tok_off.p, (n_docs + 1) * 8, hipMemcpyDeviceToHost));
         *tokens_out = host.release();
         *n_tokens_out = total;
@@ -2042,6 +2049,22 @@ static int encode_batch_kept(tk_core* c, const uint8_t* utf8, const uint64_t* do
                              uint64_t n_allowed, const CheckArgs& chk, uint64_t* n_tokens_out) {
     return encode_batch_impl(c, utf8, doc_off, n_docs, use_special, allowed_ids, n_allowed, nullptr, n_tokens_out, nullptr, /* device_result */ true, /* no_small */ true,
                              chk.n ? &chk : nullptr, /* locked */ true);
+}
+// The host-text entries that run a pass over the ids of the batch they have just encoded (tk_encode_batch_spans, _rows, _padded), under
+// the core's mutex from the encode to the end: `outs`: the entry's own pointers are there; check(): what of its arguments can be refused
+// before anything is encoded; pass(n): the device pass over c->out_tokens (n ids) and c->out_tok_off; tail(n): its results to the caller.
+template <class Check, class Pass, class Tail>
+static int encode_batch_pass(tk_core* c, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special, const uint32_t* allowed_ids, uint64_t n_allowed,
+                             const uint32_t* disallowed_ids, uint64_t n_disallowed, tk_special_hit* hit, bool outs, Check&& check, Pass&& pass, Tail&& tail) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if (!outs || (n_disallowed && !hit)) return fail(TK_VALUE_ERROR, "null argument");
+    TRY(check());
+    const CheckArgs chk{disallowed_ids, n_disallowed, hit};
+    std::lock_guard<std::mutex> lk(c->mu);
+    uint64_t n = 0;
+    TRY(encode_batch_kept(c, utf8, doc_off, n_docs, use_special, allowed_ids, n_allowed, chk, &n));
+    TRY(drained(c, [&] { return pass(n); }));
+    return tail(n);
 }
 
 extern "C" int tk_encode_batch(tk_core* c, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special,
@@ -2505,18 +2528,6 @@ extern "C" int tk_token_spans_device(tk_core* c, const void* d_tokens, uint64_t 
     return TK_OK;
 }
 
-// the spans of n tokens from the device into two result arrays
-static int spans_to_host(const SpanView& v, uint64_t n, HostResult<uint32_t>& bs, HostResult<uint32_t>& cs) {
-    bs = HostResult<uint32_t>(result_alloc(n * 4));
-    cs = HostResult<uint32_t>(result_alloc(n * 4));
-    if (!bs || !cs) return fail(TK_RUNTIME_ERROR, "out of host memory");
-    if (n) {
-        HIPCHK(hipMemcpy(bs, v.byte_start, n * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(cs, v.char_start, n * 4, hipMemcpyDeviceToHost));
-    }
-    return TK_OK;
-}
-
 // Host buffers in and out.  A batch of less than two ranges of 16 Mi ids takes one copy each way.  A larger one runs in those ranges, as
 // tk_decode_batch does: the ids of range k + 1 travel to the device (straight from the caller's buffer, sent by a thread of their own)
 // while range k is scanned and the spans of range k - 1 travel back -- both directions of the link at once; the scan's carry (sums and
@@ -2605,12 +2616,9 @@ extern "C" int tk_decode_batch_spans(tk_core* c, const uint32_t* tokens, const u
     } else {
         if (n) HIPCHK(hipMemcpyAsync(c->d_tok.p, tokens, n * 4, hipMemcpyHostToDevice, s));
         TRY(drained(c, [&] { return spans_run(c, s, c->d_tok.as<uint32_t>(), n, c->d_boff.as<uint64_t>(), n_docs, nullptr, bytes_out != nullptr, validate != 0, &v); }));
-        TRY(spans_to_host(v, n, bs, cs));
-        if (bytes_out) {
-            host = HostResult<uint8_t>(result_alloc(v.n_bytes));
-            if (!host) return fail(TK_RUNTIME_ERROR, "out of host memory");
-            if (v.n_bytes) HIPCHK(hipMemcpy(host, c->d_bytes.p, v.n_bytes, hipMemcpyDeviceToHost));
-        }
+        TRY(result_from_device(bs, v.byte_start, n));
+        TRY(result_from_device(cs, v.char_start, n));
+        if (bytes_out) TRY(result_from_device(host, c->d_bytes.p, v.n_bytes));
     }
     if (byte_off_out) HIPCHK(hipMemcpy(byte_off_out, v.byte_off, (n_docs + 1) * 8, hipMemcpyDeviceToHost));
     if (char_off_out) HIPCHK(hipMemcpy(char_off_out, v.char_off, (n_docs + 1) * 8, hipMemcpyDeviceToHost));
@@ -2627,24 +2635,23 @@ extern "C" int tk_decode_batch_spans(tk_core* c, const uint32_t* tokens, const u
 extern "C" int tk_encode_batch_spans(tk_core* c, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special, const uint32_t* allowed_ids,
                                      uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed, uint32_t** tokens_out, uint64_t* n_tokens_out,
                                      uint64_t* tok_off_out, uint32_t** byte_start_out, uint32_t** char_start_out, tk_special_hit* hit) {
-    if (!c) return fail(TK_VALUE_ERROR, "core is null");
-    if (!tokens_out || !n_tokens_out || !byte_start_out || !char_start_out || (n_disallowed && !hit)) return fail(TK_VALUE_ERROR, "null argument");
-    const CheckArgs chk{disallowed_ids, n_disallowed, hit};
-    std::lock_guard<std::mutex> lk(c->mu);
-    uint64_t n = 0;
-    TRY(encode_batch_kept(c, utf8, doc_off, n_docs, use_special, allowed_ids, n_allowed, chk, &n));
     SpanView v;
-    TRY(drained(c, [&] { return spans_run(c, c->stream, c->out_tokens.as<uint32_t>(), n, c->out_tok_off.as<uint64_t>(), n_docs, c->doc_off.as<uint64_t>(), false, false, &v); }));
-    HostResult<uint32_t> bs, cs, tok(result_alloc(n * 4));
-    if (!tok) return fail(TK_RUNTIME_ERROR, "out of host memory");
-    TRY(spans_to_host(v, n, bs, cs));
-    if (n) HIPCHK(hipMemcpy(tok, c->out_tokens.p, n * 4, hipMemcpyDeviceToHost));
-    if (tok_off_out) HIPCHK(hipMemcpy(tok_off_out, c->out_tok_off.p, (n_docs + 1) * 8, hipMemcpyDeviceToHost));
-    *tokens_out = tok.release();
-    *n_tokens_out = n;
-    *byte_start_out = bs.release();
-    *char_start_out = cs.release();
-    return TK_OK;
+    return encode_batch_pass(
+        c, utf8, doc_off, n_docs, use_special, allowed_ids, n_allowed, disallowed_ids, n_disallowed, hit, tokens_out && n_tokens_out && byte_start_out && char_start_out,
+        [] { return TK_OK; },
+        [&](uint64_t n) { return spans_run(c, c->stream, c->out_tokens.as<uint32_t>(), n, c->out_tok_off.as<uint64_t>(), n_docs, c->doc_off.as<uint64_t>(), false, false, &v); },
+        [&](uint64_t n) -> int {
+            HostResult<uint32_t> bs, cs, tok;
+            TRY(result_from_device(tok, c->out_tokens.p, n));
+            TRY(result_from_device(bs, v.byte_start, n));
+            TRY(result_from_device(cs, v.char_start, n));
+            if (tok_off_out) HIPCHK(hipMemcpy(tok_off_out, c->out_tok_off.p, (n_docs + 1) * 8, hipMemcpyDeviceToHost));
+            *tokens_out = tok.release();
+            *n_tokens_out = n;
+            *byte_start_out = bs.release();
+            *char_start_out = cs.release();
+            return TK_OK;
+        });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2667,8 +2674,30 @@ static int ids16_check(tk_core* c, uint32_t bos_id, uint32_t eos_id, uint32_t pa
         if (extra[i] > 0xFFFFu && (i == 2 || extra[i] != TK_ROWS_NO_TOKEN)) return fail(TK_VALUE_ERROR, std::string("16-bit ids: ") + names[i] + " does not fit");
     return TK_OK;
 }
-// rows_run: the caller holds c->mu.  Everything but the number of segments follows from the arguments; the host waits once, at the end, for
-// that number and for what tk_k_rows_mark has to say about tok_off.
+// The report words of the row and the padded passes (device memory); word TK_BAD_OFF is what the check of the caller's tok_off found.
+// Before the passes: all ones = no entry offends (the other words are the passes' to write, or the caller's to clear)
+static int report_arm(unsigned long long* words, hipStream_t s) {
+    HIPCHK(hipMemsetAsync(words + TK_BAD_OFF, 0xFF, 8, s));
+    return TK_OK;
+}
+// TK_OK, or the refusal of a tok_off that does not describe the batch: the first offending document and what is wrong with it
+static int tok_off_refusal(unsigned long long word) {
+    if (word == ~0ull) return TK_OK;
+    const std::string d = std::to_string(word >> 2);
+    switch (word & 3u) {
+        case 1: return fail(TK_VALUE_ERROR, "tok_off[0] must be 0 (document " + d + ")");
+        case 2: return fail(TK_VALUE_ERROR, "tok_off must be non-decreasing: document " + d + " ends before it starts");
+        default: return fail(TK_VALUE_ERROR, "tok_off must end at n_tokens: document " + d + " ends elsewhere");
+    }
+}
+// Behind the passes: the stream is waited for, the n words come over (synchronous: nothing is on its way into `got` when this returns,
+// however it returns), and an offending tok_off is refused
+static int report_read(const unsigned long long* words, unsigned long long* got, size_t n, hipStream_t s) {
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(got, words, n * 8, hipMemcpyDeviceToHost));
+    return tok_off_refusal(got[TK_BAD_OFF]);
+}
 // What of a tk_rows_spec can be refused without looking at the batch (the host-text entry asks before it encodes anything).
 static int rows_check_spec(tk_core* c, const tk_rows_spec* spec) {
     if (!spec) return fail(TK_VALUE_ERROR, "null argument");
@@ -2677,6 +2706,8 @@ static int rows_check_spec(tk_core* c, const tk_rows_spec* spec) {
     if (spec->flags & TK_ROWS_IDS16) TRY(ids16_check(c, spec->bos_id, spec->eos_id, spec->pad_id));
     return TK_OK;
 }
+// rows_run: the caller holds c->mu.  Everything but the number of segments follows from the arguments; the host waits once, at the end, for
+// that number and for what tk_k_rows_mark has to say about tok_off.
 static int rows_run(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n, const uint64_t* d_tok_off, uint64_t n_docs, const tk_rows_spec* spec, RowsView* out) {
     TRY(rows_check_spec(c, spec));
     TkRows r;
@@ -2705,7 +2736,7 @@ static int rows_run(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n
     out->n_pos = r.M;
     out->n_tail = (spec->flags & TK_ROWS_DROP_LAST) ? r.S - r.R * r.seq_len : 0;
     unsigned long long* cnt = c->d_rows_blk.as<unsigned long long>();
-    HIPCHK(hipMemsetAsync(words + TK_ROWS_BAD_OFF, 0xFF, 8, s));  // (all ones: none; tk_k_rows_scan writes the other word)
+    TRY(report_arm(words, s));  // (tk_k_rows_scan writes the other word)
     HIPCHK(hipMemsetAsync(c->d_rows_marks.p, 0, (r.M / 32 + 4) * 4, s));
     TRY(timed(c, s, "tk_k_rows_mark", [&] {
         hipLaunchKernelGGL(tk_k_rows_mark, dim3(grid_for(n_docs + 1, 256, 4096)), dim3(256), 0, s, d_tok_off, r, c->d_rows_marks.as<uint32_t>(), words);
@@ -2719,17 +2750,7 @@ static int rows_run(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n
             else hipLaunchKernelGGL(tk_k_rows_write<false>, dim3((uint32_t)nb), dim3(256), 0, s, d_tok, d_tok_off, r, cnt, words, out->ids, out->doc, out->pos, out->cu, out->row_seg);
         }));
     unsigned long long got[TK_ROWS_WORDS];
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(got, words, sizeof got, hipMemcpyDeviceToHost));  // (synchronous: nothing is on its way into `got` when this returns, however it returns)
-    if (got[TK_ROWS_BAD_OFF] != ~0ull) {
-        const std::string d = std::to_string(got[TK_ROWS_BAD_OFF] >> 2);
-        switch (got[TK_ROWS_BAD_OFF] & 3u) {
-            case 1: return fail(TK_VALUE_ERROR, "tok_off[0] must be 0 (document " + d + ")");
-            case 2: return fail(TK_VALUE_ERROR, "tok_off must be non-decreasing: document " + d + " ends before it starts");
-            default: return fail(TK_VALUE_ERROR, "tok_off must end at n_tokens: document " + d + " ends elsewhere");
-        }
-    }
+    TRY(report_read(words, got, TK_ROWS_WORDS, s));
     out->n_segs = got[TK_ROWS_NSEGS];
     return TK_OK;
 }
@@ -2761,37 +2782,31 @@ extern "C" int tk_encode_batch_rows(tk_core* c, const uint8_t* utf8, const uint6
                                     uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed, const tk_rows_spec* spec, void** ids_out,
                                     uint32_t** doc_out, uint32_t** pos_out, uint32_t** cu_seqlens_out, uint32_t** row_seg_out, uint64_t* n_rows_out,
                                     uint64_t* n_segs_out, uint64_t* n_stream_out, uint64_t* n_tail_out, tk_special_hit* hit) {
-    if (!c) return fail(TK_VALUE_ERROR, "core is null");
-    if (!spec || !ids_out || !doc_out || !pos_out || !cu_seqlens_out || !row_seg_out || !n_rows_out || !n_segs_out || (n_disallowed && !hit))
-        return fail(TK_VALUE_ERROR, "null argument");
-    TRY(rows_check_spec(c, spec));  // (before the encode, not after it)
-    const CheckArgs chk{disallowed_ids, n_disallowed, hit};
-    std::lock_guard<std::mutex> lk(c->mu);
-    uint64_t n = 0;
-    TRY(encode_batch_kept(c, utf8, doc_off, n_docs, use_special, allowed_ids, n_allowed, chk, &n));
     RowsView v;
-    TRY(drained(c, [&] { return rows_run(c, c->stream, c->out_tokens.as<uint32_t>(), n, c->out_tok_off.as<uint64_t>(), n_docs, spec, &v); }));
-    const uint64_t ids_bytes = v.n_pos * (v.ids16 ? 2 : 4);
-    HostResult<uint8_t> ids(result_alloc(ids_bytes));
-    HostResult<uint32_t> doc(result_alloc(v.n_pos * 4)), pos(result_alloc(v.n_pos * 4)), cu(result_alloc((v.n_segs + 1) * 4)), rs(result_alloc((v.n_rows + 1) * 4));
-    if (!ids || !doc || !pos || !cu || !rs) return fail(TK_RUNTIME_ERROR, "out of host memory");
-    if (v.n_pos) {
-        HIPCHK(hipMemcpy(ids, v.ids, ids_bytes, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(doc, v.doc, v.n_pos * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(pos, v.pos, v.n_pos * 4, hipMemcpyDeviceToHost));
-    }
-    HIPCHK(hipMemcpy(cu, v.cu, (v.n_segs + 1) * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(rs, v.row_seg, (v.n_rows + 1) * 4, hipMemcpyDeviceToHost));
-    *ids_out = ids.release();
-    *doc_out = doc.release();
-    *pos_out = pos.release();
-    *cu_seqlens_out = cu.release();
-    *row_seg_out = rs.release();
-    *n_rows_out = v.n_rows;
-    *n_segs_out = v.n_segs;
-    if (n_stream_out) *n_stream_out = v.n_stream;
-    if (n_tail_out) *n_tail_out = v.n_tail;
-    return TK_OK;
+    return encode_batch_pass(
+        c, utf8, doc_off, n_docs, use_special, allowed_ids, n_allowed, disallowed_ids, n_disallowed, hit,
+        spec && ids_out && doc_out && pos_out && cu_seqlens_out && row_seg_out && n_rows_out && n_segs_out,
+        [&] { return rows_check_spec(c, spec); },  // (before the encode, not after it)
+        [&](uint64_t n) { return rows_run(c, c->stream, c->out_tokens.as<uint32_t>(), n, c->out_tok_off.as<uint64_t>(), n_docs, spec, &v); },
+        [&](uint64_t) -> int {
+            HostResult<uint8_t> ids;
+            HostResult<uint32_t> doc, pos, cu, rs;
+            TRY(result_from_device(ids, v.ids, v.n_pos * (v.ids16 ? 2 : 4)));
+            TRY(result_from_device(doc, v.doc, v.n_pos));
+            TRY(result_from_device(pos, v.pos, v.n_pos));
+            TRY(result_from_device(cu, v.cu, v.n_segs + 1));
+            TRY(result_from_device(rs, v.row_seg, v.n_rows + 1));
+            *ids_out = ids.release();
+            *doc_out = doc.release();
+            *pos_out = pos.release();
+            *cu_seqlens_out = cu.release();
+            *row_seg_out = rs.release();
+            *n_rows_out = v.n_rows;
+            *n_segs_out = v.n_segs;
+            if (n_stream_out) *n_stream_out = v.n_stream;
+            if (n_tail_out) *n_tail_out = v.n_tail;
+            return TK_OK;
+        });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2837,22 +2852,12 @@ static int pad_run(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n,
     TRY(ensure(c->d_pad_cnt, TK_PAD_WORDS * 8 + (n_docs + 1) * 4));
     unsigned long long* words = c->d_pad_cnt.as<unsigned long long>();
     uint32_t* counted = (uint32_t*)(words + TK_PAD_WORDS);  // (the result's doc_row is written once the call is accepted)
-    HIPCHK(hipMemsetAsync(words + TK_PAD_BAD_OFF, 0xFF, 8, s));  // (all ones: none; tk_k_pad_scan writes the second word)
+    TRY(report_arm(words, s));  // (tk_k_pad_scan writes the second word)
     HIPCHK(hipMemsetAsync(words + TK_PAD_LONGEST, 0, 8, s));
     TRY(timed(c, s, "tk_k_pad_count", [&] { hipLaunchKernelGGL(tk_k_pad_count, dim3(grid_for(n_docs + 1, 256, 4096)), dim3(256), 0, s, d_tok_off, p, counted, words); }));
     TRY(timed(c, s, "tk_k_pad_scan", [&] { hipLaunchKernelGGL(tk_k_pad_scan, dim3(1), dim3(1024), 0, s, counted, n_docs, words); }));
     unsigned long long got[TK_PAD_WORDS];
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(got, words, sizeof got, hipMemcpyDeviceToHost));  // (synchronous: nothing is on its way into `got` when this returns, however it returns)
-    if (got[TK_PAD_BAD_OFF] != ~0ull) {
-        const std::string d = std::to_string(got[TK_PAD_BAD_OFF] >> 2);
-        switch (got[TK_PAD_BAD_OFF] & 3u) {
-            case 1: return fail(TK_VALUE_ERROR, "tok_off[0] must be 0 (document " + d + ")");
-            case 2: return fail(TK_VALUE_ERROR, "tok_off must be non-decreasing: document " + d + " ends before it starts");
-            default: return fail(TK_VALUE_ERROR, "tok_off must end at n_tokens: document " + d + " ends elsewhere");
-        }
-    }
+    TRY(report_read(words, got, TK_PAD_WORDS, s));
     TRY(pad_refusal(tk_pad_size(&p, got[TK_PAD_NROWS], (uint32_t)got[TK_PAD_LONGEST])));
     const bool ids16 = (spec->flags & TK_PAD_IDS16) != 0;
     const uint64_t N = p.R * p.W, n8 = (N + 7) & ~7ull, ids_bytes = n8 * (ids16 ? 2 : 4), r4 = (p.R + 3) & ~3ull;  // (every array starts at a multiple of 16 bytes)
@@ -2911,39 +2916,32 @@ extern "C" int tk_encode_batch_padded(tk_core* c, const uint8_t* utf8, const uin
                                       uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed, const tk_pad_spec* spec, void** ids_out,
                                       uint8_t** mask_out, uint32_t** len_out, uint32_t** row_doc_out, uint32_t** row_tok_out, uint32_t** doc_row_out,
                                       uint64_t* n_rows_out, uint64_t* width_out, tk_special_hit* hit) {
-    if (!c) return fail(TK_VALUE_ERROR, "core is null");
-    if (!spec || !ids_out || !mask_out || !len_out || !row_doc_out || !row_tok_out || !doc_row_out || !n_rows_out || !width_out || (n_disallowed && !hit))
-        return fail(TK_VALUE_ERROR, "null argument");
-    TRY(pad_check_spec(c, spec));  // (before the encode, not after it)
-    const CheckArgs chk{disallowed_ids, n_disallowed, hit};
-    std::lock_guard<std::mutex> lk(c->mu);
-    uint64_t n = 0;
-    TRY(encode_batch_kept(c, utf8, doc_off, n_docs, use_special, allowed_ids, n_allowed, chk, &n));
     PadView v;
-    TRY(drained(c, [&] { return pad_run(c, c->stream, c->out_tokens.as<uint32_t>(), n, c->out_tok_off.as<uint64_t>(), n_docs, spec, &v); }));
-    const uint64_t N = v.n_rows * v.width, ids_bytes = N * (v.ids16 ? 2 : 4);
-    HostResult<uint8_t> ids(result_alloc(ids_bytes)), mask(result_alloc(N));
-    HostResult<uint32_t> len(result_alloc(v.n_rows * 4)), rd(result_alloc(v.n_rows * 4)), rt(result_alloc(v.n_rows * 4)), dr(result_alloc((n_docs + 1) * 4));
-    if (!ids || !mask || !len || !rd || !rt || !dr) return fail(TK_RUNTIME_ERROR, "out of host memory");
-    if (N) {
-        HIPCHK(hipMemcpy(ids, v.ids, ids_bytes, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(mask, v.mask, N, hipMemcpyDeviceToHost));
-    }
-    if (v.n_rows) {
-        HIPCHK(hipMemcpy(len, v.len, v.n_rows * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(rd, v.row_doc, v.n_rows * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(rt, v.row_tok, v.n_rows * 4, hipMemcpyDeviceToHost));
-    }
-    HIPCHK(hipMemcpy(dr, v.doc_row, (n_docs + 1) * 4, hipMemcpyDeviceToHost));
-    *ids_out = ids.release();
-    *mask_out = mask.release();
-    *len_out = len.release();
-    *row_doc_out = rd.release();
-    *row_tok_out = rt.release();
-    *doc_row_out = dr.release();
-    *n_rows_out = v.n_rows;
-    *width_out = v.width;
-    return TK_OK;
+    return encode_batch_pass(
+        c, utf8, doc_off, n_docs, use_special, allowed_ids, n_allowed, disallowed_ids, n_disallowed, hit,
+        spec && ids_out && mask_out && len_out && row_doc_out && row_tok_out && doc_row_out && n_rows_out && width_out,
+        [&] { return pad_check_spec(c, spec); },  // (before the encode, not after it)
+        [&](uint64_t n) { return pad_run(c, c->stream, c->out_tokens.as<uint32_t>(), n, c->out_tok_off.as<uint64_t>(), n_docs, spec, &v); },
+        [&](uint64_t) -> int {
+            const uint64_t N = v.n_rows * v.width;
+            HostResult<uint8_t> ids, mask;
+            HostResult<uint32_t> len, rd, rt, dr;
+            TRY(result_from_device(ids, v.ids, N * (v.ids16 ? 2 : 4)));
+            TRY(result_from_device(mask, v.mask, N));
+            TRY(result_from_device(len, v.len, v.n_rows));
+            TRY(result_from_device(rd, v.row_doc, v.n_rows));
+            TRY(result_from_device(rt, v.row_tok, v.n_rows));
+            TRY(result_from_device(dr, v.doc_row, n_docs + 1));
+            *ids_out = ids.release();
+            *mask_out = mask.release();
+            *len_out = len.release();
+            *row_doc_out = rd.release();
+            *row_tok_out = rt.release();
+            *doc_row_out = dr.release();
+            *n_rows_out = v.n_rows;
+            *width_out = v.width;
+            return TK_OK;
+        });
 }
 
 // ------------------------------------------------------------------------------------------

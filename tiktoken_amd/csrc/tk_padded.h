@@ -20,17 +20,17 @@
 #pragma once
 #include "tk_decode.h"
 #include "tk_padded_rule.h"
+#include "tk_rows.h"  // TkTokens, tk_ids_store8, tk_ids_store1
 #include "tk_scan.h"
 
-// the words the passes report in (unsigned long long each): the lowest tk_rows_bad_key (starts as all ones = none), R, the longest len
-enum { TK_PAD_BAD_OFF = 0, TK_PAD_NROWS, TK_PAD_LONGEST, TK_PAD_WORDS };
+// the words the passes report in (unsigned long long each): the lowest tk_rows_bad_key (TK_BAD_OFF; starts as all ones = none), R, the longest len
+enum { TK_PAD_NROWS = TK_BAD_OFF + 1, TK_PAD_LONGEST, TK_PAD_WORDS };
 
 __global__ __launch_bounds__(256) void tk_k_pad_count(const uint64_t* __restrict__ tok_off, TkPad p, uint32_t* __restrict__ doc_row, unsigned long long* __restrict__ words) {
     uint32_t longest = 0;
     for (uint64_t d = blockIdx.x * 256ull + threadIdx.x; d <= p.n_docs; d += (uint64_t)gridDim.x * 256) {
-        const uint64_t a = tok_off[d], b = d < p.n_docs ? tok_off[d + 1] : p.n_tokens;
-        const uint32_t why = tk_rows_off_error(a, b, d, p.n_docs);
-        if (why) atomicMin(words + TK_PAD_BAD_OFF, (unsigned long long)tk_rows_bad_key(d, p.n_docs, why));
+        uint64_t a, b;
+        const uint32_t why = tk_rows_off_check(tok_off, d, p.n_docs, p.n_tokens, &a, &b, words + TK_BAD_OFF);
         if (d < p.n_docs) {
             const uint64_t n = why ? 0 : b - a;  // (no error here: a <= b)
             doc_row[d] = (uint32_t)tk_pad_windows(p, n);  // (at most n, and n < 2^32 unless another entry is reported)
@@ -63,18 +63,6 @@ __global__ __launch_bounds__(256) void tk_k_pad_rows(const uint64_t* __restrict_
     }
 }
 
-// The caller's token array as tk_pad_lane reads it: eight ids as two 16-byte loads where their address is a multiple of 16
-struct TkPadTokens {
-    const uint32_t* __restrict__ p;
-    __device__ __forceinline__ uint32_t one(uint64_t i) const { return p[i]; }
-    __device__ __forceinline__ bool eight(uint64_t i, uint32_t out[8]) const {
-        if ((uintptr_t)(p + i) & 15u) return false;
-        const uint4 a = *(const uint4*)(p + i), b = *(const uint4*)(p + i + 4);
-        out[0] = a.x, out[1] = a.y, out[2] = a.z, out[3] = a.w, out[4] = b.x, out[5] = b.y, out[6] = b.z, out[7] = b.w;
-        return true;
-    }
-};
-
 // ids_out, mask_out: 16-byte aligned (the library's own buffers): a lane's eight ids leave as 16-byte stores, its eight mask bytes as one
 // 8-byte store.  tokens is the caller's: the eight ids arrive as two 16-byte loads where the lane's positions are eight body tokens of one
 // row and their address allows it (a row's body starts wherever its document and its window do, so that is one lane in four), otherwise
@@ -90,22 +78,15 @@ __global__ __launch_bounds__(256) void tk_k_pad_write(const uint32_t* __restrict
     if (N - b0 <= threadIdx.x * 8u) return;
     uint32_t id[8];
     uint64_t mask;
-    tk_pad_lane(p, TkPadTokens{tokens}, tok_off, doc_row, sh_doc[0], sh_doc[1], i0, N, id, &mask);
+    tk_pad_lane(p, TkTokens{tokens}, tok_off, doc_row, sh_doc[0], sh_doc[1], i0, N, id, &mask);
     if (N - i0 >= 8u) {
-        if (IDS16) {  // (the host has checked that every id of the vocabulary fits; ids of no vocabulary are cut, as a uint16 store cuts them)
-            *(uint4*)((uint16_t*)ids_out + i0) = make_uint4((id[0] & 0xFFFFu) | (id[1] << 16), (id[2] & 0xFFFFu) | (id[3] << 16), (id[4] & 0xFFFFu) | (id[5] << 16),
-                                                            (id[6] & 0xFFFFu) | (id[7] << 16));
-        } else {
-            *(uint4*)((uint32_t*)ids_out + i0) = make_uint4(id[0], id[1], id[2], id[3]);
-            *(uint4*)((uint32_t*)ids_out + i0 + 4) = make_uint4(id[4], id[5], id[6], id[7]);
-        }
+        tk_ids_store8<IDS16>(ids_out, i0, id);
         *(unsigned long long*)(mask_out + i0) = mask;
     } else {
 #pragma unroll
         for (uint32_t j = 0; j < 8; ++j)
             if (N - i0 > j) {
-                if (IDS16) ((uint16_t*)ids_out)[i0 + j] = (uint16_t)id[j];
-                else ((uint32_t*)ids_out)[i0 + j] = id[j];
+                tk_ids_store1<IDS16>(ids_out, i0 + j, id[j]);
                 mask_out[i0 + j] = (uint8_t)(mask >> (8 * j));
             }
     }

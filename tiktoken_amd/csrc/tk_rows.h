@@ -23,14 +23,13 @@
 #include "tk_rows_rule.h"
 #include "tk_scan.h"
 
-// the words the passes report in (unsigned long long each): the lowest tk_rows_bad_key (starts as all ones = none), the segments
-enum { TK_ROWS_BAD_OFF = 0, TK_ROWS_NSEGS, TK_ROWS_WORDS };
+// the words the passes report in (unsigned long long each): the lowest tk_rows_bad_key (TK_BAD_OFF; starts as all ones = none), the segments
+enum { TK_ROWS_NSEGS = TK_BAD_OFF + 1, TK_ROWS_WORDS };
 
 __global__ __launch_bounds__(256) void tk_k_rows_mark(const uint64_t* __restrict__ tok_off, TkRows r, uint32_t* __restrict__ bm, unsigned long long* __restrict__ words) {
     for (uint64_t d = blockIdx.x * 256ull + threadIdx.x; d <= r.n_docs; d += (uint64_t)gridDim.x * 256) {
-        const uint64_t a = tok_off[d], b = d < r.n_docs ? tok_off[d + 1] : r.n_tokens;
-        const uint32_t why = tk_rows_off_error(a, b, d, r.n_docs);
-        if (why) atomicMin(words + TK_ROWS_BAD_OFF, (unsigned long long)tk_rows_bad_key(d, r.n_docs, why));
+        uint64_t a, b;
+        tk_rows_off_check(tok_off, d, r.n_docs, r.n_tokens, &a, &b, words + TK_BAD_OFF);
         const uint64_t p = tk_rows_mark_at(a, b, d, r);
         if (p != ~0ull) atomicOr(&bm[p >> 5], 1u << (p & 31u));
     }
@@ -59,11 +58,43 @@ __global__ __launch_bounds__(1024) void tk_k_rows_scan(unsigned long long* __res
     }
 }
 
+// The caller's token array as a lane of a write pass reads it (tk_rows_lane, tk_pad_lane): eight ids as two 16-byte loads where their
+// address is a multiple of 16
+struct TkTokens {
+    const uint32_t* __restrict__ p;
+    __device__ __forceinline__ uint32_t one(uint64_t i) const { return p[i]; }
+    __device__ __forceinline__ bool eight(uint64_t i, uint32_t out[8]) const {
+        if ((uintptr_t)(p + i) & 15u) return false;
+        const uint4 a = *(const uint4*)(p + i), b = *(const uint4*)(p + i + 4);
+        out[0] = a.x, out[1] = a.y, out[2] = a.z, out[3] = a.w, out[4] = b.x, out[5] = b.y, out[6] = b.z, out[7] = b.w;
+        return true;
+    }
+};
+// ... and how its eight ids leave, as uint32 or uint16 (the host has checked that every id of the vocabulary fits; ids of no vocabulary are
+// cut, as a uint16 store cuts them): a whole lane as 16-byte stores (ids_out 16-byte aligned, i0 a multiple of 8), the last lane's one by
+// one, each behind the caller's test that the position exists
+template <bool IDS16>
+__device__ __forceinline__ void tk_ids_store8(void* __restrict__ ids_out, uint64_t i0, const uint32_t id[8]) {
+    if (IDS16) {
+        *(uint4*)((uint16_t*)ids_out + i0) = make_uint4((id[0] & 0xFFFFu) | (id[1] << 16), (id[2] & 0xFFFFu) | (id[3] << 16), (id[4] & 0xFFFFu) | (id[5] << 16),
+                                                        (id[6] & 0xFFFFu) | (id[7] << 16));
+    } else {
+        *(uint4*)((uint32_t*)ids_out + i0) = make_uint4(id[0], id[1], id[2], id[3]);
+        *(uint4*)((uint32_t*)ids_out + i0 + 4) = make_uint4(id[4], id[5], id[6], id[7]);
+    }
+}
+template <bool IDS16>
+__device__ __forceinline__ void tk_ids_store1(void* __restrict__ ids_out, uint64_t i, uint32_t id) {
+    if (IDS16) ((uint16_t*)ids_out)[i] = (uint16_t)id;
+    else ((uint32_t*)ids_out)[i] = id;
+}
+
 // ids_out, doc_out, pos_out: 16-byte aligned (the library's own buffers): a lane's eight positions leave as 16-byte stores.  tokens is the
 // caller's: its eight ids arrive as two 16-byte loads where the stream is the token array (k == 0) and the pointer allows it.  Otherwise
 // (bos / eos shift the ids by a different amount in every document, so no aligned word holds a lane's ids) they arrive as eight 4-byte
 // loads per lane, as in the span passes: for one j the lanes of a wavefront are 32 bytes apart, so an instruction uses 4 bytes of every
-// 32 and the eight of them together read every cache line of the wavefront's 2 KiB once from HBM and seven times from the L1.
+// 32 and the eight of them together read every cache line of the wavefront's 2 KiB once from HBM and seven times from the L1.  What a lane
+// computes is tk_rows_lane (tk_rows_rule.h), the same statements the CPU simulation runs.
 template <bool IDS16>
 __global__ __launch_bounds__(256) void tk_k_rows_write(const uint32_t* __restrict__ tokens, const uint64_t* __restrict__ tok_off, TkRows r,
                                                        const unsigned long long* __restrict__ seg_base, const unsigned long long* __restrict__ words,
@@ -71,71 +102,16 @@ __global__ __launch_bounds__(256) void tk_k_rows_write(const uint32_t* __restric
                                                        uint32_t* __restrict__ cu, uint32_t* __restrict__ row_seg) {
     __shared__ uint32_t sh[8];
     __shared__ uint64_t sh_doc[2];
-    if (words[TK_ROWS_BAD_OFF] != ~0ull) return;  // (the same in every thread) tok_off does not describe the batch: nothing is indexed with it
+    if (words[TK_BAD_OFF] != ~0ull) return;  // (the same in every thread) tok_off does not describe the batch: nothing is indexed with it
     const uint64_t b0 = (uint64_t)blockIdx.x * TK_DEC_BLOCK, i0 = b0 + (uint64_t)threadIdx.x * 8;
-    if (threadIdx.x == 0) {  // the documents of the workgroup's first and last stream position
-        uint64_t lo = 0, hi = 0;
-        if (b0 < r.S) {
-            const uint64_t last = b0 + TK_DEC_BLOCK <= r.S ? b0 + TK_DEC_BLOCK - 1 : r.S - 1;
-            lo = tk_rows_last_doc(tok_off, 0, r.n_docs, r.k, b0);
-            hi = tk_rows_last_doc(tok_off, lo, r.n_docs, r.k, last) + 1;
-        }
-        sh_doc[0] = lo;
-        sh_doc[1] = hi;
-    }
+    if (threadIdx.x == 0) tk_rows_block_docs(r, tok_off, b0, TK_DEC_BLOCK, &sh_doc[0], &sh_doc[1]);
     __syncthreads();
-    const uint64_t d_hi = sh_doc[1];
-    uint32_t id[8], dc[8], ps[8], seg = 0, rows = 0;
+    uint32_t seg = 0, rows = 0;
     if (i0 < r.M) {
-        uint64_t d = 0, start = r.S, next = r.S;  // (beyond the stream: the padding, one segment from S on)
-        if (i0 < r.S) {
-            d = tk_rows_last_doc(tok_off, sh_doc[0], d_hi, r.k, i0);
-            start = tk_rows_out_off(tok_off[d], d, r.k);
-            next = tk_rows_out_off(tok_off[d + 1], d + 1, r.k);
-        }
-        const bool wide = r.k == 0 && i0 + 8 <= r.n_tokens && ((uintptr_t)tokens & 15u) == 0;
-        uint4 ta = make_uint4(0, 0, 0, 0), tb = ta;
-        if (wide) {
-            ta = *(const uint4*)(tokens + i0);
-            tb = *(const uint4*)(tokens + i0 + 4);
-        }
-        const uint32_t tw[8] = {ta.x, ta.y, ta.z, ta.w, tb.x, tb.y, tb.z, tb.w};
-        uint32_t rem = (uint32_t)i0 % r.seq_len;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const uint64_t p = i0 + j;
-            id[j] = r.pad;
-            dc[j] = TK_ROWS_NONE;
-            ps[j] = 0;
-            if (p < r.M) {
-                if (p < r.S) {
-                    if (p >= next) {  // the next document that owns a position: the one after, unless that one is empty
-                        ++d;
-                        if (tk_rows_out_off(tok_off[d + 1], d + 1, r.k) <= p) d = tk_rows_last_doc(tok_off, d + 1, d_hi, r.k, p);
-                        start = tk_rows_out_off(tok_off[d], d, r.k);
-                        next = tk_rows_out_off(tok_off[d + 1], d + 1, r.k);
-                    }
-                    uint64_t t = 0;
-                    const int src = tk_rows_source(r, d, start, next, p, &t);
-                    id[j] = src == TK_ROWS_BOS ? r.bos : src == TK_ROWS_EOS ? r.eos : wide ? tw[j] : tokens[t];
-                    dc[j] = (uint32_t)d;
-                } else {
-                    start = r.S;
-                }
-                ps[j] = tk_rows_pos(p, start, p - rem);
-                seg |= (ps[j] == 0u ? 1u : 0u) << j;
-                rows |= (rem == 0u ? 1u : 0u) << j;
-            }
-            if (++rem == r.seq_len) rem = 0u;
-        }
+        uint32_t id[8], dc[8], ps[8];
+        tk_rows_lane(r, TkTokens{tokens}, tok_off, sh_doc[0], sh_doc[1], i0, id, dc, ps, &seg, &rows);
         if (i0 + 8 <= r.M) {
-            if (IDS16) {  // (the host has checked that every id of the vocabulary fits; ids of no vocabulary are cut, as a uint16 store cuts them)
-                *(uint4*)((uint16_t*)ids_out + i0) = make_uint4((id[0] & 0xFFFFu) | (id[1] << 16), (id[2] & 0xFFFFu) | (id[3] << 16), (id[4] & 0xFFFFu) | (id[5] << 16),
-                                                                (id[6] & 0xFFFFu) | (id[7] << 16));
-            } else {
-                *(uint4*)((uint32_t*)ids_out + i0) = make_uint4(id[0], id[1], id[2], id[3]);
-                *(uint4*)((uint32_t*)ids_out + i0 + 4) = make_uint4(id[4], id[5], id[6], id[7]);
-            }
+            tk_ids_store8<IDS16>(ids_out, i0, id);
             *(uint4*)(doc_out + i0) = make_uint4(dc[0], dc[1], dc[2], dc[3]);
             *(uint4*)(doc_out + i0 + 4) = make_uint4(dc[4], dc[5], dc[6], dc[7]);
             *(uint4*)(pos_out + i0) = make_uint4(ps[0], ps[1], ps[2], ps[3]);
@@ -144,8 +120,7 @@ __global__ __launch_bounds__(256) void tk_k_rows_write(const uint32_t* __restric
 #pragma unroll
             for (int j = 0; j < 8; ++j)
                 if (i0 + j < r.M) {
-                    if (IDS16) ((uint16_t*)ids_out)[i0 + j] = (uint16_t)id[j];
-                    else ((uint32_t*)ids_out)[i0 + j] = id[j];
+                    tk_ids_store1<IDS16>(ids_out, i0 + j, id[j]);
                     doc_out[i0 + j] = dc[j];
                     pos_out[i0 + j] = ps[j];
                 }

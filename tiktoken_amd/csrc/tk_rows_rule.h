@@ -1,6 +1,7 @@
 // Training rows from a packed batch: the parts of the device passes of tk_rows.h that are plain C++ -- the shape of the result, what a
 // tok_off entry must satisfy, which document a stream position belongs to, where a stream element comes from (bos, body, eos or pad), the
-// pos rule and what counts as a segment start.  Compiles for the host too: tests/test_rows_sim.py drives them lane by lane on the CPU.
+// pos rule, what counts as a segment start, and a whole lane of the write pass (tk_rows_lane).  Compiles for the host too:
+// tests/test_rows_sim.py drives them lane by lane on the CPU.
 //
 // The stream: for every document d, in order, [bos] tokens[tok_off[d] .. tok_off[d + 1]) [eos]; k = how many of bos / eos there are, so
 // document d starts at out_off(d) = tok_off[d] + d * k and the stream has S = T + n_docs * k elements.  It is cut into R rows of L; M
@@ -50,6 +51,26 @@ TK_HD uint32_t tk_rows_off_error(uint64_t a, uint64_t b, uint64_t d, uint64_t n_
 }
 // the word an offending entry is reported in: the lowest key is the first offending document (entry n_docs speaks for the last document)
 TK_HD uint64_t tk_rows_bad_key(uint64_t d, uint64_t n_docs, uint32_t why) { return ((d == n_docs && d ? d - 1 : d) << 2) | why; }
+// The head of a pass over the entries of tok_off (the row passes' and the padded passes'): *a = entry d, *b = the next one (n_tokens behind
+// the last), and what tk_rows_off_error says about them.  An offending entry's key goes into *bad, which keeps the lowest: on the device
+// that is the report word TK_BAD_OFF (all ones = none), shared by every thread, on the CPU a plain variable.  `tok_off` is indexed with []:
+// the device passes the caller's array, a CPU simulation may pass one that checks every index.
+enum { TK_BAD_OFF = 0 };
+template <class Off>
+TK_HD uint32_t tk_rows_off_check(Off tok_off, uint64_t d, uint64_t n_docs, uint64_t n_tokens, uint64_t* a, uint64_t* b, unsigned long long* bad) {
+    *a = tok_off[d];
+    *b = d < n_docs ? tok_off[d + 1] : n_tokens;
+    const uint32_t why = tk_rows_off_error(*a, *b, d, n_docs);
+    if (why) {
+        const unsigned long long key = tk_rows_bad_key(d, n_docs, why);
+#if defined(__HIP_DEVICE_COMPILE__)
+        atomicMin(bad, key);
+#else
+        *bad = key < *bad ? key : *bad;
+#endif
+    }
+    return why;
+}
 // The stream position entry d marks, or all ones: the start of a document that owns a position (with k == 0 an empty document owns none),
 // and -- entry n_docs -- the start of the padding.  Guarded by a <= n_tokens: whatever tok_off holds, a mark lies below M.
 TK_HD uint64_t tk_rows_mark_at(uint64_t a, uint64_t b, uint64_t d, const TkRows& r) {
@@ -61,7 +82,8 @@ TK_HD uint64_t tk_rows_mark_at(uint64_t a, uint64_t b, uint64_t d, const TkRows&
 
 // The document a stream position j < S belongs to, searched in [lo, hi): the last d there with out_off(d) <= j (out_off(lo) <= j).  Behind a
 // run of empty documents with k == 0 that is the one that is not empty -- the last of those that start at one position.
-TK_HD uint64_t tk_rows_last_doc(const uint64_t* tok_off, uint64_t lo, uint64_t hi, uint32_t k, uint64_t j) {
+template <class Off>
+TK_HD uint64_t tk_rows_last_doc(Off tok_off, uint64_t lo, uint64_t hi, uint32_t k, uint64_t j) {
     uint64_t a = lo, b = hi;  // first index with out_off > j
     while (a < b) {
         const uint64_t mid = (a + b) >> 1;
@@ -99,3 +121,64 @@ TK_HD uint32_t tk_rows_row_bits(uint32_t rem, uint32_t L) {
 }
 // segment starts among them: marked positions (document starts, the padding's start) and row starts, a coincidence counted once
 TK_HD uint32_t tk_rows_seg_bits(uint32_t marks, uint32_t rows, uint32_t valid) { return (marks | rows) & valid; }
+
+// The documents a workgroup's lanes search between: those of its first stream position b0 and of its last (none where b0 lies in the padding)
+template <class Off>
+TK_HD void tk_rows_block_docs(const TkRows& r, Off tok_off, uint64_t b0, uint64_t block, uint64_t* d_lo, uint64_t* d_hi) {
+    *d_lo = *d_hi = 0;
+    if (b0 < r.S) {
+        const uint64_t last = b0 + block <= r.S ? b0 + block - 1 : r.S - 1;
+        *d_lo = tk_rows_last_doc(tok_off, 0, r.n_docs, r.k, b0);
+        *d_hi = tk_rows_last_doc(tok_off, *d_lo, r.n_docs, r.k, last) + 1;
+    }
+}
+// A lane of the write pass: ids, documents and positions of the eight stream positions from i0 < M on (i0 a multiple of 8; positions at and
+// past M left as padding), and as bits which of them start a segment and which a row.  The lane's first position belongs to a document in
+// [d_lo, d_hi); from there it walks along the documents: a position at or beyond the current document's end moves on to the next one that
+// owns a position.  `tok` fetches body tokens: tok.one(i) is tokens[i], and tok.eight(i, out) fetches tokens[i .. i + 8) as two 16-byte
+// words where their address allows it and says whether it did -- asked only where the stream is the token array (k == 0) and all eight
+// exist.  The device passes the caller's arrays, the CPU simulation ones that check every index.
+template <class Tok, class Off>
+TK_HD void tk_rows_lane(const TkRows& r, const Tok& tok, Off tok_off, uint64_t d_lo, uint64_t d_hi, uint64_t i0, uint32_t id[8], uint32_t dc[8], uint32_t ps[8],
+                        uint32_t* seg_out, uint32_t* rows_out) {
+    uint64_t d = 0, start = r.S, next = r.S;  // (beyond the stream: the padding, one segment from S on)
+    if (i0 < r.S) {
+        d = tk_rows_last_doc(tok_off, d_lo, d_hi, r.k, i0);
+        start = tk_rows_out_off(tok_off[d], d, r.k);
+        next = tk_rows_out_off(tok_off[d + 1], d + 1, r.k);
+    }
+    uint32_t tw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const bool wide = r.k == 0 && i0 + 8 <= r.n_tokens && tok.eight(i0, tw);
+    uint32_t rem = (uint32_t)i0 % r.seq_len, seg = 0, rows = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int j = 0; j < 8; ++j) {
+        const uint64_t p = i0 + j;
+        id[j] = r.pad;
+        dc[j] = TK_ROWS_NONE;
+        ps[j] = 0;
+        if (p < r.M) {
+            if (p < r.S) {
+                if (p >= next) {  // the next document that owns a position: the one after, unless that one is empty
+                    ++d;
+                    if (tk_rows_out_off(tok_off[d + 1], d + 1, r.k) <= p) d = tk_rows_last_doc(tok_off, d + 1, d_hi, r.k, p);
+                    start = tk_rows_out_off(tok_off[d], d, r.k);
+                    next = tk_rows_out_off(tok_off[d + 1], d + 1, r.k);
+                }
+                uint64_t t = 0;
+                const int src = tk_rows_source(r, d, start, next, p, &t);
+                id[j] = src == TK_ROWS_BOS ? r.bos : src == TK_ROWS_EOS ? r.eos : wide ? tw[j] : tok.one(t);
+                dc[j] = (uint32_t)d;
+            } else {
+                start = r.S;
+            }
+            ps[j] = tk_rows_pos(p, start, p - rem);
+            seg |= (ps[j] == 0u ? 1u : 0u) << j;
+            rows |= (rem == 0u ? 1u : 0u) << j;
+        }
+        if (++rem == r.seq_len) rem = 0u;
+    }
+    *seg_out = seg;
+    *rows_out = rows;
+}
