@@ -254,6 +254,66 @@ int tk_encode_batch_padded(tk_core* core, const uint8_t* utf8, const uint64_t* d
                            const uint32_t* allowed_ids, uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed,
                            const tk_pad_spec* spec, void** ids_out, uint8_t** mask_out, uint32_t** len_out, uint32_t** row_doc_out,
                            uint32_t** row_tok_out, uint32_t** doc_row_out, uint64_t* n_rows_out, uint64_t* width_out, tk_special_hit* hit);
+/* Supervised samples: a packed batch whose documents are the PARTS of samples -- the messages of a conversation, a prompt and its answer --
+ * -> one row per sample with the template's ids around every part, an attention mask and labels.  Replaces nothing in the reference: it is
+ * the host loop of the reference's users, the fine-tuning script that calls encode_ordinary once per message, adds header and footer ids and
+ * builds ids and labels as Python lists -- here one call on ids that are on the device anyway.
+ * The rule.  Input: tokens uint32[T]; tok_off uint64[n_parts + 1]: part p (what the encode call knows as a document) has
+ * n_p = tok_off[p + 1] - tok_off[p] body tokens; part_role uint8[n_parts]; sample_off uint64[n_samples + 1], ascending from 0 to n_parts:
+ * sample s is the parts [sample_off[s], sample_off[s + 1]), and a sample with no parts is legal.  The role table (host memory in every
+ * entry): n_roles <= 256; role_ids uint32[], at most 4096 in all; role_off uint32[2 * n_roles + 1] ascending from 0: the BEFORE ids of role r
+ * are role_ids[role_off[2r] .. role_off[2r + 1]), its AFTER ids role_ids[role_off[2r + 1] .. role_off[2r + 2]), either may be empty;
+ * role_train uint8[n_roles].
+ *  Stream of a sample.  [bos_id], then for each of its parts in order before(role) body after(role), then [eos_id] (TK_ROWS_NO_TOKEN: no
+ *   bos / no eos).  Its length is full_len[s].  A part that contributes no element owns no position.
+ *  Trained elements.  The body and the after ids of a part whose role has role_train != 0.  Before ids and bos never; eos iff the sample
+ *   has a part and its last part's role trains.
+ *  Truncation.  len[s] = min(full_len[s], max_len); the row holds the stream elements [0, len), with TK_SMP_KEEP_TAIL
+ *   [full_len - len, full_len).  The stream is cut as it is: nothing is re-inserted, and a cut may fall inside a before run, a body or an
+ *   after run.
+ *  Row s of [R = n_samples, W].  Its elements are in columns [0, len), with TK_SMP_LEFT in [W - len, W).  ids (uint32): the element, pad_id
+ *   elsewhere.  mask (uint8): 1 on elements, 0 elsewhere.  labels (int32): the id where the element is trained, ignore_index everywhere
+ *   else, padding included.  Labels are NOT shifted: the model shifts them.
+ *  Per sample.  len uint32[R]; full_len uint64[R] (a caller drops over-long samples by it); n_trained uint32[R]: the trained elements that
+ *   survived the cut (a caller drops samples with nothing to learn by it, and normalises the loss).
+ *  Width.  As tk_pad_batch_device: width_multiple == 0: W = max_len, otherwise W = min(max_len, ceil(longest / width_multiple) *
+ *   width_multiple) with longest = max len[s], 0 when there is no sample.  W = 0 is a legal result.
+ *  TK_VALUE_ERROR, every one found before any output is written (a refused call leaves the previous result whole): max_len == 0;
+ *   n_roles == 0 while there are parts; n_roles > 256, more than 4096 role ids or a role_off that does not ascend from 0;
+ *   part_role[p] >= n_roles (the message names the first such part); a tok_off that does not ascend from 0 to n_tokens (the first offending
+ *   part, called a document as in the other passes); a sample_off that does not ascend from 0 to n_parts (the first offending sample);
+ *   T >= 2^32; n_parts or n_samples >= 2^32 - 1; 2^32 elements or more over all parts; R * W >= 2^32.  The three device arrays are checked
+ *   on the device before anything is indexed with them: no kernel reads or writes out of bounds, whatever they hold.
+ *  One device per call: a group has no samples entry.  NOT built: several samples packed into one row; 16-bit ids; windows for over-long
+ *   samples; a special-token policy per part (the call's policy holds for all parts); a template language (callers encode their few header
+ *   and footer strings once and pass the ids). */
+#define TK_SMP_KEEP_TAIL 1u /* keep an over-long sample's last elements, not its first */
+#define TK_SMP_LEFT 2u      /* padding in front of the row's elements, not behind */
+typedef struct {
+    uint32_t max_len, width_multiple, bos_id, eos_id, pad_id;
+    int32_t ignore_index;
+    uint32_t flags;
+} tk_smp_spec;
+/* Device pointers in (ids uint32, d_tok_off uint64[n_parts + 1]: e.g. the results of tk_encode_batch_device; d_part_role uint8[n_parts],
+ * d_sample_off uint64[n_samples + 1]), the role table in host memory (role_ids / role_off / role_train may be null where they would be
+ * empty), device pointers out: buffers of the core, valid until its next samples call that succeeds (a refused call writes into none of
+ * them) and apart from the encode, decode, span, rows and padded buffers (assembling an encode call's result leaves it intact).  *d_ids_out,
+ * *d_mask_out, *d_labels_out: *n_rows_out x *width_out; *d_len_out, *d_full_len_out, *d_n_trained_out: *n_rows_out.  `stream`: a hipStream_t
+ * or null (the core's); the call returns when the rows are there. */
+int tk_assemble_samples_device(tk_core* core, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_parts, const void* d_part_role,
+                               const void* d_sample_off, uint64_t n_samples, uint32_t n_roles, const uint32_t* role_ids, const uint32_t* role_off,
+                               const uint8_t* role_train, const tk_smp_spec* spec, void* stream, const uint32_t** d_ids_out, const uint8_t** d_mask_out,
+                               const int32_t** d_labels_out, const uint32_t** d_len_out, const uint64_t** d_full_len_out, const uint32_t** d_n_trained_out,
+                               uint64_t* n_rows_out, uint64_t* width_out);
+/* tk_encode_batch -- with n_disallowed != 0: tk_encode_batch_checked, whose *hit names the PART -- over the parts' text (doc_off: n_parts + 1
+ * byte offsets), with the samples assembled while the ids are on the device: host text, part_role and sample_off in, and only the sample
+ * arrays cross the link back (the ids themselves are not handed out).  *ids_out .. *n_trained_out: library-owned (tk_free), sized as above.
+ * On TK_DISALLOWED_SPECIAL nothing is handed out. */
+int tk_encode_batch_samples(tk_core* core, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_parts, int use_special, const uint32_t* allowed_ids,
+                            uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed, const uint8_t* part_role, const uint64_t* sample_off,
+                            uint64_t n_samples, uint32_t n_roles, const uint32_t* role_ids, const uint32_t* role_off, const uint8_t* role_train,
+                            const tk_smp_spec* spec, uint32_t** ids_out, uint8_t** mask_out, int32_t** labels_out, uint32_t** len_out, uint64_t** full_len_out,
+                            uint32_t** n_trained_out, uint64_t* n_rows_out, uint64_t* width_out, tk_special_hit* hit);
 /* bpe_train(data, vocab_size, pat_str, visualise=None)                      tiktoken/_educational.py:119-185
  * Training a vocabulary: the merges the reference's educational trainer makes on the same text -- the same pairs in the same order -- for a
  * packed batch of documents, under the core's pat_str (stock scanners or the generic engine).  The core's ranks and special tokens play

@@ -42,6 +42,15 @@ class PadSpec(ctypes.Structure):
 PAD_WINDOWS, PAD_KEEP_TAIL, PAD_LEFT, PAD_IDS16 = 1, 2, 4, 8
 
 
+class SmpSpec(ctypes.Structure):
+    """tk_smp_spec: how the parts of a packed batch become supervised samples (include/tiktoken_amd.h)."""
+    _fields_ = [("max_len", ctypes.c_uint32), ("width_multiple", ctypes.c_uint32), ("bos_id", ctypes.c_uint32), ("eos_id", ctypes.c_uint32), ("pad_id", ctypes.c_uint32),
+                ("ignore_index", ctypes.c_int32), ("flags", ctypes.c_uint32)]
+
+
+SMP_KEEP_TAIL, SMP_LEFT = 1, 2
+
+
 def build(force: bool = False) -> str:
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     if force or not os.path.exists(_SO):
@@ -108,6 +117,11 @@ def lib() -> ctypes.CDLL:
         L.tk_pad_batch_device.argtypes = [vp, vp, u64, vp, u64, P(PadSpec), vp, P(vp), P(vp), P(vp), P(vp), P(vp), P(vp), P(u64), P(u64)]
         L.tk_encode_batch_padded.restype = i32
         L.tk_encode_batch_padded.argtypes = [vp, vp, vp, u64, i32, vp, u64, vp, u64, P(PadSpec), P(vp), P(vp), P(vp), P(vp), P(vp), P(vp), P(u64), P(u64), P(SpecialHit)]
+        L.tk_assemble_samples_device.restype = i32
+        L.tk_assemble_samples_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, u32, vp, vp, vp, P(SmpSpec), vp, P(vp), P(vp), P(vp), P(vp), P(vp), P(vp), P(u64), P(u64)]
+        L.tk_encode_batch_samples.restype = i32
+        L.tk_encode_batch_samples.argtypes = [vp, vp, vp, u64, i32, vp, u64, vp, u64, vp, vp, u64, u32, vp, vp, vp, P(SmpSpec), P(vp), P(vp), P(vp), P(vp), P(vp), P(vp),
+                                              P(u64), P(u64), P(SpecialHit)]
         L.tk_decode_single_token_bytes.restype = i32
         L.tk_decode_single_token_bytes.argtypes = [vp, u32, P(vp), P(u64)]
         L.tk_n_tokens.restype = u64

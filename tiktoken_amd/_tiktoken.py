@@ -6,7 +6,8 @@ Same constructor and the same eleven methods, same exception types.  Two additiv
 (one launch sequence per batch instead of one FFI call per document); `decode_batch_spans_packed`, `token_spans_device` and
 `encode_batch_spans_packed` give, for whole batches, where every token starts in its document (bytes and chars); `pack_rows_device` and
 `encode_batch_rows_packed` cut a batch into fixed-length training rows with document ids, positions and cu_seqlens; `pad_batch_device` and
-`encode_batch_padded_packed` give one padded row per document (or overlapping windows) with an attention mask; `train_bpe_packed`
+`encode_batch_padded_packed` give one padded row per document (or overlapping windows) with an attention mask; `assemble_samples_device` and
+`encode_batch_samples_packed` join the parts of supervised samples with their roles' ids into rows with labels; `train_bpe_packed`
 trains a vocabulary: the merges of the reference's educational `bpe_train`, made on the device.  With `disallowed_special` the batch
 calls also search the text for those special tokens, on the device, and raise `DisallowedSpecialError`.
 """
@@ -100,6 +101,15 @@ def _take_u8(ptr: ctypes.c_void_p, n: int) -> np.ndarray:
     return out
 
 
+def _take_u64(ptr: ctypes.c_void_p, n: int) -> np.ndarray:
+    """... of a uint64 result"""
+    if n >= (1 << 16):
+        return np.asarray(_OwnedBuffer(ptr.value, n, "<u8"))
+    out = np.frombuffer(ctypes.string_at(ptr, n * 8), dtype=np.uint64).copy() if n else np.zeros(0, dtype=np.uint64)
+    _lib.lib().tk_free(ptr)
+    return out
+
+
 def _check_packed(blob: np.ndarray, doc_off: np.ndarray) -> None:
     """The C ABI reads doc_off[n_docs] bytes of the blob: refuse offsets that do not describe it."""
     if doc_off.ndim != 1 or len(doc_off) < 1:
@@ -184,6 +194,42 @@ class PaddedDevice(NamedTuple):
     row_doc: int
     row_tok: int
     doc_row: int
+    n_rows: int
+    width: int
+
+
+class Role(NamedTuple):
+    """A role of a sample's parts (tk_assemble_samples_device): the token ids put before and after the body of every part of that role -- a
+    chat template's header and footer, given as ids, never as text --, and whether the part is trained: its body and its `after` ids get
+    labels, its `before` ids never do."""
+    before: Sequence[int] = ()
+    after: Sequence[int] = ()
+    train: bool = False
+
+
+class SampleBatch(NamedTuple):
+    """A batch as supervised samples (tk_encode_batch_samples; the rule: include/tiktoken_amd.h): one row per sample -- [bos], for every
+    part the before ids of its role, its tokens, the after ids, [eos] -- cut to max_length at the head or the tail.  attention_mask is 1
+    on the row's elements, input_ids the pad id elsewhere; labels holds the id where the element is trained and ignore_index everywhere
+    else (not shifted: the model shifts).  length[s] elements are in the row, full_length[s] the sample had before the cut, n_trained[s]
+    of the trained ones survived it."""
+    input_ids: np.ndarray  # [R, W] uint32
+    attention_mask: np.ndarray  # [R, W] uint8
+    labels: np.ndarray  # [R, W] int32
+    length: np.ndarray  # uint32[R]
+    full_length: np.ndarray  # uint64[R]
+    n_trained: np.ndarray  # uint32[R]
+
+
+class SamplesDevice(NamedTuple):
+    """`assemble_samples_device`: device pointers (the core's buffers, valid until its next samples call that succeeds) and the figures that
+    size them: input_ids / attention_mask / labels hold n_rows * width elements, length / full_length / n_trained n_rows."""
+    input_ids: int
+    attention_mask: int
+    labels: int
+    length: int
+    full_length: int
+    n_trained: int
     n_rows: int
     width: int
 
@@ -799,6 +845,99 @@ class CoreBPE:
         lengths, row_doc, row_tok, doc_row = _take_u32(out[2], n_rows), _take_u32(out[3], n_rows), _take_u32(out[4], n_rows), _take_u32(out[5], n_docs + 1)
         self._pad_id_needed(has_pad, n_rows, width, lengths)
         return PaddedBatch(input_ids, mask, lengths, row_doc, row_tok, doc_row)
+
+    # ------------------------------------------------------------------ supervised samples (no reference counterpart: the host loop of its users)
+    @staticmethod
+    def _role_table(roles: "Sequence[Role]"):
+        """(n_roles, role_ids uint32[], role_off uint32[2 n + 1], role_train uint8[n]) of a sequence of Role; the limits are the library's to refuse"""
+        ids, off, train = [], [0], []
+        for r in roles:
+            before, after, t = r
+            for run in (before, after):
+                for v in run:
+                    if not 0 <= int(v) <= 0xFFFFFFFF:
+                        raise ValueError("a role's ids must be token ids below 2^32")
+                    ids.append(int(v))
+                off.append(len(ids))
+            train.append(1 if t else 0)
+        return (len(train), np.array(ids if ids else [0], dtype=np.uint32), np.array(off, dtype=np.uint32), np.array(train if train else [0], dtype=np.uint8))
+
+    @staticmethod
+    def _smp_spec(max_length: int, keep: str, padding_side: str, pad_to_multiple_of, bos, eos, pad: int, ignore_index: int) -> "_lib.SmpSpec":
+        if keep not in ("head", "tail"):
+            raise ValueError("keep must be 'head' or 'tail'")
+        if padding_side not in ("right", "left"):
+            raise ValueError("padding_side must be 'right' or 'left'")
+        if pad_to_multiple_of is not None and int(pad_to_multiple_of) < 1:
+            raise ValueError("pad_to_multiple_of must be at least 1 (None: the fixed width max_length)")
+        for name, v in (("max_length", max_length), ("pad_to_multiple_of", pad_to_multiple_of or 0), ("pad", pad)):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise ValueError(f"{name} must fit 32 bits")
+        for name, v in (("bos", bos), ("eos", eos)):
+            if v is not None and not 0 <= int(v) < 0xFFFFFFFF:
+                raise ValueError(f"{name} must be a token id below 2^32 - 1")
+        if not -(1 << 31) <= int(ignore_index) < (1 << 31):
+            raise ValueError("ignore_index must fit a signed 32-bit integer")
+        none = _lib.ROWS_NO_TOKEN
+        flags = (_lib.SMP_KEEP_TAIL if keep == "tail" else 0) | (_lib.SMP_LEFT if padding_side == "left" else 0)
+        return _lib.SmpSpec(int(max_length), int(pad_to_multiple_of or 0), none if bos is None else int(bos), none if eos is None else int(eos), int(pad), int(ignore_index),
+                            flags)
+
+    def assemble_samples_device(self, d_tokens: int, n_tokens: int, d_tok_off: int, n_parts: int, d_part_role: int, d_sample_off: int, n_samples: int,
+                                roles: "Sequence[Role]", *, max_length: int, keep: str = "head", padding_side: str = "right", pad_to_multiple_of: int | None = None,
+                                bos: int | None = None, eos: int | None = None, pad: int = 0, ignore_index: int = -100, stream: int = 0) -> SamplesDevice:
+        """Device-resident supervised samples (tk_assemble_samples_device): pointers to uint32 ids and uint64[n_parts + 1] token offsets on
+        this core's device -- e.g. what `encode_batch_device` returns, which stays intact --, to uint8[n_parts] roles of the parts and to
+        uint64[n_samples + 1] offsets that group the parts into samples; `roles`: a sequence of `Role` (host side).  One row per sample, cut
+        to `max_length` (`keep`: its head or its tail); see `SampleBatch` for the arrays."""
+        self._one_device("assemble_samples_device")
+        spec = self._smp_spec(max_length, keep, padding_side, pad_to_multiple_of, bos, eos, pad, ignore_index)
+        n_roles, ids, off, train = self._role_table(roles)
+        out = [ctypes.c_void_p() for _ in range(6)]
+        cnt = [ctypes.c_uint64() for _ in range(2)]
+        rc = self._L.tk_assemble_samples_device(self._h, d_tokens or None, n_tokens, d_tok_off or None, n_parts, d_part_role or None, d_sample_off or None, n_samples,
+                                                n_roles, ids.ctypes.data, off.ctypes.data, train.ctypes.data, ctypes.byref(spec), stream or None,
+                                                *[ctypes.byref(x) for x in out], *[ctypes.byref(x) for x in cnt])
+        _lib.raise_for(rc)
+        return SamplesDevice(*[x.value or 0 for x in out], *[int(x.value) for x in cnt])
+
+    def encode_batch_samples_packed(self, blob: np.ndarray, doc_off: np.ndarray, allowed_special: AbstractSet[str] | None = None, *, disallowed_special=None,
+                                    part_role, sample_off, roles: "Sequence[Role]", max_length: int, keep: str = "head", padding_side: str = "right",
+                                    pad_to_multiple_of: int | None = None, bos: int | None = None, eos: int | None = None, pad: int = 0,
+                                    ignore_index: int = -100) -> SampleBatch:
+        """`encode_batch_packed` over the parts' text with the samples assembled while the ids are on the device (tk_encode_batch_samples):
+        only the sample arrays come back.  doc_off holds the parts' byte offsets; `part_role` (one index into `roles` per part) and
+        `sample_off` (n_samples + 1 part offsets) group them.  The special-token arguments as in `encode_batch_packed` -- a disallowed
+        special token raises DisallowedSpecialError whose `doc` is the part --, the others as in `assemble_samples_device`."""
+        self._one_device("encode_batch_samples_packed")
+        text, dis, n_parts, _keep = self._batch_args(blob, doc_off, allowed_special, disallowed_special)
+        roles_in = np.asarray(part_role)
+        if roles_in.size and (roles_in.min() < 0 or roles_in.max() > 255):
+            raise ValueError("part_role must hold role indices below 256")
+        part_role = np.ascontiguousarray(roles_in, dtype=np.uint8)
+        sample_off = np.ascontiguousarray(sample_off, dtype=np.uint64)
+        if part_role.ndim != 1 or len(part_role) != n_parts:
+            raise ValueError("part_role must hold one role per part")
+        if sample_off.ndim != 1 or len(sample_off) < 1:
+            raise ValueError("sample_off must hold n_samples + 1 offsets (at least one)")
+        n_samples = len(sample_off) - 1
+        spec = self._smp_spec(max_length, keep, padding_side, pad_to_multiple_of, bos, eos, pad, ignore_index)
+        n_roles, ids, off, train = self._role_table(roles)
+        hit = _lib.SpecialHit()
+        out = [ctypes.c_void_p() for _ in range(6)]
+        cnt = [ctypes.c_uint64() for _ in range(2)]
+        held = part_role if n_parts else np.zeros(1, dtype=np.uint8)
+        rc = self._L.tk_encode_batch_samples(self._h, *text, *dis, held.ctypes.data, sample_off.ctypes.data, n_samples, n_roles, ids.ctypes.data, off.ctypes.data,
+                                             train.ctypes.data, ctypes.byref(spec), *[ctypes.byref(x) for x in out], *[ctypes.byref(x) for x in cnt], ctypes.byref(hit))
+        self._raise_for(rc, hit)
+        n_rows, width = (int(x.value) for x in cnt)
+        n = n_rows * width
+        input_ids = _take_u32(out[0], n).reshape(n_rows, width)
+        mask = _take_u8(out[1], n)
+        if not mask.flags.writeable:  # (a small result comes as a view of a bytes object: the caller gets an array of its own, as for the ids)
+            mask = mask.copy()
+        labels = _take_u32(out[2], n).view(np.int32).reshape(n_rows, width)
+        return SampleBatch(input_ids, mask.reshape(n_rows, width), labels, _take_u32(out[3], n_rows), _take_u64(out[4], n_rows), _take_u32(out[5], n_rows))
 
     # ------------------------------------------------------------------ training (tiktoken/_educational.py: bpe_train)
     def train_bpe_packed(self, blob: np.ndarray, doc_off: np.ndarray, vocab_size: int) -> tuple[np.ndarray, np.ndarray]:

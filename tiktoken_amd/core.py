@@ -303,6 +303,70 @@ class Encoding:
             raise RuntimeError(f"internal error: the device reported the disallowed special token {e.token!r} in document {e.doc} at byte "
                                f"{e.pos}, the host search finds none there") from e
 
+    def encode_ordinary_batch_samples(self, parts: Sequence[str], sample_off, part_role, roles: "Sequence[_tiktoken.Role]", max_length: int, *, keep: str = "head",
+                                      padding_side: str = "right", pad_to_multiple_of: int | None = None, bos: int | None = None, eos: int | None = None,
+                                      pad: int = 0, ignore_index: int = -100) -> "_tiktoken.SampleBatch":
+        """A batch as supervised fine-tuning samples, ignoring special tokens in the text: every part is encoded as ordinary text, sample s
+        is the parts `sample_off[s] .. sample_off[s + 1]`, and its row is `[bos]`, then for each part `roles[part_role[p]].before`, the
+        part's tokens, `.after`, then `[eos]` -- cut to `max_length` at its head or, keep="tail", its tail, padded with `pad` on the right
+        or the left; in one GPU call, only the sample arrays come back.  Returns a `SampleBatch`: `input_ids`, `attention_mask` and `labels`
+        as [R, W] arrays -- labels hold the id where the element is trained (the tokens and the `after` ids of a part whose role trains, the
+        eos behind such a part) and `ignore_index` elsewhere, not shifted --, `length`, `full_length` (before the cut) and `n_trained` (what
+        of the trained elements survived it).  W is `max_length`, or with `pad_to_multiple_of` the longest row rounded up to a multiple of
+        it.  A role's ids are token ids, never text: encode a template's few header and footer strings once."""
+        blob, off = self._pack(parts)
+        return self._core_bpe.encode_batch_samples_packed(blob, off, None, part_role=part_role, sample_off=sample_off, roles=roles, max_length=max_length, keep=keep,
+                                                          padding_side=padding_side, pad_to_multiple_of=pad_to_multiple_of, bos=bos, eos=eos, pad=pad,
+                                                          ignore_index=ignore_index)
+
+    def encode_batch_samples(self, parts: Sequence[str], sample_off, part_role, roles: "Sequence[_tiktoken.Role]", max_length: int, *,
+                             allowed_special: Literal["all"] | AbstractSet[str] = set(),  # noqa: B006
+                             disallowed_special: Literal["all"] | Collection[str] = "all", keep: str = "head", padding_side: str = "right",
+                             pad_to_multiple_of: int | None = None, bos: int | None = None, eos: int | None = None, pad: int = 0,
+                             ignore_index: int = -100) -> "_tiktoken.SampleBatch":
+        """`encode_ordinary_batch_samples` with the special-token arguments of `encode`; the policy holds for all parts.  A part that holds a
+        disallowed special token raises `DisallowedSpecialError` -- a ValueError with the reference's message -- whose `doc` is the part's
+        index, `pos` the byte offset inside it."""
+        rows = dict(part_role=part_role, sample_off=sample_off, roles=roles, max_length=max_length, keep=keep, padding_side=padding_side,
+                    pad_to_multiple_of=pad_to_multiple_of, bos=bos, eos=eos, pad=pad, ignore_index=ignore_index)
+        allowed_special, disallowed_special = self._special_policy(allowed_special, disallowed_special)
+        if not disallowed_special:
+            blob, off = self._pack(parts)
+            return self._core_bpe.encode_batch_samples_packed(blob, off, allowed_special, **rows)
+        if not isinstance(disallowed_special, frozenset):
+            disallowed_special = frozenset(disallowed_special)
+        blob, off, repaired = self._pack_repaired(parts)
+        if repaired or not all(t in self._special_tokens for t in disallowed_special):  # (as encode_batch_packed: the host's search)
+            for i, t in enumerate(parts):
+                if match := _special_token_regex(disallowed_special).search(t):
+                    raise _tiktoken.DisallowedSpecialError(i, len(t[: match.start()].encode("utf-8", "surrogatepass")), match.group())
+            return self._core_bpe.encode_batch_samples_packed(blob, off, allowed_special, **rows)
+        return self._core_bpe.encode_batch_samples_packed(blob, off, allowed_special, disallowed_special=disallowed_special, **rows)
+
+    def encode_chat_batch(self, conversations: "Sequence[Sequence[tuple[str, str]]]", template: "dict[str, _tiktoken.Role]", max_length: int, *,
+                          allowed_special: Literal["all"] | AbstractSet[str] = set(),  # noqa: B006
+                          disallowed_special: Literal["all"] | Collection[str] = "all", keep: str = "head", padding_side: str = "right",
+                          pad_to_multiple_of: int | None = None, bos: int | None = None, eos: int | None = None, pad: int = 0,
+                          ignore_index: int = -100) -> "_tiktoken.SampleBatch":
+        """Conversations as supervised samples: `conversations` is a sequence of sequences of `(role_name, text)`, `template` maps a role
+        name to its `Role` (header ids, footer ids, whether the turn is trained).  Flattens to the arrays of `encode_batch_samples` and
+        calls it: message text is encoded as text, so with the default `disallowed_special="all"` content that spells a special token
+        raises `DisallowedSpecialError` with `doc` = the index of the message among all messages; the template's special tokens go in as
+        ids.  An unknown role name is a ValueError."""
+        names = list(template)
+        index = {name: i for i, name in enumerate(names)}
+        parts, part_role, sample_off = [], [], [0]
+        for conv in conversations:
+            for role, text in conv:
+                if role not in index:
+                    raise ValueError(f"unknown role {role!r}: the template has {names}")
+                parts.append(text)
+                part_role.append(index[role])
+            sample_off.append(len(parts))
+        return self.encode_batch_samples(parts, sample_off, part_role, [template[n] for n in names], max_length, allowed_special=allowed_special,
+                                         disallowed_special=disallowed_special, keep=keep, padding_side=padding_side, pad_to_multiple_of=pad_to_multiple_of, bos=bos,
+                                         eos=eos, pad=pad, ignore_index=ignore_index)
+
     def encode_ordinary_batch(self, text: list[str], *, num_threads: int = 8) -> list[list[int]]:
         """Encode a list of strings, ignoring special tokens (one GPU batch; `num_threads` is kept for
         signature compatibility)."""

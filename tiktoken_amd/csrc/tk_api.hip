@@ -25,6 +25,7 @@
 #include "tk_decode.h"
 #include "tk_offsets.h"
 #include "tk_padded.h"
+#include "tk_samples.h"
 #include "tk_rows.h"
 #include "tk_train.h"
 #include "tk_fused.h"
@@ -274,6 +275,10 @@ struct tk_core {
     // Padded inputs (tk_padded.h), apart from everything above: d_pad: ids and mask of every position; d_pad_row: len, row_doc, row_tok of
     // every row; d_pad_doc: doc_row; d_pad_cnt: the TK_PAD_WORDS report words and the doc_row a call counts in until it is accepted.
     Buf d_pad, d_pad_row, d_pad_doc, d_pad_cnt;
+    // Supervised samples (tk_samples.h), apart from everything above: d_smp: ids, labels and mask of every position; d_smp_row: full_len, len,
+    // n_trained of every sample; d_smp_cnt: the TK_SMP_WORDS report words, the role table, pstart and the per-sample figures a call counts in
+    // until it is accepted; d_smp_in: part_role and sample_off of a host-text call.
+    Buf d_smp, d_smp_row, d_smp_cnt, d_smp_in;
     // Small calls (tk_k_small) do not take `mu`: the reference's normal use is several threads on one Encoding (core.py:175, a thread pool
     // over encode; lib.rs:232-238 keeps a regex per thread for it), and a small call needs nothing of the shared workspace -- a slot of its
     // own (page-locked text and result buffers the kernel reads and writes directly, merge scratch, a stream) is all.  A caller takes a
@@ -2938,6 +2943,197 @@ extern "C" int tk_encode_batch_padded(tk_core* c, const uint8_t* utf8, const uin
             *row_doc_out = rd.release();
             *row_tok_out = rt.release();
             *doc_row_out = dr.release();
+            *n_rows_out = v.n_rows;
+            *width_out = v.width;
+            return TK_OK;
+        });
+}
+
+// ------------------------------------------------------------------------------------------
+// Supervised samples (tk_samples.h): a packed batch of parts on the device -> one row per sample, ids, mask and labels as [R, W].
+// ------------------------------------------------------------------------------------------
+static_assert(TK_SMP_KEEP_TAIL == TK_SMPF_KEEP_TAIL && TK_SMP_LEFT == TK_SMPF_LEFT, "tk_smp_spec flags");
+struct SmpRoles {  // the role table as the caller gave it (host memory)
+    uint32_t n_roles;
+    const uint32_t *ids, *off;
+    const uint8_t* train;
+};
+struct SmpView {  // device buffers of the core, valid until its next samples call that succeeds
+    uint32_t* ids = nullptr;
+    uint8_t* mask = nullptr;
+    int32_t* labels = nullptr;
+    uint32_t *len = nullptr, *n_trained = nullptr;
+    uint64_t* full = nullptr;
+    uint64_t n_rows = 0, width = 0;
+};
+static int smp_refusal(int why) {
+    switch (why) {
+        case 0: return TK_OK;
+        case 1: return fail(TK_VALUE_ERROR, "max_len must be at least 1");
+        case 2: return fail(TK_VALUE_ERROR, "n_roles is 0 while there are parts");
+        case 3: return fail(TK_VALUE_ERROR, "the role table holds at most 256 roles");
+        case 4: return fail(TK_VALUE_ERROR, "role_off must ascend from 0");
+        case 5: return fail(TK_VALUE_ERROR, "the role table holds at most 4096 ids");
+        case 6: return fail(TK_VALUE_ERROR, "2^32 tokens or more: the positions of the rows are 32-bit");
+        case 7: return fail(TK_VALUE_ERROR, "too many parts: part indices are 32-bit");
+        case 8: return fail(TK_VALUE_ERROR, "too many samples: the row indices are 32-bit");
+        case 9: return fail(TK_VALUE_ERROR, "the parts have 2^32 elements or more: the positions of the rows are 32-bit");
+        default: return fail(TK_VALUE_ERROR, "rows times width reaches 2^32: the positions are 32-bit");
+    }
+}
+// What of a samples call can be refused without looking at the batch (the host-text entry asks before it encodes anything).
+static int smp_check_spec(const tk_smp_spec* spec, const SmpRoles& roles, uint64_t n_tokens, uint64_t n_parts, uint64_t n_samples, TkSmp* p) {
+    if (!spec) return fail(TK_VALUE_ERROR, "null argument");
+    if (spec->flags & ~(TK_SMP_KEEP_TAIL | TK_SMP_LEFT)) return fail(TK_VALUE_ERROR, "tk_smp_spec: unknown flag");
+    if (roles.n_roles && (!roles.off || !roles.train)) return fail(TK_VALUE_ERROR, "null argument");
+    TRY(smp_refusal(tk_smp_shape(n_tokens, n_parts, n_samples, roles.n_roles, roles.off, spec->max_len, spec->width_multiple, spec->bos_id, spec->eos_id, spec->pad_id,
+                                 spec->ignore_index, spec->flags, p)));
+    if (roles.n_roles && roles.off[2 * roles.n_roles] && !roles.ids) return fail(TK_VALUE_ERROR, "null argument");
+    return TK_OK;
+}
+// smp_run: the caller holds c->mu.  The host waits twice, as pad_run does: for the report words -- what the count pass has to say about
+// the caller's arrays, the elements of all parts, the longest row: W and the sizes of the outputs follow from them --, and at the end.  A
+// call that is refused has written into d_smp_cnt only: the previous result stays whole.
+static int smp_run(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n, const uint64_t* d_tok_off, uint64_t n_parts, const uint8_t* d_part_role,
+                   const uint64_t* d_sample_off, uint64_t n_samples, const SmpRoles& roles, const tk_smp_spec* spec, SmpView* out) {
+    TkSmp p;
+    TRY(smp_check_spec(spec, roles, n, n_parts, n_samples, &p));
+    // scratch: the report words | role_off, role_ids, role_train | pstart | full | len | n_trained (every array at a multiple of 16 bytes)
+    const uint32_t n_off = 2 * roles.n_roles + 1, n_ids = roles.n_roles ? roles.off[2 * roles.n_roles] : 0;
+    auto up16 = [](uint64_t x) { return (x + 15) & ~15ull; };
+    const uint64_t at_off = up16(TK_SMP_WORDS * 8), at_ids = at_off + up16(n_off * 4ull), at_train = at_ids + up16(n_ids * 4ull), at_ps = at_train + up16(roles.n_roles);
+    const uint64_t at_full = at_ps + up16((n_parts + 1) * 8), at_len = at_full + up16(n_samples * 8), at_ntr = at_len + up16(n_samples * 4);
+    TRY(ensure(c->d_smp_cnt, at_ntr + up16(n_samples * 4)));
+    uint8_t* base = c->d_smp_cnt.as<uint8_t>();
+    unsigned long long* words = (unsigned long long*)base;
+    uint64_t* pstart = (uint64_t*)(base + at_ps);
+    uint64_t* full = (uint64_t*)(base + at_full);
+    uint32_t *len = (uint32_t*)(base + at_len), *ntr = (uint32_t*)(base + at_ntr);
+    const TkSmpTable tab{(const uint32_t*)(base + at_off), (const uint32_t*)(base + at_ids), base + at_train, n_ids};
+    std::vector<uint8_t> table(at_ps - at_off, 0);  // (role_off of no roles: one 0)
+    if (roles.n_roles) {
+        memcpy(table.data(), roles.off, n_off * 4ull);
+        if (n_ids) memcpy(table.data() + (at_ids - at_off), roles.ids, n_ids * 4ull);
+        memcpy(table.data() + (at_train - at_off), roles.train, roles.n_roles);
+    }
+    HIPCHK(hipMemcpyAsync(base + at_off, table.data(), table.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(words, 0xFF, 8 * (TK_SMP_BAD_ROLE + 1), s));  // (the three words that keep the lowest offender: all ones = none)
+    HIPCHK(hipMemsetAsync(words + TK_SMP_TOTAL, 0, 16, s));
+    const uint64_t n_entries = std::max(n_parts, n_samples) + 1;
+    TRY(timed(c, s, "tk_k_smp_count", [&] {
+        hipLaunchKernelGGL(tk_k_smp_count, dim3(grid_for(n_entries, 256, 4096)), dim3(256), 0, s, d_tok_off, d_sample_off, d_part_role, tab, p, pstart, words);
+    }));
+    TRY(timed(c, s, "tk_k_smp_scan", [&] { hipLaunchKernelGGL(tk_k_smp_scan, dim3(1), dim3(1024), 0, s, pstart, n_parts, words); }));
+    if (n_samples)
+        TRY(timed(c, s, "tk_k_smp_samples", [&] {
+            hipLaunchKernelGGL(tk_k_smp_samples, dim3(grid_for(n_samples, 256, 4096)), dim3(256), 0, s, d_sample_off, d_part_role, pstart, tab, p, full, len, ntr, words);
+        }));
+    unsigned long long got[TK_SMP_WORDS];
+    TRY(report_read(words, got, TK_SMP_WORDS, s));  // (waits for the table's copy too: `table` may go)
+    if (got[TK_SMP_BAD_SOFF] != ~0ull) {
+        const std::string d = std::to_string(got[TK_SMP_BAD_SOFF] >> 2);
+        switch (got[TK_SMP_BAD_SOFF] & 3u) {
+            case 1: return fail(TK_VALUE_ERROR, "sample_off[0] must be 0 (sample " + d + ")");
+            case 2: return fail(TK_VALUE_ERROR, "sample_off must be non-decreasing: sample " + d + " ends before it starts");
+            default: return fail(TK_VALUE_ERROR, "sample_off must end at n_parts: sample " + d + " ends elsewhere");
+        }
+    }
+    if (got[TK_SMP_BAD_ROLE] != ~0ull) return fail(TK_VALUE_ERROR, "part_role must be below n_roles: part " + std::to_string(got[TK_SMP_BAD_ROLE]) + " has no such role");
+    TRY(smp_refusal(tk_smp_size(&p, got[TK_SMP_TOTAL], (uint32_t)got[TK_SMP_LONGEST])));
+    const uint64_t N = p.R * p.W, n8 = (N + 7) & ~7ull, r4 = (p.R + 3) & ~3ull;  // (every array starts at a multiple of 16 bytes)
+    const uint64_t nb = (N + TK_DEC_BLOCK - 1) / TK_DEC_BLOCK;
+    TRY(ensure(c->d_smp, n8 * 9 + 64));
+    TRY(ensure(c->d_smp_row, r4 * 16 + 64));
+    out->ids = c->d_smp.as<uint32_t>();
+    out->labels = (int32_t*)(out->ids + n8);
+    out->mask = (uint8_t*)(out->labels + n8);
+    out->full = c->d_smp_row.as<uint64_t>();
+    out->len = (uint32_t*)(out->full + r4);
+    out->n_trained = out->len + r4;
+    out->n_rows = p.R;
+    out->width = p.W;
+    if (p.R) {
+        HIPCHK(hipMemcpyAsync(out->full, full, p.R * 8, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(out->len, len, p.R * 4, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(out->n_trained, ntr, p.R * 4, hipMemcpyDeviceToDevice, s));
+    }
+    if (nb)
+        TRY(timed(c, s, "tk_k_smp_write", [&] {
+            hipLaunchKernelGGL(tk_k_smp_write, dim3((uint32_t)nb), dim3(256), 0, s, d_tok, d_tok_off, d_sample_off, d_part_role, pstart, tab, p, out->ids, out->labels, out->mask);
+        }));
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    return TK_OK;
+}
+
+extern "C" int tk_assemble_samples_device(tk_core* c, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_parts, const void* d_part_role,
+                                          const void* d_sample_off, uint64_t n_samples, uint32_t n_roles, const uint32_t* role_ids, const uint32_t* role_off,
+                                          const uint8_t* role_train, const tk_smp_spec* spec, void* stream, const uint32_t** d_ids_out, const uint8_t** d_mask_out,
+                                          const int32_t** d_labels_out, const uint32_t** d_len_out, const uint64_t** d_full_len_out, const uint32_t** d_n_trained_out,
+                                          uint64_t* n_rows_out, uint64_t* width_out) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if (!d_tok_off || !d_sample_off || (n_tokens && !d_tokens) || (n_parts && !d_part_role) || !spec) return fail(TK_VALUE_ERROR, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    SmpView v;
+    const SmpRoles roles{n_roles, role_ids, role_off, role_train};
+    TRY(drained(c, [&] {
+        return smp_run(c, stream ? (hipStream_t)stream : c->stream, (const uint32_t*)d_tokens, n_tokens, (const uint64_t*)d_tok_off, n_parts, (const uint8_t*)d_part_role,
+                       (const uint64_t*)d_sample_off, n_samples, roles, spec, &v);
+    }));
+    if (d_ids_out) *d_ids_out = v.ids;
+    if (d_mask_out) *d_mask_out = v.mask;
+    if (d_labels_out) *d_labels_out = v.labels;
+    if (d_len_out) *d_len_out = v.len;
+    if (d_full_len_out) *d_full_len_out = v.full;
+    if (d_n_trained_out) *d_n_trained_out = v.n_trained;
+    if (n_rows_out) *n_rows_out = v.n_rows;
+    if (width_out) *width_out = v.width;
+    return TK_OK;
+}
+
+// tk_encode_batch (tk_encode_batch_checked with disallowed ids) over the parts' text with the samples assembled from the tokens it has just
+// produced: the passes run over the ids while they are still on the device, and only the sample arrays travel back.
+extern "C" int tk_encode_batch_samples(tk_core* c, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_parts, int use_special, const uint32_t* allowed_ids,
+                                       uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed, const uint8_t* part_role, const uint64_t* sample_off,
+                                       uint64_t n_samples, uint32_t n_roles, const uint32_t* role_ids, const uint32_t* role_off, const uint8_t* role_train,
+                                       const tk_smp_spec* spec, uint32_t** ids_out, uint8_t** mask_out, int32_t** labels_out, uint32_t** len_out, uint64_t** full_len_out,
+                                       uint32_t** n_trained_out, uint64_t* n_rows_out, uint64_t* width_out, tk_special_hit* hit) {
+    SmpView v;
+    const SmpRoles roles{n_roles, role_ids, role_off, role_train};
+    return encode_batch_pass(
+        c, utf8, doc_off, n_parts, use_special, allowed_ids, n_allowed, disallowed_ids, n_disallowed, hit,
+        spec && sample_off && (part_role || !n_parts) && ids_out && mask_out && labels_out && len_out && full_len_out && n_trained_out && n_rows_out && width_out,
+        [&] {  // (before the encode, not after it)
+            TkSmp p;
+            return smp_check_spec(spec, roles, 0, n_parts, n_samples, &p);
+        },
+        [&](uint64_t n) {
+            const uint64_t at_so = (n_parts + 15) & ~15ull;  // part_role, then sample_off at a multiple of 16 bytes
+            TRY(ensure(c->d_smp_in, at_so + (n_samples + 1) * 8));
+            uint8_t* in = c->d_smp_in.as<uint8_t>();
+            if (n_parts) HIPCHK(hipMemcpyAsync(in, part_role, n_parts, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(in + at_so, sample_off, (n_samples + 1) * 8, hipMemcpyHostToDevice, c->stream));
+            return smp_run(c, c->stream, c->out_tokens.as<uint32_t>(), n, c->out_tok_off.as<uint64_t>(), n_parts, in, (const uint64_t*)(in + at_so), n_samples, roles, spec, &v);
+        },
+        [&](uint64_t) -> int {
+            const uint64_t N = v.n_rows * v.width;
+            HostResult<uint32_t> ids, len, ntr;
+            HostResult<uint8_t> mask;
+            HostResult<int32_t> labels;
+            HostResult<uint64_t> full;
+            TRY(result_from_device(ids, v.ids, N));
+            TRY(result_from_device(mask, v.mask, N));
+            TRY(result_from_device(labels, v.labels, N));
+            TRY(result_from_device(len, v.len, v.n_rows));
+            TRY(result_from_device(full, v.full, v.n_rows));
+            TRY(result_from_device(ntr, v.n_trained, v.n_rows));
+            *ids_out = ids.release();
+            *mask_out = mask.release();
+            *labels_out = labels.release();
+            *len_out = len.release();
+            *full_len_out = full.release();
+            *n_trained_out = ntr.release();
             *n_rows_out = v.n_rows;
             *width_out = v.width;
             return TK_OK;
