@@ -9,32 +9,24 @@
 
 extern "C" {
 // The figures of a call: counts = {R, W}.  Returns 0; 1 .. 8: tk_pad_shape's / tk_pad_size's refusal; 16 + tk_rows_bad_key: tok_off is
-// refused.  doc_row: room for n_docs + 1.  Nothing else is written: the caller sizes the other arrays from counts and calls padded_sim.
+// refused; -1: an index out of bounds.  doc_row: room for n_docs + 1.  Nothing else is written: the caller sizes the other arrays from counts and calls padded_sim.
 int64_t padded_sim_count(uint64_t T, const uint64_t* tok_off, uint64_t n_docs, uint32_t max_len, uint32_t stride, uint32_t width_multiple, uint32_t bos, uint32_t eos,
                          uint32_t pad, uint32_t flags, uint32_t* doc_row, uint64_t* counts) {
     TkPad p;
     const int refused = tk_pad_shape(T, n_docs, max_len, stride, width_multiple, bos, eos, pad, flags, &p);
     if (refused) return refused;
     // tk_k_pad_count
+    bool oob = false;
+    const SimOffsets off{tok_off, n_docs, &oob};
     unsigned long long bad = ~0ull;
     uint32_t longest = 0;
     for (uint64_t d = 0; d <= n_docs; ++d) {
-        uint64_t a, b;
-        const uint32_t why = tk_rows_off_check(tok_off, d, p.n_docs, p.n_tokens, &a, &b, &bad);
-        if (d < n_docs) {
-            const uint64_t n = why ? 0 : b - a;
-            doc_row[d] = (uint32_t)tk_pad_windows(p, n);
-            const uint32_t l = tk_pad_longest(p, n);
-            longest = l > longest ? l : longest;
-        }
+        const uint32_t l = tk_pad_count_entry(p, off, d, doc_row, &bad);
+        longest = l > longest ? l : longest;
     }
+    if (oob) return -1;
     // tk_k_pad_scan
-    uint64_t carry = 0;
-    for (uint64_t d = 0; d < n_docs; ++d) {
-        const uint64_t at = carry;
-        carry += doc_row[d];
-        doc_row[d] = (uint32_t)at;
-    }
+    const uint64_t carry = sim_scan(doc_row, n_docs);
     doc_row[n_docs] = (uint32_t)carry;
     // the host
     if (bad != ~0ull) return 16 + (int64_t)bad;
@@ -44,29 +36,26 @@ int64_t padded_sim_count(uint64_t T, const uint64_t* tok_off, uint64_t n_docs, u
     return too_big;
 }
 
-// tk_k_pad_rows and tk_k_pad_write after padded_sim_count has accepted the call and left doc_row: the per-row pass statement by statement,
-// the write pass through tk_pad_block_docs and tk_pad_lane -- the functions the kernel itself calls -- with the kernel's stores.  ids /
-// mask: room for R * W, len / row_doc / row_tok: R.  -1 if a token index or a document index lies out of bounds.
-int64_t padded_sim(const uint32_t* tokens, uint64_t T, const uint64_t* tok_off, uint64_t n_docs, uint32_t max_len, uint32_t stride, uint32_t width_multiple, uint32_t bos,
-                   uint32_t eos, uint32_t pad, uint32_t flags, uint32_t block, const uint32_t* doc_row, uint64_t R, uint32_t W, uint32_t* ids_out, uint8_t* mask_out,
-                   uint32_t* len, uint32_t* row_doc, uint32_t* row_tok) {
+// tk_k_pad_rows and tk_k_pad_write after padded_sim_count has accepted the call and left doc_row: through tk_pad_row_entry,
+// tk_pad_block_docs and tk_pad_lane -- the functions the kernels themselves call -- with the kernels' stores.  ids / mask: room for R * W,
+// len / row_doc / row_tok: R.  tok_off holds off_len entries and doc_row row_len (n_docs + 1 each, unless a test hands in less): -1 if an
+// index into them or into tokens lies out of bounds.
+int64_t padded_sim(const uint32_t* tokens, uint64_t T, const uint64_t* tok_off_in, uint64_t off_len, uint64_t n_docs, uint32_t max_len, uint32_t stride, uint32_t width_multiple,
+                   uint32_t bos, uint32_t eos, uint32_t pad, uint32_t flags, uint32_t block, const uint32_t* doc_row_in, uint64_t row_len, uint64_t R, uint32_t W,
+                   uint32_t* ids_out, uint8_t* mask_out, uint32_t* len, uint32_t* row_doc, uint32_t* row_tok) {
     TkPad p;
     if (tk_pad_shape(T, n_docs, max_len, stride, width_multiple, bos, eos, pad, flags, &p)) return -3;
     p.R = R;
     p.W = W;  // (what padded_sim_count settled)
-    // tk_k_pad_rows
-    for (uint64_t r = 0; r < p.R; ++r) {
-        const uint64_t d = tk_pad_doc_of_row(doc_row, 0, p.n_docs, r);
-        if (d >= n_docs) return -1;
-        TkPadRow w;
-        tk_pad_row_load(p, tok_off, doc_row, d, r, &w);
-        len[r] = w.len;
-        row_doc[r] = (uint32_t)w.d;
-        row_tok[r] = (uint32_t)w.tok;
-    }
-    // tk_k_pad_write
     bool oob = false;
+    if (!off_len) return -1;
+    const SimOffsets tok_off{tok_off_in, off_len - 1, &oob};  // (entries [0, off_len - 1])
+    const SimArray<uint32_t> doc_row{doc_row_in, row_len, &oob};
     const SimTokens tok{tokens, T, &oob};
+    // tk_k_pad_rows
+    for (uint64_t r = 0; r < p.R; ++r) tk_pad_row_entry(p, tok_off, doc_row, r, len, row_doc, row_tok);
+    if (oob) return -1;  // (nothing further is computed from what was not read)
+    // tk_k_pad_write
     const uint32_t N = (uint32_t)(p.R * p.W), nb = (uint32_t)(((uint64_t)N + block - 1) / block);
     for (uint32_t blk = 0; blk < nb; ++blk) {
         const uint32_t b0 = blk * block;

@@ -10,6 +10,15 @@
 #include "sim_readers.h"
 
 extern "C" {
+// The search every pass shares (tk_last_le) over `n` keys, and the width rule of the padded and the samples passes, each on its own
+int64_t rows_sim_last_le(const uint64_t* keys, uint64_t n, uint64_t lo, uint64_t hi, uint64_t x) {
+    bool oob = false;
+    const SimArray<uint64_t> k{keys, n, &oob};
+    const uint64_t at = tk_last_le(k, lo, hi, x);
+    return oob ? -1 : (int64_t)at;
+}
+uint32_t rows_sim_row_width(uint32_t max_len, uint32_t width_multiple, uint32_t longest) { return tk_row_width(max_len, width_multiple, longest); }
+
 // The passes in the kernels' order, with the kernels' stores.  ids / doc / pos: room for M (+ 8), cu: n_docs + R + 4, row_seg: R + 1;
 // counts: {R, n_segs, S, n_tail, M}.  Every access to tokens and tok_off is checked here: -1 if one lies out of bounds.
 // Returns 0; 1 .. 3: tk_rows_shape's refusal; 16 + tk_rows_bad_key: tok_off is refused.
@@ -46,12 +55,7 @@ int64_t rows_sim(const uint32_t* tokens_in, uint64_t T, const uint64_t* tok_off_
             cnt[blk] += (uint32_t)__builtin_popcount(bits);
         }
     // tk_k_rows_scan
-    uint64_t carry = 0;
-    for (uint64_t blk = 0; blk < nb; ++blk) {
-        const uint64_t at = carry;
-        carry += cnt[blk];
-        cnt[blk] = at;
-    }
+    const uint64_t carry = sim_scan(cnt.data(), nb);
     if (carry > n_docs + r.R + 3) return -1;
     cu[carry] = (uint32_t)r.M;
     if (r.R * r.seq_len == r.M) row_seg[r.R] = (uint32_t)carry;

@@ -13,20 +13,6 @@
 #include "sim_readers.h"
 
 namespace {
-// entries [0, n) of an array; an index out of bounds sets *oob instead of being read
-template <class T>
-struct SimArray {
-    const T* p;
-    uint64_t n;
-    bool* oob;
-    T operator[](uint64_t i) const {
-        if (i >= n) {
-            *oob = true;
-            return 0;
-        }
-        return p[i];
-    }
-};
 using SimRoles = TkSmpRoles<SimArray<uint32_t>, SimArray<uint32_t>, SimArray<uint8_t>>;
 using SimIn = TkSmpIn<SimOffsets, SimOffsets, SimArray<uint8_t>, SimArray<uint64_t>>;
 }  // namespace
@@ -52,24 +38,15 @@ int64_t samples_sim_count(uint64_t T, const uint64_t* tok_off, uint64_t n_parts,
     const uint64_t n = n_parts > n_samples ? n_parts : n_samples;
     for (uint64_t i = 0; i <= n; ++i) tk_smp_count_entry(p, toff, soff, roles, roff, i, pstart, words);
     // tk_k_smp_scan
-    uint64_t carry = 0;
-    for (uint64_t q = 0; q < n_parts; ++q) {
-        const uint64_t at = carry;
-        carry += pstart[q];
-        pstart[q] = at;
-    }
+    const uint64_t carry = sim_scan(pstart, n_parts);
     pstart[n_parts] = carry;
     words[TK_SMP_TOTAL] = carry;
     // tk_k_smp_samples
     if (!tk_smp_reported(words)) {
         const SimArray<uint64_t> ps{pstart, n_parts + 1, &oob};
         for (uint64_t s = 0; s < n_samples; ++s) {
-            TkSmpRow w;
-            tk_smp_row_load(p, soff, ps, s, &w);
-            full[s] = w.full;
-            len[s] = w.len;
-            n_trained[s] = tk_smp_n_trained(p, w, ps, roles, t);
-            if (w.len > words[TK_SMP_LONGEST]) words[TK_SMP_LONGEST] = w.len;
+            const uint32_t l = tk_smp_sample_entry(p, soff, ps, roles, t, s, full, len, n_trained);
+            if (l > words[TK_SMP_LONGEST]) words[TK_SMP_LONGEST] = l;
         }
     }
     if (oob) return -1;

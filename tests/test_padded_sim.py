@@ -23,7 +23,7 @@ def lib():
         L.padded_sim_count.restype = ctypes.c_int64
         L.padded_sim_count.argtypes = [u64, vp, u64, u32, u32, u32, u32, u32, u32, u32, vp, vp]
         L.padded_sim.restype = ctypes.c_int64
-        L.padded_sim.argtypes = [vp, u64, vp, u64, u32, u32, u32, u32, u32, u32, u32, u32, vp, u64, u32, vp, vp, vp, vp, vp]
+        L.padded_sim.argtypes = [vp, u64, vp, u64, u64, u32, u32, u32, u32, u32, u32, u32, u32, vp, u64, u64, u32, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -32,8 +32,9 @@ def flags_of(windows=False, keep_tail=False, left=False):
     return (WINDOWS if windows else 0) | (KEEP_TAIL if keep_tail else 0) | (LEFT if left else 0)
 
 
-def run_sim(tokens, tok_off, max_len, block, *, stride=0, width_multiple=0, bos=None, eos=None, pad=0, T=None, **fl):
-    """(rc, Padded or None) of the simulation; the arrays sit between guard words that must survive."""
+def run_sim(tokens, tok_off, max_len, block, *, stride=0, width_multiple=0, bos=None, eos=None, pad=0, T=None, short=None, **fl):
+    """(rc, Padded or None) of the simulation; the arrays sit between guard words that must survive.  short: "tok_off" or "doc_row" -- the
+    write passes get that array without its last entry, as an array of its own of exactly that size."""
     tokens = np.ascontiguousarray(tokens, np.uint32)
     tok_off = np.ascontiguousarray(tok_off, np.uint64)
     T, n_docs = len(tokens) if T is None else T, len(tok_off) - 1
@@ -50,8 +51,10 @@ def run_sim(tokens, tok_off, max_len, block, *, stride=0, width_multiple=0, bos=
     mask = np.full(R * W + 1, 0xAB, np.uint8)
     ln, row_doc, row_tok = (np.full(R + 1, G, np.uint32) for _ in range(3))
     src = tokens if T else np.zeros(1, np.uint32)
-    rc = lib().padded_sim(src.ctypes.data, T, tok_off.ctypes.data, n_docs, *spec, block, doc_row.ctypes.data, R, W, ids.ctypes.data, mask.ctypes.data, ln.ctypes.data,
-                          row_doc.ctypes.data, row_tok.ctypes.data)
+    off_in = tok_off[:-1].copy() if short == "tok_off" else tok_off
+    rows_in = doc_row[:n_docs].copy() if short == "doc_row" else doc_row
+    rc = lib().padded_sim(src.ctypes.data, T, off_in.ctypes.data, len(off_in), n_docs, *spec, block, rows_in.ctypes.data, min(len(rows_in), n_docs + 1), R, W, ids.ctypes.data,
+                          mask.ctypes.data, ln.ctypes.data, row_doc.ctypes.data, row_tok.ctypes.data)
     if rc:
         return rc, None
     assert ids[-1] == G and mask[-1] == 0xAB and ln[-1] == G and row_doc[-1] == G and row_tok[-1] == G and doc_row[-1] == G
@@ -214,3 +217,27 @@ def test_refusals():
                 rc, _ = run_sim(tokens, np.array(bad, np.uint64), 4 + (bos is not None) + (eos is not None), 16, bos=bos, eos=eos, **kw)
                 assert rc == 16 + (doc << 2 | why), (bad, rc)
     assert run_sim(np.zeros(0, np.uint32), np.array([3], np.uint64), 4, 16, eos=1)[0] == 16 + 1  # no documents, tok_off = [3]
+
+
+@pytest.mark.parametrize("short", ("tok_off", "doc_row"))
+def test_an_array_one_entry_too_short_is_reported_not_read(short):
+    """tok_off and doc_row reach the rule functions through readers that check every index.  With the last entry missing (the array is built
+    at exactly that size) the per-row pass is the first to ask for it -- tk_pad_row_entry reads entry d + 1 of the last document -- and the
+    simulation says -1 there instead of reading behind the array; the write pass, which would ask for the same entry, is not reached."""
+    tokens, tok_off = pr.pack_docs([[1, 2, 3], [], [4, 5, 6, 7, 8, 9, 10]])
+    for kw in (dict(), dict(windows=True, stride=1), dict(keep_tail=True, left=True, width_multiple=8)):
+        for block in BLOCKS:
+            assert run_sim(tokens, tok_off, 4, block, eos=9, **kw)[0] == 0
+            assert run_sim(tokens, tok_off, 4, block, eos=9, short=short, **kw)[0] == -1
+
+
+def test_an_offending_entry_counts_as_an_empty_document():
+    """tk_pad_count_entry takes no length from an entry it has reported: the document owns one row, as an empty one does, so the row
+    counts stay small whatever tok_off holds (a length of b - a with a > b would be close to 2^64)"""
+    doc_row, counts = np.full(5, 0xDEADBEEF, np.uint32), np.zeros(2, np.uint64)
+    for bad, why in (([0, 4, 3, 6], 1 << 2 | 2), ([0, 4, 1 << 63, 6], 2 << 2 | 2)):  # documents of 4, (offending), 3 tokens; of 4, 2^63 - 4, (offending)
+        off = np.array(bad, np.uint64)
+        rc = lib().padded_sim_count(6, off.ctypes.data, 3, 3, 1, 0, pr.NONE, pr.NONE, 0, WINDOWS, doc_row.ctypes.data, counts.ctypes.data)
+        assert rc == 16 + why
+        rows = [1 + -(-(n - 3) // 2) if n > 3 else 1 for n in (4, 0 if why >> 2 == 1 else (1 << 63) - 4, 3 if why >> 2 == 1 else 0)]  # c = 3, step = 2
+        assert doc_row.tolist() == [0, rows[0], (rows[0] + rows[1]) & 0xFFFFFFFF, sum(rows) & 0xFFFFFFFF, 0xDEADBEEF], (bad, doc_row.tolist())

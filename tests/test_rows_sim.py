@@ -2,6 +2,7 @@
 for the host and drives it the way the kernels do -- lanes of eight positions, workgroups of 8, 16 and 2048; the write pass runs through
 tk_rows_lane, the function the kernel itself calls.  Compared with the numpy restatement of the rule in tests/rows_ref.py, which is written
 from the rule's description (include/tiktoken_amd.h), not from the kernels."""
+import bisect
 import ctypes
 
 import numpy as np
@@ -21,6 +22,10 @@ def lib():
         vp, u64, u32 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32
         L.rows_sim.restype = ctypes.c_int64
         L.rows_sim.argtypes = [vp, u64, vp, u64, u32, u32, u32, u32, ctypes.c_int, u32, vp, vp, vp, vp, vp, vp]
+        L.rows_sim_last_le.restype = ctypes.c_int64
+        L.rows_sim_last_le.argtypes = [vp, u64, u64, u64, u64]
+        L.rows_sim_row_width.restype = u32
+        L.rows_sim_row_width.argtypes = [u32, u32, u32]
         _lib = L
     return _lib
 
@@ -168,3 +173,43 @@ def test_refusals():
                 rc, _ = run_sim(tokens, np.array(bad, np.uint64), 4, bos, eos, 0, False, block)
                 assert rc == 16 + (doc << 2 | why), (bad, rc)
     assert run_sim(np.zeros(0, np.uint32), np.array([3], np.uint64), 4, None, 1, 0, False, 8)[0] == 16 + 1  # no documents, tok_off = [3]
+
+
+def test_the_shared_search_on_its_own():
+    """tk_last_le, the one search of the row, padded and samples passes: the last index in [lo, hi) whose key is <= x, lo if there is none
+    -- bisect_right(keys, x, lo, hi) - 1, clamped to lo.  The keys are handed in as an array of exactly `hi` entries behind a reader that
+    checks the index: -1 would say the search looked outside its window."""
+    def check(keys, lo, hi, xs):
+        held = np.array(keys[:hi] if hi else [0], np.uint64)
+        for x in xs:
+            want = max(bisect.bisect_right(keys, x, lo, hi) - 1, lo)
+            assert lib().rows_sim_last_le(held.ctypes.data, hi, lo, hi, x) == want, (keys, lo, hi, x)
+
+    def around(keys):
+        return sorted({x for k in keys for x in (k - 1, k, k + 1) if x >= 0} | {0, 1 << 40})
+
+    for lo in (0, 3):  # windows of 0, 1 and 2 entries; x below keys[lo], at every key, at and above the last
+        front = [1, 1, 2][:lo]
+        for window in ([], [5], [5, 9], [5, 5]):
+            keys = front + window
+            check(keys, lo, len(keys), around(keys + [5]))
+    for run in (2, 5):  # runs of equal keys at the front, in the middle and at the end of the window
+        for lo in (0, 2):
+            front = [0, 3][:lo]
+            for keys in ([7] * run + [9, 12, 20], [4, 6] + [7] * run + [9, 12], [4, 5, 6] + [7] * run):
+                check(front + keys, lo, lo + len(keys), around(keys))
+    rng = np.random.default_rng(0x1E)
+    keys = np.cumsum(rng.choice([0, 0, 1, 3, 50], size=300)).tolist()
+    check(keys, 0, 300, around(keys))
+    check(keys, 17, 290, around(keys))
+
+
+def test_the_width_rule_on_its_own():
+    """tk_row_width against the expression of padded_ref.py / samples_ref.py"""
+    for max_len in (1, 16, 100):
+        for wm in (0, 1, 8):
+            for longest in sorted({0, 1, max_len - 1, max_len, 8 * (max_len // 8) + 1 if max_len > 8 else max_len}):  # (the last: its round-up exceeds max_len)
+                want = max_len if wm == 0 else min(max_len, -(-longest // wm) * wm)
+                assert lib().rows_sim_row_width(max_len, wm, longest) == want, (max_len, wm, longest)
+    assert lib().rows_sim_row_width(100, 8, 97) == 100 and lib().rows_sim_row_width(16, 8, 9) == 16 and lib().rows_sim_row_width(100, 8, 9) == 16
+    assert lib().rows_sim_row_width(0xFFFFFFFF, 0x80000000, 0x80000001) == 0xFFFFFFFF  # (the round-up is 2^32: computed in 64 bits)

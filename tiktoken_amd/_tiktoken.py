@@ -729,6 +729,32 @@ class CoreBPE:
         none = _lib.ROWS_NO_TOKEN
         return none if bos is None else int(bos), none if eos is None else int(eos), 0 if pad is None else int(pad), pad is not None, dtype == np.uint16
 
+    @staticmethod
+    def _width_spec(keep: str, padding_side: str, pad_to_multiple_of, **fit32) -> "tuple[bool, bool, int]":
+        """What tk_pad_spec and tk_smp_spec share: (keep the tail, pad on the left, width_multiple); `fit32`: what else must fit 32 bits"""
+        if keep not in ("head", "tail"):
+            raise ValueError("keep must be 'head' or 'tail'")
+        if padding_side not in ("right", "left"):
+            raise ValueError("padding_side must be 'right' or 'left'")
+        if pad_to_multiple_of is not None and int(pad_to_multiple_of) < 1:
+            raise ValueError("pad_to_multiple_of must be at least 1 (None: the fixed width max_length)")
+        for name, v in (*fit32.items(), ("pad_to_multiple_of", pad_to_multiple_of or 0)):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise ValueError(f"{name} must fit 32 bits")
+        return keep == "tail", padding_side == "left", int(pad_to_multiple_of or 0)
+
+    @staticmethod
+    def _outs(n_ptr: int, n_cnt: int):
+        """(pointers, counts, all of them by reference) for the result arrays and the figures a C entry hands back"""
+        out, cnt = [ctypes.c_void_p() for _ in range(n_ptr)], [ctypes.c_uint64() for _ in range(n_cnt)]
+        return out, cnt, [ctypes.byref(x) for x in out + cnt]
+
+    @staticmethod
+    def _own_mask(ptr: ctypes.c_void_p, n: int) -> np.ndarray:
+        """A result's mask bytes.  A small result comes as a view of a bytes object: the caller gets an array of its own, as for the ids"""
+        mask = _take_u8(ptr, n)
+        return mask if mask.flags.writeable else mask.copy()
+
     @classmethod
     def _rows_spec(cls, seq_len: int, bos, eos, pad, drop_last: bool, dtype) -> "tuple[_lib.RowsSpec, bool]":
         """(the tk_rows_spec, whether the caller has named a pad id)"""
@@ -752,10 +778,8 @@ class CoreBPE:
         spec, has_pad = self._rows_spec(seq_len, bos, eos, pad, drop_last, dtype)
         k = (bos is not None) + (eos is not None)
         self._pad_needed(has_pad, drop_last, n_tokens + n_docs * k, spec.seq_len)
-        out = [ctypes.c_void_p() for _ in range(5)]
-        cnt = [ctypes.c_uint64() for _ in range(4)]
-        rc = self._L.tk_pack_rows_device(self._h, d_tokens or None, n_tokens, d_tok_off or None, n_docs, ctypes.byref(spec), stream or None,
-                                         *[ctypes.byref(x) for x in out], *[ctypes.byref(x) for x in cnt])
+        out, cnt, refs = self._outs(5, 4)
+        rc = self._L.tk_pack_rows_device(self._h, d_tokens or None, n_tokens, d_tok_off or None, n_docs, ctypes.byref(spec), stream or None, *refs)
         _lib.raise_for(rc)
         return RowsDevice(*[x.value or 0 for x in out], *[int(x.value) for x in cnt])
 
@@ -768,9 +792,8 @@ class CoreBPE:
         text, dis, n_docs, _keep = self._batch_args(blob, doc_off, allowed_special, disallowed_special)
         spec, has_pad = self._rows_spec(seq_len, bos, eos, pad, drop_last, dtype)
         hit = _lib.SpecialHit()
-        out = [ctypes.c_void_p() for _ in range(5)]
-        cnt = [ctypes.c_uint64() for _ in range(4)]
-        rc = self._L.tk_encode_batch_rows(self._h, *text, *dis, ctypes.byref(spec), *[ctypes.byref(x) for x in out], *[ctypes.byref(x) for x in cnt], ctypes.byref(hit))
+        out, cnt, refs = self._outs(5, 4)
+        rc = self._L.tk_encode_batch_rows(self._h, *text, *dis, ctypes.byref(spec), *refs, ctypes.byref(hit))
         self._raise_for(rc, hit)
         n_rows, n_segs, n_stream, n_tail = (int(x.value) for x in cnt)
         L = spec.seq_len
@@ -785,18 +808,9 @@ class CoreBPE:
     def _pad_spec(cls, max_length: int, stride: int, windows: bool, keep: str, padding_side: str, pad_to_multiple_of, bos, eos, pad, dtype) -> "tuple[_lib.PadSpec, bool]":
         """(the tk_pad_spec, whether the caller has named a pad id)"""
         bos_id, eos_id, pad_id, has_pad, ids16 = cls._ids_spec(bos, eos, pad, dtype)
-        if keep not in ("head", "tail"):
-            raise ValueError("keep must be 'head' or 'tail'")
-        if padding_side not in ("right", "left"):
-            raise ValueError("padding_side must be 'right' or 'left'")
-        if pad_to_multiple_of is not None and int(pad_to_multiple_of) < 1:
-            raise ValueError("pad_to_multiple_of must be at least 1 (None: the fixed width max_length)")
-        for name, v in (("max_length", max_length), ("stride", stride), ("pad_to_multiple_of", pad_to_multiple_of or 0)):
-            if not 0 <= int(v) <= 0xFFFFFFFF:
-                raise ValueError(f"{name} must fit 32 bits")
-        flags = ((_lib.PAD_WINDOWS if windows else 0) | (_lib.PAD_KEEP_TAIL if keep == "tail" else 0) | (_lib.PAD_LEFT if padding_side == "left" else 0)
-                 | (_lib.PAD_IDS16 if ids16 else 0))
-        return _lib.PadSpec(int(max_length), int(stride), int(pad_to_multiple_of or 0), bos_id, eos_id, pad_id, flags), has_pad
+        tail, left, width_multiple = cls._width_spec(keep, padding_side, pad_to_multiple_of, max_length=max_length, stride=stride)
+        flags = (_lib.PAD_WINDOWS if windows else 0) | (_lib.PAD_KEEP_TAIL if tail else 0) | (_lib.PAD_LEFT if left else 0) | (_lib.PAD_IDS16 if ids16 else 0)
+        return _lib.PadSpec(int(max_length), int(stride), width_multiple, bos_id, eos_id, pad_id, flags), has_pad
 
     @staticmethod
     def _pad_id_needed(has_pad: bool, n_rows: int, width: int, lengths) -> None:
@@ -815,10 +829,8 @@ class CoreBPE:
         spec, has_pad = self._pad_spec(max_length, stride, windows, keep, padding_side, pad_to_multiple_of, bos, eos, pad, dtype)
         if not has_pad:  # (the lengths stay on the device: whether a row needs padding cannot be seen from here)
             raise ValueError("pad_batch_device: name a pad or eos id")
-        out = [ctypes.c_void_p() for _ in range(6)]
-        cnt = [ctypes.c_uint64() for _ in range(2)]
-        rc = self._L.tk_pad_batch_device(self._h, d_tokens or None, n_tokens, d_tok_off or None, n_docs, ctypes.byref(spec), stream or None,
-                                         *[ctypes.byref(x) for x in out], *[ctypes.byref(x) for x in cnt])
+        out, cnt, refs = self._outs(6, 2)
+        rc = self._L.tk_pad_batch_device(self._h, d_tokens or None, n_tokens, d_tok_off or None, n_docs, ctypes.byref(spec), stream or None, *refs)
         _lib.raise_for(rc)
         return PaddedDevice(*[x.value or 0 for x in out], *[int(x.value) for x in cnt])
 
@@ -832,16 +844,12 @@ class CoreBPE:
         text, dis, n_docs, _keep = self._batch_args(blob, doc_off, allowed_special, disallowed_special)
         spec, has_pad = self._pad_spec(max_length, stride, windows, keep, padding_side, pad_to_multiple_of, bos, eos, pad, dtype)
         hit = _lib.SpecialHit()
-        out = [ctypes.c_void_p() for _ in range(6)]
-        cnt = [ctypes.c_uint64() for _ in range(2)]
-        rc = self._L.tk_encode_batch_padded(self._h, *text, *dis, ctypes.byref(spec), *[ctypes.byref(x) for x in out], *[ctypes.byref(x) for x in cnt], ctypes.byref(hit))
+        out, cnt, refs = self._outs(6, 2)
+        rc = self._L.tk_encode_batch_padded(self._h, *text, *dis, ctypes.byref(spec), *refs, ctypes.byref(hit))
         self._raise_for(rc, hit)
         n_rows, width = (int(x.value) for x in cnt)
         input_ids = _take(out[0], n_rows * width, dtype).reshape(n_rows, width)
-        mask = _take_u8(out[1], n_rows * width)
-        if not mask.flags.writeable:  # (a small result comes as a view of a bytes object: the caller gets an array of its own, as for the ids)
-            mask = mask.copy()
-        mask = mask.reshape(n_rows, width)
+        mask = self._own_mask(out[1], n_rows * width).reshape(n_rows, width)
         lengths, row_doc, row_tok, doc_row = _take_u32(out[2], n_rows), _take_u32(out[3], n_rows), _take_u32(out[4], n_rows), _take_u32(out[5], n_docs + 1)
         self._pad_id_needed(has_pad, n_rows, width, lengths)
         return PaddedBatch(input_ids, mask, lengths, row_doc, row_tok, doc_row)
@@ -862,26 +870,17 @@ class CoreBPE:
             train.append(1 if t else 0)
         return (len(train), np.array(ids if ids else [0], dtype=np.uint32), np.array(off, dtype=np.uint32), np.array(train if train else [0], dtype=np.uint8))
 
-    @staticmethod
-    def _smp_spec(max_length: int, keep: str, padding_side: str, pad_to_multiple_of, bos, eos, pad: int, ignore_index: int) -> "_lib.SmpSpec":
-        if keep not in ("head", "tail"):
-            raise ValueError("keep must be 'head' or 'tail'")
-        if padding_side not in ("right", "left"):
-            raise ValueError("padding_side must be 'right' or 'left'")
-        if pad_to_multiple_of is not None and int(pad_to_multiple_of) < 1:
-            raise ValueError("pad_to_multiple_of must be at least 1 (None: the fixed width max_length)")
-        for name, v in (("max_length", max_length), ("pad_to_multiple_of", pad_to_multiple_of or 0), ("pad", pad)):
-            if not 0 <= int(v) <= 0xFFFFFFFF:
-                raise ValueError(f"{name} must fit 32 bits")
+    @classmethod
+    def _smp_spec(cls, max_length: int, keep: str, padding_side: str, pad_to_multiple_of, bos, eos, pad: int, ignore_index: int) -> "_lib.SmpSpec":
+        tail, left, width_multiple = cls._width_spec(keep, padding_side, pad_to_multiple_of, max_length=max_length, pad=pad)
         for name, v in (("bos", bos), ("eos", eos)):
             if v is not None and not 0 <= int(v) < 0xFFFFFFFF:
                 raise ValueError(f"{name} must be a token id below 2^32 - 1")
         if not -(1 << 31) <= int(ignore_index) < (1 << 31):
             raise ValueError("ignore_index must fit a signed 32-bit integer")
         none = _lib.ROWS_NO_TOKEN
-        flags = (_lib.SMP_KEEP_TAIL if keep == "tail" else 0) | (_lib.SMP_LEFT if padding_side == "left" else 0)
-        return _lib.SmpSpec(int(max_length), int(pad_to_multiple_of or 0), none if bos is None else int(bos), none if eos is None else int(eos), int(pad), int(ignore_index),
-                            flags)
+        flags = (_lib.SMP_KEEP_TAIL if tail else 0) | (_lib.SMP_LEFT if left else 0)
+        return _lib.SmpSpec(int(max_length), width_multiple, none if bos is None else int(bos), none if eos is None else int(eos), int(pad), int(ignore_index), flags)
 
     def assemble_samples_device(self, d_tokens: int, n_tokens: int, d_tok_off: int, n_parts: int, d_part_role: int, d_sample_off: int, n_samples: int,
                                 roles: "Sequence[Role]", *, max_length: int, keep: str = "head", padding_side: str = "right", pad_to_multiple_of: int | None = None,
@@ -893,11 +892,9 @@ class CoreBPE:
         self._one_device("assemble_samples_device")
         spec = self._smp_spec(max_length, keep, padding_side, pad_to_multiple_of, bos, eos, pad, ignore_index)
         n_roles, ids, off, train = self._role_table(roles)
-        out = [ctypes.c_void_p() for _ in range(6)]
-        cnt = [ctypes.c_uint64() for _ in range(2)]
+        out, cnt, refs = self._outs(6, 2)
         rc = self._L.tk_assemble_samples_device(self._h, d_tokens or None, n_tokens, d_tok_off or None, n_parts, d_part_role or None, d_sample_off or None, n_samples,
-                                                n_roles, ids.ctypes.data, off.ctypes.data, train.ctypes.data, ctypes.byref(spec), stream or None,
-                                                *[ctypes.byref(x) for x in out], *[ctypes.byref(x) for x in cnt])
+                                                n_roles, ids.ctypes.data, off.ctypes.data, train.ctypes.data, ctypes.byref(spec), stream or None, *refs)
         _lib.raise_for(rc)
         return SamplesDevice(*[x.value or 0 for x in out], *[int(x.value) for x in cnt])
 
@@ -924,18 +921,15 @@ class CoreBPE:
         spec = self._smp_spec(max_length, keep, padding_side, pad_to_multiple_of, bos, eos, pad, ignore_index)
         n_roles, ids, off, train = self._role_table(roles)
         hit = _lib.SpecialHit()
-        out = [ctypes.c_void_p() for _ in range(6)]
-        cnt = [ctypes.c_uint64() for _ in range(2)]
+        out, cnt, refs = self._outs(6, 2)
         held = part_role if n_parts else np.zeros(1, dtype=np.uint8)
         rc = self._L.tk_encode_batch_samples(self._h, *text, *dis, held.ctypes.data, sample_off.ctypes.data, n_samples, n_roles, ids.ctypes.data, off.ctypes.data,
-                                             train.ctypes.data, ctypes.byref(spec), *[ctypes.byref(x) for x in out], *[ctypes.byref(x) for x in cnt], ctypes.byref(hit))
+                                             train.ctypes.data, ctypes.byref(spec), *refs, ctypes.byref(hit))
         self._raise_for(rc, hit)
         n_rows, width = (int(x.value) for x in cnt)
         n = n_rows * width
         input_ids = _take_u32(out[0], n).reshape(n_rows, width)
-        mask = _take_u8(out[1], n)
-        if not mask.flags.writeable:  # (a small result comes as a view of a bytes object: the caller gets an array of its own, as for the ids)
-            mask = mask.copy()
+        mask = self._own_mask(out[1], n)
         labels = _take_u32(out[2], n).view(np.int32).reshape(n_rows, width)
         return SampleBatch(input_ids, mask.reshape(n_rows, width), labels, _take_u32(out[3], n_rows), _take_u64(out[4], n_rows), _take_u32(out[5], n_rows))
 

@@ -1671,6 +1671,20 @@ static int result_from_device(HostResult<T>& host, const void* d_src, uint64_t n
     if (n) HIPCHK(hipMemcpy(host, d_src, n * sizeof(T), hipMemcpyDeviceToHost));
     return TK_OK;
 }
+// The result arrays of one call: fetch() makes each and fills it from the device, give() hands them all to the caller's out-pointers --
+// called once every fetch has succeeded; a bag that goes without it frees what it has fetched.
+struct ResultBag {
+    HostResult<uint8_t> host[6];
+    void* out[6];  // the caller's pointers, a T* each: set[i] knows which T
+    void (*set[6])(void*, void*);
+    int n = 0;
+    template <class T>
+    int fetch(T** o, const void* d_src, uint64_t count) {
+        out[n] = o, set[n] = [](void* where, void* p) { *(T**)where = (T*)p; };
+        return result_from_device(host[n++], d_src, count * sizeof(T));
+    }
+    void give() { for (int i = 0; i < n; ++i) set[i](out[i], host[i].release()); }
+};
 // A result array that is filled while its final size is not known yet, sized by the density so far: `done` of the call's `all` input units
 // have made `need` elements (`filled` of them are in the array or on their way into it on c->cs_d2h, the others follow once this returns).
 // An array that turns out too small is replaced by one of the new estimate and what it holds is copied over.
@@ -2685,14 +2699,15 @@ static int report_arm(unsigned long long* words, hipStream_t s) {
     HIPCHK(hipMemsetAsync(words + TK_BAD_OFF, 0xFF, 8, s));
     return TK_OK;
 }
-// TK_OK, or the refusal of a tok_off that does not describe the batch: the first offending document and what is wrong with it
-static int tok_off_refusal(unsigned long long word) {
+// TK_OK, or the refusal of an offsets array that does not describe the batch (`word`: its report word, a tk_rows_bad_key): the first
+// offending entry and what is wrong with it.  ("tok_off", "document", "n_tokens") and ("sample_off", "sample", "n_parts").
+static int offsets_refusal(unsigned long long word, const char* array, const char* entry, const char* count) {
     if (word == ~0ull) return TK_OK;
-    const std::string d = std::to_string(word >> 2);
+    const std::string a = array, e = std::string(entry) + " " + std::to_string(word >> 2);
     switch (word & 3u) {
-        case 1: return fail(TK_VALUE_ERROR, "tok_off[0] must be 0 (document " + d + ")");
-        case 2: return fail(TK_VALUE_ERROR, "tok_off must be non-decreasing: document " + d + " ends before it starts");
-        default: return fail(TK_VALUE_ERROR, "tok_off must end at n_tokens: document " + d + " ends elsewhere");
+        case 1: return fail(TK_VALUE_ERROR, a + "[0] must be 0 (" + e + ")");
+        case 2: return fail(TK_VALUE_ERROR, a + " must be non-decreasing: " + e + " ends before it starts");
+        default: return fail(TK_VALUE_ERROR, a + " must end at " + count + ": " + e + " ends elsewhere");
     }
 }
 // Behind the passes: the stream is waited for, the n words come over (synchronous: nothing is on its way into `got` when this returns,
@@ -2701,8 +2716,26 @@ static int report_read(const unsigned long long* words, unsigned long long* got,
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(got, words, n * 8, hipMemcpyDeviceToHost));
-    return tok_off_refusal(got[TK_BAD_OFF]);
+    return offsets_refusal(got[TK_BAD_OFF], "tok_off", "document", "n_tokens");
 }
+// The opening of tk_pack_rows_device, tk_pad_batch_device and tk_assemble_samples_device (`args`: the entry's own pointers are there):
+// run(s) under the core's mutex, on its device, s the caller's stream or the core's, and the timed launches drained behind it.
+template <class Run>
+static int device_pass(tk_core* c, bool args, void* stream, Run&& run) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if (!args) return fail(TK_VALUE_ERROR, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    return drained(c, [&] { return run(stream ? (hipStream_t)stream : c->stream); });
+}
+// A buffer carved into arrays: add(bytes) gives the offset of the next one, every one at a multiple of 16 bytes (the write passes store 16
+// bytes at a time); `total` is what to ask ensure() for, once; carved<T>(buf, offset) is the array.
+struct Carve {
+    uint64_t total = 0;
+    uint64_t add(uint64_t bytes) { return std::exchange(total, total + ((bytes + 15) & ~15ull)); }
+};
+template <class T>
+static T* carved(const Buf& b, uint64_t off) { return (T*)(b.as<uint8_t>() + off); }
 // What of a tk_rows_spec can be refused without looking at the batch (the host-text entry asks before it encodes anything).
 static int rows_check_spec(tk_core* c, const tk_rows_spec* spec) {
     if (!spec) return fail(TK_VALUE_ERROR, "null argument");
@@ -2723,18 +2756,20 @@ static int rows_run(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n
         default: return fail(TK_VALUE_ERROR, "the stream has 2^32 positions or more: the positions of the rows are 32-bit");
     }
     const bool ids16 = (spec->flags & TK_ROWS_IDS16) != 0;
-    const uint64_t m8 = (r.M + 7) & ~7ull, ids_bytes = m8 * (ids16 ? 2 : 4);  // (every array starts at a multiple of 16 bytes)
-    const uint64_t nb = (r.M + TK_DEC_BLOCK - 1) / TK_DEC_BLOCK, cu_cap = (n_docs + r.R + 4 + 3) & ~3ull;
-    TRY(ensure(c->d_rows, ids_bytes + m8 * 8 + 64));
-    TRY(ensure(c->d_rows_seg, TK_ROWS_WORDS * 8 + (cu_cap + r.R + 1) * 4));
+    const uint64_t m8 = (r.M + 7) & ~7ull, nb = (r.M + TK_DEC_BLOCK - 1) / TK_DEC_BLOCK;  // (m8: room for whole lanes of eight)
+    Carve rows, seg;
+    const uint64_t at_ids = rows.add(m8 * (ids16 ? 2 : 4)), at_doc = rows.add(m8 * 4), at_pos = rows.add(m8 * 4);
+    const uint64_t at_words = seg.add(TK_ROWS_WORDS * 8), at_cu = seg.add((n_docs + r.R + 4) * 4), at_rs = seg.add((r.R + 1) * 4);
+    TRY(ensure(c->d_rows, rows.total + 64));
+    TRY(ensure(c->d_rows_seg, seg.total));
     TRY(ensure(c->d_rows_marks, (r.M / 32 + 4) * 4));
     TRY(ensure(c->d_rows_blk, (nb + 1) * 8));
-    out->ids = c->d_rows.p;
-    out->doc = (uint32_t*)((uint8_t*)c->d_rows.p + ids_bytes);
-    out->pos = out->doc + m8;
-    unsigned long long* words = c->d_rows_seg.as<unsigned long long>();
-    out->cu = (uint32_t*)(words + TK_ROWS_WORDS);
-    out->row_seg = out->cu + cu_cap;
+    out->ids = carved<void>(c->d_rows, at_ids);
+    out->doc = carved<uint32_t>(c->d_rows, at_doc);
+    out->pos = carved<uint32_t>(c->d_rows, at_pos);
+    unsigned long long* words = carved<unsigned long long>(c->d_rows_seg, at_words);
+    out->cu = carved<uint32_t>(c->d_rows_seg, at_cu);
+    out->row_seg = carved<uint32_t>(c->d_rows_seg, at_rs);
     out->ids16 = ids16;
     out->n_rows = r.R;
     out->n_stream = r.S;
@@ -2763,12 +2798,9 @@ static int rows_run(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n
 extern "C" int tk_pack_rows_device(tk_core* c, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_docs, const tk_rows_spec* spec, void* stream,
                                    const void** d_ids_out, const uint32_t** d_doc_out, const uint32_t** d_pos_out, const uint32_t** d_cu_seqlens_out,
                                    const uint32_t** d_row_seg_out, uint64_t* n_rows_out, uint64_t* n_segs_out, uint64_t* n_stream_out, uint64_t* n_tail_out) {
-    if (!c) return fail(TK_VALUE_ERROR, "core is null");
-    if (!d_tok_off || (n_tokens && !d_tokens) || !spec) return fail(TK_VALUE_ERROR, "null argument");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->device));
     RowsView v;
-    TRY(drained(c, [&] { return rows_run(c, stream ? (hipStream_t)stream : c->stream, (const uint32_t*)d_tokens, n_tokens, (const uint64_t*)d_tok_off, n_docs, spec, &v); }));
+    TRY(device_pass(c, d_tok_off && (d_tokens || !n_tokens) && spec, stream,
+                    [&](hipStream_t s) { return rows_run(c, s, (const uint32_t*)d_tokens, n_tokens, (const uint64_t*)d_tok_off, n_docs, spec, &v); }));
     if (d_ids_out) *d_ids_out = v.ids;
     if (d_doc_out) *d_doc_out = v.doc;
     if (d_pos_out) *d_pos_out = v.pos;
@@ -2794,18 +2826,13 @@ extern "C" int tk_encode_batch_rows(tk_core* c, const uint8_t* utf8, const uint6
         [&] { return rows_check_spec(c, spec); },  // (before the encode, not after it)
         [&](uint64_t n) { return rows_run(c, c->stream, c->out_tokens.as<uint32_t>(), n, c->out_tok_off.as<uint64_t>(), n_docs, spec, &v); },
         [&](uint64_t) -> int {
-            HostResult<uint8_t> ids;
-            HostResult<uint32_t> doc, pos, cu, rs;
-            TRY(result_from_device(ids, v.ids, v.n_pos * (v.ids16 ? 2 : 4)));
-            TRY(result_from_device(doc, v.doc, v.n_pos));
-            TRY(result_from_device(pos, v.pos, v.n_pos));
-            TRY(result_from_device(cu, v.cu, v.n_segs + 1));
-            TRY(result_from_device(rs, v.row_seg, v.n_rows + 1));
-            *ids_out = ids.release();
-            *doc_out = doc.release();
-            *pos_out = pos.release();
-            *cu_seqlens_out = cu.release();
-            *row_seg_out = rs.release();
+            ResultBag bag;
+            TRY(bag.fetch((uint8_t**)ids_out, v.ids, v.n_pos * (v.ids16 ? 2 : 4)));
+            TRY(bag.fetch(doc_out, v.doc, v.n_pos));
+            TRY(bag.fetch(pos_out, v.pos, v.n_pos));
+            TRY(bag.fetch(cu_seqlens_out, v.cu, v.n_segs + 1));
+            TRY(bag.fetch(row_seg_out, v.row_seg, v.n_rows + 1));
+            bag.give();
             *n_rows_out = v.n_rows;
             *n_segs_out = v.n_segs;
             if (n_stream_out) *n_stream_out = v.n_stream;
@@ -2854,9 +2881,11 @@ static int pad_run(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n,
     TRY(pad_check_spec(c, spec));
     TkPad p;
     TRY(pad_refusal(tk_pad_shape(n, n_docs, spec->max_len, spec->stride, spec->width_multiple, spec->bos_id, spec->eos_id, spec->pad_id, spec->flags, &p)));
-    TRY(ensure(c->d_pad_cnt, TK_PAD_WORDS * 8 + (n_docs + 1) * 4));
-    unsigned long long* words = c->d_pad_cnt.as<unsigned long long>();
-    uint32_t* counted = (uint32_t*)(words + TK_PAD_WORDS);  // (the result's doc_row is written once the call is accepted)
+    Carve cnt;
+    const uint64_t at_words = cnt.add(TK_PAD_WORDS * 8), at_counted = cnt.add((n_docs + 1) * 4);
+    TRY(ensure(c->d_pad_cnt, cnt.total));
+    unsigned long long* words = carved<unsigned long long>(c->d_pad_cnt, at_words);
+    uint32_t* counted = carved<uint32_t>(c->d_pad_cnt, at_counted);  // (the result's doc_row is written once the call is accepted)
     TRY(report_arm(words, s));  // (tk_k_pad_scan writes the second word)
     HIPCHK(hipMemsetAsync(words + TK_PAD_LONGEST, 0, 8, s));
     TRY(timed(c, s, "tk_k_pad_count", [&] { hipLaunchKernelGGL(tk_k_pad_count, dim3(grid_for(n_docs + 1, 256, 4096)), dim3(256), 0, s, d_tok_off, p, counted, words); }));
@@ -2865,18 +2894,20 @@ static int pad_run(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n,
     TRY(report_read(words, got, TK_PAD_WORDS, s));
     TRY(pad_refusal(tk_pad_size(&p, got[TK_PAD_NROWS], (uint32_t)got[TK_PAD_LONGEST])));
     const bool ids16 = (spec->flags & TK_PAD_IDS16) != 0;
-    const uint64_t N = p.R * p.W, n8 = (N + 7) & ~7ull, ids_bytes = n8 * (ids16 ? 2 : 4), r4 = (p.R + 3) & ~3ull;  // (every array starts at a multiple of 16 bytes)
-    const uint64_t nb = (N + TK_DEC_BLOCK - 1) / TK_DEC_BLOCK;
-    TRY(ensure(c->d_pad, ids_bytes + n8 + 64));
-    TRY(ensure(c->d_pad_row, r4 * 12 + 64));
+    const uint64_t N = p.R * p.W, n8 = (N + 7) & ~7ull, nb = (N + TK_DEC_BLOCK - 1) / TK_DEC_BLOCK;  // (n8: room for whole lanes of eight)
+    Carve pos, row;
+    const uint64_t at_ids = pos.add(n8 * (ids16 ? 2 : 4)), at_mask = pos.add(n8);
+    const uint64_t at_len = row.add(p.R * 4), at_rd = row.add(p.R * 4), at_rt = row.add(p.R * 4);
+    TRY(ensure(c->d_pad, pos.total));
+    TRY(ensure(c->d_pad_row, row.total));
     TRY(ensure(c->d_pad_doc, (n_docs + 1) * 4));
     uint32_t* doc_row = c->d_pad_doc.as<uint32_t>();
     HIPCHK(hipMemcpyAsync(doc_row, counted, (n_docs + 1) * 4, hipMemcpyDeviceToDevice, s));
-    out->ids = c->d_pad.p;
-    out->mask = (uint8_t*)c->d_pad.p + ids_bytes;
-    out->len = c->d_pad_row.as<uint32_t>();
-    out->row_doc = out->len + r4;
-    out->row_tok = out->row_doc + r4;
+    out->ids = carved<void>(c->d_pad, at_ids);
+    out->mask = carved<uint8_t>(c->d_pad, at_mask);
+    out->len = carved<uint32_t>(c->d_pad_row, at_len);
+    out->row_doc = carved<uint32_t>(c->d_pad_row, at_rd);
+    out->row_tok = carved<uint32_t>(c->d_pad_row, at_rt);
     out->doc_row = doc_row;
     out->n_rows = p.R;
     out->width = p.W;
@@ -2898,12 +2929,9 @@ static int pad_run(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n,
 extern "C" int tk_pad_batch_device(tk_core* c, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_docs, const tk_pad_spec* spec, void* stream,
                                    const void** d_ids_out, const uint8_t** d_mask_out, const uint32_t** d_len_out, const uint32_t** d_row_doc_out,
                                    const uint32_t** d_row_tok_out, const uint32_t** d_doc_row_out, uint64_t* n_rows_out, uint64_t* width_out) {
-    if (!c) return fail(TK_VALUE_ERROR, "core is null");
-    if (!d_tok_off || (n_tokens && !d_tokens) || !spec) return fail(TK_VALUE_ERROR, "null argument");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->device));
     PadView v;
-    TRY(drained(c, [&] { return pad_run(c, stream ? (hipStream_t)stream : c->stream, (const uint32_t*)d_tokens, n_tokens, (const uint64_t*)d_tok_off, n_docs, spec, &v); }));
+    TRY(device_pass(c, d_tok_off && (d_tokens || !n_tokens) && spec, stream,
+                    [&](hipStream_t s) { return pad_run(c, s, (const uint32_t*)d_tokens, n_tokens, (const uint64_t*)d_tok_off, n_docs, spec, &v); }));
     if (d_ids_out) *d_ids_out = v.ids;
     if (d_mask_out) *d_mask_out = v.mask;
     if (d_len_out) *d_len_out = v.len;
@@ -2929,20 +2957,14 @@ extern "C" int tk_encode_batch_padded(tk_core* c, const uint8_t* utf8, const uin
         [&](uint64_t n) { return pad_run(c, c->stream, c->out_tokens.as<uint32_t>(), n, c->out_tok_off.as<uint64_t>(), n_docs, spec, &v); },
         [&](uint64_t) -> int {
             const uint64_t N = v.n_rows * v.width;
-            HostResult<uint8_t> ids, mask;
-            HostResult<uint32_t> len, rd, rt, dr;
-            TRY(result_from_device(ids, v.ids, N * (v.ids16 ? 2 : 4)));
-            TRY(result_from_device(mask, v.mask, N));
-            TRY(result_from_device(len, v.len, v.n_rows));
-            TRY(result_from_device(rd, v.row_doc, v.n_rows));
-            TRY(result_from_device(rt, v.row_tok, v.n_rows));
-            TRY(result_from_device(dr, v.doc_row, n_docs + 1));
-            *ids_out = ids.release();
-            *mask_out = mask.release();
-            *len_out = len.release();
-            *row_doc_out = rd.release();
-            *row_tok_out = rt.release();
-            *doc_row_out = dr.release();
+            ResultBag bag;
+            TRY(bag.fetch((uint8_t**)ids_out, v.ids, N * (v.ids16 ? 2 : 4)));
+            TRY(bag.fetch(mask_out, v.mask, N));
+            TRY(bag.fetch(len_out, v.len, v.n_rows));
+            TRY(bag.fetch(row_doc_out, v.row_doc, v.n_rows));
+            TRY(bag.fetch(row_tok_out, v.row_tok, v.n_rows));
+            TRY(bag.fetch(doc_row_out, v.doc_row, n_docs + 1));
+            bag.give();
             *n_rows_out = v.n_rows;
             *width_out = v.width;
             return TK_OK;
@@ -2998,25 +3020,23 @@ static int smp_run(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n,
                    const uint64_t* d_sample_off, uint64_t n_samples, const SmpRoles& roles, const tk_smp_spec* spec, SmpView* out) {
     TkSmp p;
     TRY(smp_check_spec(spec, roles, n, n_parts, n_samples, &p));
-    // scratch: the report words | role_off, role_ids, role_train | pstart | full | len | n_trained (every array at a multiple of 16 bytes)
+    // scratch: the report words | role_off, role_ids, role_train | pstart | full | len | n_trained
     const uint32_t n_off = 2 * roles.n_roles + 1, n_ids = roles.n_roles ? roles.off[2 * roles.n_roles] : 0;
-    auto up16 = [](uint64_t x) { return (x + 15) & ~15ull; };
-    const uint64_t at_off = up16(TK_SMP_WORDS * 8), at_ids = at_off + up16(n_off * 4ull), at_train = at_ids + up16(n_ids * 4ull), at_ps = at_train + up16(roles.n_roles);
-    const uint64_t at_full = at_ps + up16((n_parts + 1) * 8), at_len = at_full + up16(n_samples * 8), at_ntr = at_len + up16(n_samples * 4);
-    TRY(ensure(c->d_smp_cnt, at_ntr + up16(n_samples * 4)));
-    uint8_t* base = c->d_smp_cnt.as<uint8_t>();
-    unsigned long long* words = (unsigned long long*)base;
-    uint64_t* pstart = (uint64_t*)(base + at_ps);
-    uint64_t* full = (uint64_t*)(base + at_full);
-    uint32_t *len = (uint32_t*)(base + at_len), *ntr = (uint32_t*)(base + at_ntr);
-    const TkSmpTable tab{(const uint32_t*)(base + at_off), (const uint32_t*)(base + at_ids), base + at_train, n_ids};
-    std::vector<uint8_t> table(at_ps - at_off, 0);  // (role_off of no roles: one 0)
+    Carve cnt;
+    const uint64_t at_words = cnt.add(TK_SMP_WORDS * 8), at_off = cnt.add(n_off * 4ull), at_ids = cnt.add(n_ids * 4ull), at_train = cnt.add(roles.n_roles);
+    const uint64_t at_ps = cnt.add((n_parts + 1) * 8), at_full = cnt.add(n_samples * 8), at_len = cnt.add(n_samples * 4), at_ntr = cnt.add(n_samples * 4);
+    TRY(ensure(c->d_smp_cnt, cnt.total));
+    unsigned long long* words = carved<unsigned long long>(c->d_smp_cnt, at_words);
+    uint64_t *pstart = carved<uint64_t>(c->d_smp_cnt, at_ps), *full = carved<uint64_t>(c->d_smp_cnt, at_full);
+    uint32_t *len = carved<uint32_t>(c->d_smp_cnt, at_len), *ntr = carved<uint32_t>(c->d_smp_cnt, at_ntr);
+    const TkSmpTable tab{carved<uint32_t>(c->d_smp_cnt, at_off), carved<uint32_t>(c->d_smp_cnt, at_ids), carved<uint8_t>(c->d_smp_cnt, at_train), n_ids};
+    std::vector<uint8_t> table(at_ps - at_off, 0);  // (the table as it lies on the device, from at_off on; role_off of no roles: one 0)
     if (roles.n_roles) {
         memcpy(table.data(), roles.off, n_off * 4ull);
         if (n_ids) memcpy(table.data() + (at_ids - at_off), roles.ids, n_ids * 4ull);
         memcpy(table.data() + (at_train - at_off), roles.train, roles.n_roles);
     }
-    HIPCHK(hipMemcpyAsync(base + at_off, table.data(), table.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(carved<uint8_t>(c->d_smp_cnt, at_off), table.data(), table.size(), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(words, 0xFF, 8 * (TK_SMP_BAD_ROLE + 1), s));  // (the three words that keep the lowest offender: all ones = none)
     HIPCHK(hipMemsetAsync(words + TK_SMP_TOTAL, 0, 16, s));
     const uint64_t n_entries = std::max(n_parts, n_samples) + 1;
@@ -3030,26 +3050,21 @@ static int smp_run(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n,
         }));
     unsigned long long got[TK_SMP_WORDS];
     TRY(report_read(words, got, TK_SMP_WORDS, s));  // (waits for the table's copy too: `table` may go)
-    if (got[TK_SMP_BAD_SOFF] != ~0ull) {
-        const std::string d = std::to_string(got[TK_SMP_BAD_SOFF] >> 2);
-        switch (got[TK_SMP_BAD_SOFF] & 3u) {
-            case 1: return fail(TK_VALUE_ERROR, "sample_off[0] must be 0 (sample " + d + ")");
-            case 2: return fail(TK_VALUE_ERROR, "sample_off must be non-decreasing: sample " + d + " ends before it starts");
-            default: return fail(TK_VALUE_ERROR, "sample_off must end at n_parts: sample " + d + " ends elsewhere");
-        }
-    }
+    TRY(offsets_refusal(got[TK_SMP_BAD_SOFF], "sample_off", "sample", "n_parts"));
     if (got[TK_SMP_BAD_ROLE] != ~0ull) return fail(TK_VALUE_ERROR, "part_role must be below n_roles: part " + std::to_string(got[TK_SMP_BAD_ROLE]) + " has no such role");
     TRY(smp_refusal(tk_smp_size(&p, got[TK_SMP_TOTAL], (uint32_t)got[TK_SMP_LONGEST])));
-    const uint64_t N = p.R * p.W, n8 = (N + 7) & ~7ull, r4 = (p.R + 3) & ~3ull;  // (every array starts at a multiple of 16 bytes)
-    const uint64_t nb = (N + TK_DEC_BLOCK - 1) / TK_DEC_BLOCK;
-    TRY(ensure(c->d_smp, n8 * 9 + 64));
-    TRY(ensure(c->d_smp_row, r4 * 16 + 64));
-    out->ids = c->d_smp.as<uint32_t>();
-    out->labels = (int32_t*)(out->ids + n8);
-    out->mask = (uint8_t*)(out->labels + n8);
-    out->full = c->d_smp_row.as<uint64_t>();
-    out->len = (uint32_t*)(out->full + r4);
-    out->n_trained = out->len + r4;
+    const uint64_t N = p.R * p.W, n8 = (N + 7) & ~7ull, nb = (N + TK_DEC_BLOCK - 1) / TK_DEC_BLOCK;  // (n8: room for whole lanes of eight)
+    Carve pos, row;
+    const uint64_t at_out_ids = pos.add(n8 * 4), at_labels = pos.add(n8 * 4), at_mask = pos.add(n8);
+    const uint64_t at_out_full = row.add(p.R * 8), at_out_len = row.add(p.R * 4), at_out_ntr = row.add(p.R * 4);
+    TRY(ensure(c->d_smp, pos.total));
+    TRY(ensure(c->d_smp_row, row.total));
+    out->ids = carved<uint32_t>(c->d_smp, at_out_ids);
+    out->labels = carved<int32_t>(c->d_smp, at_labels);
+    out->mask = carved<uint8_t>(c->d_smp, at_mask);
+    out->full = carved<uint64_t>(c->d_smp_row, at_out_full);
+    out->len = carved<uint32_t>(c->d_smp_row, at_out_len);
+    out->n_trained = carved<uint32_t>(c->d_smp_row, at_out_ntr);
     out->n_rows = p.R;
     out->width = p.W;
     if (p.R) {
@@ -3071,15 +3086,11 @@ extern "C" int tk_assemble_samples_device(tk_core* c, const void* d_tokens, uint
                                           const uint8_t* role_train, const tk_smp_spec* spec, void* stream, const uint32_t** d_ids_out, const uint8_t** d_mask_out,
                                           const int32_t** d_labels_out, const uint32_t** d_len_out, const uint64_t** d_full_len_out, const uint32_t** d_n_trained_out,
                                           uint64_t* n_rows_out, uint64_t* width_out) {
-    if (!c) return fail(TK_VALUE_ERROR, "core is null");
-    if (!d_tok_off || !d_sample_off || (n_tokens && !d_tokens) || (n_parts && !d_part_role) || !spec) return fail(TK_VALUE_ERROR, "null argument");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->device));
     SmpView v;
     const SmpRoles roles{n_roles, role_ids, role_off, role_train};
-    TRY(drained(c, [&] {
-        return smp_run(c, stream ? (hipStream_t)stream : c->stream, (const uint32_t*)d_tokens, n_tokens, (const uint64_t*)d_tok_off, n_parts, (const uint8_t*)d_part_role,
-                       (const uint64_t*)d_sample_off, n_samples, roles, spec, &v);
+    TRY(device_pass(c, d_tok_off && d_sample_off && (d_tokens || !n_tokens) && (d_part_role || !n_parts) && spec, stream, [&](hipStream_t s) {
+        return smp_run(c, s, (const uint32_t*)d_tokens, n_tokens, (const uint64_t*)d_tok_off, n_parts, (const uint8_t*)d_part_role, (const uint64_t*)d_sample_off, n_samples,
+                       roles, spec, &v);
     }));
     if (d_ids_out) *d_ids_out = v.ids;
     if (d_mask_out) *d_mask_out = v.mask;
@@ -3109,31 +3120,25 @@ extern "C" int tk_encode_batch_samples(tk_core* c, const uint8_t* utf8, const ui
             return smp_check_spec(spec, roles, 0, n_parts, n_samples, &p);
         },
         [&](uint64_t n) {
-            const uint64_t at_so = (n_parts + 15) & ~15ull;  // part_role, then sample_off at a multiple of 16 bytes
-            TRY(ensure(c->d_smp_in, at_so + (n_samples + 1) * 8));
-            uint8_t* in = c->d_smp_in.as<uint8_t>();
-            if (n_parts) HIPCHK(hipMemcpyAsync(in, part_role, n_parts, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(in + at_so, sample_off, (n_samples + 1) * 8, hipMemcpyHostToDevice, c->stream));
-            return smp_run(c, c->stream, c->out_tokens.as<uint32_t>(), n, c->out_tok_off.as<uint64_t>(), n_parts, in, (const uint64_t*)(in + at_so), n_samples, roles, spec, &v);
+            Carve in;
+            const uint64_t at_role = in.add(n_parts), at_so = in.add((n_samples + 1) * 8);
+            TRY(ensure(c->d_smp_in, in.total));
+            uint8_t* d_role = carved<uint8_t>(c->d_smp_in, at_role);
+            uint64_t* d_so = carved<uint64_t>(c->d_smp_in, at_so);
+            if (n_parts) HIPCHK(hipMemcpyAsync(d_role, part_role, n_parts, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(d_so, sample_off, (n_samples + 1) * 8, hipMemcpyHostToDevice, c->stream));
+            return smp_run(c, c->stream, c->out_tokens.as<uint32_t>(), n, c->out_tok_off.as<uint64_t>(), n_parts, d_role, d_so, n_samples, roles, spec, &v);
         },
         [&](uint64_t) -> int {
             const uint64_t N = v.n_rows * v.width;
-            HostResult<uint32_t> ids, len, ntr;
-            HostResult<uint8_t> mask;
-            HostResult<int32_t> labels;
-            HostResult<uint64_t> full;
-            TRY(result_from_device(ids, v.ids, N));
-            TRY(result_from_device(mask, v.mask, N));
-            TRY(result_from_device(labels, v.labels, N));
-            TRY(result_from_device(len, v.len, v.n_rows));
-            TRY(result_from_device(full, v.full, v.n_rows));
-            TRY(result_from_device(ntr, v.n_trained, v.n_rows));
-            *ids_out = ids.release();
-            *mask_out = mask.release();
-            *labels_out = labels.release();
-            *len_out = len.release();
-            *full_len_out = full.release();
-            *n_trained_out = ntr.release();
+            ResultBag bag;
+            TRY(bag.fetch(ids_out, v.ids, N));
+            TRY(bag.fetch(mask_out, v.mask, N));
+            TRY(bag.fetch(labels_out, v.labels, N));
+            TRY(bag.fetch(len_out, v.len, v.n_rows));
+            TRY(bag.fetch(full_len_out, v.full, v.n_rows));
+            TRY(bag.fetch(n_trained_out, v.n_trained, v.n_rows));
+            bag.give();
             *n_rows_out = v.n_rows;
             *width_out = v.width;
             return TK_OK;

@@ -16,6 +16,9 @@
 // search between the two results.
 // tok_off is the caller's: tk_k_pad_count indexes nothing with it, and the host launches the other passes only when no entry was reported,
 // so no kernel reads or writes out of bounds whatever tok_off holds.
+// What the CPU simulation (tests/test_padded_sim.py) shares with the kernels: tk_pad_count_entry (the body of tk_k_pad_count's loop),
+// tk_pad_row_entry (tk_k_pad_rows'), tk_pad_block_docs and tk_pad_lane (tk_k_pad_write); the wave reduction, the atomicMax, the scan and
+// the stores are the kernels' own.
 // Included by tk_api.hip only.
 #pragma once
 #include "tk_decode.h"
@@ -29,14 +32,8 @@ enum { TK_PAD_NROWS = TK_BAD_OFF + 1, TK_PAD_LONGEST, TK_PAD_WORDS };
 __global__ __launch_bounds__(256) void tk_k_pad_count(const uint64_t* __restrict__ tok_off, TkPad p, uint32_t* __restrict__ doc_row, unsigned long long* __restrict__ words) {
     uint32_t longest = 0;
     for (uint64_t d = blockIdx.x * 256ull + threadIdx.x; d <= p.n_docs; d += (uint64_t)gridDim.x * 256) {
-        uint64_t a, b;
-        const uint32_t why = tk_rows_off_check(tok_off, d, p.n_docs, p.n_tokens, &a, &b, words + TK_BAD_OFF);
-        if (d < p.n_docs) {
-            const uint64_t n = why ? 0 : b - a;  // (no error here: a <= b)
-            doc_row[d] = (uint32_t)tk_pad_windows(p, n);  // (at most n, and n < 2^32 unless another entry is reported)
-            const uint32_t l = tk_pad_longest(p, n);
-            longest = l > longest ? l : longest;
-        }
+        const uint32_t l = tk_pad_count_entry(p, tok_off, d, doc_row, words);
+        longest = l > longest ? l : longest;
     }
     longest = tk_wave_max_u32(longest);  // (behind the loop: every lane is here)
     if ((threadIdx.x & 63) == 0 && longest) atomicMax(words + TK_PAD_LONGEST, (unsigned long long)longest);
@@ -54,13 +51,7 @@ __global__ __launch_bounds__(1024) void tk_k_pad_scan(uint32_t* __restrict__ doc
 
 __global__ __launch_bounds__(256) void tk_k_pad_rows(const uint64_t* __restrict__ tok_off, const uint32_t* __restrict__ doc_row, TkPad p, uint32_t* __restrict__ len,
                                                      uint32_t* __restrict__ row_doc, uint32_t* __restrict__ row_tok) {
-    for (uint64_t r = blockIdx.x * 256ull + threadIdx.x; r < p.R; r += (uint64_t)gridDim.x * 256) {
-        TkPadRow w;
-        tk_pad_row_load(p, tok_off, doc_row, tk_pad_doc_of_row(doc_row, 0, p.n_docs, r), r, &w);
-        len[r] = w.len;
-        row_doc[r] = (uint32_t)w.d;
-        row_tok[r] = (uint32_t)w.tok;
-    }
+    for (uint64_t r = blockIdx.x * 256ull + threadIdx.x; r < p.R; r += (uint64_t)gridDim.x * 256) tk_pad_row_entry(p, tok_off, doc_row, r, len, row_doc, row_tok);
 }
 
 // ids_out, mask_out: 16-byte aligned (the library's own buffers): a lane's eight ids leave as 16-byte stores, its eight mask bytes as one

@@ -5,7 +5,7 @@
 #pragma once
 #include <stdint.h>
 
-#include "tk_rows_rule.h"  // TK_ROWS_NONE, tk_rows_off_error, tk_rows_bad_key
+#include "tk_rows_rule.h"  // TK_ROWS_NONE, tk_rows_off_check, tk_last_le, tk_row_width
 
 #define TK_PADF_WINDOWS 1u  // (= TK_PAD_WINDOWS .. TK_PAD_IDS16 of the C ABI; tk_api.hip asserts it)
 #define TK_PADF_KEEP_TAIL 2u
@@ -61,11 +61,7 @@ TK_HD uint32_t tk_pad_longest(const TkPad& p, uint64_t n) { return p.k + (uint32
 // R and W once the count is known.  0, or why it is refused: 7 R >= 2^32, 8 R * W >= 2^32.
 TK_HD int tk_pad_size(TkPad* p, uint64_t R, uint32_t longest) {
     p->R = R;
-    p->W = p->max_len;
-    if (p->width_multiple) {
-        const uint64_t w = ((uint64_t)longest + p->width_multiple - 1) / p->width_multiple * p->width_multiple;
-        if (w < p->max_len) p->W = (uint32_t)w;
-    }
+    p->W = tk_row_width(p->max_len, p->width_multiple, longest);
     if (R >> 32) return 7;
     if ((R * p->W) >> 32) return 8;
     return 0;
@@ -82,17 +78,21 @@ TK_HD uint32_t tk_pad_row(const TkPad& p, uint64_t n, uint64_t j, uint64_t* tok)
     return (uint32_t)(n < p.c ? n : p.c);
 }
 
-// The document row r < R belongs to, searched in [lo, hi): the last d there with doc_row[d] <= r (doc_row[lo] <= r).  Every document owns
-// a row, so doc_row ascends strictly and that document is the one whose rows hold r.
-TK_HD uint64_t tk_pad_doc_of_row(const uint32_t* doc_row, uint64_t lo, uint64_t hi, uint64_t r) {
-    uint64_t a = lo, b = hi;  // first index with doc_row > r
-    while (a < b) {
-        const uint64_t mid = (a + b) >> 1;
-        if (doc_row[mid] <= r) a = mid + 1;
-        else b = mid;
-    }
-    return a > lo ? a - 1 : lo;
+// Entry d <= n_docs of the count pass (tk_k_pad_count): the entry of tok_off is checked (nothing is indexed with it) and, for a document,
+// doc_row[d] = the rows it owns (one where its entry offends).  Returns the len of the document's longest row, 0 for entry n_docs.
+template <class Off>
+TK_HD uint32_t tk_pad_count_entry(const TkPad& p, Off tok_off, uint64_t d, uint32_t* doc_row, unsigned long long* words) {
+    uint64_t a, b;
+    const uint32_t why = tk_rows_off_check(tok_off, d, p.n_docs, p.n_tokens, &a, &b, words + TK_BAD_OFF);
+    if (d >= p.n_docs) return 0u;
+    const uint64_t n = why ? 0 : b - a;           // (no error here: a <= b)
+    doc_row[d] = (uint32_t)tk_pad_windows(p, n);  // (at most n, and n < 2^32 unless another entry is reported)
+    return tk_pad_longest(p, n);
 }
+
+// The document row r < R belongs to, searched in [lo, hi) (doc_row[lo] <= r): every document owns a row, so doc_row ascends strictly
+template <class Rows>
+TK_HD uint64_t tk_pad_doc_of_row(Rows doc_row, uint64_t lo, uint64_t hi, uint64_t r) { return tk_last_le(doc_row, lo, hi, r); }
 
 // A row as the write pass carries it from column to column: its document, the rows of that document, where its body lies in tokens
 struct TkPadRow {
@@ -107,7 +107,8 @@ TK_HD void tk_pad_row_set(const TkPad& p, uint64_t r, TkPadRow* w) {
     w->src = w->off + w->tok;
 }
 // row r of document d (doc_row[d] <= r < doc_row[d + 1]; d < n_docs, so entry d + 1 of both arrays exists)
-TK_HD void tk_pad_row_load(const TkPad& p, const uint64_t* tok_off, const uint32_t* doc_row, uint64_t d, uint64_t r, TkPadRow* w) {
+template <class Off, class Rows>
+TK_HD void tk_pad_row_load(const TkPad& p, Off tok_off, Rows doc_row, uint64_t d, uint64_t r, TkPadRow* w) {
     w->d = d;
     w->first = doc_row[d];
     w->next_first = doc_row[d + 1];
@@ -116,9 +117,19 @@ TK_HD void tk_pad_row_load(const TkPad& p, const uint64_t* tok_off, const uint32
     tk_pad_row_set(p, r, w);
 }
 // from row r - 1 to row r < R: the same document's next window, or the first row of the next document
-TK_HD void tk_pad_row_next(const TkPad& p, const uint64_t* tok_off, const uint32_t* doc_row, uint64_t r, TkPadRow* w) {
+template <class Off, class Rows>
+TK_HD void tk_pad_row_next(const TkPad& p, Off tok_off, Rows doc_row, uint64_t r, TkPadRow* w) {
     if (r >= w->next_first) tk_pad_row_load(p, tok_off, doc_row, w->d + 1, r, w);
     else tk_pad_row_set(p, r, w);
+}
+// Row r < R of the per-row pass (tk_k_pad_rows): its len, its document and its first body token (inside the document)
+template <class Off, class Rows>
+TK_HD void tk_pad_row_entry(const TkPad& p, Off tok_off, Rows doc_row, uint64_t r, uint32_t* len, uint32_t* row_doc, uint32_t* row_tok) {
+    TkPadRow w;
+    tk_pad_row_load(p, tok_off, doc_row, tk_pad_doc_of_row(doc_row, 0, p.n_docs, r), r, &w);
+    len[r] = w.len;
+    row_doc[r] = (uint32_t)w.d;
+    row_tok[r] = (uint32_t)w.tok;
 }
 
 // Where the element in column col < W of a row of `len` elements comes from; for the body *t is the index of the token inside the row's body
@@ -150,9 +161,9 @@ TK_HD bool tk_pad_all_body(const TkPad& p, uint32_t len, uint32_t col, uint32_t*
 // at and past N left as padding.  The lane's first row belongs to a document in [d_lo, d_hi) (doc_row[d_lo] <= i0 / W); from there it steps
 // from row to row.  N is below 2^32, so positions, rows and columns are 32-bit.  `tok` fetches body tokens: tok.one(i) is tokens[i], and
 // tok.eight(i, out) fetches tokens[i .. i + 8) as two 16-byte words where their address allows it and says whether it did -- the device
-// passes the caller's array, the CPU simulation one that checks every index.
-template <class Tok>
-TK_HD void tk_pad_lane(const TkPad& p, const Tok& tok, const uint64_t* tok_off, const uint32_t* doc_row, uint64_t d_lo, uint64_t d_hi, uint32_t i0, uint32_t N,
+// passes the caller's arrays, the CPU simulation ones that check every index (tok_off and doc_row, indexed with [], too).
+template <class Tok, class Off, class Rows>
+TK_HD void tk_pad_lane(const TkPad& p, const Tok& tok, Off tok_off, Rows doc_row, uint64_t d_lo, uint64_t d_hi, uint32_t i0, uint32_t N,
                        uint32_t id[8], uint64_t* mask_out) {
     uint32_t r = i0 / p.W, col = i0 - r * p.W;
     TkPadRow w;
@@ -181,7 +192,8 @@ TK_HD void tk_pad_lane(const TkPad& p, const Tok& tok, const uint64_t* tok_off, 
     *mask_out = mask;
 }
 // The documents a workgroup's lanes search between: those of the rows of its first position b0 < N and of its last
-TK_HD void tk_pad_block_docs(const TkPad& p, const uint32_t* doc_row, uint32_t b0, uint32_t block, uint32_t N, uint64_t* d_lo, uint64_t* d_hi) {
+template <class Rows>
+TK_HD void tk_pad_block_docs(const TkPad& p, Rows doc_row, uint32_t b0, uint32_t block, uint32_t N, uint64_t* d_lo, uint64_t* d_hi) {
     const uint32_t last = N - b0 > block ? b0 + block - 1 : N - 1;
     *d_lo = tk_pad_doc_of_row(doc_row, 0, p.n_docs, b0 / p.W);
     *d_hi = tk_pad_doc_of_row(doc_row, *d_lo, p.n_docs, last / p.W) + 1;

@@ -51,24 +51,25 @@ TK_HD uint32_t tk_rows_off_error(uint64_t a, uint64_t b, uint64_t d, uint64_t n_
 }
 // the word an offending entry is reported in: the lowest key is the first offending document (entry n_docs speaks for the last document)
 TK_HD uint64_t tk_rows_bad_key(uint64_t d, uint64_t n_docs, uint32_t why) { return ((d == n_docs && d ? d - 1 : d) << 2) | why; }
-// The head of a pass over the entries of tok_off (the row passes' and the padded passes'): *a = entry d, *b = the next one (n_tokens behind
-// the last), and what tk_rows_off_error says about them.  An offending entry's key goes into *bad, which keeps the lowest: on the device
-// that is the report word TK_BAD_OFF (all ones = none), shared by every thread, on the CPU a plain variable.  `tok_off` is indexed with []:
-// the device passes the caller's array, a CPU simulation may pass one that checks every index.
+// A report word that keeps the lowest value it is handed: on the device a word every thread shares (all ones = none), on the CPU a plain variable
+TK_HD void tk_report_min(unsigned long long* word, unsigned long long v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    atomicMin(word, v);
+#else
+    *word = v < *word ? v : *word;
+#endif
+}
+// The head of a pass over the entries of an offsets array (tok_off in the row, padded and samples passes; sample_off): *a = entry d, *b =
+// the next one (n_tokens behind the last), and what tk_rows_off_error says about them.  An offending entry's key goes into *bad, the report
+// word TK_BAD_OFF, which keeps the lowest.  `tok_off` is indexed with []: the device passes the caller's array, a CPU simulation may pass
+// one that checks every index.
 enum { TK_BAD_OFF = 0 };
 template <class Off>
 TK_HD uint32_t tk_rows_off_check(Off tok_off, uint64_t d, uint64_t n_docs, uint64_t n_tokens, uint64_t* a, uint64_t* b, unsigned long long* bad) {
     *a = tok_off[d];
     *b = d < n_docs ? tok_off[d + 1] : n_tokens;
     const uint32_t why = tk_rows_off_error(*a, *b, d, n_docs);
-    if (why) {
-        const unsigned long long key = tk_rows_bad_key(d, n_docs, why);
-#if defined(__HIP_DEVICE_COMPILE__)
-        atomicMin(bad, key);
-#else
-        *bad = key < *bad ? key : *bad;
-#endif
-    }
+    if (why) tk_report_min(bad, tk_rows_bad_key(d, n_docs, why));
     return why;
 }
 // The stream position entry d marks, or all ones: the start of a document that owns a position (with k == 0 an empty document owns none),
@@ -80,17 +81,33 @@ TK_HD uint64_t tk_rows_mark_at(uint64_t a, uint64_t b, uint64_t d, const TkRows&
     return (r.k || b > a) && p < r.M ? p : ~0ull;
 }
 
-// The document a stream position j < S belongs to, searched in [lo, hi): the last d there with out_off(d) <= j (out_off(lo) <= j).  Behind a
-// run of empty documents with k == 0 that is the one that is not empty -- the last of those that start at one position.
-template <class Off>
-TK_HD uint64_t tk_rows_last_doc(Off tok_off, uint64_t lo, uint64_t hi, uint32_t k, uint64_t j) {
-    uint64_t a = lo, b = hi;  // first index with out_off > j
+// The one search of the row, padded and samples passes: the last index in [lo, hi) whose key is <= x, lo if there is none.  key[mid] is
+// the key of entry mid (doc_row, pstart, or a reader that computes it); the keys do not descend.  Among entries with one key -- a run of
+// empty documents, of empty parts -- that is the last: the one that is not empty, the one that owns the position.
+template <class Key>
+TK_HD uint64_t tk_last_le(Key key, uint64_t lo, uint64_t hi, uint64_t x) {
+    uint64_t a = lo, b = hi;  // first index with key > x
     while (a < b) {
         const uint64_t mid = (a + b) >> 1;
-        if (tk_rows_out_off(tok_off[mid], mid, k) <= j) a = mid + 1;
+        if (key[mid] <= x) a = mid + 1;
         else b = mid;
     }
     return a > lo ? a - 1 : lo;
+}
+// The document a stream position j < S belongs to, searched in [lo, hi): the last d there with out_off(d) <= j (out_off(lo) <= j)
+template <class Off>
+struct TkRowsOutOff {
+    Off tok_off;
+    uint32_t k;
+    TK_HD uint64_t operator[](uint64_t d) const { return tk_rows_out_off(tok_off[d], d, k); }
+};
+template <class Off>
+TK_HD uint64_t tk_rows_last_doc(Off tok_off, uint64_t lo, uint64_t hi, uint32_t k, uint64_t j) { return tk_last_le(TkRowsOutOff<Off>{tok_off, k}, lo, hi, j); }
+// The width of padded rows (tk_pad_size, tk_smp_size): the longest rounded up to a multiple of width_multiple, at most max_len (0: max_len)
+TK_HD uint32_t tk_row_width(uint32_t max_len, uint32_t width_multiple, uint32_t longest) {
+    if (!width_multiple) return max_len;
+    const uint64_t w = ((uint64_t)longest + width_multiple - 1) / width_multiple * width_multiple;
+    return w < max_len ? (uint32_t)w : max_len;
 }
 
 // Where the element at position p of document d (stream range [start, next)) comes from: TK_ROWS_BOS, TK_ROWS_EOS, or the body -- then

@@ -24,6 +24,9 @@
 // The three caller arrays: tk_k_smp_count indexes nothing with their entries except the role table with a role it has compared with
 // n_roles; tk_k_smp_samples runs behind it and does nothing when it reported; the host launches tk_k_smp_write only when nothing was
 // reported.  So no kernel reads or writes out of bounds whatever tok_off, sample_off and part_role hold.
+// What the CPU simulation (tests/test_samples_sim.py) shares with the kernels: tk_smp_count_entry (the body of tk_k_smp_count's loop),
+// tk_smp_reported and tk_smp_sample_entry (tk_k_smp_samples') and tk_smp_lane (tk_k_smp_write); the wave reduction, the atomicMax, the
+// scan, the LDS copy of the role table and the stores are the kernels' own.
 // Included by tk_api.hip only.
 #pragma once
 #include "tk_decode.h"
@@ -64,12 +67,8 @@ __global__ __launch_bounds__(256) void tk_k_smp_samples(const uint64_t* __restri
     const TkSmpRolesPtr t{tab.off, tab.ids, tab.train};
     uint32_t longest = 0;
     for (uint64_t s = blockIdx.x * 256ull + threadIdx.x; s < p.n_samples; s += (uint64_t)gridDim.x * 256) {
-        TkSmpRow w;
-        tk_smp_row_load(p, sample_off, pstart, s, &w);
-        full[s] = w.full;
-        len[s] = w.len;
-        n_trained[s] = tk_smp_n_trained(p, w, pstart, part_role, t);
-        longest = w.len > longest ? w.len : longest;
+        const uint32_t l = tk_smp_sample_entry(p, sample_off, pstart, part_role, t, s, full, len, n_trained);
+        longest = l > longest ? l : longest;
     }
     longest = tk_wave_max_u32(longest);  // (behind the loop: every lane is here)
     if ((threadIdx.x & 63) == 0 && longest) atomicMax(words + TK_SMP_LONGEST, (unsigned long long)longest);

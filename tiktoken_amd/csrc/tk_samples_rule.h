@@ -10,7 +10,7 @@
 #pragma once
 #include <stdint.h>
 
-#include "tk_rows_rule.h"  // TK_ROWS_NONE, tk_rows_off_check, tk_rows_bad_key
+#include "tk_rows_rule.h"  // TK_ROWS_NONE, tk_rows_off_check, tk_report_min, tk_last_le, tk_row_width
 
 #define TK_SMPF_KEEP_TAIL 1u  // (= TK_SMP_KEEP_TAIL, TK_SMP_LEFT of the C ABI; tk_api.hip asserts it)
 #define TK_SMPF_LEFT 2u
@@ -62,11 +62,7 @@ inline int tk_smp_shape(uint64_t n_tokens, uint64_t n_parts, uint64_t n_samples,
 }
 // W once the per-sample pass has run.  0, or why it is refused: 9 the parts have 2^32 elements or more, 10 R * W >= 2^32.
 TK_HD int tk_smp_size(TkSmp* p, uint64_t total, uint32_t longest) {
-    p->W = p->max_len;
-    if (p->width_multiple) {
-        const uint64_t w = ((uint64_t)longest + p->width_multiple - 1) / p->width_multiple * p->width_multiple;
-        if (w < p->max_len) p->W = (uint32_t)w;
-    }
+    p->W = tk_row_width(p->max_len, p->width_multiple, longest);
     if (total >> 32) return 9;
     if ((p->R * p->W) >> 32) return 10;
     return 0;
@@ -91,13 +87,6 @@ TK_HD uint64_t tk_smp_part_count(uint32_t n_before, uint64_t n_body, uint32_t n_
 // sample_off, the first part whose role is no role (all ones = none), the elements of all parts, the longest len
 enum { TK_SMP_BAD_SOFF = TK_BAD_OFF + 1, TK_SMP_BAD_ROLE, TK_SMP_TOTAL, TK_SMP_LONGEST, TK_SMP_WORDS };
 
-TK_HD void tk_smp_report_min(unsigned long long* word, unsigned long long v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    atomicMin(word, v);
-#else
-    *word = v < *word ? v : *word;
-#endif
-}
 // Entry i of the count pass, i <= max(n_parts, n_samples): entry i of tok_off and of sample_off is checked where it exists (an offending
 // one goes into its report word; nothing is indexed with either), the role of part i is checked, and pstart[i] = the elements of part i
 // (0 where its entry or its role offends).  `off` of the role table: global memory here, 2 * n_roles + 1 entries.
@@ -109,7 +98,7 @@ TK_HD void tk_smp_count_entry(const TkSmp& p, Off tok_off, SOff sample_off, Role
         if (i < p.n_parts) {
             const uint32_t role = part_role[i];
             uint64_t cnt = 0;
-            if (role >= p.n_roles) tk_smp_report_min(words + TK_SMP_BAD_ROLE, i);
+            if (role >= p.n_roles) tk_report_min(words + TK_SMP_BAD_ROLE, i);
             else cnt = tk_smp_part_count(role_off[2 * role + 1] - role_off[2 * role], why ? 0 : b - a, role_off[2 * role + 2] - role_off[2 * role + 1]);
             pstart[i] = cnt;
         }
@@ -124,20 +113,8 @@ TK_HD bool tk_smp_reported(const unsigned long long* words) {
     return words[TK_BAD_OFF] != ~0ull || words[TK_SMP_BAD_SOFF] != ~0ull || words[TK_SMP_BAD_ROLE] != ~0ull;
 }
 
-// The part that holds element g (counted over all parts), searched in [lo, hi): the last p there with pstart[p] <= g (pstart[lo] <= g).
-// Behind a run of empty parts that is the one that is not empty -- the last of those that start at one element -- as in tk_rows_last_doc.
-template <class PS>
-TK_HD uint64_t tk_smp_part_of(PS pstart, uint64_t lo, uint64_t hi, uint64_t g) {
-    uint64_t a = lo, b = hi;  // first index with pstart > g
-    while (a < b) {
-        const uint64_t mid = (a + b) >> 1;
-        if (pstart[mid] <= g) a = mid + 1;
-        else b = mid;
-    }
-    return a > lo ? a - 1 : lo;
-}
-
-// A sample as the passes carry it: its parts [a, b), the element its first part starts at, its stream length, what the row keeps
+// A sample as the passes carry it: its parts [a, b), the element its first part starts at, its stream length, what the row keeps.  The part
+// that holds element g (counted over all parts) is tk_last_le(pstart, lo, hi, g), searched in [lo, hi) of [a, b) (pstart[lo] <= g).
 struct TkSmpRow {
     uint64_t a, b, base, full;
     uint32_t len, lo;  // elements kept; the stream position of the first one (below 2^32: full - len with len = max_len)
@@ -188,7 +165,7 @@ TK_HD uint32_t tk_smp_n_trained(const TkSmp& p, const TkSmpRow& w, PS pstart, Ro
     uint64_t n = 0;
     if (e0 < e1) {
         const uint64_t g0 = w.base + e0, g1 = w.base + e1;
-        for (uint64_t q = tk_smp_part_of(pstart, w.a, w.b, g0); q < w.b; ++q) {
+        for (uint64_t q = tk_last_le(pstart, w.a, w.b, g0); q < w.b; ++q) {
             const uint64_t ps = pstart[q], pe = pstart[q + 1];
             if (ps >= g1) break;
             const uint32_t role = part_role[q];
@@ -199,6 +176,17 @@ TK_HD uint32_t tk_smp_n_trained(const TkSmp& p, const TkSmpRow& w, PS pstart, Ro
     }
     if (p.has_eos && w.len && end == w.full && tk_smp_eos_trained(w, part_role, t)) ++n;
     return (uint32_t)n;
+}
+
+// Sample s of the per-sample pass (tk_k_smp_samples): its full_len, len and n_trained; returns len
+template <class SOff, class PS, class Role, class Roles>
+TK_HD uint32_t tk_smp_sample_entry(const TkSmp& p, SOff sample_off, PS pstart, Role part_role, const Roles& t, uint64_t s, uint64_t* full, uint32_t* len, uint32_t* n_trained) {
+    TkSmpRow w;
+    tk_smp_row_load(p, sample_off, pstart, s, &w);
+    full[s] = w.full;
+    len[s] = w.len;
+    n_trained[s] = tk_smp_n_trained(p, w, pstart, part_role, t);
+    return w.len;
 }
 
 // The caller's arrays and the passes' own as a lane reads them; every member is indexed with [] (the device passes pointers, the CPU
@@ -263,7 +251,7 @@ TK_HD void tk_smp_lane(const TkSmp& p, const Tok& tok, const In& in, const Roles
         const uint64_t q0 = (uint64_t)w.lo + (col - lead);
         if (q0 >= p.has_bos && q0 + 8 + p.has_eos <= w.full) {
             const uint64_t g = w.base + (q0 - p.has_bos);
-            tk_smp_part_load(in, t, tk_smp_part_of(in.pstart, w.a, w.b, g), &c);
+            tk_smp_part_load(in, t, tk_last_le(in.pstart, w.a, w.b, g), &c);
             have = true;
             const uint64_t i = g - c.ps;
             wide = i >= c.n_before && i + 8 <= c.n_before + c.n_body && tok.eight(c.toff + (i - c.n_before), tw);
@@ -290,11 +278,11 @@ TK_HD void tk_smp_lane(const TkSmp& p, const Tok& tok, const In& in, const Roles
                     trains = tk_smp_eos_trained(w, in.part_role, t);
                 } else {
                     if (!have) {
-                        tk_smp_part_load(in, t, tk_smp_part_of(in.pstart, w.a, w.b, g), &c);
+                        tk_smp_part_load(in, t, tk_last_le(in.pstart, w.a, w.b, g), &c);
                         have = true;
                     } else if (g >= c.pe) {  // the next part that owns an element: the one after, unless that one is empty
                         uint64_t q = c.p + 1;
-                        if (in.pstart[q + 1] <= g) q = tk_smp_part_of(in.pstart, q + 1, w.b, g);
+                        if (in.pstart[q + 1] <= g) q = tk_last_le(in.pstart, q + 1, w.b, g);
                         tk_smp_part_load(in, t, q, &c);
                     }
                     src = tk_smp_in_part(g - c.ps, c.n_before, c.n_body, &k);
