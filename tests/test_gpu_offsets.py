@@ -96,6 +96,21 @@ def numpy_spans(enc, tokens, tok_off):
     return byte_off, char_off, gb[:-1] - byte_off[doc], np.where(cont[tokens] & (rel > 0), rel - 1, rel)
 
 
+def numpy_bytes(enc, tokens):
+    """The decoded bytes as a gather over a numpy table of the vocabulary's token bytes (nothing of the library's decode in it)"""
+    n_ids = enc.max_token_value + 1
+    table = [(enc._mergeable_ranks[t], t) for t in enc.token_byte_values()] + [(i, s.encode()) for s, i in enc._special_tokens.items()]
+    start, length = np.zeros(n_ids, np.int64), np.zeros(n_ids, np.int64)
+    at = 0
+    for i, t in table:
+        start[i], length[i] = at, len(t)
+        at += len(t)
+    blob = np.frombuffer(b"".join(t for _, t in table), np.uint8)
+    tl = length[tokens]
+    ends = np.cumsum(tl)
+    return blob[np.arange(int(ends[-1])) + np.repeat(start[tokens] - (ends - tl), tl)]
+
+
 def test_large_batch_against_numpy():
     enc = tiktoken.get_encoding("o200k_shaped")
     blob, off = h.gen_corpus(0x0FF5, 1, 12 << 20)
@@ -120,8 +135,9 @@ def test_large_batch_against_numpy():
     w_boff, w_coff, w_bs, w_cs = numpy_spans(enc, tokens, tok_off)
     assert np.array_equal(byte_off, w_boff) and np.array_equal(char_off, w_coff)
     assert np.array_equal(byte_start, w_bs) and np.array_equal(char_start, w_cs)
+    w_bytes = numpy_bytes(enc, tokens)
     ref_bytes, ref_off = enc._core_bpe.decode_batch_packed(tokens, tok_off, as_array=True)
-    assert np.array_equal(ref_off, byte_off) and np.array_equal(ref_bytes, data)
+    assert np.array_equal(ref_off, w_boff) and np.array_equal(ref_bytes, w_bytes) and np.array_equal(data, w_bytes)
     # spans only: the same arrays, no bytes
     only = enc._core_bpe.decode_batch_spans_packed(tokens, tok_off, want_bytes=False, validate=False)
     assert only[0] is None and np.array_equal(only[3], w_bs) and np.array_equal(only[4], w_cs) and np.array_equal(only[2], w_coff)

@@ -9,9 +9,7 @@
 #pragma once
 #include "tk_kernels.h"
 #include "tk_device.h"
-
-#define TK_DEC_SPEC 0x80000000u  // entry.x bit: the bytes live in the special-token blob
-#define TK_DEC_BLOCK 2048        // tokens per workgroup of the scan passes (256 threads x 8)
+#include "tk_decode_rule.h"  // TK_DEC_SPEC, TK_DEC_BLOCK, tk_dec_len_of, tk_dec_lane, tk_dec_doc_off
 
 __global__ __launch_bounds__(256) void tk_k_dec_len(const uint32_t* __restrict__ tokens, uint64_t n, const uint2* __restrict__ dec,
                                                     uint32_t n_ids, uint32_t* __restrict__ lens, unsigned long long* __restrict__ bsum,
@@ -26,7 +24,7 @@ __global__ __launch_bounds__(256) void tk_k_dec_len(const uint32_t* __restrict__
         uint32_t len = 0;
         if (i < n) {
             const uint32_t t = tokens[i];
-            len = t < n_ids ? dec[t].y : 0u;
+            len = tk_dec_len_of(dec, n_ids, t);
             if (len == 0u) atomicMin(bad, (unsigned long long)(pos_base + i));  // (every real token has at least one byte)
             lens[i] = len;
         }
@@ -62,47 +60,9 @@ __global__ __launch_bounds__(256) void tk_k_dec_copy(const uint32_t* __restrict_
     }
     uint32_t tot;
     const uint32_t ex = tk_block_exscan_256(mine, &tot, sh);
-    unsigned long long at = bbase[blockIdx.x] + ex;
-    // the stream: `acc` holds the bytes of the aligned word at `word` from byte `fill` on (bytes below `first_lo` of the first word are
-    // a neighbour's)
-    unsigned long long word = at & ~7ull;
-    const uint32_t first_lo = (uint32_t)(at & 7ull);
-    uint32_t fill = first_lo;
-    uint64_t acc = 0;
-    bool first = true;
-    auto flush = [&](uint32_t upto /* bytes of the word that are valid: fill */) {
-        if (!first && upto == 8u) {
-            *(uint64_t*)(out + word) = acc;
-        } else {
-            for (uint32_t b = first ? first_lo : 0u; b < upto; ++b) out[word + b] = (uint8_t)(acc >> (8u * b));
-        }
-        first = false;
-    };
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const uint64_t i = i0 + j;
-        if (i < n) {
-            if (tok_byte_off) tok_byte_off[i] = off_base + at;
-            const uint2 e = dec[tokens[i]];
-            const uint8_t* src = ((e.x & TK_DEC_SPEC) ? spec_bytes : tok_bytes);
-            const uint64_t so = e.x & ~TK_DEC_SPEC;
-            for (uint32_t b = 0; b < len[j]; b += 8u) {
-                const uint32_t nb = len[j] - b < 8u ? len[j] - b : 8u;
-                const uint64_t w = tk_mask_low_bytes(tk_load8(src, so + b), nb);
-                acc |= w << (8u * fill);
-                if (fill + nb >= 8u) {
-                    flush(8u);
-                    acc = fill ? (w >> (8u * (8u - fill))) : 0ull;
-                    word += 8ull;
-                    fill = fill + nb - 8u;
-                } else {
-                    fill += nb;
-                }
-            }
-            at += len[j];
-        }
-    }
-    if (fill > (first ? first_lo : 0u)) flush(fill);
+    const unsigned long long at = bbase[blockIdx.x] + ex;
+    TkDecStores stores{out};
+    tk_dec_lane(tokens, i0, n, len, at, dec, tok_bytes, spec_bytes, stores, tok_byte_off, off_base);
 }
 
 // byte_off[d] = byte offset of the first token of document d (tok_off: n_docs + 1 token offsets, non-decreasing)
@@ -110,7 +70,6 @@ __global__ __launch_bounds__(256) void tk_k_dec_docoff(const uint64_t* __restric
                                                        const unsigned long long* __restrict__ tok_byte_off,
                                                        const unsigned long long* __restrict__ total, uint64_t* __restrict__ byte_off) {
     for (uint64_t d = blockIdx.x * 256ull + threadIdx.x; d <= n_docs; d += (uint64_t)gridDim.x * 256) {
-        const uint64_t t = tok_off[d];
-        byte_off[d] = t < n ? tok_byte_off[t] : total[0];
+        byte_off[d] = tk_dec_doc_off(tok_off, d, n, tok_byte_off, total);
     }
 }
