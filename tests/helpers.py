@@ -375,6 +375,10 @@ def sim_lib():
         L.tks_destroy.argtypes = [vp]
         L.tks_n_pairs.restype = u64
         L.tks_n_pairs.argtypes = [vp]
+        L.tks_lookup_pair.restype = ctypes.c_uint32
+        L.tks_lookup_pair.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32]
+        L.tks_table_format.restype = ctypes.c_uint32
+        L.tks_table_format.argtypes = [vp]
         L.tks_tables_digest.restype = u64
         L.tks_tables_digest.argtypes = [vp]
         L.tks_pretok.restype = u64
@@ -426,6 +430,14 @@ class HostSim:
 
     def n_pairs(self):
         return sim_lib().tks_n_pairs(self._h)
+
+    def lookup_pair(self, a: int, b: int) -> int:
+        """tk_probe_pair on the sim's pair table: the id of the token whose bytes are those of a and b, or 0xFFFFFFFF"""
+        return sim_lib().tks_lookup_pair(self._h, a, b)
+
+    def table_format(self) -> int:
+        """bit 0: a short table; bit 1: the pair table packed; bit 2: the host decoder dense"""
+        return sim_lib().tks_table_format(self._h)
 
     def table_stats(self):
         probes, slots = (ctypes.c_double * 3)(), (ctypes.c_uint64 * 3)()

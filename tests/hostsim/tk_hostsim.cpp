@@ -119,6 +119,13 @@ void* tks_create(const uint8_t* ranks_blob, const uint64_t* ranks_off, const uin
 }
 void tks_destroy(void* p) { delete (Sim*)p; }
 uint64_t tks_n_pairs(void* p) { return ((Sim*)p)->H.n_pairs; }
+// the merge kernels' probe of the pair table, packed or wide: the id of the token a + b, TK_RANK_MAX when there is none
+uint32_t tks_lookup_pair(void* p, uint32_t a, uint32_t b) { return tk_probe_pair(((Sim*)p)->T, a, b); }
+// which tables the vocabulary's ids left: bit 0 a short table, bit 1 the pair table packed, bit 2 the host decoder dense
+uint32_t tks_table_format(void* p) {
+    const Sim* s = (const Sim*)p;
+    return (s->T.short_tab ? 1u : 0u) | (s->T.pair8 ? 2u : 0u) | (s->H.dec_is_dense ? 4u : 0u);
+}
 // FNV-1a over every table the device gets (the build must not depend on the number of host threads)
 uint64_t tks_tables_digest(void* p) {
     const TkHostTables& H = ((Sim*)p)->H;

@@ -231,11 +231,14 @@ def test_pair_table_is_exactly_the_set_of_token_splits():
     ranks = h.load_vocab("gpt2_shaped")
     sim = h.HostSim(h.PAT_STR[0], ranks, {})
     n = 0
-    for tb in list(ranks)[::17]:
+    for tb, r in ranks.items():
         for s in range(1, len(tb)):
-            if tb[:s] in ranks and tb[s:] in ranks:
+            a, b = ranks.get(tb[:s]), ranks.get(tb[s:])
+            if a is not None and b is not None:
                 n += 1
-    assert sim.n_pairs() >= n > 0
+                assert sim.lookup_pair(a, b) == r, (tb, s)
+    assert sim.n_pairs() == n > 0
+    # (other vocabulary shapes, and pairs that must be absent: tests/test_vocab_shapes_sim.py)
 
 
 def test_rejects_bad_vocabularies():

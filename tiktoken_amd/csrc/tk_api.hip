@@ -3816,6 +3816,10 @@ extern "C" uint64_t tk_stat(tk_core* c, const char* name) {
     if (k == "host_finish_us") return (uint64_t)c->host_us[3];
     if (k == "host_tail_us") return (uint64_t)c->host_us[4];
     if (k == "host_total_us") return (uint64_t)c->host_us[5];
+    // which device tables the vocabulary's ids left this core with (tk_build_tables, tk_create): tests assert the path they mean to take
+    if (k == "pair_table_packed") return c->D.pair8 != nullptr;  // 0: 16-byte slots, and a merge kernel per length bin instead of tk_k_merge_all
+    if (k == "short_table") return c->D.short_tab != nullptr;    // 0: tokens of 1..4 bytes live in the mid table
+    if (k == "decode_table_ids") return c->n_dec;                // 0: ids too sparse for the device decode table
     if (k == "chunk_bytes") return c->chunk_bytes;
     if (k == "stage_bytes") return TK_STAGE_BYTES;  // a block of text on its way to the device; host-buffer batches of twice that and more are pipelined (encode_batch_impl)
 #ifdef TKF_TIMING

@@ -106,7 +106,9 @@ struct TkShortSlot {  // 8 bytes
     uint32_t val;      // rank | (len - 1) << 30; 0xFFFFFFFF = empty
 };
 #define TK_SHORT_EMPTY 0xFFFFFFFFu
-#define TK_SHORT_MAX_RANK 0x3FFFFFFFu  // larger ranks: no short table, pieces of <= 4 bytes live in the mid table
+#define TK_SHORT_RANK_MASK 0x3FFFFFFFu
+#define TK_SHORT_MAX_RANK 0x3FFFFFFEu  // larger ranks: no short table, pieces of <= 4 bytes live in the mid table (rank 0x3FFFFFFF fits the field, but
+                                      // with a length of 4 its val IS TK_SHORT_EMPTY: the token would never be found)
 // Pieces of 9..23 bytes -- a fifth of the pieces of web text, and three in five of them are NOT tokens -- are looked up by their IDENTITY:
 // three words that hold the bytes themselves and the length (tk_ident), so that a slot answers exactly without a look at the token blob
 // (the 16-byte slots of `piece` hold a hash; their candidates are verified in the blob: a chain of dependent loads, and a hash over all

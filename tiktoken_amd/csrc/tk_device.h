@@ -744,7 +744,7 @@ TK_HD uint32_t tk_piece_len_bits32(const W32& w, A& a, uint64_t p, uint32_t c, T
 // Short: key = the 1..4 bytes packed little-endian.
 TK_HD uint32_t tk_probe_short_from(const TkTables& T, uint32_t key, uint32_t len, uint32_t i, TkShortSlot s) {
     for (;;) {
-        if (s.key == key && (s.val >> 30) == len - 1u && s.val != TK_SHORT_EMPTY) return s.val & TK_SHORT_MAX_RANK;
+        if (s.key == key && (s.val >> 30) == len - 1u && s.val != TK_SHORT_EMPTY) return s.val & TK_SHORT_RANK_MASK;
         if (s.val == TK_SHORT_EMPTY) return TK_RANK_MAX;
         i = (i + 1u) & T.short_mask;
         s = T.short_tab[i];

@@ -78,7 +78,7 @@ uint32_t TkHostTables::lookup_piece(const uint8_t* p, uint32_t len) const {
             for (;;) {
                 const TkShortSlot& s = short_tab[i];
                 if (s.val == TK_SHORT_EMPTY) return TK_RANK_MAX;
-                if (s.key == (uint32_t)key && (s.val >> 30) == len - 1) return s.val & TK_SHORT_MAX_RANK;
+                if (s.key == (uint32_t)key && (s.val >> 30) == len - 1) return s.val & TK_SHORT_RANK_MASK;
                 i = (i + 1) & short_mask;
             }
         }
