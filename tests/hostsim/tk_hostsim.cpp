@@ -692,7 +692,8 @@ uint64_t tks_chunk_check(void* pv, const uint8_t* text_in, uint64_t n, const uin
 }
 
 // Mirror of the per-piece work (whole-piece probe, lane merge) for pieces of <= 16 bytes; longer pieces use the
-// same probes with a simple sequential merge over ids (the wave / tree kernels cannot run here).
+// same probes with a simple sequential merge over ids.  (The kernels for pieces of more than TK_GLANE_MAX bytes -- the rounds and the level
+// tree -- run on the CPU in merge_sim.cpp, through the rules they share with it: tk_merge_rule.h.)
 int64_t tks_encode_piece(void* p, const uint8_t* piece, uint32_t len, uint32_t* out) {
     Sim* s = (Sim*)p;
     std::vector<uint8_t> text(piece, piece + len);

@@ -669,6 +669,35 @@ def test_rounds_and_one_at_a_time_merges_agree(monkeypatch):
     assert np.array_equal(toff, ro) and np.array_equal(toks, rt)
 
 
+TK_WIDE_MIN = 1 << 17  # tk_fused.h: from here on all the workgroups of tk_k_merge_rounds_wide share a piece
+
+
+@pytest.fixture(scope="module")
+def long_piece_cores(cores):
+    """(core, oracle) by vocabulary: gpt2_shaped, and the untrained 3 000-string vocabulary of tests/vocab_shapes.py -- its ranks say nothing
+    about length, so rounds are not valid there and pieces are redone one merge at a time"""
+    import vocab_shapes as vs
+    from oracle import c_oracle
+    from tiktoken_amd import CoreBPE
+
+    ranks, specials = vs.vocab("untrained", "dense")
+    return {"gpt2_shaped": (cores["gpt2_shaped"], h.c_oracle_for("gpt2_shaped")),
+            "untrained": (CoreBPE(ranks, specials, h.PAT_STR[0]), c_oracle.COracle(0, ranks, specials))}
+
+
+@pytest.mark.parametrize("n", [1025, 8191, 8192, 8193, TK_WIDE_MIN - 1, TK_WIDE_MIN, TK_WIDE_MIN + 1])
+@pytest.mark.parametrize("name", ["gpt2_shaped", "untrained"])
+def test_long_pieces_at_the_boundary_lengths(long_piece_cores, name, n):
+    """Single pieces one above TK_GLANE_MAX, either side of 16 rows of 512 parts (a workgroup's wavefronts with one row each, then two)
+    and either side of TK_WIDE_MIN: a run of one byte, "abab...", random letters; token for token the C oracle's, and counted as long pieces."""
+    core, C = long_piece_cores[name]
+    rng = np.random.default_rng(n)
+    # ("ae...": both letters are of the untrained vocabulary's alphabet, where "ab..." has no pair that is a token and runs no round)
+    for piece in (b"a" * n, (b"ab" * n)[:n], (b"ae" * n)[:n], bytes(rng.choice(np.frombuffer(b"aeinst", np.uint8), size=n))):
+        assert core.encode_single_piece(piece) == C.encode_piece(piece), (name, n, piece[:8])
+        assert core.last_stats()["long_pieces"] == 1
+
+
 # ---------------------------------------------------------------- decode on the device (src/lib.rs:345-358)
 def test_decode_batch_on_device(cores):
     core = cores["o200k_shaped"]

@@ -37,6 +37,7 @@
 
 #include "tk_chunk.h"
 #include "tk_kernels.h"
+#include "tk_merge_rule.h"
 
 #define TKF_NONE 0xFFFFFFFFu
 #define TK_MERGE_REDO 0xFFFFFFFFu  // TkMissData::res_cnt after tk_k_merge_rounds: the piece has to go through tk_k_merge_long
@@ -2640,35 +2641,19 @@ __global__ __launch_bounds__(256) void tk_k_merge_long(TkTables T, const uint8_t
         uint32_t* pv = g_pv + ent[3];
         uint64_t* lv = g_lv + ent[4];
         uint32_t cntl[TK_MAX_LEVELS + 1], offl[TK_MAX_LEVELS + 1];
-        int nl = 0;
-        cntl[0] = n;
-        offl[0] = 0;
-        {
-            uint32_t c = n, o = 0;
-            do {
-                c = (c + 63) >> 6;
-                ++nl;
-                cntl[nl] = c;
-                offl[nl] = o;
-                o += c;
-            } while (c > 64);
-        }
+        const int nl = tk_long_levels(n, cntl, offl);
         for (uint32_t k = lane; k < n; k += 64) {
-            uint32_t b0 = text[s + k];
-            id[k] = T.byte_rank[b0];
-            rk[k] = k + 1 < n ? T.pair2[(b0 << 8) | text[s + k + 1]] : TK_RANK_MAX;
+            tk_piece_part(T, text, s, k, n, id[k], rk[k]);
             nx[k] = k + 1;
             pv[k] = k - 1;
         }
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        auto refresh = [&](int l, uint32_t b) {  // entry b of level l <- the minimum of its 64 entries of the level below
+            const uint64_t key = tk_wave_min_u64(tk_long_key(cntl, offl, l, b * 64 + lane, rk, lv));
+            if (lane == 0) lv[offl[l] + b] = key;
+        };
         for (int l = 1; l <= nl; ++l) {
-            for (uint32_t b = 0; b < cntl[l]; ++b) {
-                uint32_t k = b * 64 + lane;
-                uint64_t key = ~0ull;
-                if (k < cntl[l - 1]) key = l == 1 ? (((uint64_t)rk[k] << 32) | k) : lv[offl[l - 1] + k];
-                key = tk_wave_min_u64(key);
-                if (lane == 0) lv[offl[l] + b] = key;
-            }
+            for (uint32_t b = 0; b < cntl[l]; ++b) refresh(l, b);
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         }
         for (;;) {
@@ -2682,31 +2667,15 @@ __global__ __launch_bounds__(256) void tk_k_merge_long(TkTables T, const uint8_t
             const uint32_t pp = pv[i];
             uint32_t newr = TK_RANK_MAX;
             if (lane == 0 && nn < n) newr = tk_probe_pair(T, m, id[nn]);
-            if (lane == 1 && pp != 0xFFFFFFFFu) newr = tk_probe_pair(T, id[pp], m);
-            if (lane == 0) {
-                id[i] = m;
-                nx[i] = nn;
-                if (nn < n) pv[nn] = i;
-                rk[j] = TK_RANK_MAX;
-                id[j] = TK_RANK_MAX;  // absorbed (no token has this id): the emit below compacts on it
-                rk[i] = newr;
-            }
-            if (lane == 1 && pp != 0xFFFFFFFFu) rk[pp] = newr;
+            if (lane == 1 && pp != TK_LONG_NONE) newr = tk_probe_pair(T, id[pp], m);
+            if (lane == 0) tk_long_link(id, rk, nx, pv, n, m, i, j, nn, newr);
+            if (lane == 1 && pp != TK_LONG_NONE) rk[pp] = newr;
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-            uint32_t bi = i, bj = j, bp = pp != 0xFFFFFFFFu ? pp : i;
             for (int l = 1; l <= nl; ++l) {
-                bi >>= 6;
-                bj >>= 6;
-                bp >>= 6;
-                for (int t = 0; t < 3; ++t) {
-                    uint32_t b = t == 0 ? bp : (t == 1 ? bi : bj);
-                    if ((t == 1 && bi == bp) || (t == 2 && (bj == bi || bj == bp))) continue;
-                    uint32_t k = b * 64 + lane;
-                    uint64_t key = ~0ull;
-                    if (k < cntl[l - 1]) key = l == 1 ? (((uint64_t)rk[k] << 32) | k) : lv[offl[l - 1] + k];
-                    key = tk_wave_min_u64(key);
-                    if (lane == 0) lv[offl[l] + b] = key;
-                }
+                const TkLongBlocks B = tk_long_blocks(l, i, j, pp);
+#pragma unroll
+                for (int t = 0; t < 3; ++t)
+                    if (B.on[t]) refresh(l, B.b[t]);
                 __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
             }
         }
@@ -2735,13 +2704,9 @@ __global__ __launch_bounds__(256) void tk_k_merge_long(TkTables T, const uint8_t
 // at a time, the reference's order literally), so the result never depends on the assumption.
 //   P0/R0 and P1/R1: the parts (token ids) and the rank of each part's pair with its right neighbour, double-buffered and compacted every round.
 // ------------------------------------------------------------------------------------------
+// The rules of a round -- which parts survive, how the ranges' summaries compose, when a round is not valid -- are tk_merge_rule.h's.
 #define TKB_THREADS 1024
-struct TkRunState {  // segment summary for the run-parity scan: is the segment all rank-m pairs, parity of its trailing run of them
-    uint32_t all, par;
-};
-__device__ __forceinline__ TkRunState tk_run_combine(TkRunState a, TkRunState b) { return TkRunState{a.all & b.all, b.all ? (a.par ^ b.par) : b.par}; }
-
-// inclusive scan of run states over a wavefront (lane order = element order)
+// inclusive scan of run states (tk_merge_rule.h) over a wavefront (lane order = element order)
 __device__ __forceinline__ TkRunState tk_run_scan_wave(TkRunState v, int lane) {
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
@@ -2749,6 +2714,12 @@ __device__ __forceinline__ TkRunState tk_run_scan_wave(TkRunState v, int lane) {
         if (lane >= o) v = tk_run_combine(up, v);
     }
     return v;
+}
+__device__ __forceinline__ TkRunState tk_run_of_lane(TkRunState v, int src) { return TkRunState{(uint32_t)__shfl((int)v.all, src, 64), (uint32_t)__shfl((int)v.par, src, 64)}; }
+// from an inclusive scan: the state of everything before the lane
+__device__ __forceinline__ TkRunState tk_run_before_lane(TkRunState v, int lane) {
+    const TkRunState ex{(uint32_t)__shfl_up((int)v.all, 1, 64), (uint32_t)__shfl_up((int)v.par, 1, 64)};
+    return lane == 0 ? TkRunState{1u, 0u} : ex;
 }
 
 // The rounds of ONE piece, by one workgroup (WIDE = false) or by all the workgroups of the launch together (WIDE = true: pieces of
@@ -2789,7 +2760,6 @@ __device__ __forceinline__ void tk_rounds_piece(const TkTables& T, const uint8_t
     const int lane = tid & 63;
     const uint32_t wib = tid >> 6, wid = WIDE ? blockIdx.x * NWB + wib : wib;
     const uint32_t gtid = WIDE ? blockIdx.x * TKB_THREADS + tid : tid, gthreads = WIDE ? gridDim.x * TKB_THREADS : (uint32_t)TKB_THREADS;
-    constexpr uint32_t MARK = 0x80000000u;  // (token ids stay below 2^31: checked at tk_create)
     auto sync = [&]() {
         if constexpr (WIDE) tk_grid_barrier(&ws->bar, epoch);
         else __syncthreads();
@@ -2834,12 +2804,12 @@ __device__ __forceinline__ void tk_rounds_piece(const TkTables& T, const uint8_t
     }
     uint32_t m = TK_RANK_MAX;  // the lowest rank among the pairs: found while the ranks are written (no pass of its own)
     for (uint32_t k = gtid; k < n; k += gthreads) {
-        const uint32_t b0 = text[s + k];
-        P0[k] = T.byte_rank[b0];
-        const uint32_t r = k + 1 < n ? T.pair2[(b0 << 8) | text[s + k + 1]] : TK_RANK_MAX;
+        uint32_t r;
+        tk_piece_part(T, text, s, k, n, P0[k], r);
         R0[k] = r;
         m = r < m ? r : m;
     }
+    const auto probe = [&](uint32_t a, uint32_t b) { return tk_probe_pair(T, a, b); };
     uint32_t round = 0;
     m = all_min(m, round);
     uint32_t cnt = n;
@@ -2849,53 +2819,35 @@ __device__ __forceinline__ void tk_rounds_piece(const TkTables& T, const uint8_t
         // Every wavefront owns a contiguous range of the parts and walks it in rows of 512 (eight consecutive parts per lane: coalesced,
         // and one wave scan per row); the state that crosses lanes, rows and wavefronts is the parity of the run of rank-m pairs that
         // ends right before a part.
-        constexpr int EPL = 8;
-        constexpr uint32_t ROW = 64 * EPL;
+        constexpr uint32_t EPL = TK_MERGE_EPL, ROW = 64 * EPL;
         const uint32_t per = ((cnt + NWV - 1) / NWV + ROW - 1u) / ROW * ROW;
         const uint32_t wlo = wid * per < cnt ? wid * per : cnt, whi = wlo + per < cnt ? wlo + per : cnt;
-        // the parts of a lane: their ranks, rank-m flags (parts beyond the range: none) and the lane's run state
-        auto lane_state = [&](uint32_t i0, uint32_t rk[EPL], uint32_t& fm) -> TkRunState {
-            if (i0 + EPL <= whi) {  // (ranges and scratch offsets are multiples of four parts: 16-byte loads)
+        // the parts of a lane: their ranks, how many of them lie inside the range, their rank-m flags and the lane's run state
+        auto lane_state = [&](uint32_t i0, uint32_t rk[EPL], uint32_t& n_in, uint32_t& fm) -> TkRunState {
+            n_in = i0 < whi ? (whi - i0 < EPL ? whi - i0 : EPL) : 0u;
+            if (n_in == EPL) {  // (ranges and scratch offsets are multiples of four parts: 16-byte loads)
 #pragma unroll
-                for (int q = 0; q < EPL; q += 4) {
+                for (uint32_t q = 0; q < EPL; q += 4) {
                     const uint4 x = *(const uint4*)(R0 + i0 + q);
                     rk[q] = x.x; rk[q + 1] = x.y; rk[q + 2] = x.z; rk[q + 3] = x.w;
                 }
             } else {
 #pragma unroll
-                for (int q = 0; q < EPL; ++q) rk[q] = i0 + q < whi ? R0[i0 + q] : 0u;
+                for (uint32_t q = 0; q < EPL; ++q) rk[q] = q < n_in ? R0[i0 + q] : 0u;
             }
-            TkRunState v{1u, 0u};
-            fm = 0;
-#pragma unroll
-            for (int q = 0; q < EPL; ++q) {
-                const bool in = i0 + q < whi;
-                const uint32_t f = in ? (uint32_t)(rk[q] == m) : 0u;
-                fm |= f << q;
-                if (in) v = tk_run_combine(v, TkRunState{f, f});
-            }
-            return v;
+            return tk_merge_lane_state(rk, m, n_in, fm);
         };
-        // b. one pass gives, per wavefront range: its run state, the number of parts that survive (a part right after an odd count of
-        // rank-m pairs is absorbed) if no run enters the range, and the length of the run of rank-m pairs the range starts with -- a run
-        // of odd length that enters flips the fate of exactly those parts and the one after them
+        // b. one pass gives, per wavefront range, what tk_range_summary publishes: its run state, the parts that survive if no run enters
+        // the range, and the length of the run of rank-m pairs the range starts with
         uint32_t keep0 = 0, lead = 0;
         TkRunState acc{1u, 0u};
         {
             bool open = true;
             for (uint32_t r0 = wlo; r0 < whi; r0 += ROW) {
-                const uint32_t i0 = r0 + (uint32_t)EPL * lane;
-                uint32_t rk[EPL], fm;
-                TkRunState v = tk_run_scan_wave(lane_state(i0, rk, fm), lane);
-                TkRunState ex{(uint32_t)__shfl_up((int)v.all, 1, 64), (uint32_t)__shfl_up((int)v.par, 1, 64)};
-                if (lane == 0) ex = TkRunState{1u, 0u};
-                uint32_t c = tk_run_combine(acc, ex).par, kl = 0;  // parity of the run of rank-m pairs right before the lane's first part
-#pragma unroll
-                for (int q = 0; q < EPL; ++q) {
-                    kl += (uint32_t)(i0 + q < whi) & (c ^ 1u);
-                    c = ((fm >> q) & 1u) ? (c ^ 1u) : 0u;
-                }
-                keep0 += tk_wave_sum_u32(kl);
+                const uint32_t i0 = r0 + EPL * (uint32_t)lane;
+                uint32_t rk[EPL], n_in, fm;
+                const TkRunState v = tk_run_scan_wave(lane_state(i0, rk, n_in, fm), lane);
+                keep0 += tk_wave_sum_u32(tk_merge_lane_rule(tk_run_combine(acc, tk_run_before_lane(v, lane)).par, fm, n_in).count);
                 if (open) {  // (parts beyond the range have no flag: the leading run ends there at the latest)
                     const uint64_t stop = __ballot(fm != (1u << EPL) - 1u);
                     if (stop) {
@@ -2906,20 +2858,19 @@ __device__ __forceinline__ void tk_rounds_piece(const TkTables& T, const uint8_t
                     } else
                         lead += ROW;
                 }
-                acc = tk_run_combine(acc, TkRunState{(uint32_t)__shfl((int)v.all, 63, 64), (uint32_t)__shfl((int)v.par, 63, 64)});
+                acc = tk_run_combine(acc, tk_run_of_lane(v, 63));
             }
         }
         if (lane == 0) {
-            const uint32_t len = whi - wlo, aff = lead + 1u < len ? lead + 1u : len;
-            sc_put(0, acc.all);
-            sc_put(1, acc.par);
-            sc_put(2, keep0);
-            sc_put(3, aff & 1u);
+            const TkRangeSum sm = tk_range_summary(acc, keep0, lead, whi - wlo);
+            sc_put(0, sm.all), sc_put(1, sm.par);
+            sc_put(2, sm.keep0), sc_put(3, sm.odd);
         }
         if constexpr (WIDE) {
             if (gtid == 0) tk_st_agent(&ws->gmin[(round + 1u) & 1u], TK_RANK_MAX);  // (last read a round ago, next written after the barrier below)
         }
         sync();
+        const auto sum_get = [&](uint32_t q) { return TkRangeSum{sc_get(0, q), sc_get(1, q), sc_get(2, q), sc_get(3, q)}; };
         TkRunState before{1u, 0u};
         uint32_t at = 0, total = 0;
         if constexpr (WIDE) {
@@ -2931,88 +2882,59 @@ __device__ __forceinline__ void tk_rounds_piece(const TkTables& T, const uint8_t
             for (uint32_t j = 0; j < blk; ++j) {
                 const uint32_t q = (uint32_t)lane * blk + j;
                 if (q < NWV) {
-                    const uint32_t a = sc_get(0, q), pr = sc_get(1, q), kp = sc_get(2, q), od = sc_get(3, q);
-                    k0 += kp - (mine.par & od);
-                    k1 += kp - ((mine.all ? (mine.par ^ 1u) : mine.par) & od);
-                    mine = tk_run_combine(mine, TkRunState{a, pr});
+                    const TkRangeSum sm = sum_get(q);
+                    TkRunState odd_in = tk_run_combine(TkRunState{1u, 1u}, mine);
+                    k1 += tk_range_enter(odd_in, sm);
+                    k0 += tk_range_enter(mine, sm);
                 }
             }
-            // exclusive scan of the lanes' states
-            TkRunState inc = tk_run_scan_wave(mine, lane);
-            TkRunState ex{(uint32_t)__shfl_up((int)inc.all, 1, 64), (uint32_t)__shfl_up((int)inc.par, 1, 64)};
-            if (lane == 0) ex = TkRunState{1u, 0u};
+            const TkRunState ex = tk_run_before_lane(tk_run_scan_wave(mine, lane), lane);
             const uint32_t kl = ex.par ? k1 : k0;  // survivors of my block given what enters it
             const uint32_t kinc = tk_wave_scan_u32(kl, lane);
             total = (uint32_t)__shfl((int)kinc, 63, 64);
             // my own wavefront's place: the lane that holds summary `wid`, then the summaries of its block before it
             const int owner = (int)(wid / blk);
-            TkRunState st{(uint32_t)__shfl((int)ex.all, owner, 64), (uint32_t)__shfl((int)ex.par, owner, 64)};
+            before = tk_run_of_lane(ex, owner);
             at = (uint32_t)__shfl((int)(kinc - kl), owner, 64);
-            for (uint32_t q = (uint32_t)owner * blk; q < wid; ++q) {
-                at += sc_get(2, q) - (st.par & sc_get(3, q));
-                st = tk_run_combine(st, TkRunState{sc_get(0, q), sc_get(1, q)});
-            }
-            before = st;
+            for (uint32_t q = (uint32_t)owner * blk; q < wid; ++q) at += tk_range_enter(before, sum_get(q));
         } else {
             TkRunState st{1u, 0u};
             for (uint32_t q = 0; q < NWV; ++q) {
                 if (q == wid) before = st;
-                const uint32_t k = sc_get(2, q) - (st.par & sc_get(3, q));
+                const uint32_t k = tk_range_enter(st, sum_get(q));
                 if (q < wid) at += k;
                 total += k;
-                st = tk_run_combine(st, TkRunState{sc_get(0, q), sc_get(1, q)});
             }
         }
+        bool bad = false;  // a merge of this round creates a pair that ranks below m
         // c. the survivors move to their places
         {
+            const auto rank0 = [&](uint32_t k) { return R0[k]; };
+            const auto id0 = [&](uint32_t k) { return P0[k] & ~TK_MERGE_MARK; };
+            const auto put = [&](uint32_t o, uint32_t part, uint32_t r) { P1[o] = part, R1[o] = r; };
             TkRunState carry = before;
             for (uint32_t r0 = wlo; r0 < whi; r0 += ROW) {
-                const uint32_t i0 = r0 + (uint32_t)EPL * lane;
-                uint32_t rk[EPL], fm;
-                TkRunState v = tk_run_scan_wave(lane_state(i0, rk, fm), lane);
-                TkRunState ex{(uint32_t)__shfl_up((int)v.all, 1, 64), (uint32_t)__shfl_up((int)v.par, 1, 64)};
-                if (lane == 0) ex = TkRunState{1u, 0u};
-                uint32_t c = tk_run_combine(carry, ex).par, kl = 0, keepm = 0;
-#pragma unroll
-                for (int q = 0; q < EPL; ++q) {
-                    const uint32_t k = (uint32_t)(i0 + q < whi) & (c ^ 1u);
-                    keepm |= k << q;
-                    kl += k;
-                    c = ((fm >> q) & 1u) ? (c ^ 1u) : 0u;
-                }
-                const uint32_t inc = tk_wave_scan_u32(kl, lane);
-                uint32_t o = at + inc - kl;
-#pragma unroll
-                for (int q = 0; q < EPL; ++q) {
-                    if ((keepm >> q) & 1u) {  // kept; selected when its own pair has rank m
-                        const uint32_t i = i0 + q, f = (fm >> q) & 1u;
-                        P1[o] = f ? (m | MARK) : (P0[i] & ~MARK);
-                        R1[o] = rk[q];  // (still right when neither this part nor the next one changes)
-                        ++o;
-                        // the next pick of this round is the pair right after this one: between the two picks the pair (merged part,
-                        // its still unmerged right neighbour) exists and must not rank below m either
-                        if (f && i + 2 < cnt && R0[i + 2] == m && tk_probe_pair(T, m, P0[i + 2] & ~MARK) < m) set_viol();
-                    }
-                }
+                const uint32_t i0 = r0 + EPL * (uint32_t)lane;
+                uint32_t rk[EPL], n_in, fm;
+                const TkRunState v = tk_run_scan_wave(lane_state(i0, rk, n_in, fm), lane);
+                const TkLaneKeep kp = tk_merge_lane_rule(tk_run_combine(carry, tk_run_before_lane(v, lane)).par, fm, n_in);
+                const uint32_t inc = tk_wave_scan_u32(kp.count, lane);
+                bad |= tk_round_move_lane(m, i0, kp.mask, fm, rk, at + inc - kp.count, cnt, rank0, id0, put, probe);
                 at += (uint32_t)__shfl((int)inc, 63, 64);
-                carry = tk_run_combine(carry, TkRunState{(uint32_t)__shfl((int)v.all, 63, 64), (uint32_t)__shfl((int)v.par, 63, 64)});
+                carry = tk_run_combine(carry, tk_run_of_lane(v, 63));
             }
         }
+        if (bad) set_viol();
         sync();
         // d. ranks of the pairs that a merge has touched; the lowest rank of the next round on the way
         uint32_t mn = TK_RANK_MAX;
+        bad = false;
         for (uint32_t j = gtid; j < total; j += gthreads) {
-            const uint32_t a = P1[j], b = j + 1 < total ? P1[j + 1] : 0u;
-            uint32_t r;
-            if (j + 1 >= total) R1[j] = r = TK_RANK_MAX;
-            else if ((a | b) & MARK) {
-                r = tk_probe_pair(T, a & ~MARK, b & ~MARK);
-                R1[j] = r;
-                if (r < m) set_viol();  // a merge created a pair that the reference would have picked before the rest of this round
-            } else
-                r = R1[j];
+            const uint32_t r = tk_round_rank(m, j, total, [&](uint32_t k) { return P1[k]; }, [&](uint32_t k) { return R1[k]; },
+                                             [&](uint32_t k, uint32_t v) { R1[k] = v; }, probe, bad);
             mn = r < mn ? r : mn;
         }
+        if (bad) set_viol();
         ++round;
         m = all_min(mn, round);  // (its barrier also publishes the violation flag and this round's writes)
         if (WIDE ? tk_ld_agent(&ws->viol) : *viol_lds) {
@@ -3026,8 +2948,8 @@ __device__ __forceinline__ void tk_rounds_piece(const TkTables& T, const uint8_t
     if (redo) {
         if (gtid == 0) tk_put_result(data, mi, TK_MERGE_REDO, 0u);
     } else {
-        for (uint32_t k = gtid; k < cnt; k += gthreads) staging[s + k] = P0[k] & ~MARK;
-        if (gtid == 0) tk_put_result(data, mi, cnt, cnt == 1 ? (P0[0] & ~MARK) : s);
+        for (uint32_t k = gtid; k < cnt; k += gthreads) staging[s + k] = P0[k] & ~TK_MERGE_MARK;
+        if (gtid == 0) tk_put_result(data, mi, cnt, cnt == 1 ? (P0[0] & ~TK_MERGE_MARK) : s);
     }
     sync();
 }

@@ -47,7 +47,6 @@ enum {
 #define TK_MT_BITS 22   // most slots of the in-call miss table (tk_fused.h); sized by the chunk
 #endif
 #define TK_MT_PROBES 8
-#define TK_MAX_LEVELS 6          // 64-ary min-tree levels of the long-piece merge
 
 // ------------------------------------------------------------------------------------------
 // wave helpers (wave64; the scans and reductions: tk_scan.h)
