@@ -161,6 +161,26 @@ def test_ids_without_an_entry(core, table, sweep, entry):
     check_three(core, *sweep)
 
 
+def test_a_refused_device_decode_leaves_no_launch_for_the_next_call_to_pay(core, table):
+    """Profiling on: the event pair of tk_k_dec_len in a call that ends in KeyError goes with that call, not into the next one's count"""
+    good = dr.random_batch(table, np.random.default_rng(16), 9)
+    bad = good.copy()
+    bad[4] = next(x for x in table.holes if x < 400)
+    tok_off = np.array([0, 9], np.uint64)
+    core.set_profiling(True)
+    try:
+        core.reset_kernel_ms()
+        with pytest.raises(KeyError):
+            on_device(core, bad, tok_off)
+        core.reset_kernel_ms()
+        data, _, _ = on_device(core, good, tok_off)
+        assert data == dr.decode_ref(table, good)[0]
+        assert core.kernel_ms("tk_k_dec_len")[1] == 1
+        assert core.kernel_ms("tk_k_dec_copy")[1] == 1
+    finally:
+        core.set_profiling(False)
+
+
 def test_ids_too_sparse_for_the_device_table():
     """A special token at id 2^26: there is no device table.  decode_batch_packed says so; Encoding's batch forms fall back to the host
     loop and equal the reference."""

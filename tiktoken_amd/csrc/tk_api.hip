@@ -421,6 +421,25 @@ static int upload(Buf& b, const void* src, size_t bytes) {
     if (bytes) HIPCHK(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
     return TK_OK;
 }
+// The opening of the entries whose batch is on the device -- tk_decode_batch_device, tk_token_spans_device, tk_pack_rows_device,
+// tk_pad_batch_device, tk_assemble_samples_device (`args`: the entry's own pointers are there): run(s) under the core's mutex, on its
+// device, s the caller's stream or the core's, and the timed launches drained behind it.
+template <class Run>
+static int device_pass(tk_core* c, bool args, void* stream, Run&& run) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if (!args) return fail(TK_VALUE_ERROR, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    return drained(c, [&] { return run(stream ? (hipStream_t)stream : c->stream); });
+}
+// A buffer carved into arrays: add(bytes) gives the offset of the next one, every one at a multiple of 16 bytes (the write passes store 16
+// bytes at a time); `total` is what to ask ensure() for, once; carved<T>(buf, offset) is the array.
+struct Carve {
+    uint64_t total = 0;
+    uint64_t add(uint64_t bytes) { return std::exchange(total, total + ((bytes + 15) & ~15ull)); }
+};
+template <class T>
+static T* carved(const Buf& b, uint64_t off) { return (T*)(b.as<uint8_t>() + off); }
 
 extern "C" void tk_free(void* p);
 extern "C" const char* tk_last_error(void) { return g_err.c_str(); }
@@ -2238,93 +2257,129 @@ extern "C" int tk_decode_bytes(tk_core* c, const uint32_t* tokens, uint64_t n, u
 }
 
 // CoreBPE.decode_bytes over a packed batch (Encoding.decode_bytes_batch / decode_batch, tiktoken/core.py:331-350), on the device.
-// One range of a packed batch on the device: lengths and their block sums, the scan, then (decode_range_copy) the bytes.
+static int decode_table_check(tk_core* c) { return c->n_dec ? TK_OK : fail(TK_UNSUPPORTED, "token ids are too sparse for the device decode table"); }
+constexpr uint64_t ID_RANGE = TK_STAGE_BYTES / 4;  // ids per range of a host batch that is decoded in ranges (a multiple of TK_DEC_BLOCK)
+static uint64_t id_ranges(uint64_t n) { return (n + ID_RANGE - 1) / ID_RANGE; }
+
+struct DecodeView {  // the decode workspace of the core, valid until its next decode or spans call
+    uint32_t* lens = nullptr;                             // bytes of every token
+    unsigned long long *bsum = nullptr, *tots = nullptr;  // bytes per workgroup; the report words {bytes, first invalid position}: the batch's, then every range's
+    unsigned long long* tboff = nullptr;                  // byte offset of every token (null unless asked for)
+    uint64_t *tok_off = nullptr, *byte_off = nullptr;     // n_docs + 1 each (null unless asked for)
+};
+// ... made for n ids in n_ranges ranges; tboff, docs: with the token offsets, with the two arrays over the n_docs documents
+static int decode_view(tk_core* c, uint64_t n, uint64_t n_ranges, bool tboff, bool docs, uint64_t n_docs, DecodeView* v) {
+    const uint64_t nb = n / TK_DEC_BLOCK + 1;  // (workgroups over the positions 0 .. n: the span passes have one more position than tk_k_dec_len)
+    Carve sums, doc;
+    const uint64_t at_bsum = sums.add(nb * 8), at_tots = sums.add((n_ranges + 1) * 16);
+    const uint64_t at_tok_off = doc.add((n_docs + 1) * 8), at_byte_off = doc.add((n_docs + 1) * 8);
+    TRY(ensure(c->d_lens, (n + 1) * 4));
+    TRY(ensure(c->d_bsum, sums.total));
+    if (tboff) TRY(ensure(c->d_tboff, (n + 1) * 8));
+    if (docs) TRY(ensure(c->d_boff, doc.total));
+    *v = DecodeView{c->d_lens.as<uint32_t>(), carved<unsigned long long>(c->d_bsum, at_bsum), carved<unsigned long long>(c->d_bsum, at_tots),
+                    tboff ? c->d_tboff.as<unsigned long long>() : nullptr, docs ? carved<uint64_t>(c->d_boff, at_tok_off) : nullptr,
+                    docs ? carved<uint64_t>(c->d_boff, at_byte_off) : nullptr};
+    return TK_OK;
+}
+
+// One range of a packed batch on the device: lengths and their block sums, the scan, then (decode_range_copy) the bytes, and the tokens'
+// byte offsets if the view has them.
 //   d_tok: the batch's ids on the device; [a, a + cnt) the range (a: a multiple of TK_DEC_BLOCK); `tot`: two device words {bytes of the
 //   range, first invalid position (the caller sets it to ~0 once)}
-static int decode_range_len(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t a, uint64_t cnt, unsigned long long* tot) {
+static int decode_range_len(tk_core* c, hipStream_t s, const DecodeView& v, const uint32_t* d_tok, uint64_t a, uint64_t cnt, unsigned long long* tot) {
     const uint64_t nb = (cnt + TK_DEC_BLOCK - 1) / TK_DEC_BLOCK;
-    unsigned long long* bsum = c->d_bsum.as<unsigned long long>() + a / TK_DEC_BLOCK;
+    unsigned long long* bsum = v.bsum + a / TK_DEC_BLOCK;
     TRY(timed(c, s, "tk_k_dec_len", [&] {
-        hipLaunchKernelGGL(tk_k_dec_len, dim3((uint32_t)nb), dim3(256), 0, s, d_tok + a, cnt, c->t_dec.as<uint2>(), c->n_dec, c->d_lens.as<uint32_t>() + a, bsum, tot + 1, a);
+        hipLaunchKernelGGL(tk_k_dec_len, dim3((uint32_t)nb), dim3(256), 0, s, d_tok + a, cnt, c->t_dec.as<uint2>(), c->n_dec, v.lens + a, bsum, tot + 1, a);
     }));
     hipLaunchKernelGGL(tk_k_dec_scan64, dim3(1), dim3(1024), 0, s, bsum, nb, tot);
     return TK_OK;
 }
-static int decode_range_copy(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t a, uint64_t cnt, uint8_t* d_out, unsigned long long* d_tboff,
-                             uint64_t byte_base) {
+static int decode_range_copy(tk_core* c, hipStream_t s, const DecodeView& v, const uint32_t* d_tok, uint64_t a, uint64_t cnt, uint8_t* d_out, uint64_t byte_base) {
     const uint64_t nb = (cnt + TK_DEC_BLOCK - 1) / TK_DEC_BLOCK;
     TRY(timed(c, s, "tk_k_dec_copy", [&] {
-        hipLaunchKernelGGL(tk_k_dec_copy, dim3((uint32_t)nb), dim3(256), 0, s, d_tok + a, cnt, c->t_dec.as<uint2>(), c->d_lens.as<uint32_t>() + a,
-                           c->d_bsum.as<unsigned long long>() + a / TK_DEC_BLOCK, c->D.tok_bytes, c->D.spec_bytes, d_out, d_tboff ? d_tboff + a : nullptr,
-                           (unsigned long long)byte_base);
+        hipLaunchKernelGGL(tk_k_dec_copy, dim3((uint32_t)nb), dim3(256), 0, s, d_tok + a, cnt, c->t_dec.as<uint2>(), v.lens + a, v.bsum + a / TK_DEC_BLOCK, c->D.tok_bytes,
+                           c->D.spec_bytes, d_out, v.tboff ? v.tboff + a : nullptr, (unsigned long long)byte_base);
     }));
     return TK_OK;
+}
+// A batch of n host ids through the device in its ranges, as tk_decode_batch and tk_decode_batch_spans run a large one: the ids travel into
+// c->d_tok on c->cs_h2d, a range at a time (`staged`: through the core's staging blocks, see Feed); step(k, a, cnt) is called once the ids
+// [a, a + cnt) of range k have been sent and `s` waits for them: it queues the range's work on `s` and what goes back to the host on
+// c->cs_d2h, so the ids of range k + 1 travel in while range k is computed and the results of range k - 1 travel out.  after(): queued behind
+// the last range.  The first error ends the ranges; however they ended, the three streams are idle when this returns: nothing is on its way
+// into the caller's result buffers when they are let go.
+template <class Step, class After>
+static int ranged_ids_pass(tk_core* c, hipStream_t s, const uint32_t* ids, uint64_t n, bool staged, Step&& step, After&& after) {
+    TRY(ensure_copy_streams(c));
+    Feed feed(c, c->d_tok.p, ids, n * 4, ID_RANGE * 4, staged);
+    TRY(feed.start());
+    int rc = TK_OK;
+    for (uint64_t k = 0; k < id_ranges(n) && rc == TK_OK; ++k) {
+        const uint64_t a = k * ID_RANGE;
+        rc = feed.wait(k, s);
+        if (rc == TK_OK) rc = step(k, a, std::min(ID_RANGE, n - a));
+    }
+    hipError_t e = feed.finish();
+    if (rc == TK_OK) rc = after();
+    const hipError_t e_s = hipStreamSynchronize(s), e_out = hipStreamSynchronize(c->cs_d2h);  // (both, whatever came before)
+    if (e == hipSuccess) e = e_s != hipSuccess ? e_s : e_out;
+    if (e == hipSuccess) e = hipGetLastError();
+    if (rc == TK_OK && e != hipSuccess) rc = fail(TK_RUNTIME_ERROR, std::string("HIP error: ") + hipGetErrorString(e));
+    return rc;
 }
 
 // Device-resident decode: ids and token offsets in HBM in, bytes and byte offsets in HBM out (library-owned buffers, valid until the core's
 // next decode call).  The host learns the byte count (one 16-byte copy): the output buffer is sized by it.
 extern "C" int tk_decode_batch_device(tk_core* c, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_docs, void* stream,
                                       const uint8_t** d_bytes_out, uint64_t* n_bytes_out, const uint64_t** d_byte_off_out) {
-    if (!c) return fail(TK_VALUE_ERROR, "core is null");
-    if (!n_bytes_out || (n_tokens && !d_tokens)) return fail(TK_VALUE_ERROR, "null argument");
-    if (!c->n_dec) return fail(TK_UNSUPPORTED, "token ids are too sparse for the device decode table");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    const uint64_t n = n_tokens, nb = (n + TK_DEC_BLOCK - 1) / TK_DEC_BLOCK;
-    TRY(ensure(c->d_lens, (n + 1) * 4));
-    TRY(ensure(c->d_bsum, (nb + 8) * 8));
-    if (d_tok_off) TRY(ensure(c->d_tboff, (n + 1) * 8));
-    TRY(ensure(c->d_boff, (n_docs + 2) * 8 * 2));
-    unsigned long long* tot = c->d_bsum.as<unsigned long long>() + nb + 2;
-    unsigned long long h_tot[2] = {0, ~0ull};
-    HIPCHK(hipMemcpyAsync(tot, h_tot, 16, hipMemcpyHostToDevice, s));
-    if (n) TRY(decode_range_len(c, s, (const uint32_t*)d_tokens, 0, n, tot));
-    HIPCHK(hipMemcpyAsync(h_tot, tot, 16, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (h_tot[1] != ~0ull) return invalid_token((const uint32_t*)d_tokens, h_tot[1], true);
-    const uint64_t nbytes = h_tot[0];
-    TRY(ensure(c->d_bytes, nbytes + 16));
-    if (n) TRY(decode_range_copy(c, s, (const uint32_t*)d_tokens, 0, n, c->d_bytes.as<uint8_t>(), d_tok_off ? c->d_tboff.as<unsigned long long>() : nullptr, 0));
-    uint64_t* d_byte_off = c->d_boff.as<uint64_t>() + n_docs + 1;
-    if (d_tok_off)
-        hipLaunchKernelGGL(tk_k_dec_docoff, dim3(grid_for(n_docs + 1, 256, 4096)), dim3(256), 0, s, (const uint64_t*)d_tok_off, n_docs, n,
-                           c->d_tboff.as<unsigned long long>(), tot, d_byte_off);
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipGetLastError());
-    TRY(drain_events(c));
+    DecodeView v;
+    uint64_t nbytes = 0;
+    TRY(device_pass(c, n_bytes_out && (d_tokens || !n_tokens), stream, [&](hipStream_t s) -> int {
+        TRY(decode_table_check(c));
+        const uint32_t* d_tok = (const uint32_t*)d_tokens;
+        const uint64_t n = n_tokens;
+        TRY(decode_view(c, n, 0, d_tok_off != nullptr, true, n_docs, &v));
+        unsigned long long h_tot[2] = {0, ~0ull};
+        HIPCHK(hipMemcpyAsync(v.tots, h_tot, 16, hipMemcpyHostToDevice, s));
+        if (n) TRY(decode_range_len(c, s, v, d_tok, 0, n, v.tots));
+        HIPCHK(hipMemcpyAsync(h_tot, v.tots, 16, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (h_tot[1] != ~0ull) return invalid_token(d_tok, h_tot[1], true);
+        nbytes = h_tot[0];
+        TRY(ensure(c->d_bytes, nbytes + 16));
+        if (n) TRY(decode_range_copy(c, s, v, d_tok, 0, n, c->d_bytes.as<uint8_t>(), 0));
+        if (d_tok_off)
+            hipLaunchKernelGGL(tk_k_dec_docoff, dim3(grid_for(n_docs + 1, 256, 4096)), dim3(256), 0, s, (const uint64_t*)d_tok_off, n_docs, n, v.tboff, v.tots, v.byte_off);
+        HIPCHK(hipStreamSynchronize(s));
+        HIPCHK(hipGetLastError());
+        return TK_OK;
+    }));
     if (d_bytes_out) *d_bytes_out = c->d_bytes.as<uint8_t>();
-    if (d_byte_off_out) *d_byte_off_out = d_tok_off ? d_byte_off : nullptr;
+    if (d_byte_off_out) *d_byte_off_out = d_tok_off ? v.byte_off : nullptr;
     *n_bytes_out = nbytes;
     return TK_OK;
 }
 
-// Host buffers in, host buffers out.  The batch is decoded in ranges of 16 Mi ids: the ids of range k + 1 travel to the device (through
-// two page-locked staging buffers filled by a few host threads, or straight from the caller's buffer when that is page-locked itself:
-// the result of an encode call is) while range k is decoded and the bytes of range k - 1 travel back -- both directions of the link at
-// once.  The result buffer is page-locked and sized by the density of the ranges seen so far (grown by a copy if a later range is
-// denser).  A batch of less than two ranges takes one copy each way.
+// Host buffers in, host buffers out.  The batch is decoded in ranges of 16 Mi ids (ranged_ids_pass): the ids travel through two page-locked
+// staging buffers filled by a few host threads, or straight from the caller's buffer when that is page-locked itself (the result of an
+// encode call is); the bytes of a range travel back from one of two buffers while the next range is decoded into the other.  The result
+// buffer is page-locked and sized by the density of the ranges seen so far (grown by a copy if a later range is denser).
 extern "C" int tk_decode_batch(tk_core* c, const uint32_t* tokens, const uint64_t* tok_off, uint64_t n_docs, uint8_t** bytes_out,
                                uint64_t* n_bytes_out, uint64_t* byte_off_out) {
     if (!c) return fail(TK_VALUE_ERROR, "core is null");
     if (!tok_off || !bytes_out || !n_bytes_out) return fail(TK_VALUE_ERROR, "null argument");
     TRY(check_offsets(tok_off, n_docs, "tok_off"));
-    if (!c->n_dec) return fail(TK_UNSUPPORTED, "token ids are too sparse for the device decode table");
-    const uint64_t n = tok_off[n_docs];
+    TRY(decode_table_check(c));
+    const uint64_t n = tok_off[n_docs], n_ranges = id_ranges(n);
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    const uint64_t nb = (n + TK_DEC_BLOCK - 1) / TK_DEC_BLOCK;
-    constexpr uint64_t RANGE = TK_STAGE_BYTES / 4;  // ids per range (a multiple of TK_DEC_BLOCK)
-    const uint64_t n_ranges = n ? (n + RANGE - 1) / RANGE : 0;
+    DecodeView v;
+    TRY(decode_view(c, n, n_ranges, byte_off_out != nullptr, true, n_docs, &v));
     TRY(ensure(c->d_tok, (n + 1) * 4));
-    TRY(ensure(c->d_lens, (n + 1) * 4));
-    TRY(ensure(c->d_bsum, (nb + 8 + 2 * n_ranges) * 8));
-    if (byte_off_out) TRY(ensure(c->d_tboff, (n + 1) * 8));
-    TRY(ensure(c->d_boff, (n_docs + 2) * 8 * 2));
-    unsigned long long* tots = c->d_bsum.as<unsigned long long>() + nb + 2;  // per range {bytes, first invalid position}; [0 .. 1] also the batch's
-    unsigned long long* d_tboff = byte_off_out ? c->d_tboff.as<unsigned long long>() : nullptr;
-    TRY(ensure_copy_streams(c));
+    const uint32_t* d_tok = c->d_tok.as<uint32_t>();
     for (int i = 0; i < 2; ++i) {  // the staging buffers (this entry's own: the text of tk_encode_batch goes straight from the caller's buffer)
         if (!c->stage[i]) HIPCHK(c->stage[i].alloc(TK_STAGE_BYTES, hipHostMallocPortable));
         if (!c->ev_stage[i]) HIPCHK(c->ev_stage[i].create());
@@ -2343,40 +2398,26 @@ extern "C" int tk_decode_batch(tk_core* c, const uint32_t* tokens, const uint64_
     HostResult<uint8_t> host;
     uint64_t host_cap = 0, base = 0;
     const GrowRule grow{1.06, 4096, n_ranges > 1, "out of host memory"};
-    Feed feed(c, c->d_tok.p, tokens, n * 4, RANGE * 4, !src_pinned);
-    TRY(feed.start());
     Buf* dout[2] = {&c->d_bytes, &c->d_bytes_alt};
-    int rc = TK_OK;
-    uint64_t bad_pos = ~0ull;
-    {
-        unsigned long long init[2] = {0, ~0ull};
-        std::vector<unsigned long long> initv(2 * (n_ranges + 1));
-        for (size_t i = 0; i < initv.size(); i += 2) initv[i] = init[0], initv[i + 1] = init[1];
-        hipError_t e = hipMemcpyAsync(tots, initv.data(), initv.size() * 8, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);  // (initv leaves scope)
-        if (e != hipSuccess) rc = fail(TK_RUNTIME_ERROR, std::string("HIP error: ") + hipGetErrorString(e));
-    }
+    // every pair's position word to all ones = no id offends (the byte counts are written before they are read: tk_k_dec_scan64, doc_offsets below)
+    HIPCHK(hipMemsetAsync(v.tots, 0xFF, (n_ranges + 1) * 16, s));
     const double t_call = now_us();
-    auto step = [&](uint64_t k) -> int {
-        const uint64_t a = k * RANGE, cnt = a + RANGE < n ? RANGE : n - a;
-        const double t_0 = now_us();
-        TRY(feed.wait(k, s));
+    double t_0 = t_call;  // when the wait for a range's ids began: the end of the step before
+    unsigned long long h_total = 0;
+    auto step = [&](uint64_t k, uint64_t a, uint64_t cnt) -> int {
         const double t_1 = now_us();
-        unsigned long long* tot = tots + 2 * (k + 1);
-        TRY(decode_range_len(c, s, c->d_tok.as<uint32_t>(), a, cnt, tot));
+        unsigned long long* tot = v.tots + 2 * (k + 1);
+        TRY(decode_range_len(c, s, v, d_tok, a, cnt, tot));
         unsigned long long h_tot[2] = {0, ~0ull};
         HIPCHK(hipMemcpyAsync(h_tot, tot, 16, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
-        if (h_tot[1] != ~0ull) {
-            bad_pos = h_tot[1];
-            return TK_KEY_ERROR;
-        }
+        if (h_tot[1] != ~0ull) return invalid_token(tokens, h_tot[1], false);
         const uint64_t nbk = h_tot[0];
         const double t_2 = now_us();
         Buf& d = *dout[k & 1];
         if (k >= 2) HIPCHK(hipEventSynchronize(ev_out[k & 1]));  // the buffer's previous bytes have left
         TRY(ensure(d, nbk + 16));
-        TRY(decode_range_copy(c, s, c->d_tok.as<uint32_t>(), a, cnt, d.as<uint8_t>(), d_tboff, base));
+        TRY(decode_range_copy(c, s, v, d_tok, a, cnt, d.as<uint8_t>(), base));
         HIPCHK(hipEventRecord(ev_copy, s));
         // the result buffer: sized by the density so far
         const uint64_t need = base + nbk, done = a + cnt;
@@ -2389,30 +2430,23 @@ extern "C" int tk_decode_batch(tk_core* c, const uint32_t* tokens, const uint64_
         if (nbk) HIPCHK(hipMemcpyAsync(host + base, d.p, nbk, hipMemcpyDeviceToHost, c->cs_d2h));
         HIPCHK(hipEventRecord(ev_out[k & 1], c->cs_d2h));
         base = need;
+        t_0 = now_us();
         return TK_OK;
     };
-    for (uint64_t k = 0; k < n_ranges && rc == TK_OK; ++k) rc = step(k);
-    hipError_t e = feed.finish();
-    if (rc == TK_OK && byte_off_out) {
-        uint64_t* d_tok_off = c->d_boff.as<uint64_t>();
-        uint64_t* d_byte_off = d_tok_off + n_docs + 1;
-        unsigned long long h_total = base;
-        if (e == hipSuccess) e = hipMemcpyAsync(tots, &h_total, 8, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_tok_off, tok_off, (n_docs + 1) * 8, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(tk_k_dec_docoff, dim3(grid_for(n_docs + 1, 256, 4096)), dim3(256), 0, s, d_tok_off, n_docs, n, d_tboff, tots, d_byte_off);
-            e = hipMemcpyAsync(byte_off_out, d_byte_off, (n_docs + 1) * 8, hipMemcpyDeviceToHost, s);
-        }
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->cs_d2h);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (c->dbg & TK_DBG_VERBOSE) fprintf(stderr, "decode: %llu ranges, ids %s, %.0f us\n", (unsigned long long)n_ranges, src_pinned ? "page-locked" : "staged", now_us() - t_call);
-    if (rc == TK_KEY_ERROR && bad_pos != ~0ull) rc = invalid_token(tokens, bad_pos, false);
-    if (rc == TK_OK && e != hipSuccess) rc = fail(TK_RUNTIME_ERROR, std::string("HIP error: ") + hipGetErrorString(e));
-    if (rc == TK_OK) rc = drain_events(c);  // (before the outputs are published: a caller that gets an error owns nothing)
-    else (void)drain_events(c);
-    TRY(rc);
+    auto doc_offsets = [&]() -> int {
+        if (!byte_off_out) return TK_OK;
+        h_total = base;
+        HIPCHK(hipMemcpyAsync(v.tots, &h_total, 8, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(v.tok_off, tok_off, (n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(tk_k_dec_docoff, dim3(grid_for(n_docs + 1, 256, 4096)), dim3(256), 0, s, v.tok_off, n_docs, n, v.tboff, v.tots, v.byte_off);
+        HIPCHK(hipMemcpyAsync(byte_off_out, v.byte_off, (n_docs + 1) * 8, hipMemcpyDeviceToHost, s));
+        return TK_OK;
+    };
+    TRY(drained(c, [&] {  // (before the outputs are published: a caller that gets an error owns nothing)
+        const int rc = ranged_ids_pass(c, s, tokens, n, !src_pinned, step, doc_offsets);
+        if (c->dbg & TK_DBG_VERBOSE) fprintf(stderr, "decode: %llu ranges, ids %s, %.0f us\n", (unsigned long long)n_ranges, src_pinned ? "page-locked" : "staged", now_us() - t_call);
+        return rc;
+    }));
     *bytes_out = host ? host.release() : (uint8_t*)malloc(1);
     *n_bytes_out = base;
     return TK_OK;
@@ -2426,15 +2460,15 @@ struct SpanView {  // device buffers of the core, valid until its next decode or
     uint64_t *byte_off = nullptr, *char_off = nullptr;
     uint64_t n_bytes = 0, n_chars = 0;
     uint64_t bad_doc = ~0ull;  // the first document that is not well-formed UTF-8 (when asked for)
+    DecodeView dec;            // the lengths and the workgroups' byte bases, where tk_k_dec_copy reads them
 };
 // The span passes in their parts; the caller holds c->mu.  spans_begin: the buffers of a batch of n tokens in n_docs documents, the report
 // words, the document starts over the tokens.  spans_range: the three passes over the tokens [a, a + cnt) (a: a multiple of TK_DEC_BLOCK;
 // ranges in order, the last one ends at n).  spans_end: the per-document pass, then the host waits and looks at the report words.
 static int spans_begin(tk_core* c, hipStream_t s, uint64_t n, const uint64_t* d_tok_off, uint64_t n_docs, SpanView* out, unsigned long long** words_out) {
-    if (!c->n_dec) return fail(TK_UNSUPPORTED, "token ids are too sparse for the device decode table");
+    TRY(decode_table_check(c));
     const uint64_t nb = n / TK_DEC_BLOCK + 1;  // (workgroups over the positions 0 .. n)
-    TRY(ensure(c->d_lens, (n + 1) * 4));
-    TRY(ensure(c->d_bsum, (nb + 8) * 8));
+    TRY(decode_view(c, n, 0, false, false, 0, &out->dec));
     TRY(ensure(c->d_span, (n + 1) * 8));
     TRY(ensure(c->d_span_blk, nb * 8 * 4));
     TRY(ensure(c->d_span_marks, (n / 32 + 4) * 4));
@@ -2457,9 +2491,9 @@ static int spans_range(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_
                        const SpanView* v, unsigned long long* words) {
     const uint32_t end = a + cnt == n ? 1u : 0u;
     const uint64_t nb_all = n / TK_DEC_BLOCK + 1, b0 = a / TK_DEC_BLOCK, nb = (cnt + end + TK_DEC_BLOCK - 1) / TK_DEC_BLOCK;
-    unsigned long long* bsum = c->d_bsum.as<unsigned long long>() + b0;  // (where tk_k_dec_copy reads the workgroups' bases)
+    unsigned long long* bsum = v->dec.bsum + b0;
     unsigned long long *csum = c->d_span_blk.as<unsigned long long>() + b0, *mkey = csum + nb_all, *doc_b = mkey + nb_all, *doc_c = doc_b + nb_all;
-    uint32_t* lens = c->d_lens.as<uint32_t>() + a;
+    uint32_t* lens = v->dec.lens + a;
     const uint8_t* marks = c->d_span_marks.as<uint8_t>() + a / 8;
     const uint32_t* cw = c->t_cw.as<uint32_t>();
     if (nb)
@@ -2521,7 +2555,7 @@ static int spans_run(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t 
     TRY(spans_end(c, s, d_tok, d_tok_off, n_docs, d_doc_off, out, words));
     if (want_bytes || validate) {
         TRY(ensure(c->d_bytes, out->n_bytes + 16));
-        if (n) TRY(decode_range_copy(c, s, d_tok, 0, n, c->d_bytes.as<uint8_t>(), nullptr, 0));
+        if (n) TRY(decode_range_copy(c, s, out->dec, d_tok, 0, n, c->d_bytes.as<uint8_t>(), 0));
         if (validate) TRY(spans_validate(c, s, n_docs, out, words));
         HIPCHK(hipStreamSynchronize(s));
         HIPCHK(hipGetLastError());
@@ -2532,13 +2566,9 @@ static int spans_run(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t 
 extern "C" int tk_token_spans_device(tk_core* c, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_docs, const void* d_doc_off, void* stream,
                                      const uint32_t** d_byte_start_out, const uint32_t** d_char_start_out, const uint64_t** d_byte_off_out,
                                      const uint64_t** d_char_off_out) {
-    if (!c) return fail(TK_VALUE_ERROR, "core is null");
-    if (!d_tok_off || (n_tokens && !d_tokens)) return fail(TK_VALUE_ERROR, "null argument");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->device));
     SpanView v;
-    TRY(drained(c, [&] {
-        return spans_run(c, stream ? (hipStream_t)stream : c->stream, (const uint32_t*)d_tokens, n_tokens, (const uint64_t*)d_tok_off, n_docs, (const uint64_t*)d_doc_off, false, false, &v);
+    TRY(device_pass(c, d_tok_off && (d_tokens || !n_tokens), stream, [&](hipStream_t s) {
+        return spans_run(c, s, (const uint32_t*)d_tokens, n_tokens, (const uint64_t*)d_tok_off, n_docs, (const uint64_t*)d_doc_off, false, false, &v);
     }));
     if (d_byte_start_out) *d_byte_start_out = v.byte_start;
     if (d_char_start_out) *d_char_start_out = v.char_start;
@@ -2547,18 +2577,14 @@ extern "C" int tk_token_spans_device(tk_core* c, const void* d_tokens, uint64_t 
     return TK_OK;
 }
 
-// Host buffers in and out.  A batch of less than two ranges of 16 Mi ids takes one copy each way.  A larger one runs in those ranges, as
-// tk_decode_batch does: the ids of range k + 1 travel to the device (straight from the caller's buffer, sent by a thread of their own)
-// while range k is scanned and the spans of range k - 1 travel back -- both directions of the link at once; the scan's carry (sums and
-// last document start) stays on the device between the ranges.  Then the bytes, range by range: the copy kernel of range k + 1 runs while
-// the bytes of range k travel (by then the byte count is known: the result buffer has its size at once), and the UTF-8 check behind them.
-static int decode_spans_ranges(tk_core* c, hipStream_t s, const uint32_t* tokens, uint64_t n, uint64_t n_docs, bool want_bytes, bool validate, SpanView* v,
-                               HostResult<uint32_t>& bs, HostResult<uint32_t>& cs, HostResult<uint8_t>& host) {
-    constexpr uint64_t RANGE = TK_STAGE_BYTES / 4;  // ids per range (a multiple of TK_DEC_BLOCK)
-    const uint64_t n_ranges = (n + RANGE - 1) / RANGE;
-    const uint64_t* d_tok_off = c->d_boff.as<uint64_t>();
-    uint32_t* d_tok = c->d_tok.as<uint32_t>();
-    TRY(ensure_copy_streams(c));
+// Host buffers in and out.  A batch of less than two ranges of 16 Mi ids takes one copy each way.  A larger one runs in those ranges
+// (ranged_ids_pass; the ids straight from the caller's buffer): the spans of a range travel back while the next one is scanned; the scan's
+// carry (sums and last document start) stays on the device between the ranges.  Then the bytes, range by range: the copy kernel of range k + 1
+// runs while the bytes of range k travel (by then the byte count is known: the result buffer has its size at once), and the UTF-8 check behind them.
+static int decode_spans_ranges(tk_core* c, hipStream_t s, const uint32_t* tokens, uint64_t n, const uint64_t* d_tok_off, uint64_t n_docs, bool want_bytes, bool validate,
+                               SpanView* v, HostResult<uint32_t>& bs, HostResult<uint32_t>& cs, HostResult<uint8_t>& host) {
+    const uint64_t n_ranges = id_ranges(n);
+    const uint32_t* d_tok = c->d_tok.as<uint32_t>();
     std::vector<Event> ev_out(n_ranges), ev_bytes(want_bytes ? n_ranges : 0);  // the spans of a range are there; so are its bytes
     for (auto& e : ev_out) HIPCHK(e.create());
     for (auto& e : ev_bytes) HIPCHK(e.create());
@@ -2569,11 +2595,7 @@ static int decode_spans_ranges(tk_core* c, hipStream_t s, const uint32_t* tokens
     if (!bs || !cs) return fail(TK_RUNTIME_ERROR, "out of page-locked host memory");
     unsigned long long* words = nullptr;
     TRY(spans_begin(c, s, n, d_tok_off, n_docs, v, &words));
-    Feed feed(c, d_tok, tokens, n * 4, RANGE * 4);
-    TRY(feed.start());
-    auto step = [&](uint64_t k) -> int {
-        const uint64_t a = k * RANGE, cnt = a + RANGE < n ? RANGE : n - a;
-        TRY(feed.wait(k, s));
+    auto step = [&](uint64_t k, uint64_t a, uint64_t cnt) -> int {
         TRY(spans_range(c, s, d_tok, n, a, cnt, d_tok_off, n_docs, v, words));
         HIPCHK(hipMemcpyAsync(cum + k + 1, words + TK_SPAN_BYTES, 8, hipMemcpyDeviceToHost, s));
         HIPCHK(hipEventRecord(ev_out[k], s));
@@ -2582,11 +2604,9 @@ static int decode_spans_ranges(tk_core* c, hipStream_t s, const uint32_t* tokens
         HIPCHK(hipMemcpyAsync(cs + a, v->char_start + a, cnt * 4, hipMemcpyDeviceToHost, c->cs_d2h));
         return TK_OK;
     };
-    int rc = TK_OK;
-    for (uint64_t k = 0; k < n_ranges && rc == TK_OK; ++k) rc = step(k);
-    hipError_t e = feed.finish();
-    if (rc == TK_OK) rc = spans_end(c, s, d_tok, d_tok_off, n_docs, nullptr, v, words);
-    if (rc == TK_OK && (want_bytes || validate)) rc = [&]() -> int {
+    auto bytes_by_range = [&]() -> int {
+        TRY(spans_end(c, s, d_tok, d_tok_off, n_docs, nullptr, v, words));
+        if (!want_bytes && !validate) return TK_OK;
         cum[0] = 0;
         TRY(ensure(c->d_bytes, v->n_bytes + 16));
         if (want_bytes) {
@@ -2594,8 +2614,8 @@ static int decode_spans_ranges(tk_core* c, hipStream_t s, const uint32_t* tokens
             if (!host) return fail(TK_RUNTIME_ERROR, "out of page-locked host memory");
         }
         for (uint64_t k = 0; k < n_ranges; ++k) {
-            const uint64_t a = k * RANGE, cnt = a + RANGE < n ? RANGE : n - a;
-            TRY(decode_range_copy(c, s, d_tok, a, cnt, c->d_bytes.as<uint8_t>(), nullptr, 0));  // (the bases are the batch's: every range writes at its place)
+            const uint64_t a = k * ID_RANGE;
+            TRY(decode_range_copy(c, s, v->dec, d_tok, a, std::min(ID_RANGE, n - a), c->d_bytes.as<uint8_t>(), 0));  // (the bases are the batch's: every range writes at its place)
             if (!want_bytes) continue;
             HIPCHK(hipEventRecord(ev_bytes[k], s));
             HIPCHK(hipStreamWaitEvent(c->cs_d2h, ev_bytes[k], 0));
@@ -2603,13 +2623,8 @@ static int decode_spans_ranges(tk_core* c, hipStream_t s, const uint32_t* tokens
         }
         if (validate) TRY(spans_validate(c, s, n_docs, v, words));
         return TK_OK;
-    }();
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    const hipError_t e2 = hipStreamSynchronize(c->cs_d2h);  // (nothing is on its way into the result buffers when they are let go)
-    if (e == hipSuccess) e = e2;
-    if (e == hipSuccess) e = hipGetLastError();
-    if (rc == TK_OK && e != hipSuccess) rc = fail(TK_RUNTIME_ERROR, std::string("HIP error: ") + hipGetErrorString(e));
-    return rc;
+    };
+    return ranged_ids_pass(c, s, tokens, n, /* staged */ false, step, bytes_by_range);
 }
 
 extern "C" int tk_decode_batch_spans(tk_core* c, const uint32_t* tokens, const uint64_t* tok_off, uint64_t n_docs, int validate, uint8_t** bytes_out,
@@ -2618,23 +2633,24 @@ extern "C" int tk_decode_batch_spans(tk_core* c, const uint32_t* tokens, const u
     if (!c) return fail(TK_VALUE_ERROR, "core is null");
     if (!tok_off || !byte_start_out || !char_start_out || (validate && !invalid_doc_out)) return fail(TK_VALUE_ERROR, "null argument");
     TRY(check_offsets(tok_off, n_docs, "tok_off"));
-    if (!c->n_dec) return fail(TK_UNSUPPORTED, "token ids are too sparse for the device decode table");
+    TRY(decode_table_check(c));
     const uint64_t n = tok_off[n_docs];
     if (n && !tokens) return fail(TK_VALUE_ERROR, "null argument");
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    TRY(ensure(c->d_tok, (n + 1) * 4));
-    TRY(ensure(c->d_boff, (n_docs + 2) * 8 * 2));
-    HIPCHK(hipMemcpyAsync(c->d_boff.p, tok_off, (n_docs + 1) * 8, hipMemcpyHostToDevice, s));
     SpanView v;
+    TRY(ensure(c->d_tok, (n + 1) * 4));
+    TRY(decode_view(c, n, 0, false, true, n_docs, &v.dec));
+    uint64_t* const d_tok_off = v.dec.tok_off;  // (spans_begin makes the view again, without the documents' arrays)
+    HIPCHK(hipMemcpyAsync(d_tok_off, tok_off, (n_docs + 1) * 8, hipMemcpyHostToDevice, s));
     HostResult<uint32_t> bs, cs;
     HostResult<uint8_t> host;
-    if (n >= 2 * (TK_STAGE_BYTES / 4)) {
-        TRY(drained(c, [&] { return decode_spans_ranges(c, s, tokens, n, n_docs, bytes_out != nullptr, validate != 0, &v, bs, cs, host); }));
+    if (n >= 2 * ID_RANGE) {
+        TRY(drained(c, [&] { return decode_spans_ranges(c, s, tokens, n, d_tok_off, n_docs, bytes_out != nullptr, validate != 0, &v, bs, cs, host); }));
     } else {
         if (n) HIPCHK(hipMemcpyAsync(c->d_tok.p, tokens, n * 4, hipMemcpyHostToDevice, s));
-        TRY(drained(c, [&] { return spans_run(c, s, c->d_tok.as<uint32_t>(), n, c->d_boff.as<uint64_t>(), n_docs, nullptr, bytes_out != nullptr, validate != 0, &v); }));
+        TRY(drained(c, [&] { return spans_run(c, s, c->d_tok.as<uint32_t>(), n, d_tok_off, n_docs, nullptr, bytes_out != nullptr, validate != 0, &v); }));
         TRY(result_from_device(bs, v.byte_start, n));
         TRY(result_from_device(cs, v.char_start, n));
         if (bytes_out) TRY(result_from_device(host, c->d_bytes.p, v.n_bytes));
@@ -2660,15 +2676,13 @@ extern "C" int tk_encode_batch_spans(tk_core* c, const uint8_t* utf8, const uint
         [] { return TK_OK; },
         [&](uint64_t n) { return spans_run(c, c->stream, c->out_tokens.as<uint32_t>(), n, c->out_tok_off.as<uint64_t>(), n_docs, c->doc_off.as<uint64_t>(), false, false, &v); },
         [&](uint64_t n) -> int {
-            HostResult<uint32_t> bs, cs, tok;
-            TRY(result_from_device(tok, c->out_tokens.p, n));
-            TRY(result_from_device(bs, v.byte_start, n));
-            TRY(result_from_device(cs, v.char_start, n));
+            ResultBag bag;
+            TRY(bag.fetch(tokens_out, c->out_tokens.p, n));
+            TRY(bag.fetch(byte_start_out, v.byte_start, n));
+            TRY(bag.fetch(char_start_out, v.char_start, n));
             if (tok_off_out) HIPCHK(hipMemcpy(tok_off_out, c->out_tok_off.p, (n_docs + 1) * 8, hipMemcpyDeviceToHost));
-            *tokens_out = tok.release();
+            bag.give();
             *n_tokens_out = n;
-            *byte_start_out = bs.release();
-            *char_start_out = cs.release();
             return TK_OK;
         });
 }
@@ -2718,24 +2732,6 @@ static int report_read(const unsigned long long* words, unsigned long long* got,
     HIPCHK(hipMemcpy(got, words, n * 8, hipMemcpyDeviceToHost));
     return offsets_refusal(got[TK_BAD_OFF], "tok_off", "document", "n_tokens");
 }
-// The opening of tk_pack_rows_device, tk_pad_batch_device and tk_assemble_samples_device (`args`: the entry's own pointers are there):
-// run(s) under the core's mutex, on its device, s the caller's stream or the core's, and the timed launches drained behind it.
-template <class Run>
-static int device_pass(tk_core* c, bool args, void* stream, Run&& run) {
-    if (!c) return fail(TK_VALUE_ERROR, "core is null");
-    if (!args) return fail(TK_VALUE_ERROR, "null argument");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    return drained(c, [&] { return run(stream ? (hipStream_t)stream : c->stream); });
-}
-// A buffer carved into arrays: add(bytes) gives the offset of the next one, every one at a multiple of 16 bytes (the write passes store 16
-// bytes at a time); `total` is what to ask ensure() for, once; carved<T>(buf, offset) is the array.
-struct Carve {
-    uint64_t total = 0;
-    uint64_t add(uint64_t bytes) { return std::exchange(total, total + ((bytes + 15) & ~15ull)); }
-};
-template <class T>
-static T* carved(const Buf& b, uint64_t off) { return (T*)(b.as<uint8_t>() + off); }
 // What of a tk_rows_spec can be refused without looking at the batch (the host-text entry asks before it encodes anything).
 static int rows_check_spec(tk_core* c, const tk_rows_spec* spec) {
     if (!spec) return fail(TK_VALUE_ERROR, "null argument");
@@ -3154,8 +3150,22 @@ struct TrainRun {
     Buf blob;                // the distinct words' bytes
     Buf cells;
     Buf sym[2], wid[2], pos[2], dec, pair, blk_mark, blk_cnt, merges, counts;
+    uint64_t pair_slots = 0;
     TkTrainTab tab() const { return TkTrainTab{key.as<unsigned long long>(), weight.as<unsigned long long>(), first.as<unsigned long long>(), slots - 1}; }
+    TkTrainStep step(uint32_t k) const {  // merge k: it reads the symbol arrays of set k & 1
+        return TkTrainStep{.sym = {sym[0].as<uint32_t>(), sym[1].as<uint32_t>()},
+                           .wid = {wid[0].as<uint32_t>(), wid[1].as<uint32_t>()},
+                           .pos = {pos[0].as<unsigned long long>(), pos[1].as<unsigned long long>()},
+                           .weight = weight.as<unsigned long long>(), .pair = pair.as<TkTrainPair>(), .pair_mask = pair_slots - 1, .dec = dec.as<uint8_t>(),
+                           .blk_mark = blk_mark.as<uint32_t>(), .blk_cnt = blk_cnt.as<unsigned long long>(), .cells = cells.as<unsigned long long>(),
+                           .merges = merges.as<uint32_t>(), .counts = counts.as<unsigned long long>(), .step = k, .par = k & 1u};
+    }
 };
+// the slots of a hash table: the power of two times `floor` that is at least x
+static uint64_t pow2_at_least(uint64_t floor, uint64_t x) {
+    while (floor < x) floor <<= 1;
+    return floor;
+}
 
 static int train_tab_alloc(tk_core* c, hipStream_t s, TrainRun& r, uint64_t slots) {
     TRY(ensure(r.key, slots * 8));
@@ -3167,8 +3177,7 @@ static int train_tab_alloc(tk_core* c, hipStream_t s, TrainRun& r, uint64_t slot
 
 // room for `words` distinct words at a load of at most one half: the slot count follows from the number of pieces, known before they go in
 static int train_tab_reserve(tk_core* c, hipStream_t s, TrainRun& r, uint64_t words) {
-    uint64_t want = 1024;
-    while (want < 2 * words) want <<= 1;
+    const uint64_t want = pow2_at_least(1024, 2 * words);
     if (want <= r.slots) return TK_OK;
     if (want > (1ull << 32)) return fail(TK_VALUE_ERROR, "tk_train_bpe: more than 2^31 pieces");
     if (!r.slots) return train_tab_alloc(c, s, r, want);
@@ -3196,34 +3205,12 @@ static int train_blob_reserve(hipStream_t s, TrainRun& r, uint64_t used, uint64_
     return TK_OK;
 }
 
-extern "C" int tk_train_bpe(tk_core* c, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, uint32_t vocab_size, uint32_t** pairs_out,
-                            uint64_t** counts_out, uint64_t* n_out) {
-    if (!c) return fail(TK_VALUE_ERROR, "core is null");
-    if (!doc_off || !pairs_out || !counts_out || !n_out) return fail(TK_VALUE_ERROR, "null argument");
-    if (vocab_size < 256) return fail(TK_VALUE_ERROR, "vocab_size must be at least 256, so that every byte is a token");
-    if (vocab_size > (1u << 30)) return fail(TK_VALUE_ERROR, "vocab_size must be at most 2^30");
-    TRY(check_offsets(doc_off, n_docs, "doc_off"));
-    const uint64_t steps = vocab_size - 256u;
-    HostResult<uint32_t> pairs(malloc(steps * 8 + 8));
-    HostResult<uint64_t> counts(malloc(steps * 8 + 8));
-    if (!pairs || !counts) return fail(TK_RUNTIME_ERROR, "out of host memory");
-    if (!steps) {
-        *pairs_out = pairs.release();
-        *counts_out = counts.release();
-        *n_out = 0;
-        return TK_OK;
-    }
-    if (!utf8 && doc_off[n_docs]) return fail(TK_VALUE_ERROR, "null argument");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    TrainRun r;
+// The word table, chunk by chunk: document ranges [d0, d1) of at most `limit` bytes; offsets stay global (doc_off[d0] + place in the chunk).
+// `cells`: the host's copy of the run's cells, as they stand behind the last chunk (cells[TKT_BLOB]: the bytes of the distinct words).
+static int train_words(tk_core* c, hipStream_t s, TrainRun& r, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, unsigned long long (&cells)[TKT_CELLS]) {
     TRY(ensure(r.cells, TKT_CELLS * 8));
-    unsigned long long cells[TKT_CELLS] = {};
     HIPCHK(hipMemsetAsync(r.cells.p, 0, TKT_CELLS * 8, s));
     unsigned long long* d_cells = r.cells.as<unsigned long long>();
-
-    // The word table, chunk by chunk: document ranges [d0, d1) of at most `limit` bytes; offsets stay global (doc_off[d0] + place in the chunk).
     const uint64_t limit = std::min<uint64_t>(c->chunk_bytes, (1ull << 31) - 4096);  // (bit 31 of a piece start marks a gap char)
     std::vector<uint64_t> local;
     for (uint64_t d0 = 0; d0 < n_docs;) {
@@ -3264,21 +3251,23 @@ extern "C" int tk_train_bpe(tk_core* c, const uint8_t* utf8, const uint64_t* doc
         }
         d0 = d1;
     }
-    TRY(drain_events(c));
-    const uint64_t N = cells[TKT_BLOB];  // symbols of the first step: a byte of a distinct word each
-    if (N < 2) return fail(TK_VALUE_ERROR, "tk_train_bpe: no pair left to merge after 0 of " + std::to_string(steps) + " merges: the text has no piece of two bytes");
+    return TK_OK;
+}
 
+// The `steps` merges over the N symbols of the distinct words (a byte each at first), and their pairs and counts into the caller's arrays.
+static int train_steps(tk_core* c, hipStream_t s, TrainRun& r, unsigned long long (&cells)[TKT_CELLS], uint64_t steps, uint32_t* pairs, uint64_t* counts) {
+    const uint64_t N = cells[TKT_BLOB];
+    if (N < 2) return fail(TK_VALUE_ERROR, "tk_train_bpe: no pair left to merge after 0 of " + std::to_string(steps) + " merges: the text has no piece of two bytes");
     // The symbol arrays (two sets: a step writes its survivors into the other one), the pair table, the per-workgroup words.
     const uint64_t nb = (N + TKT_BLOCK - 1) / TKT_BLOCK;
-    uint64_t pair_slots = 1024;
-    while (pair_slots < 2 * N) pair_slots <<= 1;
+    r.pair_slots = pow2_at_least(1024, 2 * N);
     for (int p = 0; p < 2; ++p) {
         TRY(ensure(r.sym[p], N * 4));
         TRY(ensure(r.wid[p], N * 4));
         TRY(ensure(r.pos[p], N * 8));
     }
     TRY(ensure(r.dec, N));
-    TRY(ensure(r.pair, pair_slots * sizeof(TkTrainPair)));
+    TRY(ensure(r.pair, r.pair_slots * sizeof(TkTrainPair)));
     TRY(ensure(r.blk_mark, nb * 4));
     TRY(ensure(r.blk_cnt, nb * 8));
     TRY(ensure(r.merges, steps * 8));
@@ -3293,30 +3282,14 @@ extern "C" int tk_train_bpe(tk_core* c, const uint8_t* utf8, const uint64_t* doc
     cells[TKT_BEST] = ~0ull;
     cells[TKT_WIN] = 0;
     cells[TKT_DONE] = 0;
-    HIPCHK(hipMemcpyAsync(d_cells, cells, sizeof(cells), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(r.cells.p, cells, sizeof(cells), hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s));  // (`cells` is pageable memory and is written again below)
 
-    TkTrainStep st{};
-    for (int p = 0; p < 2; ++p) {
-        st.sym[p] = r.sym[p].as<uint32_t>();
-        st.wid[p] = r.wid[p].as<uint32_t>();
-        st.pos[p] = r.pos[p].as<unsigned long long>();
-    }
-    st.weight = r.weight.as<unsigned long long>();
-    st.pair = r.pair.as<TkTrainPair>();
-    st.pair_mask = pair_slots - 1;
-    st.dec = r.dec.as<uint8_t>();
-    st.blk_mark = r.blk_mark.as<uint32_t>();
-    st.blk_cnt = r.blk_cnt.as<unsigned long long>();
-    st.cells = d_cells;
-    st.merges = r.merges.as<uint32_t>();
-    st.counts = r.counts.as<unsigned long long>();
     const dim3 grid((uint32_t)nb), one(1);
     // The merge loop: no host wait inside -- the live count, the winner and the "no pair left" flag stay in the cells.
     for (uint64_t k = 0; k < steps; ++k) {
-        st.step = (uint32_t)k;
-        st.par = (uint32_t)(k & 1u);
-        TRY(timed(c, s, "tk_train_pair_clear", [&] { (void)hipMemsetAsync(r.pair.p, 0, pair_slots * sizeof(TkTrainPair), s); }));
+        const TkTrainStep st = r.step((uint32_t)k);
+        TRY(timed(c, s, "tk_train_pair_clear", [&] { (void)hipMemsetAsync(r.pair.p, 0, r.pair_slots * sizeof(TkTrainPair), s); }));
         TRY(timed(c, s, "tk_k_train_count", [&] { hipLaunchKernelGGL(tk_k_train_count, grid, dim3(TKT_BLOCK), 0, s, st); }));
         TRY(timed(c, s, "tk_k_train_best", [&] { hipLaunchKernelGGL(tk_k_train_best, grid, dim3(TKT_BLOCK), 0, s, st); }));
         TRY(timed(c, s, "tk_k_train_pick", [&] { hipLaunchKernelGGL(tk_k_train_pick, grid, dim3(TKT_BLOCK), 0, s, st); }));
@@ -3326,14 +3299,36 @@ extern "C" int tk_train_bpe(tk_core* c, const uint8_t* utf8, const uint64_t* doc
         TRY(timed(c, s, "tk_k_train_offsets", [&] { hipLaunchKernelGGL(tk_k_train_offsets, one, dim3(1024), 0, s, st); }));
         TRY(timed(c, s, "tk_k_train_rewrite", [&] { hipLaunchKernelGGL(tk_k_train_rewrite, grid, dim3(TKT_BLOCK), 0, s, st); }));
     }
-    HIPCHK(hipMemcpyAsync(cells, d_cells, sizeof(cells), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(cells, r.cells.p, sizeof(cells), hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(pairs, r.merges.p, steps * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(counts, r.counts.p, steps * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    TRY(drain_events(c));
     if (cells[TKT_DONE])
         return fail(TK_VALUE_ERROR, "tk_train_bpe: no pair left to merge after " + std::to_string(cells[TKT_DONE] - 1) + " of " + std::to_string(steps) +
                                         " merges: vocab_size is too large for this text");
+    return TK_OK;
+}
+
+extern "C" int tk_train_bpe(tk_core* c, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, uint32_t vocab_size, uint32_t** pairs_out,
+                            uint64_t** counts_out, uint64_t* n_out) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if (!doc_off || !pairs_out || !counts_out || !n_out) return fail(TK_VALUE_ERROR, "null argument");
+    if (vocab_size < 256) return fail(TK_VALUE_ERROR, "vocab_size must be at least 256, so that every byte is a token");
+    if (vocab_size > (1u << 30)) return fail(TK_VALUE_ERROR, "vocab_size must be at most 2^30");
+    TRY(check_offsets(doc_off, n_docs, "doc_off"));
+    const uint64_t steps = vocab_size - 256u;
+    HostResult<uint32_t> pairs(malloc(steps * 8 + 8));
+    HostResult<uint64_t> counts(malloc(steps * 8 + 8));
+    if (!pairs || !counts) return fail(TK_RUNTIME_ERROR, "out of host memory");
+    if (steps) {
+        if (!utf8 && doc_off[n_docs]) return fail(TK_VALUE_ERROR, "null argument");
+        std::lock_guard<std::mutex> lk(c->mu);
+        HIPCHK(hipSetDevice(c->device));
+        TrainRun r;
+        unsigned long long cells[TKT_CELLS] = {};
+        TRY(drained(c, [&] { return train_words(c, c->stream, r, utf8, doc_off, n_docs, cells); }));
+        TRY(drained(c, [&] { return train_steps(c, c->stream, r, cells, steps, pairs, counts); }));
+    }
     *pairs_out = pairs.release();
     *counts_out = counts.release();
     *n_out = steps;
