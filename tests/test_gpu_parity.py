@@ -354,6 +354,45 @@ def test_one_hundred_bytes_through_the_device_entry(cores):
             assert core.stat("chunks") == 1 and core.stat("small_calls") == small
 
 
+@pytest.mark.parametrize("name", ["gpt2_shaped", "o200k_shaped"])
+def test_back_end_edges_tokens_and_offsets(cores, name):
+    """What the back end's rules turn on (tk_back_rule.h; tests/test_back_sim.py has them on the CPU), tokens AND token offsets against the
+    oracle: more than sixty-four documents starting in one tile, empty documents behind a single tile, documents starting at a tile's last
+    and the next tile's first byte, and one piece of more tokens than its count byte holds (500 random letters: more than 255 tokens)."""
+    import torch
+
+    core, C = cores[name], h.c_oracle_for(name)
+    rng = np.random.default_rng(0xBAC)
+    letters = lambda k: bytes(rng.integers(97, 123, size=k).astype(np.uint8))
+    words = lambda k: b" ".join(letters(int(rng.integers(1, 9))) for _ in range(k))
+    filler = (words(1500) + b"x" * 3840)[:3839]
+    batches = {
+        "200 one-byte documents": [letters(1) for _ in range(200)],
+        "a tile and five empty documents": [words(400)[:2000]] + [b""] * 5,
+        "documents at bytes 3839 and 3840": [filler, b"y", b" z" + words(40)],
+        "a piece of more than 255 tokens": [letters(500)],
+    }
+    for what, docs in batches.items():
+        blob, off = h.pack(docs)
+        rt, ro = C.encode_batch(blob, off, None, 1)
+        if what.startswith("documents at"):
+            assert off[1] == 3839 and off[2] == 3840
+        if what.startswith("a piece"):
+            assert len(rt) > 255
+        toks, toff = core.encode_batch_packed(blob, off)
+        assert np.array_equal(toff, ro), (what, toff[:8], ro[:8])
+        assert np.array_equal(toks, rt), what
+        # ... and through the device entry, which has no small-call path: whatever encode_batch_packed does with a lone short document
+        # (today tk_k_small gives up on a piece that long and the chunk pipeline takes over), this run is the back end's
+        host = np.zeros(len(blob) + 64, np.uint8)
+        host[:len(blob)] = blob
+        d_text, d_off = torch.from_numpy(host).cuda(), torch.from_numpy(off.view(np.int64)).cuda()
+        small = core.stat("small_calls")
+        dt, nt, do = core.encode_batch_device(d_text.data_ptr(), len(blob), d_off.data_ptr(), off, len(docs))
+        assert np.array_equal(h.dev_u32(dt, nt), rt) and np.array_equal(h.dev_u64(do, len(docs) + 1), ro), what
+        assert core.stat("chunks") == 1 and core.stat("small_calls") == small, what
+
+
 def test_size_independent_properties_at_scale(cores):
     """At a size the oracle would need minutes for: decode(encode(x)) == x per document (sampled), token
     offsets are non-decreasing and end at the token count, and re-encoding a document alone gives the same

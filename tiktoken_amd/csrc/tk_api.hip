@@ -129,7 +129,7 @@ struct KernelStat {
 
 // Work buffers of ONE chunk in flight.  This list is the one place that names them: it declares the members and adds them up (WorkSet::bytes).
 #define TK_WORK_BUFS(X)                                                                                                                                  \
-    X(text_al) X(tile_sum) X(wide_ws) X(scan_sums) X(row_base) X(brk) X(docb) X(cand) X(ss) X(si) X(starts) X(blockcnt) X(pstart) X(res) X(staging)     \
+    X(text_al) X(tile_sum) X(wide_ws) X(scan_sums) X(doc_first) X(brk) X(docb) X(cand) X(ss) X(si) X(starts) X(blockcnt) X(pstart) X(res) X(staging)     \
     X(listB) X(listC) X(counters) X(total) X(g_id) X(g_rk) X(g_nx) X(g_pv) X(g_lv) X(tile_np) X(tile_nt) X(mt_keys) X(mtab) X(movf) X(mcnt) X(wbin)       \
     X(deferred) X(big) X(rx_spec) X(rx_gst) X(rx_lnk) X(rx_exit) X(merge_work) X(find)
 // (Members go in reverse order: the buffers, declared last, are freed first -- hipFree waits for the device -- then the events, the
@@ -175,7 +175,7 @@ struct ChunkAsk {  // (call sites name the fields they set, in this order)
     const uint64_t* d_doc_off = nullptr;  // uint64 offsets of the chunk's documents (n_docs + 1 entries, absolute: `base` is subtracted)
     uint64_t n = 0, n_docs = 0, base = 0;
     uint32_t* d_out = nullptr;            // the batch's token buffer (null: piece starts only)
-    uint64_t* d_tok_off = nullptr;        // the documents' token offsets (null: not wanted)
+    uint64_t* d_tok_off = nullptr;        // the documents' token offsets (null: not wanted; the single-piece kinds are refused with one)
     bool use_special = false;
     bool single_piece() const { return kind == ChunkKind::SinglePiece || kind == ChunkKind::SinglePieceNoLookup; }
     bool piece_starts() const { return kind == ChunkKind::PieceStarts; }
@@ -197,6 +197,7 @@ struct ChunkJob {
     FrontArgs front;
     uint64_t ntiles = 0;
     bool find = false;  // the chunk's text was searched for disallowed special tokens (tk_k_spec_find -> w.find)
+    bool docs_in_place = false;  // tk_k_place writes the documents' token offsets (w.doc_first is filled); else, if they are wanted, the chunk is empty: tk_k_docoff
     uint32_t index = 0;  // position of the chunk in its batch
     uint32_t mt_bits = 14;
     TkMissKey* mt = nullptr;   // the in-call miss table's keys (null: no table -- every missed piece gets an overflow entry)
@@ -680,9 +681,6 @@ extern "C" void tk_destroy(tk_core* c) {
     delete c;  // (its members free what they own)
 }
 
-// entries of the piece-id space of an n-byte chunk: TKF_CAP per tile (a tile's pieces form a run at tile * TKF_CAP)
-static uint64_t tk_pid_cap(uint64_t n) { return (n / TK_TILE + 1) * TKF_CAP + 64; }
-
 static uint32_t grid_for(uint64_t items, uint32_t per_block, uint32_t cap) {
     uint64_t g = (items + per_block - 1) / per_block;
     if (g < 1) g = 1;
@@ -872,10 +870,11 @@ static int stage_front(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, con
     const uint64_t nwords = (n + 31) / 32;
     const uint64_t nblk = (nwords + 255) / 256;
     const uint64_t ntiles = (n && !single_piece) ? (n + TK_TILE - 1) / TK_TILE : 1;  // (single piece: one run of one piece)
+    if (single_piece && ask.d_tok_off) return fail(TK_RUNTIME_ERROR, "internal error: token offsets asked of a single piece");
     job = ChunkJob();
     job.ask = ask;
     job.ntiles = ntiles;
-    TRY(ensure(w.starts, (nwords + 2) * 4));
+    job.docs_in_place = n > 0 && !single_piece && ask.d_tok_off != nullptr;
     TRY(ensure(w.blockcnt, (nblk + 2) * 4));
     TRY(ensure(w.tile_np, (ntiles + 2) * 4));
     TRY(ensure(w.tile_nt, (ntiles + 2) * 4));
@@ -908,10 +907,13 @@ static int stage_front(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, con
     TRY(ensure(w.big, (1 + 3 * TK_BIGCOPY_CAP) * 4));
     TkClearArgs clr;
     clr.n = 0;
-    auto clear = [&](Buf& b, uint64_t bytes, uint32_t v) -> int {  // room for `bytes` (nothing to do where more was asked for above), all of them filled
+    // room for `bytes` (nothing to do where more was asked for above), those from `from` on filled -- from the 16-byte unit that holds
+    // `from`: up to three words before it are filled too, so whoever writes those must run behind tk_k_chunk_clear on this stream
+    auto clear = [&](Buf& b, uint64_t bytes, uint32_t v, uint64_t from = 0) -> int {
+        if (clr.n >= TK_CLEAR_MAX) return fail(TK_RUNTIME_ERROR, "internal error: more buffers to clear than tk_k_chunk_clear takes");
         TRY(ensure(b, bytes));
-        clr.p[clr.n] = b.as<uint4>();
-        clr.n16[clr.n] = (bytes + 15) / 16;  // (every Buf has at least 256 bytes of slack behind what was asked for)
+        clr.p[clr.n] = b.as<uint4>() + from / 16;
+        clr.n16[clr.n] = (bytes + 15) / 16 - from / 16;  // (every Buf has at least 256 bytes of slack behind what was asked for)
         clr.v[clr.n] = v;
         ++clr.n;
         return TK_OK;
@@ -921,12 +923,13 @@ static int stage_front(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, con
     TRY(clear(w.big, 4, 0u));
     TRY(clear(w.merge_work, 16 * TKM_WORK_STRIDE * 4, 0u));
     TRY(clear(w.total, 32, 0u));
+    // (tk_k_place reads all 120 words of the last tile's piece starts; the front kernel, launched below behind the clears, writes those
+    // below nwords, the others stay zero)
+    TRY(clear(w.starts, tk_starts_words(nwords, ntiles) * 4, 0u, nwords * 4));
     uint32_t* find_docb = nullptr;  // the document starts for the disallowed scan: `docb`, or the same bitmap made for the scan alone
-    // (round 6) the first document that starts in every tile (tk_k_mark_docs), for tk_k_place, which writes the documents' token offsets as it
-    // passes their pieces; one piece without pre-tokenisation and empty chunks keep tk_k_docoff
-    const bool docs_in_place = n > 0 && !single_piece && ask.d_tok_off != nullptr;
-    TRY(ensure(w.row_base, (ntiles + 4) * 4));
-    if (docs_in_place) TRY(clear(w.row_base, (ntiles + 2) * 4, 0xFFFFFFFFu));
+    // the first document that starts in every tile (tk_k_mark_docs), for tk_k_place, which writes the documents' token offsets as it passes
+    // their pieces (an empty chunk has no pieces: tk_k_docoff)
+    if (job.docs_in_place) TRY(clear(w.doc_first, (ntiles + 2) * 4, 0xFFFFFFFFu));
     TRY(clear(w.tile_sum, ntiles + 16, 0xFFFFFFFFu));
     FrontArgs& f = job.front;
     if (job.ovf_base) {
@@ -962,7 +965,7 @@ static int stage_front(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, con
         clr.n = 0;
         TRY(timed(c, s, "tk_k_mark_docs", [&] {
             hipLaunchKernelGGL(tk_k_mark_docs, dim3(grid_for(n_docs, 256, 4096)), dim3(256), 0, s, ask.d_doc_off, n_docs, base, n, f.brk, f.docb ? f.docb : find_docb,
-                               docs_in_place ? w.row_base.as<uint32_t>() : (uint32_t*)nullptr, ntiles);
+                               job.docs_in_place ? w.doc_first.as<uint32_t>() : (uint32_t*)nullptr, ntiles);
         }));
         if (ask.use_special) {
             const uint8_t* allowed = c->allowed.as<uint8_t>();
@@ -1060,7 +1063,7 @@ static int stage_back(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, hipE
             // every bin in one launch (tk_k_merge_all); TK_DBG_MERGE_PER_BIN: the kernel-per-bin form below
             uint64_t most_units = 0;
             for (int b = 0; b < TK_NBIN; ++b)
-                if (n >= tk_bin_lo(b)) most_units += std::min<uint64_t>(n / tk_bin_lo(b), n_entries) / (64u >> (b == 0 ? 0 : (b <= 2 ? 1 : (b <= 4 ? 2 : b - 2)))) + 1;
+                if (n >= tk_bin_lo(b)) most_units += std::min<uint64_t>(n / tk_bin_lo(b), n_entries) / (64u >> tkm_lg_of_bin(b)) + 1;
             uint32_t wgs = (uint32_t)std::min<uint64_t>((most_units + TKM_WAVES - 1) / TKM_WAVES, (uint64_t)c->n_cu * TKM_WGS_PER_CU);
             wgs = std::max(16u / TKM_WAVES, (wgs + 16u / TKM_WAVES - 1u) / (16u / TKM_WAVES) * (16u / TKM_WAVES));  // (wavefronts: a multiple of 16, tk_k_merge_all's work counters rely on it)
             TRY(timed(c, s, "tk_k_merge_all", [&] {
@@ -1169,8 +1172,7 @@ static int stage_back(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, hipE
     if (encode) {
         TRY(timed(c, s, "tk_k_place", [&] {
             // (one instance for every size: three rows per step for inputs of a few tiles measured slower -- C1 0.082 ms against 0.060 --, profiles/r05_place_experiments.txt)
-            const bool docs_in_place = !ask.single_piece() && ask.d_tok_off != nullptr;
-            const TkPlaceDocs docs{ask.d_doc_off, ask.base, n, ask.n_docs, w.row_base.as<uint32_t>(), w.starts.as<uint32_t>(), w.total.as<uint64_t>(), docs_in_place ? ask.d_tok_off : (uint64_t*)nullptr};
+            const TkPlaceDocs docs{ask.d_doc_off, ask.base, n, ask.n_docs, w.doc_first.as<uint32_t>(), w.starts.as<uint32_t>(), w.total.as<uint64_t>(), job.docs_in_place ? ask.d_tok_off : (uint64_t*)nullptr};
             // (six workgroups per CU: 80 registers, 26 688 B of LDS; a grid of four times what is resident -- 0.84 ms with 4096 workgroups, 0.81 with 1536 or 3072,
             // 0.80 with 6144 or 12 288, round 6)
             hipLaunchKernelGGL(tk_k_place<TKP_ROWS_PLACE>, dim3(grid_for(ntiles, 4, 6144)), dim3(256), 0, s, ntiles, tile_np, tile_nt, res, data, stg, d_out, tok_base, w.big.as<uint32_t>(), docs);
@@ -1178,12 +1180,9 @@ static int stage_back(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, hipE
     }
     if (encode && n > TK_BIGCOPY)  // (a token run of TK_BIGCOPY tokens needs at least as many bytes)
         hipLaunchKernelGGL(tk_k_bigcopy, dim3(1024), dim3(256), 0, s, w.big.as<uint32_t>(), stg, d_out, tok_base);
-    // (the document offsets need the tile counts only, but beside tk_k_place on a second stream the two take as long as one after the
-    // other: both are bound by the rate of random accesses -- measured in round 4)
-    if (!front_only && ask.d_tok_off && (n == 0 || ask.single_piece())) {  // (else tk_k_place has written them)
+    if (!front_only && n == 0 && ask.d_tok_off) {  // (else tk_k_place has written them)
         TRY(timed(c, s, "tk_k_docoff", [&] {
-            hipLaunchKernelGGL(tk_k_docoff, dim3(grid_for(ask.n_docs + 1, 16, 4096)), dim3(256), 0, s, ask.n_docs, ask.d_doc_off, ask.base, n, w.starts.as<uint32_t>(), tile_nt, res, data,
-                               (n > 0 && !ask.single_piece()) ? w.row_base.as<uint32_t>() : (const uint32_t*)nullptr, w.total.as<uint64_t>(), tok_base, ask.d_tok_off);
+            hipLaunchKernelGGL(tk_k_docoff, dim3(grid_for(ask.n_docs + 1, 256, 4096)), dim3(256), 0, s, ask.n_docs, w.total.as<uint64_t>(), tok_base, ask.d_tok_off);
         }));
     }
     HIPCHK(hipMemcpyAsync(w.h_total, w.total.p, 16, hipMemcpyDeviceToHost, s));

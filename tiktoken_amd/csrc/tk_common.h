@@ -28,6 +28,7 @@
 #endif
 
 #define TK_RANK_MAX 0xFFFFFFFFu
+#define TK_TILE 3840  // text bytes per tile: with 128 bytes of left context and 128 of look-ahead the LDS window is 4096 = 256 lanes x 16
 
 // The debug word: $TIKTOKEN_AMD_DEBUG, an int read at tk_create (tests and experiments only; wrong tokens where a bit says so), and the flags the host
 // adds to it for the front kernel's launches.  Every expression on it stays in `int`.  (Hooks that only time a part of a kernel are compile-time

@@ -16,7 +16,7 @@
 //   tk_k_count_tiles      token count per tile (a missed piece's count from its entry)
 //   tk_k_scan_*           exclusive scan of the tile counts
 //   tk_k_place            per tile: tokens to their final place (a missed piece's tokens from its entry), whole lines through LDS
-//   tk_k_docoff          per document: token offset of the piece that starts it
+//   tk_k_docoff          an empty chunk's document offsets (tk_k_place writes the others)
 //   tk_k_small            one document of up to 2 KiB (or one segment of a mid-size document) by one workgroup, start to finish
 //
 // Tile rule (checked on the CPU by tests/test_device_logic_sim.py): a tile derives exactly the piece starts
@@ -35,14 +35,13 @@
 #pragma once
 #include <type_traits>
 
+#include "tk_back_rule.h"
 #include "tk_chunk.h"
 #include "tk_kernels.h"
 #include "tk_merge_rule.h"
 
-#define TKF_NONE 0xFFFFFFFFu
 #define TK_MERGE_REDO 0xFFFFFFFFu  // TkMissData::res_cnt after tk_k_merge_rounds: the piece has to go through tk_k_merge_long
-#define TK_BIGCOPY 4096      // token runs from this length on are copied by tk_k_bigcopy
-#define TK_BIGCOPY_CAP 1024  // entries of its list
+#define TK_BIGCOPY_CAP 1024  // entries of tk_k_bigcopy's list
 #define TKF_CHAIN_END 0xFFFFFFFFFFFFFFFFull
 #define TKF_CONT_CAP 768       // continuation list of the scanners: deferred-tile variant (own array)
 #define TKF_CONT_CAP_FAST 768  // ... one-workgroup-per-tile variant (the list lives in the byte table's LDS, dead after phase B)
@@ -66,19 +65,7 @@
 #define TKF_MODE_GIVEN 2
 #define TKF_BATCH 896  // pieces per part of a tile in the front kernel's phase F (the class lists hold 1024 entries)
 #define TKF_BL 14      // ... = the 28 bitmap words = 896 positions of this many lanes of phase E, when a tile has more pieces than that
-#define TKF_CAP 4096  // piece ids per tile: pid = tile * TKF_CAP + k (a 4096-byte tile starts at most 4096 pieces)
-// The tail of a tile's run of result words holds, from the back: the number of its pieces that are not tokens (TKF_TAIL_NMISS), the number
-// of its gap chars (TKF_TAIL_NGAP), then the entries of the pieces that are not tokens once more, in no particular order -- what the counting
-// pass of the back end needs, 0.12 GB per GiB instead of all the result words (0.65 GB).  It always fits: a piece that is not a token has at
-// least two bytes, so pieces + missed pieces <= the tile's 3840 bytes.
-#define TKF_TAIL_NMISS (TKF_CAP - 1)
-#define TKF_TAIL_NGAP (TKF_CAP - 2)
-#define TKF_TAIL_REFS (TKF_CAP - 3)  // the q-th missed piece's entry: res[run + TKF_TAIL_REFS - q]
-
-// Per-piece result word res[piece id]: a token id (the piece is a vocabulary token, src/lib.rs:367), or a reference to where its
-// tokens will be once the merge kernels have run.
-#define TK_RES_FLAG 0x80000000u  // not a single token: TK_RES_FLAG | i = entry i of the chunk's miss data (TkMissData: its result is there)
-#define TK_RES_GAP 0x7FFFFFFFu   // no token at all: a char at which a pat_str of the generic engine matches nothing (find_iter skips it, src/lib.rs:365)
+// (a tile's run of result words and the classes of a result word: tk_back_rule.h)
 // Pieces that are not vocabulary tokens ("missed" pieces: they have to be merged, src/lib.rs:369).  A batch repeats them -- 30 M per GiB of
 // web text, 1.2 M distinct -- so each DISTINCT one is merged once: the front kernel claims a slot of an open-addressed table keyed by the
 // piece's bytes (TkMissKey; exact: equal hashes are verified byte for byte), every occurrence refers to the slot, the merge kernels leave
@@ -99,11 +86,7 @@ struct TkMissKey {
 // Where a distinct missed piece and its result live: a table slot has a 64-byte line of its own -- {start, len, count, tokens}: a piece of up
 // to TKD_INLINE tokens (97.5 % of the missed pieces of the web-text corpus) has them IN the entry, so an occurrence costs ONE random
 // access; an overflow entry is 16 bytes (sized for the worst case, n / 2 of them), its tokens are in the staging area.
-// res_cnt: the token count; with TKD_INLINE_BIT the tokens are tok[0 .. count); without it tok[0] (res_tok) is the token (count 1) or
-// the staging position of the tokens.  TK_MERGE_REDO: see above.
-#define TKD_INLINE 13
-#define TKD_INLINE_BIT 0x40000000u
-#define TKD_COUNT(w) ((w) & 0x3FFFFFFFu)
+// res_cnt: the count word of tk_back_rule.h (TKD_*).  TK_MERGE_REDO: see above.
 struct TkMissTab {  // 64 bytes
     uint32_t start, len, res_cnt, tok[TKD_INLINE];
 };
@@ -2280,7 +2263,7 @@ __global__ __launch_bounds__(256) void tk_k_merge_group(TkTables T, const uint8_
 // ------------------------------------------------------------------------------------------
 #define TKM_NOKEY 0xFFFFFFFFu
 __device__ __forceinline__ uint32_t tkm_key(uint32_t rank, uint32_t pos) { return rank == TK_RANK_MAX ? TKM_NOKEY : ((rank << 10) | pos); }
-__device__ __forceinline__ int tkm_lg_of_bin(int b) {  // log2 of the lanes per piece: 16 positions per lane
+TK_HD int tkm_lg_of_bin(int b) {  // log2 of the lanes per piece: 16 positions per lane
     return b == 0 ? 0 : (b <= 2 ? 1 : (b <= 4 ? 2 : b - 2));  // bins <= 16, 24, 32, 48, 64, 128, 256, 512, 1024 bytes
 }
 // minimum over the aligned group of 1 << lg lanes, in every lane of it: DPP steps inside a row of 16 lanes (a few cycles each; a
@@ -2984,7 +2967,7 @@ __global__ __launch_bounds__(TKB_THREADS) void tk_k_merge_rounds_wide(TkTables T
 }
 
 // ------------------------------------------------------------------------------------------
-// back end: tk_k_count_tiles -> exclusive scan of the tile counts -> tk_k_place (and, beside it, tk_k_docoff)
+// back end: tk_k_count_tiles -> exclusive scan of the tile counts -> tk_k_place (an empty chunk: tk_k_docoff alone).  Layout and rules: tk_back_rule.h
 //
 // The tokens of tile t go behind those of all the tiles before it, and a tile's token count is known only when the results of its
 // missed pieces are (a missed piece is two or more tokens).  Both passes read the per-piece result words -- four pieces per lane and
@@ -3040,28 +3023,28 @@ __global__ __launch_bounds__(256) void tk_k_count_tiles(uint64_t ntiles, const u
             for (int j = 0; j < ROWS * 2; ++j) {
                 const uint32_t q = q0 + (uint32_t)j * 32u + hl;
                 ref[j] = res[rb + TKF_TAIL_REFS - (q < nm ? q : 0u)];
-                if (q >= nm) ref[j] = 0xFFFFFFFFu;  // (also what the front kernel leaves for a piece it had no entry for: one token)
+                if (q >= nm) ref[j] = TKF_NONE;
             }
             bool escape = false;
 #pragma unroll
             for (int j = 0; j < ROWS * 2; ++j) {
-                const bool in_tab = ref[j] < data.ovf_base;
-                cb[j] = data.cnt8[in_tab ? ref[j] : 0u];
-                if (ref[j] != 0xFFFFFFFFu && (!in_tab || cb[j] == 255u)) escape = true;
+                const bool in_tab = TK_REF_IN_TAB(ref[j], data.ovf_base);
+                cb[j] = data.cnt8[TK_REF_CNT8_AT(ref[j], in_tab)];
+                if (TK_REF_ESCAPES(ref[j], in_tab, cb[j])) escape = true;
                 else if (in_tab) extra += cb[j] - 1u;
             }
             if (__ballot(escape)) {  // (an overflow entry, a piece of 255 tokens and more: the entry itself)
 #pragma unroll
                 for (int j = 0; j < ROWS * 2; ++j) {
-                    const bool in_tab = ref[j] < data.ovf_base, esc = ref[j] != 0xFFFFFFFFu && (!in_tab || cb[j] == 255u);
-                    const uint32_t cw = data.head(esc ? ref[j] : data.ovf_base)[2];
+                    const bool in_tab = TK_REF_IN_TAB(ref[j], data.ovf_base), esc = TK_REF_ESCAPES(ref[j], in_tab, cb[j]);
+                    const uint32_t cw = data.head(TK_REF_HEAD_AT(ref[j], esc, data.ovf_base))[2];
                     if (esc) extra += TKD_COUNT(cw) - 1u;
                 }
             }
         }
         extra = tk_row16_sum(extra);                                   // the sixteen lanes of a DPP row
         extra += (uint32_t)__shfl_xor((int)extra, 16, 64);             // ... and the other row of the half
-        if (have && hl == 0) tile_nt[t] = np - ng + extra;
+        if (have && hl == 0) tile_nt[t] = TK_TILE_TOKENS(np, ng, extra);
     }
     // (one atomic per WORKGROUP: same-address atomics are served one after the other at ~10 M/s on this part -- one per wavefront of a
     // 4096-workgroup grid was 0.2 ms, the floor of this kernel however small the chunk)
@@ -3087,9 +3070,6 @@ __global__ __launch_bounds__(256) void tk_k_count_tiles(uint64_t ntiles, const u
 //    partial write of sixteen lines -- 136 M write requests per GiB where the tokens need 16 M (TCP_TCC_WRITE_REQ, profiles/r04_sq_counters.csv).
 // 1.21 -> 0.78 ms per GiB.  Neither half alone moved it (the list without the staging: 1.14 ms; round 4's kernel with every store sent to one
 // 4 KiB window: 1.06), nor did more rows in flight or a staging per step, which loads every head twice (0.97): profiles/r05_place_experiments.txt.
-#ifndef TKP_STAGE
-#define TKP_STAGE 1024
-#endif
 struct TkPlaceDocs {
     const uint64_t* doc_off;    // [n_docs + 1] offsets of the chunk's documents (absolute: chunk_base is subtracted)
     uint64_t chunk_base, n, n_docs;
@@ -3103,7 +3083,7 @@ __global__ __launch_bounds__(256, 6) void tk_k_place(uint64_t ntiles, const uint
                                                   const uint32_t* __restrict__ res, TkMiss data, const uint32_t* __restrict__ staging, uint32_t* __restrict__ out_all,
                                                   const unsigned long long* __restrict__ tok_base, uint32_t* __restrict__ big,
                                                   // (round 6) the document offsets, written here as a tile's pieces are placed: tok_off[d] = tokens before the piece
-                                                  // that starts document d.  tk_k_docoff found that piece again per document -- five dependent loads, the result
+                                                  // that starts document d.  A kernel of its own found that piece again per document -- five dependent loads, the result
                                                   // words of up to 255 pieces before it read once more: 0.15 ms and 0.36 GB per GiB.  docs.tok_off == nullptr: not asked for.
                                                   TkPlaceDocs docs) {
     constexpr uint32_t CAP = 256u * ROWS, SCAP = (uint32_t)TKP_STAGE;
@@ -3155,10 +3135,10 @@ __global__ __launch_bounds__(256, 6) void tk_k_place(uint64_t ntiles, const uint
             const uint64_t d = (uint64_t)dfirst + 64u * c + (uint32_t)lane;
             const uint64_t pos = d < docs.n_docs ? docs.doc_off[d] - docs.chunk_base : ~0ull;
             const bool in = pos >= tile_lo && pos < tile_hi;
-            const uint32_t it = in ? (uint32_t)(pos - tile_lo) : 0u, w = it >> 5;
-            const uint32_t a0 = (uint32_t)__shfl((int)sb0, (int)(w >> 1), 64), a1 = (uint32_t)__shfl((int)sb1, (int)(w >> 1), 64);
-            const uint32_t px = (uint32_t)__shfl((int)spx, (int)(w >> 1), 64);
-            const uint32_t kp = px + ((w & 1u) ? (uint32_t)__popc(a0) + (uint32_t)__popc(a1 & ((1u << (it & 31u)) - 1u)) : (uint32_t)__popc(a0 & ((1u << (it & 31u)) - 1u)));
+            const uint32_t it = in ? (uint32_t)(pos - tile_lo) : 0u, g = TK_START_GROUP(it);
+            const uint32_t a0 = (uint32_t)__shfl((int)sb0, (int)g, 64), a1 = (uint32_t)__shfl((int)sb1, (int)g, 64);
+            const uint32_t px = (uint32_t)__shfl((int)spx, (int)g, 64);
+            const uint32_t kp = TK_PIECE_INDEX(it, a0, a1, px);
             return in ? kp : 0xFFFFFFFFu;
         };
         const uint32_t kp0 = has_docs ? doc_piece(0u) : 0xFFFFFFFFu;
@@ -3189,7 +3169,7 @@ __global__ __launch_bounds__(256, 6) void tk_k_place(uint64_t ntiles, const uint
                     fm[r] = 0;
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
-                        if ((tk[r][j] & TK_RES_FLAG) || tk[r][j] == TK_RES_GAP) fm[r] |= 1u << j;
+                        if (TK_RES_LISTED(tk[r][j])) fm[r] |= 1u << j;
                     const uint32_t nf = (uint32_t)__popc(fm[r]);
                     const uint32_t inc = tk_wave_scan_u32(nf, lane);
                     lbase[r] = nlist + inc - nf;
@@ -3211,8 +3191,8 @@ __global__ __launch_bounds__(256, 6) void tk_k_place(uint64_t ntiles, const uint
                     const bool have = d < nlist;
                     const uint32_t w = have ? refl[d] : TK_RES_GAP;
                     const uint32_t pidx = have ? (uint32_t)idxl[d] : 0u;
-                    const bool flagged = (w & TK_RES_FLAG) != 0u;
-                    const uint32_t e = w & ~TK_RES_FLAG;
+                    const bool flagged = TK_RES_FLAGGED(w);
+                    const uint32_t e = TK_RES_ENTRY(w);
                     const bool in_tab = flagged && e < data.ovf_base;
                     // (no `if` around the loads: the head and the entry's next sixteen bytes are in flight together; a lane without an entry
                     // reads the first overflow entry)
@@ -3224,12 +3204,12 @@ __global__ __launch_bounds__(256, 6) void tk_k_place(uint64_t ntiles, const uint
                     const uint32_t cum = carry + incx;
                     if (have) cuml[d] = cum;
                     carry += (uint32_t)__shfl((int)incx, 63, 64);
-                    const uint32_t off = run + pidx + (cum - extra);
+                    const uint32_t off = TK_PIECE_PLACE(run, pidx, cum, extra);
                     bool stg = false;  // its tokens are in the staging area
                     if (flagged) {
-                        if (cnt == 1u) {  // (a long piece that is a token after all, tk_k_bincount; entries written that way)
+                        if (TK_FROM_HEAD(cnt)) {  // (a long piece that is a token after all, tk_k_bincount; entries written that way)
                             W(off, hd.y);
-                        } else if (hd.x & TKD_INLINE_BIT) {
+                        } else if (TK_FROM_ENTRY(hd.x)) {
                             W(off, hd.y);
                             W(off + 1u, a.x);
                             if (cnt > 2u) W(off + 2u, a.y);
@@ -3251,7 +3231,7 @@ __global__ __launch_bounds__(256, 6) void tk_k_place(uint64_t ntiles, const uint
                                     if (cnt > 12u) W(off + 12u, c4.w);
                                 }
                             }
-                        } else if (cnt > 1u) {
+                        } else if (TK_FROM_STAGING(cnt)) {
                             stg = true;
                         }
                     }
@@ -3260,7 +3240,7 @@ __global__ __launch_bounds__(256, 6) void tk_k_place(uint64_t ntiles, const uint
                     for (uint64_t m = __ballot(stg); m; m &= m - 1ull) {
                         const int l = __ffsll((unsigned long long)m) - 1;
                         const uint32_t src = (uint32_t)__shfl((int)hd.y, l, 64), cc = (uint32_t)__shfl((int)cnt, l, 64), dst = (uint32_t)__shfl((int)off, l, 64);
-                        if (ST || cc < TK_BIGCOPY) {  // (a tile that goes through LDS holds no piece that long)
+                        if (TK_COPIED_IN_PLACE(ST, cc)) {  // (a tile that goes through LDS holds no piece that long)
                             for (uint32_t i = (uint32_t)lane; i < cc; i += 64u) W(dst + i, staging[src + i]);
                         } else if (lane == 0) {
                             const uint32_t bat = atomicAdd(&big[0], 1u);
@@ -3293,7 +3273,7 @@ __global__ __launch_bounds__(256, 6) void tk_k_place(uint64_t ntiles, const uint
                         }
                         const uint32_t nl = lb + (uint32_t)__popc(fmv & ((1u << (j & 3u)) - 1u));
                         const uint32_t ex = (mine && nl) ? cuml[nl - 1u] : 0u;
-                        if (mine) docs.tok_off[(uint64_t)dfirst + 64u * c + (uint32_t)lane] = tok_base_global + (uint64_t)(uint32_t)(run0 + run + j + ex);  // (32-bit sum first: `ex` is negative behind gap chars)
+                        if (mine) docs.tok_off[(uint64_t)dfirst + 64u * c + (uint32_t)lane] = TK_DOC_TOK_OFF(tok_base_global, run0, run, j, ex);
                     };
                     emit(kp0, 0u);
                     if (more_docs)
@@ -3370,74 +3350,11 @@ __global__ __launch_bounds__(256) void tk_k_bigcopy(const uint32_t* __restrict__
     }
 }
 
-// tok_off[d] = tokens before the piece at which document d starts.  SIXTEEN LANES per document (round 4; a wavefront per document before:
-// the kernel waits for a chain of five dependent loads per document, so four documents per wavefront are four times the documents in flight).
-// The piece is found in the piece-start bitmap of the document's tile (a document start is a hard piece start); its token offset is the tile's
-// place (tile_tb) plus what tk_k_count_tiles has left for the row of 256 pieces it lies in plus the counts of the row's pieces before it --
-// single tokens count one, the others what their count byte says.  (Needs nothing of tk_k_place.)
-__global__ __launch_bounds__(256) void tk_k_docoff(uint64_t n_docs, const uint64_t* __restrict__ doc_off, uint64_t chunk_base, uint64_t n,
-                                                    const uint32_t* __restrict__ starts, const uint32_t* __restrict__ tile_tb,
-                                                    const uint32_t* __restrict__ res, TkMiss data, const uint32_t* __restrict__ row_rel /* tk_k_place's row_abs */,
-                                                    const uint64_t* __restrict__ total, const unsigned long long* __restrict__ tok_base, uint64_t* __restrict__ tok_off) {
-    const uint64_t tok_base_global = tok_base[0];  // tokens of the chunks before this one
-    const uint32_t sl = threadIdx.x & 15u;
-    const uint64_t grp = (blockIdx.x * 256ull + threadIdx.x) >> 4, ngrp = ((uint64_t)gridDim.x * 256) >> 4;
-    const uint64_t rounds = (n_docs + 1 + ngrp - 1) / ngrp;  // (every group runs the same number of rounds: the row sums are wave-wide instructions)
-    for (uint64_t r = 0; r < rounds; ++r) {
-        const uint64_t d = grp + r * ngrp;
-        const bool have = d <= n_docs;
-        const uint64_t pos = (have && d < n_docs) ? doc_off[d] - chunk_base : n;
-        const bool inside = pos < n;  // (else: empty documents at the end of the chunk, and the closing offset -> the chunk's total)
-        const uint32_t t = (inside && row_rel) ? (uint32_t)(pos / TK_TILE) : 0u, in_tile = inside ? (uint32_t)(pos - (uint64_t)t * TK_TILE) : 0u;  // (no rows: one piece)
-        // pieces of the tile that start before pos: eight words of the tile's 120 per lane
-        uint32_t kp = 0;
-        if (row_rel) {
-            const uint32_t* sw = starts + (uint64_t)t * (TK_TILE / 32) + sl * 8u;
-            const bool any = sl * 256u < in_tile;
-            const uint4 a = *(const uint4*)(any ? sw : starts), b = *(const uint4*)(any && sl * 256u + 128u < in_tile ? sw + 4 : starts);
-            const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const uint32_t lo = sl * 256u + (uint32_t)j * 32u;
-                if (lo < in_tile) kp += (uint32_t)__popc(in_tile - lo >= 32u ? w[j] : (w[j] & ((1u << (in_tile - lo)) - 1u)));
-            }
-            kp = tk_row16_sum(kp);
-        }
-        const uint32_t rb = t * TKF_CAP;
-        uint64_t row_run = tile_tb[t];
-        uint32_t kstart = 0;
-        if (row_rel && kp >= 256u) {  // (the row's place in the chunk, left by tk_k_place: the document's first piece is piece kp of the tile, so the row exists)
-            row_run = row_rel[(uint64_t)t * (TKF_CAP / 256) + (kp >> 8)];
-            kstart = kp & ~255u;
-        }
-        // the row's pieces before the document's: at most 255, sixteen per lane, all loads without an `if` of their own
-        uint32_t sum = 0;
-        {
-            const uint32_t k0 = kstart + sl * 16u;
-            const uint32_t* rp = res + rb + (k0 < kp ? k0 : kstart);
-            const uint4 q0 = ((const uint4*)rp)[0], q1 = ((const uint4*)rp)[1], q2 = ((const uint4*)rp)[2], q3 = ((const uint4*)rp)[3];
-            uint32_t rv[16] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w};
-            uint32_t cb[16];
-            bool escape = false;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                if (k0 + (uint32_t)j >= kp) rv[j] = TK_RES_GAP;
-                const bool flagged = rv[j] != TK_RES_GAP && (rv[j] & TK_RES_FLAG), in_tab = flagged && (rv[j] & ~TK_RES_FLAG) < data.ovf_base;
-                cb[j] = data.cnt8[in_tab ? (rv[j] & ~TK_RES_FLAG) : 0u];
-                if (flagged && (!in_tab || cb[j] == 255u)) escape = true;
-                else sum += flagged ? cb[j] : (rv[j] != TK_RES_GAP ? 1u : 0u);
-            }
-            if (escape) {  // (rare: an overflow entry, a piece of 255 tokens and more)
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    const bool flagged = rv[j] != TK_RES_GAP && (rv[j] & TK_RES_FLAG), in_tab = flagged && (rv[j] & ~TK_RES_FLAG) < data.ovf_base;
-                    if (flagged && (!in_tab || cb[j] == 255u)) sum += TKD_COUNT(data.head(rv[j] & ~TK_RES_FLAG)[2]);
-                }
-            }
-        }
-        const uint64_t v = inside ? row_run + tk_row16_sum(sum) : total[0];
-        if (have && sl == 0) tok_off[d] = tok_base_global + v;
-    }
+// An empty chunk's document offsets (every other chunk's are written by tk_k_place, which needs a tile to do it): all its documents are
+// empty, so every offset and the closing one is the token count of the chunks before -- tok_base[0] + total[0], with total[0] = 0.
+__global__ __launch_bounds__(256) void tk_k_docoff(uint64_t n_docs, const uint64_t* __restrict__ total, const unsigned long long* __restrict__ tok_base,
+                                                    uint64_t* __restrict__ tok_off) {
+    for (uint64_t d = blockIdx.x * 256ull + threadIdx.x; d <= n_docs; d += (uint64_t)gridDim.x * 256) tok_off[d] = tok_base[0] + total[0];
 }
 
 // chunk k knows its token count: the next chunk's tokens start behind them (tok_bases[0] = 0)

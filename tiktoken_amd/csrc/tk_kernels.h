@@ -14,8 +14,6 @@
 #include "tk_scan.h"
 #include "tk_special.h"
 
-#define TK_TILE 3840  // text bytes per tile: with 128 bytes of left context and 128 of look-ahead the LDS window is 4096 = 256 lanes x 16
-
 // Deferred pieces are binned by length so that the 64 lanes of a wave run similar trip counts.
 #define TK_NBIN 9
 #define TK_GLANE_MAX 1024  // longest piece handled by the lane / lane-group kernels; longer ones go to the tree kernel
