@@ -4,10 +4,11 @@
 // `encoder: FxHashMap<Vec<u8>, Rank>` (src/lib.rs:321) with three exact structures:
 //   * piece tables : the whole-piece probe of src/lib.rs:367-368, keyed by the piece's BYTES and split by length so that each
 //                    length class runs its own short code path on tables that fit the L2:
-//                      short (1..4 bytes): 8-byte slots {key32, rank | (len-1) << 30}, the bytes packed little-endian;
-//                      mid   (5..8 bytes): 16-byte slots {key64, rank, len}, the bytes packed little-endian;
+//                      short (1..4 bytes): 8-byte slots {key32, rank | (len-1) << 30}, the bytes packed little-endian, four to a bucket;
+//                      mid   (5..8 bytes): 16-byte slots {key64, rank, len}, the bytes packed little-endian, two to a bucket;
 //                      long  (> 8 bytes) : 16-byte slots {hash64, rank, len}, verified against the token-bytes blob,
-//                    so a hit is always an exact byte match (never a fingerprint alone).
+//                    so a hit is always an exact byte match (never a fingerprint alone).  Short, mid and the by-identity table of
+//                    9..23 bytes are probed a BUCKET at a time (below, "bucketed tables"): one memory round trip for nearly every lookup.
 //   * pair table   : open-addressed {(id_left << 32) | id_right -> id_merged} for every vocabulary
 //                    token T and every split T = A || B with A and B both vocabulary tokens.  Every
 //                    part that ever exists during _byte_pair_merge (src/lib.rs:140-196) is itself
@@ -100,8 +101,9 @@ enum {
 struct TkPieceSlot {  // 16 bytes
     uint64_t key;     // packed bytes (len <= 8) or tk_hash_bytes (len > 8); ~0 = empty
     uint32_t rank;
-    uint32_t len;
+    uint32_t len;     // 0 = empty.  Mid table, last slot of a bucket: | TK_MID_PASSED once a key has been carried past the bucket
 };
+#define TK_MID_PASSED 0x100u
 struct TkShortSlot {  // 8 bytes
     uint32_t key;      // packed bytes (len <= 4)
     uint32_t val;      // rank | (len - 1) << 30; 0xFFFFFFFF = empty
@@ -120,7 +122,7 @@ struct TkShortSlot {  // 8 bytes
 struct alignas(16) TkXlSlot {  // 32 bytes
     uint64_t w0, w1, w2;  // tk_ident of the token's bytes (w2's top byte is the length)
     uint32_t rank;        // TK_RANK_MAX = empty
-    uint32_t pad;
+    uint32_t passed;      // last slot of a bucket: 1 once a key has been carried past the bucket, else 0
 };
 struct TkPairSlot {  // 16 bytes
     uint64_t key;    // (id_left << 32) | id_right; ~0 = empty
@@ -278,6 +280,87 @@ TK_HD uint64_t tk_ident_hash(uint64_t w0, uint64_t w1, uint64_t w2, bool exact) 
     h2 *= 0x9E3779B1u;
     h2 ^= h2 >> 16;
     return ((uint64_t)h2 << 32) | h1;
+}
+
+// ---- bucketed tables: short, mid and by-identity ----
+// Open addressing over BUCKETS: TK_SHORT_BW / TK_MID_BW / TK_XL_BW neighbouring slots, aligned to the bucket's size, which a probe
+// fetches whole with 16-byte loads that depend on nothing but the bucket's index -- one memory round trip.  A key's sequence starts at
+// the bucket its hash slot lies in and goes on bucket by bucket (wrapping).  The builder (tk_bucket_place_*) puts a key into the first
+// bucket of its sequence with a free slot, and a bucket's slots fill in order, so a bucket whose LAST slot is free ends a search, for
+// hits and misses alike.  The mid and by-identity slots have room for one more bit, in the bucket's last slot: "a key was carried past
+// this bucket"; a FULL bucket without it ends a search as well.  (With one slot per step a wavefront's row of 64 lookups ran as long as
+// its unluckiest lane: 2.2 / 2.9 / 5.6 steps on the bench corpus where these take 1.1 / 1.3 / 2.0 -- profiles/probe_lengths.txt.)
+// The compare over a bucket's slots is straight-line code; only "bucket full, no match, keys carried past it" goes round the loop.
+#define TK_SHORT_BW 4u  // 32-byte buckets
+#define TK_MID_BW 2u    // 32-byte buckets
+#define TK_XL_BW 2u     // 64-byte buckets
+#define TK_BUCKET_BOUND 64u  // the builder refuses a vocabulary one of whose keys would lie more than this many buckets into its sequence
+
+// slot = the key's hash slot (tk_short_slot); mask = slots - 1
+TK_HD uint32_t tk_bucket_probe_short(const TkShortSlot* tab, uint32_t mask, uint32_t slot, uint32_t key, uint32_t len) {
+    const uint32_t tag = (len - 1u) << 30;
+    for (uint32_t b = slot & ~(TK_SHORT_BW - 1u);; b = (b + TK_SHORT_BW) & mask) {
+        const TkShortSlot* p = tab + b;
+#if defined(__HIP_DEVICE_COMPILE__)
+        const uint4 q0 = *(const uint4*)p, q1 = *(const uint4*)(p + 2);
+        const uint32_t k0 = q0.x, v0 = q0.y, k1 = q0.z, v1 = q0.w, k2 = q1.x, v2 = q1.y, k3 = q1.z, v3 = q1.w;
+#else
+        const uint32_t k0 = p[0].key, v0 = p[0].val, k1 = p[1].key, v1 = p[1].val, k2 = p[2].key, v2 = p[2].val, k3 = p[3].key, v3 = p[3].val;
+#endif
+        uint32_t v = TK_SHORT_EMPTY;  // (a free slot that "matches" -- four bytes of 0xFF -- leaves it at that)
+        if (k3 == key && ((v3 ^ tag) >> 30) == 0u) v = v3;
+        if (k2 == key && ((v2 ^ tag) >> 30) == 0u) v = v2;
+        if (k1 == key && ((v1 ^ tag) >> 30) == 0u) v = v1;
+        if (k0 == key && ((v0 ^ tag) >> 30) == 0u) v = v0;
+        if (v != TK_SHORT_EMPTY) return v & TK_SHORT_RANK_MASK;
+        if (v3 == TK_SHORT_EMPTY) return TK_RANK_MAX;
+    }
+}
+// slot = tk_mid_slot of the key
+TK_HD uint32_t tk_bucket_probe_mid(const TkPieceSlot* tab, uint32_t mask, uint32_t slot, uint64_t key, uint32_t len) {
+    for (uint32_t b = slot & ~(TK_MID_BW - 1u);; b = (b + TK_MID_BW) & mask) {
+        const TkPieceSlot* p = tab + b;
+#if defined(__HIP_DEVICE_COMPILE__)
+        const uint4 q0 = *(const uint4*)p, q1 = *(const uint4*)(p + 1);
+        const uint64_t k0 = ((uint64_t)q0.y << 32) | q0.x, k1 = ((uint64_t)q1.y << 32) | q1.x;
+        const uint32_t r0 = q0.z, l0 = q0.w, r1 = q1.z, l1 = q1.w;
+#else
+        const uint64_t k0 = p[0].key, k1 = p[1].key;
+        const uint32_t r0 = p[0].rank, l0 = p[0].len, r1 = p[1].rank, l1 = p[1].len;
+#endif
+        if (k0 == key && l0 == len) return r0;
+        if (k1 == key && (l1 & 0xFFu) == len) return r1;
+        if (l1 < TK_MID_PASSED) return TK_RANK_MAX;  // the last slot free, or nothing carried past the bucket
+    }
+}
+// slot = the low word of tk_ident_hash(w0, w1, w2, true) & mask
+TK_HD uint32_t tk_bucket_probe_xl(const TkXlSlot* tab, uint32_t mask, uint32_t slot, uint64_t w0, uint64_t w1, uint64_t w2) {
+    for (uint32_t b = slot & ~(TK_XL_BW - 1u);; b = (b + TK_XL_BW) & mask) {
+        const TkXlSlot* p = tab + b;
+#if defined(__HIP_DEVICE_COMPILE__)
+        const ulonglong2 a0 = *(const ulonglong2*)p, a1 = *((const ulonglong2*)p + 1), c0 = *((const ulonglong2*)p + 2), c1 = *((const ulonglong2*)p + 3);
+        const uint64_t x0 = a0.x, x1 = a0.y, x2 = a1.x, y0 = c0.x, y1 = c0.y, y2 = c1.x;
+        const uint32_t r0 = (uint32_t)a1.y, r1 = (uint32_t)c1.y, passed = (uint32_t)(c1.y >> 32);
+#else
+        const uint64_t x0 = p[0].w0, x1 = p[0].w1, x2 = p[0].w2, y0 = p[1].w0, y1 = p[1].w1, y2 = p[1].w2;
+        const uint32_t r0 = p[0].rank, r1 = p[1].rank, passed = p[1].passed;
+#endif
+        if (x0 == w0 && x1 == w1 && x2 == w2) return r0;  // (a free slot holds ~0 in all three: no identity, whose top byte is a length)
+        if (y0 == w0 && y1 == w1 && y2 == w2) return r1;
+        if (!passed) return TK_RANK_MAX;  // the last slot free, or nothing carried past the bucket
+    }
+}
+// The builder's side: the slot for a new key (which the caller has found absent) whose hash slot is `slot`, or 0xFFFFFFFF when the key
+// would lie more than TK_BUCKET_BOUND buckets into its sequence; full(i) = slot i is taken, pass(i) marks the bucket whose last slot is i.
+template <class Full, class Pass>
+inline uint32_t tk_bucket_place(uint32_t bw, uint32_t mask, uint32_t slot, Full&& full, Pass&& pass) {
+    uint32_t b = slot & ~(bw - 1u);
+    for (uint32_t step = 0; step < TK_BUCKET_BOUND; ++step, b = (b + bw) & mask) {
+        for (uint32_t j = 0; j < bw; ++j)
+            if (!full(b + j)) return b + j;
+        pass(b + bw - 1u);
+    }
+    return 0xFFFFFFFFu;
 }
 
 // streaming hash for keys longer than 8 bytes: fold 8-byte little-endian words (last one zero padded)

@@ -739,33 +739,15 @@ TK_HD uint32_t tk_piece_len_bits32(const W32& w, A& a, uint64_t p, uint32_t c, T
 // ------------------------------------------------------------------------------------------
 // table probes
 // ------------------------------------------------------------------------------------------
-// Exact bytes -> rank probes, one per length class (tk_common.h).  The `_from` forms continue from a slot the caller has already
-// loaded (so that the first loads of several independent probes can be in flight together).
+// Exact bytes -> rank probes, one per length class (tk_common.h).  Short, mid and by-identity: a bucket per step (tk_common.h,
+// "bucketed tables"), its loads issued together.
 // Short: key = the 1..4 bytes packed little-endian.
-TK_HD uint32_t tk_probe_short_from(const TkTables& T, uint32_t key, uint32_t len, uint32_t i, TkShortSlot s) {
-    for (;;) {
-        if (s.key == key && (s.val >> 30) == len - 1u && s.val != TK_SHORT_EMPTY) return s.val & TK_SHORT_RANK_MASK;
-        if (s.val == TK_SHORT_EMPTY) return TK_RANK_MAX;
-        i = (i + 1u) & T.short_mask;
-        s = T.short_tab[i];
-    }
-}
 TK_HD uint32_t tk_probe_short(const TkTables& T, uint32_t key, uint32_t len) {
-    const uint32_t i = tk_short_slot(key, T.short_shift);
-    return tk_probe_short_from(T, key, len, i, T.short_tab[i]);
+    return tk_bucket_probe_short(T.short_tab, T.short_mask, tk_short_slot(key, T.short_shift), key, len);
 }
 // Mid: key = the bytes (<= 8) packed little-endian.
-TK_HD uint32_t tk_probe_mid_from(const TkTables& T, uint64_t key, uint32_t len, uint32_t i, TkPieceSlot s) {
-    for (;;) {
-        if (s.key == key && s.len == len) return s.rank;
-        if (s.len == 0u) return TK_RANK_MAX;
-        i = (i + 1u) & T.mid_mask;
-        s = T.mid_tab[i];
-    }
-}
 TK_HD uint32_t tk_probe_mid(const TkTables& T, uint64_t key, uint32_t len) {
-    const uint32_t i = tk_mid_slot(key, T.mid_shift);
-    return tk_probe_mid_from(T, key, len, i, T.mid_tab[i]);
+    return tk_bucket_probe_mid(T.mid_tab, T.mid_mask, tk_mid_slot(key, T.mid_shift), key, len);
 }
 // Long (> 8 bytes): key = tk hash of the bytes; the candidate is verified byte for byte against the token blob through `verify(off)`.
 template <class Verify>
@@ -783,19 +765,9 @@ TK_HD uint32_t tk_probe_piece(const TkTables& T, uint64_t key, uint32_t len, Ver
     return tk_probe_piece_from(T, key, len, i, T.piece[i], verify);
 }
 
-// Tokens of TK_XL_MIN..TK_XL_MAX bytes by identity (tk_common.h, tk_ident): the slot holds the bytes, a match is exact.  `s` = slot i,
-// which the caller has loaded (together with whatever else it needs: one memory round trip).
-TK_HD uint32_t tk_probe_xl_from(const TkTables& T, uint64_t w0, uint64_t w1, uint64_t w2, uint32_t i, TkXlSlot s) {
-    for (;;) {
-        if (s.rank == TK_RANK_MAX) return TK_RANK_MAX;
-        if (s.w0 == w0 && s.w1 == w1 && s.w2 == w2) return s.rank;
-        i = (i + 1u) & T.xl_mask;
-        s = T.xl[i];
-    }
-}
+// Tokens of TK_XL_MIN..TK_XL_MAX bytes by identity (tk_common.h, tk_ident): the slot holds the bytes, a match is exact.
 TK_HD uint32_t tk_probe_xl(const TkTables& T, uint64_t w0, uint64_t w1, uint64_t w2) {
-    const uint32_t i = (uint32_t)tk_ident_hash(w0, w1, w2, true) & T.xl_mask;
-    return tk_probe_xl_from(T, w0, w1, w2, i, T.xl[i]);
+    return tk_bucket_probe_xl(T.xl, T.xl_mask, (uint32_t)tk_ident_hash(w0, w1, w2, true) & T.xl_mask, w0, w1, w2);
 }
 
 // Pair probe.  Packed format: 4-slot (32-byte, 32-byte-aligned) buckets; a bucket is fetched with two

@@ -73,23 +73,10 @@ uint32_t TkHostTables::lookup_piece(const uint8_t* p, uint32_t len) const {
     if (len <= 8) {
         uint64_t key = 0;
         memcpy(&key, p, len);
-        if (len <= 4 && !short_tab.empty()) {
-            uint32_t i = tk_short_slot((uint32_t)key, short_shift);
-            for (;;) {
-                const TkShortSlot& s = short_tab[i];
-                if (s.val == TK_SHORT_EMPTY) return TK_RANK_MAX;
-                if (s.key == (uint32_t)key && (s.val >> 30) == len - 1) return s.val & TK_SHORT_RANK_MASK;
-                i = (i + 1) & short_mask;
-            }
-        }
+        // (the probes the device runs: tk_common.h, "bucketed tables")
+        if (len <= 4 && !short_tab.empty()) return tk_bucket_probe_short(short_tab.data(), short_mask, tk_short_slot((uint32_t)key, short_shift), (uint32_t)key, len);
         if (mid_tab.empty()) return TK_RANK_MAX;
-        uint32_t i = tk_mid_slot(key, mid_shift);
-        for (;;) {
-            const TkPieceSlot& s = mid_tab[i];
-            if (s.len == 0) return TK_RANK_MAX;
-            if (s.key == key && s.len == len) return s.rank;
-            i = (i + 1) & mid_mask;
-        }
+        return tk_bucket_probe_mid(mid_tab.data(), mid_mask, tk_mid_slot(key, mid_shift), key, len);
     }
     if (piece.empty()) return TK_RANK_MAX;
     uint64_t key = tk_key_of_bytes(p, len);
@@ -200,6 +187,13 @@ std::string tk_build_tables(const uint8_t* ranks_blob, const uint64_t* ranks_off
         else T.dec_sparse.reserve(n_ranks * 2);
     }
     uint64_t pr_short = 0, pr_mid = 0, pr_long = 0, pr_xl = 0;
+    // short, mid and by-identity: buckets (tk_common.h, "bucketed tables"); a key goes into the first bucket of its sequence with a free slot,
+    // in the order of the file, and one that would lie beyond the bound is an error (a vocabulary made to collide; never a silent long walk)
+    auto too_deep = [](const char* which) {
+        return std::string("the ") + which + " token table cannot take this vocabulary: more than " + std::to_string(TK_BUCKET_BOUND) +
+               " full buckets in a row (token bytes chosen to collide?)";
+    };
+    auto bucket_steps = [](uint32_t slot, uint32_t home, uint32_t bw, uint32_t mask) { return (((slot & ~(bw - 1u)) - (home & ~(bw - 1u))) & mask) / bw + 1u; };
     for (uint64_t k = 0; k < n_ranks; ++k) {
         uint64_t o = ranks_off[k], len64 = ranks_off[k + 1] - o;
         if (len64 == 0) return "mergeable_ranks contains an empty key";
@@ -221,20 +215,16 @@ std::string tk_build_tables(const uint8_t* ranks_blob, const uint64_t* ranks_off
             uint64_t key = 0;
             memcpy(&key, p, len);
             if (len <= 4 && use_short) {
-                uint32_t i = tk_short_slot((uint32_t)key, T.short_shift);
-                ++pr_short;
-                while (T.short_tab[i].val != TK_SHORT_EMPTY) {
-                    i = (i + 1) & T.short_mask;
-                    ++pr_short;
-                }
+                const uint32_t h = tk_short_slot((uint32_t)key, T.short_shift);
+                const uint32_t i = tk_bucket_place(TK_SHORT_BW, T.short_mask, h, [&](uint32_t j) { return T.short_tab[j].val != TK_SHORT_EMPTY; }, [](uint32_t) {});
+                if (i == 0xFFFFFFFFu) return too_deep("short");
+                pr_short += bucket_steps(i, h, TK_SHORT_BW, T.short_mask);
                 T.short_tab[i] = TkShortSlot{(uint32_t)key, rank | ((len - 1) << 30)};
             } else {
-                uint32_t i = tk_mid_slot(key, T.mid_shift);
-                ++pr_mid;
-                while (T.mid_tab[i].len != 0) {
-                    i = (i + 1) & T.mid_mask;
-                    ++pr_mid;
-                }
+                const uint32_t h = tk_mid_slot(key, T.mid_shift);
+                const uint32_t i = tk_bucket_place(TK_MID_BW, T.mid_mask, h, [&](uint32_t j) { return T.mid_tab[j].len != 0; }, [&](uint32_t j) { T.mid_tab[j].len |= TK_MID_PASSED; });
+                if (i == 0xFFFFFFFFu) return too_deep("mid");
+                pr_mid += bucket_steps(i, h, TK_MID_BW, T.mid_mask);
                 T.mid_tab[i] = TkPieceSlot{key, rank, len};
             }
         } else {
@@ -260,12 +250,10 @@ std::string tk_build_tables(const uint8_t* ranks_blob, const uint64_t* ranks_off
                 T.xfilter[bit >> 5] |= 1u << (bit & 31u);
             }
             if (len >= TK_XL_MIN && len <= TK_XL_MAX) {
-                uint32_t j = (uint32_t)tk_ident_hash(w0, w1, w2, true) & T.xl_mask;
-                ++pr_xl;
-                while (T.xl[j].rank != TK_RANK_MAX) {
-                    j = (j + 1) & T.xl_mask;
-                    ++pr_xl;
-                }
+                const uint32_t h = (uint32_t)tk_ident_hash(w0, w1, w2, true) & T.xl_mask;
+                const uint32_t j = tk_bucket_place(TK_XL_BW, T.xl_mask, h, [&](uint32_t q) { return T.xl[q].rank != TK_RANK_MAX; }, [&](uint32_t q) { T.xl[q].passed = 1u; });
+                if (j == 0xFFFFFFFFu) return too_deep("by-identity");
+                pr_xl += bucket_steps(j, h, TK_XL_BW, T.xl_mask);
                 T.xl[j] = TkXlSlot{w0, w1, w2, rank, 0u};
             }
         }

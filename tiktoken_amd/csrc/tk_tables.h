@@ -18,17 +18,17 @@ struct TkHostTables {
     TkRxCompiled rx;          // a pat_str outside the scanner families: its program for the generic engine (tk_regex.cpp); pat is then
                               // the "no split" member of the r50k family, run over a class table in which every char is a letter
     std::vector<uint8_t> tok_bytes;
-    std::vector<TkShortSlot> short_tab;  // tokens of 1..4 bytes (empty when a rank exceeds TK_SHORT_MAX_RANK)
+    std::vector<TkShortSlot> short_tab;  // tokens of 1..4 bytes in buckets of TK_SHORT_BW slots (empty when a rank exceeds TK_SHORT_MAX_RANK)
     uint32_t short_mask = 0, short_shift = 0;
-    std::vector<TkPieceSlot> mid_tab;    // tokens of 5..8 bytes (1..8 without a short table)
+    std::vector<TkPieceSlot> mid_tab;    // tokens of 5..8 bytes in buckets of TK_MID_BW slots (1..8 without a short table)
     uint32_t mid_mask = 0, mid_shift = 0;
     std::vector<TkPieceSlot> piece;      // tokens of more than 8 bytes
     std::vector<uint32_t> piece_off;
     uint64_t piece_mask = 0;
-    std::vector<TkXlSlot> xl;            // tokens of TK_XL_MIN..TK_XL_MAX bytes once more, by identity (tk_common.h)
+    std::vector<TkXlSlot> xl;            // tokens of TK_XL_MIN..TK_XL_MAX bytes once more, by identity, in buckets of TK_XL_BW slots (tk_common.h)
     uint32_t xl_mask = 0;
     std::vector<uint32_t> xfilter;       // which identity hashes tokens of more than TK_XL_MAX bytes have (tk_common.h)
-    double probes_short = 0, probes_mid = 0, probes_long = 0, probes_xl = 0;  // average slots inspected per stored token (build statistics)
+    double probes_short = 0, probes_mid = 0, probes_long = 0, probes_xl = 0;  // average steps (buckets; long: slots) per stored token (build statistics)
     std::vector<TkPairSlot> pair;   // wide format (empty when packed)
     std::vector<uint64_t> pair8;    // packed format (empty when wide)
     uint64_t pair_mask = 0;
