@@ -284,11 +284,14 @@ int tk_encode_batch_padded(tk_core* core, const uint8_t* utf8, const uint64_t* d
  *   part, called a document as in the other passes); a sample_off that does not ascend from 0 to n_parts (the first offending sample);
  *   T >= 2^32; n_parts or n_samples >= 2^32 - 1; 2^32 elements or more over all parts; R * W >= 2^32.  The three device arrays are checked
  *   on the device before anything is indexed with them: no kernel reads or writes out of bounds, whatever they hold.
- *  One device per call: a group has no samples entry.  NOT built: several samples packed into one row; 16-bit ids; windows for over-long
- *   samples; a special-token policy per part (the call's policy holds for all parts); a template language (callers encode their few header
- *   and footer strings once and pass the ids). */
-#define TK_SMP_KEEP_TAIL 1u /* keep an over-long sample's last elements, not its first */
-#define TK_SMP_LEFT 2u      /* padding in front of the row's elements, not behind */
+ *  One device per call: a group has no samples entry.  NOT built: 16-bit ids; windows for over-long samples; a special-token policy per
+ *   part (the call's policy holds for all parts); a template language (callers encode their few header and footer strings once and pass
+ *   the ids).  Several samples in one row: tk_pack_samples_device below.  TK_SMP_SKIP_LONG and TK_SMP_IGNORE_FIRST mean something there
+ *   only: this entry refuses them with TK_VALUE_ERROR, as it refuses every flag bit it does not know. */
+#define TK_SMP_KEEP_TAIL 1u    /* keep an over-long sample's last elements, not its first */
+#define TK_SMP_LEFT 2u         /* padding in front of the row's elements, not behind (tk_assemble_samples_device only) */
+#define TK_SMP_SKIP_LONG 4u    /* tk_pack_samples_device only: leave an over-long sample out instead of cutting it */
+#define TK_SMP_IGNORE_FIRST 8u /* tk_pack_samples_device only: the label of every sample's first element is ignore_index */
 typedef struct {
     uint32_t max_len, width_multiple, bos_id, eos_id, pad_id;
     int32_t ignore_index;
@@ -314,6 +317,63 @@ int tk_encode_batch_samples(tk_core* core, const uint8_t* utf8, const uint64_t* 
                             uint64_t n_samples, uint32_t n_roles, const uint32_t* role_ids, const uint32_t* role_off, const uint8_t* role_train,
                             const tk_smp_spec* spec, uint32_t** ids_out, uint8_t** mask_out, int32_t** labels_out, uint32_t** len_out, uint64_t** full_len_out,
                             uint32_t** n_trained_out, uint64_t* n_rows_out, uint64_t* width_out, tk_special_hit* hit);
+/* Packed sample rows: the samples of tk_assemble_samples_device, several whole ones to a row of max_len, with what block-diagonal /
+ * variable-length attention needs to keep them apart.  Replaces nothing in the reference: it is the packing loop of its users' SFT data
+ * collators -- here one call on ids that are on the device anyway, and a third less padding through the model than one row per sample.
+ * The rule.  Inputs, role table, stream of a sample, trained elements, truncation (len[s] = min(full_len[s], max_len), TK_SMP_KEEP_TAIL) and
+ * full_len are exactly those of tk_assemble_samples_device, and so is the tk_smp_spec.  L = max_len.
+ *  Placed length.  plen[s] = len[s]; with TK_SMP_SKIP_LONG plen[s] = 0 where full_len[s] > L: the sample is left out instead of cut.  A
+ *   sample with plen == 0 owns no position.
+ *  Placement is next-fit in input order -- it keeps the caller's order, so the caller's shuffle or sort is the policy:
+ *     row = 0; fill = 0; any = false
+ *     for s in 0 .. n_samples - 1:
+ *         p = plen[s]
+ *         if p == 0: sample_row[s] = TK_ROWS_NO_TOKEN; sample_col[s] = 0; continue
+ *         if fill + p > L: row += 1; fill = 0
+ *         sample_row[s] = row; sample_col[s] = fill; fill += p; any = true
+ *     R = any ? row + 1 : 0
+ *   row_sample uint32[R + 1]: the first sample with sample_row == r, and row_sample[R] = n_samples.  Every row holds at least one element.
+ *   The width is L always.
+ *  Per position (r, c) of [R, L], fill_r being the placed lengths of row r's samples together:
+ *   ids (uint32)    the element, or pad_id on the row's tail (c >= fill_r)
+ *   labels (int32)  as in tk_assemble_samples_device, unshifted: the id where the element is trained, ignore_index everywhere else; with
+ *                   TK_SMP_IGNORE_FIRST also ignore_index at pos == 0 of every sample (after the model's shift that element would be
+ *                   predicted from the previous sample's last token)
+ *   seg (uint32)    the sample, or TK_ROWS_NO_TOKEN on padding
+ *   pos (uint32)    c - sample_col[seg] on elements, c - fill_r on the tail: a row's padding tail is a segment of its own, as padding is in
+ *                   tk_pack_rows_device
+ *  Segments.  cu_seqlens uint32[n_segs + 1]: the flat positions r * L + c with pos == 0, ascending, then R * L; row_seg uint32[R + 1]: the
+ *   segment starts below r * L, so cu_seqlens[row_seg[a] .. row_seg[b]] - a * L are the boundaries of the rows a .. b alone.
+ *   n_segs = placed samples + rows with fill_r < L.
+ *  Per sample.  len uint32[n_samples] and full_len uint64[n_samples] as in tk_assemble_samples_device (of an unplaced sample too);
+ *   n_trained uint32[n_samples]: the labels of the sample that are not ignore_index by the rule -- tk_assemble_samples_device's figure, one
+ *   less where TK_SMP_IGNORE_FIRST masks a trained first element, and 0 for a sample that is not placed; sample_row, sample_col uint32[n_samples].
+ *  TK_VALUE_ERROR, every one found before any output is written (a refused call leaves the previous result of this entry, and the encode
+ *   result, whole): everything tk_assemble_samples_device refuses; width_multiple != 0; TK_SMP_LEFT; R * L >= 2^32.  The three device
+ *   arrays are checked on the device before anything is indexed with them: no kernel reads or writes out of bounds, whatever they hold.
+ *  One device per call: a group has no packed-samples entry.  NOT built: best-fit or sorted packing (sort the samples before the call);
+ *   16-bit ids; windows for over-long samples; a special-token policy per part. */
+/* Device pointers in and the role table in host memory as in tk_assemble_samples_device, device pointers out: buffers of the core, valid
+ * until its next packed-samples call that succeeds (a refused call writes into none of them) and apart from every other entry's buffers
+ * (packing an encode call's result leaves it intact, and so does it a tk_assemble_samples_device result).  *d_ids_out, *d_labels_out,
+ * *d_seg_out, *d_pos_out: *n_rows_out x max_len; *d_cu_seqlens_out: *n_segs_out + 1; *d_row_seg_out, *d_row_sample_out: *n_rows_out + 1;
+ * *d_len_out .. *d_sample_col_out: n_samples.  `stream`: a hipStream_t or null (the core's); the call returns when the rows are there. */
+int tk_pack_samples_device(tk_core* core, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_parts, const void* d_part_role,
+                           const void* d_sample_off, uint64_t n_samples, uint32_t n_roles, const uint32_t* role_ids, const uint32_t* role_off,
+                           const uint8_t* role_train, const tk_smp_spec* spec, void* stream, const uint32_t** d_ids_out, const int32_t** d_labels_out,
+                           const uint32_t** d_seg_out, const uint32_t** d_pos_out, const uint32_t** d_cu_seqlens_out, const uint32_t** d_row_seg_out,
+                           const uint32_t** d_row_sample_out, const uint32_t** d_len_out, const uint64_t** d_full_len_out, const uint32_t** d_n_trained_out,
+                           const uint32_t** d_sample_row_out, const uint32_t** d_sample_col_out, uint64_t* n_rows_out, uint64_t* n_segs_out);
+/* tk_encode_batch -- with n_disallowed != 0: tk_encode_batch_checked, whose *hit names the PART -- over the parts' text (doc_off: n_parts + 1
+ * byte offsets), with the samples packed into rows while the ids are on the device: host text, part_role and sample_off in, and only the
+ * row arrays cross the link back.  *ids_out .. *sample_col_out: library-owned (tk_free), sized as above.  On TK_DISALLOWED_SPECIAL nothing
+ * is handed out. */
+int tk_encode_batch_sample_rows(tk_core* core, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_parts, int use_special, const uint32_t* allowed_ids,
+                                uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed, const uint8_t* part_role, const uint64_t* sample_off,
+                                uint64_t n_samples, uint32_t n_roles, const uint32_t* role_ids, const uint32_t* role_off, const uint8_t* role_train,
+                                const tk_smp_spec* spec, uint32_t** ids_out, int32_t** labels_out, uint32_t** seg_out, uint32_t** pos_out, uint32_t** cu_seqlens_out,
+                                uint32_t** row_seg_out, uint32_t** row_sample_out, uint32_t** len_out, uint64_t** full_len_out, uint32_t** n_trained_out,
+                                uint32_t** sample_row_out, uint32_t** sample_col_out, uint64_t* n_rows_out, uint64_t* n_segs_out, tk_special_hit* hit);
 /* bpe_train(data, vocab_size, pat_str, visualise=None)                      tiktoken/_educational.py:119-185
  * Training a vocabulary: the merges the reference's educational trainer makes on the same text -- the same pairs in the same order -- for a
  * packed batch of documents, under the core's pat_str (stock scanners or the generic engine).  The core's ranks and special tokens play

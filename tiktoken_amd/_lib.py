@@ -48,7 +48,7 @@ class SmpSpec(ctypes.Structure):
                 ("ignore_index", ctypes.c_int32), ("flags", ctypes.c_uint32)]
 
 
-SMP_KEEP_TAIL, SMP_LEFT = 1, 2
+SMP_KEEP_TAIL, SMP_LEFT, SMP_SKIP_LONG, SMP_IGNORE_FIRST = 1, 2, 4, 8
 
 
 def build(force: bool = False) -> str:
@@ -122,6 +122,12 @@ def lib() -> ctypes.CDLL:
         L.tk_encode_batch_samples.restype = i32
         L.tk_encode_batch_samples.argtypes = [vp, vp, vp, u64, i32, vp, u64, vp, u64, vp, vp, u64, u32, vp, vp, vp, P(SmpSpec), P(vp), P(vp), P(vp), P(vp), P(vp), P(vp),
                                               P(u64), P(u64), P(SpecialHit)]
+        if hasattr(L, "tk_pack_samples_device"):  # (absent from older builds selected through $TIKTOKEN_AMD_LIB)
+            L.tk_pack_samples_device.restype = i32
+            L.tk_pack_samples_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, u32, vp, vp, vp, P(SmpSpec), vp, *[P(vp)] * 12, P(u64), P(u64)]
+            L.tk_encode_batch_sample_rows.restype = i32
+            L.tk_encode_batch_sample_rows.argtypes = [vp, vp, vp, u64, i32, vp, u64, vp, u64, vp, vp, u64, u32, vp, vp, vp, P(SmpSpec), *[P(vp)] * 12, P(u64), P(u64),
+                                                      P(SpecialHit)]
         L.tk_decode_single_token_bytes.restype = i32
         L.tk_decode_single_token_bytes.argtypes = [vp, u32, P(vp), P(u64)]
         L.tk_n_tokens.restype = u64

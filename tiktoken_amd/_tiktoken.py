@@ -234,6 +234,47 @@ class SamplesDevice(NamedTuple):
     width: int
 
 
+class SampleRows(NamedTuple):
+    """A batch as packed sample rows (tk_encode_batch_sample_rows; the rule: include/tiktoken_amd.h): the samples of `SampleBatch`, several
+    whole ones to a row of max_length, placed next-fit in input order.  Per position: input_ids (the pad id on a row's tail), labels (not
+    shifted; ignore_index where nothing is trained), segment_ids (the sample; 2^32 - 1 on padding) and position_ids (restarting at every
+    sample, and at a row's padding tail).  cu_seqlens holds the flat positions where a segment starts and, last, R * max_length --
+    cu_seqlens[row_seg[a] : row_seg[b] + 1] - a * max_length are the boundaries of the rows a .. b alone.  Per sample: length, full_length,
+    n_trained (0 for a sample that is not placed), sample_row (2^32 - 1: not placed) and sample_col; row_sample[r] is row r's first sample."""
+    input_ids: np.ndarray  # [R, L] uint32
+    labels: np.ndarray  # [R, L] int32
+    segment_ids: np.ndarray  # [R, L] uint32
+    position_ids: np.ndarray  # [R, L] uint32
+    cu_seqlens: np.ndarray  # uint32[n_segs + 1]
+    row_seg: np.ndarray  # uint32[R + 1]
+    row_sample: np.ndarray  # uint32[R + 1]
+    length: np.ndarray  # uint32[n_samples]
+    full_length: np.ndarray  # uint64[n_samples]
+    n_trained: np.ndarray  # uint32[n_samples]
+    sample_row: np.ndarray  # uint32[n_samples]
+    sample_col: np.ndarray  # uint32[n_samples]
+
+
+class SampleRowsDevice(NamedTuple):
+    """`pack_samples_device`: device pointers (the core's buffers, valid until its next packed-samples call that succeeds) and the figures
+    that size them: input_ids / labels / segment_ids / position_ids hold n_rows * max_length elements, cu_seqlens n_segs + 1, row_seg and
+    row_sample n_rows + 1, the others n_samples."""
+    input_ids: int
+    labels: int
+    segment_ids: int
+    position_ids: int
+    cu_seqlens: int
+    row_seg: int
+    row_sample: int
+    length: int
+    full_length: int
+    n_trained: int
+    sample_row: int
+    sample_col: int
+    n_rows: int
+    n_segs: int
+
+
 class DisallowedSpecialError(ValueError):
     """A batch holds a disallowed special token: the first occurrence -- document `doc`, byte offset `pos` inside it, the `token` (the
     longest disallowed one that matches there).  What the reference raises as a plain ValueError, with its message."""
@@ -932,6 +973,67 @@ class CoreBPE:
         mask = self._own_mask(out[1], n)
         labels = _take_u32(out[2], n).view(np.int32).reshape(n_rows, width)
         return SampleBatch(input_ids, mask.reshape(n_rows, width), labels, _take_u32(out[3], n_rows), _take_u64(out[4], n_rows), _take_u32(out[5], n_rows))
+
+    # ------------------------------------------------------------------ packed sample rows (no reference counterpart: the collator of its users)
+    @classmethod
+    def _srow_spec(cls, max_length: int, keep: str, skip_long: bool, ignore_first: bool, padding_side: str, pad_to_multiple_of, bos, eos, pad: int,
+                   ignore_index: int) -> "_lib.SmpSpec":
+        """The tk_smp_spec of a packed-samples call; `padding_side` and `pad_to_multiple_of` are passed on for the library to refuse"""
+        spec = cls._smp_spec(max_length, keep, padding_side, pad_to_multiple_of, bos, eos, pad, ignore_index)
+        spec.flags |= (_lib.SMP_SKIP_LONG if skip_long else 0) | (_lib.SMP_IGNORE_FIRST if ignore_first else 0)
+        return spec
+
+    def pack_samples_device(self, d_tokens: int, n_tokens: int, d_tok_off: int, n_parts: int, d_part_role: int, d_sample_off: int, n_samples: int,
+                            roles: "Sequence[Role]", *, max_length: int, keep: str = "head", skip_long: bool = False, ignore_first: bool = False,
+                            padding_side: str = "right", pad_to_multiple_of: int | None = None, bos: int | None = None, eos: int | None = None, pad: int = 0,
+                            ignore_index: int = -100, stream: int = 0) -> SampleRowsDevice:
+        """Device-resident packed sample rows (tk_pack_samples_device): the arguments of `assemble_samples_device`; the samples go several
+        to a row of `max_length`, next-fit in input order; see `SampleRows` for the arrays.  `skip_long`: an over-long sample is left out
+        instead of cut; `ignore_first`: the label of every sample's first element is `ignore_index`.  The rows are `max_length` wide and
+        padded on the right: `padding_side="left"` and `pad_to_multiple_of` are refused."""
+        self._one_device("pack_samples_device")
+        spec = self._srow_spec(max_length, keep, skip_long, ignore_first, padding_side, pad_to_multiple_of, bos, eos, pad, ignore_index)
+        n_roles, ids, off, train = self._role_table(roles)
+        out, cnt, refs = self._outs(12, 2)
+        rc = self._L.tk_pack_samples_device(self._h, d_tokens or None, n_tokens, d_tok_off or None, n_parts, d_part_role or None, d_sample_off or None, n_samples,
+                                            n_roles, ids.ctypes.data, off.ctypes.data, train.ctypes.data, ctypes.byref(spec), stream or None, *refs)
+        _lib.raise_for(rc)
+        return SampleRowsDevice(*[x.value or 0 for x in out], *[int(x.value) for x in cnt])
+
+    def encode_batch_sample_rows_packed(self, blob: np.ndarray, doc_off: np.ndarray, allowed_special: AbstractSet[str] | None = None, *, disallowed_special=None,
+                                        part_role, sample_off, roles: "Sequence[Role]", max_length: int, keep: str = "head", skip_long: bool = False,
+                                        ignore_first: bool = False, padding_side: str = "right", pad_to_multiple_of: int | None = None, bos: int | None = None,
+                                        eos: int | None = None, pad: int = 0, ignore_index: int = -100) -> SampleRows:
+        """`encode_batch_packed` over the parts' text with the samples packed into rows while the ids are on the device
+        (tk_encode_batch_sample_rows): only the row arrays come back.  The text and special-token arguments as in
+        `encode_batch_samples_packed`, the others as in `pack_samples_device`."""
+        self._one_device("encode_batch_sample_rows_packed")
+        text, dis, n_parts, _keep = self._batch_args(blob, doc_off, allowed_special, disallowed_special)
+        roles_in = np.asarray(part_role)
+        if roles_in.size and (roles_in.min() < 0 or roles_in.max() > 255):
+            raise ValueError("part_role must hold role indices below 256")
+        part_role = np.ascontiguousarray(roles_in, dtype=np.uint8)
+        sample_off = np.ascontiguousarray(sample_off, dtype=np.uint64)
+        if part_role.ndim != 1 or len(part_role) != n_parts:
+            raise ValueError("part_role must hold one role per part")
+        if sample_off.ndim != 1 or len(sample_off) < 1:
+            raise ValueError("sample_off must hold n_samples + 1 offsets (at least one)")
+        n_samples = len(sample_off) - 1
+        spec = self._srow_spec(max_length, keep, skip_long, ignore_first, padding_side, pad_to_multiple_of, bos, eos, pad, ignore_index)
+        n_roles, ids, off, train = self._role_table(roles)
+        hit = _lib.SpecialHit()
+        out, cnt, refs = self._outs(12, 2)
+        held = part_role if n_parts else np.zeros(1, dtype=np.uint8)
+        rc = self._L.tk_encode_batch_sample_rows(self._h, *text, *dis, held.ctypes.data, sample_off.ctypes.data, n_samples, n_roles, ids.ctypes.data, off.ctypes.data,
+                                                 train.ctypes.data, ctypes.byref(spec), *refs, ctypes.byref(hit))
+        self._raise_for(rc, hit)
+        n_rows, n_segs = (int(x.value) for x in cnt)
+        L = int(spec.max_len)
+        n = n_rows * L
+        grid = [_take_u32(out[i], n).reshape(n_rows, L) for i in range(4)]
+        grid[1] = grid[1].view(np.int32)
+        return SampleRows(*grid, _take_u32(out[4], n_segs + 1), _take_u32(out[5], n_rows + 1), _take_u32(out[6], n_rows + 1), _take_u32(out[7], n_samples),
+                          _take_u64(out[8], n_samples), _take_u32(out[9], n_samples), _take_u32(out[10], n_samples), _take_u32(out[11], n_samples))
 
     # ------------------------------------------------------------------ training (tiktoken/_educational.py: bpe_train)
     def train_bpe_packed(self, blob: np.ndarray, doc_off: np.ndarray, vocab_size: int) -> tuple[np.ndarray, np.ndarray]:

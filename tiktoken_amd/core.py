@@ -367,6 +367,63 @@ class Encoding:
                                          disallowed_special=disallowed_special, keep=keep, padding_side=padding_side, pad_to_multiple_of=pad_to_multiple_of, bos=bos,
                                          eos=eos, pad=pad, ignore_index=ignore_index)
 
+    def encode_ordinary_batch_sample_rows(self, parts: Sequence[str], sample_off, part_role, roles: "Sequence[_tiktoken.Role]", max_length: int, *, keep: str = "head",
+                                          skip_long: bool = False, ignore_first: bool = False, bos: int | None = None, eos: int | None = None, pad: int = 0,
+                                          ignore_index: int = -100) -> "_tiktoken.SampleRows":
+        """The samples of `encode_ordinary_batch_samples`, several whole ones packed into every row of `max_length`: next-fit in the order
+        given (shuffle or sort the samples first: that order is the packing policy), an over-long sample cut at its head or tail -- or,
+        `skip_long`, left out --, in one GPU call.  Returns a `SampleRows`: `input_ids`, `labels` (not shifted), `segment_ids` and
+        `position_ids` (restarting at every sample) as [R, max_length] arrays, `cu_seqlens` / `row_seg` for variable-length attention, and
+        per sample `length`, `full_length`, `n_trained`, `sample_row`, `sample_col`.  `ignore_first`: the label of every sample's first
+        element is `ignore_index`, so that after the model's shift no sample is predicted from the one before it."""
+        blob, off = self._pack(parts)
+        return self._core_bpe.encode_batch_sample_rows_packed(blob, off, None, part_role=part_role, sample_off=sample_off, roles=roles, max_length=max_length, keep=keep,
+                                                              skip_long=skip_long, ignore_first=ignore_first, bos=bos, eos=eos, pad=pad, ignore_index=ignore_index)
+
+    def encode_batch_sample_rows(self, parts: Sequence[str], sample_off, part_role, roles: "Sequence[_tiktoken.Role]", max_length: int, *,
+                                 allowed_special: Literal["all"] | AbstractSet[str] = set(),  # noqa: B006
+                                 disallowed_special: Literal["all"] | Collection[str] = "all", keep: str = "head", skip_long: bool = False,
+                                 ignore_first: bool = False, bos: int | None = None, eos: int | None = None, pad: int = 0,
+                                 ignore_index: int = -100) -> "_tiktoken.SampleRows":
+        """`encode_ordinary_batch_sample_rows` with the special-token arguments of `encode`; the policy holds for all parts.  A part that
+        holds a disallowed special token raises `DisallowedSpecialError` whose `doc` is the part's index, `pos` the byte offset inside it."""
+        rows = dict(part_role=part_role, sample_off=sample_off, roles=roles, max_length=max_length, keep=keep, skip_long=skip_long, ignore_first=ignore_first, bos=bos,
+                    eos=eos, pad=pad, ignore_index=ignore_index)
+        allowed_special, disallowed_special = self._special_policy(allowed_special, disallowed_special)
+        if not disallowed_special:
+            blob, off = self._pack(parts)
+            return self._core_bpe.encode_batch_sample_rows_packed(blob, off, allowed_special, **rows)
+        if not isinstance(disallowed_special, frozenset):
+            disallowed_special = frozenset(disallowed_special)
+        blob, off, repaired = self._pack_repaired(parts)
+        if repaired or not all(t in self._special_tokens for t in disallowed_special):  # (as encode_batch_packed: the host's search)
+            for i, t in enumerate(parts):
+                if match := _special_token_regex(disallowed_special).search(t):
+                    raise _tiktoken.DisallowedSpecialError(i, len(t[: match.start()].encode("utf-8", "surrogatepass")), match.group())
+            return self._core_bpe.encode_batch_sample_rows_packed(blob, off, allowed_special, **rows)
+        return self._core_bpe.encode_batch_sample_rows_packed(blob, off, allowed_special, disallowed_special=disallowed_special, **rows)
+
+    def encode_chat_batch_rows(self, conversations: "Sequence[Sequence[tuple[str, str]]]", template: "dict[str, _tiktoken.Role]", max_length: int, *,
+                               allowed_special: Literal["all"] | AbstractSet[str] = set(),  # noqa: B006
+                               disallowed_special: Literal["all"] | Collection[str] = "all", keep: str = "head", skip_long: bool = False,
+                               ignore_first: bool = False, bos: int | None = None, eos: int | None = None, pad: int = 0,
+                               ignore_index: int = -100) -> "_tiktoken.SampleRows":
+        """`encode_chat_batch` with the conversations packed several to a row (`encode_batch_sample_rows`): the same flattening, the same
+        `DisallowedSpecialError` with `doc` = the index of the message among all messages, the same ValueError for an unknown role name."""
+        names = list(template)
+        index = {name: i for i, name in enumerate(names)}
+        parts, part_role, sample_off = [], [], [0]
+        for conv in conversations:
+            for role, text in conv:
+                if role not in index:
+                    raise ValueError(f"unknown role {role!r}: the template has {names}")
+                parts.append(text)
+                part_role.append(index[role])
+            sample_off.append(len(parts))
+        return self.encode_batch_sample_rows(parts, sample_off, part_role, [template[n] for n in names], max_length, allowed_special=allowed_special,
+                                             disallowed_special=disallowed_special, keep=keep, skip_long=skip_long, ignore_first=ignore_first, bos=bos, eos=eos, pad=pad,
+                                             ignore_index=ignore_index)
+
     def encode_ordinary_batch(self, text: list[str], *, num_threads: int = 8) -> list[list[int]]:
         """Encode a list of strings, ignoring special tokens (one GPU batch; `num_threads` is kept for
         signature compatibility)."""

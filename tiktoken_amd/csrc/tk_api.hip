@@ -25,6 +25,7 @@
 #include "tk_decode.h"
 #include "tk_offsets.h"
 #include "tk_padded.h"
+#include "tk_sample_rows.h"
 #include "tk_samples.h"
 #include "tk_rows.h"
 #include "tk_train.h"
@@ -280,6 +281,10 @@ struct tk_core {
     // n_trained of every sample; d_smp_cnt: the TK_SMP_WORDS report words, the role table, pstart and the per-sample figures a call counts in
     // until it is accepted; d_smp_in: part_role and sample_off of a host-text call.
     Buf d_smp, d_smp_row, d_smp_cnt, d_smp_in;
+    // Packed sample rows (tk_sample_rows.h), apart from everything above: d_srow: ids, labels, seg and pos of every position; d_srow_row: the
+    // per-sample and per-row arrays and cu_seqlens; d_srow_cnt: the report words, the role table and everything a call computes until it is
+    // accepted (the write pass reads pstart, c, f, row_sample and row_seg there); d_srow_in: part_role and sample_off of a host-text call.
+    Buf d_srow, d_srow_row, d_srow_cnt, d_srow_in;
     // Small calls (tk_k_small) do not take `mu`: the reference's normal use is several threads on one Encoding (core.py:175, a thread pool
     // over encode; lib.rs:232-238 keeps a regex per thread for it), and a small call needs nothing of the shared workspace -- a slot of its
     // own (page-locked text and result buffers the kernel reads and writes directly, merge scratch, a stream) is all.  A caller takes a
@@ -1692,9 +1697,9 @@ static int result_from_device(HostResult<T>& host, const void* d_src, uint64_t n
 // The result arrays of one call: fetch() makes each and fills it from the device, give() hands them all to the caller's out-pointers --
 // called once every fetch has succeeded; a bag that goes without it frees what it has fetched.
 struct ResultBag {
-    HostResult<uint8_t> host[6];
-    void* out[6];  // the caller's pointers, a T* each: set[i] knows which T
-    void (*set[6])(void*, void*);
+    HostResult<uint8_t> host[12];
+    void* out[12];  // the caller's pointers, a T* each: set[i] knows which T
+    void (*set[12])(void*, void*);
     int n = 0;
     template <class T>
     int fetch(T** o, const void* d_src, uint64_t count) {
@@ -3136,6 +3141,222 @@ extern "C" int tk_encode_batch_samples(tk_core* c, const uint8_t* utf8, const ui
             bag.give();
             *n_rows_out = v.n_rows;
             *width_out = v.width;
+            return TK_OK;
+        });
+}
+
+// ------------------------------------------------------------------------------------------
+// Packed sample rows (tk_sample_rows.h): a packed batch of parts on the device -> several whole samples per row of max_len, with labels,
+// the sample and the position of every element, and the segment boundaries.
+// ------------------------------------------------------------------------------------------
+static_assert(TK_SMP_SKIP_LONG == TK_SMPF_SKIP_LONG && TK_SMP_IGNORE_FIRST == TK_SMPF_IGNORE_FIRST, "tk_smp_spec flags");
+struct SrowView {  // device buffers of the core, valid until its next packed-samples call that succeeds
+    uint32_t *ids = nullptr, *seg = nullptr, *pos = nullptr, *cu = nullptr, *row_seg = nullptr, *row_sample = nullptr;
+    int32_t* labels = nullptr;
+    uint32_t *len = nullptr, *n_trained = nullptr, *sample_row = nullptr, *sample_col = nullptr;
+    uint64_t* full = nullptr;
+    uint64_t n_rows = 0, n_segs = 0, width = 0;
+};
+static int srow_refusal(int why) {
+    switch (why) {
+        case 11: return fail(TK_VALUE_ERROR, "packed sample rows are max_len wide: width_multiple must be 0");
+        case 12: return fail(TK_VALUE_ERROR, "packed sample rows are padded behind their samples: TK_SMP_LEFT does not apply");
+        default: return smp_refusal(why);
+    }
+}
+// What of a packed-samples call can be refused without looking at the batch (the host-text entry asks before it encodes anything).
+static int srow_check_spec(const tk_smp_spec* spec, const SmpRoles& roles, uint64_t n_tokens, uint64_t n_parts, uint64_t n_samples, TkSmp* p) {
+    if (!spec) return fail(TK_VALUE_ERROR, "null argument");
+    if (spec->flags & ~(TK_SMP_KEEP_TAIL | TK_SMP_LEFT | TK_SMP_SKIP_LONG | TK_SMP_IGNORE_FIRST)) return fail(TK_VALUE_ERROR, "tk_smp_spec: unknown flag");
+    if (roles.n_roles && (!roles.off || !roles.train)) return fail(TK_VALUE_ERROR, "null argument");
+    TRY(srow_refusal(tk_srow_shape(n_tokens, n_parts, n_samples, roles.n_roles, roles.off, spec->max_len, spec->width_multiple, spec->bos_id, spec->eos_id, spec->pad_id,
+                                   spec->ignore_index, spec->flags, p)));
+    if (roles.n_roles && roles.off[2 * roles.n_roles] && !roles.ids) return fail(TK_VALUE_ERROR, "null argument");
+    return TK_OK;
+}
+// srow_run: the caller holds c->mu.  The host waits twice, as smp_run does: for the report words -- what the count pass has to say about
+// the caller's arrays, the elements of all parts, R and the number of segments: the sizes of the outputs follow from them --, and at the
+// end.  A call that is refused has written into d_srow_cnt only: the previous result stays whole.
+static int srow_run(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n, const uint64_t* d_tok_off, uint64_t n_parts, const uint8_t* d_part_role,
+                    const uint64_t* d_sample_off, uint64_t n_samples, const SmpRoles& roles, const tk_smp_spec* spec, SrowView* out) {
+    TkSmp p;
+    TRY(srow_check_spec(spec, roles, n, n_parts, n_samples, &p));
+    // scratch: the report words | role_off, role_ids, role_train | pstart | full | c | f | len | n_trained | succ | two jump arrays | mark
+    // (then ex) | sample_row | sample_col | row_sample | row_pad (then row_seg)
+    const uint32_t n_off = 2 * roles.n_roles + 1, n_ids = roles.n_roles ? roles.off[2 * roles.n_roles] : 0;
+    const uint64_t ns = n_samples;
+    Carve cnt;
+    const uint64_t at_words = cnt.add(TK_SROW_WORDS * 8), at_off = cnt.add(n_off * 4ull), at_ids = cnt.add(n_ids * 4ull), at_train = cnt.add(roles.n_roles);
+    const uint64_t at_ps = cnt.add((n_parts + 1) * 8), at_full = cnt.add(ns * 8), at_c = cnt.add((ns + 1) * 8), at_f = cnt.add((ns + 1) * 8);
+    const uint64_t at_len = cnt.add(ns * 4), at_ntr = cnt.add(ns * 4), at_succ = cnt.add((ns + 1) * 4), at_j0 = cnt.add((ns + 1) * 4), at_j1 = cnt.add((ns + 1) * 4);
+    const uint64_t at_mark = cnt.add((ns + 1) * 4), at_srow = cnt.add(ns * 4), at_scol = cnt.add(ns * 4), at_rsmp = cnt.add((ns + 1) * 4), at_rpad = cnt.add((ns + 1) * 4);
+    TRY(ensure(c->d_srow_cnt, cnt.total));
+    const Buf& B = c->d_srow_cnt;
+    unsigned long long* words = carved<unsigned long long>(B, at_words);
+    uint64_t *pstart = carved<uint64_t>(B, at_ps), *full = carved<uint64_t>(B, at_full), *cs = carved<uint64_t>(B, at_c), *fs = carved<uint64_t>(B, at_f);
+    uint32_t *len = carved<uint32_t>(B, at_len), *ntr = carved<uint32_t>(B, at_ntr), *succ = carved<uint32_t>(B, at_succ), *mark = carved<uint32_t>(B, at_mark);
+    uint32_t* jump[2] = {carved<uint32_t>(B, at_j0), carved<uint32_t>(B, at_j1)};
+    uint32_t *srow = carved<uint32_t>(B, at_srow), *scol = carved<uint32_t>(B, at_scol), *rsmp = carved<uint32_t>(B, at_rsmp), *rpad = carved<uint32_t>(B, at_rpad);
+    const TkSmpTable tab{carved<uint32_t>(B, at_off), carved<uint32_t>(B, at_ids), carved<uint8_t>(B, at_train), n_ids};
+    std::vector<uint8_t> table(at_ps - at_off, 0);  // (the table as it lies on the device, from at_off on; role_off of no roles: one 0)
+    if (roles.n_roles) {
+        memcpy(table.data(), roles.off, n_off * 4ull);
+        if (n_ids) memcpy(table.data() + (at_ids - at_off), roles.ids, n_ids * 4ull);
+        memcpy(table.data() + (at_train - at_off), roles.train, roles.n_roles);
+    }
+    HIPCHK(hipMemcpyAsync(carved<uint8_t>(B, at_off), table.data(), table.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(words, 0xFF, 8 * (TK_SMP_BAD_ROLE + 1), s));  // (the three words that keep the lowest offender: all ones = none)
+    HIPCHK(hipMemsetAsync(words + TK_SMP_TOTAL, 0, 8 * (TK_SROW_WORDS - TK_SMP_TOTAL), s));
+    const uint64_t n_entries = std::max(n_parts, n_samples) + 1;
+    const uint32_t g_smp = grid_for(ns + 1, 256, 4096);
+    TRY(timed(c, s, "tk_k_smp_count", [&] {
+        hipLaunchKernelGGL(tk_k_smp_count, dim3(grid_for(n_entries, 256, 4096)), dim3(256), 0, s, d_tok_off, d_sample_off, d_part_role, tab, p, pstart, words);
+    }));
+    TRY(timed(c, s, "tk_k_smp_scan", [&] { hipLaunchKernelGGL(tk_k_smp_scan, dim3(1), dim3(1024), 0, s, pstart, n_parts, words); }));
+    if (ns) {
+        TRY(timed(c, s, "tk_k_smp_samples", [&] {
+            hipLaunchKernelGGL(tk_k_smp_samples, dim3(g_smp), dim3(256), 0, s, d_sample_off, d_part_role, pstart, tab, p, full, len, ntr, words);
+        }));
+        TRY(timed(c, s, "tk_k_srow_plen", [&] {
+            hipLaunchKernelGGL(tk_k_srow_plen, dim3(g_smp), dim3(256), 0, s, d_tok_off, d_sample_off, d_part_role, pstart, tab, p, full, len, ntr, cs, fs, words);
+        }));
+    }
+    TRY(timed(c, s, "tk_k_srow_sums", [&] { hipLaunchKernelGGL(tk_k_srow_sums, dim3(1), dim3(1024), 0, s, cs, fs, ns, words); }));
+    TRY(timed(c, s, "tk_k_srow_succ", [&] { hipLaunchKernelGGL(tk_k_srow_succ, dim3(g_smp), dim3(256), 0, s, cs, fs, ns, p.max_len, succ, mark, words); }));
+    const uint32_t rounds = tk_srow_rounds(ns);
+    for (uint32_t k = 0; k < rounds; ++k) {
+        const uint32_t* jin = k ? jump[(k - 1) & 1] : succ;
+        TRY(timed(c, s, "tk_k_srow_double", [&] { hipLaunchKernelGGL(tk_k_srow_double, dim3(g_smp), dim3(256), 0, s, jin, jump[k & 1], mark, ns, words); }));
+    }
+    TRY(timed(c, s, "tk_k_srow_rows", [&] { hipLaunchKernelGGL(tk_k_srow_rows, dim3(1), dim3(1024), 0, s, mark, ns, words); }));
+    TRY(timed(c, s, "tk_k_srow_place", [&] { hipLaunchKernelGGL(tk_k_srow_place, dim3(g_smp), dim3(256), 0, s, mark, cs, succ, ns, p.max_len, srow, scol, rsmp, rpad, words); }));
+    TRY(timed(c, s, "tk_k_srow_segs", [&] { hipLaunchKernelGGL(tk_k_srow_segs, dim3(1), dim3(1024), 0, s, mark, fs, rsmp, ns, rpad, words); }));
+    unsigned long long got[TK_SROW_WORDS];
+    TRY(report_read(words, got, TK_SROW_WORDS, s));  // (waits for the table's copy too: `table` may go)
+    TRY(offsets_refusal(got[TK_SMP_BAD_SOFF], "sample_off", "sample", "n_parts"));
+    if (got[TK_SMP_BAD_ROLE] != ~0ull) return fail(TK_VALUE_ERROR, "part_role must be below n_roles: part " + std::to_string(got[TK_SMP_BAD_ROLE]) + " has no such role");
+    TRY(srow_refusal(tk_srow_size(&p, got[TK_SMP_TOTAL], got[TK_SROW_R])));
+    const uint64_t R = p.R, n_segs = got[TK_SROW_NSEGS], N = R * p.W, n8 = (N + 7) & ~7ull, nb = (N + TK_DEC_BLOCK - 1) / TK_DEC_BLOCK;  // (n8: room for whole lanes of eight)
+    Carve pos, row;
+    const uint64_t at_out_ids = pos.add(n8 * 4), at_labels = pos.add(n8 * 4), at_seg = pos.add(n8 * 4), at_pos = pos.add(n8 * 4);
+    const uint64_t at_out_full = row.add(ns * 8), at_out_len = row.add(ns * 4), at_out_ntr = row.add(ns * 4), at_out_srow = row.add(ns * 4), at_out_scol = row.add(ns * 4);
+    const uint64_t at_out_rsmp = row.add((R + 1) * 4), at_out_rseg = row.add((R + 1) * 4), at_cu = row.add((n_segs + 1) * 4);
+    TRY(ensure(c->d_srow, pos.total));
+    TRY(ensure(c->d_srow_row, row.total));
+    out->ids = carved<uint32_t>(c->d_srow, at_out_ids);
+    out->labels = carved<int32_t>(c->d_srow, at_labels);
+    out->seg = carved<uint32_t>(c->d_srow, at_seg);
+    out->pos = carved<uint32_t>(c->d_srow, at_pos);
+    out->full = carved<uint64_t>(c->d_srow_row, at_out_full);
+    out->len = carved<uint32_t>(c->d_srow_row, at_out_len);
+    out->n_trained = carved<uint32_t>(c->d_srow_row, at_out_ntr);
+    out->sample_row = carved<uint32_t>(c->d_srow_row, at_out_srow);
+    out->sample_col = carved<uint32_t>(c->d_srow_row, at_out_scol);
+    out->row_sample = carved<uint32_t>(c->d_srow_row, at_out_rsmp);
+    out->row_seg = carved<uint32_t>(c->d_srow_row, at_out_rseg);
+    out->cu = carved<uint32_t>(c->d_srow_row, at_cu);
+    out->n_rows = R;
+    out->n_segs = n_segs;
+    out->width = p.W;
+    if (ns) {
+        HIPCHK(hipMemcpyAsync(out->full, full, ns * 8, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(out->len, len, ns * 4, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(out->n_trained, ntr, ns * 4, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(out->sample_row, srow, ns * 4, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(out->sample_col, scol, ns * 4, hipMemcpyDeviceToDevice, s));
+    }
+    HIPCHK(hipMemcpyAsync(out->row_sample, rsmp, (R + 1) * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(out->row_seg, rpad, (R + 1) * 4, hipMemcpyDeviceToDevice, s));
+    if (nb) {
+        const TkSrowInPtr rw{cs, fs, rsmp, rpad};
+        TRY(timed(c, s, "tk_k_srow_write", [&] {
+            hipLaunchKernelGGL(tk_k_srow_write, dim3((uint32_t)nb), dim3(256), 0, s, d_tok, d_tok_off, d_sample_off, d_part_role, pstart, rw, tab, p, (uint32_t)n_segs, out->ids,
+                               out->labels, out->seg, out->pos, out->cu);
+        }));
+    } else {
+        HIPCHK(hipMemsetAsync(out->cu, 0, 4, s));  // (no row: cu_seqlens is its closing entry, R * L = 0)
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    return TK_OK;
+}
+
+extern "C" int tk_pack_samples_device(tk_core* c, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_parts, const void* d_part_role,
+                                      const void* d_sample_off, uint64_t n_samples, uint32_t n_roles, const uint32_t* role_ids, const uint32_t* role_off,
+                                      const uint8_t* role_train, const tk_smp_spec* spec, void* stream, const uint32_t** d_ids_out, const int32_t** d_labels_out,
+                                      const uint32_t** d_seg_out, const uint32_t** d_pos_out, const uint32_t** d_cu_seqlens_out, const uint32_t** d_row_seg_out,
+                                      const uint32_t** d_row_sample_out, const uint32_t** d_len_out, const uint64_t** d_full_len_out, const uint32_t** d_n_trained_out,
+                                      const uint32_t** d_sample_row_out, const uint32_t** d_sample_col_out, uint64_t* n_rows_out, uint64_t* n_segs_out) {
+    SrowView v;
+    const SmpRoles roles{n_roles, role_ids, role_off, role_train};
+    TRY(device_pass(c, d_tok_off && d_sample_off && (d_tokens || !n_tokens) && (d_part_role || !n_parts) && spec, stream, [&](hipStream_t s) {
+        return srow_run(c, s, (const uint32_t*)d_tokens, n_tokens, (const uint64_t*)d_tok_off, n_parts, (const uint8_t*)d_part_role, (const uint64_t*)d_sample_off, n_samples,
+                        roles, spec, &v);
+    }));
+    if (d_ids_out) *d_ids_out = v.ids;
+    if (d_labels_out) *d_labels_out = v.labels;
+    if (d_seg_out) *d_seg_out = v.seg;
+    if (d_pos_out) *d_pos_out = v.pos;
+    if (d_cu_seqlens_out) *d_cu_seqlens_out = v.cu;
+    if (d_row_seg_out) *d_row_seg_out = v.row_seg;
+    if (d_row_sample_out) *d_row_sample_out = v.row_sample;
+    if (d_len_out) *d_len_out = v.len;
+    if (d_full_len_out) *d_full_len_out = v.full;
+    if (d_n_trained_out) *d_n_trained_out = v.n_trained;
+    if (d_sample_row_out) *d_sample_row_out = v.sample_row;
+    if (d_sample_col_out) *d_sample_col_out = v.sample_col;
+    if (n_rows_out) *n_rows_out = v.n_rows;
+    if (n_segs_out) *n_segs_out = v.n_segs;
+    return TK_OK;
+}
+
+// tk_encode_batch (tk_encode_batch_checked with disallowed ids) over the parts' text with the samples packed into rows from the tokens it
+// has just produced: the passes run over the ids while they are still on the device, and only the row arrays travel back.
+extern "C" int tk_encode_batch_sample_rows(tk_core* c, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_parts, int use_special, const uint32_t* allowed_ids,
+                                           uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed, const uint8_t* part_role, const uint64_t* sample_off,
+                                           uint64_t n_samples, uint32_t n_roles, const uint32_t* role_ids, const uint32_t* role_off, const uint8_t* role_train,
+                                           const tk_smp_spec* spec, uint32_t** ids_out, int32_t** labels_out, uint32_t** seg_out, uint32_t** pos_out,
+                                           uint32_t** cu_seqlens_out, uint32_t** row_seg_out, uint32_t** row_sample_out, uint32_t** len_out, uint64_t** full_len_out,
+                                           uint32_t** n_trained_out, uint32_t** sample_row_out, uint32_t** sample_col_out, uint64_t* n_rows_out, uint64_t* n_segs_out,
+                                           tk_special_hit* hit) {
+    SrowView v;
+    const SmpRoles roles{n_roles, role_ids, role_off, role_train};
+    return encode_batch_pass(
+        c, utf8, doc_off, n_parts, use_special, allowed_ids, n_allowed, disallowed_ids, n_disallowed, hit,
+        spec && sample_off && (part_role || !n_parts) && ids_out && labels_out && seg_out && pos_out && cu_seqlens_out && row_seg_out && row_sample_out && len_out &&
+            full_len_out && n_trained_out && sample_row_out && sample_col_out && n_rows_out && n_segs_out,
+        [&] {  // (before the encode, not after it)
+            TkSmp p;
+            return srow_check_spec(spec, roles, 0, n_parts, n_samples, &p);
+        },
+        [&](uint64_t n) {
+            Carve in;
+            const uint64_t at_role = in.add(n_parts), at_so = in.add((n_samples + 1) * 8);
+            TRY(ensure(c->d_srow_in, in.total));
+            uint8_t* d_role = carved<uint8_t>(c->d_srow_in, at_role);
+            uint64_t* d_so = carved<uint64_t>(c->d_srow_in, at_so);
+            if (n_parts) HIPCHK(hipMemcpyAsync(d_role, part_role, n_parts, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(d_so, sample_off, (n_samples + 1) * 8, hipMemcpyHostToDevice, c->stream));
+            return srow_run(c, c->stream, c->out_tokens.as<uint32_t>(), n, c->out_tok_off.as<uint64_t>(), n_parts, d_role, d_so, n_samples, roles, spec, &v);
+        },
+        [&](uint64_t) -> int {
+            const uint64_t N = v.n_rows * v.width;
+            ResultBag bag;
+            TRY(bag.fetch(ids_out, v.ids, N));
+            TRY(bag.fetch(labels_out, v.labels, N));
+            TRY(bag.fetch(seg_out, v.seg, N));
+            TRY(bag.fetch(pos_out, v.pos, N));
+            TRY(bag.fetch(cu_seqlens_out, v.cu, v.n_segs + 1));
+            TRY(bag.fetch(row_seg_out, v.row_seg, v.n_rows + 1));
+            TRY(bag.fetch(row_sample_out, v.row_sample, v.n_rows + 1));
+            TRY(bag.fetch(len_out, v.len, n_samples));
+            TRY(bag.fetch(full_len_out, v.full, n_samples));
+            TRY(bag.fetch(n_trained_out, v.n_trained, n_samples));
+            TRY(bag.fetch(sample_row_out, v.sample_row, n_samples));
+            TRY(bag.fetch(sample_col_out, v.sample_col, n_samples));
+            bag.give();
+            *n_rows_out = v.n_rows;
+            *n_segs_out = v.n_segs;
             return TK_OK;
         });
 }
