@@ -244,6 +244,7 @@ struct tk_core {
     bool find_on = false;
     uint64_t find_hit = ~0ull;
     uint64_t st_find_launches = 0;  // launches of that scan since the core was made
+    uint64_t st_mark_launches = 0;  // launches of the marking pair (tk_k_spec_cand + tk_k_spec_resolve) since the core was made
     // Streams of the back stages of a multi-chunk batch.  HIP multiplexes its streams onto a few hardware queues (four by default), and
     // two streams that share a queue run one after the other: the back stage of chunk k, queued behind the front kernel of chunk
     // k + 1, then waits for that kernel to END instead of running beside it (seen in the kernel timeline of round 4: no overlap at all).
@@ -982,6 +983,7 @@ static int stage_front(tk_core* c, WorkSet& w, ChunkJob& job, hipStream_t s, con
                 hipLaunchKernelGGL(tk_k_spec_resolve, dim3(grid_for(nwords, 256, 65536)), dim3(256), 0, s, T, d_text, n, allowed, f.docb, cand,
                                    c->spec_max_len, f.ss, f.si, f.brk);
             }));
+            c->st_mark_launches += 1;
         }
         if (job.find) {
             // (a match ends inside the chunk -- tk_special_at asks for pos + len <= n -- and inside its document: the text behind the chunk, the
@@ -4010,6 +4012,7 @@ extern "C" uint64_t tk_stat(tk_core* c, const char* name) {
     if (k == "back_streams") return (uint64_t)c->n_back;  // streams found to run beside the front stream (0: no multi-chunk batch yet)
     if (k == "resynced") return c->st_resynced;  // batches repeated because a deferred tile gave up while the host was not waiting (stage_deferred)
     if (k == "spec_find_launches") return c->st_find_launches;  // launches of the disallowed scan (tk_k_spec_find) since the core was made: one per chunk of a checked call
+    if (k == "spec_mark_launches") return c->st_mark_launches;  // launches of the pair that marks allowed special tokens (tk_k_spec_cand + tk_k_spec_resolve): one per chunk that has them
     if (k == "regrown") return c->st_regrown;  // batches repeated with a larger miss data since the core was made (encode_device_locked)
     if (k == "workspace_bytes") {             // device memory of the work sets (everything but the text, the tables and the outputs)
         uint64_t t = 0;

@@ -147,72 +147,18 @@ __global__ void tk_k_spec_find(TkTables T, const uint8_t* __restrict__ text, uin
     }
 }
 
-// Resolve overlapping candidates exactly as a left-to-right search would (src/lib.rs:389-401,432):
-// a candidate is taken iff the greedy non-overlapping walk from the head of its overlap cluster
-// lands on it.  (Earlier candidates are looked for in the 64 bits of the bitmap before the position -- two loads, not one per bit;
-// special tokens of 66 bytes and more take the walk bit by bit.)
+// Resolve overlapping candidates exactly as a left-to-right search would (src/lib.rs:389-401,432): tk_spec_resolve_one (tk_special.h)
+// for every candidate, one thread per 32-position word of the candidate bitmap (candidates are sparse).
+struct TkAtomicOrBit {
+    __device__ __forceinline__ void operator()(uint32_t* bm, uint64_t word, uint32_t mask) const { atomicOr(&bm[word], mask); }
+};
 __global__ void tk_k_spec_resolve(TkTables T, const uint8_t* __restrict__ text, uint64_t n, const uint8_t* __restrict__ allowed,
                                   const uint32_t* __restrict__ docb, const uint32_t* __restrict__ cand, uint32_t max_len,
                                   uint32_t* __restrict__ spec_start, uint32_t* __restrict__ spec_in, uint32_t* __restrict__ brk) {
-    // one thread per 32-position word of the candidate bitmap (candidates are sparse)
     const uint64_t nwords = (n + 31) / 32;
     for (uint64_t wi = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; wi < nwords; wi += (uint64_t)gridDim.x * blockDim.x)
-      for (uint32_t cw = cand[wi]; cw; cw &= cw - 1) {
-        const uint64_t pos = wi * 32 + (uint32_t)(__ffs((int)cw) - 1);
-        uint32_t idx;
-        // head of the overlap cluster: walk left while some earlier candidate's span covers `h`
-        uint64_t h = pos;
-        for (;;) {
-            bool moved = false;
-            uint64_t lo = h >= (uint64_t)(max_len - 1) ? h - (max_len - 1) : 0;
-            if (max_len <= 65u && h >= 64u) {
-                uint64_t before = tk_bits64(cand, h - 64u);          // candidates at h - 64 .. h - 1 (bit 63 = h - 1)
-                before = h > lo ? (before & (~0ull << (64u - (uint32_t)(h - lo)))) : 0ull;  // only those at lo .. h - 1
-                while (before) {  // nearest first
-                    const uint32_t b = 63u - (uint32_t)__clzll((long long)before);
-                    before &= ~(1ull << b);
-                    const uint64_t j = h - 64u + b;
-                    if (j + tk_special_at(T, text, j, n, allowed, docb, &idx) > h) {
-                        h = j;
-                        moved = true;
-                        break;
-                    }
-                }
-            } else {
-                for (uint64_t j = h; j-- > lo;) {
-                    if (tk_bit(cand, j) && j + tk_special_at(T, text, j, n, allowed, docb, &idx) > h) {
-                        h = j;
-                        moved = true;
-                        break;
-                    }
-                }
-            }
-            if (!moved) break;
-        }
-        // greedy walk from the head
-        uint64_t cur = h;
-        bool taken = false;
-        while (cur <= pos) {
-            if (cur == pos) {
-                taken = true;
-                break;
-            }
-            uint64_t nx = cur + tk_special_at(T, text, cur, n, allowed, docb, &idx);
-            while (nx <= pos && !tk_bit(cand, nx)) ++nx;
-            cur = nx;
-        }
-        if (!taken) continue;
-        uint32_t len = tk_special_at(T, text, pos, n, allowed, docb, &idx);
-        atomicOr(&spec_start[pos >> 5], 1u << (pos & 31));
-        atomicOr(&brk[pos >> 5], 1u << (pos & 31));
-        for (uint64_t a = pos + 1, b = pos + len; a < b;) {  // the token's interior, a word of the bitmap at a time
-            const uint64_t we = (a | 31u) + 1u, hi = we < b ? we : b;
-            const uint32_t cnt = (uint32_t)(hi - a);
-            atomicOr(&spec_in[a >> 5], (cnt >= 32u ? 0xFFFFFFFFu : ((1u << cnt) - 1u)) << (a & 31u));
-            a = hi;
-        }
-        if (pos + len < n) atomicOr(&brk[(pos + len) >> 5], 1u << ((pos + len) & 31));
-    }
+      for (uint32_t cw = cand[wi]; cw; cw &= cw - 1)
+        tk_spec_resolve_one(T, text, n, allowed, docb, cand, max_len, wi * 32 + tk_ctz32(cw), spec_start, spec_in, brk, TkAtomicOrBit());
 }
 
 // id of the special token whose bytes are text[pos..pos+len)

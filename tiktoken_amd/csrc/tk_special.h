@@ -122,6 +122,73 @@ TK_HD uint64_t tk_spec_find16(const TkTables& T, const uint8_t* __restrict__ tex
     return ~0ull;
 }
 
+// The resolving pass's share of one candidate (tk_k_spec_resolve): overlapping candidates are resolved exactly as a left-to-right search
+// would (src/lib.rs:389-401,432) -- the candidate at `pos` is taken iff the greedy non-overlapping walk from the head of its overlap
+// cluster lands on it.  A taken candidate is marked: its first byte in spec_start and brk, its other bytes in spec_in, the byte behind
+// it (inside the text) in brk.  `cand`: the candidates of tk_k_spec_cand, readable two words past a position's; max_len: the longest
+// registered special token.  Marks go through or_bit(bitmap, word, mask): an atomic OR on the device, |= on the host.
+// (Earlier candidates are looked for in the 64 bits of the bitmap before the position -- two loads, not one per bit; with special tokens
+// of 66 bytes and more the walk goes bit by bit.)  The head walk asks about every earlier candidate of the cluster: a cluster of L
+// overlapping candidates costs about L * L / 2 calls of tk_special_at.
+template <class OrBit>
+TK_HD void tk_spec_resolve_one(const TkTables& T, const uint8_t* __restrict__ text, uint64_t n, const uint8_t* __restrict__ allowed,
+                               const uint32_t* __restrict__ docb, const uint32_t* __restrict__ cand, uint32_t max_len, uint64_t pos,
+                               uint32_t* __restrict__ spec_start, uint32_t* __restrict__ spec_in, uint32_t* __restrict__ brk, OrBit or_bit) {
+    uint32_t idx;
+    // head of the overlap cluster: walk left while some earlier candidate's span covers `h`
+    uint64_t h = pos;
+    for (;;) {
+        bool moved = false;
+        uint64_t lo = h >= (uint64_t)(max_len - 1) ? h - (max_len - 1) : 0;
+        if (max_len <= 65u && h >= 64u) {
+            uint64_t before = tk_bits64(cand, h - 64u);          // candidates at h - 64 .. h - 1 (bit 63 = h - 1)
+            before = h > lo ? (before & (~0ull << (64u - (uint32_t)(h - lo)))) : 0ull;  // only those at lo .. h - 1
+            while (before) {  // nearest first
+                const uint32_t b = 63u - tk_clz64(before);
+                before &= ~(1ull << b);
+                const uint64_t j = h - 64u + b;
+                if (j + tk_special_at(T, text, j, n, allowed, docb, &idx) > h) {
+                    h = j;
+                    moved = true;
+                    break;
+                }
+            }
+        } else {
+            for (uint64_t j = h; j-- > lo;) {
+                if (tk_bit(cand, j) && j + tk_special_at(T, text, j, n, allowed, docb, &idx) > h) {
+                    h = j;
+                    moved = true;
+                    break;
+                }
+            }
+        }
+        if (!moved) break;
+    }
+    // greedy walk from the head
+    uint64_t cur = h;
+    bool taken = false;
+    while (cur <= pos) {
+        if (cur == pos) {
+            taken = true;
+            break;
+        }
+        uint64_t nx = cur + tk_special_at(T, text, cur, n, allowed, docb, &idx);
+        while (nx <= pos && !tk_bit(cand, nx)) ++nx;
+        cur = nx;
+    }
+    if (!taken) return;
+    uint32_t len = tk_special_at(T, text, pos, n, allowed, docb, &idx);
+    or_bit(spec_start, pos >> 5, 1u << (pos & 31));
+    or_bit(brk, pos >> 5, 1u << (pos & 31));
+    for (uint64_t a = pos + 1, b = pos + len; a < b;) {  // the token's interior, a word of the bitmap at a time
+        const uint64_t we = (a | 31u) + 1u, hi = we < b ? we : b;
+        const uint32_t cnt = (uint32_t)(hi - a);
+        or_bit(spec_in, a >> 5, (cnt >= 32u ? 0xFFFFFFFFu : ((1u << cnt) - 1u)) << (a & 31u));
+        a = hi;
+    }
+    if (pos + len < n) or_bit(brk, (pos + len) >> 5, 1u << ((pos + len) & 31));
+}
+
 // (host) What the functions above ask of TkTables beyond the host tables' arrays: every special token's head (T.spec_head points at a copy of
 // `head` wherever the caller keeps it), the set of first bytes in both forms, the set of second bytes.
 static inline void tk_spec_tables(const TkHostTables& H, std::vector<uint32_t>& head, TkTables& D) {
