@@ -374,6 +374,52 @@ int tk_encode_batch_sample_rows(tk_core* core, const uint8_t* utf8, const uint64
                                 const tk_smp_spec* spec, uint32_t** ids_out, int32_t** labels_out, uint32_t** seg_out, uint32_t** pos_out, uint32_t** cu_seqlens_out,
                                 uint32_t** row_seg_out, uint32_t** row_sample_out, uint32_t** len_out, uint64_t** full_len_out, uint32_t** n_trained_out,
                                 uint32_t** sample_row_out, uint32_t** sample_col_out, uint64_t* n_rows_out, uint64_t* n_segs_out, tk_special_hit* hit);
+/* Decoding id matrices: what a generation, evaluation or reranking loop hands back -- an id matrix [R, W] in HBM -- -> the text of every
+ * row.  Replaces nothing in the reference: it is the host loop of the reference's users (the matrix copied to the host, every row cut at its
+ * first eos and stripped of pad and special ids in Python, the lists handed to decode_batch; elsewhere `batch_decode(ids,
+ * skip_special_tokens=True)`) -- here one call on ids that are on the device anyway.  The decode-side counterpart of tk_pad_batch_device.
+ * The rule.  Input: ids holds R rows of W columns, element (r, c) at ids[r * ld + c] with ld >= W, so a column slice of a wider matrix
+ *  needs no copy; its elements are uint32, with TK_DROWS_I32 int32, with TK_DROWS_I64 int64.  begin / end (uint32[R] each, may be null: 0
+ *  and W).  Up to 16 stop_ids and up to 16 skip_ids (uint32) in the spec.
+ *  Live range of row r.  stop_col[r] = the least c in [begin[r], end[r]) whose id is in stop_ids, or end[r] when there is none; columns
+ *   before begin[r] are never looked at.  The live range is [begin[r], stop_col[r]), with TK_DROWS_KEEP_STOP also stop_col[r] itself when a
+ *   stop was found.  stop_col[r] < end[r] says that the row finished.
+ *  Kept tokens.  A live column is kept unless its id is in skip_ids or -- TK_DROWS_SKIP_SPECIAL -- is a special token of the vocabulary.
+ *   The stop test comes first: a kept stop id then passes the skip test like any other id.
+ *  Output.  tokens uint32[K]: the kept ids of all rows back to back, in row and column order; tok_off uint64[R + 1]: each row's place in
+ *   tokens; n_kept uint32[R] and stop_col uint32[R]; bytes and byte_off uint64[R + 1]: what tk_decode_batch_device makes of (tokens,
+ *   tok_off), by the same kernels.  R == 0, W == 0 and K == 0 are legal.
+ *  TK_VALUE_ERROR: more than 16 stop or skip ids; both dtype flags; an unknown flag; ld < W; R >= 2^32 - 1, W >= 2^32 or K >= 2^32; a
+ *   matrix of 2^60 elements or more; a row with begin > end or end > W (checked on the device before anything is indexed with either;
+ *   the message names the first such row).  TK_KEY_ERROR: a kept column whose id has no decode entry -- a negative element, or one at
+ *   or above 2^32 in a 64-bit matrix, is such an id; in no list either --: the reference's "Invalid token for decoding: N", then the row and
+ *   column of the first such element in row-major order.  Ids outside the live range are never judged, and skipped ids are not either: a
+ *   pad id outside the vocabulary is legal in skip_ids.  TK_UNSUPPORTED where tk_decode_batch returns it: ids at or above 2^26.
+ *   Every refusal is found before any output is written: a refused call leaves the previous result whole.  No kernel reads outside the
+ *   (R - 1) * ld + W elements of the matrix, whatever begin and end hold.  One device per call: a group has no such entry.
+ *  NOT built: uint16 matrices; UTF-8 repair on the device (errors= stays the caller's step per row); token spans of a matrix (feed tokens
+ *   and tok_off to tk_token_spans_device); streaming. */
+#define TK_DROWS_KEEP_STOP 1u    /* the stop id that ends a row belongs to it */
+#define TK_DROWS_SKIP_SPECIAL 2u /* special tokens are dropped as if they were in skip_ids */
+#define TK_DROWS_I32 4u          /* the matrix holds int32 */
+#define TK_DROWS_I64 8u          /* the matrix holds int64 */
+typedef struct {
+    uint32_t flags, n_stop, n_skip;
+    uint32_t stop_ids[16], skip_ids[16];
+} tk_drows_spec;
+/* Device pointers in (d_ids; d_begin / d_end uint32[n_rows] or null), device pointers out: *d_tokens_out .. *d_stop_col_out are buffers
+ * of the core, valid until its next decode-rows call that succeeds (a refused call writes into none of them) and apart from every other
+ * entry's buffers; *d_bytes_out and *d_byte_off_out are the decode buffers of tk_decode_batch_device, valid until the core's next decode
+ * call.  *n_tokens_out: K.  `stream`: a hipStream_t or null (the core's); the call returns when the bytes are there. */
+int tk_decode_rows_device(tk_core* core, const void* d_ids, uint64_t n_rows, uint64_t width, uint64_t ld, const void* d_begin, const void* d_end,
+                          const tk_drows_spec* spec, void* stream, const uint32_t** d_tokens_out, const uint64_t** d_tok_off_out,
+                          const uint32_t** d_n_kept_out, const uint32_t** d_stop_col_out, const uint8_t** d_bytes_out,
+                          const uint64_t** d_byte_off_out, uint64_t* n_tokens_out, uint64_t* n_bytes_out);
+/* The same for a matrix in host memory ((n_rows - 1) * ld + width elements travel to the device as they lie): host arrays out,
+ * library-owned (tk_free), sized as above. */
+int tk_decode_rows(tk_core* core, const void* ids, uint64_t n_rows, uint64_t width, uint64_t ld, const uint32_t* begin, const uint32_t* end,
+                   const tk_drows_spec* spec, uint32_t** tokens_out, uint64_t** tok_off_out, uint32_t** n_kept_out, uint32_t** stop_col_out,
+                   uint8_t** bytes_out, uint64_t** byte_off_out, uint64_t* n_tokens_out, uint64_t* n_bytes_out);
 /* bpe_train(data, vocab_size, pat_str, visualise=None)                      tiktoken/_educational.py:119-185
  * Training a vocabulary: the merges the reference's educational trainer makes on the same text -- the same pairs in the same order -- for a
  * packed batch of documents, under the core's pat_str (stock scanners or the generic engine).  The core's ranks and special tokens play

@@ -51,6 +51,14 @@ class SmpSpec(ctypes.Structure):
 SMP_KEEP_TAIL, SMP_LEFT, SMP_SKIP_LONG, SMP_IGNORE_FIRST = 1, 2, 4, 8
 
 
+class DrowsSpec(ctypes.Structure):
+    """tk_drows_spec: how the rows of an id matrix are trimmed before they are decoded (include/tiktoken_amd.h)."""
+    _fields_ = [("flags", ctypes.c_uint32), ("n_stop", ctypes.c_uint32), ("n_skip", ctypes.c_uint32), ("stop_ids", ctypes.c_uint32 * 16), ("skip_ids", ctypes.c_uint32 * 16)]
+
+
+DROWS_KEEP_STOP, DROWS_SKIP_SPECIAL, DROWS_I32, DROWS_I64 = 1, 2, 4, 8
+
+
 def build(force: bool = False) -> str:
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     if force or not os.path.exists(_SO):
@@ -128,6 +136,11 @@ def lib() -> ctypes.CDLL:
             L.tk_encode_batch_sample_rows.restype = i32
             L.tk_encode_batch_sample_rows.argtypes = [vp, vp, vp, u64, i32, vp, u64, vp, u64, vp, vp, u64, u32, vp, vp, vp, P(SmpSpec), *[P(vp)] * 12, P(u64), P(u64),
                                                       P(SpecialHit)]
+        if hasattr(L, "tk_decode_rows_device"):  # (absent from older builds selected through $TIKTOKEN_AMD_LIB)
+            L.tk_decode_rows_device.restype = i32
+            L.tk_decode_rows_device.argtypes = [vp, vp, u64, u64, u64, vp, vp, P(DrowsSpec), vp, *[P(vp)] * 6, P(u64), P(u64)]
+            L.tk_decode_rows.restype = i32
+            L.tk_decode_rows.argtypes = [vp, vp, u64, u64, u64, vp, vp, P(DrowsSpec), *[P(vp)] * 6, P(u64), P(u64)]
         L.tk_decode_single_token_bytes.restype = i32
         L.tk_decode_single_token_bytes.argtypes = [vp, u32, P(vp), P(u64)]
         L.tk_n_tokens.restype = u64

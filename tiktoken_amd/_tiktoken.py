@@ -7,7 +7,8 @@ Same constructor and the same eleven methods, same exception types.  Two additiv
 `encode_batch_spans_packed` give, for whole batches, where every token starts in its document (bytes and chars); `pack_rows_device` and
 `encode_batch_rows_packed` cut a batch into fixed-length training rows with document ids, positions and cu_seqlens; `pad_batch_device` and
 `encode_batch_padded_packed` give one padded row per document (or overlapping windows) with an attention mask; `assemble_samples_device` and
-`encode_batch_samples_packed` join the parts of supervised samples with their roles' ids into rows with labels; `train_bpe_packed`
+`encode_batch_samples_packed` join the parts of supervised samples with their roles' ids into rows with labels; `decode_rows_device` and
+`decode_rows_packed` decode the rows of an id matrix, each cut at its first stop id and stripped of skipped and special ids; `train_bpe_packed`
 trains a vocabulary: the merges of the reference's educational `bpe_train`, made on the device.  With `disallowed_special` the batch
 calls also search the text for those special tokens, on the device, and raise `DisallowedSpecialError`.
 """
@@ -273,6 +274,33 @@ class SampleRowsDevice(NamedTuple):
     sample_col: int
     n_rows: int
     n_segs: int
+
+
+class DecodedRows(NamedTuple):
+    """The rows of an id matrix, trimmed and decoded (tk_decode_rows; the rule: include/tiktoken_amd.h).  Row r is live from begin[r] to its
+    first stop id, stop_col[r] (end[r] when it has none, so stop_col[r] < end[r] says that the row finished); of the live ids those in
+    `skip` (and, with skip_special, the special tokens) are dropped, the n_kept[r] others are tokens[tok_off[r] : tok_off[r + 1]] and decode
+    to data[byte_off[r] : byte_off[r + 1]]."""
+    data: np.ndarray  # uint8: the rows' bytes back to back
+    byte_off: np.ndarray  # uint64[R + 1]
+    tokens: np.ndarray  # uint32[K]
+    tok_off: np.ndarray  # uint64[R + 1]
+    n_kept: np.ndarray  # uint32[R]
+    stop_col: np.ndarray  # uint32[R]
+
+
+class DecodedRowsDevice(NamedTuple):
+    """`decode_rows_device`: device pointers and the figures that size them: tokens holds n_tokens ids, data n_bytes bytes, tok_off and
+    byte_off n_rows + 1 entries, n_kept and stop_col n_rows.  tokens .. stop_col are the core's buffers, valid until its next decode-rows
+    call that succeeds; data and byte_off are its decode buffers, valid until its next decode call."""
+    tokens: int
+    tok_off: int
+    n_kept: int
+    stop_col: int
+    data: int
+    byte_off: int
+    n_tokens: int
+    n_bytes: int
 
 
 class DisallowedSpecialError(ValueError):
@@ -697,6 +725,75 @@ class CoreBPE:
                                             ctypes.byref(nb), ctypes.byref(do))
         _lib.raise_for(rc)
         return db.value or 0, nb.value, do.value or 0
+
+    # ------------------------------------------------------------------ id matrices (no reference counterpart: the host loop of its users)
+    _ROW_DTYPES = {np.dtype(np.uint32): 0, np.dtype(np.int32): _lib.DROWS_I32, np.dtype(np.int64): _lib.DROWS_I64}
+
+    @classmethod
+    def _drows_spec(cls, dtype, stop, skip, skip_special: bool, keep_stop: bool) -> "_lib.DrowsSpec":
+        try:
+            flags = cls._ROW_DTYPES[np.dtype(dtype)]
+        except (KeyError, TypeError):
+            raise ValueError("an id matrix holds uint32, int32 or int64") from None
+        stop, skip = [int(t) for t in stop], [int(t) for t in skip]
+        for name, ids in (("stop", stop), ("skip", skip)):
+            if len(ids) > 16:
+                raise ValueError(f"more than 16 {name} ids")
+            if any(not 0 <= t <= 0xFFFFFFFF for t in ids):
+                raise ValueError(f"{name} ids must be token ids below 2^32")
+        flags |= (_lib.DROWS_SKIP_SPECIAL if skip_special else 0) | (_lib.DROWS_KEEP_STOP if keep_stop else 0)
+        U16 = ctypes.c_uint32 * 16
+        return _lib.DrowsSpec(flags, len(stop), len(skip), U16(*stop), U16(*skip))
+
+    def decode_rows_device(self, d_ids: int, n_rows: int, width: int, ld: int | None = None, *, dtype=np.int64, d_begin: int = 0, d_end: int = 0, stop: Sequence[int] = (),
+                           skip: Sequence[int] = (), skip_special: bool = False, keep_stop: bool = False, stream: int = 0) -> DecodedRowsDevice:
+        """Device-resident decode of an id matrix (tk_decode_rows_device): a pointer to element (0, 0) of n_rows x width ids of `dtype`
+        (uint32, int32, int64) on this core's device, rows `ld` elements apart (None: width) -- a column slice of a wider matrix goes in as
+        it lies --, d_begin / d_end: pointers to uint32[n_rows] (0: every row is live from column 0 / to column width); see `DecodedRows`
+        for the rule and the arrays."""
+        self._one_device("decode_rows_device")
+        spec = self._drows_spec(dtype, stop, skip, skip_special, keep_stop)
+        out, cnt, refs = self._outs(6, 2)
+        rc = self._L.tk_decode_rows_device(self._h, d_ids or None, n_rows, width, width if ld is None else ld, d_begin or None, d_end or None, ctypes.byref(spec),
+                                           stream or None, *refs)
+        _lib.raise_for(rc)
+        return DecodedRowsDevice(*[x.value or 0 for x in out], *[int(x.value) for x in cnt])
+
+    @staticmethod
+    def _row_bounds(x, n_rows: int, name: str):
+        if x is None:
+            return None
+        a = np.asarray(x)
+        if a.shape != (n_rows,) or (len(a) and (int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF)):
+            raise ValueError(f"{name} must hold one column index below 2^32 per row")
+        return np.ascontiguousarray(a, dtype=np.uint32)
+
+    def decode_rows_packed(self, ids: np.ndarray, *, begin=None, end=None, stop: Sequence[int] = (), skip: Sequence[int] = (), skip_special: bool = False,
+                           keep_stop: bool = False) -> DecodedRows:
+        """One GPU call for an id matrix in host memory (tk_decode_rows): a 2-D array of uint32, int32 or int64 whose column stride is one
+        element -- any row stride of at least a row: a column slice of a wider matrix is not copied first."""
+        self._one_device("decode_rows_packed")
+        ids = np.asarray(ids)
+        if ids.ndim != 2:
+            raise ValueError("an id matrix has two dimensions")
+        spec = self._drows_spec(ids.dtype, stop, skip, skip_special, keep_stop)
+        n_rows, width = ids.shape
+        item = ids.itemsize
+        if n_rows and width > 1 and ids.strides[1] != item:  # (the strides of an array without elements say nothing)
+            raise ValueError("the column stride of an id matrix must be one element")
+        ld = width
+        if n_rows > 1 and width:
+            if ids.strides[0] % item or ids.strides[0] < width * item:
+                raise ValueError("the row stride of an id matrix must be a whole number of elements, at least a row")
+            ld = ids.strides[0] // item
+        begin, end = self._row_bounds(begin, n_rows, "begin"), self._row_bounds(end, n_rows, "end")
+        out, cnt, refs = self._outs(6, 2)
+        rc = self._L.tk_decode_rows(self._h, ids.ctypes.data if n_rows and width else None, n_rows, width, ld, None if begin is None else begin.ctypes.data,
+                                    None if end is None else end.ctypes.data, ctypes.byref(spec), *refs)
+        _lib.raise_for(rc)
+        n_tokens, n_bytes = (int(x.value) for x in cnt)
+        return DecodedRows(_take_u8(out[4], n_bytes), _take_u64(out[5], n_rows + 1), _take_u32(out[0], n_tokens), _take_u64(out[1], n_rows + 1),
+                           _take_u32(out[2], n_rows), _take_u32(out[3], n_rows))
 
     # ------------------------------------------------------------------ token spans (tiktoken/core.py:303-335 over batches)
     def _one_device(self, what: str) -> None:

@@ -568,6 +568,83 @@ class Encoding:
         view = memoryview(data)
         return [bytes(view[a:b]) for a, b in zip(bounds[:-1], bounds[1:])]
 
+    # ---- id matrices, as a generation loop hands them back: rows cut at their first stop id, pad and special ids dropped, on the device
+    def _row_ids(self, ids, what: str) -> list[int]:
+        """stop / skip as ids: a special token may be named by its string"""
+        if isinstance(ids, (str, int)):
+            ids = (ids,)
+        out = []
+        for t in ids:
+            if isinstance(t, str):
+                if t not in self._special_tokens:
+                    raise ValueError(f"{what}: {t!r} is no special token of this encoding")
+                t = self._special_tokens[t]
+            out.append(int(t))
+        return out
+
+    def decode_rows_packed(self, ids, *, begin=None, end=None, stop=(), skip=(), skip_special: bool = False,
+                           keep_stop: bool = False) -> "_tiktoken.DecodedRows":
+        """Decode the rows of an id matrix [R, W] in one GPU call (tk_decode_rows / tk_decode_rows_device), as arrays -- see
+        `_tiktoken.DecodedRows`.  Row r is read from column begin[r] (default 0) up to its first id in `stop`, or to end[r] (default W)
+        when it has none; ids in `skip`, and with `skip_special` every special token, are dropped.  `stop` and `skip` take up to 16 ids or
+        special-token strings each; with `keep_stop` the stop id belongs to its row.  An id outside the live range or in `skip` may be
+        anything (a pad id outside the vocabulary); a kept id without a token raises KeyError with its row and column.
+        `ids`: a 2-D numpy array of uint32, int32 or int64 whose column stride is one element (any row stride: `out[:, prompt_len:]` is not
+        copied), or a torch tensor of int32 / int64 on this encoding's GPU, which goes in by pointer."""
+        kw = dict(stop=self._row_ids(stop, "stop"), skip=self._row_ids(skip, "skip"), skip_special=skip_special, keep_stop=keep_stop)
+        if hasattr(ids, "data_ptr") and hasattr(ids, "is_cuda"):
+            return self._decode_rows_tensor(ids, begin, end, kw)
+        return self._core_bpe.decode_rows_packed(ids, begin=begin, end=end, **kw)
+
+    def _decode_rows_tensor(self, ids, begin, end, kw) -> "_tiktoken.DecodedRows":
+        import torch
+
+        core = self._core_bpe
+        if not ids.is_cuda or ids.device.index != core.device:
+            raise ValueError(f"the id tensor lives on {ids.device}: this encoding runs on GPU {core.device} (numpy arrays go through the host entry)")
+        dtype = {torch.int32: np.int32, torch.int64: np.int64}.get(ids.dtype)
+        if ids.dim() != 2 or dtype is None:
+            raise ValueError("an id tensor has two dimensions and holds int32 or int64")
+        n_rows, width = ids.shape
+        if n_rows and width > 1 and ids.stride(1) != 1:
+            raise ValueError("the column stride of an id matrix must be one element")
+        ld = ids.stride(0) if n_rows > 1 and width else width
+
+        def bounds(x, name):
+            if x is None:
+                return None
+            if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.int32 and x.is_contiguous() and x.shape == (n_rows,)):
+                x = torch.from_numpy(core._row_bounds(x.cpu().numpy() if isinstance(x, torch.Tensor) else x, n_rows, name).view(np.int32)).to(ids.device)
+            return x
+
+        d_begin, d_end = bounds(begin, "begin"), bounds(end, "end")
+        torch.cuda.current_stream(ids.device).synchronize()  # (the library runs on a stream of its own: the ids must be there)
+        r = core.decode_rows_device(ids.data_ptr() if n_rows and width else 0, n_rows, width, ld, dtype=dtype, d_begin=d_begin.data_ptr() if d_begin is not None else 0,
+                                    d_end=d_end.data_ptr() if d_end is not None else 0, **kw)
+
+        def host(ptr, n, typestr, np_dtype):  # a buffer of the library, copied to the host
+            if not n:
+                return np.zeros(0, np_dtype)
+            return torch.as_tensor(_DeviceArray(ptr, n, typestr), device=ids.device).cpu().numpy().view(np_dtype)
+
+        return _tiktoken.DecodedRows(host(r.data, r.n_bytes, "|u1", np.uint8), host(r.byte_off, n_rows + 1, "<i8", np.uint64), host(r.tokens, r.n_tokens, "<i4", np.uint32),
+                                     host(r.tok_off, n_rows + 1, "<i8", np.uint64), host(r.n_kept, n_rows, "<i4", np.uint32), host(r.stop_col, n_rows, "<i4", np.uint32))
+
+    def decode_rows_bytes(self, ids, *, begin=None, end=None, stop=(), skip=(), skip_special: bool = False, keep_stop: bool = False) -> list[bytes]:
+        """The bytes of every row of an id matrix; the arguments as in `decode_rows_packed`."""
+        rows = self.decode_rows_packed(ids, begin=begin, end=end, stop=stop, skip=skip, skip_special=skip_special, keep_stop=keep_stop)
+        view, bounds = memoryview(rows.data), rows.byte_off.tolist()
+        return [bytes(view[a:b]) for a, b in zip(bounds[:-1], bounds[1:])]
+
+    def decode_rows(self, ids, *, begin=None, end=None, stop=(), skip=(), skip_special: bool = False, keep_stop: bool = False,
+                    errors: str = "replace") -> list[str]:
+        """The text of every row of an id matrix: `[enc.decode(trimmed_row) for row in ids]` without the host loop that trims.  The
+        arguments as in `decode_rows_packed`; `errors` as in `decode`, applied per row on the host.  The defaults skip nothing and stop
+        nowhere."""
+        rows = self.decode_rows_packed(ids, begin=begin, end=end, stop=stop, skip=skip, skip_special=skip_special, keep_stop=keep_stop)
+        view, bounds = memoryview(rows.data), rows.byte_off.tolist()
+        return [str(view[a:b], "utf-8", errors) if b > a else "" for a, b in zip(bounds[:-1], bounds[1:])]
+
     def token_byte_values(self) -> list[bytes]:
         return self._core_bpe.token_byte_values()
 
@@ -622,6 +699,13 @@ class Encoding:
             self.__dict__ = plugins.get_encoding(value).__dict__
             return
         self.__init__(**value)
+
+
+class _DeviceArray:
+    """A device buffer of the library seen through __cuda_array_interface__ (torch.as_tensor reads it in place)."""
+
+    def __init__(self, ptr: int, n: int, typestr: str):
+        self.__cuda_array_interface__ = {"shape": (n,), "typestr": typestr, "data": (ptr, False), "version": 2}
 
 
 @functools.lru_cache(maxsize=128)

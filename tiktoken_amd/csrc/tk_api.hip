@@ -23,6 +23,7 @@
 
 #include "../../include/tiktoken_amd.h"
 #include "tk_decode.h"
+#include "tk_decode_rows.h"
 #include "tk_offsets.h"
 #include "tk_padded.h"
 #include "tk_sample_rows.h"
@@ -286,6 +287,10 @@ struct tk_core {
     // per-sample and per-row arrays and cu_seqlens; d_srow_cnt: the report words, the role table and everything a call computes until it is
     // accepted (the write pass reads pstart, c, f, row_sample and row_seg there); d_srow_in: part_role and sample_off of a host-text call.
     Buf d_srow, d_srow_row, d_srow_cnt, d_srow_in;
+    // Decoded id matrices (tk_decode_rows.h), apart from everything above: d_drows_tok: the kept ids; d_drows_row: tok_off, n_kept and stop_col
+    // of every row; d_drows_cnt: the TK_DROWS_WORDS report words, the rows' stop words and the tile counts a call computes until it is
+    // accepted; d_drows_in: the matrix, begin and end of a host call.
+    Buf d_drows_tok, d_drows_row, d_drows_cnt, d_drows_in;
     // Small calls (tk_k_small) do not take `mu`: the reference's normal use is several threads on one Encoding (core.py:175, a thread pool
     // over encode; lib.rs:232-238 keeps a regex per thread for it), and a small call needs nothing of the shared workspace -- a slot of its
     // own (page-locked text and result buffers the kernel reads and writes directly, merge scratch, a stream) is all.  A caller takes a
@@ -2338,29 +2343,31 @@ static int ranged_ids_pass(tk_core* c, hipStream_t s, const uint32_t* ids, uint6
 
 // Device-resident decode: ids and token offsets in HBM in, bytes and byte offsets in HBM out (library-owned buffers, valid until the core's
 // next decode call).  The host learns the byte count (one 16-byte copy): the output buffer is sized by it.
+// decode_device_run: the caller holds c->mu (tk_decode_batch_device, and the decode-rows entries behind their own passes).
+static int decode_device_run(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n, const uint64_t* d_tok_off, uint64_t n_docs, DecodeView* v, uint64_t* nbytes) {
+    TRY(decode_table_check(c));
+    TRY(decode_view(c, n, 0, d_tok_off != nullptr, true, n_docs, v));
+    unsigned long long h_tot[2] = {0, ~0ull};
+    HIPCHK(hipMemcpyAsync(v->tots, h_tot, 16, hipMemcpyHostToDevice, s));
+    if (n) TRY(decode_range_len(c, s, *v, d_tok, 0, n, v->tots));
+    HIPCHK(hipMemcpyAsync(h_tot, v->tots, 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (h_tot[1] != ~0ull) return invalid_token(d_tok, h_tot[1], true);
+    *nbytes = h_tot[0];
+    TRY(ensure(c->d_bytes, *nbytes + 16));
+    if (n) TRY(decode_range_copy(c, s, *v, d_tok, 0, n, c->d_bytes.as<uint8_t>(), 0));
+    if (d_tok_off)
+        hipLaunchKernelGGL(tk_k_dec_docoff, dim3(grid_for(n_docs + 1, 256, 4096)), dim3(256), 0, s, d_tok_off, n_docs, n, v->tboff, v->tots, v->byte_off);
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    return TK_OK;
+}
 extern "C" int tk_decode_batch_device(tk_core* c, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_docs, void* stream,
                                       const uint8_t** d_bytes_out, uint64_t* n_bytes_out, const uint64_t** d_byte_off_out) {
     DecodeView v;
     uint64_t nbytes = 0;
     TRY(device_pass(c, n_bytes_out && (d_tokens || !n_tokens), stream, [&](hipStream_t s) -> int {
-        TRY(decode_table_check(c));
-        const uint32_t* d_tok = (const uint32_t*)d_tokens;
-        const uint64_t n = n_tokens;
-        TRY(decode_view(c, n, 0, d_tok_off != nullptr, true, n_docs, &v));
-        unsigned long long h_tot[2] = {0, ~0ull};
-        HIPCHK(hipMemcpyAsync(v.tots, h_tot, 16, hipMemcpyHostToDevice, s));
-        if (n) TRY(decode_range_len(c, s, v, d_tok, 0, n, v.tots));
-        HIPCHK(hipMemcpyAsync(h_tot, v.tots, 16, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        if (h_tot[1] != ~0ull) return invalid_token(d_tok, h_tot[1], true);
-        nbytes = h_tot[0];
-        TRY(ensure(c->d_bytes, nbytes + 16));
-        if (n) TRY(decode_range_copy(c, s, v, d_tok, 0, n, c->d_bytes.as<uint8_t>(), 0));
-        if (d_tok_off)
-            hipLaunchKernelGGL(tk_k_dec_docoff, dim3(grid_for(n_docs + 1, 256, 4096)), dim3(256), 0, s, (const uint64_t*)d_tok_off, n_docs, n, v.tboff, v.tots, v.byte_off);
-        HIPCHK(hipStreamSynchronize(s));
-        HIPCHK(hipGetLastError());
-        return TK_OK;
+        return decode_device_run(c, s, (const uint32_t*)d_tokens, n_tokens, (const uint64_t*)d_tok_off, n_docs, &v, &nbytes);
     }));
     if (d_bytes_out) *d_bytes_out = c->d_bytes.as<uint8_t>();
     if (d_byte_off_out) *d_byte_off_out = d_tok_off ? v.byte_off : nullptr;
@@ -3361,6 +3368,179 @@ extern "C" int tk_encode_batch_sample_rows(tk_core* c, const uint8_t* utf8, cons
             *n_segs_out = v.n_segs;
             return TK_OK;
         });
+}
+
+// ------------------------------------------------------------------------------------------
+// Decoding id matrices (tk_decode_rows.h): an id matrix on the device -> the compact ids of its rows' live ranges, then the decode passes.
+// ------------------------------------------------------------------------------------------
+static_assert(TK_DROWS_KEEP_STOP == TK_DROWSF_KEEP_STOP && TK_DROWS_SKIP_SPECIAL == TK_DROWSF_SKIP_SPECIAL && TK_DROWS_I32 == TK_DROWSF_I32 && TK_DROWS_I64 == TK_DROWSF_I64,
+              "tk_drows_spec flags");
+static_assert(sizeof(((tk_drows_spec*)nullptr)->stop_ids) == TK_DROWS_LIST * 4 && sizeof(((tk_drows_spec*)nullptr)->skip_ids) == TK_DROWS_LIST * 4, "tk_drows_spec lists");
+struct DrowsView {  // device buffers of the core: the first four valid until its next decode-rows call that succeeds, the last two until its next decode call
+    const uint32_t* tokens = nullptr;
+    const uint64_t* tok_off = nullptr;
+    const uint32_t *n_kept = nullptr, *stop_col = nullptr;
+    const uint8_t* bytes = nullptr;
+    const uint64_t* byte_off = nullptr;
+    uint64_t n_tokens = 0, n_bytes = 0;
+};
+static int drows_refusal(int why) {
+    switch (why) {
+        case 0: return TK_OK;
+        case 1: return fail(TK_VALUE_ERROR, "more than 16 stop ids");
+        case 2: return fail(TK_VALUE_ERROR, "more than 16 skip ids");
+        case 3: return fail(TK_VALUE_ERROR, "TK_DROWS_I32 together with TK_DROWS_I64");
+        case 4: return fail(TK_VALUE_ERROR, "ld must be at least the width");
+        case 5: return fail(TK_VALUE_ERROR, "too many rows: the row indices are 32-bit");
+        case 6: return fail(TK_VALUE_ERROR, "2^32 columns or more: the column indices are 32-bit");
+        case 7: return fail(TK_VALUE_ERROR, "tk_drows_spec: unknown flag");
+        default: return fail(TK_VALUE_ERROR, "the matrix spans 2^60 elements or more");
+    }
+}
+// What can be refused without looking at the matrix
+static int drows_check_spec(tk_core* c, const tk_drows_spec* spec, uint64_t R, uint64_t W, uint64_t ld, TkDrows* p) {
+    if (!spec) return fail(TK_VALUE_ERROR, "null argument");
+    TRY(drows_refusal(tk_drows_shape(R, W, ld, spec->flags, spec->n_stop, spec->stop_ids, spec->n_skip, spec->skip_ids, TK_DEC_BLOCK, p)));
+    return decode_table_check(c);
+}
+// the kernels of a matrix's element type: f(std::integral_constant<int, MODE>) with TkIdMatrix's MODE
+template <class F>
+static void drows_by_type(uint32_t flags, F&& f) {
+    if (flags & TK_DROWS_I64) f(std::integral_constant<int, 2>());
+    else if (flags & TK_DROWS_I32) f(std::integral_constant<int, 1>());
+    else f(std::integral_constant<int, 0>());
+}
+// the reference's KeyError for element (r, c) of the matrix, which has no bytes
+static int drows_invalid_token(const void* d_ids, const TkDrows& p, uint64_t pos) {
+    const uint64_t r = pos / p.W, col = pos - r * p.W;  // (W != 0: there is an element)
+    const uint32_t es = tk_drows_elem_size(p.flags);
+    int64_t wide = 0;
+    uint32_t narrow = 0;
+    (void)hipMemcpy(es == 8 ? (void*)&wide : (void*)&narrow, (const uint8_t*)d_ids + (r * p.ld + col) * es, es, hipMemcpyDeviceToHost);
+    const std::string n = es == 8 ? std::to_string(wide) : (p.flags & TK_DROWS_I32) ? std::to_string((int32_t)narrow) : std::to_string(narrow);
+    return fail(TK_KEY_ERROR, "Invalid token for decoding: " + n + " (row " + std::to_string(r) + ", column " + std::to_string(col) + ")");
+}
+// drows_run: the caller holds c->mu.  The host waits once for the report words -- the first offending row, the first kept id without entry,
+// K --, refuses or sizes the outputs, and hands (tokens, tok_off) to the decode passes.  A call that is refused has written into
+// d_drows_cnt only: the previous result stays whole.
+static int drows_run(tk_core* c, hipStream_t s, const void* d_ids, uint64_t R, uint64_t W, uint64_t ld, const uint32_t* d_begin, const uint32_t* d_end,
+                     const tk_drows_spec* spec, DrowsView* out) {
+    TkDrows p;
+    TRY(drows_check_spec(c, spec, R, W, ld, &p));
+    const uint64_t nt = tk_drows_n_tiles(p);
+    Carve scratch;
+    const uint64_t at_words = scratch.add(TK_DROWS_WORDS * 8), at_found = scratch.add(R * 4), at_cnt = scratch.add(nt * 8);
+    TRY(ensure(c->d_drows_cnt, scratch.total));
+    unsigned long long* words = carved<unsigned long long>(c->d_drows_cnt, at_words);
+    uint32_t* found = carved<uint32_t>(c->d_drows_cnt, at_found);
+    unsigned long long* cnt = carved<unsigned long long>(c->d_drows_cnt, at_cnt);
+    HIPCHK(hipMemsetAsync(words, 0xFF, (TK_DROWS_K - TK_DROWS_BAD_ROW) * 8, s));  // (no row, no id offends; tk_k_drows_scan writes K)
+    if (R) HIPCHK(hipMemsetAsync(found, 0xFF, R * 4, s));
+    const dim3 grid((uint32_t)std::min<uint64_t>(nt, 1u << 20)), block(256);
+    const uint2* dec = c->t_dec.as<uint2>();
+    if (nt && (p.n_stop || d_begin || d_end))  // (nothing to find, nothing to check otherwise)
+        TRY(timed(c, s, "tk_k_drows_stop", [&] {
+            drows_by_type(p.flags, [&](auto m) { hipLaunchKernelGGL(tk_k_drows_stop<decltype(m)::value>, grid, block, 0, s, d_ids, d_begin, d_end, p, nt, found, words); });
+        }));
+    if (nt)
+        TRY(timed(c, s, "tk_k_drows_count", [&] {
+            drows_by_type(p.flags, [&](auto m) {
+                hipLaunchKernelGGL(tk_k_drows_count<decltype(m)::value>, grid, block, 0, s, d_ids, d_begin, d_end, p, nt, found, dec, c->n_dec, cnt, words);
+            });
+        }));
+    TRY(timed(c, s, "tk_k_drows_scan", [&] { hipLaunchKernelGGL(tk_k_drows_scan, dim3(1), dim3(1024), 0, s, cnt, nt, words); }));
+    unsigned long long got[TK_DROWS_WORDS];
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(got, words, sizeof(got), hipMemcpyDeviceToHost));
+    if (got[TK_DROWS_BAD_ROW] != ~0ull)
+        return fail(TK_VALUE_ERROR, "begin and end must satisfy begin <= end <= width: row " + std::to_string(got[TK_DROWS_BAD_ROW]) + " does not");
+    if (got[TK_DROWS_BAD_ID] != ~0ull) return drows_invalid_token(d_ids, p, got[TK_DROWS_BAD_ID]);
+    const uint64_t K = got[TK_DROWS_K];
+    if (K >> 32) return fail(TK_VALUE_ERROR, "2^32 kept ids or more: decode the matrix in parts");
+    Carve row;
+    const uint64_t at_off = row.add((R + 1) * 8), at_kept = row.add(R * 4), at_stop = row.add(R * 4);
+    TRY(ensure(c->d_drows_tok, (K + 1) * 4));
+    TRY(ensure(c->d_drows_row, row.total));
+    uint32_t* tokens = c->d_drows_tok.as<uint32_t>();
+    uint64_t* tok_off = carved<uint64_t>(c->d_drows_row, at_off);
+    uint32_t *n_kept = carved<uint32_t>(c->d_drows_row, at_kept), *stop_col = carved<uint32_t>(c->d_drows_row, at_stop);
+    TRY(timed(c, s, "tk_k_drows_rows", [&] {
+        hipLaunchKernelGGL(tk_k_drows_rows, dim3(grid_for(R + 1, 256, 4096)), block, 0, s, d_begin, d_end, p, cnt, found, K, tok_off, n_kept, stop_col);
+    }));
+    if (nt && K)
+        TRY(timed(c, s, "tk_k_drows_write", [&] {
+            drows_by_type(p.flags, [&](auto m) {
+                hipLaunchKernelGGL(tk_k_drows_write<decltype(m)::value>, grid, block, 0, s, d_ids, d_begin, d_end, p, nt, found, dec, c->n_dec, cnt, tokens);
+            });
+        }));
+    DecodeView dv;
+    TRY(decode_device_run(c, s, tokens, K, tok_off, R, &dv, &out->n_bytes));  // (waits for the stream at its end)
+    out->tokens = tokens;
+    out->tok_off = tok_off;
+    out->n_kept = n_kept;
+    out->stop_col = stop_col;
+    out->bytes = c->d_bytes.as<uint8_t>();
+    out->byte_off = dv.byte_off;
+    out->n_tokens = K;
+    return TK_OK;
+}
+
+extern "C" int tk_decode_rows_device(tk_core* c, const void* d_ids, uint64_t n_rows, uint64_t width, uint64_t ld, const void* d_begin, const void* d_end,
+                                     const tk_drows_spec* spec, void* stream, const uint32_t** d_tokens_out, const uint64_t** d_tok_off_out, const uint32_t** d_n_kept_out,
+                                     const uint32_t** d_stop_col_out, const uint8_t** d_bytes_out, const uint64_t** d_byte_off_out, uint64_t* n_tokens_out,
+                                     uint64_t* n_bytes_out) {
+    DrowsView v;
+    TRY(device_pass(c, spec && n_tokens_out && n_bytes_out && (d_ids || !n_rows || !width), stream,
+                    [&](hipStream_t s) { return drows_run(c, s, d_ids, n_rows, width, ld, (const uint32_t*)d_begin, (const uint32_t*)d_end, spec, &v); }));
+    if (d_tokens_out) *d_tokens_out = v.tokens;
+    if (d_tok_off_out) *d_tok_off_out = v.tok_off;
+    if (d_n_kept_out) *d_n_kept_out = v.n_kept;
+    if (d_stop_col_out) *d_stop_col_out = v.stop_col;
+    if (d_bytes_out) *d_bytes_out = v.bytes;
+    if (d_byte_off_out) *d_byte_off_out = v.byte_off;
+    *n_tokens_out = v.n_tokens;
+    *n_bytes_out = v.n_bytes;
+    return TK_OK;
+}
+
+// A matrix in host memory: its (R - 1) * ld + W elements travel to the device as they lie (a slice keeps its row stride), begin and end behind
+// them, and the six arrays travel back.
+extern "C" int tk_decode_rows(tk_core* c, const void* ids, uint64_t n_rows, uint64_t width, uint64_t ld, const uint32_t* begin, const uint32_t* end,
+                              const tk_drows_spec* spec, uint32_t** tokens_out, uint64_t** tok_off_out, uint32_t** n_kept_out, uint32_t** stop_col_out, uint8_t** bytes_out,
+                              uint64_t** byte_off_out, uint64_t* n_tokens_out, uint64_t* n_bytes_out) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if (!spec || !tokens_out || !tok_off_out || !n_kept_out || !stop_col_out || !bytes_out || !byte_off_out || !n_tokens_out || !n_bytes_out || (!ids && n_rows && width))
+        return fail(TK_VALUE_ERROR, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    return drained(c, [&]() -> int {
+        TkDrows p;
+        TRY(drows_check_spec(c, spec, n_rows, width, ld, &p));  // (before anything is copied)
+        const uint64_t n_elems = n_rows && width ? (n_rows - 1) * ld + width : 0;
+        Carve in;
+        const uint64_t at_ids = in.add(n_elems * tk_drows_elem_size(p.flags)), at_begin = in.add(n_rows * 4), at_end = in.add(n_rows * 4);
+        TRY(ensure(c->d_drows_in, in.total + 16));
+        void* d_ids = carved<void>(c->d_drows_in, at_ids);
+        uint32_t *d_begin = carved<uint32_t>(c->d_drows_in, at_begin), *d_end = carved<uint32_t>(c->d_drows_in, at_end);
+        hipStream_t s = c->stream;
+        if (n_elems) HIPCHK(hipMemcpyAsync(d_ids, ids, n_elems * tk_drows_elem_size(p.flags), hipMemcpyHostToDevice, s));
+        if (begin && n_rows) HIPCHK(hipMemcpyAsync(d_begin, begin, n_rows * 4, hipMemcpyHostToDevice, s));
+        if (end && n_rows) HIPCHK(hipMemcpyAsync(d_end, end, n_rows * 4, hipMemcpyHostToDevice, s));
+        DrowsView v;
+        TRY(drows_run(c, s, d_ids, n_rows, width, ld, begin ? d_begin : nullptr, end ? d_end : nullptr, spec, &v));
+        ResultBag bag;
+        TRY(bag.fetch(tokens_out, v.tokens, v.n_tokens));
+        TRY(bag.fetch(tok_off_out, v.tok_off, n_rows + 1));
+        TRY(bag.fetch(n_kept_out, v.n_kept, n_rows));
+        TRY(bag.fetch(stop_col_out, v.stop_col, n_rows));
+        TRY(bag.fetch(bytes_out, v.bytes, v.n_bytes));
+        TRY(bag.fetch(byte_off_out, v.byte_off, n_rows + 1));
+        bag.give();
+        *n_tokens_out = v.n_tokens;
+        *n_bytes_out = v.n_bytes;
+        return TK_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------
