@@ -515,7 +515,9 @@ void tk_last_stats(tk_core* core, uint64_t* n_bytes, uint64_t* n_pieces, uint64_
 /* One named figure of the last encode call; 0 for a name it does not know: "chunks", "small_launches", "small_calls", "mid_calls",
  * "back_streams", "regrown", "workspace_bytes", "front_wgs_per_cu", "compute_units", "spec_find_launches" (launches of the disallowed scan since
  * the core was made: one per chunk of a _checked call), "spec_mark_launches" (launches of the pair of kernels that marks allowed special tokens
- * since the core was made: one per chunk encoded with an allowed set), "stage_bytes" (host-buffer batches of twice that many bytes and more are pipelined); and of the core itself, by its vocabulary's ids:
+ * since the core was made: one per chunk encoded with an allowed set), "stage_bytes" (host-buffer batches of twice that many bytes and more are pipelined),
+ * "train_table_moves" / "train_blob_moves" (of the last tk_train_bpe: how often the word table was rehashed into a larger one, and how often
+ * the distinct words' bytes were copied into a larger blob; both 0 for a corpus of one chunk); and of the core itself, by its vocabulary's ids:
  * "pair_table_packed" (1: every rank fits the packed pair table; 0: 16-byte slots and a merge kernel per length bin), "short_table" (0: an id
  * above 0x3FFFFFFE, tokens of 1 .. 4 bytes live in the mid table), "decode_table_ids" (entries of the device decode table; 0: an id of 2^26
  * or above, the decode entries answer TK_UNSUPPORTED). */

@@ -220,6 +220,11 @@ extern "C" int64_t train_sim(const uint8_t* blob_in, const uint64_t* off, const 
     return rc;
 }
 
+// tk_train_hash of a word: where its probe chain starts (tests/test_train_shapes.py shows that its words share one)
+extern "C" uint64_t train_sim_hash(const uint8_t* word, uint32_t len, uint64_t seed) {
+    return tk_train_hash([&](uint32_t j) { return word[j]; }, len, seed);
+}
+
 #ifdef TRAIN_SIM_MAIN
 // Case file: per case nine uint64 {n_words, slots, seed, block, n_merges, flags, blob bytes, 0, 0}, off[n_words + 1], weight[n_words],
 // first[n_words], the blob.  Result file: per case {rc, n_done, n_sym} (int64 / uint64), pairs[2 * n_merges] uint32, counts[n_merges],

@@ -246,6 +246,7 @@ struct tk_core {
     uint64_t find_hit = ~0ull;
     uint64_t st_find_launches = 0;  // launches of that scan since the core was made
     uint64_t st_mark_launches = 0;  // launches of the marking pair (tk_k_spec_cand + tk_k_spec_resolve) since the core was made
+    uint64_t st_train_table_moves = 0, st_train_blob_moves = 0;  // of the last tk_train_bpe: word tables rehashed into a larger one, word blobs copied into a larger one
     // Streams of the back stages of a multi-chunk batch.  HIP multiplexes its streams onto a few hardware queues (four by default), and
     // two streams that share a queue run one after the other: the back stage of chunk k, queued behind the front kernel of chunk
     // k + 1, then waits for that kernel to END instead of running beside it (seen in the kernel timeline of round 4: no overlap at all).
@@ -3594,14 +3595,18 @@ static int train_tab_reserve(tk_core* c, hipStream_t s, TrainRun& r, uint64_t wo
                            r.cells.as<unsigned long long>());
     }));
     HIPCHK(hipStreamSynchronize(s));  // (the old table goes with `old`)
+    c->st_train_table_moves += 1;
     return TK_OK;
 }
 
-static int train_blob_reserve(hipStream_t s, TrainRun& r, uint64_t used, uint64_t bytes) {
+static int train_blob_reserve(tk_core* c, hipStream_t s, TrainRun& r, uint64_t used, uint64_t bytes) {
     if (bytes <= r.blob.cap && r.blob.p) return TK_OK;
     Buf bigger;
     TRY(ensure(bigger, bytes + bytes / 2));
-    if (used) HIPCHK(hipMemcpyAsync(bigger.p, r.blob.p, used, hipMemcpyDeviceToDevice, s));
+    if (used) {
+        HIPCHK(hipMemcpyAsync(bigger.p, r.blob.p, used, hipMemcpyDeviceToDevice, s));
+        c->st_train_blob_moves += 1;
+    }
     HIPCHK(hipStreamSynchronize(s));
     r.blob = std::move(bigger);
     return TK_OK;
@@ -3634,7 +3639,7 @@ static int train_words(tk_core* c, hipStream_t s, TrainRun& r, const uint8_t* ut
             const ChunkAsk ask{.kind = ChunkKind::PieceStarts, .d_text = c->text.as<uint8_t>(), .d_doc_off = c->doc_off.as<uint64_t>(), .n = n, .n_docs = nd};
             TRY(run_chunk(c, s, ask, &P));  // (waits: P is known)
             if (P) {
-                TRY(train_blob_reserve(s, r, cells[TKT_BLOB], cells[TKT_BLOB] + n + 64));
+                TRY(train_blob_reserve(c, s, r, cells[TKT_BLOB], cells[TKT_BLOB] + n + 64));
                 if ((cells[TKT_BLOB] + n) >> 32) return fail(TK_VALUE_ERROR, "tk_train_bpe: more than 4 GiB of distinct words");
                 TRY(train_tab_reserve(c, s, r, cells[TKT_NWORDS] + P));
                 const TkTrainTab t = r.tab();
@@ -3727,6 +3732,7 @@ extern "C" int tk_train_bpe(tk_core* c, const uint8_t* utf8, const uint64_t* doc
         std::lock_guard<std::mutex> lk(c->mu);
         HIPCHK(hipSetDevice(c->device));
         TrainRun r;
+        c->st_train_table_moves = c->st_train_blob_moves = 0;
         unsigned long long cells[TKT_CELLS] = {};
         TRY(drained(c, [&] { return train_words(c, c->stream, r, utf8, doc_off, n_docs, cells); }));
         TRY(drained(c, [&] { return train_steps(c, c->stream, r, cells, steps, pairs, counts); }));
@@ -4193,6 +4199,8 @@ extern "C" uint64_t tk_stat(tk_core* c, const char* name) {
     if (k == "resynced") return c->st_resynced;  // batches repeated because a deferred tile gave up while the host was not waiting (stage_deferred)
     if (k == "spec_find_launches") return c->st_find_launches;  // launches of the disallowed scan (tk_k_spec_find) since the core was made: one per chunk of a checked call
     if (k == "spec_mark_launches") return c->st_mark_launches;  // launches of the pair that marks allowed special tokens (tk_k_spec_cand + tk_k_spec_resolve): one per chunk that has them
+    if (k == "train_table_moves") return c->st_train_table_moves;  // of the last tk_train_bpe: launches of tk_k_train_rehash (train_tab_reserve)
+    if (k == "train_blob_moves") return c->st_train_blob_moves;    // ... and copies of the words' bytes into a larger blob (train_blob_reserve)
     if (k == "regrown") return c->st_regrown;  // batches repeated with a larger miss data since the core was made (encode_device_locked)
     if (k == "workspace_bytes") {             // device memory of the work sets (everything but the text, the tables and the outputs)
         uint64_t t = 0;
