@@ -397,8 +397,8 @@ int tk_encode_batch_sample_rows(tk_core* core, const uint8_t* utf8, const uint64
  *   pad id outside the vocabulary is legal in skip_ids.  TK_UNSUPPORTED where tk_decode_batch returns it: ids at or above 2^26.
  *   Every refusal is found before any output is written: a refused call leaves the previous result whole.  No kernel reads outside the
  *   (R - 1) * ld + W elements of the matrix, whatever begin and end hold.  One device per call: a group has no such entry.
- *  NOT built: uint16 matrices; UTF-8 repair on the device (errors= stays the caller's step per row); token spans of a matrix (feed tokens
- *   and tok_off to tk_token_spans_device); streaming. */
+ *  Text instead of bytes (errors="replace" / "ignore" applied on the device): tk_decode_rows_text_device / tk_decode_rows_text below.
+ *  NOT built: uint16 matrices; token spans of a matrix (feed tokens and tok_off to tk_token_spans_device); streaming. */
 #define TK_DROWS_KEEP_STOP 1u    /* the stop id that ends a row belongs to it */
 #define TK_DROWS_SKIP_SPECIAL 2u /* special tokens are dropped as if they were in skip_ids */
 #define TK_DROWS_I32 4u          /* the matrix holds int32 */
@@ -420,6 +420,63 @@ int tk_decode_rows_device(tk_core* core, const void* d_ids, uint64_t n_rows, uin
 int tk_decode_rows(tk_core* core, const void* ids, uint64_t n_rows, uint64_t width, uint64_t ld, const uint32_t* begin, const uint32_t* end,
                    const tk_drows_spec* spec, uint32_t** tokens_out, uint64_t** tok_off_out, uint32_t** n_kept_out, uint32_t** stop_col_out,
                    uint8_t** bytes_out, uint64_t** byte_off_out, uint64_t* n_tokens_out, uint64_t* n_bytes_out);
+/* Encoding.decode(tokens, errors="replace")                                  tiktoken/core.py:275-287
+ * UTF-8 repair on the device: packed bytes in HBM -> packed, well-formed UTF-8 in HBM.  The reference's decode is
+ * bytes.decode("utf-8", errors) on one document; this is that call on every document of a packed batch (bytes uint8[n_bytes], byte_off
+ * uint64[n_docs + 1]), each on its own, without the text leaving the device and without a host loop over the documents.
+ * The rule.  A document's bytes fall into consecutive units:
+ *  ASCII byte (00..7F): a unit of its own, copied.
+ *  Lead byte with a declared length: C2..DF declares L = 2, E0..EF L = 3, F0..F4 L = 4.  It accepts the bytes that follow it while they
+ *   are fewer than L - 1, lie inside the document, and each is a continuation byte 80..BF; the FIRST accepted byte has a narrower range
+ *   after four leads: E0: A0..BF, ED: 80..9F, F0: 90..BF, F4: 80..8F.  With all L - 1 bytes accepted the unit is well-formed and its L
+ *   bytes are copied.  Otherwise the lead and what it accepted are one ill-formed unit (the "maximal subpart").
+ *  Any other byte -- C0, C1, F5..FF, a continuation byte that no lead accepted -- is an ill-formed unit of one byte.
+ *  TK_U8_REPLACE writes EF BF BD (U+FFFD) for every ill-formed unit, TK_U8_IGNORE writes nothing for it.
+ *  Nothing crosses a document boundary: a sequence cut by one is ill-formed on both sides.
+ *  Under TK_U8_REPLACE the output is at most three times the input (a run of stray continuation bytes).
+ *  The same length does not mean clean: F0 9F 98 at a document's end becomes EF BF BD.  "Nothing replaced" is a count of its own,
+ *   *n_replaced_out == 0, never *n_text_out == n_bytes.
+ * Whether a byte starts a unit, is swallowed by one or is replaced depends on the three bytes before it and the three behind it, inside
+ * its document: the pass is local (tk_utf8_repair.h).
+ * Output.  text uint8[n_text]; text_off, char_off, repl_off uint64[n_docs + 1]: the bytes of the output, its chars (code points, U+FFFD
+ *  included) and the ill-formed units (replaced or dropped) of the documents before each document; entry n_docs is the total.
+ * In: d_bytes on the core's device, 16-byte aligned and readable for 16 bytes past n_bytes (the core's decode buffers are); d_byte_off
+ *  uint64[n_docs + 1] there, ascending from 0 to n_bytes.  mode: TK_U8_REPLACE or TK_U8_IGNORE.  n_bytes == 0 and n_docs == 0 are legal.
+ * Out: buffers of the core that belong to this entry alone, valid until the core's next repair call (this entry, tk_decode_batch_text,
+ *  tk_decode_rows_text_device, tk_decode_rows_text) -- except that with *n_replaced_out == 0 nothing is written: *d_text_out == d_bytes
+ *  and *d_text_off_out == d_byte_off, the caller's own (char_off and repl_off are made all the same).  The input must not be this entry's
+ *  own previous output buffer.
+ * TK_VALUE_ERROR: a misaligned pointer, an unknown mode, n_bytes of 2^43 or more, offsets that do not ascend from 0 to n_bytes (checked on the device before
+ *  anything is indexed with them; the message names the first offending document).  A refused call leaves the previous result whole.
+ *  No kernel reads outside [d_bytes, d_bytes + n_bytes + 16), whatever the offsets hold.  Holds the core's mutex; `stream`: a
+ *  hipStream_t or null (the core's); the call returns when the text is there.  One device per call: a group has no such entry.
+ * NOT built: token spans inside repaired text (tk_token_spans_device speaks of the bytes before repair). */
+#define TK_U8_REPLACE 0u /* errors="replace" */
+#define TK_U8_IGNORE 1u  /* errors="ignore" */
+int tk_utf8_repair_device(tk_core* core, const void* d_bytes, uint64_t n_bytes, const void* d_byte_off, uint64_t n_docs, uint32_t mode, void* stream,
+                          const uint8_t** d_text_out, uint64_t* n_text_out, const uint64_t** d_text_off_out, const uint64_t** d_char_off_out,
+                          const uint64_t** d_repl_off_out, uint64_t* n_replaced_out);
+/* Encoding.decode_batch(batch, errors=...) as packed text              tiktoken/core.py:337-343
+ * tk_decode_batch's input, host to host: the ids decoded on the device, the repair over their bytes, one copy out.  *text_out ..
+ * *repl_off_out: library-owned (tk_free), text_off / char_off / repl_off of n_docs + 1 entries as above.  Errors: those of
+ * tk_decode_batch (TK_KEY_ERROR "Invalid token for decoding: N", TK_UNSUPPORTED for ids at or above 2^26), and an unknown mode.
+ * One pass over the whole batch: the overlapped ranges of 16 Mi ids that tk_decode_batch runs large batches in are NOT built here. */
+int tk_decode_batch_text(tk_core* core, const uint32_t* tokens, const uint64_t* tok_off, uint64_t n_docs, uint32_t mode, uint8_t** text_out,
+                         uint64_t* n_text_out, uint64_t** text_off_out, uint64_t** char_off_out, uint64_t** repl_off_out, uint64_t* n_replaced_out);
+/* tk_decode_rows_device / tk_decode_rows with text for bytes: the rows passes run unchanged (the rule, the tk_drows_spec and every refusal
+ * are theirs), then the repair runs over the rows' bytes, every row a document.  A multi-byte char spelled by byte-level tokens is
+ * routinely split by the stop id, by begin, by end and by skipped ids: here the packed result is well-formed UTF-8 all the same.
+ * *d_tokens_out .. *d_stop_col_out as tk_decode_rows_device; *d_text_out .. *d_repl_off_out as tk_utf8_repair_device (with
+ * *n_replaced_out == 0 text and text_off ARE the decode buffers, valid until the core's next decode call). */
+int tk_decode_rows_text_device(tk_core* core, const void* d_ids, uint64_t n_rows, uint64_t width, uint64_t ld, const void* d_begin, const void* d_end,
+                               const tk_drows_spec* spec, uint32_t mode, void* stream, const uint32_t** d_tokens_out, const uint64_t** d_tok_off_out,
+                               const uint32_t** d_n_kept_out, const uint32_t** d_stop_col_out, const uint8_t** d_text_out, const uint64_t** d_text_off_out,
+                               const uint64_t** d_char_off_out, const uint64_t** d_repl_off_out, uint64_t* n_tokens_out, uint64_t* n_text_out,
+                               uint64_t* n_replaced_out);
+int tk_decode_rows_text(tk_core* core, const void* ids, uint64_t n_rows, uint64_t width, uint64_t ld, const uint32_t* begin, const uint32_t* end,
+                        const tk_drows_spec* spec, uint32_t mode, uint32_t** tokens_out, uint64_t** tok_off_out, uint32_t** n_kept_out, uint32_t** stop_col_out,
+                        uint8_t** text_out, uint64_t** text_off_out, uint64_t** char_off_out, uint64_t** repl_off_out, uint64_t* n_tokens_out,
+                        uint64_t* n_text_out, uint64_t* n_replaced_out);
 /* bpe_train(data, vocab_size, pat_str, visualise=None)                      tiktoken/_educational.py:119-185
  * Training a vocabulary: the merges the reference's educational trainer makes on the same text -- the same pairs in the same order -- for a
  * packed batch of documents, under the core's pat_str (stock scanners or the generic engine).  The core's ranks and special tokens play

@@ -57,6 +57,7 @@ class DrowsSpec(ctypes.Structure):
 
 
 DROWS_KEEP_STOP, DROWS_SKIP_SPECIAL, DROWS_I32, DROWS_I64 = 1, 2, 4, 8
+U8_REPLACE, U8_IGNORE = 0, 1  # TK_U8_REPLACE, TK_U8_IGNORE
 
 
 def build(force: bool = False) -> str:
@@ -141,6 +142,15 @@ def lib() -> ctypes.CDLL:
             L.tk_decode_rows_device.argtypes = [vp, vp, u64, u64, u64, vp, vp, P(DrowsSpec), vp, *[P(vp)] * 6, P(u64), P(u64)]
             L.tk_decode_rows.restype = i32
             L.tk_decode_rows.argtypes = [vp, vp, u64, u64, u64, vp, vp, P(DrowsSpec), *[P(vp)] * 6, P(u64), P(u64)]
+        if hasattr(L, "tk_utf8_repair_device"):  # (absent from older builds selected through $TIKTOKEN_AMD_LIB)
+            L.tk_utf8_repair_device.restype = i32
+            L.tk_utf8_repair_device.argtypes = [vp, vp, u64, vp, u64, u32, vp, P(vp), P(u64), P(vp), P(vp), P(vp), P(u64)]
+            L.tk_decode_batch_text.restype = i32
+            L.tk_decode_batch_text.argtypes = [vp, vp, vp, u64, u32, P(vp), P(u64), P(vp), P(vp), P(vp), P(u64)]
+            L.tk_decode_rows_text_device.restype = i32
+            L.tk_decode_rows_text_device.argtypes = [vp, vp, u64, u64, u64, vp, vp, P(DrowsSpec), u32, vp, *[P(vp)] * 8, P(u64), P(u64), P(u64)]
+            L.tk_decode_rows_text.restype = i32
+            L.tk_decode_rows_text.argtypes = [vp, vp, u64, u64, u64, vp, vp, P(DrowsSpec), u32, *[P(vp)] * 8, P(u64), P(u64), P(u64)]
         L.tk_decode_single_token_bytes.restype = i32
         L.tk_decode_single_token_bytes.argtypes = [vp, u32, P(vp), P(u64)]
         L.tk_n_tokens.restype = u64

@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import atexit
 import ctypes
+import dataclasses
 import weakref
 from typing import AbstractSet, NamedTuple, Sequence
 
@@ -301,6 +302,73 @@ class DecodedRowsDevice(NamedTuple):
     byte_off: int
     n_tokens: int
     n_bytes: int
+
+
+class RepairedText(NamedTuple):
+    """Packed, well-formed UTF-8 (tk_decode_batch_text; the rule: include/tiktoken_amd.h, tk_utf8_repair_device): document d is
+    data[text_off[d] : text_off[d + 1]], has char_off[d + 1] - char_off[d] chars, and repl_off[d + 1] - repl_off[d] of its units were
+    ill-formed (replaced by U+FFFD, or dropped with errors="ignore")."""
+    data: np.ndarray  # uint8
+    text_off: np.ndarray  # uint64[n + 1]
+    char_off: np.ndarray  # uint64[n + 1]
+    repl_off: np.ndarray  # uint64[n + 1]
+
+
+class RepairedDevice(NamedTuple):
+    """`utf8_repair_device`: device pointers and the figures that size them: data holds n_bytes bytes, the three offset arrays n_docs + 1
+    entries.  The core's buffers, valid until its next repair call -- but with n_replaced == 0 data and text_off are the caller's own input
+    pointers: nothing was written."""
+    data: int
+    text_off: int
+    char_off: int
+    repl_off: int
+    n_bytes: int
+    n_replaced: int
+
+
+@dataclasses.dataclass(frozen=True)
+class DecodedRowsText:
+    """`DecodedRows` with text for bytes (tk_decode_rows_text): data is well-formed UTF-8, row r is data[byte_off[r] : byte_off[r + 1]];
+    char_off and repl_off as in `RepairedText`.  tokens, tok_off, n_kept and stop_col are those of `decode_rows_packed`."""
+    data: np.ndarray  # uint8: the rows' text back to back
+    byte_off: np.ndarray  # uint64[R + 1]
+    tokens: np.ndarray  # uint32[K]
+    tok_off: np.ndarray  # uint64[R + 1]
+    n_kept: np.ndarray  # uint32[R]
+    stop_col: np.ndarray  # uint32[R]
+    char_off: np.ndarray  # uint64[R + 1]
+    repl_off: np.ndarray  # uint64[R + 1]
+
+    @property
+    def text_off(self) -> np.ndarray:
+        return self.byte_off
+
+
+class DecodedRowsTextDevice(NamedTuple):
+    """`decode_rows_text_device`: `DecodedRowsDevice` with the repaired text in data / byte_off (n_bytes bytes), char_off, repl_off and
+    n_replaced.  tokens .. stop_col are valid until the core's next decode-rows call that succeeds, the others until its next repair call
+    (with n_replaced == 0 data and byte_off are the decode buffers: until its next decode call)."""
+    tokens: int
+    tok_off: int
+    n_kept: int
+    stop_col: int
+    data: int
+    byte_off: int
+    char_off: int
+    repl_off: int
+    n_tokens: int
+    n_bytes: int
+    n_replaced: int
+
+
+def repair_mode(errors: str) -> int:
+    """errors= of the text entries -> TK_U8_REPLACE / TK_U8_IGNORE"""
+    if errors == "replace":
+        return _lib.U8_REPLACE
+    if errors == "ignore":
+        return _lib.U8_IGNORE
+    raise ValueError(f"errors={errors!r}: the packed text entries repair on the device with errors='replace' or 'ignore'; for 'strict' and other "
+                     "handlers use decode, decode_batch or decode_rows (or decode_with_offsets_packed, which validates)")
 
 
 class DisallowedSpecialError(ValueError):
@@ -768,11 +836,8 @@ class CoreBPE:
             raise ValueError(f"{name} must hold one column index below 2^32 per row")
         return np.ascontiguousarray(a, dtype=np.uint32)
 
-    def decode_rows_packed(self, ids: np.ndarray, *, begin=None, end=None, stop: Sequence[int] = (), skip: Sequence[int] = (), skip_special: bool = False,
-                           keep_stop: bool = False) -> DecodedRows:
-        """One GPU call for an id matrix in host memory (tk_decode_rows): a 2-D array of uint32, int32 or int64 whose column stride is one
-        element -- any row stride of at least a row: a column slice of a wider matrix is not copied first."""
-        self._one_device("decode_rows_packed")
+    def _host_matrix(self, ids, begin, end, stop, skip, skip_special: bool, keep_stop: bool):
+        """(ids, n_rows, width, ld, begin, end, spec) of an id matrix in host memory, checked"""
         ids = np.asarray(ids)
         if ids.ndim != 2:
             raise ValueError("an id matrix has two dimensions")
@@ -786,7 +851,14 @@ class CoreBPE:
             if ids.strides[0] % item or ids.strides[0] < width * item:
                 raise ValueError("the row stride of an id matrix must be a whole number of elements, at least a row")
             ld = ids.strides[0] // item
-        begin, end = self._row_bounds(begin, n_rows, "begin"), self._row_bounds(end, n_rows, "end")
+        return ids, n_rows, width, ld, self._row_bounds(begin, n_rows, "begin"), self._row_bounds(end, n_rows, "end"), spec
+
+    def decode_rows_packed(self, ids: np.ndarray, *, begin=None, end=None, stop: Sequence[int] = (), skip: Sequence[int] = (), skip_special: bool = False,
+                           keep_stop: bool = False) -> DecodedRows:
+        """One GPU call for an id matrix in host memory (tk_decode_rows): a 2-D array of uint32, int32 or int64 whose column stride is one
+        element -- any row stride of at least a row: a column slice of a wider matrix is not copied first."""
+        self._one_device("decode_rows_packed")
+        ids, n_rows, width, ld, begin, end, spec = self._host_matrix(ids, begin, end, stop, skip, skip_special, keep_stop)
         out, cnt, refs = self._outs(6, 2)
         rc = self._L.tk_decode_rows(self._h, ids.ctypes.data if n_rows and width else None, n_rows, width, ld, None if begin is None else begin.ctypes.data,
                                     None if end is None else end.ctypes.data, ctypes.byref(spec), *refs)
@@ -794,6 +866,60 @@ class CoreBPE:
         n_tokens, n_bytes = (int(x.value) for x in cnt)
         return DecodedRows(_take_u8(out[4], n_bytes), _take_u64(out[5], n_rows + 1), _take_u32(out[0], n_tokens), _take_u64(out[1], n_rows + 1),
                            _take_u32(out[2], n_rows), _take_u32(out[3], n_rows))
+
+    # ------------------------------------------------------------------ text instead of bytes: errors="replace" / "ignore" on the device
+    def utf8_repair_device(self, d_bytes: int, n_bytes: int, d_byte_off: int, n_docs: int, errors: str = "replace", stream: int = 0) -> RepairedDevice:
+        """UTF-8 repair of packed text that is on this core's device (tk_utf8_repair_device): d_bytes 16-byte aligned and readable for 16
+        bytes past n_bytes (the decode buffers are), d_byte_off uint64[n_docs + 1] ascending from 0 to n_bytes."""
+        self._one_device("utf8_repair_device")
+        out, cnt = [ctypes.c_void_p() for _ in range(4)], [ctypes.c_uint64(), ctypes.c_uint64()]
+        rc = self._L.tk_utf8_repair_device(self._h, d_bytes or None, n_bytes, d_byte_off or None, n_docs, repair_mode(errors), stream or None, ctypes.byref(out[0]),
+                                           ctypes.byref(cnt[0]), ctypes.byref(out[1]), ctypes.byref(out[2]), ctypes.byref(out[3]), ctypes.byref(cnt[1]))
+        _lib.raise_for(rc)
+        return RepairedDevice(*[x.value or 0 for x in out], int(cnt[0].value), int(cnt[1].value))
+
+    def decode_batch_text_packed(self, tokens: np.ndarray, tok_off: np.ndarray, errors: str = "replace") -> "tuple[RepairedText, int]":
+        """One GPU call for a packed batch (tk_decode_batch_text): (`RepairedText`, units replaced)."""
+        self._one_device("decode_batch_text_packed")
+        mode = repair_mode(errors)
+        tokens = np.ascontiguousarray(tokens, dtype=np.uint32)
+        tok_off = np.ascontiguousarray(tok_off, dtype=np.uint64)
+        if tok_off.ndim != 1 or len(tok_off) < 1 or int(tok_off[-1]) != len(tokens):
+            raise ValueError("tok_off must hold n_docs + 1 offsets ending at len(tokens)")
+        n_docs = len(tok_off) - 1
+        out, cnt = [ctypes.c_void_p() for _ in range(4)], [ctypes.c_uint64(), ctypes.c_uint64()]
+        src = tokens if len(tokens) else np.zeros(1, dtype=np.uint32)
+        rc = self._L.tk_decode_batch_text(self._h, src.ctypes.data, tok_off.ctypes.data, n_docs, mode, ctypes.byref(out[0]), ctypes.byref(cnt[0]), ctypes.byref(out[1]),
+                                          ctypes.byref(out[2]), ctypes.byref(out[3]), ctypes.byref(cnt[1]))
+        _lib.raise_for(rc)
+        return RepairedText(_take_u8(out[0], int(cnt[0].value)), *[_take_u64(p, n_docs + 1) for p in out[1:]]), int(cnt[1].value)
+
+    def decode_rows_text_device(self, d_ids: int, n_rows: int, width: int, ld: int | None = None, *, dtype=np.int64, d_begin: int = 0, d_end: int = 0,
+                                stop: Sequence[int] = (), skip: Sequence[int] = (), skip_special: bool = False, keep_stop: bool = False, errors: str = "replace",
+                                stream: int = 0) -> DecodedRowsTextDevice:
+        """`decode_rows_device` with text for bytes (tk_decode_rows_text_device)."""
+        self._one_device("decode_rows_text_device")
+        mode = repair_mode(errors)
+        spec = self._drows_spec(dtype, stop, skip, skip_special, keep_stop)
+        out, cnt, refs = self._outs(8, 3)
+        rc = self._L.tk_decode_rows_text_device(self._h, d_ids or None, n_rows, width, width if ld is None else ld, d_begin or None, d_end or None, ctypes.byref(spec), mode,
+                                                stream or None, *refs)
+        _lib.raise_for(rc)
+        return DecodedRowsTextDevice(*[x.value or 0 for x in out], *[int(x.value) for x in cnt])
+
+    def decode_rows_text_packed(self, ids: np.ndarray, *, begin=None, end=None, stop: Sequence[int] = (), skip: Sequence[int] = (), skip_special: bool = False,
+                                keep_stop: bool = False, errors: str = "replace") -> DecodedRowsText:
+        """`decode_rows_packed` with text for bytes (tk_decode_rows_text); the matrix as there."""
+        self._one_device("decode_rows_text_packed")
+        mode = repair_mode(errors)
+        ids, n_rows, width, ld, begin, end, spec = self._host_matrix(ids, begin, end, stop, skip, skip_special, keep_stop)
+        out, cnt, refs = self._outs(8, 3)
+        rc = self._L.tk_decode_rows_text(self._h, ids.ctypes.data if n_rows and width else None, n_rows, width, ld, None if begin is None else begin.ctypes.data,
+                                         None if end is None else end.ctypes.data, ctypes.byref(spec), mode, *refs)
+        _lib.raise_for(rc)
+        n_tokens, n_bytes, _ = (int(x.value) for x in cnt)
+        return DecodedRowsText(_take_u8(out[4], n_bytes), _take_u64(out[5], n_rows + 1), _take_u32(out[0], n_tokens), _take_u64(out[1], n_rows + 1),
+                               _take_u32(out[2], n_rows), _take_u32(out[3], n_rows), _take_u64(out[6], n_rows + 1), _take_u64(out[7], n_rows + 1))
 
     # ------------------------------------------------------------------ token spans (tiktoken/core.py:303-335 over batches)
     def _one_device(self, what: str) -> None:

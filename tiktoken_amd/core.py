@@ -597,6 +597,55 @@ class Encoding:
         return self._core_bpe.decode_rows_packed(ids, begin=begin, end=end, **kw)
 
     def _decode_rows_tensor(self, ids, begin, end, kw) -> "_tiktoken.DecodedRows":
+        r, host = self._rows_tensor_call(ids, begin, end, lambda **a: self._core_bpe.decode_rows_device(**a, **kw))
+        n_rows = ids.shape[0]
+        return _tiktoken.DecodedRows(host(r.data, r.n_bytes, "|u1", np.uint8), host(r.byte_off, n_rows + 1, "<i8", np.uint64), host(r.tokens, r.n_tokens, "<i4", np.uint32),
+                                     host(r.tok_off, n_rows + 1, "<i8", np.uint64), host(r.n_kept, n_rows, "<i4", np.uint32), host(r.stop_col, n_rows, "<i4", np.uint32))
+
+    def decode_rows_bytes(self, ids, *, begin=None, end=None, stop=(), skip=(), skip_special: bool = False, keep_stop: bool = False) -> list[bytes]:
+        """The bytes of every row of an id matrix; the arguments as in `decode_rows_packed`."""
+        rows = self.decode_rows_packed(ids, begin=begin, end=end, stop=stop, skip=skip, skip_special=skip_special, keep_stop=keep_stop)
+        view, bounds = memoryview(rows.data), rows.byte_off.tolist()
+        return [bytes(view[a:b]) for a, b in zip(bounds[:-1], bounds[1:])]
+
+    def decode_rows(self, ids, *, begin=None, end=None, stop=(), skip=(), skip_special: bool = False, keep_stop: bool = False,
+                    errors: str = "replace") -> list[str]:
+        """The text of every row of an id matrix: `[enc.decode(trimmed_row) for row in ids]` without the host loop that trims.  The
+        arguments as in `decode_rows_packed`; `errors` as in `decode`, applied per row on the host.  The defaults skip nothing and stop
+        nowhere."""
+        rows = self.decode_rows_packed(ids, begin=begin, end=end, stop=stop, skip=skip, skip_special=skip_special, keep_stop=keep_stop)
+        view, bounds = memoryview(rows.data), rows.byte_off.tolist()
+        return [str(view[a:b], "utf-8", errors) if b > a else "" for a, b in zip(bounds[:-1], bounds[1:])]
+
+    # ---- packed text: errors="replace" / "ignore" applied on the device, the result well-formed UTF-8 in one array
+    def decode_batch_text_packed(self, tokens: "npt.NDArray[np.uint32]", tok_off: "npt.NDArray[np.uint64]", errors: str = "replace") -> "_tiktoken.RepairedText":
+        """`decode_batch(..., errors=errors)` for a packed batch (ids of all documents back to back, tok_off uint64[n + 1]) as ONE array of
+        well-formed UTF-8: (data, text_off, char_off, repl_off) -- document d is data[text_off[d] : text_off[d + 1]], the bytes of
+        `decode(doc, errors=errors).encode()`; char_off counts its chars and repl_off the ill-formed units that were replaced by U+FFFD
+        (errors="replace") or dropped ("ignore"), both as running totals of n + 1 entries.  One GPU call (tk_decode_batch_text), no host
+        loop over the documents: the array goes into an Arrow string column or a JSONL writer as it is.  KeyError for an id without a
+        token, as `decode_batch`.  errors="strict" and other handlers are not run on the device: ValueError naming the entries that take them."""
+        return self._core_bpe.decode_batch_text_packed(tokens, tok_off, errors)[0]
+
+    def decode_rows_text_packed(self, ids, *, begin=None, end=None, stop=(), skip=(), skip_special: bool = False, keep_stop: bool = False,
+                                errors: str = "replace") -> "_tiktoken.DecodedRowsText":
+        """`decode_rows_packed` with text for bytes (tk_decode_rows_text / tk_decode_rows_text_device): the rows are trimmed and decoded as
+        there, then repaired on the device -- a char that the stop id, begin, end or a skipped id cuts becomes U+FFFD (errors="replace")
+        or nothing ("ignore"), as in `decode_rows(..., errors=errors)`, and data is well-formed UTF-8.  See `_tiktoken.DecodedRowsText`;
+        `ids` and the other arguments as in `decode_rows_packed`."""
+        _tiktoken.repair_mode(errors)  # (refused before anything runs)
+        kw = dict(stop=self._row_ids(stop, "stop"), skip=self._row_ids(skip, "skip"), skip_special=skip_special, keep_stop=keep_stop)
+        if not (hasattr(ids, "data_ptr") and hasattr(ids, "is_cuda")):
+            return self._core_bpe.decode_rows_text_packed(ids, begin=begin, end=end, errors=errors, **kw)
+        r, host = self._rows_tensor_call(ids, begin, end, lambda **a: self._core_bpe.decode_rows_text_device(errors=errors, **a, **kw))
+        n_rows = ids.shape[0]
+        return _tiktoken.DecodedRowsText(host(r.data, r.n_bytes, "|u1", np.uint8), host(r.byte_off, n_rows + 1, "<i8", np.uint64), host(r.tokens, r.n_tokens, "<i4", np.uint32),
+                                         host(r.tok_off, n_rows + 1, "<i8", np.uint64), host(r.n_kept, n_rows, "<i4", np.uint32), host(r.stop_col, n_rows, "<i4", np.uint32),
+                                         host(r.char_off, n_rows + 1, "<i8", np.uint64), host(r.repl_off, n_rows + 1, "<i8", np.uint64))
+
+    def _rows_tensor_call(self, ids, begin, end, call):
+        """An id tensor on this encoding's GPU through a device entry: (the entry's result, host(ptr, n, typestr, dtype): one of its buffers
+        copied to the host)."""
         import torch
 
         core = self._core_bpe
@@ -619,31 +668,15 @@ class Encoding:
 
         d_begin, d_end = bounds(begin, "begin"), bounds(end, "end")
         torch.cuda.current_stream(ids.device).synchronize()  # (the library runs on a stream of its own: the ids must be there)
-        r = core.decode_rows_device(ids.data_ptr() if n_rows and width else 0, n_rows, width, ld, dtype=dtype, d_begin=d_begin.data_ptr() if d_begin is not None else 0,
-                                    d_end=d_end.data_ptr() if d_end is not None else 0, **kw)
+        r = call(d_ids=ids.data_ptr() if n_rows and width else 0, n_rows=n_rows, width=width, ld=ld, dtype=dtype, d_begin=d_begin.data_ptr() if d_begin is not None else 0,
+                 d_end=d_end.data_ptr() if d_end is not None else 0)
 
         def host(ptr, n, typestr, np_dtype):  # a buffer of the library, copied to the host
             if not n:
                 return np.zeros(0, np_dtype)
             return torch.as_tensor(_DeviceArray(ptr, n, typestr), device=ids.device).cpu().numpy().view(np_dtype)
 
-        return _tiktoken.DecodedRows(host(r.data, r.n_bytes, "|u1", np.uint8), host(r.byte_off, n_rows + 1, "<i8", np.uint64), host(r.tokens, r.n_tokens, "<i4", np.uint32),
-                                     host(r.tok_off, n_rows + 1, "<i8", np.uint64), host(r.n_kept, n_rows, "<i4", np.uint32), host(r.stop_col, n_rows, "<i4", np.uint32))
-
-    def decode_rows_bytes(self, ids, *, begin=None, end=None, stop=(), skip=(), skip_special: bool = False, keep_stop: bool = False) -> list[bytes]:
-        """The bytes of every row of an id matrix; the arguments as in `decode_rows_packed`."""
-        rows = self.decode_rows_packed(ids, begin=begin, end=end, stop=stop, skip=skip, skip_special=skip_special, keep_stop=keep_stop)
-        view, bounds = memoryview(rows.data), rows.byte_off.tolist()
-        return [bytes(view[a:b]) for a, b in zip(bounds[:-1], bounds[1:])]
-
-    def decode_rows(self, ids, *, begin=None, end=None, stop=(), skip=(), skip_special: bool = False, keep_stop: bool = False,
-                    errors: str = "replace") -> list[str]:
-        """The text of every row of an id matrix: `[enc.decode(trimmed_row) for row in ids]` without the host loop that trims.  The
-        arguments as in `decode_rows_packed`; `errors` as in `decode`, applied per row on the host.  The defaults skip nothing and stop
-        nowhere."""
-        rows = self.decode_rows_packed(ids, begin=begin, end=end, stop=stop, skip=skip, skip_special=skip_special, keep_stop=keep_stop)
-        view, bounds = memoryview(rows.data), rows.byte_off.tolist()
-        return [str(view[a:b], "utf-8", errors) if b > a else "" for a, b in zip(bounds[:-1], bounds[1:])]
+        return r, host
 
     def token_byte_values(self) -> list[bytes]:
         return self._core_bpe.token_byte_values()

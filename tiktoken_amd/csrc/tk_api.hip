@@ -25,6 +25,7 @@
 #include "tk_decode.h"
 #include "tk_decode_rows.h"
 #include "tk_offsets.h"
+#include "tk_utf8_repair.h"
 #include "tk_padded.h"
 #include "tk_sample_rows.h"
 #include "tk_samples.h"
@@ -292,6 +293,10 @@ struct tk_core {
     // of every row; d_drows_cnt: the TK_DROWS_WORDS report words, the rows' stop words and the tile counts a call computes until it is
     // accepted; d_drows_in: the matrix, begin and end of a host call.
     Buf d_drows_tok, d_drows_row, d_drows_cnt, d_drows_in;
+    // UTF-8 repair (tk_utf8_repair.h), apart from everything above: d_u8r_text: the repaired text; d_u8r_doc: text_off, char_off, repl_off;
+    // d_u8r_cnt: the TK_U8R_WORDS report words, the workgroups' sums, the lanes' places, the documents' prefixes and the bitmap of document
+    // starts -- everything a call computes until it is accepted.
+    Buf d_u8r_text, d_u8r_doc, d_u8r_cnt;
     // Small calls (tk_k_small) do not take `mu`: the reference's normal use is several threads on one Encoding (core.py:175, a thread pool
     // over encode; lib.rs:232-238 keeps a regex per thread for it), and a small call needs nothing of the shared workspace -- a slot of its
     // own (page-locked text and result buffers the kernel reads and writes directly, merge scratch, a stream) is all.  A caller takes a
@@ -3506,7 +3511,21 @@ extern "C" int tk_decode_rows_device(tk_core* c, const void* d_ids, uint64_t n_r
 }
 
 // A matrix in host memory: its (R - 1) * ld + W elements travel to the device as they lie (a slice keeps its row stride), begin and end behind
-// them, and the six arrays travel back.
+// them (drows_host_in), and the six arrays travel back.
+static int drows_host_in(tk_core* c, hipStream_t s, const void* ids, uint64_t n_rows, uint64_t width, uint64_t ld, const uint32_t* begin, const uint32_t* end,
+                         const TkDrows& p, void** d_ids, uint32_t** d_begin, uint32_t** d_end) {
+    const uint64_t n_elems = n_rows && width ? (n_rows - 1) * ld + width : 0;
+    Carve in;
+    const uint64_t at_ids = in.add(n_elems * tk_drows_elem_size(p.flags)), at_begin = in.add(n_rows * 4), at_end = in.add(n_rows * 4);
+    TRY(ensure(c->d_drows_in, in.total + 16));
+    *d_ids = carved<void>(c->d_drows_in, at_ids);
+    *d_begin = begin ? carved<uint32_t>(c->d_drows_in, at_begin) : nullptr;
+    *d_end = end ? carved<uint32_t>(c->d_drows_in, at_end) : nullptr;
+    if (n_elems) HIPCHK(hipMemcpyAsync(*d_ids, ids, n_elems * tk_drows_elem_size(p.flags), hipMemcpyHostToDevice, s));
+    if (begin && n_rows) HIPCHK(hipMemcpyAsync(*d_begin, begin, n_rows * 4, hipMemcpyHostToDevice, s));
+    if (end && n_rows) HIPCHK(hipMemcpyAsync(*d_end, end, n_rows * 4, hipMemcpyHostToDevice, s));
+    return TK_OK;
+}
 extern "C" int tk_decode_rows(tk_core* c, const void* ids, uint64_t n_rows, uint64_t width, uint64_t ld, const uint32_t* begin, const uint32_t* end,
                               const tk_drows_spec* spec, uint32_t** tokens_out, uint64_t** tok_off_out, uint32_t** n_kept_out, uint32_t** stop_col_out, uint8_t** bytes_out,
                               uint64_t** byte_off_out, uint64_t* n_tokens_out, uint64_t* n_bytes_out) {
@@ -3518,18 +3537,12 @@ extern "C" int tk_decode_rows(tk_core* c, const void* ids, uint64_t n_rows, uint
     return drained(c, [&]() -> int {
         TkDrows p;
         TRY(drows_check_spec(c, spec, n_rows, width, ld, &p));  // (before anything is copied)
-        const uint64_t n_elems = n_rows && width ? (n_rows - 1) * ld + width : 0;
-        Carve in;
-        const uint64_t at_ids = in.add(n_elems * tk_drows_elem_size(p.flags)), at_begin = in.add(n_rows * 4), at_end = in.add(n_rows * 4);
-        TRY(ensure(c->d_drows_in, in.total + 16));
-        void* d_ids = carved<void>(c->d_drows_in, at_ids);
-        uint32_t *d_begin = carved<uint32_t>(c->d_drows_in, at_begin), *d_end = carved<uint32_t>(c->d_drows_in, at_end);
         hipStream_t s = c->stream;
-        if (n_elems) HIPCHK(hipMemcpyAsync(d_ids, ids, n_elems * tk_drows_elem_size(p.flags), hipMemcpyHostToDevice, s));
-        if (begin && n_rows) HIPCHK(hipMemcpyAsync(d_begin, begin, n_rows * 4, hipMemcpyHostToDevice, s));
-        if (end && n_rows) HIPCHK(hipMemcpyAsync(d_end, end, n_rows * 4, hipMemcpyHostToDevice, s));
+        void* d_ids;
+        uint32_t *d_begin, *d_end;
+        TRY(drows_host_in(c, s, ids, n_rows, width, ld, begin, end, p, &d_ids, &d_begin, &d_end));
         DrowsView v;
-        TRY(drows_run(c, s, d_ids, n_rows, width, ld, begin ? d_begin : nullptr, end ? d_end : nullptr, spec, &v));
+        TRY(drows_run(c, s, d_ids, n_rows, width, ld, d_begin, d_end, spec, &v));
         ResultBag bag;
         TRY(bag.fetch(tokens_out, v.tokens, v.n_tokens));
         TRY(bag.fetch(tok_off_out, v.tok_off, n_rows + 1));
@@ -3540,6 +3553,188 @@ extern "C" int tk_decode_rows(tk_core* c, const void* ids, uint64_t n_rows, uint
         bag.give();
         *n_tokens_out = v.n_tokens;
         *n_bytes_out = v.n_bytes;
+        return TK_OK;
+    });
+}
+
+// ------------------------------------------------------------------------------------------
+// UTF-8 repair (tk_utf8_repair.h; the rule: include/tiktoken_amd.h): packed text on the device -> what errors="replace" / "ignore" makes of
+// every document, and the packed decode entries that hand out text instead of bytes.
+// ------------------------------------------------------------------------------------------
+static_assert(TK_U8_REPLACE == TK_U8R_REPLACE && TK_U8_IGNORE == TK_U8R_IGNORE, "repair modes");
+struct RepairView {  // device buffers of the core, valid until its next repair call (text / text_off: the INPUT where nothing was replaced)
+    const uint8_t* text = nullptr;
+    const uint64_t *text_off = nullptr, *char_off = nullptr, *repl_off = nullptr;
+    uint64_t n_text = 0, n_chars = 0, n_replaced = 0;
+};
+// repair_run: the caller holds c->mu.  The host waits once, for the report words -- the first offending offset, the three totals --, refuses
+// or sizes the outputs.  A call that is refused has written into d_u8r_cnt only: the previous result stays whole.
+static int repair_run(tk_core* c, hipStream_t s, const uint8_t* d_bytes, uint64_t n, const uint64_t* d_off, uint64_t n_docs, uint32_t mode, RepairView* out) {
+    if (mode != TK_U8_REPLACE && mode != TK_U8_IGNORE) return fail(TK_VALUE_ERROR, "mode must be TK_U8_REPLACE or TK_U8_IGNORE");
+    if (!d_off || (n && !d_bytes)) return fail(TK_VALUE_ERROR, "null argument");
+    if (((uintptr_t)d_bytes & 15u) || ((uintptr_t)d_off & 7u)) return fail(TK_VALUE_ERROR, "d_bytes must be 16-byte aligned and d_byte_off 8-byte aligned");
+    if (n_docs >= (1ull << 60)) return fail(TK_VALUE_ERROR, "2^60 documents or more");
+    if (n / TK_U8R_BLOCK >= 0x7FFFFFFFull) return fail(TK_VALUE_ERROR, "2^43 bytes or more: a workgroup per 4096 bytes is more than a grid holds -- repair the text in parts");
+    const uint64_t nb = n / TK_U8R_BLOCK + 1, lanes = n / 16 + 1, bm_bytes = (n / 32 + 4) * 4;
+    Carve scratch;
+    const uint64_t at_words = scratch.add(TK_U8R_WORDS * 8), at_sums = scratch.add(3 * nb * 8), at_rel = scratch.add(3 * (n_docs + 1) * 4), at_place = scratch.add(lanes * 2),
+                   at_bm = scratch.add(bm_bytes);
+    TRY(ensure(c->d_u8r_cnt, scratch.total));
+    unsigned long long *words = carved<unsigned long long>(c->d_u8r_cnt, at_words), *sums = carved<unsigned long long>(c->d_u8r_cnt, at_sums);
+    uint32_t *rel = carved<uint32_t>(c->d_u8r_cnt, at_rel), *docb = carved<uint32_t>(c->d_u8r_cnt, at_bm);
+    uint16_t* place = carved<uint16_t>(c->d_u8r_cnt, at_place);
+    const unsigned long long h_words[TK_U8R_WORDS] = {~0ull, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(words, h_words, sizeof h_words, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(docb, 0, bm_bytes, s));
+    const dim3 per_doc(grid_for(n_docs + 1, 256, 4096)), block(256);
+    TRY(timed(c, s, "tk_k_u8r_check", [&] { hipLaunchKernelGGL(tk_k_u8r_check, per_doc, block, 0, s, d_off, n_docs, n, words); }));
+    TRY(timed(c, s, "tk_k_span_mark", [&] { hipLaunchKernelGGL(tk_k_span_mark, per_doc, block, 0, s, d_off, n_docs + 1, n, docb); }));
+    TRY(timed(c, s, "tk_k_u8r_count", [&] {
+        hipLaunchKernelGGL(tk_k_u8r_count, dim3((uint32_t)nb), block, 0, s, d_bytes, n, docb, d_off, n_docs, mode, nb, sums, place, rel);
+    }));
+    TRY(timed(c, s, "tk_k_u8r_scan", [&] { hipLaunchKernelGGL(tk_k_u8r_scan, dim3(3), dim3(1024), 0, s, sums, nb, words); }));
+    unsigned long long got[TK_U8R_WORDS];
+    HIPCHK(hipMemcpyAsync(got, words, sizeof got, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    if (got[TK_U8R_BAD_DOC] != ~0ull)
+        return fail(TK_VALUE_ERROR, "byte_off must ascend from 0 to n_bytes: document " + std::to_string(got[TK_U8R_BAD_DOC]) + " does not");
+    const uint64_t n_text = got[TK_U8R_OUT], n_repl = got[TK_U8R_REPL];
+    TRY(ensure(c->d_u8r_doc, 3 * (n_docs + 1) * 8));
+    uint64_t* doc = c->d_u8r_doc.as<uint64_t>();
+    TRY(timed(c, s, "tk_k_u8r_docs", [&] { hipLaunchKernelGGL(tk_k_u8r_docs, per_doc, block, 0, s, d_off, n_docs, nb, sums, rel, doc); }));
+    if (n_repl) {
+        TRY(ensure(c->d_u8r_text, n_text + 16));
+        if (n)
+            TRY(timed(c, s, "tk_k_u8r_write", [&] {
+                hipLaunchKernelGGL(tk_k_u8r_write, dim3((uint32_t)((n + TK_U8R_BLOCK - 1) / TK_U8R_BLOCK)), block, 0, s, d_bytes, n, docb, mode, sums, place,
+                                   c->d_u8r_text.as<uint8_t>());
+            }));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    out->text = n_repl ? c->d_u8r_text.as<uint8_t>() : d_bytes;
+    out->text_off = n_repl ? doc : d_off;
+    out->char_off = doc + (n_docs + 1);
+    out->repl_off = doc + 2 * (n_docs + 1);
+    out->n_text = n_text;
+    out->n_chars = got[TK_U8R_CHARS];
+    out->n_replaced = n_repl;
+    return TK_OK;
+}
+
+extern "C" int tk_utf8_repair_device(tk_core* c, const void* d_bytes, uint64_t n_bytes, const void* d_byte_off, uint64_t n_docs, uint32_t mode, void* stream,
+                                     const uint8_t** d_text_out, uint64_t* n_text_out, const uint64_t** d_text_off_out, const uint64_t** d_char_off_out,
+                                     const uint64_t** d_repl_off_out, uint64_t* n_replaced_out) {
+    RepairView v;
+    TRY(device_pass(c, n_text_out && n_replaced_out, stream,
+                    [&](hipStream_t s) { return repair_run(c, s, (const uint8_t*)d_bytes, n_bytes, (const uint64_t*)d_byte_off, n_docs, mode, &v); }));
+    if (d_text_out) *d_text_out = v.text;
+    if (d_text_off_out) *d_text_off_out = v.text_off;
+    if (d_char_off_out) *d_char_off_out = v.char_off;
+    if (d_repl_off_out) *d_repl_off_out = v.repl_off;
+    *n_text_out = v.n_text;
+    *n_replaced_out = v.n_replaced;
+    return TK_OK;
+}
+
+// Host ids in, host text out: the ids and their offsets in one copy, decode_device_run, the repair over its bytes, one copy out.  One pass:
+// the overlapped ranges of tk_decode_batch are not built for it.
+extern "C" int tk_decode_batch_text(tk_core* c, const uint32_t* tokens, const uint64_t* tok_off, uint64_t n_docs, uint32_t mode, uint8_t** text_out, uint64_t* n_text_out,
+                                    uint64_t** text_off_out, uint64_t** char_off_out, uint64_t** repl_off_out, uint64_t* n_replaced_out) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if (!tok_off || !text_out || !n_text_out || !text_off_out || !char_off_out || !repl_off_out || !n_replaced_out) return fail(TK_VALUE_ERROR, "null argument");
+    TRY(check_offsets(tok_off, n_docs, "tok_off"));
+    TRY(decode_table_check(c));
+    const uint64_t n = tok_off[n_docs];
+    if (n && !tokens) return fail(TK_VALUE_ERROR, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    return drained(c, [&]() -> int {
+        hipStream_t s = c->stream;
+        DecodeView dv;
+        TRY(ensure(c->d_tok, (n + 1) * 4));
+        TRY(decode_view(c, n, 0, true, true, n_docs, &dv));  // (decode_device_run makes the same view again)
+        uint64_t* const d_tok_off = dv.tok_off;
+        HIPCHK(hipMemcpyAsync(d_tok_off, tok_off, (n_docs + 1) * 8, hipMemcpyHostToDevice, s));
+        if (n) HIPCHK(hipMemcpyAsync(c->d_tok.p, tokens, n * 4, hipMemcpyHostToDevice, s));
+        uint64_t n_bytes = 0;
+        TRY(decode_device_run(c, s, c->d_tok.as<uint32_t>(), n, d_tok_off, n_docs, &dv, &n_bytes));  // (TK_KEY_ERROR names the id from its device copy)
+        RepairView v;
+        TRY(repair_run(c, s, c->d_bytes.as<uint8_t>(), n_bytes, dv.byte_off, n_docs, mode, &v));
+        ResultBag bag;
+        TRY(bag.fetch(text_out, v.text, v.n_text));
+        TRY(bag.fetch(text_off_out, v.text_off, n_docs + 1));
+        TRY(bag.fetch(char_off_out, v.char_off, n_docs + 1));
+        TRY(bag.fetch(repl_off_out, v.repl_off, n_docs + 1));
+        bag.give();
+        *n_text_out = v.n_text;
+        *n_replaced_out = v.n_replaced;
+        return TK_OK;
+    });
+}
+
+// The decode-rows passes unchanged, then the repair over their bytes.
+extern "C" int tk_decode_rows_text_device(tk_core* c, const void* d_ids, uint64_t n_rows, uint64_t width, uint64_t ld, const void* d_begin, const void* d_end,
+                                          const tk_drows_spec* spec, uint32_t mode, void* stream, const uint32_t** d_tokens_out, const uint64_t** d_tok_off_out,
+                                          const uint32_t** d_n_kept_out, const uint32_t** d_stop_col_out, const uint8_t** d_text_out, const uint64_t** d_text_off_out,
+                                          const uint64_t** d_char_off_out, const uint64_t** d_repl_off_out, uint64_t* n_tokens_out, uint64_t* n_text_out,
+                                          uint64_t* n_replaced_out) {
+    if (mode != TK_U8_REPLACE && mode != TK_U8_IGNORE) return fail(TK_VALUE_ERROR, "mode must be TK_U8_REPLACE or TK_U8_IGNORE");  // (before the rows passes write)
+    DrowsView v;
+    RepairView t;
+    TRY(device_pass(c, spec && n_tokens_out && n_text_out && n_replaced_out && (d_ids || !n_rows || !width), stream, [&](hipStream_t s) -> int {
+        TRY(drows_run(c, s, d_ids, n_rows, width, ld, (const uint32_t*)d_begin, (const uint32_t*)d_end, spec, &v));
+        return repair_run(c, s, v.bytes, v.n_bytes, v.byte_off, n_rows, mode, &t);
+    }));
+    if (d_tokens_out) *d_tokens_out = v.tokens;
+    if (d_tok_off_out) *d_tok_off_out = v.tok_off;
+    if (d_n_kept_out) *d_n_kept_out = v.n_kept;
+    if (d_stop_col_out) *d_stop_col_out = v.stop_col;
+    if (d_text_out) *d_text_out = t.text;
+    if (d_text_off_out) *d_text_off_out = t.text_off;
+    if (d_char_off_out) *d_char_off_out = t.char_off;
+    if (d_repl_off_out) *d_repl_off_out = t.repl_off;
+    *n_tokens_out = v.n_tokens;
+    *n_text_out = t.n_text;
+    *n_replaced_out = t.n_replaced;
+    return TK_OK;
+}
+extern "C" int tk_decode_rows_text(tk_core* c, const void* ids, uint64_t n_rows, uint64_t width, uint64_t ld, const uint32_t* begin, const uint32_t* end,
+                                   const tk_drows_spec* spec, uint32_t mode, uint32_t** tokens_out, uint64_t** tok_off_out, uint32_t** n_kept_out, uint32_t** stop_col_out,
+                                   uint8_t** text_out, uint64_t** text_off_out, uint64_t** char_off_out, uint64_t** repl_off_out, uint64_t* n_tokens_out,
+                                   uint64_t* n_text_out, uint64_t* n_replaced_out) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if (!spec || !tokens_out || !tok_off_out || !n_kept_out || !stop_col_out || !text_out || !text_off_out || !char_off_out || !repl_off_out || !n_tokens_out || !n_text_out ||
+        !n_replaced_out || (!ids && n_rows && width))
+        return fail(TK_VALUE_ERROR, "null argument");
+    if (mode != TK_U8_REPLACE && mode != TK_U8_IGNORE) return fail(TK_VALUE_ERROR, "mode must be TK_U8_REPLACE or TK_U8_IGNORE");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    return drained(c, [&]() -> int {
+        TkDrows p;
+        TRY(drows_check_spec(c, spec, n_rows, width, ld, &p));  // (before anything is copied)
+        hipStream_t s = c->stream;
+        void* d_ids;
+        uint32_t *d_begin, *d_end;
+        TRY(drows_host_in(c, s, ids, n_rows, width, ld, begin, end, p, &d_ids, &d_begin, &d_end));
+        DrowsView v;
+        TRY(drows_run(c, s, d_ids, n_rows, width, ld, d_begin, d_end, spec, &v));
+        RepairView t;
+        TRY(repair_run(c, s, v.bytes, v.n_bytes, v.byte_off, n_rows, mode, &t));
+        ResultBag bag;
+        TRY(bag.fetch(tokens_out, v.tokens, v.n_tokens));
+        TRY(bag.fetch(tok_off_out, v.tok_off, n_rows + 1));
+        TRY(bag.fetch(n_kept_out, v.n_kept, n_rows));
+        TRY(bag.fetch(stop_col_out, v.stop_col, n_rows));
+        TRY(bag.fetch(text_out, t.text, t.n_text));
+        TRY(bag.fetch(text_off_out, t.text_off, n_rows + 1));
+        TRY(bag.fetch(char_off_out, t.char_off, n_rows + 1));
+        TRY(bag.fetch(repl_off_out, t.repl_off, n_rows + 1));
+        bag.give();
+        *n_tokens_out = v.n_tokens;
+        *n_text_out = t.n_text;
+        *n_replaced_out = t.n_replaced;
         return TK_OK;
     });
 }
