@@ -398,6 +398,7 @@ int tk_encode_batch_sample_rows(tk_core* core, const uint8_t* utf8, const uint64
  *   Every refusal is found before any output is written: a refused call leaves the previous result whole.  No kernel reads outside the
  *   (R - 1) * ld + W elements of the matrix, whatever begin and end hold.  One device per call: a group has no such entry.
  *  Text instead of bytes (errors="replace" / "ignore" applied on the device): tk_decode_rows_text_device / tk_decode_rows_text below.
+ *  Rows cut at a stop STRING as well (until=, stop=, stop_strings=): tk_decode_rows_until_device / tk_decode_rows_until below.
  *  NOT built: uint16 matrices; token spans of a matrix (feed tokens and tok_off to tk_token_spans_device); streaming. */
 #define TK_DROWS_KEEP_STOP 1u    /* the stop id that ends a row belongs to it */
 #define TK_DROWS_SKIP_SPECIAL 2u /* special tokens are dropped as if they were in skip_ids */
@@ -450,7 +451,8 @@ int tk_decode_rows(tk_core* core, const void* ids, uint64_t n_rows, uint64_t wid
  *  anything is indexed with them; the message names the first offending document).  A refused call leaves the previous result whole.
  *  No kernel reads outside [d_bytes, d_bytes + n_bytes + 16), whatever the offsets hold.  Holds the core's mutex; `stream`: a
  *  hipStream_t or null (the core's); the call returns when the text is there.  One device per call: a group has no such entry.
- * NOT built: token spans inside repaired text (tk_token_spans_device speaks of the bytes before repair). */
+ * NOT built: token spans inside repaired text (tk_token_spans_device speaks of the bytes before repair).  Stop strings are searched in
+ *  the bytes BEFORE the repair (tk_stop_text_device below, which says why that is the same cut for well-formed stop strings). */
 #define TK_U8_REPLACE 0u /* errors="replace" */
 #define TK_U8_IGNORE 1u  /* errors="ignore" */
 int tk_utf8_repair_device(tk_core* core, const void* d_bytes, uint64_t n_bytes, const void* d_byte_off, uint64_t n_docs, uint32_t mode, void* stream,
@@ -477,6 +479,67 @@ int tk_decode_rows_text(tk_core* core, const void* ids, uint64_t n_rows, uint64_
                         const tk_drows_spec* spec, uint32_t mode, uint32_t** tokens_out, uint64_t** tok_off_out, uint32_t** n_kept_out, uint32_t** stop_col_out,
                         uint8_t** text_out, uint64_t** text_off_out, uint64_t** char_off_out, uint64_t** repl_off_out, uint64_t* n_tokens_out,
                         uint64_t* n_text_out, uint64_t* n_replaced_out);
+/* Stop strings: packed text in HBM -> every document cut at the first place where one of a few stop strings lies.  What evaluation
+ * harnesses call until=["\n\n", "Question:"], servers stop=[...] and generate stop_strings: the end of a generated row that is a piece of
+ * TEXT, not a token -- "\n\n" may be one id, two ids or the tail of ".\n\n" -- and can therefore only be found in the decoded bytes.
+ * Replaces nothing in the reference: it is the host loop of its users (the text copied to the host, find per row and per string).
+ * The rule.  Input: packed text (bytes uint8[n_bytes], byte_off uint64[n_docs + 1]) under the contract of tk_utf8_repair_device, and a
+ *  stop set: n strings, 0 <= n <= 16, of 1 .. 64 bytes each, given as a host blob and off uint32[n + 1] ascending from 0.  Any bytes are
+ *  legal: the search is a byte search.
+ *  Hit.  Document d has the bytes B.  A hit is a pair (p, k) with B[p : p + len(s_k)] == s_k that lies entirely inside the document: a
+ *   match that needs a byte of the next document is none, and neither is one that needs a byte behind n_bytes.
+ *  Per document.  cut[d] = the least p over all hits, or len(B) without one.  hit[d] = the least k among the hits at p == cut[d], or
+ *   0xFFFFFFFF without one: position decides before list order, and list order between "ab" and "abc" at one place.  The kept length
+ *   is cut[d]; with TK_STOPS_KEEP and a hit, cut[d] + len(s_hit): the stop string that ends a document then belongs to it.
+ *  Output.  text: the kept prefixes back to back; text_off uint64[n_docs + 1]; hit uint32[n_docs]; *n_hit_out: the documents with a hit.
+ *   With *n_hit_out == 0 nothing is written: *d_text_out == d_bytes and *d_text_off_out == d_byte_off, the caller's own, as the repair
+ *   hands them back with *n_replaced_out == 0; hit is made all the same.  n == 0, n_docs == 0 and n_bytes == 0 are legal.
+ *  TK_VALUE_ERROR, before any output is written (a refused call leaves the previous result whole): more than 16 strings, an empty
+ *   string, a string over 64 bytes, stop offsets that do not ascend from 0, an unknown flag, a misaligned pointer, and the repair's limits
+ *   on n_bytes and byte_off (checked on the device before anything is indexed with them; the message names the first offending
+ *   document).  No kernel reads outside [d_bytes, d_bytes + n_bytes + 16), whatever the offsets hold.
+ * Order with the repair: search, cut, then repair.  For well-formed stop strings the order does not matter: a stop string starts with an
+ *  ASCII byte or a lead byte, and no ill-formed unit before it can swallow that byte (a unit only ever accepts continuation bytes); its
+ *  last char is complete, so the unit that ends it ends with it.  The repair of the bytes before a hit is therefore the same whether or
+ *  not the hit and what follows is still there: repair(cut(B)) is the matching prefix of repair(B).  Under TK_U8_REPLACE, for stop strings
+ *  that do not contain U+FFFD themselves, the cut is where str.find on the replaced text puts it.  The search IS on the bytes before the
+ *  repair: under TK_U8_IGNORE, dropping a unit can join "ab" and "cd" around it into a "bc" that the text shows and the search never
+ *  saw; and a stop string that contains U+FFFD matches the bytes EF BF BD of the input only, never a replaced unit.
+ * In / out: d_bytes and d_byte_off as tk_utf8_repair_device takes them.  *d_text_out, *d_text_off_out, *d_hit_out: buffers of the core
+ *  that belong to this entry alone, valid until the core's next stop-string call (this entry, tk_decode_rows_until_device,
+ *  tk_decode_rows_until).  The input must not be this entry's own previous output.  Holds the core's mutex; `stream`: a hipStream_t or
+ *  null (the core's); the call returns when the text is there.  One device per call: a group has no such entry.
+ * NOT built: streaming (no state carried between calls, no per-document start offset of the search). */
+#define TK_STOPS_KEEP 1u /* the stop string that ends a document belongs to it */
+typedef struct {
+    uint32_t n;           /* strings: 0 .. 16 */
+    const uint8_t* blob;  /* the strings back to back (host memory) */
+    const uint32_t* off;  /* uint32[n + 1], ascending from 0: string k is blob[off[k] : off[k + 1]]; may be null with n == 0 */
+} tk_stops;
+int tk_stop_text_device(tk_core* core, const void* d_bytes, uint64_t n_bytes, const void* d_byte_off, uint64_t n_docs, const tk_stops* stops, uint32_t flags,
+                        void* stream, const uint8_t** d_text_out, uint64_t* n_text_out, const uint64_t** d_text_off_out, const uint32_t** d_hit_out,
+                        uint64_t* n_hit_out);
+/* tk_decode_rows_text_device / tk_decode_rows_text with stop strings.  The tk_decode_rows_device rule runs unchanged first -- begin, end,
+ * stop ids, skip ids; its refusals and errors, TK_KEY_ERROR included, come first and unchanged --, each row's kept bytes are then a
+ * document of the search above, and the cut text is repaired: mode TK_U8_REPLACE, TK_U8_IGNORE, or TK_U8_BYTES -- no repair, the cut bytes
+ * as they are, *d_char_off_out and *d_repl_off_out null.  What lies behind a stop id is never searched; a stop string may be spelled
+ * across a skipped id.  One more output, n_tok uint32[R]: the number of the row's kept tokens whose first byte lies before the end of
+ * the kept text (before the repair) -- 0 for empty kept text; a token that the cut splits counts.  With empty skip lists begin[r] +
+ * n_tok[r] is the column behind the last token used.  *d_hit_out and *d_n_tok_out are valid until the core's next stop-string call.
+ * NOT built: that column under skip lists. */
+#define TK_U8_BYTES 2u /* tk_decode_rows_until*: no repair */
+int tk_decode_rows_until_device(tk_core* core, const void* d_ids, uint64_t n_rows, uint64_t width, uint64_t ld, const void* d_begin, const void* d_end,
+                                const tk_drows_spec* spec, const tk_stops* stops, uint32_t stop_flags, uint32_t mode, void* stream,
+                                const uint32_t** d_tokens_out, const uint64_t** d_tok_off_out, const uint32_t** d_n_kept_out, const uint32_t** d_stop_col_out,
+                                const uint8_t** d_text_out, const uint64_t** d_text_off_out, const uint64_t** d_char_off_out, const uint64_t** d_repl_off_out,
+                                const uint32_t** d_hit_out, const uint32_t** d_n_tok_out, uint64_t* n_tokens_out, uint64_t* n_text_out,
+                                uint64_t* n_replaced_out, uint64_t* n_hit_out);
+/* ... for a matrix in host memory: host arrays out, library-owned (tk_free); *char_off_out and *repl_off_out null under TK_U8_BYTES. */
+int tk_decode_rows_until(tk_core* core, const void* ids, uint64_t n_rows, uint64_t width, uint64_t ld, const uint32_t* begin, const uint32_t* end,
+                         const tk_drows_spec* spec, const tk_stops* stops, uint32_t stop_flags, uint32_t mode, uint32_t** tokens_out, uint64_t** tok_off_out,
+                         uint32_t** n_kept_out, uint32_t** stop_col_out, uint8_t** text_out, uint64_t** text_off_out, uint64_t** char_off_out,
+                         uint64_t** repl_off_out, uint32_t** hit_out, uint32_t** n_tok_out, uint64_t* n_tokens_out, uint64_t* n_text_out,
+                         uint64_t* n_replaced_out, uint64_t* n_hit_out);
 /* bpe_train(data, vocab_size, pat_str, visualise=None)                      tiktoken/_educational.py:119-185
  * Training a vocabulary: the merges the reference's educational trainer makes on the same text -- the same pairs in the same order -- for a
  * packed batch of documents, under the core's pat_str (stock scanners or the generic engine).  The core's ranks and special tokens play

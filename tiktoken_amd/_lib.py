@@ -58,6 +58,12 @@ class DrowsSpec(ctypes.Structure):
 
 DROWS_KEEP_STOP, DROWS_SKIP_SPECIAL, DROWS_I32, DROWS_I64 = 1, 2, 4, 8
 U8_REPLACE, U8_IGNORE = 0, 1  # TK_U8_REPLACE, TK_U8_IGNORE
+U8_BYTES = 2  # TK_U8_BYTES (the stop-string entries over id matrices: no repair)
+STOPS_KEEP = 1  # TK_STOPS_KEEP
+
+
+class Stops(ctypes.Structure):  # tk_stops
+    _fields_ = [("n", ctypes.c_uint32), ("blob", ctypes.c_void_p), ("off", ctypes.c_void_p)]
 
 
 def build(force: bool = False) -> str:
@@ -151,6 +157,13 @@ def lib() -> ctypes.CDLL:
             L.tk_decode_rows_text_device.argtypes = [vp, vp, u64, u64, u64, vp, vp, P(DrowsSpec), u32, vp, *[P(vp)] * 8, P(u64), P(u64), P(u64)]
             L.tk_decode_rows_text.restype = i32
             L.tk_decode_rows_text.argtypes = [vp, vp, u64, u64, u64, vp, vp, P(DrowsSpec), u32, *[P(vp)] * 8, P(u64), P(u64), P(u64)]
+        if hasattr(L, "tk_stop_text_device"):  # (absent from older builds selected through $TIKTOKEN_AMD_LIB)
+            L.tk_stop_text_device.restype = i32
+            L.tk_stop_text_device.argtypes = [vp, vp, u64, vp, u64, P(Stops), u32, vp, P(vp), P(u64), P(vp), P(vp), P(u64)]
+            L.tk_decode_rows_until_device.restype = i32
+            L.tk_decode_rows_until_device.argtypes = [vp, vp, u64, u64, u64, vp, vp, P(DrowsSpec), P(Stops), u32, u32, vp, *[P(vp)] * 10, *[P(u64)] * 4]
+            L.tk_decode_rows_until.restype = i32
+            L.tk_decode_rows_until.argtypes = [vp, vp, u64, u64, u64, vp, vp, P(DrowsSpec), P(Stops), u32, u32, *[P(vp)] * 10, *[P(u64)] * 4]
         L.tk_decode_single_token_bytes.restype = i32
         L.tk_decode_single_token_bytes.argtypes = [vp, u32, P(vp), P(u64)]
         L.tk_n_tokens.restype = u64

@@ -361,6 +361,79 @@ class DecodedRowsTextDevice(NamedTuple):
     n_replaced: int
 
 
+class StoppedTextDevice(NamedTuple):
+    """`stop_text_device`: device pointers and the figures that size them: data holds n_bytes bytes, text_off n_docs + 1 entries, hit
+    n_docs.  The core's buffers, valid until its next stop-string call -- but with n_hit == 0 data and text_off are the caller's own input
+    pointers: nothing was written."""
+    data: int
+    text_off: int
+    hit: int
+    n_bytes: int
+    n_hit: int
+
+
+@dataclasses.dataclass(frozen=True)
+class StoppedRows:
+    """`DecodedRowsText` of rows that were cut at their first stop string as well (tk_decode_rows_until; the rule:
+    include/tiktoken_amd.h, tk_stop_text_device): row r is data[byte_off[r] : byte_off[r + 1]]; hit[r] is the index of the stop string
+    that ended it (NO_HIT: none did); n_tok[r] counts the row's kept tokens whose first byte lies before the end of the kept text.
+    char_off and repl_off are None in the bytes mode, which repairs nothing."""
+    data: np.ndarray  # uint8
+    byte_off: np.ndarray  # uint64[R + 1]
+    char_off: "np.ndarray | None"  # uint64[R + 1]
+    repl_off: "np.ndarray | None"  # uint64[R + 1]
+    tokens: np.ndarray  # uint32[K]
+    tok_off: np.ndarray  # uint64[R + 1]
+    n_kept: np.ndarray  # uint32[R]
+    stop_col: np.ndarray  # uint32[R]
+    hit: np.ndarray  # uint32[R]
+    n_tok: np.ndarray  # uint32[R]
+
+    NO_HIT = 0xFFFFFFFF
+
+
+class StoppedRowsDevice(NamedTuple):
+    """`decode_rows_until_device`: `DecodedRowsTextDevice` with hit and n_tok (valid until the core's next stop-string call) and n_hit;
+    char_off and repl_off are 0 in the bytes mode."""
+    tokens: int
+    tok_off: int
+    n_kept: int
+    stop_col: int
+    data: int
+    byte_off: int
+    char_off: int
+    repl_off: int
+    hit: int
+    n_tok: int
+    n_tokens: int
+    n_bytes: int
+    n_replaced: int
+    n_hit: int
+
+
+def until_mode(errors: "str | None") -> int:
+    """errors= of the stop-string entries -> TK_U8_REPLACE / TK_U8_IGNORE, None -> TK_U8_BYTES"""
+    return _lib.U8_BYTES if errors is None else repair_mode(errors)
+
+
+class _StopSet:
+    """stop strings (str: its UTF-8; bytes) as a tk_stops, with the arrays it points into"""
+
+    def __init__(self, stop_text):
+        if isinstance(stop_text, (str, bytes, bytearray)):
+            stop_text = (stop_text,)
+        strings = [s.encode("utf-8") if isinstance(s, str) else bytes(s) for s in stop_text]
+        self.strings = strings
+        self.blob = np.frombuffer(b"".join(strings) + b"\0", dtype=np.uint8)
+        self.off = np.zeros(len(strings) + 1, dtype=np.uint32)
+        total = sum(map(len, strings))
+        if total >= 1 << 32:
+            raise ValueError("stop strings of 4 GiB or more")
+        if strings:
+            self.off[1:] = np.cumsum([len(s) for s in strings])
+        self.c = _lib.Stops(len(strings), self.blob.ctypes.data, self.off.ctypes.data)
+
+
 def repair_mode(errors: str) -> int:
     """errors= of the text entries -> TK_U8_REPLACE / TK_U8_IGNORE"""
     if errors == "replace":
@@ -920,6 +993,50 @@ class CoreBPE:
         n_tokens, n_bytes, _ = (int(x.value) for x in cnt)
         return DecodedRowsText(_take_u8(out[4], n_bytes), _take_u64(out[5], n_rows + 1), _take_u32(out[0], n_tokens), _take_u64(out[1], n_rows + 1),
                                _take_u32(out[2], n_rows), _take_u32(out[3], n_rows), _take_u64(out[6], n_rows + 1), _take_u64(out[7], n_rows + 1))
+
+    # ------------------------------------------------------------------ stop strings: rows and documents cut at the first stop text
+    def stop_text_device(self, d_bytes: int, n_bytes: int, d_byte_off: int, n_docs: int, stop_text, keep_stop_text: bool = False, stream: int = 0) -> StoppedTextDevice:
+        """Packed text on this core's device cut at every document's first stop string (tk_stop_text_device): the buffers as
+        `utf8_repair_device` takes them; stop_text: up to 16 str (their UTF-8) or bytes of 1 .. 64 bytes each."""
+        self._one_device("stop_text_device")
+        stops = _StopSet(stop_text)
+        out, cnt = [ctypes.c_void_p() for _ in range(3)], [ctypes.c_uint64(), ctypes.c_uint64()]
+        rc = self._L.tk_stop_text_device(self._h, d_bytes or None, n_bytes, d_byte_off or None, n_docs, ctypes.byref(stops.c), _lib.STOPS_KEEP if keep_stop_text else 0,
+                                         stream or None, ctypes.byref(out[0]), ctypes.byref(cnt[0]), ctypes.byref(out[1]), ctypes.byref(out[2]), ctypes.byref(cnt[1]))
+        _lib.raise_for(rc)
+        return StoppedTextDevice(*[x.value or 0 for x in out], int(cnt[0].value), int(cnt[1].value))
+
+    def decode_rows_until_device(self, d_ids: int, n_rows: int, width: int, ld: int | None = None, *, stop_text, dtype=np.int64, d_begin: int = 0, d_end: int = 0,
+                                 stop: Sequence[int] = (), skip: Sequence[int] = (), skip_special: bool = False, keep_stop: bool = False, keep_stop_text: bool = False,
+                                 errors: "str | None" = "replace", stream: int = 0) -> StoppedRowsDevice:
+        """`decode_rows_text_device` with stop strings (tk_decode_rows_until_device); errors=None: the cut bytes, not repaired."""
+        self._one_device("decode_rows_until_device")
+        mode = until_mode(errors)
+        stops = _StopSet(stop_text)
+        spec = self._drows_spec(dtype, stop, skip, skip_special, keep_stop)
+        out, cnt, refs = self._outs(10, 4)
+        rc = self._L.tk_decode_rows_until_device(self._h, d_ids or None, n_rows, width, width if ld is None else ld, d_begin or None, d_end or None, ctypes.byref(spec),
+                                                 ctypes.byref(stops.c), _lib.STOPS_KEEP if keep_stop_text else 0, mode, stream or None, *refs)
+        _lib.raise_for(rc)
+        return StoppedRowsDevice(*[x.value or 0 for x in out], *[int(x.value) for x in cnt])
+
+    def decode_rows_until_packed(self, ids: np.ndarray, stop_text, *, begin=None, end=None, stop: Sequence[int] = (), skip: Sequence[int] = (), skip_special: bool = False,
+                                 keep_stop: bool = False, keep_stop_text: bool = False, errors: "str | None" = "replace") -> StoppedRows:
+        """`decode_rows_text_packed` with stop strings (tk_decode_rows_until); the matrix as there; errors=None: the cut bytes."""
+        self._one_device("decode_rows_until_packed")
+        mode = until_mode(errors)
+        stops = _StopSet(stop_text)
+        ids, n_rows, width, ld, begin, end, spec = self._host_matrix(ids, begin, end, stop, skip, skip_special, keep_stop)
+        out, cnt, refs = self._outs(10, 4)
+        rc = self._L.tk_decode_rows_until(self._h, ids.ctypes.data if n_rows and width else None, n_rows, width, ld, None if begin is None else begin.ctypes.data,
+                                          None if end is None else end.ctypes.data, ctypes.byref(spec), ctypes.byref(stops.c), _lib.STOPS_KEEP if keep_stop_text else 0, mode,
+                                          *refs)
+        _lib.raise_for(rc)
+        n_tokens, n_bytes = int(cnt[0].value), int(cnt[1].value)
+        text = mode != _lib.U8_BYTES
+        return StoppedRows(_take_u8(out[4], n_bytes), _take_u64(out[5], n_rows + 1), _take_u64(out[6], n_rows + 1) if text else None,
+                           _take_u64(out[7], n_rows + 1) if text else None, _take_u32(out[0], n_tokens), _take_u64(out[1], n_rows + 1), _take_u32(out[2], n_rows),
+                           _take_u32(out[3], n_rows), _take_u32(out[8], n_rows), _take_u32(out[9], n_rows))
 
     # ------------------------------------------------------------------ token spans (tiktoken/core.py:303-335 over batches)
     def _one_device(self, what: str) -> None:

@@ -643,6 +643,47 @@ class Encoding:
                                          host(r.tok_off, n_rows + 1, "<i8", np.uint64), host(r.n_kept, n_rows, "<i4", np.uint32), host(r.stop_col, n_rows, "<i4", np.uint32),
                                          host(r.char_off, n_rows + 1, "<i8", np.uint64), host(r.repl_off, n_rows + 1, "<i8", np.uint64))
 
+    # ---- rows cut at a stop STRING as well (until=, stop=, stop_strings=): searched in the decoded bytes, on the device
+    def decode_rows_until_packed(self, ids, stop_text, *, begin=None, end=None, stop=(), skip=(), skip_special: bool = False, keep_stop: bool = False,
+                                 keep_stop_text: bool = False, errors: "str | None" = "replace") -> "_tiktoken.StoppedRows":
+        """`decode_rows_text_packed` whose rows also end at the first place where one of `stop_text` lies (tk_decode_rows_until /
+        tk_decode_rows_until_device): up to 16 stop strings, each a str (its UTF-8 is searched) or bytes, of 1 .. 64 bytes.  A stop
+        string is text, not a token -- it may be one id, several, or the tail of one -- so it is searched in the row's decoded bytes: the
+        earliest match wins, and at one place the string listed first.  The row rule of `decode_rows_packed` runs first (begin, end,
+        stop ids, skipped ids: what lies behind a stop id is never searched), then the search, the cut, and the repair of the cut text
+        (errors="replace" / "ignore"; None: the cut bytes as they are).  keep_stop_text: the stop string stays at the row's end.
+        See `_tiktoken.StoppedRows`: hit[r] names the string that ended row r, n_tok[r] the tokens the kept text covers."""
+        _tiktoken.until_mode(errors)  # (refused before anything runs)
+        kw = dict(stop=self._row_ids(stop, "stop"), skip=self._row_ids(skip, "skip"), skip_special=skip_special, keep_stop=keep_stop, keep_stop_text=keep_stop_text,
+                  errors=errors)
+        if not (hasattr(ids, "data_ptr") and hasattr(ids, "is_cuda")):
+            return self._core_bpe.decode_rows_until_packed(ids, stop_text, begin=begin, end=end, **kw)
+        r, host = self._rows_tensor_call(ids, begin, end, lambda **a: self._core_bpe.decode_rows_until_device(stop_text=stop_text, **a, **kw))
+        n_rows = ids.shape[0]
+        text = errors is not None
+        return _tiktoken.StoppedRows(host(r.data, r.n_bytes, "|u1", np.uint8), host(r.byte_off, n_rows + 1, "<i8", np.uint64),
+                                     host(r.char_off, n_rows + 1, "<i8", np.uint64) if text else None, host(r.repl_off, n_rows + 1, "<i8", np.uint64) if text else None,
+                                     host(r.tokens, r.n_tokens, "<i4", np.uint32), host(r.tok_off, n_rows + 1, "<i8", np.uint64), host(r.n_kept, n_rows, "<i4", np.uint32),
+                                     host(r.stop_col, n_rows, "<i4", np.uint32), host(r.hit, n_rows, "<i4", np.uint32), host(r.n_tok, n_rows, "<i4", np.uint32))
+
+    def decode_rows_until(self, ids, stop_text, *, begin=None, end=None, stop=(), skip=(), skip_special: bool = False, keep_stop: bool = False,
+                          keep_stop_text: bool = False, errors: str = "replace") -> list[str]:
+        """The text of every row of an id matrix up to its first stop string; the arguments as in `decode_rows_until_packed`
+        (errors: "replace" or "ignore")."""
+        _tiktoken.repair_mode(errors)  # (text: no bytes mode here)
+        rows = self.decode_rows_until_packed(ids, stop_text, begin=begin, end=end, stop=stop, skip=skip, skip_special=skip_special, keep_stop=keep_stop,
+                                             keep_stop_text=keep_stop_text, errors=errors)
+        view, bounds = memoryview(rows.data), rows.byte_off.tolist()
+        return [str(view[a:b], "utf-8") if b > a else "" for a, b in zip(bounds[:-1], bounds[1:])]
+
+    def decode_rows_until_bytes(self, ids, stop_text, *, begin=None, end=None, stop=(), skip=(), skip_special: bool = False, keep_stop: bool = False,
+                                keep_stop_text: bool = False) -> list[bytes]:
+        """The bytes of every row of an id matrix up to its first stop string, not repaired; the arguments as in `decode_rows_until_packed`."""
+        rows = self.decode_rows_until_packed(ids, stop_text, begin=begin, end=end, stop=stop, skip=skip, skip_special=skip_special, keep_stop=keep_stop,
+                                             keep_stop_text=keep_stop_text, errors=None)
+        view, bounds = memoryview(rows.data), rows.byte_off.tolist()
+        return [bytes(view[a:b]) for a, b in zip(bounds[:-1], bounds[1:])]
+
     def _rows_tensor_call(self, ids, begin, end, call):
         """An id tensor on this encoding's GPU through a device entry: (the entry's result, host(ptr, n, typestr, dtype): one of its buffers
         copied to the host)."""

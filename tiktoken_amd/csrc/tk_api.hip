@@ -26,6 +26,7 @@
 #include "tk_decode_rows.h"
 #include "tk_offsets.h"
 #include "tk_utf8_repair.h"
+#include "tk_stop_text.h"
 #include "tk_padded.h"
 #include "tk_sample_rows.h"
 #include "tk_samples.h"
@@ -297,6 +298,10 @@ struct tk_core {
     // d_u8r_cnt: the TK_U8R_WORDS report words, the workgroups' sums, the lanes' places, the documents' prefixes and the bitmap of document
     // starts -- everything a call computes until it is accepted.
     Buf d_u8r_text, d_u8r_doc, d_u8r_cnt;
+    // Stop strings (tk_stop_text.h), apart from everything above: d_stop_text: the cut text; d_stop_doc: text_off, hit and (id matrices)
+    // n_tok; d_stop_cnt: the TK_STOPS_WORDS report words, the stop set, the documents' words, kept lengths and hits, the workgroups' sums --
+    // everything a call computes until it is accepted.
+    Buf d_stop_text, d_stop_doc, d_stop_cnt;
     // Small calls (tk_k_small) do not take `mu`: the reference's normal use is several threads on one Encoding (core.py:175, a thread pool
     // over encode; lib.rs:232-238 keeps a regex per thread for it), and a small call needs nothing of the shared workspace -- a slot of its
     // own (page-locked text and result buffers the kernel reads and writes directly, merge scratch, a stream) is all.  A caller takes a
@@ -3389,6 +3394,7 @@ struct DrowsView {  // device buffers of the core: the first four valid until it
     const uint8_t* bytes = nullptr;
     const uint64_t* byte_off = nullptr;
     uint64_t n_tokens = 0, n_bytes = 0;
+    const unsigned long long* tok_byte = nullptr;  // the byte position of every kept token in `bytes` (the decode passes leave it: valid as long as they are)
 };
 static int drows_refusal(int why) {
     switch (why) {
@@ -3488,6 +3494,7 @@ static int drows_run(tk_core* c, hipStream_t s, const void* d_ids, uint64_t R, u
     out->stop_col = stop_col;
     out->bytes = c->d_bytes.as<uint8_t>();
     out->byte_off = dv.byte_off;
+    out->tok_byte = dv.tboff;
     out->n_tokens = K;
     return TK_OK;
 }
@@ -3735,6 +3742,203 @@ extern "C" int tk_decode_rows_text(tk_core* c, const void* ids, uint64_t n_rows,
         *n_tokens_out = v.n_tokens;
         *n_text_out = t.n_text;
         *n_replaced_out = t.n_replaced;
+        return TK_OK;
+    });
+}
+
+// ------------------------------------------------------------------------------------------
+// Stop strings (tk_stop_text.h; the rule: include/tiktoken_amd.h): packed text on the device -> every document cut at its first stop
+// string, and the decode-rows entries that cut their rows so before the repair.
+// ------------------------------------------------------------------------------------------
+static_assert(TK_STOPS_KEEP == TK_STOPSF_KEEP, "stop flags");
+struct StopsView {  // device buffers of the core, valid until its next stop-string call (text / text_off: the INPUT where no document has a hit)
+    const uint8_t* text = nullptr;
+    const uint64_t* text_off = nullptr;
+    const uint32_t* hit = nullptr;
+    uint32_t* n_tok = nullptr;  // room for a count per document behind hit, for the entries over id matrices
+    uint64_t n_text = 0, n_hit = 0;
+};
+// What can be refused without looking at the text
+static int stops_check(const tk_stops* stops, uint32_t flags, TkStopSet* set) {
+    if (!stops || (stops->n && (!stops->blob || !stops->off))) return fail(TK_VALUE_ERROR, "null argument");
+    switch (tk_stops_make(stops->n, stops->blob, stops->off, flags, set)) {
+        case 0: return TK_OK;
+        case 1: return fail(TK_VALUE_ERROR, "more than 16 stop strings");
+        case 2: return fail(TK_VALUE_ERROR, "an empty stop string");
+        case 3: return fail(TK_VALUE_ERROR, "a stop string of more than 64 bytes");
+        case 4: return fail(TK_VALUE_ERROR, "the offsets of the stop strings must ascend from 0");
+        default: return fail(TK_VALUE_ERROR, "stop strings: unknown flag");
+    }
+}
+// stops_run: the caller holds c->mu.  The host waits once, for the report words -- the first offending offset, the bytes kept, the documents
+// with a hit --, refuses, hands back the input or sizes the outputs.  A call that is refused has written into d_stop_cnt only.
+static int stops_run(tk_core* c, hipStream_t s, const uint8_t* d_bytes, uint64_t n, const uint64_t* d_off, uint64_t n_docs, const TkStopSet& set, StopsView* out) {
+    if (!d_off || (n && !d_bytes)) return fail(TK_VALUE_ERROR, "null argument");
+    if (((uintptr_t)d_bytes & 15u) || ((uintptr_t)d_off & 7u)) return fail(TK_VALUE_ERROR, "d_bytes must be 16-byte aligned and d_byte_off 8-byte aligned");
+    if (n_docs >= (1ull << 40)) return fail(TK_VALUE_ERROR, "2^40 documents or more");
+    if (n / TK_STOPS_BLOCK >= 0x7FFFFFFFull) return fail(TK_VALUE_ERROR, "2^43 bytes or more: a workgroup per 4096 bytes is more than a grid holds -- search the text in parts");
+    const uint64_t nb_find = (n + TK_STOPS_BLOCK - 1) / TK_STOPS_BLOCK, nb_rows = (n_docs + TK_STOPS_ROWS_BLOCK - 1) / TK_STOPS_ROWS_BLOCK;
+    Carve scratch;
+    const uint64_t at_words = scratch.add(TK_STOPS_WORDS * 8), at_set = scratch.add(sizeof(TkStopSet)), at_word = scratch.add(n_docs * 8), at_rel = scratch.add(n_docs * 8),
+                   at_hit = scratch.add(n_docs * 4), at_bsum = scratch.add(nb_rows * 8);
+    TRY(ensure(c->d_stop_cnt, scratch.total));
+    unsigned long long *words = carved<unsigned long long>(c->d_stop_cnt, at_words), *word = carved<unsigned long long>(c->d_stop_cnt, at_word),
+                       *rel = carved<unsigned long long>(c->d_stop_cnt, at_rel), *bsum = carved<unsigned long long>(c->d_stop_cnt, at_bsum);
+    uint32_t *d_set = carved<uint32_t>(c->d_stop_cnt, at_set), *hit_s = carved<uint32_t>(c->d_stop_cnt, at_hit);
+    const unsigned long long h_words[TK_STOPS_WORDS] = {~0ull, 0, 0};
+    HIPCHK(hipMemcpyAsync(words, h_words, sizeof h_words, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_set, &set, sizeof set, hipMemcpyHostToDevice, s));
+    if (n_docs) HIPCHK(hipMemsetAsync(word, 0xFF, n_docs * 8, s));
+    const dim3 per_doc(grid_for(n_docs + 1, 256, 4096)), block(256);
+    TRY(timed(c, s, "tk_k_u8r_check", [&] { hipLaunchKernelGGL(tk_k_u8r_check, per_doc, block, 0, s, d_off, n_docs, n, words); }));
+    if (n && n_docs && set.n)
+        TRY(timed(c, s, "tk_k_stops_find", [&] { hipLaunchKernelGGL(tk_k_stops_find, dim3((uint32_t)nb_find), block, 0, s, d_bytes, n, d_off, n_docs, d_set, word); }));
+    if (n_docs)
+        TRY(timed(c, s, "tk_k_stops_rows", [&] {
+            hipLaunchKernelGGL(tk_k_stops_rows, dim3((uint32_t)nb_rows), dim3(TK_STOPS_ROWS_BLOCK), 0, s, d_off, n_docs, word, d_set, rel, hit_s, bsum, words);
+        }));
+    TRY(timed(c, s, "tk_k_stops_scan", [&] { hipLaunchKernelGGL(tk_k_stops_scan, dim3(1), dim3(1024), 0, s, bsum, nb_rows, words); }));
+    unsigned long long got[TK_STOPS_WORDS];
+    HIPCHK(hipMemcpyAsync(got, words, sizeof got, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    if (got[TK_STOPS_BAD_DOC] != ~0ull)
+        return fail(TK_VALUE_ERROR, "byte_off must ascend from 0 to n_bytes: document " + std::to_string(got[TK_STOPS_BAD_DOC]) + " does not");
+    const uint64_t n_text = got[TK_STOPS_OUT], n_hit = got[TK_STOPS_N_HIT];
+    Carve doc;
+    const uint64_t at_off = doc.add((n_docs + 1) * 8), at_out_hit = doc.add(n_docs * 4), at_ntok = doc.add(n_docs * 4);
+    TRY(ensure(c->d_stop_doc, doc.total + 16));
+    uint64_t* text_off = carved<uint64_t>(c->d_stop_doc, at_off);
+    uint32_t* hit = carved<uint32_t>(c->d_stop_doc, at_out_hit);
+    TRY(timed(c, s, "tk_k_stops_docs", [&] { hipLaunchKernelGGL(tk_k_stops_docs, per_doc, block, 0, s, n_docs, bsum, rel, hit_s, words, n_hit ? text_off : nullptr, hit); }));
+    if (n_hit) {
+        TRY(ensure(c->d_stop_text, n_text + 16));
+        if (n_text)
+            TRY(timed(c, s, "tk_k_stops_cut", [&] {
+                hipLaunchKernelGGL(tk_k_stops_cut, dim3(grid_for((n_text + 15) / 16, 256, 1u << 16)), block, 0, s, d_bytes, d_off, text_off, n_docs, n_text,
+                                   c->d_stop_text.as<uint8_t>());
+            }));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    out->text = n_hit ? c->d_stop_text.as<uint8_t>() : d_bytes;
+    out->text_off = n_hit ? text_off : d_off;
+    out->hit = hit;
+    out->n_tok = carved<uint32_t>(c->d_stop_doc, at_ntok);
+    out->n_text = n_text;
+    out->n_hit = n_hit;
+    return TK_OK;
+}
+
+extern "C" int tk_stop_text_device(tk_core* c, const void* d_bytes, uint64_t n_bytes, const void* d_byte_off, uint64_t n_docs, const tk_stops* stops, uint32_t flags,
+                                   void* stream, const uint8_t** d_text_out, uint64_t* n_text_out, const uint64_t** d_text_off_out, const uint32_t** d_hit_out,
+                                   uint64_t* n_hit_out) {
+    TkStopSet set;
+    TRY(stops_check(stops, flags, &set));
+    StopsView v;
+    TRY(device_pass(c, n_text_out && n_hit_out, stream,
+                    [&](hipStream_t s) { return stops_run(c, s, (const uint8_t*)d_bytes, n_bytes, (const uint64_t*)d_byte_off, n_docs, set, &v); }));
+    if (d_text_out) *d_text_out = v.text;
+    if (d_text_off_out) *d_text_off_out = v.text_off;
+    if (d_hit_out) *d_hit_out = v.hit;
+    *n_text_out = v.n_text;
+    *n_hit_out = v.n_hit;
+    return TK_OK;
+}
+
+// The decode-rows passes unchanged, the search and the cut over their bytes, the rows' token counts, then the repair (mode TK_U8_BYTES: none)
+static int until_mode_check(uint32_t mode) {
+    return mode == TK_U8_REPLACE || mode == TK_U8_IGNORE || mode == TK_U8_BYTES ? TK_OK : fail(TK_VALUE_ERROR, "mode must be TK_U8_REPLACE, TK_U8_IGNORE or TK_U8_BYTES");
+}
+static int until_run(tk_core* c, hipStream_t s, const void* d_ids, uint64_t R, uint64_t W, uint64_t ld, const uint32_t* d_begin, const uint32_t* d_end, const tk_drows_spec* spec,
+                     const TkStopSet& set, uint32_t mode, DrowsView* v, StopsView* t, RepairView* u) {
+    TRY(drows_run(c, s, d_ids, R, W, ld, d_begin, d_end, spec, v));
+    TRY(stops_run(c, s, v->bytes, v->n_bytes, v->byte_off, R, set, t));
+    if (R)
+        TRY(timed(c, s, "tk_k_stops_ntok", [&] {
+            hipLaunchKernelGGL(tk_k_stops_ntok, dim3(grid_for(R, 256, 4096)), dim3(256), 0, s, v->tok_off, v->byte_off, t->text_off, v->tok_byte, R, t->n_tok);
+        }));
+    if (mode != TK_U8_BYTES) return repair_run(c, s, t->text, t->n_text, t->text_off, R, mode, u);  // (waits for the stream at its end)
+    *u = RepairView{t->text, t->text_off, nullptr, nullptr, t->n_text, 0, 0};
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    return TK_OK;
+}
+extern "C" int tk_decode_rows_until_device(tk_core* c, const void* d_ids, uint64_t n_rows, uint64_t width, uint64_t ld, const void* d_begin, const void* d_end,
+                                           const tk_drows_spec* spec, const tk_stops* stops, uint32_t stop_flags, uint32_t mode, void* stream,
+                                           const uint32_t** d_tokens_out, const uint64_t** d_tok_off_out, const uint32_t** d_n_kept_out, const uint32_t** d_stop_col_out,
+                                           const uint8_t** d_text_out, const uint64_t** d_text_off_out, const uint64_t** d_char_off_out, const uint64_t** d_repl_off_out,
+                                           const uint32_t** d_hit_out, const uint32_t** d_n_tok_out, uint64_t* n_tokens_out, uint64_t* n_text_out,
+                                           uint64_t* n_replaced_out, uint64_t* n_hit_out) {
+    TRY(until_mode_check(mode));  // (both before the rows passes write)
+    TkStopSet set;
+    TRY(stops_check(stops, stop_flags, &set));
+    DrowsView v;
+    StopsView t;
+    RepairView u;
+    TRY(device_pass(c, spec && n_tokens_out && n_text_out && n_replaced_out && n_hit_out && (d_ids || !n_rows || !width), stream, [&](hipStream_t s) -> int {
+        return until_run(c, s, d_ids, n_rows, width, ld, (const uint32_t*)d_begin, (const uint32_t*)d_end, spec, set, mode, &v, &t, &u);
+    }));
+    if (d_tokens_out) *d_tokens_out = v.tokens;
+    if (d_tok_off_out) *d_tok_off_out = v.tok_off;
+    if (d_n_kept_out) *d_n_kept_out = v.n_kept;
+    if (d_stop_col_out) *d_stop_col_out = v.stop_col;
+    if (d_text_out) *d_text_out = u.text;
+    if (d_text_off_out) *d_text_off_out = u.text_off;
+    if (d_char_off_out) *d_char_off_out = u.char_off;
+    if (d_repl_off_out) *d_repl_off_out = u.repl_off;
+    if (d_hit_out) *d_hit_out = t.hit;
+    if (d_n_tok_out) *d_n_tok_out = t.n_tok;
+    *n_tokens_out = v.n_tokens;
+    *n_text_out = u.n_text;
+    *n_replaced_out = u.n_replaced;
+    *n_hit_out = t.n_hit;
+    return TK_OK;
+}
+extern "C" int tk_decode_rows_until(tk_core* c, const void* ids, uint64_t n_rows, uint64_t width, uint64_t ld, const uint32_t* begin, const uint32_t* end,
+                                    const tk_drows_spec* spec, const tk_stops* stops, uint32_t stop_flags, uint32_t mode, uint32_t** tokens_out, uint64_t** tok_off_out,
+                                    uint32_t** n_kept_out, uint32_t** stop_col_out, uint8_t** text_out, uint64_t** text_off_out, uint64_t** char_off_out,
+                                    uint64_t** repl_off_out, uint32_t** hit_out, uint32_t** n_tok_out, uint64_t* n_tokens_out, uint64_t* n_text_out,
+                                    uint64_t* n_replaced_out, uint64_t* n_hit_out) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if (!spec || !tokens_out || !tok_off_out || !n_kept_out || !stop_col_out || !text_out || !text_off_out || !char_off_out || !repl_off_out || !hit_out || !n_tok_out ||
+        !n_tokens_out || !n_text_out || !n_replaced_out || !n_hit_out || (!ids && n_rows && width))
+        return fail(TK_VALUE_ERROR, "null argument");
+    TRY(until_mode_check(mode));
+    TkStopSet set;
+    TRY(stops_check(stops, stop_flags, &set));
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    return drained(c, [&]() -> int {
+        TkDrows p;
+        TRY(drows_check_spec(c, spec, n_rows, width, ld, &p));  // (before anything is copied)
+        hipStream_t s = c->stream;
+        void* d_ids;
+        uint32_t *d_begin, *d_end;
+        TRY(drows_host_in(c, s, ids, n_rows, width, ld, begin, end, p, &d_ids, &d_begin, &d_end));
+        DrowsView v;
+        StopsView t;
+        RepairView u;
+        TRY(until_run(c, s, d_ids, n_rows, width, ld, d_begin, d_end, spec, set, mode, &v, &t, &u));
+        ResultBag bag;
+        TRY(bag.fetch(tokens_out, v.tokens, v.n_tokens));
+        TRY(bag.fetch(tok_off_out, v.tok_off, n_rows + 1));
+        TRY(bag.fetch(n_kept_out, v.n_kept, n_rows));
+        TRY(bag.fetch(stop_col_out, v.stop_col, n_rows));
+        TRY(bag.fetch(text_out, u.text, u.n_text));
+        TRY(bag.fetch(text_off_out, u.text_off, n_rows + 1));
+        if (mode != TK_U8_BYTES) {
+            TRY(bag.fetch(char_off_out, u.char_off, n_rows + 1));
+            TRY(bag.fetch(repl_off_out, u.repl_off, n_rows + 1));
+        }
+        TRY(bag.fetch(hit_out, t.hit, n_rows));
+        TRY(bag.fetch(n_tok_out, t.n_tok, n_rows));
+        bag.give();
+        if (mode == TK_U8_BYTES) *char_off_out = *repl_off_out = nullptr;
+        *n_tokens_out = v.n_tokens;
+        *n_text_out = u.n_text;
+        *n_replaced_out = u.n_replaced;
+        *n_hit_out = t.n_hit;
         return TK_OK;
     });
 }
