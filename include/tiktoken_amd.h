@@ -399,7 +399,8 @@ int tk_encode_batch_sample_rows(tk_core* core, const uint8_t* utf8, const uint64
  *   (R - 1) * ld + W elements of the matrix, whatever begin and end hold.  One device per call: a group has no such entry.
  *  Text instead of bytes (errors="replace" / "ignore" applied on the device): tk_decode_rows_text_device / tk_decode_rows_text below.
  *  Rows cut at a stop STRING as well (until=, stop=, stop_strings=): tk_decode_rows_until_device / tk_decode_rows_until below.
- *  NOT built: uint16 matrices; token spans of a matrix (feed tokens and tok_off to tk_token_spans_device); streaming. */
+ *  Rows that arrive a few columns per step (a generation loop): tk_stream_create below.
+ *  NOT built: uint16 matrices; token spans of a matrix (feed tokens and tok_off to tk_token_spans_device). */
 #define TK_DROWS_KEEP_STOP 1u    /* the stop id that ends a row belongs to it */
 #define TK_DROWS_SKIP_SPECIAL 2u /* special tokens are dropped as if they were in skip_ids */
 #define TK_DROWS_I32 4u          /* the matrix holds int32 */
@@ -509,7 +510,7 @@ int tk_decode_rows_text(tk_core* core, const void* ids, uint64_t n_rows, uint64_
  *  that belong to this entry alone, valid until the core's next stop-string call (this entry, tk_decode_rows_until_device,
  *  tk_decode_rows_until).  The input must not be this entry's own previous output.  Holds the core's mutex; `stream`: a hipStream_t or
  *  null (the core's); the call returns when the text is there.  One device per call: a group has no such entry.
- * NOT built: streaming (no state carried between calls, no per-document start offset of the search). */
+ * Text that arrives piece by piece, the state carried between the calls: tk_stream_create below. */
 #define TK_STOPS_KEEP 1u /* the stop string that ends a document belongs to it */
 typedef struct {
     uint32_t n;           /* strings: 0 .. 16 */
@@ -540,7 +541,71 @@ int tk_decode_rows_until(tk_core* core, const void* ids, uint64_t n_rows, uint64
                          uint32_t** n_kept_out, uint32_t** stop_col_out, uint8_t** text_out, uint64_t** text_off_out, uint64_t** char_off_out,
                          uint64_t** repl_off_out, uint32_t** hit_out, uint32_t** n_tok_out, uint64_t* n_tokens_out, uint64_t* n_text_out,
                          uint64_t* n_replaced_out, uint64_t* n_hit_out);
-/* bpe_train(data, vocab_size, pat_str, visualise=None)                      tiktoken/_educational.py:119-185
+/* Streaming decode: tk_decode_rows_until for rows that arrive a few ids per step.  A generation loop has one column per step, or a few
+ * under speculative decoding; it must show text as it arrives, notice a stop string the moment it completes, and print neither half a
+ * UTF-8 char nor the first half of "\n\nQuestion:".  A stream is n_rows row slots whose state lives in HBM; a step takes ids [n_rows, W]
+ * and returns, per row, the text that became final.  Replaces nothing in the reference: it is the per-row incremental detokenizer of its
+ * users' serving loops.
+ * The rule.  A stream is created with a tk_drows_spec, a tk_stops set with its flag and a mode -- the arguments and limits of
+ *  tk_decode_rows_until_device, refused the same way -- and w_max, 1 .. 64, the widest step.  Per row r: state[r] (0 live, 1 ended by a
+ *  stop id, 2 ended by a stop string, 3 flushed), hit[r] as in tk_stop_text_device, tail[r]: at most 66 kept, decoded bytes that are not
+ *  emitted yet and begin on a unit boundary of the row's text, and the running totals n_kept, n_text, n_chars.
+ *  Step on ids [n_rows, W], element (r, c) at ids[r * ld + c], begin / end uint32[n_rows] or null.  A row whose state is not 0 emits
+ *   nothing; none of its columns is read or judged, its begin and end neither.  For a live row:
+ *   1. the tk_decode_rows_device row rule runs on its columns [begin, end): stop_col and the kept ids; a kept id without a decode entry is
+ *      TK_KEY_ERROR with the reference's message, the row and the column; begin > end or end > W is TK_VALUE_ERROR;
+ *   2. N = the bytes of the kept ids, B = tail ++ N;
+ *   3. full hits are searched in B by the tk_stop_text_device rule, B the document: the least p wins, then the least k.  On a hit (p, k)
+ *      the row emits B[:p] -- B[:p + len(s_k)] with TK_STOPS_KEEP -- repaired as the end of a document, takes state 2 and hit k; otherwise,
+ *      if a stop id was found, it emits all of B, repaired as the end of a document, and takes state 1;
+ *   4. otherwise it stays live.  e0 = the least p such that B[p:] is a non-empty proper prefix of a stop string, or len(B).  B is parsed
+ *      into the units of tk_utf8_repair_device from offset 0, with one difference: a lead byte that has accepted every byte up to the end
+ *      of B, fewer than L - 1 of them, is unfinished, not ill-formed; e1 = its offset, or len(B).  e = the greatest unit start <= min(e0,
+ *      e1); under TK_U8_BYTES e = e0.  The row emits B[:e], repaired, and its new tail is B[e:]: at most 63 + 3 bytes.
+ *  Flush (some rows, or all): a live row emits its tail repaired as the end of a document -- an unfinished char becomes U+FFFD under
+ *   TK_U8_REPLACE -- and takes state 3.  Reset (some rows, or all): the slot is live again, its tail empty, its totals zero, its hit
+ *   0xFFFFFFFF; continuous batching reuses slots this way.
+ *  For every row, everything emitted, concatenated, equals what tk_decode_rows_until returns for the row made of all the live columns
+ *   fed to it, up to and including the step that ended it (or the flush): bytes, hit and mode alike.  Columns fed afterwards do not exist
+ *   for that row.  Why: (a) B[:e] ends on a unit boundary and no unit reaches back over one, so the repair of the pieces is the pieces of
+ *   the repair.  (b) A hit cannot start in bytes already emitted: when those were emitted the hit was not complete, so B[p:] was a proper
+ *   prefix of the string, e0 <= p held it back, and e <= e0.  (c) A hit that is found is final: another one at a lower position that
+ *   would complete later needs columns of a later step, which the row, ended by this one, never consumes -- and every hit that lies inside
+ *   this step's B takes part in this step's minimum.  (d) Without a hit nothing behind e0 is emitted, so a string that completes later is
+ *   still whole in the tail.
+ * Output of a step (and of a flush): text uint8[*n_text_out], the emitted pieces back to back; text_off and char_off uint64[n_rows + 1]
+ *  (char_off null under TK_U8_BYTES); state and hit uint32[n_rows]: the rows' state and hit after the call.
+ * tk_stream_create.  TK_VALUE_ERROR for what tk_decode_rows_until_device refuses in spec, stops, flags and mode; w_max outside 1 .. 64;
+ *  more than 65536 rows; a vocabulary and w_max whose row buffer 66 + w_max * (the longest token's bytes) exceeds the 16000 bytes of LDS
+ *  a row takes (the message says to use tk_decode_rows_until for such input).  TK_UNSUPPORTED where tk_decode_batch returns it.  The stream belongs to the core and must be destroyed before it; several
+ *  streams per core are legal; every call of a stream holds the core's mutex.  The element type of the matrices is the spec's dtype flag
+ *  until tk_stream_dtype names another.
+ * tk_stream_step_device: d_ids, d_begin, d_end on the core's device.  *d_text_out .. *d_hit_out are buffers of the stream, valid until
+ *  its next call.  W > w_max, ld < W, begin > end, end > W and TK_KEY_ERROR refuse the step: state, totals and the previous outputs stay
+ *  whole (the row kernel writes into a second copy of the slots that the host swaps in on success).  No kernel reads outside the
+ *  (n_rows - 1) * ld + W elements of the matrix, whatever begin and end hold.  Two launches per call, whatever n_rows, W and the data
+ *  are (tk_k_stream_row, tk_k_stream_pack under tk_get_kernel_ms), and one wait.  W == 0 and n_rows == 0 are legal.
+ * tk_stream_step: the matrix in host memory; tk_stream_fetch: the last accepted call's outputs as host arrays of the stream, valid until
+ *  its next call; tk_stream_flush / tk_stream_reset: rows uint32[n_listed] in host memory, or null for all; a row at or beyond n_rows is
+ *  TK_VALUE_ERROR.  tk_stream_rows: the slots' state, hit and totals into the caller's arrays of n_rows entries (each may be null).
+ * NOT built: n_tok per step; token spans in streamed text; W > 64; a stream across several GPUs. */
+typedef struct tk_stream tk_stream;
+int tk_stream_create(tk_core* core, uint64_t n_rows, uint32_t w_max, const tk_drows_spec* spec, const tk_stops* stops, uint32_t stop_flags, uint32_t mode,
+                     tk_stream** stream_out);
+void tk_stream_destroy(tk_stream* stream);
+int tk_stream_dtype(tk_stream* stream, uint32_t dtype_flags); /* 0 (uint32), TK_DROWS_I32 or TK_DROWS_I64: of the matrices from here on */
+int tk_stream_step_device(tk_stream* stream, const void* d_ids, uint64_t width, uint64_t ld, const void* d_begin, const void* d_end, void* hip_stream,
+                          const uint8_t** d_text_out, uint64_t* n_text_out, const uint64_t** d_text_off_out, const uint64_t** d_char_off_out,
+                          const uint32_t** d_state_out, const uint32_t** d_hit_out);
+int tk_stream_step(tk_stream* stream, const void* ids, uint64_t width, uint64_t ld, const uint32_t* begin, const uint32_t* end, const uint8_t** text_out,
+                   uint64_t* n_text_out, const uint64_t** text_off_out, const uint64_t** char_off_out, const uint32_t** state_out, const uint32_t** hit_out);
+int tk_stream_fetch(tk_stream* stream, const uint8_t** text_out, uint64_t* n_text_out, const uint64_t** text_off_out, const uint64_t** char_off_out,
+                    const uint32_t** state_out, const uint32_t** hit_out);
+int tk_stream_flush(tk_stream* stream, const uint32_t* rows, uint64_t n_listed, const uint8_t** text_out, uint64_t* n_text_out, const uint64_t** text_off_out,
+                    const uint64_t** char_off_out, const uint32_t** state_out, const uint32_t** hit_out);
+int tk_stream_reset(tk_stream* stream, const uint32_t* rows, uint64_t n_listed);
+int tk_stream_rows(tk_stream* stream, uint32_t* state, uint32_t* hit, uint64_t* n_kept, uint64_t* n_text, uint64_t* n_chars);
+/* bpe_train(data, vocab_size, pat_str, visualise=None)                    tiktoken/_educational.py:119-185
  * Training a vocabulary: the merges the reference's educational trainer makes on the same text -- the same pairs in the same order -- for a
  * packed batch of documents, under the core's pat_str (stock scanners or the generic engine).  The core's ranks and special tokens play
  * no part.  On success *pairs_out holds *n_out = vocab_size - 256 pairs {left, right} and *counts_out the count of each pair when it won

@@ -164,6 +164,25 @@ def lib() -> ctypes.CDLL:
             L.tk_decode_rows_until_device.argtypes = [vp, vp, u64, u64, u64, vp, vp, P(DrowsSpec), P(Stops), u32, u32, vp, *[P(vp)] * 10, *[P(u64)] * 4]
             L.tk_decode_rows_until.restype = i32
             L.tk_decode_rows_until.argtypes = [vp, vp, u64, u64, u64, vp, vp, P(DrowsSpec), P(Stops), u32, u32, *[P(vp)] * 10, *[P(u64)] * 4]
+        if hasattr(L, "tk_stream_create"):  # (absent from older builds selected through $TIKTOKEN_AMD_LIB)
+            outs = [P(vp), P(u64), P(vp), P(vp), P(vp), P(vp)]  # text, n_text, text_off, char_off, state, hit
+            L.tk_stream_create.restype = i32
+            L.tk_stream_create.argtypes = [vp, u64, u32, P(DrowsSpec), P(Stops), u32, u32, P(vp)]
+            L.tk_stream_destroy.argtypes = [vp]
+            L.tk_stream_dtype.restype = i32
+            L.tk_stream_dtype.argtypes = [vp, u32]
+            L.tk_stream_step_device.restype = i32
+            L.tk_stream_step_device.argtypes = [vp, vp, u64, u64, vp, vp, vp, *outs]
+            L.tk_stream_step.restype = i32
+            L.tk_stream_step.argtypes = [vp, vp, u64, u64, vp, vp, *outs]
+            L.tk_stream_fetch.restype = i32
+            L.tk_stream_fetch.argtypes = [vp, *outs]
+            L.tk_stream_flush.restype = i32
+            L.tk_stream_flush.argtypes = [vp, vp, u64, *outs]
+            L.tk_stream_reset.restype = i32
+            L.tk_stream_reset.argtypes = [vp, vp, u64]
+            L.tk_stream_rows.restype = i32
+            L.tk_stream_rows.argtypes = [vp, vp, vp, vp, vp, vp]
         L.tk_decode_single_token_bytes.restype = i32
         L.tk_decode_single_token_bytes.argtypes = [vp, u32, P(vp), P(u64)]
         L.tk_n_tokens.restype = u64

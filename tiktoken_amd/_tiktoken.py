@@ -411,6 +411,117 @@ class StoppedRowsDevice(NamedTuple):
     n_hit: int
 
 
+class StreamPacked(NamedTuple):
+    """What a call of a decode stream emitted, as arrays (copies: the stream's own buffers last until its next call): row r emitted
+    text[text_off[r] : text_off[r + 1]], char_off counts its chars (None in the bytes mode); state and hit: the rows' state (0 live, 1 ended
+    by a stop id, 2 by a stop string, 3 flushed) and the stop string that ended them (NO_HIT: none) after the call."""
+    text: np.ndarray  # uint8
+    text_off: np.ndarray  # uint64[R + 1]
+    char_off: "np.ndarray | None"  # uint64[R + 1]
+    state: np.ndarray  # uint32[R]
+    hit: np.ndarray  # uint32[R]
+
+    NO_HIT = 0xFFFFFFFF
+
+
+class StreamStep(NamedTuple):
+    """`DecodeStream.step` / `flush`: text[r] is what row r emitted (str; bytes under errors=None), finished[r] says that the row has ended."""
+    text: list
+    finished: np.ndarray  # bool[R]
+    state: np.ndarray  # uint32[R]
+    hit: np.ndarray  # uint32[R]
+
+
+class NativeStream:
+    """A tk_stream and the calls on it; made by `CoreBPE.stream_create`.  Keeps its core alive: the stream must go first."""
+
+    def __init__(self, core: "CoreBPE", handle, n_rows: int, w_max: int, mode: int):
+        self._core, self._h, self.n_rows, self.w_max, self.mode = core, handle, n_rows, w_max, mode
+        self._dtype = _lib.DROWS_I64
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and getattr(self._core, "_h", None):  # (a core that is closed has taken its device's buffers along)
+            try:
+                self._core._L.tk_stream_destroy(h)
+            except Exception:
+                pass
+
+    __del__ = close
+
+    def _handle(self):
+        if not self._h:
+            raise ValueError("the decode stream is closed")
+        return self._h
+
+    def _set_dtype(self, dtype) -> None:
+        try:
+            flag = CoreBPE._ROW_DTYPES[np.dtype(dtype)]
+        except (KeyError, TypeError):
+            raise ValueError("an id matrix holds uint32, int32 or int64") from None
+        if flag != self._dtype:
+            _lib.raise_for(self._core._L.tk_stream_dtype(self._handle(), flag))
+            self._dtype = flag
+
+    @staticmethod
+    def _outs():
+        out = [ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()]
+        return out, [ctypes.byref(x) for x in out]
+
+    def _packed(self, out) -> StreamPacked:
+        def arr(ptr, n, dtype):
+            if not n or not ptr.value:
+                return np.zeros(0 if not n else n, dtype)
+            return np.frombuffer(ctypes.string_at(ptr.value, n * np.dtype(dtype).itemsize), dtype)
+
+        R = self.n_rows
+        return StreamPacked(arr(out[0], int(out[1].value), np.uint8), arr(out[2], R + 1, np.uint64), arr(out[3], R + 1, np.uint64) if self.mode != _lib.U8_BYTES else None,
+                            arr(out[4], R, np.uint32), arr(out[5], R, np.uint32))
+
+    def step_host(self, ids: np.ndarray, width: int, ld: int, begin, end) -> StreamPacked:
+        self._set_dtype(ids.dtype)
+        out, refs = self._outs()
+        rc = self._core._L.tk_stream_step(self._handle(), ids.ctypes.data if self.n_rows and width else None, width, ld, None if begin is None else begin.ctypes.data,
+                                          None if end is None else end.ctypes.data, *refs)
+        _lib.raise_for(rc)
+        return self._packed(out)
+
+    def step_device(self, d_ids: int, width: int, ld: int, dtype, d_begin: int = 0, d_end: int = 0, stream: int = 0) -> StreamPacked:
+        self._set_dtype(dtype)
+        out, refs = self._outs()
+        _lib.raise_for(self._core._L.tk_stream_step_device(self._handle(), d_ids or None, width, ld, d_begin or None, d_end or None, stream or None, *refs))
+        out, refs = self._outs()
+        _lib.raise_for(self._core._L.tk_stream_fetch(self._handle(), *refs))
+        return self._packed(out)
+
+    def _rows_arg(self, rows):
+        if rows is None:
+            return None, 0
+        a = np.ascontiguousarray([int(r) for r in rows], dtype=np.int64)
+        if len(a) and (int(a.min()) < 0 or int(a.max()) >= self.n_rows):
+            raise ValueError(f"rows must name slots 0 .. {self.n_rows - 1} of the stream")
+        a = np.concatenate([a, [0]]).astype(np.uint32)  # (never an empty buffer)
+        return a, len(a) - 1
+
+    def flush(self, rows=None) -> StreamPacked:
+        a, n = self._rows_arg(rows)
+        out, refs = self._outs()
+        _lib.raise_for(self._core._L.tk_stream_flush(self._handle(), None if a is None else a.ctypes.data, n, *refs))
+        return self._packed(out)
+
+    def reset(self, rows=None) -> None:
+        a, n = self._rows_arg(rows)
+        _lib.raise_for(self._core._L.tk_stream_reset(self._handle(), None if a is None else a.ctypes.data, n))
+
+    def rows(self) -> "dict[str, np.ndarray]":
+        """state, hit (uint32[R]) and the totals n_kept, n_text, n_chars (uint64[R]) of the slots"""
+        R = self.n_rows
+        a = dict(state=np.zeros(R + 1, np.uint32), hit=np.zeros(R + 1, np.uint32), n_kept=np.zeros(R + 1, np.uint64), n_text=np.zeros(R + 1, np.uint64),
+                 n_chars=np.zeros(R + 1, np.uint64))
+        _lib.raise_for(self._core._L.tk_stream_rows(self._handle(), *[v.ctypes.data for v in a.values()]))
+        return {k: v[:R] for k, v in a.items()}
+
+
 def until_mode(errors: "str | None") -> int:
     """errors= of the stop-string entries -> TK_U8_REPLACE / TK_U8_IGNORE, None -> TK_U8_BYTES"""
     return _lib.U8_BYTES if errors is None else repair_mode(errors)
@@ -1037,6 +1148,18 @@ class CoreBPE:
         return StoppedRows(_take_u8(out[4], n_bytes), _take_u64(out[5], n_rows + 1), _take_u64(out[6], n_rows + 1) if text else None,
                            _take_u64(out[7], n_rows + 1) if text else None, _take_u32(out[0], n_tokens), _take_u64(out[1], n_rows + 1), _take_u32(out[2], n_rows),
                            _take_u32(out[3], n_rows), _take_u32(out[8], n_rows), _take_u32(out[9], n_rows))
+
+    # ------------------------------------------------------------------ streaming decode: row slots on the device, fed a few ids per step
+    def stream_create(self, n_rows: int, stop_text=(), *, w_max: int = 1, stop: Sequence[int] = (), skip: Sequence[int] = (), skip_special: bool = False,
+                      keep_stop: bool = False, keep_stop_text: bool = False, errors: "str | None" = "replace") -> "NativeStream":
+        """A decode stream of n_rows slots on this core's device (tk_stream_create); the arguments as in `decode_rows_until_packed`."""
+        self._one_device("decode_stream")
+        mode = until_mode(errors)
+        stops = _StopSet(stop_text)
+        spec = self._drows_spec(np.int64, stop, skip, skip_special, keep_stop)
+        h = ctypes.c_void_p()
+        _lib.raise_for(self._L.tk_stream_create(self._h, n_rows, w_max, ctypes.byref(spec), ctypes.byref(stops.c), _lib.STOPS_KEEP if keep_stop_text else 0, mode, ctypes.byref(h)))
+        return NativeStream(self, h, n_rows, w_max, mode)
 
     # ------------------------------------------------------------------ token spans (tiktoken/core.py:303-335 over batches)
     def _one_device(self, what: str) -> None:

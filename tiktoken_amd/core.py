@@ -684,6 +684,19 @@ class Encoding:
         view, bounds = memoryview(rows.data), rows.byte_off.tolist()
         return [bytes(view[a:b]) for a, b in zip(bounds[:-1], bounds[1:])]
 
+    # ---- the same for rows that arrive a few ids per step: a generation loop's incremental detokenizer, its state on the device
+    def decode_stream(self, n_rows: int, stop_text=(), *, w_max: int = 1, stop=(), skip=(), skip_special: bool = False, keep_stop: bool = False,
+                      keep_stop_text: bool = False, errors: "str | None" = "replace") -> "DecodeStream":
+        """A decode stream of `n_rows` row slots whose state lives on the GPU (tk_stream_create): `step(ids)` takes the [n_rows, W] ids a
+        generation step made, W <= w_max <= 64, and returns per row the text that became final -- never half a UTF-8 char, never the
+        first half of a stop string that may still complete --; a row ends at a stop id or the moment a stop string completes.  Everything
+        a row emits, concatenated, is what `decode_rows_until` returns for all the live columns it was fed.  The arguments as in
+        `decode_rows_until_packed`; errors=None: bytes, not repaired.  See `DecodeStream`."""
+        _tiktoken.until_mode(errors)  # (refused before anything runs)
+        native = self._core_bpe.stream_create(n_rows, stop_text, w_max=w_max, stop=self._row_ids(stop, "stop"), skip=self._row_ids(skip, "skip"), skip_special=skip_special,
+                                              keep_stop=keep_stop, keep_stop_text=keep_stop_text, errors=errors)
+        return DecodeStream(self, native, errors)
+
     def _rows_tensor_call(self, ids, begin, end, call):
         """An id tensor on this encoding's GPU through a device entry: (the entry's result, host(ptr, n, typestr, dtype): one of its buffers
         copied to the host)."""
@@ -773,6 +786,88 @@ class Encoding:
             self.__dict__ = plugins.get_encoding(value).__dict__
             return
         self.__init__(**value)
+
+
+class DecodeStream:
+    """`Encoding.decode_stream`: row slots on the GPU, fed a few ids per step.  A context manager; `close()` releases the device buffers.
+    A call that is refused (KeyError for a kept id without a token, ValueError for W > w_max, begin > end, end > W) changes nothing."""
+
+    def __init__(self, enc: Encoding, native: "_tiktoken.NativeStream", errors: "str | None"):
+        self._enc, self._native, self._errors = enc, native, errors
+        self.n_rows, self.w_max = native.n_rows, native.w_max
+
+    def close(self) -> None:
+        self._native.close()
+
+    def __enter__(self) -> "DecodeStream":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def step_packed(self, ids, begin=None, end=None) -> "_tiktoken.StreamPacked":
+        """One step, as arrays (see `_tiktoken.StreamPacked`).  `ids`: what `decode_rows` takes -- a numpy array of uint32, int32 or
+        int64 of any row stride, or a torch tensor of int32 / int64 on this encoding's GPU, which goes in by pointer (`out[:, t:t + W]`
+        is not copied) --, [n_rows, W] or 1-D as [n_rows, 1]; begin / end: per row, as there."""
+        core, native = self._enc._core_bpe, self._native
+        if hasattr(ids, "data_ptr") and hasattr(ids, "is_cuda"):
+            if ids.dim() == 1:
+                ids = ids.unsqueeze(1)
+            if ids.dim() == 2 and ids.shape[0] != self.n_rows:
+                raise ValueError(f"the stream has {self.n_rows} rows: the ids have {ids.shape[0]}")
+            r, _ = self._enc._rows_tensor_call(ids, begin, end, lambda d_ids, n_rows, width, ld, dtype, d_begin, d_end: native.step_device(d_ids, width, ld, dtype, d_begin, d_end))
+            return r
+        ids = np.asarray(ids)
+        if ids.ndim == 1:
+            ids = ids.reshape(len(ids), 1)
+        if ids.ndim == 2 and ids.shape[0] != self.n_rows:
+            raise ValueError(f"the stream has {self.n_rows} rows: the ids have {ids.shape[0]}")
+        ids, _, width, ld, begin, end, _ = core._host_matrix(ids, begin, end, (), (), False, False)
+        return native.step_host(ids, width, ld, begin, end)
+
+    def _texts(self, p: "_tiktoken.StreamPacked") -> "_tiktoken.StreamStep":
+        view, bounds = memoryview(p.text), p.text_off.tolist()
+        if self._errors is None:
+            text = [bytes(view[a:b]) for a, b in zip(bounds[:-1], bounds[1:])]
+        else:
+            text = [str(view[a:b], "utf-8") if b > a else "" for a, b in zip(bounds[:-1], bounds[1:])]
+        return _tiktoken.StreamStep(text, p.state != 0, p.state, p.hit)
+
+    def step(self, ids, begin=None, end=None) -> "_tiktoken.StreamStep":
+        """One step: `StreamStep(text, finished, state, hit)`, text[r] what row r emitted (str; bytes under errors=None)."""
+        return self._texts(self.step_packed(ids, begin, end))
+
+    def flush_packed(self, rows=None) -> "_tiktoken.StreamPacked":
+        return self._native.flush(rows)
+
+    def flush(self, rows=None) -> "_tiktoken.StreamStep":
+        """The live rows among `rows` (None: all) emit what they held back -- an unfinished char becomes U+FFFD under errors="replace"
+        -- and are flushed (state 3)."""
+        return self._texts(self._native.flush(rows))
+
+    def reset(self, rows=None) -> None:
+        """`rows` (None: all) are live again, with nothing held back and zero totals: a slot taken by the next request."""
+        self._native.reset(rows)
+
+    @property
+    def state(self) -> np.ndarray:
+        return self._native.rows()["state"]
+
+    @property
+    def hit(self) -> np.ndarray:
+        return self._native.rows()["hit"]
+
+    @property
+    def n_kept(self) -> np.ndarray:
+        return self._native.rows()["n_kept"]
+
+    @property
+    def n_text(self) -> np.ndarray:
+        return self._native.rows()["n_text"]
+
+    @property
+    def n_chars(self) -> np.ndarray:
+        return self._native.rows()["n_chars"]
 
 
 class _DeviceArray:

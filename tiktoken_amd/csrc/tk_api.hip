@@ -27,6 +27,7 @@
 #include "tk_offsets.h"
 #include "tk_utf8_repair.h"
 #include "tk_stop_text.h"
+#include "tk_stream.h"
 #include "tk_padded.h"
 #include "tk_sample_rows.h"
 #include "tk_samples.h"
@@ -3939,6 +3940,260 @@ extern "C" int tk_decode_rows_until(tk_core* c, const void* ids, uint64_t n_rows
         *n_text_out = u.n_text;
         *n_replaced_out = u.n_replaced;
         *n_hit_out = t.n_hit;
+        return TK_OK;
+    });
+}
+
+// ------------------------------------------------------------------------------------------
+// Streaming decode (tk_stream.h; the rule: include/tiktoken_amd.h): row slots in HBM, fed a few columns per step.  Every buffer of a stream
+// belongs to its tk_stream and goes with it; a call holds the core's mutex.  A call is two launches and one wait: the row kernel writes
+// scratch and the other copy of the slots, the pack pass writes the outputs unless the row kernel reported a refusal, and the host swaps the
+// copies once it has read the report words.
+// ------------------------------------------------------------------------------------------
+static_assert(TK_U8_BYTES == TK_STREAM_MODE_BYTES, "stream modes");
+struct tk_stream {
+    tk_core* c = nullptr;
+    int device = 0;
+    uint64_t R = 0, slot = 0;
+    uint32_t w_max = 0, mode = 0, cap = 0, dtype = 0;
+    tk_drows_spec spec{};
+    int cur = 0;  // which copy of the slots holds the state
+    uint64_t n_text = 0, n_chars = 0;  // of the last accepted call
+    bool fetched = false;
+    Pinned<unsigned long long> h_words;  // [0, TK_STREAM_WORDS): what a call starts from; [8, 8 + TK_STREAM_WORDS): what it reported
+    std::vector<uint8_t> h_text;         // the last accepted call's outputs on the host (stream_fetch)
+    std::vector<uint64_t> h_text_off, h_char_off;
+    std::vector<uint32_t> h_state, h_hit;
+    Buf rows[2], set, scratch, len, text, doc, out, words, in;
+};
+struct StreamView {  // device buffers of the stream, valid until its next call
+    const uint8_t* text = nullptr;
+    const uint64_t *text_off = nullptr, *char_off = nullptr;
+    const uint32_t *state = nullptr, *hit = nullptr;
+};
+static StreamView stream_view(const tk_stream* st) {
+    const uint64_t* doc = st->doc.as<uint64_t>();
+    const uint32_t* out = st->out.as<uint32_t>();
+    return StreamView{st->text.as<uint8_t>(), doc, st->mode == TK_U8_BYTES ? nullptr : doc + (st->R + 1), out, out + st->R};
+}
+// stream_run: the caller holds the core's mutex.  op: TK_STREAM_OP_*; d_sel: a byte per row for flush and reset (null: every row).
+static int stream_run(tk_stream* st, hipStream_t s, uint32_t op, const void* d_ids, uint64_t W, uint64_t ld, const uint32_t* d_begin, const uint32_t* d_end,
+                      const uint8_t* d_sel) {
+    tk_core* c = st->c;
+    TkDrows p;
+    const uint32_t flags = (st->spec.flags & ~(TK_DROWS_I32 | TK_DROWS_I64)) | st->dtype;
+    TRY(drows_refusal(tk_drows_shape(st->R, W, ld, flags, st->spec.n_stop, st->spec.stop_ids, st->spec.n_skip, st->spec.skip_ids, TK_DEC_BLOCK, &p)));
+    if (W > st->w_max) return fail(TK_VALUE_ERROR, "a step of " + std::to_string(W) + " columns: the stream was created with w_max = " + std::to_string(st->w_max));
+    if (W && st->R && !d_ids) return fail(TK_VALUE_ERROR, "null argument");
+    unsigned long long* words = st->words.as<unsigned long long>();
+    HIPCHK(hipMemcpyAsync(words, st->h_words.p, TK_STREAM_WORDS * 8, hipMemcpyHostToDevice, s));
+    const TkStreamRow* cur = st->rows[st->cur].as<TkStreamRow>();
+    TkStreamRow* next = st->rows[st->cur ^ 1].as<TkStreamRow>();
+    uint32_t *len = st->len.as<uint32_t>(), *chars = len + st->R;
+    const dim3 grid_row((uint32_t)std::max<uint64_t>((st->R + TK_STREAM_ROWS_WG - 1) / TK_STREAM_ROWS_WG, 1)), grid_pack((uint32_t)(st->R / TK_STREAM_PACK_BLOCK + 1));
+    const size_t lds = TK_STREAM_SET_BYTES + (size_t)TK_STREAM_ROWS_WG * st->cap;
+    TRY(timed(c, s, "tk_k_stream_row", [&] {
+        drows_by_type(p.flags, [&](auto m) {
+            hipLaunchKernelGGL(tk_k_stream_row<decltype(m)::value>, grid_row, dim3(64 * TK_STREAM_ROWS_WG), lds, s, d_ids, d_begin, d_end, p, op, d_sel, c->t_dec.as<uint2>(), c->n_dec,
+                               c->D.tok_bytes, c->D.spec_bytes, st->set.as<uint32_t>(), st->mode, st->cap, cur, next, st->scratch.as<uint8_t>(), st->slot, len, chars, words);
+        });
+    }));
+    uint64_t* doc = st->doc.as<uint64_t>();
+    uint32_t* out = st->out.as<uint32_t>();
+    TRY(timed(c, s, "tk_k_stream_pack", [&] {
+        hipLaunchKernelGGL(tk_k_stream_pack, grid_pack, dim3(TK_STREAM_PACK_BLOCK), 0, s, st->R, len, chars, next, st->scratch.as<uint8_t>(), st->slot, words,
+                           st->text.as<uint8_t>(), doc, doc + (st->R + 1), out, out + st->R);
+    }));
+    unsigned long long* got = st->h_words.p + 8;
+    HIPCHK(hipMemcpyAsync(got, words, TK_STREAM_WORDS * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    if (got[TK_STREAM_BAD_ROW] != ~0ull)
+        return fail(TK_VALUE_ERROR, "begin and end must satisfy begin <= end <= width: row " + std::to_string(got[TK_STREAM_BAD_ROW]) + " does not");
+    if (got[TK_STREAM_BAD_ID] != ~0ull) return drows_invalid_token(d_ids, p, got[TK_STREAM_BAD_ID]);
+    if (got[TK_STREAM_OVERFLOW]) return fail(TK_RUNTIME_ERROR, "a row of the stream outgrew its buffer");
+    st->cur ^= 1;
+    st->n_text = got[TK_STREAM_N_TEXT];
+    st->n_chars = got[TK_STREAM_N_CHARS];
+    st->fetched = false;
+    return TK_OK;
+}
+// the opening of a stream's entries: run(s) under the core's mutex, on its device, the timed launches drained behind it
+template <class Run>
+static int stream_pass(tk_stream* st, void* stream, Run&& run) {
+    if (!st) return fail(TK_VALUE_ERROR, "stream is null");
+    return device_pass(st->c, true, stream, run);
+}
+// rows (null: all) as the byte per row the row kernel takes, in st->in; *d_sel null for all
+static int stream_select(tk_stream* st, hipStream_t s, const uint32_t* rows, uint64_t n, const uint8_t** d_sel) {
+    *d_sel = nullptr;
+    if (!rows) return TK_OK;
+    std::vector<uint8_t> sel(st->R + 1, 0);
+    for (uint64_t i = 0; i < n; ++i) {
+        if (rows[i] >= st->R) return fail(TK_VALUE_ERROR, "row " + std::to_string(rows[i]) + ": the stream has " + std::to_string(st->R) + " rows");
+        sel[rows[i]] = 1;
+    }
+    TRY(ensure(st->in, sel.size()));
+    HIPCHK(hipMemcpyAsync(st->in.p, sel.data(), sel.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));  // (sel goes with this frame)
+    *d_sel = st->in.as<uint8_t>();
+    return TK_OK;
+}
+// the last accepted call's outputs as host arrays of the stream
+static int stream_fetch(tk_stream* st, const uint8_t** text, uint64_t* n_text, const uint64_t** text_off, const uint64_t** char_off, const uint32_t** state,
+                        const uint32_t** hit) {
+    if (!st->fetched) {
+        const StreamView v = stream_view(st);
+        st->h_text.resize(st->n_text + 1);
+        st->h_text_off.resize(st->R + 1);
+        st->h_char_off.resize(st->R + 1);
+        st->h_state.resize(st->R + 1);
+        st->h_hit.resize(st->R + 1);
+        if (st->n_text) HIPCHK(hipMemcpy(st->h_text.data(), v.text, st->n_text, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(st->h_text_off.data(), v.text_off, (st->R + 1) * 8, hipMemcpyDeviceToHost));
+        if (v.char_off) HIPCHK(hipMemcpy(st->h_char_off.data(), v.char_off, (st->R + 1) * 8, hipMemcpyDeviceToHost));
+        if (st->R) {
+            HIPCHK(hipMemcpy(st->h_state.data(), v.state, st->R * 4, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(st->h_hit.data(), v.hit, st->R * 4, hipMemcpyDeviceToHost));
+        }
+        st->fetched = true;
+    }
+    if (text) *text = st->h_text.data();
+    if (n_text) *n_text = st->n_text;
+    if (text_off) *text_off = st->h_text_off.data();
+    if (char_off) *char_off = st->mode == TK_U8_BYTES ? nullptr : st->h_char_off.data();
+    if (state) *state = st->h_state.data();
+    if (hit) *hit = st->h_hit.data();
+    return TK_OK;
+}
+
+extern "C" void tk_stream_destroy(tk_stream* st) {
+    if (!st) return;
+    (void)hipSetDevice(st->device);
+    delete st;
+}
+extern "C" int tk_stream_create(tk_core* c, uint64_t n_rows, uint32_t w_max, const tk_drows_spec* spec, const tk_stops* stops, uint32_t stop_flags, uint32_t mode,
+                                tk_stream** stream_out) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if (!stream_out) return fail(TK_VALUE_ERROR, "null argument");
+    TRY(until_mode_check(mode));
+    TkStopSet set;
+    TRY(stops_check(stops, stop_flags, &set));
+    TkDrows p;
+    TRY(drows_check_spec(c, spec, n_rows, w_max, w_max, &p));
+    const uint64_t max_tok = std::max<uint64_t>(c->H.max_token_len, c->spec_max_len);
+    switch (tk_stream_shape(n_rows, w_max, max_tok, mode)) {
+        case 0: break;
+        case 1: return fail(TK_VALUE_ERROR, "w_max must be 1 .. 64: decode wider matrices with decode_rows_until");
+        case 2: return fail(TK_VALUE_ERROR, "more than 65536 rows in a stream");
+        case 3:
+            return fail(TK_VALUE_ERROR, "w_max = " + std::to_string(w_max) + " columns of tokens of up to " + std::to_string(max_tok) +
+                                            " bytes do not fit a row's buffer on the device: use decode_rows_until for such input");
+        default: return fail(TK_VALUE_ERROR, "mode must be TK_U8_REPLACE, TK_U8_IGNORE or TK_U8_BYTES");
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    std::unique_ptr<tk_stream, void (*)(tk_stream*)> st(new tk_stream, tk_stream_destroy);
+    st->c = c;
+    st->device = c->device;
+    st->R = n_rows;
+    st->w_max = w_max;
+    st->mode = mode;
+    st->spec = *spec;
+    st->dtype = spec->flags & (TK_DROWS_I32 | TK_DROWS_I64);
+    const uint64_t cap = tk_stream_cap(w_max, max_tok);
+    st->cap = (uint32_t)((cap + 15) & ~15ull);
+    st->slot = tk_stream_slot(cap, mode);
+    HIPCHK(st->h_words.alloc(16 * 8, hipHostMallocDefault));
+    const unsigned long long start[TK_STREAM_WORDS] = {~0ull, ~0ull, 0, 0, 0};
+    memcpy(st->h_words.p, start, sizeof start);
+    for (Buf& b : st->rows) {
+        TRY(ensure(b, n_rows * sizeof(TkStreamRow) + 16));
+        HIPCHK(hipMemset(b.p, 0, n_rows * sizeof(TkStreamRow) + 16));
+    }
+    TRY(upload(st->set, &set, sizeof set));
+    TRY(ensure(st->scratch, n_rows * st->slot + 16));
+    TRY(ensure(st->text, n_rows * st->slot + 16));
+    TRY(ensure(st->len, 2 * n_rows * 4 + 16));
+    TRY(ensure(st->doc, 2 * (n_rows + 1) * 8));
+    TRY(ensure(st->out, 2 * n_rows * 4 + 16));
+    TRY(ensure(st->words, TK_STREAM_WORDS * 8));
+    TRY(drained(c, [&] { return stream_run(st.get(), c->stream, TK_STREAM_OP_RESET, nullptr, 0, 0, nullptr, nullptr, nullptr); }));
+    *stream_out = st.release();
+    return TK_OK;
+}
+extern "C" int tk_stream_dtype(tk_stream* st, uint32_t dtype_flags) {
+    if (!st) return fail(TK_VALUE_ERROR, "stream is null");
+    if ((dtype_flags & ~(TK_DROWS_I32 | TK_DROWS_I64)) || dtype_flags == (TK_DROWS_I32 | TK_DROWS_I64)) return fail(TK_VALUE_ERROR, "dtype: 0, TK_DROWS_I32 or TK_DROWS_I64");
+    std::lock_guard<std::mutex> lk(st->c->mu);
+    st->dtype = dtype_flags;
+    return TK_OK;
+}
+extern "C" int tk_stream_step_device(tk_stream* st, const void* d_ids, uint64_t width, uint64_t ld, const void* d_begin, const void* d_end, void* stream,
+                                     const uint8_t** d_text_out, uint64_t* n_text_out, const uint64_t** d_text_off_out, const uint64_t** d_char_off_out,
+                                     const uint32_t** d_state_out, const uint32_t** d_hit_out) {
+    TRY(stream_pass(st, stream, [&](hipStream_t s) {
+        return stream_run(st, s, TK_STREAM_OP_STEP, d_ids, width, ld, (const uint32_t*)d_begin, (const uint32_t*)d_end, nullptr);
+    }));
+    const StreamView v = stream_view(st);
+    if (d_text_out) *d_text_out = v.text;
+    if (n_text_out) *n_text_out = st->n_text;
+    if (d_text_off_out) *d_text_off_out = v.text_off;
+    if (d_char_off_out) *d_char_off_out = v.char_off;
+    if (d_state_out) *d_state_out = v.state;
+    if (d_hit_out) *d_hit_out = v.hit;
+    return TK_OK;
+}
+extern "C" int tk_stream_fetch(tk_stream* st, const uint8_t** text_out, uint64_t* n_text_out, const uint64_t** text_off_out, const uint64_t** char_off_out,
+                               const uint32_t** state_out, const uint32_t** hit_out) {
+    return stream_pass(st, nullptr, [&](hipStream_t) { return stream_fetch(st, text_out, n_text_out, text_off_out, char_off_out, state_out, hit_out); });
+}
+extern "C" int tk_stream_step(tk_stream* st, const void* ids, uint64_t width, uint64_t ld, const uint32_t* begin, const uint32_t* end, const uint8_t** text_out,
+                              uint64_t* n_text_out, const uint64_t** text_off_out, const uint64_t** char_off_out, const uint32_t** state_out, const uint32_t** hit_out) {
+    return stream_pass(st, nullptr, [&](hipStream_t s) -> int {
+        if (width > st->w_max) return fail(TK_VALUE_ERROR, "a step of " + std::to_string(width) + " columns: the stream was created with w_max = " + std::to_string(st->w_max));
+        if (ld < width) return fail(TK_VALUE_ERROR, "ld must be at least the width");
+        if (!ids && st->R && width) return fail(TK_VALUE_ERROR, "null argument");
+        const uint64_t R = st->R, es = tk_drows_elem_size(st->dtype), n_elems = R && width ? (R - 1) * ld + width : 0;
+        if (ld >= (1ull << 40)) return fail(TK_VALUE_ERROR, "the matrix spans 2^60 elements or more");
+        Carve in;
+        const uint64_t at_ids = in.add(n_elems * es), at_begin = in.add(R * 4), at_end = in.add(R * 4);
+        TRY(ensure(st->in, in.total + 16));
+        if (n_elems) HIPCHK(hipMemcpyAsync(carved<void>(st->in, at_ids), ids, n_elems * es, hipMemcpyHostToDevice, s));
+        if (begin && R) HIPCHK(hipMemcpyAsync(carved<void>(st->in, at_begin), begin, R * 4, hipMemcpyHostToDevice, s));
+        if (end && R) HIPCHK(hipMemcpyAsync(carved<void>(st->in, at_end), end, R * 4, hipMemcpyHostToDevice, s));
+        TRY(stream_run(st, s, TK_STREAM_OP_STEP, carved<void>(st->in, at_ids), width, ld, begin ? carved<uint32_t>(st->in, at_begin) : nullptr,
+                       end ? carved<uint32_t>(st->in, at_end) : nullptr, nullptr));
+        return stream_fetch(st, text_out, n_text_out, text_off_out, char_off_out, state_out, hit_out);
+    });
+}
+extern "C" int tk_stream_flush(tk_stream* st, const uint32_t* rows, uint64_t n_listed, const uint8_t** text_out, uint64_t* n_text_out, const uint64_t** text_off_out,
+                               const uint64_t** char_off_out, const uint32_t** state_out, const uint32_t** hit_out) {
+    return stream_pass(st, nullptr, [&](hipStream_t s) -> int {
+        const uint8_t* d_sel;
+        TRY(stream_select(st, s, rows, n_listed, &d_sel));
+        TRY(stream_run(st, s, TK_STREAM_OP_FLUSH, nullptr, 0, 0, nullptr, nullptr, d_sel));
+        return stream_fetch(st, text_out, n_text_out, text_off_out, char_off_out, state_out, hit_out);
+    });
+}
+extern "C" int tk_stream_reset(tk_stream* st, const uint32_t* rows, uint64_t n_listed) {
+    return stream_pass(st, nullptr, [&](hipStream_t s) -> int {
+        const uint8_t* d_sel;
+        TRY(stream_select(st, s, rows, n_listed, &d_sel));
+        return stream_run(st, s, TK_STREAM_OP_RESET, nullptr, 0, 0, nullptr, nullptr, d_sel);
+    });
+}
+extern "C" int tk_stream_rows(tk_stream* st, uint32_t* state, uint32_t* hit, uint64_t* n_kept, uint64_t* n_text, uint64_t* n_chars) {
+    return stream_pass(st, nullptr, [&](hipStream_t) -> int {
+        std::vector<TkStreamRow> rows(st->R + 1);
+        if (st->R) HIPCHK(hipMemcpy(rows.data(), st->rows[st->cur].p, st->R * sizeof(TkStreamRow), hipMemcpyDeviceToHost));
+        for (uint64_t r = 0; r < st->R; ++r) {
+            if (state) state[r] = rows[r].state;
+            if (hit) hit[r] = rows[r].hit;
+            if (n_kept) n_kept[r] = rows[r].n_kept;
+            if (n_text) n_text[r] = rows[r].n_text;
+            if (n_chars) n_chars[r] = rows[r].n_chars;
+        }
         return TK_OK;
     });
 }
