@@ -156,7 +156,11 @@ def chop(row_ids, widths):
 
 
 # ---------------------------------------------------------------- a small vocabulary: id == byte below 256, a few longer tokens, ids without a token, two specials
-TOKENS = {256: b"\n\n", 257: b".\n\n", 258: b"Question:", 259: b" the", 260: "é".encode(), 261: "😀".encode(), 262: b"ab", 263: b"abc", 264: "中文".encode(), 265: b"x" * 40}
+STOP64 = S.stop_of(64, first=0x80)  # a stop string of the greatest length that starts with a continuation byte: a lead in front of it takes it
+TOKENS = {256: b"\n\n", 257: b".\n\n", 258: b"Question:", 259: b" the", 260: "é".encode(), 261: "😀".encode(), 262: b"ab", 263: b"abc", 264: "中文".encode(), 265: b"x" * 40,
+          266: b"\x80" * 40, 267: b"\xf0\x9f\x98", 268: STOP64[:30]}
+X40, BAD40, LEAD3, HALF_STOP = 265, 266, 267, 268
+ROW_LDS = 16000  # TK_STREAM_ROW_LDS: a row's buffer, HOLD + w_max * (the longest token), is at most this
 SPECIALS = {300: b"<|eot|>", 301: b"<|pad|>"}
 HOLE, N_IDS, PAD = 280, 302, 100000
 
@@ -181,3 +185,107 @@ def stop_cases():
         "the hit beats a lower, longer candidate": (["bc", "abcdef"], list(b"xabcdefy")),
         "a stop string inside a char's bytes": ([b"\x9f\x98"], list("a😀b".encode())),
     }
+
+
+# ---------------------------------------------------------------- steps as wide as the row's wavefront
+EDGES = (0, 31, 32, 33, 63, 64)  # begin and end on both sides of the wavefront's halves
+
+
+def full_width_steps():
+    """(the stream's arguments, steps): nine rows, no two alike, fed steps of 64, 63, 33, 32 and 64 columns -- begin and end per row at
+    every one of EDGES, stop ids at columns 31, 32 and 63 (and outside a row's range, where they do not count), skipped ids and a skipped
+    special all over both halves, a stop string across columns 31 / 32; HOLE where a row has ended: such ids are not judged."""
+    rng = np.random.default_rng(0xF011)
+    alphabet = [32, 46, 97, 98, 99, 100, 101, 0xC3, 0xA9, 0xE4, 0x98, 0xF0, 259, 260, 261, 262, 263, 264, X40, 7, 7, PAD, PAD, 301]
+
+    def ids(W, dead=()):
+        m = rng.choice(alphabet, size=(9, W)).astype(np.int64)
+        m[list(dead)] = HOLE
+        return m
+
+    s1 = ids(64)
+    s1[0, 63] = s1[6, 40] = s1[1, 5] = 300  # (row 6 ends at 31, row 1 begins at 31: only row 0's counts)
+    s2 = ids(63, dead=[0])
+    s2[1, 31] = s2[2, 32] = 300
+    s3 = ids(33, dead=[0, 1, 2])
+    s3[8, 31] = s3[8, 32] = 10
+    s4 = ids(32, dead=[0, 1, 2, 8])
+    s5 = ids(64, dead=[0, 1, 2, 8])
+    s5[3, 32], s5[4, 63], s5[5, 31] = 300, 300, 300
+    steps = [(s1, [0, 31, 32, 33, 63, 64, 0, 0, 0], [64, 64, 64, 64, 64, 64, 31, 32, 33]), (s2, [0, 0, 0, 31, 32, 33, 62, 63, 0], [63] * 9),
+             (s3, None, [0, 0, 0, 0, 31, 32, 33, 33, 33]), (s4, [0, 0, 0, 31, 32, 0, 0, 0, 0], None), (s5, None, None)]
+    return dict(stops=[b"\n\n"], stop=[300], skip=[PAD, 7], skip_special=True, w_max=64), steps
+
+
+def coverage(ref: Stream, steps):
+    """what the steps reach, by the rule alone (ref: a fresh Stream, fed here): the begins and ends of rows that were live, the columns of
+    the stop ids that ended a row, the halves of the wavefront in which a skipped id was passed over, the states at the end"""
+    begins, ends, stop_cols, skipped = set(), set(), set(), set()
+    for ids, begin, end in steps:
+        ids = np.asarray(ids, np.int64)
+        W = ids.shape[1]
+        for r in range(ref.R):
+            if ref.state[r] != LIVE:
+                continue
+            b, e = (0 if begin is None else int(begin[r])), (W if end is None else int(end[r]))
+            begins.add(b), ends.add(e)
+            row = ids[r].tolist()
+            s = next((c for c in range(b, e) if row[c] in ref.rule["stop"]), e)
+            if s < e:
+                stop_cols.add(s)
+            skipped |= {c >= 32 for c in range(b, s) if row[c] in ref.rule["skip"] or (ref.rule["skip_special"] and ref.special(row[c]))}
+        ref.step(ids, begin, end)
+    return dict(begins=begins, ends=ends, stop_cols=stop_cols, skipped=skipped, state=list(ref.state))
+
+
+# ---------------------------------------------------------------- more than 1024 bytes emitted by one row in one call
+def straddles(piece: bytes, at: int) -> bool:
+    """a well-formed char of several bytes lies on both sides of byte offset `at` of `piece`"""
+    starts, _ = unit_starts(piece)
+    return any(a < at < b for a, b in zip(starts[:-1], starts[1:]))
+
+
+def long_emit_steps():
+    """(stop strings, steps) for five rows.  Step 2 is 64 columns of mostly the 40-byte tokens: over 2048 bytes a row, three turns of the
+    emit loop -- ASCII with short tokens between the long ones (so that a turn written to the wrong place shows), the same behind a held
+    byte, 2560 bytes of 0x80, and two rows of chars of 2, 3 and 4 bytes of which one lies across byte 1024 and one across byte 2048.  Step 3:
+    rows 0 and 1 end by a stop id behind 1024 bytes whose last is an unfinished lead, and behind 1025 with the lead's first continuation;
+    the others take an unfinished lead into their tails, which the flush emits."""
+    x, cjk, e2, smile = X40, 264, 260, 261
+    ascii_row = [x] * 64
+    for c, t in ((5, 258), (26, 259), (27, 46), (40, 263), (52, 262), (63, 97)):
+        ascii_row[c] = t
+
+    def chars(lead):  # the chars across 1024 and 2048 for a lead of 1 or 2 bytes
+        return [lead] + [x] * 25 + [cjk, cjk, smile, e2, cjk] + [x] * 25 + [cjk, cjk, e2, cjk, smile] + [e2, cjk, x]
+
+    s1 = np.array([[0], [10], [0], [0], [0]], np.int64)
+    s2 = np.array([ascii_row, [x] * 64, [BAD40] * 64, chars(97), chars(262)], np.int64)
+    assert s2.shape == (5, 64)
+    head = [x] * 25 + [258, 259, 259, 259, 262, 0xF0]  # 1024 bytes, the last a lead
+    s3 = np.full((5, 64), HOLE, np.int64)
+    s3[0, :32], s3[1, :33] = head + [300], head + [0x9F, 300]
+    s3[2, 0], s3[3, :2] = 0xF0, [10, 0xE4]
+    s3[4] = [e2, smile] * 32
+    s3[4, 63] = 0xF0
+    return [b"\n\n"], [(s1, None, [0, 1, 0, 0, 0]), (s2, None, None), (s3, None, [32, 33, 1, 2, 64])]
+
+
+# ---------------------------------------------------------------- tails at the most a row holds back
+def hold_cases():
+    """name -> (ids fed one per step unless they are a tuple: a step of several, the longest tail the row holds unless it holds bytes
+    only, it ends by the stop string): STOP64 behind an unfinished lead whose next byte it may be.  F0 takes 90 .. BF only, so it is a unit
+    of its own in front of STOP64's 80 and the row holds the 63 bytes alone; F1 takes it, which gives the 64."""
+    out = {}
+    for lead, held in ((b"\xf0", 63), (b"\xf1", 64), (b"\xf0\x9f", 65), (b"\xf0\x9f\x98", 66)):
+        for last, hit in ((STOP64[63], True), (0x41, False)):
+            out[f"{lead.hex()} then a byte per step, {'hit' if hit else 'broken'}"] = (list(b"ab") + list(lead) + list(STOP64[:63]) + [last, 0x42], held, hit)
+    for last, hit in ((STOP64[63], True), (0x41, False)):
+        what = "hit" if hit else "broken"
+        out[f"a lead and 30 bytes in one step, {what}"] = ([98, (LEAD3, HALF_STOP)] + list(STOP64[30:63]) + [last, 0x42], 66, hit)
+        out[f"30 bytes in one token behind f09f, {what}"] = ([0xF0, 0x9F, HALF_STOP, tuple(STOP64[30:62])] + [STOP64[62], last, 0x42], 65, hit)
+    return out
+
+
+def hold_steps(ids):
+    return [(np.array([list(t) if isinstance(t, tuple) else [t]], np.int64), None, None) for t in ids]

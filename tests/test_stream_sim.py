@@ -257,3 +257,97 @@ def test_random_streams(mode):
                 rows = rng.choice(n_rows, size=int(rng.integers(1, n_rows + 1)), replace=False).tolist()
                 sim.reset(rows), ref.reset(rows)
         finish(sim, ref, trial)
+
+
+# ---------------------------------------------------------------- steps as wide as the wavefront, rows that emit in several turns, tails at the limit
+ORDERS = (0, 1, 2)
+
+
+@pytest.mark.parametrize("keep_stop", (False, True))
+@pytest.mark.parametrize("order", ORDERS)
+@pytest.mark.parametrize("mode", MODES)
+def test_full_width_steps(mode, order, keep_stop):
+    kw, steps = R.full_width_steps()
+    stops = kw.pop("stops")
+    assert sorted(len(s[0][0]) for s in steps) == [32, 33, 63, 64, 64]
+    seen = R.coverage(R.Stream(9, stops, token_bytes=token_bytes, special=lambda t: t in SPECIALS, keep_stop=keep_stop, mode=mode, **kw), steps)
+    assert seen["begins"] >= set(R.EDGES) and seen["ends"] >= set(R.EDGES) and seen["stop_cols"] >= {31, 32, 63} and seen["skipped"] == {False, True}, seen
+    assert seen["state"].count(R.STOP_ID) == 6 and seen["state"][8] == R.STOP_TEXT, seen
+    sim, ref = pair(9, stops, order=order, keep_stop=keep_stop, mode=mode, **kw)
+    feed(sim, ref, steps, (mode, order, keep_stop))
+    assert len(set(ref.emitted)) == 9  # (no two rows alike)
+    finish(sim, ref)
+
+
+@pytest.mark.parametrize("order", ORDERS)
+@pytest.mark.parametrize("mode", MODES)
+def test_more_than_1024_bytes_emitted_in_one_call(mode, order):
+    stops, steps = R.long_emit_steps()
+    sim, ref = pair(5, stops, order=order, stop=[300], mode=mode, w_max=64)
+    feed(sim, ref, steps[:1])
+    assert ref.tail == [b"", b"\n", b"", b"", b""]
+    raw = [ref.tail[r] + b"".join(token_bytes(t) for t in steps[1][0][r].tolist()) for r in range(5)]
+    assert all(len(b) > 2048 for b in raw) and len(raw[1]) == 2561 and raw[2] == b"\x80" * 2560
+    assert all(R.straddles(raw[r], 1024) and R.straddles(raw[r], 2048) for r in (3, 4)) and raw[3][1022:1025] == "文".encode() and raw[4][2046:2050] == "😀".encode()
+    got, want = sim.step(steps[1][0]), ref.step(steps[1][0])
+    assert want == [{R.REPLACE: R.U.FFFD * 2560, R.IGNORE: b"", R.BYTES: raw[2]}[mode] if r == 2 else raw[r] for r in range(5)]  # (the rule, before the simulation is asked)
+    assert got == want and sim.view() == ref_view(ref)
+    assert ref.tail == [b""] * 5
+    got, want = sim.step(*steps[2]), ref.step(*steps[2])
+    lead = {R.REPLACE: R.U.FFFD, R.IGNORE: b"", R.BYTES: b"\xf0"}[mode]
+    assert len(want[0]) == 1023 + len(lead) and want[0].endswith(b"ab" + lead) and want[1] == want[0][:1023] + {R.REPLACE: R.U.FFFD, R.IGNORE: b"", R.BYTES: b"\xf0\x9f"}[mode]
+    assert got == want and sim.view() == ref_view(ref)
+    assert ref.state == [R.STOP_ID, R.STOP_ID, R.LIVE, R.LIVE, R.LIVE] and ref.tail[2:] == ([b"\xf0", b"\xe4", b"\xf0"] if mode != R.BYTES else [b""] * 3)
+    finish(sim, ref)
+
+
+@pytest.mark.parametrize("order", ORDERS)
+@pytest.mark.parametrize("mode", MODES)
+def test_tails_at_the_hold_limit(mode, order):
+    longest = set()
+    for name, (ids, held, hit) in R.hold_cases().items():
+        for keep in (False, True):
+            steps = R.hold_steps(ids)
+            sim, ref = pair(1, [R.STOP64, b"\n\n"], order=order, keep_stop_text=keep, mode=mode, w_max=max(s[0].shape[1] for s in steps))
+            most = 0
+            for k, s in enumerate(steps):
+                feed(sim, ref, [s], (name, k))
+                most = max(most, len(ref.tail[0]))
+            assert most == (held if mode != R.BYTES else 63), (name, most)  # (the case is void unless the rule's own tail gets there)
+            longest.add(most)
+            assert ref.state == [R.STOP_TEXT if hit else R.LIVE] and ref.hit == [0 if hit else R.NO_HIT], name
+            finish(sim, ref, name)
+    assert longest == ({63, 64, 65, R.HOLD} if mode != R.BYTES else {63})
+
+
+WIDE_ALPHABET = [10, 10, 46, 97, 98, 99, 0xC3, 0xA9, 0xF0, 0x9F, 0x98, 0x80, 0xE4, 256, 257, 258, 260, 261, 262, 263, 264, 7, PAD, 301, R.X40, R.X40, R.BAD40, R.LEAD3, R.HALF_STOP,
+                 0xB1, 0xB2]
+LONG_ALPHABET = [R.X40] * 12 + [R.BAD40] * 4 + [260, 261, 264, 0xF0, 0xC3, 0xE4, 97, 46, 32, 7, PAD, 301, R.HALF_STOP, 0xB1]  # (every third trial: rows that live long and emit much)
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_random_wide_streams(mode):
+    """as test_random_streams, in steps of 0 .. 64 columns over an alphabet with the 40-byte tokens and the pieces of the 64-byte stop string"""
+    rng = np.random.default_rng(0x51DE + mode)
+    turns = []
+    for trial in range(40):
+        n_rows = int(rng.integers(1, 6))
+        stops = [[b"\n\n", b"Question:", b"abc", b"ab", "é😀".encode(), b"\x98", b".\n\nab", R.STOP64, R.STOP64[:33]][i] for i in rng.choice(9, size=int(rng.integers(0, 5)), replace=False)]
+        kw = dict(stop=[300] if trial % 2 else [], skip=[PAD, 7], skip_special=bool(trial % 3 == 0), keep_stop=bool(trial % 5 == 0), keep_stop_text=bool(trial % 2), mode=mode, w_max=64)
+        sim, ref = pair(n_rows, stops, order=trial % 3, **kw)
+        for _ in range(int(rng.integers(1, 12))):
+            W = int(rng.integers(0, 65))
+            ids = rng.choice(LONG_ALPHABET if trial % 3 == 1 else WIDE_ALPHABET, size=(n_rows, W)).astype(np.int64)
+            if W and rng.random() < 0.3:
+                ids[int(rng.integers(0, n_rows)), int(rng.integers(0, W))] = 300
+            end = rng.integers(0, W + 1, size=n_rows) if rng.random() < 0.3 else None
+            begin = np.minimum(rng.integers(0, W + 1, size=n_rows), end if end is not None else W) if rng.random() < 0.3 else None
+            before = list(ref.n_text)
+            feed(sim, ref, [(ids, begin, end)], trial)
+            turns.append(max(a - b for a, b in zip(ref.n_text, before)))
+            if rng.random() < 0.1:
+                rows = rng.choice(n_rows, size=int(rng.integers(1, n_rows + 1)), replace=False).tolist()
+                sim.reset(rows), ref.reset(rows)
+        finish(sim, ref, trial)
+    if mode != R.IGNORE:
+        assert sum(1 for t in turns if t > 1024) >= 3, sorted(turns)[-5:]  # (rows that emit in more than one turn are among them)
