@@ -5,6 +5,7 @@ import random
 
 import numpy as np
 
+from utf8_repair_ref import WIDE_FORCED, WIDE_N, WIDE_PREFIXES, draw, pooled_docs, spread  # noqa: F401  (the pooled batches' sizes and tools)
 from utf8_repair_ref import pack  # noqa: F401  (bytes with 16 readable bytes of 0xA5 behind them, n, byte_off)
 
 NO_HIT = 0xFFFFFFFF
@@ -116,6 +117,38 @@ def random_cases(seed: int, count: int):
         docs = [bytes(rng.choice(alphabet) for _ in range(rng.choice([0, 1, 7, 40, 300, 5000]))) for _ in range(rng.choice([1, 3, 12]))]
         out.append((f"random {i}", docs, stops))
     return out
+
+
+# ---------------------------------------------------------------- pooled batches (utf8_repair_ref.py: WIDE_N documents from a small pool)
+WIDE_STOPS = [b"<END>", b"##", b"<EN"]  # where <END> lies, <EN lies too: the list's order decides there
+NO_STOPS = [b"\n\n", b"<ENX", b"#!"]  # strings that lie nowhere in the pool's documents; two of them start like ones that do
+WIDE_POOL = [
+    # no hit: empty, plain, and the halves of stop strings -- a proper prefix at the end, the rest at the start: neighbours form a match
+    # across their boundary, which is none
+    b"", b"", b"a", b"plain text", b"twelve bytes", "中文".encode(), b"xy<E", b"ND>zz", b"ab#", b"#cd", b"q<", b"EN", b"D>", b"<E#N>",
+    # a hit at byte 0, in the middle, at the end; the document that is the stop string
+    b"<END>tail", b"ab<END>cd", b"abc<END>", b"##", b"x##y", "中##".encode(), b"0123456789##",
+    # two strings at different places (the position decides), one string alone where the other is cut short
+    b"a##b<END>", b"<END>##", b"<EN##", b"x<ENx", b"#<EN", b"z<END",
+]
+
+
+def wide_batch():
+    """(pool, idx): WIDE_N documents; those of WIDE_FORCED have a hit behind their first byte and before their last, with either `keep`"""
+    mid = [i for i, p in enumerate(WIDE_POOL) if 1 <= cut_doc(p, WIDE_STOPS, False)[0] and cut_doc(p, WIDE_STOPS, True)[0] < len(p)]
+    return WIDE_POOL, draw(len(WIDE_POOL), mid, 0x570D)
+
+
+def pooled_cut(pool, idx, stops, keep: bool):
+    """`cut_batch` of the documents pool[idx], the rule run once per pool entry: (text uint8[...], text_off uint64[n + 1], hit uint32[n])"""
+    per = [cut_doc(p, stops, keep) for p in pool]
+    text, text_off = spread([p[:kept] for p, (kept, _) in zip(pool, per)], idx)
+    return text, text_off, np.array([k for _, k in per], np.uint32)[idx]
+
+
+def crosses(a: bytes, b: bytes, stops) -> bool:
+    """a stop string lies in a + b across the boundary between the two"""
+    return any((a + b)[p:p + len(s)] == s for s in stops for p in range(max(len(a) - len(s) + 1, 0), len(a)) if p + len(s) > len(a))
 
 
 def stop_arrays(stops):

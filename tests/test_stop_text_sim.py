@@ -130,6 +130,49 @@ def test_token_counts():
                 assert got == S.n_tok_ref(lens, kept), (lens, kept)
 
 
+# ---------------------------------------------------------------- the pooled batch of tests/test_gpu_text_passes_wide.py, without a GPU
+WINDOWS = ((0, 5000), ((1 << 20) - 1070, (1 << 20) + 1030))  # a prefix, and the 2 100 documents around index 2^20, the last among them
+
+
+def test_pooled_reference_is_the_per_document_one():
+    pool, idx = S.wide_batch()
+    assert len(idx) == S.WIDE_N == (1 << 20) + 1030 and S.WIDE_PREFIXES[-1] == S.WIDE_N
+    for stops in (S.WIDE_STOPS, S.NO_STOPS):
+        for keep in (False, True):
+            text, text_off, hit = S.pooled_cut(pool, idx, stops, keep)
+            assert len(text_off) == S.WIDE_N + 1 and len(hit) == S.WIDE_N and len(text) == text_off[-1]
+            for lo, hi in WINDOWS:
+                want_text, want_off, want_hit, _ = S.cut_batch(S.pooled_docs(pool, idx, lo, hi), stops, keep)
+                assert bytes(text[int(text_off[lo]):int(text_off[hi])]) == want_text, (keep, lo)
+                assert (text_off[lo:hi + 1] - text_off[lo]).tolist() == want_off, (keep, lo)
+                assert hit[lo:hi].tolist() == want_hit, (keep, lo)
+
+
+def test_pooled_batch_holds_what_it_was_built_for():
+    pool, idx = S.wide_batch()
+    stops = S.WIDE_STOPS
+    assert all(len(p) <= 12 for p in pool) and len(pool) <= 48
+    assert np.array_equal(np.unique(idx), np.arange(len(pool)))  # every entry is drawn
+    cut = {p: S.cut_doc(p, stops, False) for p in pool}
+    assert b"" in cut and cut[b"plain text"] == (10, S.NO_HIT)
+    assert cut[b"<END>tail"] == (0, 0) and cut[b"ab<END>cd"] == (2, 0) and cut[b"abc<END>"] == (3, 0) and cut[b"##"] == (0, 1)
+    assert cut[b"xy<E"][1] == S.NO_HIT and cut[b"ND>zz"][1] == S.NO_HIT and S.crosses(b"xy<E", b"ND>zz", stops)  # the halves of a stop string
+    assert cut[b"a##b<END>"] == (1, 1) and cut[b"<END>##"] == (0, 0) and cut[b"<EN##"] == (0, 2) and cut[b"x<ENx"] == (1, 2)  # position, then list order
+    for d in S.WIDE_FORCED:  # a hit in the middle, something kept, on both sides of every edge
+        p = pool[idx[d]]
+        for keep in (False, True):
+            kept, k = S.cut_doc(p, stops, keep)
+            assert k != S.NO_HIT and 1 <= kept < len(p), (d, p)
+    cross = np.array([[S.crosses(a, b, stops) for b in pool] for a in pool])
+    assert cross[idx[:-1], idx[1:]].sum() > 1000  # neighbours that form a stop string across their boundary ...
+    assert not any(S.crosses(a, b, S.NO_STOPS) or S.cut_doc(a, S.NO_STOPS, False)[1] != S.NO_HIT for a in pool for b in pool)
+    for n in S.WIDE_PREFIXES[:3]:  # ... already in the smallest prefixes
+        assert cross[idx[:n - 1], idx[1:n]].any()
+    has_hit = np.array([cut[p][1] != S.NO_HIT for p in pool])[idx]
+    for n in S.WIDE_PREFIXES:
+        assert 0.25 < has_hit[:n].mean() < 0.75, n
+
+
 # ---------------------------------------------------------------- under the sanitizers, as a program of its own
 def test_passes_under_the_sanitizers(tmp_path):
     """tests/hostsim/stop_text_sanitize.cpp: the same driver built with AddressSanitizer and UBSan, the input allocated so that it ends

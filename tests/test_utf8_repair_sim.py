@@ -102,6 +102,20 @@ def test_growth_three_fold_over_several_workgroups():
     check([b"ab", b"\x80" * 5000, b"", b"\xbf" * 33, b"z"])
 
 
+def test_growth_reaches_the_count_pass_s_bound():
+    """R.growth: the most one workgroup leaves is 3 x its bytes + 3 -- the bound tk_k_u8r_count states for its 16-bit scan -- and the inputs
+    reach it, by CPython's incremental decoder; the passes agree with the rule on them at the kernels' geometry and at a smaller one"""
+    for block, wg in ((4096, 256), (256, 16)):
+        most = []
+        for docs in R.growth(block):
+            per_wg = R.charged(docs, block)
+            assert sum(per_wg) == len(R.repair_batch(docs, R.REPLACE)[0])
+            most.append(max(per_wg))
+            check(docs, wgs=(wg,), orders=(0, 2))
+        assert most[0] == 3 * block and most[1:4] == [3 * block - 3 * k + 3 for k in (1, 2, 3)]  # a lead that its document's end cuts is charged there
+        assert most[4:10] == [3 * block + 3] * 6 and max(most) == 3 * block + 3 < 1 << 16
+
+
 def test_clean_text_takes_no_write_pass():
     clean = [("The quick brown fox. 中文😀é " * 40).encode(), b"", b"plain", "żółć".encode() * 500]
     for mode in MODES:
@@ -142,6 +156,43 @@ def test_offsets_that_do_not_ascend_to_n_are_refused():
         totals = np.zeros(5, np.uint64)
         rc = lib().u8r_run(blob.ctypes.data, n, o.ctypes.data, 2, 0, 16, 0, out.ctypes.data, offs[0].ctypes.data, offs[1].ctypes.data, offs[2].ctypes.data, totals.ctypes.data)
         assert rc == 1000 + doc, (bad, rc)
+
+
+# ---------------------------------------------------------------- the pooled batch of tests/test_gpu_text_passes_wide.py, without a GPU
+WINDOWS = ((0, 5000), ((1 << 20) - 1070, (1 << 20) + 1030))  # a prefix, and the 2 100 documents around index 2^20, the last among them
+
+
+def test_pooled_reference_is_the_per_document_one():
+    pool, idx = R.wide_batch()
+    assert len(idx) == R.WIDE_N == (1 << 20) + 1030 and R.WIDE_PREFIXES[-1] == R.WIDE_N
+    for mode in MODES:
+        R.check_against_cpython(pool, mode)  # ties the pooled reference to CPython's decoder: the GPU test compares with it alone
+        text, *offs = R.pooled_repair(pool, idx, mode)
+        assert all(len(o) == R.WIDE_N + 1 for o in offs) and len(text) == offs[0][-1]
+        for lo, hi in WINDOWS:
+            want_text, *want_offs = R.repair_batch(R.pooled_docs(pool, idx, lo, hi), mode)
+            assert bytes(text[int(offs[0][lo]):int(offs[0][hi])]) == want_text, (mode, lo)
+            for o, w in zip(offs, want_offs):
+                assert (o[lo:hi + 1] - o[lo]).tolist() == w, (mode, lo)
+
+
+def test_pooled_batch_holds_what_it_was_built_for():
+    pool, idx = R.wide_batch()
+    assert all(len(p) <= 12 for p in pool) and len(pool) <= 48
+    assert np.array_equal(np.unique(idx), np.arange(len(pool)))  # every entry is drawn
+    for whole in (b"", b"hello", "é".encode(), "中".encode(), "😀".encode()):
+        assert whole in pool and R.repair(whole, R.REPLACE) == (whole, len(whole.decode()), 0)
+    for cut, rest in ((b"x\xe4\xb8", b"\xad z"), (b"ab\xe4", b"\xb8\xad"), (b"\xf0\x9f\x98", b"\x80"), (b"\xf0\x9f", b"\x98\x80ok"), (b"\xc3", b"\xa9")):
+        assert cut in pool and rest in pool and R.repair(cut + rest, R.REPLACE)[2] == 0  # together they are a char; apart, two ill-formed units at least
+        assert R.repair(cut, R.IGNORE)[2] >= 1 and R.repair(rest, R.IGNORE)[2] >= 1
+        a, b = pool.index(cut), pool.index(rest)
+        assert ((idx[:-1] == a) & (idx[1:] == b)).any()  # ... and they are neighbours somewhere
+    for lone in (b"\x80", b"\xbf\xbf", b"\xc0\x80", b"x\xf5y", b"\xff"):
+        assert lone in pool
+    ill = np.array([R.repair(p, R.REPLACE)[2] > 0 for p in pool])
+    assert ill[idx[list(R.WIDE_FORCED)]].all()  # an ill-formed unit on both sides of every edge
+    for n in R.WIDE_PREFIXES:
+        assert 0.25 < ill[idx[:n]].mean() < 0.75, n
 
 
 # ---------------------------------------------------------------- under the sanitizers, as a program of its own

@@ -128,6 +128,40 @@ def random_batches(seed: int, count: int):
     return out
 
 
+def growth(block: int):
+    """Batches (each meant to start at a workgroup's first byte) whose output per workgroup of `block` bytes is as large as 'replace' can
+    make it: every byte an ill-formed unit of its own, three bytes each, and before them a lead at the end of the workgroup before, whose
+    replacement is charged to the byte that does not continue it -- 3 x block + 3 bytes from one workgroup (`charged`)."""
+    cont, ff = b"\x80" * block, b"\xff" * block
+    out = [[cont]]
+    out += [[lead, cont] for lead in (b"\xe4", b"\xf0\x9f", b"\xf0\x9f\x98")]  # the same document 1, 2 and 3 bytes behind a lead that its document's end cuts
+    for lead, run in ((b"\xf0", cont), (b"\xe0", cont), (b"\xf4", b"\x90" * block), (b"\xc2", ff), (b"\xf0\x9f", ff), (b"\xf0\x9f\x98", ff)):
+        out.append([b"x" * (block - len(lead)) + lead + run + b"z"])  # the lead inside the document: the next workgroup pays for it
+    out.append([b"\xff" * (3 * block + 5)])
+    out.append([b"\xf0\x9f\x98" * (block // 3 + 2)])  # every unit keeps its length
+    out.append([b"\xc2" * (block + 7)])  # every unit grows, and each is charged to the byte behind it
+    out.append([b"ab", b"\xf0\x9f\x98" * (2 * block // 3), b"\xc2" * block, b"\x80"])
+    return out
+
+
+def charged(docs, block: int):
+    """The bytes that 'replace' leaves per `block` bytes of the packed documents, a unit counted at the byte where its fate is known (the
+    lane rule of tk_utf8_repair_rule.h) -- by CPython's incremental decoder, which holds back exactly a sequence that may still continue."""
+    import codecs
+
+    out = [0] * (sum(map(len, docs)) // block + 1)
+    pos = 0
+    for d in docs:
+        dec = codecs.getincrementaldecoder("utf-8")("replace")
+        i = 0
+        while i < len(d):
+            j = min(len(d), i + block - pos % block)  # up to the next workgroup's first byte
+            out[pos // block] += len(dec.decode(d[i:j], final=j == len(d)).encode())
+            pos += j - i
+            i = j
+    return out
+
+
 def pack(docs):
     """(bytes uint8 with 16 readable bytes behind them that are not zero, n, byte_off uint64[n + 1])"""
     n = sum(len(d) for d in docs)
@@ -136,3 +170,70 @@ def pack(docs):
     if docs:
         off[1:] = np.cumsum([len(d) for d in docs], dtype=np.uint64)
     return blob, n, off
+
+
+# ---------------------------------------------------------------- pooled batches: very many documents drawn from a few dozen
+# What a batch of a million documents can show lies in the code around the lanes (the second workgroup of a scan, the second trip of a
+# grid-stride loop), not in the documents: these are drawn from a small pool, the rule runs once per pool entry, and numpy spreads the
+# result over the batch.  One batch of WIDE_N documents; every smaller size is a prefix of it, and its reference a slice.
+WIDE_N = (1 << 20) + 1030
+WIDE_PREFIXES = (1024, 1025, 2051, (1 << 20) - 1, 1 << 20, WIDE_N)
+# the documents on both sides of the 1024-document workgroups' edges and of the 2^20 items of a capped grid, and the last
+WIDE_FORCED = (1023, 1024, 1025, 2047, 2048, (1 << 20) - 1, 1 << 20, (1 << 20) + 1, WIDE_N - 1)
+
+
+def draw(n_pool: int, forced, seed: int, n: int = WIDE_N, at=WIDE_FORCED):
+    """the pool entry of each of n documents: uniform, seeded; the documents `at` take the entries `forced` in turn"""
+    idx = np.random.default_rng(seed).integers(0, n_pool, n)
+    forced = list(forced)
+    for k, d in enumerate(at):
+        idx[d] = forced[k % len(forced)]
+    return idx
+
+
+def spread(parts, idx, dtype=np.uint8):
+    """parts[i] (bytes, or a list of numbers) for every i of idx back to back: (the elements as one array, offsets uint64[len(idx) + 1])"""
+    lens = np.array([len(p) for p in parts], np.int64)
+    table = np.zeros((len(parts), max(int(lens.max()), 1)), dtype)
+    for i, p in enumerate(parts):
+        table[i, :len(p)] = np.frombuffer(p, np.uint8) if isinstance(p, bytes) else p
+    took = lens[idx]
+    off = np.zeros(len(idx) + 1, np.uint64)
+    off[1:] = np.cumsum(took)
+    return table[idx][np.arange(table.shape[1]) < took[:, None]], off
+
+
+def running(per_entry, idx):
+    """the running total, n + 1 entries, of a figure known per pool entry"""
+    out = np.zeros(len(idx) + 1, np.uint64)
+    out[1:] = np.cumsum(np.asarray(per_entry, np.int64)[idx])
+    return out
+
+
+WIDE_POOL = [
+    # well-formed: empty, ASCII, whole chars of two, three and four bytes
+    b"", b"", b"a", b" ", b"hello", b"12345678", b"The quick br", "é".encode(), "中".encode(), "😀".encode(), "文😀".encode(), "aé中😀".encode(), "żółć".encode(),
+    # a lead that its document's end cuts ...
+    b"ab\xe4", b"x\xe4\xb8", b"\xf0\x9f\x98", b"\xc3", b"q\xf0", b"\xf0\x9f", "中".encode() + b"\xe4",
+    # ... and the continuation bytes it misses at the start of another
+    b"\xb8\xad", b"\xad z", b"\x80", b"\x98\x80ok", b"\xa9",
+    # lone continuation bytes, C0, F5, FF, and leads whose first continuation byte is outside the narrowed range
+    b"a\x80b", b"\xbf\xbf", b"\xc0\x80", b"x\xf5y", b"\xff", b"\xff\xff\xff", b"\xed\xa0\x80", b"\xe0\x9f\xbf", b"\xf4\x90\x80\x80",
+]
+
+
+def wide_batch():
+    """(pool, idx): WIDE_N documents; those of WIDE_FORCED hold an ill-formed unit"""
+    ill = [i for i, p in enumerate(WIDE_POOL) if repair(p, REPLACE)[2]]
+    return WIDE_POOL, draw(len(WIDE_POOL), ill, 0x81DE)
+
+
+def pooled_docs(pool, idx, lo: int = 0, hi=None):
+    return [pool[i] for i in idx[lo:hi].tolist()]
+
+
+def pooled_repair(pool, idx, mode: int):
+    """`repair_batch` of the documents pool[idx], the rule run once per pool entry: (text uint8[...], text_off, char_off, repl_off), arrays"""
+    per = [repair(p, mode) for p in pool]
+    text, text_off = spread([t for t, _, _ in per], idx)
+    return text, text_off, running([c for _, c, _ in per], idx), running([r for _, _, r in per], idx)
