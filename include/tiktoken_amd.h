@@ -254,6 +254,72 @@ int tk_encode_batch_padded(tk_core* core, const uint8_t* utf8, const uint64_t* d
                            const uint32_t* allowed_ids, uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed,
                            const tk_pad_spec* spec, void** ids_out, uint8_t** mask_out, uint32_t** len_out, uint32_t** row_doc_out,
                            uint32_t** row_tok_out, uint32_t** doc_row_out, uint64_t* n_rows_out, uint64_t* width_out, tk_special_hit* hit);
+/* Text chunks: every document of a batch cut into pieces of at most max_tokens tokens, each cut placed at the best separator that fits
+ * (a blank line before a line break before a sentence end before a space) and never inside a char.  Replaces nothing in the reference: it
+ * is the host loop of the reference's users, the text splitter of a retrieval or embedding ingest that counts tokens with the encoder
+ * (elsewhere `RecursiveCharacterTextSplitter.from_tiktoken_encoder`) -- here one call on ids and text that are on the device anyway.
+ * The rule.  Input: tokens uint32[T], tok_off uint64[n_docs + 1]; the text they were encoded from, utf8 and doc_off uint64[n_docs + 1]; a
+ * tk_split_spec: max_tokens N, min_tokens M, overlap O, n_levels L <= 4 levels of up to 4 separators each (level 0 is the best place to
+ * cut), seg_tokens K.  A separator is a pair (tail, head) of byte strings of 0 .. 16 bytes, not both empty.  Document d has
+ * n_d = tok_off[d + 1] - tok_off[d] tokens.
+ *  Token boundaries.  Boundary i of a document (0 < i < n_d) lies before its token i, at byte p = byte_start[i] of the document (the
+ *   span rule of tk_token_spans_device).  It MATCHES a separator when the document's bytes before p end with tail and its bytes from p on
+ *   start with head -- both inside the document: ("\n\n", "") cuts behind a blank line, ("", " ") before a space, (".", " ") behind a
+ *   sentence's full stop but not inside 3.14.  It is LEGAL when the byte at p is not a continuation byte 0x80 .. 0xBF.  Its LEVEL is the
+ *   lowest level with a separator it matches, if it is legal and there is one.  Only legal boundaries are chosen, so no chunk starts or
+ *   ends inside a char.
+ *  The chain of a document.  The first chunk starts at s = 0; an empty document owns no chunk.  If n_d - s <= N the chunk is [s, n_d), its
+ *   cut is TK_SPLIT_END and the chain ends.  Otherwise look at the legal boundaries e in [s + M, s + N] (all interior): take the lowest
+ *   level that occurs among them and of that level the largest e, cut = that level; if none of them has a level the largest legal e,
+ *   cut = TK_SPLIT_HARD; if none is legal e = s + N, cut = TK_SPLIT_FORCED (with N - M >= 3 only on ill-formed text: a char is at most
+ *   four tokens).  The chunk is [s, e).  The next chunk starts at the smallest legal boundary in [e - O, e], at e if there is none;
+ *   O < M makes every start larger than the one before.
+ *  Output.  Per chunk, in document order (C of them): doc; tok_begin, tok_end: token indices inside the document; byte_begin, byte_end and
+ *   char_begin, char_end: the same places in the document's text, bytes and chars (byte_start / char_start of the span rule, the
+ *   document's length at its end; chars are exact at legal boundaries); cut (uint8).  doc_chunk uint32[n_docs + 1]: the first chunk of
+ *   every document, C at the end.
+ *  What the chunks promise.  tok_end - tok_begin <= N counts the document's OWN tokenisation: a chunk's text encoded on its own may
+ *   tokenise differently at its two edges, so its count may differ by a few.  With O == 0 the byte ranges of a document's chunks tile it
+ *   exactly.  The result depends on nothing but the rule: not on K, which only sets how the work is spread (0: the library's choice).
+ *  TK_VALUE_ERROR: M == 0, M + 3 > N, O >= M; a separator part longer than 16 bytes or a separator with both parts empty; more than 4
+ *   levels or more than 4 separators in a level; K neither 0 nor a multiple of 64; an unknown flag; T >= 2^32 or n_docs >= 2^32 - 1; a
+ *   tok_off that does not ascend from 0 to n_tokens (checked on the device before anything is indexed with it; the message names the first
+ *   offending document).  What tk_token_spans_device refuses is refused in its words: TK_UNSUPPORTED for ids too sparse for a direct table
+ *   and for text a generic pat_str leaves unmatched, TK_VALUE_ERROR for a document of 4 GiB, TK_KEY_ERROR for an id without an entry.
+ *   A refused call leaves the previous result whole.  One device per call: a group has no split entry.
+ *  NOT built: a bound on the count of a chunk encoded on its own; separators longer than 16 bytes; regex separators; an overlap that
+ *   snaps to separators (it snaps to chars only); several GPUs. */
+#define TK_SPLIT_HARD 0xFDu   /* cut: no separator in the window, the last legal boundary */
+#define TK_SPLIT_FORCED 0xFEu /* cut: no legal boundary in the window either (ill-formed text) */
+#define TK_SPLIT_END 0xFFu    /* cut: the document's end */
+typedef struct {
+    uint8_t tail_len, head_len;
+    uint8_t tail[16], head[16];
+} tk_split_sep;
+typedef struct {
+    uint32_t max_tokens, min_tokens, overlap, n_levels, seg_tokens, flags; /* flags: none defined, must be 0 */
+    uint32_t n_seps[4];                                                   /* separators of every level */
+    tk_split_sep sep[4][4];
+} tk_split_spec;
+/* Device pointers in (ids uint32, d_tok_off and d_doc_off uint64[n_docs + 1], d_utf8 the text: e.g. the arguments and results of
+ * tk_encode_batch_device), device pointers out: buffers of the core, valid until its next split call that succeeds (a refused call writes
+ * into none of them) and apart from all others, except that the span buffers are used on the way (a split call ends the validity of
+ * tk_token_spans_device's results).  *d_doc_out .. *d_char_end_out (uint32) and *d_cut_out (uint8): *n_chunks_out each; *d_doc_chunk_out:
+ * n_docs + 1.  `stream`: a hipStream_t or null (the core's); the call returns when the chunks are there. */
+int tk_split_device(tk_core* core, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_docs, const void* d_utf8,
+                    const void* d_doc_off, const tk_split_spec* spec, void* stream, const uint32_t** d_doc_out, const uint32_t** d_tok_begin_out,
+                    const uint32_t** d_tok_end_out, const uint32_t** d_byte_begin_out, const uint32_t** d_byte_end_out,
+                    const uint32_t** d_char_begin_out, const uint32_t** d_char_end_out, const uint8_t** d_cut_out,
+                    const uint32_t** d_doc_chunk_out, uint64_t* n_chunks_out);
+/* tk_encode_batch -- with n_disallowed != 0: tk_encode_batch_checked -- with the text cut into chunks while ids and text are on the
+ * device: host text in; the chunk arrays and the ids come out.  *doc_out .. *doc_chunk_out and *tokens_out: library-owned (tk_free), sized
+ * as above; tok_off_out (may be null): the caller's array of n_docs + 1.  On TK_DISALLOWED_SPECIAL nothing is handed out. */
+int tk_encode_batch_split(tk_core* core, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special,
+                          const uint32_t* allowed_ids, uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed,
+                          const tk_split_spec* spec, uint32_t** doc_out, uint32_t** tok_begin_out, uint32_t** tok_end_out,
+                          uint32_t** byte_begin_out, uint32_t** byte_end_out, uint32_t** char_begin_out, uint32_t** char_end_out,
+                          uint8_t** cut_out, uint32_t** doc_chunk_out, uint64_t* n_chunks_out, uint32_t** tokens_out, uint64_t* n_tokens_out,
+                          uint64_t* tok_off_out, tk_special_hit* hit);
 /* Supervised samples: a packed batch whose documents are the PARTS of samples -- the messages of a conversation, a prompt and its answer --
  * -> one row per sample with the template's ids around every part, an attention mask and labels.  Replaces nothing in the reference: it is
  * the host loop of the reference's users, the fine-tuning script that calls encode_ordinary once per message, adds header and footer ids and
@@ -705,7 +771,9 @@ void tk_last_stats(tk_core* core, uint64_t* n_bytes, uint64_t* n_pieces, uint64_
  * the distinct words' bytes were copied into a larger blob; both 0 for a corpus of one chunk); and of the core itself, by its vocabulary's ids:
  * "pair_table_packed" (1: every rank fits the packed pair table; 0: 16-byte slots and a merge kernel per length bin), "short_table" (0: an id
  * above 0x3FFFFFFE, tokens of 1 .. 4 bytes live in the mid table), "decode_table_ids" (entries of the device decode table; 0: an id of 2^26
- * or above, the decode entries answer TK_UNSUPPORTED). */
+ * or above, the decode entries answer TK_UNSUPPORTED); and of the last split call (tk_split_device, tk_encode_batch_split): "split_segments"
+ * (document parts per block of K positions), "split_joined" (blocks in which the true chain met the speculative walk), "split_stitch_steps"
+ * (steps of the stitch pass) and "split_spec_steps" (steps of the speculative walks). */
 uint64_t tk_stat(tk_core* core, const char* name);
 
 #ifdef __cplusplus

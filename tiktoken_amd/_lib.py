@@ -42,6 +42,20 @@ class PadSpec(ctypes.Structure):
 PAD_WINDOWS, PAD_KEEP_TAIL, PAD_LEFT, PAD_IDS16 = 1, 2, 4, 8
 
 
+class SplitSep(ctypes.Structure):
+    """tk_split_sep: a separator, the bytes before a token boundary and the bytes from it on (include/tiktoken_amd.h)."""
+    _fields_ = [("tail_len", ctypes.c_uint8), ("head_len", ctypes.c_uint8), ("tail", ctypes.c_uint8 * 16), ("head", ctypes.c_uint8 * 16)]
+
+
+class SplitSpec(ctypes.Structure):
+    """tk_split_spec: how the documents of a batch are cut into chunks (include/tiktoken_amd.h)."""
+    _fields_ = [("max_tokens", ctypes.c_uint32), ("min_tokens", ctypes.c_uint32), ("overlap", ctypes.c_uint32), ("n_levels", ctypes.c_uint32),
+                ("seg_tokens", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("n_seps", ctypes.c_uint32 * 4), ("sep", SplitSep * 4 * 4)]
+
+
+SPLIT_HARD, SPLIT_FORCED, SPLIT_END = 0xFD, 0xFE, 0xFF
+
+
 class SmpSpec(ctypes.Structure):
     """tk_smp_spec: how the parts of a packed batch become supervised samples (include/tiktoken_amd.h)."""
     _fields_ = [("max_len", ctypes.c_uint32), ("width_multiple", ctypes.c_uint32), ("bos_id", ctypes.c_uint32), ("eos_id", ctypes.c_uint32), ("pad_id", ctypes.c_uint32),
@@ -132,6 +146,11 @@ def lib() -> ctypes.CDLL:
         L.tk_pad_batch_device.argtypes = [vp, vp, u64, vp, u64, P(PadSpec), vp, P(vp), P(vp), P(vp), P(vp), P(vp), P(vp), P(u64), P(u64)]
         L.tk_encode_batch_padded.restype = i32
         L.tk_encode_batch_padded.argtypes = [vp, vp, vp, u64, i32, vp, u64, vp, u64, P(PadSpec), P(vp), P(vp), P(vp), P(vp), P(vp), P(vp), P(u64), P(u64), P(SpecialHit)]
+        if hasattr(L, "tk_split_device"):  # (absent from older builds selected through $TIKTOKEN_AMD_LIB)
+            L.tk_split_device.restype = i32
+            L.tk_split_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, P(SplitSpec), vp, *[P(vp)] * 9, P(u64)]
+            L.tk_encode_batch_split.restype = i32
+            L.tk_encode_batch_split.argtypes = [vp, vp, vp, u64, i32, vp, u64, vp, u64, P(SplitSpec), *[P(vp)] * 9, P(u64), P(vp), P(u64), vp, P(SpecialHit)]
         L.tk_assemble_samples_device.restype = i32
         L.tk_assemble_samples_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, u32, vp, vp, vp, P(SmpSpec), vp, P(vp), P(vp), P(vp), P(vp), P(vp), P(vp), P(u64), P(u64)]
         L.tk_encode_batch_samples.restype = i32

@@ -6,7 +6,8 @@ Same constructor and the same eleven methods, same exception types.  Two additiv
 (one launch sequence per batch instead of one FFI call per document); `decode_batch_spans_packed`, `token_spans_device` and
 `encode_batch_spans_packed` give, for whole batches, where every token starts in its document (bytes and chars); `pack_rows_device` and
 `encode_batch_rows_packed` cut a batch into fixed-length training rows with document ids, positions and cu_seqlens; `pad_batch_device` and
-`encode_batch_padded_packed` give one padded row per document (or overlapping windows) with an attention mask; `assemble_samples_device` and
+`encode_batch_padded_packed` give one padded row per document (or overlapping windows) with an attention mask; `split_device` and
+`encode_batch_split_packed` cut every document into chunks of at most so many tokens, at separators and never inside a char; `assemble_samples_device` and
 `encode_batch_samples_packed` join the parts of supervised samples with their roles' ids into rows with labels; `decode_rows_device` and
 `decode_rows_packed` decode the rows of an id matrix, each cut at its first stop id and stripped of skipped and special ids; `train_bpe_packed`
 trains a vocabulary: the merges of the reference's educational `bpe_train`, made on the device.  With `disallowed_special` the batch
@@ -198,6 +199,54 @@ class PaddedDevice(NamedTuple):
     doc_row: int
     n_rows: int
     width: int
+
+
+class TextChunks:
+    """A batch cut into chunks (tk_encode_batch_split; the rule: include/tiktoken_amd.h): per chunk, in document order, `doc`, `tok_begin` /
+    `tok_end` (token indices inside the document), `byte_begin` / `byte_end` and `char_begin` / `char_end` (the same places in the
+    document's text) and `cut` (the separator level the chunk ends at, or SPLIT_HARD, SPLIT_FORCED, SPLIT_END); `doc_chunk[d]` is the
+    first chunk of document d, `doc_chunk[-1]` the number of chunks; `tokens` and `tok_off` are the batch's ids.  `text(i)` and `ids(i)`
+    give chunk i's text and ids."""
+    SPLIT_HARD, SPLIT_FORCED, SPLIT_END = _lib.SPLIT_HARD, _lib.SPLIT_FORCED, _lib.SPLIT_END
+    FIELDS = ("doc", "tok_begin", "tok_end", "byte_begin", "byte_end", "char_begin", "char_end", "cut", "doc_chunk")
+
+    def __init__(self, arrays, tokens: np.ndarray, tok_off: np.ndarray, blob: np.ndarray, doc_off: np.ndarray):
+        for name, a in zip(self.FIELDS, arrays):
+            setattr(self, name, a)
+        self.tokens, self.tok_off = tokens, tok_off
+        self._blob, self._doc_off = blob, doc_off
+
+    def __len__(self) -> int:
+        return len(self.doc)
+
+    def text_bytes(self, i: int) -> bytes:
+        a = int(self._doc_off[int(self.doc[i])])
+        return self._blob[a + int(self.byte_begin[i]):a + int(self.byte_end[i])].tobytes()
+
+    def text(self, i: int, errors: str = "replace") -> str:
+        return self.text_bytes(i).decode("utf-8", errors)
+
+    def ids(self, i: int) -> np.ndarray:
+        a = int(self.tok_off[int(self.doc[i])])
+        return self.tokens[a + int(self.tok_begin[i]):a + int(self.tok_end[i])]
+
+
+class SplitDevice(NamedTuple):
+    """`split_device`: device pointers (the core's buffers, valid until its next split call that succeeds) to the arrays of `TextChunks`
+    -- uint32[n_chunks] each, `cut` uint8[n_chunks], `doc_chunk` uint32[n_docs + 1] -- and the number of chunks."""
+    doc: int
+    tok_begin: int
+    tok_end: int
+    byte_begin: int
+    byte_end: int
+    char_begin: int
+    char_end: int
+    cut: int
+    doc_chunk: int
+    n_chunks: int
+
+
+DEFAULT_SEPARATORS = ((("\n\n", ""),), (("\n", ""),), ((".", " "), ("?", " "), ("!", " ")), (("", " "),))
 
 
 class Role(NamedTuple):
@@ -1357,6 +1406,66 @@ class CoreBPE:
         lengths, row_doc, row_tok, doc_row = _take_u32(out[2], n_rows), _take_u32(out[3], n_rows), _take_u32(out[4], n_rows), _take_u32(out[5], n_docs + 1)
         self._pad_id_needed(has_pad, n_rows, width, lengths)
         return PaddedBatch(input_ids, mask, lengths, row_doc, row_tok, doc_row)
+
+    # ------------------------------------------------------------------ text chunks (no reference counterpart: the host loop of its users)
+    @staticmethod
+    def _split_spec(max_tokens: int, min_tokens, overlap: int, separators, seg_tokens: int) -> "_lib.SplitSpec":
+        """The tk_split_spec.  min_tokens None: max(overlap + 1, max_tokens // 2).  separators: levels, best first, of (tail, head) pairs
+        of str or bytes; a bare str / bytes x means (x, "").  What does not fit the structure is refused here, in the library's words;
+        the library refuses the rest."""
+        if min_tokens is None:
+            min_tokens = max(int(overlap) + 1, int(max_tokens) // 2)
+        for name, v in (("max_tokens", max_tokens), ("min_tokens", min_tokens), ("overlap", overlap), ("seg_tokens", seg_tokens)):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise ValueError(f"{name} must fit 32 bits")
+        levels = [list(lv) for lv in separators]
+        if len(levels) > 4:
+            raise ValueError("n_levels: at most 4 levels of separators")
+        spec = _lib.SplitSpec(int(max_tokens), int(min_tokens), int(overlap), len(levels), int(seg_tokens), 0)
+        for l, seps in enumerate(levels):
+            if len(seps) > 4:
+                raise ValueError("n_seps: at most 4 separators in a level")
+            spec.n_seps[l] = len(seps)
+            for k, sp in enumerate(seps):
+                tail, head = (sp, b"") if isinstance(sp, (str, bytes)) else sp
+                tail, head = (x.encode("utf-8") if isinstance(x, str) else bytes(x) for x in (tail, head))
+                if len(tail) > 16 or len(head) > 16:
+                    raise ValueError("separators: a part (tail, head) is at most 16 bytes")
+                o = spec.sep[l][k]
+                o.tail_len, o.head_len = len(tail), len(head)
+                o.tail[:len(tail)] = tail
+                o.head[:len(head)] = head
+        return spec
+
+    def split_device(self, d_tokens: int, n_tokens: int, d_tok_off: int, n_docs: int, d_utf8: int, d_doc_off: int, *, max_tokens: int, min_tokens: int | None = None,
+                     overlap: int = 0, separators=DEFAULT_SEPARATORS, seg_tokens: int = 0, stream: int = 0) -> SplitDevice:
+        """Device-resident text chunks (tk_split_device): pointers to uint32 ids, uint64[n_docs + 1] token offsets, the text they were encoded
+        from and its uint64[n_docs + 1] byte offsets on this core's device -- e.g. the arguments and results of `encode_batch_device`, which
+        stay intact; every document is cut into chunks of at most `max_tokens` tokens at the best separator in the window
+        [`min_tokens`, `max_tokens`], consecutive chunks sharing up to `overlap` tokens; see `TextChunks` for the arrays."""
+        self._one_device("split_device")
+        spec = self._split_spec(max_tokens, min_tokens, overlap, separators, seg_tokens)
+        out, cnt, refs = self._outs(9, 1)
+        rc = self._L.tk_split_device(self._h, d_tokens or None, n_tokens, d_tok_off or None, n_docs, d_utf8 or None, d_doc_off or None, ctypes.byref(spec), stream or None, *refs)
+        _lib.raise_for(rc)
+        return SplitDevice(*[x.value or 0 for x in out], int(cnt[0].value))
+
+    def encode_batch_split_packed(self, blob: np.ndarray, doc_off: np.ndarray, allowed_special: AbstractSet[str] | None = None, *, disallowed_special=None,
+                                  max_tokens: int, min_tokens: int | None = None, overlap: int = 0, separators=DEFAULT_SEPARATORS, seg_tokens: int = 0) -> TextChunks:
+        """`encode_batch_packed` with the text cut into chunks while ids and text are on the device (tk_encode_batch_split).  The
+        special-token arguments as in `encode_batch_packed`, the others as in `split_device`."""
+        self._one_device("encode_batch_split_packed")
+        text, dis, n_docs, keep = self._batch_args(blob, doc_off, allowed_special, disallowed_special)
+        spec = self._split_spec(max_tokens, min_tokens, overlap, separators, seg_tokens)
+        hit = _lib.SpecialHit()
+        out, cnt, _ = self._outs(10, 2)
+        tok_off = np.empty(n_docs + 1, dtype=np.uint64)
+        refs = [ctypes.byref(x) for x in (*out[:9], cnt[0], out[9], cnt[1])]
+        rc = self._L.tk_encode_batch_split(self._h, *text, *dis, ctypes.byref(spec), *refs, tok_off.ctypes.data, ctypes.byref(hit))
+        self._raise_for(rc, hit)
+        C, n = int(cnt[0].value), int(cnt[1].value)
+        arrays = [_take_u32(x, C) for x in out[:7]] + [self._own_mask(out[7], C), _take_u32(out[8], n_docs + 1)]
+        return TextChunks(arrays, _take_u32(out[9], n), tok_off, keep[0], keep[1])
 
     # ------------------------------------------------------------------ supervised samples (no reference counterpart: the host loop of its users)
     @staticmethod

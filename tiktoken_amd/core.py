@@ -264,6 +264,58 @@ class Encoding:
             raise RuntimeError(f"internal error: the device reported the disallowed special token {e.token!r} in document {e.doc} at byte "
                                f"{e.pos}, the host search finds none there") from e
 
+    def split_ordinary_batch_packed(self, text: Sequence[str], max_tokens: int, *, min_tokens: int | None = None, overlap: int = 0,
+                                    separators=_tiktoken.DEFAULT_SEPARATORS, seg_tokens: int = 0) -> "_tiktoken.TextChunks":
+        """A batch cut into chunks of at most `max_tokens` tokens, ignoring special tokens: every text is encoded and cut, each cut at the
+        best separator among the token boundaries in [`min_tokens`, `max_tokens`] from the chunk's start -- `separators` lists levels,
+        best first, of (tail, head) pairs: the text before the cut ends with tail, the text behind it starts with head (a bare str x means
+        (x, "")) --, never inside a char; consecutive chunks share up to `overlap` tokens.  In one GPU call.  Returns a `TextChunks`.  The
+        budget counts the text's own tokens: a chunk encoded on its own may differ by a few at its edges.  `min_tokens` defaults to
+        max(overlap + 1, max_tokens // 2)."""
+        blob, off = self._pack(text)
+        return self._core_bpe.encode_batch_split_packed(blob, off, None, max_tokens=max_tokens, min_tokens=min_tokens, overlap=overlap, separators=separators,
+                                                        seg_tokens=seg_tokens)
+
+    def _split_packed(self, text: Sequence[str], max_tokens: int, *, min_tokens: int | None = None, overlap: int = 0, separators=_tiktoken.DEFAULT_SEPARATORS,
+                      allowed_special: Literal["all"] | AbstractSet[str] = set(),  # noqa: B006
+                      disallowed_special: Literal["all"] | Collection[str] = "all", seg_tokens: int = 0):
+        """(the TextChunks of `split_batch_packed`, whether a text with surrogates was repaired before it was encoded)"""
+        rows = dict(max_tokens=max_tokens, min_tokens=min_tokens, overlap=overlap, separators=separators, seg_tokens=seg_tokens)
+        allowed_special, disallowed_special = self._special_policy(allowed_special, disallowed_special)
+        blob, off, repaired = self._pack_repaired(text)
+        if not disallowed_special:
+            return self._core_bpe.encode_batch_split_packed(blob, off, allowed_special, **rows), repaired
+        if not isinstance(disallowed_special, frozenset):
+            disallowed_special = frozenset(disallowed_special)
+        if repaired or not all(t in self._special_tokens for t in disallowed_special):  # (as encode_batch_packed: the host's search)
+            for t in text:
+                self._reject_disallowed(t, disallowed_special)
+            return self._core_bpe.encode_batch_split_packed(blob, off, allowed_special, **rows), repaired
+        try:
+            return self._core_bpe.encode_batch_split_packed(blob, off, allowed_special, disallowed_special=disallowed_special, **rows), repaired
+        except _tiktoken.DisallowedSpecialError as e:
+            self._reject_disallowed(text[e.doc], disallowed_special)
+            raise RuntimeError(f"internal error: the device reported the disallowed special token {e.token!r} in document {e.doc} at byte "
+                               f"{e.pos}, the host search finds none there") from e
+
+    def split_batch_packed(self, text: Sequence[str], max_tokens: int, *, min_tokens: int | None = None, overlap: int = 0, separators=_tiktoken.DEFAULT_SEPARATORS,
+                           allowed_special: Literal["all"] | AbstractSet[str] = set(),  # noqa: B006
+                           disallowed_special: Literal["all"] | Collection[str] = "all", seg_tokens: int = 0) -> "_tiktoken.TextChunks":
+        """`split_ordinary_batch_packed` with the special-token arguments of `encode` -- the policy, and the error, of `encode_batch_packed`."""
+        return self._split_packed(text, max_tokens, min_tokens=min_tokens, overlap=overlap, separators=separators, allowed_special=allowed_special,
+                                  disallowed_special=disallowed_special, seg_tokens=seg_tokens)[0]
+
+    def split_batch(self, text: Sequence[str], max_tokens: int, **kwargs) -> "list[list[str]]":
+        """The chunks of every text as strings (`split_batch_packed`, each str sliced by the chunks' char offsets)."""
+        if not isinstance(text, (list, tuple)):
+            text = list(text)
+        ch, repaired = self._split_packed(text, max_tokens, **kwargs)
+        first, a, b = ch.doc_chunk.tolist(), ch.char_begin.tolist(), ch.char_end.tolist()
+        if not repaired:
+            return [[t[a[i]:b[i]] for i in range(first[d], first[d + 1])] for d, t in enumerate(text)]
+        # (a text with surrogates was repaired before it was encoded: the offsets speak of the repaired text, which the chunks hold)
+        return [[ch.text(i) for i in range(first[d], first[d + 1])] for d in range(len(text))]
+
     def encode_ordinary_batch_padded(self, text: Sequence[str], max_length: int, *, stride: int = 0, windows: bool = False, keep: str = "head",
                                      padding_side: str = "right", pad_to_multiple_of: int | None = None, bos: int | None = None, eos: int | None = None,
                                      pad: int | None = None, dtype=np.uint32) -> "_tiktoken.PaddedBatch":

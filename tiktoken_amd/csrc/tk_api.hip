@@ -29,6 +29,7 @@
 #include "tk_stop_text.h"
 #include "tk_stream.h"
 #include "tk_padded.h"
+#include "tk_split.h"
 #include "tk_sample_rows.h"
 #include "tk_samples.h"
 #include "tk_rows.h"
@@ -283,6 +284,11 @@ struct tk_core {
     // Padded inputs (tk_padded.h), apart from everything above: d_pad: ids and mask of every position; d_pad_row: len, row_doc, row_tok of
     // every row; d_pad_doc: doc_row; d_pad_cnt: the TK_PAD_WORDS report words and the doc_row a call counts in until it is accepted.
     Buf d_pad, d_pad_row, d_pad_doc, d_pad_cnt;
+    // Text chunks (tk_split.h), apart from everything above: d_split: the arrays of every chunk and doc_chunk; d_split_work: the report words,
+    // the class planes, the cut and spec planes, exit_at / join_at of every block and the starts per count block -- everything a call computes
+    // until it is accepted.  st_split: the counters of the last call (TK_SPLIT_ST_*).
+    Buf d_split, d_split_work;
+    uint64_t st_split[TK_SPLIT_STATS] = {0, 0, 0, 0};
     // Supervised samples (tk_samples.h), apart from everything above: d_smp: ids, labels and mask of every position; d_smp_row: full_len, len,
     // n_trained of every sample; d_smp_cnt: the TK_SMP_WORDS report words, the role table, pstart and the per-sample figures a call counts in
     // until it is accepted; d_smp_in: part_role and sample_off of a host-text call.
@@ -2993,6 +2999,169 @@ extern "C" int tk_encode_batch_padded(tk_core* c, const uint8_t* utf8, const uin
 }
 
 // ------------------------------------------------------------------------------------------
+// Text chunks (tk_split.h): a packed batch and its text on the device -> every document cut at separators under a token budget.
+// ------------------------------------------------------------------------------------------
+static_assert(TK_SPLIT_HARD == TK_SPLITC_HARD && TK_SPLIT_FORCED == TK_SPLITC_FORCED && TK_SPLIT_END == TK_SPLITC_END, "tk_split cut values");
+static_assert(sizeof(tk_split_sep) == sizeof(TkSplitSep) && sizeof(tk_split_sep) == 34, "tk_split_sep layout");
+struct SplitView {  // device buffers of the core, valid until its next split call that succeeds
+    TkSplitOut out = {};
+    uint32_t* doc_chunk = nullptr;
+    uint64_t n_chunks = 0;
+};
+static int split_refusal(int why) {
+    switch (why) {
+        case 0: return TK_OK;
+        case 1: return fail(TK_VALUE_ERROR, "min_tokens must be at least 1");
+        case 2: return fail(TK_VALUE_ERROR, "max_tokens must be at least min_tokens + 3 (a char is at most four tokens of one byte)");
+        case 3: return fail(TK_VALUE_ERROR, "overlap must be less than min_tokens");
+        case 4: return fail(TK_VALUE_ERROR, "n_levels: at most 4 levels of separators");
+        case 5: return fail(TK_VALUE_ERROR, "n_seps: at most 4 separators in a level");
+        case 6: return fail(TK_VALUE_ERROR, "separators: a part (tail, head) is at most 16 bytes");
+        case 7: return fail(TK_VALUE_ERROR, "separators: tail and head of a separator are both empty");
+        case 8: return fail(TK_VALUE_ERROR, "seg_tokens must be 0 or a multiple of 64");
+        case 9: return fail(TK_VALUE_ERROR, "n_tokens: 2^32 tokens or more: the token indices of the chunks are 32-bit");
+        case 10: return fail(TK_VALUE_ERROR, "n_docs: too many documents: the document indices of the chunks are 32-bit");
+        default: return fail(TK_VALUE_ERROR, "tk_split_spec: unknown flag");
+    }
+}
+static int split_shape(const tk_split_spec* spec, uint64_t n, uint64_t n_docs, TkSplit* p) {
+    return split_refusal(tk_split_shape(n, n_docs, spec->max_tokens, spec->min_tokens, spec->overlap, spec->n_levels, spec->n_seps, spec->sep, spec->seg_tokens, spec->flags, p));
+}
+// What of a tk_split_spec can be refused without looking at the batch (the host-text entry asks before it encodes anything).
+static int split_check_spec(const tk_split_spec* spec) {
+    if (!spec) return fail(TK_VALUE_ERROR, "null argument");
+    TkSplit p;
+    return split_shape(spec, 0, 0, &p);
+}
+// split_run: the caller holds c->mu.  The host waits for what tk_k_split_check has to say about tok_off (nothing is indexed with it before),
+// inside the span passes, and once in the split passes proper: for C, before the outputs are sized.  A call that is refused has written
+// into d_split_work (and the span buffers) only: the previous result stays whole.
+static int split_run(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n, const uint64_t* d_tok_off, uint64_t n_docs, const uint8_t* d_utf8,
+                     const uint64_t* d_doc_off, const tk_split_spec* spec, SplitView* out) {
+    TkSplit p;
+    TRY(split_shape(spec, n, n_docs, &p));  // (spec is not null: device_pass's arguments, split_check_spec before the encode)
+    const uint64_t n_blocks = (n + p.K - 1) / p.K, nb = (p.W + TK_SPLIT_CB_WORDS - 1) / TK_SPLIT_CB_WORDS;
+    Carve work;
+    const uint64_t at_words = work.add(TK_SPLIT_WORDS * 8), at_planes = work.add((p.L + 1) * p.W * 8), at_cut = work.add(p.W * 8), at_spec = work.add(p.W * 8);
+    const uint64_t at_exit = work.add((n_blocks + 1) * 4), at_join = work.add((n_blocks + 1) * 4), at_cnt = work.add((nb + 1) * 4);
+    TRY(ensure(c->d_split_work, work.total));
+    unsigned long long* words = carved<unsigned long long>(c->d_split_work, at_words);
+    unsigned long long *planes = carved<unsigned long long>(c->d_split_work, at_planes), *cut = carved<unsigned long long>(c->d_split_work, at_cut);
+    unsigned long long* spec_plane = carved<unsigned long long>(c->d_split_work, at_spec);
+    uint32_t *exit_at = carved<uint32_t>(c->d_split_work, at_exit), *join_at = carved<uint32_t>(c->d_split_work, at_join), *cnt = carved<uint32_t>(c->d_split_work, at_cnt);
+    HIPCHK(hipMemsetAsync(words, 0, TK_SPLIT_WORDS * 8, s));
+    TRY(report_arm(words, s));
+    TRY(timed(c, s, "tk_k_split_check", [&] { hipLaunchKernelGGL(tk_k_split_check, dim3(grid_for(n_docs + 1, 256, 4096)), dim3(256), 0, s, d_tok_off, n_docs, n, words); }));
+    unsigned long long got[TK_SPLIT_WORDS];
+    TRY(report_read(words, got, TK_SPLIT_WORDS, s));
+    SpanView v;
+    TRY(spans_run(c, s, d_tok, n, d_tok_off, n_docs, d_doc_off, false, false, &v));
+    // (cut and spec lie one behind the other, exit_at and join_at too: one memset each)
+    HIPCHK(hipMemsetAsync(cut, 0, (at_exit - at_cut), s));
+    HIPCHK(hipMemsetAsync(exit_at, 0xFF, (at_cnt - at_exit), s));
+    TRY(timed(c, s, "tk_k_split_class", [&] {
+        hipLaunchKernelGGL(tk_k_split_class, dim3((uint32_t)((p.W * 64 + 255) / 256)), dim3(256), 0, s, p, d_utf8, d_doc_off, d_tok_off, v.byte_start, planes);
+    }));
+    if (n_blocks)
+        TRY(timed(c, s, "tk_k_split_walk", [&] {
+            hipLaunchKernelGGL(tk_k_split_walk, dim3((uint32_t)((n_blocks + 3) / 4)), dim3(256), 0, s, p, planes, d_tok_off, n_blocks, cut, spec_plane, exit_at, words);
+        }));
+    if (n_blocks > 1)
+        TRY(timed(c, s, "tk_k_split_stitch", [&] {
+            hipLaunchKernelGGL(tk_k_split_stitch, dim3(grid_for(n_docs, 4, 65536)), dim3(256), 0, s, p, planes, d_tok_off, cut, spec_plane, exit_at, join_at, words);
+        }));
+    TRY(timed(c, s, "tk_k_split_count", [&] {
+        hipLaunchKernelGGL(tk_k_split_count, dim3((uint32_t)((p.W + 255) / 256)), dim3(256), 0, s, p, cut, spec_plane, join_at, cnt);
+    }));
+    TRY(timed(c, s, "tk_k_split_scan", [&] { hipLaunchKernelGGL(tk_k_split_scan, dim3(1), dim3(1024), 0, s, cnt, nb, words); }));
+    TRY(report_read(words, got, TK_SPLIT_WORDS, s));
+    const uint64_t C = got[TK_SPLIT_NCHUNKS];  // (below 2^32: a chunk owns a token)
+    for (int i = 0; i < TK_SPLIT_STATS; ++i) c->st_split[i] = got[TK_SPLIT_STAT0 + i];
+    Carve res;
+    uint64_t at[7];
+    for (uint64_t& a : at) a = res.add(C * 4);
+    const uint64_t at_cutv = res.add(C), at_dc = res.add((n_docs + 1) * 4);
+    TRY(ensure(c->d_split, res.total + 16));
+    out->out = TkSplitOut{carved<uint32_t>(c->d_split, at[0]), carved<uint32_t>(c->d_split, at[1]), carved<uint32_t>(c->d_split, at[2]), carved<uint32_t>(c->d_split, at[3]),
+                          carved<uint32_t>(c->d_split, at[4]), carved<uint32_t>(c->d_split, at[5]), carved<uint32_t>(c->d_split, at[6]), carved<uint8_t>(c->d_split, at_cutv)};
+    out->doc_chunk = carved<uint32_t>(c->d_split, at_dc);
+    out->n_chunks = C;
+    if (C)
+        TRY(timed(c, s, "tk_k_split_write", [&] {
+            hipLaunchKernelGGL(tk_k_split_write, dim3((uint32_t)((p.W + 255) / 256)), dim3(256), 0, s, p, planes, cut, cnt, d_tok_off, v.byte_start, v.char_start, v.byte_off,
+                               v.char_off, out->out);
+        }));
+    TRY(timed(c, s, "tk_k_split_docs", [&] {
+        hipLaunchKernelGGL(tk_k_split_docs, dim3(grid_for(n_docs + 1, 256, 4096)), dim3(256), 0, s, p, cut, cnt, d_tok_off, out->doc_chunk);
+    }));
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    return TK_OK;
+}
+static void split_give(const SplitView& v, const uint32_t** doc, const uint32_t** tok_begin, const uint32_t** tok_end, const uint32_t** byte_begin, const uint32_t** byte_end,
+                       const uint32_t** char_begin, const uint32_t** char_end, const uint8_t** cut, const uint32_t** doc_chunk, uint64_t* n_chunks) {
+    if (doc) *doc = v.out.doc;
+    if (tok_begin) *tok_begin = v.out.tok_begin;
+    if (tok_end) *tok_end = v.out.tok_end;
+    if (byte_begin) *byte_begin = v.out.byte_begin;
+    if (byte_end) *byte_end = v.out.byte_end;
+    if (char_begin) *char_begin = v.out.char_begin;
+    if (char_end) *char_end = v.out.char_end;
+    if (cut) *cut = v.out.cut;
+    if (doc_chunk) *doc_chunk = v.doc_chunk;
+    if (n_chunks) *n_chunks = v.n_chunks;
+}
+
+extern "C" int tk_split_device(tk_core* c, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_docs, const void* d_utf8, const void* d_doc_off,
+                               const tk_split_spec* spec, void* stream, const uint32_t** d_doc_out, const uint32_t** d_tok_begin_out, const uint32_t** d_tok_end_out,
+                               const uint32_t** d_byte_begin_out, const uint32_t** d_byte_end_out, const uint32_t** d_char_begin_out, const uint32_t** d_char_end_out,
+                               const uint8_t** d_cut_out, const uint32_t** d_doc_chunk_out, uint64_t* n_chunks_out) {
+    SplitView v;
+    TRY(device_pass(c, d_tok_off && d_doc_off && (d_tokens || !n_tokens) && (d_utf8 || !n_tokens) && spec, stream, [&](hipStream_t s) {
+        return split_run(c, s, (const uint32_t*)d_tokens, n_tokens, (const uint64_t*)d_tok_off, n_docs, (const uint8_t*)d_utf8, (const uint64_t*)d_doc_off, spec, &v);
+    }));
+    split_give(v, d_doc_out, d_tok_begin_out, d_tok_end_out, d_byte_begin_out, d_byte_end_out, d_char_begin_out, d_char_end_out, d_cut_out, d_doc_chunk_out, n_chunks_out);
+    return TK_OK;
+}
+
+// tk_encode_batch (tk_encode_batch_checked with disallowed ids) with the chunks of the text it has just encoded: the passes run over the
+// ids and the text while both are on the device; the chunk arrays and the ids travel back.
+extern "C" int tk_encode_batch_split(tk_core* c, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special, const uint32_t* allowed_ids,
+                                     uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed, const tk_split_spec* spec, uint32_t** doc_out,
+                                     uint32_t** tok_begin_out, uint32_t** tok_end_out, uint32_t** byte_begin_out, uint32_t** byte_end_out, uint32_t** char_begin_out,
+                                     uint32_t** char_end_out, uint8_t** cut_out, uint32_t** doc_chunk_out, uint64_t* n_chunks_out, uint32_t** tokens_out,
+                                     uint64_t* n_tokens_out, uint64_t* tok_off_out, tk_special_hit* hit) {
+    SplitView v;
+    return encode_batch_pass(
+        c, utf8, doc_off, n_docs, use_special, allowed_ids, n_allowed, disallowed_ids, n_disallowed, hit,
+        spec && doc_out && tok_begin_out && tok_end_out && byte_begin_out && byte_end_out && char_begin_out && char_end_out && cut_out && doc_chunk_out && n_chunks_out &&
+            tokens_out && n_tokens_out,
+        [&] { return split_check_spec(spec); },  // (before the encode, not after it)
+        [&](uint64_t n) {
+            return split_run(c, c->stream, c->out_tokens.as<uint32_t>(), n, c->out_tok_off.as<uint64_t>(), n_docs, c->text.as<uint8_t>(), c->doc_off.as<uint64_t>(), spec, &v);
+        },
+        [&](uint64_t n) -> int {
+            const uint64_t C = v.n_chunks;
+            ResultBag bag;
+            TRY(bag.fetch(doc_out, v.out.doc, C));
+            TRY(bag.fetch(tok_begin_out, v.out.tok_begin, C));
+            TRY(bag.fetch(tok_end_out, v.out.tok_end, C));
+            TRY(bag.fetch(byte_begin_out, v.out.byte_begin, C));
+            TRY(bag.fetch(byte_end_out, v.out.byte_end, C));
+            TRY(bag.fetch(char_begin_out, v.out.char_begin, C));
+            TRY(bag.fetch(char_end_out, v.out.char_end, C));
+            TRY(bag.fetch(cut_out, v.out.cut, C));
+            TRY(bag.fetch(doc_chunk_out, v.doc_chunk, n_docs + 1));
+            TRY(bag.fetch(tokens_out, c->out_tokens.p, n));
+            if (tok_off_out) HIPCHK(hipMemcpy(tok_off_out, c->out_tok_off.p, (n_docs + 1) * 8, hipMemcpyDeviceToHost));
+            bag.give();
+            *n_chunks_out = C;
+            *n_tokens_out = n;
+            return TK_OK;
+        });
+}
+
+// ------------------------------------------------------------------------------------------
 // Supervised samples (tk_samples.h): a packed batch of parts on the device -> one row per sample, ids, mask and labels as [R, W].
 // ------------------------------------------------------------------------------------------
 static_assert(TK_SMP_KEEP_TAIL == TK_SMPF_KEEP_TAIL && TK_SMP_LEFT == TK_SMPF_LEFT, "tk_smp_spec flags");
@@ -4855,6 +5024,10 @@ extern "C" uint64_t tk_stat(tk_core* c, const char* name) {
     if (k == "spec_mark_launches") return c->st_mark_launches;  // launches of the pair that marks allowed special tokens (tk_k_spec_cand + tk_k_spec_resolve): one per chunk that has them
     if (k == "train_table_moves") return c->st_train_table_moves;  // of the last tk_train_bpe: launches of tk_k_train_rehash (train_tab_reserve)
     if (k == "train_blob_moves") return c->st_train_blob_moves;    // ... and copies of the words' bytes into a larger blob (train_blob_reserve)
+    if (k == "split_segments") return c->st_split[TK_SPLIT_ST_SEGS];          // of the last split call: document parts per block of K positions the walk pass walked
+    if (k == "split_joined") return c->st_split[TK_SPLIT_ST_JOINED];          // ... blocks in which the true chain met the speculative walk
+    if (k == "split_stitch_steps") return c->st_split[TK_SPLIT_ST_STITCH];    // ... steps of the stitch pass (one wavefront per document, in order)
+    if (k == "split_spec_steps") return c->st_split[TK_SPLIT_ST_SPEC];        // ... steps of the speculative walks
     if (k == "regrown") return c->st_regrown;  // batches repeated with a larger miss data since the core was made (encode_device_locked)
     if (k == "workspace_bytes") {             // device memory of the work sets (everything but the text, the tables and the outputs)
         uint64_t t = 0;
