@@ -23,7 +23,8 @@
 extern "C" {
 #endif
 
-enum { TK_OK = 0, TK_VALUE_ERROR = 1, TK_KEY_ERROR = 2, TK_RUNTIME_ERROR = 3, TK_UNSUPPORTED = 4, TK_DISALLOWED_SPECIAL = 5 };
+enum { TK_OK = 0, TK_VALUE_ERROR = 1, TK_KEY_ERROR = 2, TK_RUNTIME_ERROR = 3, TK_UNSUPPORTED = 4, TK_DISALLOWED_SPECIAL = 5,
+       TK_JSONL_ERROR = 6 /* the JSON Lines entries under TK_JSONL_RAISE: a line that is neither a record nor blank (JsonlError, a ValueError) */ };
 
 typedef struct tk_core tk_core;
 
@@ -320,6 +321,63 @@ int tk_encode_batch_split(tk_core* core, const uint8_t* utf8, const uint64_t* do
                           uint32_t** byte_begin_out, uint32_t** byte_end_out, uint32_t** char_begin_out, uint32_t** char_end_out,
                           uint8_t** cut_out, uint32_t** doc_chunk_out, uint64_t* n_chunks_out, uint32_t** tokens_out, uint64_t* n_tokens_out,
                           uint64_t* tok_off_out, tk_special_hit* hit);
+/* JSON Lines: a buffer of lines {"text": "...", "meta": ...}\n -> the unescaped text of ONE field per line, packed as the encode entries
+ * take it (text, doc_off), with the status of every line.  Replaces nothing in the reference: it is the host loop of the reference's
+ * users, `for line in f: json.loads(line)["text"]`, in front of every batch encode -- here a pass over bytes that go to the device anyway.
+ * The rule (its plain C++: tiktoken_amd/csrc/tk_jsonl_rule.h; restated in tests/jsonl_ref.py).  The buffer is cut into lines at every raw
+ * 0x0A; a last line without a newline counts; a \r before the newline is trailing whitespace; a UTF-8 BOM at byte 0 is skipped.  JSON
+ * forbids a raw newline inside a string, so string state never crosses a line: lines are independent, which makes the pass parallel.
+ * Within a line: a byte is ESCAPED if an odd run of backslashes ends right before it; an unescaped " toggles the IN-STRING state; outside
+ * strings { [ raise the DEPTH and } ] lower it.  A KEY is a string that opens at depth 1 and whose closing quote is followed, after any of
+ * space \t \r, by ':'.  The FIELD (1 .. 64 bytes, no ", \ or byte < 0x20) matches a key whose raw bytes between the quotes equal it -- a
+ * key spelled with escapes does not match.  Of several matching keys the last wins, as with json.loads.  After the colon and whitespace,
+ * if the next byte is " the VALUE is the string that opens there; anything else gives TK_JSONL_NOT_STRING.  UNESCAPE: \" \\ \/ \b \f \n
+ * \r \t become one byte each; \uXXXX (hex in either case) the UTF-8 of the code point; a high surrogate escape directly followed by a low
+ * one becomes one 4-byte char; a surrogate escape without its partner becomes U+FFFD (what Encoding.encode makes of the str json.loads
+ * returns for it); other bytes are copied.  Every escape shrinks: the text never exceeds n_bytes.
+ * STATUS per line (uint8): TK_JSONL_OK; TK_JSONL_BLANK: only whitespace, never a record; TK_JSONL_MISSING: no matching key at depth 1;
+ * TK_JSONL_NOT_STRING; TK_JSONL_BAD: the first non-whitespace byte is not '{'; a string is open at the line's end; the depth is not 0 at
+ * the line's end or drops below 1 before the last structural byte; a raw byte < 0x20 inside any string; inside the SELECTED VALUE a
+ * backslash followed by anything outside the list above or \u without four hex digits; inside the selected value ill-formed UTF-8, by
+ * the strictness of tk_validate_utf8.  BAD takes precedence over the others.  THE PASS IS NOT A JSON VALIDATOR: numbers, literals, commas
+ * and escapes in strings other than the selected value are not checked.  For every line json.loads accepts as an object, status and text
+ * equal what json.loads(line).get(field) gives, with the surrogate repair above.
+ * flags: TK_JSONL_RAISE refuses the call (TK_JSONL_ERROR) with the first line that is neither OK nor BLANK: *bad and tk_last_error() name
+ * its index, its byte offset and its status; a refused call leaves the previous result whole.  TK_JSONL_SKIP leaves such lines out.
+ * TK_JSONL_EMPTY keeps an empty document for every non-blank line, so documents align with records.
+ * Results: text uint8[n_text] and doc_off uint64[n_docs + 1] (what tk_encode_batch_device takes; 64 readable bytes follow the text);
+ * line uint64[n_docs]: the line every document came from; line_off uint64[n_lines + 1]: where every line starts, n_bytes at the end;
+ * status uint8[n_lines].  TK_VALUE_ERROR: a field that is not 1 .. 64 bytes or holds ", \ or a byte < 0x20; an unknown flag; more than
+ * 0xFFFF0000 bytes.  NOT built: several fields or a nested path; keys spelled with escapes; full JSON validation; gzip / zstd input;
+ * several GPUs; the row, padded, chunk and sample entries fed straight from JSON Lines (they chain through the device entries). */
+#define TK_JSONL_OK 0u
+#define TK_JSONL_BLANK 1u
+#define TK_JSONL_MISSING 2u
+#define TK_JSONL_NOT_STRING 3u
+#define TK_JSONL_BAD 4u
+#define TK_JSONL_RAISE 0u
+#define TK_JSONL_SKIP 1u
+#define TK_JSONL_EMPTY 2u
+typedef struct {
+    uint64_t line, pos; /* the refused line's index and where it starts in the buffer */
+    uint32_t status, reserved;
+} tk_jsonl_bad;
+/* Device pointer in, device pointers out: buffers of the core, valid until its next JSON Lines call that succeeds and apart from all
+ * others.  `stream`: a hipStream_t or null (the core's); the call returns when the results are there.  bad may be null. */
+int tk_jsonl_extract_device(tk_core* core, const void* d_bytes, uint64_t n_bytes, const uint8_t* field, uint64_t field_len, uint32_t flags, void* stream,
+                            const uint8_t** d_text_out, const uint64_t** d_doc_off_out, const uint64_t** d_line_out, const uint64_t** d_line_off_out,
+                            const uint8_t** d_status_out, uint64_t* n_docs_out, uint64_t* n_lines_out, uint64_t* n_text_out, tk_jsonl_bad* bad);
+/* Host in, host out: the arrays are library-owned (tk_free). */
+int tk_jsonl_extract(tk_core* core, const uint8_t* bytes, uint64_t n_bytes, const uint8_t* field, uint64_t field_len, uint32_t flags, uint8_t** text_out,
+                     uint64_t** doc_off_out, uint64_t** line_out, uint64_t** line_off_out, uint8_t** status_out, uint64_t* n_docs_out, uint64_t* n_lines_out,
+                     uint64_t* n_text_out, tk_jsonl_bad* bad);
+/* Extracts, then encodes the text while it is in HBM (tk_encode_batch_device, with n_disallowed != 0 tk_encode_batch_device_checked): the
+ * text never visits the host.  tokens, tok_off uint64[n_docs + 1], line and status are library-owned (tk_free).  On
+ * TK_DISALLOWED_SPECIAL hit->doc is the document; its line is line[doc] of an extract call with the same arguments. */
+int tk_encode_jsonl(tk_core* core, const uint8_t* bytes, uint64_t n_bytes, const uint8_t* field, uint64_t field_len, uint32_t flags, int use_special,
+                    const uint32_t* allowed_ids, uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed, uint32_t** tokens_out,
+                    uint64_t* n_tokens_out, uint64_t** tok_off_out, uint64_t** line_out, uint8_t** status_out, uint64_t* n_docs_out, uint64_t* n_lines_out,
+                    tk_special_hit* hit, tk_jsonl_bad* bad);
 /* Supervised samples: a packed batch whose documents are the PARTS of samples -- the messages of a conversation, a prompt and its answer --
  * -> one row per sample with the template's ids around every part, an attention mask and labels.  Replaces nothing in the reference: it is
  * the host loop of the reference's users, the fine-tuning script that calls encode_ordinary once per message, adds header and footer ids and
@@ -773,7 +831,8 @@ void tk_last_stats(tk_core* core, uint64_t* n_bytes, uint64_t* n_pieces, uint64_
  * above 0x3FFFFFFE, tokens of 1 .. 4 bytes live in the mid table), "decode_table_ids" (entries of the device decode table; 0: an id of 2^26
  * or above, the decode entries answer TK_UNSUPPORTED); and of the last split call (tk_split_device, tk_encode_batch_split): "split_segments"
  * (document parts per block of K positions), "split_joined" (blocks in which the true chain met the speculative walk), "split_stitch_steps"
- * (steps of the stitch pass) and "split_spec_steps" (steps of the speculative walks). */
+ * (steps of the stitch pass) and "split_spec_steps" (steps of the speculative walks); "jsonl_tile": the bytes of a tile of the JSON Lines
+ * passes (a constant of the build). */
 uint64_t tk_stat(tk_core* core, const char* name);
 
 #ifdef __cplusplus

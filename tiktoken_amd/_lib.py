@@ -18,6 +18,16 @@ _lock = threading.Lock()
 _lib = None
 
 TK_OK, TK_VALUE_ERROR, TK_KEY_ERROR, TK_RUNTIME_ERROR, TK_UNSUPPORTED, TK_DISALLOWED_SPECIAL = range(6)
+TK_JSONL_ERROR = 6  # (the JSON Lines calls raise JsonlError themselves: _tiktoken.py)
+
+
+class JsonlBad(ctypes.Structure):
+    """tk_jsonl_bad: the line a JSON Lines call under TK_JSONL_RAISE refuses (include/tiktoken_amd.h)."""
+    _fields_ = [("line", ctypes.c_uint64), ("pos", ctypes.c_uint64), ("status", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+JSONL_OK, JSONL_BLANK, JSONL_MISSING, JSONL_NOT_STRING, JSONL_BAD = range(5)  # TK_JSONL_OK ..: the status of a line
+JSONL_MODES = {"raise": 0, "skip": 1, "empty": 2}                             # on_error -> TK_JSONL_RAISE, TK_JSONL_SKIP, TK_JSONL_EMPTY
 
 
 class SpecialHit(ctypes.Structure):
@@ -151,6 +161,13 @@ def lib() -> ctypes.CDLL:
             L.tk_split_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, P(SplitSpec), vp, *[P(vp)] * 9, P(u64)]
             L.tk_encode_batch_split.restype = i32
             L.tk_encode_batch_split.argtypes = [vp, vp, vp, u64, i32, vp, u64, vp, u64, P(SplitSpec), *[P(vp)] * 9, P(u64), P(vp), P(u64), vp, P(SpecialHit)]
+        if hasattr(L, "tk_jsonl_extract_device"):  # (absent from older builds selected through $TIKTOKEN_AMD_LIB)
+            L.tk_jsonl_extract_device.restype = i32
+            L.tk_jsonl_extract_device.argtypes = [vp, vp, u64, vp, u64, u32, vp, *[P(vp)] * 5, *[P(u64)] * 3, P(JsonlBad)]
+            L.tk_jsonl_extract.restype = i32
+            L.tk_jsonl_extract.argtypes = [vp, vp, u64, vp, u64, u32, *[P(vp)] * 5, *[P(u64)] * 3, P(JsonlBad)]
+            L.tk_encode_jsonl.restype = i32
+            L.tk_encode_jsonl.argtypes = [vp, vp, u64, vp, u64, u32, i32, vp, u64, vp, u64, P(vp), P(u64), P(vp), P(vp), P(vp), P(u64), P(u64), P(SpecialHit), P(JsonlBad)]
         L.tk_assemble_samples_device.restype = i32
         L.tk_assemble_samples_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, u32, vp, vp, vp, P(SmpSpec), vp, P(vp), P(vp), P(vp), P(vp), P(vp), P(vp), P(u64), P(u64)]
         L.tk_encode_batch_samples.restype = i32
@@ -266,7 +283,7 @@ def raise_for(rc: int, key=None):
     if rc == TK_OK:
         return
     msg = last_error()
-    if rc in (TK_VALUE_ERROR, TK_UNSUPPORTED, TK_DISALLOWED_SPECIAL):  # (the checked calls raise DisallowedSpecialError themselves: _tiktoken.py)
+    if rc in (TK_VALUE_ERROR, TK_UNSUPPORTED, TK_DISALLOWED_SPECIAL, TK_JSONL_ERROR):  # (the checked calls raise DisallowedSpecialError themselves: _tiktoken.py)
         raise ValueError(msg)
     if rc == TK_KEY_ERROR:
         raise KeyError(key if key is not None else msg)

@@ -604,6 +604,57 @@ def repair_mode(errors: str) -> int:
                      "handlers use decode, decode_batch or decode_rows (or decode_with_offsets_packed, which validates)")
 
 
+class JsonlError(ValueError):
+    """A JSON Lines call with on_error="raise" met a line that is neither a record nor blank: its index `line`, the byte offset `pos` it
+    starts at in the buffer and its `status` (JSONL_MISSING, JSONL_NOT_STRING or JSONL_BAD)."""
+
+    def __init__(self, line: int, pos: int, status: int, message: str):
+        super().__init__(message)
+        self.line, self.pos, self.status = line, pos, status
+
+
+class JsonlText(NamedTuple):
+    """One field of every line of a JSON Lines buffer (tk_jsonl_extract; the rule: include/tiktoken_amd.h): `text` uint8, the unescaped
+    values back to back, `doc_off` uint64[n_docs + 1] their boundaries -- what the packed encode entries take --, `line` uint64[n_docs]
+    the line every document came from, `status` uint8[n_lines] the status of every line, `line_off` uint64[n_lines + 1] where it starts."""
+    text: np.ndarray
+    doc_off: np.ndarray
+    line: np.ndarray
+    status: np.ndarray
+    n_lines: int
+    line_off: np.ndarray
+
+    def text_bytes(self, i: int) -> bytes:
+        return self.text[int(self.doc_off[i]):int(self.doc_off[i + 1])].tobytes()
+
+    def texts(self) -> "list[str]":
+        off, blob = self.doc_off.tolist(), self.text.tobytes()
+        return [blob[a:b].decode("utf-8") for a, b in zip(off[:-1], off[1:])]
+
+
+class JsonlTokens(NamedTuple):
+    """A JSON Lines buffer encoded (tk_encode_jsonl): `tokens` and `tok_off` as `encode_batch_packed` gives them, `line` and `status` as in
+    `JsonlText`."""
+    tokens: np.ndarray
+    tok_off: np.ndarray
+    line: np.ndarray
+    status: np.ndarray
+    n_lines: int
+
+
+class JsonlDevice(NamedTuple):
+    """`jsonl_extract_device`: device pointers (the core's buffers, valid until its next JSON Lines call that succeeds) to the arrays of
+    `JsonlText`, and the counts."""
+    text: int
+    doc_off: int
+    line: int
+    line_off: int
+    status: int
+    n_docs: int
+    n_lines: int
+    n_text: int
+
+
 class DisallowedSpecialError(ValueError):
     """A batch holds a disallowed special token: the first occurrence -- document `doc`, byte offset `pos` inside it, the `token` (the
     longest disallowed one that matches there).  What the reference raises as a plain ValueError, with its message."""
@@ -1466,6 +1517,70 @@ class CoreBPE:
         C, n = int(cnt[0].value), int(cnt[1].value)
         arrays = [_take_u32(x, C) for x in out[:7]] + [self._own_mask(out[7], C), _take_u32(out[8], n_docs + 1)]
         return TextChunks(arrays, _take_u32(out[9], n), tok_off, keep[0], keep[1])
+
+    # ------------------------------------------------------------------ JSON Lines (no reference counterpart: the host loop of its users)
+    @staticmethod
+    def _jsonl_args(field, on_error: str):
+        f = field.encode("utf-8") if isinstance(field, str) else bytes(field)
+        if on_error not in _lib.JSONL_MODES:
+            raise ValueError(f"on_error={on_error!r}: 'raise', 'skip' or 'empty'")
+        return np.frombuffer(f + b"\0", dtype=np.uint8), len(f), _lib.JSONL_MODES[on_error]
+
+    @staticmethod
+    def _jsonl_bytes(data) -> np.ndarray:
+        """bytes, bytearray, memoryview, mmap or a uint8 array as a uint8 view: no copy"""
+        a = data if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
+        if a.dtype != np.uint8 or a.ndim != 1 or not a.flags.c_contiguous:
+            raise ValueError("data must be contiguous bytes (bytes, bytearray, memoryview, mmap or a one-dimensional uint8 array)")
+        return a
+
+    def _jsonl_raise(self, rc: int, bad: "_lib.JsonlBad", hit=None) -> None:
+        if rc == _lib.TK_JSONL_ERROR:
+            raise JsonlError(int(bad.line), int(bad.pos), int(bad.status), _lib.last_error())
+        if hit is not None:
+            self._raise_for(rc, hit)
+        _lib.raise_for(rc)
+
+    def jsonl_extract_device(self, d_bytes: int, n_bytes: int, field="text", on_error: str = "raise", stream: int = 0) -> JsonlDevice:
+        """Device-resident JSON Lines (tk_jsonl_extract_device): a pointer to n_bytes bytes on this core's device; the unescaped text of
+        `field` of every line stays there, packed as `encode_batch_device` takes it.  See `JsonlText` for the arrays."""
+        self._one_device("jsonl_extract_device")
+        f, flen, mode = self._jsonl_args(field, on_error)
+        out, cnt, refs = self._outs(5, 3)
+        bad = _lib.JsonlBad()
+        rc = self._L.tk_jsonl_extract_device(self._h, d_bytes or None, n_bytes, f.ctypes.data, flen, mode, stream or None, *refs, ctypes.byref(bad))
+        self._jsonl_raise(rc, bad)
+        return JsonlDevice(*[x.value or 0 for x in out], *[int(x.value) for x in cnt])
+
+    def jsonl_extract_packed(self, data, field="text", on_error: str = "raise") -> JsonlText:
+        """One field of every line of a JSON Lines buffer (tk_jsonl_extract): host bytes in, a `JsonlText` out."""
+        self._one_device("jsonl_extract_packed")
+        src = self._jsonl_bytes(data)
+        f, flen, mode = self._jsonl_args(field, on_error)
+        out, cnt, refs = self._outs(5, 3)
+        bad = _lib.JsonlBad()
+        rc = self._L.tk_jsonl_extract(self._h, src.ctypes.data if len(src) else None, len(src), f.ctypes.data, flen, mode, *refs, ctypes.byref(bad))
+        self._jsonl_raise(rc, bad)
+        n_docs, n_lines, n_text = (int(x.value) for x in cnt)
+        return JsonlText(self._own_mask(out[0], n_text), _take_u64(out[1], n_docs + 1), _take_u64(out[2], n_docs), self._own_mask(out[4], n_lines), n_lines,
+                         _take_u64(out[3], n_lines + 1))
+
+    def encode_jsonl_packed(self, data, field="text", on_error: str = "raise", allowed_special: AbstractSet[str] | None = None, *, disallowed_special=None) -> JsonlTokens:
+        """A JSON Lines buffer encoded (tk_encode_jsonl): the field is extracted and encoded while it is on the device.  The special-token
+        arguments as in `encode_batch_packed`; a `DisallowedSpecialError` names the document (`doc`), not the line."""
+        self._one_device("encode_jsonl_packed")
+        src = self._jsonl_bytes(data)
+        f, flen, mode = self._jsonl_args(field, on_error)
+        ids, k = (np.zeros(1, dtype=np.uint32), 0) if allowed_special is None else self._allowed_ids(allowed_special)
+        dis, n_dis = self._disallowed_ids(disallowed_special)
+        out, cnt = [ctypes.c_void_p() for _ in range(4)], [ctypes.c_uint64() for _ in range(3)]
+        hit, bad = _lib.SpecialHit(), _lib.JsonlBad()
+        rc = self._L.tk_encode_jsonl(self._h, src.ctypes.data if len(src) else None, len(src), f.ctypes.data, flen, mode, 0 if allowed_special is None else 1, ids.ctypes.data, k,
+                                     dis.ctypes.data, n_dis, ctypes.byref(out[0]), ctypes.byref(cnt[0]), ctypes.byref(out[1]), ctypes.byref(out[2]), ctypes.byref(out[3]),
+                                     ctypes.byref(cnt[1]), ctypes.byref(cnt[2]), ctypes.byref(hit), ctypes.byref(bad))
+        self._jsonl_raise(rc, bad, hit)
+        n_tok, n_docs, n_lines = (int(x.value) for x in cnt)
+        return JsonlTokens(_take_u32(out[0], n_tok), _take_u64(out[1], n_docs + 1), _take_u64(out[2], n_docs), self._own_mask(out[3], n_lines), n_lines)
 
     # ------------------------------------------------------------------ supervised samples (no reference counterpart: the host loop of its users)
     @staticmethod

@@ -264,6 +264,87 @@ class Encoding:
             raise RuntimeError(f"internal error: the device reported the disallowed special token {e.token!r} in document {e.doc} at byte "
                                f"{e.pos}, the host search finds none there") from e
 
+    # ------------------------------------------------------------------ JSON Lines
+    @staticmethod
+    def _from_device(tensor, ptr: int, n: int, typestr: str) -> np.ndarray:
+        """n elements at a device pointer of `tensor`'s device, on the host (through torch, which the caller has: the tensor is its)"""
+        import torch
+
+        if not n:
+            return np.zeros(0, dtype=np.dtype(typestr))
+
+        class View:
+            __cuda_array_interface__ = {"shape": (n,), "typestr": typestr, "data": (ptr, False), "version": 2}  # (torch takes no read-only view; the copy below is all that touches it)
+
+        return torch.as_tensor(View(), device=tensor.device).cpu().numpy()
+
+    def _jsonl_device(self, data, field, on_error):
+        """(the JsonlDevice of a uint8 tensor on the encoding's GPU, taken by pointer)"""
+        import torch
+
+        if data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous() or not data.is_cuda or data.device.index != self._core_bpe.device:
+            raise ValueError("a tensor as data must be a contiguous one-dimensional uint8 tensor on the encoding's GPU")
+        torch.cuda.current_stream(data.device).synchronize()  # (the library runs on a stream of its own)
+        return self._core_bpe.jsonl_extract_device(data.data_ptr() if data.numel() else 0, data.numel(), field, on_error)
+
+    def extract_jsonl(self, data, field: str = "text", on_error: str = "raise") -> "_tiktoken.JsonlText":
+        """One field of every line of a JSON Lines buffer, unescaped on the GPU: what `[json.loads(l)[field] for l in f]` gives, packed as
+        the batch entries take it.  `data`: bytes, bytearray, memoryview, an mmap or a uint8 numpy array (no copy before staging), or a uint8
+        torch tensor on the encoding's GPU (by pointer).  `on_error`: "raise" (`JsonlError` with the first line that is neither a record nor
+        blank), "skip" (such lines are left out; `line` says which line a document came from) or "empty" (an empty document for every
+        non-blank line, so documents align with records).  The rule -- one field at depth 1, keys compared as raw bytes, the last duplicate
+        wins, lone surrogate escapes become U+FFFD, no full JSON validation -- is stated in include/tiktoken_amd.h."""
+        if hasattr(data, "data_ptr"):
+            v = self._jsonl_device(data, field, on_error)
+            return _tiktoken.JsonlText(self._from_device(data, v.text, v.n_text, "|u1"), self._from_device(data, v.doc_off, v.n_docs + 1, "<u8"),
+                                       self._from_device(data, v.line, v.n_docs, "<u8"), self._from_device(data, v.status, v.n_lines, "|u1"), v.n_lines,
+                                       self._from_device(data, v.line_off, v.n_lines + 1, "<u8"))
+        return self._core_bpe.jsonl_extract_packed(data, field, on_error)
+
+    def _encode_jsonl(self, data, field, on_error, allowed_special, disallowed_special) -> "_tiktoken.JsonlTokens":
+        if not hasattr(data, "data_ptr"):
+            return self._core_bpe.encode_jsonl_packed(data, field, on_error, allowed_special, disallowed_special=disallowed_special)
+        v = self._jsonl_device(data, field, on_error)
+        line, status = self._from_device(data, v.line, v.n_docs, "<u8"), self._from_device(data, v.status, v.n_lines, "|u1")
+        doc_off = self._from_device(data, v.doc_off, v.n_docs + 1, "<u8")
+        d_tok, n_tok, d_off = self._core_bpe.encode_batch_device(v.text, v.n_text, v.doc_off, doc_off, v.n_docs, allowed_special, disallowed_special=disallowed_special)
+        return _tiktoken.JsonlTokens(self._from_device(data, d_tok, n_tok, "<u4"), self._from_device(data, d_off, v.n_docs + 1, "<u8"), line, status, v.n_lines)
+
+    def encode_ordinary_jsonl_packed(self, data, field: str = "text", on_error: str = "raise") -> "_tiktoken.JsonlTokens":
+        """A JSON Lines buffer encoded, ignoring special tokens: `extract_jsonl` and `encode_ordinary_batch_packed` in one GPU call -- the
+        text never visits the host.  Returns a `JsonlTokens` (tokens, tok_off, line, status)."""
+        return self._encode_jsonl(data, field, on_error, None, None)
+
+    def encode_jsonl_packed(self, data, field: str = "text", on_error: str = "raise", *, allowed_special: Literal["all"] | AbstractSet[str] = set(),  # noqa: B006
+                            disallowed_special: Literal["all"] | Collection[str] = "all") -> "_tiktoken.JsonlTokens":
+        """`encode_ordinary_jsonl_packed` with the special-token arguments of `encode` -- the policy of `encode_batch_packed`.  A disallowed
+        special token raises `DisallowedSpecialError` with the reference's message and, besides `doc`, the `line` it stands in."""
+        allowed_special, disallowed_special = self._special_policy(allowed_special, disallowed_special)
+        if not disallowed_special:
+            return self._encode_jsonl(data, field, on_error, allowed_special, None)
+        if not isinstance(disallowed_special, frozenset):
+            disallowed_special = frozenset(disallowed_special)
+        if not all(t in self._special_tokens for t in disallowed_special):  # (as encode_batch_packed: the host's search, on the extracted text)
+            ex = self.extract_jsonl(data, field, on_error)
+            for d, t in enumerate(ex.texts()):
+                self._reject_jsonl(t, disallowed_special, d, int(ex.line[d]))
+            return self._encode_jsonl(data, field, on_error, allowed_special, None)
+        try:
+            return self._encode_jsonl(data, field, on_error, allowed_special, disallowed_special)
+        except _tiktoken.DisallowedSpecialError as e:
+            ex = self.extract_jsonl(data, field, on_error)  # (the message is the host search's, run on that one document's text)
+            self._reject_jsonl(ex.text_bytes(e.doc).decode("utf-8"), disallowed_special, e.doc, int(ex.line[e.doc]), e)
+            raise RuntimeError(f"internal error: the device reported the disallowed special token {e.token!r} in document {e.doc} at byte "
+                               f"{e.pos}, the host search finds none there") from e
+
+    @staticmethod
+    def _reject_jsonl(text: str, disallowed_special, doc: int, line: int, found=None) -> None:
+        hit = _special_token_regex(disallowed_special).search(text)
+        if hit:
+            err = _tiktoken.DisallowedSpecialError(doc, found.pos if found is not None else len(text[:hit.start()].encode("utf-8")), hit.group())
+            err.line = line
+            raise err
+
     def split_ordinary_batch_packed(self, text: Sequence[str], max_tokens: int, *, min_tokens: int | None = None, overlap: int = 0,
                                     separators=_tiktoken.DEFAULT_SEPARATORS, seg_tokens: int = 0) -> "_tiktoken.TextChunks":
         """A batch cut into chunks of at most `max_tokens` tokens, ignoring special tokens: every text is encoded and cut, each cut at the

@@ -30,6 +30,7 @@
 #include "tk_stream.h"
 #include "tk_padded.h"
 #include "tk_split.h"
+#include "tk_jsonl.h"
 #include "tk_sample_rows.h"
 #include "tk_samples.h"
 #include "tk_rows.h"
@@ -288,6 +289,10 @@ struct tk_core {
     // the class planes, the cut and spec planes, exit_at / join_at of every block and the starts per count block -- everything a call computes
     // until it is accepted.  st_split: the counters of the last call (TK_SPLIT_ST_*).
     Buf d_split, d_split_work;
+    // JSON Lines (tk_jsonl.h), apart from everything above: d_jsonl: text, doc_off, line, line_off and status of the last call that
+    // succeeded; d_jsonl_work: the report words, the tiles' summaries and entry states, the escaped plane, the tiles' counts; d_jsonl_lines:
+    // everything per line and per block of lines -- what a call computes until it is accepted; d_jsonl_in: the bytes of a host call.
+    Buf d_jsonl, d_jsonl_work, d_jsonl_lines, d_jsonl_in;
     uint64_t st_split[TK_SPLIT_STATS] = {0, 0, 0, 0};
     // Supervised samples (tk_samples.h), apart from everything above: d_smp: ids, labels and mask of every position; d_smp_row: full_len, len,
     // n_trained of every sample; d_smp_cnt: the TK_SMP_WORDS report words, the role table, pstart and the per-sample figures a call counts in
@@ -1567,10 +1572,11 @@ static int encode_device_locked(tk_core* c, hipStream_t s, const uint8_t* d_utf8
 
 static int encode_batch_device_impl(tk_core* c, const void* d_utf8, uint64_t n_bytes, const void* d_doc_off, const uint64_t* h_doc_off, uint64_t n_docs,
                                     int use_special, const uint32_t* allowed_ids, uint64_t n_allowed, void* stream, const uint32_t** d_tokens_out,
-                                    uint64_t* n_tokens_out, const uint64_t** d_tok_off_out, const CheckArgs* chk) {
+                                    uint64_t* n_tokens_out, const uint64_t** d_tok_off_out, const CheckArgs* chk, bool locked = false) {
     if (!c) return fail(TK_VALUE_ERROR, "core is null");
     TRY(check_disallowed_ids(c, chk));
-    std::lock_guard<std::mutex> lk(c->mu);
+    std::unique_lock<std::mutex> lk(c->mu, std::defer_lock);
+    if (!locked) lk.lock();  // (locked: the caller holds c->mu -- tk_encode_jsonl, whose text is the core's own)
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     bool any = false;
@@ -3159,6 +3165,195 @@ extern "C" int tk_encode_batch_split(tk_core* c, const uint8_t* utf8, const uint
             *n_tokens_out = n;
             return TK_OK;
         });
+}
+
+// ------------------------------------------------------------------------------------------
+// JSON Lines (tk_jsonl.h): a buffer of lines on the device -> the unescaped text of one field per line as (text, doc_off), line statuses.
+// ------------------------------------------------------------------------------------------
+static_assert(TK_JSONL_OK == TK_JSONL_ST_OK && TK_JSONL_BLANK == TK_JSONL_ST_BLANK && TK_JSONL_MISSING == TK_JSONL_ST_MISSING &&
+                  TK_JSONL_NOT_STRING == TK_JSONL_ST_NOT_STRING && TK_JSONL_BAD == TK_JSONL_ST_BAD,
+              "tk_jsonl statuses");
+static_assert(TK_JSONL_RAISE == TK_JSONL_M_RAISE && TK_JSONL_SKIP == TK_JSONL_M_SKIP && TK_JSONL_EMPTY == TK_JSONL_M_EMPTY, "tk_jsonl modes");
+struct JsonlView {  // device buffers of the core, valid until its next JSON Lines call that succeeds
+    uint8_t *text = nullptr, *status = nullptr;
+    uint64_t *doc_off = nullptr, *line = nullptr, *line_off = nullptr;
+    uint64_t n_docs = 0, n_lines = 0, n_text = 0;
+};
+static int jsonl_refusal(int why) {
+    switch (why) {
+        case 0: return TK_OK;
+        case 1: return fail(TK_VALUE_ERROR, "field must be 1 .. 64 bytes");
+        case 2: return fail(TK_VALUE_ERROR, "field must not hold a quote, a backslash or a byte below 0x20 (keys are compared as raw bytes)");
+        case 3: return fail(TK_VALUE_ERROR, "flags: TK_JSONL_RAISE, TK_JSONL_SKIP or TK_JSONL_EMPTY");
+        case 4: return fail(TK_VALUE_ERROR, "n_bytes: a JSON Lines buffer is at most 0xFFFF0000 bytes (positions are 32-bit)");
+        default: return fail(TK_VALUE_ERROR, "tile must be a multiple of 64");
+    }
+}
+static const char* jsonl_status_name(unsigned st) {
+    static const char* names[] = {"ok", "blank", "the field is missing", "the field's value is not a string", "not a JSON object the pass can read"};
+    return st < 5 ? names[st] : "?";
+}
+// jsonl_run: the caller holds c->mu.  The host waits twice: for the number of lines, and for documents, text bytes and the first line
+// TK_JSONL_RAISE refuses.  A call that is refused has written into d_jsonl_work and d_jsonl_lines only: the previous result stays whole.
+static int jsonl_run(tk_core* c, hipStream_t s, const uint8_t* d_bytes, uint64_t n, const uint8_t* field, uint64_t flen, uint32_t flags, JsonlView* out, tk_jsonl_bad* bad) {
+    if (!field) return fail(TK_VALUE_ERROR, "null argument");
+    TkJsonl j;
+    TRY(jsonl_refusal(tk_jsonl_shape(n, field, flen, flags, TK_JSONL_TILE, &j)));
+    uint8_t head[3] = {0, 0, 0}, last = '\n';
+    if (n >= 3) HIPCHK(hipMemcpyAsync(head, d_bytes, 3, hipMemcpyDeviceToHost, s));
+    if (n) HIPCHK(hipMemcpyAsync(&last, d_bytes + n - 1, 1, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    j.p = d_bytes;
+    j.bom = n >= 3 && head[0] == 0xEF && head[1] == 0xBB && head[2] == 0xBF ? 3u : 0u;
+    j.eof_nl = n && last != '\n' ? 1u : 0u;
+    const uint64_t nt = j.n_tiles, W = nt * (TK_JSONL_TILE / 64);
+    Carve work;
+    const uint64_t at_words = work.add(TK_JSONL_WORDS * 8);
+    uint64_t at_t[14];
+    for (uint64_t& a : at_t) a = work.add(nt * 4);
+    const uint64_t at_entry = work.add(nt * sizeof(TkJsonlCarry)), at_ep = work.add(W * 8), at_cnt = work.add(nt * 4);
+    TRY(ensure(c->d_jsonl_work, work.total));
+    unsigned long long* words = carved<unsigned long long>(c->d_jsonl_work, at_words);
+    auto tu = [&](int i) { return carved<uint32_t>(c->d_jsonl_work, at_t[i]); };
+    auto ti = [&](int i) { return carved<int32_t>(c->d_jsonl_work, at_t[i]); };
+    const TkJsonlTiles T{tu(0), tu(1), tu(2), tu(3), tu(4), tu(5), ti(6), tu(7), tu(8), ti(9), ti(10), ti(11), ti(12), tu(13)};
+    TkJsonlCarry* entry = carved<TkJsonlCarry>(c->d_jsonl_work, at_entry);
+    unsigned long long* ep = carved<unsigned long long>(c->d_jsonl_work, at_ep);
+    uint32_t* cnt = carved<uint32_t>(c->d_jsonl_work, at_cnt);
+    HIPCHK(hipMemsetAsync(words, 0, TK_JSONL_WORDS * 8, s));
+    HIPCHK(hipMemsetAsync(words + TK_JSONL_W_BADLINE, 0xFF, 8, s));
+    const dim3 tiles((uint32_t)((nt + 3) / 4));
+    TRY(timed(c, s, "tk_k_jsonl_sum", [&] { hipLaunchKernelGGL(tk_k_jsonl_sum, tiles, dim3(256), 0, s, j, T); }));
+    TRY(timed(c, s, "tk_k_jsonl_carry", [&] { hipLaunchKernelGGL(tk_k_jsonl_carry, dim3(1), dim3(1024), 0, s, j, T, entry, words); }));
+    unsigned long long got[TK_JSONL_WORDS];
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(got, words, sizeof got, hipMemcpyDeviceToHost));
+    const uint64_t n_lines = got[TK_JSONL_W_LINES], nb = (n_lines + TK_JSONL_LB - 1) / TK_JSONL_LB;
+    Carve lines;
+    uint64_t at_l[7];
+    for (uint64_t& a : at_l) a = lines.add((n_lines + 1) * 4);
+    const uint64_t at_vmax = lines.add((n_lines + 1) * 8), at_status = lines.add(n_lines + 1), at_loff = lines.add((n_lines + 1) * 8);
+    const uint64_t at_blen = lines.add((nb + 1) * 4), at_bdocs = lines.add((nb + 1) * 4);
+    TRY(ensure(c->d_jsonl_lines, lines.total));
+    HIPCHK(hipMemsetAsync(c->d_jsonl_lines.p, 0, lines.total, s));
+    auto lu = [&](int i) { return carved<uint32_t>(c->d_jsonl_lines, at_l[i]); };
+    const TkJsonlLines L{lu(0), lu(1), lu(2), lu(3), lu(4), lu(5), lu(6), carved<uint64_t>(c->d_jsonl_lines, at_vmax), carved<uint8_t>(c->d_jsonl_lines, at_status)};
+    uint64_t* w_loff = carved<uint64_t>(c->d_jsonl_lines, at_loff);
+    uint32_t *blen = carved<uint32_t>(c->d_jsonl_lines, at_blen), *bdocs = carved<uint32_t>(c->d_jsonl_lines, at_bdocs);
+    TRY(timed(c, s, "tk_k_jsonl_select", [&] { hipLaunchKernelGGL(tk_k_jsonl_select, tiles, dim3(256), 0, s, j, entry, L, w_loff, ep); }));
+    TRY(timed(c, s, "tk_k_jsonl_count", [&] { hipLaunchKernelGGL(tk_k_jsonl_count, tiles, dim3(256), 0, s, j, entry, ep, L, cnt); }));
+    TRY(timed(c, s, "tk_k_jsonl_tile_scan", [&] { hipLaunchKernelGGL(tk_k_jsonl_tile_scan, dim3(1), dim3(1024), 0, s, cnt, (uint32_t)nt); }));
+    if (nb) TRY(timed(c, s, "tk_k_jsonl_lines", [&] { hipLaunchKernelGGL(tk_k_jsonl_lines, dim3((uint32_t)nb), dim3(256), 0, s, j, L, cnt, (uint32_t)n_lines, blen, bdocs, words); }));
+    TRY(timed(c, s, "tk_k_jsonl_line_scan", [&] { hipLaunchKernelGGL(tk_k_jsonl_line_scan, dim3(1), dim3(1024), 0, s, blen, bdocs, (uint32_t)nb, words); }));
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(got, words, sizeof got, hipMemcpyDeviceToHost));
+    if (got[TK_JSONL_W_BADLINE] != ~0ull) {  // TK_JSONL_RAISE: the first line that is neither a record nor blank
+        const uint64_t line = got[TK_JSONL_W_BADLINE];
+        uint64_t pos = 0;
+        uint8_t st = 0;
+        HIPCHK(hipMemcpy(&pos, w_loff + line, 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(&st, L.status + line, 1, hipMemcpyDeviceToHost));
+        if (bad) *bad = tk_jsonl_bad{line, pos, st, 0};
+        return fail(TK_JSONL_ERROR, "line " + std::to_string(line) + " (byte " + std::to_string(pos) + "): " + jsonl_status_name(st));
+    }
+    const uint64_t n_docs = got[TK_JSONL_W_DOCS], n_text = got[TK_JSONL_W_TEXT];
+    Carve res;
+    const uint64_t at_text = res.add(n_text + 64), at_doff = res.add((n_docs + 1) * 8), at_line = res.add((n_docs + 1) * 8), at_rloff = res.add((n_lines + 1) * 8);
+    const uint64_t at_rst = res.add(n_lines + 1);
+    TRY(ensure(c->d_jsonl, res.total));
+    out->text = carved<uint8_t>(c->d_jsonl, at_text), out->status = carved<uint8_t>(c->d_jsonl, at_rst);
+    out->doc_off = carved<uint64_t>(c->d_jsonl, at_doff), out->line = carved<uint64_t>(c->d_jsonl, at_line), out->line_off = carved<uint64_t>(c->d_jsonl, at_rloff);
+    out->n_docs = n_docs, out->n_lines = n_lines, out->n_text = n_text;
+    HIPCHK(hipMemsetAsync(out->text + n_text, 0, 64, s));  // (the encode entries read up to 64 bytes behind the text)
+    TRY(timed(c, s, "tk_k_jsonl_docs", [&] {
+        hipLaunchKernelGGL(tk_k_jsonl_docs, dim3((uint32_t)(nb ? nb : 1)), dim3(256), 0, s, j, L, (uint32_t)n_lines, blen, bdocs, n_docs, n_text, out->doc_off, out->line);
+    }));
+    if (n_text) TRY(timed(c, s, "tk_k_jsonl_write", [&] { hipLaunchKernelGGL(tk_k_jsonl_write, tiles, dim3(256), 0, s, j, entry, ep, L, cnt, out->doc_off, out->text); }));
+    HIPCHK(hipMemcpyAsync(out->line_off, w_loff, (n_lines + 1) * 8, hipMemcpyDeviceToDevice, s));
+    if (n_lines) HIPCHK(hipMemcpyAsync(out->status, L.status, n_lines, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    return TK_OK;
+}
+
+extern "C" int tk_jsonl_extract_device(tk_core* c, const void* d_bytes, uint64_t n_bytes, const uint8_t* field, uint64_t field_len, uint32_t flags, void* stream,
+                                       const uint8_t** d_text_out, const uint64_t** d_doc_off_out, const uint64_t** d_line_out, const uint64_t** d_line_off_out,
+                                       const uint8_t** d_status_out, uint64_t* n_docs_out, uint64_t* n_lines_out, uint64_t* n_text_out, tk_jsonl_bad* bad) {
+    JsonlView v;
+    TRY(device_pass(c, d_bytes || !n_bytes, stream, [&](hipStream_t s) { return jsonl_run(c, s, (const uint8_t*)d_bytes, n_bytes, field, field_len, flags, &v, bad); }));
+    if (d_text_out) *d_text_out = v.text;
+    if (d_doc_off_out) *d_doc_off_out = v.doc_off;
+    if (d_line_out) *d_line_out = v.line;
+    if (d_line_off_out) *d_line_off_out = v.line_off;
+    if (d_status_out) *d_status_out = v.status;
+    if (n_docs_out) *n_docs_out = v.n_docs;
+    if (n_lines_out) *n_lines_out = v.n_lines;
+    if (n_text_out) *n_text_out = v.n_text;
+    return TK_OK;
+}
+// the bytes of a host call on their way to d_jsonl_in, block by block on the copy stream (the caller holds c->mu), then jsonl_run
+static int jsonl_run_host(tk_core* c, const uint8_t* bytes, uint64_t n, const uint8_t* field, uint64_t flen, uint32_t flags, JsonlView* v, tk_jsonl_bad* bad) {
+    if (n > TK_JSONL_MAX_BYTES) return jsonl_refusal(4);
+    HIPCHK(hipSetDevice(c->device));
+    TRY(ensure_copy_streams(c));
+    TRY(ensure(c->d_jsonl_in, n + 64));
+    if (n) {
+        Feed feed(c, c->d_jsonl_in.p, bytes, n, TK_STAGE_BYTES);
+        TRY(feed.start());
+        TRY(feed.wait(feed.n_blocks - 1, c->stream));
+        const hipError_t e = feed.finish();
+        if (e != hipSuccess) return fail(TK_RUNTIME_ERROR, std::string("HIP error: ") + hipGetErrorString(e));
+    }
+    return drained(c, [&] { return jsonl_run(c, c->stream, c->d_jsonl_in.as<uint8_t>(), n, field, flen, flags, v, bad); });
+}
+extern "C" int tk_jsonl_extract(tk_core* c, const uint8_t* bytes, uint64_t n_bytes, const uint8_t* field, uint64_t field_len, uint32_t flags, uint8_t** text_out,
+                                uint64_t** doc_off_out, uint64_t** line_out, uint64_t** line_off_out, uint8_t** status_out, uint64_t* n_docs_out, uint64_t* n_lines_out,
+                                uint64_t* n_text_out, tk_jsonl_bad* bad) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if ((!bytes && n_bytes) || !text_out || !doc_off_out || !line_out || !line_off_out || !status_out || !n_docs_out || !n_lines_out || !n_text_out)
+        return fail(TK_VALUE_ERROR, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    JsonlView v;
+    TRY(jsonl_run_host(c, bytes, n_bytes, field, field_len, flags, &v, bad));
+    ResultBag bag;
+    TRY(bag.fetch(text_out, v.text, v.n_text));
+    TRY(bag.fetch(doc_off_out, v.doc_off, v.n_docs + 1));
+    TRY(bag.fetch(line_out, v.line, v.n_docs));
+    TRY(bag.fetch(line_off_out, v.line_off, v.n_lines + 1));
+    TRY(bag.fetch(status_out, v.status, v.n_lines));
+    bag.give();
+    *n_docs_out = v.n_docs, *n_lines_out = v.n_lines, *n_text_out = v.n_text;
+    return TK_OK;
+}
+// Extract, then the batch encode of the device entries on the text where it is: the text never visits the host.
+extern "C" int tk_encode_jsonl(tk_core* c, const uint8_t* bytes, uint64_t n_bytes, const uint8_t* field, uint64_t field_len, uint32_t flags, int use_special,
+                               const uint32_t* allowed_ids, uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed, uint32_t** tokens_out,
+                               uint64_t* n_tokens_out, uint64_t** tok_off_out, uint64_t** line_out, uint8_t** status_out, uint64_t* n_docs_out, uint64_t* n_lines_out,
+                               tk_special_hit* hit, tk_jsonl_bad* bad) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if ((!bytes && n_bytes) || !tokens_out || !n_tokens_out || !tok_off_out || !line_out || !status_out || !n_docs_out || !n_lines_out || (n_disallowed && !hit))
+        return fail(TK_VALUE_ERROR, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    JsonlView v;
+    TRY(jsonl_run_host(c, bytes, n_bytes, field, field_len, flags, &v, bad));
+    const CheckArgs chk{disallowed_ids, n_disallowed, hit};
+    const uint32_t* d_tok = nullptr;
+    const uint64_t* d_tok_off = nullptr;
+    uint64_t n_tok = 0;
+    std::vector<uint64_t> h_doc_off(v.n_docs + 1);  // (a batch of several chunks is cut by the host's copy of the offsets)
+    HIPCHK(hipMemcpy(h_doc_off.data(), v.doc_off, (v.n_docs + 1) * 8, hipMemcpyDeviceToHost));
+    TRY(encode_batch_device_impl(c, v.text, v.n_text, v.doc_off, h_doc_off.data(), v.n_docs, use_special, allowed_ids, n_allowed, nullptr, &d_tok, &n_tok, &d_tok_off,
+                                 n_disallowed ? &chk : nullptr, /* locked */ true));
+    ResultBag bag;
+    TRY(bag.fetch(tokens_out, d_tok, n_tok));
+    TRY(bag.fetch(tok_off_out, d_tok_off, v.n_docs + 1));
+    TRY(bag.fetch(line_out, v.line, v.n_docs));
+    TRY(bag.fetch(status_out, v.status, v.n_lines));
+    bag.give();
+    *n_tokens_out = n_tok, *n_docs_out = v.n_docs, *n_lines_out = v.n_lines;
+    return TK_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -5028,6 +5223,7 @@ extern "C" uint64_t tk_stat(tk_core* c, const char* name) {
     if (k == "split_joined") return c->st_split[TK_SPLIT_ST_JOINED];          // ... blocks in which the true chain met the speculative walk
     if (k == "split_stitch_steps") return c->st_split[TK_SPLIT_ST_STITCH];    // ... steps of the stitch pass (one wavefront per document, in order)
     if (k == "split_spec_steps") return c->st_split[TK_SPLIT_ST_SPEC];        // ... steps of the speculative walks
+    if (k == "jsonl_tile") return TK_JSONL_TILE;  // bytes of a tile of the JSON Lines passes (tk_jsonl_rule.h)
     if (k == "regrown") return c->st_regrown;  // batches repeated with a larger miss data since the core was made (encode_device_locked)
     if (k == "workspace_bytes") {             // device memory of the work sets (everything but the text, the tables and the outputs)
         uint64_t t = 0;
