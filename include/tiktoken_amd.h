@@ -378,6 +378,54 @@ int tk_encode_jsonl(tk_core* core, const uint8_t* bytes, uint64_t n_bytes, const
                     const uint32_t* allowed_ids, uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed, uint32_t** tokens_out,
                     uint64_t* n_tokens_out, uint64_t** tok_off_out, uint64_t** line_out, uint8_t** status_out, uint64_t* n_docs_out, uint64_t* n_lines_out,
                     tk_special_hit* hit, tk_jsonl_bad* bad);
+/* Near-duplicate fingerprints: a packed batch -> per document a MinHash signature over its token shingles, the LSH band keys of that
+ * signature, an exact hash and the shingle count.  Replaces nothing in the reference: it is the host step of the reference's users
+ * between "tokenise" and "pack rows", duplicate and near-duplicate removal -- here one call on ids that are on the device anyway.
+ * The rule.  All arithmetic is unsigned, modulo 2^64 unless a narrower width is said.
+ *  mix(z): z += 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; the result is
+ *   z ^ (z >> 31).
+ *  Parameters (tk_fingerprint_spec): ngram k in 1 .. 32; n_perm P in 1 .. 256; bands B in 1 .. P with P % B == 0, r = P / B; seed, a
+ *   uint64.  Anything else is TK_VALUE_ERROR, and nothing is written.
+ *  Shingles.  Document d holds the tokens t[s .. e), s = tok_off[d], e = tok_off[d + 1], L = e - s.  L == 0: it has no shingle.
+ *   1 <= L < k: it has one shingle, over all its L ids (m = L).  L >= k: it has L - k + 1 shingles, one per start position, of m = k ids.
+ *   A shingle never crosses a document boundary.
+ *  A shingle's hash over the ids u[0 .. m): x = mix(seed ^ m), then for j = 0 .. m - 1: x = mix(x ^ u[j]); the hash h is the last x.
+ *   Ids are taken as uint32 values, whatever they are: an id need not be a token of the vocabulary.
+ *  Permutation p (0 <= p < P): a_p = mix(seed + 2p + 1) | 1, b_p = mix(seed + 2p + 2); its value at h is (uint32)((a_p * h + b_p) >> 32).
+ *  sig[d][p]: the minimum of permutation p's values over the hashes of d's shingles; 0xFFFFFFFF if d has none.
+ *  n_shingles[d] (uint64): how many shingles d has.
+ *  band[d][j] (0 <= j < B): x = mix(seed ^ 0x42414E4400000000 ^ j), then for i = 0 .. r - 1: x = mix(x ^ sig[d][j * r + i]); the key is
+ *   the last x.  It is defined for empty documents too; consumers skip documents with n_shingles == 0.
+ *  exact[d] = mix(L ^ sum over i < L of mix(seed ^ ((i + 1) << 32) ^ t[s + i])): the position makes it depend on the order.
+ *  Minimum and sum are commutative: the result is a function of (tokens, tok_off, spec) alone.
+ * NOT built: shingles of the text's words or chars; grouping on the device; an index across batches; several GPUs; b-bit signatures;
+ *  entries fed from JSON Lines or from chunks. */
+typedef struct {
+    uint32_t ngram, n_perm, bands;
+    uint64_t seed;
+} tk_fingerprint_spec;
+/* Device pointers in (ids uint32, d_tok_off uint64[n_docs + 1]: e.g. the results of tk_encode_batch_device), the caller's device arrays
+ * out, any of which may be null: d_sig uint32[n_docs * P], d_band uint64[n_docs * B], d_exact and d_n_shingles uint64[n_docs].  Everything
+ * is queued on `stream` and the call returns without waiting: the arrays are ready when the stream has got there, and whoever reads them
+ * orders the read behind this call on that stream, as the call orders itself behind whatever made d_tokens and d_tok_off there.  `stream`
+ * is a hipStream_t exactly as a kernel launch takes one; null is HIP's null stream -- not the core's own stream, as in the entries
+ * that wait before they return: the caller could not wait on that.  With d_band but without d_sig the signatures pass through a buffer
+ * of the core; the library orders the calls that use that buffer among themselves on the device (an event, no host wait), whatever
+ * their streams and entries, so nothing is asked of the caller.  d_tok_off is not checked: it must ascend from 0 to n_tokens; one that does not gives values nobody has defined, never
+ * an access outside the arrays.  d_exact holds the sum until the last pass closes it.  n_docs == 0 and n_tokens == 0 are valid. */
+int tk_fingerprint_device(tk_core* core, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_docs, const tk_fingerprint_spec* spec,
+                          void* stream, uint32_t* d_sig, uint64_t* d_band, uint64_t* d_exact, uint64_t* d_n_shingles);
+/* The same from host arrays to the caller's host arrays (sized as above, any may be null); tok_off[n_docs] is the number of tokens, and
+ * a tok_off that does not ascend from 0 is TK_VALUE_ERROR. */
+int tk_fingerprint(tk_core* core, const uint32_t* tokens, const uint64_t* tok_off, uint64_t n_docs, const tk_fingerprint_spec* spec, uint32_t* sig_out,
+                   uint64_t* band_out, uint64_t* exact_out, uint64_t* n_shingles_out);
+/* tk_encode_batch -- with n_disallowed != 0: tk_encode_batch_checked -- with the fingerprints of the ids while they are on the device:
+ * host text in, the caller's host arrays out (sized as above, any may be null; tok_off_out: n_docs + 1).  The ids stay on the device
+ * unless tokens_out is there (library-owned, tk_free; *n_tokens_out ids).  On TK_DISALLOWED_SPECIAL nothing is handed out. */
+int tk_encode_batch_fingerprint(tk_core* core, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special, const uint32_t* allowed_ids,
+                                uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed, const tk_fingerprint_spec* spec, uint32_t* sig_out,
+                                uint64_t* band_out, uint64_t* exact_out, uint64_t* n_shingles_out, uint64_t* tok_off_out, uint32_t** tokens_out,
+                                uint64_t* n_tokens_out, tk_special_hit* hit);
 /* Supervised samples: a packed batch whose documents are the PARTS of samples -- the messages of a conversation, a prompt and its answer --
  * -> one row per sample with the template's ids around every part, an attention mask and labels.  Replaces nothing in the reference: it is
  * the host loop of the reference's users, the fine-tuning script that calls encode_ordinary once per message, adds header and footer ids and
@@ -832,7 +880,7 @@ void tk_last_stats(tk_core* core, uint64_t* n_bytes, uint64_t* n_pieces, uint64_
  * or above, the decode entries answer TK_UNSUPPORTED); and of the last split call (tk_split_device, tk_encode_batch_split): "split_segments"
  * (document parts per block of K positions), "split_joined" (blocks in which the true chain met the speculative walk), "split_stitch_steps"
  * (steps of the stitch pass) and "split_spec_steps" (steps of the speculative walks); "jsonl_tile": the bytes of a tile of the JSON Lines
- * passes (a constant of the build). */
+ * passes (a constant of the build); "fingerprint_tile": the token positions of a tile of the fingerprint pass (likewise). */
 uint64_t tk_stat(tk_core* core, const char* name);
 
 #ifdef __cplusplus

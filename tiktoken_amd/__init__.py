@@ -7,7 +7,7 @@ methods handing whole batches to the GPU; `get_encoding` / `list_encoding_names`
 """
 __version__ = "0.1.0"
 
-from ._tiktoken import CoreBPE, DisallowedSpecialError, JsonlError, JsonlText, JsonlTokens, Role, SampleBatch, SampleRows, SampleRowsDevice, StoppedRows, StreamPacked, StreamStep, TextChunks  # noqa: F401
+from ._tiktoken import CoreBPE, DisallowedSpecialError, Fingerprints, JsonlError, JsonlText, JsonlTokens, Role, SampleBatch, SampleRows, SampleRowsDevice, StoppedRows, StreamPacked, StreamStep, TextChunks  # noqa: F401
 from .core import DecodeStream  # noqa: F401
 from .core import Encoding  # noqa: F401
 from .train import bpe_train, merges_to_ranks, train_encoding  # noqa: F401

@@ -35,6 +35,11 @@ class SpecialHit(ctypes.Structure):
     _fields_ = [("doc", ctypes.c_uint64), ("pos", ctypes.c_uint64), ("id", ctypes.c_uint32), ("len", ctypes.c_uint32)]
 
 
+class FingerprintSpec(ctypes.Structure):
+    """tk_fingerprint_spec: shingle length, permutations, bands and seed of a fingerprint call (include/tiktoken_amd.h)."""
+    _fields_ = [("ngram", ctypes.c_uint32), ("n_perm", ctypes.c_uint32), ("bands", ctypes.c_uint32), ("seed", ctypes.c_uint64)]
+
+
 class RowsSpec(ctypes.Structure):
     """tk_rows_spec: how a packed batch is cut into training rows (include/tiktoken_amd.h)."""
     _fields_ = [("seq_len", ctypes.c_uint32), ("bos_id", ctypes.c_uint32), ("eos_id", ctypes.c_uint32), ("pad_id", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
@@ -161,6 +166,13 @@ def lib() -> ctypes.CDLL:
             L.tk_split_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, P(SplitSpec), vp, *[P(vp)] * 9, P(u64)]
             L.tk_encode_batch_split.restype = i32
             L.tk_encode_batch_split.argtypes = [vp, vp, vp, u64, i32, vp, u64, vp, u64, P(SplitSpec), *[P(vp)] * 9, P(u64), P(vp), P(u64), vp, P(SpecialHit)]
+        if hasattr(L, "tk_fingerprint_device"):  # (absent from older builds selected through $TIKTOKEN_AMD_LIB)
+            L.tk_fingerprint_device.restype = i32
+            L.tk_fingerprint_device.argtypes = [vp, vp, u64, vp, u64, P(FingerprintSpec), vp, vp, vp, vp, vp]
+            L.tk_fingerprint.restype = i32
+            L.tk_fingerprint.argtypes = [vp, vp, vp, u64, P(FingerprintSpec), vp, vp, vp, vp]
+            L.tk_encode_batch_fingerprint.restype = i32
+            L.tk_encode_batch_fingerprint.argtypes = [vp, vp, vp, u64, i32, vp, u64, vp, u64, P(FingerprintSpec), vp, vp, vp, vp, vp, P(vp), P(u64), P(SpecialHit)]
         if hasattr(L, "tk_jsonl_extract_device"):  # (absent from older builds selected through $TIKTOKEN_AMD_LIB)
             L.tk_jsonl_extract_device.restype = i32
             L.tk_jsonl_extract_device.argtypes = [vp, vp, u64, vp, u64, u32, vp, *[P(vp)] * 5, *[P(u64)] * 3, P(JsonlBad)]

@@ -655,6 +655,57 @@ class JsonlDevice(NamedTuple):
     n_text: int
 
 
+class Fingerprints(NamedTuple):
+    """Near-duplicate fingerprints of a batch (tk_fingerprint; the rule: include/tiktoken_amd.h): `sig` uint32[n, P] the MinHash signatures
+    over token shingles, `band` uint64[n, B] the LSH keys of their bands, `exact` uint64[n] a hash of the whole document, `n_shingles`
+    uint64[n], `length` uint64[n] the documents' token counts.  The helpers run on the host, in numpy, and are deterministic."""
+    sig: np.ndarray
+    band: np.ndarray
+    exact: np.ndarray
+    n_shingles: np.ndarray
+    length: np.ndarray
+
+    def jaccard(self, i: int, j: int) -> float:
+        """The share of signature positions documents i and j agree in: an estimate of their shingle sets' Jaccard index."""
+        return float(np.count_nonzero(self.sig[i] == self.sig[j])) / self.sig.shape[1]
+
+    def exact_groups(self) -> np.ndarray:
+        """int64[n]: for every document the lowest index of a document with the same (exact, length)."""
+        if not len(self.exact):
+            return np.zeros(0, dtype=np.int64)
+        _, first, inv = np.unique(np.stack([self.exact, self.length], axis=1), axis=0, return_index=True, return_inverse=True)
+        return first[inv.reshape(-1)].astype(np.int64)
+
+    def duplicate_groups(self, threshold: float = 0.8) -> np.ndarray:
+        """int64[n]: the lowest index of every document's group.  Per band, the documents with shingles that share a key are each compared
+        with the lowest of them and joined to it (union-find) when `jaccard` >= threshold: n * B comparisons at the most."""
+        n, P = self.sig.shape
+        parent = list(range(n))
+
+        def find(x: int) -> int:
+            while parent[x] != x:
+                parent[x] = parent[parent[x]]
+                x = parent[x]
+            return x
+
+        live = np.flatnonzero(self.n_shingles > 0)
+        for j in range(self.band.shape[1] if len(live) else 0):
+            _, first, inv = np.unique(self.band[live, j], return_index=True, return_inverse=True)
+            rep = live[first[inv.reshape(-1)]]  # (live ascends: the first occurrence of a key is its lowest index)
+            other = rep != live
+            a, b = live[other], rep[other]
+            close = np.count_nonzero(self.sig[a] == self.sig[b], axis=1) / P >= threshold
+            for x, y in zip(a[close].tolist(), b[close].tolist()):
+                rx, ry = find(x), find(y)
+                if rx != ry:
+                    parent[max(rx, ry)] = min(rx, ry)  # (the root of a group is its lowest index)
+        return np.fromiter((find(x) for x in range(n)), dtype=np.int64, count=n)
+
+    def keep_mask(self, threshold: float = 0.8) -> np.ndarray:
+        """bool[n]: true for the representative (the lowest index) of every group of `duplicate_groups`."""
+        return self.duplicate_groups(threshold) == np.arange(len(self.exact))
+
+
 class DisallowedSpecialError(ValueError):
     """A batch holds a disallowed special token: the first occurrence -- document `doc`, byte offset `pos` inside it, the `token` (the
     longest disallowed one that matches there).  What the reference raises as a plain ValueError, with its message."""
@@ -1581,6 +1632,80 @@ class CoreBPE:
         self._jsonl_raise(rc, bad, hit)
         n_tok, n_docs, n_lines = (int(x.value) for x in cnt)
         return JsonlTokens(_take_u32(out[0], n_tok), _take_u64(out[1], n_docs + 1), _take_u64(out[2], n_docs), self._own_mask(out[3], n_lines), n_lines)
+
+    # ------------------------------------------------------------------ near-duplicate fingerprints (no reference counterpart: the host step of its users)
+    @staticmethod
+    def _fp_spec(ngram: int, n_perm: int, bands: int, seed: int) -> "_lib.FingerprintSpec":
+        """The tk_fingerprint_spec; what does not fit the structure is refused here, the library refuses the rest."""
+        for name, v in (("ngram", ngram), ("n_perm", n_perm), ("bands", bands)):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise ValueError(f"{name} must fit 32 bits")
+        if not 0 <= int(seed) <= 0xFFFFFFFFFFFFFFFF:
+            raise ValueError("seed must fit 64 bits")
+        return _lib.FingerprintSpec(int(ngram), int(n_perm), int(bands), int(seed))
+
+    def fingerprint_device(self, tokens, tok_off, *, ngram: int = 5, n_perm: int = 128, bands: int = 16, seed: int = 0, sig=None, band=None, exact=None, n_shingles=None,
+                           stream: int | None = None) -> None:
+        """Device-resident fingerprints (tk_fingerprint_device): torch tensors on this core's device, taken by pointer -- `tokens` (a
+        32-bit dtype) and `tok_off` (a 64-bit dtype, n_docs + 1 entries ascending from 0 to len(tokens)) in; the caller's tensors out, any
+        of which may be None: `sig` (32-bit, n_docs * n_perm), `band` (64-bit, n_docs * bands), `exact` and `n_shingles` (64-bit, n_docs).
+        The work is queued on `stream` -- a HIP stream handle; default: torch's current stream of the device; 0 is the null stream, which is
+        torch's default stream -- and the call does not wait for it: it is ordered on that stream like a kernel torch itself had launched."""
+        import torch
+
+        self._one_device("fingerprint_device")
+        spec = self._fp_spec(ngram, n_perm, bands, seed)
+        n_docs = tok_off.numel() - 1
+        if n_docs < 0:
+            raise ValueError("tok_off must hold n_docs + 1 entries")
+        for name, t, size, count in (("tokens", tokens, 4, tokens.numel()), ("tok_off", tok_off, 8, n_docs + 1), ("sig", sig, 4, n_docs * spec.n_perm),
+                                     ("band", band, 8, n_docs * spec.bands), ("exact", exact, 8, n_docs), ("n_shingles", n_shingles, 8, n_docs)):
+            if t is None:
+                continue
+            if not t.is_cuda or t.device.index != self.device or not t.is_contiguous() or t.element_size() != size or t.numel() != count:
+                raise ValueError(f"{name} must be a contiguous tensor of {count} elements of {size} bytes on this core's GPU")
+        if stream is None:
+            stream = torch.cuda.current_stream(tokens.device).cuda_stream
+        ptr = [t.data_ptr() if t is not None and t.numel() else None for t in (sig, band, exact, n_shingles)]
+        rc = self._L.tk_fingerprint_device(self._h, tokens.data_ptr() if tokens.numel() else None, tokens.numel(), tok_off.data_ptr(), n_docs, ctypes.byref(spec),
+                                           stream or None, *ptr)  # (a null handle is the null stream here, not the core's stream)
+        _lib.raise_for(rc)
+
+    def fingerprint_packed(self, tokens: np.ndarray, tok_off: np.ndarray, *, ngram: int = 5, n_perm: int = 128, bands: int = 16, seed: int = 0) -> Fingerprints:
+        """The fingerprints of packed tokens (tk_fingerprint): host arrays in -- `tokens` uint32[T], `tok_off` uint64[n + 1] --, a
+        `Fingerprints` out."""
+        self._one_device("fingerprint_packed")
+        tokens = np.ascontiguousarray(tokens, dtype=np.uint32)
+        tok_off = np.ascontiguousarray(tok_off, dtype=np.uint64)
+        if tok_off.ndim != 1 or tokens.ndim != 1 or len(tok_off) < 1 or int(tok_off[-1]) != len(tokens):
+            raise ValueError("tok_off must hold n + 1 offsets that end at len(tokens)")
+        spec = self._fp_spec(ngram, n_perm, bands, seed)
+        n = len(tok_off) - 1
+        out = self._fp_outs(n, spec)
+        rc = self._L.tk_fingerprint(self._h, tokens.ctypes.data if len(tokens) else None, tok_off.ctypes.data, n, ctypes.byref(spec), *[a.ctypes.data for a in out])
+        _lib.raise_for(rc)
+        return Fingerprints(*out, np.diff(tok_off))
+
+    @staticmethod
+    def _fp_outs(n: int, spec: "_lib.FingerprintSpec"):
+        """(sig, band, exact, n_shingles) for n documents, to be filled by the library (one spare element each: no empty array's pointer)"""
+        P, B = max(int(spec.n_perm), 1), max(int(spec.bands), 1)
+        return (np.zeros(n * P + 1, dtype=np.uint32)[:n * P].reshape(n, P), np.zeros(n * B + 1, dtype=np.uint64)[:n * B].reshape(n, B),
+                np.zeros(n + 1, dtype=np.uint64)[:n], np.zeros(n + 1, dtype=np.uint64)[:n])
+
+    def encode_batch_fingerprint_packed(self, blob: np.ndarray, doc_off: np.ndarray, allowed_special: AbstractSet[str] | None = None, *, disallowed_special=None,
+                                        ngram: int = 5, n_perm: int = 128, bands: int = 16, seed: int = 0) -> Fingerprints:
+        """`encode_batch_packed` with its result fingerprinted while the ids are on the device (tk_encode_batch_fingerprint): the ids stay
+        there, only the `Fingerprints` come back.  The special-token arguments as in `encode_batch_packed`."""
+        self._one_device("encode_batch_fingerprint_packed")
+        text, dis, n_docs, _keep = self._batch_args(blob, doc_off, allowed_special, disallowed_special)
+        spec = self._fp_spec(ngram, n_perm, bands, seed)
+        hit = _lib.SpecialHit()
+        out = self._fp_outs(n_docs, spec)
+        tok_off = np.zeros(n_docs + 1, dtype=np.uint64)
+        rc = self._L.tk_encode_batch_fingerprint(self._h, *text, *dis, ctypes.byref(spec), *[a.ctypes.data for a in out], tok_off.ctypes.data, None, None, ctypes.byref(hit))
+        self._raise_for(rc, hit)
+        return Fingerprints(*out, np.diff(tok_off))
 
     # ------------------------------------------------------------------ supervised samples (no reference counterpart: the host loop of its users)
     @staticmethod

@@ -345,6 +345,36 @@ class Encoding:
             err.line = line
             raise err
 
+    # ------------------------------------------------------------------ near-duplicate fingerprints
+    def fingerprint_ordinary_batch(self, text: Sequence[str], *, ngram: int = 5, n_perm: int = 128, bands: int = 16, seed: int = 0) -> "_tiktoken.Fingerprints":
+        """Near-duplicate fingerprints of a batch, ignoring special tokens: every text is encoded and, while its ids are on the GPU,
+        fingerprinted -- a MinHash signature of `n_perm` values over its shingles of `ngram` tokens, the LSH keys of the signature's `bands`,
+        an exact hash and the shingle count; the ids never come back.  Returns a `Fingerprints`, whose `exact_groups`, `duplicate_groups`
+        and `keep_mask` find the duplicates on the host.  The rule is stated in include/tiktoken_amd.h."""
+        blob, off = self._pack(text)
+        return self._core_bpe.encode_batch_fingerprint_packed(blob, off, None, ngram=ngram, n_perm=n_perm, bands=bands, seed=seed)
+
+    def fingerprint_batch(self, text: Sequence[str], *, ngram: int = 5, n_perm: int = 128, bands: int = 16, seed: int = 0,
+                          allowed_special: Literal["all"] | AbstractSet[str] = set(),  # noqa: B006
+                          disallowed_special: Literal["all"] | Collection[str] = "all") -> "_tiktoken.Fingerprints":
+        """`fingerprint_ordinary_batch` with the special-token arguments of `encode` -- the policy, and the error, of `encode_batch_packed`."""
+        fp = dict(ngram=ngram, n_perm=n_perm, bands=bands, seed=seed)
+        allowed_special, disallowed_special = self._special_policy(allowed_special, disallowed_special)
+        blob, off, repaired = self._pack_repaired(text)
+        if not disallowed_special:
+            return self._core_bpe.encode_batch_fingerprint_packed(blob, off, allowed_special, **fp)
+        if not isinstance(disallowed_special, frozenset):
+            disallowed_special = frozenset(disallowed_special)
+        if repaired or not all(t in self._special_tokens for t in disallowed_special):  # (as encode_batch_packed: the host's search)
+            for t in text:
+                self._reject_disallowed(t, disallowed_special)
+            return self._core_bpe.encode_batch_fingerprint_packed(blob, off, allowed_special, **fp)
+        return self._core_bpe.encode_batch_fingerprint_packed(blob, off, allowed_special, disallowed_special=disallowed_special, **fp)
+
+    def fingerprint_tokens_packed(self, tokens, tok_off, *, ngram: int = 5, n_perm: int = 128, bands: int = 16, seed: int = 0) -> "_tiktoken.Fingerprints":
+        """The fingerprints of tokens that are packed already (`tokens` uint32[T], `tok_off` uint64[n + 1], e.g. `encode_batch_packed`'s)."""
+        return self._core_bpe.fingerprint_packed(tokens, tok_off, ngram=ngram, n_perm=n_perm, bands=bands, seed=seed)
+
     def split_ordinary_batch_packed(self, text: Sequence[str], max_tokens: int, *, min_tokens: int | None = None, overlap: int = 0,
                                     separators=_tiktoken.DEFAULT_SEPARATORS, seg_tokens: int = 0) -> "_tiktoken.TextChunks":
         """A batch cut into chunks of at most `max_tokens` tokens, ignoring special tokens: every text is encoded and cut, each cut at the

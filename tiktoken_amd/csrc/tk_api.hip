@@ -30,6 +30,7 @@
 #include "tk_stream.h"
 #include "tk_padded.h"
 #include "tk_split.h"
+#include "tk_fingerprint.h"
 #include "tk_jsonl.h"
 #include "tk_sample_rows.h"
 #include "tk_samples.h"
@@ -293,6 +294,11 @@ struct tk_core {
     // succeeded; d_jsonl_work: the report words, the tiles' summaries and entry states, the escaped plane, the tiles' counts; d_jsonl_lines:
     // everything per line and per block of lines -- what a call computes until it is accepted; d_jsonl_in: the bytes of a host call.
     Buf d_jsonl, d_jsonl_work, d_jsonl_lines, d_jsonl_in;
+    // Fingerprints (tk_fingerprint.h), apart from everything above: d_fp: the signatures of a call whose caller wants band keys without
+    // them, and the four result arrays of the host entries; d_fp_in: tokens and tok_off of a host call.
+    // fp_done: recorded behind every call that has used d_fp, on that call's stream; the next such call's stream waits for it first.
+    Buf d_fp, d_fp_in;
+    Event fp_done;
     uint64_t st_split[TK_SPLIT_STATS] = {0, 0, 0, 0};
     // Supervised samples (tk_samples.h), apart from everything above: d_smp: ids, labels and mask of every position; d_smp_row: full_len, len,
     // n_trained of every sample; d_smp_cnt: the TK_SMP_WORDS report words, the role table, pstart and the per-sample figures a call counts in
@@ -3357,6 +3363,129 @@ extern "C" int tk_encode_jsonl(tk_core* c, const uint8_t* bytes, uint64_t n_byte
 }
 
 // ------------------------------------------------------------------------------------------
+// Fingerprints (tk_fingerprint.h): a packed batch on the device -> MinHash signatures, LSH band keys, exact hashes, shingle counts.
+// ------------------------------------------------------------------------------------------
+struct FpOuts {  // the caller's arrays (device memory for fp_run, host memory for fp_to_host); any may be null
+    uint32_t* sig;
+    uint64_t *band, *exact, *n_shingles;
+};
+static int fp_shape(const tk_fingerprint_spec* spec, uint64_t n, uint64_t n_docs, TkFp* p) {
+    switch (tk_fp_shape(spec->ngram, spec->n_perm, spec->bands, spec->seed, n, n_docs, p)) {
+        case 0: return TK_OK;
+        case 1: return fail(TK_VALUE_ERROR, "ngram must be 1 .. 32");
+        case 2: return fail(TK_VALUE_ERROR, "n_perm must be 1 .. 256");
+        default: return fail(TK_VALUE_ERROR, "bands must be 1 .. n_perm and divide n_perm");
+    }
+}
+// What of a tk_fingerprint_spec can be refused without looking at the batch (the host-text entry asks before it encodes anything).
+static int fp_check_spec(const tk_fingerprint_spec* spec) {
+    if (!spec) return fail(TK_VALUE_ERROR, "null argument");
+    TkFp p;
+    return fp_shape(spec, 0, 0, &p);
+}
+// fp_run: the caller holds c->mu.  Three launches on s, and no wait of the host: the results are there when the stream has got to them.
+// in_core: the outputs lie in c->d_fp.  A call that uses c->d_fp -- that, or band keys without signatures -- may follow one that is still
+// running on another stream: its stream waits for that call's event first.
+static int fp_run(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n, const uint64_t* d_tok_off, uint64_t n_docs, const tk_fingerprint_spec* spec, FpOuts o,
+                  bool in_core = false) {
+    TkFp p;
+    TRY(fp_shape(spec, n, n_docs, &p));
+    if (n >= (1ull << 41)) return fail(TK_VALUE_ERROR, "n_tokens: 2^41 tokens or more");
+    if (!n_docs || !(o.sig || o.band || o.exact || o.n_shingles)) return TK_OK;
+    const bool core_buf = in_core || (o.band && !o.sig);
+    if (core_buf) {
+        if (!c->fp_done.e) HIPCHK(c->fp_done.create());
+        HIPCHK(hipStreamWaitEvent(s, c->fp_done, 0));  // (an event nothing has recorded yet holds nobody up)
+    }
+    if (o.band && !o.sig) {  // (the band keys are made from the signatures)
+        TRY(ensure(c->d_fp, n_docs * p.P * 4));
+        o.sig = c->d_fp.as<uint32_t>();
+    }
+    const TkFpOut out{o.sig, (unsigned long long*)o.exact, (unsigned long long*)o.n_shingles};
+    TRY(timed(c, s, "tk_k_fp_fill", [&] { hipLaunchKernelGGL(tk_k_fp_fill, dim3(grid_for(n_docs * (o.sig ? p.P : 1), 256, 65536)), dim3(256), 0, s, p, out); }));
+    if (n)
+        TRY(timed(c, s, "tk_k_fp_tile", [&] {
+            hipLaunchKernelGGL(tk_k_fp_tile, dim3((uint32_t)((n + TK_FP_TILE - 1) / TK_FP_TILE)), dim3(TK_FP_THREADS), 0, s, p, d_tok, d_tok_off, out);
+        }));
+    if (o.band || o.exact)
+        TRY(timed(c, s, "tk_k_fp_finish", [&] {
+            hipLaunchKernelGGL(tk_k_fp_finish, dim3(grid_for(n_docs * p.B, 256, 65536)), dim3(256), 0, s, p, d_tok_off, o.sig, o.band, o.exact);
+        }));
+    if (core_buf) HIPCHK(hipEventRecord(c->fp_done, s));
+    return TK_OK;
+}
+// fp_run into buffers of the core, then every array the caller asked for to the host (the caller holds c->mu; the stream is waited for)
+static int fp_to_host(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n, const uint64_t* d_tok_off, uint64_t n_docs, const tk_fingerprint_spec* spec, FpOuts h) {
+    TkFp p;
+    TRY(fp_shape(spec, n, n_docs, &p));
+    Carve res;
+    const uint64_t at_sig = res.add(n_docs * p.P * 4), at_band = res.add(n_docs * p.B * 8), at_exact = res.add(n_docs * 8), at_nsh = res.add(n_docs * 8);
+    TRY(ensure(c->d_fp, res.total + 16));
+    const FpOuts d{h.sig || h.band ? carved<uint32_t>(c->d_fp, at_sig) : nullptr, h.band ? carved<uint64_t>(c->d_fp, at_band) : nullptr,
+                   h.exact ? carved<uint64_t>(c->d_fp, at_exact) : nullptr, h.n_shingles ? carved<uint64_t>(c->d_fp, at_nsh) : nullptr};
+    TRY(fp_run(c, s, d_tok, n, d_tok_off, n_docs, spec, d, /* in_core */ true));
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    if (!n_docs) return TK_OK;
+    if (h.sig) HIPCHK(hipMemcpy(h.sig, d.sig, n_docs * p.P * 4, hipMemcpyDeviceToHost));
+    if (h.band) HIPCHK(hipMemcpy(h.band, d.band, n_docs * p.B * 8, hipMemcpyDeviceToHost));
+    if (h.exact) HIPCHK(hipMemcpy(h.exact, d.exact, n_docs * 8, hipMemcpyDeviceToHost));
+    if (h.n_shingles) HIPCHK(hipMemcpy(h.n_shingles, d.n_shingles, n_docs * 8, hipMemcpyDeviceToHost));
+    return TK_OK;
+}
+
+extern "C" int tk_fingerprint_device(tk_core* c, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_docs, const tk_fingerprint_spec* spec, void* stream,
+                                     uint32_t* d_sig, uint64_t* d_band, uint64_t* d_exact, uint64_t* d_n_shingles) {
+    // This entry does not wait, so its stream must be one the caller can wait on: `stream` as it is, null being HIP's null stream (not
+    // the core's own stream, which device_pass hands to the entries that wait before they return).
+    return device_pass(c, d_tok_off && (d_tokens || !n_tokens) && spec, stream, [&](hipStream_t) {
+        return fp_run(c, (hipStream_t)stream, (const uint32_t*)d_tokens, n_tokens, (const uint64_t*)d_tok_off, n_docs, spec, FpOuts{d_sig, d_band, d_exact, d_n_shingles});
+    });
+}
+
+extern "C" int tk_fingerprint(tk_core* c, const uint32_t* tokens, const uint64_t* tok_off, uint64_t n_docs, const tk_fingerprint_spec* spec, uint32_t* sig_out,
+                              uint64_t* band_out, uint64_t* exact_out, uint64_t* n_shingles_out) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if (!tok_off || !spec) return fail(TK_VALUE_ERROR, "null argument");
+    TRY(fp_check_spec(spec));
+    TRY(check_offsets(tok_off, n_docs, "tok_off"));
+    const uint64_t n = tok_off[n_docs];
+    if (n && !tokens) return fail(TK_VALUE_ERROR, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    Carve in;
+    const uint64_t at_off = in.add((n_docs + 1) * 8), at_tok = in.add(n * 4);
+    TRY(ensure(c->d_fp_in, in.total + 16));
+    uint64_t* d_off = carved<uint64_t>(c->d_fp_in, at_off);
+    uint32_t* d_tok = carved<uint32_t>(c->d_fp_in, at_tok);
+    HIPCHK(hipMemcpyAsync(d_off, tok_off, (n_docs + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    if (n) HIPCHK(hipMemcpyAsync(d_tok, tokens, n * 4, hipMemcpyHostToDevice, c->stream));
+    return drained(c, [&] { return fp_to_host(c, c->stream, d_tok, n, d_off, n_docs, spec, FpOuts{sig_out, band_out, exact_out, n_shingles_out}); });
+}
+
+// tk_encode_batch (tk_encode_batch_checked with disallowed ids) with the fingerprints of the ids it has just produced: the passes run over
+// the ids while they are on the device; the ids travel back only when tokens_out is there.
+extern "C" int tk_encode_batch_fingerprint(tk_core* c, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special, const uint32_t* allowed_ids,
+                                           uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed, const tk_fingerprint_spec* spec, uint32_t* sig_out,
+                                           uint64_t* band_out, uint64_t* exact_out, uint64_t* n_shingles_out, uint64_t* tok_off_out, uint32_t** tokens_out,
+                                           uint64_t* n_tokens_out, tk_special_hit* hit) {
+    return encode_batch_pass(
+        c, utf8, doc_off, n_docs, use_special, allowed_ids, n_allowed, disallowed_ids, n_disallowed, hit, spec && (!tokens_out || n_tokens_out),
+        [&] { return fp_check_spec(spec); },  // (before the encode, not after it)
+        [&](uint64_t n) {
+            return fp_to_host(c, c->stream, c->out_tokens.as<uint32_t>(), n, c->out_tok_off.as<uint64_t>(), n_docs, spec, FpOuts{sig_out, band_out, exact_out, n_shingles_out});
+        },
+        [&](uint64_t n) -> int {
+            ResultBag bag;
+            if (tokens_out) TRY(bag.fetch(tokens_out, c->out_tokens.p, n));
+            if (tok_off_out) HIPCHK(hipMemcpy(tok_off_out, c->out_tok_off.p, (n_docs + 1) * 8, hipMemcpyDeviceToHost));
+            bag.give();
+            if (n_tokens_out) *n_tokens_out = n;
+            return TK_OK;
+        });
+}
+
+// ------------------------------------------------------------------------------------------
 // Supervised samples (tk_samples.h): a packed batch of parts on the device -> one row per sample, ids, mask and labels as [R, W].
 // ------------------------------------------------------------------------------------------
 static_assert(TK_SMP_KEEP_TAIL == TK_SMPF_KEEP_TAIL && TK_SMP_LEFT == TK_SMPF_LEFT, "tk_smp_spec flags");
@@ -5223,6 +5352,7 @@ extern "C" uint64_t tk_stat(tk_core* c, const char* name) {
     if (k == "split_joined") return c->st_split[TK_SPLIT_ST_JOINED];          // ... blocks in which the true chain met the speculative walk
     if (k == "split_stitch_steps") return c->st_split[TK_SPLIT_ST_STITCH];    // ... steps of the stitch pass (one wavefront per document, in order)
     if (k == "split_spec_steps") return c->st_split[TK_SPLIT_ST_SPEC];        // ... steps of the speculative walks
+    if (k == "fingerprint_tile") return TK_FP_TILE;  // token positions of a tile of the fingerprint pass (tk_fingerprint_rule.h)
     if (k == "jsonl_tile") return TK_JSONL_TILE;  // bytes of a tile of the JSON Lines passes (tk_jsonl_rule.h)
     if (k == "regrown") return c->st_regrown;  // batches repeated with a larger miss data since the core was made (encode_device_locked)
     if (k == "workspace_bytes") {             // device memory of the work sets (everything but the text, the tables and the outputs)
