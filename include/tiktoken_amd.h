@@ -398,8 +398,8 @@ int tk_encode_jsonl(tk_core* core, const uint8_t* bytes, uint64_t n_bytes, const
  *   the last x.  It is defined for empty documents too; consumers skip documents with n_shingles == 0.
  *  exact[d] = mix(L ^ sum over i < L of mix(seed ^ ((i + 1) << 32) ^ t[s + i])): the position makes it depend on the order.
  *  Minimum and sum are commutative: the result is a function of (tokens, tok_off, spec) alone.
- * NOT built: shingles of the text's words or chars; grouping on the device; an index across batches; several GPUs; b-bit signatures;
- *  entries fed from JSON Lines or from chunks. */
+ * NOT built: shingles of the text's words or chars; an index across batches; several GPUs; b-bit signatures; entries fed from JSON
+ *  Lines or from chunks.  (Grouping on the device: tk_fingerprint_groups_device, below.) */
 typedef struct {
     uint32_t ngram, n_perm, bands;
     uint64_t seed;
@@ -426,6 +426,53 @@ int tk_encode_batch_fingerprint(tk_core* core, const uint8_t* utf8, const uint64
                                 uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed, const tk_fingerprint_spec* spec, uint32_t* sig_out,
                                 uint64_t* band_out, uint64_t* exact_out, uint64_t* n_shingles_out, uint64_t* tok_off_out, uint32_t** tokens_out,
                                 uint64_t* n_tokens_out, tk_special_hit* hit);
+/* Near-duplicate groups: the fingerprints of a batch -> per document the lowest index of its group, a keep mask, the number kept.  What
+ * Fingerprints.duplicate_groups does on the host, value for value, on arrays that are on the device anyway.
+ * The rule.  Input: sig uint32[n * P], band uint64[n * B], n_shingles uint64[n] -- what tk_fingerprint_device writes --, P, B and
+ * min_match, a uint32.
+ *  Document d is live when n_shingles[d] > 0.
+ *  For a live d and a band j (0 <= j < B), rep_j(d) is the lowest live document e with band[e][j] == band[d][j].  Every value of a key
+ *   is an ordinary one: no key is reserved.
+ *  There is an edge d -- rep_j(d) when rep_j(d) != d and the number of positions p (0 <= p < P) with sig[d][p] == sig[rep_j(d)][p] is
+ *   >= min_match.  min_match == 0: every document is joined to the lowest of each of its keys; min_match > P: there is no edge.
+ *  group[d] (uint32): the lowest index in d's connected component; a document that is not live is its own group.
+ *  keep[d] (uint8): 1 when group[d] == d, else 0.  n_kept (uint64): how many documents are kept.
+ *  The edges depend on the inputs alone, and the components of a graph do not depend on the order in which its edges are joined: the
+ *   result is a function of (sig, band, n_shingles, P, B, min_match) alone, whatever the schedule.
+ *  The entries take the integer min_match and no float.  For a threshold t, as Fingerprints.duplicate_groups compares count / P >= t in
+ *   double precision, min_match is the least c in 0 .. P + 1 with c / P >= t -- P + 1 when there is none (t above 1, or NaN).
+ *  Refused with TK_VALUE_ERROR, and nothing written: P outside 1 .. 256; B outside 1 .. P; P % B != 0; n >= 2^32 - 1.  n == 0 is valid.
+ * NOT built: exact-hash grouping on the device (Fingerprints.exact_groups stays on the host); an index across batches; several GPUs;
+ *  comparing a document with more than the lowest document of a key.
+ * Device pointers in, the caller's device arrays out, any of which may be null: d_group uint32[n_docs], d_keep uint8[n_docs], d_n_kept one
+ * uint64.  Stream and waiting as tk_fingerprint_device: everything is queued on `stream`, null being HIP's null stream, and the call
+ * returns without waiting.  The forest and the claim table (4 n bytes, and at most 256 MiB of table -- bands go in rounds over it --
+ * unless one band alone needs more: 4 bytes for each of the power of two >= 2 n slots) lie in a buffer of the core; the library orders
+ * the calls that use it among themselves on the device (an event, no host wait). */
+int tk_fingerprint_groups_device(tk_core* core, const uint32_t* d_sig, const uint64_t* d_band, const uint64_t* d_n_shingles, uint64_t n_docs, uint32_t n_perm,
+                                 uint32_t bands, uint32_t min_match, void* stream, uint32_t* d_group, uint8_t* d_keep, uint64_t* d_n_kept);
+/* The same from host arrays to the caller's host arrays (any output may be null). */
+int tk_fingerprint_groups(tk_core* core, const uint32_t* sig, const uint64_t* band, const uint64_t* n_shingles, uint64_t n_docs, uint32_t n_perm, uint32_t bands,
+                          uint32_t min_match, uint32_t* group_out, uint8_t* keep_out, uint64_t* n_kept_out);
+/* The kept documents of a packed batch, packed in their order: d_tokens uint32[n_tokens], d_tok_off uint64[n_docs + 1], d_keep
+ * uint8[n_docs] (nonzero: keep; any mask, not only a dedup's) in; out: d_tokens_out, sized n_tokens by the caller, of which the kept
+ * tokens are written; d_tok_off_out uint64[n_docs + 1], of which the first n_kept + 1 entries are written; d_doc_out uint32[n_docs], the
+ * source index of every kept document (n_kept entries); d_counts_out uint64[2] = (n_kept, tokens kept).  All are required (the token
+ * arrays when n_tokens != 0, d_keep and d_doc_out when n_docs != 0).  Not in place: d_tokens_out == d_tokens or d_tok_off_out ==
+ * d_tok_off is TK_VALUE_ERROR, as is n_docs >= 2^32 - 1.  Stream and waiting as above; d_tok_off is not checked, as in
+ * tk_fingerprint_device: one that does not ascend from 0 to n_tokens gives values nobody has defined, never an access outside the arrays. */
+int tk_select_docs_device(tk_core* core, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_docs, const uint8_t* d_keep, void* stream,
+                          uint32_t* d_tokens_out, uint64_t* d_tok_off_out, uint32_t* d_doc_out, uint64_t* d_counts_out);
+/* Fingerprints (spec), groups (min_match) and selection over host ids, in one call and with one wait: the survivors come back --
+ * tokens_out (*n_tokens_out ids), tok_off_out uint64[*n_kept_out + 1], doc_out uint32[*n_kept_out], library-owned (tk_free) -- and
+ * group_out, the caller's uint32[n_docs] (may be null), over all documents. */
+int tk_dedup_tokens(tk_core* core, const uint32_t* tokens, const uint64_t* tok_off, uint64_t n_docs, const tk_fingerprint_spec* spec, uint32_t min_match,
+                    uint32_t** tokens_out, uint64_t* n_tokens_out, uint64_t** tok_off_out, uint32_t** doc_out, uint64_t* n_kept_out, uint32_t* group_out);
+/* tk_encode_batch -- with n_disallowed != 0: tk_encode_batch_checked -- and the same three passes over the ids while they are on the
+ * device: only the survivors' ids leave it.  On TK_DISALLOWED_SPECIAL nothing is handed out. */
+int tk_encode_batch_dedup(tk_core* core, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special, const uint32_t* allowed_ids, uint64_t n_allowed,
+                          const uint32_t* disallowed_ids, uint64_t n_disallowed, const tk_fingerprint_spec* spec, uint32_t min_match, uint32_t** tokens_out,
+                          uint64_t* n_tokens_out, uint64_t** tok_off_out, uint32_t** doc_out, uint64_t* n_kept_out, uint32_t* group_out, tk_special_hit* hit);
 /* Supervised samples: a packed batch whose documents are the PARTS of samples -- the messages of a conversation, a prompt and its answer --
  * -> one row per sample with the template's ids around every part, an attention mask and labels.  Replaces nothing in the reference: it is
  * the host loop of the reference's users, the fine-tuning script that calls encode_ordinary once per message, adds header and footer ids and

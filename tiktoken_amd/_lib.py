@@ -173,6 +173,17 @@ def lib() -> ctypes.CDLL:
             L.tk_fingerprint.argtypes = [vp, vp, vp, u64, P(FingerprintSpec), vp, vp, vp, vp]
             L.tk_encode_batch_fingerprint.restype = i32
             L.tk_encode_batch_fingerprint.argtypes = [vp, vp, vp, u64, i32, vp, u64, vp, u64, P(FingerprintSpec), vp, vp, vp, vp, vp, P(vp), P(u64), P(SpecialHit)]
+        if hasattr(L, "tk_fingerprint_groups_device"):  # (absent from older builds selected through $TIKTOKEN_AMD_LIB)
+            L.tk_fingerprint_groups_device.restype = i32
+            L.tk_fingerprint_groups_device.argtypes = [vp, vp, vp, vp, u64, u32, u32, u32, vp, vp, vp, vp]
+            L.tk_fingerprint_groups.restype = i32
+            L.tk_fingerprint_groups.argtypes = [vp, vp, vp, vp, u64, u32, u32, u32, vp, vp, vp]
+            L.tk_select_docs_device.restype = i32
+            L.tk_select_docs_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, vp, vp, vp]
+            L.tk_dedup_tokens.restype = i32
+            L.tk_dedup_tokens.argtypes = [vp, vp, vp, u64, P(FingerprintSpec), u32, P(vp), P(u64), P(vp), P(vp), P(u64), vp]
+            L.tk_encode_batch_dedup.restype = i32
+            L.tk_encode_batch_dedup.argtypes = [vp, vp, vp, u64, i32, vp, u64, vp, u64, P(FingerprintSpec), u32, P(vp), P(u64), P(vp), P(vp), P(u64), vp, P(SpecialHit)]
         if hasattr(L, "tk_jsonl_extract_device"):  # (absent from older builds selected through $TIKTOKEN_AMD_LIB)
             L.tk_jsonl_extract_device.restype = i32
             L.tk_jsonl_extract_device.argtypes = [vp, vp, u64, vp, u64, u32, vp, *[P(vp)] * 5, *[P(u64)] * 3, P(JsonlBad)]

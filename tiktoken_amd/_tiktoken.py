@@ -706,6 +706,25 @@ class Fingerprints(NamedTuple):
         return self.duplicate_groups(threshold) == np.arange(len(self.exact))
 
 
+def min_match(threshold: float, n_perm: int) -> int:
+    """The `min_match` of the groups entries (include/tiktoken_amd.h) for a threshold: the least c in 0 .. P + 1 with c / P >= threshold in
+    float64 -- the comparison `Fingerprints.duplicate_groups` makes; P + 1 when no count reaches it (a threshold above 1, or NaN)."""
+    P, t = int(n_perm), float(threshold)
+    if P < 1:
+        return 0  # (the library refuses such a P)
+    return next((c for c in range(P + 1) if c / P >= t), P + 1)
+
+
+class DedupedBatch(NamedTuple):
+    """A batch without its near-duplicates (tk_dedup_tokens, tk_encode_batch_dedup): `tokens` uint32 and `tok_off` uint64[n_kept + 1] the
+    kept documents, packed in their order; `doc` int64[n_kept] the input index of each; `group` int64[n], over ALL input documents, the
+    lowest index of every document's group -- what `Fingerprints.duplicate_groups` gives; a document is kept when it is its group's."""
+    tokens: np.ndarray
+    tok_off: np.ndarray
+    doc: np.ndarray
+    group: np.ndarray
+
+
 class DisallowedSpecialError(ValueError):
     """A batch holds a disallowed special token: the first occurrence -- document `doc`, byte offset `pos` inside it, the `token` (the
     longest disallowed one that matches there).  What the reference raises as a plain ValueError, with its message."""
@@ -1706,6 +1725,104 @@ class CoreBPE:
         rc = self._L.tk_encode_batch_fingerprint(self._h, *text, *dis, ctypes.byref(spec), *[a.ctypes.data for a in out], tok_off.ctypes.data, None, None, ctypes.byref(hit))
         self._raise_for(rc, hit)
         return Fingerprints(*out, np.diff(tok_off))
+
+    # ------------------------------------------------------------------ near-duplicate groups and the selection of the kept documents
+    def _on_gpu(self, named, stream):
+        """The tensors of a device entry checked -- (name, tensor or None, element size, count) each -- and the stream's handle."""
+        import torch
+
+        for name, t, size, count in named:
+            if t is None:
+                continue
+            if not t.is_cuda or t.device.index != self.device or not t.is_contiguous() or t.element_size() != size or t.numel() != count:
+                raise ValueError(f"{name} must be a contiguous tensor of {count} elements of {size} bytes on this core's GPU")
+        return torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream if stream is None else stream
+
+    def fingerprint_groups_device(self, sig, band, n_shingles, threshold: float = 0.8, *, group=None, keep=None, n_kept=None, stream: int | None = None) -> None:
+        """Near-duplicate groups of fingerprints that are on the device (tk_fingerprint_groups_device): torch tensors on this core's GPU,
+        taken by pointer -- `sig` (32-bit, [n, P]), `band` (64-bit, [n, B]) and `n_shingles` (64-bit, n), as `fingerprint_device` wrote
+        them, in; the caller's tensors out, any of which may be None: `group` (32-bit, n: the lowest index of every document's group),
+        `keep` (8-bit, n: 1 for a group's lowest document) and `n_kept` (64-bit, 1).  What `Fingerprints.duplicate_groups(threshold)`
+        gives.  Stream and waiting as in `fingerprint_device`: queued on `stream`, and the call does not wait."""
+        self._one_device("fingerprint_groups_device")
+        if sig.dim() != 2 or band.dim() != 2 or band.shape[0] != sig.shape[0]:
+            raise ValueError("sig must be [n, n_perm] and band [n, bands]")
+        n, P, B = int(sig.shape[0]), int(sig.shape[1]), int(band.shape[1])
+        stream = self._on_gpu((("sig", sig, 4, n * P), ("band", band, 8, n * B), ("n_shingles", n_shingles, 8, n), ("group", group, 4, n), ("keep", keep, 1, n),
+                               ("n_kept", n_kept, 8, 1)), stream)
+        ptr = [t.data_ptr() if t is not None and t.numel() else None for t in (sig, band, n_shingles)]
+        outs = [t.data_ptr() if t is not None and t.numel() else None for t in (group, keep, n_kept)]
+        _lib.raise_for(self._L.tk_fingerprint_groups_device(self._h, *ptr, n, P, B, min_match(threshold, P), stream or None, *outs))
+
+    def fingerprint_groups_packed(self, fp: Fingerprints, threshold: float = 0.8) -> tuple[np.ndarray, np.ndarray]:
+        """(group int64[n], keep bool[n]) of a `Fingerprints` (tk_fingerprint_groups): `fp.duplicate_groups(threshold)` and
+        `fp.keep_mask(threshold)`, computed on the GPU."""
+        self._one_device("fingerprint_groups_packed")
+        sig, band = np.ascontiguousarray(fp.sig, dtype=np.uint32), np.ascontiguousarray(fp.band, dtype=np.uint64)
+        nsh = np.ascontiguousarray(fp.n_shingles, dtype=np.uint64)
+        if sig.ndim != 2 or band.ndim != 2 or nsh.ndim != 1 or not len(sig) == len(band) == len(nsh):
+            raise ValueError("sig must be [n, n_perm], band [n, bands] and n_shingles [n]")
+        n = len(nsh)
+        group, keep = np.zeros(n + 1, dtype=np.uint32)[:n], np.zeros(n + 1, dtype=np.uint8)[:n]
+        rc = self._L.tk_fingerprint_groups(self._h, sig.ctypes.data if n else None, band.ctypes.data if n else None, nsh.ctypes.data if n else None, n, sig.shape[1],
+                                           band.shape[1], min_match(threshold, sig.shape[1]), group.ctypes.data, keep.ctypes.data, None)
+        _lib.raise_for(rc)
+        return group.astype(np.int64), keep.astype(bool)
+
+    def select_docs_device(self, tokens, tok_off, keep, *, tokens_out, tok_off_out, doc_out, counts_out, stream: int | None = None) -> None:
+        """The kept documents of a packed batch that is on the device, packed in their order (tk_select_docs_device): torch tensors on
+        this core's GPU, taken by pointer -- `tokens` (32-bit, T), `tok_off` (64-bit, n + 1) and `keep` (8-bit, n; nonzero: keep) in;
+        `tokens_out` (32-bit, T), `tok_off_out` (64-bit, n + 1), `doc_out` (32-bit, n: the source index of every kept document) and
+        `counts_out` (64-bit, 2: documents kept, tokens kept) out.  Of the first three as much is written as is kept.  Not in place.
+        Stream and waiting as in `fingerprint_device`."""
+        self._one_device("select_docs_device")
+        n, T = tok_off.numel() - 1, tokens.numel()
+        if n < 0:
+            raise ValueError("tok_off must hold n_docs + 1 entries")
+        stream = self._on_gpu((("tokens", tokens, 4, T), ("tok_off", tok_off, 8, n + 1), ("keep", keep, 1, n), ("tokens_out", tokens_out, 4, T),
+                               ("tok_off_out", tok_off_out, 8, n + 1), ("doc_out", doc_out, 4, n), ("counts_out", counts_out, 8, 2)), stream)
+        for name, t in (("tokens_out", tokens_out), ("tok_off_out", tok_off_out), ("doc_out", doc_out), ("counts_out", counts_out)):
+            if t is None:
+                raise ValueError(f"{name} is required")
+        p = [t.data_ptr() if t.numel() else None for t in (tokens, tok_off, keep, tokens_out, tok_off_out, doc_out, counts_out)]
+        _lib.raise_for(self._L.tk_select_docs_device(self._h, p[0], T, p[1], n, p[2], stream or None, *p[3:]))
+
+    def _deduped(self, call, n_docs: int) -> "DedupedBatch":
+        """call(the result pointers of tk_dedup_tokens / tk_encode_batch_dedup) -> rc; the survivors as a DedupedBatch"""
+        out, cnt = [ctypes.c_void_p() for _ in range(3)], [ctypes.c_uint64() for _ in range(2)]
+        group = np.zeros(n_docs + 1, dtype=np.uint32)[:n_docs]
+        call(ctypes.byref(out[0]), ctypes.byref(cnt[0]), ctypes.byref(out[1]), ctypes.byref(out[2]), ctypes.byref(cnt[1]), group.ctypes.data)
+        n_tok, n_kept = int(cnt[0].value), int(cnt[1].value)
+        return DedupedBatch(_take_u32(out[0], n_tok), _take_u64(out[1], n_kept + 1), _take_u32(out[2], n_kept).astype(np.int64), group.astype(np.int64))
+
+    def dedup_packed(self, tokens: np.ndarray, tok_off: np.ndarray, threshold: float = 0.8, *, ngram: int = 5, n_perm: int = 128, bands: int = 16,
+                     seed: int = 0) -> "DedupedBatch":
+        """Packed tokens without their near-duplicates (tk_dedup_tokens): fingerprints, groups and selection on the GPU, one wait."""
+        self._one_device("dedup_packed")
+        tokens = np.ascontiguousarray(tokens, dtype=np.uint32)
+        tok_off = np.ascontiguousarray(tok_off, dtype=np.uint64)
+        if tok_off.ndim != 1 or tokens.ndim != 1 or len(tok_off) < 1 or int(tok_off[-1]) != len(tokens):
+            raise ValueError("tok_off must hold n + 1 offsets that end at len(tokens)")
+        spec = self._fp_spec(ngram, n_perm, bands, seed)
+        n = len(tok_off) - 1
+
+        def call(*res):
+            _lib.raise_for(self._L.tk_dedup_tokens(self._h, tokens.ctypes.data if len(tokens) else None, tok_off.ctypes.data, n, ctypes.byref(spec),
+                                                   min_match(threshold, spec.n_perm), *res))
+        return self._deduped(call, n)
+
+    def encode_batch_dedup_packed(self, blob: np.ndarray, doc_off: np.ndarray, allowed_special: AbstractSet[str] | None = None, *, disallowed_special=None,
+                                  threshold: float = 0.8, ngram: int = 5, n_perm: int = 128, bands: int = 16, seed: int = 0) -> "DedupedBatch":
+        """`encode_batch_packed` without the near-duplicates (tk_encode_batch_dedup): the ids are fingerprinted, grouped and selected while
+        they are on the device, and only the survivors' come back.  The special-token arguments as in `encode_batch_packed`."""
+        self._one_device("encode_batch_dedup_packed")
+        text, dis, n_docs, _keep = self._batch_args(blob, doc_off, allowed_special, disallowed_special)
+        spec = self._fp_spec(ngram, n_perm, bands, seed)
+        hit = _lib.SpecialHit()
+
+        def call(*res):
+            self._raise_for(self._L.tk_encode_batch_dedup(self._h, *text, *dis, ctypes.byref(spec), min_match(threshold, spec.n_perm), *res, ctypes.byref(hit)), hit)
+        return self._deduped(call, n_docs)
 
     # ------------------------------------------------------------------ supervised samples (no reference counterpart: the host loop of its users)
     @staticmethod

@@ -31,6 +31,7 @@
 #include "tk_padded.h"
 #include "tk_split.h"
 #include "tk_fingerprint.h"
+#include "tk_groups.h"
 #include "tk_jsonl.h"
 #include "tk_sample_rows.h"
 #include "tk_samples.h"
@@ -299,6 +300,11 @@ struct tk_core {
     // fp_done: recorded behind every call that has used d_fp, on that call's stream; the next such call's stream waits for it first.
     Buf d_fp, d_fp_in;
     Event fp_done;
+    // Groups and selection (tk_groups.h), apart from everything above: d_grp: parent and the claim table of a groups call, grp_done its
+    // event -- as d_fp and fp_done; d_sel: the two per-workgroup arrays of a selection, sel_done its event; d_grp_in: the arrays of a
+    // host groups call; d_dedup: everything between the ids and the survivors of a host dedup call (it waits before it returns).
+    Buf d_grp, d_sel, d_grp_in, d_dedup;
+    Event grp_done, sel_done;
     uint64_t st_split[TK_SPLIT_STATS] = {0, 0, 0, 0};
     // Supervised samples (tk_samples.h), apart from everything above: d_smp: ids, labels and mask of every position; d_smp_row: full_len, len,
     // n_trained of every sample; d_smp_cnt: the TK_SMP_WORDS report words, the role table, pstart and the per-sample figures a call counts in
@@ -3486,6 +3492,226 @@ extern "C" int tk_encode_batch_fingerprint(tk_core* c, const uint8_t* utf8, cons
 }
 
 // ------------------------------------------------------------------------------------------
+// Groups and selection (tk_groups.h): fingerprints on the device -> group, keep mask and count; a packed batch and a keep mask -> the
+// kept documents, packed.  Neither waits: like fp_run they queue on the stream they are given.
+// ------------------------------------------------------------------------------------------
+struct GrpOuts {  // the caller's device arrays; any may be null
+    uint32_t* group;
+    uint8_t* keep;
+    uint64_t* n_kept;
+};
+static int grp_shape(uint64_t n, uint32_t P, uint32_t B, uint32_t min_match, TkGrp* g) {
+    switch (tk_grp_shape(n, P, B, min_match, g)) {
+        case 0: return TK_OK;
+        case 2: return fail(TK_VALUE_ERROR, "n_perm must be 1 .. 256");
+        case 3: return fail(TK_VALUE_ERROR, "bands must be 1 .. n_perm and divide n_perm");
+        default: return fail(TK_VALUE_ERROR, "n_docs: 2^32 - 1 documents or more (document indices are 32-bit)");
+    }
+}
+// grp_run: the caller holds c->mu.  parent and the claim table lie in c->d_grp: the stream waits for the event of the call that used
+// it last and records its own behind the last launch.  The bands go in rounds of g.per_round over a table of at most
+// TK_GRP_TABLE_BYTES (one region at least): clear, claim, join per round; the forest carries over.  min_match > P: nothing can join,
+// and no table is made.
+static int grp_run(tk_core* c, hipStream_t s, const uint32_t* d_sig, const uint64_t* d_band, const uint64_t* d_nsh, uint64_t n, uint32_t P, uint32_t B, uint32_t min_match,
+                   GrpOuts o) {
+    TkGrp g;
+    TRY(grp_shape(n, P, B, min_match, &g));
+    if (!(o.group || o.keep || o.n_kept)) return TK_OK;
+    unsigned long long* n_kept = (unsigned long long*)o.n_kept;
+    if (!n) {
+        if (n_kept) TRY(timed(c, s, "tk_k_grp_clear", [&] { hipLaunchKernelGGL(tk_k_grp_clear, dim3(1), dim3(256), 0, s, nullptr, 0ull, nullptr, 0ull, n_kept); }));
+        return TK_OK;
+    }
+    const bool edges = min_match <= P;
+    if (!c->grp_done.e) HIPCHK(c->grp_done.create());
+    HIPCHK(hipStreamWaitEvent(s, c->grp_done, 0));
+    Carve sc;
+    const uint64_t at_parent = sc.add(n * 4), at_slot = sc.add(edges ? g.per_round * g.S * 4 : 0);
+    TRY(ensure(c->d_grp, sc.total + 16));
+    uint32_t *parent = carved<uint32_t>(c->d_grp, at_parent), *slot = carved<uint32_t>(c->d_grp, at_slot);
+    const bool vec = P % 4 == 0 && ((uintptr_t)d_sig & 15) == 0;
+    uint32_t j0 = 0;
+    do {
+        const uint32_t nb = !edges ? 0u : B - j0 < g.per_round ? B - j0 : g.per_round;
+        const uint64_t n_slots = nb * g.S;
+        TRY(timed(c, s, "tk_k_grp_clear", [&] {
+            hipLaunchKernelGGL(tk_k_grp_clear, dim3(grid_for(n_slots > n ? n_slots : n, 256, 65536)), dim3(256), 0, s, slot, n_slots, j0 ? nullptr : parent, n,
+                               j0 ? nullptr : n_kept);
+        }));
+        if (nb) {
+            TRY(timed(c, s, "tk_k_grp_claim", [&] { hipLaunchKernelGGL(tk_k_grp_claim, dim3(grid_for(n * nb, 256, 1u << 20)), dim3(256), 0, s, g, d_band, d_nsh, slot, j0, nb); }));
+            TRY(timed(c, s, "tk_k_grp_join", [&] {
+                hipLaunchKernelGGL(tk_k_grp_join, dim3(grid_for(n * nb, 256, 1u << 20)), dim3(256), 0, s, g, d_sig, d_band, d_nsh, slot, parent, j0, nb, vec);
+            }));
+        }
+        j0 += g.per_round;
+    } while (edges && j0 < B);
+    TRY(timed(c, s, "tk_k_grp_flat", [&] { hipLaunchKernelGGL(tk_k_grp_flat, dim3(grid_for(n, 256, 1u << 24)), dim3(256), 0, s, n, parent, o.group, o.keep, n_kept); }));
+    HIPCHK(hipEventRecord(c->grp_done, s));
+    return TK_OK;
+}
+
+extern "C" int tk_fingerprint_groups_device(tk_core* c, const uint32_t* d_sig, const uint64_t* d_band, const uint64_t* d_n_shingles, uint64_t n_docs, uint32_t n_perm,
+                                            uint32_t bands, uint32_t min_match, void* stream, uint32_t* d_group, uint8_t* d_keep, uint64_t* d_n_kept) {
+    // (the stream as given, null being HIP's null stream: tk_fingerprint_device's convention)
+    return device_pass(c, !n_docs || (d_sig && d_band && d_n_shingles), stream, [&](hipStream_t) {
+        return grp_run(c, (hipStream_t)stream, d_sig, d_band, d_n_shingles, n_docs, n_perm, bands, min_match, GrpOuts{d_group, d_keep, d_n_kept});
+    });
+}
+
+extern "C" int tk_fingerprint_groups(tk_core* c, const uint32_t* sig, const uint64_t* band, const uint64_t* n_shingles, uint64_t n_docs, uint32_t n_perm, uint32_t bands,
+                                     uint32_t min_match, uint32_t* group_out, uint8_t* keep_out, uint64_t* n_kept_out) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if (n_docs && !(sig && band && n_shingles)) return fail(TK_VALUE_ERROR, "null argument");
+    TkGrp g;
+    TRY(grp_shape(n_docs, n_perm, bands, min_match, &g));
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    Carve in;
+    const uint64_t at_sig = in.add(n_docs * n_perm * 4), at_band = in.add(n_docs * bands * 8), at_nsh = in.add(n_docs * 8), at_group = in.add(n_docs * 4),
+                   at_keep = in.add(n_docs), at_cnt = in.add(8);
+    TRY(ensure(c->d_grp_in, in.total + 16));
+    uint32_t *d_sig = carved<uint32_t>(c->d_grp_in, at_sig), *d_group = carved<uint32_t>(c->d_grp_in, at_group);
+    uint64_t *d_band = carved<uint64_t>(c->d_grp_in, at_band), *d_nsh = carved<uint64_t>(c->d_grp_in, at_nsh), *d_cnt = carved<uint64_t>(c->d_grp_in, at_cnt);
+    uint8_t* d_keep = carved<uint8_t>(c->d_grp_in, at_keep);
+    if (n_docs) {
+        HIPCHK(hipMemcpyAsync(d_sig, sig, n_docs * n_perm * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(d_band, band, n_docs * bands * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(d_nsh, n_shingles, n_docs * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    return drained(c, [&]() -> int {
+        TRY(grp_run(c, c->stream, d_sig, d_band, d_nsh, n_docs, n_perm, bands, min_match,
+                    GrpOuts{group_out ? d_group : nullptr, keep_out ? d_keep : nullptr, n_kept_out ? d_cnt : nullptr}));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipGetLastError());
+        if (group_out && n_docs) HIPCHK(hipMemcpy(group_out, d_group, n_docs * 4, hipMemcpyDeviceToHost));
+        if (keep_out && n_docs) HIPCHK(hipMemcpy(keep_out, d_keep, n_docs, hipMemcpyDeviceToHost));
+        if (n_kept_out) HIPCHK(hipMemcpy(n_kept_out, d_cnt, 8, hipMemcpyDeviceToHost));
+        return TK_OK;
+    });
+}
+
+struct SelOuts {  // the caller's device arrays
+    uint32_t* tokens;
+    uint64_t* tok_off;
+    uint32_t* doc;
+    uint64_t* counts;
+};
+// sel_run: the caller holds c->mu.  The two per-workgroup arrays lie in c->d_sel, ordered by c->sel_done as grp_run's scratch is.
+static int sel_run(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n, const uint64_t* d_tok_off, uint64_t n_docs, const uint8_t* d_keep, SelOuts o) {
+    if (n_docs >= 0xFFFFFFFFull) return fail(TK_VALUE_ERROR, "n_docs: 2^32 - 1 documents or more (document indices are 32-bit)");
+    if (o.tokens && o.tokens == d_tok) return fail(TK_VALUE_ERROR, "tokens_out must not be tokens: the selection does not run in place");
+    if (o.tok_off == d_tok_off) return fail(TK_VALUE_ERROR, "tok_off_out must not be tok_off: the selection does not run in place");
+    const uint64_t nb = (n_docs + 255) / 256;
+    if (!c->sel_done.e) HIPCHK(c->sel_done.create());
+    HIPCHK(hipStreamWaitEvent(s, c->sel_done, 0));
+    Carve sc;
+    const uint64_t at_docs = sc.add(nb * 8), at_toks = sc.add(nb * 8);
+    TRY(ensure(c->d_sel, sc.total + 16));
+    unsigned long long *blk_docs = carved<unsigned long long>(c->d_sel, at_docs), *blk_toks = carved<unsigned long long>(c->d_sel, at_toks);
+    if (nb) TRY(timed(c, s, "tk_k_sel_count", [&] { hipLaunchKernelGGL(tk_k_sel_count, dim3((uint32_t)nb), dim3(256), 0, s, d_keep, d_tok_off, n_docs, blk_docs, blk_toks); }));
+    TRY(timed(c, s, "tk_k_sel_scan", [&] { hipLaunchKernelGGL(tk_k_sel_scan, dim3(1), dim3(1024), 0, s, blk_docs, blk_toks, nb, o.tok_off, o.counts); }));
+    if (nb)
+        TRY(timed(c, s, "tk_k_sel_place", [&] {
+            hipLaunchKernelGGL(tk_k_sel_place, dim3((uint32_t)nb), dim3(256), 0, s, d_keep, d_tok_off, n_docs, blk_docs, blk_toks, o.tok_off, o.doc);
+        }));
+    if (nb && n)
+        TRY(timed(c, s, "tk_k_sel_copy", [&] {
+            hipLaunchKernelGGL(tk_k_sel_copy, dim3(grid_for(n, TK_SEL_TILE, 65536)), dim3(TK_SEL_THREADS), 0, s, d_tok, n, d_tok_off, o.tok_off, o.doc, o.counts, o.tokens);
+        }));
+    HIPCHK(hipEventRecord(c->sel_done, s));
+    return TK_OK;
+}
+
+extern "C" int tk_select_docs_device(tk_core* c, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_docs, const uint8_t* d_keep, void* stream,
+                                     uint32_t* d_tokens_out, uint64_t* d_tok_off_out, uint32_t* d_doc_out, uint64_t* d_counts_out) {
+    const bool args = d_tok_off && d_tok_off_out && d_counts_out && (!n_tokens || (d_tokens && d_tokens_out)) && (!n_docs || (d_keep && d_doc_out));
+    return device_pass(c, args, stream, [&](hipStream_t) {
+        return sel_run(c, (hipStream_t)stream, (const uint32_t*)d_tokens, n_tokens, (const uint64_t*)d_tok_off, n_docs, d_keep,
+                       SelOuts{d_tokens_out, d_tok_off_out, d_doc_out, d_counts_out});
+    });
+}
+
+// Fingerprints, groups and selection over ids that are on the device, into c->d_dedup; one wait; then only the survivors (and `group`,
+// which is over all documents) travel to the host.  The caller holds c->mu.
+struct DedupOuts {
+    uint32_t** tokens;
+    uint64_t* n_tokens;
+    uint64_t** tok_off;
+    uint32_t** doc;
+    uint64_t* n_kept;
+    uint32_t* group;  // the caller's array, n_docs entries; may be null
+    bool there() const { return tokens && n_tokens && tok_off && doc && n_kept; }
+};
+static int dedup_check(const tk_fingerprint_spec* spec, uint64_t n_docs) {
+    TRY(fp_check_spec(spec));
+    TkGrp g;
+    return grp_shape(n_docs, spec->n_perm, spec->bands, 0, &g);
+}
+static int dedup_to_host(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n, const uint64_t* d_tok_off, uint64_t n_docs, const tk_fingerprint_spec* spec,
+                         uint32_t min_match, const DedupOuts& h) {
+    TRY(dedup_check(spec, n_docs));
+    const uint32_t P = spec->n_perm, B = spec->bands;
+    Carve cv;
+    const uint64_t at_sig = cv.add(n_docs * P * 4), at_band = cv.add(n_docs * B * 8), at_nsh = cv.add(n_docs * 8), at_group = cv.add(n_docs * 4), at_keep = cv.add(n_docs),
+                   at_tok = cv.add(n * 4), at_off = cv.add((n_docs + 1) * 8), at_doc = cv.add(n_docs * 4), at_cnt = cv.add(16);
+    TRY(ensure(c->d_dedup, cv.total + 16));
+    uint32_t *d_sig = carved<uint32_t>(c->d_dedup, at_sig), *d_group = carved<uint32_t>(c->d_dedup, at_group);
+    uint64_t *d_band = carved<uint64_t>(c->d_dedup, at_band), *d_nsh = carved<uint64_t>(c->d_dedup, at_nsh);
+    uint8_t* d_keep = carved<uint8_t>(c->d_dedup, at_keep);
+    const SelOuts sel{carved<uint32_t>(c->d_dedup, at_tok), carved<uint64_t>(c->d_dedup, at_off), carved<uint32_t>(c->d_dedup, at_doc), carved<uint64_t>(c->d_dedup, at_cnt)};
+    TRY(fp_run(c, s, d_tok, n, d_tok_off, n_docs, spec, FpOuts{d_sig, d_band, nullptr, d_nsh}));
+    TRY(grp_run(c, s, d_sig, d_band, d_nsh, n_docs, P, B, min_match, GrpOuts{d_group, d_keep, nullptr}));
+    TRY(sel_run(c, s, d_tok, n, d_tok_off, n_docs, d_keep, sel));
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    uint64_t counts[2] = {0, 0};
+    HIPCHK(hipMemcpy(counts, sel.counts, 16, hipMemcpyDeviceToHost));
+    if (counts[0] > n_docs || counts[1] > n) return fail(TK_RUNTIME_ERROR, "internal error: the selection kept more than there is");
+    ResultBag bag;
+    TRY(bag.fetch(h.tokens, sel.tokens, counts[1]));
+    TRY(bag.fetch(h.tok_off, sel.tok_off, counts[0] + 1));
+    TRY(bag.fetch(h.doc, sel.doc, counts[0]));
+    if (h.group && n_docs) HIPCHK(hipMemcpy(h.group, d_group, n_docs * 4, hipMemcpyDeviceToHost));
+    bag.give();
+    *h.n_kept = counts[0], *h.n_tokens = counts[1];
+    return TK_OK;
+}
+
+extern "C" int tk_dedup_tokens(tk_core* c, const uint32_t* tokens, const uint64_t* tok_off, uint64_t n_docs, const tk_fingerprint_spec* spec, uint32_t min_match,
+                               uint32_t** tokens_out, uint64_t* n_tokens_out, uint64_t** tok_off_out, uint32_t** doc_out, uint64_t* n_kept_out, uint32_t* group_out) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    const DedupOuts h{tokens_out, n_tokens_out, tok_off_out, doc_out, n_kept_out, group_out};
+    if (!tok_off || !spec || !h.there()) return fail(TK_VALUE_ERROR, "null argument");
+    TRY(dedup_check(spec, n_docs));
+    TRY(check_offsets(tok_off, n_docs, "tok_off"));
+    const uint64_t n = tok_off[n_docs];
+    if (n && !tokens) return fail(TK_VALUE_ERROR, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    Carve in;
+    const uint64_t at_off = in.add((n_docs + 1) * 8), at_tok = in.add(n * 4);
+    TRY(ensure(c->d_fp_in, in.total + 16));
+    uint64_t* d_off = carved<uint64_t>(c->d_fp_in, at_off);
+    uint32_t* d_tok = carved<uint32_t>(c->d_fp_in, at_tok);
+    HIPCHK(hipMemcpyAsync(d_off, tok_off, (n_docs + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    if (n) HIPCHK(hipMemcpyAsync(d_tok, tokens, n * 4, hipMemcpyHostToDevice, c->stream));
+    return drained(c, [&] { return dedup_to_host(c, c->stream, d_tok, n, d_off, n_docs, spec, min_match, h); });
+}
+
+// tk_encode_batch (tk_encode_batch_checked with disallowed ids), then the three passes over the ids it has just produced
+extern "C" int tk_encode_batch_dedup(tk_core* c, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special, const uint32_t* allowed_ids, uint64_t n_allowed,
+                                     const uint32_t* disallowed_ids, uint64_t n_disallowed, const tk_fingerprint_spec* spec, uint32_t min_match, uint32_t** tokens_out,
+                                     uint64_t* n_tokens_out, uint64_t** tok_off_out, uint32_t** doc_out, uint64_t* n_kept_out, uint32_t* group_out, tk_special_hit* hit) {
+    const DedupOuts h{tokens_out, n_tokens_out, tok_off_out, doc_out, n_kept_out, group_out};
+    return encode_batch_pass(
+        c, utf8, doc_off, n_docs, use_special, allowed_ids, n_allowed, disallowed_ids, n_disallowed, hit, spec && h.there(),
+        [&] { return dedup_check(spec, n_docs); },  // (before the encode, not after it)
+        [&](uint64_t n) { return dedup_to_host(c, c->stream, c->out_tokens.as<uint32_t>(), n, c->out_tok_off.as<uint64_t>(), n_docs, spec, min_match, h); },
+        [&](uint64_t) { return TK_OK; });
+}
+
+// ------------------------------------------------------------------------------------------
 // Supervised samples (tk_samples.h): a packed batch of parts on the device -> one row per sample, ids, mask and labels as [R, W].
 // ------------------------------------------------------------------------------------------
 static_assert(TK_SMP_KEEP_TAIL == TK_SMPF_KEEP_TAIL && TK_SMP_LEFT == TK_SMPF_LEFT, "tk_smp_spec flags");
@@ -5353,6 +5579,7 @@ extern "C" uint64_t tk_stat(tk_core* c, const char* name) {
     if (k == "split_stitch_steps") return c->st_split[TK_SPLIT_ST_STITCH];    // ... steps of the stitch pass (one wavefront per document, in order)
     if (k == "split_spec_steps") return c->st_split[TK_SPLIT_ST_SPEC];        // ... steps of the speculative walks
     if (k == "fingerprint_tile") return TK_FP_TILE;  // token positions of a tile of the fingerprint pass (tk_fingerprint_rule.h)
+    if (k == "select_tile") return TK_SEL_TILE;  // output positions of a tile of the selection's copy (tk_groups_rule.h)
     if (k == "jsonl_tile") return TK_JSONL_TILE;  // bytes of a tile of the JSON Lines passes (tk_jsonl_rule.h)
     if (k == "regrown") return c->st_regrown;  // batches repeated with a larger miss data since the core was made (encode_device_locked)
     if (k == "workspace_bytes") {             // device memory of the work sets (everything but the text, the tables and the outputs)

@@ -1,8 +1,10 @@
 // Scans and reductions over a wavefront (wave64) and over a workgroup: the one place for them.  Every kernel header takes its sums,
 // minima, maxima and prefix scans from here; a __shfl_up / __shfl_xor elsewhere fetches a neighbour's value and nothing more.
 //   tk_wave_min_u32 / _min_u64 / _max_u32 / _max_u64 / _sum_u32   the reduction, in every lane
+//   tk_lanes_sum_u32                                               the sum over every aligned group of g lanes, g a power of two
 //   tk_wave_scan_u32                                               inclusive prefix sum over the wavefront
 //   tk_block_exscan_256 / tk_block_exmax32_256 / tk_block_exmax64_256   exclusive scan over a workgroup of 256 threads
+//   tk_block_exscan64_256                                          ... of 64-bit sums
 //   tk_block_sum_256                                               sum over a workgroup of 256 threads
 //   tk_scan1024 / tk_scan_blocks                                   the one workgroup of 1024 threads that scans per-workgroup values
 #pragma once
@@ -46,6 +48,11 @@ __device__ __forceinline__ uint32_t tk_wave_sum_u32(uint32_t v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// the sum over each aligned group of g lanes (g a power of two, 1 .. 64), in every lane of the group; every lane of the wavefront is here
+__device__ __forceinline__ uint32_t tk_lanes_sum_u32(uint32_t v, uint32_t g) {
+    for (uint32_t o = g >> 1; o > 0; o >>= 1) v += __shfl_xor(v, (int)o, 64);
+    return v;
+}
 // inclusive prefix sum across the wave
 // inclusive prefix sum over the wavefront: four DPP row shifts inside the rows of sixteen lanes, then the last lane of a row to the rows
 // behind it (row_bcast:15 to rows 1 and 3, row_bcast:31 to rows 2 and 3) -- six full-rate instructions (round 4: six __shfl_up, each a
@@ -85,6 +92,28 @@ __device__ __forceinline__ uint32_t tk_block_exscan_256(uint32_t v, uint32_t* to
 #pragma unroll
     for (int w = 0; w < 4; ++w) {
         uint32_t s = sh[w];
+        if (w < wid) base += s;
+        tot += s;
+    }
+    __syncthreads();
+    *total = tot;
+    return base + inc - v;
+}
+// ... its 64-bit sibling (sums modulo 2^64)
+__device__ __forceinline__ unsigned long long tk_block_exscan64_256(unsigned long long v, unsigned long long* total, unsigned long long* sh /*[4]*/) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    unsigned long long inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long w = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += w;
+    }
+    if (lane == 63) sh[wid] = inc;
+    __syncthreads();
+    unsigned long long base = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const unsigned long long s = sh[w];
         if (w < wid) base += s;
         tot += s;
     }
