@@ -473,6 +473,66 @@ int tk_dedup_tokens(tk_core* core, const uint32_t* tokens, const uint64_t* tok_o
 int tk_encode_batch_dedup(tk_core* core, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special, const uint32_t* allowed_ids, uint64_t n_allowed,
                           const uint32_t* disallowed_ids, uint64_t n_disallowed, const tk_fingerprint_spec* spec, uint32_t min_match, uint32_t** tokens_out,
                           uint64_t* n_tokens_out, uint64_t** tok_off_out, uint32_t** doc_out, uint64_t* n_kept_out, uint32_t* group_out, tk_special_hit* hit);
+/* Token n-gram sets: a set of token n-grams that lives on the device across calls -- the n-grams of evaluation benchmarks
+ * (decontamination), of a block list, of shards already written --, filled by some calls and asked by others: per document of a packed
+ * batch, how many of its n-grams are in the set and which tokens they cover.  Replaces nothing in the reference: it is the host step of
+ * the reference's users between "dedup" and "pack rows", a loop over Python sets -- here on ids that are on the device anyway.  The
+ * survivors go on through tk_select_docs_device, which takes any keep mask.
+ * The rule.  All arithmetic is unsigned, modulo 2^64.  mix and a shingle's hash are tk_fingerprint's.
+ *  A set has ngram k in 1 .. 32, a seed (uint64) and a capacity in 1 .. 2^30.
+ *  N-grams.  Document d holds the tokens t[s .. e), s = tok_off[d], e = tok_off[d + 1], L = e - s.  L >= k: its n-grams start at the
+ *   positions [s, e - k + 1), one each, over k ids.  L < k: it has none (unlike tk_fingerprint, where a short document has one
+ *   shingle).  No n-gram crosses a document boundary.  Ids are taken as uint32 values, whatever they are.
+ *  Key.  The key of the n-gram u[0 .. k) is the hash x = mix(seed ^ k), then x = mix(x ^ u[j]) for j = 0 .. k - 1; a hash of 0 is the
+ *   key 1, because 0 is the empty slot.  Membership is equality of keys: two different n-grams are confused with probability 2^-64 per pair.
+ *  Table.  An open-addressing table of uint64 slots in device memory: S slots, S the power of two >= 2 * capacity; a key's probe starts
+ *   at slot key & (S - 1) and goes on linearly, wrapping; an empty slot is claimed by a 64-bit compare-and-swap, and a counter on the
+ *   device rises by one per claim.  Beside it a filter of 4 S bits (S / 2 bytes): bit (key >> 31) & (4 S - 1) is set for every key.
+ *   The distinct keys, their number and membership are functions of what was added, never of the schedule.
+ *  Add.  An add of n_tokens tokens is refused, before anything is written, when bound + n_tokens > capacity: the bound is kept on the
+ *   host, the sum of n_tokens of the adds so far (every add of n tokens adds at most n keys); tk_ngram_set_count waits, reads the exact
+ *   number of distinct keys and lowers the bound to it.
+ *  Overlap, per document d: n_ngrams[d], the number of its n-grams; n_hit[d], the number of n-gram starts whose key is in the set;
+ *   n_covered[d], the number of its tokens that lie inside at least one such n-gram -- a union, not a sum --; first_hit[d], the lowest
+ *   such start relative to s, 2^64 - 1 when there is none; mask[i] (uint8, per token of the batch): 1 when token i is covered, else 0.
+ *  Sums and minima are commutative: the result is a function of (the set's keys, tokens, tok_off) alone.
+ *  Refused with TK_VALUE_ERROR, and nothing written: ngram outside 1 .. 32; capacity 0 or above 2^30; a set of another core; an add
+ *   past the capacity.
+ * NOT built: a call that adds and asks at once; sets larger than the device's memory; several GPUs; n-grams of words or chars; removal
+ *  of single keys; saving a set to a file.
+ * A tk_ngram_set belongs to the core it was made on and must be destroyed before it; it owns its device memory (8 S bytes of table,
+ * S / 2 of filter, the buffers of its host entries).  The library orders the calls on one set among themselves on the device (an
+ * event, no host wait), whatever their streams and entries. */
+typedef struct tk_ngram_set tk_ngram_set;
+int tk_ngram_set_create(tk_core* core, uint32_t ngram, uint64_t seed, uint64_t capacity, tk_ngram_set** set_out);
+void tk_ngram_set_destroy(tk_ngram_set* set);
+/* The exact number of distinct keys; waits for every call queued on the set. */
+int tk_ngram_set_count(tk_ngram_set* set, uint64_t* count_out);
+/* Empties the set (queued on the core's stream; no wait). */
+int tk_ngram_set_clear(tk_ngram_set* set);
+/* The n-grams of a packed batch into the set.  Device pointers in (ids uint32, d_tok_off uint64[n_docs + 1]); stream and waiting as
+ * tk_fingerprint_device: everything is queued on `stream`, null being HIP's null stream, and the call returns without waiting.
+ * d_tok_off is not checked, as there. */
+int tk_ngram_add_device(tk_core* core, tk_ngram_set* set, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_docs, void* stream);
+/* The same from host arrays; a tok_off that does not ascend from 0 is TK_VALUE_ERROR. */
+int tk_ngram_add(tk_core* core, tk_ngram_set* set, const uint32_t* tokens, const uint64_t* tok_off, uint64_t n_docs);
+/* A packed batch against the set.  Device pointers in, the caller's device arrays out, any of which may be null: d_n_hit, d_n_covered,
+ * d_n_ngrams, d_first_hit uint64[n_docs], d_mask uint8[n_tokens].  Stream and waiting as tk_ngram_add_device. */
+int tk_ngram_overlap_device(tk_core* core, tk_ngram_set* set, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_docs, void* stream,
+                            uint64_t* d_n_hit, uint64_t* d_n_covered, uint64_t* d_n_ngrams, uint64_t* d_first_hit, uint8_t* d_mask);
+/* The same from host arrays to the caller's host arrays (sized as above, any may be null). */
+int tk_ngram_overlap(tk_core* core, tk_ngram_set* set, const uint32_t* tokens, const uint64_t* tok_off, uint64_t n_docs, uint64_t* n_hit_out, uint64_t* n_covered_out,
+                     uint64_t* n_ngrams_out, uint64_t* first_hit_out, uint8_t* mask_out);
+/* tk_encode_batch -- with n_disallowed != 0: tk_encode_batch_checked -- and the add, or the overlap, over the ids while they are on
+ * the device: the ids never come back.  *n_tokens_out (may be null): how many there were.  The overlap's arrays are the caller's
+ * (any may be null; tok_off_out: n_docs + 1), its mask is library-owned (tk_free; *n_tokens_out bytes; mask_out may be null).  On
+ * TK_DISALLOWED_SPECIAL nothing is added and nothing handed out. */
+int tk_encode_batch_ngram_add(tk_core* core, tk_ngram_set* set, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special,
+                              const uint32_t* allowed_ids, uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed, uint64_t* n_tokens_out,
+                              tk_special_hit* hit);
+int tk_encode_batch_overlap(tk_core* core, tk_ngram_set* set, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special, const uint32_t* allowed_ids,
+                            uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed, uint64_t* n_hit_out, uint64_t* n_covered_out,
+                            uint64_t* n_ngrams_out, uint64_t* first_hit_out, uint64_t* tok_off_out, uint8_t** mask_out, uint64_t* n_tokens_out, tk_special_hit* hit);
 /* Supervised samples: a packed batch whose documents are the PARTS of samples -- the messages of a conversation, a prompt and its answer --
  * -> one row per sample with the template's ids around every part, an attention mask and labels.  Replaces nothing in the reference: it is
  * the host loop of the reference's users, the fine-tuning script that calls encode_ordinary once per message, adds header and footer ids and
@@ -927,7 +987,8 @@ void tk_last_stats(tk_core* core, uint64_t* n_bytes, uint64_t* n_pieces, uint64_
  * or above, the decode entries answer TK_UNSUPPORTED); and of the last split call (tk_split_device, tk_encode_batch_split): "split_segments"
  * (document parts per block of K positions), "split_joined" (blocks in which the true chain met the speculative walk), "split_stitch_steps"
  * (steps of the stitch pass) and "split_spec_steps" (steps of the speculative walks); "jsonl_tile": the bytes of a tile of the JSON Lines
- * passes (a constant of the build); "fingerprint_tile": the token positions of a tile of the fingerprint pass (likewise). */
+ * passes (a constant of the build); "fingerprint_tile": the token positions of a tile of the fingerprint pass, "ngram_tile": of the
+ * n-gram passes (likewise). */
 uint64_t tk_stat(tk_core* core, const char* name);
 
 #ifdef __cplusplus

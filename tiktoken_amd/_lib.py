@@ -184,6 +184,26 @@ def lib() -> ctypes.CDLL:
             L.tk_dedup_tokens.argtypes = [vp, vp, vp, u64, P(FingerprintSpec), u32, P(vp), P(u64), P(vp), P(vp), P(u64), vp]
             L.tk_encode_batch_dedup.restype = i32
             L.tk_encode_batch_dedup.argtypes = [vp, vp, vp, u64, i32, vp, u64, vp, u64, P(FingerprintSpec), u32, P(vp), P(u64), P(vp), P(vp), P(u64), vp, P(SpecialHit)]
+        if hasattr(L, "tk_ngram_set_create"):  # (absent from older builds selected through $TIKTOKEN_AMD_LIB)
+            L.tk_ngram_set_create.restype = i32
+            L.tk_ngram_set_create.argtypes = [vp, u32, u64, u64, P(vp)]
+            L.tk_ngram_set_destroy.argtypes = [vp]
+            L.tk_ngram_set_count.restype = i32
+            L.tk_ngram_set_count.argtypes = [vp, P(u64)]
+            L.tk_ngram_set_clear.restype = i32
+            L.tk_ngram_set_clear.argtypes = [vp]
+            L.tk_ngram_add_device.restype = i32
+            L.tk_ngram_add_device.argtypes = [vp, vp, vp, u64, vp, u64, vp]
+            L.tk_ngram_add.restype = i32
+            L.tk_ngram_add.argtypes = [vp, vp, vp, vp, u64]
+            L.tk_ngram_overlap_device.restype = i32
+            L.tk_ngram_overlap_device.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp, vp, vp, vp, vp]
+            L.tk_ngram_overlap.restype = i32
+            L.tk_ngram_overlap.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, vp, vp]
+            L.tk_encode_batch_ngram_add.restype = i32
+            L.tk_encode_batch_ngram_add.argtypes = [vp, vp, vp, vp, u64, i32, vp, u64, vp, u64, P(u64), P(SpecialHit)]
+            L.tk_encode_batch_overlap.restype = i32
+            L.tk_encode_batch_overlap.argtypes = [vp, vp, vp, vp, u64, i32, vp, u64, vp, u64, vp, vp, vp, vp, vp, P(vp), P(u64), P(SpecialHit)]
         if hasattr(L, "tk_jsonl_extract_device"):  # (absent from older builds selected through $TIKTOKEN_AMD_LIB)
             L.tk_jsonl_extract_device.restype = i32
             L.tk_jsonl_extract_device.argtypes = [vp, vp, u64, vp, u64, u32, vp, *[P(vp)] * 5, *[P(u64)] * 3, P(JsonlBad)]

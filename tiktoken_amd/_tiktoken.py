@@ -725,6 +725,49 @@ class DedupedBatch(NamedTuple):
     group: np.ndarray
 
 
+class NgramOverlap(NamedTuple):
+    """A batch against an n-gram set (tk_ngram_overlap; the rule: include/tiktoken_amd.h), per document: `n_hit` uint64[n] the n-gram
+    starts whose n-gram is in the set, `n_covered` uint64[n] the tokens inside at least one such n-gram, `n_ngrams` uint64[n] the
+    document's n-grams, `first_hit` uint64[n] the lowest such start in the document (2^64 - 1: none), `length` its tokens; `mask`
+    uint8[T], 1 on the covered tokens of the batch, or None where it was not asked for."""
+    n_hit: np.ndarray
+    n_covered: np.ndarray
+    n_ngrams: np.ndarray
+    first_hit: np.ndarray
+    length: np.ndarray
+    mask: "np.ndarray | None"
+
+    def keep_mask(self, max_hits: int = 0, max_covered_ratio: "float | None" = None) -> np.ndarray:
+        """bool[n]: the documents with at most `max_hits` n-grams in the set and, where `max_covered_ratio` is given, at most that
+        share of their tokens covered (n_covered <= max_covered_ratio * length, in double precision)."""
+        keep = self.n_hit <= np.uint64(max_hits)
+        if max_covered_ratio is not None:
+            keep &= self.n_covered.astype(np.float64) <= float(max_covered_ratio) * self.length.astype(np.float64)
+        return keep
+
+
+class NativeNgramSet:
+    """A tk_ngram_set; made by `CoreBPE.ngram_set_create`.  Keeps its core alive: the set must go first."""
+
+    def __init__(self, core: "CoreBPE", handle, ngram: int, capacity: int, seed: int):
+        self._core, self._h, self.ngram, self.capacity, self.seed = core, handle, ngram, capacity, seed
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and getattr(self._core, "_h", None):  # (a core that is closed has taken its device's buffers along)
+            try:
+                self._core._L.tk_ngram_set_destroy(h)
+            except Exception:
+                pass
+
+    __del__ = close
+
+    def handle(self):
+        if not self._h:
+            raise ValueError("the n-gram set is closed")
+        return self._h
+
+
 class DisallowedSpecialError(ValueError):
     """A batch holds a disallowed special token: the first occurrence -- document `doc`, byte offset `pos` inside it, the `token` (the
     longest disallowed one that matches there).  What the reference raises as a plain ValueError, with its message."""
@@ -1823,6 +1866,107 @@ class CoreBPE:
         def call(*res):
             self._raise_for(self._L.tk_encode_batch_dedup(self._h, *text, *dis, ctypes.byref(spec), min_match(threshold, spec.n_perm), *res, ctypes.byref(hit)), hit)
         return self._deduped(call, n_docs)
+
+    # ------------------------------------------------------------------ token n-gram sets (no reference counterpart: the host step of its users)
+    def ngram_set_create(self, ngram: int = 13, capacity: int = 1 << 20, seed: int = 0) -> NativeNgramSet:
+        """An empty n-gram set on this core's device (tk_ngram_set_create) for up to `capacity` distinct n-grams of `ngram` tokens."""
+        self._one_device("ngram_set_create")
+        if not 0 <= int(ngram) <= 0xFFFFFFFF or not 0 <= int(capacity) <= 0xFFFFFFFFFFFFFFFF or not 0 <= int(seed) <= 0xFFFFFFFFFFFFFFFF:
+            raise ValueError("ngram must fit 32 bits, capacity and seed 64")
+        h = ctypes.c_void_p()
+        _lib.raise_for(self._L.tk_ngram_set_create(self._h, int(ngram), int(seed), int(capacity), ctypes.byref(h)))
+        return NativeNgramSet(self, h, int(ngram), int(capacity), int(seed))
+
+    def ngram_count(self, ngs: NativeNgramSet) -> int:
+        """The distinct n-grams in the set (tk_ngram_set_count): waits for the calls queued on it."""
+        n = ctypes.c_uint64()
+        _lib.raise_for(self._L.tk_ngram_set_count(ngs.handle(), ctypes.byref(n)))
+        return int(n.value)
+
+    def ngram_clear(self, ngs: NativeNgramSet) -> None:
+        _lib.raise_for(self._L.tk_ngram_set_clear(ngs.handle()))
+
+    def ngram_add_device(self, ngs: NativeNgramSet, tokens, tok_off, *, stream: int | None = None) -> None:
+        """The n-grams of a packed batch that is on the device into the set (tk_ngram_add_device): torch tensors on this core's GPU, taken
+        by pointer -- `tokens` (32-bit, T) and `tok_off` (64-bit, n + 1, ascending from 0 to T).  Stream and waiting as in
+        `fingerprint_device`: queued on `stream`, and the call does not wait."""
+        self._one_device("ngram_add_device")
+        n, T = tok_off.numel() - 1, tokens.numel()
+        if n < 0:
+            raise ValueError("tok_off must hold n_docs + 1 entries")
+        stream = self._on_gpu((("tokens", tokens, 4, T), ("tok_off", tok_off, 8, n + 1)), stream)
+        _lib.raise_for(self._L.tk_ngram_add_device(self._h, ngs.handle(), tokens.data_ptr() if T else None, T, tok_off.data_ptr(), n, stream or None))
+
+    def ngram_overlap_device(self, ngs: NativeNgramSet, tokens, tok_off, *, n_hit=None, n_covered=None, n_ngrams=None, first_hit=None, mask=None,
+                             stream: int | None = None) -> None:
+        """A packed batch that is on the device against the set (tk_ngram_overlap_device): `tokens` and `tok_off` as in `ngram_add_device`;
+        the caller's tensors out, any of which may be None: `n_hit`, `n_covered`, `n_ngrams`, `first_hit` (64-bit, n) and `mask` (8-bit,
+        T).  Stream and waiting as there."""
+        self._one_device("ngram_overlap_device")
+        n, T = tok_off.numel() - 1, tokens.numel()
+        if n < 0:
+            raise ValueError("tok_off must hold n_docs + 1 entries")
+        outs = (n_hit, n_covered, n_ngrams, first_hit, mask)
+        stream = self._on_gpu((("tokens", tokens, 4, T), ("tok_off", tok_off, 8, n + 1), ("n_hit", n_hit, 8, n), ("n_covered", n_covered, 8, n),
+                               ("n_ngrams", n_ngrams, 8, n), ("first_hit", first_hit, 8, n), ("mask", mask, 1, T)), stream)
+        ptr = [t.data_ptr() if t is not None and t.numel() else None for t in outs]
+        _lib.raise_for(self._L.tk_ngram_overlap_device(self._h, ngs.handle(), tokens.data_ptr() if T else None, T, tok_off.data_ptr(), n, stream or None, *ptr))
+
+    @staticmethod
+    def _packed_tokens(tokens, tok_off):
+        tokens = np.ascontiguousarray(tokens, dtype=np.uint32)
+        tok_off = np.ascontiguousarray(tok_off, dtype=np.uint64)
+        if tok_off.ndim != 1 or tokens.ndim != 1 or len(tok_off) < 1 or int(tok_off[-1]) != len(tokens):
+            raise ValueError("tok_off must hold n + 1 offsets that end at len(tokens)")
+        return tokens, tok_off
+
+    def ngram_add_packed(self, ngs: NativeNgramSet, tokens: np.ndarray, tok_off: np.ndarray) -> None:
+        """The n-grams of packed tokens into the set (tk_ngram_add): host arrays in -- `tokens` uint32[T], `tok_off` uint64[n + 1]."""
+        self._one_device("ngram_add_packed")
+        tokens, tok_off = self._packed_tokens(tokens, tok_off)
+        _lib.raise_for(self._L.tk_ngram_add(self._h, ngs.handle(), tokens.ctypes.data if len(tokens) else None, tok_off.ctypes.data, len(tok_off) - 1))
+
+    @staticmethod
+    def _ng_outs(n: int):
+        """(n_hit, n_covered, n_ngrams, first_hit) for n documents, to be filled by the library (one spare element each: no empty array's pointer)"""
+        return tuple(np.zeros(n + 1, dtype=np.uint64)[:n] for _ in range(4))
+
+    def ngram_overlap_packed(self, ngs: NativeNgramSet, tokens: np.ndarray, tok_off: np.ndarray, mask: bool = False) -> NgramOverlap:
+        """Packed tokens against the set (tk_ngram_overlap): host arrays in, an `NgramOverlap` out, with its token mask if `mask`."""
+        self._one_device("ngram_overlap_packed")
+        tokens, tok_off = self._packed_tokens(tokens, tok_off)
+        n = len(tok_off) - 1
+        out = self._ng_outs(n)
+        m = np.zeros(len(tokens) + 1, dtype=np.uint8)[:len(tokens)] if mask else None
+        rc = self._L.tk_ngram_overlap(self._h, ngs.handle(), tokens.ctypes.data if len(tokens) else None, tok_off.ctypes.data, n, *[a.ctypes.data for a in out],
+                                      m.ctypes.data if mask else None)
+        _lib.raise_for(rc)
+        return NgramOverlap(*out, np.diff(tok_off), m)
+
+    def encode_batch_ngram_add_packed(self, ngs: NativeNgramSet, blob: np.ndarray, doc_off: np.ndarray, allowed_special: AbstractSet[str] | None = None, *,
+                                      disallowed_special=None) -> int:
+        """`encode_batch_packed` with the n-grams of its result added to the set while the ids are on the device
+        (tk_encode_batch_ngram_add): the ids stay there.  Returns the number of tokens.  The special-token arguments as in
+        `encode_batch_packed`."""
+        self._one_device("encode_batch_ngram_add_packed")
+        text, dis, _n_docs, _keep = self._batch_args(blob, doc_off, allowed_special, disallowed_special)
+        hit, n_tok = _lib.SpecialHit(), ctypes.c_uint64()
+        self._raise_for(self._L.tk_encode_batch_ngram_add(self._h, ngs.handle(), *text, *dis, ctypes.byref(n_tok), ctypes.byref(hit)), hit)
+        return int(n_tok.value)
+
+    def encode_batch_overlap_packed(self, ngs: NativeNgramSet, blob: np.ndarray, doc_off: np.ndarray, allowed_special: AbstractSet[str] | None = None, *,
+                                    disallowed_special=None, mask: bool = False) -> NgramOverlap:
+        """`encode_batch_packed` with its result asked against the set while the ids are on the device (tk_encode_batch_overlap): the ids
+        stay there, only the `NgramOverlap` comes back.  The special-token arguments as in `encode_batch_packed`."""
+        self._one_device("encode_batch_overlap_packed")
+        text, dis, n_docs, _keep = self._batch_args(blob, doc_off, allowed_special, disallowed_special)
+        hit, n_tok, m = _lib.SpecialHit(), ctypes.c_uint64(), ctypes.c_void_p()
+        out = self._ng_outs(n_docs)
+        tok_off = np.zeros(n_docs + 1, dtype=np.uint64)
+        rc = self._L.tk_encode_batch_overlap(self._h, ngs.handle(), *text, *dis, *[a.ctypes.data for a in out], tok_off.ctypes.data, ctypes.byref(m) if mask else None,
+                                             ctypes.byref(n_tok), ctypes.byref(hit))
+        self._raise_for(rc, hit)
+        return NgramOverlap(*out, np.diff(tok_off), self._own_mask(m, int(n_tok.value)) if mask else None)
 
     # ------------------------------------------------------------------ supervised samples (no reference counterpart: the host loop of its users)
     @staticmethod

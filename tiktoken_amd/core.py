@@ -406,6 +406,14 @@ class Encoding:
         """Tokens that are packed already (`tokens` uint32[T], `tok_off` uint64[n + 1]) without their near-duplicates."""
         return self._core_bpe.dedup_packed(tokens, tok_off, threshold, ngram=ngram, n_perm=n_perm, bands=bands, seed=seed)
 
+    # ------------------------------------------------------------------ token n-gram sets
+    def ngram_set(self, ngram: int = 13, *, capacity: int, seed: int = 0) -> "NgramSet":
+        """An empty set of token n-grams that lives on the GPU across calls (tk_ngram_set_create): the n-grams of evaluation benchmarks,
+        of a block list, of shards already written.  Some calls fill it (`add_batch`, ...), others ask it (`overlap_batch`, ...): per
+        document how many of its n-grams of `ngram` tokens are in the set and which tokens they cover.  `capacity`: the most distinct
+        n-grams it holds, at most 2^30 (16 bytes of device memory to 32 each).  The rule is stated in include/tiktoken_amd.h."""
+        return NgramSet(self, self._core_bpe.ngram_set_create(ngram, capacity, seed))
+
     def split_ordinary_batch_packed(self, text: Sequence[str], max_tokens: int, *, min_tokens: int | None = None, overlap: int = 0,
                                     separators=_tiktoken.DEFAULT_SEPARATORS, seg_tokens: int = 0) -> "_tiktoken.TextChunks":
         """A batch cut into chunks of at most `max_tokens` tokens, ignoring special tokens: every text is encoded and cut, each cut at the
@@ -980,6 +988,77 @@ class Encoding:
             self.__dict__ = plugins.get_encoding(value).__dict__
             return
         self.__init__(**value)
+
+
+class NgramSet:
+    """`Encoding.ngram_set`: a set of token n-grams on the GPU.  A context manager; `close()` releases the device memory.  An add is
+    refused (ValueError), before anything is written, when the tokens added so far plus its own exceed the capacity; `len()` waits,
+    counts the distinct n-grams exactly and lowers that bound to the count."""
+
+    def __init__(self, enc: Encoding, native: "_tiktoken.NativeNgramSet"):
+        self._enc, self._native = enc, native
+        self.ngram, self.capacity, self.seed = native.ngram, native.capacity, native.seed
+
+    def close(self) -> None:
+        self._native.close()
+
+    def __enter__(self) -> "NgramSet":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __len__(self) -> int:
+        return self._enc._core_bpe.ngram_count(self._native)
+
+    def clear(self) -> None:
+        """Empties the set."""
+        self._enc._core_bpe.ngram_clear(self._native)
+
+    def _checked(self, call, text, allowed_special, disallowed_special, **kw):
+        """call(set, blob, off, allowed_special, ...) under the special-token policy, and the error, of `encode_batch_packed`"""
+        enc = self._enc
+        allowed_special, disallowed_special = enc._special_policy(allowed_special, disallowed_special)
+        blob, off, repaired = enc._pack_repaired(text)
+        if not disallowed_special:
+            return call(self._native, blob, off, allowed_special, **kw)
+        if not isinstance(disallowed_special, frozenset):
+            disallowed_special = frozenset(disallowed_special)
+        if repaired or not all(t in enc._special_tokens for t in disallowed_special):  # (as encode_batch_packed: the host's search)
+            for t in text:
+                enc._reject_disallowed(t, disallowed_special)
+            return call(self._native, blob, off, allowed_special, **kw)
+        return call(self._native, blob, off, allowed_special, disallowed_special=disallowed_special, **kw)
+
+    def add_ordinary_batch(self, text: Sequence[str]) -> int:
+        """The n-grams of a batch, ignoring special tokens, into the set: every text is encoded and, while its ids are on the GPU, its
+        n-grams are inserted; the ids never come back.  Returns the number of tokens."""
+        blob, off = self._enc._pack(text)
+        return self._enc._core_bpe.encode_batch_ngram_add_packed(self._native, blob, off, None)
+
+    def add_batch(self, text: Sequence[str], *, allowed_special: Literal["all"] | AbstractSet[str] = set(),  # noqa: B006
+                  disallowed_special: Literal["all"] | Collection[str] = "all") -> int:
+        """`add_ordinary_batch` with the special-token arguments of `encode`."""
+        return self._checked(self._enc._core_bpe.encode_batch_ngram_add_packed, text, allowed_special, disallowed_special)
+
+    def add_tokens_packed(self, tokens, tok_off) -> None:
+        """The n-grams of tokens that are packed already (`tokens` uint32[T], `tok_off` uint64[n + 1], e.g. `encode_batch_packed`'s)."""
+        self._enc._core_bpe.ngram_add_packed(self._native, tokens, tok_off)
+
+    def overlap_ordinary_batch(self, text: Sequence[str], *, mask: bool = False) -> "_tiktoken.NgramOverlap":
+        """A batch, ignoring special tokens, against the set: every text is encoded and, while its ids are on the GPU, asked; the ids
+        never come back.  Returns an `NgramOverlap`, whose `keep_mask` says which documents to keep."""
+        blob, off = self._enc._pack(text)
+        return self._enc._core_bpe.encode_batch_overlap_packed(self._native, blob, off, None, mask=mask)
+
+    def overlap_batch(self, text: Sequence[str], *, mask: bool = False, allowed_special: Literal["all"] | AbstractSet[str] = set(),  # noqa: B006
+                      disallowed_special: Literal["all"] | Collection[str] = "all") -> "_tiktoken.NgramOverlap":
+        """`overlap_ordinary_batch` with the special-token arguments of `encode`."""
+        return self._checked(self._enc._core_bpe.encode_batch_overlap_packed, text, allowed_special, disallowed_special, mask=mask)
+
+    def overlap_tokens_packed(self, tokens, tok_off, mask: bool = False) -> "_tiktoken.NgramOverlap":
+        """Tokens that are packed already against the set."""
+        return self._enc._core_bpe.ngram_overlap_packed(self._native, tokens, tok_off, mask)
 
 
 class DecodeStream:

@@ -32,6 +32,7 @@
 #include "tk_split.h"
 #include "tk_fingerprint.h"
 #include "tk_groups.h"
+#include "tk_ngram.h"
 #include "tk_jsonl.h"
 #include "tk_sample_rows.h"
 #include "tk_samples.h"
@@ -3712,6 +3713,243 @@ extern "C" int tk_encode_batch_dedup(tk_core* c, const uint8_t* utf8, const uint
 }
 
 // ------------------------------------------------------------------------------------------
+// Token n-gram sets (tk_ngram.h): a set of n-gram keys on the device, filled by some calls and asked by others.  The first state of this
+// library that outlives a batch: it is the set's, not the core's -- the table, the filter, the counter, the buffers of the host entries
+// and the event that orders the set's calls among themselves on the device go with the tk_ngram_set.
+// ------------------------------------------------------------------------------------------
+struct tk_ngram_set {
+    tk_core* c = nullptr;
+    int device = 0;
+    TkNg p{};
+    uint64_t capacity = 0;
+    uint64_t bound = 0;  // at least the distinct keys in the table: the tokens added since the last exact count
+    Event done;          // recorded behind every call on the set, on that call's stream; the next call's stream waits for it first
+    Buf table, filter, count, in, out;  // in, out: ids and tok_off, and the results, of the entries that take host arrays
+};
+static int ng_refusal(int why) {
+    switch (why) {
+        case 0: return TK_OK;
+        case 1: return fail(TK_VALUE_ERROR, "ngram must be 1 .. 32");
+        default: return fail(TK_VALUE_ERROR, "capacity must be 1 .. 2^30");
+    }
+}
+static int ng_check(tk_core* c, tk_ngram_set* st) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if (!st) return fail(TK_VALUE_ERROR, "set is null");
+    if (st->c != c) return fail(TK_VALUE_ERROR, "the n-gram set belongs to another core");
+    return TK_OK;
+}
+static TkNg ng_call(const tk_ngram_set* st, uint64_t n, uint64_t n_docs) {
+    TkNg p = st->p;
+    p.n_tokens = n, p.n_docs = n_docs;
+    return p;
+}
+static int ng_clear_run(tk_ngram_set* st, hipStream_t s) {
+    tk_core* c = st->c;
+    HIPCHK(hipStreamWaitEvent(s, st->done, 0));
+    TRY(timed(c, s, "tk_k_ng_clear", [&] {
+        hipLaunchKernelGGL(tk_k_ng_clear, dim3(grid_for(st->p.S, 256, 65536)), dim3(256), 0, s, st->table.as<unsigned long long>(), st->p.S, st->filter.as<uint32_t>(),
+                           tk_ng_filter_words(st->p.S), st->count.as<unsigned long long>());
+    }));
+    HIPCHK(hipEventRecord(st->done, s));
+    st->bound = 0;
+    return TK_OK;
+}
+// Is an add of n tokens refused?  Before anything is queued: the bound is the host's, no wait.
+static int ng_add_check(const tk_ngram_set* st, uint64_t n) {
+    if (n > st->capacity || st->bound > st->capacity - n)
+        return fail(TK_VALUE_ERROR, "an add of " + std::to_string(n) + " tokens to an n-gram set of capacity " + std::to_string(st->capacity) + " that may hold " +
+                                        std::to_string(st->bound) + " keys: count it (the bound falls to the exact number), clear it, or make a larger set");
+    return TK_OK;
+}
+// ng_add_run, ng_overlap_run: the caller holds c->mu.  Launches on s, and no wait of the host.
+static int ng_add_run(tk_ngram_set* st, hipStream_t s, const uint32_t* d_tok, uint64_t n, const uint64_t* d_tok_off, uint64_t n_docs) {
+    TRY(ng_add_check(st, n));
+    if (!n || !n_docs) return TK_OK;
+    tk_core* c = st->c;
+    const TkNg p = ng_call(st, n, n_docs);
+    HIPCHK(hipStreamWaitEvent(s, st->done, 0));
+    TRY(timed(c, s, "tk_k_ng_add", [&] {
+        hipLaunchKernelGGL(tk_k_ng_add, dim3((uint32_t)((n + TK_NG_TILE - 1) / TK_NG_TILE)), dim3(TK_NG_THREADS), 0, s, p, d_tok, d_tok_off, st->table.as<unsigned long long>(),
+                           st->filter.as<uint32_t>(), st->count.as<unsigned long long>());
+    }));
+    HIPCHK(hipEventRecord(st->done, s));
+    st->bound += n;
+    return TK_OK;
+}
+struct NgOuts {  // the caller's arrays (device memory for ng_overlap_run, host memory for ng_to_host); any may be null
+    uint64_t *n_hit, *n_covered, *n_ngrams, *first_hit;
+    uint8_t* mask;
+};
+static int ng_overlap_run(tk_ngram_set* st, hipStream_t s, const uint32_t* d_tok, uint64_t n, const uint64_t* d_tok_off, uint64_t n_docs, NgOuts o) {
+    if (n >= (1ull << 41)) return fail(TK_VALUE_ERROR, "n_tokens: 2^41 tokens or more");
+    const TkNgOut out{(unsigned long long*)o.n_hit, (unsigned long long*)o.n_covered, (unsigned long long*)o.n_ngrams, (unsigned long long*)o.first_hit, o.mask};
+    if (!n_docs || !(out.per_doc() || out.mask)) return TK_OK;
+    tk_core* c = st->c;
+    const TkNg p = ng_call(st, n, n_docs);
+    HIPCHK(hipStreamWaitEvent(s, st->done, 0));
+    if (out.per_doc()) TRY(timed(c, s, "tk_k_ng_fill", [&] { hipLaunchKernelGGL(tk_k_ng_fill, dim3(grid_for(n_docs, 256, 65536)), dim3(256), 0, s, p, d_tok_off, out); }));
+    if (n && (out.mask || out.n_hit || out.n_covered || out.first_hit))
+        TRY(timed(c, s, "tk_k_ng_overlap", [&] {
+            hipLaunchKernelGGL(tk_k_ng_overlap, dim3((uint32_t)((n + TK_NG_TILE - 1) / TK_NG_TILE)), dim3(TK_NG_THREADS), 0, s, p, d_tok, d_tok_off,
+                               st->table.as<unsigned long long>(), st->filter.as<uint32_t>(), out);
+        }));
+    HIPCHK(hipEventRecord(st->done, s));
+    return TK_OK;
+}
+// ng_overlap_run into st->out, then every array the caller asked for to the host (the caller holds c->mu; the stream is waited for);
+// mask_own: the mask as a library-owned array instead of h.mask
+static int ng_to_host(tk_ngram_set* st, hipStream_t s, const uint32_t* d_tok, uint64_t n, const uint64_t* d_tok_off, uint64_t n_docs, NgOuts h, uint8_t** mask_own = nullptr) {
+    Carve res;
+    const uint64_t at_hit = res.add(n_docs * 8), at_cov = res.add(n_docs * 8), at_ng = res.add(n_docs * 8), at_first = res.add(n_docs * 8), at_mask = res.add(n);
+    TRY(ensure(st->out, res.total + 16));
+    const bool mask = h.mask || mask_own;
+    const NgOuts d{h.n_hit ? carved<uint64_t>(st->out, at_hit) : nullptr, h.n_covered ? carved<uint64_t>(st->out, at_cov) : nullptr,
+                   h.n_ngrams ? carved<uint64_t>(st->out, at_ng) : nullptr, h.first_hit ? carved<uint64_t>(st->out, at_first) : nullptr,
+                   mask ? carved<uint8_t>(st->out, at_mask) : nullptr};
+    TRY(ng_overlap_run(st, s, d_tok, n, d_tok_off, n_docs, d));
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    ResultBag bag;
+    if (mask_own) TRY(bag.fetch(mask_own, d.mask, n_docs ? n : 0));
+    if (n_docs) {
+        if (h.n_hit) HIPCHK(hipMemcpy(h.n_hit, d.n_hit, n_docs * 8, hipMemcpyDeviceToHost));
+        if (h.n_covered) HIPCHK(hipMemcpy(h.n_covered, d.n_covered, n_docs * 8, hipMemcpyDeviceToHost));
+        if (h.n_ngrams) HIPCHK(hipMemcpy(h.n_ngrams, d.n_ngrams, n_docs * 8, hipMemcpyDeviceToHost));
+        if (h.first_hit) HIPCHK(hipMemcpy(h.first_hit, d.first_hit, n_docs * 8, hipMemcpyDeviceToHost));
+        if (h.mask && n) HIPCHK(hipMemcpy(h.mask, d.mask, n, hipMemcpyDeviceToHost));
+    }
+    bag.give();
+    return TK_OK;
+}
+// host ids and offsets into st->in, on the core's stream: run(d_tok, n, d_off) behind them, under the core's mutex
+template <class Run>
+static int ng_from_host(tk_core* c, tk_ngram_set* st, const uint32_t* tokens, const uint64_t* tok_off, uint64_t n_docs, Run&& run) {
+    TRY(ng_check(c, st));
+    if (!tok_off) return fail(TK_VALUE_ERROR, "null argument");
+    TRY(check_offsets(tok_off, n_docs, "tok_off"));
+    const uint64_t n = tok_off[n_docs];
+    if (n && !tokens) return fail(TK_VALUE_ERROR, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    TRY(run(nullptr, n, nullptr, /* ask */ true));  // (what can be refused before anything moves)
+    Carve in;
+    const uint64_t at_off = in.add((n_docs + 1) * 8), at_tok = in.add(n * 4);
+    TRY(ensure(st->in, in.total + 16));
+    uint64_t* d_off = carved<uint64_t>(st->in, at_off);
+    uint32_t* d_tok = carved<uint32_t>(st->in, at_tok);
+    HIPCHK(hipStreamWaitEvent(c->stream, st->done, 0));  // (st->in may still be read by a call on another stream)
+    HIPCHK(hipMemcpyAsync(d_off, tok_off, (n_docs + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    if (n) HIPCHK(hipMemcpyAsync(d_tok, tokens, n * 4, hipMemcpyHostToDevice, c->stream));
+    return drained(c, [&] { return run(d_tok, n, d_off, false); });
+}
+
+extern "C" void tk_ngram_set_destroy(tk_ngram_set* st) {
+    if (!st) return;
+    (void)hipSetDevice(st->device);
+    delete st;
+}
+extern "C" int tk_ngram_set_create(tk_core* c, uint32_t ngram, uint64_t seed, uint64_t capacity, tk_ngram_set** set_out) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if (!set_out) return fail(TK_VALUE_ERROR, "null argument");
+    TkNg p;
+    TRY(ng_refusal(tk_ng_shape(ngram, seed, capacity, &p)));
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    std::unique_ptr<tk_ngram_set, void (*)(tk_ngram_set*)> st(new tk_ngram_set, tk_ngram_set_destroy);
+    st->c = c, st->device = c->device, st->p = p, st->capacity = capacity;
+    HIPCHK(st->done.create());
+    TRY(ensure(st->table, p.S * 8));
+    TRY(ensure(st->filter, tk_ng_filter_words(p.S) * 4));
+    TRY(ensure(st->count, 8));
+    TRY(drained(c, [&] { return ng_clear_run(st.get(), c->stream); }));
+    *set_out = st.release();
+    return TK_OK;
+}
+extern "C" int tk_ngram_set_clear(tk_ngram_set* st) {
+    if (!st) return fail(TK_VALUE_ERROR, "set is null");
+    return device_pass(st->c, true, nullptr, [&](hipStream_t s) { return ng_clear_run(st, s); });
+}
+// The exact number of distinct keys: waits for the calls queued on the set, whatever their streams.
+extern "C" int tk_ngram_set_count(tk_ngram_set* st, uint64_t* count_out) {
+    if (!st) return fail(TK_VALUE_ERROR, "set is null");
+    if (!count_out) return fail(TK_VALUE_ERROR, "null argument");
+    return device_pass(st->c, true, nullptr, [&](hipStream_t) -> int {
+        HIPCHK(hipEventSynchronize(st->done));
+        uint64_t n = 0;
+        HIPCHK(hipMemcpy(&n, st->count.p, 8, hipMemcpyDeviceToHost));
+        if (n > st->capacity) return fail(TK_RUNTIME_ERROR, "internal error: the n-gram set holds more keys than its capacity");
+        *count_out = st->bound = n;
+        return TK_OK;
+    });
+}
+
+extern "C" int tk_ngram_add_device(tk_core* c, tk_ngram_set* st, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_docs, void* stream) {
+    TRY(ng_check(c, st));
+    // (the stream as given, null being HIP's null stream: tk_fingerprint_device's convention)
+    return device_pass(c, d_tok_off && (d_tokens || !n_tokens), stream,
+                       [&](hipStream_t) { return ng_add_run(st, (hipStream_t)stream, (const uint32_t*)d_tokens, n_tokens, (const uint64_t*)d_tok_off, n_docs); });
+}
+extern "C" int tk_ngram_add(tk_core* c, tk_ngram_set* st, const uint32_t* tokens, const uint64_t* tok_off, uint64_t n_docs) {
+    return ng_from_host(c, st, tokens, tok_off, n_docs, [&](const uint32_t* d_tok, uint64_t n, const uint64_t* d_off, bool ask) -> int {
+        if (ask) return ng_add_check(st, n);
+        TRY(ng_add_run(st, c->stream, d_tok, n, d_off, n_docs));
+        HIPCHK(hipStreamSynchronize(c->stream));  // (the caller's arrays are his again)
+        return TK_OK;
+    });
+}
+extern "C" int tk_ngram_overlap_device(tk_core* c, tk_ngram_set* st, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_docs, void* stream,
+                                       uint64_t* d_n_hit, uint64_t* d_n_covered, uint64_t* d_n_ngrams, uint64_t* d_first_hit, uint8_t* d_mask) {
+    TRY(ng_check(c, st));
+    return device_pass(c, d_tok_off && (d_tokens || !n_tokens), stream, [&](hipStream_t) {
+        return ng_overlap_run(st, (hipStream_t)stream, (const uint32_t*)d_tokens, n_tokens, (const uint64_t*)d_tok_off, n_docs,
+                              NgOuts{d_n_hit, d_n_covered, d_n_ngrams, d_first_hit, d_mask});
+    });
+}
+extern "C" int tk_ngram_overlap(tk_core* c, tk_ngram_set* st, const uint32_t* tokens, const uint64_t* tok_off, uint64_t n_docs, uint64_t* n_hit_out, uint64_t* n_covered_out,
+                                uint64_t* n_ngrams_out, uint64_t* first_hit_out, uint8_t* mask_out) {
+    return ng_from_host(c, st, tokens, tok_off, n_docs, [&](const uint32_t* d_tok, uint64_t n, const uint64_t* d_off, bool ask) -> int {
+        if (ask) return TK_OK;
+        return ng_to_host(st, c->stream, d_tok, n, d_off, n_docs, NgOuts{n_hit_out, n_covered_out, n_ngrams_out, first_hit_out, mask_out});
+    });
+}
+// tk_encode_batch (tk_encode_batch_checked with disallowed ids), then the add, or the overlap, over the ids it has just produced: the ids
+// never come back.
+extern "C" int tk_encode_batch_ngram_add(tk_core* c, tk_ngram_set* st, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special,
+                                         const uint32_t* allowed_ids, uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed, uint64_t* n_tokens_out,
+                                         tk_special_hit* hit) {
+    TRY(ng_check(c, st));
+    return encode_batch_pass(
+        c, utf8, doc_off, n_docs, use_special, allowed_ids, n_allowed, disallowed_ids, n_disallowed, hit, true, [&] { return TK_OK; },
+        [&](uint64_t n) -> int {  // (refused, if it is, before anything is written to the set)
+            TRY(ng_add_run(st, c->stream, c->out_tokens.as<uint32_t>(), n, c->out_tok_off.as<uint64_t>(), n_docs));
+            HIPCHK(hipStreamSynchronize(c->stream));  // (the core's ids are the next call's)
+            return TK_OK;
+        },
+        [&](uint64_t n) {
+            if (n_tokens_out) *n_tokens_out = n;
+            return TK_OK;
+        });
+}
+extern "C" int tk_encode_batch_overlap(tk_core* c, tk_ngram_set* st, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special,
+                                       const uint32_t* allowed_ids, uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed, uint64_t* n_hit_out,
+                                       uint64_t* n_covered_out, uint64_t* n_ngrams_out, uint64_t* first_hit_out, uint64_t* tok_off_out, uint8_t** mask_out,
+                                       uint64_t* n_tokens_out, tk_special_hit* hit) {
+    TRY(ng_check(c, st));
+    return encode_batch_pass(
+        c, utf8, doc_off, n_docs, use_special, allowed_ids, n_allowed, disallowed_ids, n_disallowed, hit, !mask_out || n_tokens_out, [&] { return TK_OK; },
+        [&](uint64_t n) {
+            return ng_to_host(st, c->stream, c->out_tokens.as<uint32_t>(), n, c->out_tok_off.as<uint64_t>(), n_docs,
+                              NgOuts{n_hit_out, n_covered_out, n_ngrams_out, first_hit_out, nullptr}, mask_out);
+        },
+        [&](uint64_t n) -> int {
+            if (tok_off_out) HIPCHK(hipMemcpy(tok_off_out, c->out_tok_off.p, (n_docs + 1) * 8, hipMemcpyDeviceToHost));
+            if (n_tokens_out) *n_tokens_out = n;
+            return TK_OK;
+        });
+}
+
+// ------------------------------------------------------------------------------------------
 // Supervised samples (tk_samples.h): a packed batch of parts on the device -> one row per sample, ids, mask and labels as [R, W].
 // ------------------------------------------------------------------------------------------
 static_assert(TK_SMP_KEEP_TAIL == TK_SMPF_KEEP_TAIL && TK_SMP_LEFT == TK_SMPF_LEFT, "tk_smp_spec flags");
@@ -5579,6 +5817,7 @@ extern "C" uint64_t tk_stat(tk_core* c, const char* name) {
     if (k == "split_stitch_steps") return c->st_split[TK_SPLIT_ST_STITCH];    // ... steps of the stitch pass (one wavefront per document, in order)
     if (k == "split_spec_steps") return c->st_split[TK_SPLIT_ST_SPEC];        // ... steps of the speculative walks
     if (k == "fingerprint_tile") return TK_FP_TILE;  // token positions of a tile of the fingerprint pass (tk_fingerprint_rule.h)
+    if (k == "ngram_tile") return TK_NG_TILE;  // token positions of a tile of the n-gram passes (tk_ngram_rule.h)
     if (k == "select_tile") return TK_SEL_TILE;  // output positions of a tile of the selection's copy (tk_groups_rule.h)
     if (k == "jsonl_tile") return TK_JSONL_TILE;  // bytes of a tile of the JSON Lines passes (tk_jsonl_rule.h)
     if (k == "regrown") return c->st_regrown;  // batches repeated with a larger miss data since the core was made (encode_device_locked)
