@@ -533,6 +533,47 @@ int tk_encode_batch_ngram_add(tk_core* core, tk_ngram_set* set, const uint8_t* u
 int tk_encode_batch_overlap(tk_core* core, tk_ngram_set* set, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special, const uint32_t* allowed_ids,
                             uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed, uint64_t* n_hit_out, uint64_t* n_covered_out,
                             uint64_t* n_ngrams_out, uint64_t* first_hit_out, uint64_t* tok_off_out, uint8_t** mask_out, uint64_t* n_tokens_out, tk_special_hit* hit);
+/* Repetition statistics: per document of a packed batch and per n-gram size of a list, the counts of the repetition rules that every
+ * corpus build runs (Gopher, Rae et al. 2021, table A1, and RefinedWeb, FineWeb, Dolma after it): drop a document whose most frequent
+ * 2-, 3- or 4-gram makes up more than a set share of it, or of which more than a set share lies inside 5- to 10-grams that occur more
+ * than once in it.  Replaces nothing in the reference: it is the host step of the reference's users between "dedup" and "pack rows", a
+ * Counter of tuples per document and size -- here on ids that are on the device anyway.  The survivors go on through
+ * tk_select_docs_device, which takes any keep mask.
+ * The rule.  Input: tokens uint32[T], tok_off uint64[n_docs + 1], and sizes: 1 to 8 values k, each in 1 .. 32, in any order, repeats
+ *  allowed (a repeated size is computed again).  For a document d of L tokens and a size k:
+ *  N-grams.  They start at the first max(L - k + 1, 0) positions of d, one each, over k ids.  None crosses a document boundary.
+ *  Equality.  Two n-grams of a document are equal when their k ids are equal.  A hash (tk_fingerprint's shingle hash under a fixed seed)
+ *   only chooses where in a table to look; the ids decide.  So the result is exact, with no 2^-64 clause, and a function of
+ *   (tokens, tok_off, sizes) alone, never of the schedule.  N-grams of different documents are never compared.
+ *  Outputs, uint64[n_docs, n_sizes], row-major, any pointer may be null:
+ *   n_ngrams       the number of starts;
+ *   n_distinct     the number of distinct n-grams;
+ *   n_dup          the starts whose n-gram occurs at least twice in d;
+ *   n_dup_covered  the tokens of d that lie inside the n-gram of at least one such start -- a union, counted once: Gopher's "duplicate
+ *                  n-gram fraction" times L, in tokens;
+ *   top_count      the occurrences of the most frequent n-gram, 0 when there is none: Gopher's "top n-gram fraction" is top_count k / L.
+ *  Refused with TK_VALUE_ERROR, and nothing written: no size, more than 8 sizes, a size outside 1 .. 32; a document of 2^31 tokens or
+ *   more (the entries that see tok_off on the host; tk_repetition_device cannot look and writes zeros for such a document).
+ * Documents of at most tk_stat("repeat_lds_tokens") tokens are counted in a table in the CU's LDS by the workgroup of the tile of
+ * tk_stat("repeat_tile") positions in which they start.  Longer ones are counted in a table in device memory that the core owns and
+ * grows on demand, 32 bytes per token it must cover: the positions from the first long document to the last for the entries that see
+ * tok_off on the host (none when no document is long), all n_tokens for tk_repetition_device -- 2 GB for a batch of 63 M ids.  Calls that
+ * share it are ordered on the device by an event, whatever their streams.
+ * NOT built: a per-token mask; line- and paragraph-level repetition; n-grams of words; several GPUs; more than 8 sizes per call. */
+/* Device pointers in (ids uint32, d_tok_off uint64[n_docs + 1], not checked), `sizes` a host array; the caller's device arrays out.
+ * Stream and waiting as tk_fingerprint_device: everything is queued on `stream`, null being HIP's null stream, and the call returns
+ * without waiting. */
+int tk_repetition_device(tk_core* core, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_docs, const uint32_t* sizes, uint64_t n_sizes, void* stream,
+                         uint64_t* d_n_ngrams, uint64_t* d_n_distinct, uint64_t* d_n_dup, uint64_t* d_n_dup_covered, uint64_t* d_top_count);
+/* The same from host arrays to the caller's host arrays; a tok_off that does not ascend from 0 is TK_VALUE_ERROR. */
+int tk_repetition(tk_core* core, const uint32_t* tokens, const uint64_t* tok_off, uint64_t n_docs, const uint32_t* sizes, uint64_t n_sizes, uint64_t* n_ngrams_out,
+                  uint64_t* n_distinct_out, uint64_t* n_dup_out, uint64_t* n_dup_covered_out, uint64_t* top_count_out);
+/* tk_encode_batch -- with n_disallowed != 0: tk_encode_batch_checked -- and the statistics over the ids while they are on the device:
+ * the ids never come back.  tok_off_out (n_docs + 1) and *n_tokens_out may be null.  On TK_DISALLOWED_SPECIAL nothing is handed out. */
+int tk_encode_batch_repetition(tk_core* core, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special, const uint32_t* allowed_ids, uint64_t n_allowed,
+                               const uint32_t* disallowed_ids, uint64_t n_disallowed, const uint32_t* sizes, uint64_t n_sizes, uint64_t* n_ngrams_out,
+                               uint64_t* n_distinct_out, uint64_t* n_dup_out, uint64_t* n_dup_covered_out, uint64_t* top_count_out, uint64_t* tok_off_out,
+                               uint64_t* n_tokens_out, tk_special_hit* hit);
 /* Supervised samples: a packed batch whose documents are the PARTS of samples -- the messages of a conversation, a prompt and its answer --
  * -> one row per sample with the template's ids around every part, an attention mask and labels.  Replaces nothing in the reference: it is
  * the host loop of the reference's users, the fine-tuning script that calls encode_ordinary once per message, adds header and footer ids and
@@ -988,7 +1029,8 @@ void tk_last_stats(tk_core* core, uint64_t* n_bytes, uint64_t* n_pieces, uint64_
  * (document parts per block of K positions), "split_joined" (blocks in which the true chain met the speculative walk), "split_stitch_steps"
  * (steps of the stitch pass) and "split_spec_steps" (steps of the speculative walks); "jsonl_tile": the bytes of a tile of the JSON Lines
  * passes (a constant of the build); "fingerprint_tile": the token positions of a tile of the fingerprint pass, "ngram_tile": of the
- * n-gram passes (likewise). */
+ * n-gram passes (likewise); "repeat_tile" and "repeat_lds_tokens": of the repetition pass, the positions of a tile of its LDS class and
+ * the longest document that class takes (likewise). */
 uint64_t tk_stat(tk_core* core, const char* name);
 
 #ifdef __cplusplus

@@ -204,6 +204,13 @@ def lib() -> ctypes.CDLL:
             L.tk_encode_batch_ngram_add.argtypes = [vp, vp, vp, vp, u64, i32, vp, u64, vp, u64, P(u64), P(SpecialHit)]
             L.tk_encode_batch_overlap.restype = i32
             L.tk_encode_batch_overlap.argtypes = [vp, vp, vp, vp, u64, i32, vp, u64, vp, u64, vp, vp, vp, vp, vp, P(vp), P(u64), P(SpecialHit)]
+        if hasattr(L, "tk_repetition_device"):  # (absent from older builds selected through $TIKTOKEN_AMD_LIB)
+            L.tk_repetition_device.restype = i32
+            L.tk_repetition_device.argtypes = [vp, vp, u64, vp, u64, vp, u64, vp, vp, vp, vp, vp, vp]
+            L.tk_repetition.restype = i32
+            L.tk_repetition.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp, vp, vp, vp]
+            L.tk_encode_batch_repetition.restype = i32
+            L.tk_encode_batch_repetition.argtypes = [vp, vp, vp, u64, i32, vp, u64, vp, u64, vp, u64, vp, vp, vp, vp, vp, vp, P(u64), P(SpecialHit)]
         if hasattr(L, "tk_jsonl_extract_device"):  # (absent from older builds selected through $TIKTOKEN_AMD_LIB)
             L.tk_jsonl_extract_device.restype = i32
             L.tk_jsonl_extract_device.argtypes = [vp, vp, u64, vp, u64, u32, vp, *[P(vp)] * 5, *[P(u64)] * 3, P(JsonlBad)]

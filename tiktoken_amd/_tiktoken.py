@@ -746,6 +746,49 @@ class NgramOverlap(NamedTuple):
         return keep
 
 
+class RepetitionStats(NamedTuple):
+    """Repetition statistics of a batch (tk_repetition; the rule: include/tiktoken_amd.h): `sizes` the n-gram sizes, one column each;
+    `length` uint64[n] the documents' tokens; and uint64[n, len(sizes)] each: `n_ngrams` the n-grams of a document, `n_distinct` the
+    distinct ones, `n_dup` the starts whose n-gram occurs at least twice in the document, `n_dup_covered` the tokens inside at least one
+    such n-gram (a union), `top_count` the occurrences of the most frequent n-gram.  Exact: equal n-grams are equal ids."""
+    sizes: "tuple[int, ...]"
+    length: np.ndarray
+    n_ngrams: np.ndarray
+    n_distinct: np.ndarray
+    n_dup: np.ndarray
+    n_dup_covered: np.ndarray
+    top_count: np.ndarray
+
+    def _column(self, k: int) -> int:
+        if k not in self.sizes:
+            raise KeyError(k)
+        return self.sizes.index(k)
+
+    def top_fraction(self, k: int) -> np.ndarray:
+        """float64[n]: top_count * k / length, the share of a document that its most frequent k-gram makes up (0 for an empty one)."""
+        length = self.length.astype(np.float64)
+        return np.divide(self.top_count[:, self._column(k)].astype(np.float64) * k, length, out=np.zeros_like(length), where=length > 0)
+
+    def dup_fraction(self, k: int) -> np.ndarray:
+        """float64[n]: n_dup_covered / length, the share of a document inside k-grams that occur more than once in it (0 for an empty one)."""
+        length = self.length.astype(np.float64)
+        return np.divide(self.n_dup_covered[:, self._column(k)].astype(np.float64), length, out=np.zeros_like(length), where=length > 0)
+
+    def keep_mask(self, max_top_fraction=None, max_dup_fraction=None) -> np.ndarray:
+        """uint8[n], what `select_docs_device` takes: 1 for the documents whose `top_fraction(k)` is at most max_top_fraction[k] and whose
+        `dup_fraction(k)` is at most max_dup_fraction[k], for every k of the two dicts -- by default the thresholds of the Gopher rules,
+        {2: .20, 3: .18, 4: .16} and {5: .15, ..., 10: .10}.  The fractions here are in tokens, where Gopher's are in characters of words.
+        Empty documents are kept; a size that was not computed raises KeyError."""
+        top = {2: .20, 3: .18, 4: .16} if max_top_fraction is None else max_top_fraction
+        dup = {5: .15, 6: .14, 7: .13, 8: .12, 9: .11, 10: .10} if max_dup_fraction is None else max_dup_fraction
+        keep = np.ones(len(self.length), dtype=bool)
+        for k, limit in top.items():
+            keep &= self.top_fraction(k) <= float(limit)
+        for k, limit in dup.items():
+            keep &= self.dup_fraction(k) <= float(limit)
+        return keep.astype(np.uint8)
+
+
 class NativeNgramSet:
     """A tk_ngram_set; made by `CoreBPE.ngram_set_create`.  Keeps its core alive: the set must go first."""
 
@@ -1967,6 +2010,56 @@ class CoreBPE:
                                              ctypes.byref(n_tok), ctypes.byref(hit))
         self._raise_for(rc, hit)
         return NgramOverlap(*out, np.diff(tok_off), self._own_mask(m, int(n_tok.value)) if mask else None)
+
+    # ------------------------------------------------------------------ repetition statistics (no reference counterpart: a Counter per document on the host)
+    def repetition_device(self, tokens, tok_off, sizes, *, n_ngrams=None, n_distinct=None, n_dup=None, n_dup_covered=None, top_count=None,
+                          stream: int | None = None) -> None:
+        """Repetition statistics of a packed batch that is on the device (tk_repetition_device): torch tensors on this core's GPU, taken by
+        pointer -- `tokens` (32-bit, T) and `tok_off` (64-bit, n + 1, ascending from 0 to T) in; the caller's tensors out, 64-bit,
+        [n, len(sizes)], any of which may be None.  At most 8 `sizes`, each 1 .. 32.  Stream and waiting as in `fingerprint_device`:
+        queued on `stream`, and the call does not wait.  This entry cannot see tok_off, so the core keeps 32 bytes of device memory per
+        token of the batch for the documents longer than stat("repeat_lds_tokens")."""
+        self._one_device("repetition_device")
+        n, T = tok_off.numel() - 1, tokens.numel()
+        if n < 0:
+            raise ValueError("tok_off must hold n_docs + 1 entries")
+        ks = np.ascontiguousarray(sizes, dtype=np.uint32)
+        outs = (n_ngrams, n_distinct, n_dup, n_dup_covered, top_count)
+        names = ("n_ngrams", "n_distinct", "n_dup", "n_dup_covered", "top_count")
+        stream = self._on_gpu((("tokens", tokens, 4, T), ("tok_off", tok_off, 8, n + 1), *[(m, o, 8, n * len(ks)) for m, o in zip(names, outs)]), stream)
+        ptr = [t.data_ptr() if t is not None and t.numel() else None for t in outs]
+        _lib.raise_for(self._L.tk_repetition_device(self._h, tokens.data_ptr() if T else None, T, tok_off.data_ptr(), n, ks.ctypes.data, len(ks), stream or None, *ptr))
+
+    @staticmethod
+    def _rp_outs(n: int, m: int):
+        """the five result arrays for n documents and m sizes, to be filled by the library (one spare element each: no empty array's pointer)"""
+        return tuple(np.zeros(n * m + 1, dtype=np.uint64)[:n * m].reshape(n, m) for _ in range(5))
+
+    def repetition_packed(self, tokens: np.ndarray, tok_off: np.ndarray, sizes) -> RepetitionStats:
+        """Repetition statistics of packed tokens (tk_repetition): host arrays in, a `RepetitionStats` out.  At most 8 sizes."""
+        self._one_device("repetition_packed")
+        tokens, tok_off = self._packed_tokens(tokens, tok_off)
+        ks = np.ascontiguousarray(sizes, dtype=np.uint32)
+        n = len(tok_off) - 1
+        out = self._rp_outs(n, len(ks))
+        _lib.raise_for(self._L.tk_repetition(self._h, tokens.ctypes.data if len(tokens) else None, tok_off.ctypes.data, n, ks.ctypes.data, len(ks),
+                                             *[a.ctypes.data for a in out]))
+        return RepetitionStats(tuple(int(k) for k in ks), np.diff(tok_off), *out)
+
+    def encode_batch_repetition_packed(self, blob: np.ndarray, doc_off: np.ndarray, allowed_special: AbstractSet[str] | None = None, *, sizes,
+                                       disallowed_special=None) -> RepetitionStats:
+        """`encode_batch_packed` with the repetition statistics of its result taken while the ids are on the device
+        (tk_encode_batch_repetition): the ids stay there.  The special-token arguments as in `encode_batch_packed`."""
+        self._one_device("encode_batch_repetition_packed")
+        text, dis, n_docs, _keep = self._batch_args(blob, doc_off, allowed_special, disallowed_special)
+        ks = np.ascontiguousarray(sizes, dtype=np.uint32)
+        hit, n_tok = _lib.SpecialHit(), ctypes.c_uint64()
+        out = self._rp_outs(n_docs, len(ks))
+        tok_off = np.zeros(n_docs + 1, dtype=np.uint64)
+        rc = self._L.tk_encode_batch_repetition(self._h, *text, *dis, ks.ctypes.data, len(ks), *[a.ctypes.data for a in out], tok_off.ctypes.data, ctypes.byref(n_tok),
+                                                ctypes.byref(hit))
+        self._raise_for(rc, hit)
+        return RepetitionStats(tuple(int(k) for k in ks), np.diff(tok_off), *out)
 
     # ------------------------------------------------------------------ supervised samples (no reference counterpart: the host loop of its users)
     @staticmethod

@@ -406,6 +406,44 @@ class Encoding:
         """Tokens that are packed already (`tokens` uint32[T], `tok_off` uint64[n + 1]) without their near-duplicates."""
         return self._core_bpe.dedup_packed(tokens, tok_off, threshold, ngram=ngram, n_perm=n_perm, bands=bands, seed=seed)
 
+    # ------------------------------------------------------------------ repetition statistics
+    def _repetition(self, sizes, call) -> "_tiktoken.RepetitionStats":
+        """call(sizes) for at most 8 sizes at a time (the library's cap), the columns joined"""
+        sizes = tuple(int(k) for k in sizes)
+        parts = [call(sizes[i:i + 8]) for i in range(0, len(sizes), 8)] or [call(sizes)]  # (no size: the library's refusal)
+        if len(parts) == 1:
+            return parts[0]
+        return _tiktoken.RepetitionStats(sizes, parts[0].length, *[np.concatenate([p[i] for p in parts], axis=1) for i in range(2, 7)])
+
+    def repetition_ordinary_batch(self, text: Sequence[str], sizes=(2, 3, 4, 5, 6, 7, 8, 9, 10)) -> "_tiktoken.RepetitionStats":
+        """Repetition statistics of a batch, ignoring special tokens: every text is encoded and, while its ids are on the GPU, its n-grams
+        of every size of `sizes` (each 1 .. 32) are counted exactly, per document: how many there are, how many distinct, how many starts
+        repeat an n-gram of the document, how many tokens lie inside such a repeat, and how often the most frequent one occurs -- the
+        figures of the Gopher repetition rules; the ids never come back.  Returns a `RepetitionStats`, whose `keep_mask` says which
+        documents pass.  More than 8 sizes are several calls, each of which encodes again.  The rule is stated in include/tiktoken_amd.h."""
+        blob, off = self._pack(text)
+        return self._repetition(sizes, lambda ks: self._core_bpe.encode_batch_repetition_packed(blob, off, None, sizes=ks))
+
+    def repetition_batch(self, text: Sequence[str], sizes=(2, 3, 4, 5, 6, 7, 8, 9, 10), *, allowed_special: Literal["all"] | AbstractSet[str] = set(),  # noqa: B006
+                         disallowed_special: Literal["all"] | Collection[str] = "all") -> "_tiktoken.RepetitionStats":
+        """`repetition_ordinary_batch` with the special-token arguments of `encode` -- the policy, and the error, of `encode_batch_packed`."""
+        allowed_special, disallowed_special = self._special_policy(allowed_special, disallowed_special)
+        blob, off, repaired = self._pack_repaired(text)
+        if disallowed_special and not isinstance(disallowed_special, frozenset):
+            disallowed_special = frozenset(disallowed_special)
+        dis = None
+        if disallowed_special:
+            if repaired or not all(t in self._special_tokens for t in disallowed_special):  # (as encode_batch_packed: the host's search)
+                for t in text:
+                    self._reject_disallowed(t, disallowed_special)
+            else:
+                dis = disallowed_special
+        return self._repetition(sizes, lambda ks: self._core_bpe.encode_batch_repetition_packed(blob, off, allowed_special, sizes=ks, disallowed_special=dis))
+
+    def repetition_tokens_packed(self, tokens, tok_off, sizes=(2, 3, 4, 5, 6, 7, 8, 9, 10)) -> "_tiktoken.RepetitionStats":
+        """The repetition statistics of tokens that are packed already (`tokens` uint32[T], `tok_off` uint64[n + 1])."""
+        return self._repetition(sizes, lambda ks: self._core_bpe.repetition_packed(tokens, tok_off, ks))
+
     # ------------------------------------------------------------------ token n-gram sets
     def ngram_set(self, ngram: int = 13, *, capacity: int, seed: int = 0) -> "NgramSet":
         """An empty set of token n-grams that lives on the GPU across calls (tk_ngram_set_create): the n-grams of evaluation benchmarks,

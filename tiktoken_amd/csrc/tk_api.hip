@@ -33,6 +33,7 @@
 #include "tk_fingerprint.h"
 #include "tk_groups.h"
 #include "tk_ngram.h"
+#include "tk_repeat.h"
 #include "tk_jsonl.h"
 #include "tk_sample_rows.h"
 #include "tk_samples.h"
@@ -306,6 +307,12 @@ struct tk_core {
     // host groups call; d_dedup: everything between the ids and the survivors of a host dedup call (it waits before it returns).
     Buf d_grp, d_sel, d_grp_in, d_dedup;
     Event grp_done, sel_done;
+    // Repetition statistics (tk_repeat.h), apart from everything above: d_rp: the long class's table, 32 bytes per token it covers;
+    // d_rp_flag: the word that says whether the running call has a long document (the serial number of the last call that had one);
+    // d_rp_in, d_rp_out: tokens and tok_off, and the five result arrays, of the host entries.  rp_done: as fp_done, for all four.
+    Buf d_rp, d_rp_flag, d_rp_in, d_rp_out;
+    Event rp_done;
+    uint64_t rp_serial = 0;
     uint64_t st_split[TK_SPLIT_STATS] = {0, 0, 0, 0};
     // Supervised samples (tk_samples.h), apart from everything above: d_smp: ids, labels and mask of every position; d_smp_row: full_len, len,
     // n_trained of every sample; d_smp_cnt: the TK_SMP_WORDS report words, the role table, pstart and the per-sample figures a call counts in
@@ -3950,6 +3957,152 @@ extern "C" int tk_encode_batch_overlap(tk_core* c, tk_ngram_set* st, const uint8
 }
 
 // ------------------------------------------------------------------------------------------
+// Repetition statistics (tk_repeat.h): a packed batch on the device -> per document and n-gram size the counts of the repetition rules.
+// ------------------------------------------------------------------------------------------
+struct RpOuts {  // the caller's arrays, uint64[n_docs, n_sizes] (device memory for rp_run, host memory for rp_to_host); any may be null
+    uint64_t *n_ngrams, *n_distinct, *n_dup, *n_cov, *top;
+    bool any() const { return n_ngrams || n_distinct || n_dup || n_cov || top; }
+};
+static int rp_shape(const uint32_t* sizes, uint64_t n_sizes, uint64_t n, uint64_t n_docs, TkRp* p) {
+    switch (tk_rp_shape(sizes, n_sizes, n, n_docs, p)) {
+        case 0: return TK_OK;
+        case 1: return fail(TK_VALUE_ERROR, "sizes: 1 .. 8 n-gram sizes per call");
+        default: return fail(TK_VALUE_ERROR, "sizes: every n-gram size must be 1 .. 32");
+    }
+}
+static int rp_check_sizes(const uint32_t* sizes, uint64_t n_sizes) {
+    TkRp p;
+    return rp_shape(sizes, n_sizes, 0, 0, &p);
+}
+// What a tok_off on the host says: the range of positions [*lo, *hi) from the first long document to the last (empty: none); refused: a
+// document of 2^31 tokens or more.
+static int rp_long_range(const uint64_t* tok_off, uint64_t n_docs, uint64_t* lo, uint64_t* hi) {
+    *lo = *hi = 0;
+    bool any = false;
+    for (uint64_t d = 0; d < n_docs; ++d) {
+        const uint64_t L = tok_off[d + 1] - tok_off[d];
+        if (L >= TK_RP_MAX_DOC) return fail(TK_VALUE_ERROR, "document " + std::to_string(d) + " has 2^31 tokens or more");
+        if (!tk_rp_is_long(L)) continue;
+        if (!any) *lo = tok_off[d];
+        any = true, *hi = tok_off[d + 1];
+    }
+    return TK_OK;
+}
+// rp_run: the caller holds c->mu.  Launches on s, and no wait of the host.  [lo, hi): the positions the long class's table must cover --
+// the whole batch for a caller who has not seen tok_off, nothing where there is no long document (then its launches are left out).
+static int rp_run(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n, const uint64_t* d_tok_off, uint64_t n_docs, const uint32_t* sizes, uint64_t n_sizes, RpOuts o,
+                  uint64_t lo, uint64_t hi) {
+    TkRp p;
+    TRY(rp_shape(sizes, n_sizes, n, n_docs, &p));
+    if (n >= (1ull << 41)) return fail(TK_VALUE_ERROR, "n_tokens: 2^41 tokens or more");
+    if (!n_docs || !o.any()) return TK_OK;
+    p.base = lo, p.end = hi;
+    if (!c->rp_done.e) HIPCHK(c->rp_done.create());
+    HIPCHK(hipStreamWaitEvent(s, c->rp_done, 0));  // (the table, the flag and the host entries' buffers are the core's)
+    if (!c->d_rp_flag.p) {
+        TRY(ensure(c->d_rp_flag, 16));
+        HIPCHK(hipMemset(c->d_rp_flag.p, 0, 16));
+    }
+    if (hi > lo) TRY(ensure(c->d_rp, 32 * (hi - lo)));
+    const TkRpOut out{(unsigned long long*)o.n_ngrams, (unsigned long long*)o.n_distinct, (unsigned long long*)o.n_dup, (unsigned long long*)o.n_cov, (unsigned long long*)o.top};
+    unsigned long long* flag = c->d_rp_flag.as<unsigned long long>();
+    unsigned long long* table = c->d_rp.as<unsigned long long>();
+    const unsigned long long serial = ++c->rp_serial;
+    TRY(timed(c, s, "tk_k_rp_fill", [&] { hipLaunchKernelGGL(tk_k_rp_fill, dim3(grid_for(n_docs, 256, 65536)), dim3(256), 0, s, p, d_tok_off, out, flag, serial); }));
+    TRY(timed(c, s, "tk_k_rp_lds", [&] { hipLaunchKernelGGL(tk_k_rp_lds, dim3((uint32_t)(n / TK_RP_TILE + 1)), dim3(TK_RP_THREADS), 0, s, p, d_tok, d_tok_off, out); }));
+    if (hi > lo) {
+        const dim3 grid((uint32_t)((n + TK_RP_LTILE - 1) / TK_RP_LTILE)), block(TK_RP_LTHREADS);
+        for (uint32_t si = 0; si < p.n_sizes; ++si) {
+            TRY(timed(c, s, "tk_k_rp_long_clear", [&] { hipLaunchKernelGGL(tk_k_rp_long_clear, grid, block, 0, s, p, d_tok_off, table, flag, serial); }));
+            TRY(timed(c, s, "tk_k_rp_long_insert", [&] { hipLaunchKernelGGL(tk_k_rp_long_insert, grid, block, 0, s, p, p.k[si], d_tok, d_tok_off, table, flag, serial); }));
+            TRY(timed(c, s, "tk_k_rp_long_count", [&] { hipLaunchKernelGGL(tk_k_rp_long_count, grid, block, 0, s, p, si, d_tok, d_tok_off, table, out, flag, serial); }));
+        }
+    }
+    HIPCHK(hipEventRecord(c->rp_done, s));
+    return TK_OK;
+}
+// rp_run into c->d_rp_out, then every array the caller asked for to the host (the caller holds c->mu; the stream is waited for)
+static int rp_to_host(tk_core* c, hipStream_t s, const uint32_t* d_tok, uint64_t n, const uint64_t* d_tok_off, uint64_t n_docs, const uint32_t* sizes, uint64_t n_sizes, RpOuts h,
+                      uint64_t lo, uint64_t hi) {
+    TRY(rp_check_sizes(sizes, n_sizes));
+    const uint64_t bytes = n_docs * n_sizes * 8;
+    uint64_t* const hp[5] = {h.n_ngrams, h.n_distinct, h.n_dup, h.n_cov, h.top};
+    uint64_t* dp[5];
+    Carve res;
+    uint64_t at[5];
+    for (int i = 0; i < 5; ++i) at[i] = res.add(bytes);
+    TRY(ensure(c->d_rp_out, res.total + 16));
+    for (int i = 0; i < 5; ++i) dp[i] = hp[i] ? carved<uint64_t>(c->d_rp_out, at[i]) : nullptr;
+    TRY(rp_run(c, s, d_tok, n, d_tok_off, n_docs, sizes, n_sizes, RpOuts{dp[0], dp[1], dp[2], dp[3], dp[4]}, lo, hi));
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    for (int i = 0; i < 5; ++i)
+        if (hp[i] && bytes) HIPCHK(hipMemcpy(hp[i], dp[i], bytes, hipMemcpyDeviceToHost));
+    return TK_OK;
+}
+
+extern "C" int tk_repetition_device(tk_core* c, const void* d_tokens, uint64_t n_tokens, const void* d_tok_off, uint64_t n_docs, const uint32_t* sizes, uint64_t n_sizes,
+                                    void* stream, uint64_t* d_n_ngrams, uint64_t* d_n_distinct, uint64_t* d_n_dup, uint64_t* d_n_dup_covered, uint64_t* d_top_count) {
+    // (the stream as given, null being HIP's null stream: tk_fingerprint_device's convention)
+    return device_pass(c, d_tok_off && (d_tokens || !n_tokens), stream, [&](hipStream_t) {
+        return rp_run(c, (hipStream_t)stream, (const uint32_t*)d_tokens, n_tokens, (const uint64_t*)d_tok_off, n_docs, sizes, n_sizes,
+                      RpOuts{d_n_ngrams, d_n_distinct, d_n_dup, d_n_dup_covered, d_top_count}, 0, n_tokens);
+    });
+}
+
+extern "C" int tk_repetition(tk_core* c, const uint32_t* tokens, const uint64_t* tok_off, uint64_t n_docs, const uint32_t* sizes, uint64_t n_sizes, uint64_t* n_ngrams_out,
+                             uint64_t* n_distinct_out, uint64_t* n_dup_out, uint64_t* n_dup_covered_out, uint64_t* top_count_out) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if (!tok_off) return fail(TK_VALUE_ERROR, "null argument");
+    TRY(rp_check_sizes(sizes, n_sizes));
+    TRY(check_offsets(tok_off, n_docs, "tok_off"));
+    uint64_t lo, hi;
+    TRY(rp_long_range(tok_off, n_docs, &lo, &hi));
+    const uint64_t n = tok_off[n_docs];
+    if (n && !tokens) return fail(TK_VALUE_ERROR, "null argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->rp_done.e) HIPCHK(c->rp_done.create());
+    Carve in;
+    const uint64_t at_off = in.add((n_docs + 1) * 8), at_tok = in.add(n * 4);
+    TRY(ensure(c->d_rp_in, in.total + 16));
+    uint64_t* d_off = carved<uint64_t>(c->d_rp_in, at_off);
+    uint32_t* d_tok = carved<uint32_t>(c->d_rp_in, at_tok);
+    HIPCHK(hipStreamWaitEvent(c->stream, c->rp_done, 0));  // (d_rp_in may still be read by a call on another stream)
+    HIPCHK(hipMemcpyAsync(d_off, tok_off, (n_docs + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    if (n) HIPCHK(hipMemcpyAsync(d_tok, tokens, n * 4, hipMemcpyHostToDevice, c->stream));
+    return drained(c, [&] {
+        return rp_to_host(c, c->stream, d_tok, n, d_off, n_docs, sizes, n_sizes, RpOuts{n_ngrams_out, n_distinct_out, n_dup_out, n_dup_covered_out, top_count_out}, lo, hi);
+    });
+}
+
+// tk_encode_batch (tk_encode_batch_checked with disallowed ids), then the statistics of the ids it has just produced: the ids never come
+// back; tok_off does, and sizes the long class's table.
+extern "C" int tk_encode_batch_repetition(tk_core* c, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, int use_special, const uint32_t* allowed_ids,
+                                          uint64_t n_allowed, const uint32_t* disallowed_ids, uint64_t n_disallowed, const uint32_t* sizes, uint64_t n_sizes,
+                                          uint64_t* n_ngrams_out, uint64_t* n_distinct_out, uint64_t* n_dup_out, uint64_t* n_dup_covered_out, uint64_t* top_count_out,
+                                          uint64_t* tok_off_out, uint64_t* n_tokens_out, tk_special_hit* hit) {
+    std::vector<uint64_t> off;
+    return encode_batch_pass(
+        c, utf8, doc_off, n_docs, use_special, allowed_ids, n_allowed, disallowed_ids, n_disallowed, hit, true,
+        [&] { return rp_check_sizes(sizes, n_sizes); },  // (before the encode, not after it)
+        [&](uint64_t n) -> int {
+            off.resize(n_docs + 1);
+            HIPCHK(hipMemcpyAsync(off.data(), c->out_tok_off.p, (n_docs + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+            uint64_t lo, hi;
+            TRY(rp_long_range(off.data(), n_docs, &lo, &hi));
+            return rp_to_host(c, c->stream, c->out_tokens.as<uint32_t>(), n, c->out_tok_off.as<uint64_t>(), n_docs, sizes, n_sizes,
+                              RpOuts{n_ngrams_out, n_distinct_out, n_dup_out, n_dup_covered_out, top_count_out}, lo, hi);
+        },
+        [&](uint64_t n) {
+            if (tok_off_out) memcpy(tok_off_out, off.data(), (n_docs + 1) * 8);
+            if (n_tokens_out) *n_tokens_out = n;
+            return TK_OK;
+        });
+}
+
+// ------------------------------------------------------------------------------------------
 // Supervised samples (tk_samples.h): a packed batch of parts on the device -> one row per sample, ids, mask and labels as [R, W].
 // ------------------------------------------------------------------------------------------
 static_assert(TK_SMP_KEEP_TAIL == TK_SMPF_KEEP_TAIL && TK_SMP_LEFT == TK_SMPF_LEFT, "tk_smp_spec flags");
@@ -5817,6 +5970,8 @@ extern "C" uint64_t tk_stat(tk_core* c, const char* name) {
     if (k == "split_stitch_steps") return c->st_split[TK_SPLIT_ST_STITCH];    // ... steps of the stitch pass (one wavefront per document, in order)
     if (k == "split_spec_steps") return c->st_split[TK_SPLIT_ST_SPEC];        // ... steps of the speculative walks
     if (k == "fingerprint_tile") return TK_FP_TILE;  // token positions of a tile of the fingerprint pass (tk_fingerprint_rule.h)
+    if (k == "repeat_tile") return TK_RP_TILE;  // positions of a tile of the repetition pass's LDS class (tk_repeat_rule.h)
+    if (k == "repeat_lds_tokens") return TK_RP_LDS_TOKENS;  // the longest document that class counts in LDS
     if (k == "ngram_tile") return TK_NG_TILE;  // token positions of a tile of the n-gram passes (tk_ngram_rule.h)
     if (k == "select_tile") return TK_SEL_TILE;  // output positions of a tile of the selection's copy (tk_groups_rule.h)
     if (k == "jsonl_tile") return TK_JSONL_TILE;  // bytes of a tile of the JSON Lines passes (tk_jsonl_rule.h)
