@@ -559,7 +559,7 @@ int tk_encode_batch_overlap(tk_core* core, tk_ngram_set* set, const uint8_t* utf
  * grows on demand, 32 bytes per token it must cover: the positions from the first long document to the last for the entries that see
  * tok_off on the host (none when no document is long), all n_tokens for tk_repetition_device -- 2 GB for a batch of 63 M ids.  Calls that
  * share it are ordered on the device by an event, whatever their streams.
- * NOT built: a per-token mask; line- and paragraph-level repetition; n-grams of words; several GPUs; more than 8 sizes per call. */
+ * NOT built: a per-token mask; n-grams of words; several GPUs; more than 8 sizes per call. */
 /* Device pointers in (ids uint32, d_tok_off uint64[n_docs + 1], not checked), `sizes` a host array; the caller's device arrays out.
  * Stream and waiting as tk_fingerprint_device: everything is queued on `stream`, null being HIP's null stream, and the call returns
  * without waiting. */
@@ -574,6 +574,54 @@ int tk_encode_batch_repetition(tk_core* core, const uint8_t* utf8, const uint64_
                                const uint32_t* disallowed_ids, uint64_t n_disallowed, const uint32_t* sizes, uint64_t n_sizes, uint64_t* n_ngrams_out,
                                uint64_t* n_distinct_out, uint64_t* n_dup_out, uint64_t* n_dup_covered_out, uint64_t* top_count_out, uint64_t* tok_off_out,
                                uint64_t* n_tokens_out, tk_special_hit* hit);
+/* Line statistics: per document of packed TEXT -- (text, doc_off), what tk_jsonl_extract_device hands out and every encode entry takes --
+ * the duplicate lines and paragraphs inside it: the line-level half of the Gopher repetition rules (Rae et al. 2021, table A1; DataTrove's
+ * GopherRepetitionFilter), which C4 and CCNet use as a line filter too, with Gopher's bullet and ellipsis counts, which cost nothing once
+ * a line's start and length are known.  Replaces nothing in the reference: it is the host step of the reference's users,
+ * Counter(text.split("\n")) per document.  It runs before the encode, so the documents it drops need not be encoded; the keep mask made
+ * from it is what tk_select_docs_device takes.
+ * The rule.  Input: text uint8[N], doc_off uint64[n_docs + 1] ascending from 0 to N; seed.  Bytes are bytes: nothing is validated as
+ *  UTF-8, '\r' is a byte like any other, nothing is trimmed or case-folded.
+ *  Chars.  A char is a byte that is not 0b10xxxxxx.
+ *  Lines.  A line is a maximal run of bytes other than '\n' inside one document: re.split(rb"\n+", t.strip(b"\n")), none for a document
+ *   that is empty or all newlines.
+ *  Paragraphs.  A '\n' is paragraph content when it is neither the first nor the last byte of its document and neither byte beside it is
+ *   '\n'; every byte other than '\n' is content; a paragraph is a maximal run of content bytes: re.split(rb"\n{2,}", t.strip(b"\n")),
+ *   none for an empty document.  No line or paragraph crosses a document.
+ *  Keys and equality.  Two lines (two paragraphs) of one document are equal when their keys are equal.  A key is 64 bits: tk_fp_mix over
+ *   two polynomial hashes of the bytes modulo 2^61 - 1 -- h(s) = sum (s[i] + 1) B^(|s| - 1 - i), so h(ab) = h(a) B^|b| + h(b), under two
+ *   bases drawn from `seed` --, the byte length, the document's index and a salt that tells lines from paragraphs.  A hash DECIDES here,
+ *   unlike in tk_repetition: two different lines of a document are taken for equal with a probability of the order of 2^-64 per pair
+ *   plus len^2 / 2^122 (same length len; different lengths: 2^-64).  Lines of different documents are never compared.
+ *  Outputs, uint64[n_docs] each, any pointer may be null:
+ *   n_chars              the chars of the whole document, newlines included: Gopher's denominator;
+ *   n_lines              its lines;
+ *   n_dup_lines          n_lines minus the distinct lines: the occurrences after the first (DataTrove's find_duplicates);
+ *   dup_line_chars       the chars of all lines minus the chars of one line per distinct class;
+ *   n_paragraphs, n_dup_paragraphs, dup_paragraph_chars   likewise;
+ *   n_bullet_lines       the lines whose first bytes are '-', '*', U+2022 (E2 80 A2) or U+25CF (E2 97 8F);
+ *   n_ellipsis_lines     the lines whose last bytes are "..." or U+2026 (E2 80 A6); both raw, no whitespace skipped.
+ *  Every value is a function of (text, doc_off, seed) alone, never of the schedule: sums commute, and whichever member of a class claims
+ *  its slot, the class has one claim and its members the same chars.
+ *  Refused with TK_VALUE_ERROR before anything is written: a doc_off that does not ascend from 0 to N; N above 0xFFFF0000 (the JSON Lines
+ *  cap: positions are 32-bit in the kernels).
+ * A workgroup takes tk_stat("lines_tile") bytes, a lane tk_stat("lines_lane"), a wavefront tk_stat("lines_wave"); a line of any length
+ * costs a scan over the tiles it crosses, never a walk.  The core owns the scratch: 100 bytes per tile, 88 bytes per document and a table of
+ * 64-bit keys, the power of two >= 2 (lines + paragraphs), cleared per call.
+ * NOT built: normalised comparison (trimmed, case-folded, digits masked); "\r\n" as a line end; duplicates ACROSS documents or calls
+ * (CCNet's rule); a per-line mask or the removal of duplicate lines; word counts and the other Gopher quality rules; several GPUs;
+ * buffers above 0xFFFF0000 bytes. */
+/* Device pointers in (d_text uint8[n_bytes] at any alignment -- 16-byte aligned is the fast path --, d_doc_off uint64[n_docs + 1], checked
+ * on the device); the caller's device arrays out.  Everything is queued on `stream`, null being HIP's null stream, and the host waits
+ * ONCE on that stream, for the report words that say whether doc_off is well-formed and how many lines and paragraphs the table must
+ * hold; the count pass and the outputs are queued behind that and not waited for. */
+int tk_line_stats_device(tk_core* core, const void* d_text, uint64_t n_bytes, const void* d_doc_off, uint64_t n_docs, uint64_t seed, void* stream, uint64_t* d_n_chars,
+                         uint64_t* d_n_lines, uint64_t* d_n_dup_lines, uint64_t* d_dup_line_chars, uint64_t* d_n_paragraphs, uint64_t* d_n_dup_paragraphs,
+                         uint64_t* d_dup_paragraph_chars, uint64_t* d_n_bullet_lines, uint64_t* d_n_ellipsis_lines);
+/* The same from host arrays to the caller's host arrays (n_bytes is doc_off[n_docs]). */
+int tk_line_stats(tk_core* core, const uint8_t* text, const uint64_t* doc_off, uint64_t n_docs, uint64_t seed, uint64_t* n_chars_out, uint64_t* n_lines_out,
+                  uint64_t* n_dup_lines_out, uint64_t* dup_line_chars_out, uint64_t* n_paragraphs_out, uint64_t* n_dup_paragraphs_out, uint64_t* dup_paragraph_chars_out,
+                  uint64_t* n_bullet_lines_out, uint64_t* n_ellipsis_lines_out);
 /* Supervised samples: a packed batch whose documents are the PARTS of samples -- the messages of a conversation, a prompt and its answer --
  * -> one row per sample with the template's ids around every part, an attention mask and labels.  Replaces nothing in the reference: it is
  * the host loop of the reference's users, the fine-tuning script that calls encode_ordinary once per message, adds header and footer ids and
@@ -1030,7 +1078,8 @@ void tk_last_stats(tk_core* core, uint64_t* n_bytes, uint64_t* n_pieces, uint64_
  * (steps of the stitch pass) and "split_spec_steps" (steps of the speculative walks); "jsonl_tile": the bytes of a tile of the JSON Lines
  * passes (a constant of the build); "fingerprint_tile": the token positions of a tile of the fingerprint pass, "ngram_tile": of the
  * n-gram passes (likewise); "repeat_tile" and "repeat_lds_tokens": of the repetition pass, the positions of a tile of its LDS class and
- * the longest document that class takes (likewise). */
+ * the longest document that class takes (likewise); "lines_tile", "lines_lane", "lines_wave" and "lines_docs": of the line statistics
+ * pass, the bytes of a tile, of a lane and of a wavefront, and the documents of a tile whose sums are gathered in LDS (likewise). */
 uint64_t tk_stat(tk_core* core, const char* name);
 
 #ifdef __cplusplus

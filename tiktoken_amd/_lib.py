@@ -211,6 +211,11 @@ def lib() -> ctypes.CDLL:
             L.tk_repetition.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp, vp, vp, vp]
             L.tk_encode_batch_repetition.restype = i32
             L.tk_encode_batch_repetition.argtypes = [vp, vp, vp, u64, i32, vp, u64, vp, u64, vp, u64, vp, vp, vp, vp, vp, vp, P(u64), P(SpecialHit)]
+        if hasattr(L, "tk_line_stats_device"):  # (absent from older builds selected through $TIKTOKEN_AMD_LIB)
+            L.tk_line_stats_device.restype = i32
+            L.tk_line_stats_device.argtypes = [vp, vp, u64, vp, u64, u64, vp, *[vp] * 9]
+            L.tk_line_stats.restype = i32
+            L.tk_line_stats.argtypes = [vp, vp, vp, u64, u64, *[vp] * 9]
         if hasattr(L, "tk_jsonl_extract_device"):  # (absent from older builds selected through $TIKTOKEN_AMD_LIB)
             L.tk_jsonl_extract_device.restype = i32
             L.tk_jsonl_extract_device.argtypes = [vp, vp, u64, vp, u64, u32, vp, *[P(vp)] * 5, *[P(u64)] * 3, P(JsonlBad)]

@@ -789,6 +789,65 @@ class RepetitionStats(NamedTuple):
         return keep.astype(np.uint8)
 
 
+class LineStats(NamedTuple):
+    """Line statistics of a batch of texts (tk_line_stats; the rule: include/tiktoken_amd.h), uint64[n] each: `length` the documents'
+    bytes, `n_chars` their chars (bytes that are not 0b10xxxxxx), `n_lines` and `n_paragraphs`, `n_dup_lines` and `n_dup_paragraphs` the
+    occurrences after the first of equal ones within the document, `dup_line_chars` and `dup_paragraph_chars` the chars in those, and
+    `n_bullet_lines` / `n_ellipsis_lines` the lines that start with - * U+2022 U+25CF / end with ... or U+2026.  Equal lines are equal
+    64-bit keys of two hashes modulo 2^61 - 1 and the length."""
+    length: np.ndarray
+    n_chars: np.ndarray
+    n_lines: np.ndarray
+    n_dup_lines: np.ndarray
+    dup_line_chars: np.ndarray
+    n_paragraphs: np.ndarray
+    n_dup_paragraphs: np.ndarray
+    dup_paragraph_chars: np.ndarray
+    n_bullet_lines: np.ndarray
+    n_ellipsis_lines: np.ndarray
+
+    @staticmethod
+    def _ratio(a: np.ndarray, b: np.ndarray) -> np.ndarray:
+        b = b.astype(np.float64)
+        return np.divide(a.astype(np.float64), b, out=np.zeros_like(b), where=b > 0)
+
+    def dup_line_fraction(self) -> np.ndarray:
+        """float64[n]: n_dup_lines / n_lines (0 where there is no line)"""
+        return self._ratio(self.n_dup_lines, self.n_lines)
+
+    def dup_paragraph_fraction(self) -> np.ndarray:
+        """float64[n]: n_dup_paragraphs / n_paragraphs (0 where there is no paragraph)"""
+        return self._ratio(self.n_dup_paragraphs, self.n_paragraphs)
+
+    def dup_line_char_fraction(self) -> np.ndarray:
+        """float64[n]: dup_line_chars / n_chars (0 for an empty document)"""
+        return self._ratio(self.dup_line_chars, self.n_chars)
+
+    def dup_paragraph_char_fraction(self) -> np.ndarray:
+        """float64[n]: dup_paragraph_chars / n_chars (0 for an empty document)"""
+        return self._ratio(self.dup_paragraph_chars, self.n_chars)
+
+    def bullet_fraction(self) -> np.ndarray:
+        """float64[n]: n_bullet_lines / n_lines (0 where there is no line)"""
+        return self._ratio(self.n_bullet_lines, self.n_lines)
+
+    def ellipsis_fraction(self) -> np.ndarray:
+        """float64[n]: n_ellipsis_lines / n_lines (0 where there is no line)"""
+        return self._ratio(self.n_ellipsis_lines, self.n_lines)
+
+    def keep_mask(self, max_dup_line_fraction=0.30, max_dup_paragraph_fraction=0.30, max_dup_line_char_fraction=0.20, max_dup_paragraph_char_fraction=0.20,
+                  max_bullet_fraction=0.90, max_ellipsis_fraction=0.30) -> np.ndarray:
+        """uint8[n], what `select_docs_device` takes: 1 for the documents of which every fraction is at most its limit -- by default the
+        thresholds of the Gopher rules.  None switches a rule off."""
+        keep = np.ones(len(self.length), dtype=bool)
+        for limit, fraction in ((max_dup_line_fraction, self.dup_line_fraction), (max_dup_paragraph_fraction, self.dup_paragraph_fraction),
+                                (max_dup_line_char_fraction, self.dup_line_char_fraction), (max_dup_paragraph_char_fraction, self.dup_paragraph_char_fraction),
+                                (max_bullet_fraction, self.bullet_fraction), (max_ellipsis_fraction, self.ellipsis_fraction)):
+            if limit is not None:
+                keep &= fraction() <= float(limit)
+        return keep.astype(np.uint8)
+
+
 class NativeNgramSet:
     """A tk_ngram_set; made by `CoreBPE.ngram_set_create`.  Keeps its core alive: the set must go first."""
 
@@ -2060,6 +2119,37 @@ class CoreBPE:
                                                 ctypes.byref(hit))
         self._raise_for(rc, hit)
         return RepetitionStats(tuple(int(k) for k in ks), np.diff(tok_off), *out)
+
+    # ------------------------------------------------------------------ line statistics (no reference counterpart: a Counter of lines per document on the host)
+    LINE_OUTS = ("n_chars", "n_lines", "n_dup_lines", "dup_line_chars", "n_paragraphs", "n_dup_paragraphs", "dup_paragraph_chars", "n_bullet_lines", "n_ellipsis_lines")
+
+    def line_stats_device(self, text, doc_off, *, seed: int = 0, n_chars=None, n_lines=None, n_dup_lines=None, dup_line_chars=None, n_paragraphs=None,
+                          n_dup_paragraphs=None, dup_paragraph_chars=None, n_bullet_lines=None, n_ellipsis_lines=None, stream: int | None = None) -> None:
+        """Line statistics of packed text that is on the device (tk_line_stats_device): torch tensors on this core's GPU, taken by pointer
+        -- `text` (8-bit, N) and `doc_off` (64-bit, n + 1, ascending from 0 to N; checked on the device) in; the caller's tensors out,
+        64-bit, n each, any of which may be None.  Queued on `stream` as in `fingerprint_device`; the host waits once on that stream, for
+        the number of lines and paragraphs, and not for the results."""
+        self._one_device("line_stats_device")
+        n, N = doc_off.numel() - 1, text.numel()
+        if n < 0:
+            raise ValueError("doc_off must hold n_docs + 1 entries")
+        outs = (n_chars, n_lines, n_dup_lines, dup_line_chars, n_paragraphs, n_dup_paragraphs, dup_paragraph_chars, n_bullet_lines, n_ellipsis_lines)
+        stream = self._on_gpu((("text", text, 1, N), ("doc_off", doc_off, 8, n + 1), *[(m, o, 8, n) for m, o in zip(self.LINE_OUTS, outs)]), stream)
+        ptr = [t.data_ptr() if t is not None and t.numel() else None for t in outs]
+        _lib.raise_for(self._L.tk_line_stats_device(self._h, text.data_ptr() if N else None, N, doc_off.data_ptr(), n, int(seed), stream or None, *ptr))
+
+    def line_stats_packed(self, text, doc_off: np.ndarray, seed: int = 0) -> LineStats:
+        """Line statistics of packed text (tk_line_stats): host arrays in -- `text` bytes or uint8[N] (no copy), `doc_off` uint64[n + 1] --,
+        a `LineStats` out."""
+        self._one_device("line_stats_packed")
+        text = self._jsonl_bytes(text)
+        doc_off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+        if doc_off.ndim != 1 or len(doc_off) < 1 or int(doc_off[-1]) != len(text):
+            raise ValueError("doc_off must hold n + 1 offsets that end at len(text)")
+        n = len(doc_off) - 1
+        out = tuple(np.zeros(n + 1, dtype=np.uint64)[:n] for _ in self.LINE_OUTS)  # (one spare element each: no empty array's pointer)
+        _lib.raise_for(self._L.tk_line_stats(self._h, text.ctypes.data if len(text) else None, doc_off.ctypes.data, n, int(seed), *[a.ctypes.data for a in out]))
+        return LineStats(np.diff(doc_off), *out)
 
     # ------------------------------------------------------------------ supervised samples (no reference counterpart: the host loop of its users)
     @staticmethod

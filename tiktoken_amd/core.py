@@ -444,6 +444,37 @@ class Encoding:
         """The repetition statistics of tokens that are packed already (`tokens` uint32[T], `tok_off` uint64[n + 1])."""
         return self._repetition(sizes, lambda ks: self._core_bpe.repetition_packed(tokens, tok_off, ks))
 
+    # ------------------------------------------------------------------ line statistics
+    def line_stats_batch(self, texts: "Sequence[str] | Sequence[bytes]", seed: int = 0) -> "_tiktoken.LineStats":
+        """Duplicate lines and paragraphs of every text of a batch, counted on the GPU from the text itself -- before any encode: per
+        document its chars, lines and paragraphs, how many of each repeat an earlier one of the same document and the chars in those, and
+        the lines that start with a bullet or end with an ellipsis: the line-level half of the Gopher repetition rules.  `texts`: str,
+        packed as `encode_ordinary_batch_packed` packs them, or bytes.  Returns a `LineStats`, whose `keep_mask` says which documents
+        pass.  The rule is stated in include/tiktoken_amd.h."""
+        if len(texts) and isinstance(texts[0], (bytes, bytearray, memoryview)):
+            off = np.zeros(len(texts) + 1, dtype=np.uint64)
+            np.cumsum([len(t) for t in texts], out=off[1:])
+            return self._core_bpe.line_stats_packed(b"".join(texts), off, seed)
+        blob, off = self._pack(texts)
+        return self._core_bpe.line_stats_packed(blob, off, seed)
+
+    def line_stats_packed(self, text, doc_off=None, seed: int = 0) -> "_tiktoken.LineStats":
+        """The line statistics of text that is packed already: `text` bytes, bytearray, memoryview or a uint8 numpy array (no copy) with
+        `doc_off` uint64[n + 1], a `JsonlText` (then `doc_off` is its own), or a uint8 torch tensor on the encoding's GPU with `doc_off` a
+        64-bit tensor there (by pointer; the results come back to the host)."""
+        if isinstance(text, _tiktoken.JsonlText):
+            text, doc_off = text.text, text.doc_off
+        if not hasattr(text, "data_ptr"):
+            return self._core_bpe.line_stats_packed(text, doc_off, seed)
+        import torch
+
+        if not hasattr(doc_off, "data_ptr"):
+            doc_off = torch.from_numpy(np.ascontiguousarray(doc_off, dtype=np.uint64).view(np.int64)).to(text.device)
+        n = doc_off.numel() - 1
+        outs = {m: torch.zeros(max(n, 0), dtype=torch.int64, device=text.device) for m in _tiktoken.CoreBPE.LINE_OUTS}
+        self._core_bpe.line_stats_device(text, doc_off, seed=seed, **outs)
+        return _tiktoken.LineStats(np.diff(doc_off.cpu().numpy().view(np.uint64)), *[outs[m].cpu().numpy().view(np.uint64) for m in _tiktoken.CoreBPE.LINE_OUTS])
+
     # ------------------------------------------------------------------ token n-gram sets
     def ngram_set(self, ngram: int = 13, *, capacity: int, seed: int = 0) -> "NgramSet":
         """An empty set of token n-grams that lives on the GPU across calls (tk_ngram_set_create): the n-grams of evaluation benchmarks,

@@ -34,6 +34,7 @@
 #include "tk_groups.h"
 #include "tk_ngram.h"
 #include "tk_repeat.h"
+#include "tk_lines.h"
 #include "tk_jsonl.h"
 #include "tk_sample_rows.h"
 #include "tk_samples.h"
@@ -313,6 +314,11 @@ struct tk_core {
     Buf d_rp, d_rp_flag, d_rp_in, d_rp_out;
     Event rp_done;
     uint64_t rp_serial = 0;
+    // Line statistics (tk_lines.h), apart from everything above: d_ln_work: the report words and the tiles' summaries; d_ln_tab: the
+    // documents' sums and the table of keys, cleared per call; d_ln_in, d_ln_out: text and doc_off, and the nine result arrays, of the
+    // host entry.  ln_done: as fp_done, for all four.
+    Buf d_ln_work, d_ln_tab, d_ln_in, d_ln_out;
+    Event ln_done;
     uint64_t st_split[TK_SPLIT_STATS] = {0, 0, 0, 0};
     // Supervised samples (tk_samples.h), apart from everything above: d_smp: ids, labels and mask of every position; d_smp_row: full_len, len,
     // n_trained of every sample; d_smp_cnt: the TK_SMP_WORDS report words, the role table, pstart and the per-sample figures a call counts in
@@ -4103,6 +4109,95 @@ extern "C" int tk_encode_batch_repetition(tk_core* c, const uint8_t* utf8, const
 }
 
 // ------------------------------------------------------------------------------------------
+// Line statistics (tk_lines.h): packed text on the device -> per document its chars, lines and paragraphs, the duplicates among them.
+// ------------------------------------------------------------------------------------------
+struct LnOuts {  // the caller's arrays, uint64[n_docs] (device memory for ln_run, host memory for tk_line_stats); any may be null
+    uint64_t* a[9];
+};
+// ln_run: the caller holds c->mu.  Launches on s; the host waits once, for the report words: whether doc_off ascends from 0 to N (it is
+// refused before anything of the caller's is written) and the lines and paragraphs of the batch, which size the table.
+static int ln_run(tk_core* c, hipStream_t s, const uint8_t* d_text, uint64_t n, const uint64_t* d_doc_off, uint64_t n_docs, uint64_t seed, LnOuts o) {
+    TkLn p;
+    if (tk_ln_shape(n, n_docs, seed, &p)) return fail(TK_VALUE_ERROR, "n_bytes: the text of a line statistics call is at most 0xFFFF0000 bytes (positions are 32-bit)");
+    if (n_docs > 0xFFFFFFFEull) return fail(TK_VALUE_ERROR, "n_docs: at most 2^32 - 2 documents");
+    if (!c->ln_done.e) HIPCHK(c->ln_done.create());
+    HIPCHK(hipStreamWaitEvent(s, c->ln_done, 0));  // (the scratch and the host entry's buffers are the core's)
+    const uint64_t nt = p.n_tiles;
+    Carve work;
+    const uint64_t at_words = work.add(TK_LN_WORDS * 8), at_seg = work.add(2 * nt * sizeof(TkLnSeg)), at_nseg = work.add(2 * nt * 4);
+    TRY(ensure(c->d_ln_work, work.total));
+    unsigned long long* words = carved<unsigned long long>(c->d_ln_work, at_words);
+    const TkLnTiles T{carved<TkLnSeg>(c->d_ln_work, at_seg), carved<uint32_t>(c->d_ln_work, at_nseg)};
+    const bool aligned = ((uintptr_t)d_text & 15u) == 0;
+    const dim3 tiles((uint32_t)nt), block(TK_LN_THREADS);
+    TRY(timed(c, s, "tk_k_ln_clear", [&] { hipLaunchKernelGGL(tk_k_ln_clear, dim3(1), dim3(256), 0, s, words, (uint64_t)TK_LN_WORDS); }));
+    TRY(timed(c, s, "tk_k_ln_sum", [&] { hipLaunchKernelGGL(tk_k_ln_sum, tiles, block, 0, s, p, d_text, d_doc_off, aligned, T, words); }));
+    TRY(timed(c, s, "tk_k_ln_carry", [&] { hipLaunchKernelGGL(tk_k_ln_carry, dim3(1), dim3(1024), 0, s, p, T, words); }));
+    unsigned long long got[TK_LN_WORDS];
+    HIPCHK(hipMemcpyAsync(got, words, sizeof got, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));  // the one wait
+    HIPCHK(hipGetLastError());
+    if (got[TK_LN_W_BAD]) return fail(TK_VALUE_ERROR, "doc_off must ascend from 0 to n_bytes");
+    const uint64_t S = tk_ln_slots(got[TK_LN_W_SEGS]), n_sums = (uint64_t)TK_LN_SUMS * n_docs;
+    TRY(ensure(c->d_ln_tab, (n_sums + S) * 8));
+    unsigned long long* sums = c->d_ln_tab.as<unsigned long long>();
+    TRY(timed(c, s, "tk_k_ln_clear", [&] { hipLaunchKernelGGL(tk_k_ln_clear, dim3(grid_for(n_sums + S, 256, 65536)), dim3(256), 0, s, sums, n_sums + S); }));
+    TRY(timed(c, s, "tk_k_ln_count", [&] { hipLaunchKernelGGL(tk_k_ln_count, tiles, block, 0, s, p, d_text, d_doc_off, aligned, T, sums + n_sums, S, sums); }));
+    const TkLnOut out{(unsigned long long*)o.a[0], (unsigned long long*)o.a[1], (unsigned long long*)o.a[2], (unsigned long long*)o.a[3], (unsigned long long*)o.a[4],
+                      (unsigned long long*)o.a[5], (unsigned long long*)o.a[6], (unsigned long long*)o.a[7], (unsigned long long*)o.a[8]};
+    if (n_docs) TRY(timed(c, s, "tk_k_ln_final", [&] { hipLaunchKernelGGL(tk_k_ln_final, dim3(grid_for(n_docs, 256, 65536)), dim3(256), 0, s, n_docs, sums, out); }));
+    HIPCHK(hipEventRecord(c->ln_done, s));
+    return TK_OK;
+}
+
+extern "C" int tk_line_stats_device(tk_core* c, const void* d_text, uint64_t n_bytes, const void* d_doc_off, uint64_t n_docs, uint64_t seed, void* stream, uint64_t* d_n_chars,
+                                    uint64_t* d_n_lines, uint64_t* d_n_dup_lines, uint64_t* d_dup_line_chars, uint64_t* d_n_paragraphs, uint64_t* d_n_dup_paragraphs,
+                                    uint64_t* d_dup_paragraph_chars, uint64_t* d_n_bullet_lines, uint64_t* d_n_ellipsis_lines) {
+    // (the stream as given, null being HIP's null stream: tk_fingerprint_device's convention)
+    return device_pass(c, d_doc_off && (d_text || !n_bytes), stream, [&](hipStream_t) {
+        return ln_run(c, (hipStream_t)stream, (const uint8_t*)d_text, n_bytes, (const uint64_t*)d_doc_off, n_docs, seed,
+                      LnOuts{{d_n_chars, d_n_lines, d_n_dup_lines, d_dup_line_chars, d_n_paragraphs, d_n_dup_paragraphs, d_dup_paragraph_chars, d_n_bullet_lines, d_n_ellipsis_lines}});
+    });
+}
+
+extern "C" int tk_line_stats(tk_core* c, const uint8_t* text, const uint64_t* doc_off, uint64_t n_docs, uint64_t seed, uint64_t* n_chars_out, uint64_t* n_lines_out,
+                             uint64_t* n_dup_lines_out, uint64_t* dup_line_chars_out, uint64_t* n_paragraphs_out, uint64_t* n_dup_paragraphs_out,
+                             uint64_t* dup_paragraph_chars_out, uint64_t* n_bullet_lines_out, uint64_t* n_ellipsis_lines_out) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if (!doc_off) return fail(TK_VALUE_ERROR, "null argument");
+    TRY(check_offsets(doc_off, n_docs, "doc_off"));
+    const uint64_t n = doc_off[n_docs];
+    if (n && !text) return fail(TK_VALUE_ERROR, "null argument");
+    if (n > TK_LN_MAX_BYTES) return fail(TK_VALUE_ERROR, "n_bytes: the text of a line statistics call is at most 0xFFFF0000 bytes (positions are 32-bit)");
+    uint64_t* const hp[9] = {n_chars_out, n_lines_out, n_dup_lines_out, dup_line_chars_out, n_paragraphs_out, n_dup_paragraphs_out, dup_paragraph_chars_out, n_bullet_lines_out,
+                             n_ellipsis_lines_out};
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->ln_done.e) HIPCHK(c->ln_done.create());
+    Carve in, res;
+    const uint64_t at_off = in.add((n_docs + 1) * 8), at_text = in.add(n + 16);
+    uint64_t at[9];
+    for (uint64_t& a : at) a = res.add(n_docs * 8);
+    TRY(ensure(c->d_ln_in, in.total + 16));
+    TRY(ensure(c->d_ln_out, res.total + 16));
+    uint64_t* d_off = carved<uint64_t>(c->d_ln_in, at_off);
+    uint8_t* d_text = carved<uint8_t>(c->d_ln_in, at_text);
+    LnOuts d;
+    for (int i = 0; i < 9; ++i) d.a[i] = hp[i] ? carved<uint64_t>(c->d_ln_out, at[i]) : nullptr;
+    HIPCHK(hipStreamWaitEvent(c->stream, c->ln_done, 0));  // (d_ln_in may still be read by a call on another stream)
+    HIPCHK(hipMemcpyAsync(d_off, doc_off, (n_docs + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    if (n) HIPCHK(hipMemcpyAsync(d_text, text, n, hipMemcpyHostToDevice, c->stream));
+    return drained(c, [&]() -> int {
+        TRY(ln_run(c, c->stream, d_text, n, d_off, n_docs, seed, d));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipGetLastError());
+        for (int i = 0; i < 9; ++i)
+            if (hp[i] && n_docs) HIPCHK(hipMemcpy(hp[i], d.a[i], n_docs * 8, hipMemcpyDeviceToHost));
+        return TK_OK;
+    });
+}
+
+// ------------------------------------------------------------------------------------------
 // Supervised samples (tk_samples.h): a packed batch of parts on the device -> one row per sample, ids, mask and labels as [R, W].
 // ------------------------------------------------------------------------------------------
 static_assert(TK_SMP_KEEP_TAIL == TK_SMPF_KEEP_TAIL && TK_SMP_LEFT == TK_SMPF_LEFT, "tk_smp_spec flags");
@@ -5972,6 +6067,10 @@ extern "C" uint64_t tk_stat(tk_core* c, const char* name) {
     if (k == "fingerprint_tile") return TK_FP_TILE;  // token positions of a tile of the fingerprint pass (tk_fingerprint_rule.h)
     if (k == "repeat_tile") return TK_RP_TILE;  // positions of a tile of the repetition pass's LDS class (tk_repeat_rule.h)
     if (k == "repeat_lds_tokens") return TK_RP_LDS_TOKENS;  // the longest document that class counts in LDS
+    if (k == "lines_tile") return TK_LN_TILE;  // bytes of a tile of the line statistics pass (tk_lines_rule.h)
+    if (k == "lines_lane") return TK_LN_LANE;  // ... of a lane
+    if (k == "lines_wave") return TK_LN_WAVE;  // ... of a wavefront
+    if (k == "lines_docs") return TK_LN_DOCS;  // documents of a tile whose sums are gathered in LDS
     if (k == "ngram_tile") return TK_NG_TILE;  // token positions of a tile of the n-gram passes (tk_ngram_rule.h)
     if (k == "select_tile") return TK_SEL_TILE;  // output positions of a tile of the selection's copy (tk_groups_rule.h)
     if (k == "jsonl_tile") return TK_JSONL_TILE;  // bytes of a tile of the JSON Lines passes (tk_jsonl_rule.h)
