@@ -608,9 +608,9 @@ int tk_encode_batch_repetition(tk_core* core, const uint8_t* utf8, const uint64_
  * A workgroup takes tk_stat("lines_tile") bytes, a lane tk_stat("lines_lane"), a wavefront tk_stat("lines_wave"); a line of any length
  * costs a scan over the tiles it crosses, never a walk.  The core owns the scratch: 100 bytes per tile, 88 bytes per document and a table of
  * 64-bit keys, the power of two >= 2 (lines + paragraphs), cleared per call.
- * NOT built: normalised comparison (trimmed, case-folded, digits masked); "\r\n" as a line end; duplicates ACROSS documents or calls
- * (CCNet's rule); a per-line mask or the removal of duplicate lines; word counts and the other Gopher quality rules; several GPUs;
- * buffers above 0xFFFF0000 bytes. */
+ * NOT built: normalised comparison (trimmed, case-folded, digits masked); "\r\n" as a line end; word counts and the other Gopher
+ * quality rules; several GPUs; buffers above 0xFFFF0000 bytes.  (Duplicates across documents and calls, the decision per line and the
+ * removal of duplicate lines are the line sets' below.) */
 /* Device pointers in (d_text uint8[n_bytes] at any alignment -- 16-byte aligned is the fast path --, d_doc_off uint64[n_docs + 1], checked
  * on the device); the caller's device arrays out.  Everything is queued on `stream`, null being HIP's null stream, and the host waits
  * ONCE on that stream, for the report words that say whether doc_off is well-formed and how many lines and paragraphs the table must
@@ -622,6 +622,63 @@ int tk_line_stats_device(tk_core* core, const void* d_text, uint64_t n_bytes, co
 int tk_line_stats(tk_core* core, const uint8_t* text, const uint64_t* doc_off, uint64_t n_docs, uint64_t seed, uint64_t* n_chars_out, uint64_t* n_lines_out,
                   uint64_t* n_dup_lines_out, uint64_t* dup_line_chars_out, uint64_t* n_paragraphs_out, uint64_t* n_dup_paragraphs_out, uint64_t* dup_paragraph_chars_out,
                   uint64_t* n_bullet_lines_out, uint64_t* n_ellipsis_lines_out);
+/* Line sets: a set of line keys that lives on the device across calls, and packed TEXT rewritten without the lines the set has seen
+ * -- navigation bars, cookie banners, licence footers: the line filter of CCNet, C4 and RefinedWeb-style builds, which drops every line
+ * that occurred anywhere earlier in the corpus.  Replaces nothing in the reference: it is the host step of the reference's users, a loop
+ * over text.split("\n") against a Python set.  The output is packed text again, what every encode entry takes.
+ * The rule.  A set has a seed (uint64), a capacity in lines, 1 .. 2^30, and min_bytes >= 1.
+ *  Input: text uint8[N], doc_off uint64[n_docs + 1] ascending from 0 to N, N <= 0xFFFF0000.  Bytes are bytes, as in tk_line_stats.
+ *  Pieces.  Inside a document the bytes split into the pieces of re.finditer(rb"[^\n]+\n?|\n", doc): a line -- what tk_line_stats calls
+ *   a line -- together with the one '\n' that directly follows it in the same document, if there is one; or a bare '\n'.  No piece
+ *   crosses a document.
+ *  Eligibility.  A line shorter than min_bytes is never dropped and never added.
+ *  Key.  64 bits: tk_fp_mix over the two polynomial hashes modulo 2^61 - 1 of tk_line_stats, under two bases drawn from the set's seed,
+ *   the byte length and a salt of the line sets.  The document's index is NOT in the key.  A hash DECIDES: two different lines are taken
+ *   for equal with a probability of the order of 2^-64 per pair plus len^2 / 2^122 (same length len; different lengths: 2^-64).
+ *  add = 1 (CCNet's rule).  An eligible line is dropped when its key was in the set before the call, or when an eligible line with the
+ *   same key starts at a lower byte position of this batch.  Otherwise it is kept and its key is in the set afterwards.  So the kept
+ *   occurrence is the one with the lowest start, and the result is a function of (the set's keys, text, doc_off, min_bytes) alone, never
+ *   of the schedule: beside every key the table keeps (call number, lowest start) under an atomic minimum.
+ *  add = 0 (a filter against a block list or an earlier shard).  An eligible line is dropped when its key is in the set.  The set does
+ *   not change; duplicates within the batch stay.
+ *  Output.  text_out: the pieces whose line is kept, and the bare '\n' pieces, in order -- dropping whole pieces keeps well-formed UTF-8
+ *   well-formed; doc_off_out uint64[n_docs + 1]: every input document keeps its index and may become empty; per document n_lines (all its
+ *   lines, as tk_line_stats counts them) and n_dropped; counts uint64[2] = (bytes kept, lines dropped).
+ *  Capacity.  An add is refused, before anything is written, when bound + the lines of the batch > capacity: the bound is kept on the
+ *   host, the sum of the lines of the adds so far; tk_line_set_count waits, reads the exact number of distinct keys and lowers the bound.
+ *  Refused with TK_VALUE_ERROR, nothing written and the set unchanged: a doc_off that does not ascend from 0 to N (seen on the device);
+ *   N above 0xFFFF0000; min_bytes 0; capacity 0 or above 2^30; a set of another core; d_text_out == d_text; an add past the capacity.
+ * A tk_line_set belongs to the core it was made on and must be destroyed before it.  It owns its device memory: a table of 16 S bytes,
+ * S the power of two >= 2 * capacity (a key and the first-occurrence word per slot); a bitmap of N / 8 bytes, one bit per position, for
+ * the drop flags, which a line's closing lane sets at the line's START and every byte of the line finds by one read; 56 bytes per tile
+ * of tk_stat("lines_tile") bytes (the line statistics' 52 for one kind, and 4); the buffers of its host entries.  The library orders
+ * the calls on one set among themselves on the device (an event), whatever their streams and entries.
+ * NOT built: normalised comparison (trimmed, case-folded, digits masked); "\r\n" as a line end; sets of paragraphs; saving a set to a
+ * file; removal of single keys; several GPUs; a fast path that hands back its input when nothing is dropped; buffers above 0xFFFF0000
+ * bytes. */
+typedef struct tk_line_set tk_line_set;
+int tk_line_set_create(tk_core* core, uint64_t seed, uint64_t capacity, uint64_t min_bytes, tk_line_set** set_out);
+void tk_line_set_destroy(tk_line_set* set);
+/* The exact number of distinct keys; waits for every call queued on the set. */
+int tk_line_set_count(tk_line_set* set, uint64_t* count_out);
+/* Empties the set (queued on the core's stream; no wait). */
+int tk_line_set_clear(tk_line_set* set);
+/* Packed text without the lines the set has seen.  Device pointers in (d_text uint8[n_bytes] at any alignment -- 16-byte aligned is the
+ * fast path --, d_doc_off uint64[n_docs + 1], checked on the device); the caller's device arrays out: d_text_out uint8[n_bytes] (at any
+ * alignment; only the first counts[0] bytes are written), d_doc_off_out uint64[n_docs + 1], and d_n_lines, d_n_dropped uint64[n_docs],
+ * d_counts_out uint64[2], which may be null.  Everything is queued on `stream`, null being HIP's null stream, and the host waits ONCE
+ * on that stream, for the report words that say whether doc_off is well-formed and how many lines the batch has; the other passes are
+ * queued behind that and not waited for. */
+int tk_line_dedup_device(tk_core* core, tk_line_set* set, const void* d_text, uint64_t n_bytes, const void* d_doc_off, uint64_t n_docs, int add, void* stream,
+                         void* d_text_out, uint64_t* d_doc_off_out, uint64_t* d_n_lines, uint64_t* d_n_dropped, uint64_t* d_counts_out);
+/* The same from host arrays (n_bytes is doc_off[n_docs]): *text_out is library-owned (tk_free), *n_bytes_out bytes; doc_off_out
+ * (n_docs + 1) and n_lines_out, n_dropped_out (n_docs; may be null) are the caller's. */
+int tk_line_dedup(tk_core* core, tk_line_set* set, const uint8_t* text, const uint64_t* doc_off, uint64_t n_docs, int add, uint8_t** text_out, uint64_t* n_bytes_out,
+                  uint64_t* doc_off_out, uint64_t* n_lines_out, uint64_t* n_dropped_out);
+/* The eligible lines of packed text into the set and nothing else -- filling a block list: the passes of an add = 1 call up to the
+ * table, no text out.  Stream and waiting as tk_line_dedup_device; tk_line_add waits for the whole call. */
+int tk_line_add_device(tk_core* core, tk_line_set* set, const void* d_text, uint64_t n_bytes, const void* d_doc_off, uint64_t n_docs, void* stream);
+int tk_line_add(tk_core* core, tk_line_set* set, const uint8_t* text, const uint64_t* doc_off, uint64_t n_docs);
 /* Supervised samples: a packed batch whose documents are the PARTS of samples -- the messages of a conversation, a prompt and its answer --
  * -> one row per sample with the template's ids around every part, an attention mask and labels.  Replaces nothing in the reference: it is
  * the host loop of the reference's users, the fine-tuning script that calls encode_ordinary once per message, adds header and footer ids and

@@ -7,9 +7,10 @@ methods handing whole batches to the GPU; `get_encoding` / `list_encoding_names`
 """
 __version__ = "0.1.0"
 
-from ._tiktoken import CoreBPE, DedupedBatch, DisallowedSpecialError, Fingerprints, JsonlError, JsonlText, JsonlTokens, LineStats, NgramOverlap, RepetitionStats, Role, SampleBatch, SampleRows, SampleRowsDevice, StoppedRows, StreamPacked, StreamStep, TextChunks  # noqa: F401
+from ._tiktoken import CoreBPE, DedupedBatch, DisallowedSpecialError, Fingerprints, JsonlError, JsonlText, JsonlTokens, LineDedup, LineStats, NgramOverlap, RepetitionStats, Role, SampleBatch, SampleRows, SampleRowsDevice, StoppedRows, StreamPacked, StreamStep, TextChunks  # noqa: F401
 from .core import DecodeStream  # noqa: F401
 from .core import Encoding  # noqa: F401
+from .core import LineSet  # noqa: F401
 from .core import NgramSet  # noqa: F401
 from .train import bpe_train, merges_to_ranks, train_encoding  # noqa: F401
 from .plugins import encoding_for_model, encoding_name_for_model, get_encoding, list_encoding_names  # noqa: F401

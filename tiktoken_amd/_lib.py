@@ -216,6 +216,22 @@ def lib() -> ctypes.CDLL:
             L.tk_line_stats_device.argtypes = [vp, vp, u64, vp, u64, u64, vp, *[vp] * 9]
             L.tk_line_stats.restype = i32
             L.tk_line_stats.argtypes = [vp, vp, vp, u64, u64, *[vp] * 9]
+        if hasattr(L, "tk_line_set_create"):  # (absent from older builds selected through $TIKTOKEN_AMD_LIB)
+            L.tk_line_set_create.restype = i32
+            L.tk_line_set_create.argtypes = [vp, u64, u64, u64, P(vp)]
+            L.tk_line_set_destroy.argtypes = [vp]
+            L.tk_line_set_count.restype = i32
+            L.tk_line_set_count.argtypes = [vp, P(u64)]
+            L.tk_line_set_clear.restype = i32
+            L.tk_line_set_clear.argtypes = [vp]
+            L.tk_line_dedup_device.restype = i32
+            L.tk_line_dedup_device.argtypes = [vp, vp, vp, u64, vp, u64, i32, vp, *[vp] * 5]
+            L.tk_line_dedup.restype = i32
+            L.tk_line_dedup.argtypes = [vp, vp, vp, vp, u64, i32, P(vp), P(u64), vp, vp, vp]
+            L.tk_line_add_device.restype = i32
+            L.tk_line_add_device.argtypes = [vp, vp, vp, u64, vp, u64, vp]
+            L.tk_line_add.restype = i32
+            L.tk_line_add.argtypes = [vp, vp, vp, vp, u64]
         if hasattr(L, "tk_jsonl_extract_device"):  # (absent from older builds selected through $TIKTOKEN_AMD_LIB)
             L.tk_jsonl_extract_device.restype = i32
             L.tk_jsonl_extract_device.argtypes = [vp, vp, u64, vp, u64, u32, vp, *[P(vp)] * 5, *[P(u64)] * 3, P(JsonlBad)]

@@ -870,6 +870,39 @@ class NativeNgramSet:
         return self._h
 
 
+class LineDedup(NamedTuple):
+    """Packed text without the lines a line set has seen (tk_line_dedup; the rule: include/tiktoken_amd.h): `text` uint8[kept bytes]
+    and `doc_off` uint64[n + 1], what every packed encode entry takes -- every input document keeps its index and may be empty --,
+    `n_lines` and `n_dropped` uint64[n] per document, and `n_dropped_total`."""
+    text: np.ndarray
+    doc_off: np.ndarray
+    n_lines: np.ndarray
+    n_dropped: np.ndarray
+    n_dropped_total: int
+
+
+class NativeLineSet:
+    """A tk_line_set; made by `CoreBPE.line_set_create`.  Keeps its core alive: the set must go first."""
+
+    def __init__(self, core: "CoreBPE", handle, capacity: int, seed: int, min_bytes: int):
+        self._core, self._h, self.capacity, self.seed, self.min_bytes = core, handle, capacity, seed, min_bytes
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and getattr(self._core, "_h", None):  # (a core that is closed has taken its device's buffers along)
+            try:
+                self._core._L.tk_line_set_destroy(h)
+            except Exception:
+                pass
+
+    __del__ = close
+
+    def handle(self):
+        if not self._h:
+            raise ValueError("the line set is closed")
+        return self._h
+
+
 class DisallowedSpecialError(ValueError):
     """A batch holds a disallowed special token: the first occurrence -- document `doc`, byte offset `pos` inside it, the `token` (the
     longest disallowed one that matches there).  What the reference raises as a plain ValueError, with its message."""
@@ -2150,6 +2183,78 @@ class CoreBPE:
         out = tuple(np.zeros(n + 1, dtype=np.uint64)[:n] for _ in self.LINE_OUTS)  # (one spare element each: no empty array's pointer)
         _lib.raise_for(self._L.tk_line_stats(self._h, text.ctypes.data if len(text) else None, doc_off.ctypes.data, n, int(seed), *[a.ctypes.data for a in out]))
         return LineStats(np.diff(doc_off), *out)
+
+    # ------------------------------------------------------------------ line sets (no reference counterpart: a loop over lines against a set on the host)
+    def line_set_create(self, capacity: int, seed: int = 0, min_bytes: int = 1) -> NativeLineSet:
+        """An empty line set on this core's device (tk_line_set_create) for up to `capacity` distinct lines of at least `min_bytes` bytes."""
+        self._one_device("line_set_create")
+        if not all(0 <= int(v) <= 0xFFFFFFFFFFFFFFFF for v in (capacity, seed, min_bytes)):
+            raise ValueError("capacity, seed and min_bytes must fit 64 bits")
+        h = ctypes.c_void_p()
+        _lib.raise_for(self._L.tk_line_set_create(self._h, int(seed), int(capacity), int(min_bytes), ctypes.byref(h)))
+        return NativeLineSet(self, h, int(capacity), int(seed), int(min_bytes))
+
+    def line_set_count(self, ls: NativeLineSet) -> int:
+        """The distinct lines in the set (tk_line_set_count): waits for the calls queued on it."""
+        n = ctypes.c_uint64()
+        _lib.raise_for(self._L.tk_line_set_count(ls.handle(), ctypes.byref(n)))
+        return int(n.value)
+
+    def line_set_clear(self, ls: NativeLineSet) -> None:
+        _lib.raise_for(self._L.tk_line_set_clear(ls.handle()))
+
+    def line_dedup_device(self, ls: NativeLineSet, text, doc_off, add: bool = True, *, text_out, doc_off_out, n_lines=None, n_dropped=None, counts=None,
+                          stream: int | None = None) -> None:
+        """Packed text that is on the device without the lines the set has seen (tk_line_dedup_device): torch tensors on this core's
+        GPU, taken by pointer -- `text` (8-bit, N) and `doc_off` (64-bit, n + 1, ascending from 0 to N; checked on the device) in; the
+        caller's tensors out: `text_out` (8-bit, N: its first counts[0] bytes are written), `doc_off_out` (64-bit, n + 1), and `n_lines`,
+        `n_dropped` (64-bit, n), `counts` (64-bit, 2: bytes kept, lines dropped), which may be None.  (`text_out`, `doc_off_out`) is what
+        the device-resident encode entries take.  `add`: the kept lines go into the set (CCNet's rule); else the set only filters.  Queued
+        on `stream` as in `fingerprint_device`; the host waits once on that stream, for the number of lines, and not for the results."""
+        self._one_device("line_dedup_device")
+        n, N = doc_off.numel() - 1, text.numel()
+        if n < 0:
+            raise ValueError("doc_off must hold n_docs + 1 entries")
+        stream = self._on_gpu((("text", text, 1, N), ("doc_off", doc_off, 8, n + 1), ("text_out", text_out, 1, N), ("doc_off_out", doc_off_out, 8, n + 1),
+                               ("n_lines", n_lines, 8, n), ("n_dropped", n_dropped, 8, n), ("counts", counts, 8, 2)), stream)
+        ptr = [t.data_ptr() if t is not None and t.numel() else None for t in (text_out, doc_off_out, n_lines, n_dropped, counts)]
+        _lib.raise_for(self._L.tk_line_dedup_device(self._h, ls.handle(), text.data_ptr() if N else None, N, doc_off.data_ptr(), n, int(bool(add)), stream or None, *ptr))
+
+    def line_add_device(self, ls: NativeLineSet, text, doc_off, *, stream: int | None = None) -> None:
+        """The lines of packed text that is on the device into the set and nothing else (tk_line_add_device); tensors, stream and waiting
+        as in `line_dedup_device`."""
+        self._one_device("line_add_device")
+        n, N = doc_off.numel() - 1, text.numel()
+        if n < 0:
+            raise ValueError("doc_off must hold n_docs + 1 entries")
+        stream = self._on_gpu((("text", text, 1, N), ("doc_off", doc_off, 8, n + 1)), stream)
+        _lib.raise_for(self._L.tk_line_add_device(self._h, ls.handle(), text.data_ptr() if N else None, N, doc_off.data_ptr(), n, stream or None))
+
+    def _packed_text(self, text, doc_off):
+        text = self._jsonl_bytes(text)
+        doc_off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+        if doc_off.ndim != 1 or len(doc_off) < 1 or int(doc_off[-1]) != len(text):
+            raise ValueError("doc_off must hold n + 1 offsets that end at len(text)")
+        return text, doc_off
+
+    def line_dedup_packed(self, ls: NativeLineSet, text, doc_off: np.ndarray, add: bool = True) -> LineDedup:
+        """Packed text without the lines the set has seen (tk_line_dedup): host arrays in -- `text` bytes or uint8[N] (no copy), `doc_off`
+        uint64[n + 1] --, a `LineDedup` out."""
+        self._one_device("line_dedup_packed")
+        text, doc_off = self._packed_text(text, doc_off)
+        n = len(doc_off) - 1
+        off_out = np.zeros(n + 1, dtype=np.uint64)
+        n_lines, n_dropped = (np.zeros(n + 1, dtype=np.uint64)[:n] for _ in range(2))  # (one spare element each: no empty array's pointer)
+        out, n_out = ctypes.c_void_p(), ctypes.c_uint64()
+        _lib.raise_for(self._L.tk_line_dedup(self._h, ls.handle(), text.ctypes.data if len(text) else None, doc_off.ctypes.data, n, int(bool(add)), ctypes.byref(out),
+                                             ctypes.byref(n_out), off_out.ctypes.data, n_lines.ctypes.data, n_dropped.ctypes.data))
+        return LineDedup(_take_u8(out, int(n_out.value)), off_out, n_lines, n_dropped, int(n_dropped.sum()))
+
+    def line_add_packed(self, ls: NativeLineSet, text, doc_off: np.ndarray) -> None:
+        """The lines of packed text into the set (tk_line_add): host arrays in, as in `line_dedup_packed`."""
+        self._one_device("line_add_packed")
+        text, doc_off = self._packed_text(text, doc_off)
+        _lib.raise_for(self._L.tk_line_add(self._h, ls.handle(), text.ctypes.data if len(text) else None, doc_off.ctypes.data, len(doc_off) - 1))
 
     # ------------------------------------------------------------------ supervised samples (no reference counterpart: the host loop of its users)
     @staticmethod

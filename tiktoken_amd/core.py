@@ -475,6 +475,15 @@ class Encoding:
         self._core_bpe.line_stats_device(text, doc_off, seed=seed, **outs)
         return _tiktoken.LineStats(np.diff(doc_off.cpu().numpy().view(np.uint64)), *[outs[m].cpu().numpy().view(np.uint64) for m in _tiktoken.CoreBPE.LINE_OUTS])
 
+    # ------------------------------------------------------------------ line sets
+    def line_set(self, capacity: int, seed: int = 0, min_bytes: int = 1) -> "LineSet":
+        """An empty set of lines that lives on the GPU across calls (tk_line_set_create), and with it the line filter of CCNet-, C4- and
+        RefinedWeb-style corpus builds: `dedup_batch` hands a batch back without the lines that occurred anywhere earlier -- in an
+        earlier call, an earlier document, or earlier in the same document -- and remembers the ones it kept.  `capacity`: the most
+        distinct lines it holds, at most 2^30 (32 bytes of device memory to 64 each); lines shorter than `min_bytes` are never dropped
+        and never remembered.  The rule is stated in include/tiktoken_amd.h."""
+        return LineSet(self, self._core_bpe.line_set_create(capacity, seed, min_bytes))
+
     # ------------------------------------------------------------------ token n-gram sets
     def ngram_set(self, ngram: int = 13, *, capacity: int, seed: int = 0) -> "NgramSet":
         """An empty set of token n-grams that lives on the GPU across calls (tk_ngram_set_create): the n-grams of evaluation benchmarks,
@@ -1128,6 +1137,89 @@ class NgramSet:
     def overlap_tokens_packed(self, tokens, tok_off, mask: bool = False) -> "_tiktoken.NgramOverlap":
         """Tokens that are packed already against the set."""
         return self._enc._core_bpe.ngram_overlap_packed(self._native, tokens, tok_off, mask)
+
+
+class LineSet:
+    """`Encoding.line_set`: a set of lines on the GPU.  A context manager; `close()` releases the device memory.  An adding call is
+    refused (ValueError), before anything is written, when the lines added so far plus its own exceed the capacity; `len()` waits,
+    counts the distinct lines exactly and lowers that bound to the count."""
+
+    def __init__(self, enc: Encoding, native: "_tiktoken.NativeLineSet"):
+        self._enc, self._native = enc, native
+        self.capacity, self.seed, self.min_bytes = native.capacity, native.seed, native.min_bytes
+
+    def close(self) -> None:
+        self._native.close()
+
+    def __enter__(self) -> "LineSet":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __len__(self) -> int:
+        return self._enc._core_bpe.line_set_count(self._native)
+
+    def clear(self) -> None:
+        """Empties the set."""
+        self._enc._core_bpe.line_set_clear(self._native)
+
+    def _packed(self, texts):
+        """(blob, doc_off, the texts are bytes) of a batch of str -- packed as `encode_ordinary_batch_packed` packs them -- or bytes"""
+        if len(texts) and isinstance(texts[0], (bytes, bytearray, memoryview)):
+            off = np.zeros(len(texts) + 1, dtype=np.uint64)
+            np.cumsum([len(t) for t in texts], out=off[1:])
+            return b"".join(texts), off, True
+        return (*self._enc._pack(texts), False)
+
+    def dedup_packed(self, text, doc_off=None, add: bool = True) -> "_tiktoken.LineDedup":
+        """Packed text without the lines the set has seen, as a `LineDedup`, whose (text, doc_off) every packed encode entry takes.  `text`
+        and `doc_off` as `Encoding.line_stats_packed` takes them: host buffers, a `JsonlText`, or a uint8 torch tensor on the encoding's
+        GPU with `doc_off` a 64-bit tensor there (by pointer; the results come back to the host).  `add`: the kept lines go into the set
+        -- the kept occurrence of a line is the one that starts lowest --; `add=False` only filters, against a block list or an earlier
+        shard, and leaves duplicates within the batch alone."""
+        core = self._enc._core_bpe
+        if isinstance(text, _tiktoken.JsonlText):
+            text, doc_off = text.text, text.doc_off
+        if not hasattr(text, "data_ptr"):
+            return core.line_dedup_packed(self._native, text, doc_off, add)
+        import torch
+
+        if not hasattr(doc_off, "data_ptr"):
+            doc_off = torch.from_numpy(np.ascontiguousarray(doc_off, dtype=np.uint64).view(np.int64)).to(text.device)
+        n = max(doc_off.numel() - 1, 0)
+        new = lambda count, dtype=torch.int64: torch.zeros(count, dtype=dtype, device=text.device)  # noqa: E731
+        out = dict(text_out=new(text.numel(), torch.uint8), doc_off_out=new(n + 1), n_lines=new(n), n_dropped=new(n), counts=new(2))
+        core.line_dedup_device(self._native, text, doc_off, add, **out)
+        host = {k: v.cpu().numpy().view(np.uint8 if k == "text_out" else np.uint64) for k, v in out.items()}
+        kept, dropped = (int(v) for v in host["counts"])
+        return _tiktoken.LineDedup(host["text_out"][:kept], host["doc_off_out"], host["n_lines"], host["n_dropped"], dropped)
+
+    def dedup_batch(self, texts: "Sequence[str] | Sequence[bytes]", add: bool = True) -> "list[str] | list[bytes]":
+        """The batch without the lines the set has seen: a list of the same length and type, every document in its place, possibly empty."""
+        blob, off, raw = self._packed(texts)
+        r = self._enc._core_bpe.line_dedup_packed(self._native, blob, off, add)
+        view, bounds = memoryview(r.text), r.doc_off.tolist()
+        docs = [bytes(view[a:b]) for a, b in zip(bounds[:-1], bounds[1:])]
+        return docs if raw else [d.decode("utf-8", errors="replace") for d in docs]
+
+    def add_packed(self, text, doc_off=None) -> None:
+        """The lines of packed text into the set and nothing else: filling a block list.  Inputs as `dedup_packed` takes them."""
+        core = self._enc._core_bpe
+        if isinstance(text, _tiktoken.JsonlText):
+            text, doc_off = text.text, text.doc_off
+        if not hasattr(text, "data_ptr"):
+            return core.line_add_packed(self._native, text, doc_off)
+        import torch
+
+        if not hasattr(doc_off, "data_ptr"):
+            doc_off = torch.from_numpy(np.ascontiguousarray(doc_off, dtype=np.uint64).view(np.int64)).to(text.device)
+        core.line_add_device(self._native, text, doc_off)
+
+    def add_batch(self, texts: "Sequence[str] | Sequence[bytes]") -> None:
+        """The lines of a batch of str or bytes into the set."""
+        blob, off, _ = self._packed(texts)
+        self._enc._core_bpe.line_add_packed(self._native, blob, off)
 
 
 class DecodeStream:

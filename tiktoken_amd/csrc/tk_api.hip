@@ -35,6 +35,7 @@
 #include "tk_ngram.h"
 #include "tk_repeat.h"
 #include "tk_lines.h"
+#include "tk_line_set.h"
 #include "tk_jsonl.h"
 #include "tk_sample_rows.h"
 #include "tk_samples.h"
@@ -4131,8 +4132,8 @@ static int ln_run(tk_core* c, hipStream_t s, const uint8_t* d_text, uint64_t n, 
     const bool aligned = ((uintptr_t)d_text & 15u) == 0;
     const dim3 tiles((uint32_t)nt), block(TK_LN_THREADS);
     TRY(timed(c, s, "tk_k_ln_clear", [&] { hipLaunchKernelGGL(tk_k_ln_clear, dim3(1), dim3(256), 0, s, words, (uint64_t)TK_LN_WORDS); }));
-    TRY(timed(c, s, "tk_k_ln_sum", [&] { hipLaunchKernelGGL(tk_k_ln_sum, tiles, block, 0, s, p, d_text, d_doc_off, aligned, T, words); }));
-    TRY(timed(c, s, "tk_k_ln_carry", [&] { hipLaunchKernelGGL(tk_k_ln_carry, dim3(1), dim3(1024), 0, s, p, T, words); }));
+    TRY(timed(c, s, "tk_k_ln_sum", [&] { hipLaunchKernelGGL((tk_k_ln_sum<2>), tiles, block, 0, s, p, d_text, d_doc_off, aligned, T, words); }));
+    TRY(timed(c, s, "tk_k_ln_carry", [&] { hipLaunchKernelGGL((tk_k_ln_carry<2>), dim3(1), dim3(1024), 0, s, p, T, words); }));
     unsigned long long got[TK_LN_WORDS];
     HIPCHK(hipMemcpyAsync(got, words, sizeof got, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));  // the one wait
@@ -4193,6 +4194,234 @@ extern "C" int tk_line_stats(tk_core* c, const uint8_t* text, const uint64_t* do
         HIPCHK(hipGetLastError());
         for (int i = 0; i < 9; ++i)
             if (hp[i] && n_docs) HIPCHK(hipMemcpy(hp[i], d.a[i], n_docs * 8, hipMemcpyDeviceToHost));
+        return TK_OK;
+    });
+}
+
+// ------------------------------------------------------------------------------------------
+// Line sets (tk_line_set.h): a set of line keys on the device, and packed text rewritten without the lines the set has seen.  Like a
+// tk_ngram_set the set owns what outlives a batch -- the table, the counter -- and what its calls work in: the tiles' scratch, the bitmap,
+// the buffers of the host entries, and the event that orders its calls among themselves on the device.
+// ------------------------------------------------------------------------------------------
+struct tk_line_set {
+    tk_core* c = nullptr;
+    int device = 0;
+    uint64_t seed = 0, capacity = 0, min_bytes = 1, S = 0;
+    uint64_t bound = 0;  // at least the distinct keys in the table: the lines of the adds since the last exact count
+    uint32_t epoch = 0;  // add calls since the last clear
+    Event done;          // recorded behind every call on the set, on that call's stream; the next call's stream waits for it first
+    Buf table, work, bits, in, out;  // table: keys, first words, the counter; in, out: of the entries that take host arrays
+    TkLsTab tab() const { return TkLsTab{table.as<unsigned long long>(), table.as<unsigned long long>() + S, table.as<unsigned long long>() + 2 * S}; }
+};
+struct LsCall {  // a call behind its one wait
+    TkLs q;
+    TkLnTiles T;
+    unsigned long long* words;  // the line statistics' report words, then TK_LS_WORDS of the set's
+    uint32_t* kept;             // [n_tiles]
+    bool aligned;
+    uint64_t lines;  // of the batch
+};
+struct LsOuts {  // the caller's device arrays; all but text and doc_off may be null
+    uint8_t* text;
+    uint64_t *doc_off, *n_lines, *n_dropped, *counts;
+};
+static const char* const LS_CAP_MSG = "n_bytes: the text of a line set call is at most 0xFFFF0000 bytes (positions are 32-bit)";
+static int ls_check(tk_core* c, tk_line_set* st) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if (!st) return fail(TK_VALUE_ERROR, "set is null");
+    if (st->c != c) return fail(TK_VALUE_ERROR, "the line set belongs to another core");
+    return TK_OK;
+}
+static int ls_clear_run(tk_line_set* st, hipStream_t s) {
+    HIPCHK(hipStreamWaitEvent(s, st->done, 0));
+    TRY(timed(st->c, s, "tk_k_ls_clear", [&] { hipLaunchKernelGGL(tk_k_ls_clear, dim3(grid_for(st->S, 256, 65536)), dim3(256), 0, s, st->tab(), st->S); }));
+    HIPCHK(hipEventRecord(st->done, s));
+    st->bound = 0, st->epoch = 0;
+    return TK_OK;
+}
+// The sum and carry passes over the line kind and the host's ONE wait, on s: doc_off is refused here, and an add past the capacity,
+// before anything of the caller's or of the set's table is written.  The caller holds c->mu.
+static int ls_front(tk_line_set* st, hipStream_t s, const uint8_t* d_text, uint64_t n, const uint64_t* d_doc_off, uint64_t n_docs, bool add, LsCall& k) {
+    tk_core* c = st->c;
+    if (tk_ln_shape(n, n_docs, st->seed, &k.q.ln)) return fail(TK_VALUE_ERROR, LS_CAP_MSG);
+    if (n_docs > 0xFFFFFFFEull) return fail(TK_VALUE_ERROR, "n_docs: at most 2^32 - 2 documents");
+    if (add && st->epoch >= TK_LS_MAX_EPOCH) return fail(TK_VALUE_ERROR, "2^32 - 2 add calls on a line set: clear it");
+    k.q.S = st->S, k.q.min_bytes = st->min_bytes, k.q.epoch = add ? st->epoch + 1 : 0u;
+    HIPCHK(hipStreamWaitEvent(s, st->done, 0));  // (the scratch is the set's)
+    const uint64_t nt = k.q.ln.n_tiles;
+    Carve work;
+    const uint64_t at_words = work.add((TK_LN_WORDS + TK_LS_WORDS) * 8), at_seg = work.add(nt * sizeof(TkLnSeg)), at_nseg = work.add(nt * 4), at_kept = work.add(nt * 4);
+    TRY(ensure(st->work, work.total));
+    k.words = carved<unsigned long long>(st->work, at_words);
+    k.T = TkLnTiles{carved<TkLnSeg>(st->work, at_seg), carved<uint32_t>(st->work, at_nseg)};
+    k.kept = carved<uint32_t>(st->work, at_kept);
+    k.aligned = ((uintptr_t)d_text & 15u) == 0;
+    TRY(timed(c, s, "tk_k_ln_clear", [&] { hipLaunchKernelGGL(tk_k_ln_clear, dim3(1), dim3(256), 0, s, k.words, (uint64_t)(TK_LN_WORDS + TK_LS_WORDS)); }));
+    TRY(timed(c, s, "tk_k_ln_sum", [&] { hipLaunchKernelGGL((tk_k_ln_sum<1>), dim3((uint32_t)nt), dim3(TK_LN_THREADS), 0, s, k.q.ln, d_text, d_doc_off, k.aligned, k.T, k.words); }));
+    TRY(timed(c, s, "tk_k_ln_carry", [&] { hipLaunchKernelGGL((tk_k_ln_carry<1>), dim3(1), dim3(1024), 0, s, k.q.ln, k.T, k.words); }));
+    unsigned long long got[TK_LN_WORDS];
+    HIPCHK(hipMemcpyAsync(got, k.words, sizeof got, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));  // the one wait
+    HIPCHK(hipGetLastError());
+    if (got[TK_LN_W_BAD]) return fail(TK_VALUE_ERROR, "doc_off must ascend from 0 to n_bytes");
+    k.lines = got[TK_LN_W_SEGS];
+    if (add && (k.lines > st->capacity || st->bound > st->capacity - k.lines))
+        return fail(TK_VALUE_ERROR, "an add of " + std::to_string(k.lines) + " lines to a line set of capacity " + std::to_string(st->capacity) + " that may hold " +
+                                        std::to_string(st->bound) + " keys: count it (the bound falls to the exact number), clear it, or make a larger set");
+    return TK_OK;
+}
+static int ls_mark(tk_line_set* st, hipStream_t s, const LsCall& k, const uint8_t* d_text, const uint64_t* d_doc_off) {
+    TRY(timed(st->c, s, "tk_k_ls_mark", [&] {
+        hipLaunchKernelGGL(tk_k_ls_mark, dim3(k.q.ln.n_tiles), dim3(TK_LN_THREADS), 0, s, k.q, d_text, d_doc_off, k.aligned, k.T, st->tab());
+    }));
+    st->epoch = k.q.epoch, st->bound += k.lines;
+    return TK_OK;
+}
+// ls_add_run, ls_dedup_run: the caller holds c->mu.  Launches on s; the host waits once (ls_front).
+static int ls_add_run(tk_line_set* st, hipStream_t s, const uint8_t* d_text, uint64_t n, const uint64_t* d_doc_off, uint64_t n_docs) {
+    LsCall k;
+    TRY(ls_front(st, s, d_text, n, d_doc_off, n_docs, true, k));
+    TRY(ls_mark(st, s, k, d_text, d_doc_off));
+    HIPCHK(hipEventRecord(st->done, s));
+    return TK_OK;
+}
+static int ls_dedup_run(tk_line_set* st, hipStream_t s, const uint8_t* d_text, uint64_t n, const uint64_t* d_doc_off, uint64_t n_docs, bool add, LsOuts o) {
+    tk_core* c = st->c;
+    if (n && o.text == d_text) return fail(TK_VALUE_ERROR, "d_text_out must not be d_text: a tile's kept bytes are written while later tiles are still read");
+    LsCall k;
+    TRY(ls_front(st, s, d_text, n, d_doc_off, n_docs, add, k));
+    const uint64_t nt = k.q.ln.n_tiles, n_bits = tk_ls_bitmap_words(n);
+    TRY(ensure(st->bits, n_bits * 8));
+    auto zero = [&](void* a, uint64_t n64) {
+        return timed(c, s, "tk_k_ln_clear", [&] { hipLaunchKernelGGL(tk_k_ln_clear, dim3(grid_for(n64, 256, 65536)), dim3(256), 0, s, (unsigned long long*)a, n64); });
+    };
+    TRY(zero(st->bits.p, n_bits));
+    if (o.n_lines && n_docs) TRY(zero(o.n_lines, n_docs));
+    if (o.n_dropped && n_docs) TRY(zero(o.n_dropped, n_docs));
+    if (add) TRY(ls_mark(st, s, k, d_text, d_doc_off));
+    const dim3 tiles((uint32_t)nt), block(TK_LN_THREADS);
+    uint32_t* bits = st->bits.as<uint32_t>();
+    TRY(timed(c, s, "tk_k_ls_decide", [&] {
+        hipLaunchKernelGGL(tk_k_ls_decide, tiles, block, 0, s, k.q, d_text, d_doc_off, k.aligned, k.T, st->tab(), bits, (unsigned long long*)o.n_lines,
+                           (unsigned long long*)o.n_dropped, k.words);
+    }));
+    TRY(timed(c, s, "tk_k_ls_keep", [&] { hipLaunchKernelGGL(tk_k_ls_keep, tiles, block, 0, s, k.q, d_text, d_doc_off, k.aligned, k.T, bits, k.kept); }));
+    TRY(timed(c, s, "tk_k_ls_scan", [&] { hipLaunchKernelGGL(tk_k_ls_scan, dim3(1), dim3(1024), 0, s, k.kept, nt); }));
+    TRY(timed(c, s, "tk_k_ls_write", [&] {
+        hipLaunchKernelGGL(tk_k_ls_write, tiles, block, 0, s, k.q, d_text, d_doc_off, k.aligned, k.T, bits, k.kept, k.words, o.text, (unsigned long long*)o.doc_off,
+                           (unsigned long long*)o.counts);
+    }));
+    HIPCHK(hipEventRecord(st->done, s));
+    return TK_OK;
+}
+// host text and offsets into st->in, on the core's stream: run(d_text, n, d_off) behind them, under the core's mutex
+template <class Run>
+static int ls_from_host(tk_core* c, tk_line_set* st, const uint8_t* text, const uint64_t* doc_off, uint64_t n_docs, Run&& run) {
+    TRY(ls_check(c, st));
+    if (!doc_off) return fail(TK_VALUE_ERROR, "null argument");
+    TRY(check_offsets(doc_off, n_docs, "doc_off"));
+    const uint64_t n = doc_off[n_docs];
+    if (n && !text) return fail(TK_VALUE_ERROR, "null argument");
+    if (n > TK_LN_MAX_BYTES) return fail(TK_VALUE_ERROR, LS_CAP_MSG);
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    Carve in;
+    const uint64_t at_off = in.add((n_docs + 1) * 8), at_text = in.add(n + 16);
+    TRY(ensure(st->in, in.total + 16));
+    uint64_t* d_off = carved<uint64_t>(st->in, at_off);
+    uint8_t* d_text = carved<uint8_t>(st->in, at_text);
+    HIPCHK(hipStreamWaitEvent(c->stream, st->done, 0));  // (st->in may still be read by a call on another stream)
+    HIPCHK(hipMemcpyAsync(d_off, doc_off, (n_docs + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    if (n) HIPCHK(hipMemcpyAsync(d_text, text, n, hipMemcpyHostToDevice, c->stream));
+    return drained(c, [&]() -> int {
+        TRY(run(d_text, n, d_off));
+        HIPCHK(hipStreamSynchronize(c->stream));  // (the caller's arrays are his again)
+        HIPCHK(hipGetLastError());
+        return TK_OK;
+    });
+}
+
+extern "C" void tk_line_set_destroy(tk_line_set* st) {
+    if (!st) return;
+    (void)hipSetDevice(st->device);
+    delete st;
+}
+extern "C" int tk_line_set_create(tk_core* c, uint64_t seed, uint64_t capacity, uint64_t min_bytes, tk_line_set** set_out) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if (!set_out) return fail(TK_VALUE_ERROR, "null argument");
+    uint64_t S = 0;
+    switch (tk_ls_shape(capacity, min_bytes, &S)) {
+        case 0: break;
+        case 1: return fail(TK_VALUE_ERROR, "min_bytes must be at least 1");
+        default: return fail(TK_VALUE_ERROR, "capacity must be 1 .. 2^30");
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    std::unique_ptr<tk_line_set, void (*)(tk_line_set*)> st(new tk_line_set, tk_line_set_destroy);
+    st->c = c, st->device = c->device, st->seed = seed, st->capacity = capacity, st->min_bytes = min_bytes, st->S = S;
+    HIPCHK(st->done.create());
+    TRY(ensure(st->table, (2 * S + 1) * 8));
+    TRY(drained(c, [&] { return ls_clear_run(st.get(), c->stream); }));
+    *set_out = st.release();
+    return TK_OK;
+}
+extern "C" int tk_line_set_clear(tk_line_set* st) {
+    if (!st) return fail(TK_VALUE_ERROR, "set is null");
+    return device_pass(st->c, true, nullptr, [&](hipStream_t s) { return ls_clear_run(st, s); });
+}
+// The exact number of distinct keys: waits for the calls queued on the set, whatever their streams.
+extern "C" int tk_line_set_count(tk_line_set* st, uint64_t* count_out) {
+    if (!st) return fail(TK_VALUE_ERROR, "set is null");
+    if (!count_out) return fail(TK_VALUE_ERROR, "null argument");
+    return device_pass(st->c, true, nullptr, [&](hipStream_t) -> int {
+        HIPCHK(hipEventSynchronize(st->done));
+        uint64_t n = 0;
+        HIPCHK(hipMemcpy(&n, st->tab().count, 8, hipMemcpyDeviceToHost));
+        if (n > st->capacity) return fail(TK_RUNTIME_ERROR, "internal error: the line set holds more keys than its capacity");
+        *count_out = st->bound = n;
+        return TK_OK;
+    });
+}
+
+extern "C" int tk_line_add_device(tk_core* c, tk_line_set* st, const void* d_text, uint64_t n_bytes, const void* d_doc_off, uint64_t n_docs, void* stream) {
+    TRY(ls_check(c, st));
+    // (the stream as given, null being HIP's null stream: tk_fingerprint_device's convention)
+    return device_pass(c, d_doc_off && (d_text || !n_bytes), stream,
+                       [&](hipStream_t) { return ls_add_run(st, (hipStream_t)stream, (const uint8_t*)d_text, n_bytes, (const uint64_t*)d_doc_off, n_docs); });
+}
+extern "C" int tk_line_add(tk_core* c, tk_line_set* st, const uint8_t* text, const uint64_t* doc_off, uint64_t n_docs) {
+    return ls_from_host(c, st, text, doc_off, n_docs, [&](const uint8_t* d_text, uint64_t n, const uint64_t* d_off) { return ls_add_run(st, c->stream, d_text, n, d_off, n_docs); });
+}
+extern "C" int tk_line_dedup_device(tk_core* c, tk_line_set* st, const void* d_text, uint64_t n_bytes, const void* d_doc_off, uint64_t n_docs, int add, void* stream,
+                                    void* d_text_out, uint64_t* d_doc_off_out, uint64_t* d_n_lines, uint64_t* d_n_dropped, uint64_t* d_counts_out) {
+    TRY(ls_check(c, st));
+    return device_pass(c, d_doc_off && d_doc_off_out && (!n_bytes || (d_text && d_text_out)), stream, [&](hipStream_t) {
+        return ls_dedup_run(st, (hipStream_t)stream, (const uint8_t*)d_text, n_bytes, (const uint64_t*)d_doc_off, n_docs, add != 0,
+                            LsOuts{(uint8_t*)d_text_out, d_doc_off_out, d_n_lines, d_n_dropped, d_counts_out});
+    });
+}
+extern "C" int tk_line_dedup(tk_core* c, tk_line_set* st, const uint8_t* text, const uint64_t* doc_off, uint64_t n_docs, int add, uint8_t** text_out, uint64_t* n_bytes_out,
+                             uint64_t* doc_off_out, uint64_t* n_lines_out, uint64_t* n_dropped_out) {
+    if (!text_out || !n_bytes_out || !doc_off_out) return fail(TK_VALUE_ERROR, "null argument");
+    return ls_from_host(c, st, text, doc_off, n_docs, [&](const uint8_t* d_text, uint64_t n, const uint64_t* d_off) -> int {
+        Carve res;
+        const uint64_t at_text = res.add(n + 16), at_off = res.add((n_docs + 1) * 8), at_lines = res.add(n_docs * 8), at_dropped = res.add(n_docs * 8), at_counts = res.add(16);
+        TRY(ensure(st->out, res.total + 16));
+        const LsOuts d{carved<uint8_t>(st->out, at_text), carved<uint64_t>(st->out, at_off), n_lines_out ? carved<uint64_t>(st->out, at_lines) : nullptr,
+                       n_dropped_out ? carved<uint64_t>(st->out, at_dropped) : nullptr, carved<uint64_t>(st->out, at_counts)};
+        TRY(ls_dedup_run(st, c->stream, d_text, n, d_off, n_docs, add != 0, d));
+        uint64_t counts[2];
+        HIPCHK(hipMemcpyAsync(counts, d.counts, 16, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipGetLastError());
+        if (counts[0] > n) return fail(TK_RUNTIME_ERROR, "internal error: a line dedup kept more bytes than it was given");
+        ResultBag bag;
+        TRY(bag.fetch(text_out, d.text, counts[0]));
+        HIPCHK(hipMemcpy(doc_off_out, d.doc_off, (n_docs + 1) * 8, hipMemcpyDeviceToHost));
+        if (n_lines_out && n_docs) HIPCHK(hipMemcpy(n_lines_out, d.n_lines, n_docs * 8, hipMemcpyDeviceToHost));
+        if (n_dropped_out && n_docs) HIPCHK(hipMemcpy(n_dropped_out, d.n_dropped, n_docs * 8, hipMemcpyDeviceToHost));
+        bag.give();
+        *n_bytes_out = counts[0];
         return TK_OK;
     });
 }

@@ -163,6 +163,8 @@ __global__ __launch_bounds__(256) void tk_k_ln_clear(unsigned long long* a, uint
     for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) a[i] = 0;
 }
 
+// (KINDS: 2, or 1 for the line kind alone -- tk_line_set.h; the same for tk_k_ln_carry, whose report word then counts lines)
+template <uint32_t KINDS>
 __global__ __launch_bounds__(TK_LN_THREADS) void tk_k_ln_sum(TkLn p, const uint8_t* __restrict__ text, const uint64_t* __restrict__ doc_off, bool aligned, TkLnTiles T,
                                                              unsigned long long* __restrict__ words) {
     __shared__ TkLnShared sh;
@@ -181,7 +183,7 @@ __global__ __launch_bounds__(TK_LN_THREADS) void tk_k_ln_sum(TkLn p, const uint8
     __syncthreads();
     const uint32_t before = tid ? last[tid - 1] : 0u;
 #pragma unroll 1
-    for (uint32_t kind = 0; kind < 2; ++kind) {
+    for (uint32_t kind = 0; kind < KINDS; ++kind) {
         TkLnSeg total;
         tk_ln_block_exscan(tk_ln_lane_tail(p, L, kind, sh), TkLnSeg{tk_ln_empty(), 0u}, sh.wsum, &total);
         const uint32_t n = tk_wave_sum_u32((uint32_t)__popc(L.cut(kind) & ((L.content(kind) << 1) | ((before >> kind) & 1u))));
@@ -195,13 +197,14 @@ __global__ __launch_bounds__(TK_LN_THREADS) void tk_k_ln_sum(TkLn p, const uint8
     }
 }
 
+template <uint32_t KINDS>
 __global__ __launch_bounds__(1024) void tk_k_ln_carry(TkLn p, TkLnTiles T, unsigned long long* __restrict__ words) {
     __shared__ TkLnSeg wsum[16];
     const uint32_t per = (p.n_tiles + 1023u) / 1024u;
     const uint64_t a = (uint64_t)threadIdx.x * per, b = a + per < p.n_tiles ? a + per : p.n_tiles;
     unsigned long long segs = 0;
 #pragma unroll 1
-    for (uint32_t kind = 0; kind < 2; ++kind) {
+    for (uint32_t kind = 0; kind < KINDS; ++kind) {
         TkLnSeg* seg = T.seg + (uint64_t)kind * p.n_tiles;
         const uint32_t* nseg = T.nseg + (uint64_t)kind * p.n_tiles;
         TkLnSeg mine{tk_ln_empty(), 0u};
