@@ -608,9 +608,9 @@ int tk_encode_batch_repetition(tk_core* core, const uint8_t* utf8, const uint64_
  * A workgroup takes tk_stat("lines_tile") bytes, a lane tk_stat("lines_lane"), a wavefront tk_stat("lines_wave"); a line of any length
  * costs a scan over the tiles it crosses, never a walk.  The core owns the scratch: 100 bytes per tile, 88 bytes per document and a table of
  * 64-bit keys, the power of two >= 2 (lines + paragraphs), cleared per call.
- * NOT built: normalised comparison (trimmed, case-folded, digits masked); "\r\n" as a line end; word counts and the other Gopher
- * quality rules; several GPUs; buffers above 0xFFFF0000 bytes.  (Duplicates across documents and calls, the decision per line and the
- * removal of duplicate lines are the line sets' below.) */
+ * NOT built: normalised comparison (trimmed, case-folded, digits masked); "\r\n" as a line end; several GPUs; buffers above 0xFFFF0000
+ * bytes.  (Word counts and the other Gopher quality rules are the word statistics' below; duplicates across documents and calls, the
+ * decision per line and the removal of duplicate lines are the line sets'.) */
 /* Device pointers in (d_text uint8[n_bytes] at any alignment -- 16-byte aligned is the fast path --, d_doc_off uint64[n_docs + 1], checked
  * on the device); the caller's device arrays out.  Everything is queued on `stream`, null being HIP's null stream, and the host waits
  * ONCE on that stream, for the report words that say whether doc_off is well-formed and how many lines and paragraphs the table must
@@ -622,6 +622,51 @@ int tk_line_stats_device(tk_core* core, const void* d_text, uint64_t n_bytes, co
 int tk_line_stats(tk_core* core, const uint8_t* text, const uint64_t* doc_off, uint64_t n_docs, uint64_t seed, uint64_t* n_chars_out, uint64_t* n_lines_out,
                   uint64_t* n_dup_lines_out, uint64_t* dup_line_chars_out, uint64_t* n_paragraphs_out, uint64_t* n_dup_paragraphs_out, uint64_t* dup_paragraph_chars_out,
                   uint64_t* n_bullet_lines_out, uint64_t* n_ellipsis_lines_out);
+/* Word statistics: per document of packed TEXT the word-level rules of the Gopher quality filter (Rae et al. 2021, A.1.1; DataTrove's
+ * GopherQualityFilter) -- word count, mean word length, symbol-to-word ratio, share of words with a letter, stop words -- and the
+ * line-punctuation rule of C4 and FineWeb, which falls out of the same pass.  Replaces nothing in the reference: it is the host step of
+ * the reference's users, text.split() per document.  With tk_line_stats and tk_repetition it makes the whole filter, each a keep mask for
+ * tk_select_docs_device, the text never leaving the device.
+ * The rule.  Input: text uint8[N], doc_off uint64[n_docs + 1] ascending from 0 to N, N <= 0xFFFF0000.  Bytes are bytes: nothing is
+ *  trimmed or case-folded, and nothing below -- a pattern, a word, a run, a line -- ever crosses a document.
+ *  White space.  The byte sequences of the 29 chars for which Python's str.isspace() holds: 09-0D, 1C-1F, 20; C2 85, C2 A0; E1 9A 80;
+ *   E2 80 80-8A, E2 80 A8, E2 80 A9, E2 80 AF; E2 81 9F; E3 80 80.  A sequence counts wherever it lies wholly inside one document, in
+ *   well-formed or ill-formed text; the sequences cannot overlap one another.  On well-formed UTF-8 the words are doc.decode().split().
+ *  Words.  A word is a maximal run of bytes that are not white space inside one document; a document that is empty or all white space
+ *   has none.
+ *  Letters.  A byte that is not 0b10xxxxxx is a letter when the continuation bytes its length asks for (2 from C0, 3 from E0, 4 from F0)
+ *   all follow inside the document and are 0b10xxxxxx, and the code point, decoded as the encoder's classifier decodes it, is a letter of
+ *   the library's Unicode table (general category L*).  Overlong forms and surrogates are not looked at any further.
+ *  Stop words.  Up to 32 distinct byte strings of 1 to 8 bytes without white space: stop_bytes, with stop_off uint64[n_stop + 1]
+ *   ascending from 0.  A word equals a stop word byte for byte or not at all; nothing is hashed.
+ *  Terminal bytes.  Up to 16 ASCII bytes (C4 and FineWeb: . ! ? " ').
+ *  Outputs, uint64[n_docs] each, any pointer may be null:
+ *   n_words          the words;
+ *   word_chars       the bytes inside words that are not 0b10xxxxxx: Gopher's mean word length is word_chars / n_words;
+ *   n_alpha_words    the words with at least one letter;
+ *   stop_mask        bit i: some word of the document equals stop word i;
+ *   n_hash           doc.count(b"#");
+ *   n_ellipsis       doc.count(b"...") + the U+2026 (E2 80 A6) inside the document: a maximal run of r '.' gives r / 3;
+ *   n_lines          the lines as tk_line_stats counts them: maximal runs of bytes other than '\n';
+ *   n_punct_lines    the lines whose last byte is a terminal byte: line.endswith(...) over the non-empty lines of split("\n").
+ *  Every value is a function of (text, doc_off, stop words, terminal bytes) alone, never of the schedule: sums and ORs commute.
+ *  Refused with TK_VALUE_ERROR before anything is written: N above 0xFFFF0000; more than 32 stop words; a stop word that is empty,
+ *  longer than 8 bytes, repeated, or holds a white-space sequence; more than 16 terminal bytes; a terminal byte >= 0x80.
+ * A workgroup takes tk_stat("words_tile") bytes, a lane tk_stat("words_lane"), a wavefront tk_stat("words_wave"); a word or a run of dots
+ * of any length costs a scan over the tiles it crosses, never a walk.  The core owns the scratch: 24 bytes per tile, 64 per document.
+ * NOT built: case folding; word splitting by a tokenizer instead of white space; stop words above 8 bytes; short-line and per-line word
+ * counts; several GPUs; buffers above 0xFFFF0000 bytes. */
+/* Device pointers in (d_text uint8[n_bytes] at any alignment -- 16-byte aligned is the fast path --, d_doc_off uint64[n_docs + 1]); the
+ * stop words and terminal bytes are host memory; the caller's device arrays out.  Everything is queued on `stream`, null being HIP's null
+ * stream, and the host waits for NOTHING: as in tk_fingerprint_device, a d_doc_off that does not ascend from 0 to n_bytes gives values
+ * nobody has defined and never an access outside the arrays. */
+int tk_word_stats_device(tk_core* core, const void* d_text, uint64_t n_bytes, const void* d_doc_off, uint64_t n_docs, const uint8_t* stop_bytes, const uint64_t* stop_off,
+                         uint64_t n_stop, const uint8_t* terminal, uint64_t n_terminal, void* stream, uint64_t* d_n_words, uint64_t* d_word_chars, uint64_t* d_n_alpha_words,
+                         uint64_t* d_stop_mask, uint64_t* d_n_hash, uint64_t* d_n_ellipsis, uint64_t* d_n_lines, uint64_t* d_n_punct_lines);
+/* The same from host arrays to the caller's host arrays (n_bytes is doc_off[n_docs]); a doc_off that does not ascend from 0 is refused. */
+int tk_word_stats(tk_core* core, const uint8_t* text, const uint64_t* doc_off, uint64_t n_docs, const uint8_t* stop_bytes, const uint64_t* stop_off, uint64_t n_stop,
+                  const uint8_t* terminal, uint64_t n_terminal, uint64_t* n_words_out, uint64_t* word_chars_out, uint64_t* n_alpha_words_out, uint64_t* stop_mask_out,
+                  uint64_t* n_hash_out, uint64_t* n_ellipsis_out, uint64_t* n_lines_out, uint64_t* n_punct_lines_out);
 /* Line sets: a set of line keys that lives on the device across calls, and packed TEXT rewritten without the lines the set has seen
  * -- navigation bars, cookie banners, licence footers: the line filter of CCNet, C4 and RefinedWeb-style builds, which drops every line
  * that occurred anywhere earlier in the corpus.  Replaces nothing in the reference: it is the host step of the reference's users, a loop
@@ -1136,7 +1181,8 @@ void tk_last_stats(tk_core* core, uint64_t* n_bytes, uint64_t* n_pieces, uint64_
  * passes (a constant of the build); "fingerprint_tile": the token positions of a tile of the fingerprint pass, "ngram_tile": of the
  * n-gram passes (likewise); "repeat_tile" and "repeat_lds_tokens": of the repetition pass, the positions of a tile of its LDS class and
  * the longest document that class takes (likewise); "lines_tile", "lines_lane", "lines_wave" and "lines_docs": of the line statistics
- * pass, the bytes of a tile, of a lane and of a wavefront, and the documents of a tile whose sums are gathered in LDS (likewise). */
+ * pass, the bytes of a tile, of a lane and of a wavefront, and the documents of a tile whose sums are gathered in LDS (likewise); "words_tile",
+ * "words_lane", "words_wave" and "words_docs": the same of the word statistics pass. */
 uint64_t tk_stat(tk_core* core, const char* name);
 
 #ifdef __cplusplus

@@ -216,6 +216,11 @@ def lib() -> ctypes.CDLL:
             L.tk_line_stats_device.argtypes = [vp, vp, u64, vp, u64, u64, vp, *[vp] * 9]
             L.tk_line_stats.restype = i32
             L.tk_line_stats.argtypes = [vp, vp, vp, u64, u64, *[vp] * 9]
+        if hasattr(L, "tk_word_stats_device"):  # (absent from older builds selected through $TIKTOKEN_AMD_LIB)
+            L.tk_word_stats_device.restype = i32
+            L.tk_word_stats_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, vp, u64, vp, *[vp] * 8]
+            L.tk_word_stats.restype = i32
+            L.tk_word_stats.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, u64, *[vp] * 8]
         if hasattr(L, "tk_line_set_create"):  # (absent from older builds selected through $TIKTOKEN_AMD_LIB)
             L.tk_line_set_create.restype = i32
             L.tk_line_set_create.argtypes = [vp, u64, u64, u64, P(vp)]

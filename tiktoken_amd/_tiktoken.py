@@ -848,6 +848,64 @@ class LineStats(NamedTuple):
         return keep.astype(np.uint8)
 
 
+GOPHER_STOP_WORDS = ("the", "be", "to", "of", "and", "that", "have", "with")
+TERMINAL_PUNCTUATION = ".!?\"'"
+
+
+class WordStats(NamedTuple):
+    """Word statistics of a batch of texts (tk_word_stats; the rule: include/tiktoken_amd.h), uint64[n] each: `length` the documents'
+    bytes, `n_words` their words -- maximal runs of bytes that are not white space, `str.split()` --, `word_chars` the chars inside words,
+    `n_alpha_words` the words with a letter, `stop_mask` bit i: stop word i occurs, `n_hash` the '#', `n_ellipsis` the "..." and U+2026,
+    `n_lines` the lines and `n_punct_lines` those that end in terminal punctuation."""
+    length: np.ndarray
+    n_words: np.ndarray
+    word_chars: np.ndarray
+    n_alpha_words: np.ndarray
+    stop_mask: np.ndarray
+    n_hash: np.ndarray
+    n_ellipsis: np.ndarray
+    n_lines: np.ndarray
+    n_punct_lines: np.ndarray
+
+    def mean_word_length(self) -> np.ndarray:
+        """float64[n]: word_chars / n_words (0 where there is no word)"""
+        return LineStats._ratio(self.word_chars, self.n_words)
+
+    def alpha_fraction(self) -> np.ndarray:
+        """float64[n]: n_alpha_words / n_words (0 where there is no word)"""
+        return LineStats._ratio(self.n_alpha_words, self.n_words)
+
+    def hash_ratio(self) -> np.ndarray:
+        """float64[n]: n_hash / n_words (0 where there is no word)"""
+        return LineStats._ratio(self.n_hash, self.n_words)
+
+    def ellipsis_ratio(self) -> np.ndarray:
+        """float64[n]: n_ellipsis / n_words (0 where there is no word)"""
+        return LineStats._ratio(self.n_ellipsis, self.n_words)
+
+    def n_stop_words(self) -> np.ndarray:
+        """uint64[n]: how many of the stop words occur: the set bits of stop_mask"""
+        return np.unpackbits(np.ascontiguousarray(self.stop_mask, dtype="<u8").view(np.uint8).reshape(-1, 8), axis=1).sum(axis=1).astype(np.uint64)
+
+    def punct_line_fraction(self) -> np.ndarray:
+        """float64[n]: n_punct_lines / n_lines (0 where there is no line)"""
+        return LineStats._ratio(self.n_punct_lines, self.n_lines)
+
+    def keep_mask(self, min_words=50, max_words=100_000, min_mean_word_length=3, max_mean_word_length=10, max_hash_ratio=0.1, max_ellipsis_ratio=0.1,
+                  min_alpha_fraction=0.8, min_stop_words=2, min_punct_line_fraction=None) -> np.ndarray:
+        """uint8[n], what `select_docs_device` takes: 1 for the documents that pass every rule -- by default the thresholds of the Gopher
+        quality filter, in float64.  None switches a rule off; `min_punct_line_fraction` is C4's and FineWeb's line-punctuation rule."""
+        keep = np.ones(len(self.length), dtype=bool)
+        for limit, value, least in ((min_words, lambda: self.n_words, True), (max_words, lambda: self.n_words, False), (min_mean_word_length, self.mean_word_length, True),
+                                    (max_mean_word_length, self.mean_word_length, False), (max_hash_ratio, self.hash_ratio, False),
+                                    (max_ellipsis_ratio, self.ellipsis_ratio, False), (min_alpha_fraction, self.alpha_fraction, True),
+                                    (min_stop_words, self.n_stop_words, True), (min_punct_line_fraction, self.punct_line_fraction, True)):
+            if limit is not None:
+                v = value().astype(np.float64)
+                keep &= v >= float(limit) if least else v <= float(limit)
+        return keep.astype(np.uint8)
+
+
 class NativeNgramSet:
     """A tk_ngram_set; made by `CoreBPE.ngram_set_create`.  Keeps its core alive: the set must go first."""
 
@@ -2183,6 +2241,48 @@ class CoreBPE:
         out = tuple(np.zeros(n + 1, dtype=np.uint64)[:n] for _ in self.LINE_OUTS)  # (one spare element each: no empty array's pointer)
         _lib.raise_for(self._L.tk_line_stats(self._h, text.ctypes.data if len(text) else None, doc_off.ctypes.data, n, int(seed), *[a.ctypes.data for a in out]))
         return LineStats(np.diff(doc_off), *out)
+
+    # ------------------------------------------------------------------ word statistics (no reference counterpart: text.split() per document on the host)
+    WORD_OUTS = ("n_words", "word_chars", "n_alpha_words", "stop_mask", "n_hash", "n_ellipsis", "n_lines", "n_punct_lines")
+
+    @staticmethod
+    def _word_args(stop_words, terminal):
+        """stop words (str or bytes each) and terminal bytes (str or bytes) as the C ABI takes them; the arrays are kept alive by the caller"""
+        stops = [s.encode() if isinstance(s, str) else bytes(s) for s in stop_words]
+        term = np.frombuffer((terminal.encode() if isinstance(terminal, str) else bytes(terminal)) + b"\0", dtype=np.uint8)
+        blob = np.frombuffer(b"".join(stops) + b"\0", dtype=np.uint8)
+        off = np.zeros(len(stops) + 1, dtype=np.uint64)
+        np.cumsum([len(s) for s in stops], out=off[1:])
+        return blob, off, term, (blob.ctypes.data, off.ctypes.data, len(stops), term.ctypes.data, len(term) - 1)
+
+    def word_stats_device(self, text, doc_off, *, stop_words=GOPHER_STOP_WORDS, terminal=TERMINAL_PUNCTUATION, n_words=None, word_chars=None, n_alpha_words=None,
+                          stop_mask=None, n_hash=None, n_ellipsis=None, n_lines=None, n_punct_lines=None, stream: int | None = None) -> None:
+        """Word statistics of packed text that is on the device (tk_word_stats_device): torch tensors on this core's GPU, taken by pointer
+        -- `text` (8-bit, N) and `doc_off` (64-bit, n + 1, ascending from 0 to N; not checked) in; the caller's tensors out, 64-bit, n
+        each, any of which may be None.  Queued on `stream` as in `fingerprint_device`; the host waits for nothing."""
+        self._one_device("word_stats_device")
+        n, N = doc_off.numel() - 1, text.numel()
+        if n < 0:
+            raise ValueError("doc_off must hold n_docs + 1 entries")
+        outs = (n_words, word_chars, n_alpha_words, stop_mask, n_hash, n_ellipsis, n_lines, n_punct_lines)
+        stream = self._on_gpu((("text", text, 1, N), ("doc_off", doc_off, 8, n + 1), *[(m, o, 8, n) for m, o in zip(self.WORD_OUTS, outs)]), stream)
+        ptr = [t.data_ptr() if t is not None and t.numel() else None for t in outs]
+        *_keep, args = self._word_args(stop_words, terminal)
+        _lib.raise_for(self._L.tk_word_stats_device(self._h, text.data_ptr() if N else None, N, doc_off.data_ptr(), n, *args, stream or None, *ptr))
+
+    def word_stats_packed(self, text, doc_off: np.ndarray, stop_words=GOPHER_STOP_WORDS, terminal=TERMINAL_PUNCTUATION) -> WordStats:
+        """Word statistics of packed text (tk_word_stats): host arrays in -- `text` bytes or uint8[N] (no copy), `doc_off` uint64[n + 1] --,
+        a `WordStats` out."""
+        self._one_device("word_stats_packed")
+        text = self._jsonl_bytes(text)
+        doc_off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+        if doc_off.ndim != 1 or len(doc_off) < 1 or int(doc_off[-1]) != len(text):
+            raise ValueError("doc_off must hold n + 1 offsets that end at len(text)")
+        n = len(doc_off) - 1
+        out = tuple(np.zeros(n + 1, dtype=np.uint64)[:n] for _ in self.WORD_OUTS)  # (one spare element each: no empty array's pointer)
+        *_keep, args = self._word_args(stop_words, terminal)
+        _lib.raise_for(self._L.tk_word_stats(self._h, text.ctypes.data if len(text) else None, doc_off.ctypes.data, n, *args, *[a.ctypes.data for a in out]))
+        return WordStats(np.diff(doc_off), *out)
 
     # ------------------------------------------------------------------ line sets (no reference counterpart: a loop over lines against a set on the host)
     def line_set_create(self, capacity: int, seed: int = 0, min_bytes: int = 1) -> NativeLineSet:

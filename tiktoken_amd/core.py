@@ -475,6 +475,38 @@ class Encoding:
         self._core_bpe.line_stats_device(text, doc_off, seed=seed, **outs)
         return _tiktoken.LineStats(np.diff(doc_off.cpu().numpy().view(np.uint64)), *[outs[m].cpu().numpy().view(np.uint64) for m in _tiktoken.CoreBPE.LINE_OUTS])
 
+    # ------------------------------------------------------------------ word statistics
+    def word_stats_batch(self, texts: "Sequence[str] | Sequence[bytes]", stop_words=_tiktoken.GOPHER_STOP_WORDS,
+                         terminal=_tiktoken.TERMINAL_PUNCTUATION) -> "_tiktoken.WordStats":
+        """The word-level figures of the Gopher quality filter for every text of a batch, counted on the GPU from the text itself --
+        before any encode: per document its words (`str.split()`), the chars in them, the words with a letter, which of up to 32
+        `stop_words` of at most 8 bytes occur, its '#' and ellipses, its lines and the lines that end in a `terminal` byte.  `texts`: str,
+        packed as `encode_ordinary_batch_packed` packs them, or bytes.  Returns a `WordStats`, whose `keep_mask` says which documents
+        pass; with `line_stats_batch` and `repetition_batch` that is the whole filter.  The rule is stated in include/tiktoken_amd.h."""
+        if len(texts) and isinstance(texts[0], (bytes, bytearray, memoryview)):
+            off = np.zeros(len(texts) + 1, dtype=np.uint64)
+            np.cumsum([len(t) for t in texts], out=off[1:])
+            return self._core_bpe.word_stats_packed(b"".join(texts), off, stop_words, terminal)
+        blob, off = self._pack(texts)
+        return self._core_bpe.word_stats_packed(blob, off, stop_words, terminal)
+
+    def word_stats_packed(self, text, doc_off=None, stop_words=_tiktoken.GOPHER_STOP_WORDS, terminal=_tiktoken.TERMINAL_PUNCTUATION) -> "_tiktoken.WordStats":
+        """The word statistics of text that is packed already: everything `line_stats_packed` takes -- host buffers (no copy) with
+        `doc_off` uint64[n + 1], a `JsonlText`, or a uint8 torch tensor on the encoding's GPU with `doc_off` a 64-bit tensor there (by
+        pointer; the results come back to the host)."""
+        if isinstance(text, _tiktoken.JsonlText):
+            text, doc_off = text.text, text.doc_off
+        if not hasattr(text, "data_ptr"):
+            return self._core_bpe.word_stats_packed(text, doc_off, stop_words, terminal)
+        import torch
+
+        if not hasattr(doc_off, "data_ptr"):
+            doc_off = torch.from_numpy(np.ascontiguousarray(doc_off, dtype=np.uint64).view(np.int64)).to(text.device)
+        n = doc_off.numel() - 1
+        outs = {m: torch.zeros(max(n, 0), dtype=torch.int64, device=text.device) for m in _tiktoken.CoreBPE.WORD_OUTS}
+        self._core_bpe.word_stats_device(text, doc_off, stop_words=stop_words, terminal=terminal, **outs)
+        return _tiktoken.WordStats(np.diff(doc_off.cpu().numpy().view(np.uint64)), *[outs[m].cpu().numpy().view(np.uint64) for m in _tiktoken.CoreBPE.WORD_OUTS])
+
     # ------------------------------------------------------------------ line sets
     def line_set(self, capacity: int, seed: int = 0, min_bytes: int = 1) -> "LineSet":
         """An empty set of lines that lives on the GPU across calls (tk_line_set_create), and with it the line filter of CCNet-, C4- and

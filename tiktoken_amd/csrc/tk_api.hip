@@ -36,6 +36,7 @@
 #include "tk_repeat.h"
 #include "tk_lines.h"
 #include "tk_line_set.h"
+#include "tk_words.h"
 #include "tk_jsonl.h"
 #include "tk_sample_rows.h"
 #include "tk_samples.h"
@@ -320,6 +321,13 @@ struct tk_core {
     // host entry.  ln_done: as fp_done, for all four.
     Buf d_ln_work, d_ln_tab, d_ln_in, d_ln_out;
     Event ln_done;
+    // Word statistics (tk_words.h), apart from everything above: d_wd_work: the tiles' summaries and the documents' sums, cleared per
+    // call; d_wd_in, d_wd_out: text and doc_off, and the eight result arrays, of the host entry.  wd_done: as fp_done, for all three.
+    // wd_tab: the class tables its letters are read from -- the core's own, or t_wd_*: the real ones where the core's split pattern runs
+    // through the generic engine and its own tables call every char a letter.
+    Buf d_wd_work, d_wd_in, d_wd_out, t_wd_stage1, t_wd_stage2, t_wd_bmp;
+    Event wd_done;
+    TkWdTab wd_tab{nullptr, nullptr, nullptr};
     uint64_t st_split[TK_SPLIT_STATS] = {0, 0, 0, 0};
     // Supervised samples (tk_samples.h), apart from everything above: d_smp: ids, labels and mask of every position; d_smp_row: full_len, len,
     // n_trained of every sample; d_smp_cnt: the TK_SMP_WORDS report words, the role table, pstart and the per-sample figures a call counts in
@@ -585,10 +593,10 @@ extern "C" int tk_create(const uint8_t* ranks_blob, const uint64_t* ranks_off, c
         return TK_OK;
     };
     // the class of every code point below U+10000 in one table (TkTables::uc_bmp), from the two stages
-    auto upload_bmp = [&](const uint8_t* s1, const uint8_t* s2) -> int {
+    auto upload_bmp = [&](Buf& to, const uint8_t* s1, const uint8_t* s2) -> int {
         std::vector<uint8_t> bmp(65536);
         for (uint32_t cp = 0; cp < 65536u; ++cp) bmp[cp] = s2[(uint32_t)s1[cp >> 8] * 256u + (cp & 255u)];
-        return upload(c->t_bmp, bmp.data(), bmp.size());
+        return upload(to, bmp.data(), bmp.size());
     };
     if (H.rx.empty()) {
         // a pattern of the scanner families: compiled for the generic engine as well, for stretches of text without certain starts
@@ -599,7 +607,7 @@ extern "C" int tk_create(const uint8_t* ranks_blob, const uint64_t* ranks_off, c
         }
         TRY(upload(c->t_stage1, tk_uc_stage1, sizeof tk_uc_stage1));
         TRY(upload(c->t_stage2, tk_uc_stage2, sizeof tk_uc_stage2));
-        TRY(upload_bmp(tk_uc_stage1, tk_uc_stage2));
+        TRY(upload_bmp(c->t_bmp, tk_uc_stage1, tk_uc_stage2));
         uint32_t bt[256 * 2];
         tk_build_byte_table(tk_uc_stage1, tk_uc_stage2, bt);
         TRY(upload(c->t_byte_tab, bt, sizeof bt));
@@ -609,13 +617,18 @@ extern "C" int tk_create(const uint8_t* ranks_blob, const uint64_t* ranks_off, c
         std::vector<uint8_t> s1(0x1100, 0), s2(256, (uint8_t)TK_C_LL);
         TRY(upload(c->t_stage1, s1.data(), s1.size()));
         TRY(upload(c->t_stage2, s2.data(), s2.size()));
-        TRY(upload_bmp(s1.data(), s2.data()));
+        TRY(upload_bmp(c->t_bmp, s1.data(), s2.data()));
         uint32_t bt[256 * 2];
         tk_build_byte_table(s1.data(), s2.data(), bt);
         TRY(upload(c->t_byte_tab, bt, sizeof bt));
         TRY(upload_rx(H.rx));
         c->has_rx = true;
+        TRY(upload(c->t_wd_stage1, tk_uc_stage1, sizeof tk_uc_stage1));  // (the word statistics' letters are Unicode's, whatever the pattern)
+        TRY(upload(c->t_wd_stage2, tk_uc_stage2, sizeof tk_uc_stage2));
+        TRY(upload_bmp(c->t_wd_bmp, tk_uc_stage1, tk_uc_stage2));
     }
+    c->wd_tab = H.rx.empty() ? TkWdTab{c->t_bmp.as<uint8_t>(), c->t_stage1.as<uint8_t>(), c->t_stage2.as<uint8_t>()}
+                             : TkWdTab{c->t_wd_bmp.as<uint8_t>(), c->t_wd_stage1.as<uint8_t>(), c->t_wd_stage2.as<uint8_t>()};
     TRY(upload(c->t_short, H.short_tab.data(), H.short_tab.size() * sizeof(TkShortSlot)));
     TRY(upload(c->t_mid, H.mid_tab.data(), H.mid_tab.size() * sizeof(TkPieceSlot)));
     TRY(upload(c->t_piece, H.piece.data(), H.piece.size() * sizeof(TkPieceSlot)));
@@ -4199,6 +4212,102 @@ extern "C" int tk_line_stats(tk_core* c, const uint8_t* text, const uint64_t* do
 }
 
 // ------------------------------------------------------------------------------------------
+// Word statistics (tk_words.h): packed text on the device -> per document its words, their chars, the words with a letter, its stop words,
+// '#' and ellipses, its lines and the punctuated ones.
+// ------------------------------------------------------------------------------------------
+struct WdOuts {  // the caller's arrays, uint64[n_docs] (device memory for wd_run, host memory for tk_word_stats); any may be null
+    uint64_t* a[TK_WD_SUMS];
+};
+// The arguments every entry refuses before anything is queued
+static int wd_shape(uint64_t n, uint64_t n_docs, const uint8_t* stop_bytes, const uint64_t* stop_off, uint64_t n_stop, const uint8_t* terminal, uint64_t n_terminal, TkWd* p) {
+    if ((n_stop && (!stop_bytes || !stop_off)) || (n_terminal && !terminal)) return fail(TK_VALUE_ERROR, "null argument");
+    switch (tk_wd_shape(n, n_docs, stop_bytes, stop_off, n_stop, terminal, n_terminal, p)) {
+        case 0: break;
+        case 1: return fail(TK_VALUE_ERROR, "n_bytes: the text of a word statistics call is at most 0xFFFF0000 bytes (positions are 32-bit)");
+        case 2: return fail(TK_VALUE_ERROR, "stop words: at most 32 (one bit of stop_mask each)");
+        case 3: return fail(TK_VALUE_ERROR, "stop words: a stop word has 1 to 8 bytes");
+        case 4: return fail(TK_VALUE_ERROR, "stop words: a stop word holds no white space");
+        case 5: return fail(TK_VALUE_ERROR, "stop words: a stop word is repeated");
+        case 6: return fail(TK_VALUE_ERROR, "terminal: at most 16 bytes");
+        default: return fail(TK_VALUE_ERROR, "terminal: the bytes are ASCII, below 0x80");
+    }
+    if (n_docs > 0xFFFFFFFEull) return fail(TK_VALUE_ERROR, "n_docs: at most 2^32 - 2 documents");
+    return TK_OK;
+}
+// wd_run: the caller holds c->mu.  Launches on s and waits for nothing.
+static int wd_run(tk_core* c, hipStream_t s, const TkWd& p, const uint8_t* d_text, const uint64_t* d_doc_off, WdOuts o) {
+    if (!c->wd_done.e) HIPCHK(c->wd_done.create());
+    HIPCHK(hipStreamWaitEvent(s, c->wd_done, 0));  // (the scratch and the host entry's buffers are the core's)
+    const uint64_t nt = p.n_tiles, n_sums = (uint64_t)TK_WD_SUMS * p.n_docs;
+    Carve work;
+    const uint64_t at_tiles = work.add(nt * sizeof(TkWdRun)), at_sums = work.add(n_sums * 8);
+    TRY(ensure(c->d_wd_work, work.total + 16));
+    TkWdRun* tiles = carved<TkWdRun>(c->d_wd_work, at_tiles);
+    unsigned long long* sums = carved<unsigned long long>(c->d_wd_work, at_sums);
+    const bool aligned = ((uintptr_t)d_text & 15u) == 0;
+    const dim3 grid((uint32_t)nt), block(TK_WD_THREADS);
+    if (n_sums) TRY(timed(c, s, "tk_k_wd_clear", [&] { hipLaunchKernelGGL(tk_k_wd_clear, dim3(grid_for(n_sums, 256, 65536)), dim3(256), 0, s, sums, n_sums); }));
+    TRY(timed(c, s, "tk_k_wd_sum", [&] { hipLaunchKernelGGL(tk_k_wd_sum, grid, block, 0, s, p, c->wd_tab, d_text, d_doc_off, aligned, tiles); }));
+    TRY(timed(c, s, "tk_k_wd_carry", [&] { hipLaunchKernelGGL(tk_k_wd_carry, dim3(1), dim3(1024), 0, s, p.n_tiles, tiles); }));
+    TRY(timed(c, s, "tk_k_wd_count", [&] { hipLaunchKernelGGL(tk_k_wd_count, grid, block, 0, s, p, c->wd_tab, d_text, d_doc_off, aligned, tiles, sums); }));
+    const TkWdOut out{(unsigned long long*)o.a[0], (unsigned long long*)o.a[1], (unsigned long long*)o.a[2], (unsigned long long*)o.a[3],
+                      (unsigned long long*)o.a[4], (unsigned long long*)o.a[5], (unsigned long long*)o.a[6], (unsigned long long*)o.a[7]};
+    if (p.n_docs) TRY(timed(c, s, "tk_k_wd_final", [&] { hipLaunchKernelGGL(tk_k_wd_final, dim3(grid_for(p.n_docs, 256, 65536)), dim3(256), 0, s, p.n_docs, sums, out); }));
+    HIPCHK(hipEventRecord(c->wd_done, s));
+    return TK_OK;
+}
+
+extern "C" int tk_word_stats_device(tk_core* c, const void* d_text, uint64_t n_bytes, const void* d_doc_off, uint64_t n_docs, const uint8_t* stop_bytes, const uint64_t* stop_off,
+                                    uint64_t n_stop, const uint8_t* terminal, uint64_t n_terminal, void* stream, uint64_t* d_n_words, uint64_t* d_word_chars,
+                                    uint64_t* d_n_alpha_words, uint64_t* d_stop_mask, uint64_t* d_n_hash, uint64_t* d_n_ellipsis, uint64_t* d_n_lines, uint64_t* d_n_punct_lines) {
+    // (the stream as given, null being HIP's null stream and not the core's, which is what device_pass would hand over:
+    // tk_fingerprint_device's convention)
+    return device_pass(c, d_doc_off && (d_text || !n_bytes), stream, [&](hipStream_t /*the core's for null*/) {
+        TkWd p;
+        TRY(wd_shape(n_bytes, n_docs, stop_bytes, stop_off, n_stop, terminal, n_terminal, &p));
+        return wd_run(c, (hipStream_t)stream, p, (const uint8_t*)d_text, (const uint64_t*)d_doc_off,
+                      WdOuts{{d_n_words, d_word_chars, d_n_alpha_words, d_stop_mask, d_n_hash, d_n_ellipsis, d_n_lines, d_n_punct_lines}});
+    });
+}
+
+extern "C" int tk_word_stats(tk_core* c, const uint8_t* text, const uint64_t* doc_off, uint64_t n_docs, const uint8_t* stop_bytes, const uint64_t* stop_off, uint64_t n_stop,
+                             const uint8_t* terminal, uint64_t n_terminal, uint64_t* n_words_out, uint64_t* word_chars_out, uint64_t* n_alpha_words_out, uint64_t* stop_mask_out,
+                             uint64_t* n_hash_out, uint64_t* n_ellipsis_out, uint64_t* n_lines_out, uint64_t* n_punct_lines_out) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if (!doc_off) return fail(TK_VALUE_ERROR, "null argument");
+    TRY(check_offsets(doc_off, n_docs, "doc_off"));
+    const uint64_t n = doc_off[n_docs];
+    if (n && !text) return fail(TK_VALUE_ERROR, "null argument");
+    TkWd p;
+    TRY(wd_shape(n, n_docs, stop_bytes, stop_off, n_stop, terminal, n_terminal, &p));
+    uint64_t* const hp[TK_WD_SUMS] = {n_words_out, word_chars_out, n_alpha_words_out, stop_mask_out, n_hash_out, n_ellipsis_out, n_lines_out, n_punct_lines_out};
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->wd_done.e) HIPCHK(c->wd_done.create());
+    Carve in, res;
+    const uint64_t at_off = in.add((n_docs + 1) * 8), at_text = in.add(n + 16);
+    uint64_t at[TK_WD_SUMS];
+    for (uint64_t& a : at) a = res.add(n_docs * 8);
+    TRY(ensure(c->d_wd_in, in.total + 16));
+    TRY(ensure(c->d_wd_out, res.total + 16));
+    uint64_t* d_off = carved<uint64_t>(c->d_wd_in, at_off);
+    uint8_t* d_text = carved<uint8_t>(c->d_wd_in, at_text);
+    WdOuts d;
+    for (uint32_t i = 0; i < TK_WD_SUMS; ++i) d.a[i] = hp[i] ? carved<uint64_t>(c->d_wd_out, at[i]) : nullptr;
+    HIPCHK(hipStreamWaitEvent(c->stream, c->wd_done, 0));  // (d_wd_in may still be read by a call on another stream)
+    HIPCHK(hipMemcpyAsync(d_off, doc_off, (n_docs + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    if (n) HIPCHK(hipMemcpyAsync(d_text, text, n, hipMemcpyHostToDevice, c->stream));
+    return drained(c, [&]() -> int {
+        TRY(wd_run(c, c->stream, p, d_text, d_off, d));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipGetLastError());
+        for (uint32_t i = 0; i < TK_WD_SUMS; ++i)
+            if (hp[i] && n_docs) HIPCHK(hipMemcpy(hp[i], d.a[i], n_docs * 8, hipMemcpyDeviceToHost));
+        return TK_OK;
+    });
+}
+
+// ------------------------------------------------------------------------------------------
 // Line sets (tk_line_set.h): a set of line keys on the device, and packed text rewritten without the lines the set has seen.  Like a
 // tk_ngram_set the set owns what outlives a batch -- the table, the counter -- and what its calls work in: the tiles' scratch, the bitmap,
 // the buffers of the host entries, and the event that orders its calls among themselves on the device.
@@ -6300,6 +6409,10 @@ extern "C" uint64_t tk_stat(tk_core* c, const char* name) {
     if (k == "lines_lane") return TK_LN_LANE;  // ... of a lane
     if (k == "lines_wave") return TK_LN_WAVE;  // ... of a wavefront
     if (k == "lines_docs") return TK_LN_DOCS;  // documents of a tile whose sums are gathered in LDS
+    if (k == "words_tile") return TK_WD_TILE;  // bytes of a tile of the word statistics pass (tk_words_rule.h)
+    if (k == "words_lane") return TK_WD_LANE;  // ... of a lane
+    if (k == "words_wave") return TK_WD_WAVE;  // ... of a wavefront
+    if (k == "words_docs") return TK_WD_DOCS;  // documents of a tile whose sums are gathered in LDS
     if (k == "ngram_tile") return TK_NG_TILE;  // token positions of a tile of the n-gram passes (tk_ngram_rule.h)
     if (k == "select_tile") return TK_SEL_TILE;  // output positions of a tile of the selection's copy (tk_groups_rule.h)
     if (k == "jsonl_tile") return TK_JSONL_TILE;  // bytes of a tile of the JSON Lines passes (tk_jsonl_rule.h)
