@@ -654,8 +654,8 @@ int tk_line_stats(tk_core* core, const uint8_t* text, const uint64_t* doc_off, u
  *  longer than 8 bytes, repeated, or holds a white-space sequence; more than 16 terminal bytes; a terminal byte >= 0x80.
  * A workgroup takes tk_stat("words_tile") bytes, a lane tk_stat("words_lane"), a wavefront tk_stat("words_wave"); a word or a run of dots
  * of any length costs a scan over the tiles it crosses, never a walk.  The core owns the scratch: 24 bytes per tile, 64 per document.
- * NOT built: case folding; word splitting by a tokenizer instead of white space; stop words above 8 bytes; short-line and per-line word
- * counts; several GPUs; buffers above 0xFFFF0000 bytes. */
+ * NOT built: case folding; word splitting by a tokenizer instead of white space; stop words above 8 bytes; several GPUs; buffers above
+ * 0xFFFF0000 bytes.  (Per-line word counts and short lines: tk_line_clean.) */
 /* Device pointers in (d_text uint8[n_bytes] at any alignment -- 16-byte aligned is the fast path --, d_doc_off uint64[n_docs + 1]); the
  * stop words and terminal bytes are host memory; the caller's device arrays out.  Everything is queued on `stream`, null being HIP's null
  * stream, and the host waits for NOTHING: as in tk_fingerprint_device, a d_doc_off that does not ascend from 0 to n_bytes gives values
@@ -667,6 +667,76 @@ int tk_word_stats_device(tk_core* core, const void* d_text, uint64_t n_bytes, co
 int tk_word_stats(tk_core* core, const uint8_t* text, const uint64_t* doc_off, uint64_t n_docs, const uint8_t* stop_bytes, const uint64_t* stop_off, uint64_t n_stop,
                   const uint8_t* terminal, uint64_t n_terminal, uint64_t* n_words_out, uint64_t* word_chars_out, uint64_t* n_alpha_words_out, uint64_t* stop_mask_out,
                   uint64_t* n_hash_out, uint64_t* n_ellipsis_out, uint64_t* n_lines_out, uint64_t* n_punct_lines_out);
+/* Line cleaning: packed TEXT rewritten without the lines that fail C4's line rules and without the documents that hold a blocked
+ * phrase -- clean_page of C4 (Raffel et al. 2020, 2.2) and DataTrove's C4QualityFilter, which FineWeb runs with three words: a line goes
+ * when it does not end in terminal punctuation, ends in an ellipsis, has too few words, holds a word that is too long or says
+ * "javascript" or "privacy policy"; a page goes when it says "lorem ipsum" or holds a '{'.  Replaces nothing in the reference: it is the
+ * host step of the reference's users, for line in text.split("\n").  The output is packed text again, what every encode entry takes.
+ * The rule.  Input: text uint8[N], doc_off uint64[n_docs + 1] ascending from 0 to N, N <= 0xFFFF0000.  Bytes are bytes, and nothing
+ *  below crosses a document.
+ *  Lines and pieces.  The line sets' pieces, re.finditer(rb"[^\n]+\n?|\n", doc): a line with the one '\n' that follows it, or a bare '\n'.
+ *  Words.  tk_word_stats' words: maximal runs between the byte sequences of the 29 chars of str.isspace(), a sequence counting where
+ *   it lies wholly inside the document.  '\n' is white space, so every word lies in one line.  words(line): the words in it;
+ *   longest(line): the most chars in one of them, a char being a byte that is not 0b10xxxxxx; 0 without a word.
+ *   A word is its bytes: in ill-formed text one of 0b10xxxxxx bytes alone is a word of no char, and counts.
+ *  End.  Blank bytes are 0x20, 0x09, 0x0D.  The line's END is the line up to and including its last byte that is not blank; it is
+ *   empty when the line is all blanks.
+ *  Fold.  Bytes 0x41 .. 0x5A map to + 0x20, every other byte to itself.
+ *  Phrases.  Two lists, line phrases and document phrases: at most 16 byte strings each, of 1 .. 32 bytes; bytes with uint64 offsets
+ *   ascending from 0, as the stop words of tk_word_stats.  Line phrases hold no '\n'.  Phrase p OCCURS AT i when fold(text[i + j]) ==
+ *   fold(p[j]) for all j and [i, i + len(p)) lies inside one document.
+ *  Line rules, each judged on its own:
+ *   SHORT     min_words > 0 and words < min_words;
+ *   LONG      max_word_chars > 0 and longest > max_word_chars;
+ *   NO_END    there are terminal bytes (at most 16, ASCII) and the end is empty or its last byte is none of them;
+ *   ELLIPSIS  TK_CLEAN_ELLIPSIS is set and the end ends with "..." or E2 80 A6;
+ *   PHRASE    a line phrase occurs at a position of the line.
+ *   A line is DROPPED when any rule holds.
+ *  Document rule.  A document at some position of which a document phrase occurs is dropped whole: every piece of it, bare '\n' too.
+ *  Outputs.  text_out: the pieces of the kept lines and the bare '\n' pieces of the documents that are not dropped, in order;
+ *   doc_off_out uint64[n_docs + 1]: every document keeps its index and may become empty; per document, uint64[n_docs] each, any may be
+ *   null: n_lines; n_kept, the lines no rule holds for, 0 in a dropped document; n_short, n_long, n_no_end, n_ellipsis, n_phrase, the
+ *   lines each rule holds for, counted in dropped documents as well; doc_hit, bit i: document phrase i occurs; counts uint64[2] = (bytes
+ *   kept, lines not written).  With text_out null the call only counts: the keep, scan and write passes are not launched, doc_off_out is
+ *   left alone and counts is (0, lines that would not be written).
+ *  Every value is a function of (text, doc_off, spec) alone, never of the schedule: sums, maxima and ORs commute.
+ *  Refused with TK_VALUE_ERROR before anything is written: N above 0xFFFF0000; more than 16 phrases in a list; a phrase that is empty
+ *  or longer than 32 bytes; a line phrase with '\n'; more than 16 terminal bytes, or one >= 0x80; text_out == text; in the host entry a
+ *  doc_off that does not ascend from 0.
+ * A workgroup takes tk_stat("clean_tile") bytes, a lane tk_stat("clean_lane"), a wavefront tk_stat("clean_wave"); a line or a word of
+ * any length costs a scan over the tiles it crosses, never a walk.  The core owns the scratch: 32 bytes per tile, 64 per document, and
+ * with text out a bit per byte.
+ * NOT built: C4's sentence count per page and its citation removal; trimming of the kept lines' own bytes; Unicode case folding; phrases
+ * above 32 bytes; several GPUs. */
+#define TK_CLEAN_ELLIPSIS 1u
+typedef struct tk_clean_spec {
+    uint64_t min_words, max_word_chars; /* 0: the rule is off */
+    uint32_t flags;                     /* TK_CLEAN_ELLIPSIS */
+    const uint8_t* terminal;            /* n_terminal bytes; none: NO_END is off */
+    uint64_t n_terminal;
+    const uint8_t* line_bytes; /* the line phrases, line_off uint64[n_line + 1] */
+    const uint64_t* line_off;
+    uint64_t n_line;
+    const uint8_t* doc_bytes; /* the document phrases, doc_off uint64[n_doc + 1] */
+    const uint64_t* doc_off;
+    uint64_t n_doc;
+} tk_clean_spec;
+/* Device pointers in (d_text uint8[n_bytes] at any alignment -- 16-byte aligned is the fast path --, d_doc_off uint64[n_docs + 1]); the
+ * spec is host memory and is read before the call returns; the caller's device arrays out: d_text_out uint8[n_bytes] (at any alignment;
+ * only the first counts[0] bytes are written), d_doc_off_out uint64[n_docs + 1], the eight per-document arrays and d_counts_out uint64[2],
+ * any of which may be null (d_doc_off_out not with d_text_out).  Everything is queued on `stream`, null being HIP's null stream, and the
+ * host waits for NOTHING.  A d_doc_off that does not ascend from 0 to n_bytes gives values nobody has defined and never an access outside
+ * the arrays: the write pass takes from doc_off only indices i <= n_docs found by binary search and tile positions it checks against the
+ * tile, and what it stores to d_text_out lies at a prefix sum of the counts of bytes below n_bytes, so below n_bytes. */
+int tk_line_clean_device(tk_core* core, const void* d_text, uint64_t n_bytes, const void* d_doc_off, uint64_t n_docs, const tk_clean_spec* spec, void* stream,
+                         void* d_text_out, uint64_t* d_doc_off_out, uint64_t* d_n_lines, uint64_t* d_n_kept, uint64_t* d_n_short, uint64_t* d_n_long, uint64_t* d_n_no_end,
+                         uint64_t* d_n_ellipsis, uint64_t* d_n_phrase, uint64_t* d_doc_hit, uint64_t* d_counts_out);
+/* The same from host arrays (n_bytes is doc_off[n_docs]): *text_out is library-owned (tk_free), *n_bytes_out bytes; doc_off_out
+ * (n_docs + 1), the eight arrays (n_docs) and counts_out (2) are the caller's and may be null; text_out null: the call only counts.  One
+ * wait, for the counts; then only the kept bytes are copied. */
+int tk_line_clean(tk_core* core, const uint8_t* text, const uint64_t* doc_off, uint64_t n_docs, const tk_clean_spec* spec, uint8_t** text_out, uint64_t* n_bytes_out,
+                  uint64_t* doc_off_out, uint64_t* n_lines_out, uint64_t* n_kept_out, uint64_t* n_short_out, uint64_t* n_long_out, uint64_t* n_no_end_out,
+                  uint64_t* n_ellipsis_out, uint64_t* n_phrase_out, uint64_t* doc_hit_out, uint64_t* counts_out);
 /* Line sets: a set of line keys that lives on the device across calls, and packed TEXT rewritten without the lines the set has seen
  * -- navigation bars, cookie banners, licence footers: the line filter of CCNet, C4 and RefinedWeb-style builds, which drops every line
  * that occurred anywhere earlier in the corpus.  Replaces nothing in the reference: it is the host step of the reference's users, a loop
@@ -1182,7 +1252,8 @@ void tk_last_stats(tk_core* core, uint64_t* n_bytes, uint64_t* n_pieces, uint64_
  * n-gram passes (likewise); "repeat_tile" and "repeat_lds_tokens": of the repetition pass, the positions of a tile of its LDS class and
  * the longest document that class takes (likewise); "lines_tile", "lines_lane", "lines_wave" and "lines_docs": of the line statistics
  * pass, the bytes of a tile, of a lane and of a wavefront, and the documents of a tile whose sums are gathered in LDS (likewise); "words_tile",
- * "words_lane", "words_wave" and "words_docs": the same of the word statistics pass. */
+ * "words_lane", "words_wave" and "words_docs": the same of the word statistics pass; "clean_tile", "clean_lane", "clean_wave" and
+ * "clean_docs": of the line cleaning pass. */
 uint64_t tk_stat(tk_core* core, const char* name);
 
 #ifdef __cplusplus

@@ -91,6 +91,16 @@ U8_BYTES = 2  # TK_U8_BYTES (the stop-string entries over id matrices: no repair
 STOPS_KEEP = 1  # TK_STOPS_KEEP
 
 
+class CleanSpec(ctypes.Structure):
+    """tk_clean_spec: the line rules and the two phrase lists of a line cleaning call (include/tiktoken_amd.h)."""
+    _fields_ = [("min_words", ctypes.c_uint64), ("max_word_chars", ctypes.c_uint64), ("flags", ctypes.c_uint32), ("terminal", ctypes.c_void_p), ("n_terminal", ctypes.c_uint64),
+                ("line_bytes", ctypes.c_void_p), ("line_off", ctypes.c_void_p), ("n_line", ctypes.c_uint64), ("doc_bytes", ctypes.c_void_p), ("doc_off", ctypes.c_void_p),
+                ("n_doc", ctypes.c_uint64)]
+
+
+CLEAN_ELLIPSIS = 1  # TK_CLEAN_ELLIPSIS
+
+
 class Stops(ctypes.Structure):  # tk_stops
     _fields_ = [("n", ctypes.c_uint32), ("blob", ctypes.c_void_p), ("off", ctypes.c_void_p)]
 
@@ -221,6 +231,11 @@ def lib() -> ctypes.CDLL:
             L.tk_word_stats_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, vp, u64, vp, *[vp] * 8]
             L.tk_word_stats.restype = i32
             L.tk_word_stats.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, u64, *[vp] * 8]
+        if hasattr(L, "tk_line_clean_device"):  # (absent from older builds selected through $TIKTOKEN_AMD_LIB)
+            L.tk_line_clean_device.restype = i32
+            L.tk_line_clean_device.argtypes = [vp, vp, u64, vp, u64, P(CleanSpec), vp, vp, vp, *[vp] * 8, vp]
+            L.tk_line_clean.restype = i32
+            L.tk_line_clean.argtypes = [vp, vp, vp, u64, P(CleanSpec), P(vp), P(u64), vp, *[vp] * 8, vp]
         if hasattr(L, "tk_line_set_create"):  # (absent from older builds selected through $TIKTOKEN_AMD_LIB)
             L.tk_line_set_create.restype = i32
             L.tk_line_set_create.argtypes = [vp, u64, u64, u64, P(vp)]

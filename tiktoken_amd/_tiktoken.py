@@ -939,6 +939,38 @@ class LineDedup(NamedTuple):
     n_dropped_total: int
 
 
+C4_LINE_PHRASES = ("javascript", "terms of use", "privacy policy", "cookie policy", "uses cookies", "use of cookies", "use cookies")
+C4_DOC_PHRASES = ("lorem ipsum", "{")
+C4_TERMINAL = ".!?\""
+
+
+class LineClean(NamedTuple):
+    """Packed text without the lines that fail C4's line rules and without the documents that hold a blocked phrase (tk_line_clean; the
+    rule: include/tiktoken_amd.h): `text` uint8[kept bytes] and `doc_off` uint64[n + 1], what every packed encode entry takes -- every
+    input document keeps its index and may be empty --, and uint64[n] per document: `n_lines`, `n_kept` (the lines no rule holds for; 0
+    in a dropped document), `n_short`, `n_long`, `n_no_end`, `n_ellipsis`, `n_phrase` (the lines each rule holds for) and `doc_hit` (bit
+    i: document phrase i occurs)."""
+    text: np.ndarray
+    doc_off: np.ndarray
+    n_lines: np.ndarray
+    n_kept: np.ndarray
+    n_short: np.ndarray
+    n_long: np.ndarray
+    n_no_end: np.ndarray
+    n_ellipsis: np.ndarray
+    n_phrase: np.ndarray
+    doc_hit: np.ndarray
+
+    def keep_mask(self, min_lines: int = 1) -> np.ndarray:
+        """uint8[n], what `select_docs_device` takes: 1 for the documents that keep at least `min_lines` lines (a dropped document keeps none)"""
+        return (self.n_kept >= max(int(min_lines), 0)).astype(np.uint8) & (self.doc_hit == 0).astype(np.uint8)
+
+    def texts(self) -> "list[bytes]":
+        """the cleaned documents as bytes, every one in its place"""
+        view, bounds = memoryview(self.text), self.doc_off.tolist()
+        return [bytes(view[a:b]) for a, b in zip(bounds[:-1], bounds[1:])]
+
+
 class NativeLineSet:
     """A tk_line_set; made by `CoreBPE.line_set_create`.  Keeps its core alive: the set must go first."""
 
@@ -2283,6 +2315,59 @@ class CoreBPE:
         *_keep, args = self._word_args(stop_words, terminal)
         _lib.raise_for(self._L.tk_word_stats(self._h, text.ctypes.data if len(text) else None, doc_off.ctypes.data, n, *args, *[a.ctypes.data for a in out]))
         return WordStats(np.diff(doc_off), *out)
+
+    # ------------------------------------------------------------------ line cleaning (no reference counterpart: for line in text.split("\n") on the host)
+    CLEAN_OUTS = ("n_lines", "n_kept", "n_short", "n_long", "n_no_end", "n_ellipsis", "n_phrase", "doc_hit")
+
+    @staticmethod
+    def _clean_spec(min_words, max_word_chars, terminal, drop_ellipsis, line_phrases, doc_phrases):
+        """(what keeps the arrays alive, the tk_clean_spec) of the rules as Python gives them: phrases str or bytes each, terminal str or bytes"""
+        keep = [np.frombuffer((terminal.encode() if isinstance(terminal, str) else bytes(terminal)) + b"\0", dtype=np.uint8)]
+        spec = _lib.CleanSpec(min_words=int(min_words), max_word_chars=int(max_word_chars), flags=_lib.CLEAN_ELLIPSIS if drop_ellipsis else 0,
+                              terminal=keep[0].ctypes.data, n_terminal=len(keep[0]) - 1)
+        for which, phrases in (("line", line_phrases), ("doc", doc_phrases)):
+            ph = [p.encode() if isinstance(p, str) else bytes(p) for p in phrases]
+            blob = np.frombuffer(b"".join(ph) + b"\0", dtype=np.uint8)
+            off = np.zeros(len(ph) + 1, dtype=np.uint64)
+            np.cumsum([len(p) for p in ph], out=off[1:])
+            keep += [blob, off]
+            setattr(spec, which + "_bytes", blob.ctypes.data), setattr(spec, which + "_off", off.ctypes.data), setattr(spec, "n_" + which, len(ph))
+        return keep, spec
+
+    def line_clean_device(self, text, doc_off, *, min_words: int = 5, max_word_chars: int = 1000, terminal=C4_TERMINAL, drop_ellipsis: bool = True,
+                          line_phrases=C4_LINE_PHRASES, doc_phrases=C4_DOC_PHRASES, text_out=None, doc_off_out=None, n_lines=None, n_kept=None, n_short=None,
+                          n_long=None, n_no_end=None, n_ellipsis=None, n_phrase=None, doc_hit=None, counts=None, stream: int | None = None) -> None:
+        """Packed text that is on the device without the lines that fail the line rules and without the documents that hold a document
+        phrase (tk_line_clean_device): torch tensors on this core's GPU, taken by pointer -- `text` (8-bit, N) and `doc_off` (64-bit,
+        n + 1, ascending from 0 to N; not checked) in; the caller's tensors out, any of which may be None: `text_out` (8-bit, N: its
+        first counts[0] bytes are written) with `doc_off_out` (64-bit, n + 1), the eight per-document tensors (64-bit, n) and `counts`
+        (64-bit, 2: bytes kept, lines not written).  Without `text_out` the call only counts.  The defaults are C4's; 0, an empty
+        `terminal`, False or an empty list switches a rule off.  Queued on `stream` as in `fingerprint_device`; the host waits for nothing."""
+        self._one_device("line_clean_device")
+        n, N = doc_off.numel() - 1, text.numel()
+        if n < 0:
+            raise ValueError("doc_off must hold n_docs + 1 entries")
+        outs = (n_lines, n_kept, n_short, n_long, n_no_end, n_ellipsis, n_phrase, doc_hit)
+        stream = self._on_gpu((("text", text, 1, N), ("doc_off", doc_off, 8, n + 1), ("text_out", text_out, 1, N), ("doc_off_out", doc_off_out, 8, n + 1),
+                               *[(m, o, 8, n) for m, o in zip(self.CLEAN_OUTS, outs)], ("counts", counts, 8, 2)), stream)
+        ptr = [t.data_ptr() if t is not None and t.numel() else None for t in (text_out, doc_off_out, *outs, counts)]
+        _keep, spec = self._clean_spec(min_words, max_word_chars, terminal, drop_ellipsis, line_phrases, doc_phrases)
+        _lib.raise_for(self._L.tk_line_clean_device(self._h, text.data_ptr() if N else None, N, doc_off.data_ptr(), n, ctypes.byref(spec), stream or None, *ptr))
+
+    def line_clean_packed(self, text, doc_off: np.ndarray, *, min_words: int = 5, max_word_chars: int = 1000, terminal=C4_TERMINAL, drop_ellipsis: bool = True,
+                          line_phrases=C4_LINE_PHRASES, doc_phrases=C4_DOC_PHRASES) -> LineClean:
+        """Packed text cleaned line by line (tk_line_clean): host arrays in -- `text` bytes or uint8[N] (no copy), `doc_off` uint64[n + 1]
+        --, a `LineClean` out.  The rules as in `line_clean_device`."""
+        self._one_device("line_clean_packed")
+        text, doc_off = self._packed_text(text, doc_off)
+        n = len(doc_off) - 1
+        off_out = np.zeros(n + 1, dtype=np.uint64)
+        per_doc = tuple(np.zeros(n + 1, dtype=np.uint64)[:n] for _ in self.CLEAN_OUTS)  # (one spare element each: no empty array's pointer)
+        out, n_out = ctypes.c_void_p(), ctypes.c_uint64()
+        _keep, spec = self._clean_spec(min_words, max_word_chars, terminal, drop_ellipsis, line_phrases, doc_phrases)
+        _lib.raise_for(self._L.tk_line_clean(self._h, text.ctypes.data if len(text) else None, doc_off.ctypes.data, n, ctypes.byref(spec), ctypes.byref(out),
+                                             ctypes.byref(n_out), off_out.ctypes.data, *[a.ctypes.data for a in per_doc], None))
+        return LineClean(_take_u8(out, int(n_out.value)), off_out, *per_doc)
 
     # ------------------------------------------------------------------ line sets (no reference counterpart: a loop over lines against a set on the host)
     def line_set_create(self, capacity: int, seed: int = 0, min_bytes: int = 1) -> NativeLineSet:

@@ -507,6 +507,41 @@ class Encoding:
         self._core_bpe.word_stats_device(text, doc_off, stop_words=stop_words, terminal=terminal, **outs)
         return _tiktoken.WordStats(np.diff(doc_off.cpu().numpy().view(np.uint64)), *[outs[m].cpu().numpy().view(np.uint64) for m in _tiktoken.CoreBPE.WORD_OUTS])
 
+    # ------------------------------------------------------------------ line cleaning
+    def clean_lines_batch(self, texts: "Sequence[str] | Sequence[bytes]", **rules) -> "list[str] | list[bytes]":
+        """C4's line cleaning for every text of a batch, on the GPU from the text itself: a list of the same length and type, every
+        document in its place, without the lines that have fewer than `min_words` words (5; FineWeb: 3), hold a word of more than
+        `max_word_chars` chars (1000), do not end -- trailing blanks apart -- in one of the `terminal` bytes, end in an ellipsis
+        (`drop_ellipsis`) or say one of the `line_phrases`; a document that says one of the `doc_phrases` ("lorem ipsum", "{") comes back
+        empty.  Phrases are compared with A-Z folded.  `clean_lines_packed` also gives the counts.  The rule is stated in
+        include/tiktoken_amd.h."""
+        if len(texts) and isinstance(texts[0], (bytes, bytearray, memoryview)):
+            off = np.zeros(len(texts) + 1, dtype=np.uint64)
+            np.cumsum([len(t) for t in texts], out=off[1:])
+            return self._core_bpe.line_clean_packed(b"".join(texts), off, **rules).texts()
+        blob, off = self._pack(texts)
+        return [d.decode("utf-8", errors="replace") for d in self._core_bpe.line_clean_packed(blob, off, **rules).texts()]
+
+    def clean_lines_packed(self, text, doc_off=None, **rules) -> "_tiktoken.LineClean":
+        """The line cleaning of text that is packed already, as a `LineClean`, whose (text, doc_off) every packed encode entry takes and
+        whose `keep_mask` is what `select_docs_device` takes: everything `word_stats_packed` takes -- host buffers (no copy) with
+        `doc_off` uint64[n + 1], a `JsonlText`, or a uint8 torch tensor on the encoding's GPU with `doc_off` a 64-bit tensor there (by
+        pointer; the results come back to the host).  `rules` as in `clean_lines_batch`."""
+        if isinstance(text, _tiktoken.JsonlText):
+            text, doc_off = text.text, text.doc_off
+        if not hasattr(text, "data_ptr"):
+            return self._core_bpe.line_clean_packed(text, doc_off, **rules)
+        import torch
+
+        if not hasattr(doc_off, "data_ptr"):
+            doc_off = torch.from_numpy(np.ascontiguousarray(doc_off, dtype=np.uint64).view(np.int64)).to(text.device)
+        n = max(doc_off.numel() - 1, 0)
+        new = lambda count, dtype=torch.int64: torch.zeros(count, dtype=dtype, device=text.device)  # noqa: E731
+        out = dict(text_out=new(text.numel(), torch.uint8), doc_off_out=new(n + 1), counts=new(2), **{m: new(n) for m in _tiktoken.CoreBPE.CLEAN_OUTS})
+        self._core_bpe.line_clean_device(text, doc_off, **rules, **out)
+        host = {k: v.cpu().numpy().view(np.uint8 if k == "text_out" else np.uint64) for k, v in out.items()}
+        return _tiktoken.LineClean(host["text_out"][:int(host["counts"][0])], host["doc_off_out"], *[host[m] for m in _tiktoken.CoreBPE.CLEAN_OUTS])
+
     # ------------------------------------------------------------------ line sets
     def line_set(self, capacity: int, seed: int = 0, min_bytes: int = 1) -> "LineSet":
         """An empty set of lines that lives on the GPU across calls (tk_line_set_create), and with it the line filter of CCNet-, C4- and

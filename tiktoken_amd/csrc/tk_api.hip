@@ -37,6 +37,7 @@
 #include "tk_lines.h"
 #include "tk_line_set.h"
 #include "tk_words.h"
+#include "tk_clean.h"
 #include "tk_jsonl.h"
 #include "tk_sample_rows.h"
 #include "tk_samples.h"
@@ -328,6 +329,11 @@ struct tk_core {
     Buf d_wd_work, d_wd_in, d_wd_out, t_wd_stage1, t_wd_stage2, t_wd_bmp;
     Event wd_done;
     TkWdTab wd_tab{nullptr, nullptr, nullptr};
+    // Line cleaning (tk_clean.h), apart from everything above: d_cl_work: the report word, the tiles' elements and kept bytes, the
+    // documents' sums and the drop bitmap, cleared per call; d_cl_in, d_cl_out: text and doc_off, and everything that comes back, of the
+    // host entry.  cl_done: as fp_done, for all three.
+    Buf d_cl_work, d_cl_in, d_cl_out;
+    Event cl_done;
     uint64_t st_split[TK_SPLIT_STATS] = {0, 0, 0, 0};
     // Supervised samples (tk_samples.h), apart from everything above: d_smp: ids, labels and mask of every position; d_smp_row: full_len, len,
     // n_trained of every sample; d_smp_cnt: the TK_SMP_WORDS report words, the role table, pstart and the per-sample figures a call counts in
@@ -4308,6 +4314,136 @@ extern "C" int tk_word_stats(tk_core* c, const uint8_t* text, const uint64_t* do
 }
 
 // ------------------------------------------------------------------------------------------
+// Line cleaning (tk_clean.h): packed text on the device -> packed text without the lines that fail C4's line rules and without the
+// documents that hold a blocked phrase, and per document the lines each rule holds for.
+// ------------------------------------------------------------------------------------------
+static_assert(TK_CLEAN_ELLIPSIS == TK_CL_ELLIPSIS, "tk_clean_spec flags");
+struct ClOuts {  // the caller's device arrays; any may be null (text and doc_off: the call only counts)
+    uint8_t* text;
+    uint64_t* doc_off;
+    uint64_t* a[TK_CL_SUMS];  // n_lines, n_kept, n_short, n_long, n_no_end, n_ellipsis, n_phrase, doc_hit
+    uint64_t* counts;
+};
+// The arguments every entry refuses before anything is queued
+static int cl_shape(uint64_t n, uint64_t n_docs, const tk_clean_spec* sp, TkCl* p) {
+    if (!sp || (sp->n_terminal && !sp->terminal) || (sp->n_line && (!sp->line_bytes || !sp->line_off)) || (sp->n_doc && (!sp->doc_bytes || !sp->doc_off)))
+        return fail(TK_VALUE_ERROR, "null argument");
+    switch (tk_cl_shape(n, n_docs, sp->min_words, sp->max_word_chars, sp->flags, sp->terminal, sp->n_terminal, sp->line_bytes, sp->line_off, sp->n_line, sp->doc_bytes,
+                        sp->doc_off, sp->n_doc, p)) {
+        case 0: break;
+        case 1: return fail(TK_VALUE_ERROR, "n_bytes: the text of a line cleaning call is at most 0xFFFF0000 bytes (positions are 32-bit)");
+        case 2: return fail(TK_VALUE_ERROR, "phrases: at most 16 in a list (one bit of doc_hit each)");
+        case 3: return fail(TK_VALUE_ERROR, "phrases: a phrase has 1 to 32 bytes");
+        case 4: return fail(TK_VALUE_ERROR, "phrases: a line phrase holds no newline");
+        case 5: return fail(TK_VALUE_ERROR, "terminal: at most 16 bytes");
+        default: return fail(TK_VALUE_ERROR, "terminal: the bytes are ASCII, below 0x80");
+    }
+    if (n_docs > 0xFFFFFFFEull) return fail(TK_VALUE_ERROR, "n_docs: at most 2^32 - 2 documents");
+    return TK_OK;
+}
+// cl_run: the caller holds c->mu.  Launches on s and waits for nothing.
+static int cl_run(tk_core* c, hipStream_t s, const TkCl& q, const uint8_t* d_text, const uint64_t* d_doc_off, const ClOuts& o) {
+    if (q.n_bytes && o.text == d_text) return fail(TK_VALUE_ERROR, "d_text_out must not be d_text: a tile's kept bytes are written while later tiles are still read");
+    if (o.text && !o.doc_off) return fail(TK_VALUE_ERROR, "null argument");
+    const bool write = o.text || (!q.n_bytes && o.doc_off);
+    if (!c->cl_done.e) HIPCHK(c->cl_done.create());
+    HIPCHK(hipStreamWaitEvent(s, c->cl_done, 0));  // (the scratch and the host entry's buffers are the core's)
+    const uint64_t nt = q.n_tiles, n_sums = (uint64_t)TK_CL_SUMS * q.n_docs, n_bits = write ? tk_ls_bitmap_words(q.n_bytes) : 0;
+    Carve work;  // (what is cleared lies together: the report word, the sums, the bitmap)
+    const uint64_t at_words = work.add(16), at_sums = work.add(n_sums * 8), at_bits = work.add(n_bits * 8), n_clear = work.total / 8;
+    const uint64_t at_tiles = work.add(nt * sizeof(TkClSt)), at_kept = work.add(nt * 4);
+    TRY(ensure(c->d_cl_work, work.total + 16));
+    unsigned long long* words = carved<unsigned long long>(c->d_cl_work, at_words);
+    unsigned long long* sums = carved<unsigned long long>(c->d_cl_work, at_sums);
+    uint32_t* bits = write ? carved<uint32_t>(c->d_cl_work, at_bits) : nullptr;
+    TkClSt* tiles = carved<TkClSt>(c->d_cl_work, at_tiles);
+    uint32_t* kept = carved<uint32_t>(c->d_cl_work, at_kept);
+    const unsigned long long* hit = q.n_doc && q.n_docs ? sums + (uint64_t)TK_CL_S_HIT * q.n_docs : nullptr;
+    const bool aligned = ((uintptr_t)d_text & 15u) == 0;
+    const dim3 grid((uint32_t)nt), block(TK_CL_THREADS);
+    TRY(timed(c, s, "tk_k_cl_clear", [&] { hipLaunchKernelGGL(tk_k_cl_clear, dim3(grid_for(n_clear, 256, 65536)), dim3(256), 0, s, words, n_clear); }));
+    TRY(timed(c, s, "tk_k_cl_sum", [&] { hipLaunchKernelGGL(tk_k_cl_sum, grid, block, 0, s, q, d_text, d_doc_off, aligned, tiles); }));
+    TRY(timed(c, s, "tk_k_cl_carry", [&] { hipLaunchKernelGGL(tk_k_cl_carry, dim3(1), dim3(1024), 0, s, q.n_tiles, tiles); }));
+    TRY(timed(c, s, "tk_k_cl_decide", [&] { hipLaunchKernelGGL(tk_k_cl_decide, grid, block, 0, s, q, d_text, d_doc_off, aligned, tiles, bits, sums); }));
+    const TkClOut out{(unsigned long long*)o.a[0], (unsigned long long*)o.a[1], (unsigned long long*)o.a[2], (unsigned long long*)o.a[3],
+                      (unsigned long long*)o.a[4], (unsigned long long*)o.a[5], (unsigned long long*)o.a[6], (unsigned long long*)o.a[7]};
+    if (q.n_docs) TRY(timed(c, s, "tk_k_cl_final", [&] { hipLaunchKernelGGL(tk_k_cl_final, dim3(grid_for(q.n_docs, 256, 65536)), dim3(256), 0, s, q.n_docs, sums, out, words); }));
+    if (write) {
+        TRY(timed(c, s, "tk_k_cl_keep", [&] { hipLaunchKernelGGL(tk_k_cl_keep, grid, block, 0, s, q, d_text, d_doc_off, aligned, tiles, bits, hit, kept); }));
+        TRY(timed(c, s, "tk_k_cl_scan", [&] { hipLaunchKernelGGL(tk_k_cl_scan, dim3(1), dim3(1024), 0, s, kept, nt); }));
+        TRY(timed(c, s, "tk_k_cl_write", [&] {
+            hipLaunchKernelGGL(tk_k_cl_write, grid, block, 0, s, q, d_text, d_doc_off, aligned, tiles, bits, hit, kept, words, o.text, (unsigned long long*)o.doc_off,
+                               (unsigned long long*)o.counts);
+        }));
+    } else if (o.counts) {
+        TRY(timed(c, s, "tk_k_cl_report", [&] { hipLaunchKernelGGL(tk_k_cl_report, dim3(1), dim3(1), 0, s, words, (unsigned long long*)o.counts); }));
+    }
+    HIPCHK(hipEventRecord(c->cl_done, s));
+    return TK_OK;
+}
+
+extern "C" int tk_line_clean_device(tk_core* c, const void* d_text, uint64_t n_bytes, const void* d_doc_off, uint64_t n_docs, const tk_clean_spec* spec, void* stream,
+                                    void* d_text_out, uint64_t* d_doc_off_out, uint64_t* d_n_lines, uint64_t* d_n_kept, uint64_t* d_n_short, uint64_t* d_n_long,
+                                    uint64_t* d_n_no_end, uint64_t* d_n_ellipsis, uint64_t* d_n_phrase, uint64_t* d_doc_hit, uint64_t* d_counts_out) {
+    // (the stream as given, null being HIP's null stream: tk_fingerprint_device's convention)
+    return device_pass(c, d_doc_off && (d_text || !n_bytes), stream, [&](hipStream_t) {
+        TkCl q;
+        TRY(cl_shape(n_bytes, n_docs, spec, &q));
+        return cl_run(c, (hipStream_t)stream, q, (const uint8_t*)d_text, (const uint64_t*)d_doc_off,
+                      ClOuts{(uint8_t*)d_text_out, d_doc_off_out, {d_n_lines, d_n_kept, d_n_short, d_n_long, d_n_no_end, d_n_ellipsis, d_n_phrase, d_doc_hit}, d_counts_out});
+    });
+}
+
+extern "C" int tk_line_clean(tk_core* c, const uint8_t* text, const uint64_t* doc_off, uint64_t n_docs, const tk_clean_spec* spec, uint8_t** text_out, uint64_t* n_bytes_out,
+                             uint64_t* doc_off_out, uint64_t* n_lines_out, uint64_t* n_kept_out, uint64_t* n_short_out, uint64_t* n_long_out, uint64_t* n_no_end_out,
+                             uint64_t* n_ellipsis_out, uint64_t* n_phrase_out, uint64_t* doc_hit_out, uint64_t* counts_out) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if (!doc_off || (text_out && (!n_bytes_out || !doc_off_out))) return fail(TK_VALUE_ERROR, "null argument");
+    TRY(check_offsets(doc_off, n_docs, "doc_off"));
+    const uint64_t n = doc_off[n_docs];
+    if (n && !text) return fail(TK_VALUE_ERROR, "null argument");
+    TkCl q;
+    TRY(cl_shape(n, n_docs, spec, &q));
+    uint64_t* const hp[TK_CL_SUMS] = {n_lines_out, n_kept_out, n_short_out, n_long_out, n_no_end_out, n_ellipsis_out, n_phrase_out, doc_hit_out};
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->cl_done.e) HIPCHK(c->cl_done.create());
+    Carve in, res;
+    const uint64_t at_off = in.add((n_docs + 1) * 8), at_text = in.add(n + 16);
+    const uint64_t at_counts = res.add(16), at_off_out = res.add((n_docs + 1) * 8), at_text_out = res.add(text_out ? n + 16 : 0);
+    uint64_t at[TK_CL_SUMS];
+    for (uint64_t& a : at) a = res.add(n_docs * 8);
+    TRY(ensure(c->d_cl_in, in.total + 16));
+    TRY(ensure(c->d_cl_out, res.total + 16));
+    uint64_t* d_off = carved<uint64_t>(c->d_cl_in, at_off);
+    uint8_t* d_text = carved<uint8_t>(c->d_cl_in, at_text);
+    ClOuts d{text_out ? carved<uint8_t>(c->d_cl_out, at_text_out) : nullptr, text_out ? carved<uint64_t>(c->d_cl_out, at_off_out) : nullptr, {}, carved<uint64_t>(c->d_cl_out, at_counts)};
+    for (uint32_t i = 0; i < TK_CL_SUMS; ++i) d.a[i] = hp[i] ? carved<uint64_t>(c->d_cl_out, at[i]) : nullptr;
+    HIPCHK(hipStreamWaitEvent(c->stream, c->cl_done, 0));  // (d_cl_in may still be read by a call on another stream)
+    HIPCHK(hipMemcpyAsync(d_off, doc_off, (n_docs + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    if (n) HIPCHK(hipMemcpyAsync(d_text, text, n, hipMemcpyHostToDevice, c->stream));
+    return drained(c, [&]() -> int {
+        TRY(cl_run(c, c->stream, q, d_text, d_off, d));
+        uint64_t counts[2];
+        HIPCHK(hipMemcpyAsync(counts, d.counts, 16, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));  // the one wait
+        HIPCHK(hipGetLastError());
+        if (counts[0] > n) return fail(TK_RUNTIME_ERROR, "internal error: a line cleaning call kept more bytes than it was given");
+        ResultBag bag;
+        if (text_out) {
+            TRY(bag.fetch(text_out, d.text, counts[0]));
+            HIPCHK(hipMemcpy(doc_off_out, d.doc_off, (n_docs + 1) * 8, hipMemcpyDeviceToHost));
+        }
+        for (uint32_t i = 0; i < TK_CL_SUMS; ++i)
+            if (hp[i] && n_docs) HIPCHK(hipMemcpy(hp[i], d.a[i], n_docs * 8, hipMemcpyDeviceToHost));
+        bag.give();
+        if (text_out) *n_bytes_out = counts[0];
+        if (counts_out) counts_out[0] = counts[0], counts_out[1] = counts[1];
+        return TK_OK;
+    });
+}
+
+// ------------------------------------------------------------------------------------------
 // Line sets (tk_line_set.h): a set of line keys on the device, and packed text rewritten without the lines the set has seen.  Like a
 // tk_ngram_set the set owns what outlives a batch -- the table, the counter -- and what its calls work in: the tiles' scratch, the bitmap,
 // the buffers of the host entries, and the event that orders its calls among themselves on the device.
@@ -6413,6 +6549,10 @@ extern "C" uint64_t tk_stat(tk_core* c, const char* name) {
     if (k == "words_lane") return TK_WD_LANE;  // ... of a lane
     if (k == "words_wave") return TK_WD_WAVE;  // ... of a wavefront
     if (k == "words_docs") return TK_WD_DOCS;  // documents of a tile whose sums are gathered in LDS
+    if (k == "clean_tile") return TK_CL_TILE;  // bytes of a tile of the line cleaning pass (tk_clean_rule.h)
+    if (k == "clean_lane") return TK_CL_LANE;  // ... of a lane
+    if (k == "clean_wave") return TK_CL_WAVE;  // ... of a wavefront
+    if (k == "clean_docs") return TK_CL_DOCS;  // documents of a tile whose sums are gathered in LDS
     if (k == "ngram_tile") return TK_NG_TILE;  // token positions of a tile of the n-gram passes (tk_ngram_rule.h)
     if (k == "select_tile") return TK_SEL_TILE;  // output positions of a tile of the selection's copy (tk_groups_rule.h)
     if (k == "jsonl_tile") return TK_JSONL_TILE;  // bytes of a tile of the JSON Lines passes (tk_jsonl_rule.h)
