@@ -763,16 +763,39 @@ int tk_line_clean(tk_core* core, const uint8_t* text, const uint64_t* doc_off, u
  *   host, the sum of the lines of the adds so far; tk_line_set_count waits, reads the exact number of distinct keys and lowers the bound.
  *  Refused with TK_VALUE_ERROR, nothing written and the set unchanged: a doc_off that does not ascend from 0 to N (seen on the device);
  *   N above 0xFFFF0000; min_bytes 0; capacity 0 or above 2^30; a set of another core; d_text_out == d_text; an add past the capacity.
+ *  Normalised comparison (CCNet's: boilerplate differs in case, numbers, blanks and punctuation).  A set made by
+ *   tk_line_set_create_normalized has a fifth property, `normalize`, a mask of TK_NORM_* fixed at creation.  The key is then computed
+ *   over the line's NORMAL FORM -- its two hashes and ITS length, under the set's bases and salt:
+ *    TK_NORM_PUNCT   the 32 bytes of Python's string.punctuation are deleted, before white space is looked at ("a , b" -> "a b" with
+ *                    TK_NORM_SPACE, "a  b" without): line.translate(None, string.punctuation.encode())
+ *    TK_NORM_CASE    'A'..'Z' become 'a'..'z'
+ *    TK_NORM_DIGITS  '0'..'9' become '0'
+ *    TK_NORM_SPACE   0x09 0x0B 0x0C 0x0D 0x20 are white space: every maximal run becomes one 0x20, the runs at the line's start and end
+ *                    vanish: b" ".join(line.split()).  A '\r' before the '\n' is therefore no part of the key: "\r\n" files and "\n"
+ *                    files meet in one set.
+ *   Bytes >= 0x80 are never touched.  With a mask of 0 the key is bit for bit the plain set's.  A line is eligible when its normal form
+ *   has at least min_bytes bytes: a line of blanks or punctuation alone has an empty normal form, is never dropped and never added, and
+ *   still counts in n_lines.  Everything else stays in terms of RAW bytes: the pieces; which occurrence survives (the eligible line with
+ *   the lowest raw start among those of one key); n_lines, n_dropped, counts; the capacity bound, which counts raw lines; and the output,
+ *   the kept pieces with their own bytes, not normalised.  A mask above 15 is refused with TK_VALUE_ERROR.
  * A tk_line_set belongs to the core it was made on and must be destroyed before it.  It owns its device memory: a table of 16 S bytes,
  * S the power of two >= 2 * capacity (a key and the first-occurrence word per slot); a bitmap of N / 8 bytes, one bit per position, for
  * the drop flags, which a line's closing lane sets at the line's START and every byte of the line finds by one read; 56 bytes per tile
- * of tk_stat("lines_tile") bytes (the line statistics' 52 for one kind, and 4); the buffers of its host entries.  The library orders
- * the calls on one set among themselves on the device (an event), whatever their streams and entries.
- * NOT built: normalised comparison (trimmed, case-folded, digits masked); "\r\n" as a line end; sets of paragraphs; saving a set to a
- * file; removal of single keys; several GPUs; a fast path that hands back its input when nothing is dropped; buffers above 0xFFFF0000
- * bytes. */
+ * of tk_stat("lines_tile") bytes (the line statistics' 52 for one kind, and 4) -- the same for a normalising set, whose scan value
+ * keeps the normal form's length where the statistics keep chars and three flags in the word of the cut bit; the buffers of its host
+ * entries.  The library orders the calls on one set among themselves on the device (an event), whatever their streams and entries.
+ * NOT built: folding of bytes >= 0x80 (no Unicode case folding; U+00A0 and the other Unicode white space are ordinary bytes); the normal
+ * form as output; "\r\n" as a line end of a plain set; sets of paragraphs; saving a set to a file; removal of single keys; several
+ * GPUs; a fast path that hands back its input when nothing is dropped; buffers above 0xFFFF0000 bytes. */
+#define TK_NORM_CASE 1u
+#define TK_NORM_DIGITS 2u
+#define TK_NORM_SPACE 4u
+#define TK_NORM_PUNCT 8u
+#define TK_NORM_ALL 15u
 typedef struct tk_line_set tk_line_set;
 int tk_line_set_create(tk_core* core, uint64_t seed, uint64_t capacity, uint64_t min_bytes, tk_line_set** set_out);
+/* The same with a `normalize` mask of TK_NORM_*; tk_line_set_create is this call with 0.  Every other entry follows the set's mask. */
+int tk_line_set_create_normalized(tk_core* core, uint64_t seed, uint64_t capacity, uint64_t min_bytes, uint32_t normalize, tk_line_set** set_out);
 void tk_line_set_destroy(tk_line_set* set);
 /* The exact number of distinct keys; waits for every call queued on the set. */
 int tk_line_set_count(tk_line_set* set, uint64_t* count_out);

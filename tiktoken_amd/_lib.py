@@ -239,6 +239,8 @@ def lib() -> ctypes.CDLL:
         if hasattr(L, "tk_line_set_create"):  # (absent from older builds selected through $TIKTOKEN_AMD_LIB)
             L.tk_line_set_create.restype = i32
             L.tk_line_set_create.argtypes = [vp, u64, u64, u64, P(vp)]
+            L.tk_line_set_create_normalized.restype = i32
+            L.tk_line_set_create_normalized.argtypes = [vp, u64, u64, u64, ctypes.c_uint32, P(vp)]
             L.tk_line_set_destroy.argtypes = [vp]
             L.tk_line_set_count.restype = i32
             L.tk_line_set_count.argtypes = [vp, P(u64)]

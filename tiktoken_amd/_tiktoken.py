@@ -971,11 +971,15 @@ class LineClean(NamedTuple):
         return [bytes(view[a:b]) for a, b in zip(bounds[:-1], bounds[1:])]
 
 
+# the bits of a line set's `normalize` mask (TK_NORM_*): what is done to a line's bytes before they are hashed
+NORM_CASE, NORM_DIGITS, NORM_SPACE, NORM_PUNCT, NORM_ALL = 1, 2, 4, 8, 15
+
+
 class NativeLineSet:
     """A tk_line_set; made by `CoreBPE.line_set_create`.  Keeps its core alive: the set must go first."""
 
-    def __init__(self, core: "CoreBPE", handle, capacity: int, seed: int, min_bytes: int):
-        self._core, self._h, self.capacity, self.seed, self.min_bytes = core, handle, capacity, seed, min_bytes
+    def __init__(self, core: "CoreBPE", handle, capacity: int, seed: int, min_bytes: int, normalize: int = 0):
+        self._core, self._h, self.capacity, self.seed, self.min_bytes, self.normalize = core, handle, capacity, seed, min_bytes, normalize
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None
@@ -2370,14 +2374,17 @@ class CoreBPE:
         return LineClean(_take_u8(out, int(n_out.value)), off_out, *per_doc)
 
     # ------------------------------------------------------------------ line sets (no reference counterpart: a loop over lines against a set on the host)
-    def line_set_create(self, capacity: int, seed: int = 0, min_bytes: int = 1) -> NativeLineSet:
-        """An empty line set on this core's device (tk_line_set_create) for up to `capacity` distinct lines of at least `min_bytes` bytes."""
+    def line_set_create(self, capacity: int, seed: int = 0, min_bytes: int = 1, normalize: int = 0) -> NativeLineSet:
+        """An empty line set on this core's device (tk_line_set_create_normalized) for up to `capacity` distinct lines of at least
+        `min_bytes` bytes, compared under the `normalize` mask of NORM_* bits."""
         self._one_device("line_set_create")
         if not all(0 <= int(v) <= 0xFFFFFFFFFFFFFFFF for v in (capacity, seed, min_bytes)):
             raise ValueError("capacity, seed and min_bytes must fit 64 bits")
+        if not 0 <= int(normalize) <= 0xFFFFFFFF:
+            raise ValueError("normalize must fit 32 bits")
         h = ctypes.c_void_p()
-        _lib.raise_for(self._L.tk_line_set_create(self._h, int(seed), int(capacity), int(min_bytes), ctypes.byref(h)))
-        return NativeLineSet(self, h, int(capacity), int(seed), int(min_bytes))
+        _lib.raise_for(self._L.tk_line_set_create_normalized(self._h, int(seed), int(capacity), int(min_bytes), int(normalize), ctypes.byref(h)))
+        return NativeLineSet(self, h, int(capacity), int(seed), int(min_bytes), int(normalize))
 
     def line_set_count(self, ls: NativeLineSet) -> int:
         """The distinct lines in the set (tk_line_set_count): waits for the calls queued on it."""

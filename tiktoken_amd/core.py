@@ -543,13 +543,16 @@ class Encoding:
         return _tiktoken.LineClean(host["text_out"][:int(host["counts"][0])], host["doc_off_out"], *[host[m] for m in _tiktoken.CoreBPE.CLEAN_OUTS])
 
     # ------------------------------------------------------------------ line sets
-    def line_set(self, capacity: int, seed: int = 0, min_bytes: int = 1) -> "LineSet":
+    def line_set(self, capacity: int, seed: int = 0, min_bytes: int = 1, normalize: int = 0) -> "LineSet":
         """An empty set of lines that lives on the GPU across calls (tk_line_set_create), and with it the line filter of CCNet-, C4- and
         RefinedWeb-style corpus builds: `dedup_batch` hands a batch back without the lines that occurred anywhere earlier -- in an
         earlier call, an earlier document, or earlier in the same document -- and remembers the ones it kept.  `capacity`: the most
         distinct lines it holds, at most 2^30 (32 bytes of device memory to 64 each); lines shorter than `min_bytes` are never dropped
-        and never remembered.  The rule is stated in include/tiktoken_amd.h."""
-        return LineSet(self, self._core_bpe.line_set_create(capacity, seed, min_bytes))
+        and never remembered.  `normalize`: a mask of `tiktoken_amd.NORM_CASE`, `NORM_DIGITS`, `NORM_SPACE`, `NORM_PUNCT` (`NORM_ALL`:
+        CCNet's comparison) -- lines are compared, and `min_bytes` is measured, on their normal form: lower-cased, digits as '0', white
+        space runs as one blank and trimmed, ASCII punctuation deleted; what is kept comes back with its own bytes.  The rule is stated
+        in include/tiktoken_amd.h."""
+        return LineSet(self, self._core_bpe.line_set_create(capacity, seed, min_bytes, normalize))
 
     # ------------------------------------------------------------------ token n-gram sets
     def ngram_set(self, ngram: int = 13, *, capacity: int, seed: int = 0) -> "NgramSet":
@@ -1214,6 +1217,11 @@ class LineSet:
     def __init__(self, enc: Encoding, native: "_tiktoken.NativeLineSet"):
         self._enc, self._native = enc, native
         self.capacity, self.seed, self.min_bytes = native.capacity, native.seed, native.min_bytes
+
+    @property
+    def normalize(self) -> int:
+        """The set's mask of NORM_* bits, fixed when it was made."""
+        return self._native.normalize
 
     def close(self) -> None:
         self._native.close()

@@ -4452,6 +4452,7 @@ struct tk_line_set {
     tk_core* c = nullptr;
     int device = 0;
     uint64_t seed = 0, capacity = 0, min_bytes = 1, S = 0;
+    uint32_t normalize = 0;  // TK_NORM_*: which instantiation of the hashing kernels the set's calls launch
     uint64_t bound = 0;  // at least the distinct keys in the table: the lines of the adds since the last exact count
     uint32_t epoch = 0;  // add calls since the last clear
     Event done;          // recorded behind every call on the set, on that call's stream; the next call's stream waits for it first
@@ -4470,6 +4471,8 @@ struct LsOuts {  // the caller's device arrays; all but text and doc_off may be 
     uint8_t* text;
     uint64_t *doc_off, *n_lines, *n_dropped, *counts;
 };
+static_assert(TK_NORM_CASE == TK_LN_N_CASE && TK_NORM_DIGITS == TK_LN_N_DIGITS && TK_NORM_SPACE == TK_LN_N_SPACE && TK_NORM_PUNCT == TK_LN_N_PUNCT && TK_NORM_ALL == TK_LN_N_ALL,
+              "normalize bits");
 static const char* const LS_CAP_MSG = "n_bytes: the text of a line set call is at most 0xFFFF0000 bytes (positions are 32-bit)";
 static int ls_check(tk_core* c, tk_line_set* st) {
     if (!c) return fail(TK_VALUE_ERROR, "core is null");
@@ -4491,7 +4494,7 @@ static int ls_front(tk_line_set* st, hipStream_t s, const uint8_t* d_text, uint6
     if (tk_ln_shape(n, n_docs, st->seed, &k.q.ln)) return fail(TK_VALUE_ERROR, LS_CAP_MSG);
     if (n_docs > 0xFFFFFFFEull) return fail(TK_VALUE_ERROR, "n_docs: at most 2^32 - 2 documents");
     if (add && st->epoch >= TK_LS_MAX_EPOCH) return fail(TK_VALUE_ERROR, "2^32 - 2 add calls on a line set: clear it");
-    k.q.S = st->S, k.q.min_bytes = st->min_bytes, k.q.epoch = add ? st->epoch + 1 : 0u;
+    k.q.S = st->S, k.q.min_bytes = st->min_bytes, k.q.epoch = add ? st->epoch + 1 : 0u, k.q.ln.norm = st->normalize;
     HIPCHK(hipStreamWaitEvent(s, st->done, 0));  // (the scratch is the set's)
     const uint64_t nt = k.q.ln.n_tiles;
     Carve work;
@@ -4502,8 +4505,15 @@ static int ls_front(tk_line_set* st, hipStream_t s, const uint8_t* d_text, uint6
     k.kept = carved<uint32_t>(st->work, at_kept);
     k.aligned = ((uintptr_t)d_text & 15u) == 0;
     TRY(timed(c, s, "tk_k_ln_clear", [&] { hipLaunchKernelGGL(tk_k_ln_clear, dim3(1), dim3(256), 0, s, k.words, (uint64_t)(TK_LN_WORDS + TK_LS_WORDS)); }));
-    TRY(timed(c, s, "tk_k_ln_sum", [&] { hipLaunchKernelGGL((tk_k_ln_sum<1>), dim3((uint32_t)nt), dim3(TK_LN_THREADS), 0, s, k.q.ln, d_text, d_doc_off, k.aligned, k.T, k.words); }));
-    TRY(timed(c, s, "tk_k_ln_carry", [&] { hipLaunchKernelGGL((tk_k_ln_carry<1>), dim3(1), dim3(1024), 0, s, k.q.ln, k.T, k.words); }));
+    if (st->normalize) {
+        TRY(timed(c, s, "tk_k_ln_sum_norm", [&] {
+            hipLaunchKernelGGL((tk_k_ln_sum<1, TkLnNorm>), dim3((uint32_t)nt), dim3(TK_LN_THREADS), 0, s, k.q.ln, d_text, d_doc_off, k.aligned, k.T, k.words);
+        }));
+        TRY(timed(c, s, "tk_k_ln_carry_norm", [&] { hipLaunchKernelGGL((tk_k_ln_carry<1, TkLnNorm>), dim3(1), dim3(1024), 0, s, k.q.ln, k.T, k.words); }));
+    } else {
+        TRY(timed(c, s, "tk_k_ln_sum", [&] { hipLaunchKernelGGL((tk_k_ln_sum<1>), dim3((uint32_t)nt), dim3(TK_LN_THREADS), 0, s, k.q.ln, d_text, d_doc_off, k.aligned, k.T, k.words); }));
+        TRY(timed(c, s, "tk_k_ln_carry", [&] { hipLaunchKernelGGL((tk_k_ln_carry<1>), dim3(1), dim3(1024), 0, s, k.q.ln, k.T, k.words); }));
+    }
     unsigned long long got[TK_LN_WORDS];
     HIPCHK(hipMemcpyAsync(got, k.words, sizeof got, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));  // the one wait
@@ -4516,9 +4526,12 @@ static int ls_front(tk_line_set* st, hipStream_t s, const uint8_t* d_text, uint6
     return TK_OK;
 }
 static int ls_mark(tk_line_set* st, hipStream_t s, const LsCall& k, const uint8_t* d_text, const uint64_t* d_doc_off) {
-    TRY(timed(st->c, s, "tk_k_ls_mark", [&] {
-        hipLaunchKernelGGL(tk_k_ls_mark, dim3(k.q.ln.n_tiles), dim3(TK_LN_THREADS), 0, s, k.q, d_text, d_doc_off, k.aligned, k.T, st->tab());
-    }));
+    const dim3 tiles(k.q.ln.n_tiles), block(TK_LN_THREADS);
+    if (st->normalize) {
+        TRY(timed(st->c, s, "tk_k_ls_mark_norm", [&] { hipLaunchKernelGGL(tk_k_ls_mark<TkLnNorm>, tiles, block, 0, s, k.q, d_text, d_doc_off, k.aligned, k.T, st->tab()); }));
+    } else {
+        TRY(timed(st->c, s, "tk_k_ls_mark", [&] { hipLaunchKernelGGL(tk_k_ls_mark<TkLnRaw>, tiles, block, 0, s, k.q, d_text, d_doc_off, k.aligned, k.T, st->tab()); }));
+    }
     st->epoch = k.q.epoch, st->bound += k.lines;
     return TK_OK;
 }
@@ -4546,10 +4559,17 @@ static int ls_dedup_run(tk_line_set* st, hipStream_t s, const uint8_t* d_text, u
     if (add) TRY(ls_mark(st, s, k, d_text, d_doc_off));
     const dim3 tiles((uint32_t)nt), block(TK_LN_THREADS);
     uint32_t* bits = st->bits.as<uint32_t>();
-    TRY(timed(c, s, "tk_k_ls_decide", [&] {
-        hipLaunchKernelGGL(tk_k_ls_decide, tiles, block, 0, s, k.q, d_text, d_doc_off, k.aligned, k.T, st->tab(), bits, (unsigned long long*)o.n_lines,
-                           (unsigned long long*)o.n_dropped, k.words);
-    }));
+    if (st->normalize) {
+        TRY(timed(c, s, "tk_k_ls_decide_norm", [&] {
+            hipLaunchKernelGGL(tk_k_ls_decide<TkLnNorm>, tiles, block, 0, s, k.q, d_text, d_doc_off, k.aligned, k.T, st->tab(), bits, (unsigned long long*)o.n_lines,
+                               (unsigned long long*)o.n_dropped, k.words);
+        }));
+    } else {
+        TRY(timed(c, s, "tk_k_ls_decide", [&] {
+            hipLaunchKernelGGL(tk_k_ls_decide<TkLnRaw>, tiles, block, 0, s, k.q, d_text, d_doc_off, k.aligned, k.T, st->tab(), bits, (unsigned long long*)o.n_lines,
+                               (unsigned long long*)o.n_dropped, k.words);
+        }));
+    }
     TRY(timed(c, s, "tk_k_ls_keep", [&] { hipLaunchKernelGGL(tk_k_ls_keep, tiles, block, 0, s, k.q, d_text, d_doc_off, k.aligned, k.T, bits, k.kept); }));
     TRY(timed(c, s, "tk_k_ls_scan", [&] { hipLaunchKernelGGL(tk_k_ls_scan, dim3(1), dim3(1024), 0, s, k.kept, nt); }));
     TRY(timed(c, s, "tk_k_ls_write", [&] {
@@ -4592,8 +4612,12 @@ extern "C" void tk_line_set_destroy(tk_line_set* st) {
     delete st;
 }
 extern "C" int tk_line_set_create(tk_core* c, uint64_t seed, uint64_t capacity, uint64_t min_bytes, tk_line_set** set_out) {
+    return tk_line_set_create_normalized(c, seed, capacity, min_bytes, 0u, set_out);
+}
+extern "C" int tk_line_set_create_normalized(tk_core* c, uint64_t seed, uint64_t capacity, uint64_t min_bytes, uint32_t normalize, tk_line_set** set_out) {
     if (!c) return fail(TK_VALUE_ERROR, "core is null");
     if (!set_out) return fail(TK_VALUE_ERROR, "null argument");
+    if (normalize > TK_NORM_ALL) return fail(TK_VALUE_ERROR, "normalize: bits 0..3");
     uint64_t S = 0;
     switch (tk_ls_shape(capacity, min_bytes, &S)) {
         case 0: break;
@@ -4603,7 +4627,7 @@ extern "C" int tk_line_set_create(tk_core* c, uint64_t seed, uint64_t capacity, 
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(hipSetDevice(c->device));
     std::unique_ptr<tk_line_set, void (*)(tk_line_set*)> st(new tk_line_set, tk_line_set_destroy);
-    st->c = c, st->device = c->device, st->seed = seed, st->capacity = capacity, st->min_bytes = min_bytes, st->S = S;
+    st->c = c, st->device = c->device, st->seed = seed, st->capacity = capacity, st->min_bytes = min_bytes, st->S = S, st->normalize = normalize;
     HIPCHK(st->done.create());
     TRY(ensure(st->table, (2 * S + 1) * 8));
     TRY(drained(c, [&] { return ls_clear_run(st.get(), c->stream); }));

@@ -28,6 +28,12 @@
 //                   stores at the ragged ends.  A tile from which nothing is dropped is a shifted copy.  For every doc_off[i] in the
 //                   tile -- the entries tk_ln_stage has found, empty documents included -- doc_off_out[i] is the kept bytes before
 //                   it.  The last tile writes counts.
+// Normalising sets (a `normalize` mask, fixed at creation).  tk_k_ln_sum<1>, tk_k_ln_carry<1>, tk_k_ls_mark and tk_k_ls_decide are
+// templates over what is hashed: TkLnRaw, the line's bytes, or TkLnNorm, its normal form (tk_lines.h; the value and its join:
+// tk_lines_rule.h).  The host chooses from the set's mask, and a set with a mask of 0 launches what it always launched.  Under
+// TkLnNorm the key and the eligibility are the normal form's; a line's start, its drop bit, the counts and the capacity stay raw, and
+// tk_k_ls_keep, tk_k_ls_scan and tk_k_ls_write, which never hash, are the same kernels: the raw count of the run that enters a tile
+// lies at one place in either scan value.
 // The text is read five times when adding (four when not) and written once.  All stores are vector stores of plain C++.  No matrix
 // instructions and no floating point: there is no contraction here.
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): see DESIGN.md.  Included by tk_api.hip only.
@@ -51,32 +57,37 @@ __global__ __launch_bounds__(256) void tk_k_ls_clear(TkLsTab tab, uint64_t S) {
 
 // The finished lines of a lane: f(j, start, run) at every cut j of the lane that closes a run -- `before`: the scanned run that enters
 // the lane --, start its first position.  The walk of tk_k_ln_count over the line kind.
-template <class F>
-__device__ __forceinline__ void tk_ls_each_line(const TkLs& q, const TkLnLane& L, const TkLnSeg& before, F&& f) {
+template <class M, class F>
+__device__ __forceinline__ void tk_ls_each_line(const typename M::View& view, const typename M::Seg& before, F&& f) {
+    const TkLnLane& L = view.L;
     const uint32_t cut = L.cut0, cont = L.content0;
     if (!cut) return;
     const uint32_t l = 31u - (uint32_t)__clz((int)cut), at = blockIdx.x * TK_LN_TILE + L.pos;
-    TkLnEl run = before.e;
+    typename M::Seg run = before;
 #pragma unroll 1
     for (uint32_t j = 0; j <= l; ++j) {
-        if (((cut >> j) & 1u) && run.bytes) f(j, at + j - run.bytes, run);
-        if ((cut >> j) & 1u) run = tk_ln_empty();
-        if (j < l && ((cont >> j) & 1u)) tk_ln_push(q.ln, run, L.byte(j));
+        if (((cut >> j) & 1u) && run.e.bytes) f(j, at + j - run.e.bytes, run);
+        if ((cut >> j) & 1u) run = M::empty();
+        if (j < l && ((cont >> j) & 1u)) view.push(run, j);
     }
 }
-__device__ __forceinline__ TkLnSeg tk_ls_before(const TkLs& q, const TkLnLane& L, const TkLnTiles& T, TkLnShared& sh) {
-    return tk_ln_block_exscan(tk_ln_lane_tail(q.ln, L, TK_LN_LINE, sh), TkLnSeg{T.seg[blockIdx.x].e, 0u}, sh.wsum, nullptr);
+template <class M>
+__device__ __forceinline__ typename M::Seg tk_ls_before(const TkLs& q, const typename M::View& view, const TkLnTiles& T, TkLnShared& sh) {
+    return tk_ln_block_exscan(M(q.ln), view.tail(TK_LN_LINE, sh), M::enters(T, blockIdx.x), M::wsum(sh), (typename M::Seg*)nullptr);
 }
 
+// (M: what is hashed -- TkLnRaw for a set with a mask of 0, TkLnNorm for a normalising one; the same for tk_k_ls_decide)
+template <class M>
 __global__ __launch_bounds__(TK_LN_THREADS) void tk_k_ls_mark(TkLs q, const uint8_t* __restrict__ text, const uint64_t* __restrict__ doc_off, bool aligned, TkLnTiles T,
                                                               TkLsTab tab) {
     __shared__ TkLnShared sh;
     const TkLnLane L = tk_ln_stage(q.ln, text, doc_off, aligned, sh);
-    const TkLnSeg before = tk_ls_before(q, L, T, sh);
+    const typename M::View view(q.ln, L);
+    const typename M::Seg before = tk_ls_before<M>(q, view, T, sh);
     uint32_t claims = 0;
-    tk_ls_each_line(q, L, before, [&](uint32_t, uint32_t start, const TkLnEl& run) {
-        if (run.bytes < q.min_bytes) return;
-        const uint64_t key = tk_ls_key(q.ln.seed, run);
+    tk_ls_each_line<M>(view, before, [&](uint32_t, uint32_t start, const typename M::Seg& run) {
+        if (!tk_ls_eligible(q, run)) return;
+        const uint64_t key = tk_ls_key(q.ln.seed, run.e);
         uint64_t slot = q.S;
         const bool won = tk_ng_insert(tab.key, q.S, key, [&](uint64_t i, uint64_t k) {
             const uint64_t v = (uint64_t)atomicCAS(tab.key + i, 0ull, (unsigned long long)k);
@@ -91,6 +102,7 @@ __global__ __launch_bounds__(TK_LN_THREADS) void tk_k_ls_mark(TkLs q, const uint
     if ((threadIdx.x & 63u) == 0 && claims) atomicAdd(tab.count, (unsigned long long)claims);
 }
 
+template <class M>
 __global__ __launch_bounds__(TK_LN_THREADS) void tk_k_ls_decide(TkLs q, const uint8_t* __restrict__ text, const uint64_t* __restrict__ doc_off, bool aligned, TkLnTiles T,
                                                                 TkLsTab tab, uint32_t* bitmap, unsigned long long* n_lines, unsigned long long* n_dropped,
                                                                 unsigned long long* words) {
@@ -113,12 +125,13 @@ __global__ __launch_bounds__(TK_LN_THREADS) void tk_k_ls_decide(TkLs q, const ui
         if (li < TK_LN_DOCS) docid[li] = (uint32_t)i;
     }
     __syncthreads();
-    const TkLnSeg before = tk_ls_before(q, L, T, sh);
+    const typename M::View view(q.ln, L);
+    const typename M::Seg before = tk_ls_before<M>(q, view, T, sh);
     unsigned long long* const outs[2] = {n_lines, n_dropped};
-    tk_ls_each_line(q, L, before, [&](uint32_t j, uint32_t start, const TkLnEl& run) {
+    tk_ls_each_line<M>(view, before, [&](uint32_t j, uint32_t start, const typename M::Seg& run) {
         bool drop = false;
-        if (run.bytes >= q.min_bytes) {
-            const uint64_t key = tk_ls_key(q.ln.seed, run), slot = tk_ls_find(tab.key, q.S, key);
+        if (tk_ls_eligible(q, run)) {
+            const uint64_t key = tk_ls_key(q.ln.seed, run.e), slot = tk_ls_find(tab.key, q.S, key);
             drop = q.epoch ? slot == q.S || tab.first[slot] != tk_ls_first(q.epoch, start) : slot < q.S;
         }
         if (drop) atomicOr(bitmap + (start >> 5), 1u << (start & 31u)), atomicAdd(&dropped_here, 1u);

@@ -41,6 +41,12 @@ TK_HD uint64_t tk_ls_key(uint64_t seed, const TkLnEl& e) {
     x = tk_fp_mix(x ^ e.h1), x = tk_fp_mix(x ^ e.h2), x = tk_fp_mix(x ^ e.bytes);
     return x ? x : 1;
 }
+// A normalising set (ln.norm != 0): the same key over the line's normal form -- its two hashes and ITS length; a line is eligible when
+// its normal form has min_bytes bytes, so a line of blanks and deleted bytes alone, whose normal form is empty, never is.  With a mask
+// of 0 the normal form is the line and both are the plain set's.
+TK_HD uint64_t tk_ls_key(uint64_t seed, const TkLnNEl& e) { return tk_ls_key(seed, TkLnEl{e.h1, 1, e.h2, 1, e.len, 0}); }
+TK_HD bool tk_ls_eligible(const TkLs& q, const TkLnSeg& line) { return line.e.bytes >= q.min_bytes; }
+TK_HD bool tk_ls_eligible(const TkLs& q, const TkLnNSeg& line) { return line.e.len >= q.min_bytes; }
 TK_HD uint64_t tk_ls_first(uint32_t epoch, uint32_t start) { return ((uint64_t)epoch << 32) | start; }
 // The slot of `key`, S when it is not in the table.  The walk ends at the key or at an empty slot, as tk_ng_probe's.
 template <class Table>

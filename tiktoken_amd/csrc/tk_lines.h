@@ -48,24 +48,30 @@ __device__ __forceinline__ TkLnSeg tk_ln_shfl_up(const TkLnSeg& v, int o) {
                           __shfl_up((unsigned long long)v.e.w2, o, 64), __shfl_up(v.e.bytes, o, 64), __shfl_up(v.e.chars, o, 64)},
                    __shfl_up(v.cut, o, 64)};
 }
-// The exclusive scan under tk_ln_seg_join over a workgroup of whole wavefronts (at most 16), `init` before the first lane; *total: `init`
-// and every lane's value.  wsum: a slot per wavefront in LDS, free again when the call returns.
-__device__ __forceinline__ TkLnSeg tk_ln_block_exscan(TkLnSeg v, const TkLnSeg& init, TkLnSeg* wsum, TkLnSeg* total) {
+__device__ __forceinline__ TkLnNSeg tk_ln_shfl_up(const TkLnNSeg& v, int o) {
+    return TkLnNSeg{TkLnNEl{__shfl_up((unsigned long long)v.e.h1, o, 64), __shfl_up((unsigned long long)v.e.w1, o, 64), __shfl_up((unsigned long long)v.e.h2, o, 64),
+                            __shfl_up((unsigned long long)v.e.w2, o, 64), __shfl_up(v.e.bytes, o, 64), __shfl_up(v.e.len, o, 64)},
+                    __shfl_up(v.cut, o, 64)};
+}
+// The exclusive scan under m.join over a workgroup of whole wavefronts (at most 16), `init` before the first lane; *total: `init` and
+// every lane's value.  wsum: a slot per wavefront in LDS, free again when the call returns.  m: TkLnRaw or TkLnNorm, below.
+template <class M>
+__device__ __forceinline__ typename M::Seg tk_ln_block_exscan(const M& m, typename M::Seg v, const typename M::Seg& init, typename M::Seg* wsum, typename M::Seg* total) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
 #pragma unroll 1
     for (int o = 1; o < 64; o <<= 1) {
-        const TkLnSeg u = tk_ln_shfl_up(v, o);
-        if ((int)lane >= o) v = tk_ln_seg_join(u, v);
+        const typename M::Seg u = tk_ln_shfl_up(v, o);
+        if ((int)lane >= o) v = m.join(u, v);
     }
     if (lane == 63u) wsum[wave] = v;
-    TkLnSeg ex = tk_ln_shfl_up(v, 1);
-    if (lane == 0) ex = TkLnSeg{tk_ln_empty(), 0u};
+    typename M::Seg ex = tk_ln_shfl_up(v, 1);
+    if (lane == 0) ex = M::empty();
     __syncthreads();
-    TkLnSeg pre = init;
+    typename M::Seg pre = init;
 #pragma unroll 1
     for (uint32_t w = 0; w < n_waves; ++w) {
-        if (w == wave) ex = tk_ln_seg_join(pre, ex);
-        if (w < wave || total) pre = tk_ln_seg_join(pre, wsum[w]);
+        if (w == wave) ex = m.join(pre, ex);
+        if (w < wave || total) pre = m.join(pre, wsum[w]);
     }
     if (total) *total = pre;
     __syncthreads();
@@ -89,7 +95,10 @@ struct TkLnShared {
     unsigned long long brkw[TK_LN_TILE / 64 + 1];  // bit i: a document starts at the tile's position i, i <= T
     uint32_t brkpre[TK_LN_TILE / 64];              // the bits of the words before a word
     uint64_t pw[2][TK_LN_LANE + 1];                // B1^i, B2^i
-    TkLnSeg wsum[4];
+    union {  // a kernel scans one kind of value
+        TkLnSeg wsum[4];
+        TkLnNSeg nwsum[4];
+    };
     uint32_t i0, i1;  // the entries of doc_off that can lie in [g0, g0 + T]: [i0, i1]
 };
 
@@ -159,12 +168,74 @@ __device__ __forceinline__ TkLnSeg tk_ln_lane_tail(const TkLn& p, const TkLnLane
     return TkLnSeg{e, cut ? 1u : 0u};
 }
 
+// What the kernels that hash are instantiated over: the value their scans carry, and a lane's bytes as that value sees them.
+//   TkLnRaw   the bytes as they are: every kernel of the line statistics, and the line sets with a mask of 0
+//   TkLnNorm  the normal form under p.norm (tk_lines_rule.h): the line sets made with a mask.  A lane's classes are SWAR words built once
+//             per 16 bytes, case and digits are mapped in the words, and the walk visits only the bytes that are not deleted: a lane of
+//             plain lower-case text does the two multiplies per byte of TkLnRaw, a lane of deleted bytes none.
+struct TkLnRaw {
+    using Seg = TkLnSeg;
+    __device__ __forceinline__ TkLnRaw() {}
+    __device__ __forceinline__ explicit TkLnRaw(const TkLn&) {}  // (its join needs nothing of the call)
+    static __device__ __forceinline__ Seg empty() { return TkLnSeg{tk_ln_empty(), 0u}; }
+    static __device__ __forceinline__ Seg enters(const TkLnTiles& T, uint64_t at) { return TkLnSeg{T.seg[at].e, 0u}; }  // the carried run: no cut lies in it
+    static __device__ __forceinline__ Seg* tiles(const TkLnTiles& T) { return T.seg; }
+    static __device__ __forceinline__ Seg* wsum(TkLnShared& sh) { return sh.wsum; }
+    __device__ __forceinline__ Seg join(const Seg& l, const Seg& r) const { return tk_ln_seg_join(l, r); }
+    struct View {
+        const TkLn& p;
+        const TkLnLane& L;
+        __device__ __forceinline__ View(const TkLn& p_, const TkLnLane& L_) : p(p_), L(L_) {}
+        __device__ __forceinline__ Seg tail(uint32_t kind, const TkLnShared& sh) const { return tk_ln_lane_tail(p, L, kind, sh); }
+        __device__ __forceinline__ void push(Seg& run, uint32_t j) const { tk_ln_push(p, run.e, L.byte(j)); }
+    };
+};
+struct TkLnNorm {
+    using Seg = TkLnNSeg;
+    const TkLn& p;
+    __device__ __forceinline__ explicit TkLnNorm(const TkLn& p_) : p(p_) {}
+    static __device__ __forceinline__ Seg empty() { return tk_lnn_empty(); }
+    static __device__ __forceinline__ Seg* tiles(const TkLnTiles& T) { return reinterpret_cast<TkLnNSeg*>(T.seg); }  // (one size, one place for the raw count)
+    static __device__ __forceinline__ Seg enters(const TkLnTiles& T, uint64_t at) {
+        Seg s = tiles(T)[at];
+        s.cut &= ~TK_LN_NF_CUT;
+        return s;
+    }
+    static __device__ __forceinline__ Seg* wsum(TkLnShared& sh) { return sh.nwsum; }
+    __device__ __forceinline__ Seg join(const Seg& l, const Seg& r) const { return tk_lnn_seg_join(p, l, r); }
+    struct View {
+        const TkLn& p;
+        const TkLnLane& L;
+        const TkLnNLane c;
+        __device__ __forceinline__ View(const TkLn& p_, const TkLnLane& L_) : p(p_), L(L_), c(tk_lnn_lane(L_.lo, L_.hi, p_.norm)) {}
+        // the run behind the lane's last cut, with its powers: tk_ln_lane_tail over the normal form
+        __device__ __forceinline__ Seg tail(uint32_t kind, const TkLnShared& sh) const {
+            const uint32_t cut = L.cut(kind);
+            uint32_t from = 0;
+            if (cut) {
+                const uint32_t l = 31u - (uint32_t)__clz((int)cut);
+                from = l + (((L.content(kind) >> l) & 1u) ^ 1u);
+            }
+            Seg s = tk_lnn_empty();
+            tk_lnn_append(p, c, from, TK_LN_LANE, s);
+            s.e.w1 = sh.pw[0][s.e.len], s.e.w2 = sh.pw[1][s.e.len];  // (a body is no longer than the bytes it came from)
+            s.cut |= cut ? TK_LN_NF_CUT : 0u;
+            return s;
+        }
+        __device__ __forceinline__ void push(Seg& run, uint32_t j) const { tk_lnn_append(p, c, j, j + 1u, run); }
+    };
+};
+__device__ __forceinline__ TkLnSeg tk_ln_block_exscan(TkLnSeg v, const TkLnSeg& init, TkLnSeg* wsum, TkLnSeg* total) {
+    return tk_ln_block_exscan(TkLnRaw(), v, init, wsum, total);
+}
+
 __global__ __launch_bounds__(256) void tk_k_ln_clear(unsigned long long* a, uint64_t n) {
     for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) a[i] = 0;
 }
 
-// (KINDS: 2, or 1 for the line kind alone -- tk_line_set.h; the same for tk_k_ln_carry, whose report word then counts lines)
-template <uint32_t KINDS>
+// (KINDS: 2, or 1 for the line kind alone -- tk_line_set.h; the same for tk_k_ln_carry, whose report word then counts lines.  M: what is
+// hashed, TkLnRaw or TkLnNorm; the lines counted are the raw ones under either)
+template <uint32_t KINDS, class M = TkLnRaw>
 __global__ __launch_bounds__(TK_LN_THREADS) void tk_k_ln_sum(TkLn p, const uint8_t* __restrict__ text, const uint64_t* __restrict__ doc_off, bool aligned, TkLnTiles T,
                                                              unsigned long long* __restrict__ words) {
     __shared__ TkLnShared sh;
@@ -182,39 +253,43 @@ __global__ __launch_bounds__(TK_LN_THREADS) void tk_k_ln_sum(TkLn p, const uint8
     if (tid < 2) cnt[tid] = 0;
     __syncthreads();
     const uint32_t before = tid ? last[tid - 1] : 0u;
+    const M m(p);
+    const typename M::View view(p, L);
 #pragma unroll 1
     for (uint32_t kind = 0; kind < KINDS; ++kind) {
-        TkLnSeg total;
-        tk_ln_block_exscan(tk_ln_lane_tail(p, L, kind, sh), TkLnSeg{tk_ln_empty(), 0u}, sh.wsum, &total);
+        typename M::Seg total;
+        tk_ln_block_exscan(m, view.tail(kind, sh), M::empty(), M::wsum(sh), &total);
         const uint32_t n = tk_wave_sum_u32((uint32_t)__popc(L.cut(kind) & ((L.content(kind) << 1) | ((before >> kind) & 1u))));
         if ((tid & 63u) == 0 && n) atomicAdd(&cnt[kind], n);
         __syncthreads();
         if (tid == 0) {
             const uint64_t at = (uint64_t)kind * p.n_tiles + blockIdx.x;
-            T.seg[at] = total;
+            M::tiles(T)[at] = total;
             T.nseg[at] = 2u * cnt[kind] + (L.cut(kind) & 1u);
         }
     }
 }
 
-template <uint32_t KINDS>
+template <uint32_t KINDS, class M = TkLnRaw>
 __global__ __launch_bounds__(1024) void tk_k_ln_carry(TkLn p, TkLnTiles T, unsigned long long* __restrict__ words) {
-    __shared__ TkLnSeg wsum[16];
+    using Seg = typename M::Seg;
+    __shared__ Seg wsum[16];
+    const M m(p);
     const uint32_t per = (p.n_tiles + 1023u) / 1024u;
     const uint64_t a = (uint64_t)threadIdx.x * per, b = a + per < p.n_tiles ? a + per : p.n_tiles;
     unsigned long long segs = 0;
 #pragma unroll 1
     for (uint32_t kind = 0; kind < KINDS; ++kind) {
-        TkLnSeg* seg = T.seg + (uint64_t)kind * p.n_tiles;
+        Seg* seg = M::tiles(T) + (uint64_t)kind * p.n_tiles;
         const uint32_t* nseg = T.nseg + (uint64_t)kind * p.n_tiles;
-        TkLnSeg mine{tk_ln_empty(), 0u};
-        for (uint64_t t = a; t < b; ++t) mine = tk_ln_seg_join(mine, seg[t]);
-        TkLnSeg run = tk_ln_block_exscan(mine, TkLnSeg{tk_ln_empty(), 0u}, wsum, nullptr);
+        Seg mine = M::empty();
+        for (uint64_t t = a; t < b; ++t) mine = m.join(mine, seg[t]);
+        Seg run = tk_ln_block_exscan(m, mine, M::empty(), wsum, (Seg*)nullptr);
         for (uint64_t t = a; t < b; ++t) {
-            const TkLnSeg s = seg[t];
+            const Seg s = seg[t];
             segs += (nseg[t] >> 1) + ((nseg[t] & 1u) && run.e.bytes ? 1u : 0u);
             seg[t] = run;
-            run = tk_ln_seg_join(run, s);
+            run = m.join(run, s);
         }
     }
     if (segs) atomicAdd(words + TK_LN_W_SEGS, segs);

@@ -15,6 +15,7 @@
 // Runs of different length never have the same tuple.  So two different lines of a document are confused with about 2^-64 + L^2 / 2^122
 // per pair -- a hash DECIDES here, unlike in tk_repeat_rule.h.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include "tk_fingerprint_rule.h"  // tk_fp_mix, tk_last_le
@@ -38,6 +39,7 @@ enum { TK_LN_W_SEGS = 0, TK_LN_W_BAD = 1, TK_LN_WORDS = 2 };  // report words: s
 struct TkLn {
     uint64_t B1, B2, seed, n_bytes, n_docs;
     uint32_t n_tiles;
+    uint32_t norm;  // TK_LN_N_* of a normalising line set; 0 everywhere else
 };
 // The shape of a call.  0, or why it is refused: 1 n_bytes.
 TK_HD uint64_t tk_ln_base(uint64_t seed, uint64_t salt) { return 257 + tk_fp_mix(seed ^ salt) % (TK_LN_P - 257); }
@@ -46,6 +48,7 @@ TK_HD int tk_ln_shape(uint64_t n_bytes, uint64_t n_docs, uint64_t seed, TkLn* p)
     p->B1 = tk_ln_base(seed, TK_LN_SALT_B1), p->B2 = tk_ln_base(seed, TK_LN_SALT_B2);
     p->seed = seed, p->n_bytes = n_bytes, p->n_docs = n_docs;
     p->n_tiles = (uint32_t)(n_bytes / TK_LN_TILE + 1);  // (position N lies in a tile)
+    p->norm = 0;
     return 0;
 }
 // slots of the table for `segs` lines and paragraphs: the power of two >= 2 segs
@@ -143,4 +146,111 @@ TK_HD bool tk_ln_ellipsis(uint32_t n, At&& at) {
     if (n < 3) return false;
     const uint32_t a = at(n - 3), b = at(n - 2), c = at(n - 1);
     return (a == '.' && b == '.' && c == '.') || (a == 0xE2 && b == 0x80 && c == 0xA6);
+}
+
+// ------------------------------------------------------------------------------------------
+// The normal form of a line: what a line set made with a `normalize` mask hashes in place of the line's bytes.  With TK_LN_N_PUNCT the
+// 32 bytes of Python's string.punctuation are deleted, first; with TK_LN_N_CASE 'A'..'Z' become 'a'..'z'; with TK_LN_N_DIGITS '0'..'9'
+// become '0'; with TK_LN_N_SPACE every maximal run of 0x09 0x0B 0x0C 0x0D 0x20 becomes one 0x20 and the runs at the line's ends vanish
+// (b" ".join(x.split()) on a line, which holds no '\n').  Bytes >= 0x80 are never touched.
+//
+// The normal form composes as the hash does.  A scan value is the BODY of the bytes seen so far -- their normal form without the blanks
+// at its ends: the two hashes, the powers, its length -- with the raw byte count, and flags beside the cut bit: LEAD, a body exists and
+// white space precedes it; TRAIL, a body exists and white space follows it; WS, no body and white space was seen.  Two bodies join with
+// one blank between them when the left has TRAIL or the right has LEAD -- a multiply by B and an add per hash, a multiply on the
+// power --; a value without a body hands its white space to the near flag of the other; deleted bytes leave no trace but the raw count.
+// The value has the size and the layout of TkLnSeg, with the body's length where the raw runs keep their chars: the passes that read
+// only the raw count of the run that enters a tile (tk_k_ls_keep, tk_k_ls_write) read either.
+// ------------------------------------------------------------------------------------------
+#define TK_LN_N_CASE 1u
+#define TK_LN_N_DIGITS 2u
+#define TK_LN_N_SPACE 4u
+#define TK_LN_N_PUNCT 8u
+#define TK_LN_N_ALL 15u
+#define TK_LN_NF_CUT 1u
+#define TK_LN_NF_LEAD 2u
+#define TK_LN_NF_TRAIL 4u
+#define TK_LN_NF_WS 8u
+
+struct TkLnNEl {
+    uint64_t h1, w1, h2, w2;  // of the body
+    uint32_t bytes, len;      // raw bytes; bytes of the body
+};
+struct TkLnNSeg {
+    TkLnNEl e;
+    uint32_t cut;  // TK_LN_NF_*
+};
+static_assert(sizeof(TkLnNSeg) == sizeof(TkLnSeg) && offsetof(TkLnNSeg, e.bytes) == offsetof(TkLnSeg, e.bytes), "the raw count of either scan value lies at one place");
+TK_HD TkLnNSeg tk_lnn_empty() { return TkLnNSeg{TkLnNEl{0, 1, 0, 1, 0, 0}, 0u}; }
+// a blank behind a body: hashes and powers
+TK_HD void tk_lnn_blank(const TkLn& p, TkLnNEl& e) {
+    e.h1 = tk_ln_addmod(tk_ln_mulmod(e.h1, p.B1), 0x21), e.h2 = tk_ln_addmod(tk_ln_mulmod(e.h2, p.B2), 0x21);
+    e.w1 = tk_ln_mulmod(e.w1, p.B1), e.w2 = tk_ln_mulmod(e.w2, p.B2), e.len += 1;
+}
+// l then r, no cut between them: the cut bit is l's
+TK_HD TkLnNSeg tk_lnn_join(const TkLn& p, const TkLnNSeg& l, const TkLnNSeg& r) {
+    const bool lb = l.e.len != 0, rb = r.e.len != 0;
+    TkLnNEl a = l.e;
+    if (lb && rb && ((l.cut & TK_LN_NF_TRAIL) || (r.cut & TK_LN_NF_LEAD))) tk_lnn_blank(p, a);
+    uint32_t f = l.cut & TK_LN_NF_CUT;
+    if (lb) f |= l.cut & TK_LN_NF_LEAD;
+    else if (rb) f |= (r.cut & TK_LN_NF_LEAD) | ((l.cut & TK_LN_NF_WS) ? TK_LN_NF_LEAD : 0u);
+    if (rb) f |= r.cut & TK_LN_NF_TRAIL;
+    else if (lb) f |= (l.cut & TK_LN_NF_TRAIL) | ((r.cut & TK_LN_NF_WS) ? TK_LN_NF_TRAIL : 0u);
+    if (!lb && !rb) f |= (l.cut | r.cut) & TK_LN_NF_WS;
+    return TkLnNSeg{TkLnNEl{tk_ln_addmod(tk_ln_mulmod(a.h1, r.e.w1), r.e.h1), tk_ln_mulmod(a.w1, r.e.w1), tk_ln_addmod(tk_ln_mulmod(a.h2, r.e.w2), r.e.h2),
+                            tk_ln_mulmod(a.w2, r.e.w2), l.e.bytes + r.e.bytes, a.len + r.e.len},
+                    f};
+}
+TK_HD TkLnNSeg tk_lnn_seg_join(const TkLn& p, const TkLnNSeg& l, const TkLnNSeg& r) { return (r.cut & TK_LN_NF_CUT) ? r : tk_lnn_join(p, l, r); }
+
+// 8 bytes: 0x80 where lo <= byte <= hi, for 1 <= lo <= hi < 0x80 (SWAR: the sums stay below 0x100, no carry crosses a byte)
+TK_HD uint64_t tk_ln_in_range(uint64_t w, uint8_t lo, uint8_t hi) {
+    const uint64_t ones = 0x0101010101010101ull, x = w & (0x7Full * ones);
+    return (x + (0x80u - lo) * ones) & ~(x + (0x7Fu - hi) * ones) & ~w & (0x80ull * ones);
+}
+TK_HD uint32_t tk_ln_gather(uint64_t z) { return (uint32_t)((z * 0x0002040810204081ull) >> 56); }  // the eight 0x80 flags of z as bits 0 .. 7
+// A lane's 16 bytes under the mask `norm`: the bytes with case and digits mapped; bit j of del: byte j is deleted; of ws: it is white space
+struct TkLnNLane {
+    uint64_t lo, hi;
+    uint32_t del, ws;
+    TK_HD uint32_t byte(uint32_t j) const { return (uint32_t)((j < 8 ? lo >> (8 * j) : hi >> (8 * (j - 8))) & 0xFFu); }
+};
+TK_HD uint64_t tk_lnn_word(uint64_t x, uint32_t norm, uint32_t shift, uint32_t& del, uint32_t& ws) {
+    const uint64_t upper = tk_ln_in_range(x, 'A', 'Z'), digit = tk_ln_in_range(x, '0', '9');
+    const uint64_t space = tk_ln_in_range(x, 0x0B, 0x0D) | tk_ln_in_range(x, 0x09, 0x09) | tk_ln_in_range(x, 0x20, 0x20);
+    const uint64_t punct = tk_ln_in_range(x, 0x21, 0x2F) | tk_ln_in_range(x, 0x3A, 0x40) | tk_ln_in_range(x, 0x5B, 0x60) | tk_ln_in_range(x, 0x7B, 0x7E);
+    if (norm & TK_LN_N_SPACE) ws |= tk_ln_gather(space) << shift;
+    if (norm & TK_LN_N_PUNCT) del |= tk_ln_gather(punct) << shift;
+    if (norm & TK_LN_N_CASE) x |= upper >> 2;                   // + 0x20
+    if (norm & TK_LN_N_DIGITS) x &= ~((digit >> 7) * 0x0Full);  // the low nibble to 0
+    return x;
+}
+TK_HD TkLnNLane tk_lnn_lane(uint64_t lo, uint64_t hi, uint32_t norm) {
+    TkLnNLane c{0, 0, 0u, 0u};
+    c.lo = tk_lnn_word(lo, norm, 0u, c.del, c.ws), c.hi = tk_lnn_word(hi, norm, 8u, c.del, c.ws);
+    return c;
+}
+// one byte that is not deleted behind a run whose powers and raw count nobody needs here; ws: it is white space
+TK_HD void tk_lnn_push(const TkLn& p, TkLnNSeg& s, uint32_t byte, bool ws) {
+    if (ws) {
+        s.cut |= s.e.len ? TK_LN_NF_TRAIL : TK_LN_NF_WS;
+        return;
+    }
+    if (s.cut & TK_LN_NF_TRAIL) {
+        s.e.h1 = tk_ln_addmod(tk_ln_mulmod(s.e.h1, p.B1), 0x21), s.e.h2 = tk_ln_addmod(tk_ln_mulmod(s.e.h2, p.B2), 0x21);
+        s.e.len += 1, s.cut &= ~TK_LN_NF_TRAIL;
+    } else if (s.cut & TK_LN_NF_WS) {
+        s.cut ^= TK_LN_NF_WS | TK_LN_NF_LEAD;
+    }
+    s.e.h1 = tk_ln_addmod(tk_ln_mulmod(s.e.h1, p.B1), byte + 1), s.e.h2 = tk_ln_addmod(tk_ln_mulmod(s.e.h2, p.B2), byte + 1);
+    s.e.len += 1;
+}
+// the bytes [from, to) of a lane behind a run, the raw count with them: only the bytes that reach the body cost a multiply
+TK_HD void tk_lnn_append(const TkLn& p, const TkLnNLane& c, uint32_t from, uint32_t to, TkLnNSeg& s) {
+    s.e.bytes += to - from;
+    for (uint32_t m = ~c.del & ((1u << to) - (1u << from)); m; m &= m - 1u) {
+        const uint32_t j = (uint32_t)__builtin_ctz(m);
+        tk_lnn_push(p, s, c.byte(j), (c.ws >> j) & 1u);
+    }
 }
