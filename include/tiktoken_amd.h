@@ -737,6 +737,67 @@ int tk_line_clean_device(tk_core* core, const void* d_text, uint64_t n_bytes, co
 int tk_line_clean(tk_core* core, const uint8_t* text, const uint64_t* doc_off, uint64_t n_docs, const tk_clean_spec* spec, uint8_t** text_out, uint64_t* n_bytes_out,
                   uint64_t* doc_off_out, uint64_t* n_lines_out, uint64_t* n_kept_out, uint64_t* n_short_out, uint64_t* n_long_out, uint64_t* n_no_end_out,
                   uint64_t* n_ellipsis_out, uint64_t* n_phrase_out, uint64_t* doc_hit_out, uint64_t* counts_out);
+/* Masking personal data: packed TEXT rewritten with every e-mail address and every IPv4 address replaced by a fixed placeholder -- the
+ * last text stage of C4-, CCNet-, Gopher- and FineWeb-style builds before the text is encoded (DataTrove's PIIFormatter).  Replaces
+ * nothing in the reference: it is the host step of the reference's users, re.sub per document.  The output is packed text again.
+ * The rule.  Input: text uint8[N], doc_off uint64[n_docs + 1] ascending from 0 to N, N <= 0xFFFF0000.  Per document, nothing crosses a
+ *  document edge, and bytes are bytes.  The result is what this Python gives for the document's bytes -- the expression IS the rule:
+ *    L     = rb"A-Za-z0-9._%+\-"
+ *    EMAIL = rb"(?<![" + L + rb"@])[" + L + rb"]{1,64}@(?=[A-Za-z0-9.\-]{1,253}(?![A-Za-z0-9.\-]))(?:[A-Za-z0-9\-]+\.)+[A-Za-z]{2,}(?![A-Za-z0-9_\-])"
+ *    OCT   = rb"(?:25[0-5]|2[0-4][0-9]|1[0-9][0-9]|[1-9]?[0-9])"
+ *    IP    = rb"(?<![A-Za-z0-9_.])" + OCT + rb"(?:\." + OCT + rb"){3}(?![A-Za-z0-9_])(?!\.[0-9])"
+ *    re.sub(rb"(" + EMAIL + rb")|(" + IP + rb")", repl, doc)
+ *  repl puts the e-mail placeholder for group 1 and the IP placeholder for group 2; with public_ip_only an address a.b.c.d that is not
+ *  public stays as it is: a is 0, 10, 127 or >= 224; a is 100 and 64 <= b <= 127; a is 169 and b is 254; a is 172 and 16 <= b <= 31; a
+ *  is 192 and b is 168.
+ *  What follows from the expression, and how the kernels decide (tk_pii_rule.h):
+ *   An e-mail match starts only at the first byte of a maximal run of L bytes that is at most 64 long, is not preceded by '@' and ends
+ *   at an '@'.  D being the maximal run of [A-Za-z0-9.-] behind the '@': no match when D is longer than 253 bytes; D split at dots, m
+ *   the number of non-empty labels before the first empty one, the match ends behind label j, the largest j with 2 <= j <= m whose
+ *   label is letters only and at least two bytes long -- where that label ends D, the byte behind D must not be '_'.  A decision reads
+ *   at most 66 bytes before the '@' and 255 behind it.
+ *   An IP match starts only at a digit whose previous byte is not of [A-Za-z0-9_.], and is decided by at most 17 bytes ahead.
+ *   Matches of one kind never overlap, so no decision depends on an earlier one.  An IP candidate counts unless its first byte lies
+ *   inside an e-mail match ("1.2.3.4@example.com", "a-1.2.3.4@x.com" and "a@b-1.2.3.4.com" are one e-mail each); no e-mail starts inside
+ *   an IP match.
+ *   "a@b.com." matches up to "com"; "a@b.com1", "a@b..com", "v1.2.3.4", "01.2.3.4", "1.2.3.256" and "1.2.3.4.5" do not match;
+ *   "10.0.0.1." matches without the dot; "a@bb.cc@dd.ee" holds one match.
+ *  Placeholders: 0 .. 32 bytes each, well-formed UTF-8, no '\n'.  Matches are ASCII, so well-formed text stays well-formed.
+ *  Outputs.  text_out: the documents with their matches replaced, in order; doc_off_out uint64[n_docs + 1]: the output position of every
+ *   doc_off[i]; n_email, n_ip uint64[n_docs]: the e-mails and the addresses replaced in the document (an address that stays is not
+ *   counted); counts uint64[4] = (bytes needed, e-mails, addresses, overflow).  Every value is a function of (text, doc_off, spec)
+ *   alone, never of the schedule: the sums are integer sums.
+ *  Refused with TK_VALUE_ERROR before anything is read or written: N above 0xFFFF0000; a placeholder outside the rule; text_out == text;
+ *  text_out without doc_off_out; in the host entry a doc_off that does not ascend from 0.
+ * A workgroup takes tk_stat("pii_tile") bytes with tk_stat("pii_halo") bytes before and behind them, a lane tk_stat("pii_lane"); a
+ * decision is made by every tile whose window holds its look-around, from the text alone, so no pass carries anything between tiles.
+ * The core owns the scratch: 8 bytes per tile.
+ * NOT built: IPv6, phone numbers, IBANs, quoted or bracketed e-mail forms, a choice among several placeholders, match positions as
+ * output, several GPUs. */
+typedef struct tk_pii_spec {
+    const uint8_t* email; /* the e-mail placeholder, n_email bytes */
+    uint64_t n_email;
+    const uint8_t* ip; /* the IP placeholder, n_ip bytes */
+    uint64_t n_ip;
+    uint32_t public_ip_only; /* not 0: an address that is not public stays */
+} tk_pii_spec;
+/* Device pointers in (d_text uint8[n_bytes] at any alignment -- 16-byte aligned is the fast path --, d_doc_off uint64[n_docs + 1]); the
+ * spec is host memory and is read before the call returns; the caller's device arrays out, any of which may be null (d_doc_off_out not
+ * with d_text_out): d_text_out uint8[cap_out] (at any alignment; only the first counts[0] bytes are written), d_doc_off_out
+ * uint64[n_docs + 1], d_n_email and d_n_ip uint64[n_docs], d_counts_out uint64[4].  Without d_text_out the call only counts: no write
+ * pass, d_doc_off_out is left alone, counts[3] is 0.  Where the bytes needed exceed cap_out the write pass reads the total on the device
+ * and stores NO byte to d_text_out; counts[3] is 1 and everything else is written, d_doc_off_out included -- call again with counts[0]
+ * bytes.  Everything is queued on `stream`, null being HIP's null stream, and the host waits for NOTHING.  A d_doc_off that does not
+ * ascend from 0 to n_bytes gives values nobody has defined and never an access outside the arrays: an entry of doc_off is only ever an
+ * index i <= n_docs found by binary search or a window position checked against the window, and what is stored to d_text_out lies below
+ * the total the write pass has compared with cap_out. */
+int tk_pii_mask_device(tk_core* core, const void* d_text, uint64_t n_bytes, const void* d_doc_off, uint64_t n_docs, const tk_pii_spec* spec, void* stream, void* d_text_out,
+                       uint64_t cap_out, uint64_t* d_doc_off_out, uint64_t* d_n_email, uint64_t* d_n_ip, uint64_t* d_counts_out);
+/* The same from host arrays (n_bytes is doc_off[n_docs]): the count passes, ONE wait for the total, a device buffer of exactly that
+ * size, the write pass, the copies out.  *text_out is library-owned (tk_free), *n_bytes_out bytes; doc_off_out (n_docs + 1), n_email_out
+ * and n_ip_out (n_docs) are the caller's and may be null; text_out null: the call only counts. */
+int tk_pii_mask(tk_core* core, const uint8_t* text, const uint64_t* doc_off, uint64_t n_docs, const tk_pii_spec* spec, uint8_t** text_out, uint64_t* n_bytes_out,
+                uint64_t* doc_off_out, uint64_t* n_email_out, uint64_t* n_ip_out);
 /* Line sets: a set of line keys that lives on the device across calls, and packed TEXT rewritten without the lines the set has seen
  * -- navigation bars, cookie banners, licence footers: the line filter of CCNet, C4 and RefinedWeb-style builds, which drops every line
  * that occurred anywhere earlier in the corpus.  Replaces nothing in the reference: it is the host step of the reference's users, a loop

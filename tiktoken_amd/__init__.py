@@ -8,7 +8,7 @@ methods handing whole batches to the GPU; `get_encoding` / `list_encoding_names`
 __version__ = "0.1.0"
 
 from ._tiktoken import NORM_ALL, NORM_CASE, NORM_DIGITS, NORM_PUNCT, NORM_SPACE  # noqa: F401
-from ._tiktoken import GOPHER_STOP_WORDS, CoreBPE, DedupedBatch, DisallowedSpecialError, Fingerprints, JsonlError, JsonlText, JsonlTokens, LineClean, LineDedup, LineStats, NgramOverlap, RepetitionStats, Role, SampleBatch, SampleRows, SampleRowsDevice, StoppedRows, StreamPacked, StreamStep, TextChunks, WordStats  # noqa: F401
+from ._tiktoken import GOPHER_STOP_WORDS, CoreBPE, DedupedBatch, DisallowedSpecialError, Fingerprints, JsonlError, JsonlText, JsonlTokens, LineClean, LineDedup, LineStats, NgramOverlap, PiiMasked, RepetitionStats, Role, SampleBatch, SampleRows, SampleRowsDevice, StoppedRows, StreamPacked, StreamStep, TextChunks, WordStats  # noqa: F401
 from .core import DecodeStream  # noqa: F401
 from .core import Encoding  # noqa: F401
 from .core import LineSet  # noqa: F401

@@ -101,6 +101,11 @@ class CleanSpec(ctypes.Structure):
 CLEAN_ELLIPSIS = 1  # TK_CLEAN_ELLIPSIS
 
 
+class PiiSpec(ctypes.Structure):
+    """tk_pii_spec: the two placeholders of a masking call and whether addresses that are not public stay (include/tiktoken_amd.h)."""
+    _fields_ = [("email", ctypes.c_void_p), ("n_email", ctypes.c_uint64), ("ip", ctypes.c_void_p), ("n_ip", ctypes.c_uint64), ("public_ip_only", ctypes.c_uint32)]
+
+
 class Stops(ctypes.Structure):  # tk_stops
     _fields_ = [("n", ctypes.c_uint32), ("blob", ctypes.c_void_p), ("off", ctypes.c_void_p)]
 
@@ -236,6 +241,11 @@ def lib() -> ctypes.CDLL:
             L.tk_line_clean_device.argtypes = [vp, vp, u64, vp, u64, P(CleanSpec), vp, vp, vp, *[vp] * 8, vp]
             L.tk_line_clean.restype = i32
             L.tk_line_clean.argtypes = [vp, vp, vp, u64, P(CleanSpec), P(vp), P(u64), vp, *[vp] * 8, vp]
+        if hasattr(L, "tk_pii_mask_device"):
+            L.tk_pii_mask_device.restype = i32
+            L.tk_pii_mask_device.argtypes = [vp, vp, u64, vp, u64, P(PiiSpec), vp, vp, u64, vp, vp, vp, vp]
+            L.tk_pii_mask.restype = i32
+            L.tk_pii_mask.argtypes = [vp, vp, vp, u64, P(PiiSpec), P(vp), P(u64), vp, vp, vp]
         if hasattr(L, "tk_line_set_create"):  # (absent from older builds selected through $TIKTOKEN_AMD_LIB)
             L.tk_line_set_create.restype = i32
             L.tk_line_set_create.argtypes = [vp, u64, u64, u64, P(vp)]

@@ -971,6 +971,24 @@ class LineClean(NamedTuple):
         return [bytes(view[a:b]) for a, b in zip(bounds[:-1], bounds[1:])]
 
 
+PII_EMAIL, PII_IP = "email@example.com", "22.214.171.124"  # the placeholders DataTrove's PIIFormatter puts
+
+
+class PiiMasked(NamedTuple):
+    """Packed text with its e-mail addresses and IPv4 addresses replaced by placeholders (tk_pii_mask; the rule: include/tiktoken_amd.h):
+    `text` uint8[bytes] and `doc_off` uint64[n + 1], what every packed encode entry takes, and uint64[n] per document: `n_email` and
+    `n_ip`, the e-mails and the addresses that were replaced."""
+    text: np.ndarray
+    doc_off: np.ndarray
+    n_email: np.ndarray
+    n_ip: np.ndarray
+
+    def texts(self) -> "list[bytes]":
+        """the masked documents as bytes, every one in its place"""
+        view, bounds = memoryview(self.text), self.doc_off.tolist()
+        return [bytes(view[a:b]) for a, b in zip(bounds[:-1], bounds[1:])]
+
+
 # the bits of a line set's `normalize` mask (TK_NORM_*): what is done to a line's bytes before they are hashed
 NORM_CASE, NORM_DIGITS, NORM_SPACE, NORM_PUNCT, NORM_ALL = 1, 2, 4, 8, 15
 
@@ -2372,6 +2390,64 @@ class CoreBPE:
         _lib.raise_for(self._L.tk_line_clean(self._h, text.ctypes.data if len(text) else None, doc_off.ctypes.data, n, ctypes.byref(spec), ctypes.byref(out),
                                              ctypes.byref(n_out), off_out.ctypes.data, *[a.ctypes.data for a in per_doc], None))
         return LineClean(_take_u8(out, int(n_out.value)), off_out, *per_doc)
+
+    # ------------------------------------------------------------------ masking (no reference counterpart: re.sub per document on the host)
+    @staticmethod
+    def _pii_spec(email, ip, public_ip_only):
+        """(what keeps the arrays alive, the tk_pii_spec) of the placeholders as Python gives them: str or bytes each"""
+        keep = [np.frombuffer((p.encode() if isinstance(p, str) else bytes(p)) + b"\0", dtype=np.uint8) for p in (email, ip)]
+        return keep, _lib.PiiSpec(email=keep[0].ctypes.data, n_email=len(keep[0]) - 1, ip=keep[1].ctypes.data, n_ip=len(keep[1]) - 1, public_ip_only=1 if public_ip_only else 0)
+
+    def pii_mask_device(self, text, doc_off, *, email=PII_EMAIL, ip=PII_IP, public_ip_only: bool = True, text_out=None, doc_off_out=None, n_email=None, n_ip=None,
+                        counts=None, stream: int | None = None) -> None:
+        """Packed text that is on the device with its e-mail addresses and its IPv4 addresses replaced by `email` and `ip`
+        (tk_pii_mask_device): torch tensors on this core's GPU, taken by pointer -- `text` (8-bit, N) and `doc_off` (64-bit, n + 1,
+        ascending from 0 to N; not checked) in; the caller's tensors out, any of which may be None: `text_out` (8-bit, of any size: its
+        first counts[0] bytes are written, none when it is too small) with `doc_off_out` (64-bit, n + 1), `n_email` and `n_ip` (64-bit,
+        n) and `counts` (64-bit, 4: bytes needed, e-mails, addresses, 1 when `text_out` was too small).  Without `text_out` the call only
+        counts.  With `public_ip_only` an address that is not public stays.  Queued on `stream` as in `fingerprint_device`; the host
+        waits for nothing."""
+        self._one_device("pii_mask_device")
+        n, N = doc_off.numel() - 1, text.numel()
+        if n < 0:
+            raise ValueError("doc_off must hold n_docs + 1 entries")
+        cap = text_out.numel() if text_out is not None else 0
+        stream = self._on_gpu((("text", text, 1, N), ("doc_off", doc_off, 8, n + 1), ("text_out", text_out, 1, cap), ("doc_off_out", doc_off_out, 8, n + 1),
+                               ("n_email", n_email, 8, n), ("n_ip", n_ip, 8, n), ("counts", counts, 8, 4)), stream)
+        ptr = [t.data_ptr() if t is not None and t.numel() else None for t in (doc_off_out, n_email, n_ip, counts)]
+        _keep, spec = self._pii_spec(email, ip, public_ip_only)
+        _lib.raise_for(self._L.tk_pii_mask_device(self._h, text.data_ptr() if N else None, N, doc_off.data_ptr(), n, ctypes.byref(spec), stream or None,
+                                                  text_out.data_ptr() if text_out is not None else None, cap, *ptr))
+
+    def mask_pii_packed(self, text, doc_off=None, *, email=PII_EMAIL, ip=PII_IP, public_ip_only: bool = True) -> PiiMasked:
+        """Packed text with its e-mail addresses and IPv4 addresses replaced, as a `PiiMasked`: `text` bytes, bytearray, memoryview or
+        uint8[N] (no copy) with `doc_off` uint64[n + 1] (tk_pii_mask); a `JsonlText`, `LineClean` or `LineDedup` (then `doc_off` is its
+        own); or a uint8 torch tensor on this core's GPU with `doc_off` a 64-bit tensor there (tk_pii_mask_device, by pointer: a counting
+        call sizes `text_out`; the results come back to the host)."""
+        self._one_device("mask_pii_packed")
+        if doc_off is None and hasattr(text, "doc_off"):
+            text, doc_off = text.text, text.doc_off
+        if hasattr(text, "data_ptr"):
+            import torch
+
+            if not hasattr(doc_off, "data_ptr"):
+                doc_off = torch.from_numpy(np.ascontiguousarray(doc_off, dtype=np.uint64).view(np.int64)).to(text.device)
+            n = max(doc_off.numel() - 1, 0)
+            new = lambda count, dtype=torch.int64: torch.zeros(count, dtype=dtype, device=text.device)  # noqa: E731
+            out = dict(doc_off_out=new(n + 1), n_email=new(n), n_ip=new(n), counts=new(4))
+            self.pii_mask_device(text, doc_off, email=email, ip=ip, public_ip_only=public_ip_only, counts=out["counts"])
+            out["text_out"] = new(int(out["counts"][0].item()), torch.uint8)
+            self.pii_mask_device(text, doc_off, email=email, ip=ip, public_ip_only=public_ip_only, **out)
+            return PiiMasked(*[out[k].cpu().numpy().view(np.uint8 if k == "text_out" else np.uint64) for k in ("text_out", "doc_off_out", "n_email", "n_ip")])
+        text, doc_off = self._packed_text(text, doc_off)
+        n = len(doc_off) - 1
+        off_out = np.zeros(n + 1, dtype=np.uint64)
+        n_email, n_ip = (np.zeros(n + 1, dtype=np.uint64)[:n] for _ in range(2))  # (one spare element each: no empty array's pointer)
+        out, n_out = ctypes.c_void_p(), ctypes.c_uint64()
+        _keep, spec = self._pii_spec(email, ip, public_ip_only)
+        _lib.raise_for(self._L.tk_pii_mask(self._h, text.ctypes.data if len(text) else None, doc_off.ctypes.data, n, ctypes.byref(spec), ctypes.byref(out), ctypes.byref(n_out),
+                                           off_out.ctypes.data, n_email.ctypes.data, n_ip.ctypes.data))
+        return PiiMasked(_take_u8(out, int(n_out.value)), off_out, n_email, n_ip)
 
     # ------------------------------------------------------------------ line sets (no reference counterpart: a loop over lines against a set on the host)
     def line_set_create(self, capacity: int, seed: int = 0, min_bytes: int = 1, normalize: int = 0) -> NativeLineSet:

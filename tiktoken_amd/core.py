@@ -542,6 +542,27 @@ class Encoding:
         host = {k: v.cpu().numpy().view(np.uint8 if k == "text_out" else np.uint64) for k, v in out.items()}
         return _tiktoken.LineClean(host["text_out"][:int(host["counts"][0])], host["doc_off_out"], *[host[m] for m in _tiktoken.CoreBPE.CLEAN_OUTS])
 
+    # ------------------------------------------------------------------ masking
+    def mask_pii_batch(self, texts: "Sequence[str] | Sequence[bytes]", email=_tiktoken.PII_EMAIL, ip=_tiktoken.PII_IP, public_ip_only: bool = True) -> "list[str] | list[bytes]":
+        """Every text of a batch with its e-mail addresses replaced by `email` and its IPv4 addresses by `ip`, on the GPU from the text
+        itself: a list of the same length and type, every document in its place.  An e-mail is up to 64 bytes of [A-Za-z0-9._%+-], an
+        '@' and dotted labels that end in letters; an address is four numbers up to 255 that no word byte or further number touches, and
+        with `public_ip_only` one of a private, loopback, link-local, shared or multicast range stays.  Placeholders are at most 32 bytes
+        without a newline.  `mask_pii_packed` also gives the counts.  The rule is stated in include/tiktoken_amd.h."""
+        if len(texts) and isinstance(texts[0], (bytes, bytearray, memoryview)):
+            off = np.zeros(len(texts) + 1, dtype=np.uint64)
+            np.cumsum([len(t) for t in texts], out=off[1:])
+            return self._core_bpe.mask_pii_packed(b"".join(texts), off, email=email, ip=ip, public_ip_only=public_ip_only).texts()
+        blob, off = self._pack(texts)
+        return [d.decode("utf-8", errors="replace") for d in self._core_bpe.mask_pii_packed(blob, off, email=email, ip=ip, public_ip_only=public_ip_only).texts()]
+
+    def mask_pii_packed(self, text, doc_off=None, **spec) -> "_tiktoken.PiiMasked":
+        """The masking of text that is packed already, as a `PiiMasked`, whose (text, doc_off) every packed encode entry takes:
+        everything `clean_lines_packed` takes -- host buffers (no copy) with `doc_off` uint64[n + 1], a `JsonlText`, a `LineClean` or a
+        `LineDedup`, or a uint8 torch tensor on the encoding's GPU with `doc_off` a 64-bit tensor there.  `spec`: `email`, `ip` and
+        `public_ip_only` as in `mask_pii_batch`."""
+        return self._core_bpe.mask_pii_packed(text, doc_off, **spec)
+
     # ------------------------------------------------------------------ line sets
     def line_set(self, capacity: int, seed: int = 0, min_bytes: int = 1, normalize: int = 0) -> "LineSet":
         """An empty set of lines that lives on the GPU across calls (tk_line_set_create), and with it the line filter of CCNet-, C4- and

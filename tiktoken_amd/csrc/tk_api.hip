@@ -38,6 +38,7 @@
 #include "tk_line_set.h"
 #include "tk_words.h"
 #include "tk_clean.h"
+#include "tk_pii.h"
 #include "tk_jsonl.h"
 #include "tk_sample_rows.h"
 #include "tk_samples.h"
@@ -334,6 +335,10 @@ struct tk_core {
     // host entry.  cl_done: as fp_done, for all three.
     Buf d_cl_work, d_cl_in, d_cl_out;
     Event cl_done;
+    // Masking (tk_pii.h), apart from everything above: d_pii_work: the report words and the tiles' bytes; d_pii_in, d_pii_out: text and
+    // doc_off, and everything that comes back, of the host entry.  pii_done: as fp_done, for all three.
+    Buf d_pii_work, d_pii_in, d_pii_out;
+    Event pii_done;
     uint64_t st_split[TK_SPLIT_STATS] = {0, 0, 0, 0};
     // Supervised samples (tk_samples.h), apart from everything above: d_smp: ids, labels and mask of every position; d_smp_row: full_len, len,
     // n_trained of every sample; d_smp_cnt: the TK_SMP_WORDS report words, the role table, pstart and the per-sample figures a call counts in
@@ -4444,6 +4449,122 @@ extern "C" int tk_line_clean(tk_core* c, const uint8_t* text, const uint64_t* do
 }
 
 // ------------------------------------------------------------------------------------------
+// Masking (tk_pii.h): packed text on the device -> packed text with every e-mail address and every IPv4 address replaced by a
+// placeholder, and per document how many of each.
+// ------------------------------------------------------------------------------------------
+struct PiiOuts {  // the caller's device arrays; any may be null (text and doc_off: the call only counts)
+    uint8_t* text;
+    uint64_t cap;
+    uint64_t *doc_off, *n_email, *n_ip, *counts;
+};
+// The arguments every entry refuses before anything is queued
+static int pii_shape(uint64_t n, uint64_t n_docs, const tk_pii_spec* sp, TkPii* p) {
+    if (!sp || (sp->n_email && !sp->email) || (sp->n_ip && !sp->ip)) return fail(TK_VALUE_ERROR, "null argument");
+    switch (tk_pii_shape(n, n_docs, sp->email, sp->n_email, sp->ip, sp->n_ip, sp->public_ip_only, p)) {
+        case 0: break;
+        case 1: return fail(TK_VALUE_ERROR, "n_bytes: the text of a masking call is at most 0xFFFF0000 bytes (positions are 32-bit)");
+        case 2: return fail(TK_VALUE_ERROR, "placeholder: at most 32 bytes");
+        case 3: return fail(TK_VALUE_ERROR, "placeholder: a placeholder holds no newline");
+        default: return fail(TK_VALUE_ERROR, "placeholder: the bytes are well-formed UTF-8");
+    }
+    if (n_docs > 0xFFFFFFFEull) return fail(TK_VALUE_ERROR, "n_docs: at most 2^32 - 2 documents");
+    return TK_OK;
+}
+// pii_count, pii_write: the caller holds c->mu.  They launch on s and wait for nothing; pii_write takes the tiles' bases pii_count
+// has left in c->d_pii_work, behind it on the same stream.
+static int pii_count(tk_core* c, hipStream_t s, const TkPii& q, const uint8_t* d_text, const uint64_t* d_doc_off, const PiiOuts& o) {
+    if (q.n_bytes && o.text == d_text) return fail(TK_VALUE_ERROR, "d_text_out must not be d_text: a tile's bytes are written while later tiles are still read");
+    if (o.text && !o.doc_off) return fail(TK_VALUE_ERROR, "null argument");
+    if (!c->pii_done.e) HIPCHK(c->pii_done.create());
+    HIPCHK(hipStreamWaitEvent(s, c->pii_done, 0));  // (the scratch and the host entry's buffers are the core's)
+    TRY(ensure(c->d_pii_work, 32 + (uint64_t)q.n_tiles * 8 + 16));
+    unsigned long long* words = carved<unsigned long long>(c->d_pii_work, 0);
+    unsigned long long* tiles = carved<unsigned long long>(c->d_pii_work, 32);
+    const bool aligned = ((uintptr_t)d_text & 15u) == 0;
+    unsigned long long *ne = (unsigned long long*)o.n_email, *ni = (unsigned long long*)o.n_ip;
+    TRY(timed(c, s, "tk_k_pii_clear", [&] { hipLaunchKernelGGL(tk_k_pii_clear, dim3(grid_for(q.n_docs ? q.n_docs : 1, 256, 65536)), dim3(256), 0, s, words, ne, ni, q.n_docs); }));
+    TRY(timed(c, s, "tk_k_pii_find", [&] { hipLaunchKernelGGL(tk_k_pii_find, dim3(q.n_tiles), dim3(TK_PII_THREADS), 0, s, q, d_text, d_doc_off, aligned, tiles, words, ne, ni); }));
+    TRY(timed(c, s, "tk_k_pii_scan", [&] {
+        hipLaunchKernelGGL(tk_k_pii_scan, dim3(1), dim3(1024), 0, s, tiles, (uint64_t)q.n_tiles, words, o.text ? (unsigned long long)o.cap : ~0ull, (unsigned long long*)o.counts);
+    }));
+    HIPCHK(hipEventRecord(c->pii_done, s));
+    return TK_OK;
+}
+static int pii_write(tk_core* c, hipStream_t s, const TkPii& q, const uint8_t* d_text, const uint64_t* d_doc_off, const PiiOuts& o) {
+    if (!o.text && (q.n_bytes || !o.doc_off)) return TK_OK;  // the call only counts
+    const unsigned long long* words = carved<unsigned long long>(c->d_pii_work, 0);
+    const unsigned long long* tiles = carved<unsigned long long>(c->d_pii_work, 32);
+    const bool aligned = ((uintptr_t)d_text & 15u) == 0;
+    TRY(timed(c, s, "tk_k_pii_write", [&] {
+        hipLaunchKernelGGL(tk_k_pii_write, dim3(q.n_tiles), dim3(TK_PII_THREADS), 0, s, q, d_text, d_doc_off, aligned, tiles, words, o.text ? (unsigned long long)o.cap : ~0ull, o.text,
+                           (unsigned long long*)o.doc_off);
+    }));
+    HIPCHK(hipEventRecord(c->pii_done, s));
+    return TK_OK;
+}
+
+extern "C" int tk_pii_mask_device(tk_core* c, const void* d_text, uint64_t n_bytes, const void* d_doc_off, uint64_t n_docs, const tk_pii_spec* spec, void* stream, void* d_text_out,
+                                  uint64_t cap_out, uint64_t* d_doc_off_out, uint64_t* d_n_email, uint64_t* d_n_ip, uint64_t* d_counts_out) {
+    // (the stream as given, null being HIP's null stream: tk_fingerprint_device's convention)
+    return device_pass(c, d_doc_off && (d_text || !n_bytes), stream, [&](hipStream_t) {
+        TkPii q;
+        TRY(pii_shape(n_bytes, n_docs, spec, &q));
+        const PiiOuts o{(uint8_t*)d_text_out, cap_out, d_doc_off_out, d_n_email, d_n_ip, d_counts_out};
+        TRY(pii_count(c, (hipStream_t)stream, q, (const uint8_t*)d_text, (const uint64_t*)d_doc_off, o));
+        return pii_write(c, (hipStream_t)stream, q, (const uint8_t*)d_text, (const uint64_t*)d_doc_off, o);
+    });
+}
+
+extern "C" int tk_pii_mask(tk_core* c, const uint8_t* text, const uint64_t* doc_off, uint64_t n_docs, const tk_pii_spec* spec, uint8_t** text_out, uint64_t* n_bytes_out,
+                           uint64_t* doc_off_out, uint64_t* n_email_out, uint64_t* n_ip_out) {
+    if (!c) return fail(TK_VALUE_ERROR, "core is null");
+    if (!doc_off || (text_out && (!n_bytes_out || !doc_off_out))) return fail(TK_VALUE_ERROR, "null argument");
+    TRY(check_offsets(doc_off, n_docs, "doc_off"));
+    const uint64_t n = doc_off[n_docs];
+    if (n && !text) return fail(TK_VALUE_ERROR, "null argument");
+    TkPii q;
+    TRY(pii_shape(n, n_docs, spec, &q));
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->pii_done.e) HIPCHK(c->pii_done.create());
+    Carve in, res;
+    const uint64_t at_off = in.add((n_docs + 1) * 8), at_text = in.add(n + 16);
+    const uint64_t at_counts = res.add(32), at_off_out = res.add((n_docs + 1) * 8), at_ne = res.add(n_docs * 8), at_ni = res.add(n_docs * 8);
+    TRY(ensure(c->d_pii_in, in.total + 16));
+    uint64_t* d_off = carved<uint64_t>(c->d_pii_in, at_off);
+    uint8_t* d_text = carved<uint8_t>(c->d_pii_in, at_text);
+    HIPCHK(hipStreamWaitEvent(c->stream, c->pii_done, 0));  // (d_pii_in and d_pii_out may still be in use by a call on another stream)
+    TRY(ensure(c->d_pii_out, res.total + 16));
+    HIPCHK(hipMemcpyAsync(d_off, doc_off, (n_docs + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    if (n) HIPCHK(hipMemcpyAsync(d_text, text, n, hipMemcpyHostToDevice, c->stream));
+    return drained(c, [&]() -> int {
+        // the count passes; the one wait, for the total; then text_out is exactly as large as it has to be (behind the other results)
+        PiiOuts d{nullptr, 0, nullptr, n_email_out ? carved<uint64_t>(c->d_pii_out, at_ne) : nullptr, n_ip_out ? carved<uint64_t>(c->d_pii_out, at_ni) : nullptr,
+                  carved<uint64_t>(c->d_pii_out, at_counts)};
+        TRY(pii_count(c, c->stream, q, d_text, d_off, d));
+        uint64_t counts[4];
+        HIPCHK(hipMemcpyAsync(counts, d.counts, 32, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipGetLastError());
+        if (n_email_out && n_docs) HIPCHK(hipMemcpy(n_email_out, d.n_email, n_docs * 8, hipMemcpyDeviceToHost));
+        if (n_ip_out && n_docs) HIPCHK(hipMemcpy(n_ip_out, d.n_ip, n_docs * 8, hipMemcpyDeviceToHost));
+        if (!text_out) return TK_OK;
+        Buf d_out;  // (of this call alone: its size is the call's result)
+        TRY(ensure(d_out, counts[0] + 16));
+        d.text = d_out.as<uint8_t>(), d.cap = counts[0], d.doc_off = carved<uint64_t>(c->d_pii_out, at_off_out), d.counts = nullptr;
+        TRY(pii_write(c, c->stream, q, d_text, d_off, d));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipGetLastError());
+        ResultBag bag;
+        TRY(bag.fetch(text_out, d.text, counts[0]));
+        HIPCHK(hipMemcpy(doc_off_out, d.doc_off, (n_docs + 1) * 8, hipMemcpyDeviceToHost));
+        bag.give();
+        *n_bytes_out = counts[0];
+        return TK_OK;
+    });
+}
+
+// ------------------------------------------------------------------------------------------
 // Line sets (tk_line_set.h): a set of line keys on the device, and packed text rewritten without the lines the set has seen.  Like a
 // tk_ngram_set the set owns what outlives a batch -- the table, the counter -- and what its calls work in: the tiles' scratch, the bitmap,
 // the buffers of the host entries, and the event that orders its calls among themselves on the device.
@@ -6577,6 +6698,10 @@ extern "C" uint64_t tk_stat(tk_core* c, const char* name) {
     if (k == "clean_lane") return TK_CL_LANE;  // ... of a lane
     if (k == "clean_wave") return TK_CL_WAVE;  // ... of a wavefront
     if (k == "clean_docs") return TK_CL_DOCS;  // documents of a tile whose sums are gathered in LDS
+    if (k == "pii_tile") return TK_PII_TILE;  // bytes of a tile of the masking pass (tk_pii_rule.h)
+    if (k == "pii_lane") return TK_PII_LANE;  // ... of a lane
+    if (k == "pii_wave") return TK_PII_WAVE;  // ... of a wavefront
+    if (k == "pii_halo") return TK_PII_HALO;  // ... staged before and behind a tile
     if (k == "ngram_tile") return TK_NG_TILE;  // token positions of a tile of the n-gram passes (tk_ngram_rule.h)
     if (k == "select_tile") return TK_SEL_TILE;  // output positions of a tile of the selection's copy (tk_groups_rule.h)
     if (k == "jsonl_tile") return TK_JSONL_TILE;  // bytes of a tile of the JSON Lines passes (tk_jsonl_rule.h)
